@@ -1,11 +1,17 @@
 #!/usr/bin/env python
 """bench.py -- FASTQ buffer-scan hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path (line index -> record chain -> int64[n][6]
 offset table, optionally Phred decode) over one batch of synthetic FASTQ that is
 already resident in HBM.  Prints ONE JSON line (rank 0).
+
+A plain run does only what the headline figure needs: set-up, warm-up, K timed steps, the outputs of the
+last timed step (--dump-outputs DIR: dump_outputs below) and the line (`value`, `ms_per_step` = milliseconds
+per timed step).  --full adds everything else the line has carried: the roofline figures (marked steps and
+unpipelined steps after the timed region), the parity check of the measured output against the generator's
+closed form, the HBM read probe, the CPU baselines and host-inclusive legs, the other workloads and `shapes`.
 
 Workloads (BASELINE.json configs):
     single-1g    1 GiB S-single, 150 bp, Phred+33            (configs[1], default)
@@ -19,8 +25,8 @@ Workloads (BASELINE.json configs):
 For N > 1 the same per-GPU workload is one byte range of a single logical
 stream N times as long (weak scaling); ranks exchange only the bytes around
 their range edges (RCCL send/recv) and verify the hand-off.  `--gpus N` without a
-launcher starts the N ranks itself (torch.distributed.run on 127.0.0.1).  The default
-run reports single-100g (and at N = 1 decode-10g, wrapped-10g) under `other_workloads`.
+launcher starts the N ranks itself (torch.distributed.run on 127.0.0.1).  A --full run of
+the default workload reports single-100g (and at N = 1 decode-10g, wrapped-10g) under `other_workloads`.
 At N = 1 it also carries `shapes`: read shapes that are no BASELINE config (long four-line reads with the decode in one
 pass, wrapped reads of kilobases, FASTA), 4 GiB each, every row verified against the generator's own offsets (shape_rates).
 """
@@ -66,6 +72,47 @@ WORKLOADS = {
     "single-100g": dict(kind="single", bytes=100 * GIB, decode=False, split=True),
     "single-4g-split": dict(kind="single", bytes=4 * GIB, decode=False, split=True),      # (quick check of the same path)
 }
+DUMP_ROWS = 1 << 19                 # --dump-outputs: rows of the offset table written (a seeded sample of larger tables)
+DUMP_QUAL_RECORDS = 4096            # ... records whose decoded qualities are written (decode workloads)
+DUMP_QUAL_VALUES = 4 << 20          # ... and at most this many decoded bytes of them
+
+
+def dump_outputs(path, table, out, qual, qoff, decode):
+    """--dump-outputs: what the last timed step handed its caller, copied out right behind the timed region, as .npy
+    files in float64 (offsets: exact below 2**53) and float32 (decoded qualities), ~40 MB at most:
+        n_records.npy   [records of this rank's range]
+        row_index.npy   which of them are written: all up to DUMP_ROWS, else a sample drawn with a fixed seed (the same
+                        indices for the same record count)
+        rows.npy        those rows of the int64[n][6] offset table
+    and for decode workloads
+        qoff.npy        the quality offsets of those rows
+        qual.npy        the decoded qualities qual[qoff[i] : qoff[i] + pos5 - pos4] of up to DUMP_QUAL_RECORDS of those rows
+                        (every k-th), concatenated
+    The input is generated from fixed seeds, so two builds run with the same arguments can be compared file for file."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    n = int(out.n_own_records)
+    if n <= DUMP_ROWS:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.unique(np.random.default_rng(0).integers(0, n, size=DUMP_ROWS))
+    it = torch.from_numpy(idx).to(table.device) + out.row_lo           # (rows of the table: this rank's own from row_lo on)
+    arrays = {"n_records": np.array([n], dtype=np.float64), "row_index": idx.astype(np.float64),
+              "rows": table[it].cpu().numpy().astype(np.float64)}
+    if decode:
+        arrays["qoff"] = qoff[it].cpu().numpy().astype(np.float64)
+        sub = it[::max(1, len(idx) // DUMP_QUAL_RECORDS)][:DUMP_QUAL_RECORDS]
+        lens = table[sub, 5] - table[sub, 4]
+        keep = torch.cumsum(lens, 0) <= DUMP_QUAL_VALUES
+        sub, lens = sub[keep], lens[keep]
+        starts = qoff[sub]
+        if len(sub):
+            assert int(starts.min()) >= 0 and int((starts + lens).max()) <= qual.numel(), "quality offsets outside the output"
+        ends = torch.cumsum(lens, 0)
+        at = torch.repeat_interleave(starts - (ends - lens), lens) + torch.arange(int(ends[-1]) if len(sub) else 0, device=table.device)
+        arrays["qual"] = qual[at].cpu().numpy().astype(np.float32)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def cpu_baseline(sample_u8, budget_s=10.0):
@@ -554,10 +601,11 @@ def spread(xs):
     return {"min": round(xs[0], 4), "median": round(xs[len(xs) // 2], 4), "max": round(xs[-1], 4)} if xs else None
 
 
-def run_workload(name, args, ctx, rank, world, dev, dist, ctl=None):
+def run_workload(name, args, ctx, rank, world, dev, dist, ctl=None, dump_dir=None):
     """Time `args.steps` passes of the hot path over workload `name`; returns (line dict, closure
     of what the CPU-side extras need) on rank 0, (None, None) elsewhere.  ctl: the side group (gloo) communicator ids
-    travel over at N > 1."""
+    travel over at N > 1.  dump_dir: rank 0 writes the last timed step's outputs there (dump_outputs).  Everything
+    after the timed region that the line's headline does not need runs with args.full only."""
     import torch
     from fastqandfurious_amd import hip, sharded
     wl = WORKLOADS[name]
@@ -679,6 +727,8 @@ def run_workload(name, args, ctx, rank, world, dev, dist, ctl=None):
         elapsed = time.perf_counter() - t0
         table = tables[(args.steps - 1) & 1]
         qual, qoff = quals[(args.steps - 1) & 1], qoffs[(args.steps - 1) & 1]
+        if dump_dir and rank == 0:
+            dump_outputs(dump_dir, table, out, qual, qoff, decode)
     elif world == 1 and not args.lanes_step:
         def step():
             return shard.scan(table, flags=flags, qual=qual, qoff=qoff)
@@ -692,6 +742,8 @@ def run_workload(name, args, ctx, rank, world, dev, dist, ctl=None):
             note(out)
         barrier()
         elapsed = time.perf_counter() - t0
+        if dump_dir and rank == 0:
+            dump_outputs(dump_dir, table, out, qual, qoff, decode)
     else:
         # Byte-range shards: the same one-step-ahead queue per rank.  A step = halo hand-off
         # (RCCL send/recv, ordered on the scan stream) + scan of [tail | own | head] + cut of the
@@ -740,7 +792,9 @@ def run_workload(name, args, ctx, rank, world, dev, dist, ctl=None):
                 out = run(args.steps, True)
                 barrier()
                 elapsed = time.perf_counter() - t0
-                if te_l > 1:
+                if dump_dir and rank == 0:
+                    dump_outputs(dump_dir, tables[(args.steps - 1) & 1], out, quals[(args.steps - 1) & 1], qoffs[(args.steps - 1) & 1], decode)
+                if te_l > 1 and args.full:
                     t_keep, c_keep = list(t_done), list(comm_steps)
                     ms_index.clear()
                     run(max(20, args.steps + (args.steps & 1)), True, every=1)      # (an even count: the last step's lane stays the same)
@@ -775,7 +829,7 @@ def run_workload(name, args, ctx, rank, world, dev, dist, ctl=None):
     # compare like for like.  (Wall-clock steps are shorter: the next step's index kernel starts behind
     # this step's last kernel with no idle gap, and host-side waits are hidden.)
     span_ms = []
-    if world == 1 and not args.sharded_step and not args.lanes_step:
+    if args.full and world == 1 and not args.sharded_step and not args.lanes_step:
         # ... and the figures `roofline` is computed from: MARKED more steps after the timed region, pipelined as the
         # timed ones but with the two HIP-event marks around the dominant kernel on EVERY step (the timed region itself
         # carries them on every --time-every-th step only: a mark is a few microseconds of idle GPU)
@@ -802,15 +856,16 @@ def run_workload(name, args, ctx, rank, world, dev, dist, ctl=None):
         torch.cuda.synchronize()
 
     # ---- parity spot check on the measured output (size-independent properties) -----
-    shard.verify(table, out)
-    if decode:
-        shard.verify_decode(table, out, qual, qoff)
+    if args.full:
+        shard.verify(table, out)
+        if decode:
+            shard.verify_decode(table, out, qual, qoff)
 
     # what this box's memory system delivers to a pure streaming read of the same buffer in the scan
     # kernel's launch geometry (16 B per lane, non-temporal), right behind the timed region: boxes of
     # the pool differ, and a throttled one shows here first
     probe_gbs = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         nprobe = min(shard.n_own_bytes, 2 * GIB) & ~((1 << 14) - 1)
         if nprobe >= (1 << 14):
             try:
@@ -825,38 +880,39 @@ def run_workload(name, args, ctx, rank, world, dev, dist, ctl=None):
         step_s = elapsed / args.steps
         value = total_bytes / step_s / 1e9
         n_rec = out.n_own_records
-        # Dominant kernel of the workload (the longest launch of a step): the Phred decode when
-        # decoding, else the line-index kernel.  Algorithmic bytes per launch:
-        #   k_scan_lines     every byte of the scanned buffer read once + 2 B of index per newline
-        #   k_decode_stream  quality bytes read + written + 16 B of (offset, pos4) per record
-        if decode and out.res.path == 8:
-            # one pass on the general path (k_scan_lines<.., WIDE>): every byte read once AND written once (decoded in place),
-            # 2 B of index per newline -- the kernel's own bytes; what of them is quality shows in path_roofline
-            dom, t_dom = "k_scan_lines<WIDE>", float(np.mean(ms_index)) * 1e-3
-            algo = 2 * shard.ext_scanned_bytes + 2 * int(out.res.n_lines)
-            traffic = pmc_traffic(name, "k_scan_lines<")
-        elif decode and out.res.path == 6:
-            # single pass (ffq_fused.h): the index kernel also writes the decoded qualities (segmented) -- every byte
-            # of the buffer read once, 2 B of index per newline and the decoded bytes written
-            dom, t_dom = "k_scan_seg", float(np.mean(ms_index)) * 1e-3
-            nq = int((table[:n_rec, 5] - table[:n_rec, 4]).sum().item())
-            algo = shard.ext_scanned_bytes + 2 * int(out.res.n_lines) + nq
-            traffic = pmc_traffic(name, "k_scan_seg")
-        elif decode:
-            dom, t_dom = "k_decode_stream", float(np.mean(ms_decode)) * 1e-3
-            algo = 2 * int(out.res.n_qual_bytes) + 16 * int(out.n_rows)
-            traffic = pmc_traffic(name, "k_decode_stream")
-        else:
-            dom, t_dom = "k_scan_lines", float(np.mean(ms_index)) * 1e-3
-            algo = shard.ext_scanned_bytes + 2 * int(out.res.n_lines)
-            traffic = pmc_traffic(name, "k_scan_lines<")
-        achieved = algo / t_dom / 1e9
-        # whole path priced with SURVEY.md 8(d): record bytes + 48 B row (+ decode bytes), over the
-        # wall-clock step (steps are queued one ahead and their small kernels overlap the next
-        # step's index kernel, so a step's own first-to-last-kernel span is longer than a step)
-        algo_path = n_own + 48 * n_rec
-        if decode:
-            algo_path += int((table[:n_rec, 5] - table[:n_rec, 4]).sum().item()) + 8 * n_rec
+        if args.full:
+            # Dominant kernel of the workload (the longest launch of a step): the Phred decode when
+            # decoding, else the line-index kernel.  Algorithmic bytes per launch:
+            #   k_scan_lines     every byte of the scanned buffer read once + 2 B of index per newline
+            #   k_decode_stream  quality bytes read + written + 16 B of (offset, pos4) per record
+            if decode and out.res.path == 8:
+                # one pass on the general path (k_scan_lines<.., WIDE>): every byte read once AND written once (decoded in place),
+                # 2 B of index per newline -- the kernel's own bytes; what of them is quality shows in path_roofline
+                dom, t_dom = "k_scan_lines<WIDE>", float(np.mean(ms_index)) * 1e-3
+                algo = 2 * shard.ext_scanned_bytes + 2 * int(out.res.n_lines)
+                traffic = pmc_traffic(name, "k_scan_lines<")
+            elif decode and out.res.path == 6:
+                # single pass (ffq_fused.h): the index kernel also writes the decoded qualities (segmented) -- every byte
+                # of the buffer read once, 2 B of index per newline and the decoded bytes written
+                dom, t_dom = "k_scan_seg", float(np.mean(ms_index)) * 1e-3
+                nq = int((table[:n_rec, 5] - table[:n_rec, 4]).sum().item())
+                algo = shard.ext_scanned_bytes + 2 * int(out.res.n_lines) + nq
+                traffic = pmc_traffic(name, "k_scan_seg")
+            elif decode:
+                dom, t_dom = "k_decode_stream", float(np.mean(ms_decode)) * 1e-3
+                algo = 2 * int(out.res.n_qual_bytes) + 16 * int(out.n_rows)
+                traffic = pmc_traffic(name, "k_decode_stream")
+            else:
+                dom, t_dom = "k_scan_lines", float(np.mean(ms_index)) * 1e-3
+                algo = shard.ext_scanned_bytes + 2 * int(out.res.n_lines)
+                traffic = pmc_traffic(name, "k_scan_lines<")
+            achieved = algo / t_dom / 1e9
+            # whole path priced with SURVEY.md 8(d): record bytes + 48 B row (+ decode bytes), over the
+            # wall-clock step (steps are queued one ahead and their small kernels overlap the next
+            # step's index kernel, so a step's own first-to-last-kernel span is longer than a step)
+            algo_path = n_own + 48 * n_rec
+            if decode:
+                algo_path += int((table[:n_rec, 5] - table[:n_rec, 4]).sum().item()) + 8 * n_rec
         steps_ms = np.diff(np.array([t0] + t_done)) * 1e3
         line = {
             "metric": "GB/s FASTQ parsed",
@@ -918,41 +974,44 @@ def run_workload(name, args, ctx, rank, world, dev, dist, ctl=None):
                 "rescan_rounds": int(sum(c["rescan_rounds"] for c in comm_steps)),
                 "regathers": int(sum(c["regathers"] for c in comm_steps)),
             },
-            "roofline": {
-                "bound": "hbm",
-                "kernel": dom,
-                "achieved": round(achieved, 2),
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 4),
-                "traffic": traffic[0] if traffic else None,
-                "traffic_source": traffic[1] if traffic else None,
-                "traffic_commit": traffic[2] if traffic else None,
-                "algorithmic_bytes_per_launch": algo,
-                "avg_launch_ms": round(t_dom * 1e3, 4),
-                "launches_timed": len(ms_decode if dom == "k_decode_stream" else ms_index),
-                "launch_ms_spread": spread(ms_decode if dom == "k_decode_stream" else ms_index),
-            },
-            "hbm_read_probe": None if probe_gbs is None else {
-                "value": round(probe_gbs, 1), "unit": "GB/s", "frac_of_peak": round(probe_gbs / HBM_PEAK_GBS, 4),
-                "what": "pure non-temporal 16 B/lane read of the same resident buffer (k_read_probe of libffq_probe.so, "
-                        "the instrumented build; not part of the product library), this box, this run"},
-            "path_roofline": {
-                "what": "all kernels of one step over the wall-clock step, SURVEY.md 8(d) bytes (record bytes + 48 B row%s)"
-                        % (" + decoded bytes + 8 B CSR offset" if decode else ""),
-                "algorithmic_bytes_per_step": algo_path,
-                "achieved": round(algo_path / step_s / 1e9, 2),
-                "frac": round(algo_path / step_s / 1e9 / HBM_PEAK_GBS, 4),
-                "ms_index": round(float(np.mean(ms_index)), 4),
-                "ms_decode": round(float(np.mean(ms_decode)), 4),
-                "basis": "throughput: wall-clock time per step with steps queued one ahead (what the driver recomputes "
-                         "from ms_per_step); device_span_* below is the round-1 definition",
-                "device_span_ms": round(float(np.median(span_ms)), 4) if span_ms else None,
-                "device_span_frac": round(algo_path / (float(np.median(span_ms)) * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if span_ms else None,
-                "device_span_what": "median of 5 unpipelined steps after the timed region: first kernel -> last kernel "
-                                    "of one step by HIP events on the scan stream (ffq_scan_result.ms_total)",
-            },
         }
+        if args.full:
+            line.update({
+                "roofline": {
+                    "bound": "hbm",
+                    "kernel": dom,
+                    "achieved": round(achieved, 2),
+                    "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 4),
+                    "traffic": traffic[0] if traffic else None,
+                    "traffic_source": traffic[1] if traffic else None,
+                    "traffic_commit": traffic[2] if traffic else None,
+                    "algorithmic_bytes_per_launch": algo,
+                    "avg_launch_ms": round(t_dom * 1e3, 4),
+                    "launches_timed": len(ms_decode if dom == "k_decode_stream" else ms_index),
+                    "launch_ms_spread": spread(ms_decode if dom == "k_decode_stream" else ms_index),
+                },
+                "hbm_read_probe": None if probe_gbs is None else {
+                    "value": round(probe_gbs, 1), "unit": "GB/s", "frac_of_peak": round(probe_gbs / HBM_PEAK_GBS, 4),
+                    "what": "pure non-temporal 16 B/lane read of the same resident buffer (k_read_probe of libffq_probe.so, "
+                            "the instrumented build; not part of the product library), this box, this run"},
+                "path_roofline": {
+                    "what": "all kernels of one step over the wall-clock step, SURVEY.md 8(d) bytes (record bytes + 48 B row%s)"
+                            % (" + decoded bytes + 8 B CSR offset" if decode else ""),
+                    "algorithmic_bytes_per_step": algo_path,
+                    "achieved": round(algo_path / step_s / 1e9, 2),
+                    "frac": round(algo_path / step_s / 1e9 / HBM_PEAK_GBS, 4),
+                    "ms_index": round(float(np.mean(ms_index)), 4),
+                    "ms_decode": round(float(np.mean(ms_decode)), 4),
+                    "basis": "throughput: wall-clock time per step with steps queued one ahead (what the driver recomputes "
+                             "from ms_per_step); device_span_* below is the round-1 definition",
+                    "device_span_ms": round(float(np.median(span_ms)), 4) if span_ms else None,
+                    "device_span_frac": round(algo_path / (float(np.median(span_ms)) * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if span_ms else None,
+                    "device_span_what": "median of 5 unpipelined steps after the timed region: first kernel -> last kernel "
+                                        "of one step by HIP events on the scan stream (ffq_scan_result.ms_total)",
+                },
+            })
     for c2 in extra_ctx:
         c2.close()
     return line, (shard, flags)
@@ -1062,9 +1121,9 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="single-1g", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no CPU baselines and host-inclusive legs")
     ap.add_argument("--no-others", action="store_true",
-                    help="N=1: do not also time decode-10g and wrapped-10g (BASELINE configs[2], [3])")
+                    help="--full, N=1: do not also time decode-10g and wrapped-10g (BASELINE configs[2], [3])")
     ap.add_argument("--settle-ms", type=float, default=50.0,
                     help="untimed steps in front of the warm-up until the GPU has been busy this long "
                          "(its clocks take ~15 ms of load to settle after an idle spell); 0: none")
@@ -1086,7 +1145,15 @@ def main():
     ap.add_argument("--lanes-step", action="store_true",
                     help="N=1 through the pipelined step of the N>1 ranks (two lanes, hand-off with no peers): "
                          "what the host side of a sharded step costs (diagnostics)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (offset table rows, decoded qualities) as .npy files "
+                         "into DIR (rank 0; a seeded sample of large outputs, see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: roofline figures, parity check of the measured output, HBM read "
+                         "probe, CPU baselines and host-inclusive legs, the other workloads and shapes")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.native_step:
         args.lanes_step = True
 
@@ -1170,7 +1237,7 @@ def main():
 
     ctx = hip.Context(local_rank)
     try:
-        line, (shard, flags) = run_workload(args.workload, args, ctx, rank, world, dev, dist, ctl)
+        line, (shard, flags) = run_workload(args.workload, args, ctx, rank, world, dev, dist, ctl, dump_dir=args.dump_outputs)
     except Exception as e:      # noqa: BLE001
         # the measured workload itself failed (N > 1: a step that did not come back even in serial mode, ranks that share a
         # GPU, a communicator that counts the wrong number of ranks): a line that SAYS so instead of a silent death at the
@@ -1187,7 +1254,9 @@ def main():
                               "wall_s": round(time.perf_counter() - t_main, 1)}), flush=True)
         os._exit(1)              # (no collective tear-down: a peer may be gone)
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if not args.full:
+            line["cpu_baseline"] = None
+        elif world == 1 and not args.no_cpu_baseline:
             sample = shard.host_sample(256 << 20)
             line["cpu_baseline"] = guarded(cpu_baseline, sample, args.cpu_seconds)
             line["cpu_baseline"]["host_cores_available"] = os.cpu_count()
@@ -1218,7 +1287,7 @@ def main():
             del sample
         else:
             line["cpu_baseline"] = None
-    if not args.no_cpu_baseline and (world == 1 or dry_gloo(dist) or os.environ.get("FFQ_BENCH_SHARDED_FILE") == "1"):
+    if args.full and not args.no_cpu_baseline and (world == 1 or dry_gloo(dist) or os.environ.get("FFQ_BENCH_SHARDED_FILE") == "1"):
         # file-backed byte-range shards (collective: every rank takes part; the line is rank 0's).  On a real multi-GPU run
         # only on request (FFQ_BENCH_SHARDED_FILE=1): it is a host-inclusive extra, and nothing that is not the metric
         # should be able to hold up the ranks of the measured line
@@ -1233,7 +1302,7 @@ def main():
     # N = 1, default workload: BASELINE configs[2] and [3] timed the same way, under their own key
     # (`value` stays configs[1]'s)
     # (at every N also BASELINE configs[4]: the one 100 GiB stream cut into `world` ranges)
-    if args.workload == "single-1g" and not args.no_others and not args.sharded_step and not args.lanes_step:
+    if args.full and args.workload == "single-1g" and not args.no_others and not args.sharded_step and not args.lanes_step:
         del shard
         torch.cuda.empty_cache()
         others = {}

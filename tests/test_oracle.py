@@ -1,13 +1,13 @@
 """The CPU oracle against the reference: committed golden vectors (captured by
-tests/golden/make_golden.py from the reference's Python module and its C
-extension) and, where /root/reference is mounted, the live reference."""
-import io
+tests/golden/make_golden.py and make_golden_live.py from the reference's Python
+module and its C extension)."""
+import os
 from array import array
 
 import numpy as np
 import pytest
 
-from conftest import end_matches, golden_file, rows_of
+from conftest import GOLDEN_DIR, end_matches, golden_file, rows_of
 
 FILES = ("test.fq", "test_longqualityheader.fq", "test_multiline.fq")
 
@@ -161,66 +161,47 @@ def test_nonsentinel_and_offset(oracle):
     assert (t3 == t1[:-1]).all() and end == 1 and st == 5 and off == t1[-2, 5] + 1 - 1
 
 
-# ---- the live reference, when mounted (this container only) -----------------
-def _live():
-    from oracle import refload
-    if not (refload.have_reference_py() and refload.have_reference_ext()):
-        pytest.skip("reference checkout / oracle/_ref not present")
-    return refload.load_py(), refload.load_ext()
+# ---- the reference's outputs on seeded random inputs -------------------------
+# (captured from the reference's Python module and C extension by tests/golden/make_golden_live.py)
+@pytest.fixture(scope="module")
+def live():
+    with np.load(os.path.join(GOLDEN_DIR, "live_reference.npz"), allow_pickle=False) as d:
+        return {k: d[k] for k in d.files}
 
 
-def test_live_reference_random_prefixes(oracle):
-    py, ext = _live()
-    rng = np.random.default_rng(7)
-    alpha = np.frombuffer(b"\n\n@+ACGT!I#", dtype=np.uint8)
+def test_live_reference_random_prefixes(oracle, live):
+    start, data = live["prefix_start"], live["prefix_bytes"]
     n = 0
-    for _ in range(3000):
-        L = int(rng.integers(0, 80))
-        b = b"\n" + rng.choice(alpha, size=L).tobytes()
-        off = int(rng.integers(0, max(L, 1)))
-        pp = array("q", [-1] * 6)
-        st = py.entrypos(b, off, pp)
+    for k in range(len(live["prefix_off"])):
+        b = data[start[k]:start[k + 1]].tobytes()
+        off = int(live["prefix_off"][k])
         so, po = oracle.entrypos(b, off, oracle.VARIANT_PY)
-        assert (st, list(pp)) == (so, po.tolist()), (b, off)
-        i = b.find(b"\n@", off)
-        if i >= 0 and i + 2 >= len(b):
-            continue   # the C scanner reads out of bounds here (_fastqandfurious.c:70-71)
-        pc = array("q", [-1] * 6)
-        st = ext.entrypos(b, off, pc)
+        assert live["prefix_py"][k].tolist() == [so] + po.tolist(), (b, off)
+        if not live["prefix_c_ok"][k]:
+            continue   # the C scanner reads out of bounds here (_fastqandfurious.c:70-71): not captured
         so, po = oracle.entrypos(b, off, oracle.VARIANT_C)
-        assert (st, list(pc)) == (so, po.tolist()), (b, off)
+        assert live["prefix_c"][k].tolist() == [so] + po.tolist(), (b, off)
         n += 1
     assert n > 2500
 
 
-def test_live_reference_iterator_bufsize_independence(oracle, pkg):
-    py, ext = _live()
-    from fastqandfurious_amd import synth
-    data, _ = synth.wrapped(100, 300, seed=43)
-    data = data.tobytes()
+def test_live_reference_iterator_bufsize_independence(oracle, live):
+    data = live["iter_data"].tobytes()
     want, end, st, off = oracle.scan(data)
-    for bs in (700, 4096, 65536):
-        got = [list(p) for p in py.readfastq_iter(io.BytesIO(data), bs, entryfunc=py.entryfunc_abspos,
-                                                  entrypos=ext.entrypos)]
+    assert len(live["iter_bufsizes"]) == 3
+    for bs in live["iter_bufsizes"]:
+        got = live["iter_rows_%d" % bs].tolist()
         assert got == rows_of(want)
 
 
-def test_live_reference_arrayadd(oracle):
-    py, ext = _live()
-    rng = np.random.default_rng(3)
-    for _ in range(50):
-        n = int(rng.integers(0, 200))
-        src = rng.integers(-128, 128, size=n, dtype=np.int8)
-        v = int(rng.integers(-300, 300))
-        a = array("b", src.tolist())
-        ext.arrayadd_b(a, v)
-        b = src.copy()
-        oracle.arrayadd_b(b, v)
-        assert a.tolist() == b.tolist()
-        src = rng.integers(-2**62, 2**62, size=n, dtype=np.int64)
-        v = int(rng.integers(-2**40, 2**40))
-        a = array("q", src.tolist())
-        ext.arrayadd_q(a, v)
-        b = src.copy()
-        oracle.arrayadd_q(b, v)
-        assert a.tolist() == b.tolist()
+def test_live_reference_arrayadd(oracle, live):
+    start = live["aa_start"]
+    assert len(start) == 51
+    for k in range(len(start) - 1):
+        s = slice(start[k], start[k + 1])
+        b = live["aa_b_src"][s].copy()
+        oracle.arrayadd_b(b, int(live["aa_b_v"][k]))
+        assert live["aa_b_out"][s].tolist() == b.tolist()
+        b = live["aa_q_src"][s].copy()
+        oracle.arrayadd_q(b, int(live["aa_q_v"][k]))
+        assert live["aa_q_out"][s].tolist() == b.tolist()

@@ -8,7 +8,7 @@ for i in $(seq $reps); do
   for v in A B; do
     if [ $v = A ]; then export FFQ_HIP_LIB=$R/gpurun_ab/libffq_hip_A.so; else unset FFQ_HIP_LIB; fi
     rm -rf /tmp/abk
-    rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/abk -o p -- python $R/bench.py --workload $wl --no-cpu-baseline --no-others > /dev/null 2>&1
+    rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/abk -o p -- python $R/bench.py --workload $wl --full --no-cpu-baseline --no-others > /dev/null 2>&1
     python - "$v" <<'PY'
 import csv, sys
 rows = [r for r in csv.DictReader(open("/tmp/abk/p_kernel_stats.csv")) if "ffq::" in r["Name"] and "synth" not in r["Name"] and "probe" not in r["Name"]]
