@@ -12,9 +12,9 @@ to run) on a mismatch -- an in-tree .so that is older or newer than the sources
 cannot stand in for them (the .so files are git-ignored but travel with the
 working tree).
 
-libffq_probe.so is the same sources with -DFFQ_PROBES: the ablation switches and
-the read / look-back / pipeline probes (include/ffq_probe.h).  Tools only; the
-product never loads it.
+libffq_probe.so is the same sources with -DFFQ_PROBES: the file loader's ablation
+switch FFQ_LOAD_ABLATE and the streaming-read probe (include/ffq_probe.h).  Tools and
+bench.py's hbm_read_probe only; the product never loads it.
 """
 import hashlib
 import os

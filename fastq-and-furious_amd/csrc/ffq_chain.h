@@ -101,7 +101,6 @@ struct ChainBufs {
     int64_t *part;       // [nblk][4] block totals (cnt, qb, lines, -) -> exclusive prefixes
     int32_t *mins;       // [4] first terminating group, first bad group, number of bad groups (from the fill value 0x7F7F7F7F up)
     int64_t *force;      // [ng] repair pass: the "\n@" the chain enters the group with (FORCE_NONE: leave alone)
-    unsigned long long *prof;   // optional: per-phase cycle sums of k_chain_wave (diagnostics)
     int32_t nmax;
     int32_t ng;
 };
@@ -274,7 +273,7 @@ __device__ __noinline__ int64_t cand_after_wave(const LineIndex *Lg, int t1, int
 // group of the list that kernel declined)
 template <int PER, int EMAX, int WPB, bool DOUBLING>
 __device__ __forceinline__ void chain_wave_group(const LineIndex &L, const LineIndex *__restrict__ Lg, int64_t offset, int eof,
-                                                 const ChainBufs &B, const int g, int only_deferred, int ablate)
+                                                 const ChainBufs &B, const int g, int only_deferred)
 {
     constexpr int NMAX = PER * 64;
     constexpr int ND = DOUBLING ? NMAX : 1;
@@ -309,9 +308,6 @@ __device__ __forceinline__ void chain_wave_group(const LineIndex &L, const LineI
     const int64_t wpos0 = (int64_t)wt0 << TILE_SHIFT;
     const int64_t len = L.len();
 
-    const bool prof = PROBES && B.prof != nullptr;
-    long long ts[6] = {0, 0, 0, 0, 0, 0};
-    if (prof) ts[0] = clock64();
     // ---- window directory + first FPE entries of every tile, one memory round trip ----
     // EPL entries per lane and pass: a pass costs ~25 instructions whatever it holds and ~20 per entry, and a tile of
     // wrapped reads has ~320 lines (80 columns, 50-300 bases: 51 bytes per line) -- with four entries per lane every
@@ -352,7 +348,6 @@ __device__ __forceinline__ void chain_wave_group(const LineIndex &L, const LineI
         }
         return;
     }
-    if (prof) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); ts[1] = clock64(); }
     // own tiles are window tiles [kown0, kown1); tile 0 is the run-in tile when has_runin
     const int kown0 = has_runin ? 1 : 0, kown1 = own1 - wt0;
     // a candidate must lie at buffer coordinate >= offset: as a window-relative bound
@@ -490,12 +485,10 @@ __device__ __forceinline__ void chain_wave_group(const LineIndex &L, const LineI
             if (runin_tile) n_runin = ncomp;
         }
     }
-    if (PROBES && ablate == 1) { if (lane == 0) B.lines[g] = lines + ncomp; return; }
     int own_hi = 0;                                    // entry index just past the own tiles
 #pragma unroll
     for (int k = 0; k <= NTW; k++)
         if (k == kown1) own_hi = tb[k];
-    if (prof) ts[2] = clock64();
     if (ncomp >= NMAX) {         // node id NMAX-1 == NO_NODE is reserved
         if (lane == 0) {
             B.y[g] = Y_UNRES; B.exit[g] = Y_UNRES; B.cnt[g] = 0; B.qb[g] = 0;
@@ -507,11 +500,9 @@ __device__ __forceinline__ void chain_wave_group(const LineIndex &L, const LineI
     // behind the last node: three positions no successor test can accept (position + 1 >= qe never holds for 0)
     if (lane < 3 && ncomp + lane <= NMAX - 1) npos[ncomp + lane] = 0u;
     wave_sync();
-    if (PROBES && ablate == 2) { if (lane == 0) B.lines[g] = lines + ncomp; return; }
     // the buffer's end as a window position (32-bit tests below)
     const uint32_t lenrel = (uint32_t)min(len - wpos0, (int64_t)0x7FFFFFF0);
 
-    if (prof) ts[3] = clock64();
     // ---- one scanner call + successor search per node (node c = u*64 + lane) -------------
     // per node ONE register: successor (16 bits) | status (5 bits, biased by 1) << 16 |
     // mi << 21 (batch index of the "\n+" entry) | sj << 25 (batch index of the successor) |
@@ -668,7 +659,6 @@ __device__ __forceinline__ void chain_wave_group(const LineIndex &L, const LineI
         if (!done) pend |= 1u << u;
     }
     // nodes the fast path could not finish (long wrapped records, window / buffer edges)
-    if (prof) { const uint32_t np = wave_sum_u32((uint32_t)__popc(pend)); if (lane == 0) atomicAdd(&B.prof[7], (unsigned long long)np | ((unsigned long long)wave_max_u32((uint32_t)__popc(pend)) << 32)); }
     // (one node at a time, by the whole wave: node_wave)
     const int64_t own_end_pos = ((int64_t)own1 << TILE_SHIFT) + L.s;      // first coordinate past the own tiles
     const int64_t win_end_pos = ((int64_t)wt1 << TILE_SHIFT) + L.s;       //                   past the window
@@ -715,7 +705,6 @@ __device__ __forceinline__ void chain_wave_group(const LineIndex &L, const LineI
         }
     }
     pend = 0;
-    if (PROBES && ablate == 3) { if (lane == 0) B.lines[g] = lines + info[0]; return; }
     int e_forced = -1;
     if (fpos != FORCE_NONE) {
         if (fpos >= ((int64_t)own1 << TILE_SHIFT) + L.s) {
@@ -734,7 +723,6 @@ __device__ __forceinline__ void chain_wave_group(const LineIndex &L, const LineI
         }
         if (e_forced >= 0) n_runin = e_forced;       // nothing in front of it belongs to the chain
     }
-    if (prof) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); ts[4] = clock64(); }
     // ---- chain membership ---------------------------------------------------------------------
     // Node ids are in position order and a successor always lies further on, so a
     // chain is a union of runs c, c+1, ..., r of "simple" nodes (successor == c+1)
@@ -803,19 +791,6 @@ __device__ __forceinline__ void chain_wave_group(const LineIndex &L, const LineI
         if (cs >= ncomp) cs = first_set_from<PER>(C2, 0);
         if (cs >= ncomp) cs = first_set_from<PER>(CL, 0);
         if (cs < ncomp) e0 = cs;
-#ifdef FFQ_PROBES
-        if (ablate >= 1000 && g == ablate - 1000) {
-            // (FFQ_ABLATE=1000+g: the nodes of one group as the start rule sees them)
-            if (lane == 0) printf("[group %d] ncomp %d n_runin %d nwin %d own_hi %d start %d (C3 %d C2 %d CL %d) wpos0 %lld\n", g, ncomp, n_runin, nwin, own_hi, e0,
-                                  first_set_from<PER>(C3, 0), first_set_from<PER>(C2, 0), first_set_from<PER>(CL, 0), (long long)wpos0);
-#pragma unroll
-            for (int u = 0; u < PER; u++) {
-                const int c = u * 64 + lane;
-                if (c < ncomp) printf("[group %d] node %3d entry %4d pos %lld succ %5u status %2d wide %d clean %d\n", g, c, (int)nidx[c], (long long)(wpos0 + (int64_t)(went[nidx[c]] & WP_MASK)),
-                                      info[u] & 0xFFFFu, (int)((info[u] >> 16) & 31u) - 1, (int)(info[u] >> 31), (int)((clean >> u) & 1u));
-            }
-        }
-#endif
     }
     bool unresolved = (fpos != FORCE_NONE && e_forced < 0), too_many_jumps = false;
     for (int attempt = 0; attempt < 4 && ncomp > 0 && !unresolved; attempt++) {
@@ -913,9 +888,7 @@ __device__ __forceinline__ void chain_wave_group(const LineIndex &L, const LineI
         if (nxt >= n_runin || attempt == 3) { unresolved = true; break; }
         e0 = nxt;
     }
-    if (PROBES && ablate == 4) { if (lane == 0) B.lines[g] = lines + lastn; return; }
 
-    if (prof) ts[5] = clock64();
     // ---- summary + staging of the own tiles' records ---------------------------------------------
     const int ynode = (ncomp > 0 && !unresolved) ? first_set_from<PER>(MB, n_runin) : NMAX;
     const bool have_y = ynode < ncomp;
@@ -1064,29 +1037,18 @@ __device__ __forceinline__ void chain_wave_group(const LineIndex &L, const LineI
             t.pos[0] = tr.p0; t.pos[1] = tr.p1; t.pos[2] = (tr.p1 >= 0) ? tr.p1 + 1 : -1;
             t.pos[3] = tr.p3; t.pos[4] = tr.p4; t.pos[5] = tr.p5;
         }
-        if (prof) {
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            const long long te = clock64();
-            atomicAdd(&B.prof[0], (unsigned long long)(ts[1] - ts[0]));   // loads landed
-            atomicAdd(&B.prof[1], (unsigned long long)(ts[2] - ts[1]));   // window written to LDS
-            atomicAdd(&B.prof[2], (unsigned long long)(ts[3] - ts[2]));   // nodes numbered
-            atomicAdd(&B.prof[3], (unsigned long long)(ts[4] - ts[3]));   // scanner calls
-            atomicAdd(&B.prof[4], (unsigned long long)(ts[5] - ts[4]));   // membership
-            atomicAdd(&B.prof[5], (unsigned long long)(te - ts[5]));      // summary + staging
-            atomicAdd(&B.prof[6], 1ull);
-        }
     }
 }
 
 template <int PER, int EMAX, int WPB, bool DOUBLING>
 __global__ __launch_bounds__(WPB * 64) void k_chain_wave(LineIndex L, const LineIndex *__restrict__ Lg,
                                                          int64_t offset, int eof, ChainBufs B, int g0, int g1,
-                                                         int only_deferred, int ablate)
+                                                         int only_deferred)
 {
     const int wid = threadIdx.x >> 6;
     const int g = g0 + blockIdx.x * WPB + wid;
     if (g >= g1) return;                 // no workgroup barrier is used below
-    chain_wave_group<PER, EMAX, WPB, DOUBLING>(L, Lg, offset, eof, B, g, only_deferred, ablate);
+    chain_wave_group<PER, EMAX, WPB, DOUBLING>(L, Lg, offset, eof, B, g, only_deferred);
 }
 
 // behind k_chain_lite (ffq_lite.h): the groups that kernel declined, from its list -- a grid of a few thousand waves takes
@@ -1102,7 +1064,7 @@ __global__ __launch_bounds__(WPB * 64) void k_chain_wave_list(LineIndex L, const
     // instead of by a 16-byte fill of its own between two kernels)
     if (blockIdx.x == 0 && threadIdx.x < 4) B.mins[threadIdx.x] = 0x7F7F7F7F;
     for (uint32_t i = blockIdx.x * WPB + wid; i < nl; i += gridDim.x * WPB)
-        chain_wave_group<PER, EMAX, WPB, DOUBLING>(L, Lg, offset, eof, B, (int)B.dlist[i], 3, 0);
+        chain_wave_group<PER, EMAX, WPB, DOUBLING>(L, Lg, offset, eof, B, (int)B.dlist[i], 3);
 }
 
 // =========================================================================

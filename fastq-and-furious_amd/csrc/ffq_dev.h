@@ -17,9 +17,9 @@
 
 namespace ffq {
 
-// Diagnostics (ablation switches of the kernels, look-back / pipeline / read probes) exist only in the
-// instrumented build of this library, libffq_probe.so (-DFFQ_PROBES; tools/ only).  In the product build
-// every `PROBES && ...` test is constant-false and the code behind it is not compiled.
+// Diagnostics (the file loader's ablation switch FFQ_LOAD_ABLATE, the streaming-read probe) exist only in the
+// instrumented build of this library, libffq_probe.so (-DFFQ_PROBES; tools/ and bench.py's hbm_read_probe).  In the
+// product build every `PROBES && ...` test is constant-false and the code behind it is not compiled.
 #ifdef FFQ_PROBES
 constexpr bool PROBES = true;
 #else

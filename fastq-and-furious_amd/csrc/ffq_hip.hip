@@ -57,10 +57,13 @@ struct ScanArgs {
 struct ScanState {
     bool active = false;
     ScanArgs a{};
+    // the caller's FFQ_F_* flags, read once at submit
+    bool serial = false, decode = false, single_pass = false, force_ranked = false, force_general = false;
+    bool poll_result = false, no_timing = false;
     int retries = 0;
     int repairs = 0;          // repair passes of the general kernels (reported with retries)
     bool dense_cfg = false, fast4_failed = false;
-    bool probe4 = false;      // the front carries the fast path's kernels as a probe (see ffq_ctx::fast4_skip)
+    bool probe4 = false;      // the front carries the fast path's kernels as a probe (see InputMemory::fast4_skip)
     bool untimed = false;     // FFQ_F_NO_TIMING: no marks around the index kernel, which may start beside the previous front's last kernel
 
     bool dense4 = false;      // the fast path's row kernel is the DENSE instantiation (it met a dense tile on this buffer, or the context remembers one)
@@ -73,6 +76,7 @@ struct ScanState {
                               //   path's decode in one pass -- no tier of this scan runs a decode kernel, qoff[i] = pos4's offset in the buffer
     bool go_ranked = false;   // the front is the index kernel only: the list-ranking tier follows at the wait
     bool index_done = false;  // the line index of this buffer is built (a later tier re-uses it)
+    bool lite_ran = false;    // the general front of this scan used the lean kernel
     int stage = 0;            // what the pending front consisted of: 1 fast four-line path, 2 general path
     int64_t ntiles = 0;
     int ngroups = 0;
@@ -91,6 +95,25 @@ struct StreamTail {
     size_t out_n[3] = {0, 0, 0};
 };
 
+// How long a verdict about a context's input holds: the scans that follow take the tier it chose without asking again.
+constexpr int HOLD_OFF = 15;
+
+// What a context remembers about its recent input: which tier its next scans start with.  ffq_ctx_forget resets all of it.
+struct InputMemory {
+    bool fast4_remember = false;         // the recent input was not plain four-line: scans start with the general kernels
+    int fast4_skip = 0;                  //   ... and this many of them do so without asking again; the one after is a PROBE
+                                         //   scan: general kernels as before, the fast path's kernels in front of them just
+                                         //   to see whether they would have stood (DevRes::fast4_hint) -- no host round trip,
+                                         //   no second front, whichever way it comes out
+    int ranked_skip = 0;                 // scans left that go straight to the list-ranking tier (long records)
+    int dense_skip = 0;                  // scans left that start with the dense configuration of the group kernels
+    int lite_skip = 0;                   // scans left whose general path runs k_chain_wave over all groups (the lean kernel declined too many)
+    bool dense4_remember = false;        // four-line input with dense tiles (reads of a dozen bases): the fast path starts with k_rows4<., true>
+    int fused_skip = 0;                  // scans left that do not try the single pass (it failed: odd records) ...
+    int fused_backoff = HOLD_OFF;        //   ... and the count after its next failure (grows 4 b + 3, up to 1023)
+    bool fz_in_place = false;            // the last single pass that stood wrote in place (long lines): start with that one
+};
+
 struct ffq_ctx {
     ScanState pend;                      // the scan enqueued by ffq_scan_submit, if any
     ffq_ctx *owner = nullptr;            // the context whose stream this one uses (itself unless created shared)
@@ -102,24 +125,13 @@ struct ffq_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    bool fast4_remember = false;         // the recent input was not plain four-line: scans start with the general kernels
-    int fast4_skip = 0;                  //   ... and this many of them do so without asking again; the one after is a PROBE
-                                         //   scan: general kernels as before, the fast path's kernels in front of them just
-                                         //   to see whether they would have stood (DevRes::fast4_hint) -- no host round trip,
-                                         //   no second front, whichever way it comes out
-    int ranked_skip = 0;                 // scans left that go straight to the list-ranking tier (long records)
+    InputMemory mem;                     // what the recent scans found the input to be
     RankBufs rk = {};                    // its scratch (ffq_ranked.h), grow-only
     int64_t rk_cap_tiles = 0, rk_cap_c = 0;
-    int dense_skip = 0;                  // scans left that start with the dense configuration of them
-    bool lite_ran = false;               // the last general front used the lean kernel
-    int lite_skip = 0;                   // scans left whose general path runs k_chain_wave over all groups (the lean kernel declined too many)
-    bool dense4_remember = false;        // four-line input with dense tiles (reads of a dozen bases): the fast path starts with k_rows4<., true>
     // single-pass index + decode (ffq_fused.h): per-tile phases, verdict; grow-only
     uint8_t *fz_qphase = nullptr;
     int64_t fz_tiles_cap = 0;
     uint32_t *fz_bad = nullptr;
-    int fused_skip = 0, fused_backoff = 15;   // scans left that do not try it (it failed: odd records), and the next count
-    bool fz_in_place = false;                 // the last single pass that stood wrote in place (long lines): start with that one
     bool decode_timed = false;           // ev[6] marks the start of the decode kernel of the pending front
     // scratch, grow-only
     int64_t cap_tiles = 0;
@@ -132,7 +144,6 @@ struct ffq_ctx {
     ChainBufs cb = {};
     int64_t stage_cap = 0;        // StageRec entries allocated
     int64_t dstage_chunks = 0;    // chunks of the walked groups' stage (cb.dstage, DCHUNK records each), grow-only
-    unsigned long long *prof_d = nullptr;
     long long *sbbase = nullptr;
     TileQ *tileq = nullptr;              // fast path + decode: records / quality bytes per tile
     unsigned int *sbq = nullptr;         //   quality bytes per 64 tiles
@@ -543,7 +554,7 @@ static int reserve_pool(ffq_ctx *c, unsigned long long entries)
 
 extern "C" void ffq_ctx_forget(ffq_ctx *c)
 {
-    if (c) { c->fast4_remember = false; c->fast4_skip = 0; c->dense_skip = 0; c->lite_skip = 0; c->dense4_remember = false; c->ranked_skip = 0; c->fused_skip = 0; c->fused_backoff = 15; c->fz_in_place = false; }
+    if (c) c->mem = InputMemory{};
 }
 
 extern "C" int ffq_ctx_reserve(ffq_ctx *c, int64_t max_bytes)
@@ -644,7 +655,7 @@ static LineIndex make_index(ffq_ctx *c, const ScanArgs &a, int64_t ntiles)
 // The line-index launch: one workgroup per whole tile; the ragged last tile (if any) rides along
 // as workgroup 0's second tile.  A buffer shorter than a tile is one workgroup.
 static void launch_scan_lines(ffq_ctx *c, hipStream_t st, const uint8_t *d_buf, int64_t n_bytes, int64_t ntiles,
-                              const LineIndex &L, uint32_t at_char, int ablate = 0, bool any_order = false,
+                              const LineIndex &L, uint32_t at_char, bool any_order = false,
                               int8_t *wout = nullptr, int wadd = 0)
 {
     const int64_t nfull = n_bytes >> TILE_SHIFT;
@@ -655,11 +666,11 @@ static void launch_scan_lines(ffq_ctx *c, hipStream_t st, const uint8_t *d_buf, 
         // layout in one pass (FFQ_F_DECODE_QUAL | FFQ_F_SINGLE_PASS on the general path)
         if (nfull > 0)
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_lines<true, 8, true>), dim3((unsigned)nfull), dim3(256), 0, st, d_buf,
-                               n_bytes, c->ent, c->cnt, c->ovf, c->pool, c->pool_cap, c->ctl, 0, ablate, L, c->d_L,
+                               n_bytes, c->ent, c->cnt, c->ovf, c->pool, c->pool_cap, c->ctl, 0, L, c->d_L,
                                at_char, ragged, wout, (uint32_t)wadd);
         else
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_lines<false, 8, true>), dim3(1), dim3(256), 0, st, d_buf,
-                               n_bytes, c->ent, c->cnt, c->ovf, c->pool, c->pool_cap, c->ctl, 0, ablate, L, c->d_L,
+                               n_bytes, c->ent, c->cnt, c->ovf, c->pool, c->pool_cap, c->ctl, 0, L, c->d_L,
                                at_char, 0, wout, (uint32_t)wadd);
         return;
     }
@@ -670,14 +681,14 @@ static void launch_scan_lines(ffq_ctx *c, hipStream_t st, const uint8_t *d_buf, 
         // scan touches; the kernels behind it are ordinary launches and wait for everything in front of them.
         hipExtLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_lines<true, 8>), dim3((unsigned)nfull), dim3(256), 0, st, nullptr, nullptr,
                               hipExtAnyOrderLaunch, d_buf, n_bytes, c->ent, c->cnt, c->ovf, c->pool, c->pool_cap, c->ctl, 0,
-                              ablate, L, c->d_L, at_char, ragged, no_out, 0u);
+                              L, c->d_L, at_char, ragged, no_out, 0u);
     else if (nfull > 0)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_lines<true, 8>), dim3((unsigned)nfull), dim3(256), 0, st, d_buf,
-                           n_bytes, c->ent, c->cnt, c->ovf, c->pool, c->pool_cap, c->ctl, 0, ablate, L, c->d_L,
+                           n_bytes, c->ent, c->cnt, c->ovf, c->pool, c->pool_cap, c->ctl, 0, L, c->d_L,
                            at_char, ragged, no_out, 0u);
     else
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_lines<false, 8>), dim3(1), dim3(256), 0, st, d_buf,
-                           n_bytes, c->ent, c->cnt, c->ovf, c->pool, c->pool_cap, c->ctl, 0, ablate, L, c->d_L,
+                           n_bytes, c->ent, c->cnt, c->ovf, c->pool, c->pool_cap, c->ctl, 0, L, c->d_L,
                            at_char, 0, no_out, 0u);
 }
 
@@ -687,11 +698,10 @@ static void enqueue_decode(ffq_ctx *c, const ScanArgs &a, hipStream_t st, bool t
 {
     if (timed) { (void)hipEventRecord(c->ev[6], st); c->decode_timed = true; }
     const int64_t nblk = qdir_blocks(a.n_bytes, a.qual_cap);
-    static const int ablate = (PROBES && getenv("FFQ_DQ_ABLATE")) ? atoi(getenv("FFQ_DQ_ABLATE")) : 0;
     hipLaunchKernelGGL(k_decode_stream, dim3((unsigned)nblk), dim3(256), 0, st, a.d_buf, a.n_bytes, a.s,
                        (const int64_t *)c->p4s, (const int64_t *)a.d_qoff, (const int64_t *)c->qdir,
                        (const DevRes *)c->dres, std::min<int64_t>(a.table_cap, c->p4s_cap), a.add, a.qual_add, a.d_qual,
-                       a.qual_cap, ablate);
+                       a.qual_cap);
 }
 
 // ---- the single-pass index + decode front (ffq_fused.h) ---------------------------------------------
@@ -753,11 +763,11 @@ static int poll_seq(ffq_ctx *c, unsigned long long want)
 }
 
 // verification + scan of the group counts, rows, result block (publishes) [-> decode]
-static int enqueue_resolve(ffq_ctx *c, const ScanArgs &a, const ChainBufs &cb, bool timed, bool mins_set = false)
+static int enqueue_resolve(ffq_ctx *c, const ScanState &st, const ChainBufs &cb, bool timed, bool mins_set = false)
 {
-    const bool decode = (a.flags & FFQ_F_DECODE_QUAL) != 0;
-    const bool wide = c->pend.wide;          // (the qualities are there already, in place: k_expand writes qoff[i] = pos4's buffer offset)
-    int64_t *qoff = decode ? a.d_qoff : nullptr;
+    const ScanArgs &a = st.a;
+    const bool wide = st.wide;          // (the qualities are there already, in place: k_expand writes qoff[i] = pos4's buffer offset)
+    int64_t *qoff = st.decode ? a.d_qoff : nullptr;
     hipStream_t sA = c->stream;
     const int ngroups = cb.ng;
     const int nblk = (ngroups + RES_BLOCK - 1) / RES_BLOCK;
@@ -770,7 +780,7 @@ static int enqueue_resolve(ffq_ctx *c, const ScanArgs &a, const ChainBufs &cb, b
     hipLaunchKernelGGL(k_finalize, dim3(1), dim3(64), 0, sA, c->dres, a.d_table, a.table_cap, a.add, a.offset, qoff,
                        make_pub(c), wide ? a.s : -1);
     c->ctl_clean = true;
-    if (decode && !wide) enqueue_decode(c, a, sA, timed);
+    if (st.decode && !wide) enqueue_decode(c, a, sA, timed);
     return FFQ_OK;
 }
 
@@ -781,7 +791,6 @@ static ChainBufs chain_bufs(ffq_ctx *c, int ngroups, int nmax)
     ChainBufs cb = c->cb;
     cb.ng = ngroups;
     cb.nmax = nmax;
-    cb.prof = nullptr;
     cb.sbase = reinterpret_cast<int32_t *>(cb.flags + ngroups);
     cb.dhead = cb.flags + 2 * (size_t)ngroups;
     cb.dcnt = cb.dhead + 1;
@@ -791,28 +800,33 @@ static ChainBufs chain_bufs(ffq_ctx *c, int ngroups, int nmax)
 
 // repair pass: the groups whose entry guess the verification rejected are re-run from their
 // predecessor's exit (k_repair_mark), then everything is verified again
-static int enqueue_repair(ffq_ctx *c, const ScanArgs &a, const LineIndex &L, bool dense_cfg, int ngroups)
+static int enqueue_repair(ffq_ctx *c, const ScanState &st, const LineIndex &L)
 {
+    const ScanArgs &a = st.a;
+    const bool dense_cfg = st.dense_cfg;
+    const int ngroups = st.ngroups;
     ChainBufs cb = chain_bufs(c, ngroups, dense_cfg ? NMAX_DENSE : NMAX_FAST);
     hipStream_t sA = c->stream;
     hipLaunchKernelGGL(k_repair_mark, dim3((unsigned)((ngroups + 255) / 256)), dim3(256), 0, sA, cb);
     if (!dense_cfg)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain_wave<PER_FAST, EMAX_FAST, WPB_FAST, false>),
                            dim3((ngroups + WPB_FAST - 1) / WPB_FAST), dim3(WPB_FAST * 64), 0, sA, L,
-                           (const LineIndex *)c->d_L, a.offset, a.eof, cb, 0, ngroups, 2, 0);
+                           (const LineIndex *)c->d_L, a.offset, a.eof, cb, 0, ngroups, 2);
     else
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain_wave<PER_DENSE, EMAX_DENSE, WPB_DENSE, true>),
                            dim3((ngroups + WPB_DENSE - 1) / WPB_DENSE), dim3(WPB_DENSE * 64), 0, sA, L,
-                           (const LineIndex *)c->d_L, a.offset, a.eof, cb, 0, ngroups, 2, 0);
+                           (const LineIndex *)c->d_L, a.offset, a.eof, cb, 0, ngroups, 2);
     // the groups that do not fit the kernel above (dense tiles) and whose entry is known: walked
     hipLaunchKernelGGL(k_dense_walk, dim3((unsigned)((ngroups + 3) / 4)), dim3(256), 0, sA, L, cb, a.offset, a.eof, 0, dense_cfg ? 1 : 0, c->ctl, 0);
-    return enqueue_resolve(c, a, cb, false);
+    return enqueue_resolve(c, st, cb, false);
 }
 
 // general path: chain summaries -> resolve -> expand -> finalize (publishes) [-> decode]
-static int enqueue_general(ffq_ctx *c, const ScanArgs &a, const LineIndex &L, bool dense_cfg, int ngroups,
-                           bool timed = false)
+static int enqueue_general(ffq_ctx *c, ScanState &st, const LineIndex &L, bool timed = false)
 {
+    const ScanArgs &a = st.a;
+    const bool dense_cfg = st.dense_cfg;
+    const int ngroups = st.ngroups;
     const int nmax = dense_cfg ? NMAX_DENSE : NMAX_FAST;
     int rc = reserve_stage(c, ngroups, nmax);
     if (rc) return rc;
@@ -820,20 +834,13 @@ static int enqueue_general(ffq_ctx *c, const ScanArgs &a, const LineIndex &L, bo
     if (rc) return rc;
     ChainBufs cb = chain_bufs(c, ngroups, nmax);
     hipStream_t sA = c->stream;
-    const char *abl = PROBES ? getenv("FFQ_ABLATE") : nullptr;
-    const int ablate = abl ? atoi(abl) : 0;
-    if (PROBES && getenv("FFQ_PROF")) {
-        if (!c->prof_d) HIPCHK(hipMalloc((void **)&c->prof_d, 128));
-        HIPCHK(hipMemsetAsync(c->prof_d, 0, 128, sA));
-        cb.prof = c->prof_d;
-    }
     HIPCHK(hipMemsetAsync(cb.flags, 0, (2 * (size_t)ngroups + 3) * 4, sA));      // flags, and: no group has a chunk of the walked groups' stage yet
     static const bool no_lite = getenv("FFQ_NO_LITE") != nullptr;
-    bool lite = !dense_cfg && ablate == 0 && (!cb.prof || (PROBES && getenv("FFQ_PROF_LITE"))) && !no_lite;
+    bool lite = !dense_cfg && !no_lite;
     // (a context whose recent input the lean kernel mostly declined -- tiles of more than LT_E lines that still fit the usual
     // window: lines of 43-48 bytes -- runs k_chain_wave directly for a while: the list kernel is the slower way to run many groups)
-    if (lite && c->lite_skip > 0) { c->lite_skip--; lite = false; }
-    c->lite_ran = lite;
+    if (lite && c->mem.lite_skip > 0) { c->mem.lite_skip--; lite = false; }
+    st.lite_ran = lite;
     if (lite) {
         // ordinary groups by the lean kernel; what it declines (flag bit 3) goes to k_chain_wave right behind.  The groups it
         // cannot take by their place -- the first one (sentinel, search offset), the last ones (the buffer's end) -- are
@@ -845,7 +852,7 @@ static int enqueue_general(ffq_ctx *c, const ScanArgs &a, const LineIndex &L, bo
         // it with whatever else was declined -- one launch of one-wave latency instead of three, and none in FRONT of the lean
         // kernel, where round 4's ordinary launch of the first group held the whole GPU for 29 us)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain_lite<WPB_LITE>), dim3((ngroups + WPB_LITE - 1) / WPB_LITE), dim3(WPB_LITE * 64), 0, sA,
-                           L, a.offset, cb, ngroups, gl, (PROBES && getenv("FFQ_LITE_ABLATE")) ? atoi(getenv("FFQ_LITE_ABLATE")) : 0);
+                           L, a.offset, cb, ngroups, gl);
     }
     if (lite)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain_wave_list<PER_FAST, EMAX_FAST, WPB_FAST, false>),
@@ -854,16 +861,44 @@ static int enqueue_general(ffq_ctx *c, const ScanArgs &a, const LineIndex &L, bo
     else if (!dense_cfg)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain_wave<PER_FAST, EMAX_FAST, WPB_FAST, false>),
                            dim3((ngroups + WPB_FAST - 1) / WPB_FAST), dim3(WPB_FAST * 64), 0, sA, L,
-                           (const LineIndex *)c->d_L, a.offset, a.eof, cb, 0, ngroups, 0, ablate);
+                           (const LineIndex *)c->d_L, a.offset, a.eof, cb, 0, ngroups, 0);
     else
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain_wave<PER_DENSE, EMAX_DENSE, WPB_DENSE, true>),
                            dim3((ngroups + WPB_DENSE - 1) / WPB_DENSE), dim3(WPB_DENSE * 64), 0, sA, L,
-                           (const LineIndex *)c->d_L, a.offset, a.eof, cb, 0, ngroups, 0, ablate);
+                           (const LineIndex *)c->d_L, a.offset, a.eof, cb, 0, ngroups, 0);
     // the groups the kernel above declined (dense tiles), each from a guessed entry
-    if (ablate == 0)
-        hipLaunchKernelGGL(k_dense_walk, dim3((unsigned)std::min((ngroups + 3) / 4, 1024)), dim3(256), 0, sA, L, cb, a.offset, a.eof, 1,
-                           dense_cfg ? 1 : 0, c->ctl, 1);
-    return enqueue_resolve(c, a, cb, timed, lite);
+    hipLaunchKernelGGL(k_dense_walk, dim3((unsigned)std::min((ngroups + 3) / 4, 1024)), dim3(256), 0, sA, L, cb, a.offset, a.eof, 1,
+                       dense_cfg ? 1 : 0, c->ctl, 1);
+    return enqueue_resolve(c, st, cb, timed, lite);
+}
+
+// The row kernels' prologue: the newline counts of every superblock of SB_TILES tiles and their scan (k_sbscan) -- for a
+// large buffer the per-superblock sums by many workgroups first (k_sum64), the scan kernel then only scans.
+static void enqueue_sbscan(ffq_ctx *c, const LineIndex &L, int64_t ntiles, int nsb, int64_t offset)
+{
+    const unsigned int *presum = nullptr;
+    if (nsb > 2048) {
+        hipLaunchKernelGGL(k_sum64, dim3((unsigned)((nsb + 3) / 4)), dim3(256), 0, c->stream, (const uint32_t *)c->cnt, 1,
+                           (int64_t)ntiles, c->sbq, nsb);
+        presum = c->sbq;
+    }
+    hipLaunchKernelGGL(k_sbscan, dim3(1), dim3(1024), 0, c->stream, L, nsb, c->sbbase, offset, c->hdr4, presum);
+}
+
+// The end of every front: ev[3] behind its last kernel (its result block is in host memory), and the stream now ends in
+// a scan front of `c` (StreamTail)
+static int end_front(ffq_ctx *c, const ScanState &st)
+{
+    const ScanArgs &a = st.a;
+    c->pub_seq = 0;                       // (publishers of later tiers, enqueued at the wait, signal with events)
+    if (!st.poll_seq) HIPCHK(hipEventRecord(c->ev[3], c->stream));
+    HIPCHK(hipGetLastError());
+    StreamTail &tl = c->owner->tail;
+    tl.is_scan = true;
+    tl.out_p[0] = a.d_table; tl.out_n[0] = (size_t)a.table_cap * 48;
+    tl.out_p[1] = st.decode ? a.d_qual : nullptr; tl.out_n[1] = st.decode ? (size_t)a.qual_cap : 0;
+    tl.out_p[2] = st.decode ? a.d_qoff : nullptr; tl.out_n[2] = st.decode ? ((size_t)a.table_cap + 1) * 8 : 0;
+    return FFQ_OK;
 }
 
 // front of a scan: everything on ONE in-order stream (the context's), no host synchronisation
@@ -873,45 +908,30 @@ static int enqueue_general(ffq_ctx *c, const ScanArgs &a, const LineIndex &L, bo
 // second tile).  The last result-writing kernel publishes the result block into host-mapped
 // memory and zeroes the control block for the next scan; ev[3] follows the last kernel.  A
 // second context on the same stream queues its front right behind: the GPU never idles.
-// the stream now ends in a scan front of `c` (StreamTail)
-static void note_scan_tail(ffq_ctx *c, const ScanArgs &a)
-{
-    StreamTail &tl = c->owner->tail;
-    tl.is_scan = true;
-    const bool decode = (a.flags & FFQ_F_DECODE_QUAL) != 0;
-    tl.out_p[0] = a.d_table; tl.out_n[0] = (size_t)a.table_cap * 48;
-    tl.out_p[1] = decode ? a.d_qual : nullptr; tl.out_n[1] = decode ? (size_t)a.qual_cap : 0;
-    tl.out_p[2] = decode ? a.d_qoff : nullptr; tl.out_n[2] = decode ? ((size_t)a.table_cap + 1) * 8 : 0;
-}
-
 static int enqueue_front(ffq_ctx *c, ScanState &st)
 {
     const ScanArgs &a = st.a;
-    const bool serial = (a.flags & FFQ_F_FORCE_SERIAL) != 0;
-    const bool decode = (a.flags & FFQ_F_DECODE_QUAL) != 0;
-    const char *abl = PROBES ? getenv("FFQ_ABLATE") : nullptr;
-    const int ablate = abl ? atoi(abl) : 0;
-    const int k1abl = (PROBES && getenv("FFQ_K1_ABLATE")) ? atoi(getenv("FFQ_K1_ABLATE")) : 0;
+    const bool serial = st.serial, decode = st.decode;
     hipStream_t sA = c->stream;
     const int64_t ntiles = st.ntiles;
     const int nsb = (int)((ntiles + SB_TILES - 1) / SB_TILES);
     // the four-line fast path (ffq_rows4.h) is tried first unless it already failed on this buffer
     // (nor while the context remembers that its recent input was not four-line)
-    if (c->ranked_skip > 0 && !serial && !st.index_done && ablate == 0) { c->ranked_skip--; st.go_ranked = true; }
-    if ((a.flags & FFQ_F_FORCE_RANKED) && !serial) st.go_ranked = true;
+    if (c->mem.ranked_skip > 0 && !serial && !st.index_done) { c->mem.ranked_skip--; st.go_ranked = true; }
+    if (st.force_ranked && !serial) st.go_ranked = true;
     st.probe4 = false;
-    if (c->fast4_remember && !st.fast4_failed) {
+    if (c->mem.fast4_remember && !st.fast4_failed) {
         st.fast4_failed = true;
-        if (c->fast4_skip > 0) c->fast4_skip--;
-        else st.probe4 = !serial && !st.go_ranked && !st.index_done && ablate == 0;
+        if (c->mem.fast4_skip > 0) c->mem.fast4_skip--;
+        else st.probe4 = !serial && !st.go_ranked && !st.index_done;
     }
-    if (c->dense_skip > 0 && !st.dense_cfg && !st.index_done) { c->dense_skip--; st.dense_cfg = true; }
-    const bool try_fast4 = !serial && !st.go_ranked && !st.dense_cfg && !st.fast4_failed && ablate == 0 &&
-                           !(a.flags & FFQ_F_FORCE_GENERAL) && getenv("FFQ_NO_FAST4") == nullptr;
+    if (c->mem.dense_skip > 0 && !st.dense_cfg && !st.index_done) { c->mem.dense_skip--; st.dense_cfg = true; }
+    const bool try_fast4 = !serial && !st.go_ranked && !st.dense_cfg && !st.fast4_failed && !st.force_general &&
+                           getenv("FFQ_NO_FAST4") == nullptr;
     const LineIndex L = make_index(c, a, ntiles);
     c->decode_timed = false;
     // without the decode every front ends in a publisher: it can say "done" itself
-    st.poll_seq = ((a.flags & FFQ_F_POLL_RESULT) && !decode) ? ++c->seq : 0;
+    st.poll_seq = (st.poll_result && !decode) ? ++c->seq : 0;
     c->pub_seq = st.poll_seq;
     c->ctl_was_clean = c->ctl_clean;
     if (!c->ctl_clean) HIPCHK(hipMemsetAsync(c->ctl, 0, sizeof(Ctl), sA));    // first scan, or an abandoned front
@@ -924,22 +944,16 @@ static int enqueue_front(ffq_ctx *c, ScanState &st)
     // few per cent slower on short reads (more bytes written); both write whole 16-byte pieces: an unaligned d_qual gets the
     // packed stream.  The segmented one first; once it has refused a buffer for its shape the in-place one, which the
     // context then remembers.)
-    st.in_place = (c->fz_in_place || st.seg_refused) && a.qual_cap >= ntiles * (int64_t)TILE;
-    if (decode && (a.flags & FFQ_F_SINGLE_PASS) && try_fast4 && !st.index_done && !st.no_fused && a.offset < 16 &&
+    st.in_place = (c->mem.fz_in_place || st.seg_refused) && a.qual_cap >= ntiles * (int64_t)TILE;
+    if (decode && st.single_pass && try_fast4 && !st.index_done && !st.no_fused && a.offset < 16 &&
         (st.in_place || (!st.seg_refused && a.qual_cap >= ntiles * (int64_t)SG_STRIDE)) && (reinterpret_cast<uintptr_t>(a.d_qual) & 15) == 0) {
-        if (c->fused_skip > 0) c->fused_skip--;
+        if (c->mem.fused_skip > 0) c->mem.fused_skip--;
         else st.fused = true;
     }
     if (st.fused) {
         int rc = enqueue_fused_index(c, a, ntiles, st.in_place);
         if (rc) return rc;
-        const unsigned int *presum = nullptr;
-        if (nsb > 2048) {
-            hipLaunchKernelGGL(k_sum64, dim3((unsigned)((nsb + 3) / 4)), dim3(256), 0, sA, (const uint32_t *)c->cnt, 1,
-                               (int64_t)ntiles, c->sbq, nsb);
-            presum = c->sbq;
-        }
-        hipLaunchKernelGGL(k_sbscan, dim3(1), dim3(1024), 0, sA, L, nsb, c->sbbase, a.offset, c->hdr4, presum);
+        enqueue_sbscan(c, L, ntiles, nsb, a.offset);
         auto rows4 = st.in_place ? k_rows4<2, false> : k_rows4<1, false>;
         hipLaunchKernelGGL(rows4, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, sA, L,
                            (const long long *)c->sbbase, a.eof, a.add, c->hdr4, c->tinfo4, a.d_table, a.table_cap,
@@ -951,17 +965,13 @@ static int enqueue_front(ffq_ctx *c, ScanState &st)
                            a.d_qoff, make_pub(c));
         c->ctl_clean = true;
         st.stage = 1;
-        c->pub_seq = 0;
-        if (!st.poll_seq) HIPCHK(hipEventRecord(c->ev[3], sA));
-        HIPCHK(hipGetLastError());
-        note_scan_tail(c, a);
-        return FFQ_OK;
+        return end_front(c, st);
     }
 
     // ---- line index --------------------------------------------------------------------
     // (FFQ_F_NO_TIMING with the polled completion: no stream marker anywhere in the front -- each is a barrier
     // packet with a few microseconds of idle GPU around it)
-    st.untimed = (a.flags & FFQ_F_NO_TIMING) && st.poll_seq && !st.index_done;
+    st.untimed = st.no_timing && st.poll_seq && !st.index_done;
     // ... and the index kernel without a barrier in front of it only where the library itself can vouch for it (StreamTail)
     bool any_order = st.untimed && c->ctl_was_clean;
     {
@@ -981,26 +991,19 @@ static int enqueue_front(ffq_ctx *c, ScanState &st)
     // refused fast path already has its index and takes the packed decode, as before.)
     static const bool no_wide = getenv("FFQ_NO_WIDE") != nullptr;
     if (!st.index_done)
-        st.wide = decode && (a.flags & FFQ_F_SINGLE_PASS) && !try_fast4 && ablate == 0 && !no_wide &&
+        st.wide = decode && st.single_pass && !try_fast4 && !no_wide &&
                   a.qual_cap >= ntiles * (int64_t)TILE && (reinterpret_cast<uintptr_t>(a.d_qual) & 15) == 0;
     if (!st.untimed) HIPCHK(hipEventRecord(c->ev[0], sA));
     if (!st.index_done)          // (a later tier of the same scan: the index is there already)
-        launch_scan_lines(c, sA, a.d_buf, a.n_bytes, ntiles, L, (uint32_t)'@', k1abl, any_order && !st.wide,
+        launch_scan_lines(c, sA, a.d_buf, a.n_bytes, ntiles, L, (uint32_t)'@', any_order && !st.wide,
                           st.wide ? a.d_qual : (int8_t *)nullptr, a.qual_add);
     if (!st.untimed) HIPCHK(hipEventRecord(c->ev[1], sA));
 
     if (try_fast4) {
         // ---- plain four-line records: rows straight from newline ordinals, then validated -----
-        const unsigned int *presum = nullptr;
-        if (nsb > 2048) {
-            // a large buffer: the per-superblock sums by many workgroups, the scan kernel only scans
-            hipLaunchKernelGGL(k_sum64, dim3((unsigned)((nsb + 3) / 4)), dim3(256), 0, sA, (const uint32_t *)c->cnt, 1,
-                               (int64_t)ntiles, c->sbq, nsb);
-            presum = c->sbq;
-        }
-        hipLaunchKernelGGL(k_sbscan, dim3(1), dim3(1024), 0, sA, L, nsb, c->sbbase, a.offset, c->hdr4, presum);
+        enqueue_sbscan(c, L, ntiles, nsb, a.offset);
         if (decode) HIPCHK(hipMemsetAsync(c->tileq, 0, (size_t)ntiles * sizeof(TileQ), sA));
-        if (c->dense4_remember) st.dense4 = true;
+        if (c->mem.dense4_remember) st.dense4 = true;
         auto rows4 = st.dense4 ? k_rows4<false, true> : k_rows4<false, false>;
         hipLaunchKernelGGL(rows4, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, sA, L,
                            (const long long *)c->sbbase, a.eof, a.add, c->hdr4, c->tinfo4, a.d_table, a.table_cap,
@@ -1032,14 +1035,8 @@ static int enqueue_front(ffq_ctx *c, ScanState &st)
             // has the input turned plain four-line again?  The fast path's kernels (rows into the caller's
             // table, which the general kernels then write again; no decode tail), their verdict left in
             // DevRes::fast4_hint for the publisher of the general path to carry out
-            const unsigned int *presum = nullptr;
-            if (nsb > 2048) {
-                hipLaunchKernelGGL(k_sum64, dim3((unsigned)((nsb + 3) / 4)), dim3(256), 0, sA, (const uint32_t *)c->cnt, 1,
-                                   (int64_t)ntiles, c->sbq, nsb);
-                presum = c->sbq;
-            }
-            hipLaunchKernelGGL(k_sbscan, dim3(1), dim3(1024), 0, sA, L, nsb, c->sbbase, a.offset, c->hdr4, presum);
-            auto rows4 = c->dense4_remember ? k_rows4<false, true> : k_rows4<false, false>;
+            enqueue_sbscan(c, L, ntiles, nsb, a.offset);
+            auto rows4 = c->mem.dense4_remember ? k_rows4<false, true> : k_rows4<false, false>;
             hipLaunchKernelGGL(rows4, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, sA, L,
                                (const long long *)c->sbbase, a.eof, a.add, c->hdr4, c->tinfo4, a.d_table, a.table_cap,
                                (uint32_t *)nullptr, c->tileq, (int64_t *)nullptr, (int64_t)0,
@@ -1048,7 +1045,7 @@ static int enqueue_front(ffq_ctx *c, ScanState &st)
                                a.offset, a.add, (const int64_t *)a.d_table, a.table_cap, c->dres, no_pub(c));
         }
         if (!serial && !st.go_ranked) {
-            int rc = enqueue_general(c, a, L, st.dense_cfg, st.ngroups, true);
+            int rc = enqueue_general(c, st, L, true);
             if (rc) return rc;
         } else {
             hipLaunchKernelGGL(k_publish, dim3(1), dim3(1), 0, sA, c->dres, make_pub(c), 1);
@@ -1056,12 +1053,7 @@ static int enqueue_front(ffq_ctx *c, ScanState &st)
         }
         st.stage = 2;
     }
-    // ev[3]: the last kernel of this front is through (its result block is in host memory)
-    c->pub_seq = 0;                       // (publishers of later tiers, enqueued at the wait, signal with events)
-    if (!st.poll_seq) HIPCHK(hipEventRecord(c->ev[3], sA));
-    HIPCHK(hipGetLastError());
-    note_scan_tail(c, a);
-    return FFQ_OK;
+    return end_front(c, st);
 }
 
 template <class T>
@@ -1190,11 +1182,26 @@ static int enqueue_offsets_in_place(ffq_ctx *c, const ScanArgs &a, int64_t n_row
     return FFQ_OK;
 }
 
+// A tier scan_finish enqueues behind the front: marked by ev[4] / ev[2], waited for, its time added to ms_chain / ms_total.
+template <class Enqueue>
+static int run_tier(ffq_ctx *c, ffq_scan_result *res, Enqueue enqueue)
+{
+    HIPCHK(hipEventRecord(c->ev[4], c->stream));
+    const int rc = enqueue();
+    if (rc) return rc;
+    HIPCHK(hipEventRecord(c->ev[2], c->stream));
+    HIPCHK(hipGetLastError());
+    CTX_WAIT_EVENT(c, c->ev[2]);
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev[4], c->ev[2]));
+    res->ms_chain += ms; res->ms_total += ms;
+    return FFQ_OK;
+}
+
 static int scan_finish(ffq_ctx *c, ScanState &st, ffq_scan_result *res)
 {
     const ScanArgs &a = st.a;
-    const bool serial = (a.flags & FFQ_F_FORCE_SERIAL) != 0;
-    const bool decode = (a.flags & FFQ_F_DECODE_QUAL) != 0;
+    const bool serial = st.serial, decode = st.decode;
     int64_t *qoff = decode ? a.d_qoff : nullptr;
     hipStream_t sA = c->stream;
     bool front_done = true;           // the first front was enqueued by the caller (submit)
@@ -1255,27 +1262,21 @@ static int scan_finish(ffq_ctx *c, ScanState &st, ffq_scan_result *res)
 
         const bool tiers = !serial && !st.go_ranked;       // the group kernels ran: their fallbacks apply
         if (st.probe4) {
-            // the probe's verdict: the next scan starts with the fast path again, or 15 more do not ask
+            // the probe's verdict: the next scan starts with the fast path again, or HOLD_OFF more do not ask
             st.probe4 = false;
-            if (c->h_res->fast4_hint == 1) { c->fast4_remember = false; c->fast4_skip = 0; }
-            else c->fast4_skip = 15;
+            if (c->h_res->fast4_hint == 1) { c->mem.fast4_remember = false; c->mem.fast4_skip = 0; }
+            else c->mem.fast4_skip = HOLD_OFF;
         }
         if (st.stage == 1) {
             if (!c->h_res->fallback) {
                 fill_result(res, *c->h_res, st.fused ? 6 : 3, st.retries);
-                if (st.fused) { c->fused_backoff = 15; c->fz_in_place = st.in_place; }
+                if (st.fused) { c->mem.fused_backoff = HOLD_OFF; c->mem.fz_in_place = st.in_place; }
                 break;
             }
             if (st.fused) {
                 // the single pass did not stand (lines longer than a tile, a quality line that is not as
                 // long as its sequence line, text in front of the first record, not four-line input at
                 // all ...): the two-pass kernels, from the index it built if that is whole
-                if (PROBES && getenv("FFQ_DEBUG")) {
-                    Fast4Hdr hh;
-                    HIPCHK(hipMemcpy(&hh, c->hdr4, sizeof hh, hipMemcpyDeviceToHost));
-                    fprintf(stderr, "[ffq debug] single pass (%s) refused: fused_bad %d attempt %d j0 %lld irr_min %llu term_min %llu\n",
-                            st.in_place ? "in place" : "segmented", c->h_res->fused_bad, hh.attempt, hh.j0, hh.irr_min, hh.term_min);
-                }
                 if (!st.in_place && !st.seg_refused && (c->h_res->fused_bad & (int32_t)FZ_BAD_SHAPE) &&
                     !(c->h_res->fused_bad & (int32_t)FZ_BAD_INDEX) && a.qual_cap >= st.ntiles * (int64_t)TILE) {
                     // a shape the segments cannot take (a line longer than SG_EXT behind a tile, no S P pair in a tile
@@ -1286,98 +1287,40 @@ static int scan_finish(ffq_ctx *c, ScanState &st, ffq_scan_result *res)
                     st.retries++;
                     continue;
                 }
-                c->fz_in_place = false;
+                c->mem.fz_in_place = false;
                 st.no_fused = true;
                 st.fused = false;
-                c->fused_skip = c->fused_backoff;
-                c->fused_backoff = std::min(4 * c->fused_backoff + 3, 1023);
+                c->mem.fused_skip = c->mem.fused_backoff;
+                c->mem.fused_backoff = std::min(4 * c->mem.fused_backoff + 3, 1023);
                 st.index_done = !(c->h_res->fused_bad & (int32_t)FZ_BAD_INDEX);
                 st.retries++;
                 continue;
-            }
-            if (PROBES && getenv("FFQ_DEBUG") && !st.fused) {
-                Fast4Hdr hh;
-                HIPCHK(hipMemcpy(&hh, c->hdr4, sizeof hh, hipMemcpyDeviceToHost));
-                fprintf(stderr, "[ffq debug] fast path refused: dense4 %d attempt %d dense_seen %d j0 %lld irr_min %llu term_min %llu (k %llu tile %llu)\n",
-                        (int)st.dense4, hh.attempt, hh.dense_seen, hh.j0, hh.irr_min, hh.term_min, hh.term_min >> 24, hh.term_min & 0xFFFFFF);
             }
             if (c->h_res->fast4_dense && !st.dense4 && !st.fused && !st.no_fused) {
                 // the row kernel met a DENSE tile (lines under 16 bytes on average: reads of a dozen bases): its DENSE
                 // instantiation takes those -- the same front again from the index that is there, and the context's next
                 // scans start with it
                 st.dense4 = true;
-                c->dense4_remember = true;
+                c->mem.dense4_remember = true;
                 st.retries++;
                 continue;
             }
             // not plain four-line input: the general kernels, from the same line index.  The next
             // scans of this context skip the attempt (and the host round trip it costs here).
             st.fast4_failed = true;
-            c->fast4_remember = true;
-            c->fast4_skip = 15;
-            HIPCHK(hipEventRecord(c->ev[4], sA));
-            int rc = enqueue_general(c, a, L, st.dense_cfg, st.ngroups);
+            c->mem.fast4_remember = true;
+            c->mem.fast4_skip = HOLD_OFF;
+            int rc = run_tier(c, res, [&] { return enqueue_general(c, st, L); });
             if (rc) return rc;
-            HIPCHK(hipEventRecord(c->ev[2], sA));
-            HIPCHK(hipGetLastError());
-            CTX_WAIT_EVENT(c, c->ev[2]);
-            HIPCHK(hipEventElapsedTime(&ms, c->ev[4], c->ev[2]));
-            res->ms_chain += ms; res->ms_total += ms;
             if (c->h_ctl->err & ERR_INTERNAL) return fail(FFQ_E_INTERNAL, "chain kernel invariant failed");
         }
-        if (PROBES && tiers && getenv("FFQ_PROF") && c->prof_d) {
-            unsigned long long hp[16];
-            HIPCHK(hipMemcpy(hp, c->prof_d, 128, hipMemcpyDeviceToHost));
-            if (getenv("FFQ_PROF_LITE"))
-                fprintf(stderr, "[ffq prof] k_chain_lite declined of %d groups: first/last/offset %llu, tile over %d entries / dense look-ahead %llu, no node / too many %llu, "
-                        "a node it does not take on the chain %llu, stage full %llu; runs walked %llu, successors found entry by entry %llu\n", st.ngroups, hp[8], LT_E, hp[9], hp[10], hp[11], hp[12], hp[14], hp[13]);
-            if (hp[6])
-                fprintf(stderr, "[ffq prof] k_chain_wave per-wave cycles: load %.0f lds %.0f nodes %.0f scan %.0f member %.0f summary %.0f (waves %llu)\n",
-                        (double)hp[0] / hp[6], (double)hp[1] / hp[6], (double)hp[2] / hp[6], (double)hp[3] / hp[6],
-                        (double)hp[4] / hp[6], (double)hp[5] / hp[6], hp[6]);
-            if (hp[6])
-                fprintf(stderr, "[ffq prof] generic-path nodes per wave %.2f, serial generic rounds per wave %.2f\n",
-                        (double)(hp[7] & 0xFFFFFFFFull) / hp[6], (double)(hp[7] >> 32) / hp[6]);
-        }
-        if (PROBES && tiers && getenv("FFQ_DEBUG")) {
-            const int ng = std::min(st.ngroups, 24);
-            std::vector<int64_t> y(ng), ex(ng);
-            std::vector<uint32_t> cn(ng), fl(ng);
-            int32_t mins[2];
-            HIPCHK(hipMemcpy(y.data(), c->cb.y, ng * 8, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(ex.data(), c->cb.exit, ng * 8, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(cn.data(), c->cb.cnt, ng * 4, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(fl.data(), c->cb.flags, ng * 4, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(mins, c->cb.mins, 8, hipMemcpyDeviceToHost));
-            fprintf(stderr, "[ffq debug] dense=%d fallback=%d ngroups=%d term=%d bad=%d\n", (int)st.dense_cfg,
-                    c->h_res->fallback, st.ngroups, mins[0], mins[1]);
-            for (int g = 0; g < ng; g++)
-                fprintf(stderr, "[ffq debug]  g=%d y=%lld exit=%lld cnt=%u flags=%u\n", g, (long long)y[g],
-                        (long long)ex[g], cn[g], fl[g]);
-            // ... and the first group the verification rejected, with its neighbours
-            fprintf(stderr, "[ffq debug] n_bad=%d bad_irregular=%d declined=%d\n", c->h_res->n_bad, c->h_res->bad_irregular, c->h_res->n_declined);
-            if (mins[1] >= 0 && mins[1] < st.ngroups) {
-                const int g0 = std::max(mins[1] - 1, 0), g1 = std::min(mins[1] + 2, st.ngroups);
-                for (int g = g0; g < g1; g++) {
-                    int64_t yy, ee; uint32_t cc, ff;
-                    HIPCHK(hipMemcpy(&yy, c->cb.y + g, 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(&ee, c->cb.exit + g, 8, hipMemcpyDeviceToHost));
-                    HIPCHK(hipMemcpy(&cc, c->cb.cnt + g, 4, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(&ff, c->cb.flags + g, 4, hipMemcpyDeviceToHost));
-                    fprintf(stderr, "[ffq debug]  g=%d y=%lld exit=%lld cnt=%u flags=%u\n", g, (long long)yy, (long long)ee, cc, ff);
-                }
-            }
-        }
         int path = 0;
-        if (PROBES && tiers && getenv("FFQ_ABLATE") && atoi(getenv("FFQ_ABLATE")) != 0) {
-            // diagnostics build of the pipeline: results are meaningless, only timings count
-            fill_result(res, *c->h_res, 0, st.retries);
-            return FFQ_OK;
-        }
         // a guess the verification rejected is repaired, not escalated: the rejected groups are
         // re-run from their predecessor's exit and everything is verified again.  Every round
         // makes the first rejected group exact, so the first bad group moves forward; a round
         // that does not move it (a group that does not fit the kernel at all) ends the repairs.
         static const bool no_ranked = getenv("FFQ_NO_RANKED") != nullptr;
-        if (tiers && !(PROBES && getenv("FFQ_ABLATE") && atoi(getenv("FFQ_ABLATE")) != 0) && !getenv("FFQ_NO_REPAIR")) {
+        if (tiers) {
             int prev_bad = -1;
             const int first_bad = c->h_res->bad_group;
             // (a group that does not FIT the kernel -- bad_irregular -- is walked by k_group_walk in
@@ -1399,14 +1342,8 @@ static int scan_finish(ffq_ctx *c, ScanState &st, ffq_scan_result *res)
                 if (round >= 4 && !c->h_res->bad_irregular &&
                     c->h_res->bad_group - first_bad < round * std::max(st.ngroups / 64, 1)) break;
                 prev_bad = c->h_res->bad_group;
-                HIPCHK(hipEventRecord(c->ev[4], sA));
-                int rc = enqueue_repair(c, a, L, st.dense_cfg, st.ngroups);
+                int rc = run_tier(c, res, [&] { return enqueue_repair(c, st, L); });
                 if (rc) return rc;
-                HIPCHK(hipEventRecord(c->ev[2], sA));
-                HIPCHK(hipGetLastError());
-                CTX_WAIT_EVENT(c, c->ev[2]);
-                HIPCHK(hipEventElapsedTime(&ms, c->ev[4], c->ev[2]));
-                res->ms_chain += ms; res->ms_total += ms;
                 st.repairs++;
                 if (c->h_ctl->err & ERR_INTERNAL) return fail(FFQ_E_INTERNAL, "chain kernel invariant failed");
             }
@@ -1420,7 +1357,7 @@ static int scan_finish(ffq_ctx *c, ScanState &st, ffq_scan_result *res)
             // second tier: the same kernels with the LDS budget for short lines / short records
             // (only a group that does not FIT is helped by it; a guess that stays wrong is not)
             st.dense_cfg = true;
-            c->dense_skip = 15;          // and the next scans of this context start there
+            c->mem.dense_skip = HOLD_OFF;    // and the next scans of this context start there
             continue;
         }
         if (st.dense_cfg) path = 2;
@@ -1428,12 +1365,12 @@ static int scan_finish(ffq_ctx *c, ScanState &st, ffq_scan_result *res)
         if (!serial && !no_ranked && (st.go_ranked || c->h_res->fallback)) {
             // the group kernels could not prove a chain (records long against a group): list ranking
             HIPCHK(hipEventRecord(c->ev[4], sA));
-            int rr = run_ranked(c, a, L, st.ntiles, st.go_ranked && !(a.flags & FFQ_F_FORCE_RANKED));
+            int rr = run_ranked(c, a, L, st.ntiles, st.go_ranked && !st.force_ranked);
             if (rr < 0) return rr;
             if (rr == 2) {
-                c->ranked_skip = 0;
-                c->fast4_skip = 0;           // (the input has changed character: what is remembered of it is void)
-                c->fast4_remember = false;
+                c->mem.ranked_skip = 0;
+                c->mem.fast4_skip = 0;           // (the input has changed character: what is remembered of it is void)
+                c->mem.fast4_remember = false;
                 st.go_ranked = false;
                 st.fast4_failed = false;
                 continue;                    // the usual tiers, from the line index that is there
@@ -1452,28 +1389,25 @@ static int scan_finish(ffq_ctx *c, ScanState &st, ffq_scan_result *res)
                 HIPCHK(hipEventElapsedTime(&ms, c->ev[4], c->ev[2]));
                 res->ms_chain += ms; res->ms_total += ms;
                 path = 5;
-                if (!(a.flags & FFQ_F_FORCE_RANKED)) c->ranked_skip = 15;     // and the next scans of this context start there
+                if (!st.force_ranked) c->mem.ranked_skip = HOLD_OFF;     // and the next scans of this context start there
             }
         } else if (st.go_ranked) walk = true;
         if (walk) {
             path = 1;
-            HIPCHK(hipEventRecord(c->ev[4], sA));
-            int64_t *const sq = st.wide ? (int64_t *)nullptr : qoff;       // (wide: the offsets from the finished table, below)
-            hipLaunchKernelGGL(k_chain_serial, dim3(1), dim3(64), 0, sA, L, a.offset, a.eof, a.add, a.d_table,
-                               a.table_cap, sq, c->qdir, c->qdir_cap, sq ? c->p4s : (int64_t *)nullptr,
-                               sq ? std::min<int64_t>(a.table_cap, c->p4s_cap) : (int64_t)0, c->dres);
-            hipLaunchKernelGGL(k_finalize_serial, dim3(1), dim3(64), 0, sA, c->dres, a.table_cap, sq, (decode && st.wide) ? no_pub(c) : make_pub(c));
-            c->ctl_clean = true;
-            if (decode && st.wide) hipLaunchKernelGGL(k_qoff_in_place, dim3(256), dim3(256), 0, sA, c->dres, (const int64_t *)a.d_table, a.table_cap, a.add, a.s, a.d_qoff, make_pub(c));
-            else if (decode) enqueue_decode(c, a, sA);
-            HIPCHK(hipEventRecord(c->ev[2], sA));
-            HIPCHK(hipGetLastError());
-            CTX_WAIT_EVENT(c, c->ev[2]);
-            HIPCHK(hipEventElapsedTime(&ms, c->ev[4], c->ev[2]));
-            res->ms_chain += ms;
-            res->ms_total += ms;
+            int rc = run_tier(c, res, [&] {
+                int64_t *const sq = st.wide ? (int64_t *)nullptr : qoff;       // (wide: the offsets from the finished table, below)
+                hipLaunchKernelGGL(k_chain_serial, dim3(1), dim3(64), 0, sA, L, a.offset, a.eof, a.add, a.d_table,
+                                   a.table_cap, sq, c->qdir, c->qdir_cap, sq ? c->p4s : (int64_t *)nullptr,
+                                   sq ? std::min<int64_t>(a.table_cap, c->p4s_cap) : (int64_t)0, c->dres);
+                hipLaunchKernelGGL(k_finalize_serial, dim3(1), dim3(64), 0, sA, c->dres, a.table_cap, sq, (decode && st.wide) ? no_pub(c) : make_pub(c));
+                c->ctl_clean = true;
+                if (decode && st.wide) hipLaunchKernelGGL(k_qoff_in_place, dim3(256), dim3(256), 0, sA, c->dres, (const int64_t *)a.d_table, a.table_cap, a.add, a.s, a.d_qoff, make_pub(c));
+                else if (decode) enqueue_decode(c, a, sA);
+                return FFQ_OK;
+            });
+            if (rc) return rc;
         }
-        if (tiers && c->lite_ran && (int64_t)c->h_res->n_declined * 4 > (int64_t)st.ngroups) c->lite_skip = 15;
+        if (tiers && st.lite_ran && (int64_t)c->h_res->n_declined * 4 > (int64_t)st.ngroups) c->mem.lite_skip = HOLD_OFF;
         fill_result(res, *c->h_res, path | ((decode && st.wide) ? FFQ_PATH_IN_PLACE : 0), st.retries + st.repairs);
         break;
     }
@@ -1516,6 +1450,13 @@ extern "C" int ffq_scan_submit(ffq_ctx *c, const uint8_t *d_buf, int64_t n_bytes
     st = ScanState{};
     st.a = ScanArgs{d_buf, n_bytes, sentinel ? 1 : 0, offset, eof, add, flags, qual_add, d_table, table_cap,
                     d_qual, qual_cap, d_qoff};
+    st.serial = (flags & FFQ_F_FORCE_SERIAL) != 0;
+    st.decode = decode;
+    st.single_pass = (flags & FFQ_F_SINGLE_PASS) != 0;
+    st.force_ranked = (flags & FFQ_F_FORCE_RANKED) != 0;
+    st.force_general = (flags & FFQ_F_FORCE_GENERAL) != 0;
+    st.poll_result = (flags & FFQ_F_POLL_RESULT) != 0;
+    st.no_timing = (flags & FFQ_F_NO_TIMING) != 0;
     st.ntiles = tiles_for(n_bytes);
     st.active = true;
     if (st.ntiles == 0) return FFQ_OK;                   // nothing to enqueue: ffq_scan_wait fills the result
@@ -1543,7 +1484,7 @@ extern "C" int ffq_scan_wait(ffq_ctx *c, ffq_scan_result *res)
         res->last_status = FFQ_POS_HEAD_BEG;
         res->end_offset = st.a.offset;
         for (int i = 0; i < 6; i++) res->last_pos[i] = -1;
-        if ((st.a.flags & FFQ_F_DECODE_QUAL) != 0) {
+        if (st.decode) {
             HIPCHK(hipMemsetAsync(st.a.d_qoff, 0, sizeof(int64_t), c->stream));
             CTX_SYNC(c);
         }
@@ -1993,7 +1934,7 @@ extern "C" int ffq_table_gather_column(ffq_ctx *c, const uint8_t *d_buf, int64_t
     if (out_cap > 0)
         hipLaunchKernelGGL(k_decode_stream, dim3((unsigned)nqb), dim3(256), 0, st, d_buf, n_bytes, sentinel ? 1 : 0,
                            (const int64_t *)c->p4s, (const int64_t *)d_off, (const int64_t *)c->qdir,
-                           (const DevRes *)c->col_res, n_rows, add, value_add, d_out, out_cap, 0);
+                           (const DevRes *)c->col_res, n_rows, add, value_add, d_out, out_cap);
     HIPCHK(hipMemcpyAsync(c->h_word, &c->col_res->n_qual_bytes, sizeof(int64_t), hipMemcpyDeviceToHost, st));
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
@@ -2098,161 +2039,28 @@ extern "C" int ffq_synth_wrapped(ffq_ctx *c, uint8_t *d_out, const int64_t *d_st
 }
 
 #ifdef FFQ_PROBES
-// ---- probes: only in the instrumented build, libffq_probe.so (include/ffq_probe.h; tools/) ----------
+// ---- probes: only in the instrumented build, libffq_probe.so (include/ffq_probe.h) ----------------------------------
+// mode 6: the streaming-read ceiling of the device in the scan kernel's launch geometry with its non-temporal loads
+// (k_read_probe), average ms over `reps` launches; every other mode is refused
 extern "C" int ffq_read_probe(ffq_ctx *c, const uint8_t *d_buf, int64_t n_bytes, int mode, int reps, float *ms_avg)
 {
     mark_other(c);
     if (!c || !d_buf || !ms_avg || n_bytes < TILE || reps < 1) return fail(FFQ_E_ARG, "ffq_read_probe: bad argument");
+    if (mode != 6) return fail(FFQ_E_ARG, "ffq_read_probe: mode %d does not exist (6: the non-temporal read)", mode);
     HIPCHK(hipSetDevice(c->device));
     const int64_t ntiles = n_bytes >> TILE_SHIFT;
     uint32_t *sink = reinterpret_cast<uint32_t *>(c->ctl);
-    ScanArgs a{};
-    a.d_buf = d_buf; a.n_bytes = ntiles << TILE_SHIFT; a.s = 1;
-    if (mode == 2) {
-        // the index kernel alone, back to back: its steady-state time without the rest of a step
-        int rc = reserve_tiles(c, ntiles);
-        if (rc) return rc;
-        rc = reserve_pool(c, POOL_MIN);
-        if (rc) return rc;
-    }
-    const LineIndex L = make_index(c, a, ntiles);
-    if (mode >= 200 && mode < 220) {
-        // the persistent streaming loop with a lagged two-level prefix (k_pipe_probe): lag = mode - 200
-        int rc = reserve_tiles(c, ntiles);
-        if (rc) return rc;
-        rc = reserve_pool(c, POOL_MIN);
-        if (rc) return rc;
-        const bool big = mode >= 210;                  // 72 KiB of LDS per workgroup, two per CU
-        const int G = big ? 512 : 1024, lag = big ? mode - 210 : mode - 200;
-        const int64_t niter = (ntiles + G - 1) / G;
-        PipeArgs pa{};
-        pa.d = d_buf; pa.ntiles = ntiles; pa.lag = lag;
-        HIPCHK(hipMalloc((void **)&pa.descA, (size_t)niter * G * 8));
-        HIPCHK(hipMalloc((void **)&pa.descG, (size_t)niter * (G / PP_GROUP) * 8));
-        HIPCHK(hipMalloc((void **)&pa.prefix, (size_t)niter * G * 8));
-        HIPCHK(hipMalloc((void **)&pa.err, 8));
-        // the tile counts to check the prefixes against
-        launch_scan_lines(c, c->stream, a.d_buf, a.n_bytes, ntiles, L, (uint32_t)'@', 0);
-        float sum = 0;
-        for (int r = 0; r < reps + 2; r++) {
-            HIPCHK(hipMemsetAsync(pa.descA, 0, (size_t)niter * G * 8, c->stream));
-            HIPCHK(hipMemsetAsync(pa.descG, 0, (size_t)niter * (G / PP_GROUP) * 8, c->stream));
-            HIPCHK(hipMemsetAsync(pa.err, 0, 8, c->stream));
-            HIPCHK(hipEventRecord(c->ev[0], c->stream));
-            if (big) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pipe_probe<72>), dim3(G), dim3(256), 0, c->stream, pa, sink);
-            else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pipe_probe<36>), dim3(G), dim3(256), 0, c->stream, pa, sink);
-            HIPCHK(hipEventRecord(c->ev[1], c->stream));
-            HIPCHK(hipEventSynchronize(c->ev[1]));
-            float ms = 0;
-            HIPCHK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-            if (r >= 2) sum += ms;
-        }
-        *ms_avg = sum / reps;
-        int bad = 0;
-        uint32_t herr2[2] = {0, 0};
-        HIPCHK(hipMemcpy(herr2, pa.err, 8, hipMemcpyDeviceToHost));
-        const uint32_t herr = herr2[0];
-        if (lag) {
-            std::vector<uint32_t> hc((size_t)ntiles);
-            std::vector<long long> hp((size_t)ntiles);
-            HIPCHK(hipMemcpy(hc.data(), c->cnt, (size_t)ntiles * 4, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(hp.data(), pa.prefix, (size_t)ntiles * 8, hipMemcpyDeviceToHost));
-            long long run = 0;
-            for (int64_t t = 0; t < ntiles; t++) { if (hp[(size_t)t] != run) bad++; run += hc[(size_t)t]; }
-        }
-        (void)hipFree(pa.descA); (void)hipFree(pa.descG); (void)hipFree(pa.prefix); (void)hipFree(pa.err);
-        HIPCHK(hipMemsetAsync(c->ctl, 0, sizeof(Ctl), c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (herr || bad) return fail(FFQ_E_INTERNAL, "pipe probe: %d wrong prefixes, poll gave up: %u", bad, herr);
-        return FFQ_OK;
-    }
-    if (mode == 7 || mode >= 100) {
-        // the index kernel with a decoupled look-back over the tile counts riding along (a probe:
-        // what a single-pass design would pay for its prefix sums on this part)
-        int rc = reserve_tiles(c, ntiles);
-        if (rc) return rc;
-        rc = reserve_pool(c, POOL_MIN);
-        if (rc) return rc;
-        float sum = 0;
-        for (int r = 0; r < reps + 2; r++) {
-            HIPCHK(hipMemsetAsync(c->ovf, 0, (size_t)ntiles * 8, c->stream));
-            HIPCHK(hipEventRecord(c->ev[0], c->stream));
-            launch_scan_lines(c, c->stream, a.d_buf, a.n_bytes, ntiles, L, (uint32_t)'@', mode == 7 ? 8 : mode);
-            HIPCHK(hipEventRecord(c->ev[1], c->stream));
-            HIPCHK(hipEventSynchronize(c->ev[1]));
-            float ms = 0;
-            HIPCHK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-            if (r >= 2) sum += ms;
-        }
-        *ms_avg = sum / reps;
-        std::vector<uint32_t> hc((size_t)ntiles);
-        HIPCHK(hipMemcpy(hc.data(), c->cnt, (size_t)ntiles * 4, hipMemcpyDeviceToHost));
-        std::vector<unsigned long long> hd((size_t)ntiles);
-        HIPCHK(hipMemcpy(hd.data(), c->ovf, (size_t)ntiles * 8, hipMemcpyDeviceToHost));
-        const int variant = mode >= 100 ? ((mode - 100) >> 5) & 7 : 0;
-        if (mode >= 100) {
-            // rounds / retries of the look-backs, as the inclusive descriptors carry them
-            const int64_t nd = variant == 3 ? ntiles >> 2 : ntiles;
-            double rounds = 0, retries = 0;
-            for (int64_t t = 1; t < nd; t++) { rounds += (double)((hd[(size_t)t] >> 40) & 0xFF); retries += (double)((hd[(size_t)t] >> 48) & 0x3FFF); }
-            fprintf(stderr, "[ffq probe] mode %d: %.2f rounds, %.2f retries per look-back\n", mode, rounds / std::max<int64_t>(nd - 1, 1),
-                    retries / std::max<int64_t>(nd - 1, 1));
-        }
-        if (variant == 0 || variant == 4) {
-            const unsigned long long VM = mode >= 100 ? (1ull << 40) - 1ull : (1ull << 62) - 1ull;
-            unsigned long long tot = 0, totm = 0;
-            for (int64_t t = 0; t < ntiles; t++) { tot += hc[(size_t)t]; if (t <= ntiles / 2) totm += hc[(size_t)t]; }
-            const unsigned long long last = hd[(size_t)(ntiles - 1)], mid = hd[(size_t)(ntiles / 2)];
-            if ((last & VM) != tot || (mid & VM) != totm || (last >> 62) != 2)
-                return fail(FFQ_E_INTERNAL, "look-back probe: prefix %llu / %llu, expected %llu / %llu", (last & VM), (mid & VM), tot, totm);
-        }
-        HIPCHK(hipMemsetAsync(c->ctl, 0, sizeof(Ctl), c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        return FFQ_OK;
-    }
-    if (mode == 3 || mode == 4 || mode == 8) {
-        // (mode 4: the variant for a buffer whose last tile is ragged; mode 8: non-temporal entry stores)
-        if (mode == 4) a.n_bytes -= 5;
-        // mode 2's kernel, every launch between its own pair of events (as a scan times it)
-        int rc = reserve_tiles(c, ntiles);
-        if (rc) return rc;
-        rc = reserve_pool(c, POOL_MIN);
-        if (rc) return rc;
-        float sum = 0;
-        for (int r = 0; r < reps + 2; r++) {
-            HIPCHK(hipEventRecord(c->ev[0], c->stream));
-            launch_scan_lines(c, c->stream, a.d_buf, a.n_bytes, ntiles, L, (uint32_t)'@', mode == 8 ? 9 : 0);
-            HIPCHK(hipEventRecord(c->ev[1], c->stream));
-            HIPCHK(hipEventSynchronize(c->ev[1]));
-            float ms = 0;
-            HIPCHK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-            if (r >= 2) sum += ms;
-        }
-        *ms_avg = sum / reps;
-        HIPCHK(hipMemsetAsync(c->ctl, 0, sizeof(Ctl), c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        return FFQ_OK;
-    }
     for (int r = 0; r < reps + 2; r++) {
         if (r == 2) HIPCHK(hipEventRecord(c->ev[0], c->stream));
-        if (mode == 2)
-            launch_scan_lines(c, c->stream, a.d_buf, a.n_bytes, ntiles, L, (uint32_t)'@');
-        else if (mode == 6)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_read_probe<2>), dim3((unsigned)ntiles), dim3(256), 0, c->stream, d_buf, ntiles, sink);
-        else if (mode == 0)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_read_probe<0>), dim3((unsigned)ntiles), dim3(256), 0, c->stream, d_buf, ntiles, sink);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_read_probe<1>), dim3(256 * 8), dim3(256), 0, c->stream, d_buf, ntiles, sink);
+        hipLaunchKernelGGL(k_read_probe, dim3((unsigned)ntiles), dim3(256), 0, c->stream, d_buf, sink);
     }
     HIPCHK(hipEventRecord(c->ev[1], c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
     *ms_avg = ms / reps;
-    if (mode == 2) { HIPCHK(hipMemsetAsync(c->ctl, 0, sizeof(Ctl), c->stream)); HIPCHK(hipStreamSynchronize(c->stream)); }
     return FFQ_OK;
 }
-
 #endif  // FFQ_PROBES
 
 // ---- diagnostics ---------------------------------------------------------------------

@@ -77,17 +77,16 @@ __device__ __forceinline__ void scan_tile_store(ScanLds &sm, const int tile, con
                                                 const bool pool_ok, const uint32_t dense_any, const uint32_t nxt,
                                                 uint16_t *__restrict__ ent, uint32_t *__restrict__ cnt,
                                                 unsigned long long *__restrict__ ovf, uint16_t *__restrict__ pool,
-                                                int ablate, uint32_t at_char)
+                                                uint32_t at_char)
 {
     uint8_t *const s_data = sm.data;
     uint16_t *const s_list = sm.list;
     const int tid = threadIdx.x, l = tid & 63;
-    if (tid == 0 && !(PROBES && ablate == 7)) {
+    if (tid == 0) {
         // no atomics here: an agent-scope atomic of 64 tiles on one address costs more than the
         // whole scan (measured: +45 us per GiB); the per-superblock sums are a kernel of their own
         cnt[tile] = total;
     }
-    if (PROBES && (ablate == 6 || ablate == 7)) return;
     // Each wave stores its own entries, flags looked up on the way, and is done: no second
     // workgroup barrier, no wave waits for another one's store (a workgroup-wide copy of the
     // finished list cost 20 us per GiB in barrier + tail latency).
@@ -100,8 +99,7 @@ __device__ __forceinline__ void scan_tile_store(ScanLds &sm, const int tile, con
             const uint32_t off = (uint32_t)s_list[wbase + j];
             const uint32_t e = off | (entry_flags(s_data, off, nxt, at_char) << 14);
             // written once, read by the row / chain kernels from HBM later: non-temporal (-4...10 us per GiB)
-            if (PROBES && ablate == 9) const_cast<uint16_t *>(gdst)[wbase + j] = (uint16_t)e;
-            else asm volatile("global_store_short %0, %1, %2 nt" : : "v"((wbase + j) * 2u), "v"(e), "s"(gdst) : "memory");
+            asm volatile("global_store_short %0, %1, %2 nt" : : "v"((wbase + j) * 2u), "v"(e), "s"(gdst) : "memory");
         }
     } else {
         // (a dense tile's entries went to the pool with their flags, straight from the compaction loop: dense_any)
@@ -121,13 +119,12 @@ __device__ __forceinline__ void scan_tile_rest(ScanLds &sm, const int tile, cons
                                                const uint32_t (&o)[4], const uint32_t nxt,
                                                uint16_t *__restrict__ ent, uint32_t *__restrict__ cnt,
                                                unsigned long long *__restrict__ ovf, uint16_t *__restrict__ pool,
-                                               unsigned long long pool_cap, Ctl *ctl, int ablate, uint32_t at_char)
+                                               unsigned long long pool_cap, Ctl *ctl, uint32_t at_char)
 {
     uint16_t *const s_list = sm.list;
     uint32_t *const s_wtot = sm.wtot;
     unsigned long long &s_ovf = sm.ovf;
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
-    if (PROBES && ablate == 3) { if ((c[0] + c[1] + c[2] + c[3]) == 77u) cnt[tile] = 1; return; }
     // wave prefix sums of the four row counts, two 16-bit fields per register
     const uint32_t s01 = wave_incl_scan(c[0] | (c[1] << 16));
     const uint32_t s23 = wave_incl_scan(c[2] | (c[3] << 16));
@@ -147,103 +144,6 @@ __device__ __forceinline__ void scan_tile_rest(ScanLds &sm, const int tile, cons
         if (q < w) wbase += t;
         total += t;
     }
-    if (PROBES && ablate == 5) { if (total + wbase == 0x7777u) cnt[tile] = 1; return; }
-#ifdef FFQ_PROBES
-    if (ablate == 8 && w == 0) {
-        // PROBE (ffq_read_probe mode 7): what a decoupled look-back over the tiles' newline counts
-        // costs on this part -- descriptors flag << 62 | value in ovf[] (zeroed before the launch),
-        // relaxed agent-scope loads / stores, no read-modify-write, no fence
-        unsigned long long *desc = ovf;
-        const unsigned long long VM = (1ull << 62) - 1ull;
-        if (tile == 0) {
-            if (l == 0) __hip_atomic_store(desc, (2ull << 62) | (unsigned long long)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-            if (l == 0) __hip_atomic_store(desc + tile, (1ull << 62) | (unsigned long long)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            unsigned long long excl = 0;
-            int64_t pos = tile - 1;
-            for (;;) {
-                const int64_t idx = pos - l;
-                const unsigned long long v = idx >= 0 ? __hip_atomic_load(desc + idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : (2ull << 62);
-                const int fl = (int)(v >> 62);
-                const unsigned long long inv = __ballot(fl == 0), inc = __ballot(fl == 2);
-                const int first_inc = inc ? __ffsll((long long)inc) - 1 : 64;
-                const int first_inv = inv ? __ffsll((long long)inv) - 1 : 64;
-                if (first_inv < first_inc) { __builtin_amdgcn_s_sleep(1); continue; }      // a descriptor in between is not there yet
-                const unsigned long long val = (l <= first_inc) ? (v & VM) : 0ull;
-                excl += (unsigned long long)(uint32_t)__shfl((int)wave_incl_scan((uint32_t)(val & 0xFFFFFu)), 63) +
-                        ((unsigned long long)(uint32_t)__shfl((int)wave_incl_scan((uint32_t)(val >> 20)), 63) << 20);
-                if (first_inc < 64) break;
-                pos -= 64;
-            }
-            if (l == 0) __hip_atomic_store(desc + tile, (2ull << 62) | (excl + total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    if (ablate >= 100) {
-        // PROBE (ffq_read_probe modes 100 + K + 16 * barrier + 32 * variant; tools/lookback_probe.py): the
-        // same look-back with a window of 64 * K descriptors per round trip (lane l reads the descriptors
-        // at distance l + 64 k, K loads in flight), optionally with the other waves waiting behind a barrier.
-        // variant 1: the two stores only; 2: stores + ONE window load, nothing waited for; 3: only every 4th
-        // tile takes part (descriptor tile >> 2: the traffic of 64 KiB super-tiles); 4: longer sleeps between
-        // polls; 6: variant 2 with plain cached loads; 7: variant 2 with sc0 loads (coherent in this XCD's L2
-        // only).  The inclusive descriptor carries the rounds (bits 40..47) and retries (48..61) of its look-back.
-        const int K = (ablate - 100) & 15, variant = ((ablate - 100) >> 5) & 7;
-        const bool part = variant != 3 || (tile & 3) == 3;
-        if (w == 0 && part) {
-            unsigned long long *desc = ovf;
-            const int64_t me = variant == 3 ? (tile >> 2) : tile;
-            const unsigned long long VM = (1ull << 40) - 1ull;
-            const bool waits = variant == 0 || variant == 3 || variant == 4;
-            if (me == 0) {
-                if (l == 0) __hip_atomic_store(desc, (2ull << 62) | (unsigned long long)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            } else {
-                if (l == 0) __hip_atomic_store(desc + me, (1ull << 62) | (unsigned long long)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                unsigned long long excl = 0, rounds = 0, retries = 0;
-                int64_t pos = me - 1;
-                if (variant != 1)
-                for (;;) {
-                    unsigned long long vv[8];
-#pragma unroll
-                    for (int k = 0; k < 8; k++) {
-                        const int64_t idx = pos - l - 64 * k;
-                        if (variant == 6) vv[k] = (k < K && idx >= 0) ? desc[idx] : 0ull;
-                        else if (variant == 7) {
-                            unsigned long long x = 0;
-                            if (k < K && idx >= 0) asm volatile("global_load_dwordx2 %0, %1, off sc0\n\ts_waitcnt vmcnt(0)" : "=v"(x) : "v"(desc + idx) : "memory");
-                            vv[k] = x;
-                        }
-                        else vv[k] = (k < K) ? (idx >= 0 ? __hip_atomic_load(desc + idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : (2ull << 62)) : 0ull;
-                    }
-                    rounds++;
-                    unsigned long long add = 0;
-                    bool retry = false, done = false;
-#pragma unroll
-                    for (int k = 0; k < 8; k++) {
-                        if (k < K && !retry && !done) {
-                            const int fl = (int)(vv[k] >> 62);
-                            const unsigned long long inv = __ballot(fl == 0), inc = __ballot(fl == 2);
-                            const int first_inc = inc ? __ffsll((long long)inc) - 1 : 64;
-                            const int first_inv = inv ? __ffsll((long long)inv) - 1 : 64;
-                            if (first_inv < first_inc && waits) retry = true;
-                            else {
-                                const unsigned long long val = (l <= first_inc) ? (vv[k] & VM) : 0ull;
-                                add += (unsigned long long)(uint32_t)__shfl((int)wave_incl_scan((uint32_t)(val & 0xFFFFFu)), 63) +
-                                       ((unsigned long long)(uint32_t)__shfl((int)wave_incl_scan((uint32_t)(val >> 20)), 63) << 20);
-                                if (first_inc < 64) done = true;
-                            }
-                        }
-                    }
-                    if (retry) { retries++; if (variant == 4) __builtin_amdgcn_s_sleep(16); else __builtin_amdgcn_s_sleep(1); continue; }
-                    excl += add;
-                    if (done || !waits) break;
-                    pos -= 64 * K;
-                }
-                if (l == 0) __hip_atomic_store(desc + me, (2ull << 62) | ((excl + total) & VM) | (min(rounds, 255ull) << 40) | (min(retries, 16383ull) << 48),
-                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-        if ((ablate - 100) & 16) __syncthreads();
-    }
-#endif
     const bool dense = total > (uint32_t)SLOT;
     if (dense) {   // rare: avg line shorter than 16 bytes over the whole tile
         if (tid == 0) {
@@ -286,7 +186,7 @@ __device__ __forceinline__ void scan_tile_rest(ScanLds &sm, const int tile, cons
         }
         rb += rowtot[i];
     }
-    scan_tile_store(sm, tile, wbase, wtot, total, dense, pbase, pool_ok, dense_any, nxt, ent, cnt, ovf, pool, ablate, at_char);
+    scan_tile_store(sm, tile, wbase, wtot, total, dense, pbase, pool_ok, dense_any, nxt, ent, cnt, ovf, pool, at_char);
 }
 
 // WIDE (round 6): the same pass also writes EVERY byte decoded -- out[p] = d[p] + qadd (int8 arithmetic) at the offset the
@@ -300,7 +200,7 @@ template <bool FULL, bool WIDE = false>
 __device__ __forceinline__ void scan_tile(ScanLds &sm, const int tile, const uint8_t *__restrict__ d, int64_t n,
                                           uint16_t *__restrict__ ent, uint32_t *__restrict__ cnt,
                                           unsigned long long *__restrict__ ovf, uint16_t *__restrict__ pool,
-                                          unsigned long long pool_cap, Ctl *ctl, int ablate, uint32_t at_char,
+                                          unsigned long long pool_cap, Ctl *ctl, uint32_t at_char,
                                           int8_t *__restrict__ wout = nullptr, uint32_t wadd = 0)
 {
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
@@ -343,7 +243,7 @@ __device__ __forceinline__ void scan_tile(ScanLds &sm, const int tile, const uin
             __builtin_nontemporal_store(t, reinterpret_cast<u32x4 *>(wout + base + o[i]));
         }
     }
-    scan_tile_rest(sm, tile, m, c, o, nxt, ent, cnt, ovf, pool, pool_cap, ctl, ablate, at_char);
+    scan_tile_rest(sm, tile, m, c, o, nxt, ent, cnt, ovf, pool, pool_cap, ctl, at_char);
 }
 
 // The launch: workgroup b takes whole tile tile0 + b.  Only the last tile of a buffer can be
@@ -358,15 +258,15 @@ __global__ __launch_bounds__(256, MINW) void k_scan_lines(const uint8_t *__restr
                                                     unsigned long long *__restrict__ ovf,
                                                     uint16_t *__restrict__ pool,
                                                     unsigned long long pool_cap, Ctl *ctl, int tile0,
-                                                    int ablate, LineIndex Lval, LineIndex *__restrict__ d_L,
+                                                    LineIndex Lval, LineIndex *__restrict__ d_L,
                                                     uint32_t at_char, int ragged_tile, int8_t *__restrict__ wout, uint32_t wadd)
 {
     __shared__ ScanLds sm;
-    if (WHOLE) scan_tile<true, WIDE>(sm, tile0 + (int)blockIdx.x, d, n, ent, cnt, ovf, pool, pool_cap, ctl, ablate, at_char, wout, wadd);
+    if (WHOLE) scan_tile<true, WIDE>(sm, tile0 + (int)blockIdx.x, d, n, ent, cnt, ovf, pool, pool_cap, ctl, at_char, wout, wadd);
     if (blockIdx.x == 0) {
         if (ragged_tile >= 0) {
             if (WHOLE) __syncthreads();
-            scan_tile<false, WIDE>(sm, ragged_tile, d, n, ent, cnt, ovf, pool, pool_cap, ctl, ablate, at_char, wout, wadd);
+            scan_tile<false, WIDE>(sm, ragged_tile, d, n, ent, cnt, ovf, pool, pool_cap, ctl, at_char, wout, wadd);
         }
         // the device copy of the index descriptor (out-of-line device functions take it by pointer)
         if (threadIdx.x == 0 && d_L) *d_L = Lval;
@@ -594,7 +494,7 @@ __global__ __launch_bounds__(256) void k_decode_stream(const uint8_t *__restrict
                                                        const int64_t *__restrict__ qdir,
                                                        const DevRes *__restrict__ res,
                                                        int64_t table_cap, int64_t add, int qadd,
-                                                       int8_t *__restrict__ out, int64_t out_cap, int ablate)
+                                                       int8_t *__restrict__ out, int64_t out_cap)
 {
     __shared__ int32_t s_q[DQ_REC];               // stream offset of cached record i, relative to ob
     __shared__ int64_t s_adj[DQ_REC];             // buffer offset of the byte decoded to stream offset ob
@@ -667,7 +567,7 @@ __global__ __launch_bounds__(256) void k_decode_stream(const uint8_t *__restrict
 #pragma unroll
             for (int j = 0; j < DQ_PER; j++) {
                 xa[j] = xb[j] = make_uint4(0, 0, 0, 0);
-                if (ci[j] < 0 || (PROBES && (ablate & 4))) continue;
+                if (ci[j] < 0) continue;
                 const int clo = 16 * (k0 + j * 256 + tid) - shiftA;
                 xa[j] = load16_any(d, nbytes, s_adj[ci[j]] + clo);
                 if (h1[j] > h0[j]) xb[j] = load16_any(d, nbytes, s_adj[ci[j] + 1] + clo);
@@ -694,8 +594,7 @@ __global__ __launch_bounds__(256) void k_decode_stream(const uint8_t *__restrict
                 }
 #pragma unroll
                 for (int w = 0; w < 4; w++) y[w] = addb4(y[w], vv);
-                if (PROBES && (ablate & 2)) { if (y[0] == 0x12345678u && y[1] == 77u) outb[0] = 1; }
-                else if (vhi - vlo == 16) {
+                if (vhi - vlo == 16) {
                     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
                     u32x4 t; t.x = y[0]; t.y = y[1]; t.z = y[2]; t.w = y[3];
                     __builtin_nontemporal_store(t, reinterpret_cast<u32x4 *>(outb + clo));      // write-once stream
@@ -1257,162 +1156,25 @@ __global__ __launch_bounds__(256) void k_synth_wrapped(uint8_t *__restrict__ out
 
 #ifdef FFQ_PROBES
 // =========================================================================
-// k_pipe_probe (ffq_read_probe modes 200 + lag; tools/pipe_probe.py): what a single-pass design would have to
-// be built on -- PERSISTENT workgroups that keep streaming tiles (workgroup b takes tiles b, b + G, b + 2G, ...;
-// the next tile's loads are issued before this one is counted) while the prefix over all earlier tiles is
-// resolved `lag` iterations later from a two-level tree of descriptors: every workgroup publishes its
-// tile's count, the last workgroup of each group of 32 sums its group's counts one iteration later, and
-// `lag` iterations later every workgroup reads the 32 group sums and the counts of its own group in ONE
-// round trip and carries the running base itself.  Nothing is decoded: the question is what the prefix
-// costs when no tile waits for it with its loads still to come.  LDS is allocated as the real thing would
-// (four workgroups per CU).  lag 0: no prefix at all (the streaming loop alone).
+// k_read_probe (instrumented build only): pure streaming read in the launch geometry of k_scan_lines -- one 16 KiB
+// tile per 256-thread workgroup, four 16-byte non-temporal loads per lane, as the scan kernel loads its tiles.
+// The measured ceiling the scan kernel is compared with (bench.py's hbm_read_probe).
 // =========================================================================
-constexpr int PP_GROUP = 32;
-struct PipeArgs {
-    const uint8_t *d;
-    int64_t ntiles;
-    unsigned long long *descA;      // [niter * G] flag << 62 | newlines of the tile
-    unsigned long long *descG;      // [niter * G / 32] flag << 62 | newlines of the group
-    long long *prefix;              // [niter * G] out: newlines in front of the tile
-    uint32_t *err;                  // set when a poll gave up
-    int lag;
-};
-
-__device__ __forceinline__ unsigned long long pp_poll(const unsigned long long *p, bool need, uint32_t *err)
-{
-    unsigned long long v = need ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : (1ull << 62);
-    for (int spins = 0; __ballot((v >> 62) == 0ull) != 0ull; spins++) {
-        if (spins > (1 << 18)) { if ((threadIdx.x & 63) == 0) atomicOr(err, 1u); break; }      // never hang the GPU
-        __builtin_amdgcn_s_sleep(2);
-        if ((v >> 62) == 0ull) v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    return v & ((1ull << 62) - 1ull);
-}
-
-// KIB: LDS per workgroup (36: four workgroups per CU, 72: two); the tile is parked in one of KIB / 16 slots
-template <int KIB>
-__global__ __launch_bounds__(256) void k_pipe_probe(PipeArgs a, uint32_t *__restrict__ sink)
-{
-    __shared__ __attribute__((aligned(16))) uint8_t s_pad[KIB * 1024];      // the residency of the real thing
-    __shared__ uint32_t s_w[2][4];
-    const int G = (int)gridDim.x, b = (int)blockIdx.x, tid = threadIdx.x, w = tid >> 6, l = tid & 63;
-    const int ngroups = G / PP_GROUP, g = b / PP_GROUP, bi = b % PP_GROUP;
-    const int64_t niter = (a.ntiles + G - 1) / G;
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    u32x4 cur[4], nxt[4];
-    auto issue = [&](u32x4 (&v)[4], int64_t t) {
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            v[i] = u32x4{0, 0, 0, 0};
-            if (t < a.ntiles)
-                v[i] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(a.d + (t << TILE_SHIFT) + w * 4096 + i * 1024 + l * 16));
-        }
-    };
-    issue(cur, b);
-    long long base = 0;
-    uint32_t acc = 0;
-    if (tid == 0) s_pad[b & 1023] = 1;
-    const int lag = a.lag;
-    for (int64_t it = 0; it < niter + lag; it++) {
-        const int64_t T = it * G + b;
-        // the descriptor loads FIRST, the next tile's loads behind them: loads return in order, and a
-        // wait for the descriptors must not be a wait for 16 KiB of tile (with the order reversed the
-        // loop ran at half speed: one tile in flight per workgroup instead of two)
-        bool lead = a.lag && w == 0 && bi == PP_GROUP - 1 && it >= 1 && it - 1 < niter;
-        bool res = a.lag && w == 0 && it >= lag && it - lag < niter;
-        int64_t j = it - lag;
-        const bool isg = l < 32;
-        const unsigned long long *pl = a.descA + (it - 1) * G + g * PP_GROUP + (l & 31);
-        const unsigned long long *pr = isg ? a.descG + j * ngroups + min(l, ngroups - 1) : a.descA + j * G + g * PP_GROUP + (l - 32);
-        const bool needr = isg ? (l < ngroups) : (l - 32 < bi);
-        unsigned long long vl = 1ull << 62, vr = 1ull << 62;
-        if (lead && l < PP_GROUP) vl = __hip_atomic_load(pl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (res && needr) vr = __hip_atomic_load(pr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (it + 1 < niter) issue(nxt, T + G);
-        if (it < niter) {
-            uint32_t c = 0;
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                c += (uint32_t)__popc(nl_mask16(make_uint4(cur[i].x, cur[i].y, cur[i].z, cur[i].w)));
-                *reinterpret_cast<u32x4 *>(s_pad + (it % (KIB / 16)) * TILE + w * 4096 + i * 1024 + l * 16) = cur[i];      // parked, as the real thing would
-            }
-            const uint32_t ws = (uint32_t)__shfl((int)wave_incl_scan(c), 63);
-            if (l == 0) s_w[it & 1][w] = ws;
-            __syncthreads();
-            const uint32_t total = s_w[it & 1][0] + s_w[it & 1][1] + s_w[it & 1][2] + s_w[it & 1][3];
-            acc += total;
-            if (a.lag && tid == 0)
-                __hip_atomic_store(a.descA + T, (1ull << 62) | (unsigned long long)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        const int64_t lit = it;
-        if (lead) {
-            // the last workgroup of a group: that group's sum of the iteration before
-            pl = a.descA + (lit - 1) * G + g * PP_GROUP + (l & 31);
-            if (__ballot((vl >> 62) == 0ull)) vl = (1ull << 62) | pp_poll(pl, l < PP_GROUP, a.err);
-            const uint32_t sum = (uint32_t)__shfl((int)wave_incl_scan(l < PP_GROUP ? (uint32_t)vl : 0u), 63);
-            if (l == 0)
-                __hip_atomic_store(a.descG + (it - 1) * ngroups + g, (1ull << 62) | (unsigned long long)sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        if (res) {
-            // everyone: the prefix of the tile taken `lag` iterations ago
-            if (__ballot((vr >> 62) == 0ull)) vr = (1ull << 62) | pp_poll(pr, needr, a.err);
-            const uint32_t val = needr ? (uint32_t)vr : 0u;
-            const uint32_t all_g = (uint32_t)__shfl((int)wave_incl_scan(isg ? val : 0u), 63);
-            const uint32_t before = (uint32_t)__shfl((int)wave_incl_scan((isg && l < g) || !isg ? val : 0u), 63);
-            if (l == 0 && j * G + b < a.ntiles) a.prefix[j * G + b] = base + (long long)before;
-            base += (long long)all_g;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; i++) cur[i] = nxt[i];
-    }
-    if (acc == 0x12345678u && s_pad[tid] == 77) sink[0] = acc;
-}
-
-// =========================================================================
-// k_read_probe: pure streaming read in the launch geometry of k_scan_lines (one 16 KiB
-// tile per 256-thread workgroup, four 16-byte loads per lane) or as a grid-stride loop.
-// The measured ceiling the scan kernel is compared with (tools/read_probe.py).
-// =========================================================================
-template <int MODE>
-__global__ __launch_bounds__(256) void k_read_probe(const uint8_t *__restrict__ d, int64_t ntiles,
-                                                    uint32_t *__restrict__ sink)
+__global__ __launch_bounds__(256) void k_read_probe(const uint8_t *__restrict__ d, uint32_t *__restrict__ sink)
 {
     const int tid = threadIdx.x;
     uint32_t acc = 0;
-    if (MODE == 0) {
-        const int64_t base = (int64_t)blockIdx.x << TILE_SHIFT;
-        const int w = tid >> 6, l = tid & 63;
-        uint4 v[4];
+    const int64_t base = (int64_t)blockIdx.x << TILE_SHIFT;
+    const int w = tid >> 6, l = tid & 63;
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    u32x4 v[4];
 #pragma unroll
-        for (int i = 0; i < 4; i++) v[i] = *reinterpret_cast<const uint4 *>(d + base + w * 4096 + i * 1024 + l * 16);
+    for (int i = 0; i < 4; i++)
+        v[i] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(d + base + w * 4096 + i * 1024 + l * 16));
 #pragma unroll
-        for (int i = 0; i < 4; i++) acc ^= v[i].x ^ v[i].y ^ v[i].z ^ v[i].w;
-    } else if (MODE == 2) {
-        // MODE 0 with the scan kernel's non-temporal loads
-        const int64_t base = (int64_t)blockIdx.x << TILE_SHIFT;
-        const int w = tid >> 6, l = tid & 63;
-        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-        u32x4 v[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-            v[i] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(d + base + w * 4096 + i * 1024 + l * 16));
-#pragma unroll
-        for (int i = 0; i < 4; i++) acc ^= v[i].x ^ v[i].y ^ v[i].z ^ v[i].w;
-    } else {
-        const int64_t nvec = ntiles << (TILE_SHIFT - 4);
-        const int64_t stride = (int64_t)gridDim.x * 256;
-        const uint4 *p = reinterpret_cast<const uint4 *>(d);
-        for (int64_t i = (int64_t)blockIdx.x * 256 + tid; i < nvec; i += stride * 4) {
-            uint4 v[4];
-#pragma unroll
-            for (int k = 0; k < 4; k++) v[k] = (i + k * stride < nvec) ? p[i + k * stride] : make_uint4(0, 0, 0, 0);
-#pragma unroll
-            for (int k = 0; k < 4; k++) acc ^= v[k].x ^ v[k].y ^ v[k].z ^ v[k].w;
-        }
-    }
+    for (int i = 0; i < 4; i++) acc ^= v[i].x ^ v[i].y ^ v[i].z ^ v[i].w;
     if (acc == 0x12345678u) sink[0] = acc;      // never true in practice: keeps the loads alive
 }
-
 #endif  // FFQ_PROBES
 
 // =========================================================================

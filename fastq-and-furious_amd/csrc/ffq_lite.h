@@ -29,9 +29,8 @@ constexpr int LT_B = 14;                   // words a node's call looks at, its 
 constexpr uint32_t LK_OK = 0, LK_GEN = 1, LK_SLOW = 2;  // node word: successor node (10 bits, NO_NODE: past the own tiles) | kind << 10 | mi << 12 | sj << 16
 constexpr uint32_t FLAG_LITE_DECLINED = 8u;
 
-__device__ __forceinline__ void lite_decline(const ChainBufs &B, int g, int why = 0)
+__device__ __forceinline__ void lite_decline(const ChainBufs &B, int g)
 {
-    if (PROBES && B.prof) atomicAdd(&B.prof[8 + why], 1ull);      // (instrumented build: why groups are declined)
     B.flags[g] = FLAG_LITE_DECLINED;
     B.dlist[atomicAdd(B.dcnt, 1u)] = (uint32_t)g;
 }
@@ -57,7 +56,7 @@ static inline int lite_first_end_group(int64_t n_bytes, int64_t ntiles, int ngro
 }
 
 template <int WPB>
-__global__ __launch_bounds__(WPB * 64) void k_chain_lite(LineIndex L, int64_t offset, ChainBufs B, int ng, int gl, int ablate)
+__global__ __launch_bounds__(WPB * 64) void k_chain_lite(LineIndex L, int64_t offset, ChainBufs B, int ng, int gl)
 {
     __shared__ __attribute__((aligned(4))) uint16_t raw_all[WPB][LT_WIN + 16];
     __shared__ uint16_t nidx_all[WPB][LT_NODES + 4];
@@ -74,10 +73,10 @@ __global__ __launch_bounds__(WPB * 64) void k_chain_lite(LineIndex L, int64_t of
     // (the first group and those from gl on -- lite_first_end_group -- are k_chain_wave's: on the list of declined groups
     // with the rest; round 4 gave them two launches of their own in front of this kernel, the first of which -- an ordinary
     // launch, one workgroup, 29 us -- ran with the GPU otherwise idle)
-    if (g == 0 || g >= gl) { if (lane == 0) lite_decline(B, g, 0); return; }
+    if (g == 0 || g >= gl) { if (lane == 0) lite_decline(B, g); return; }
     bool ok = own1 + 1 <= L.ntiles && (((int64_t)(wt0 + OWN_T + 2) << TILE_SHIFT) + L.s + 4 < L.len()) &&
               offset <= wpos0 + L.s + (TILE - RUNIN_BYTES);
-    if (!ok) { if (lane == 0) lite_decline(B, g, 0); return; }
+    if (!ok) { if (lane == 0) lite_decline(B, g); return; }
     // ---- the window's entries, one memory round trip --------------------------------------------------------------
     const uint32_t cl = (lane < OWN_T + 2) ? L.cnt[wt0 + lane] : 0u;
     uint32_t ev[OWN_T + 1][3];
@@ -110,7 +109,7 @@ __global__ __launch_bounds__(WPB * 64) void k_chain_lite(LineIndex L, int64_t of
         }
         return;
     }
-    if (!ok) { if (lane == 0) lite_decline(B, g, 1); return; }
+    if (!ok) { if (lane == 0) lite_decline(B, g); return; }
     const int lac = min(tc[OWN_T + 1], LT_LA);
     const int own_hi = tb[OWN_T + 1], nwin = own_hi + lac;
     // ---- entries -> LDS as they are; nodes (the "\n@" matches of the run-in tail and the own tiles) numbered ------------
@@ -152,10 +151,9 @@ __global__ __launch_bounds__(WPB * 64) void k_chain_lite(LineIndex L, int64_t of
         if (k == 0) n_runin = ncomp;
     }
     if (lane < lac) raw[own_hi + lane] = (uint16_t)la_raw;
-    if (ncomp == 0 || ncomp > LT_NODES) { if (lane == 0) lite_decline(B, g, 2); return; }     // (no candidate: the chain passes over -- a search of its own)
+    if (ncomp == 0 || ncomp > LT_NODES) { if (lane == 0) lite_decline(B, g); return; }     // (no candidate: the chain passes over -- a search of its own)
     if (lane < 3) nidx[ncomp + lane] = 0x7FF;                 // behind the last node: no entry index any successor could have
     wave_sync();
-    if (PROBES && ablate == 1) { if (lane == 0) B.lines[g] = lines + (uint32_t)ncomp; return; }      // (instruction counts per phase: tools/pmc_insts.sh)
     // ---- one scanner call per node ------------------------------------------------------------------------------------
     // A record of this kernel's kind: header line, mi - 1 sequence lines, the '+' line, as many quality lines -- entry k + mi
     // is the "\n+" match, k + mi + 1 the '+' line's end, and the next call's "\n@" (the first one at >= pos5 - 1 behind the
@@ -218,7 +216,6 @@ __global__ __launch_bounds__(WPB * 64) void k_chain_lite(LineIndex L, int64_t of
         infr[u] = inf; kreg[u] = kw;
         NS[u] = __ballot(!(((inf >> 10) & 3u) == LK_OK && (inf & WN_MASK) == (uint32_t)(c + 1)));
     }
-    if (PROBES && ablate == 2) { uint32_t x = 0; for (int u = 0; u < NB; u++) x += infr[u] + kreg[u]; if (x == 0x12345u) B.lines[g] = x; return; }
     // ---- chain membership: run by run, on the scalar side (the chain only moves forward: batch after batch) -------------
     // (the walk only marks where a run of members starts and where it ends; runs are disjoint and in order, so the
     // members of a batch are (ends << 1) - starts, modulo 2^64 for a run that ends with the batch)
@@ -240,9 +237,7 @@ __global__ __launch_bounds__(WPB * 64) void k_chain_lite(LineIndex L, int64_t of
             const int r = b + __ffsll((long long)ns) - 1;
             en |= 1ull << r;
             uint32_t ir = (uint32_t)__builtin_amdgcn_readlane((int)infr[u], r);
-            if (PROBES && B.prof && lane == 0) atomicAdd(&B.prof[14], 1ull);
             if (((ir >> 10) & 3u) == LK_SLOW) {
-                if (PROBES && B.prof && lane == 0) atomicAdd(&B.prof[13], 1ull);
                 // the successor rule entry by entry, by the whole wave: the first "\n@" behind the '+' line's end at >= pos5 - 1
                 const uint32_t kw_ = (uint32_t)__builtin_amdgcn_readlane((int)kreg[u], r);
                 const int k = (int)(kw_ & 0x7FFu), mi = (int)((ir >> 12) & 15u), c = u * 64 + r;
@@ -281,8 +276,7 @@ __global__ __launch_bounds__(WPB * 64) void k_chain_lite(LineIndex L, int64_t of
         }
         MB[u] = (en << 1) - st;
     }
-    if (PROBES && ablate == 3) { if (lane == 0) B.lines[g] = lines + (uint32_t)lastn + (uint32_t)MB[0]; return; }
-    if (bad || lastn < 0) { if (lane == 0) lite_decline(B, g, 3); return; }
+    if (bad || lastn < 0) { if (lane == 0) lite_decline(B, g); return; }
     // ---- records of the own tiles, staged in chain order -----------------------------------------------------------------
     uint32_t ntot = 0;
     unsigned long long OWN[NB];
@@ -293,7 +287,7 @@ __global__ __launch_bounds__(WPB * 64) void k_chain_lite(LineIndex L, int64_t of
         OWN[u] = MB[u] & (lo <= 0 ? ~0ull : lo >= 64 ? 0ull : (~0ull << lo));
         ntot += (uint32_t)__popcll(OWN[u]);
     }
-    if (ntot > (uint32_t)B.nmax) { if (lane == 0) lite_decline(B, g, 4); return; }
+    if (ntot > (uint32_t)B.nmax) { if (lane == 0) lite_decline(B, g); return; }
     StageRec *stg = B.stage + (int64_t)g * B.nmax;
     uint32_t nbase = 0, qsum = 0;
     int64_t Y = Y_UNRES;

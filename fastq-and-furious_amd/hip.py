@@ -169,9 +169,9 @@ def _share_torch_hip_runtime():
 
 
 def use_probe_build():
-    """tools/ only: load libffq_probe.so (the same sources compiled with -DFFQ_PROBES: ablation
-    switches, read / look-back / pipeline probes; include/ffq_probe.h) in place of the product
-    library.  Must be called before the first use of lib()."""
+    """tools/ only: load libffq_probe.so (the same sources compiled with -DFFQ_PROBES: the file
+    loader's ablation switch FFQ_LOAD_ABLATE, the streaming-read probe of include/ffq_probe.h) in
+    place of the product library.  Must be called before the first use of lib()."""
     global _probe, LIB_PATH
     assert _lib is None, "use_probe_build() must come before the library is loaded"
     from . import build as _build
@@ -244,7 +244,7 @@ def lib():
     global _lib
     if _lib is None:
         if os.environ.get("FFQ_USE_PROBE_BUILD") == "1" and not _probe:
-            use_probe_build()            # (tools/*.sh: the ablation switches live in the instrumented build)
+            use_probe_build()            # (tools: FFQ_LOAD_ABLATE lives in the instrumented build)
         _share_torch_hip_runtime()
         _checked_build()
         if not os.path.exists(LIB_PATH):
@@ -351,8 +351,6 @@ def lib():
         L.ffq_synth_wrapped_size.argtypes = [i64, u64]
         L.ffq_synth_wrapped_size.restype = i64
         L.ffq_synth_wrapped.argtypes = [vp, vp, vp, i64, i64, u64]
-        if _probe:
-            L.ffq_read_probe.argtypes = [vp, vp, i64, i32, i32, P(ctypes.c_float)]
         L.ffq_selftest.argtypes = [vp]
         _lib = L
     return _lib
@@ -581,15 +579,6 @@ class Context:
         check(lib().ffq_table_lower_bound(self.handle, ctypes.c_void_p(d_table), int(n_rows), int(col),
                                           int(value), ctypes.byref(idx)))
         return idx.value
-
-    def read_probe(self, dptr, n_bytes, mode=0, reps=10):
-        """Instrumented build only (use_probe_build(); include/ffq_probe.h)."""
-        if not _probe:
-            raise FFQError(E_ARG, "ffq_read_probe exists only in libffq_probe.so: call hip.use_probe_build() first (tools)")
-        ms = ctypes.c_float(0)
-        check(lib().ffq_read_probe(self.handle, ctypes.c_void_p(dptr), int(n_bytes), int(mode), int(reps),
-                                   ctypes.byref(ms)))
-        return ms.value
 
     def table_cut(self, d_table, n_rows, lo, hi):
         """(i0, i1, pos0[i0], pos0[i1], pos5[i0 - 1], pos5[i1 - 1]): first rows with pos0 >= lo / >= hi,
