@@ -48,8 +48,13 @@ def _writable_view(obj, itemsize, fmt_name):
     return m
 
 
-class _GpuEntrypos:
-    """entrypos(blob, offset, posbuffer) -> status, computed on the MI355X."""
+class _TableServer:
+    """The reference's per-record plug-in protocol over a scan that returns a whole table: the first call on a buffer scans
+    all of it on the GPU, the following calls of the same chain (same bytes object, offset = where the previous entry says
+    the next search starts) are served from that table; when it is used up, the scan's closing status and positions."""
+    _ncols = 6          # positions an entry fills
+    _next_col = 5       # the next call's offset is row[_next_col] + _next_add
+    _next_add = -1
 
     def __init__(self, device=None):
         self._device = device
@@ -65,6 +70,32 @@ class _GpuEntrypos:
             self._ctx = _hip.default_context(self._device)
         return self._ctx
 
+    def _serve(self, blob, offset, out):
+        """COMPLETE and the next row in out[:_ncols], or None at the end of the chain: (status, last positions) of the scan."""
+        offset = int(offset)
+        cacheable = isinstance(blob, bytes)
+        if not (cacheable and self._blob is blob and offset == self._next_offset):
+            table, res = self._scan(blob, offset)
+            self._blob = blob if cacheable else None
+            self._table = table
+            self._row = 0
+            self._term = (int(res.last_status), [int(x) for x in res.last_pos])
+        if self._row < len(self._table):
+            row = self._table[self._row]
+            out[:self._ncols] = row[:self._ncols]
+            self._row += 1
+            self._next_offset = int(row[self._next_col]) + self._next_add
+            return None
+        self._next_offset = None        # the chain has ended: rescan on the next call
+        return self._term
+
+
+class _GpuEntrypos(_TableServer):
+    """entrypos(blob, offset, posbuffer) -> status, computed on the MI355X."""
+
+    def _scan(self, blob, offset):
+        return self._context().scan_host(blob, sentinel=False, offset=offset, eof=False, add=0)
+
     # -- the reference's plug-in protocol ---------------------------------
     def __call__(self, blob, offset, posbuffer):
         pos = _writable_view(posbuffer, 8, 'q')
@@ -73,24 +104,11 @@ class _GpuEntrypos:
         out = np.frombuffer(pos, dtype=np.int64)
         if isinstance(blob, str):
             blob = blob.encode('utf-8')
-        offset = int(offset)
-        cacheable = isinstance(blob, bytes)
-        if not (cacheable and self._blob is blob and offset == self._next_offset):
-            table, res = self._context().scan_host(blob, sentinel=False, offset=offset, eof=False, add=0)
-            self._blob = blob if cacheable else None
-            self._table = table
-            self._row = 0
-            self._term = (int(res.last_status), [int(x) for x in res.last_pos])
-        if self._row < len(self._table):
-            row = self._table[self._row]
-            out[:6] = row
-            self._row += 1
-            self._next_offset = int(row[5]) - 1
+        term = self._serve(blob, offset, out)
+        if term is None:
             return COMPLETE
-        status, last = self._term
-        out[:6] = last
-        self._next_offset = None        # the chain has ended: rescan on the next call
-        return status
+        out[:6] = term[1]
+        return term[0]
 
     # -- stream protocol: the source is read, carried and scanned by the library itself ----------
     # Buffer fills are scanned whole, and the entries do not depend on how the stream is cut into fills
@@ -175,45 +193,29 @@ def _gzip_leave(fh, st):
 entrypos = _GpuEntrypos()
 
 
-class _GpuEntryposFasta:
+class _GpuEntryposFasta(_TableServer):
     """entrypos_fasta(buf, offset, posbuffer) -> status on the MI355X: the FASTA plug-in scanner
     of the reference (fastqandfurious.py:103-143) with the per-call protocol kept; the first call
     on a buffer scans all of it (ffq_scan_fasta_host), the following calls (offset = the previous
     pos[3]) are served from that table.  Like the reference's, it only fills the positions it
     gets to."""
+    _ncols, _next_col, _next_add = 4, 3, 0
 
-    def __init__(self, device=None):
-        self._device = device
-        self._blob = None
-        self._table = None
-        self._row = 0
-        self._next_offset = None
-        self._term = None
+    def _scan(self, buf, offset):
+        return self._context().scan_fasta_host(buf, offset=offset)
 
     def __call__(self, buf, offset, posbuffer):
         pos = _writable_view(posbuffer, 8, 'q')
         if pos.nbytes < 32:
             raise ValueError("posbuffer must hold at least 4 positions")
         out = np.frombuffer(pos, dtype=np.int64)
-        offset = int(offset)
-        cacheable = isinstance(buf, bytes)
-        if not (cacheable and self._blob is buf and offset == self._next_offset):
-            table, res = _hip.default_context(self._device).scan_fasta_host(buf, offset=offset)
-            self._blob = buf if cacheable else None
-            self._table = table
-            self._row = 0
-            self._term = (int(res.last_status), [int(x) for x in res.last_pos])
-        if self._row < len(self._table):
-            row = self._table[self._row]
-            out[:4] = row[:4]
-            self._row += 1
-            self._next_offset = int(row[3])
+        term = self._serve(buf, offset, out)
+        if term is None:
             return COMPLETE
-        status, last = self._term
+        status, last = term
         for i in range(4):
             if last[i] >= 0:
                 out[i] = last[i]
-        self._next_offset = None
         return status
 
 

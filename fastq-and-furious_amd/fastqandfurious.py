@@ -23,11 +23,16 @@ Beyond the hot path: the FASTA plug-in scanner of the 
 """
 from array import array
 from collections import namedtuple
+from functools import partial
 import importlib
+from itertools import islice, repeat
 import os
 import typing
 
+import numpy as np
+
 from . import entries as _entries
+from . import hip as _hip
 
 CHAR_AT: int = ord(b'@')
 CHAR_PLUS: int = ord(b'+')
@@ -227,30 +232,11 @@ def entryfunc_abspos(buf: bytes, pos, globaloffset: int):
     return pos
 
 
-def _raise_for_end(end_state: int, where: int):
-    if end_state == _END_ERR_FINAL_QUAL:
-        raise ValueError('Incomplete final quality string at byte')
-    if end_state == _END_ERR_INCOMPLETE:
-        raise ValueError('Incomplete entry at byte %i' % where)
-    if end_state == _END_ERR_INVALID:
-        raise ValueError('Entry is invalid at byte %i' % where)
-    raise RuntimeError('unknown end state %r' % (end_state,))
+_raise_for_end = _hip.raise_for_end
 
 
 _ENTRY_CHUNK = 1024     # rows per native call: the tuples of one chunk are consumed (and their memory
                         # reused) before the next is built -- a whole fill at once is 3 x slower
-
-
-def _default_entries(buf, rows, shift, cls=None):
-    """The default entryfunc (:161-171) over a table: (header, sequence, quality) of every row of
-    `rows` (C-contiguous int64, six per record; positions minus `shift` index `buf`); cls=Entry: what
-    entryfunc_namedtuple (:146-158) builds."""
-    cut = _entries.native().entries
-    mv = memoryview(rows).cast('B')
-    step = 48 * _ENTRY_CHUNK
-    # (one LIST per chunk: the caller yields from the list itself -- a generator level less per record)
-    for at in range(0, len(mv), step):
-        yield cut(buf, mv[at:at + step], shift, 1, cls)
 
 
 def _pushes_down(entryfunc):
@@ -264,92 +250,119 @@ def _pushes_down(entryfunc):
                                            getattr(t, "keeps", None) is getattr(entryfunc_lengthfilter, "keeps", None))
 
 
-def _phred_entries(st, fill, rows, shift):
-    """entryfunc_phred over a whole table, from the stream's bulk decode of that fill."""
-    qual, qoff = st.quals()
+def _table_entries(entryfunc, buf, rows, shift, quals=None):
+    """What readfastq_iter yields for one table, as an iterable of iterables (every front does `yield from` each): `rows` is
+    C-contiguous int64, six stream positions per record (array('q') or ndarray); stream byte x is buf[x - shift], `buf` any
+    buffer.  quals: None, or a callable giving the table's bulk Phred decode (qual, qoff) -- record i's bytes are
+    qual[qoff[i] : qoff[i] + pos5 - pos4], packed stream and single-pass segments alike -- for entryfunc_phred.
+
+    The bulk paths (entryfunc_phred over a decode, the default entryfunc and entryfunc_namedtuple) hand over one LIST per
+    _ENTRY_CHUNK rows, cut natively (csrc/ffq_entries.c) straight out of `buf` where the module is built -- a generator
+    level less per record.  Any other entryfunc is CALLED per record, lazily (not for record k + 1 before record k has been
+    handed out), with what the reference's loop passes (:252-255): `buf` as bytes, a fresh array('q') of six
+    buffer-relative positions, and `shift` as globaloffset; a length filter that is not pushed down and does not yield its
+    dropped records has its Nones left out."""
+    if not len(rows):
+        return ()
+    mv = memoryview(rows).cast('B')
     nat = _entries.native()
-    if nat is not None and hasattr(nat, "entries_phred"):
-        mv, mo = memoryview(rows).cast('B'), memoryview(qoff).cast('B')
-        step = _ENTRY_CHUNK
-        for at in range(0, rows.shape[0], step):
-            yield nat.entries_phred(fill, mv[48 * at:48 * (at + step)], shift, qual, mo[8 * at:8 * (at + step + 1)], array)
-        return
-    buf = fill.tobytes()
-    qb = qual.tobytes()
-    offs = qoff.tolist()
-    # (record i's bytes: qual[qoff[i] : qoff[i] + pos5 - pos4] -- packed stream and single-pass segments alike)
-    yield [(buf[p0 + 1:p1], buf[p2:p3], array('b', qb[offs[i]:offs[i] + p5 - p4]))
-           for i, (p0, p1, p2, p3, p4, p5) in enumerate((rows - shift).tolist())]
-
-
-def _np_arange(k):
-    import numpy as np
-    return np.arange(k, dtype=np.int64)
-
-
-def _filtered_items(st, flt, rows, fill, fill_offset):
-    """What readfastq_iter yields for one fill of a filtered stream: n_scanned items, None for the dropped records, the
-    filter's component for the kept ones (from the device's gathered column, or cut out of the fill for "entry")."""
-    idx, n_scanned, col, off = st.selected()
-    nat = _entries.native()
-    k = int(idx.shape[0])
-    if not flt.yield_dropped:                   # the kept records' items only: as if every record had been kept
-        n_scanned, idx = k, _np_arange(k)
-    if n_scanned == 0:
-        return []
-    if k == 0:
-        return [None] * n_scanned
-    if flt.column == "entry":
-        if nat is not None and hasattr(nat, "sparse_entries"):
-            return nat.sparse_entries(n_scanned, memoryview(idx).cast('B'), fill, memoryview(rows).cast('B'), fill_offset)
-        out = [None] * n_scanned
-        buf = fill.tobytes()
-        for k, (p0, p1, p2, p3, p4, p5) in zip(idx.tolist(), (rows - fill_offset).tolist()):
-            out[k] = (buf[p0 + 1:p1], buf[p2:p3], buf[p4:p5])
-        return out
-    if nat is not None and hasattr(nat, "sparse"):
-        return nat.sparse(n_scanned, memoryview(idx).cast('B'), col, memoryview(off).cast('B'))
-    out = [None] * n_scanned
-    cb, o = col.tobytes(), off.tolist()
-    for j, k in enumerate(idx.tolist()):
-        out[k] = cb[o[j]:o[j + 1]]
+    step = 48 * _ENTRY_CHUNK
+    if quals is not None and entryfunc is entryfunc_phred:
+        qual, qoff = quals()
+        if nat is not None and hasattr(nat, "entries_phred"):
+            mo = memoryview(qoff).cast('B')
+            return (nat.entries_phred(buf, mv[at:at + step], shift, qual, mo[at // 6:(at + step) // 6 + 8], array)
+                    for at in range(0, len(mv), step))
+        buf, qb, offs = bytes(buf), qual.tobytes(), qoff.tolist()
+        rel = (np.frombuffer(mv, dtype=np.int64).reshape(-1, 6) - shift).tolist()
+        return ([(buf[p0 + 1:p1], buf[p2:p3], array('b', qb[offs[i]:offs[i] + p5 - p4]))
+                 for i, (p0, p1, p2, p3, p4, p5) in enumerate(rel)],)
+    if (entryfunc is _ENTRYFUNC or entryfunc is entryfunc_namedtuple) and nat is not None:
+        cls = None if entryfunc is _ENTRYFUNC else Entry
+        return (nat.entries(buf, mv[at:at + step], shift, 1, cls) for at in range(0, len(mv), step))
+    if not isinstance(buf, bytes):
+        buf = bytes(buf)
+    rel = array('q')
+    rel.frombytes((np.frombuffer(mv, dtype=np.int64) - shift).tobytes())
+    if entryfunc is _ENTRYFUNC:
+        # the default entryfunc inlined: the same three slices per record (:161-171) without a posbuffer object and a
+        # call per record (1.7 x the entries per second; a list of lists from tolist() is slower than either)
+        it = iter(rel)
+        z = zip(it, it, it, it, it, it)
+        return iter(lambda: [(buf[p0 + 1:p1], buf[p2:p3], buf[p4:p5]) for p0, p1, p2, p3, p4, p5 in islice(z, _ENTRY_CHUNK)], [])
+    out = _called(entryfunc, buf, rel, shift)
+    if isinstance(entryfunc, entryfunc_lengthfilter) and not entryfunc.yield_dropped:
+        return ((e for e in chunk if e is not None) for chunk in out)
     return out
 
 
-def _iter_batched(fh, fbufsize, entryfunc, scan_buffer):
-    """readfastq_iter with a batched scanner: one scan per buffer fill.
+_POS = tuple(slice(i, i + 6) for i in range(0, 6 * _ENTRY_CHUNK, 6))       # where the records of a chunk lie among its positions
 
-    scan_buffer(buf, offset, eof) -> (rows, end_state, end_offset) where rows
-    is an array('q') of 6*n buffer-relative positions.  The refill, the
-    sentinel, globaloffset and the error texts follow the reference loop
-    (:241-279) step for step.
-    """
-    # a scanner may name a number of bytes below which reads are coalesced into k * fbufsize per scan
-    # (the entries do not depend on where the stream is cut into fills)
-    co = getattr(getattr(scan_buffer, '__self__', None), 'coalesce_bytes', 0) or 0
-    if 0 < fbufsize < co:
-        fbufsize *= -(-co // fbufsize)
+
+def _called(entryfunc, buf, rel, shift):
+    """entryfunc(buf, pos, shift) for every six positions of `rel` (array('q')), one lazy `map` per _ENTRY_CHUNK records: the
+    call for a record is made when the front asks for its item, and nothing per record runs in the interpreter but the
+    entryfunc itself (a generator level per record costs a tenth of the rate, slices built per record a twentieth)."""
+    for at in range(0, len(rel), 6 * _ENTRY_CHUNK):
+        part = rel[at:at + 6 * _ENTRY_CHUNK]
+        yield map(entryfunc, repeat(buf), map(part.__getitem__, _POS[:len(part) // 6]), repeat(shift))
+
+
+def _phred_entries(st, fill, rows, shift):
+    """entryfunc_phred over a whole table, from the stream's bulk decode of that fill."""
+    return _table_entries(entryfunc_phred, fill, rows, shift, st.quals)
+
+
+def _kept_items(yield_dropped, n_items, where, col=None, off=None, buf=None, rows=None, shift=0):
+    """The pushed-down length filter's items for n_items records of which the device kept len(where): a list with kept
+    record j's item at where[j] and None elsewhere -- or, yield_dropped False, the kept records' items alone.  The item is
+    col[off[j] : off[j + 1]] of the gathered column, or, col None ("entry"), the (header, sequence, quality) of row j of
+    `rows` cut out of `buf` (positions minus `shift` index it)."""
+    k = len(where)
+    if not yield_dropped:                       # as if every record had been kept
+        n_items, where = k, np.arange(k, dtype=np.int64)
+    if k == 0:
+        return [None] * n_items
+    nat = _entries.native()
+    if col is None:
+        if nat is not None and hasattr(nat, "sparse_entries"):
+            return nat.sparse_entries(n_items, memoryview(where).cast('B'), buf, memoryview(rows).cast('B'), shift)
+        out, buf = [None] * n_items, bytes(buf)
+        for j, (p0, p1, p2, p3, p4, p5) in zip(where.tolist(), (rows - shift).tolist()):
+            out[j] = (buf[p0 + 1:p1], buf[p2:p3], buf[p4:p5])
+        return out
+    if nat is not None and hasattr(nat, "sparse"):
+        return nat.sparse(n_items, memoryview(where).cast('B'), col, memoryview(off).cast('B'))
+    out, cb, o = [None] * n_items, col.tobytes(), off.tolist()
+    for j, at in enumerate(where.tolist()):
+        out[at] = cb[o[j]:o[j + 1]]
+    return out
+
+
+def _cut_column(buf, rows, shift, column):
+    """(bytes uint8[], offsets int64[n + 1]) of one component ("header" as entryfunc cuts it, "sequence", "quality") of
+    every row, cut out of `buf` (positions minus `shift` index it) in one numpy gather: FileShard.kept_column on the host."""
+    ca, shf, cb = _hip.Context.COLUMNS[column]
+    beg, lens = rows[:, ca] + shf - shift, np.maximum(rows[:, cb] - rows[:, ca] - shf, 0)
+    off = np.zeros(len(rows) + 1, dtype=np.int64)
+    np.cumsum(lens, out=off[1:])
+    src = np.repeat(beg - off[:-1], lens) + np.arange(int(off[-1]), dtype=np.int64)
+    return np.frombuffer(buf, dtype=np.uint8)[src], off
+
+
+def iter_tables(fh, fbufsize, scan_buffer):
+    """One (buf, rows, globaloffset) per buffer fill that holds a record, with a batched scanner:
+    scan_buffer(buf, offset, eof) -> (rows, end_state, end_offset) where rows is an array('q') of 6*n
+    buffer-relative positions, `rows[i] + globaloffset` the absolute ones.  The refill, the sentinel,
+    globaloffset and the error texts follow the reference loop (:241-279) step for step."""
     globaloffset = -1
     offset = 0
     buf, eof = read(fh, fbufsize)
     buf = b'\n' + buf
     while True:
         rows, end_state, end_offset = scan_buffer(buf, offset, eof)
-        if (entryfunc is _ENTRYFUNC or entryfunc is entryfunc_namedtuple) and _entries.native() is not None:
-            for chunk in _default_entries(buf, rows, 0, None if entryfunc is _ENTRYFUNC else Entry):
-                yield from chunk
-        elif entryfunc is _ENTRYFUNC:
-            it = iter(rows)                      # the default entryfunc inlined (see _iter_stream)
-            for p0, p1, p2, p3, p4, p5 in zip(it, it, it, it, it, it):
-                yield (buf[p0 + 1:p1], buf[p2:p3], buf[p4:p5])
-        elif isinstance(entryfunc, entryfunc_lengthfilter) and not entryfunc.yield_dropped:
-            for i in range(0, len(rows), 6):
-                e = entryfunc(buf, rows[i:i + 6], globaloffset)
-                if e is not None:
-                    yield e
-        else:
-            for i in range(0, len(rows), 6):
-                yield entryfunc(buf, rows[i:i + 6], globaloffset)
+        if len(rows):
+            yield buf, rows, globaloffset
         offset = end_offset
         if end_state == _END_OK:
             return
@@ -362,46 +375,31 @@ def _iter_batched(fh, fbufsize, entryfunc, scan_buffer):
         offset = 0
 
 
+def _iter_batched(fh, fbufsize, entryfunc, scan_buffer):
+    """readfastq_iter with a batched scanner: one scan per buffer fill (iter_tables)."""
+    # a scanner may name a number of bytes below which reads are coalesced into k * fbufsize per scan
+    # (the entries do not depend on where the stream is cut into fills)
+    co = getattr(getattr(scan_buffer, '__self__', None), 'coalesce_bytes', 0) or 0
+    if 0 < fbufsize < co:
+        fbufsize *= -(-co // fbufsize)
+    for buf, rows, globaloffset in iter_tables(fh, fbufsize, scan_buffer):
+        for chunk in _table_entries(entryfunc, buf, np.frombuffer(rows, dtype=np.int64) + globaloffset, globaloffset):
+            yield from chunk
+
+
 def _iter_stream(st, entryfunc):
     """readfastq_iter over the native stream front end (ffq_stream_*): the library reads the
     file (ahead, into pinned memory), scans every buffer fill and hands back the rows; this loop
-    only builds the entries.  `buf` is the fill as bytes and `pos` its buffer-relative positions,
-    exactly what the reference's loop passes to entryfunc (:252-255), globaloffset included."""
+    only builds the entries, out of the stream's own (pinned) fill."""
     try:
         for rows, fill, fill_offset, end_state, err_offset in st:
             if st.filtered:
                 # the stream dropped rows on the device (entryfunc_lengthfilter): one item per scanned record all the same
-                yield from _filtered_items(st, entryfunc, rows, fill, fill_offset)
-            elif rows.shape[0] and entryfunc is entryfunc_phred and st.decode:
-                for chunk in _phred_entries(st, fill, rows, fill_offset):
+                idx, n_scanned, col, off = st.selected()
+                yield from _kept_items(entryfunc.yield_dropped, n_scanned, idx, col, off, fill, rows, fill_offset)
+            else:
+                for chunk in _table_entries(entryfunc, fill, rows, fill_offset, st.quals if st.decode else None):
                     yield from chunk
-            elif rows.shape[0] and (entryfunc is _ENTRYFUNC or entryfunc is entryfunc_namedtuple) and _entries.native() is not None:
-                # the default entryfunc over the whole table, natively (csrc/ffq_entries.c): the slices
-                # are cut straight out of the stream's own (pinned) fill -- no bytes copy of the fill,
-                # no posbuffer and no interpreter loop per record
-                for chunk in _default_entries(fill, rows, fill_offset, None if entryfunc is _ENTRYFUNC else Entry):
-                    yield from chunk
-            elif rows.shape[0]:
-                buf = fill.tobytes()
-                rel = array('q')
-                rel.frombytes((rows - fill_offset).tobytes())
-                if entryfunc is _ENTRYFUNC:
-                    # the default entryfunc, inlined over the whole table: the same three slices per
-                    # record (:161-171) without a posbuffer object and a call per record (1.7 x the
-                    # entries per second; a list of lists from tolist() is slower than either)
-                    it = iter(rel)
-                    for p0, p1, p2, p3, p4, p5 in zip(it, it, it, it, it, it):
-                        yield (buf[p0 + 1:p1], buf[p2:p3], buf[p4:p5])
-                elif isinstance(entryfunc, entryfunc_lengthfilter) and not entryfunc.yield_dropped:
-                    # (a length filter that is not pushed down -- a subclass with a __call__ / keeps() of its own: called per
-                    # record, its dropped records left out as on every other scanner)
-                    for i in range(0, len(rel), 6):
-                        e = entryfunc(buf, rel[i:i + 6], fill_offset)
-                        if e is not None:
-                            yield e
-                else:
-                    for i in range(0, len(rel), 6):
-                        yield entryfunc(buf, rel[i:i + 6], fill_offset)
             if end_state != _END_OK and end_state != _END_REFILL:
                 _raise_for_end(end_state, err_offset)
     finally:
@@ -512,55 +510,28 @@ class RangeEntries:
         self._gen.close()
         self._sh.close()         # (a generator that never started has no `finally` to run)
 
-    def _filtered(self, view, mm):
+    def _filtered(self, view):
         """entryfunc_lengthfilter over this rank's records with the filter ON THE DEVICE (FileShard.select): one item per
         record -- None for a dropped one, the filter's component for a kept one (/root/reference/doc/user-guide.rst:153-180) --
         or, yield_dropped=False, the kept records' items alone.  Only the kept rows (and, from a resident range, their
         gathered component) cross the link; a dropped record costs the host one pointer in a list."""
-        import numpy as np
-        sh, flt, nat = self._sh, self._entryfunc, _entries.native()
+        sh, flt = self._sh, self._entryfunc
         k, idx = sh.select(flt.min_len, flt.max_len)
         step = self._batch
         for i0 in range(0, self.n_records, step):                       # windows of ORIGINAL records
             i1 = min(i0 + step, self.n_records)
             ka, kb = int(np.searchsorted(idx, i0)), int(np.searchsorted(idx, i1))
-            n_items = i1 - i0
+            where = np.ascontiguousarray(idx[ka:kb] - i0)
             if kb == ka:
-                if flt.yield_dropped:
-                    yield from [None] * n_items
+                yield from _kept_items(flt.yield_dropped, i1 - i0, where)
                 continue
             rows = sh.kept_rows(ka, kb)
-            local = np.ascontiguousarray(idx[ka:kb] - i0)
-            if not flt.yield_dropped:
-                n_items, local = kb - ka, _np_arange(kb - ka)
             a, b = int(rows[0, 0]), int(rows[-1, 5]) + 1
-            if flt.column == "entry":
-                if nat is not None and hasattr(nat, "sparse_entries"):
-                    yield from nat.sparse_entries(n_items, memoryview(local).cast('B'), view[a:b], memoryview(rows).cast('B'), a)
-                else:
-                    out, buf = [None] * n_items, mm[a:b]
-                    for j, (p0, p1, p2, p3, p4, p5) in zip(local.tolist(), (rows - a).tolist()):
-                        out[j] = (buf[p0 + 1:p1], buf[p2:p3], buf[p4:p5])
-                    yield from out
-                continue
-            got = sh.kept_column(ka, kb, flt.column, rows)
-            if got is None:
-                # the range is not resident (slabs; a view that grew): the kept rows' slices out of the file, in one numpy gather
-                ca, shf, cb = {"header": (0, 1, 1), "sequence": (2, 0, 3), "quality": (4, 0, 5)}[flt.column]
-                beg, lens = rows[:, ca] + shf - a, np.maximum(rows[:, cb] - rows[:, ca] - shf, 0)
-                off = np.zeros(kb - ka + 1, dtype=np.int64)
-                np.cumsum(lens, out=off[1:])
-                src = np.repeat(beg - off[:-1], lens) + np.arange(int(off[-1]), dtype=np.int64)
-                col = np.frombuffer(view[a:b], dtype=np.uint8)[src]
-            else:
-                col, off = got
-            if nat is not None and hasattr(nat, "sparse"):
-                yield from nat.sparse(n_items, memoryview(local).cast('B'), col, memoryview(off).cast('B'))
-            else:
-                out, cb_, offs = [None] * n_items, col.tobytes(), off.tolist()
-                for j, kk in zip(local.tolist(), range(kb - ka)):
-                    out[j] = cb_[offs[kk]:offs[kk + 1]]
-                yield from out
+            col = off = None
+            if flt.column != "entry":
+                # (None: the range is not resident -- slabs; a view that grew --: the kept rows' slices out of the file)
+                col, off = sh.kept_column(ka, kb, flt.column, rows) or _cut_column(view[a:b], rows, a, flt.column)
+            yield from _kept_items(flt.yield_dropped, i1 - i0, where, col, off, view[a:b], rows, a)
 
     def _entries(self):
         import mmap
@@ -571,35 +542,25 @@ class RangeEntries:
                 # (a BGZF shard: the rank's inflated bytes are in host memory, sliced with stream offsets like a map of a plain file)
                 from .sharded import _Shifted
                 base, arr = sh.host_bytes()
-                mm, view = _Shifted(arr, base, as_bytes=True), _Shifted(arr, base)
+                mm = view = _Shifted(arr, base)
             elif self.n_records:
                 mm = mmap.mmap(sh.fd, 0, access=mmap.ACCESS_READ)       # (the page cache holds the range: it was just read)
                 view = memoryview(mm)
             if self.n_records and _pushes_down(entryfunc):
-                yield from self._filtered(view, mm)
+                yield from self._filtered(view)
                 return
-            drop_none = isinstance(entryfunc, entryfunc_lengthfilter) and not entryfunc.yield_dropped      # (a filter that is not pushed down)
             for i0 in range(0, self.n_records, self._batch):
                 i1 = min(i0 + self._batch, self.n_records)
                 rows = sh.rows(i0, i1)
                 a, b = int(rows[0, 0]), int(rows[-1, 5]) + 1
-                if entryfunc is entryfunc_phred and (sh.decoded or sh.slab_bytes) and _entries.native() is not None and hasattr(_entries.native(), "entries_phred"):
-                    # the qualities from the step's own decode -- or, over slabs (nothing resident), decoded on the device batch by batch
-                    qual, qoff = sh.quals(i0, i1, rows) if sh.decoded else sh.quals_from_file(rows)
-                    yield from _entries.native().entries_phred(view[a:b], memoryview(rows).cast('B'), a, qual, memoryview(qoff).cast('B'), array)
-                elif (entryfunc is _ENTRYFUNC or entryfunc is entryfunc_namedtuple) and _entries.native() is not None:
-                    for chunk in _default_entries(view[a:b], rows, a, None if entryfunc is _ENTRYFUNC else Entry):
-                        yield from chunk
-                else:
-                    # any entryfunc: `buf` holds the batch's bytes, `pos` is relative to it and pos + globaloffset the
-                    # absolute file offsets (entryfunc_abspos, :186-195) -- the contract of the reference's loop (:252-255)
-                    buf = mm[a:b]
-                    rel = array('q')
-                    rel.frombytes((rows - a).tobytes())
-                    for i in range(0, len(rel), 6):
-                        e = entryfunc(buf, rel[i:i + 6], a)
-                        if e is not None or not drop_none:
-                            yield e
+                # entryfunc_phred: the qualities from the step's own decode -- or, over slabs (nothing resident), decoded on the
+                # device batch by batch.  Any entryfunc sees the batch's bytes, positions relative to them, and `a` as the
+                # globaloffset that makes them absolute file offsets (entryfunc_abspos, :186-195)
+                quals = None
+                if entryfunc is entryfunc_phred and (sh.decoded or sh.slab_bytes):
+                    quals = partial(sh.quals, i0, i1, rows) if sh.decoded else partial(sh.quals_from_file, rows)
+                for chunk in _table_entries(entryfunc, view[a:b], rows, a, quals):
+                    yield from chunk
         finally:
             if mm is not None:
                 try:

@@ -26,6 +26,28 @@ COMPLETE = 6
 MISSING_QUALHEADER_END = 7
 
 END_OK, END_REFILL, END_ERR_FINAL_QUAL, END_ERR_INCOMPLETE, END_ERR_INVALID = range(5)
+_END_ERRORS = {END_ERR_FINAL_QUAL: 'Incomplete final quality string at byte',
+               END_ERR_INCOMPLETE: 'Incomplete entry at byte %i',
+               END_ERR_INVALID: 'Entry is invalid at byte %i'}
+
+
+def raise_for_end(end_state, where):
+    """The reference iterator's ValueError (fastqandfurious.py:262, :269, :272) for an END_ERR_* state met at stream byte `where`."""
+    text = _END_ERRORS.get(end_state)
+    if text is None:
+        raise RuntimeError('unknown end state %r' % (end_state,))
+    raise ValueError(text % where if '%' in text else text)
+
+
+def length_bounds(min_len, max_len, open_low=-(1 << 62)):
+    """(lo, hi) as the length filter's entry points take them: None is an open bound."""
+    return open_low if min_len is None else int(min_len), (1 << 62) if max_len is None else int(max_len)
+
+
+def _add(add, sentinel):
+    """The default of every `add` argument: positions count the stream's bytes, not the sentinel in front of them."""
+    return (-1 if sentinel else 0) if add is None else add
+
 
 ABI_VERSION = 6
 OK = 0
@@ -458,8 +480,7 @@ class Context:
         """Record chain over a device-resident buffer (raw device pointers).
 
         Returns (rc, ScanResult); rc is OK or E_TABLE_FULL."""
-        if add is None:
-            add = -1 if sentinel else 0
+        add = _add(add, sentinel)
         res = ScanResult()
         rc = lib().ffq_scan_device(self.handle, ctypes.c_void_p(d_buf), int(n_bytes), int(bool(sentinel)),
                                    int(offset), int(bool(eof)), int(add), int(flags), int(qual_add),
@@ -472,8 +493,7 @@ class Context:
     def scan_submit(self, d_buf, n_bytes, d_table, table_cap, sentinel=True, offset=0, eof=True,
                     add=None, flags=0, qual_add=-33, d_qual=None, qual_cap=0, d_qoff=None):
         """Enqueue a scan and return at once; scan_wait() completes it."""
-        if add is None:
-            add = -1 if sentinel else 0
+        add = _add(add, sentinel)
         check(lib().ffq_scan_submit(self.handle, ctypes.c_void_p(d_buf), int(n_bytes), int(bool(sentinel)),
                                     int(offset), int(bool(eof)), int(add), int(flags), int(qual_add),
                                     ctypes.c_void_p(d_table), int(table_cap),
@@ -486,6 +506,18 @@ class Context:
         check(rc, allow=(E_TABLE_FULL,))
         return rc, res
 
+    @staticmethod
+    def _sized(run, n_bytes, table_cap):
+        """run(cap) -> (rc, ScanResult, result) with a table of table_cap rows; table_cap None: a row per 64 bytes of input, and
+        a table that was too small (E_TABLE_FULL) is sized from the records the scan counted and the scan run again."""
+        cap = int(table_cap) if table_cap is not None else max(n_bytes // 64 + 16, 16)
+        while True:
+            rc, res, result = run(cap)
+            if rc == E_TABLE_FULL and table_cap is None:
+                cap = int(res.n_records) + 1
+                continue
+            return result
+
     def scan_host(self, buf, sentinel=True, offset=0, eof=True, add=None, flags=0, qual_add=-33,
                   table_cap=None, qual_room=None):
         """Record chain over a host bytes-like object.
@@ -494,11 +526,10 @@ class Context:
         admits the in-place layout, i.e. long lines, as well).
         Returns (table int64[n,6], ScanResult[, qual int8[], qoff int64[n+1]])."""
         a = np.frombuffer(buf, dtype=np.uint8) if not isinstance(buf, np.ndarray) else buf
-        if add is None:
-            add = -1 if sentinel else 0
+        add = _add(add, sentinel)
         decode = bool(flags & F_DECODE_QUAL)
-        cap = int(table_cap) if table_cap is not None else max(a.size // 64 + 16, 16)
-        while True:
+
+        def run(cap):
             table = np.empty((cap, 6), dtype=np.int64)
             nq = a.size if decode else 0
             if decode and (flags & F_SINGLE_PASS):
@@ -512,32 +543,24 @@ class Context:
                                      qual.ctypes.data if decode else None, qual.size,
                                      qoff.ctypes.data if decode else None, ctypes.byref(res))
             check(rc, allow=(E_TABLE_FULL,))
-            if rc == E_TABLE_FULL and table_cap is None:
-                cap = int(res.n_records) + 1
-                continue
-            break
-        n = min(int(res.n_records), cap)
-        if decode:
-            return table[:n], res, qual[:int(res.n_qual_bytes)], qoff[:n + 1]
-        return table[:n], res
+            n = min(int(res.n_records), cap)
+            return rc, res, (table[:n], res, qual[:int(res.n_qual_bytes)], qoff[:n + 1]) if decode else (table[:n], res)
+        return self._sized(run, a.size, table_cap)
 
     def scan_fasta_host(self, buf, sentinel=False, offset=0, add=0, table_cap=None):
         """Every COMPLETE FASTA entry of a host buffer (the repeated entrypos_fasta call,
         reference fastqandfurious.py:103-143): (table int64[n,6] with pos4 = pos5 = -1,
         ScanResult with the last call's status / posbuffer / offset)."""
         a = np.frombuffer(buf, dtype=np.uint8) if not isinstance(buf, np.ndarray) else buf
-        cap = int(table_cap) if table_cap is not None else max(a.size // 64 + 16, 16)
-        while True:
+
+        def run(cap):
             table = np.empty((cap, 6), dtype=np.int64)
             res = ScanResult()
             rc = lib().ffq_scan_fasta_host(self.handle, a.ctypes.data if a.size else None, a.size, int(bool(sentinel)),
                                            int(offset), int(add), table.ctypes.data, cap, ctypes.byref(res))
             check(rc, allow=(E_TABLE_FULL,))
-            if rc == E_TABLE_FULL and table_cap is None:
-                cap = int(res.n_records) + 1
-                continue
-            break
-        return table[:min(int(res.n_records), cap)], res
+            return rc, res, (table[:min(int(res.n_records), cap)], res)
+        return self._sized(run, a.size, table_cap)
 
     def scan_fasta_device(self, d_buf, n_bytes, d_table, table_cap, sentinel=False, offset=0, add=0):
         res = ScanResult()
@@ -611,8 +634,7 @@ class Context:
         byte, into d_out with CSR offsets d_off (n_rows + 1); raw device pointers.  Returns
         (rc, bytes of the stream); rc is OK or E_TABLE_FULL (out_cap too small)."""
         ca, sh, cb = self.COLUMNS[which] if isinstance(which, str) else which
-        if add is None:
-            add = -1 if sentinel else 0
+        add = _add(add, sentinel)
         nb = ctypes.c_int64(0)
         rc = lib().ffq_table_gather_column(self.handle, ctypes.c_void_p(d_buf), int(n_bytes), int(bool(sentinel)),
                                            int(add), ctypes.c_void_p(d_table), int(n_rows), int(ca), int(sh), int(cb),
@@ -636,21 +658,18 @@ def shard_unique_id():
     return bytes(buf)
 
 
-def shard_host_step(rank, world, bounds, tail_bytes, head_bytes, ext_ptr, table_ptr, table_cap, exchange, allgather, scan=None, ctx=None):
-    """One step of the byte-range shards over HOST memory (ffq_shard_host_step): the protocol is the library's
-    (csrc/ffq_shard_proto.h), the transport the caller's --
-        exchange(pieces)   pieces = [(src, dst, a, b, ptr)]: the same list on every rank; ptr is this rank's end (or None)
-        allgather(words)   eight ints in, [world][8] out
-        scan(buf_ptr, n, sentinel, offset, eof, add, table_ptr, cap, res) -> FFQ code, res (a ScanResult) filled;
-                           None: ffq_scan_host on `ctx` (the GPU)
-    An exception raised inside a callback is re-raised here.  Returns (rc, ShardResult); rc is OK or E_TABLE_FULL."""
+def _host_ops(world, exchange, allgather, scan=None):
+    """(ShardHostOps, errors): the ctypes adapters of a host transport -- exchange(pieces), allgather(words) and, optionally,
+    scan(...) as shard_host_step documents them.  An exception raised inside one must not propagate through the C frames: it
+    is appended to `errors` (the caller re-raises it once the library has returned) and the library is told E_INTERNAL.  The
+    structure holds the callbacks: they live as long as it does."""
     err = []
 
     def guard(fn):
         def run(*a):
             try:
                 return int(fn(*a) or 0)
-            except BaseException as e:      # noqa: BLE001  (must not propagate through the C frames)
+            except BaseException as e:      # noqa: BLE001
                 err.append(e)
                 return E_INTERNAL
         return run
@@ -667,8 +686,19 @@ def shard_host_step(rank, world, bounds, tail_bytes, head_bytes, ext_ptr, table_
     def c_scan(_user, buf, n, sentinel, offset, eof, add, table, cap, res):
         return scan(buf, n, sentinel, offset, eof, add, table, cap, res.contents)
 
-    ops = ShardHostOps(None, _SCAN_CB(guard(c_scan)) if scan is not None else _SCAN_CB(), _EXCHANGE_CB(guard(c_exchange)),
-                       _GATHER_CB(guard(c_gather)))
+    return ShardHostOps(None, _SCAN_CB(guard(c_scan)) if scan is not None else _SCAN_CB(), _EXCHANGE_CB(guard(c_exchange)),
+                        _GATHER_CB(guard(c_gather))), err
+
+
+def shard_host_step(rank, world, bounds, tail_bytes, head_bytes, ext_ptr, table_ptr, table_cap, exchange, allgather, scan=None, ctx=None):
+    """One step of the byte-range shards over HOST memory (ffq_shard_host_step): the protocol is the library's
+    (csrc/ffq_shard_proto.h), the transport the caller's --
+        exchange(pieces)   pieces = [(src, dst, a, b, ptr)]: the same list on every rank; ptr is this rank's end (or None)
+        allgather(words)   eight ints in, [world][8] out
+        scan(buf_ptr, n, sentinel, offset, eof, add, table_ptr, cap, res) -> FFQ code, res (a ScanResult) filled;
+                           None: ffq_scan_host on `ctx` (the GPU)
+    An exception raised inside a callback is re-raised here.  Returns (rc, ShardResult); rc is OK or E_TABLE_FULL."""
+    ops, err = _host_ops(world, exchange, allgather, scan)
     b = (ctypes.c_int64 * (world + 1))(*[int(x) for x in bounds])
     res = ShardResult()
     rc = lib().ffq_shard_host_step(ctypes.byref(ops), ctx.handle if ctx is not None else None, int(rank), int(world), b,
@@ -714,27 +744,7 @@ class Shard:
         self._err = []
         b = (ctypes.c_int64 * (world + 1))(*[int(x) for x in bounds])
         if hosted is not None:
-            err = self._err
-
-            def c_exchange(_user, pieces, n):
-                try:
-                    hosted.exchange([(pieces[i].src, pieces[i].dst, pieces[i].a, pieces[i].b, pieces[i].ptr) for i in range(n)])
-                    return 0
-                except BaseException as e:      # noqa: BLE001
-                    err.append(e)
-                    return E_INTERNAL
-
-            def c_gather(_user, mine, out):
-                try:
-                    allv = hosted.allgather([mine[i] for i in range(8)])
-                    for r in range(world):
-                        for k in range(8):
-                            out[r * 8 + k] = int(allv[r][k])
-                    return 0
-                except BaseException as e:      # noqa: BLE001
-                    err.append(e)
-                    return E_INTERNAL
-            ops = ShardHostOps(None, _SCAN_CB(), _EXCHANGE_CB(c_exchange), _GATHER_CB(c_gather))
+            ops, self._err = _host_ops(world, hosted.exchange, hosted.allgather)
             self._keep = (ops, hosted)                     # (the callbacks live as long as the shard)
             check(lib().ffq_shard_create_hosted(ctx.handle, ctypes.byref(ops), int(rank), int(world), b, int(tail_bytes), int(head_bytes),
                                                 ctypes.byref(self._h)))
@@ -890,8 +900,7 @@ class _Stream:
         """Push-down (ffq_stream_set_filter; doc/user-guide.rst:153-180): from the next fill on the iteration yields only the
         rows with min_seq_len <= pos3 - pos2 <= max_seq_len; column = "header" | "sequence" | "quality": that component
         of the kept rows is gathered on the device (selected())."""
-        lo = -(1 << 62) if min_seq_len is None else int(min_seq_len)
-        hi = (1 << 62) if max_seq_len is None else int(max_seq_len)
+        lo, hi = length_bounds(min_seq_len, max_seq_len)
         check(lib().ffq_stream_set_filter(self._h, lo, hi, self.COLUMNS[column], int(value_add)))
         self.filtered = True
 

@@ -11,12 +11,12 @@ The GPU scan already produces exactly this table for a whole buffer fill, so the
 written table by table (`build_index`) and replayed in chunks of rows (`iter_indexed`).
 Filtering or trimming reads is editing rows (`select_rows`), as the user guide suggests.
 """
-from array import array
 
 import numpy as np
 
 from . import entries as _entries
 from . import fastqandfurious as _F
+from . import hip as _hip
 
 ROW_BYTES = 48          # 6 x int64 per record
 
@@ -53,29 +53,7 @@ def _leave_at(fh, st):
         pass
 
 
-def iter_tables(fh, fbufsize, scan_buffer):
-    """One (buf, rows, globaloffset) per buffer fill: `rows` is an array('q') of 6*n
-    buffer-relative positions, `rows[i] + globaloffset` the absolute ones.  Same refill,
-    sentinel, globaloffset and error behaviour as readfastq_iter
-    (/root/reference/src/fastqandfurious.py:241-279)."""
-    globaloffset = -1
-    offset = 0
-    buf, eof = _F.read(fh, fbufsize)
-    buf = b'\n' + buf
-    while True:
-        rows, end_state, end_offset = scan_buffer(buf, offset, eof)
-        if len(rows):
-            yield buf, rows, globaloffset
-        offset = end_offset
-        if end_state == _F._END_OK:
-            return
-        if end_state != _F._END_REFILL:
-            _F._raise_for_end(end_state, globaloffset + offset)
-        globaloffset += offset
-        tmp_buf, eof = _F.read(fh, fbufsize)
-        buf = buf[offset:] + tmp_buf
-        del tmp_buf
-        offset = 0
+iter_tables = _F.iter_tables        # one (buf, rows, globaloffset) per buffer fill: the refill loop of readfastq_iter's batched front
 
 
 def build_index(fh, fh_index, fbufsize=1 << 24, entrypos=None):
@@ -91,9 +69,8 @@ def build_index(fh, fh_index, fbufsize=1 << 24, entrypos=None):
         if f is not None:
             # a real file and the GPU scanner: the native stream front end (ffq_stream_*) reads
             # ahead into pinned memory and hands back whole tables; no per-fill Python copies
-            from . import hip
             n = 0
-            st = hip.FileStream(hip.default_context(), f[0], fbufsize, start=f[1])
+            st = _hip.FileStream(_hip.default_context(), f[0], fbufsize, start=f[1])
             try:
                 for rows, _fill, _off, end_state, err in st:
                     if rows.shape[0]:
@@ -174,8 +151,7 @@ def select_rows_device(ctx, table, min_seq_len=None, max_seq_len=None):
     import torch
     n = int(table.shape[0])
     out = torch.empty_like(table)
-    lo = -(1 << 62) if min_seq_len is None else int(min_seq_len)
-    hi = (1 << 62) if max_seq_len is None else int(max_seq_len)
+    lo, hi = _hip.length_bounds(min_seq_len, max_seq_len)
     k = ctx.table_select_seqlen(table.data_ptr(), n, lo, hi, out.data_ptr()) if n else 0
     return out[:k]
 
@@ -194,5 +170,6 @@ def select_column_device(ctx, buf, table, which, sentinel=True, add=None, value_
     out = torch.empty(max(total, 16), dtype=torch.int8, device=table.device)
     rc, nb = ctx.table_gather_column(buf.data_ptr(), buf.numel(), table.data_ptr(), n, which, out.data_ptr(), total,
                                      off.data_ptr(), sentinel=sentinel, add=add, value_add=value_add)
-    assert rc == 0 and nb == total
+    if rc != 0 or nb != total:
+        raise RuntimeError("select_column_device: gathered %d of %d bytes (code %d)" % (nb, total, rc))
     return out[:total], off

@@ -174,15 +174,7 @@ class ScanOutput:
         self.comm = None              # {handoff_ms, handoff_bytes, allgather_ms, rescan_rounds, regathers}
 
 
-_ERR_TEXT = {_hip.END_ERR_FINAL_QUAL: "Incomplete final quality string at byte",
-             _hip.END_ERR_INCOMPLETE: "Incomplete entry at byte %i",
-             _hip.END_ERR_INVALID: "Entry is invalid at byte %i"}
-
-
-def raise_stream_error(end_state, byte):
-    """The reference iterator's ValueErrors (fastqandfurious.py:262, :269, :272)."""
-    text = _ERR_TEXT[end_state]
-    raise ValueError(text % byte if "%" in text else text)
+raise_stream_error = _hip.raise_for_end        # the reference iterator's ValueErrors (fastqandfurious.py:262, :269, :272)
 
 
 def _output(res, rc):
@@ -613,8 +605,7 @@ class FileShard:
         if n_own == 0:
             return 0, np.zeros(0, dtype=np.int64)
         self.d_sel, self.d_idx = c.dev_alloc(n_own * 48), c.dev_alloc(n_own * 8)
-        lo = 0 if min_len is None else int(min_len)
-        hi = (1 << 62) if max_len is None else int(max_len)
+        lo, hi = _hip.length_bounds(min_len, max_len, open_low=0)
         k = c.table_select_seqlen_idx(self.d_table + int(res.row_lo) * 48, n_own, lo, hi, self.d_sel, self.d_idx)
         self.n_kept = k
         idx = np.empty(k, dtype=np.int64)
@@ -667,7 +658,9 @@ class FileShard:
         d_buf, d_rows = c.dev_alloc(b - a + 64), c.dev_alloc(n * 48)
         d_col, d_off = c.dev_alloc(need + 64), c.dev_alloc((n + 1) * 8)
         try:
-            assert c.load_fd(self.fd, a, b - a, d_buf) == b - a
+            got = c.load_fd(self.fd, a, b - a, d_buf)
+            if got != b - a:
+                raise _hip.FFQError(_hip.E_INTERNAL, "quals_from_file: %d of the %d bytes at %d could be read" % (got, b - a, a))
             c.h2d(d_rows, np.ascontiguousarray(rows))
             rc, nb = c.table_gather_column(d_buf, b - a, d_rows, n, "quality", d_col, need + 64, d_off, sentinel=False, add=a, value_add=-33)
             _hip.check(rc)
@@ -728,14 +721,13 @@ def is_gzip(path_or_fd):
 
 class _Shifted:
     """bytes [base, base + len) of a stream held in memory, sliced with STREAM offsets (what a map of the file is for a
-    plain one): view[a:b] -> a memoryview, or, as_bytes, a bytes object."""
+    plain one): view[a:b] -> a memoryview."""
 
-    def __init__(self, arr, base, as_bytes=False):
-        self._mv, self._base, self._as_bytes = memoryview(arr), int(base), as_bytes
+    def __init__(self, arr, base):
+        self._mv, self._base = memoryview(arr), int(base)
 
     def __getitem__(self, sl):
-        v = self._mv[sl.start - self._base:sl.stop - self._base]
-        return v.tobytes() if self._as_bytes else v
+        return self._mv[sl.start - self._base:sl.stop - self._base]
 
     def release(self):
         pass
@@ -808,7 +800,8 @@ class BgzfFileShard(FileShard):
         self.h_own = np.empty(max(own, 1), dtype=np.uint8)[:own]
         if own:
             got = _hip.bgzf_range(self.fd, self.c_lo, self.c_hi, out=self.h_own, threads=self.threads)
-            assert got[2] == own, (got, own)
+            if got[2] != own:
+                raise _hip.FFQError(_hip.E_INTERNAL, "BGZF: this rank's members inflated to %d bytes, their trailers promise %d" % (got[2], own))
             self.ctx.h2d(self.d_ext + self.tail, self.h_own)
         self._h_view = None
         self.loaded = True

@@ -1,5 +1,5 @@
 """The drop-in iterator's rate on one host core, outside bench.py: readfastq_iter over a plain file in /dev/shm with the
-default entryfunc and with entryfunc_phred; WITH_TORCH=1 imports torch first (its objects make every full collection of the
+default entryfunc, entryfunc_phred, entryfunc_namedtuple (bulk paths) and entryfunc_abspos (called per record); WITH_TORCH=1 imports torch first (its objects make every full collection of the
 cycle collector slower: DESIGN_LOG.md).  tools/iter_rate.py [records]"""
 import os, sys, time
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,7 +19,8 @@ def run(ef):
     return k / (time.perf_counter() - t) / 1e6
 try:
     for _ in range(3):
-        print("torch=%s records=%d: entryfunc %.2f M reads/s  entryfunc_phred %.2f  entryfunc_namedtuple %.2f" %
-              (os.environ.get("WITH_TORCH", "0"), n, run(F.entryfunc), run(F.entryfunc_phred), run(F.entryfunc_namedtuple)), flush=True)
+        print("torch=%s records=%d: entryfunc %.2f M reads/s  entryfunc_phred %.2f  entryfunc_namedtuple %.2f  entryfunc_abspos %.2f" %
+              (os.environ.get("WITH_TORCH", "0"), n, run(F.entryfunc), run(F.entryfunc_phred), run(F.entryfunc_namedtuple),
+               run(F.entryfunc_abspos)), flush=True)
 finally:
     os.unlink(p)
