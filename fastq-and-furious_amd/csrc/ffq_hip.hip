@@ -8,6 +8,7 @@
 #endif
 #include "ffq_kernels.h"
 #include "ffq_fasta.h"
+#include "ffq_trim.h"
 #include "ffq_pool.h"
 
 #include <hip/hip_runtime.h>
@@ -172,6 +173,9 @@ struct ffq_ctx {
     int64_t *d_word = nullptr;          // 2 scratch words for the small table queries
     int64_t *h_word = nullptr;          //   and their pinned mirror
     int64_t *d_cut = nullptr, *h_cut = nullptr;    // ffq_table_cut: 6 words
+    TrimBlock *d_trim = nullptr, *h_trim = nullptr;    // ffq_table_trim_quality: the call's counters and their pinned mirror
+    int64_t *trim_list = nullptr;       //   rows left to the wave-per-row launch
+    int64_t trim_list_cap = 0;
     FaHdr *fa_hdr = nullptr;            // FASTA scan: starts, the last start
     // staging for the host-buffer entry points
     uint8_t *stage_d = nullptr;
@@ -268,6 +272,8 @@ static int ctx_create_impl(int device, ffq_ctx *share, ffq_ctx **out)
     if (e == hipSuccess) e = hipMalloc((void **)&c->d_word, 16);
     if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_word, 16, hipHostMallocDefault);
     if (e == hipSuccess) e = hipMalloc((void **)&c->d_cut, 48);
+    if (e == hipSuccess) e = hipMalloc((void **)&c->d_trim, sizeof(TrimBlock));
+    if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_trim, sizeof(TrimBlock), hipHostMallocDefault);
     if (e == hipSuccess) e = hipMalloc((void **)&c->fa_hdr, sizeof(FaHdr));
     if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_cut, 48, hipHostMallocDefault);
     if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_L, sizeof(LineIndex), hipHostMallocDefault);
@@ -334,6 +340,8 @@ extern "C" void ffq_ctx_destroy(ffq_ctx *c)
     (void)hipFree(c->stage_d); (void)hipFree(c->tab_d); (void)hipFree(c->qual_d); (void)hipFree(c->qoff_d);
     if (c->h_word) (void)hipHostFree(c->h_word);
     if (c->h_cut) (void)hipHostFree(c->h_cut);
+    if (c->h_trim) (void)hipHostFree(c->h_trim);
+    (void)hipFree(c->d_trim); (void)hipFree(c->trim_list);
     (void)hipFree(c->d_word); (void)hipFree(c->d_cut); (void)hipFree(c->fa_hdr);
     if (c->h_seq) (void)hipHostFree(c->h_seq);
     if (c->h_ctl) (void)hipHostFree(c->h_ctl);
@@ -1942,6 +1950,43 @@ extern "C" int ffq_table_gather_column(ffq_ctx *c, const uint8_t *d_buf, int64_t
     if (*n_out_bytes > out_cap)
         return fail(FFQ_E_TABLE_FULL, "output holds %lld bytes, the column has %lld", (long long)out_cap,
                     (long long)*n_out_bytes);
+    return FFQ_OK;
+}
+
+// ---- quality trimming: rows of the table edited in place (csrc/ffq_trim.h) -------------------
+extern "C" int ffq_table_trim_quality(ffq_ctx *c, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
+                                      const int64_t *d_table, int64_t n_rows, int qual_base, int cutoff_front,
+                                      int cutoff_back, int64_t *d_out, int64_t stats[3])
+{
+    mark_other(c);
+    if (!c || !stats || n_rows < 0 || n_bytes < 0 || (n_bytes > 0 && !d_buf) || (n_rows > 0 && (!d_table || !d_out)))
+        return fail(FFQ_E_ARG, "ffq_table_trim_quality: bad argument");
+    if (cutoff_front < 0 || cutoff_front > 127 || cutoff_back < 0 || cutoff_back > 127)
+        return fail(FFQ_E_ARG, "ffq_table_trim_quality: cutoffs are 0..127");
+    if (qual_base < 0 || qual_base > 255) return fail(FFQ_E_ARG, "ffq_table_trim_quality: qual_base is 0..255");
+    if (((reinterpret_cast<uintptr_t>(d_table) | reinterpret_cast<uintptr_t>(d_out)) & 15) != 0)
+        return fail(FFQ_E_ARG, "ffq_table_trim_quality: tables must be 16-byte aligned");
+    if (c->pend.active) return fail(FFQ_E_ARG, "ffq_table_trim_quality: a scan is pending on this context");
+    HIPCHK(hipSetDevice(c->device));
+    stats[0] = stats[1] = stats[2] = 0;
+    if (n_rows == 0) return FFQ_OK;
+    int rc = grow_dev(c, &c->trim_list, &c->trim_list_cap, n_rows);
+    if (rc) return rc;
+    hipStream_t st = c->stream;
+    HIPCHK(hipMemsetAsync(c->d_trim, 0, sizeof(TrimBlock), st));
+    // TRIM_WG / TRIM_G rows per workgroup and step; as many workgroups as the device holds at once, striding over the table
+    constexpr int64_t rpb = TRIM_WG / TRIM_G;
+    const int64_t nblk = std::min<int64_t>((n_rows + rpb - 1) / rpb, 2048);
+    hipLaunchKernelGGL(k_trim_rows, dim3((unsigned)nblk), dim3(TRIM_WG), 0, st, d_buf, n_bytes, sentinel ? 1 : 0, add, d_table,
+                       n_rows, qual_base, cutoff_front, cutoff_back, d_out, c->trim_list, c->d_trim);
+    // the rows it left (above TRIM_LONG quality bytes; their number is known on the device only): a wave each
+    const int64_t nblk_long = std::min<int64_t>((n_rows + 3) / 4, 1024);
+    hipLaunchKernelGGL(k_trim_long, dim3((unsigned)nblk_long), dim3(TRIM_WG), 0, st, d_buf, n_bytes, sentinel ? 1 : 0, add,
+                       d_table, qual_base, cutoff_front, cutoff_back, d_out, (const int64_t *)c->trim_list, c->d_trim);
+    HIPCHK(hipMemcpyAsync(c->h_trim, c->d_trim, sizeof(TrimBlock), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    stats[0] = (int64_t)c->h_trim->changed; stats[1] = (int64_t)c->h_trim->removed; stats[2] = (int64_t)c->h_trim->skipped;
     return FFQ_OK;
 }
 

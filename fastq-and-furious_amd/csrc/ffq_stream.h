@@ -339,6 +339,10 @@ struct ffq_stream {
     int64_t f_min = 0, f_max = 0;
     int f_col = 0, f_add = 0;
     int64_t last_scanned = 0, last_kept = 0, last_col_bytes = 0;
+    // quality trimming of every fill's table, in front of the filter (ffq_stream_set_trim)
+    bool trim_on = false;
+    int t_base = 33, t_front = 0, t_back = 0;
+    int64_t last_trim[3] = {0, 0, 0};
     // FFQ_STREAM_PROF=1: where the time of a stream goes (printed when it closes)
     bool prof = false;
     double t_read = 0, t_slot = 0, t_feed = 0, t_scan = 0, t_rows = 0, t_copy = 0;
@@ -1043,6 +1047,33 @@ extern "C" int ffq_stream_set_filter(ffq_stream *s, int64_t min_seq_len, int64_t
     return FFQ_OK;
 }
 
+// Quality trimming in the stream: from the next fill on, every fill's table is trimmed in place on the device
+// (ffq_table_trim_quality) right behind the scan -- in front of the filter, the column gather and the rows' copy back, so
+// that all of them see the trimmed rows.  Refill and carry go by the scan's end offset, not by the table.
+extern "C" int ffq_stream_set_trim(ffq_stream *s, int qual_base, int cutoff_front, int cutoff_back)
+{
+    if (!s) return fail(FFQ_E_ARG, "ffq_stream_set_trim: NULL stream");
+    if (cutoff_front < 0 || cutoff_front > 127 || cutoff_back < 0 || cutoff_back > 127)
+        return fail(FFQ_E_ARG, "ffq_stream_set_trim: cutoffs are 0..127");
+    if (qual_base < 0 || qual_base > 255) return fail(FFQ_E_ARG, "ffq_stream_set_trim: qual_base is 0..255");
+    if (s->flags & FFQ_F_DECODE_QUAL) return fail(FFQ_E_ARG, "ffq_stream_set_trim: the stream decodes every record's qualities (FFQ_F_DECODE_QUAL) "
+                                                              "beside the scan, untrimmed; a filtered stream gathers the trimmed ones "
+                                                              "(ffq_stream_set_filter: column = FFQ_COL_QUALITY, value_add)");
+    if (s->cur >= 0) return fail(FFQ_E_ARG, "ffq_stream_set_trim: the stream has handed out a fill already");
+    s->trim_on = true;
+    s->t_base = qual_base; s->t_front = cutoff_front; s->t_back = cutoff_back;
+    return FFQ_OK;
+}
+
+// {rows changed, bases removed, rows skipped} of the fill ffq_stream_next has just returned
+extern "C" int ffq_stream_trimmed(ffq_stream *s, int64_t stats[3])
+{
+    if (!s || !stats) return fail(FFQ_E_ARG, "ffq_stream_trimmed: NULL argument");
+    if (!s->trim_on) return fail(FFQ_E_ARG, "ffq_stream_trimmed: the stream does not trim (ffq_stream_set_trim)");
+    for (int i = 0; i < 3; i++) stats[i] = s->last_trim[i];
+    return FFQ_OK;
+}
+
 // What the filter did with the fill ffq_stream_next has just returned: h_index[i] = ordinal, among the n_scanned records of
 // the fill, of kept row i (the caller that owes its own caller one item per record puts the kept ones back by it); the
 // gathered column: bytes of kept row i = h_col[h_coloff[i] : h_coloff[i + 1]].  Pinned memory, valid until the next call.
@@ -1147,6 +1178,12 @@ extern "C" int ffq_stream_next(ffq_stream *s, const int64_t **h_rows, int64_t *n
     const double tp2 = s->prof ? stream_now() : 0;
     int64_t n_out = res.n_records;
     s->last_scanned = res.n_records; s->last_kept = res.n_records; s->last_col_bytes = 0;
+    if (s->trim_on) {
+        // ---- the fill's rows are trimmed where they lie, over the buffer and the `add` the scan was given ----
+        int rc2 = ffq_table_trim_quality(c, sl.d + start - mis, len + mis, 0, s->globaloffset - mis, b->dtab, res.n_records,
+                                         s->t_base, s->t_front, s->t_back, b->dtab, s->last_trim);
+        if (rc2) return rc2;
+    }
     if (s->filter_on) {
         // ---- push-down: the fill's table is filtered (and one component of the kept rows gathered) on the DEVICE, before
         // anything is copied back: a dropped record costs the host nothing (doc/user-guide.rst:153-180) -----------------

@@ -224,6 +224,91 @@ class entryfunc_lengthfilter:
         return (buf[(pos[0] + 1):pos[1]], buf[pos[2]:pos[3]], buf[pos[4]:pos[5]])
 
 
+def _trim_end(d):
+    """Bases the running-sum rule takes off the end that `d` = cutoff - (q - base) is walked from: the walk stops when the
+    sum goes negative; the cut is behind the FIRST maximum of the sums in front of that, if it is above 0."""
+    c = np.cumsum(d)
+    neg = np.flatnonzero(c < 0)
+    if neg.size:
+        c = c[:neg[0]]
+    if not c.size:
+        return 0
+    k = int(np.argmax(c))               # (the first maximum)
+    return k + 1 if c[k] > 0 else 0
+
+
+def quality_trim_span(quality, cutoff_back, cutoff_front=0, qual_base=33):
+    """(start, stop) of the quality-trimmed read within `quality` (bytes of one record's quality line): the running-sum
+    rule of BWA's and cutadapt's -q, either end with its own cutoff and independent of the other (include/ffq.h,
+    ffq_table_trim_quality, states it as a loop).  A read that is trimmed away is (0, 0)."""
+    n = len(quality)
+    if n == 0:
+        return 0, 0
+    q = np.frombuffer(quality, dtype=np.uint8).astype(np.int64) - qual_base
+    start = _trim_end(cutoff_front - q)
+    stop = n - _trim_end(cutoff_back - q[::-1])
+    return (start, stop) if start < stop else (0, 0)
+
+
+def trimmable(buf, pos):
+    """Does the device trim this row (ffq_table_trim_quality's eligibility)?  pos2..pos5 inside `buf`, sequence and
+    quality of one length, no newline in the quality (a wrapped record)."""
+    p2, p3, p4, p5 = pos[2], pos[3], pos[4], pos[5]
+    return (p2 >= 0 and p4 >= 0 and p2 <= p3 <= len(buf) and p4 <= p5 <= len(buf) and p3 - p2 == p5 - p4
+            and b'\n' not in buf[p4:p5])
+
+
+class entryfunc_qualitytrim:
+    """Quality trimming as an entryfunc OBJECT -- the other use the reference's user guide names for a table of positions
+    (doc/user-guide.rst:196-204: "trimming either end of the read could be done by ... modifying the values in a table of
+    indices"): the running-sum rule of BWA / cutadapt -q (quality_trim_span) moves pos2..pos5 of the record inwards, a read
+    whose trimmed length is outside [min_len, max_len] gives None, any other the component `column` says ("entry": the
+    (header, sequence, quality) tuple of entryfunc; "sequence", "quality", "header") cut at the trimmed positions.  A
+    record the rule does not apply to (wrapped lines, sequence and quality of different lengths) is left as it is.
+
+    Called per record (any scanner) it works on a copy of `pos`: the caller's posbuffer is not touched.  readfastq_iter
+    RECOGNISES the unmodified class when the scanner is the GPU one: the stream front end then trims every fill's table
+    on the device right behind the scan (ffq_stream_set_trim), drops what became too short there and gathers the one
+    component of the kept rows (ffq_stream_set_filter) -- no quality string reaches the interpreter to be trimmed.  Same
+    items, same order, one per record."""
+
+    yield_dropped = True
+
+    def __init__(self, cutoff_back, cutoff_front=0, qual_base=33, min_len=None, max_len=None, column="entry"):
+        if column not in ("sequence", "header", "quality", "entry"):
+            raise ValueError("column must be 'sequence', 'header', 'quality' or 'entry'")
+        if not (0 <= int(cutoff_back) <= 127 and 0 <= int(cutoff_front) <= 127):
+            raise ValueError("cutoffs are 0..127")
+        if not 0 <= int(qual_base) <= 255:
+            raise ValueError("qual_base is 0..255")
+        self.cutoff_back, self.cutoff_front, self.qual_base = int(cutoff_back), int(cutoff_front), int(qual_base)
+        self.min_len = None if min_len is None else int(min_len)
+        self.max_len = None if max_len is None else int(max_len)
+        self.column = column
+
+    def trimmed_pos(self, buf, pos):
+        """A copy of the six positions with the rule applied."""
+        pos = list(pos)
+        if trimmable(buf, pos):
+            start, stop = quality_trim_span(buf[pos[4]:pos[5]], self.cutoff_back, self.cutoff_front, self.qual_base)
+            pos[2], pos[3], pos[4], pos[5] = pos[2] + start, pos[2] + stop, pos[4] + start, pos[4] + stop
+        return pos
+
+    def __call__(self, buf, pos, globaloffset=None):
+        pos = self.trimmed_pos(buf, pos)
+        length = pos[3] - pos[2]
+        if (self.min_len is not None and length < self.min_len) or (self.max_len is not None and length > self.max_len):
+            return None
+        c = self.column
+        if c == "sequence":
+            return buf[pos[2]:pos[3]]
+        if c == "header":
+            return buf[(pos[0] + 1):pos[1]]
+        if c == "quality":
+            return buf[pos[4]:pos[5]]
+        return (buf[(pos[0] + 1):pos[1]], buf[pos[2]:pos[3]], buf[pos[4]:pos[5]])
+
+
 def entryfunc_abspos(buf: bytes, pos, globaloffset: int):
     """Absolute stream positions: pos[i] += globaloffset, in place; returns
     the same `pos` object (reference :186-195)."""
@@ -248,6 +333,15 @@ def _pushes_down(entryfunc):
     t = type(entryfunc)
     return t is entryfunc_lengthfilter or (t.__call__ is entryfunc_lengthfilter.__call__ and
                                            getattr(t, "keeps", None) is getattr(entryfunc_lengthfilter, "keeps", None))
+
+
+def _pushes_down_trim(entryfunc):
+    """... and its own quality trimmer, unchanged (a subclass with a __call__ or trimmed_pos of its own is called per record)."""
+    if not isinstance(entryfunc, entryfunc_qualitytrim):
+        return False
+    t = type(entryfunc)
+    return t is entryfunc_qualitytrim or (t.__call__ is entryfunc_qualitytrim.__call__ and
+                                          t.trimmed_pos is entryfunc_qualitytrim.trimmed_pos)
 
 
 def _table_entries(entryfunc, buf, rows, shift, quals=None):
@@ -427,9 +521,12 @@ def readfastq_iter(fh: typing.BinaryIO, fbufsize: int,
         # the native stream front end: a real file, a gzip file, or anything with readinto() / read();
         # with entryfunc_phred the qualities of every fill are decoded on the device
         st = open_stream(fh, fbufsize, entryfunc is entryfunc_phred) if entryfunc is entryfunc_phred else open_stream(fh, fbufsize)
-        if st is not None and _pushes_down(entryfunc):
-            # push-down: the filter runs on the device, on every fill's table, before anything is copied back
+        if st is not None and (_pushes_down(entryfunc) or _pushes_down_trim(entryfunc)):
+            # push-down: the filter runs on the device, on every fill's table, before anything is copied back -- behind the
+            # quality trimming of the rows, if that is what the entryfunc does
             try:
+                if isinstance(entryfunc, entryfunc_qualitytrim):
+                    st.set_trim(entryfunc.cutoff_back, entryfunc.cutoff_front, entryfunc.qual_base)
                 st.set_filter(entryfunc.min_len, entryfunc.max_len, None if entryfunc.column == "entry" else entryfunc.column)
             except BaseException:
                 st.close()                 # (the native stream, its pinned buffers and its feeder thread; a gzip stream's hook)

@@ -84,6 +84,7 @@ SYMBOLS = (
     "ffq_shard_host_step", "ffq_shard_host_free", "ffq_stream_set_filter", "ffq_stream_selected",
     "ffq_shard_create_hosted",
     "ffq_shard_create2", "ffq_shard_scan_fd_slabs", "ffq_table_select_seqlen_idx", "ffq_shard_get_info", "ffq_shard_set_timeout", "ffq_shard_set_serial", "ffq_shard_abort", "ffq_shard_inject_stall",
+    "ffq_table_trim_quality", "ffq_stream_set_trim", "ffq_stream_trimmed",
 )
 
 
@@ -314,6 +315,7 @@ def lib():
         L.ffq_table_select_seqlen.argtypes = [vp, vp, i64, i64, i64, vp, P(i64)]
         L.ffq_table_select_seqlen_idx.argtypes = [vp, vp, i64, i64, i64, vp, vp, P(i64)]
         L.ffq_table_cut.argtypes = [vp, vp, i64, i64, i64, P(i64)]
+        L.ffq_table_trim_quality.argtypes = [vp, vp, i64, i32, i64, vp, i64, i32, i32, i32, vp, P(i64)]
         L.ffq_table_gather_column.argtypes = [vp, vp, i64, i32, i64, vp, i64, i32, i32, i32, i32, vp, i64, vp, P(i64)]
         L.ffq_stream_open.argtypes = [vp, i32, i64, P(vp)]
         L.ffq_stream_next.argtypes = [vp, P(vp), P(i64), P(i32), P(i64), P(vp), P(i64), P(i64)]
@@ -366,6 +368,8 @@ def lib():
         L.ffq_shard_host_free.argtypes = [vp]
         L.ffq_shard_host_free.restype = None
         L.ffq_stream_set_filter.argtypes = [vp, i64, i64, i32, i32]
+        L.ffq_stream_set_trim.argtypes = [vp, i32, i32, i32]
+        L.ffq_stream_trimmed.argtypes = [vp, P(i64)]
         L.ffq_stream_selected.argtypes = [vp, P(vp), P(i64), P(vp), P(vp), P(i64)]
         L.ffq_stream_quals.argtypes = [vp, P(vp), P(vp), P(i64)]
         L.ffq_stream_close.restype = None
@@ -643,6 +647,19 @@ class Context:
         check(rc, allow=(E_TABLE_FULL,))
         return rc, nb.value
 
+    def table_trim_quality(self, d_buf, n_bytes, d_table, n_rows, cutoff_back, cutoff_front=0, qual_base=33, d_out=None,
+                           sentinel=True, add=None):
+        """Quality-trim the rows of a device table (ffq_table_trim_quality: the running-sum rule of BWA / cutadapt -q,
+        either end with its own cutoff): pos2..pos5 of every eligible row move inwards, every other row is copied
+        unchanged.  d_out: n_rows rows of room (None: in place); raw device pointers; d_buf / n_bytes / sentinel / add as
+        for table_gather_column.  Returns (rows changed, bases removed, rows skipped)."""
+        add = _add(add, sentinel)
+        stats = (ctypes.c_int64 * 3)()
+        check(lib().ffq_table_trim_quality(self.handle, ctypes.c_void_p(d_buf), int(n_bytes), int(bool(sentinel)), int(add),
+                                           ctypes.c_void_p(d_table), int(n_rows), int(qual_base), int(cutoff_front),
+                                           int(cutoff_back), ctypes.c_void_p(d_table if d_out is None else d_out), stats))
+        return int(stats[0]), int(stats[1]), int(stats[2])
+
     def synth_single(self, dptr, first, count, seed=42):
         check(lib().ffq_synth_single(self.handle, ctypes.c_void_p(dptr), int(first), int(count), int(seed)))
 
@@ -903,6 +920,17 @@ class _Stream:
         lo, hi = length_bounds(min_seq_len, max_seq_len)
         check(lib().ffq_stream_set_filter(self._h, lo, hi, self.COLUMNS[column], int(value_add)))
         self.filtered = True
+
+    def set_trim(self, cutoff_back, cutoff_front=0, qual_base=33):
+        """Quality trimming in the stream (ffq_stream_set_trim; before the first fill): every fill's rows are trimmed on
+        the device right behind the scan, in front of the filter and the column gather (set_filter)."""
+        check(lib().ffq_stream_set_trim(self._h, int(qual_base), int(cutoff_front), int(cutoff_back)))
+
+    def trimmed(self):
+        """(rows changed, bases removed, rows skipped) of the fill the iteration has just yielded (set_trim)."""
+        stats = (ctypes.c_int64 * 3)()
+        check(lib().ffq_stream_trimmed(self._h, stats))
+        return int(stats[0]), int(stats[1]), int(stats[2])
 
     def selected(self):
         """(index int64[kept], n_scanned, col int8[] or None, coloff int64[kept + 1] or None) of the fill the iteration has

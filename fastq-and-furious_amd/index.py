@@ -156,6 +156,35 @@ def select_rows_device(ctx, table, min_seq_len=None, max_seq_len=None):
     return out[:k]
 
 
+def trim_rows(buf, table, cutoff_back, cutoff_front=0, qual_base=33, shift=0):
+    """Quality-trimmed copy of a table, on the host: pos2..pos5 of every row the rule applies to (_F.trimmable: positions
+    minus `shift` index `buf`) moved inwards by the running-sum rule (_F.quality_trim_span); the same rows, none dropped
+    -- select_rows then drops what became too short.  The user guide's "modifying the values in a table of indices"
+    (doc/user-guide.rst:196-204)."""
+    t = np.array(table, dtype=np.int64).reshape(-1, 6)
+    buf = bytes(buf) if not isinstance(buf, bytes) else buf
+    for row in t:
+        rel = (row - shift).tolist()
+        if _F.trimmable(buf, rel):
+            start, stop = _F.quality_trim_span(buf[rel[4]:rel[5]], cutoff_back, cutoff_front, qual_base)
+            row[2:6] = (row[2] + start, row[2] + stop, row[4] + start, row[4] + stop)
+    return t
+
+
+def trim_rows_device(ctx, buf, table, cutoff_back, cutoff_front=0, qual_base=33, sentinel=True, add=None, out=None):
+    """trim_rows on the GPU: `buf` is the CUDA uint8 tensor the rows of `table` (CUDA int64[n][6]) were scanned from,
+    sentinel / add as that scan had them.  Returns (tensor with the trimmed rows -- a new one, or `out`, which may be
+    `table` itself: in place --, (rows changed, bases removed, rows skipped)).  One C-ABI call
+    (ffq_table_trim_quality)."""
+    import torch
+    n = int(table.shape[0])
+    if out is None:
+        out = torch.empty_like(table)
+    stats = ctx.table_trim_quality(buf.data_ptr(), buf.numel(), table.data_ptr(), n, cutoff_back, cutoff_front, qual_base,
+                                   d_out=out.data_ptr(), sentinel=sentinel, add=add)
+    return out, stats
+
+
 def select_column_device(ctx, buf, table, which, sentinel=True, add=None, value_add=0):
     """One component of every row, packed, on the GPU: `buf` is the CUDA uint8 tensor the rows of
     `table` (CUDA int64[n][6]) were scanned from; which = "header" | "sequence" | "quality".

@@ -280,6 +280,29 @@ int ffq_table_gather_column(ffq_ctx *ctx, const uint8_t *d_buf, int64_t n_bytes,
                             int col_end, int value_add, int8_t *d_out, int64_t out_cap, int64_t *d_off,
                             int64_t *n_out_bytes);
 
+/* Quality trimming by MODIFYING rows -- the other thing the user guide's table of indices is for ("trimming either end
+ * of the read could be done by ... modifying the values in a table of indices", doc/user-guide.rst:196-204) -- with the
+ * running-sum rule of BWA's and cutadapt's -q.  For one row, q[0..n) = buf[pos4:pos5] (unsigned bytes):
+ *     start = 0; stop = n
+ *     s = 0; best = 0; for i = 0 .. n-1:  s += cutoff_front - (q[i] - qual_base); if s < 0: break;
+ *                                         if s > best: best = s, start = i + 1          (5' end)
+ *     s = 0; best = 0; for i = n-1 .. 0:  s += cutoff_back  - (q[i] - qual_base); if s < 0: break;
+ *                                         if s > best: best = s, stop = i               (3' end, independent of the 5')
+ *     if start >= stop: start = stop = 0                    (trimmed away: the header stays, the length is 0)
+ * and the row becomes pos0, pos1, pos2 + start, pos2 + stop, pos4 + start, pos4 + stop.  Ties keep the first maximum; a
+ * cutoff of 0 leaves an end alone unless bytes lie below qual_base; the sums are carried in 64 bits.  A row is trimmed
+ * only if pos2..pos5 - add are all >= 0, pos2 <= pos3 and pos4 <= pos5 lie inside the buffer (with sentinel, coordinate
+ * 0 is the virtual "\n"), pos3 - pos2 == pos5 - pos4 and no quality byte is "\n"; every other row -- wrapped records,
+ * FASTA rows (-1), rows that point outside the buffer -- is copied unchanged and counted as skipped; no byte outside
+ * [d_buf, d_buf + n_bytes) is read.  d_buf / n_bytes / sentinel / add: as for ffq_table_gather_column.  d_out: n_rows
+ * rows; it MAY be d_table (rows are independent).  Both tables 16-byte aligned.  stats = {rows changed, bases removed
+ * (front + back, summed over the rows), rows skipped}.  FFQ_E_ARG: cutoffs outside 0..127, qual_base outside 0..255, a
+ * scan pending on the context.  One host wait.  After it, ffq_table_select_seqlen drops what became too short and
+ * ffq_table_gather_column returns the trimmed sequence or (value_add = -33) the trimmed, decoded quality.             */
+int ffq_table_trim_quality(ffq_ctx *ctx, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
+                           const int64_t *d_table, int64_t n_rows, int qual_base, int cutoff_front, int cutoff_back,
+                           int64_t *d_out, int64_t stats[3]);
+
 /* ---- FASTA (reference: the plug-in scanner entrypos_fasta, fastqandfurious.py:103-143) -------
  * Every COMPLETE entry of a buffer, i.e. the repeated scanner call with offset := pos[3]:
  * rows = pos0 ('>'), pos1 (header end), pos2, pos3 (the "\n" of the next "\n>") + add, -1, -1.
@@ -355,6 +378,14 @@ int  ffq_stream_path(ffq_stream *s);
 int  ffq_stream_set_filter(ffq_stream *s, int64_t min_seq_len, int64_t max_seq_len, int column, int value_add);
 int  ffq_stream_selected(ffq_stream *s, const int64_t **h_index, int64_t *n_scanned, const int8_t **h_col,
                          const int64_t **h_coloff, int64_t *n_col_bytes);
+/* Quality trimming in the stream (any kind of stream, before the first ffq_stream_next; not with FFQ_F_DECODE_QUAL,
+ * whose qualities are decoded beside the scan: a filtered stream gathers the TRIMMED quality, column = FFQ_COL_QUALITY,
+ * value_add): every fill's table is trimmed in place on the device (ffq_table_trim_quality) right behind the scan -- in
+ * front of the filter, the column gather and the rows' copy back, which all see the trimmed rows; pos0 / pos1 and the
+ * refill (it goes by the scan's end offset) are untouched.  ffq_stream_trimmed: {rows changed, bases removed, rows
+ * skipped} of the fill ffq_stream_next has just returned.                                                          */
+int  ffq_stream_set_trim(ffq_stream *s, int qual_base, int cutoff_front, int cutoff_back);
+int  ffq_stream_trimmed(ffq_stream *s, int64_t stats[3]);
 /* The same over a gzip-compressed file (what FORMAT_OPENERS['gz'] / automagic_open hand to
  * readfastq_iter, fastqandfurious.py:282-334): the stream's reader thread inflates (zlib; concatenated
  * members, zero padding behind the last one) straight into the pinned chunk buffers -- decompression
