@@ -9,6 +9,7 @@
 #include "ffq_kernels.h"
 #include "ffq_fasta.h"
 #include "ffq_trim.h"
+#include "ffq_render.h"
 #include "ffq_pool.h"
 
 #include <hip/hip_runtime.h>
@@ -176,6 +177,9 @@ struct ffq_ctx {
     TrimBlock *d_trim = nullptr, *h_trim = nullptr;    // ffq_table_trim_quality: the call's counters and their pinned mirror
     int64_t *trim_list = nullptr;       //   rows left to the wave-per-row launch
     int64_t trim_list_cap = 0;
+    RenderBlock *d_render = nullptr, *h_render = nullptr;  // ffq_table_render_fastq: the call's counters and their pinned mirror
+    int64_t *render_list = nullptr;     //   (row, place in the output) of the rows left to the wave-per-row launch
+    int64_t render_list_cap = 0;
     FaHdr *fa_hdr = nullptr;            // FASTA scan: starts, the last start
     // staging for the host-buffer entry points
     uint8_t *stage_d = nullptr;
@@ -274,6 +278,8 @@ static int ctx_create_impl(int device, ffq_ctx *share, ffq_ctx **out)
     if (e == hipSuccess) e = hipMalloc((void **)&c->d_cut, 48);
     if (e == hipSuccess) e = hipMalloc((void **)&c->d_trim, sizeof(TrimBlock));
     if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_trim, sizeof(TrimBlock), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMalloc((void **)&c->d_render, sizeof(RenderBlock));
+    if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_render, sizeof(RenderBlock), hipHostMallocDefault);
     if (e == hipSuccess) e = hipMalloc((void **)&c->fa_hdr, sizeof(FaHdr));
     if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_cut, 48, hipHostMallocDefault);
     if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_L, sizeof(LineIndex), hipHostMallocDefault);
@@ -342,6 +348,8 @@ extern "C" void ffq_ctx_destroy(ffq_ctx *c)
     if (c->h_cut) (void)hipHostFree(c->h_cut);
     if (c->h_trim) (void)hipHostFree(c->h_trim);
     (void)hipFree(c->d_trim); (void)hipFree(c->trim_list);
+    if (c->h_render) (void)hipHostFree(c->h_render);
+    (void)hipFree(c->d_render); (void)hipFree(c->render_list);
     (void)hipFree(c->d_word); (void)hipFree(c->d_cut); (void)hipFree(c->fa_hdr);
     if (c->h_seq) (void)hipHostFree(c->h_seq);
     if (c->h_ctl) (void)hipHostFree(c->h_ctl);
@@ -1987,6 +1995,59 @@ extern "C" int ffq_table_trim_quality(ffq_ctx *c, const uint8_t *d_buf, int64_t 
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
     stats[0] = (int64_t)c->h_trim->changed; stats[1] = (int64_t)c->h_trim->removed; stats[2] = (int64_t)c->h_trim->skipped;
+    return FFQ_OK;
+}
+
+// ---- FASTQ text from (buffer, table) (csrc/ffq_render.h) ---------------------------------------
+extern "C" int ffq_table_render_fastq(ffq_ctx *c, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
+                                      const int64_t *d_table, int64_t n_rows, uint8_t *d_out, int64_t out_cap,
+                                      int64_t *d_off, int64_t stats[3])
+{
+    mark_other(c);
+    if (!c || !stats || n_rows < 0 || n_bytes < 0 || out_cap < 0 || (n_bytes > 0 && !d_buf) || (n_rows > 0 && !d_table) ||
+        (out_cap > 0 && !d_out))
+        return fail(FFQ_E_ARG, "ffq_table_render_fastq: bad argument");
+    if ((reinterpret_cast<uintptr_t>(d_table) & 15) != 0 || (reinterpret_cast<uintptr_t>(d_off) & 7) != 0)
+        return fail(FFQ_E_ARG, "ffq_table_render_fastq: the table must be 16-byte aligned, the offsets 8-byte");
+    if (c->pend.active) return fail(FFQ_E_ARG, "ffq_table_render_fastq: a scan is pending on this context");
+    HIPCHK(hipSetDevice(c->device));
+    stats[0] = stats[1] = stats[2] = 0;
+    hipStream_t st = c->stream;
+    if (n_rows == 0) {
+        if (d_off) {
+            HIPCHK(hipMemsetAsync(d_off, 0, sizeof(int64_t), st));
+            HIPCHK(hipStreamSynchronize(st));
+        }
+        return FFQ_OK;
+    }
+    const int64_t nblk = (n_rows + RENDER_WG - 1) / RENDER_WG;
+    int rc = grow_dev(c, &c->col_sum, &c->col_sum_cap, nblk);
+    if (!rc) rc = grow_dev(c, &c->render_list, &c->render_list_cap, 2 * n_rows);
+    if (!rc && !c->col_res) {
+        hipError_t e = hipMalloc((void **)&c->col_res, sizeof(DevRes));
+        if (e != hipSuccess) rc = fail(FFQ_E_NOMEM, "hipMalloc failed: %s", hipGetErrorString(e));
+    }
+    if (rc) return rc;
+    const int s = sentinel ? 1 : 0;
+    HIPCHK(hipMemsetAsync(c->d_render, 0, sizeof(RenderBlock), st));
+    hipLaunchKernelGGL(k_render_sum, dim3((unsigned)std::min<int64_t>(nblk, 2048)), dim3(RENDER_WG), 0, st, n_bytes, s, add,
+                       d_table, n_rows, nblk, c->col_sum, c->d_render);
+    if ((rc = launch_scan_i64v(c, st, c->col_sum, nblk, n_rows, c->col_res))) return rc;
+    hipLaunchKernelGGL(k_render_rows, dim3((unsigned)nblk), dim3(RENDER_WG), 0, st, d_buf, n_bytes, s, add, d_table, n_rows,
+                       (const long long *)c->col_sum, (const DevRes *)c->col_res, d_out, out_cap, d_off, c->render_list,
+                       c->d_render);
+    // the rows it left (above RENDER_LONG output bytes; their number is known on the device only): a wave each
+    const int64_t nblk_long = std::min<int64_t>((n_rows + 3) / 4, 1024);
+    hipLaunchKernelGGL(k_render_long, dim3((unsigned)nblk_long), dim3(RENDER_WG), 0, st, d_buf, n_bytes, s, add, d_table, n_rows,
+                       d_out, (const int64_t *)c->render_list, (const RenderBlock *)c->d_render);
+    HIPCHK(hipMemcpyAsync(c->h_render, c->d_render, sizeof(RenderBlock), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    stats[0] = (int64_t)c->h_render->total; stats[1] = (int64_t)c->h_render->rendered;
+    stats[2] = n_rows - stats[1];
+    if (stats[0] > out_cap)
+        return fail(FFQ_E_TABLE_FULL, "output holds %lld bytes, the rendered rows have %lld", (long long)out_cap,
+                    (long long)stats[0]);
     return FFQ_OK;
 }
 

@@ -87,6 +87,9 @@ struct StreamBufs {
     int64_t col_cap = 0;
     int64_t *dcoff = nullptr, *hcoff = nullptr;
     int64_t coff_cap = 0;
+    // rendering (ffq_stream_set_render): the fill's FASTQ text
+    uint8_t *dren = nullptr, *hren = nullptr;
+    int64_t ren_cap = 0;
     ReadPool *pool = nullptr;    // the context's helper threads (not owned)
 };
 
@@ -110,6 +113,8 @@ static void streambufs_free(StreamBufs *b)
     if (b->hidx) (void)hipHostFree(b->hidx);
     if (b->hcol) (void)hipHostFree(b->hcol);
     if (b->hcoff) (void)hipHostFree(b->hcoff);
+    if (b->hren) (void)hipHostFree(b->hren);
+    (void)hipFree(b->dren);
     (void)hipFree(b->dsel); (void)hipFree(b->didx); (void)hipFree(b->dcol); (void)hipFree(b->dcoff);
     (void)hipFree(b->dtab); (void)hipFree(b->dqual); (void)hipFree(b->dqoff);
     for (auto &st : b->cs) if (st) (void)hipStreamDestroy(st);
@@ -343,6 +348,9 @@ struct ffq_stream {
     bool trim_on = false;
     int t_base = 33, t_front = 0, t_back = 0;
     int64_t last_trim[3] = {0, 0, 0};
+    // FASTQ text of every fill's table, behind the trim and the filter (ffq_stream_set_render)
+    bool render_on = false;
+    int64_t last_render[3] = {0, 0, 0};
     // FFQ_STREAM_PROF=1: where the time of a stream goes (printed when it closes)
     bool prof = false;
     double t_read = 0, t_slot = 0, t_feed = 0, t_scan = 0, t_rows = 0, t_copy = 0;
@@ -788,6 +796,43 @@ static int stream_alloc_sel(ffq_stream *s, int64_t rows, int64_t bytes)
     return FFQ_OK;
 }
 
+// device / pinned buffer for the rendered text of a fill
+static int stream_alloc_render(ffq_stream *s, int64_t bytes)
+{
+    StreamBufs *b = s->b;
+    if (bytes <= b->ren_cap) return FFQ_OK;
+    NearGpu near(s->c);
+    if (b->hren) (void)hipHostFree(b->hren);
+    (void)hipFree(b->dren);
+    b->hren = nullptr; b->dren = nullptr; b->ren_cap = 0;
+    if (hipMalloc((void **)&b->dren, (size_t)bytes) != hipSuccess ||
+        hipHostMalloc((void **)&b->hren, (size_t)bytes, hipHostMallocDefault) != hipSuccess)
+        return fail(FFQ_E_NOMEM, "ffq_stream: no memory for %lld rendered bytes", (long long)bytes);
+    b->ren_cap = bytes;
+    return FFQ_OK;
+}
+
+// The rows the fill hands out (trimmed and filtered, if the stream does that) as FASTQ text, on the device, and its copy
+// back enqueued.  BOUND: the rows of a fill are records of the fill that do not overlap, and a scanned record never
+// renders longer than it was -- "@header\n", "sequence\n" and "quality\n" are copied, the '+' line becomes the bare "+\n"
+// (it had at least that), a trim only takes bytes away -- except a record whose quality ends with the buffer, without a newline, which gains one
+// byte: a fill of `len` bytes renders to at most len + 1.
+static int stream_render(ffq_stream *s, const uint8_t *d_buf, int64_t len, int64_t add, const int64_t *d_rows, int64_t n)
+{
+    StreamBufs *b = s->b;
+    s->last_render[0] = s->last_render[1] = s->last_render[2] = 0;
+    if (n <= 0) return FFQ_OK;
+    int rc = stream_alloc_render(s, len + 64);
+    if (rc) return rc;
+    rc = ffq_table_render_fastq(s->c, d_buf, len, 0, add, d_rows, n, b->dren, len + 1, nullptr, s->last_render);
+    if (rc == FFQ_E_TABLE_FULL)
+        return fail(FFQ_E_INTERNAL, "ffq_stream: a fill of %lld bytes rendered to %lld", (long long)len, (long long)s->last_render[0]);
+    if (rc) return rc;
+    if (s->last_render[0] > 0)
+        HIPCHK(hipMemcpyAsync(b->hren, b->dren, (size_t)s->last_render[0], hipMemcpyDeviceToHost, s->c->stream));
+    return FFQ_OK;
+}
+
 static int stream_alloc_qual(ffq_stream *s, int64_t bytes)
 {
     StreamBufs *b = s->b;
@@ -1042,6 +1087,7 @@ extern "C" int ffq_stream_set_filter(ffq_stream *s, int64_t min_seq_len, int64_t
     if (column < 0 || column > 3) return fail(FFQ_E_ARG, "ffq_stream_set_filter: column is FFQ_COL_NONE / _HEADER / _SEQUENCE / _QUALITY");
     if (s->flags & FFQ_F_DECODE_QUAL) return fail(FFQ_E_ARG, "ffq_stream_set_filter: the stream decodes every record's qualities (FFQ_F_DECODE_QUAL); "
                                                               "a filtered stream gathers the kept records' (column = FFQ_COL_QUALITY, value_add)");
+    if (s->render_on && column) return fail(FFQ_E_ARG, "ffq_stream_set_filter: a stream that renders FASTQ (ffq_stream_set_render) gathers no column");
     s->filter_on = true;
     s->f_min = min_seq_len; s->f_max = max_seq_len; s->f_col = column; s->f_add = value_add;
     return FFQ_OK;
@@ -1071,6 +1117,32 @@ extern "C" int ffq_stream_trimmed(ffq_stream *s, int64_t stats[3])
     if (!s || !stats) return fail(FFQ_E_ARG, "ffq_stream_trimmed: NULL argument");
     if (!s->trim_on) return fail(FFQ_E_ARG, "ffq_stream_trimmed: the stream does not trim (ffq_stream_set_trim)");
     for (int i = 0; i < 3; i++) stats[i] = s->last_trim[i];
+    return FFQ_OK;
+}
+
+// Rendering in the stream: from the first fill on, the rows ffq_stream_next hands out -- trimmed (ffq_stream_set_trim) and
+// filtered (ffq_stream_set_filter, without a column) first, if the stream does that -- are rendered as FASTQ text on the
+// device (ffq_table_render_fastq) and the text is copied back to pinned memory beside the rows.
+extern "C" int ffq_stream_set_render(ffq_stream *s)
+{
+    if (!s) return fail(FFQ_E_ARG, "ffq_stream_set_render: NULL stream");
+    if (s->flags & FFQ_F_DECODE_QUAL) return fail(FFQ_E_ARG, "ffq_stream_set_render: the stream decodes every record's qualities (FFQ_F_DECODE_QUAL); "
+                                                              "FASTQ text holds them as they are");
+    if (s->filter_on && s->f_col) return fail(FFQ_E_ARG, "ffq_stream_set_render: the stream's filter gathers a column (ffq_stream_set_filter: "
+                                                          "column != FFQ_COL_NONE); a stream that renders FASTQ gathers none");
+    if (s->cur >= 0) return fail(FFQ_E_ARG, "ffq_stream_set_render: the stream has handed out a fill already");
+    s->render_on = true;
+    return FFQ_OK;
+}
+
+// FASTQ text of the fill ffq_stream_next has just returned and {bytes rendered, rows rendered, rows skipped}; pinned
+// memory, valid until the next call.
+extern "C" int ffq_stream_rendered(ffq_stream *s, const uint8_t **h_fastq, int64_t *n_fastq_bytes, int64_t stats[3])
+{
+    if (!s || !h_fastq || !n_fastq_bytes) return fail(FFQ_E_ARG, "ffq_stream_rendered: NULL argument");
+    if (!s->render_on) return fail(FFQ_E_ARG, "ffq_stream_rendered: the stream does not render (ffq_stream_set_render)");
+    *h_fastq = s->b->hren; *n_fastq_bytes = s->last_render[0];
+    if (stats) for (int i = 0; i < 3; i++) stats[i] = s->last_render[i];
     return FFQ_OK;
 }
 
@@ -1195,6 +1267,10 @@ extern "C" int ffq_stream_next(ffq_stream *s, const int64_t **h_rows, int64_t *n
             if (rc2) return rc2;
         }
         s->last_kept = n_out;
+        if (s->render_on) {
+            int rc2 = stream_render(s, sl.d + start - mis, len + mis, s->globaloffset - mis, b->dsel, n_out);
+            if (rc2) return rc2;
+        }
         if (n_out > 0) {
             HIPCHK(hipMemcpyAsync(b->htab, b->dsel, (size_t)n_out * 48, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(hipMemcpyAsync(b->hidx, b->didx, (size_t)n_out * 8, hipMemcpyDeviceToHost, c->stream));
@@ -1210,8 +1286,14 @@ extern "C" int ffq_stream_next(ffq_stream *s, const int64_t **h_rows, int64_t *n
             if (nb > 0) HIPCHK(hipMemcpyAsync(b->hcol, b->dcol, (size_t)nb, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(hipMemcpyAsync(b->hcoff, b->dcoff, (size_t)(n_out + 1) * 8, hipMemcpyDeviceToHost, c->stream));
         }
-    } else if (res.n_records > 0)
-        HIPCHK(hipMemcpyAsync(b->htab, b->dtab, (size_t)res.n_records * 48, hipMemcpyDeviceToHost, c->stream));
+    } else {
+        if (s->render_on) {
+            int rc2 = stream_render(s, sl.d + start - mis, len + mis, s->globaloffset - mis, b->dtab, res.n_records);
+            if (rc2) return rc2;
+        }
+        if (res.n_records > 0)
+            HIPCHK(hipMemcpyAsync(b->htab, b->dtab, (size_t)res.n_records * 48, hipMemcpyDeviceToHost, c->stream));
+    }
     s->last_nq = 0;
     s->last_path = res.path;
     if (decode) {

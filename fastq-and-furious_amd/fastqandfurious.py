@@ -581,6 +581,85 @@ def readfastq_iter(fh: typing.BinaryIO, fbufsize: int,
         offset = 0
 
 
+FilterResult = namedtuple('FilterResult', 'records_in records_out bases_removed bytes_out')
+
+
+def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1 << 24, quality_cutoff=None,
+                 qual_base: int = 33, min_len=None, max_len=None, entrypos: typing.Optional[typing.Callable] = None) -> FilterResult:
+    """Trim, filter and WRITE a FASTQ stream: the file `cutadapt -q 20 -m 30` leaves behind, which is what the tables of
+    positions of the reference's user guide are kept for in the end ("to avoid saving a FASTQ file after each filtering or
+    read-trimming step", doc/user-guide.rst:196-204).  Every record of `fh` is quality-trimmed (quality_cutoff: an int --
+    the 3' end -- or a (front, back) pair, as entryfunc_qualitytrim orders them after its first argument; None: no
+    trimming), dropped if its trimmed length lies outside [min_len, max_len], and written to `fh_out` as
+
+        b"@" + header + b"\\n" + sequence + b"\\n+\\n" + quality + b"\\n"
+
+    -- the slices of entryfunc, a bare '+' line; a wrapped record stays wrapped (and untrimmed: the rule does not apply to
+    it).  Returns FilterResult(records_in, records_out, bases_removed -- over every record, the dropped ones included --,
+    bytes_out).
+
+    entrypos None (the GPU scanner): the stream front end scans, trims, filters and renders every buffer fill on the device
+    (ffq_stream_set_trim / _set_filter / _set_render) and this loop does one fh_out.write(memoryview) per fill -- a plain
+    file is read by the library itself, any other readable object chunk by chunk into pinned memory.  Any other scanner:
+    a loop over readfastq_iter that writes the same bytes record by record.  Malformed input raises what readfastq_iter
+    raises, behind the records in front of it; `fh` is left where that iterator leaves it.
+
+    A read trimmed to length 0 is written as b"@h\\n\\n+\\n\\n" unless min_len >= 1 drops it: this package's scanners
+    read that back, the reference's C scanner treats empty reads differently."""
+    trim = None
+    if quality_cutoff is not None:
+        front, back = (0, quality_cutoff) if isinstance(quality_cutoff, (int, np.integer)) else quality_cutoff
+        trim = entryfunc_qualitytrim(back, front, qual_base)            # (checks the ranges)
+    lo = None if min_len is None else int(min_len)
+    hi = None if max_len is None else int(max_len)
+    if entrypos is None:
+        from . import _fastqandfurious as _C
+        entrypos = _C.entrypos
+    n_in = n_out = removed = n_bytes = 0
+    open_stream = getattr(entrypos, 'open_stream', None)
+    st = open_stream(fh, fbufsize) if open_stream is not None else None
+    if st is not None:
+        try:
+            if trim is not None:
+                st.set_trim(trim.cutoff_back, trim.cutoff_front, trim.qual_base)
+            if lo is not None or hi is not None:
+                st.set_filter(lo, hi)
+            st.set_render()
+            for rows, _fill, _fill_offset, end_state, err_offset in st:
+                text, (nb, rendered, _skipped) = st.rendered()
+                if nb:
+                    fh_out.write(memoryview(text))
+                n_in += st.selected()[1] if st.filtered else rows.shape[0]
+                n_out += rendered
+                n_bytes += nb
+                if trim is not None:
+                    removed += st.trimmed()[1]
+                if end_state != _END_OK and end_state != _END_REFILL:
+                    _raise_for_end(end_state, err_offset)
+        finally:
+            st.close()
+        return FilterResult(n_in, n_out, removed, n_bytes)
+
+    def record(buf, pos, globaloffset=None):
+        length = pos[3] - pos[2]
+        if trim is not None:
+            pos = trim.trimmed_pos(buf, pos)
+        cut = length - (pos[3] - pos[2])
+        length -= cut
+        if (lo is not None and length < lo) or (hi is not None and length > hi):
+            return cut, None
+        return cut, b"".join((b"@", buf[(pos[0] + 1):pos[1]], b"\n", buf[pos[2]:pos[3]], b"\n+\n", buf[pos[4]:pos[5]], b"\n"))
+
+    for cut, text in readfastq_iter(fh, fbufsize, record, entrypos):
+        n_in += 1
+        removed += cut
+        if text is not None:
+            fh_out.write(text)
+            n_out += 1
+            n_bytes += len(text)
+    return FilterResult(n_in, n_out, removed, n_bytes)
+
+
 class RangeEntries:
     """What readfastq_iter_range returns: an iterator over ONE rank's entries of a file that `world` ranks read
     together, with what the ranks agreed on -- `record_base` (global ordinal of this rank's first record: entry i of

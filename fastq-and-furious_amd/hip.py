@@ -85,6 +85,7 @@ SYMBOLS = (
     "ffq_shard_create_hosted",
     "ffq_shard_create2", "ffq_shard_scan_fd_slabs", "ffq_table_select_seqlen_idx", "ffq_shard_get_info", "ffq_shard_set_timeout", "ffq_shard_set_serial", "ffq_shard_abort", "ffq_shard_inject_stall",
     "ffq_table_trim_quality", "ffq_stream_set_trim", "ffq_stream_trimmed",
+    "ffq_table_render_fastq", "ffq_stream_set_render", "ffq_stream_rendered",
 )
 
 
@@ -316,6 +317,7 @@ def lib():
         L.ffq_table_select_seqlen_idx.argtypes = [vp, vp, i64, i64, i64, vp, vp, P(i64)]
         L.ffq_table_cut.argtypes = [vp, vp, i64, i64, i64, P(i64)]
         L.ffq_table_trim_quality.argtypes = [vp, vp, i64, i32, i64, vp, i64, i32, i32, i32, vp, P(i64)]
+        L.ffq_table_render_fastq.argtypes = [vp, vp, i64, i32, i64, vp, i64, vp, i64, vp, P(i64)]
         L.ffq_table_gather_column.argtypes = [vp, vp, i64, i32, i64, vp, i64, i32, i32, i32, i32, vp, i64, vp, P(i64)]
         L.ffq_stream_open.argtypes = [vp, i32, i64, P(vp)]
         L.ffq_stream_next.argtypes = [vp, P(vp), P(i64), P(i32), P(i64), P(vp), P(i64), P(i64)]
@@ -370,6 +372,8 @@ def lib():
         L.ffq_stream_set_filter.argtypes = [vp, i64, i64, i32, i32]
         L.ffq_stream_set_trim.argtypes = [vp, i32, i32, i32]
         L.ffq_stream_trimmed.argtypes = [vp, P(i64)]
+        L.ffq_stream_set_render.argtypes = [vp]
+        L.ffq_stream_rendered.argtypes = [vp, P(vp), P(i64), P(i64)]
         L.ffq_stream_selected.argtypes = [vp, P(vp), P(i64), P(vp), P(vp), P(i64)]
         L.ffq_stream_quals.argtypes = [vp, P(vp), P(vp), P(i64)]
         L.ffq_stream_close.restype = None
@@ -660,6 +664,20 @@ class Context:
                                            int(cutoff_back), ctypes.c_void_p(d_table if d_out is None else d_out), stats))
         return int(stats[0]), int(stats[1]), int(stats[2])
 
+    def table_render_fastq(self, d_buf, n_bytes, d_table, n_rows, d_out, out_cap, d_off=None, sentinel=True, add=None):
+        """FASTQ text of the rows of a device table (ffq_table_render_fastq): row p renders as "@" + buf[p0 + 1:p1] + "\\n"
+        + buf[p2:p3] + "\\n+\\n" + buf[p4:p5] + "\\n", a row that is not renderable as nothing.  d_out: out_cap bytes, any
+        alignment; d_off: n_rows + 1 offsets or None; raw device pointers; d_buf / n_bytes / sentinel / add as for
+        table_gather_column.  Returns (rc, (bytes rendered, rows rendered, rows skipped)); rc is OK or E_TABLE_FULL
+        (out_cap too small: stats[0] is the need, d_out is not touched)."""
+        add = _add(add, sentinel)
+        stats = (ctypes.c_int64 * 3)()
+        rc = lib().ffq_table_render_fastq(self.handle, ctypes.c_void_p(d_buf), int(n_bytes), int(bool(sentinel)), int(add),
+                                          ctypes.c_void_p(d_table), int(n_rows), ctypes.c_void_p(d_out) if d_out else None,
+                                          int(out_cap), ctypes.c_void_p(d_off) if d_off else None, stats)
+        check(rc, allow=(E_TABLE_FULL,))
+        return rc, (int(stats[0]), int(stats[1]), int(stats[2]))
+
     def synth_single(self, dptr, first, count, seed=42):
         check(lib().ffq_synth_single(self.handle, ctypes.c_void_p(dptr), int(first), int(count), int(seed)))
 
@@ -931,6 +949,21 @@ class _Stream:
         stats = (ctypes.c_int64 * 3)()
         check(lib().ffq_stream_trimmed(self._h, stats))
         return int(stats[0]), int(stats[1]), int(stats[2])
+
+    def set_render(self):
+        """FASTQ text in the stream (ffq_stream_set_render; before the first fill, behind set_trim / set_filter): the rows
+        of every fill -- trimmed and filtered first, if the stream does that -- are rendered on the device (rendered())."""
+        check(lib().ffq_stream_set_render(self._h))
+
+    def rendered(self):
+        """(text, (bytes rendered, rows rendered, rows skipped)) of the fill the iteration has just yielded (set_render):
+        `text` is a uint8 view of the stream's pinned memory, valid until the next iteration step."""
+        tp, nb = ctypes.c_void_p(), ctypes.c_int64()
+        stats = (ctypes.c_int64 * 3)()
+        check(lib().ffq_stream_rendered(self._h, ctypes.byref(tp), ctypes.byref(nb), stats))
+        text = (np.ctypeslib.as_array((ctypes.c_uint8 * nb.value).from_address(tp.value)) if nb.value
+                else np.zeros(0, dtype=np.uint8))
+        return text, (int(stats[0]), int(stats[1]), int(stats[2]))
 
     def selected(self):
         """(index int64[kept], n_scanned, col int8[] or None, coloff int64[kept + 1] or None) of the fill the iteration has

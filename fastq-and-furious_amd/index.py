@@ -202,3 +202,40 @@ def select_column_device(ctx, buf, table, which, sentinel=True, add=None, value_
     if rc != 0 or nb != total:
         raise RuntimeError("select_column_device: gathered %d of %d bytes (code %d)" % (nb, total, rc))
     return out[:total], off
+
+
+def render_rows(buf, table, shift=0):
+    """FASTQ text of a table, on the host: row p renders as b"@" + buf[p0 + 1:p1] + b"\\n" + buf[p2:p3] + b"\\n+\\n" +
+    buf[p4:p5] + b"\\n" (positions minus `shift` index `buf`) -- the three slices of entryfunc and a bare '+' line, in table
+    order; a row that is not renderable (a position below 0, a slice that ends in front of its beginning or behind the
+    buffer: FASTA rows, rows that point elsewhere) renders as nothing.  What a pipeline that deleted and edited rows
+    "to avoid saving a FASTQ file after each filtering or read-trimming step" (doc/user-guide.rst:196-204) saves at its
+    end.  A read of length 0 renders as b"@h\\n\\n+\\n\\n": this package's scanners read that back, the reference's C scanner
+    treats empty reads differently -- filter with min_seq_len >= 1 in front of a file other tools will read."""
+    t = np.asarray(table, dtype=np.int64).reshape(-1, 6)
+    buf = bytes(buf) if not isinstance(buf, bytes) else buf
+    n = len(buf)
+    out = []
+    for p0, p1, p2, p3, p4, p5 in (t - shift).tolist():
+        if min(p0, p1, p2, p3, p4, p5) < 0 or p0 + 1 > p1 or p2 > p3 or p4 > p5 or max(p1, p3, p5) > n:
+            continue
+        out += (b"@", buf[p0 + 1:p1], b"\n", buf[p2:p3], b"\n+\n", buf[p4:p5], b"\n")
+    return b"".join(out)
+
+
+def render_rows_device(ctx, buf, table, sentinel=True, add=None):
+    """render_rows on the GPU: `buf` is the CUDA uint8 tensor the rows of `table` (CUDA int64[n][6]) were scanned from,
+    sentinel / add as that scan had them.  Returns (uint8 tensor with the text, int64 tensor with n + 1 offsets -- row i's
+    record is text[off[i]:off[i + 1]], empty for a row that is not renderable --, (bytes rendered, rows rendered, rows
+    skipped)).  Two C-ABI calls (ffq_table_render_fastq): the first, without an output, says how many bytes there are."""
+    import torch
+    n = int(table.shape[0])
+    off = torch.empty(n + 1, dtype=torch.int64, device=table.device)
+    _, (need, _, _) = ctx.table_render_fastq(buf.data_ptr(), buf.numel(), table.data_ptr(), n, None, 0, None,
+                                             sentinel=sentinel, add=add)
+    out = torch.empty(max(need, 16), dtype=torch.uint8, device=table.device)
+    rc, stats = ctx.table_render_fastq(buf.data_ptr(), buf.numel(), table.data_ptr(), n, out.data_ptr(), need, off.data_ptr(),
+                                       sentinel=sentinel, add=add)
+    if rc != 0 or stats[0] != need:
+        raise RuntimeError("render_rows_device: rendered %d of %d bytes (code %d)" % (stats[0], need, rc))
+    return out[:need], off, stats

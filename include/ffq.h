@@ -303,6 +303,27 @@ int ffq_table_trim_quality(ffq_ctx *ctx, const uint8_t *d_buf, int64_t n_bytes, 
                            const int64_t *d_table, int64_t n_rows, int qual_base, int cutoff_front, int cutoff_back,
                            int64_t *d_out, int64_t stats[3]);
 
+/* FASTQ text from (buffer, table): what a pipeline that excluded reads by deleting rows and trimmed them by editing rows
+ * ("to avoid saving a FASTQ file after each filtering or read-trimming step", doc/user-guide.rst:196-204) saves at its
+ * end.  Row p renders as
+ *     "@" + buf[p0 + 1 : p1] + "\n" + buf[p2 : p3] + "\n+\n" + buf[p4 : p5] + "\n"
+ * -- the three slices entryfunc cuts (fastqandfurious.py:161-171), copied verbatim (a wrapped record keeps its embedded
+ * newlines), and six literal bytes; the '+' line is always the bare "+", a repeated header is not copied; a row whose
+ * pos2..pos5 a trim moved renders the trimmed read.  A row is RENDERABLE if all six positions - add are >= 0,
+ * p0 + 1 <= p1, p2 <= p3, p4 <= p5 and every slice lies inside the buffer (it may end at its end; with sentinel,
+ * coordinate 0 is the virtual "\n": never read).  Every other row -- FASTA rows (-1), rows that point outside -- renders
+ * as zero bytes and is counted as skipped; no byte outside [d_buf, d_buf + n_bytes) is read.  Rows are independent: any
+ * order, repeated, overlapping; the output follows table order.  d_buf / n_bytes / sentinel / add: as for
+ * ffq_table_gather_column.  d_table 16-byte aligned; d_out: out_cap bytes, no alignment asked; d_off: n_rows + 1
+ * offsets (d_off[i] = where row i's record starts in d_out, d_off[n_rows] = the total), or NULL.  stats = {bytes
+ * rendered, rows rendered, rows skipped}.  FFQ_E_TABLE_FULL: out_cap is smaller than the total -- stats[0] holds the
+ * need, d_off is written, d_out is not touched.  FFQ_E_ARG: a scan pending on the context.  One host wait.
+ * A read of length 0 renders as "@h\n\n+\n\n": this package's scanners read that back, the reference's C scanner treats
+ * empty reads differently -- filter with min_seq_len >= 1 in front of a file that other tools will read.            */
+int ffq_table_render_fastq(ffq_ctx *ctx, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
+                           const int64_t *d_table, int64_t n_rows, uint8_t *d_out, int64_t out_cap, int64_t *d_off,
+                           int64_t stats[3]);
+
 /* ---- FASTA (reference: the plug-in scanner entrypos_fasta, fastqandfurious.py:103-143) -------
  * Every COMPLETE entry of a buffer, i.e. the repeated scanner call with offset := pos[3]:
  * rows = pos0 ('>'), pos1 (header end), pos2, pos3 (the "\n" of the next "\n>") + add, -1, -1.
@@ -386,6 +407,15 @@ int  ffq_stream_selected(ffq_stream *s, const int64_t **h_index, int64_t *n_scan
  * skipped} of the fill ffq_stream_next has just returned.                                                          */
 int  ffq_stream_set_trim(ffq_stream *s, int qual_base, int cutoff_front, int cutoff_back);
 int  ffq_stream_trimmed(ffq_stream *s, int64_t stats[3]);
+/* FASTQ text in the stream (any kind of stream, before the first ffq_stream_next, behind ffq_stream_set_trim /
+ * ffq_stream_set_filter if those are set; FFQ_E_ARG with FFQ_F_DECODE_QUAL and with a filter that gathers a column):
+ * the rows of every fill -- trimmed and filtered first, if the stream does that -- are rendered on the device
+ * (ffq_table_render_fastq) and the text copied back to pinned memory of the stream.  ffq_stream_rendered: the text of
+ * the fill ffq_stream_next has just returned and {bytes rendered, rows rendered, rows skipped}; valid until the next
+ * call.  A last record whose quality line no newline ends (the scan takes it when a byte follows its quality; a file
+ * that ends with the quality's last byte is FFQ_END_ERR_FINAL_QUAL) renders with one.                               */
+int  ffq_stream_set_render(ffq_stream *s);
+int  ffq_stream_rendered(ffq_stream *s, const uint8_t **h_fastq, int64_t *n_fastq_bytes, int64_t stats[3]);
 /* The same over a gzip-compressed file (what FORMAT_OPENERS['gz'] / automagic_open hand to
  * readfastq_iter, fastqandfurious.py:282-334): the stream's reader thread inflates (zlib; concatenated
  * members, zero padding behind the last one) straight into the pinned chunk buffers -- decompression
