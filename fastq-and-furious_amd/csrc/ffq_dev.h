@@ -15,6 +15,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ffq_dqwalk.h"
+
 namespace ffq {
 
 // Diagnostics (the file loader's ablation switch FFQ_LOAD_ABLATE, the streaming-read probe) exist only in the
@@ -314,16 +316,8 @@ __device__ __forceinline__ uint32_t addb4(uint32_t y, uint32_t vv)
     return ((y & 0x7F7F7F7Fu) + (vv & 0x7F7F7F7Fu)) ^ ((y ^ vv) & 0x80808080u);
 }
 
-// Directory of the decoded-quality stream: qdir[b] = the record whose decoded bytes cover
-// stream offset b << DQ_SHIFT.  Record r with bytes [q, q + len) owns every such boundary
-// inside its range, so each entry below the stream's end has exactly one writer.
-constexpr int DQ_SHIFT = 16;
-__device__ __forceinline__ void qdir_mark(int64_t *__restrict__ qdir, int64_t qdir_cap, int64_t q, int64_t len,
-                                          int64_t r)
-{
-    for (int64_t b = (q + (1 << DQ_SHIFT) - 1) >> DQ_SHIFT; (b << DQ_SHIFT) < q + len && b < qdir_cap; b++)
-        qdir[b] = r;
-}
+// (the directory of the decoded-quality stream, qdir_mark, and the constants of the decode kernel's blocks:
+// ffq_dqwalk.h)
 
 __host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t x)
 {

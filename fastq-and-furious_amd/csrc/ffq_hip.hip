@@ -1178,11 +1178,13 @@ static int enqueue_offsets_and_decode(ffq_ctx *c, const ScanArgs &a, int64_t n_r
     const int64_t nblk = (n_rows + 255) / 256;
     int rc = grow_dev(c, &c->col_sum, &c->col_sum_cap, nblk);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_col_sum, dim3((unsigned)nblk), dim3(256), 0, sA, (const int64_t *)a.d_table, n_rows, 4, 0, 5, c->col_sum);
+    hipLaunchKernelGGL(k_col_sum, dim3((unsigned)nblk), dim3(256), 0, sA, (const int64_t *)a.d_table, n_rows, 4, 0, 5,
+                       a.n_bytes, a.s, a.add, c->col_sum);
     // (the scan's totals go into the scan's own result block: the decode kernel and the host read them there)
     if ((rc = launch_scan_i64v(c, sA, c->col_sum, nblk, n_rows, c->dres))) return rc;
     hipLaunchKernelGGL(k_col_offsets, dim3((unsigned)nblk), dim3(256), 0, sA, (const int64_t *)a.d_table, n_rows, 4, 0, 5,
-                       (const long long *)c->col_sum, (const DevRes *)c->dres, a.d_qoff, c->p4s, c->qdir, c->qdir_cap);
+                       a.n_bytes, a.s, a.add, (const long long *)c->col_sum, (const DevRes *)c->dres, a.d_qoff, c->p4s, c->qdir,
+                       c->qdir_cap);
     hipLaunchKernelGGL(k_publish, dim3(1), dim3(1), 0, sA, c->dres, make_pub(c), 0);
     enqueue_decode(c, a, sA);
     return FFQ_OK;
@@ -1919,6 +1921,8 @@ extern "C" int ffq_table_gather_column(ffq_ctx *c, const uint8_t *d_buf, int64_t
     mark_other(c);
     if (!c || !n_out_bytes || n_rows < 0 || n_bytes < 0 || out_cap < 0 || !d_off || (n_rows > 0 && !d_table))
         return fail(FFQ_E_ARG, "ffq_table_gather_column: bad argument");
+    if (out_cap > 0 && (!d_out || (n_bytes > 0 && !d_buf)))
+        return fail(FFQ_E_ARG, "ffq_table_gather_column: no output, or no buffer, to copy %lld bytes", (long long)out_cap);
     if (col_begin < 0 || col_begin > 5 || col_end < 0 || col_end > 5)
         return fail(FFQ_E_ARG, "ffq_table_gather_column: columns are 0..5");
     if (c->pend.active) return fail(FFQ_E_ARG, "ffq_table_gather_column: a scan is pending on this context");
@@ -1942,11 +1946,11 @@ extern "C" int ffq_table_gather_column(ffq_ctx *c, const uint8_t *d_buf, int64_t
     if (!rc) rc = reserve_p4s(c, n_rows);
     if (rc) return rc;
     hipLaunchKernelGGL(k_col_sum, dim3((unsigned)nblk), dim3(256), 0, st, d_table, n_rows, col_begin, begin_shift, col_end,
-                       c->col_sum);
+                       n_bytes, sentinel ? 1 : 0, add, c->col_sum);
     if ((rc = launch_scan_i64v(c, st, c->col_sum, nblk, n_rows, c->col_res))) return rc;
     hipLaunchKernelGGL(k_col_offsets, dim3((unsigned)nblk), dim3(256), 0, st, d_table, n_rows, col_begin, begin_shift,
-                       col_end, (const long long *)c->col_sum, (const DevRes *)c->col_res, d_off, c->p4s, c->qdir,
-                       c->qdir_cap);
+                       col_end, n_bytes, sentinel ? 1 : 0, add, (const long long *)c->col_sum, (const DevRes *)c->col_res, d_off,
+                       c->p4s, c->qdir, c->qdir_cap);
     if (out_cap > 0)
         hipLaunchKernelGGL(k_decode_stream, dim3((unsigned)nqb), dim3(256), 0, st, d_buf, n_bytes, sentinel ? 1 : 0,
                            (const int64_t *)c->p4s, (const int64_t *)d_off, (const int64_t *)c->qdir,

@@ -423,9 +423,7 @@ __global__ void k_publish(DevRes *res, Pub pb, int later_tier_follows)
 // (pos4 from the compact copy the row kernels write beside the table: the 48-byte rows would
 // come in whole lines, 1.5 GiB instead of 0.25 per 10 GiB of input).
 // =========================================================================
-constexpr int DQ_PER = 4;                         // chunks per thread and batch
-constexpr int DQ_BLK = 1 << DQ_SHIFT;             // output bytes per workgroup
-constexpr int DQ_REC = 1024;                      // records cached in LDS per window
+constexpr int DQ_PER = 4;                         // chunks per thread and batch (DQ_BLK, DQ_REC: ffq_dqwalk.h)
 
 // dword w of the 16-byte mask with bytes [0, nb) set
 __device__ __forceinline__ uint32_t lt_mask(int nb, int w)
@@ -469,7 +467,8 @@ __device__ __noinline__ void store16_part(int8_t *__restrict__ o, uint4 v, int k
 }
 
 // records shorter than 16 bytes: chunk bytes [kb, kend) gathered byte by byte from the
-// cached records m, m+1, ...
+// cached records m, m+1, ...  (Every byte read is a byte OF a record: inside the buffer, since whoever
+// wrote qoff gave a component that does not lie inside it the length 0 -- col_len.)
 __device__ __noinline__ uint4 gather_tail(const uint8_t *__restrict__ d, const int32_t *s_q, const int64_t *s_adj,
                                           uint4 v, int m, int kb, int kend, int clo, int vhi)
 {
@@ -488,6 +487,20 @@ __device__ __noinline__ uint4 gather_tail(const uint8_t *__restrict__ d, const i
     return make_uint4(y[0], y[1], y[2], y[3]);
 }
 
+// one chunk without the cache (the window walk's slow step, ffq_dqwalk.h): thread t writes byte clo + t
+__device__ __noinline__ void decode_chunk_slow(const uint8_t *__restrict__ d, int64_t nbytes, int s,
+                                               const int64_t *__restrict__ p4s, const int64_t *__restrict__ qoff, int64_t n,
+                                               int64_t rbase, int64_t ob, int64_t add, int qadd, int8_t *__restrict__ outb,
+                                               int clo, int oe)
+{
+    const int x = clo + (int)threadIdx.x;
+    if (threadIdx.x >= 16 || x < 0 || x >= oe) return;
+    const int64_t r = dq_find_record(qoff, rbase, n - 1, ob + x);
+    const int64_t src = p4s[r] - add - s + (ob + x - qoff[r]);
+    const uint32_t b = (src >= 0 && src < nbytes) ? d[src] : 0u;
+    outb[x] = (int8_t)(uint8_t)(b + (uint32_t)qadd);
+}
+
 __global__ __launch_bounds__(256) void k_decode_stream(const uint8_t *__restrict__ d, int64_t nbytes, int s,
                                                        const int64_t *__restrict__ p4s,
                                                        const int64_t *__restrict__ qoff,
@@ -500,7 +513,10 @@ __global__ __launch_bounds__(256) void k_decode_stream(const uint8_t *__restrict
     __shared__ int64_t s_adj[DQ_REC];             // buffer offset of the byte decoded to stream offset ob
     const int tid = threadIdx.x;
     const int64_t ob = (int64_t)blockIdx.x << DQ_SHIFT;
-    int64_t rbase = qdir[blockIdx.x];             // garbage past the end of the stream: not used then
+    DqWalk w;                                     // the walk over the block's windows: ffq_dqwalk.h
+    w.rbase = qdir[blockIdx.x];                   // garbage past the end of the stream: not used then
+    w.done = 0;
+    w.want = 0;
     const int64_t n = res->n_records;
     const int64_t qtotal = res->n_qual_bytes;     // == qoff[n]
     if (res->fallback || n > table_cap || n <= 0) return;        // a table that overflowed decodes nothing
@@ -509,33 +525,30 @@ __global__ __launch_bounds__(256) void k_decode_stream(const uint8_t *__restrict
     const int oe = (int)min((int64_t)DQ_BLK, total - ob);        // block-relative from here on
     const int shiftA = (int)(reinterpret_cast<uintptr_t>(out + ob) & 15);
     int8_t *__restrict__ outb = out + ob;
-    const int mean = (int)min(max(qtotal / n, (int64_t)1), (int64_t)1 << 20);
+    const int mean = dq_mean(qtotal, n);
     const uint32_t vv = (uint32_t)(uint8_t)qadd * 0x01010101u;
 
     // chunk k covers [16 k - shiftA, +16) cut to [0, oe); a destination that is not 16-byte
     // aligned has one more (partial) chunk at the end
-    const int nchunk = (oe + shiftA + 15) >> 4;
-    int done = 0;                                  // chunks [0, done) are written
-    int want = 0;
+    const int nchunk = dq_nchunk(oe, shiftA);
     for (;;) {
         // ---- window: (offset, source) of records rbase .. rbase + nrec in LDS.  Sized from the
         //      mean quality length; a window that covers no whole chunk is redone at full size
-        const int rem = oe - max(16 * done - shiftA, 0);
-        want = (want < 0) ? DQ_REC - 1 : min(DQ_REC - 1, rem / mean + rem / (8 * mean) + 8);
-        const int nrec = (int)min((int64_t)want, n - rbase);     // >= 1
+        const int64_t rbase = w.rbase;
+        const int done = w.done;
+        const int nrec = dq_window_nrec(dq_window_want(w.want, done, oe, shiftA, mean), n, rbase);      // >= 1
         for (int i = tid; i <= nrec; i += 256) {
             // both loads before either is used (the source position of index nrec is not needed:
             // a clamped address keeps the load unconditional)
             const int64_t qraw = qoff[rbase + i];
             const int64_t p4 = p4s[rbase + min(i, nrec - 1)];            // (pos4 of the rows, compact)
             asm volatile("" ::"v"(qraw), "v"(p4));
-            const int64_t q = qraw - ob;
-            s_q[i] = (int32_t)min(max(q, (int64_t)-0x7FFFFFFF), (int64_t)0x7FFFFFFF);
-            if (i < nrec) s_adj[i] = p4 - add - s - q;
+            s_q[i] = dq_rel(qraw, ob);
+            if (i < nrec) s_adj[i] = p4 - add - s - (qraw - ob);
         }
         __syncthreads();
         const int cend = s_q[nrec];                // every byte below cend has its record cached
-        const int klim = (rbase + nrec == n || cend >= oe) ? nchunk : min(nchunk, (cend + shiftA) >> 4);
+        const int klim = dq_klim(rbase, nrec, n, cend, oe, shiftA, nchunk);
         const float inv_mean = (float)nrec / (float)(cend - s_q[0]);
 
         for (int k0 = done; k0 < klim; k0 += 256 * DQ_PER) {
@@ -547,19 +560,11 @@ __global__ __launch_bounds__(256) void k_decode_stream(const uint8_t *__restrict
 #pragma unroll
             for (int j = 0; j < DQ_PER; j++) {
                 const int k = k0 + j * 256 + tid;
-                const int clo = 16 * k - shiftA;
+                const int clo = dq_clo(k, shiftA);
                 const int vlo = max(clo, 0), vhi = min(clo + 16, oe);
                 ci[j] = -1;
                 if (k >= klim || vlo >= vhi) continue;
-                // largest cached index a with s_q[a] <= vlo (it is below nrec); equal-length
-                // records make the interpolated guess exact
-                int a = 0, b = nrec - 1;
-                const int g = min(max((int)((float)(vlo - s_q[0]) * inv_mean), 0), nrec - 1);
-                if (s_q[g] <= vlo) { a = g; if (s_q[g + 1] > vlo) b = g; } else b = g - 1;
-                while (b > a) {
-                    const int m = (a + b + 1) >> 1;
-                    if (s_q[m] <= vlo) a = m; else b = m - 1;
-                }
+                const int a = dq_chunk_record(s_q, nrec, vlo, inv_mean);
                 ci[j] = a;
                 h0[j] = min(s_q[a + 1], vhi) - clo;                 // chunk bytes [.., h0) come from record a
                 h1[j] = (h0[j] < vhi - clo) ? min(s_q[a + 2], vhi) - clo : h0[j];
@@ -568,14 +573,14 @@ __global__ __launch_bounds__(256) void k_decode_stream(const uint8_t *__restrict
             for (int j = 0; j < DQ_PER; j++) {
                 xa[j] = xb[j] = make_uint4(0, 0, 0, 0);
                 if (ci[j] < 0) continue;
-                const int clo = 16 * (k0 + j * 256 + tid) - shiftA;
+                const int clo = dq_clo(k0 + j * 256 + tid, shiftA);
                 xa[j] = load16_any(d, nbytes, s_adj[ci[j]] + clo);
                 if (h1[j] > h0[j]) xb[j] = load16_any(d, nbytes, s_adj[ci[j] + 1] + clo);
             }
 #pragma unroll
             for (int j = 0; j < DQ_PER; j++) {
                 if (ci[j] < 0) continue;
-                const int clo = 16 * (k0 + j * 256 + tid) - shiftA;
+                const int clo = dq_clo(k0 + j * 256 + tid, shiftA);
                 const int vlo = max(clo, 0), vhi = min(clo + 16, oe);
                 uint32_t y[4];
                 {
@@ -604,22 +609,15 @@ __global__ __launch_bounds__(256) void k_decode_stream(const uint8_t *__restrict
             }
         }
         if (klim >= nchunk) break;
-        // ---- next window starts at the record under the first byte of chunk klim
-        int nb = -1;
-        if (klim > done) {
-            const int vlo = 16 * klim - shiftA;    // > 0 and < cend
-            int a = 0, b = nrec - 1;
-            while (b > a) {
-                const int m = (a + b + 1) >> 1;
-                if (s_q[m] <= vlo) a = m; else b = m - 1;
-            }
-            nb = a;
-        }
+        const int nxt = dq_next(w, s_q, nrec, klim, shiftA);
         __syncthreads();                           // the cache is rewritten next
-        if (nb < 0) { want = -1; continue; }       // no whole chunk covered: full-size window, same base
-        rbase += nb;
-        done = klim;
-        want = 0;
+        if (nxt == DQ_NEXT_SLOW) {
+            // ---- not even a full window reaches from the record under the first byte of chunk `done` to the one under
+            //      its last: more than DQ_REC - 2 empty records lie in between.  That chunk byte by byte, each byte's
+            //      record searched in qoff itself; then the walk goes on behind the empty records
+            decode_chunk_slow(d, nbytes, s, p4s, qoff, n, rbase, ob, add, qadd, outb, dq_clo(done, shiftA), oe);
+            if (dq_after_slow(w, qoff, n, ob, shiftA, nchunk)) break;
+        }
     }
 }
 
@@ -747,13 +745,18 @@ __global__ __launch_bounds__(256) void k_sel_scatter(const int64_t *__restrict__
 //   k_col_offsets  offsets[i], start[i], directory of the output stream (qdir_mark)
 //   k_decode_stream (above) then copies: it is the Phred decode with another pair of columns
 // =========================================================================
+// A component that does not lie inside the buffer -- buffer offsets [start - add - s, end - add - s) outside
+// [0, nbytes); with a sentinel, coordinate 0 is the virtual "\n" in front of it -- has the length 0, like a component
+// whose end lies at or below its start: the copy kernel never forms an address of a byte outside the buffer.
 __device__ __forceinline__ int64_t col_len(const int64_t *__restrict__ table, int64_t i, int64_t n, int ca, int shift,
-                                           int cb, int64_t &start)
+                                           int cb, int64_t nbytes, int s, int64_t add, int64_t &start)
 {
     if (i >= n) { start = 0; return 0; }
     start = table[i * 6 + ca] + shift;
-    const int64_t len = table[i * 6 + cb] - start;
-    return len > 0 ? min(len, (int64_t)0x7FFFFFF0) : 0;
+    const int64_t end = table[i * 6 + cb], len = end - start;
+    const int64_t b0 = start - add - s;
+    if (len <= 0 || b0 < 0 || b0 > nbytes || len > nbytes - b0) return 0;
+    return min(len, (int64_t)0x7FFFFFF0);
 }
 
 // exclusive prefix of `len` inside a 256-thread workgroup (lengths below 2^31) and the block's sum
@@ -777,10 +780,10 @@ __device__ __forceinline__ int64_t block_excl_scan_len(int64_t len, int64_t &blo
 }
 
 __global__ __launch_bounds__(256) void k_col_sum(const int64_t *__restrict__ table, int64_t n, int ca, int shift, int cb,
-                                                 long long *__restrict__ bsum)
+                                                 int64_t nbytes, int s, int64_t add, long long *__restrict__ bsum)
 {
     int64_t start, tot;
-    const int64_t len = col_len(table, (int64_t)blockIdx.x * 256 + threadIdx.x, n, ca, shift, cb, start);
+    const int64_t len = col_len(table, (int64_t)blockIdx.x * 256 + threadIdx.x, n, ca, shift, cb, nbytes, s, add, start);
     (void)block_excl_scan_len(len, tot);
     if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
 }
@@ -976,13 +979,13 @@ __global__ __launch_bounds__(256) void k_scan_blkapply(long long *__restrict__ v
 }
 
 __global__ __launch_bounds__(256) void k_col_offsets(const int64_t *__restrict__ table, int64_t n, int ca, int shift, int cb,
-                                                     const long long *__restrict__ bbase, const DevRes *__restrict__ res,
+                                                     int64_t nbytes, int s, int64_t add, const long long *__restrict__ bbase, const DevRes *__restrict__ res,
                                                      int64_t *__restrict__ coff, int64_t *__restrict__ starts,
                                                      int64_t *__restrict__ qdir, int64_t qdir_cap)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     int64_t start, tot;
-    const int64_t len = col_len(table, i, n, ca, shift, cb, start);
+    const int64_t len = col_len(table, i, n, ca, shift, cb, nbytes, s, add, start);
     const int64_t off = bbase[blockIdx.x] + block_excl_scan_len(len, tot);
     if (i < n) {
         coff[i] = off;

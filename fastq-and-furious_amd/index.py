@@ -199,9 +199,10 @@ def select_column_device(ctx, buf, table, which, sentinel=True, add=None, value_
     out = torch.empty(max(total, 16), dtype=torch.int8, device=table.device)
     rc, nb = ctx.table_gather_column(buf.data_ptr(), buf.numel(), table.data_ptr(), n, which, out.data_ptr(), total,
                                      off.data_ptr(), sentinel=sentinel, add=add, value_add=value_add)
-    if rc != 0 or nb != total:
+    # (fewer than `total`: rows that do not lie inside `buf` gather as nothing, include/ffq.h)
+    if rc != 0 or nb > total:
         raise RuntimeError("select_column_device: gathered %d of %d bytes (code %d)" % (nb, total, rc))
-    return out[:total], off
+    return out[:nb], off
 
 
 def render_rows(buf, table, shift=0):

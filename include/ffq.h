@@ -273,8 +273,19 @@ int ffq_table_select_seqlen_idx(ffq_ctx *ctx, const int64_t *d_table, int64_t n_
  * (doc/user-guide.rst:206-214).  d_buf / n_bytes / sentinel / add: the buffer the rows were
  * scanned from and the `add` of that scan (rows - add are buffer coordinates).  d_off: n_rows + 1
  * entries.  *n_out_bytes = bytes of the stream; FFQ_E_TABLE_FULL if out_cap is smaller (nothing
- * is written past out_cap).  After ffq_table_select_seqlen this is the user guide's length-filter
- * entryfunc in two calls.                                                                     */
+ * is written past out_cap: d_off is complete, d_out holds the first out_cap bytes of the stream;
+ * d_out may be NULL if out_cap is 0 -- the sizing call).  After ffq_table_select_seqlen this is the
+ * user guide's length-filter entryfunc in two calls.
+ * Rows are independent: any order, repeated, overlapping, written by hand.  A component is EMPTY
+ * (d_off[i + 1] == d_off[i]) if its end does not lie above its beginning (pos[col_end] <=
+ * pos[col_begin] + begin_shift: rows of length 0 as a trim leaves them, however many in a row; the
+ * -1, -1 of a FASTA row; a row of negative length) or if it does not lie inside the buffer, i.e.
+ * unless 0 <= pos[col_begin] + begin_shift - add - sentinel and pos[col_end] - add - sentinel <=
+ * n_bytes (with sentinel, coordinate 0 is the virtual "\n": never read).  A component partly outside
+ * is empty as a whole; no byte outside [d_buf, d_buf + n_bytes) is read.  value_add is added to
+ * every byte modulo 256 (arrayadd_b's wrap-around, _fastqandfurious.c:161-185; only its low 8 bits
+ * count) and the sum is stored as int8: value_add = -33 turns '!' into 0 and the byte 0x10 into -17.
+ * d_out: no alignment asked.                                                                   */
 int ffq_table_gather_column(ffq_ctx *ctx, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
                             const int64_t *d_table, int64_t n_rows, int col_begin, int begin_shift,
                             int col_end, int value_add, int8_t *d_out, int64_t out_cap, int64_t *d_off,

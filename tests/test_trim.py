@@ -324,6 +324,7 @@ def scan_on_device(ctx, data):
 
 @pytest.mark.gpu
 def test_synth_single_every_row(gpu_ctx):
+    import torch
     from fastqandfurious_amd import synth, index as X
     data = synth.single(0, 4096).tobytes()
     dbuf, table = scan_on_device(gpu_ctx, data)
@@ -344,6 +345,11 @@ def test_synth_single_every_row(gpu_ctx):
             assert empty.sum() >= 8
         if (cf, cb) == (30, 30):
             assert empty.sum() >= 1024          # the whole-read path
+            # ... and the gather takes the table as the trim left it, the rows of length 0 among the others
+            qual, off = X.select_column_device(gpu_ctx, dbuf, torch.from_numpy(want).cuda(), "quality", value_add=-33)
+            exp = np.concatenate([np.frombuffer(data, dtype=np.uint8)[a:b] for a, b in want[:, 4:6]]).astype(np.int16) - 33
+            assert (np.diff(off.cpu().numpy()) == want[:, 5] - want[:, 4]).all() and exp.size > 0
+            assert (qual.cpu().numpy().astype(np.int16) == exp).all()
         if (cf, cb) == (0, 10):
             assert (front == 0).all() and back.max() <= 9 and ((back >= 1) & (back <= 9)).sum() >= 500
     # in place: the same rows
