@@ -604,8 +604,10 @@ def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1
     a loop over readfastq_iter that writes the same bytes record by record.  Malformed input raises what readfastq_iter
     raises, behind the records in front of it; `fh` is left where that iterator leaves it.
 
-    A read trimmed to length 0 is written as b"@h\\n\\n+\\n\\n" unless min_len >= 1 drops it: this package's scanners
-    read that back, the reference's C scanner treats empty reads differently."""
+    A read trimmed to length 0 is written as b"@h\\n\\n+\\n\\n" unless min_len >= 1 drops it.  A file with such records
+    is read back record for record by the Python scanner (entrypos of this module) only: the GPU scanner answers as the
+    reference's C scanner does and reads an empty record and the one behind it as one longer record, without an error.
+    min_len >= 1 is what makes the output safe for the GPU scanner and for other tools."""
     trim = None
     if quality_cutoff is not None:
         front, back = (0, quality_cutoff) if isinstance(quality_cutoff, (int, np.integer)) else quality_cutoff

@@ -211,8 +211,9 @@ def render_rows(buf, table, shift=0):
     order; a row that is not renderable (a position below 0, a slice that ends in front of its beginning or behind the
     buffer: FASTA rows, rows that point elsewhere) renders as nothing.  What a pipeline that deleted and edited rows
     "to avoid saving a FASTQ file after each filtering or read-trimming step" (doc/user-guide.rst:196-204) saves at its
-    end.  A read of length 0 renders as b"@h\\n\\n+\\n\\n": this package's scanners read that back, the reference's C scanner
-    treats empty reads differently -- filter with min_seq_len >= 1 in front of a file other tools will read."""
+    end.  A read of length 0 renders as b"@h\\n\\n+\\n\\n": a file with such records is read back record for record by the
+    Python scanner only (the GPU scanner answers as the reference's C scanner does and joins an empty record with the one
+    behind it) -- filter with min_seq_len >= 1 in front of a file the GPU scanner or other tools will read."""
     t = np.asarray(table, dtype=np.int64).reshape(-1, 6)
     buf = bytes(buf) if not isinstance(buf, bytes) else buf
     n = len(buf)

@@ -329,8 +329,11 @@ int ffq_table_trim_quality(ffq_ctx *ctx, const uint8_t *d_buf, int64_t n_bytes, 
  * offsets (d_off[i] = where row i's record starts in d_out, d_off[n_rows] = the total), or NULL.  stats = {bytes
  * rendered, rows rendered, rows skipped}.  FFQ_E_TABLE_FULL: out_cap is smaller than the total -- stats[0] holds the
  * need, d_off is written, d_out is not touched.  FFQ_E_ARG: a scan pending on the context.  One host wait.
- * A read of length 0 renders as "@h\n\n+\n\n": this package's scanners read that back, the reference's C scanner treats
- * empty reads differently -- filter with min_seq_len >= 1 in front of a file that other tools will read.            */
+ * A read of length 0 renders as "@h\n\n+\n\n".  A file with such records is read back record for record by the Python
+ * scanner (fastqandfurious.entrypos) ONLY: the device scanners answer as the reference's C scanner does, which looks for
+ * the end of a sequence behind its first byte and reads an empty record and its successor as one longer record, without
+ * an error.  Filter with min_seq_len >= 1 in front of the rendering: that is what makes the text safe for the GPU
+ * scanner and for other tools.                                                                                        */
 int ffq_table_render_fastq(ffq_ctx *ctx, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
                            const int64_t *d_table, int64_t n_rows, uint8_t *d_out, int64_t out_cap, int64_t *d_off,
                            int64_t stats[3]);
