@@ -11,6 +11,7 @@
 #include "ffq_trim.h"
 #include "ffq_render.h"
 #include "ffq_pool.h"
+#include "ffq_mem.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -116,6 +117,22 @@ struct InputMemory {
     bool fz_in_place = false;            // the last single pass that stood wrote in place (long lines): start with that one
 };
 
+// The memory behind the kernel argument structs ChainBufs (ffq_chain.h) and RankBufs (ffq_ranked.h).  Those are plain
+// structs of raw pointers that go to the kernels by value; these own what they point to.
+struct ChainMem {
+    DevBuf<int64_t> y, exit, qb, rloc, qloc, part, force;
+    DevBuf<uint32_t> cnt, flags, lines, dlist, ilist;
+    DevBuf<GroupTerm> term;
+    DevBuf<int32_t> mins;
+    DevBuf<StageRec> stage, dstage;
+};
+struct RankMem {
+    DevBuf<long long> tbase;
+    DevBuf<H> cand;
+    DevBuf<RankRec> rec;
+    DevBuf<uint32_t> succ, S[2], C[2], D, root;
+};
+
 struct ffq_ctx {
     ScanState pend;                      // the scan enqueued by ffq_scan_submit, if any
     ffq_ctx *owner = nullptr;            // the context whose stream this one uses (itself unless created shared)
@@ -128,82 +145,68 @@ struct ffq_ctx {
     hipStream_t stream = nullptr;
     hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     InputMemory mem;                     // what the recent scans found the input to be
-    RankBufs rk = {};                    // its scratch (ffq_ranked.h), grow-only
-    int64_t rk_cap_tiles = 0, rk_cap_c = 0;
-    // single-pass index + decode (ffq_fused.h): per-tile phases, verdict; grow-only
-    uint8_t *fz_qphase = nullptr;
-    int64_t fz_tiles_cap = 0;
-    uint32_t *fz_bad = nullptr;
+    // Scratch, grow-only.  Every buffer is a member that frees itself (ffq_mem.h); the kernel argument structs `rk` and
+    // `cb` are raw-pointer VIEWS of the members of RankMem / ChainMem, rebuilt by the functions that regrow those.
+    RankMem rm;                          // list ranking (ffq_ranked.h): rm.tbase.cap tiles, rm.cand.cap candidates
+    RankBufs rk = {};
+    // single-pass index + decode (ffq_fused.h): per-tile phases, verdict
+    DevBuf<uint8_t> fz_qphase;
+    DevBuf<uint32_t> fz_bad;
     bool decode_timed = false;           // ev[6] marks the start of the decode kernel of the pending front
-    // scratch, grow-only
-    int64_t cap_tiles = 0;
-    uint16_t *ent = nullptr;
-    uint32_t *cnt = nullptr;
-    unsigned long long *ovf = nullptr;
-    uint16_t *pool = nullptr;
-    unsigned long long pool_cap = 0;
-    int64_t cap_groups = 0;
+    int64_t cap_tiles = 0;               // what ent .. sbqbase and the per-group buffers of `cm` are sized for (reserve_tiles)
+    DevBuf<uint16_t> ent;
+    DevBuf<uint32_t> cnt;
+    DevBuf<unsigned long long> ovf;
+    DevBuf<uint16_t> pool;
+    ChainMem cm;                         // cm.stage.cap: StageRec entries; cm.dstage.cap / DCHUNK: chunks of the walked groups' stage
     ChainBufs cb = {};
-    int64_t stage_cap = 0;        // StageRec entries allocated
-    int64_t dstage_chunks = 0;    // chunks of the walked groups' stage (cb.dstage, DCHUNK records each), grow-only
-    long long *sbbase = nullptr;
-    TileQ *tileq = nullptr;              // fast path + decode: records / quality bytes per tile
-    unsigned int *sbq = nullptr;         //   quality bytes per 64 tiles
-    long long *sbqbase = nullptr;        //   their exclusive scan
-    Fast4Hdr *hdr4 = nullptr;
-    TermInfo4 *tinfo4 = nullptr;
-    Ctl *ctl = nullptr;
-    LineIndex *d_L = nullptr;          // device copy of the LineIndex (out-of-line device functions)
-    LineIndex *h_L = nullptr;          // pinned source of that copy
-    DevRes *dres = nullptr;
-    int64_t *qdir = nullptr;           // directory of the decoded-quality stream (qdir_mark)
-    int64_t qdir_cap = 0;
-    int64_t *p4s = nullptr;            // pos4 of every record, compact: what the decode reads instead of the 48-byte rows
-    int64_t p4s_cap = 0;
-    uint32_t *qrel = nullptr;          // tile-relative quality offsets of the fast path (p4s_cap entries)
+    DevBuf<long long> sbbase;
+    DevBuf<TileQ> tileq;                 // fast path + decode: records / quality bytes per tile
+    DevBuf<unsigned int> sbq;            //   quality bytes per 64 tiles
+    DevBuf<long long> sbqbase;           //   their exclusive scan
+    DevBuf<Fast4Hdr> hdr4;
+    DevBuf<TermInfo4> tinfo4;
+    DevBuf<Ctl> ctl;
+    DevBuf<LineIndex> d_L;               // device copy of the LineIndex (out-of-line device functions)
+    PinBuf<LineIndex> h_L;               // pinned source of that copy
+    DevBuf<DevRes> dres;
+    DevBuf<int64_t> qdir;                // directory of the decoded-quality stream (qdir_mark)
+    DevBuf<int64_t> p4s;                 // pos4 of every record, compact: what the decode reads instead of the 48-byte rows
+    DevBuf<uint32_t> qrel;               // tile-relative quality offsets of the fast path (p4s.cap entries)
     // pinned mirrors
-    Ctl *h_ctl = nullptr;               // host-mapped pinned: written by the publishing kernel (Pub)
-    DevRes *h_res = nullptr;
+    PinBuf<Ctl, hipHostMallocMapped> h_ctl;        // host-mapped pinned: written by the publishing kernel (Pub)
+    PinBuf<DevRes, hipHostMallocMapped> h_res;
     Ctl *hm_ctl = nullptr;              // device addresses of the two
     DevRes *hm_res = nullptr;
-    unsigned long long *h_seq = nullptr, *hm_seq = nullptr;   // completion word of FFQ_F_POLL_RESULT (host-mapped) and its device address
+    PinBuf<unsigned long long, hipHostMallocMapped> h_seq;    // completion word of FFQ_F_POLL_RESULT (host-mapped)
+    unsigned long long *hm_seq = nullptr;                     //   and its device address
     unsigned long long seq = 0;         // last number handed out
     unsigned long long pub_seq = 0;     // what the publisher being enqueued writes (0: nothing)
     bool ctl_clean = false;             // the control block is zero (creation, or a publisher ran last)
     bool ctl_was_clean = false;         //   ... as it was when the front being enqueued began (no memset in front of it)
-    int64_t *d_word = nullptr;          // 2 scratch words for the small table queries
-    int64_t *h_word = nullptr;          //   and their pinned mirror
-    int64_t *d_cut = nullptr, *h_cut = nullptr;    // ffq_table_cut: 6 words
-    TrimBlock *d_trim = nullptr, *h_trim = nullptr;    // ffq_table_trim_quality: the call's counters and their pinned mirror
-    int64_t *trim_list = nullptr;       //   rows left to the wave-per-row launch
-    int64_t trim_list_cap = 0;
-    RenderBlock *d_render = nullptr, *h_render = nullptr;  // ffq_table_render_fastq: the call's counters and their pinned mirror
-    int64_t *render_list = nullptr;     //   (row, place in the output) of the rows left to the wave-per-row launch
-    int64_t render_list_cap = 0;
-    FaHdr *fa_hdr = nullptr;            // FASTA scan: starts, the last start
+    DevBuf<int64_t> d_word;             // 2 scratch words for the small table queries
+    PinBuf<int64_t> h_word;             //   and their pinned mirror
+    DevBuf<int64_t> d_cut;              // ffq_table_cut: 6 words
+    PinBuf<int64_t> h_cut;
+    DevBuf<TrimBlock> d_trim;           // ffq_table_trim_quality: the call's counters and their pinned mirror
+    PinBuf<TrimBlock> h_trim;
+    DevBuf<int64_t> trim_list;          //   rows left to the wave-per-row launch
+    DevBuf<RenderBlock> d_render;       // ffq_table_render_fastq: the call's counters and their pinned mirror
+    PinBuf<RenderBlock> h_render;
+    DevBuf<int64_t> render_list;        //   (row, place in the output) of the rows left to the wave-per-row launch
+    DevBuf<FaHdr> fa_hdr;               // FASTA scan: starts, the last start
     // staging for the host-buffer entry points
-    uint8_t *stage_d = nullptr;
-    int64_t stage_d_cap = 0;
-    uint8_t *stage_h = nullptr;
-    int64_t stage_h_cap = 0;
-    int64_t *tab_d = nullptr;
-    int64_t tab_d_cap = 0;
-    int8_t *qual_d = nullptr;
-    int64_t qual_d_cap = 0;
-    int64_t *qoff_d = nullptr;
-    int64_t qoff_d_cap = 0;
-    unsigned int *sel_cnt = nullptr;   // row selection: kept rows per workgroup, their scan
-    int64_t sel_cnt_cap = 0;
-    long long *sel_base = nullptr;
-    int64_t sel_base_cap = 0;
-    int64_t *tab_h = nullptr;      // pinned bounce for rows
-    int64_t tab_h_cap = 0;
-    long long *col_sum = nullptr;  // column selection: bytes per block of rows, their scan
-    int64_t col_sum_cap = 0;
-    long long *scan_bs = nullptr;  // block sums of the two-level scan (launch_scan_i64v)
-    int64_t scan_bs_cap = 0;
-    DevRes *scan_res = nullptr;    // (the middle level's result block: nobody reads it)
-    DevRes *col_res = nullptr;     //   its result block (row count, total bytes)
+    DevBuf<uint8_t> stage_d;
+    PinBuf<uint8_t> stage_h;
+    DevBuf<int64_t> tab_d;
+    DevBuf<int8_t> qual_d;
+    DevBuf<int64_t> qoff_d;
+    DevBuf<unsigned int> sel_cnt;       // row selection: kept rows per workgroup, their scan
+    DevBuf<long long> sel_base;
+    DevBuf<long long> col_sum;          // column selection: bytes per block of rows, their scan
+    DevBuf<long long> scan_bs;          // block sums of the two-level scan (launch_scan_i64v)
+    DevBuf<DevRes> scan_res;            // (the middle level's result block: nobody reads it)
+    DevBuf<DevRes> col_res;             //   its result block (row count, total bytes)
     // ffq_scan_host: pageable memory goes through three pinned staging slots, copied in by the
     // helper threads and out over two copy streams (and back the same way)
     hipEvent_t stage_ev[3][2] = {};
@@ -270,22 +273,22 @@ static int ctx_create_impl(int device, ffq_ctx *share, ffq_ctx **out)
     for (int i = 0; i < 7 && e == hipSuccess; i++)
         e = (i == 2 || i == 3) ? hipEventCreate(&c->ev[i])
                                : hipEventCreateWithFlags(&c->ev[i], hipEventDisableSystemFence);
-    if (e == hipSuccess) e = hipMalloc((void **)&c->ctl, sizeof(Ctl));
-    if (e == hipSuccess) e = hipMalloc((void **)&c->dres, sizeof(DevRes));
-    if (e == hipSuccess) e = hipMalloc((void **)&c->d_L, sizeof(LineIndex));
-    if (e == hipSuccess) e = hipMalloc((void **)&c->d_word, 16);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_word, 16, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc((void **)&c->d_cut, 48);
-    if (e == hipSuccess) e = hipMalloc((void **)&c->d_trim, sizeof(TrimBlock));
-    if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_trim, sizeof(TrimBlock), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc((void **)&c->d_render, sizeof(RenderBlock));
-    if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_render, sizeof(RenderBlock), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc((void **)&c->fa_hdr, sizeof(FaHdr));
-    if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_cut, 48, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_L, sizeof(LineIndex), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_ctl, sizeof(Ctl), hipHostMallocMapped);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_res, sizeof(DevRes), hipHostMallocMapped);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_seq, 64, hipHostMallocMapped);
+    if (e == hipSuccess) e = c->ctl.grow(1);
+    if (e == hipSuccess) e = c->dres.grow(1);
+    if (e == hipSuccess) e = c->d_L.grow(1);
+    if (e == hipSuccess) e = c->d_word.grow(2);
+    if (e == hipSuccess) e = c->h_word.grow(2);
+    if (e == hipSuccess) e = c->d_cut.grow(6);
+    if (e == hipSuccess) e = c->d_trim.grow(1);
+    if (e == hipSuccess) e = c->h_trim.grow(1);
+    if (e == hipSuccess) e = c->d_render.grow(1);
+    if (e == hipSuccess) e = c->h_render.grow(1);
+    if (e == hipSuccess) e = c->fa_hdr.grow(1);
+    if (e == hipSuccess) e = c->h_cut.grow(6);
+    if (e == hipSuccess) e = c->h_L.grow(1);
+    if (e == hipSuccess) e = c->h_ctl.grow(1);
+    if (e == hipSuccess) e = c->h_res.grow(1);
+    if (e == hipSuccess) e = c->h_seq.grow(8);
     if (e == hipSuccess) { *c->h_seq = 0; e = hipHostGetDevicePointer((void **)&c->hm_seq, c->h_seq, 0); }
     if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&c->hm_ctl, c->h_ctl, 0);
     if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&c->hm_res, c->h_res, 0);
@@ -297,24 +300,30 @@ static int ctx_create_impl(int device, ffq_ctx *share, ffq_ctx **out)
     return FFQ_OK;
 }
 
+// c->cb as the buffers of c->cm are now.  The functions that regrow those (reserve_tiles, reserve_stage, reserve_dstage)
+// hold one of these: whichever way they return, the view is rebuilt -- no kernel gets a pointer to a block that was freed.
+struct ChainView {
+    ffq_ctx *c;
+    ~ChainView()
+    {
+        ChainMem &m = c->cm;
+        ChainBufs &b = c->cb;
+        b = ChainBufs{};
+        b.y = m.y; b.exit = m.exit; b.cnt = m.cnt; b.flags = m.flags; b.lines = m.lines; b.qb = m.qb; b.term = m.term;
+        b.stage = m.stage; b.dstage = m.dstage; b.dchunks = (int32_t)(m.dstage.cap / DCHUNK);
+        b.dlist = m.dlist; b.ilist = m.ilist; b.rloc = m.rloc; b.qloc = m.qloc; b.part = m.part; b.mins = m.mins;
+        b.force = m.force;
+    }
+};
+
+// everything sized by the tile count but the line index itself
 static void free_chain(ffq_ctx *c)
 {
-    (void)hipFree(c->cb.y); (void)hipFree(c->cb.exit); (void)hipFree(c->cb.cnt); (void)hipFree(c->cb.flags);
-    (void)hipFree(c->cb.lines); (void)hipFree(c->cb.qb); (void)hipFree(c->cb.term); (void)hipFree(c->cb.stage);
-    (void)hipFree(c->cb.rloc); (void)hipFree(c->cb.qloc); (void)hipFree(c->cb.part); (void)hipFree(c->cb.mins);
-    (void)hipFree(c->cb.force); (void)hipFree(c->cb.dlist); (void)hipFree(c->cb.ilist);
-    (void)hipFree(c->sbbase); (void)hipFree(c->tinfo4);
-    (void)hipFree(c->tileq); (void)hipFree(c->sbq); (void)hipFree(c->sbqbase);
-    c->sbbase = nullptr; c->tinfo4 = nullptr;
-    c->tileq = nullptr; c->sbq = nullptr; c->sbqbase = nullptr;
-    {
-        // (the walked groups' stage does not depend on the tile count: it stays)
-        StageRec *ds = c->cb.dstage; const int32_t dc = c->cb.dchunks;
-        c->cb = ChainBufs{};
-        c->cb.dstage = ds; c->cb.dchunks = dc;
-    }
-    c->stage_cap = 0;
-    c->cap_groups = 0;
+    ChainMem &m = c->cm;
+    m.y.reset(); m.exit.reset(); m.cnt.reset(); m.flags.reset(); m.lines.reset(); m.qb.reset(); m.term.reset(); m.stage.reset();
+    m.rloc.reset(); m.qloc.reset(); m.part.reset(); m.mins.reset(); m.force.reset(); m.dlist.reset(); m.ilist.reset();
+    // (the walked groups' stage, m.dstage, does not depend on the tile count: it stays)
+    c->sbbase.reset(); c->tinfo4.reset(); c->tileq.reset(); c->sbq.reset(); c->sbqbase.reset();
 }
 
 extern "C" int ffq_ctx_create_shared(ffq_ctx *parent, ffq_ctx **out)
@@ -332,33 +341,9 @@ extern "C" void ffq_ctx_destroy(ffq_ctx *c)
     for (auto &r : c->stage_ev) for (auto &e : r) if (e) (void)hipEventDestroy(e);
     for (auto &st : c->stage_cs) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
     delete c->helpers;
-    (void)hipFree(c->ent); (void)hipFree(c->cnt); (void)hipFree(c->ovf); (void)hipFree(c->pool);
-    (void)hipFree(c->rk.tbase); (void)hipFree(c->rk.cand); (void)hipFree(c->rk.rec); (void)hipFree(c->rk.succ);
-    (void)hipFree(c->rk.S[0]); (void)hipFree(c->rk.S[1]); (void)hipFree(c->rk.C[0]); (void)hipFree(c->rk.C[1]);
-    (void)hipFree(c->rk.D); (void)hipFree(c->rk.root);
-    free_chain(c);
-    (void)hipFree(c->cb.dstage);
-    (void)hipFree(c->fz_qphase); (void)hipFree(c->fz_bad);
-    (void)hipFree(c->ctl); (void)hipFree(c->dres); (void)hipFree(c->d_L); (void)hipFree(c->hdr4);
-    if (c->h_L) (void)hipHostFree(c->h_L);
-    (void)hipFree(c->qdir); (void)hipFree(c->p4s); (void)hipFree(c->qrel);
-    (void)hipFree(c->sel_cnt); (void)hipFree(c->sel_base); (void)hipFree(c->col_sum); (void)hipFree(c->scan_bs); (void)hipFree(c->scan_res); (void)hipFree(c->col_res);
-    (void)hipFree(c->stage_d); (void)hipFree(c->tab_d); (void)hipFree(c->qual_d); (void)hipFree(c->qoff_d);
-    if (c->h_word) (void)hipHostFree(c->h_word);
-    if (c->h_cut) (void)hipHostFree(c->h_cut);
-    if (c->h_trim) (void)hipHostFree(c->h_trim);
-    (void)hipFree(c->d_trim); (void)hipFree(c->trim_list);
-    if (c->h_render) (void)hipHostFree(c->h_render);
-    (void)hipFree(c->d_render); (void)hipFree(c->render_list);
-    (void)hipFree(c->d_word); (void)hipFree(c->d_cut); (void)hipFree(c->fa_hdr);
-    if (c->h_seq) (void)hipHostFree(c->h_seq);
-    if (c->h_ctl) (void)hipHostFree(c->h_ctl);
-    if (c->h_res) (void)hipHostFree(c->h_res);
-    if (c->stage_h) (void)hipHostFree(c->stage_h);
-    if (c->tab_h) (void)hipHostFree(c->tab_h);
     for (int i = 0; i < 7; i++) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
     if (c->stream && c->owns_streams) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                            // (the buffers are members: they free themselves here)
 }
 
 // something other than a scan front goes onto the context's stream (every entry point that enqueues there says so)
@@ -455,67 +440,62 @@ static int reserve_tiles(ffq_ctx *c, int64_t ntiles)
 {
     if (ntiles <= c->cap_tiles) return FFQ_OK;
     CTX_SYNC(c);
-    (void)hipFree(c->ent); (void)hipFree(c->cnt); (void)hipFree(c->ovf);
-    c->ent = nullptr; c->cnt = nullptr; c->ovf = nullptr;
+    ChainView refill{c};
+    ChainMem &m = c->cm;
+    c->ent.reset(); c->cnt.reset(); c->ovf.reset();
     free_chain(c);
     c->cap_tiles = 0;
     const int64_t ng = groups_for(ntiles);
     const int64_t nblk = (ng + RES_BLOCK - 1) / RES_BLOCK;
-    HIPCHK(hipMalloc((void **)&c->ent, (size_t)ntiles * SLOT * sizeof(uint16_t)));
-    HIPCHK(hipMalloc((void **)&c->cnt, (size_t)ntiles * sizeof(uint32_t)));
-    HIPCHK(hipMalloc((void **)&c->ovf, (size_t)ntiles * sizeof(unsigned long long)));
-    HIPCHK(hipMalloc((void **)&c->cb.y, (size_t)ng * 8));
-    HIPCHK(hipMalloc((void **)&c->cb.exit, (size_t)ng * 8));
-    HIPCHK(hipMalloc((void **)&c->cb.cnt, (size_t)ng * 4));
-    HIPCHK(hipMalloc((void **)&c->cb.flags, (size_t)(2 * ng + 8) * 4));      // (flags | sbase | dhead | dcnt: one fill per scan, chain_bufs)
-    HIPCHK(hipMalloc((void **)&c->cb.dlist, (size_t)ng * 4));
-    HIPCHK(hipMalloc((void **)&c->cb.ilist, (size_t)ng * 4));
-    HIPCHK(hipMalloc((void **)&c->cb.lines, (size_t)ng * 4));
-    HIPCHK(hipMalloc((void **)&c->cb.qb, (size_t)ng * 8));
-    HIPCHK(hipMalloc((void **)&c->cb.term, (size_t)ng * sizeof(GroupTerm)));
-    HIPCHK(hipMalloc((void **)&c->cb.rloc, (size_t)ng * 8));
-    HIPCHK(hipMalloc((void **)&c->cb.qloc, (size_t)ng * 8));
-    HIPCHK(hipMalloc((void **)&c->cb.part, (size_t)nblk * 4 * 8));
-    HIPCHK(hipMalloc((void **)&c->cb.mins, 16));
-    HIPCHK(hipMalloc((void **)&c->cb.force, (size_t)ng * 8));
+    HIPCHK(c->ent.grow(ntiles * SLOT));
+    HIPCHK(c->cnt.grow(ntiles));
+    HIPCHK(c->ovf.grow(ntiles));
+    HIPCHK(m.y.grow(ng));
+    HIPCHK(m.exit.grow(ng));
+    HIPCHK(m.cnt.grow(ng));
+    HIPCHK(m.flags.grow(2 * ng + 8));      // (flags | sbase | dhead | dcnt: one fill per scan, chain_bufs)
+    HIPCHK(m.dlist.grow(ng));
+    HIPCHK(m.ilist.grow(ng));
+    HIPCHK(m.lines.grow(ng));
+    HIPCHK(m.qb.grow(ng));
+    HIPCHK(m.term.grow(ng));
+    HIPCHK(m.rloc.grow(ng));
+    HIPCHK(m.qloc.grow(ng));
+    HIPCHK(m.part.grow(nblk * 4));
+    HIPCHK(m.mins.grow(4));
+    HIPCHK(m.force.grow(ng));
     {
         const int64_t nsb = (ntiles + SB_TILES - 1) / SB_TILES;
-        HIPCHK(hipMalloc((void **)&c->sbbase, (size_t)nsb * sizeof(long long)));
-        HIPCHK(hipMalloc((void **)&c->tinfo4, (size_t)ntiles * sizeof(TermInfo4)));
-        HIPCHK(hipMalloc((void **)&c->tileq, (size_t)ntiles * sizeof(TileQ)));
-        HIPCHK(hipMalloc((void **)&c->sbq, (size_t)nsb * sizeof(unsigned int)));
-        HIPCHK(hipMalloc((void **)&c->sbqbase, (size_t)nsb * sizeof(long long)));
-        if (!c->hdr4) HIPCHK(hipMalloc((void **)&c->hdr4, sizeof(Fast4Hdr)));
+        HIPCHK(c->sbbase.grow(nsb));
+        HIPCHK(c->tinfo4.grow(ntiles));
+        HIPCHK(c->tileq.grow(ntiles));
+        HIPCHK(c->sbq.grow(nsb));
+        HIPCHK(c->sbqbase.grow(nsb));
+        HIPCHK(c->hdr4.grow(1));
     }
     c->cap_tiles = ntiles;
-    c->cap_groups = ng;
     return FFQ_OK;
 }
 
 // the walked groups' stage (k_dense_walk): `chunks` chunks of DCHUNK records
 static int reserve_dstage(ffq_ctx *c, int64_t chunks)
 {
-    if (chunks <= c->dstage_chunks) return FFQ_OK;
+    if (chunks * DCHUNK <= c->cm.dstage.cap) return FFQ_OK;
     CTX_SYNC(c);
-    (void)hipFree(c->cb.dstage);
-    c->cb.dstage = nullptr; c->dstage_chunks = 0; c->cb.dchunks = 0;
-    hipError_t e = hipMalloc((void **)&c->cb.dstage, (size_t)chunks * DCHUNK * sizeof(StageRec));
+    ChainView refill{c};
+    const hipError_t e = c->cm.dstage.grow(chunks * DCHUNK);
     if (e != hipSuccess) return fail(FFQ_E_NOMEM, "hipMalloc(walked groups' stage, %lld chunks) failed: %s", (long long)chunks, hipGetErrorString(e));
-    c->dstage_chunks = chunks;
-    c->cb.dchunks = (int32_t)chunks;
     return FFQ_OK;
 }
 
 static int reserve_stage(ffq_ctx *c, int64_t ng, int nmax)
 {
     const int64_t need = ng * nmax;
-    if (need <= c->stage_cap) return FFQ_OK;
+    if (need <= c->cm.stage.cap) return FFQ_OK;
     CTX_SYNC(c);
-    (void)hipFree(c->cb.stage);
-    c->cb.stage = nullptr; c->stage_cap = 0;
-    hipError_t e = hipMalloc((void **)&c->cb.stage, (size_t)need * sizeof(StageRec));
+    ChainView refill{c};
+    const hipError_t e = c->cm.stage.grow(need);
     if (e != hipSuccess) return fail(FFQ_E_NOMEM, "hipMalloc(stage) failed: %s", hipGetErrorString(e));
-    c->stage_cap = need;
     return FFQ_OK;
 }
 
@@ -528,13 +508,10 @@ static int64_t qdir_blocks(int64_t n_bytes, int64_t qual_cap)
 
 static int reserve_qdir(ffq_ctx *c, int64_t blocks)
 {
-    if (blocks <= c->qdir_cap) return FFQ_OK;
+    if (blocks <= c->qdir.cap) return FFQ_OK;
     CTX_SYNC(c);
-    (void)hipFree(c->qdir);
-    c->qdir = nullptr; c->qdir_cap = 0;
-    hipError_t e = hipMalloc((void **)&c->qdir, (size_t)blocks * sizeof(int64_t));
+    const hipError_t e = c->qdir.grow(blocks);
     if (e != hipSuccess) return fail(FFQ_E_NOMEM, "hipMalloc(qdir) failed: %s", hipGetErrorString(e));
-    c->qdir_cap = blocks;
     return FFQ_OK;
 }
 
@@ -543,14 +520,15 @@ static int reserve_qdir(ffq_ctx *c, int64_t blocks)
 static int64_t p4s_need(int64_t n_bytes, int64_t table_cap) { return std::min<int64_t>(table_cap, n_bytes / 4 + 2); }
 static int reserve_p4s(ffq_ctx *c, int64_t entries)
 {
-    if (entries <= c->p4s_cap) return FFQ_OK;
+    if (entries <= c->p4s.cap) return FFQ_OK;
     CTX_SYNC(c);
-    (void)hipFree(c->p4s); (void)hipFree(c->qrel);
-    c->p4s = nullptr; c->qrel = nullptr; c->p4s_cap = 0;
-    hipError_t e = hipMalloc((void **)&c->p4s, (size_t)entries * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&c->qrel, (size_t)entries * sizeof(uint32_t));
-    if (e != hipSuccess) return fail(FFQ_E_NOMEM, "hipMalloc(p4s) failed: %s", hipGetErrorString(e));
-    c->p4s_cap = entries;
+    c->p4s.reset(); c->qrel.reset();
+    hipError_t e = c->p4s.grow(entries);
+    if (e == hipSuccess) e = c->qrel.grow(entries);
+    if (e != hipSuccess) {
+        c->p4s.reset(); c->qrel.reset();          // (p4s.cap stands for both)
+        return fail(FFQ_E_NOMEM, "hipMalloc(p4s) failed: %s", hipGetErrorString(e));
+    }
     return FFQ_OK;
 }
 
@@ -559,12 +537,9 @@ constexpr unsigned long long POOL_MIN = (unsigned long long)POOL_NB * TILE;
 
 static int reserve_pool(ffq_ctx *c, unsigned long long entries)
 {
-    if (entries <= c->pool_cap) return FFQ_OK;
+    if (entries <= (unsigned long long)c->pool.cap) return FFQ_OK;
     CTX_SYNC(c);
-    (void)hipFree(c->pool);
-    c->pool = nullptr; c->pool_cap = 0;
-    HIPCHK(hipMalloc((void **)&c->pool, (size_t)entries * sizeof(uint16_t)));
-    c->pool_cap = entries;
+    HIPCHK(c->pool.grow((int64_t)entries));
     return FFQ_OK;
 }
 
@@ -664,7 +639,7 @@ static LineIndex make_index(ffq_ctx *c, const ScanArgs &a, int64_t ntiles)
 {
     LineIndex L;
     L.d = a.d_buf; L.n = a.n_bytes; L.s = a.s; L.ntiles = (int32_t)ntiles; L.ready = (int32_t)ntiles; L.pad_ = 0;
-    L.ent = c->ent; L.cnt = c->cnt; L.ovf = c->ovf; L.pool = c->pool; L.pool_cap = c->pool_cap;
+    L.ent = c->ent; L.cnt = c->cnt; L.ovf = c->ovf; L.pool = c->pool; L.pool_cap = (unsigned long long)c->pool.cap;
     return L;
 }
 
@@ -676,17 +651,18 @@ static void launch_scan_lines(ffq_ctx *c, hipStream_t st, const uint8_t *d_buf, 
 {
     const int64_t nfull = n_bytes >> TILE_SHIFT;
     const int ragged = ntiles > nfull ? (int)nfull : -1;
+    const unsigned long long pool_cap = (unsigned long long)c->pool.cap;
     int8_t *const no_out = nullptr;
     if (wout) {
         // the WIDE instantiation (ffq_kernels.h): the index AND every byte decoded in place, for the decode of records of any
         // layout in one pass (FFQ_F_DECODE_QUAL | FFQ_F_SINGLE_PASS on the general path)
         if (nfull > 0)
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_lines<true, 8, true>), dim3((unsigned)nfull), dim3(256), 0, st, d_buf,
-                               n_bytes, c->ent, c->cnt, c->ovf, c->pool, c->pool_cap, c->ctl, 0, L, c->d_L,
+                               n_bytes, c->ent, c->cnt, c->ovf, c->pool, pool_cap, c->ctl, 0, L, c->d_L,
                                at_char, ragged, wout, (uint32_t)wadd);
         else
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_lines<false, 8, true>), dim3(1), dim3(256), 0, st, d_buf,
-                               n_bytes, c->ent, c->cnt, c->ovf, c->pool, c->pool_cap, c->ctl, 0, L, c->d_L,
+                               n_bytes, c->ent, c->cnt, c->ovf, c->pool, pool_cap, c->ctl, 0, L, c->d_L,
                                at_char, 0, wout, (uint32_t)wadd);
         return;
     }
@@ -696,15 +672,15 @@ static void launch_scan_lines(ffq_ctx *c, hipStream_t st, const uint8_t *d_buf, 
         // index kernel reads the caller's bytes and writes this context's own scratch, nothing the previous
         // scan touches; the kernels behind it are ordinary launches and wait for everything in front of them.
         hipExtLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_lines<true, 8>), dim3((unsigned)nfull), dim3(256), 0, st, nullptr, nullptr,
-                              hipExtAnyOrderLaunch, d_buf, n_bytes, c->ent, c->cnt, c->ovf, c->pool, c->pool_cap, c->ctl, 0,
-                              L, c->d_L, at_char, ragged, no_out, 0u);
+                              hipExtAnyOrderLaunch, d_buf, n_bytes, c->ent.p, c->cnt.p, c->ovf.p, c->pool.p, pool_cap, c->ctl.p, 0,
+                              L, c->d_L.p, at_char, ragged, no_out, 0u);
     else if (nfull > 0)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_lines<true, 8>), dim3((unsigned)nfull), dim3(256), 0, st, d_buf,
-                           n_bytes, c->ent, c->cnt, c->ovf, c->pool, c->pool_cap, c->ctl, 0, L, c->d_L,
+                           n_bytes, c->ent, c->cnt, c->ovf, c->pool, pool_cap, c->ctl, 0, L, c->d_L,
                            at_char, ragged, no_out, 0u);
     else
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_lines<false, 8>), dim3(1), dim3(256), 0, st, d_buf,
-                           n_bytes, c->ent, c->cnt, c->ovf, c->pool, c->pool_cap, c->ctl, 0, L, c->d_L,
+                           n_bytes, c->ent, c->cnt, c->ovf, c->pool, pool_cap, c->ctl, 0, L, c->d_L,
                            at_char, 0, no_out, 0u);
 }
 
@@ -716,7 +692,7 @@ static void enqueue_decode(ffq_ctx *c, const ScanArgs &a, hipStream_t st, bool t
     const int64_t nblk = qdir_blocks(a.n_bytes, a.qual_cap);
     hipLaunchKernelGGL(k_decode_stream, dim3((unsigned)nblk), dim3(256), 0, st, a.d_buf, a.n_bytes, a.s,
                        (const int64_t *)c->p4s, (const int64_t *)a.d_qoff, (const int64_t *)c->qdir,
-                       (const DevRes *)c->dres, std::min<int64_t>(a.table_cap, c->p4s_cap), a.add, a.qual_add, a.d_qual,
+                       (const DevRes *)c->dres, std::min<int64_t>(a.table_cap, c->p4s.cap), a.add, a.qual_add, a.d_qual,
                        a.qual_cap);
 }
 
@@ -727,14 +703,11 @@ static_assert(SG_STRIDE == FFQ_SEG_STRIDE, "include/ffq.h and csrc/ffq_fused.h d
 
 static int enqueue_fused_index(ffq_ctx *c, const ScanArgs &a, int64_t ntiles, bool in_place)
 {
-    if (ntiles > c->fz_tiles_cap) {
+    if (ntiles > c->fz_qphase.cap) {
         CTX_SYNC(c);
-        (void)hipFree(c->fz_qphase);
-        c->fz_qphase = nullptr; c->fz_tiles_cap = 0;
-        if (hipMalloc((void **)&c->fz_qphase, (size_t)ntiles) != hipSuccess) return fail(FFQ_E_NOMEM, "hipMalloc(fused scratch) failed");
-        c->fz_tiles_cap = ntiles;
+        if (c->fz_qphase.grow(ntiles) != hipSuccess) return fail(FFQ_E_NOMEM, "hipMalloc(fused scratch) failed");
     }
-    if (!c->fz_bad && hipMalloc((void **)&c->fz_bad, 16) != hipSuccess) return fail(FFQ_E_NOMEM, "hipMalloc failed");
+    if (c->fz_bad.grow(4) != hipSuccess) return fail(FFQ_E_NOMEM, "hipMalloc failed");
     hipStream_t sA = c->stream;
     HIPCHK(hipMemsetAsync(c->fz_bad, 0, 16, sA));
     SegArgs fa{};
@@ -760,7 +733,7 @@ static int poll_seq(ffq_ctx *c, unsigned long long want)
 {
     const auto t0 = std::chrono::steady_clock::now();
     for (uint64_t spins = 1;; spins++) {
-        if (__atomic_load_n(c->h_seq, __ATOMIC_ACQUIRE) >= want) return FFQ_OK;
+        if (__atomic_load_n(c->h_seq.p, __ATOMIC_ACQUIRE) >= want) return FFQ_OK;
         if ((spins & 0x7FFF) == 0) {
             if (c->watchdog_s > 0) {
                 const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -769,7 +742,7 @@ static int poll_seq(ffq_ctx *c, unsigned long long want)
             }
             const hipError_t e = hipStreamQuery(c->stream);
             if (e == hipSuccess) {           // the stream has drained: the publisher has run, or never will
-                if (__atomic_load_n(c->h_seq, __ATOMIC_ACQUIRE) >= want) return FFQ_OK;
+                if (__atomic_load_n(c->h_seq.p, __ATOMIC_ACQUIRE) >= want) return FFQ_OK;
                 return fail(FFQ_E_INTERNAL, "the result block was not published");
             }
             if (e != hipErrorNotReady) return fail(FFQ_E_HIP, "hipStreamQuery failed: %s", hipGetErrorString(e));
@@ -791,8 +764,8 @@ static int enqueue_resolve(ffq_ctx *c, const ScanState &st, const ChainBufs &cb,
     hipLaunchKernelGGL(k_resolve_a, dim3(nblk), dim3(RES_BLOCK), 0, sA, cb);
     hipLaunchKernelGGL(k_resolve_b, dim3(1), dim3(1024), 0, sA, cb, nblk, a.eof, a.offset, a.add, c->dres);
     hipLaunchKernelGGL(k_expand, dim3(ngroups), dim3(64), 0, sA, cb, (const DevRes *)c->dres, a.add, a.d_table,
-                       a.table_cap, qoff, wide ? (int64_t *)nullptr : c->qdir, c->qdir_cap, (qoff && !wide) ? c->p4s : (int64_t *)nullptr,
-                       (qoff && !wide) ? std::min<int64_t>(a.table_cap, c->p4s_cap) : (int64_t)0, a.s, wide ? 1 : 0);
+                       a.table_cap, qoff, wide ? (int64_t *)nullptr : c->qdir, c->qdir.cap, (qoff && !wide) ? c->p4s : (int64_t *)nullptr,
+                       (qoff && !wide) ? std::min<int64_t>(a.table_cap, c->p4s.cap) : (int64_t)0, a.s, wide ? 1 : 0);
     hipLaunchKernelGGL(k_finalize, dim3(1), dim3(64), 0, sA, c->dres, a.d_table, a.table_cap, a.add, a.offset, qoff,
                        make_pub(c), wide ? a.s : -1);
     c->ctl_clean = true;
@@ -1024,7 +997,7 @@ static int enqueue_front(ffq_ctx *c, ScanState &st)
         hipLaunchKernelGGL(rows4, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, sA, L,
                            (const long long *)c->sbbase, a.eof, a.add, c->hdr4, c->tinfo4, a.d_table, a.table_cap,
                            decode ? c->qrel : (uint32_t *)nullptr, c->tileq, decode ? c->p4s : (int64_t *)nullptr,
-                           decode ? std::min<int64_t>(a.table_cap, c->p4s_cap) : (int64_t)0,
+                           decode ? std::min<int64_t>(a.table_cap, c->p4s.cap) : (int64_t)0,
                            (int64_t)0, (const uint8_t *)nullptr, (int64_t *)nullptr);
         hipLaunchKernelGGL(k_finalize4, dim3(1), dim3(64), 0, sA, L, c->hdr4, (const TermInfo4 *)c->tinfo4, a.eof,
                            a.offset, a.add, (const int64_t *)a.d_table, a.table_cap, c->dres,
@@ -1034,12 +1007,12 @@ static int enqueue_front(ffq_ctx *c, ScanState &st)
             // (publishes); then the decode itself.  All of it is skipped on the device if the
             // fast path is rejected.
             hipLaunchKernelGGL(k_sum64, dim3((unsigned)((nsb + 3) / 4)), dim3(256), 0, sA,
-                               reinterpret_cast<const uint32_t *>(c->tileq) + 3, 4, (int64_t)ntiles, c->sbq, nsb);
+                               reinterpret_cast<const uint32_t *>(c->tileq.p) + 3, 4, (int64_t)ntiles, c->sbq, nsb);
             hipLaunchKernelGGL(k_qscan4, dim3(1), dim3(1024), 0, sA, (const unsigned int *)c->sbq, nsb, c->sbqbase);
             hipLaunchKernelGGL(k_qfix4, dim3((unsigned)((ntiles + 7) / 8)), dim3(256), 0, sA, (int)ntiles,
                                (const Fast4Hdr *)c->hdr4, (const TileQ *)c->tileq, (const long long *)c->sbqbase,
-                               (const uint32_t *)c->qrel, a.d_qoff, std::min<int64_t>(a.table_cap, c->p4s_cap), c->qdir,
-                               c->qdir_cap);
+                               (const uint32_t *)c->qrel, a.d_qoff, std::min<int64_t>(a.table_cap, c->p4s.cap), c->qdir,
+                               c->qdir.cap);
             hipLaunchKernelGGL(k_qtotal4, dim3(1), dim3(1), 0, sA, c->dres, (const int64_t *)a.d_table, a.table_cap,
                                a.d_qoff, make_pub(c));
             enqueue_decode(c, a, sA, true);
@@ -1073,7 +1046,7 @@ static int enqueue_front(ffq_ctx *c, ScanState &st)
 }
 
 template <class T>
-static int grow_dev(ffq_ctx *c, T **p, int64_t *cap, int64_t need);
+static int grow_dev(ffq_ctx *c, DevBuf<T> &b, int64_t need);
 
 // in-place exclusive scan of nv int64 values on stream st, total into res (k_scan_i64v's contract): one workgroup for short
 // arrays, two levels for long ones
@@ -1084,7 +1057,7 @@ static int launch_scan_i64v(ffq_ctx *c, hipStream_t st, long long *v, int64_t nv
         return FFQ_OK;
     }
     const int64_t nb = (nv + SCAN_BLK - 1) / SCAN_BLK;
-    int rc = grow_dev(c, &c->scan_bs, &c->scan_bs_cap, nb);
+    int rc = grow_dev(c, c->scan_bs, nb);
     if (rc) return rc;
     hipLaunchKernelGGL(k_scan_blksum, dim3((unsigned)nb), dim3(256), 0, st, (const long long *)v, nv, c->scan_bs);
     hipLaunchKernelGGL(k_scan_i64v, dim3(1), dim3(1024), 0, st, c->scan_bs, nb, n_rows, res);
@@ -1100,9 +1073,9 @@ static int launch_scan_u32(ffq_ctx *c, hipStream_t st, const unsigned int *v, in
         return FFQ_OK;
     }
     const int64_t nb = (nv + SCAN_BLK - 1) / SCAN_BLK;
-    int rc = grow_dev(c, &c->scan_bs, &c->scan_bs_cap, nb);
+    int rc = grow_dev(c, c->scan_bs, nb);
     if (rc) return rc;
-    if (!c->scan_res && hipMalloc((void **)&c->scan_res, sizeof(DevRes)) != hipSuccess) return fail(FFQ_E_NOMEM, "hipMalloc failed");
+    if (c->scan_res.grow(1) != hipSuccess) return fail(FFQ_E_NOMEM, "hipMalloc failed");
     hipLaunchKernelGGL(k_scan_blksum_u32, dim3((unsigned)nb), dim3(256), 0, st, v, nv, c->scan_bs);
     hipLaunchKernelGGL(k_scan_i64v, dim3(1), dim3(1024), 0, st, c->scan_bs, nb, (int64_t)0, c->scan_res);
     hipLaunchKernelGGL(k_scan_blkapply_u32, dim3((unsigned)nb), dim3(256), 0, st, v, nv, (const long long *)c->scan_bs, base, total);
@@ -1110,6 +1083,36 @@ static int launch_scan_u32(ffq_ctx *c, hipStream_t st, const unsigned int *v, in
 }
 
 // ---- the list-ranking tier (ffq_ranked.h): exact on any input, cost per "\n@" match ----------------
+// Its scratch comes in two groups, one per tile and one per candidate.  Each has ONE function that grows its buffers and
+// then rebuilds c->rk from c->rm, whichever way the growing went (RankBufs::nc is the caller's); false: no memory.
+static void rank_view(ffq_ctx *c)
+{
+    RankMem &M = c->rm;
+    c->rk = RankBufs{M.tbase, M.cand, M.rec, M.succ, {M.S[0], M.S[1]}, {M.C[0], M.C[1]}, M.D, M.root, 0};
+}
+
+static bool rank_reserve_tiles(ffq_ctx *c, int64_t ntiles)
+{
+    RankMem &M = c->rm;
+    const bool ok = M.tbase.grow(ntiles) == hipSuccess && M.root.grow(4) == hipSuccess;
+    rank_view(c);
+    return ok;
+}
+
+static bool rank_reserve_cands(ffq_ctx *c, int64_t nc)
+{
+    RankMem &M = c->rm;
+    if (nc <= M.cand.cap) return true;             // (M.cand.cap stands for the group)
+    M.cand.reset(); M.rec.reset(); M.succ.reset(); M.D.reset();
+    for (int i = 0; i < 2; i++) { M.S[i].reset(); M.C[i].reset(); }
+    const int64_t n = nc + (nc >> 3) + 1024;
+    bool ok = M.cand.grow(n) == hipSuccess && M.rec.grow(n) == hipSuccess && M.succ.grow(n) == hipSuccess && M.D.grow(n) == hipSuccess;
+    for (int i = 0; i < 2 && ok; i++) ok = M.S[i].grow(n) == hipSuccess && M.C[i].grow(n) == hipSuccess;
+    if (!ok) M.cand.reset();                       // (the next scan asks again)
+    rank_view(c);
+    return ok;
+}
+
 // Returns FFQ_OK with the result published, 1 if the tier cannot run here (too many candidates for
 // 32-bit ranks, no memory: the caller then takes the one-wave walker), 2 if only_if_sparse is set
 // and the buffer has more than one candidate per 512 bytes.
@@ -1117,13 +1120,8 @@ static int run_ranked(ffq_ctx *c, const ScanArgs &a, const LineIndex &L, int64_t
 {
     hipStream_t sA = c->stream;
     RankBufs &R = c->rk;
-    if (ntiles > c->rk_cap_tiles) {
-        (void)hipFree(R.tbase); R.tbase = nullptr; c->rk_cap_tiles = 0;
-        if (hipMalloc((void **)&R.tbase, (size_t)ntiles * sizeof(long long)) != hipSuccess) return 1;
-        c->rk_cap_tiles = ntiles;
-    }
-    if (!R.root && hipMalloc((void **)&R.root, 16) != hipSuccess) return 1;
-    if (!c->col_res && hipMalloc((void **)&c->col_res, sizeof(DevRes)) != hipSuccess) return 1;
+    if (!rank_reserve_tiles(c, ntiles)) return 1;
+    if (c->col_res.grow(1) != hipSuccess) return 1;
     hipLaunchKernelGGL(k_rk_count, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, sA, L, R.tbase);
     if (launch_scan_i64v(c, sA, R.tbase, ntiles, (int64_t)0, c->col_res)) return 1;
     HIPCHK(hipMemcpyAsync(c->h_word, &c->col_res->n_qual_bytes, sizeof(int64_t), hipMemcpyDeviceToHost, sA));
@@ -1133,18 +1131,7 @@ static int run_ranked(ffq_ctx *c, const ScanArgs &a, const LineIndex &L, int64_t
     if (nc >= 0x7FFFFFF0ll) return 1;
     // a context that remembers long records meets short ones again: back to the group kernels
     if (only_if_sparse && nc * 512 > a.n_bytes) return 2;
-    if (nc > c->rk_cap_c) {
-        (void)hipFree(R.cand); (void)hipFree(R.rec); (void)hipFree(R.succ); (void)hipFree(R.D);
-        for (int i = 0; i < 2; i++) { (void)hipFree(R.S[i]); (void)hipFree(R.C[i]); R.S[i] = R.C[i] = nullptr; }
-        R.cand = nullptr; R.rec = nullptr; R.succ = nullptr; R.D = nullptr; c->rk_cap_c = 0;
-        const size_t n = (size_t)nc + (nc >> 3) + 1024;
-        bool ok = hipMalloc((void **)&R.cand, n * sizeof(H)) == hipSuccess && hipMalloc((void **)&R.rec, n * sizeof(RankRec)) == hipSuccess &&
-                  hipMalloc((void **)&R.succ, n * 4) == hipSuccess && hipMalloc((void **)&R.D, n * 4) == hipSuccess;
-        for (int i = 0; i < 2 && ok; i++)
-            ok = hipMalloc((void **)&R.S[i], n * 4) == hipSuccess && hipMalloc((void **)&R.C[i], n * 4) == hipSuccess;
-        if (!ok) { (void)hipGetLastError(); return 1; }
-        c->rk_cap_c = (int64_t)n;
-    }
+    if (!rank_reserve_cands(c, nc)) { (void)hipGetLastError(); return 1; }
     R.nc = nc;
     const unsigned gthr = (unsigned)std::max<int64_t>((nc + 255) / 256, 1);
     if (nc > 0) {
@@ -1176,7 +1163,7 @@ static int enqueue_offsets_and_decode(ffq_ctx *c, const ScanArgs &a, int64_t n_r
         return FFQ_OK;
     }
     const int64_t nblk = (n_rows + 255) / 256;
-    int rc = grow_dev(c, &c->col_sum, &c->col_sum_cap, nblk);
+    int rc = grow_dev(c, c->col_sum, nblk);
     if (rc) return rc;
     hipLaunchKernelGGL(k_col_sum, dim3((unsigned)nblk), dim3(256), 0, sA, (const int64_t *)a.d_table, n_rows, 4, 0, 5,
                        a.n_bytes, a.s, a.add, c->col_sum);
@@ -1184,7 +1171,7 @@ static int enqueue_offsets_and_decode(ffq_ctx *c, const ScanArgs &a, int64_t n_r
     if ((rc = launch_scan_i64v(c, sA, c->col_sum, nblk, n_rows, c->dres))) return rc;
     hipLaunchKernelGGL(k_col_offsets, dim3((unsigned)nblk), dim3(256), 0, sA, (const int64_t *)a.d_table, n_rows, 4, 0, 5,
                        a.n_bytes, a.s, a.add, (const long long *)c->col_sum, (const DevRes *)c->dres, a.d_qoff, c->p4s, c->qdir,
-                       c->qdir_cap);
+                       c->qdir.cap);
     hipLaunchKernelGGL(k_publish, dim3(1), dim3(1), 0, sA, c->dres, make_pub(c), 0);
     enqueue_decode(c, a, sA);
     return FFQ_OK;
@@ -1256,7 +1243,7 @@ static int scan_finish(ffq_ctx *c, ScanState &st, ffq_scan_result *res)
             if (st.retries >= 4) return fail(FFQ_E_INTERNAL, "the walked groups' stage stays too small");
             uint32_t asked = 0;
             HIPCHK(hipMemcpy(&asked, c->cb.flags + 2 * (size_t)st.ngroups, sizeof asked, hipMemcpyDeviceToHost));
-            int rc = reserve_dstage(c, std::max<int64_t>((int64_t)asked + (asked >> 3) + 8, 2 * c->dstage_chunks));
+            int rc = reserve_dstage(c, std::max<int64_t>((int64_t)asked + (asked >> 3) + 8, 2 * (int64_t)c->cb.dchunks));
             if (rc) return rc;
             st.retries++;
             st.index_done = true;
@@ -1415,8 +1402,8 @@ static int scan_finish(ffq_ctx *c, ScanState &st, ffq_scan_result *res)
             int rc = run_tier(c, res, [&] {
                 int64_t *const sq = st.wide ? (int64_t *)nullptr : qoff;       // (wide: the offsets from the finished table, below)
                 hipLaunchKernelGGL(k_chain_serial, dim3(1), dim3(64), 0, sA, L, a.offset, a.eof, a.add, a.d_table,
-                                   a.table_cap, sq, c->qdir, c->qdir_cap, sq ? c->p4s : (int64_t *)nullptr,
-                                   sq ? std::min<int64_t>(a.table_cap, c->p4s_cap) : (int64_t)0, c->dres);
+                                   a.table_cap, sq, c->qdir, c->qdir.cap, sq ? c->p4s : (int64_t *)nullptr,
+                                   sq ? std::min<int64_t>(a.table_cap, c->p4s.cap) : (int64_t)0, c->dres);
                 hipLaunchKernelGGL(k_finalize_serial, dim3(1), dim3(64), 0, sA, c->dres, a.table_cap, sq, (decode && st.wide) ? no_pub(c) : make_pub(c));
                 c->ctl_clean = true;
                 if (decode && st.wide) hipLaunchKernelGGL(k_qoff_in_place, dim3(256), dim3(256), 0, sA, c->dres, (const int64_t *)a.d_table, a.table_cap, a.add, a.s, a.d_qoff, make_pub(c));
@@ -1523,17 +1510,15 @@ extern "C" int ffq_scan_device(ffq_ctx *c, const uint8_t *d_buf, int64_t n_bytes
     return ffq_scan_wait(c, res);
 }
 
+// a buffer of the table utilities and the host-buffer entry points: at least 65536 elements, so that small calls of
+// growing sizes do not each reallocate
 template <class T>
-static int grow_dev(ffq_ctx *c, T **p, int64_t *cap, int64_t need)
+static int grow_dev(ffq_ctx *c, DevBuf<T> &b, int64_t need)
 {
-    if (need <= *cap) return FFQ_OK;
+    if (need <= b.cap) return FFQ_OK;
     CTX_SYNC(c);
-    (void)hipFree(*p);
-    *p = nullptr; *cap = 0;
-    const int64_t want = std::max<int64_t>(need, 1 << 16);
-    hipError_t e = hipMalloc((void **)p, (size_t)want * sizeof(T));
+    const hipError_t e = b.grow(std::max<int64_t>(need, 1 << 16));
     if (e != hipSuccess) return fail(FFQ_E_NOMEM, "hipMalloc failed: %s", hipGetErrorString(e));
-    *cap = want;
     return FFQ_OK;
 }
 
@@ -1542,13 +1527,10 @@ constexpr int64_t STAGE_CH = 8 << 20;
 
 static int stage_setup(ffq_ctx *c, int64_t ch = STAGE_CH)
 {
-    if (c->stage_h_cap < 3 * ch) {
-        if (c->stage_h) (void)hipHostFree(c->stage_h);
-        c->stage_h = nullptr; c->stage_h_cap = 0;
+    if (c->stage_h.cap < 3 * ch) {
         NearGpu near(c);
-        hipError_t e = hipHostMalloc((void **)&c->stage_h, (size_t)(3 * ch), hipHostMallocDefault);
+        const hipError_t e = c->stage_h.grow(3 * ch);
         if (e != hipSuccess) return fail(FFQ_E_NOMEM, "hipHostMalloc failed: %s", hipGetErrorString(e));
-        c->stage_h_cap = 3 * ch;
     }
     for (auto &st : c->stage_cs)
         if (!st) HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
@@ -1675,11 +1657,11 @@ extern "C" int ffq_scan_host(ffq_ctx *c, const uint8_t *h_buf, int64_t n_bytes, 
     if (decode && (!h_qual || !h_qoff)) return fail(FFQ_E_ARG, "ffq_scan_host: FFQ_F_DECODE_QUAL needs h_qual and h_qoff");
     HIPCHK(hipSetDevice(c->device));
     int rc;
-    if ((rc = grow_dev(c, &c->stage_d, &c->stage_d_cap, n_bytes + 16))) return rc;
-    if ((rc = grow_dev(c, &c->tab_d, &c->tab_d_cap, std::max<int64_t>(table_cap, 1) * 6))) return rc;
+    if ((rc = grow_dev(c, c->stage_d, n_bytes + 16))) return rc;
+    if ((rc = grow_dev(c, c->tab_d, std::max<int64_t>(table_cap, 1) * 6))) return rc;
     if (decode) {
-        if ((rc = grow_dev(c, &c->qual_d, &c->qual_d_cap, std::max<int64_t>(qual_cap, 16)))) return rc;
-        if ((rc = grow_dev(c, &c->qoff_d, &c->qoff_d_cap, table_cap + 1))) return rc;
+        if ((rc = grow_dev(c, c->qual_d, std::max<int64_t>(qual_cap, 16)))) return rc;
+        if ((rc = grow_dev(c, c->qoff_d, table_cap + 1))) return rc;
     }
     // pageable -> device: three pinned staging slots, filled by the helper threads (slices of a
     // chunk in parallel), emptied over two copy streams (half a chunk each): the host copy of chunk
@@ -1789,8 +1771,8 @@ extern "C" int ffq_scan_fasta_device(ffq_ctx *c, const uint8_t *d_buf, int64_t n
     if (ntiles > 0x7FFFFFF0) return fail(FFQ_E_ARG, "buffer too large");
     int rc = reserve_tiles(c, ntiles);
     if (!rc) rc = reserve_pool(c, POOL_MIN);
-    if (!rc) rc = grow_dev(c, &c->sel_cnt, &c->sel_cnt_cap, ntiles);
-    if (!rc) rc = grow_dev(c, &c->sel_base, &c->sel_base_cap, ntiles);
+    if (!rc) rc = grow_dev(c, c->sel_cnt, ntiles);
+    if (!rc) rc = grow_dev(c, c->sel_base, ntiles);
     if (rc) return rc;
     hipStream_t sA = c->stream;
     ScanArgs a{};
@@ -1805,9 +1787,9 @@ extern "C" int ffq_scan_fasta_device(ffq_ctx *c, const uint8_t *d_buf, int64_t n
         HIPCHK(hipEventRecord(c->ev[1], sA));
         const unsigned tb = (unsigned)((ntiles + 3) / 4);
         hipLaunchKernelGGL(k_fa_count, dim3(tb), dim3(256), 0, sA, L, offset, c->sel_cnt);
-        { const int rs = launch_scan_u32(c, sA, (const unsigned int *)c->sel_cnt, ntiles, c->sel_base, (long long *)c->d_word); if (rs) return rs; }
+        { const int rs = launch_scan_u32(c, sA, (const unsigned int *)c->sel_cnt, ntiles, c->sel_base, (long long *)c->d_word.p); if (rs) return rs; }
         hipLaunchKernelGGL(k_fa_rows, dim3(tb), dim3(256), 0, sA, L, offset, add, (const long long *)c->sel_base,
-                           (const long long *)c->d_word, d_table, table_cap, c->fa_hdr, (const unsigned int *)c->sel_cnt);
+                           (const long long *)c->d_word.p, d_table, table_cap, c->fa_hdr, (const unsigned int *)c->sel_cnt);
         hipLaunchKernelGGL(k_fa_fix, dim3((unsigned)((ntiles + 255) / 256)), dim3(256), 0, sA, L, offset, add,
                            (const FaHdr *)c->fa_hdr, (const unsigned int *)c->sel_cnt, (const long long *)c->sel_base, d_table,
                            table_cap, c->dres, make_pub(c));
@@ -1843,8 +1825,8 @@ extern "C" int ffq_scan_fasta_host(ffq_ctx *c, const uint8_t *h_buf, int64_t n_b
     if (n_bytes > 0 && !h_buf) return fail(FFQ_E_ARG, "ffq_scan_fasta_host: h_buf is NULL");
     HIPCHK(hipSetDevice(c->device));
     int rc;
-    if ((rc = grow_dev(c, &c->stage_d, &c->stage_d_cap, n_bytes + 16))) return rc;
-    if ((rc = grow_dev(c, &c->tab_d, &c->tab_d_cap, std::max<int64_t>(table_cap, 1) * 6))) return rc;
+    if ((rc = grow_dev(c, c->stage_d, n_bytes + 16))) return rc;
+    if ((rc = grow_dev(c, c->tab_d, std::max<int64_t>(table_cap, 1) * 6))) return rc;
     if (n_bytes > 0) HIPCHK(hipMemcpyAsync(c->stage_d, h_buf, (size_t)n_bytes, hipMemcpyHostToDevice, c->stream));
     rc = ffq_scan_fasta_device(c, c->stage_d, n_bytes, sentinel, offset, add, c->tab_d, table_cap, res);
     if (rc != FFQ_OK && rc != FFQ_E_TABLE_FULL) return rc;
@@ -1896,13 +1878,13 @@ static int table_select(ffq_ctx *c, const int64_t *d_table, int64_t n_rows, int6
     *n_out = 0;
     if (n_rows == 0) return FFQ_OK;
     const int64_t nblk = (n_rows + 255) / 256;
-    int rc = grow_dev(c, &c->sel_cnt, &c->sel_cnt_cap, nblk);
-    if (!rc) rc = grow_dev(c, &c->sel_base, &c->sel_base_cap, nblk);
+    int rc = grow_dev(c, c->sel_cnt, nblk);
+    if (!rc) rc = grow_dev(c, c->sel_base, nblk);
     if (rc) return rc;
     hipStream_t st = c->stream;
     hipLaunchKernelGGL(k_sel_count, dim3((unsigned)nblk), dim3(256), 0, st, d_table, n_rows, min_len, max_len,
                        c->sel_cnt);
-    if ((rc = launch_scan_u32(c, st, (const unsigned int *)c->sel_cnt, nblk, c->sel_base, (long long *)c->d_word))) return rc;
+    if ((rc = launch_scan_u32(c, st, (const unsigned int *)c->sel_cnt, nblk, c->sel_base, (long long *)c->d_word.p))) return rc;
     hipLaunchKernelGGL(k_sel_scatter, dim3((unsigned)nblk), dim3(256), 0, st, d_table, n_rows, min_len, max_len,
                        (const long long *)c->sel_base, d_out, d_idx);
     HIPCHK(hipMemcpyAsync(c->h_word, c->d_word, sizeof(int64_t), hipMemcpyDeviceToHost, st));
@@ -1935,9 +1917,9 @@ extern "C" int ffq_table_gather_column(ffq_ctx *c, const uint8_t *d_buf, int64_t
         return FFQ_OK;
     }
     const int64_t nblk = (n_rows + 255) / 256;
-    int rc = grow_dev(c, &c->col_sum, &c->col_sum_cap, nblk);
-    if (!rc && !c->col_res) {
-        hipError_t e = hipMalloc((void **)&c->col_res, sizeof(DevRes));
+    int rc = grow_dev(c, c->col_sum, nblk);
+    if (!rc) {
+        const hipError_t e = c->col_res.grow(1);
         if (e != hipSuccess) rc = fail(FFQ_E_NOMEM, "hipMalloc failed: %s", hipGetErrorString(e));
     }
     // the copy kernel's scratch: a start per row, the directory of the output stream
@@ -1950,7 +1932,7 @@ extern "C" int ffq_table_gather_column(ffq_ctx *c, const uint8_t *d_buf, int64_t
     if ((rc = launch_scan_i64v(c, st, c->col_sum, nblk, n_rows, c->col_res))) return rc;
     hipLaunchKernelGGL(k_col_offsets, dim3((unsigned)nblk), dim3(256), 0, st, d_table, n_rows, col_begin, begin_shift,
                        col_end, n_bytes, sentinel ? 1 : 0, add, (const long long *)c->col_sum, (const DevRes *)c->col_res, d_off,
-                       c->p4s, c->qdir, c->qdir_cap);
+                       c->p4s, c->qdir, c->qdir.cap);
     if (out_cap > 0)
         hipLaunchKernelGGL(k_decode_stream, dim3((unsigned)nqb), dim3(256), 0, st, d_buf, n_bytes, sentinel ? 1 : 0,
                            (const int64_t *)c->p4s, (const int64_t *)d_off, (const int64_t *)c->qdir,
@@ -1982,7 +1964,7 @@ extern "C" int ffq_table_trim_quality(ffq_ctx *c, const uint8_t *d_buf, int64_t 
     HIPCHK(hipSetDevice(c->device));
     stats[0] = stats[1] = stats[2] = 0;
     if (n_rows == 0) return FFQ_OK;
-    int rc = grow_dev(c, &c->trim_list, &c->trim_list_cap, n_rows);
+    int rc = grow_dev(c, c->trim_list, n_rows);
     if (rc) return rc;
     hipStream_t st = c->stream;
     HIPCHK(hipMemsetAsync(c->d_trim, 0, sizeof(TrimBlock), st));
@@ -2025,10 +2007,10 @@ extern "C" int ffq_table_render_fastq(ffq_ctx *c, const uint8_t *d_buf, int64_t 
         return FFQ_OK;
     }
     const int64_t nblk = (n_rows + RENDER_WG - 1) / RENDER_WG;
-    int rc = grow_dev(c, &c->col_sum, &c->col_sum_cap, nblk);
-    if (!rc) rc = grow_dev(c, &c->render_list, &c->render_list_cap, 2 * n_rows);
-    if (!rc && !c->col_res) {
-        hipError_t e = hipMalloc((void **)&c->col_res, sizeof(DevRes));
+    int rc = grow_dev(c, c->col_sum, nblk);
+    if (!rc) rc = grow_dev(c, c->render_list, 2 * n_rows);
+    if (!rc) {
+        const hipError_t e = c->col_res.grow(1);
         if (e != hipSuccess) rc = fail(FFQ_E_NOMEM, "hipMalloc failed: %s", hipGetErrorString(e));
     }
     if (rc) return rc;
@@ -2092,10 +2074,10 @@ extern "C" int ffq_arrayadd_b(ffq_ctx *c, int8_t *h_a, int64_t n, int value)
     if (!c || n < 0 || (n > 0 && !h_a)) return fail(FFQ_E_ARG, "ffq_arrayadd_b: bad argument");
     HIPCHK(hipSetDevice(c->device));
     if (n == 0) return FFQ_OK;
-    int rc = grow_dev(c, &c->stage_d, &c->stage_d_cap, n + 16);
+    int rc = grow_dev(c, c->stage_d, n + 16);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(c->stage_d, h_a, (size_t)n, hipMemcpyHostToDevice, c->stream));
-    rc = ffq_arrayadd_b_device(c, (int8_t *)c->stage_d, n, value);
+    rc = ffq_arrayadd_b_device(c, (int8_t *)c->stage_d.p, n, value);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(h_a, c->stage_d, (size_t)n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -2108,10 +2090,10 @@ extern "C" int ffq_arrayadd_q(ffq_ctx *c, int64_t *h_a, int64_t n, int64_t value
     if (!c || n < 0 || (n > 0 && !h_a)) return fail(FFQ_E_ARG, "ffq_arrayadd_q: bad argument");
     HIPCHK(hipSetDevice(c->device));
     if (n == 0) return FFQ_OK;
-    int rc = grow_dev(c, &c->stage_d, &c->stage_d_cap, n * 8 + 16);
+    int rc = grow_dev(c, c->stage_d, n * 8 + 16);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(c->stage_d, h_a, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    rc = ffq_arrayadd_q_device(c, (int64_t *)c->stage_d, n, value);
+    rc = ffq_arrayadd_q_device(c, (int64_t *)c->stage_d.p, n, value);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(h_a, c->stage_d, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -2159,7 +2141,7 @@ extern "C" int ffq_read_probe(ffq_ctx *c, const uint8_t *d_buf, int64_t n_bytes,
     if (mode != 6) return fail(FFQ_E_ARG, "ffq_read_probe: mode %d does not exist (6: the non-temporal read)", mode);
     HIPCHK(hipSetDevice(c->device));
     const int64_t ntiles = n_bytes >> TILE_SHIFT;
-    uint32_t *sink = reinterpret_cast<uint32_t *>(c->ctl);
+    uint32_t *sink = reinterpret_cast<uint32_t *>(c->ctl.p);
     for (int r = 0; r < reps + 2; r++) {
         if (r == 2) HIPCHK(hipEventRecord(c->ev[0], c->stream));
         hipLaunchKernelGGL(k_read_probe, dim3((unsigned)ntiles), dim3(256), 0, c->stream, d_buf, sink);

@@ -57,8 +57,7 @@
 constexpr int STREAM_SLOTS = FFQ_STREAM_SLOTS;
 
 struct StreamSlot {
-    uint8_t *h = nullptr;        // pinned  [room | fbufsize (+16)]
-    uint8_t *d = nullptr;        // device  same layout
+    Mirror<uint8_t> buf;         // pinned h and device d, the same layout: [room | fbufsize (+16)]
     hipEvent_t copied[2] = {nullptr, nullptr};   // the chunk's H2D copy is through (one half per copy stream)
     int64_t got = 0;             // bytes of the chunk (at offset room)
     bool eof = false;            // the source is exhausted behind this chunk
@@ -74,51 +73,26 @@ struct StreamBufs {
     hipStream_t cs[2] = {nullptr, nullptr};      // copy streams of the chunks: a chunk goes over in two halves, one
                                                  // per stream (two DMA engines: one did 41-45 GB/s of the link's ~55)
     bool one_copy_stream = false;                // ... unless much goes BACK as well (stream_copy_chunk)
-    int64_t *dtab = nullptr, *htab = nullptr;
-    int64_t tab_cap = 0;
-    int8_t *dqual = nullptr, *hqual = nullptr;
-    int64_t qual_cap = 0;
-    int64_t *dqoff = nullptr, *hqoff = nullptr;
-    int64_t qoff_cap = 0;
+    // device + pinned pairs (ffq_mem.h), grown by stream_grow
+    Mirror<int64_t> tab;         // the fill's rows: 6 words each (stream_tab_rows)
+    Mirror<int8_t> qual;
+    Mirror<int64_t> qoff;
     // push-down (ffq_stream_set_filter): the kept rows and their ordinals, the gathered column
-    int64_t *dsel = nullptr, *didx = nullptr, *hidx = nullptr;
-    int64_t sel_cap = 0;
-    int8_t *dcol = nullptr, *hcol = nullptr;
-    int64_t col_cap = 0;
-    int64_t *dcoff = nullptr, *hcoff = nullptr;
-    int64_t coff_cap = 0;
+    DevBuf<int64_t> sel;
+    Mirror<int64_t> idx;
+    Mirror<int8_t> col;
+    Mirror<int64_t> coff;
     // rendering (ffq_stream_set_render): the fill's FASTQ text
-    uint8_t *dren = nullptr, *hren = nullptr;
-    int64_t ren_cap = 0;
+    Mirror<uint8_t> ren;
     ReadPool *pool = nullptr;    // the context's helper threads (not owned)
 };
-
-static void streambufs_free_slots(StreamBufs *b)
-{
-    for (auto &s : b->slot) {
-        if (s.h) (void)hipHostFree(s.h);
-        (void)hipFree(s.d);
-        s.h = nullptr; s.d = nullptr;
-    }
-}
 
 static void streambufs_free(StreamBufs *b)
 {
     if (!b) return;
-    streambufs_free_slots(b);
     for (auto &s : b->slot) for (auto &e : s.copied) if (e) (void)hipEventDestroy(e);
-    if (b->htab) (void)hipHostFree(b->htab);
-    if (b->hqual) (void)hipHostFree(b->hqual);
-    if (b->hqoff) (void)hipHostFree(b->hqoff);
-    if (b->hidx) (void)hipHostFree(b->hidx);
-    if (b->hcol) (void)hipHostFree(b->hcol);
-    if (b->hcoff) (void)hipHostFree(b->hcoff);
-    if (b->hren) (void)hipHostFree(b->hren);
-    (void)hipFree(b->dren);
-    (void)hipFree(b->dsel); (void)hipFree(b->didx); (void)hipFree(b->dcol); (void)hipFree(b->dcoff);
-    (void)hipFree(b->dtab); (void)hipFree(b->dqual); (void)hipFree(b->dqoff);
     for (auto &st : b->cs) if (st) (void)hipStreamDestroy(st);
-    delete b;
+    delete b;                    // (the buffers free themselves)
 }
 
 // called by ffq_ctx_destroy
@@ -131,12 +105,10 @@ static void stream_cache_drop(ffq_ctx *c)
 static int streambufs_alloc_slots(ffq_ctx *c, StreamBufs *b, int64_t room)
 {
     NearGpu near(c);                   // (the pinned slots on the GPU's node: ffq_hip.hip)
-    for (auto &s : b->slot) {
-        if (hipHostMalloc((void **)&s.h, (size_t)(room + b->fbufsize + 16), hipHostMallocDefault) != hipSuccess ||
-            hipMalloc((void **)&s.d, (size_t)(room + b->fbufsize + 16)) != hipSuccess)
+    for (auto &s : b->slot)
+        if (s.buf.grow(room + b->fbufsize + 16) != hipSuccess)
             return fail(FFQ_E_NOMEM, "ffq_stream: no memory for %lld-byte chunks with a %lld-byte carry",
                         (long long)b->fbufsize, (long long)room);
-    }
     b->room = room;
     return FFQ_OK;
 }
@@ -153,7 +125,7 @@ static hipError_t stream_copy_chunk(StreamBufs *b, StreamSlot &sl, int64_t got)
     for (int h = 0; h < 2 && e == hipSuccess; h++) {
         const int64_t a = h ? std::min(half, got) : 0, z = h ? got : std::min(half, got);
         hipStream_t st = b->cs[one ? 0 : h];
-        if (z > a) e = hipMemcpyAsync(sl.d + b->room + a, sl.h + b->room + a, (size_t)(z - a), hipMemcpyHostToDevice, st);
+        if (z > a) e = hipMemcpyAsync(sl.buf.d + b->room + a, sl.buf.h + b->room + a, (size_t)(z - a), hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipEventRecord(sl.copied[h], st);
     }
     return e;
@@ -658,7 +630,7 @@ static void stream_feeder(ffq_stream *s)
                 if (s->seekable && s->src == SRC_FD && !s->pause_req && e - s->released < STREAM_SLOTS && e - p < FFQ_STREAM_AHEAD) {
                     StreamSlot &sq = b->slot[e % STREAM_SLOTS];
                     lk.unlock();
-                    b->pool->enqueue(s->fd, sq.h + b->room, b->fbufsize, pos0 + e * b->fbufsize, &sq.cr);
+                    b->pool->enqueue(s->fd, sq.buf.h + b->room, b->fbufsize, pos0 + e * b->fbufsize, &sq.cr);
                     e++;
                     continue;
                 }
@@ -670,9 +642,9 @@ static void stream_feeder(ffq_stream *s)
         int64_t got;
         bool src_eof = false;
         if (s->seekable && s->src == SRC_FD) { b->pool->wait(&sl.cr); got = sl.cr.total(); src_eof = got < b->fbufsize; }
-        else if (s->src == SRC_GZIP) { got = stream_gz_read(s, sl.h + b->room, b->fbufsize, &src_eof); e = p + 1; }
+        else if (s->src == SRC_GZIP) { got = stream_gz_read(s, sl.buf.h + b->room, b->fbufsize, &src_eof); e = p + 1; }
         else {
-            got = stream_fd_read(s, sl.h + b->room, b->fbufsize, &src_eof);
+            got = stream_fd_read(s, sl.buf.h + b->room, b->fbufsize, &src_eof);
             if (got == -2) { p--; continue; }      // stop / pause asked for with nothing read yet: back to the parking loop
             e = p + 1;
         }
@@ -738,78 +710,45 @@ static void stream_free(ffq_stream *s)
     delete s;
 }
 
+// One of the stream's buffers (a device + pinned pair, or the device-only rows of the push-down) grown to `n` elements, or
+// FFQ_E_NOMEM with the text `what` ("ffq_stream: no memory for %lld ...") about `said`.  What is large enough stays.
+template <class B>
+static int stream_grow(B &buf, int64_t n, const char *what, int64_t said)
+{
+    if (buf.grow(n) == hipSuccess) return FFQ_OK;
+    return fail(FFQ_E_NOMEM, what, (long long)said);
+}
+
+static int64_t stream_tab_rows(const StreamBufs *b) { return b->tab.d.cap / 6; }
+
 static int stream_alloc_tab(ffq_stream *s, int64_t rows)
 {
     StreamBufs *b = s->b;
     NearGpu near(s->c);
-    if (rows > b->tab_cap) {
-        if (b->htab) (void)hipHostFree(b->htab);
-        (void)hipFree(b->dtab);
-        b->htab = nullptr; b->dtab = nullptr; b->tab_cap = 0;
-        if (hipMalloc((void **)&b->dtab, (size_t)rows * 48) != hipSuccess ||
-            hipHostMalloc((void **)&b->htab, (size_t)rows * 48, hipHostMallocDefault) != hipSuccess)
-            return fail(FFQ_E_NOMEM, "ffq_stream: no memory for %lld rows", (long long)rows);
-        b->tab_cap = rows;
-    }
-    if ((s->flags & FFQ_F_DECODE_QUAL) && b->qoff_cap < b->tab_cap + 1) {
-        if (b->hqoff) (void)hipHostFree(b->hqoff);
-        (void)hipFree(b->dqoff);
-        b->hqoff = nullptr; b->dqoff = nullptr; b->qoff_cap = 0;
-        if (hipMalloc((void **)&b->dqoff, (size_t)(b->tab_cap + 1) * 8) != hipSuccess ||
-            hipHostMalloc((void **)&b->hqoff, (size_t)(b->tab_cap + 1) * 8, hipHostMallocDefault) != hipSuccess)
-            return fail(FFQ_E_NOMEM, "ffq_stream: no memory for %lld quality offsets", (long long)b->tab_cap);
-        b->qoff_cap = b->tab_cap + 1;
-    }
-    return FFQ_OK;
+    int rc = stream_grow(b->tab, rows * 6, "ffq_stream: no memory for %lld rows", rows);
+    if (!rc && (s->flags & FFQ_F_DECODE_QUAL))
+        rc = stream_grow(b->qoff, stream_tab_rows(b) + 1, "ffq_stream: no memory for %lld quality offsets", stream_tab_rows(b));
+    return rc;
 }
 
 // device / pinned buffers of the push-down for a fill of up to `rows` rows (and `bytes` of column)
 static int stream_alloc_sel(ffq_stream *s, int64_t rows, int64_t bytes)
 {
     StreamBufs *b = s->b;
-    if (rows > b->sel_cap) {
-        if (b->hidx) (void)hipHostFree(b->hidx);
-        (void)hipFree(b->dsel); (void)hipFree(b->didx);
-        b->hidx = nullptr; b->dsel = nullptr; b->didx = nullptr; b->sel_cap = 0;
-        if (hipMalloc((void **)&b->dsel, (size_t)rows * 48) != hipSuccess || hipMalloc((void **)&b->didx, (size_t)rows * 8) != hipSuccess ||
-            hipHostMalloc((void **)&b->hidx, (size_t)rows * 8, hipHostMallocDefault) != hipSuccess)
-            return fail(FFQ_E_NOMEM, "ffq_stream: no memory for %lld selected rows", (long long)rows);
-        b->sel_cap = rows;
-    }
-    if (s->f_col && rows + 1 > b->coff_cap) {
-        if (b->hcoff) (void)hipHostFree(b->hcoff);
-        (void)hipFree(b->dcoff);
-        b->hcoff = nullptr; b->dcoff = nullptr; b->coff_cap = 0;
-        if (hipMalloc((void **)&b->dcoff, (size_t)(rows + 1) * 8) != hipSuccess ||
-            hipHostMalloc((void **)&b->hcoff, (size_t)(rows + 1) * 8, hipHostMallocDefault) != hipSuccess)
-            return fail(FFQ_E_NOMEM, "ffq_stream: no memory for %lld column offsets", (long long)rows);
-        b->coff_cap = rows + 1;
-    }
-    if (s->f_col && bytes > b->col_cap) {
-        if (b->hcol) (void)hipHostFree(b->hcol);
-        (void)hipFree(b->dcol);
-        b->hcol = nullptr; b->dcol = nullptr; b->col_cap = 0;
-        if (hipMalloc((void **)&b->dcol, (size_t)bytes) != hipSuccess || hipHostMalloc((void **)&b->hcol, (size_t)bytes, hipHostMallocDefault) != hipSuccess)
-            return fail(FFQ_E_NOMEM, "ffq_stream: no memory for %lld column bytes", (long long)bytes);
-        b->col_cap = bytes;
-    }
-    return FFQ_OK;
+    int rc = stream_grow(b->sel, rows * 6, "ffq_stream: no memory for %lld selected rows", rows);
+    if (!rc) rc = stream_grow(b->idx, rows, "ffq_stream: no memory for %lld selected rows", rows);
+    if (!rc && s->f_col) rc = stream_grow(b->coff, rows + 1, "ffq_stream: no memory for %lld column offsets", rows);
+    if (!rc && s->f_col) rc = stream_grow(b->col, bytes, "ffq_stream: no memory for %lld column bytes", bytes);
+    return rc;
 }
 
 // device / pinned buffer for the rendered text of a fill
 static int stream_alloc_render(ffq_stream *s, int64_t bytes)
 {
     StreamBufs *b = s->b;
-    if (bytes <= b->ren_cap) return FFQ_OK;
+    if (bytes <= b->ren.d.cap) return FFQ_OK;
     NearGpu near(s->c);
-    if (b->hren) (void)hipHostFree(b->hren);
-    (void)hipFree(b->dren);
-    b->hren = nullptr; b->dren = nullptr; b->ren_cap = 0;
-    if (hipMalloc((void **)&b->dren, (size_t)bytes) != hipSuccess ||
-        hipHostMalloc((void **)&b->hren, (size_t)bytes, hipHostMallocDefault) != hipSuccess)
-        return fail(FFQ_E_NOMEM, "ffq_stream: no memory for %lld rendered bytes", (long long)bytes);
-    b->ren_cap = bytes;
-    return FFQ_OK;
+    return stream_grow(b->ren, bytes, "ffq_stream: no memory for %lld rendered bytes", bytes);
 }
 
 // The rows the fill hands out (trimmed and filtered, if the stream does that) as FASTQ text, on the device, and its copy
@@ -824,26 +763,12 @@ static int stream_render(ffq_stream *s, const uint8_t *d_buf, int64_t len, int64
     if (n <= 0) return FFQ_OK;
     int rc = stream_alloc_render(s, len + 64);
     if (rc) return rc;
-    rc = ffq_table_render_fastq(s->c, d_buf, len, 0, add, d_rows, n, b->dren, len + 1, nullptr, s->last_render);
+    rc = ffq_table_render_fastq(s->c, d_buf, len, 0, add, d_rows, n, b->ren.d, len + 1, nullptr, s->last_render);
     if (rc == FFQ_E_TABLE_FULL)
         return fail(FFQ_E_INTERNAL, "ffq_stream: a fill of %lld bytes rendered to %lld", (long long)len, (long long)s->last_render[0]);
     if (rc) return rc;
     if (s->last_render[0] > 0)
-        HIPCHK(hipMemcpyAsync(b->hren, b->dren, (size_t)s->last_render[0], hipMemcpyDeviceToHost, s->c->stream));
-    return FFQ_OK;
-}
-
-static int stream_alloc_qual(ffq_stream *s, int64_t bytes)
-{
-    StreamBufs *b = s->b;
-    if (bytes <= b->qual_cap) return FFQ_OK;
-    if (b->hqual) (void)hipHostFree(b->hqual);
-    (void)hipFree(b->dqual);
-    b->hqual = nullptr; b->dqual = nullptr; b->qual_cap = 0;
-    if (hipMalloc((void **)&b->dqual, (size_t)bytes) != hipSuccess ||
-        hipHostMalloc((void **)&b->hqual, (size_t)bytes, hipHostMallocDefault) != hipSuccess)
-        return fail(FFQ_E_NOMEM, "ffq_stream: no memory for %lld decoded bytes", (long long)bytes);
-    b->qual_cap = bytes;
+        HIPCHK(hipMemcpyAsync(b->ren.h, b->ren.d, (size_t)s->last_render[0], hipMemcpyDeviceToHost, s->c->stream));
     return FFQ_OK;
 }
 
@@ -865,27 +790,29 @@ static int stream_grow_room(ffq_stream *s, int64_t need)
     if (e == hipSuccess) e = hipStreamSynchronize(b->cs[1]);
     if (e != hipSuccess) rc = fail(FFQ_E_HIP, "ffq_stream: %s", hipGetErrorString(e));
     const int64_t room = (std::max<int64_t>(2 * b->room, need + 4096) + 4095) & ~(int64_t)4095;
-    StreamSlot old[STREAM_SLOTS];
-    for (int i = 0; i < STREAM_SLOTS; i++) { old[i] = b->slot[i]; b->slot[i].h = nullptr; b->slot[i].d = nullptr; }
-    const int64_t old_room = b->room;
-    if (!rc) rc = streambufs_alloc_slots(s->c, b, room);
-    if (!rc) {
-        // chunks [released, produced) are alive: the one being carried from (cur, all of its fill)
-        // and the ones read ahead (their chunk bytes)
-        for (int64_t k = std::max<int64_t>(s->released, 0); k < s->produced && !rc; k++) {
-            StreamSlot &n = b->slot[k % STREAM_SLOTS];
-            const StreamSlot &o = old[k % STREAM_SLOTS];
-            if (k == s->cur) {
-                memcpy(n.h + room - (old_room - s->fill_start), o.h + s->fill_start, (size_t)s->fill_len);
-                s->fill_start = room - (old_room - s->fill_start);
-            } else {
-                memcpy(n.h + room, o.h + old_room, (size_t)o.got);
-                e = stream_copy_chunk(b, n, o.got);
-                if (e != hipSuccess) rc = fail(FFQ_E_HIP, "ffq_stream: %s", hipGetErrorString(e));
+    {
+        // the slots' memory moves into `old` and is freed where that ends: both copy streams are through with it (above)
+        Mirror<uint8_t> old[STREAM_SLOTS];
+        for (int i = 0; i < STREAM_SLOTS; i++) old[i] = std::move(b->slot[i].buf);
+        const int64_t old_room = b->room;
+        if (!rc) rc = streambufs_alloc_slots(s->c, b, room);
+        if (!rc) {
+            // chunks [released, produced) are alive: the one being carried from (cur, all of its fill)
+            // and the ones read ahead (their chunk bytes)
+            for (int64_t k = std::max<int64_t>(s->released, 0); k < s->produced && !rc; k++) {
+                StreamSlot &n = b->slot[k % STREAM_SLOTS];
+                const uint8_t *oh = old[k % STREAM_SLOTS].h;
+                if (k == s->cur) {
+                    memcpy(n.buf.h + room - (old_room - s->fill_start), oh + s->fill_start, (size_t)s->fill_len);
+                    s->fill_start = room - (old_room - s->fill_start);
+                } else {
+                    memcpy(n.buf.h + room, oh + old_room, (size_t)n.got);
+                    e = stream_copy_chunk(b, n, n.got);
+                    if (e != hipSuccess) rc = fail(FFQ_E_HIP, "ffq_stream: %s", hipGetErrorString(e));
+                }
             }
         }
     }
-    for (auto &o : old) { if (o.h) (void)hipHostFree(o.h); (void)hipFree(o.d); }
     {
         std::lock_guard<std::mutex> lk(s->m);
         s->pause_req = false;
@@ -1028,7 +955,7 @@ extern "C" int ffq_stream_push_buffer(ffq_stream *s, uint8_t **dst, int64_t *cap
     if (!s || !dst || !cap || s->src != SRC_PUSH) return fail(FFQ_E_ARG, "ffq_stream_push_buffer: not a push stream");
     if (s->failed || s->done) return fail(FFQ_E_ARG, "ffq_stream_push_buffer: the stream has %s", s->failed ? "failed" : "ended");
     if (s->produced - s->released >= STREAM_SLOTS) return fail(FFQ_E_ARG, "ffq_stream_push_buffer: every slot holds an unconsumed chunk");
-    *dst = s->b->slot[s->produced % STREAM_SLOTS].h + s->b->room;
+    *dst = s->b->slot[s->produced % STREAM_SLOTS].buf.h + s->b->room;
     *cap = s->b->fbufsize;
     return FFQ_OK;
 }
@@ -1073,7 +1000,7 @@ extern "C" int ffq_stream_quals(ffq_stream *s, const int8_t **h_qual, const int6
 {
     if (!s || !h_qual || !h_qoff || !n_qual_bytes) return fail(FFQ_E_ARG, "ffq_stream_quals: NULL argument");
     if (!(s->flags & FFQ_F_DECODE_QUAL)) return fail(FFQ_E_ARG, "ffq_stream_quals: the stream was opened without FFQ_F_DECODE_QUAL");
-    *h_qual = s->b->hqual; *h_qoff = s->b->hqoff; *n_qual_bytes = s->last_nq;
+    *h_qual = s->b->qual.h; *h_qoff = s->b->qoff.h; *n_qual_bytes = s->last_nq;
     return FFQ_OK;
 }
 
@@ -1141,7 +1068,7 @@ extern "C" int ffq_stream_rendered(ffq_stream *s, const uint8_t **h_fastq, int64
 {
     if (!s || !h_fastq || !n_fastq_bytes) return fail(FFQ_E_ARG, "ffq_stream_rendered: NULL argument");
     if (!s->render_on) return fail(FFQ_E_ARG, "ffq_stream_rendered: the stream does not render (ffq_stream_set_render)");
-    *h_fastq = s->b->hren; *n_fastq_bytes = s->last_render[0];
+    *h_fastq = s->b->ren.h; *n_fastq_bytes = s->last_render[0];
     if (stats) for (int i = 0; i < 3; i++) stats[i] = s->last_render[i];
     return FFQ_OK;
 }
@@ -1154,9 +1081,9 @@ extern "C" int ffq_stream_selected(ffq_stream *s, const int64_t **h_index, int64
 {
     if (!s || !h_index || !n_scanned) return fail(FFQ_E_ARG, "ffq_stream_selected: NULL argument");
     if (!s->filter_on) return fail(FFQ_E_ARG, "ffq_stream_selected: the stream has no filter (ffq_stream_set_filter)");
-    *h_index = s->b->hidx; *n_scanned = s->last_scanned;
-    if (h_col) *h_col = s->f_col ? s->b->hcol : nullptr;
-    if (h_coloff) *h_coloff = s->f_col ? s->b->hcoff : nullptr;
+    *h_index = s->b->idx.h; *n_scanned = s->last_scanned;
+    if (h_col) *h_col = s->f_col ? s->b->col.h : nullptr;
+    if (h_coloff) *h_coloff = s->f_col ? s->b->coff.h : nullptr;
     if (n_col_bytes) *n_col_bytes = s->last_col_bytes;
     return FFQ_OK;
 }
@@ -1169,7 +1096,7 @@ extern "C" int ffq_stream_next(ffq_stream *s, const int64_t **h_rows, int64_t *n
     ffq_ctx *c = s->c;
     StreamBufs *b = s->b;
     HIPCHK(hipSetDevice(c->device));
-    *h_rows = b->htab; *n_rows = 0; *end_state = FFQ_END_OK;
+    *h_rows = b->tab.h; *n_rows = 0; *end_state = FFQ_END_OK;
     if (err_offset) *err_offset = -1;
     if (h_bytes) *h_bytes = nullptr;
     if (n_bytes) *n_bytes = 0;
@@ -1203,10 +1130,10 @@ extern "C" int ffq_stream_next(ffq_stream *s, const int64_t **h_rows, int64_t *n
     }
     StreamSlot &sl = b->slot[k % STREAM_SLOTS];
     const int64_t room = b->room;
-    if (k == 0) sl.h[room - 1] = (uint8_t)'\n';
+    if (k == 0) sl.buf.h[room - 1] = (uint8_t)'\n';
     else {
         const StreamSlot &pv = b->slot[s->cur % STREAM_SLOTS];
-        memcpy(sl.h + room - carry, pv.h + s->fill_start + s->carry_from, (size_t)carry);
+        memcpy(sl.buf.h + room - carry, pv.buf.h + s->fill_start + s->carry_from, (size_t)carry);
         // the previous fill's slot goes back to the feeder (the caller's pointers into it expired
         // with this call)
         { std::lock_guard<std::mutex> lk(s->m); s->released = k; }
@@ -1215,7 +1142,7 @@ extern "C" int ffq_stream_next(ffq_stream *s, const int64_t **h_rows, int64_t *n
     const int64_t start = room - carry, len = carry + sl.got;
     const bool fill_eof = sl.eof;
     mark_other(c);          // (a copy and two event waits go onto the scan stream in front of the scan)
-    HIPCHK(hipMemcpyAsync(sl.d + start, sl.h + start, (size_t)carry, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(sl.buf.d + start, sl.buf.h + start, (size_t)carry, hipMemcpyHostToDevice, c->stream));
     if (s->prof) {          // (profiling only: the wait for the chunk's copy on its own)
         const double t = stream_now();
         HIPCHK(hipEventSynchronize(sl.copied[0]));
@@ -1232,16 +1159,16 @@ extern "C" int ffq_stream_next(ffq_stream *s, const int64_t **h_rows, int64_t *n
         // qualities are at most half of the bytes; the segmented layout of the single pass owns FFQ_SEG_STRIDE bytes per tile
         int64_t need = len / 2 + 64;
         if (s->flags & FFQ_F_SINGLE_PASS) need = std::max<int64_t>(need, ((len + mis + 16383) >> 14) * (int64_t)FFQ_SEG_STRIDE);
-        int rc2 = stream_alloc_qual(s, need);
+        int rc2 = stream_grow(b->qual, need, "ffq_stream: no memory for %lld decoded bytes", need);
         if (rc2) return rc2;
     }
     ffq_scan_result res;
     memset(&res, 0, sizeof res);
     int rc = FFQ_OK;
     for (int attempt = 0; attempt < 2; attempt++) {
-        rc = ffq_scan_device(c, sl.d + start - mis, len + mis, 0, mis, fill_eof ? 1 : 0, s->globaloffset - mis, s->flags,
-                             s->qual_add, b->dtab, b->tab_cap, decode ? b->dqual : nullptr, decode ? b->qual_cap : 0,
-                             decode ? b->dqoff : nullptr, &res);
+        rc = ffq_scan_device(c, sl.buf.d + start - mis, len + mis, 0, mis, fill_eof ? 1 : 0, s->globaloffset - mis, s->flags,
+                             s->qual_add, b->tab.d, stream_tab_rows(b), decode ? b->qual.d.p : nullptr, decode ? b->qual.d.cap : 0,
+                             decode ? b->qoff.d : nullptr, &res);
         if (rc != FFQ_E_TABLE_FULL) break;
         int rc2 = stream_alloc_tab(s, res.n_records + 1024);
         if (rc2) return rc2;
@@ -1252,8 +1179,8 @@ extern "C" int ffq_stream_next(ffq_stream *s, const int64_t **h_rows, int64_t *n
     s->last_scanned = res.n_records; s->last_kept = res.n_records; s->last_col_bytes = 0;
     if (s->trim_on) {
         // ---- the fill's rows are trimmed where they lie, over the buffer and the `add` the scan was given ----
-        int rc2 = ffq_table_trim_quality(c, sl.d + start - mis, len + mis, 0, s->globaloffset - mis, b->dtab, res.n_records,
-                                         s->t_base, s->t_front, s->t_back, b->dtab, s->last_trim);
+        int rc2 = ffq_table_trim_quality(c, sl.buf.d + start - mis, len + mis, 0, s->globaloffset - mis, b->tab.d, res.n_records,
+                                         s->t_base, s->t_front, s->t_back, b->tab.d, s->last_trim);
         if (rc2) return rc2;
     }
     if (s->filter_on) {
@@ -1263,44 +1190,44 @@ extern "C" int ffq_stream_next(ffq_stream *s, const int64_t **h_rows, int64_t *n
         if (res.n_records > 0) {
             int rc2 = stream_alloc_sel(s, res.n_records, len + 64);
             if (rc2) return rc2;
-            rc2 = table_select(c, b->dtab, res.n_records, s->f_min, s->f_max, b->dsel, b->didx, &n_out);
+            rc2 = table_select(c, b->tab.d, res.n_records, s->f_min, s->f_max, b->sel, b->idx.d, &n_out);
             if (rc2) return rc2;
         }
         s->last_kept = n_out;
         if (s->render_on) {
-            int rc2 = stream_render(s, sl.d + start - mis, len + mis, s->globaloffset - mis, b->dsel, n_out);
+            int rc2 = stream_render(s, sl.buf.d + start - mis, len + mis, s->globaloffset - mis, b->sel, n_out);
             if (rc2) return rc2;
         }
         if (n_out > 0) {
-            HIPCHK(hipMemcpyAsync(b->htab, b->dsel, (size_t)n_out * 48, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipMemcpyAsync(b->hidx, b->didx, (size_t)n_out * 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(b->tab.h, b->sel, (size_t)n_out * 48, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(b->idx.h, b->idx.d, (size_t)n_out * 8, hipMemcpyDeviceToHost, c->stream));
         }
         if (s->f_col && res.n_records > 0) {
             static const int COLS[4][3] = {{0, 0, 0}, {0, 1, 1}, {2, 0, 3}, {4, 0, 5}};       // header: buf[pos0 + 1 : pos1] (:161-171)
             int64_t nb = 0;
             // rows are stream offsets: buffer coordinate = row - add, with add = globaloffset - mis as the scan was given
-            int rc2 = ffq_table_gather_column(c, sl.d + start - mis, len + mis, 0, s->globaloffset - mis, b->dsel, n_out, COLS[s->f_col][0],
-                                              COLS[s->f_col][1], COLS[s->f_col][2], s->f_add, b->dcol, b->col_cap, b->dcoff, &nb);
+            int rc2 = ffq_table_gather_column(c, sl.buf.d + start - mis, len + mis, 0, s->globaloffset - mis, b->sel, n_out, COLS[s->f_col][0],
+                                              COLS[s->f_col][1], COLS[s->f_col][2], s->f_add, b->col.d, b->col.d.cap, b->coff.d, &nb);
             if (rc2) return rc2;
             s->last_col_bytes = nb;
-            if (nb > 0) HIPCHK(hipMemcpyAsync(b->hcol, b->dcol, (size_t)nb, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipMemcpyAsync(b->hcoff, b->dcoff, (size_t)(n_out + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+            if (nb > 0) HIPCHK(hipMemcpyAsync(b->col.h, b->col.d, (size_t)nb, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(b->coff.h, b->coff.d, (size_t)(n_out + 1) * 8, hipMemcpyDeviceToHost, c->stream));
         }
     } else {
         if (s->render_on) {
-            int rc2 = stream_render(s, sl.d + start - mis, len + mis, s->globaloffset - mis, b->dtab, res.n_records);
+            int rc2 = stream_render(s, sl.buf.d + start - mis, len + mis, s->globaloffset - mis, b->tab.d, res.n_records);
             if (rc2) return rc2;
         }
         if (res.n_records > 0)
-            HIPCHK(hipMemcpyAsync(b->htab, b->dtab, (size_t)res.n_records * 48, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(b->tab.h, b->tab.d, (size_t)res.n_records * 48, hipMemcpyDeviceToHost, c->stream));
     }
     s->last_nq = 0;
     s->last_path = res.path;
     if (decode) {
         s->last_nq = res.n_qual_bytes;
         if (res.n_qual_bytes > 0)
-            HIPCHK(hipMemcpyAsync(b->hqual, b->dqual, (size_t)res.n_qual_bytes, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(b->hqoff, b->dqoff, (size_t)(res.n_records + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(b->qual.h, b->qual.d, (size_t)res.n_qual_bytes, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(b->qoff.h, b->qoff.d, (size_t)(res.n_records + 1) * 8, hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(hipStreamSynchronize(c->stream));
     if (s->prof) { const double t = stream_now(); s->t_feed += tp1 - tp0; s->t_scan += tp2 - tp1; s->t_rows += t - tp2; }
@@ -1308,9 +1235,9 @@ extern "C" int ffq_stream_next(ffq_stream *s, const int64_t **h_rows, int64_t *n
     s->cur = k;
     s->handed_pos = sl.end_pos;
     s->fill_start = start; s->fill_len = len;
-    *h_rows = b->htab;
+    *h_rows = b->tab.h;
     *n_rows = n_out;
-    if (h_bytes) *h_bytes = sl.h + start;
+    if (h_bytes) *h_bytes = sl.buf.h + start;
     if (n_bytes) *n_bytes = len;
     // byte i of this fill is stream offset globaloffset + i (the sentinel of the first fill is -1)
     if (bytes_offset) *bytes_offset = s->globaloffset;
