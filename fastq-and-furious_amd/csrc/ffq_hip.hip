@@ -9,6 +9,7 @@
 #include "ffq_kernels.h"
 #include "ffq_fasta.h"
 #include "ffq_trim.h"
+#include "ffq_adapter.h"
 #include "ffq_render.h"
 #include "ffq_pool.h"
 #include "ffq_mem.h"
@@ -1977,6 +1978,59 @@ extern "C" int ffq_table_trim_quality(ffq_ctx *c, const uint8_t *d_buf, int64_t 
     const int64_t nblk_long = std::min<int64_t>((n_rows + 3) / 4, 1024);
     hipLaunchKernelGGL(k_trim_long, dim3((unsigned)nblk_long), dim3(TRIM_WG), 0, st, d_buf, n_bytes, sentinel ? 1 : 0, add,
                        d_table, qual_base, cutoff_front, cutoff_back, d_out, (const int64_t *)c->trim_list, c->d_trim);
+    HIPCHK(hipMemcpyAsync(c->h_trim, c->d_trim, sizeof(TrimBlock), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    stats[0] = (int64_t)c->h_trim->changed; stats[1] = (int64_t)c->h_trim->removed; stats[2] = (int64_t)c->h_trim->skipped;
+    return FFQ_OK;
+}
+
+// ---- 3' adapter trimming: rows of the table edited in place (csrc/ffq_adapter.h) --------------
+// parameters of an adapter call, checked; the adapter's bytes and its wildcard mask as the kernels take them
+static int adapter_arg(const char *who, const uint8_t *adapter, int adapter_len, int err_permille, int min_overlap, AdapterArg *ad)
+{
+    if (!adapter || adapter_len < 1 || adapter_len > ADAPTER_MAX) return fail(FFQ_E_ARG, "%s: the adapter has 1..%d bytes", who, ADAPTER_MAX);
+    if (min_overlap < 1 || min_overlap > adapter_len) return fail(FFQ_E_ARG, "%s: min_overlap is 1..adapter_len", who);
+    if (err_permille < 0 || err_permille > 1000) return fail(FFQ_E_ARG, "%s: err_permille is 0..1000", who);
+    if (ad) {
+        memset(ad, 0, sizeof *ad);
+        for (int j = 0; j < adapter_len; j++) {
+            ad->a[j >> 2] |= (uint32_t)adapter[j] << (8 * (j & 3));
+            if (adapter[j] != (uint8_t)'N') ad->k[j >> 2] |= 0xFFu << (8 * (j & 3));
+        }
+    }
+    return FFQ_OK;
+}
+
+extern "C" int ffq_table_trim_adapter(ffq_ctx *c, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
+                                      const int64_t *d_table, int64_t n_rows, const uint8_t *adapter, int adapter_len,
+                                      int err_permille, int min_overlap, int64_t *d_out, int64_t stats[3])
+{
+    mark_other(c);
+    if (!c || !stats || n_rows < 0 || n_bytes < 0 || (n_bytes > 0 && !d_buf) || (n_rows > 0 && (!d_table || !d_out)))
+        return fail(FFQ_E_ARG, "ffq_table_trim_adapter: bad argument");
+    AdapterArg ad;
+    int rc = adapter_arg("ffq_table_trim_adapter", adapter, adapter_len, err_permille, min_overlap, &ad);
+    if (rc) return rc;
+    if (((reinterpret_cast<uintptr_t>(d_table) | reinterpret_cast<uintptr_t>(d_out)) & 15) != 0)
+        return fail(FFQ_E_ARG, "ffq_table_trim_adapter: tables must be 16-byte aligned");
+    if (c->pend.active) return fail(FFQ_E_ARG, "ffq_table_trim_adapter: a scan is pending on this context");
+    HIPCHK(hipSetDevice(c->device));
+    stats[0] = stats[1] = stats[2] = 0;
+    if (n_rows == 0) return FFQ_OK;
+    rc = grow_dev(c, c->trim_list, n_rows);
+    if (rc) return rc;
+    hipStream_t st = c->stream;
+    // (the counters and the long list are the quality trim's: calls on a context follow one another)
+    HIPCHK(hipMemsetAsync(c->d_trim, 0, sizeof(TrimBlock), st));
+    constexpr int64_t rpb = TRIM_WG / TRIM_G;
+    const int64_t nblk = std::min<int64_t>((n_rows + rpb - 1) / rpb, 2048);
+    hipLaunchKernelGGL(k_adapter_rows, dim3((unsigned)nblk), dim3(TRIM_WG), 0, st, d_buf, n_bytes, sentinel ? 1 : 0, add, d_table,
+                       n_rows, ad, adapter_len, err_permille, min_overlap, d_out, c->trim_list, c->d_trim);
+    // the rows it left (above ADAPTER_LONG bases; their number is known on the device only): a wave each
+    const int64_t nblk_long = std::min<int64_t>((n_rows + 3) / 4, 1024);
+    hipLaunchKernelGGL(k_adapter_long, dim3((unsigned)nblk_long), dim3(TRIM_WG), 0, st, d_buf, n_bytes, sentinel ? 1 : 0, add,
+                       d_table, ad, adapter_len, err_permille, min_overlap, d_out, (const int64_t *)c->trim_list, c->d_trim);
     HIPCHK(hipMemcpyAsync(c->h_trim, c->d_trim, sizeof(TrimBlock), hipMemcpyDeviceToHost, st));
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));

@@ -320,6 +320,11 @@ struct ffq_stream {
     bool trim_on = false;
     int t_base = 33, t_front = 0, t_back = 0;
     int64_t last_trim[3] = {0, 0, 0};
+    // 3' adapter trimming of every fill's table, behind the quality trim and in front of the filter (ffq_stream_set_adapter)
+    bool adapter_on = false;
+    uint8_t ad_bytes[64] = {0};
+    int ad_len = 0, ad_err = 0, ad_overlap = 0;
+    int64_t last_adapter[3] = {0, 0, 0};
     // FASTQ text of every fill's table, behind the trim and the filter (ffq_stream_set_render)
     bool render_on = false;
     int64_t last_render[3] = {0, 0, 0};
@@ -1047,6 +1052,33 @@ extern "C" int ffq_stream_trimmed(ffq_stream *s, int64_t stats[3])
     return FFQ_OK;
 }
 
+// 3' adapter trimming in the stream: every fill's table is adapter-trimmed in place on the device (ffq_table_trim_adapter)
+// right behind the quality trim (cutadapt's own order: -q first, -a on the row as that trim left it) -- in front of the
+// filter, the column gather, the render and the rows' copy back.  The other rules are ffq_stream_set_trim's.
+extern "C" int ffq_stream_set_adapter(ffq_stream *s, const uint8_t *adapter, int adapter_len, int err_permille, int min_overlap)
+{
+    if (!s) return fail(FFQ_E_ARG, "ffq_stream_set_adapter: NULL stream");
+    int rc = adapter_arg("ffq_stream_set_adapter", adapter, adapter_len, err_permille, min_overlap, nullptr);
+    if (rc) return rc;
+    if (s->flags & FFQ_F_DECODE_QUAL) return fail(FFQ_E_ARG, "ffq_stream_set_adapter: the stream decodes every record's qualities (FFQ_F_DECODE_QUAL) "
+                                                              "beside the scan, untrimmed; a filtered stream gathers the trimmed ones "
+                                                              "(ffq_stream_set_filter: column = FFQ_COL_QUALITY, value_add)");
+    if (s->cur >= 0) return fail(FFQ_E_ARG, "ffq_stream_set_adapter: the stream has handed out a fill already");
+    s->adapter_on = true;
+    memcpy(s->ad_bytes, adapter, (size_t)adapter_len);
+    s->ad_len = adapter_len; s->ad_err = err_permille; s->ad_overlap = min_overlap;
+    return FFQ_OK;
+}
+
+// {rows changed, bases removed, rows skipped} by the adapter step of the fill ffq_stream_next has just returned
+extern "C" int ffq_stream_adapter_trimmed(ffq_stream *s, int64_t stats[3])
+{
+    if (!s || !stats) return fail(FFQ_E_ARG, "ffq_stream_adapter_trimmed: NULL argument");
+    if (!s->adapter_on) return fail(FFQ_E_ARG, "ffq_stream_adapter_trimmed: the stream trims no adapter (ffq_stream_set_adapter)");
+    for (int i = 0; i < 3; i++) stats[i] = s->last_adapter[i];
+    return FFQ_OK;
+}
+
 // Rendering in the stream: from the first fill on, the rows ffq_stream_next hands out -- trimmed (ffq_stream_set_trim) and
 // filtered (ffq_stream_set_filter, without a column) first, if the stream does that -- are rendered as FASTQ text on the
 // device (ffq_table_render_fastq) and the text is copied back to pinned memory beside the rows.
@@ -1181,6 +1213,12 @@ extern "C" int ffq_stream_next(ffq_stream *s, const int64_t **h_rows, int64_t *n
         // ---- the fill's rows are trimmed where they lie, over the buffer and the `add` the scan was given ----
         int rc2 = ffq_table_trim_quality(c, sl.buf.d + start - mis, len + mis, 0, s->globaloffset - mis, b->tab.d, res.n_records,
                                          s->t_base, s->t_front, s->t_back, b->tab.d, s->last_trim);
+        if (rc2) return rc2;
+    }
+    if (s->adapter_on) {
+        // ---- ... and cut at the 3' adapter, as the quality trim left them ----
+        int rc2 = ffq_table_trim_adapter(c, sl.buf.d + start - mis, len + mis, 0, s->globaloffset - mis, b->tab.d, res.n_records,
+                                         s->ad_bytes, s->ad_len, s->ad_err, s->ad_overlap, b->tab.d, s->last_adapter);
         if (rc2) return rc2;
     }
     if (s->filter_on) {

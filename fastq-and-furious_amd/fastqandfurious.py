@@ -309,6 +309,87 @@ class entryfunc_qualitytrim:
         return (buf[(pos[0] + 1):pos[1]], buf[pos[2]:pos[3]], buf[pos[4]:pos[5]])
 
 
+def _adapter_args(adapter, err_permille, min_overlap):
+    """(adapter as bytes, err_permille, min_overlap) or ValueError: the ranges ffq_table_trim_adapter takes."""
+    adapter = bytes(adapter)
+    if not 1 <= len(adapter) <= 64:
+        raise ValueError("the adapter has 1..64 bytes")
+    if not 1 <= int(min_overlap) <= len(adapter):
+        raise ValueError("min_overlap is 1..len(adapter)")
+    if not 0 <= int(err_permille) <= 1000:
+        raise ValueError("err_permille is 0..1000")
+    return adapter, int(err_permille), int(min_overlap)
+
+
+def adapter_cut(sequence, adapter, err_permille=100, min_overlap=3):
+    """Length that is left of `sequence` (bytes of one record's sequence line) when it is cut at the 3' adapter: the LEFTMOST
+    position p <= len(sequence) - min_overlap at which the first ov = min(len(adapter), len(sequence) - p) bytes of the
+    adapter differ from sequence[p:p + ov] in at most ov * err_permille // 1000 places -- a full copy inside the read or a
+    prefix of the adapter at its end; b'N' in the adapter matches anything, bytes are compared as they are, no indels
+    (include/ffq.h, ffq_table_trim_adapter, states it as a loop; cutadapt -a AD --no-indels -e E -O O takes the best-scoring
+    position where this takes the leftmost).  len(sequence) if there is none."""
+    adapter, err, mo = _adapter_args(adapter, err_permille, min_overlap)
+    n, m = len(sequence), len(adapter)
+    if n < mo:
+        return n
+    ncand = n - mo + 1
+    pos = np.arange(ncand, dtype=np.int64)
+    seq = np.concatenate((np.frombuffer(sequence, dtype=np.uint8), np.zeros(m, dtype=np.uint8)))
+    mm = np.zeros(ncand, dtype=np.int64)
+    for j, a in enumerate(adapter):
+        if a != 0x4E:
+            mm += (seq[j:j + ncand] != a) & (pos + j < n)
+    hit = np.flatnonzero(mm <= np.minimum(m, n - pos) * err // 1000)
+    return int(hit[0]) if hit.size else n
+
+
+def adapter_trimmable(buf, pos):
+    """Does the device cut this row at an adapter (ffq_table_trim_adapter's eligibility)?  trimmable()'s rule with the newline
+    looked for in the SEQUENCE."""
+    p2, p3, p4, p5 = pos[2], pos[3], pos[4], pos[5]
+    return (p2 >= 0 and p4 >= 0 and p2 <= p3 <= len(buf) and p4 <= p5 <= len(buf) and p3 - p2 == p5 - p4
+            and b'\n' not in buf[p2:p3])
+
+
+class entryfunc_adaptertrim:
+    """3' adapter trimming as an entryfunc OBJECT, beside entryfunc_qualitytrim: what `cutadapt [-q CUTOFF] -a ADAPTER
+    --no-indels -e E -O O` does to a record.  The quality rule first if quality_cutoff is given (an int -- the 3' end -- or a
+    (front, back) pair), then the read as that left it is cut at the adapter (adapter_cut); a read whose trimmed length is
+    outside [min_len, max_len] gives None, any other the component `column` says, cut at the trimmed positions.  A record a
+    rule does not apply to (trimmable / adapter_trimmable: wrapped lines, sequence and quality of different lengths) is left
+    as that rule found it.
+
+    Called per record (any scanner) it works on a copy of `pos`.  readfastq_iter RECOGNISES the unmodified class when the
+    scanner is the GPU one: the stream front end trims every fill's table on the device (ffq_stream_set_trim,
+    ffq_stream_set_adapter), filters it and gathers the one component of the kept rows.  Same items, same order, one per
+    record.  Not done: 5' and anchored adapters, indels, several adapters, paired-end files, readfastq_iter_range."""
+
+    yield_dropped = True
+
+    def __init__(self, adapter, err_permille=100, min_overlap=3, quality_cutoff=None, qual_base=33, min_len=None, max_len=None,
+                 column="entry"):
+        if column not in ("sequence", "header", "quality", "entry"):
+            raise ValueError("column must be 'sequence', 'header', 'quality' or 'entry'")
+        self.adapter, self.err_permille, self.min_overlap = _adapter_args(adapter, err_permille, min_overlap)
+        self.quality = None
+        if quality_cutoff is not None:
+            front, back = (0, quality_cutoff) if isinstance(quality_cutoff, (int, np.integer)) else quality_cutoff
+            self.quality = entryfunc_qualitytrim(back, front, qual_base)        # (checks the ranges)
+        self.min_len = None if min_len is None else int(min_len)
+        self.max_len = None if max_len is None else int(max_len)
+        self.column = column
+
+    def trimmed_pos(self, buf, pos):
+        """A copy of the six positions with the rules applied."""
+        pos = self.quality.trimmed_pos(buf, pos) if self.quality is not None else list(pos)
+        if adapter_trimmable(buf, pos):
+            cut = adapter_cut(buf[pos[2]:pos[3]], self.adapter, self.err_permille, self.min_overlap)
+            pos[3], pos[5] = pos[2] + cut, pos[4] + cut
+        return pos
+
+    __call__ = entryfunc_qualitytrim.__call__
+
+
 def entryfunc_abspos(buf: bytes, pos, globaloffset: int):
     """Absolute stream positions: pos[i] += globaloffset, in place; returns
     the same `pos` object (reference :186-195)."""
@@ -342,6 +423,15 @@ def _pushes_down_trim(entryfunc):
     t = type(entryfunc)
     return t is entryfunc_qualitytrim or (t.__call__ is entryfunc_qualitytrim.__call__ and
                                           t.trimmed_pos is entryfunc_qualitytrim.trimmed_pos)
+
+
+def _pushes_down_adapter(entryfunc):
+    """... and its own adapter trimmer, unchanged."""
+    if not isinstance(entryfunc, entryfunc_adaptertrim):
+        return False
+    t = type(entryfunc)
+    return t is entryfunc_adaptertrim or (t.__call__ is entryfunc_adaptertrim.__call__ and
+                                          t.trimmed_pos is entryfunc_adaptertrim.trimmed_pos)
 
 
 def _table_entries(entryfunc, buf, rows, shift, quals=None):
@@ -521,12 +611,17 @@ def readfastq_iter(fh: typing.BinaryIO, fbufsize: int,
         # the native stream front end: a real file, a gzip file, or anything with readinto() / read();
         # with entryfunc_phred the qualities of every fill are decoded on the device
         st = open_stream(fh, fbufsize, entryfunc is entryfunc_phred) if entryfunc is entryfunc_phred else open_stream(fh, fbufsize)
-        if st is not None and (_pushes_down(entryfunc) or _pushes_down_trim(entryfunc)):
+        if st is not None and (_pushes_down(entryfunc) or _pushes_down_trim(entryfunc) or _pushes_down_adapter(entryfunc)):
             # push-down: the filter runs on the device, on every fill's table, before anything is copied back -- behind the
-            # quality trimming of the rows, if that is what the entryfunc does
+            # quality and adapter trimming of the rows, if that is what the entryfunc does
             try:
                 if isinstance(entryfunc, entryfunc_qualitytrim):
                     st.set_trim(entryfunc.cutoff_back, entryfunc.cutoff_front, entryfunc.qual_base)
+                if isinstance(entryfunc, entryfunc_adaptertrim):
+                    if entryfunc.quality is not None:
+                        q = entryfunc.quality
+                        st.set_trim(q.cutoff_back, q.cutoff_front, q.qual_base)
+                    st.set_adapter(entryfunc.adapter, entryfunc.err_permille, entryfunc.min_overlap)
                 st.set_filter(entryfunc.min_len, entryfunc.max_len, None if entryfunc.column == "entry" else entryfunc.column)
             except BaseException:
                 st.close()                 # (the native stream, its pinned buffers and its feeder thread; a gzip stream's hook)
@@ -585,21 +680,24 @@ FilterResult = namedtuple('FilterResult', 'records_in records_out bases_removed 
 
 
 def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1 << 24, quality_cutoff=None,
-                 qual_base: int = 33, min_len=None, max_len=None, entrypos: typing.Optional[typing.Callable] = None) -> FilterResult:
+                 qual_base: int = 33, min_len=None, max_len=None, entrypos: typing.Optional[typing.Callable] = None,
+                 adapter=None, err_permille: int = 100, min_overlap: int = 3) -> FilterResult:
     """Trim, filter and WRITE a FASTQ stream: the file `cutadapt -q 20 -m 30` leaves behind, which is what the tables of
     positions of the reference's user guide are kept for in the end ("to avoid saving a FASTQ file after each filtering or
     read-trimming step", doc/user-guide.rst:196-204).  Every record of `fh` is quality-trimmed (quality_cutoff: an int --
     the 3' end -- or a (front, back) pair, as entryfunc_qualitytrim orders them after its first argument; None: no
-    trimming), dropped if its trimmed length lies outside [min_len, max_len], and written to `fh_out` as
+    trimming), then cut at the 3' adapter (adapter: bytes, with err_permille and min_overlap as adapter_cut takes them --
+    `cutadapt -q 20 -a AGATCGGAAGAGC --no-indels -m 30`; None: no adapter), dropped if its trimmed length lies outside
+    [min_len, max_len], and written to `fh_out` as
 
         b"@" + header + b"\\n" + sequence + b"\\n+\\n" + quality + b"\\n"
 
-    -- the slices of entryfunc, a bare '+' line; a wrapped record stays wrapped (and untrimmed: the rule does not apply to
-    it).  Returns FilterResult(records_in, records_out, bases_removed -- over every record, the dropped ones included --,
-    bytes_out).
+    -- the slices of entryfunc, a bare '+' line; a wrapped record stays wrapped (and untrimmed: the rules do not apply to
+    it).  Returns FilterResult(records_in, records_out, bases_removed -- by both trims, over every record, the dropped ones
+    included --, bytes_out).
 
     entrypos None (the GPU scanner): the stream front end scans, trims, filters and renders every buffer fill on the device
-    (ffq_stream_set_trim / _set_filter / _set_render) and this loop does one fh_out.write(memoryview) per fill -- a plain
+    (ffq_stream_set_trim / _set_adapter / _set_filter / _set_render) and this loop does one fh_out.write(memoryview) per fill -- a plain
     file is read by the library itself, any other readable object chunk by chunk into pinned memory.  Any other scanner:
     a loop over readfastq_iter that writes the same bytes record by record.  Malformed input raises what readfastq_iter
     raises, behind the records in front of it; `fh` is left where that iterator leaves it.
@@ -612,6 +710,9 @@ def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1
     if quality_cutoff is not None:
         front, back = (0, quality_cutoff) if isinstance(quality_cutoff, (int, np.integer)) else quality_cutoff
         trim = entryfunc_qualitytrim(back, front, qual_base)            # (checks the ranges)
+    cutter = None
+    if adapter is not None:
+        cutter = entryfunc_adaptertrim(adapter, err_permille, min_overlap, quality_cutoff, qual_base)
     lo = None if min_len is None else int(min_len)
     hi = None if max_len is None else int(max_len)
     if entrypos is None:
@@ -624,6 +725,8 @@ def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1
         try:
             if trim is not None:
                 st.set_trim(trim.cutoff_back, trim.cutoff_front, trim.qual_base)
+            if cutter is not None:
+                st.set_adapter(cutter.adapter, cutter.err_permille, cutter.min_overlap)
             if lo is not None or hi is not None:
                 st.set_filter(lo, hi)
             st.set_render()
@@ -636,6 +739,8 @@ def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1
                 n_bytes += nb
                 if trim is not None:
                     removed += st.trimmed()[1]
+                if cutter is not None:
+                    removed += st.adapter_trimmed()[1]
                 if end_state != _END_OK and end_state != _END_REFILL:
                     _raise_for_end(end_state, err_offset)
         finally:
@@ -644,7 +749,9 @@ def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1
 
     def record(buf, pos, globaloffset=None):
         length = pos[3] - pos[2]
-        if trim is not None:
+        if cutter is not None:
+            pos = cutter.trimmed_pos(buf, pos)          # (the quality rule first, if there is one)
+        elif trim is not None:
             pos = trim.trimmed_pos(buf, pos)
         cut = length - (pos[3] - pos[2])
         length -= cut

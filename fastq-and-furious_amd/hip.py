@@ -86,6 +86,7 @@ SYMBOLS = (
     "ffq_shard_create2", "ffq_shard_scan_fd_slabs", "ffq_table_select_seqlen_idx", "ffq_shard_get_info", "ffq_shard_set_timeout", "ffq_shard_set_serial", "ffq_shard_abort", "ffq_shard_inject_stall",
     "ffq_table_trim_quality", "ffq_stream_set_trim", "ffq_stream_trimmed",
     "ffq_table_render_fastq", "ffq_stream_set_render", "ffq_stream_rendered",
+    "ffq_table_trim_adapter", "ffq_stream_set_adapter", "ffq_stream_adapter_trimmed",
 )
 
 
@@ -317,6 +318,7 @@ def lib():
         L.ffq_table_select_seqlen_idx.argtypes = [vp, vp, i64, i64, i64, vp, vp, P(i64)]
         L.ffq_table_cut.argtypes = [vp, vp, i64, i64, i64, P(i64)]
         L.ffq_table_trim_quality.argtypes = [vp, vp, i64, i32, i64, vp, i64, i32, i32, i32, vp, P(i64)]
+        L.ffq_table_trim_adapter.argtypes = [vp, vp, i64, i32, i64, vp, i64, ctypes.c_char_p, i32, i32, i32, vp, P(i64)]
         L.ffq_table_render_fastq.argtypes = [vp, vp, i64, i32, i64, vp, i64, vp, i64, vp, P(i64)]
         L.ffq_table_gather_column.argtypes = [vp, vp, i64, i32, i64, vp, i64, i32, i32, i32, i32, vp, i64, vp, P(i64)]
         L.ffq_stream_open.argtypes = [vp, i32, i64, P(vp)]
@@ -372,6 +374,8 @@ def lib():
         L.ffq_stream_set_filter.argtypes = [vp, i64, i64, i32, i32]
         L.ffq_stream_set_trim.argtypes = [vp, i32, i32, i32]
         L.ffq_stream_trimmed.argtypes = [vp, P(i64)]
+        L.ffq_stream_set_adapter.argtypes = [vp, ctypes.c_char_p, i32, i32, i32]
+        L.ffq_stream_adapter_trimmed.argtypes = [vp, P(i64)]
         L.ffq_stream_set_render.argtypes = [vp]
         L.ffq_stream_rendered.argtypes = [vp, P(vp), P(i64), P(i64)]
         L.ffq_stream_selected.argtypes = [vp, P(vp), P(i64), P(vp), P(vp), P(i64)]
@@ -664,6 +668,21 @@ class Context:
                                            int(cutoff_back), ctypes.c_void_p(d_table if d_out is None else d_out), stats))
         return int(stats[0]), int(stats[1]), int(stats[2])
 
+    def table_trim_adapter(self, d_buf, n_bytes, d_table, n_rows, adapter, err_permille=100, min_overlap=3, d_out=None,
+                           sentinel=True, add=None):
+        """Cut the rows of a device table at a 3' adapter (ffq_table_trim_adapter: the leftmost position at which `adapter`
+        -- bytes, 1..64 of them, 'N' a wildcard -- or a prefix of it that runs into the read's end matches with at most
+        overlap * err_permille // 1000 mismatches; no indels): pos3 and pos5 of every eligible row move inwards, every other
+        row is copied unchanged.  d_out: n_rows rows of room (None: in place); raw device pointers; d_buf / n_bytes /
+        sentinel / add as for table_gather_column.  Returns (rows changed, bases removed, rows skipped)."""
+        add = _add(add, sentinel)
+        adapter = bytes(adapter)
+        stats = (ctypes.c_int64 * 3)()
+        check(lib().ffq_table_trim_adapter(self.handle, ctypes.c_void_p(d_buf), int(n_bytes), int(bool(sentinel)), int(add),
+                                           ctypes.c_void_p(d_table), int(n_rows), adapter, len(adapter), int(err_permille),
+                                           int(min_overlap), ctypes.c_void_p(d_table if d_out is None else d_out), stats))
+        return int(stats[0]), int(stats[1]), int(stats[2])
+
     def table_render_fastq(self, d_buf, n_bytes, d_table, n_rows, d_out, out_cap, d_off=None, sentinel=True, add=None):
         """FASTQ text of the rows of a device table (ffq_table_render_fastq): row p renders as "@" + buf[p0 + 1:p1] + "\\n"
         + buf[p2:p3] + "\\n+\\n" + buf[p4:p5] + "\\n", a row that is not renderable as nothing.  d_out: out_cap bytes, any
@@ -948,6 +967,19 @@ class _Stream:
         """(rows changed, bases removed, rows skipped) of the fill the iteration has just yielded (set_trim)."""
         stats = (ctypes.c_int64 * 3)()
         check(lib().ffq_stream_trimmed(self._h, stats))
+        return int(stats[0]), int(stats[1]), int(stats[2])
+
+    def set_adapter(self, adapter, err_permille=100, min_overlap=3):
+        """3' adapter trimming in the stream (ffq_stream_set_adapter; before the first fill): every fill's rows are cut at
+        the adapter on the device right behind the quality trim (set_trim), in front of the filter, the column gather and
+        the render."""
+        adapter = bytes(adapter)
+        check(lib().ffq_stream_set_adapter(self._h, adapter, len(adapter), int(err_permille), int(min_overlap)))
+
+    def adapter_trimmed(self):
+        """(rows changed, bases removed, rows skipped) by the adapter step of the fill the iteration has just yielded."""
+        stats = (ctypes.c_int64 * 3)()
+        check(lib().ffq_stream_adapter_trimmed(self._h, stats))
         return int(stats[0]), int(stats[1]), int(stats[2])
 
     def set_render(self):

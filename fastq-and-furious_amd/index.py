@@ -185,6 +185,34 @@ def trim_rows_device(ctx, buf, table, cutoff_back, cutoff_front=0, qual_base=33,
     return out, stats
 
 
+def trim_adapter_rows(buf, table, adapter, err_permille=100, min_overlap=3, shift=0):
+    """Copy of a table cut at a 3' adapter, on the host: pos3 and pos5 of every row the rule applies to
+    (_F.adapter_trimmable: positions minus `shift` index `buf`) moved to the leftmost place the adapter matches
+    (_F.adapter_cut); the same rows, none dropped.  Run it behind trim_rows (cutadapt's order: -q first)."""
+    t = np.array(table, dtype=np.int64).reshape(-1, 6)
+    buf = bytes(buf) if not isinstance(buf, bytes) else buf
+    _F._adapter_args(adapter, err_permille, min_overlap)
+    for row in t:
+        rel = (row - shift).tolist()
+        if _F.adapter_trimmable(buf, rel):
+            cut = _F.adapter_cut(buf[rel[2]:rel[3]], adapter, err_permille, min_overlap)
+            row[3], row[5] = row[2] + cut, row[4] + cut
+    return t
+
+
+def trim_adapter_rows_device(ctx, buf, table, adapter, err_permille=100, min_overlap=3, sentinel=True, add=None, out=None):
+    """trim_adapter_rows on the GPU: `buf` is the CUDA uint8 tensor the rows of `table` (CUDA int64[n][6]) were scanned from,
+    sentinel / add as that scan had them.  Returns (tensor with the trimmed rows -- a new one, or `out`, which may be
+    `table` itself: in place --, (rows changed, bases removed, rows skipped)).  One C-ABI call (ffq_table_trim_adapter)."""
+    import torch
+    n = int(table.shape[0])
+    if out is None:
+        out = torch.empty_like(table)
+    stats = ctx.table_trim_adapter(buf.data_ptr(), buf.numel(), table.data_ptr(), n, adapter, err_permille, min_overlap,
+                                   d_out=out.data_ptr(), sentinel=sentinel, add=add)
+    return out, stats
+
+
 def select_column_device(ctx, buf, table, which, sentinel=True, add=None, value_add=0):
     """One component of every row, packed, on the GPU: `buf` is the CUDA uint8 tensor the rows of
     `table` (CUDA int64[n][6]) were scanned from; which = "header" | "sequence" | "quality".

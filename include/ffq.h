@@ -314,6 +314,32 @@ int ffq_table_trim_quality(ffq_ctx *ctx, const uint8_t *d_buf, int64_t n_bytes, 
                            const int64_t *d_table, int64_t n_rows, int qual_base, int cutoff_front, int cutoff_back,
                            int64_t *d_out, int64_t stats[3]);
 
+/* 3' adapter trimming by MODIFYING rows: what `cutadapt -a ADAPTER --no-indels -e E -O O` does, with E = err_permille /
+ * 1000 and O = min_overlap.  For one row, seq[0..n) = buf[pos2:pos3], ad[0..m) the adapter (1 <= m <= 64), min_overlap in
+ * 1..m, err_permille in 0..1000:
+ *     cut = n
+ *     for p = 0 .. n - min_overlap:                 (leftmost first; no candidate if n < min_overlap)
+ *         ov = min(m, n - p)                        (a full copy inside the read, or a prefix of the adapter at its 3' end)
+ *         mm = #{ j < ov : ad[j] != 'N' and seq[p + j] != ad[j] }
+ *         if mm <= (ov * err_permille) / 1000:      (integer division)
+ *             cut = p; break
+ * and the row becomes pos0, pos1, pos2, pos2 + cut, pos4, pos4 + cut.  Bytes are compared as they are (a lower-case read
+ * does not match an upper-case adapter); 'N' (0x4E) in the adapter matches any byte, 'N' in the read only an 'N' of the
+ * adapter; mismatches only, no insertions or deletions.  ONE DIFFERENCE from cutadapt: of several qualifying positions the
+ * LEFTMOST is taken, not the best-scoring one.  A row is trimmed only if pos2..pos5 - add are all >= 0, pos2 <= pos3 and
+ * pos4 <= pos5 lie inside the buffer (with sentinel, coordinate 0 is the virtual "\n": never read), pos3 - pos2 == pos5 -
+ * pos4 and no byte of the whole sequence buf[pos2:pos3] is "\n" (a wrapped record is left alone even when a hit lies in
+ * front of its newline); every other row is copied unchanged and counted as skipped; a row of length 0 is eligible,
+ * unchanged and not skipped.  No byte outside [d_buf, d_buf + n_bytes) and outside the row's own checked sequence range is
+ * read.  adapter: HOST memory.  d_buf / n_bytes / sentinel / add: as for ffq_table_gather_column.  d_out: n_rows rows; it
+ * MAY be d_table.  Both tables 16-byte aligned.  stats = {rows changed, bases removed, rows skipped}.  FFQ_E_ARG:
+ * adapter_len outside 1..64, min_overlap outside 1..adapter_len, err_permille outside 0..1000, a scan pending on the
+ * context.  One host wait.  Run it behind ffq_table_trim_quality (cutadapt's order: -q first).  Not done: 5' and anchored
+ * adapters, indels, several adapters per call, paired-end files.                                                       */
+int ffq_table_trim_adapter(ffq_ctx *ctx, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
+                           const int64_t *d_table, int64_t n_rows, const uint8_t *adapter, int adapter_len,
+                           int err_permille, int min_overlap, int64_t *d_out, int64_t stats[3]);
+
 /* FASTQ text from (buffer, table): what a pipeline that excluded reads by deleting rows and trimmed them by editing rows
  * ("to avoid saving a FASTQ file after each filtering or read-trimming step", doc/user-guide.rst:196-204) saves at its
  * end.  Row p renders as
@@ -421,6 +447,14 @@ int  ffq_stream_selected(ffq_stream *s, const int64_t **h_index, int64_t *n_scan
  * skipped} of the fill ffq_stream_next has just returned.                                                          */
 int  ffq_stream_set_trim(ffq_stream *s, int qual_base, int cutoff_front, int cutoff_back);
 int  ffq_stream_trimmed(ffq_stream *s, int64_t stats[3]);
+/* 3' adapter trimming in the stream (the rules of ffq_stream_set_trim: before the first ffq_stream_next, not with
+ * FFQ_F_DECODE_QUAL): every fill's table is adapter-trimmed in place on the device (ffq_table_trim_adapter) right BEHIND
+ * the quality trim, if the stream has one -- cutadapt's own order, -q first and -a on the row as that trim left it -- and
+ * in front of the filter, the column gather, the render and the rows' copy back; the refill goes by the scan's end offset.
+ * `adapter` (host memory) is copied.  ffq_stream_adapter_trimmed: {rows changed, bases removed, rows skipped} of the fill
+ * ffq_stream_next has just returned.                                                                                  */
+int  ffq_stream_set_adapter(ffq_stream *s, const uint8_t *adapter, int adapter_len, int err_permille, int min_overlap);
+int  ffq_stream_adapter_trimmed(ffq_stream *s, int64_t stats[3]);
 /* FASTQ text in the stream (any kind of stream, before the first ffq_stream_next, behind ffq_stream_set_trim /
  * ffq_stream_set_filter if those are set; FFQ_E_ARG with FFQ_F_DECODE_QUAL and with a filter that gathers a column):
  * the rows of every fill -- trimmed and filtered first, if the stream does that -- are rendered on the device
