@@ -10,6 +10,7 @@
 #include "ffq_fasta.h"
 #include "ffq_trim.h"
 #include "ffq_adapter.h"
+#include "ffq_stats.h"
 #include "ffq_render.h"
 #include "ffq_pool.h"
 #include "ffq_mem.h"
@@ -191,6 +192,7 @@ struct ffq_ctx {
     PinBuf<int64_t> h_cut;
     DevBuf<TrimBlock> d_trim;           // ffq_table_trim_quality: the call's counters and their pinned mirror
     PinBuf<TrimBlock> h_trim;
+    PinBuf<uint64_t> h_stats;           // ffq_table_stats: the head words handed back
     DevBuf<int64_t> trim_list;          //   rows left to the wave-per-row launch
     DevBuf<RenderBlock> d_render;       // ffq_table_render_fastq: the call's counters and their pinned mirror
     PinBuf<RenderBlock> h_render;
@@ -282,6 +284,7 @@ static int ctx_create_impl(int device, ffq_ctx *share, ffq_ctx **out)
     if (e == hipSuccess) e = c->d_cut.grow(6);
     if (e == hipSuccess) e = c->d_trim.grow(1);
     if (e == hipSuccess) e = c->h_trim.grow(1);
+    if (e == hipSuccess) e = c->h_stats.grow(STATS_HEAD);
     if (e == hipSuccess) e = c->d_render.grow(1);
     if (e == hipSuccess) e = c->h_render.grow(1);
     if (e == hipSuccess) e = c->fa_hdr.grow(1);
@@ -2035,6 +2038,60 @@ extern "C" int ffq_table_trim_adapter(ffq_ctx *c, const uint8_t *d_buf, int64_t 
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
     stats[0] = (int64_t)c->h_trim->changed; stats[1] = (int64_t)c->h_trim->removed; stats[2] = (int64_t)c->h_trim->skipped;
+    return FFQ_OK;
+}
+
+// ---- per-cycle base and quality statistics of a table (csrc/ffq_stats.h) ----------------------
+static_assert(STATS_QBINS == FFQ_STATS_QBINS && STATS_GCBINS == FFQ_STATS_GCBINS && STATS_HEAD == FFQ_STATS_HEAD &&
+              STATS_MAX_CYCLES == FFQ_STATS_MAX_CYCLES && stats_words(150) == FFQ_STATS_WORDS(150), "include/ffq.h");
+
+extern "C" int ffq_table_stats(ffq_ctx *c, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
+                               const int64_t *d_table, int64_t n_rows, int qual_base, int max_cycles, int accumulate,
+                               uint64_t *d_stats, int64_t head[FFQ_STATS_HEAD])
+{
+    mark_other(c);
+    if (!c || n_rows < 0 || n_bytes < 0 || (n_bytes > 0 && !d_buf) || (n_rows > 0 && !d_table))
+        return fail(FFQ_E_ARG, "ffq_table_stats: bad argument");
+    if (max_cycles < 1 || max_cycles > STATS_MAX_CYCLES) return fail(FFQ_E_ARG, "ffq_table_stats: max_cycles is 1..%d", STATS_MAX_CYCLES);
+    if (qual_base < 0 || qual_base > 255) return fail(FFQ_E_ARG, "ffq_table_stats: qual_base is 0..255");
+    if (!d_stats || ((reinterpret_cast<uintptr_t>(d_stats) | reinterpret_cast<uintptr_t>(d_table)) & 15) != 0)
+        return fail(FFQ_E_ARG, "ffq_table_stats: d_stats and the table must be 16-byte aligned");
+    if (c->pend.active) return fail(FFQ_E_ARG, "ffq_table_stats: a scan is pending on this context");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    stats_u64 *out = reinterpret_cast<stats_u64 *>(d_stats);
+    if (n_rows > 0) {
+        // (before anything is enqueued: growing the list waits for the stream)
+        int rc = grow_dev(c, c->trim_list, n_rows);
+        if (rc) return rc;
+    }
+    if (!accumulate) HIPCHK(hipMemsetAsync(d_stats, 0, (size_t)stats_words(max_cycles) * 8, st));
+    if (n_rows > 0) {
+        // (the long list and its counter are the quality trim's: calls on a context follow one another)
+        HIPCHK(hipMemsetAsync(c->d_trim, 0, sizeof(TrimBlock), st));
+        // 64 rows per workgroup and step; two workgroups per CU (their LDS), striding: every workgroup flushes a whole tile at its end
+        constexpr int64_t rpb = STATS_WG / STATS_G;
+        const int64_t nblk = std::min<int64_t>((n_rows + rpb - 1) / rpb, 512);
+        hipLaunchKernelGGL(k_stats_rows, dim3((unsigned)nblk), dim3(STATS_WG), 0, st, d_buf, n_bytes, sentinel ? 1 : 0, add, d_table,
+                           n_rows, qual_base, max_cycles, out, c->trim_list, c->d_trim);
+        // the rows it left (above STATS_TILE bases; their number is known on the device only): a wave each, checked
+        // and counted per read first, then per cycle tile
+        constexpr int64_t wpb = STATS_WG / 64;
+        const int64_t nblk_long = std::min<int64_t>((n_rows + wpb - 1) / wpb, 512);
+        hipLaunchKernelGGL(k_stats_long_check, dim3((unsigned)nblk_long), dim3(STATS_WG), 0, st, d_buf, n_bytes, sentinel ? 1 : 0, add,
+                           d_table, qual_base, max_cycles, out, c->trim_list, (const TrimBlock *)c->d_trim);
+        const int n_tiles = (max_cycles + STATS_TILE - 1) / STATS_TILE;
+        const int64_t nblk_cnt = std::min<int64_t>((n_rows + wpb - 1) / wpb, 128);
+        hipLaunchKernelGGL(k_stats_long_count, dim3((unsigned)nblk_cnt, (unsigned)n_tiles), dim3(STATS_WG), 0, st, d_buf, n_bytes,
+                           sentinel ? 1 : 0, add, d_table, qual_base, max_cycles, out, (const int64_t *)c->trim_list,
+                           (const TrimBlock *)c->d_trim);
+    }
+    HIPCHK(hipGetLastError());
+    if (head) {
+        HIPCHK(hipMemcpyAsync(c->h_stats, d_stats, STATS_HEAD * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (int i = 0; i < STATS_HEAD; i++) head[i] = (int64_t)c->h_stats[i];
+    }
     return FFQ_OK;
 }
 

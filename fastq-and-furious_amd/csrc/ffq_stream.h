@@ -325,6 +325,9 @@ struct ffq_stream {
     uint8_t ad_bytes[64] = {0};
     int ad_len = 0, ad_err = 0, ad_overlap = 0;
     int64_t last_adapter[3] = {0, 0, 0};
+    // statistics of every fill's table, summed over the fills on the device (ffq_stream_set_stats): the IN block, the OUT block
+    int stats_which = 0, st_base = 33, st_cycles = 0;
+    DevBuf<uint64_t> stats_d;
     // FASTQ text of every fill's table, behind the trim and the filter (ffq_stream_set_render)
     bool render_on = false;
     int64_t last_render[3] = {0, 0, 0};
@@ -1079,6 +1082,52 @@ extern "C" int ffq_stream_adapter_trimmed(ffq_stream *s, int64_t stats[3])
     return FFQ_OK;
 }
 
+// Statistics in the stream: every fill's table is counted on the device (ffq_table_stats, accumulating, no host wait) --
+// FFQ_STATS_IN right behind the scan, FFQ_STATS_OUT on the table that is rendered and copied back -- into two blocks of
+// FFQ_STATS_WORDS(max_cycles) words the stream owns.
+extern "C" int ffq_stream_set_stats(ffq_stream *s, int which, int qual_base, int max_cycles)
+{
+    if (!s) return fail(FFQ_E_ARG, "ffq_stream_set_stats: NULL stream");
+    if (which < 1 || which > (FFQ_STATS_IN | FFQ_STATS_OUT)) return fail(FFQ_E_ARG, "ffq_stream_set_stats: which is FFQ_STATS_IN, FFQ_STATS_OUT or both");
+    if (max_cycles < 1 || max_cycles > FFQ_STATS_MAX_CYCLES) return fail(FFQ_E_ARG, "ffq_stream_set_stats: max_cycles is 1..%d", FFQ_STATS_MAX_CYCLES);
+    if (qual_base < 0 || qual_base > 255) return fail(FFQ_E_ARG, "ffq_stream_set_stats: qual_base is 0..255");
+    if (s->cur >= 0) return fail(FFQ_E_ARG, "ffq_stream_set_stats: the stream has handed out a fill already");
+    ffq_ctx *c = s->c;
+    HIPCHK(hipSetDevice(c->device));
+    // (an even number of words per block: the OUT block is 16-byte aligned as well)
+    const int64_t words = (FFQ_STATS_WORDS(max_cycles) + 1) & ~(int64_t)1;
+    if (s->stats_d.cap < 2 * words) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        int rc = stream_grow(s->stats_d, 2 * words, "ffq_stream: no memory for %lld words of statistics", 2 * words);
+        if (rc) return rc;
+    }
+    HIPCHK(hipMemsetAsync(s->stats_d.p, 0, (size_t)(2 * words) * 8, c->stream));
+    s->stats_which = which; s->st_base = qual_base; s->st_cycles = max_cycles;
+    return FFQ_OK;
+}
+
+static uint64_t *stream_stats_block(ffq_stream *s, int which)
+{
+    const int64_t words = (FFQ_STATS_WORDS(s->st_cycles) + 1) & ~(int64_t)1;
+    return s->stats_d.p + (which == FFQ_STATS_OUT ? words : 0);
+}
+
+// the running totals of one of the blocks, over every fill handed out so far; one host wait
+extern "C" int ffq_stream_stats(ffq_stream *s, int which, uint64_t *h_out, int64_t cap_words)
+{
+    if (!s || !h_out) return fail(FFQ_E_ARG, "ffq_stream_stats: NULL argument");
+    if ((which != FFQ_STATS_IN && which != FFQ_STATS_OUT) || !(s->stats_which & which))
+        return fail(FFQ_E_ARG, "ffq_stream_stats: the stream does not count that (ffq_stream_set_stats)");
+    const int64_t words = FFQ_STATS_WORDS(s->st_cycles);
+    if (cap_words < words) return fail(FFQ_E_ARG, "ffq_stream_stats: the totals have %lld words, the output holds %lld", (long long)words,
+                                       (long long)cap_words);
+    ffq_ctx *c = s->c;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(h_out, stream_stats_block(s, which), (size_t)words * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return FFQ_OK;
+}
+
 // Rendering in the stream: from the first fill on, the rows ffq_stream_next hands out -- trimmed (ffq_stream_set_trim) and
 // filtered (ffq_stream_set_filter, without a column) first, if the stream does that -- are rendered as FASTQ text on the
 // device (ffq_table_render_fastq) and the text is copied back to pinned memory beside the rows.
@@ -1209,6 +1258,12 @@ extern "C" int ffq_stream_next(ffq_stream *s, const int64_t **h_rows, int64_t *n
     const double tp2 = s->prof ? stream_now() : 0;
     int64_t n_out = res.n_records;
     s->last_scanned = res.n_records; s->last_kept = res.n_records; s->last_col_bytes = 0;
+    if (s->stats_which & FFQ_STATS_IN) {
+        // ---- the rows as scanned, counted into the stream's block (enqueued only) ----
+        int rc2 = ffq_table_stats(c, sl.buf.d + start - mis, len + mis, 0, s->globaloffset - mis, b->tab.d, res.n_records, s->st_base,
+                                  s->st_cycles, 1, stream_stats_block(s, FFQ_STATS_IN), nullptr);
+        if (rc2) return rc2;
+    }
     if (s->trim_on) {
         // ---- the fill's rows are trimmed where they lie, over the buffer and the `add` the scan was given ----
         int rc2 = ffq_table_trim_quality(c, sl.buf.d + start - mis, len + mis, 0, s->globaloffset - mis, b->tab.d, res.n_records,
@@ -1232,6 +1287,11 @@ extern "C" int ffq_stream_next(ffq_stream *s, const int64_t **h_rows, int64_t *n
             if (rc2) return rc2;
         }
         s->last_kept = n_out;
+        if (s->stats_which & FFQ_STATS_OUT) {
+            int rc2 = ffq_table_stats(c, sl.buf.d + start - mis, len + mis, 0, s->globaloffset - mis, b->sel, n_out, s->st_base,
+                                      s->st_cycles, 1, stream_stats_block(s, FFQ_STATS_OUT), nullptr);
+            if (rc2) return rc2;
+        }
         if (s->render_on) {
             int rc2 = stream_render(s, sl.buf.d + start - mis, len + mis, s->globaloffset - mis, b->sel, n_out);
             if (rc2) return rc2;
@@ -1252,6 +1312,11 @@ extern "C" int ffq_stream_next(ffq_stream *s, const int64_t **h_rows, int64_t *n
             HIPCHK(hipMemcpyAsync(b->coff.h, b->coff.d, (size_t)(n_out + 1) * 8, hipMemcpyDeviceToHost, c->stream));
         }
     } else {
+        if (s->stats_which & FFQ_STATS_OUT) {
+            int rc2 = ffq_table_stats(c, sl.buf.d + start - mis, len + mis, 0, s->globaloffset - mis, b->tab.d, res.n_records, s->st_base,
+                                      s->st_cycles, 1, stream_stats_block(s, FFQ_STATS_OUT), nullptr);
+            if (rc2) return rc2;
+        }
         if (s->render_on) {
             int rc2 = stream_render(s, sl.buf.d + start - mis, len + mis, s->globaloffset - mis, b->tab.d, res.n_records);
             if (rc2) return rc2;

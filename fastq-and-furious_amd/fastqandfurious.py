@@ -676,12 +676,179 @@ def readfastq_iter(fh: typing.BinaryIO, fbufsize: int,
         offset = 0
 
 
+def stats_eligible(buf, pos):
+    """Does the device count this row (ffq_table_stats' eligibility)?  pos2..pos5 inside `buf`, sequence and quality of one
+    length, no newline in either (a wrapped record)."""
+    p2, p3, p4, p5 = pos[2], pos[3], pos[4], pos[5]
+    return (p2 >= 0 and p4 >= 0 and p2 <= p3 <= len(buf) and p4 <= p5 <= len(buf) and p3 - p2 == p5 - p4
+            and b'\n' not in buf[p2:p3] and b'\n' not in buf[p4:p5])
+
+
+_BASE_CLASS = np.full(256, 4, dtype=np.int64)
+for _i, _pair in enumerate((b"Aa", b"Cc", b"Gg", b"Tt")):
+    _BASE_CLASS[list(_pair)] = _i
+
+
+class FastqStats:
+    """Per-cycle base and quality statistics of reads: the words ffq_table_stats counts (include/ffq.h has the layout),
+    as named numpy uint64 views of one array `words` -- head (8), cycle_base (C x 5: A C G T other), cycle_qual (C x 96),
+    len_hist (C + 1, the last bin "C or longer"), readq_hist (96, by a read's mean quality), gc_hist (101, by its GC per
+    cent) -- with C = max_cycles.  This class is the host statement of the rule: add_record for one eligible record,
+    add_rows for a table (rows the rule does not apply to count in head[1] only); from_words wraps what the device counted;
+    += merges two of one shape (the ranks of a sharded read summing theirs)."""
+
+    def __init__(self, max_cycles=512, qual_base=33):
+        max_cycles, qual_base = int(max_cycles), int(qual_base)
+        if not 1 <= max_cycles <= _hip.STATS_MAX_CYCLES:
+            raise ValueError("max_cycles is 1..%d" % _hip.STATS_MAX_CYCLES)
+        if not 0 <= qual_base <= 255:
+            raise ValueError("qual_base is 0..255")
+        self.max_cycles, self.qual_base = max_cycles, qual_base
+        self._view(np.zeros(_hip.stats_words(max_cycles), dtype=np.uint64))
+
+    def _view(self, words):
+        C = self.max_cycles
+        self.words = words
+        self.head = words[:8]
+        self.cycle_base = words[8:8 + 5 * C].reshape(C, 5)
+        self.cycle_qual = words[8 + 5 * C:8 + 101 * C].reshape(C, 96)
+        self.len_hist = words[8 + 101 * C:8 + 102 * C + 1]
+        self.readq_hist = words[8 + 102 * C + 1:8 + 102 * C + 97]
+        self.gc_hist = words[8 + 102 * C + 97:]
+
+    @classmethod
+    def from_words(cls, words, max_cycles=512, qual_base=33):
+        """The statistics the device counted: `words` (anything numpy reads as stats_words(max_cycles) uint64) is copied."""
+        self = cls(max_cycles, qual_base)
+        words = np.array(words, dtype=np.uint64).reshape(-1)
+        if words.size != self.words.size:
+            raise ValueError("%d words, max_cycles = %d has %d" % (words.size, self.max_cycles, self.words.size))
+        self._view(words)
+        return self
+
+    def add_record(self, sequence, quality):
+        """One eligible record: `sequence` and `quality` are bytes of one length without a newline."""
+        n = len(sequence)
+        if len(quality) != n:
+            raise ValueError("sequence and quality differ in length")
+        C, one = self.max_cycles, np.uint64(1)
+        self.head[0] += one
+        self.len_hist[min(n, C)] += one
+        if n == 0:
+            return
+        cls_ = _BASE_CLASS[np.frombuffer(sequence, dtype=np.uint8)]
+        v = np.clip(np.frombuffer(quality, dtype=np.uint8).astype(np.int64) - self.qual_base, 0, 95)
+        m = min(n, C)
+        cyc = np.arange(m)
+        np.add.at(self.cycle_base, (cyc, cls_[:m]), one)
+        np.add.at(self.cycle_qual, (cyc, v[:m]), one)
+        sv, gc = int(v.sum()), int(np.count_nonzero((cls_ == 1) | (cls_ == 2)))
+        self.head[2] += np.uint64(n)
+        self.head[3] += np.uint64(n - m)
+        self.head[4] += np.uint64(sv)
+        self.head[5] += np.uint64(gc)
+        self.head[6] += np.uint64(np.count_nonzero(cls_ == 4))
+        self.readq_hist[sv // n] += one
+        self.gc_hist[(100 * gc) // n] += one
+
+    def add_pos(self, buf, pos):
+        """One row of positions into `buf`: counted if the rule applies to it (stats_eligible), else skipped (head[1])."""
+        if stats_eligible(buf, pos):
+            self.add_record(buf[pos[2]:pos[3]], buf[pos[4]:pos[5]])
+        else:
+            self.head[1] += np.uint64(1)
+
+    def add_rows(self, buf, rows, shift=0):
+        """Every row of a table (int64 [n][6]; positions minus `shift` index `buf`)."""
+        buf = bytes(buf) if not isinstance(buf, bytes) else buf
+        for row in np.asarray(rows, dtype=np.int64).reshape(-1, 6):
+            self.add_pos(buf, (row - shift).tolist())
+        return self
+
+    def __iadd__(self, other):
+        if not isinstance(other, FastqStats):
+            return NotImplemented
+        if (other.max_cycles, other.qual_base) != (self.max_cycles, self.qual_base):
+            raise ValueError("statistics of different max_cycles / qual_base do not add")
+        self.words += other.words
+        return self
+
+    def __eq__(self, other):
+        return (isinstance(other, FastqStats) and (other.max_cycles, other.qual_base) == (self.max_cycles, self.qual_base)
+                and np.array_equal(self.words, other.words))
+
+    __hash__ = None
+
+    reads = property(lambda self: int(self.head[0]), doc="records counted")
+    bases = property(lambda self: int(self.head[2]), doc="their bases")
+
+    @property
+    def gc_fraction(self):
+        """G + C among all bases (NaN without bases)."""
+        return float(self.head[5]) / self.bases if self.bases else float("nan")
+
+    @property
+    def mean_quality_per_cycle(self):
+        """Mean quality value of every cycle (float64[max_cycles]; NaN where no read reaches)."""
+        q = self.cycle_qual.astype(np.float64)
+        tot = q.sum(axis=1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return (q * np.arange(96)).sum(axis=1) / tot
+
+    def _rate(self, q):
+        tot = int(self.cycle_qual.sum())
+        return float(self.cycle_qual[:, q:].sum()) / tot if tot else float("nan")
+
+    q20_rate = property(lambda self: self._rate(20), doc="share of the bases at cycles below max_cycles with quality >= 20")
+    q30_rate = property(lambda self: self._rate(30), doc="... with quality >= 30")
+
+
+class FilterReport:
+    """What filter_fastq(report=...) fills: the statistics of the reads as they came in (`before`) and as they were written
+    (`after`: behind the trims and the length filter)."""
+
+    def __init__(self, max_cycles=512):
+        self.max_cycles = int(max_cycles)
+        self.before = FastqStats(self.max_cycles)
+        self.after = FastqStats(self.max_cycles)
+
+
+def fastq_stats(fh: typing.BinaryIO, fbufsize: int = 1 << 24, qual_base: int = 33, max_cycles: int = 512,
+                entrypos: typing.Optional[typing.Callable] = None) -> FastqStats:
+    """The statistics of every record of a FASTQ stream.  entrypos None (the GPU scanner): the stream front end scans
+    every buffer fill and counts its table on the device (ffq_stream_set_stats); no row is looked at here and the totals
+    are read once at the end.  Any other scanner: a loop over readfastq_iter with FastqStats.add_pos.  Malformed input
+    raises what readfastq_iter raises."""
+    out = FastqStats(max_cycles, qual_base)
+    if entrypos is None:
+        from . import _fastqandfurious as _C
+        entrypos = _C.entrypos
+    open_stream = getattr(entrypos, 'open_stream', None)
+    st = open_stream(fh, fbufsize) if open_stream is not None else None
+    if st is not None:
+        try:
+            st.set_stats(_hip.STATS_IN, qual_base, max_cycles)
+            for _rows, _fill, _fill_offset, end_state, err_offset in st:
+                if end_state != _END_OK and end_state != _END_REFILL:
+                    _raise_for_end(end_state, err_offset)
+            return FastqStats.from_words(st.stats(_hip.STATS_IN), max_cycles, qual_base)
+        finally:
+            st.close()
+
+    def count(buf, pos, globaloffset=None):
+        out.add_pos(buf, pos)
+
+    for _ in readfastq_iter(fh, fbufsize, count, entrypos):
+        pass
+    return out
+
+
 FilterResult = namedtuple('FilterResult', 'records_in records_out bases_removed bytes_out')
 
 
 def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1 << 24, quality_cutoff=None,
                  qual_base: int = 33, min_len=None, max_len=None, entrypos: typing.Optional[typing.Callable] = None,
-                 adapter=None, err_permille: int = 100, min_overlap: int = 3) -> FilterResult:
+                 adapter=None, err_permille: int = 100, min_overlap: int = 3, report=None) -> FilterResult:
     """Trim, filter and WRITE a FASTQ stream: the file `cutadapt -q 20 -m 30` leaves behind, which is what the tables of
     positions of the reference's user guide are kept for in the end ("to avoid saving a FASTQ file after each filtering or
     read-trimming step", doc/user-guide.rst:196-204).  Every record of `fh` is quality-trimmed (quality_cutoff: an int --
@@ -705,7 +872,14 @@ def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1
     A read trimmed to length 0 is written as b"@h\\n\\n+\\n\\n" unless min_len >= 1 drops it.  A file with such records
     is read back record for record by the Python scanner (entrypos of this module) only: the GPU scanner answers as the
     reference's C scanner does and reads an empty record and the one behind it as one longer record, without an error.
-    min_len >= 1 is what makes the output safe for the GPU scanner and for other tools."""
+    min_len >= 1 is what makes the output safe for the GPU scanner and for other tools.
+
+    report: a FilterReport; its `before` is filled with the statistics of the records as read (qual_base as given here),
+    its `after` with those of the records as written -- counted on the device beside the rest (ffq_stream_set_stats, no
+    host wait per fill) and read once at the end, or record by record with another scanner.  None: nothing is counted."""
+    if report is not None:
+        report.before = FastqStats(report.max_cycles, qual_base)
+        report.after = FastqStats(report.max_cycles, qual_base)
     trim = None
     if quality_cutoff is not None:
         front, back = (0, quality_cutoff) if isinstance(quality_cutoff, (int, np.integer)) else quality_cutoff
@@ -730,6 +904,8 @@ def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1
             if lo is not None or hi is not None:
                 st.set_filter(lo, hi)
             st.set_render()
+            if report is not None:
+                st.set_stats(_hip.STATS_IN | _hip.STATS_OUT, qual_base, report.max_cycles)
             for rows, _fill, _fill_offset, end_state, err_offset in st:
                 text, (nb, rendered, _skipped) = st.rendered()
                 if nb:
@@ -743,12 +919,17 @@ def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1
                     removed += st.adapter_trimmed()[1]
                 if end_state != _END_OK and end_state != _END_REFILL:
                     _raise_for_end(end_state, err_offset)
+            if report is not None:
+                report.before = FastqStats.from_words(st.stats(_hip.STATS_IN), report.max_cycles, qual_base)
+                report.after = FastqStats.from_words(st.stats(_hip.STATS_OUT), report.max_cycles, qual_base)
         finally:
             st.close()
         return FilterResult(n_in, n_out, removed, n_bytes)
 
     def record(buf, pos, globaloffset=None):
         length = pos[3] - pos[2]
+        if report is not None:
+            report.before.add_pos(buf, pos)
         if cutter is not None:
             pos = cutter.trimmed_pos(buf, pos)          # (the quality rule first, if there is one)
         elif trim is not None:
@@ -757,6 +938,8 @@ def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1
         length -= cut
         if (lo is not None and length < lo) or (hi is not None and length > hi):
             return cut, None
+        if report is not None:
+            report.after.add_pos(buf, pos)
         return cut, b"".join((b"@", buf[(pos[0] + 1):pos[1]], b"\n", buf[pos[2]:pos[3]], b"\n+\n", buf[pos[4]:pos[5]], b"\n"))
 
     for cut, text in readfastq_iter(fh, fbufsize, record, entrypos):

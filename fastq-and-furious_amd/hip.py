@@ -55,6 +55,16 @@ E_NODEVICE, E_HIP, E_ARG, E_NOMEM, E_TABLE_FULL, E_INTERNAL, E_TIMEOUT = -1, -2,
 STAGE_NONE, STAGE_HANDOFF, STAGE_SCAN, STAGE_GATHER = 0, 1, 2, 3      # FFQ_SHARD_STAGE_*
 STAGE_NAMES = ("none", "hand-off", "scan", "gather")
 
+# statistics (include/ffq.h: FFQ_STATS_*)
+STATS_QBINS, STATS_GCBINS, STATS_HEAD, STATS_MAX_CYCLES = 96, 101, 8, 4096
+STATS_IN, STATS_OUT = 1, 2
+
+
+def stats_words(max_cycles):
+    """uint64 words of a block of statistics for max_cycles cycles (FFQ_STATS_WORDS)."""
+    return 8 + max_cycles * 101 + (max_cycles + 1) + STATS_QBINS + STATS_GCBINS
+
+
 F_DECODE_QUAL = 1
 F_FORCE_SERIAL = 2
 F_FORCE_RANKED = 4
@@ -87,6 +97,7 @@ SYMBOLS = (
     "ffq_table_trim_quality", "ffq_stream_set_trim", "ffq_stream_trimmed",
     "ffq_table_render_fastq", "ffq_stream_set_render", "ffq_stream_rendered",
     "ffq_table_trim_adapter", "ffq_stream_set_adapter", "ffq_stream_adapter_trimmed",
+    "ffq_table_stats", "ffq_stream_set_stats", "ffq_stream_stats",
 )
 
 
@@ -319,6 +330,7 @@ def lib():
         L.ffq_table_cut.argtypes = [vp, vp, i64, i64, i64, P(i64)]
         L.ffq_table_trim_quality.argtypes = [vp, vp, i64, i32, i64, vp, i64, i32, i32, i32, vp, P(i64)]
         L.ffq_table_trim_adapter.argtypes = [vp, vp, i64, i32, i64, vp, i64, ctypes.c_char_p, i32, i32, i32, vp, P(i64)]
+        L.ffq_table_stats.argtypes = [vp, vp, i64, i32, i64, vp, i64, i32, i32, i32, vp, P(i64)]
         L.ffq_table_render_fastq.argtypes = [vp, vp, i64, i32, i64, vp, i64, vp, i64, vp, P(i64)]
         L.ffq_table_gather_column.argtypes = [vp, vp, i64, i32, i64, vp, i64, i32, i32, i32, i32, vp, i64, vp, P(i64)]
         L.ffq_stream_open.argtypes = [vp, i32, i64, P(vp)]
@@ -376,6 +388,8 @@ def lib():
         L.ffq_stream_trimmed.argtypes = [vp, P(i64)]
         L.ffq_stream_set_adapter.argtypes = [vp, ctypes.c_char_p, i32, i32, i32]
         L.ffq_stream_adapter_trimmed.argtypes = [vp, P(i64)]
+        L.ffq_stream_set_stats.argtypes = [vp, i32, i32, i32]
+        L.ffq_stream_stats.argtypes = [vp, i32, vp, i64]
         L.ffq_stream_set_render.argtypes = [vp]
         L.ffq_stream_rendered.argtypes = [vp, P(vp), P(i64), P(i64)]
         L.ffq_stream_selected.argtypes = [vp, P(vp), P(i64), P(vp), P(vp), P(i64)]
@@ -683,6 +697,20 @@ class Context:
                                            int(min_overlap), ctypes.c_void_p(d_table if d_out is None else d_out), stats))
         return int(stats[0]), int(stats[1]), int(stats[2])
 
+    def table_stats(self, d_buf, n_bytes, d_table, n_rows, d_stats, qual_base=33, max_cycles=512, accumulate=False, sentinel=True,
+                    add=None, wait=True):
+        """Per-cycle base and quality statistics of the rows of a device table (ffq_table_stats), counted into the
+        stats_words(max_cycles) uint64 words at d_stats (device memory, 16-byte aligned; include/ffq.h has the layout):
+        overwritten, or added to with accumulate.  Raw device pointers; d_buf / n_bytes / sentinel / add as for
+        table_gather_column.  Returns the eight head words (rows counted, rows skipped, bases, ...) as they stand after the
+        call -- one host wait --, or None with wait=False: the call is only enqueued on the context's stream."""
+        add = _add(add, sentinel)
+        head = (ctypes.c_int64 * STATS_HEAD)() if wait else None
+        check(lib().ffq_table_stats(self.handle, ctypes.c_void_p(d_buf), int(n_bytes), int(bool(sentinel)), int(add),
+                                    ctypes.c_void_p(d_table), int(n_rows), int(qual_base), int(max_cycles), int(bool(accumulate)),
+                                    ctypes.c_void_p(d_stats), head))
+        return [int(x) for x in head] if wait else None
+
     def table_render_fastq(self, d_buf, n_bytes, d_table, n_rows, d_out, out_cap, d_off=None, sentinel=True, add=None):
         """FASTQ text of the rows of a device table (ffq_table_render_fastq): row p renders as "@" + buf[p0 + 1:p1] + "\\n"
         + buf[p2:p3] + "\\n+\\n" + buf[p4:p5] + "\\n", a row that is not renderable as nothing.  d_out: out_cap bytes, any
@@ -981,6 +1009,21 @@ class _Stream:
         stats = (ctypes.c_int64 * 3)()
         check(lib().ffq_stream_adapter_trimmed(self._h, stats))
         return int(stats[0]), int(stats[1]), int(stats[2])
+
+    def set_stats(self, which, qual_base=33, max_cycles=512):
+        """Statistics in the stream (ffq_stream_set_stats; before the first fill): which = STATS_IN (the rows as scanned),
+        STATS_OUT (the rows as handed out, behind trim, adapter and filter) or both; counted on the device over all fills,
+        with no host wait per fill."""
+        check(lib().ffq_stream_set_stats(self._h, int(which), int(qual_base), int(max_cycles)))
+        self._stats_cycles = int(max_cycles)
+
+    def stats(self, which):
+        """The running totals (numpy uint64[stats_words(max_cycles)]) of STATS_IN or STATS_OUT over every fill up to and
+        including the one the iteration has just yielded (ffq_stream_stats; one host wait)."""
+        import numpy as np
+        out = np.zeros(stats_words(getattr(self, "_stats_cycles", 1)), dtype=np.uint64)
+        check(lib().ffq_stream_stats(self._h, int(which), ctypes.c_void_p(out.ctypes.data), int(out.size)))
+        return out
 
     def set_render(self):
         """FASTQ text in the stream (ffq_stream_set_render; before the first fill, behind set_trim / set_filter): the rows

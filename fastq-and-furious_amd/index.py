@@ -213,6 +213,27 @@ def trim_adapter_rows_device(ctx, buf, table, adapter, err_permille=100, min_ove
     return out, stats
 
 
+def stats_rows(buf, table, qual_base=33, max_cycles=512, shift=0):
+    """Per-cycle base and quality statistics of the rows of a table, on the host (_F.FastqStats.add_rows: positions minus
+    `shift` index `buf`; a row the rule does not apply to counts as skipped)."""
+    return _F.FastqStats(max_cycles, qual_base).add_rows(buf, table, shift)
+
+
+def stats_rows_device(ctx, buf, table, qual_base=33, max_cycles=512, sentinel=True, add=None, out=None, accumulate=False):
+    """stats_rows on the GPU: `buf` is the CUDA uint8 tensor the rows of `table` (CUDA int64[n][6]) were scanned from,
+    sentinel / add as that scan had them.  out: a CUDA int64 tensor of hip.stats_words(max_cycles) elements to count into
+    (overwritten, or added to with accumulate); None: a new one.  Returns (_F.FastqStats of what `out` holds after the call,
+    out).  One C-ABI call (ffq_table_stats) and one copy back."""
+    import torch
+    words = _hip.stats_words(max_cycles)
+    if out is None:
+        out = torch.zeros(words, dtype=torch.int64, device=buf.device)
+        torch.cuda.current_stream(buf.device).synchronize()      # (the call runs on the context's stream, not on torch's)
+    ctx.table_stats(buf.data_ptr(), buf.numel(), table.data_ptr(), int(table.shape[0]), out.data_ptr(), qual_base, max_cycles,
+                    accumulate=accumulate, sentinel=sentinel, add=add)
+    return _F.FastqStats.from_words(out.cpu().numpy().view(np.uint64), max_cycles, qual_base), out
+
+
 def select_column_device(ctx, buf, table, which, sentinel=True, add=None, value_add=0):
     """One component of every row, packed, on the GPU: `buf` is the CUDA uint8 tensor the rows of
     `table` (CUDA int64[n][6]) were scanned from; which = "header" | "sequence" | "quality".

@@ -340,6 +340,37 @@ int ffq_table_trim_adapter(ffq_ctx *ctx, const uint8_t *d_buf, int64_t n_bytes, 
                            const int64_t *d_table, int64_t n_rows, const uint8_t *adapter, int adapter_len,
                            int err_permille, int min_overlap, int64_t *d_out, int64_t stats[3]);
 
+/* Per-cycle base and quality statistics of a table, counted on the device: what the QC report of fastp / FastQC is made
+ * of.  d_stats: DEVICE memory, 16-byte aligned, FFQ_STATS_WORDS(C) uint64 words with C = max_cycles; overwritten
+ * (accumulate == 0, whatever they held) or added to (accumulate != 0).  For one eligible row, seq = buf[pos2:pos3], q =
+ * buf[pos4:pos5], n = len(seq), v[i] = clamp(q[i] - qual_base, 0, 95), cls[i] = 0 / 1 / 2 / 3 for A a / C c / G g / T t
+ * and 4 for every other byte:
+ *     words 0..7            head: [0] rows counted, [1] rows skipped, [2] bases (sum of n), [3] bases at cycles >= C,
+ *                                 [4] sum of v over all bases, [5] bases of class 1 or 2 (GC), [6] bases of class 4, [7] 0
+ *     8 + c*5 + b           cycle_base[c][b]: for every i < min(n, C): [i][cls[i]] += 1
+ *     8 + 5C + c*96 + v     cycle_qual[c][v]: for every i < min(n, C): [i][v[i]] += 1
+ *     8 + 101C + l          len_hist[l], l in 0..C: [min(n, C)] += 1 (the last bin is "C or longer")
+ *     8 + 102C + 1 + m      readq_hist[m]: if n > 0: [(sum of v) / n] += 1 (integer division)
+ *     8 + 102C + 97 + g     gc_hist[g]: if n > 0: [(100 * gc) / n] += 1, gc = bases of class 1 or 2
+ * Bases at cycles >= C count in the head and in the two per-read histograms, not in the per-cycle arrays.  A row is
+ * ELIGIBLE if pos2..pos5 - add are all >= 0, pos2 <= pos3 and pos4 <= pos5 lie inside the buffer (with sentinel, coordinate
+ * 0 is the virtual "\n": never read), pos3 - pos2 == pos5 - pos4 and no byte of the sequence or of the quality is "\n" (a
+ * wrapped record); every other row adds 1 to head[1] and nothing else; a row of length 0 counts in head[0] and len_hist[0]
+ * only.  Rows are independent: any order, repeated, overlapping.  No byte outside [d_buf, d_buf + n_bytes) is read.  All
+ * sums are integers added with integer atomics: the result does not depend on the order of anything.  d_buf / n_bytes /
+ * sentinel / add: as for ffq_table_gather_column.  head: HOST memory; non-NULL: one host wait, words 0..7 of d_stats as they
+ * stand after this call; NULL: the call only enqueues on the context's stream.  n_rows == 0 is valid (accumulate == 0: the
+ * block is zeroed).  FFQ_E_ARG: max_cycles outside 1..FFQ_STATS_MAX_CYCLES, qual_base outside 0..255, d_stats NULL or
+ * misaligned, a scan pending on the context.                                                                          */
+#define FFQ_STATS_QBINS      96     /* quality value v = clamp(byte - qual_base, 0, 95) */
+#define FFQ_STATS_GCBINS     101
+#define FFQ_STATS_HEAD       8
+#define FFQ_STATS_MAX_CYCLES 4096
+#define FFQ_STATS_WORDS(C)   (8 + (int64_t)(C) * 101 + ((C) + 1) + 96 + 101)
+int ffq_table_stats(ffq_ctx *ctx, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
+                    const int64_t *d_table, int64_t n_rows, int qual_base, int max_cycles,
+                    int accumulate, uint64_t *d_stats, int64_t head[FFQ_STATS_HEAD]);
+
 /* FASTQ text from (buffer, table): what a pipeline that excluded reads by deleting rows and trimmed them by editing rows
  * ("to avoid saving a FASTQ file after each filtering or read-trimming step", doc/user-guide.rst:196-204) saves at its
  * end.  Row p renders as
@@ -455,6 +486,18 @@ int  ffq_stream_trimmed(ffq_stream *s, int64_t stats[3]);
  * ffq_stream_next has just returned.                                                                                  */
 int  ffq_stream_set_adapter(ffq_stream *s, const uint8_t *adapter, int adapter_len, int err_permille, int min_overlap);
 int  ffq_stream_adapter_trimmed(ffq_stream *s, int64_t stats[3]);
+/* Statistics in the stream (any kind of stream, also with FFQ_F_DECODE_QUAL, a filter, a gathered column and a render;
+ * before the first ffq_stream_next): every fill's table is counted on the device (ffq_table_stats) into a block the stream
+ * owns, summed over all fills.  FFQ_STATS_IN: the rows as scanned, before any trim; FFQ_STATS_OUT: the rows as handed out,
+ * behind trim, adapter and filter (what is rendered and copied back).  `which` = one of them or both; both share qual_base
+ * and max_cycles.  The counting adds no host wait to a fill.  ffq_stream_stats (`which`: exactly one): the totals over every
+ * fill up to and including the one ffq_stream_next has just returned, copied to h_out (host memory, cap_words >=
+ * FFQ_STATS_WORDS(max_cycles) words) with one wait; after any fill and after the last one.  FFQ_E_ARG: a `which` that was
+ * not set, cap_words too small, set_stats behind the first fill.                                                       */
+#define FFQ_STATS_IN  1   /* rows as scanned, before any trim                       */
+#define FFQ_STATS_OUT 2   /* rows as handed out: behind trim, adapter and filter    */
+int  ffq_stream_set_stats(ffq_stream *s, int which /* IN | OUT */, int qual_base, int max_cycles);
+int  ffq_stream_stats(ffq_stream *s, int which /* exactly one */, uint64_t *h_out, int64_t cap_words);
 /* FASTQ text in the stream (any kind of stream, before the first ffq_stream_next, behind ffq_stream_set_trim /
  * ffq_stream_set_filter if those are set; FFQ_E_ARG with FFQ_F_DECODE_QUAL and with a filter that gathers a column):
  * the rows of every fill -- trimmed and filtered first, if the stream does that -- are rendered on the device
