@@ -6,10 +6,9 @@
 // pos5 = pos4 + p.  Mismatches only, no indels.  Eligibility is ffq_table_trim_quality's, with the newline looked for in the
 // SEQUENCE; any other row is copied unchanged and counted.
 //
-// Shape: ffq_trim.h's.  A GROUP of G lanes owns a row (G = 8 in k_adapter_rows, thirty-two rows per workgroup and step; rows
-// of more than ADAPTER_LONG bases go onto the long list and k_adapter_long gives each a whole wave, G = 64); workgroups stride
-// over the table and ask for their next rows before they work on these; the counters are ffq_trim.h's TrimBlock.  The new
-// part is the match.  Candidates are taken in CHUNKS of G * 8 ascending positions, eight consecutive ones per lane:
+// Shape: the row frame of ffq_rows.h -- eight lanes per row; rows of more than ADAPTER_LONG bases get a whole wave in the second
+// launch.  The pass's own part is the match.  Candidates are taken in CHUNKS of G * 8 ascending positions, eight consecutive
+// ones per lane:
 //   * the chunk's bytes seq[p0 .. p0 + G * 8 + 64) -- its candidates and the 63 bytes behind the last of them -- are staged
 //     once into the group's LDS window, sixteen bytes per lane (unaligned dword loads; a piece the read's end cuts short
 //     byte by byte, zeros behind it), and looked through for '\n' on the way;
@@ -21,16 +20,17 @@
 //     as soon as no lane of the wave has a live candidate (on random bases: after the second dword);
 //   * one max-reduction of (chunk size - position) over the group finds the leftmost hit; the group stops at the first chunk
 //     that has one.
-// Every loop is uniform over the wave: a group without a row, with an empty or ineligible row, or done with its row, steps
+// Every loop is uniform over the wave, as the frame asks: a group with an empty or ineligible row, or done with its row, steps
 // along with nothing to do until every group of the wave is done.  What the chunks did not read (the read behind a hit) is
 // then looked through for '\n' sixteen bytes per lane.  No byte outside the row's own sequence range, itself checked against
 // the buffer, is read.
 #pragma once
-#include "ffq_trim.h"
+#include "ffq_rows.h"
 
 namespace ffq {
 
 constexpr int ADAPTER_LONG = 2048;    // bases above which a row gets a wave of its own
+constexpr int ADAPTER_WG = 256;
 constexpr int ADAPTER_MAX = 64;       // longest adapter
 constexpr int ADAPTER_K = 8;          // consecutive candidates per lane and chunk
 
@@ -55,7 +55,7 @@ __device__ __forceinline__ void adapter_load16(const uint8_t *__restrict__ seq, 
     x[0] = x[1] = x[2] = x[3] = 0;
     if (a + 16 <= n) {
 #pragma unroll
-        for (int w = 0; w < 4; w++) x[w] = *reinterpret_cast<const trim_u32u *>(seq + a + 4 * w);
+        for (int w = 0; w < 4; w++) x[w] = *reinterpret_cast<const rows_u32u *>(seq + a + 4 * w);
     } else {
         const int have = (int)max(n - a, (int64_t)0);
 #pragma unroll
@@ -65,10 +65,7 @@ __device__ __forceinline__ void adapter_load16(const uint8_t *__restrict__ seq, 
         // (zeros behind the end are no newlines)
     }
 #pragma unroll
-    for (int w = 0; w < 4; w++) {
-        const uint32_t y = x[w] ^ 0x0A0A0A0Au;
-        nl |= adapter_nzbytes(y) != 4;
-    }
+    for (int w = 0; w < 4; w++) nl |= has_nl(x[w]);
 }
 
 // The cut of one row per group: the leftmost qualifying position, n if there is none.  live: the group has an eligible row
@@ -119,7 +116,7 @@ __device__ __forceinline__ void adapter_match(const uint8_t *__restrict__ seq, i
             }
             if (mm <= allowed && key == 0) key = CH - (gl * K + k);
         }
-        const int gmax = TrimGroup<G>::maxall(key);             // the leftmost hit of the chunk: CH - its position; 0: none
+        const int gmax = RowGroup<G>::maxall(key);             // the leftmost hit of the chunk: CH - its position; 0: none
         if (act) {
             nread = min(p0 + WIN, n);
             if (gmax > 0) { cut = p0 + (CH - gmax); act = false; }
@@ -129,59 +126,42 @@ __device__ __forceinline__ void adapter_match(const uint8_t *__restrict__ seq, i
 }
 
 // One row per group.  have: this group has a row (uniform in the group).  defer_long: rows above ADAPTER_LONG are left to the
-// second launch (is_long).
+// second launch; returns whether this is one.
 template <int G>
-__device__ __forceinline__ void adapter_row(const uint8_t *__restrict__ d, int64_t nbytes, int s, int64_t add,
-                                            const int64_t *__restrict__ table, int64_t *__restrict__ out, int64_t row, bool have,
-                                            longlong2 r01, longlong2 r23, longlong2 r45, const AdapterArg &ad, int m, int err,
-                                            int min_overlap, bool defer_long, int gl, int gshift, uint32_t *__restrict__ win,
-                                            bool &is_long, unsigned int &changed, unsigned long long &removed, unsigned int &skipped)
+__device__ __forceinline__ bool adapter_row(const uint8_t *__restrict__ d, int64_t nbytes, int s, int64_t add, const int64_t *table,
+                                            int64_t *out, int64_t row, bool have, longlong2 r01, longlong2 r23, longlong2 r45,
+                                            const AdapterArg &ad, int m, int err, int min_overlap, bool defer_long, int gl,
+                                            int gshift, uint32_t *__restrict__ win, RowCounts &cnt)
 {
-    // buffer coordinates (wrapping arithmetic: a row may hold anything)
-    const int64_t p2 = (int64_t)((uint64_t)r23.x - (uint64_t)add), p3 = (int64_t)((uint64_t)r23.y - (uint64_t)add);
-    const int64_t p4 = (int64_t)((uint64_t)r45.x - (uint64_t)add), p5 = (int64_t)((uint64_t)r45.y - (uint64_t)add);
-    const int64_t L = nbytes + s;
-    const int64_t n = p3 - p2;
-    bool elig = have && p2 >= 0 && p4 >= 0 && p2 <= p3 && p4 <= p5 && p3 <= L && p5 <= L && p5 - p4 == n;
-    // coordinate 0 of a buffer with a sentinel is the virtual '\n'
-    if (elig && n > 0 && p2 < s) elig = false;
-    is_long = defer_long && elig && n > ADAPTER_LONG;
+    int64_t p2 = 0, p4 = 0, n = 0;
+    const bool elig = have && row_pos<true, false>(nbytes, s, add, r23, r45, p2, p4, n);
+    const bool is_long = defer_long && elig && n > ADAPTER_LONG;
     const bool live = elig && !is_long && n > 0;
     const uint8_t *seq = d + (p2 - s);
 
     int64_t cut = n, nread = 0;
     bool nl = false;
     adapter_match<G>(seq, n, live, ad, m, err, min_overlap, gl, win, cut, nread, nl);
-    trim_scan_nl<G>(seq, nread, n, live, gl, nl);
-    const bool any_nl = trim_first<G>(__ballot(nl), gshift) != G;
+    rows_scan_nl<G>(seq, nread, n, live, gl, nl);
+    const bool any_nl = group_any<G>(nl, gshift);
 
-    if (!have || is_long) return;
-    if (!elig || any_nl) {
-        if (gl == 0) skipped++;
-        if (out != table) trim_store_row(out, row, gl, r01, r23, r45);
-        return;
-    }
-    const bool ch = cut != n;
-    if (gl == 0 && ch) { changed++; removed += (unsigned long long)(n - cut); }
-    if (ch || out != table) {
-        // (pos + cut: the row's own coordinates, whatever `add` is)
-        const longlong2 n23 = make_longlong2(r23.x, r23.x + cut), n45 = make_longlong2(r45.x, r45.x + cut);
-        trim_store_row(out, row, gl, r01, n23, n45);
-    }
+    // (pos + cut: the row's own coordinates, whatever `add` is)
+    row_edit_finish(table, out, row, gl, have, is_long, elig && !any_nl, r01, r23, r45, make_longlong2(r23.x, r23.x + cut),
+                    make_longlong2(r45.x, r45.x + cut), n - cut, cnt);
+    return is_long;
 }
 
-// thirty-two rows per workgroup and step, eight lanes each; the shape of k_trim_rows
-__global__ __launch_bounds__(TRIM_WG) void k_adapter_rows(const uint8_t *__restrict__ d, int64_t nbytes, int s, int64_t add,
-                                                          const int64_t *table, int64_t n_rows, const AdapterArg ad, int m,
-                                                          int err, int min_overlap, int64_t *out,
-                                                          int64_t *__restrict__ long_list, TrimBlock *__restrict__ blk)
+__global__ __launch_bounds__(ADAPTER_WG) void k_adapter_rows(const uint8_t *__restrict__ d, int64_t nbytes, int s, int64_t add,
+                                                             const int64_t *table, int64_t n_rows, const AdapterArg ad, int m,
+                                                             int err, int min_overlap, int64_t *out,
+                                                             int64_t *__restrict__ long_list, RowsBlock *__restrict__ blk)
 {
-    constexpr int G = TRIM_G, RPB = TRIM_WG / G;
-    __shared__ __attribute__((aligned(16))) uint32_t s_win[RPB][AdapterShape<G>::WIN / 4];
+    constexpr int G = ROWS_G;
+    __shared__ __attribute__((aligned(16))) uint32_t s_win[ADAPTER_WG / G][AdapterShape<G>::WIN / 4];
     const int lane = threadIdx.x & 63, gl = lane & (G - 1), gshift = lane & ~(G - 1);
     uint32_t *win = s_win[threadIdx.x / G];
-    unsigned int changed = 0, skipped = 0;
-    unsigned long long removed = 0;
+    RowCounts cnt;
+    constexpr int RPB = ADAPTER_WG / G;
     const int64_t step = (int64_t)gridDim.x * RPB;
     longlong2 x01 = make_longlong2(0, 0), x23 = x01, x45 = x01;
     {
@@ -198,48 +178,28 @@ __global__ __launch_bounds__(TRIM_WG) void k_adapter_rows(const uint8_t *__restr
             const longlong2 *src = reinterpret_cast<const longlong2 *>(table + (row + step) * 6);
             x01 = src[0]; x23 = src[1]; x45 = src[2];
         }
-        bool is_long = false;
-        adapter_row<G>(d, nbytes, s, add, table, out, row, row < n_rows, r01, r23, r45, ad, m, err, min_overlap, true, gl, gshift,
-                       win, is_long, changed, removed, skipped);
-        // the long rows of the wave take their places on the list with one atomic
-        const unsigned long long lm = __ballot(is_long && gl == 0);
-        if (lm) {
-            unsigned long long at = 0;
-            if (lane == 0) at = atomicAdd(&blk->n_long, (unsigned long long)__popcll(lm));
-            at = (unsigned long long)__shfl((long long)at, 0);
-            if (is_long && gl == 0) long_list[at + __popcll(lm & ((1ull << lane) - 1ull))] = row;
-        }
+        const bool is_long = adapter_row<G>(d, nbytes, s, add, table, out, row, row < n_rows, r01, r23, r45, ad, m, err, min_overlap, true,
+                                            gl, gshift, win, cnt);
+        const int64_t at = long_list_append(is_long && gl == 0, lane, &blk->n_long);
+        if (at >= 0) long_list[at] = row;
     }
-    trim_add_counters(blk, changed, removed, skipped);
+    cnt.add_to<ADAPTER_WG>(blk);
 }
 
-// the rows k_adapter_rows left: a wave per row, 512 candidates per chunk
-__global__ __launch_bounds__(TRIM_WG) void k_adapter_long(const uint8_t *__restrict__ d, int64_t nbytes, int s, int64_t add,
-                                                          const int64_t *table, const AdapterArg ad, int m, int err,
-                                                          int min_overlap, int64_t *out, const int64_t *__restrict__ long_list,
-                                                          TrimBlock *__restrict__ blk)
+// the rows k_adapter_rows left: 512 candidates per chunk
+__global__ __launch_bounds__(ADAPTER_WG) void k_adapter_long(const uint8_t *__restrict__ d, int64_t nbytes, int s, int64_t add,
+                                                             const int64_t *table, const AdapterArg ad, int m, int err,
+                                                             int min_overlap, int64_t *out, const int64_t *__restrict__ long_list,
+                                                             RowsBlock *__restrict__ blk)
 {
-    constexpr int WPB = TRIM_WG / 64;
-    __shared__ __attribute__((aligned(16))) uint32_t s_win[WPB][AdapterShape<64>::WIN / 4];
+    __shared__ __attribute__((aligned(16))) uint32_t s_win[ADAPTER_WG / 64][AdapterShape<64>::WIN / 4];
     const int lane = threadIdx.x & 63;
     uint32_t *win = s_win[threadIdx.x >> 6];
-    const int64_t n_long = (int64_t)blk->n_long;
-    unsigned int changed = 0, skipped = 0;
-    unsigned long long removed = 0;
-    for (int64_t j0 = (int64_t)blockIdx.x * WPB; j0 < n_long; j0 += (int64_t)gridDim.x * WPB) {
-        const int64_t j = j0 + (threadIdx.x >> 6);
-        const bool have = j < n_long;
-        const int64_t row = have ? long_list[j] : 0;
-        longlong2 r01 = make_longlong2(0, 0), r23 = r01, r45 = r01;
-        if (have) {
-            const longlong2 *src = reinterpret_cast<const longlong2 *>(table + row * 6);
-            r01 = src[0]; r23 = src[1]; r45 = src[2];
-        }
-        bool is_long = false;
-        adapter_row<64>(d, nbytes, s, add, table, out, row, have, r01, r23, r45, ad, m, err, min_overlap, false, lane, 0, win,
-                        is_long, changed, removed, skipped);
-    }
-    trim_add_counters(blk, changed, removed, skipped);
+    RowCounts cnt;
+    for (LongRows<ADAPTER_WG, true> it((int64_t)blk->n_long, long_list, table); it.next();)
+        adapter_row<64>(d, nbytes, s, add, table, out, it.row, it.have, it.r01, it.r23, it.r45, ad, m, err, min_overlap, false, lane, 0, win,
+                        cnt);
+    cnt.add_to<ADAPTER_WG>(blk);
 }
 
 }  // namespace ffq

@@ -8,6 +8,7 @@
 #endif
 #include "ffq_kernels.h"
 #include "ffq_fasta.h"
+#include "ffq_rows.h"
 #include "ffq_trim.h"
 #include "ffq_adapter.h"
 #include "ffq_stats.h"
@@ -190,10 +191,10 @@ struct ffq_ctx {
     PinBuf<int64_t> h_word;             //   and their pinned mirror
     DevBuf<int64_t> d_cut;              // ffq_table_cut: 6 words
     PinBuf<int64_t> h_cut;
-    DevBuf<TrimBlock> d_trim;           // ffq_table_trim_quality: the call's counters and their pinned mirror
-    PinBuf<TrimBlock> h_trim;
+    DevBuf<RowsBlock> d_rows;           // the table passes of ffq_rows.h: a call's counters and their pinned mirror
+    PinBuf<RowsBlock> h_rows;
+    DevBuf<int64_t> rows_list;          //   rows left to the wave-per-row launch
     PinBuf<uint64_t> h_stats;           // ffq_table_stats: the head words handed back
-    DevBuf<int64_t> trim_list;          //   rows left to the wave-per-row launch
     DevBuf<RenderBlock> d_render;       // ffq_table_render_fastq: the call's counters and their pinned mirror
     PinBuf<RenderBlock> h_render;
     DevBuf<int64_t> render_list;        //   (row, place in the output) of the rows left to the wave-per-row launch
@@ -282,8 +283,8 @@ static int ctx_create_impl(int device, ffq_ctx *share, ffq_ctx **out)
     if (e == hipSuccess) e = c->d_word.grow(2);
     if (e == hipSuccess) e = c->h_word.grow(2);
     if (e == hipSuccess) e = c->d_cut.grow(6);
-    if (e == hipSuccess) e = c->d_trim.grow(1);
-    if (e == hipSuccess) e = c->h_trim.grow(1);
+    if (e == hipSuccess) e = c->d_rows.grow(1);
+    if (e == hipSuccess) e = c->h_rows.grow(1);
     if (e == hipSuccess) e = c->h_stats.grow(STATS_HEAD);
     if (e == hipSuccess) e = c->d_render.grow(1);
     if (e == hipSuccess) e = c->h_render.grow(1);
@@ -1951,44 +1952,65 @@ extern "C" int ffq_table_gather_column(ffq_ctx *c, const uint8_t *d_buf, int64_t
     return FFQ_OK;
 }
 
-// ---- quality trimming: rows of the table edited in place (csrc/ffq_trim.h) -------------------
+// ---- the table passes on csrc/ffq_rows.h: quality trim, adapter trim, statistics (ffq_trim.h, ffq_adapter.h, ffq_stats.h) ----
+// Workgroups of a pass's launches, each capped: they stride over what there is.  The short rows' launch has WG / ROWS_G rows
+// per workgroup and step; the long rows' launches have a wave per row, and as the list's length is known on the device only,
+// they are sized by the table.
+constexpr int EDIT_GRID_SHORT = 2048, EDIT_GRID_LONG = 1024;                       // the two trims
+constexpr int STATS_GRID_SHORT = 512, STATS_GRID_CHECK = 512, STATS_GRID_COUNT = 128;   // (two workgroups per CU: their LDS); x tiles
+
+static unsigned rows_grid(int64_t n_rows, int per_wg, int cap) { return (unsigned)std::min<int64_t>((n_rows + per_wg - 1) / per_wg, cap); }
+
+// What the passes check and set up alike.  args_ok: the caller's own pointers; d_dst: what the pass writes on the device.  With
+// rows, the long list is grown (before anything is enqueued: growing waits for the stream) and the call's counters are cleared.
+// The list and the counters are the context's, not a pass's: calls on a context follow one another.
+static int rows_begin(ffq_ctx *c, const char *who, bool args_ok, const uint8_t *d_buf, int64_t n_bytes, const int64_t *d_table,
+                      int64_t n_rows, const void *d_dst)
+{
+    if (!c || !args_ok || n_rows < 0 || n_bytes < 0 || (n_bytes > 0 && !d_buf) || (n_rows > 0 && (!d_table || !d_dst)))
+        return fail(FFQ_E_ARG, "%s: bad argument", who);
+    if (((reinterpret_cast<uintptr_t>(d_table) | reinterpret_cast<uintptr_t>(d_dst)) & 15) != 0)
+        return fail(FFQ_E_ARG, "%s: the table and what is written must be 16-byte aligned", who);
+    if (c->pend.active) return fail(FFQ_E_ARG, "%s: a scan is pending on this context", who);
+    HIPCHK(hipSetDevice(c->device));
+    if (n_rows == 0) return FFQ_OK;
+    const int rc = grow_dev(c, c->rows_list, n_rows);
+    if (rc) return rc;
+    HIPCHK(hipMemsetAsync(c->d_rows, 0, sizeof(RowsBlock), c->stream));
+    return FFQ_OK;
+}
+
+// the counters of an editing pass back: the call's one host wait
+static int rows_end(ffq_ctx *c, int64_t stats[3])
+{
+    HIPCHK(hipMemcpyAsync(c->h_rows, c->d_rows, sizeof(RowsBlock), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    stats[0] = (int64_t)c->h_rows->changed; stats[1] = (int64_t)c->h_rows->removed; stats[2] = (int64_t)c->h_rows->skipped;
+    return FFQ_OK;
+}
+
 extern "C" int ffq_table_trim_quality(ffq_ctx *c, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
                                       const int64_t *d_table, int64_t n_rows, int qual_base, int cutoff_front,
                                       int cutoff_back, int64_t *d_out, int64_t stats[3])
 {
     mark_other(c);
-    if (!c || !stats || n_rows < 0 || n_bytes < 0 || (n_bytes > 0 && !d_buf) || (n_rows > 0 && (!d_table || !d_out)))
-        return fail(FFQ_E_ARG, "ffq_table_trim_quality: bad argument");
     if (cutoff_front < 0 || cutoff_front > 127 || cutoff_back < 0 || cutoff_back > 127)
         return fail(FFQ_E_ARG, "ffq_table_trim_quality: cutoffs are 0..127");
     if (qual_base < 0 || qual_base > 255) return fail(FFQ_E_ARG, "ffq_table_trim_quality: qual_base is 0..255");
-    if (((reinterpret_cast<uintptr_t>(d_table) | reinterpret_cast<uintptr_t>(d_out)) & 15) != 0)
-        return fail(FFQ_E_ARG, "ffq_table_trim_quality: tables must be 16-byte aligned");
-    if (c->pend.active) return fail(FFQ_E_ARG, "ffq_table_trim_quality: a scan is pending on this context");
-    HIPCHK(hipSetDevice(c->device));
+    const int rc = rows_begin(c, "ffq_table_trim_quality", stats != nullptr, d_buf, n_bytes, d_table, n_rows, d_out);
+    if (rc) return rc;
     stats[0] = stats[1] = stats[2] = 0;
     if (n_rows == 0) return FFQ_OK;
-    int rc = grow_dev(c, c->trim_list, n_rows);
-    if (rc) return rc;
     hipStream_t st = c->stream;
-    HIPCHK(hipMemsetAsync(c->d_trim, 0, sizeof(TrimBlock), st));
-    // TRIM_WG / TRIM_G rows per workgroup and step; as many workgroups as the device holds at once, striding over the table
-    constexpr int64_t rpb = TRIM_WG / TRIM_G;
-    const int64_t nblk = std::min<int64_t>((n_rows + rpb - 1) / rpb, 2048);
-    hipLaunchKernelGGL(k_trim_rows, dim3((unsigned)nblk), dim3(TRIM_WG), 0, st, d_buf, n_bytes, sentinel ? 1 : 0, add, d_table,
-                       n_rows, qual_base, cutoff_front, cutoff_back, d_out, c->trim_list, c->d_trim);
-    // the rows it left (above TRIM_LONG quality bytes; their number is known on the device only): a wave each
-    const int64_t nblk_long = std::min<int64_t>((n_rows + 3) / 4, 1024);
-    hipLaunchKernelGGL(k_trim_long, dim3((unsigned)nblk_long), dim3(TRIM_WG), 0, st, d_buf, n_bytes, sentinel ? 1 : 0, add,
-                       d_table, qual_base, cutoff_front, cutoff_back, d_out, (const int64_t *)c->trim_list, c->d_trim);
-    HIPCHK(hipMemcpyAsync(c->h_trim, c->d_trim, sizeof(TrimBlock), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-    stats[0] = (int64_t)c->h_trim->changed; stats[1] = (int64_t)c->h_trim->removed; stats[2] = (int64_t)c->h_trim->skipped;
-    return FFQ_OK;
+    hipLaunchKernelGGL(k_trim_rows, dim3(rows_grid(n_rows, TRIM_WG / ROWS_G, EDIT_GRID_SHORT)), dim3(TRIM_WG), 0, st, d_buf, n_bytes,
+                       sentinel ? 1 : 0, add, d_table, n_rows, qual_base, cutoff_front, cutoff_back, d_out, c->rows_list, c->d_rows);
+    hipLaunchKernelGGL(k_trim_long, dim3(rows_grid(n_rows, TRIM_WG / 64, EDIT_GRID_LONG)), dim3(TRIM_WG), 0, st, d_buf, n_bytes,
+                       sentinel ? 1 : 0, add, d_table, qual_base, cutoff_front, cutoff_back, d_out, (const int64_t *)c->rows_list,
+                       c->d_rows);
+    return rows_end(c, stats);
 }
 
-// ---- 3' adapter trimming: rows of the table edited in place (csrc/ffq_adapter.h) --------------
 // parameters of an adapter call, checked; the adapter's bytes and its wildcard mask as the kernels take them
 static int adapter_arg(const char *who, const uint8_t *adapter, int adapter_len, int err_permille, int min_overlap, AdapterArg *ad)
 {
@@ -2010,38 +2032,22 @@ extern "C" int ffq_table_trim_adapter(ffq_ctx *c, const uint8_t *d_buf, int64_t 
                                       int err_permille, int min_overlap, int64_t *d_out, int64_t stats[3])
 {
     mark_other(c);
-    if (!c || !stats || n_rows < 0 || n_bytes < 0 || (n_bytes > 0 && !d_buf) || (n_rows > 0 && (!d_table || !d_out)))
-        return fail(FFQ_E_ARG, "ffq_table_trim_adapter: bad argument");
     AdapterArg ad;
     int rc = adapter_arg("ffq_table_trim_adapter", adapter, adapter_len, err_permille, min_overlap, &ad);
+    if (!rc) rc = rows_begin(c, "ffq_table_trim_adapter", stats != nullptr, d_buf, n_bytes, d_table, n_rows, d_out);
     if (rc) return rc;
-    if (((reinterpret_cast<uintptr_t>(d_table) | reinterpret_cast<uintptr_t>(d_out)) & 15) != 0)
-        return fail(FFQ_E_ARG, "ffq_table_trim_adapter: tables must be 16-byte aligned");
-    if (c->pend.active) return fail(FFQ_E_ARG, "ffq_table_trim_adapter: a scan is pending on this context");
-    HIPCHK(hipSetDevice(c->device));
     stats[0] = stats[1] = stats[2] = 0;
     if (n_rows == 0) return FFQ_OK;
-    rc = grow_dev(c, c->trim_list, n_rows);
-    if (rc) return rc;
     hipStream_t st = c->stream;
-    // (the counters and the long list are the quality trim's: calls on a context follow one another)
-    HIPCHK(hipMemsetAsync(c->d_trim, 0, sizeof(TrimBlock), st));
-    constexpr int64_t rpb = TRIM_WG / TRIM_G;
-    const int64_t nblk = std::min<int64_t>((n_rows + rpb - 1) / rpb, 2048);
-    hipLaunchKernelGGL(k_adapter_rows, dim3((unsigned)nblk), dim3(TRIM_WG), 0, st, d_buf, n_bytes, sentinel ? 1 : 0, add, d_table,
-                       n_rows, ad, adapter_len, err_permille, min_overlap, d_out, c->trim_list, c->d_trim);
-    // the rows it left (above ADAPTER_LONG bases; their number is known on the device only): a wave each
-    const int64_t nblk_long = std::min<int64_t>((n_rows + 3) / 4, 1024);
-    hipLaunchKernelGGL(k_adapter_long, dim3((unsigned)nblk_long), dim3(TRIM_WG), 0, st, d_buf, n_bytes, sentinel ? 1 : 0, add,
-                       d_table, ad, adapter_len, err_permille, min_overlap, d_out, (const int64_t *)c->trim_list, c->d_trim);
-    HIPCHK(hipMemcpyAsync(c->h_trim, c->d_trim, sizeof(TrimBlock), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-    stats[0] = (int64_t)c->h_trim->changed; stats[1] = (int64_t)c->h_trim->removed; stats[2] = (int64_t)c->h_trim->skipped;
-    return FFQ_OK;
+    hipLaunchKernelGGL(k_adapter_rows, dim3(rows_grid(n_rows, ADAPTER_WG / ROWS_G, EDIT_GRID_SHORT)), dim3(ADAPTER_WG), 0, st, d_buf,
+                       n_bytes, sentinel ? 1 : 0, add, d_table, n_rows, ad, adapter_len, err_permille, min_overlap, d_out,
+                       c->rows_list, c->d_rows);
+    hipLaunchKernelGGL(k_adapter_long, dim3(rows_grid(n_rows, ADAPTER_WG / 64, EDIT_GRID_LONG)), dim3(ADAPTER_WG), 0, st, d_buf,
+                       n_bytes, sentinel ? 1 : 0, add, d_table, ad, adapter_len, err_permille, min_overlap, d_out,
+                       (const int64_t *)c->rows_list, c->d_rows);
+    return rows_end(c, stats);
 }
 
-// ---- per-cycle base and quality statistics of a table (csrc/ffq_stats.h) ----------------------
 static_assert(STATS_QBINS == FFQ_STATS_QBINS && STATS_GCBINS == FFQ_STATS_GCBINS && STATS_HEAD == FFQ_STATS_HEAD &&
               STATS_MAX_CYCLES == FFQ_STATS_MAX_CYCLES && stats_words(150) == FFQ_STATS_WORDS(150), "include/ffq.h");
 
@@ -2050,41 +2056,25 @@ extern "C" int ffq_table_stats(ffq_ctx *c, const uint8_t *d_buf, int64_t n_bytes
                                uint64_t *d_stats, int64_t head[FFQ_STATS_HEAD])
 {
     mark_other(c);
-    if (!c || n_rows < 0 || n_bytes < 0 || (n_bytes > 0 && !d_buf) || (n_rows > 0 && !d_table))
-        return fail(FFQ_E_ARG, "ffq_table_stats: bad argument");
     if (max_cycles < 1 || max_cycles > STATS_MAX_CYCLES) return fail(FFQ_E_ARG, "ffq_table_stats: max_cycles is 1..%d", STATS_MAX_CYCLES);
     if (qual_base < 0 || qual_base > 255) return fail(FFQ_E_ARG, "ffq_table_stats: qual_base is 0..255");
-    if (!d_stats || ((reinterpret_cast<uintptr_t>(d_stats) | reinterpret_cast<uintptr_t>(d_table)) & 15) != 0)
-        return fail(FFQ_E_ARG, "ffq_table_stats: d_stats and the table must be 16-byte aligned");
-    if (c->pend.active) return fail(FFQ_E_ARG, "ffq_table_stats: a scan is pending on this context");
-    HIPCHK(hipSetDevice(c->device));
+    const int rc = rows_begin(c, "ffq_table_stats", d_stats != nullptr, d_buf, n_bytes, d_table, n_rows, d_stats);
+    if (rc) return rc;
     hipStream_t st = c->stream;
     stats_u64 *out = reinterpret_cast<stats_u64 *>(d_stats);
-    if (n_rows > 0) {
-        // (before anything is enqueued: growing the list waits for the stream)
-        int rc = grow_dev(c, c->trim_list, n_rows);
-        if (rc) return rc;
-    }
     if (!accumulate) HIPCHK(hipMemsetAsync(d_stats, 0, (size_t)stats_words(max_cycles) * 8, st));
     if (n_rows > 0) {
-        // (the long list and its counter are the quality trim's: calls on a context follow one another)
-        HIPCHK(hipMemsetAsync(c->d_trim, 0, sizeof(TrimBlock), st));
-        // 64 rows per workgroup and step; two workgroups per CU (their LDS), striding: every workgroup flushes a whole tile at its end
-        constexpr int64_t rpb = STATS_WG / STATS_G;
-        const int64_t nblk = std::min<int64_t>((n_rows + rpb - 1) / rpb, 512);
-        hipLaunchKernelGGL(k_stats_rows, dim3((unsigned)nblk), dim3(STATS_WG), 0, st, d_buf, n_bytes, sentinel ? 1 : 0, add, d_table,
-                           n_rows, qual_base, max_cycles, out, c->trim_list, c->d_trim);
-        // the rows it left (above STATS_TILE bases; their number is known on the device only): a wave each, checked
-        // and counted per read first, then per cycle tile
-        constexpr int64_t wpb = STATS_WG / 64;
-        const int64_t nblk_long = std::min<int64_t>((n_rows + wpb - 1) / wpb, 512);
-        hipLaunchKernelGGL(k_stats_long_check, dim3((unsigned)nblk_long), dim3(STATS_WG), 0, st, d_buf, n_bytes, sentinel ? 1 : 0, add,
-                           d_table, qual_base, max_cycles, out, c->trim_list, (const TrimBlock *)c->d_trim);
+        // every workgroup of the short rows' launch flushes a whole tile at its end; the rows it left are checked and counted
+        // per read first, then per cycle tile
+        hipLaunchKernelGGL(k_stats_rows, dim3(rows_grid(n_rows, STATS_WG / STATS_G, STATS_GRID_SHORT)), dim3(STATS_WG), 0, st, d_buf,
+                           n_bytes, sentinel ? 1 : 0, add, d_table, n_rows, qual_base, max_cycles, out, c->rows_list, c->d_rows);
+        hipLaunchKernelGGL(k_stats_long_check, dim3(rows_grid(n_rows, STATS_WG / 64, STATS_GRID_CHECK)), dim3(STATS_WG), 0, st, d_buf,
+                           n_bytes, sentinel ? 1 : 0, add, d_table, qual_base, max_cycles, out, c->rows_list,
+                           (const RowsBlock *)c->d_rows);
         const int n_tiles = (max_cycles + STATS_TILE - 1) / STATS_TILE;
-        const int64_t nblk_cnt = std::min<int64_t>((n_rows + wpb - 1) / wpb, 128);
-        hipLaunchKernelGGL(k_stats_long_count, dim3((unsigned)nblk_cnt, (unsigned)n_tiles), dim3(STATS_WG), 0, st, d_buf, n_bytes,
-                           sentinel ? 1 : 0, add, d_table, qual_base, max_cycles, out, (const int64_t *)c->trim_list,
-                           (const TrimBlock *)c->d_trim);
+        hipLaunchKernelGGL(k_stats_long_count, dim3(rows_grid(n_rows, STATS_WG / 64, STATS_GRID_COUNT), (unsigned)n_tiles),
+                           dim3(STATS_WG), 0, st, d_buf, n_bytes, sentinel ? 1 : 0, add, d_table, qual_base, max_cycles, out,
+                           (const int64_t *)c->rows_list, (const RowsBlock *)c->d_rows);
     }
     HIPCHK(hipGetLastError());
     if (head) {

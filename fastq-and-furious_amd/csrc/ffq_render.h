@@ -25,6 +25,7 @@
 // exceeds out_cap.
 #pragma once
 #include "ffq_kernels.h"
+#include "ffq_rows.h"
 
 namespace ffq {
 
@@ -43,13 +44,12 @@ struct RenderRow { int64_t hsrc, ssrc, qsrc, h, s, q; };
 __device__ __forceinline__ int64_t render_parse(longlong2 r01, longlong2 r23, longlong2 r45, int64_t nbytes, int s,
                                                 int64_t add, RenderRow &R)
 {
-    // buffer coordinates (wrapping arithmetic: a row may hold anything)
-    const int64_t p0 = (int64_t)((uint64_t)r01.x - (uint64_t)add), p1 = (int64_t)((uint64_t)r01.y - (uint64_t)add);
-    const int64_t p2 = (int64_t)((uint64_t)r23.x - (uint64_t)add), p3 = (int64_t)((uint64_t)r23.y - (uint64_t)add);
-    const int64_t p4 = (int64_t)((uint64_t)r45.x - (uint64_t)add), p5 = (int64_t)((uint64_t)r45.y - (uint64_t)add);
+    const int64_t p0 = row_coord(r01.x, add), p1 = row_coord(r01.y, add), p2 = row_coord(r23.x, add), p3 = row_coord(r23.y, add);
+    const int64_t p4 = row_coord(r45.x, add), p5 = row_coord(r45.y, add);
     const int64_t L = nbytes + s;
     bool ok = p0 >= 0 && p2 >= 0 && p4 >= 0 && p0 < p1 && p2 <= p3 && p4 <= p5 && p1 <= L && p3 <= L && p5 <= L;
-    // coordinate 0 of a buffer with a sentinel is the virtual '\n' (the header begins at p0 + 1 >= 1)
+    // all three lines are read, so none with a byte in it may begin at the virtual '\n' (ffq_rows.h: row_pos); the header
+    // begins at p0 + 1 >= 1
     if (s && ((p3 > p2 && p2 < s) || (p5 > p4 && p4 < s))) ok = false;
     if (!ok) { R.hsrc = R.ssrc = R.qsrc = 0; R.h = R.s = R.q = 0; return 0; }
     R.hsrc = p0 + 1 - s; R.h = p1 - p0 - 1;
@@ -253,17 +253,8 @@ __global__ __launch_bounds__(RENDER_WG) void k_render_rows(const uint8_t *__rest
             const RenderRow R = s_row[r];
             render_copy<G>(d, nbytes, R, len, out + s_off[r], gl);
         }
-        // the long rows of the wave take their places on the list with one atomic
-        const unsigned long long lm = __ballot(is_long && gl == 0);
-        if (lm) {
-            unsigned long long at = 0;
-            if (lane == 0) at = atomicAdd(&blk->n_long, (unsigned long long)__popcll(lm));
-            at = (unsigned long long)__shfl((long long)at, 0);
-            if (is_long && gl == 0) {
-                const unsigned long long e = at + __popcll(lm & ((1ull << lane) - 1ull));
-                long_list[2 * e] = r0 + r; long_list[2 * e + 1] = s_off[r];
-            }
-        }
+        const int64_t e = long_list_append(is_long && gl == 0, lane, &blk->n_long);
+        if (e >= 0) { long_list[2 * e] = r0 + r; long_list[2 * e + 1] = s_off[r]; }
     }
 }
 

@@ -4,8 +4,7 @@
 // and every global update is an integer atomicAdd, so the result does not depend on the order rows arrive in.
 //
 // Shape (it differs from the trims' in two places, both said here).  Three launches on the context's stream:
-//   k_stats_rows        a GROUP of 8 lanes owns a row, 64 rows per workgroup and step, 512 workgroups stride over the table and
-//                       ask for their next rows before they work on these (ffq_trim.h's frame).  A row of up to STATS_TILE
+//   k_stats_rows        the short rows' shape of ffq_rows.h, 64 rows per workgroup and step, 512 workgroups.  A row of up to STATS_TILE
 //                       bases is held in REGISTERS: lane gl takes dwords gl, gl + 8, ... of the sequence and of the quality
 //                       (five of either: every load of a row is in flight at once), the group looks for '\n' with one
 //                       ballot -- eligibility has to be known before the first count --, and then counts out of the
@@ -33,15 +32,14 @@
 // at most STATS_WG / STATS_G = 64 rows and flushes and clears its counters between rounds: STATS_ROUND * 64 = 2^26 < 2^32
 // whatever n_rows and the table are (static_assert below).  The head sums are 64-bit, as are the words they are added to.
 #pragma once
-#include "ffq_dev.h"
-#include "ffq_trim.h"
+#include "ffq_rows.h"
 
 namespace ffq {
 
 constexpr int STATS_QBINS = 96, STATS_GCBINS = 101, STATS_HEAD = 8, STATS_MAX_CYCLES = 4096;
 constexpr int STATS_TILE = 152;       // cycles per LDS tile; a row above it gets a wave of its own (151-base reads do not)
 constexpr int STATS_WG = 512;
-constexpr int STATS_G = 8;            // lanes per row of the short rows' kernel, a dword of either line each per step
+constexpr int STATS_G = ROWS_G;       // lanes per row of the short rows' kernel, a dword of either line each per step
 constexpr int STATS_NS = (STATS_TILE + STATS_G * 4 - 1) / (STATS_G * 4);    // dwords per lane and line: 5
 constexpr int STATS_QSTRIDE = 97;     // words between the quality counters of two cycles in LDS
 constexpr int STATS_TILE_WORDS = STATS_TILE * (5 + STATS_QSTRIDE);
@@ -59,35 +57,14 @@ typedef unsigned long long stats_u64;
 // head sums of a lane: rows counted, rows skipped, bases, bases at cycles >= C, sum of v, GC bases, bases of class 4
 struct StatsHead { stats_u64 v[7]; };
 
-// buffer coordinates of a row and whether it is eligible as far as its positions say (ffq_trim.h: trim_row)
-__device__ __forceinline__ bool stats_row_pos(int64_t nbytes, int s, int64_t add, longlong2 r23, longlong2 r45, int64_t &p2,
-                                              int64_t &p4, int64_t &n)
-{
-    p2 = (int64_t)((uint64_t)r23.x - (uint64_t)add);
-    p4 = (int64_t)((uint64_t)r45.x - (uint64_t)add);
-    const int64_t p3 = (int64_t)((uint64_t)r23.y - (uint64_t)add), p5 = (int64_t)((uint64_t)r45.y - (uint64_t)add);
-    const int64_t L = nbytes + s;
-    n = p5 - p4;
-    bool elig = p2 >= 0 && p4 >= 0 && p2 <= p3 && p4 <= p5 && p3 <= L && p5 <= L && p3 - p2 == n;
-    // coordinate 0 of a buffer with a sentinel is the virtual '\n'
-    if (elig && n > 0 && (p2 < s || p4 < s)) elig = false;
-    return elig;
-}
-
 // bytes a[o .. min(o + 4, n)) as a dword, the missing ones 0; 0 <= o < n.  Reads inside a[0 .. n) only.
 __device__ __forceinline__ uint32_t stats_ld(const uint8_t *__restrict__ a, int64_t o, int64_t n)
 {
-    if (o + 4 <= n) return *reinterpret_cast<const trim_u32u *>(a + o);
-    if (n >= 4) return *reinterpret_cast<const trim_u32u *>(a + (n - 4)) >> (8 * (int)(o + 4 - n));
+    if (o + 4 <= n) return *reinterpret_cast<const rows_u32u *>(a + o);
+    if (n >= 4) return *reinterpret_cast<const rows_u32u *>(a + (n - 4)) >> (8 * (int)(o + 4 - n));
     uint32_t x = 0;
     for (int64_t j = o; j < n; j++) x |= (uint32_t)a[j] << (8 * (int)(j - o));
     return x;
-}
-
-__device__ __forceinline__ bool stats_has_nl(uint32_t x)
-{
-    x ^= 0x0A0A0A0Au;
-    return ((x - 0x01010101u) & ~x & 0x80808080u) != 0;
 }
 
 // class of a base: A a / C c / G g / T t = 0..3, any other byte 4
@@ -145,15 +122,38 @@ __device__ __forceinline__ void stats_flush_hist(uint32_t *__restrict__ s_h, int
     }
 }
 
+// the three per-read histograms (n_len bins of the first)
+__device__ __forceinline__ void stats_flush_reads(uint32_t *__restrict__ s_len, int n_len, uint32_t *__restrict__ s_rq,
+                                                  uint32_t *__restrict__ s_gc, int C, stats_u64 *__restrict__ out)
+{
+    stats_flush_hist(s_len, n_len, out + 8 + (int64_t)C * 101);
+    stats_flush_hist(s_rq, STATS_QBINS, out + 8 + (int64_t)C * 102 + 1);
+    stats_flush_hist(s_gc, STATS_GCBINS, out + 8 + (int64_t)C * 102 + 1 + STATS_QBINS);
+}
+
+// once per step of the three kernels, by every thread of the workgroup: every STATS_ROUND steps the workgroup flushes its counters (Wrap, above)
+struct StatsRound {
+    int64_t in_round = 0;
+    template <class Flush>
+    __device__ __forceinline__ void step(Flush flush)
+    {
+        if (++in_round == STATS_ROUND) {
+            in_round = 0;
+            __syncthreads();
+            flush();
+            __syncthreads();
+        }
+    }
+};
+
 // every thread of the workgroup is here: the head sums over the wave, over the waves through LDS, one set of atomics
 __device__ __forceinline__ void stats_add_head(stats_u64 *__restrict__ out, StatsHead h)
 {
     __shared__ stats_u64 s_head[STATS_WG / 64][7];
 #pragma unroll
     for (int k = 0; k < 7; k++) {
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) h.v[k] += (stats_u64)__shfl_xor((long long)h.v[k], o);
-        if ((threadIdx.x & 63) == 0) s_head[threadIdx.x >> 6][k] = h.v[k];
+        const stats_u64 t = wave_sum_u64(h.v[k]);
+        if ((threadIdx.x & 63) == 0) s_head[threadIdx.x >> 6][k] = t;
     }
     __syncthreads();
     if (threadIdx.x < 7) {
@@ -182,12 +182,13 @@ __device__ __forceinline__ void stats_read(StatsHead &h, int64_t n, int C, T sv,
 
 // (four waves per SIMD asked for: two workgroups then fit a CU -- their LDS allows it -- at the price of 128 VGPRs and a
 // spill of two dozen of them; one workgroup per CU with 157 VGPRs took 1.40 ms where this takes 1.03 on the table of DESIGN.md 4d)
+// (the strided walk is written out, as in the two trims, without pos0 / pos1: ffq_rows.h says why)
 __global__ __launch_bounds__(STATS_WG, 4) void k_stats_rows(const uint8_t *__restrict__ d, int64_t nbytes, int s, int64_t add,
                                                          const int64_t *__restrict__ table, int64_t n_rows, int qbase, int C,
                                                          stats_u64 *__restrict__ out, int64_t *__restrict__ long_list,
-                                                         TrimBlock *__restrict__ blk)
+                                                         RowsBlock *__restrict__ blk)
 {
-    constexpr int G = STATS_G, RPB = STATS_WG / G;
+    constexpr int G = STATS_G;
     __shared__ uint32_t s_tile[STATS_TILE_WORDS];
     __shared__ uint32_t s_len[STATS_TILE + 1], s_rq[STATS_QBINS], s_gc[STATS_GCBINS];
     const int lane = threadIdx.x & 63, gl = lane & (G - 1), gshift = lane & ~(G - 1), rot = (lane / G) & 3;
@@ -200,6 +201,13 @@ __global__ __launch_bounds__(STATS_WG, 4) void k_stats_rows(const uint8_t *__res
     StatsHead h;
 #pragma unroll
     for (int k = 0; k < 7; k++) h.v[k] = 0;
+    auto flush = [&] {
+        stats_flush_tile(s_tile, 0, C, out);
+        // (a row of this kernel has min(n, C) <= STATS_TILE; bins above C stay 0)
+        stats_flush_reads(s_len, min(STATS_TILE, C) + 1, s_rq, s_gc, C, out);
+    };
+    StatsRound round;
+    constexpr int RPB = STATS_WG / G;
     const int64_t step = (int64_t)gridDim.x * RPB;
     longlong2 x23 = make_longlong2(0, 0), x45 = x23;
     {
@@ -209,7 +217,6 @@ __global__ __launch_bounds__(STATS_WG, 4) void k_stats_rows(const uint8_t *__res
             x23 = src[1]; x45 = src[2];
         }
     }
-    int64_t in_round = 0;
     for (int64_t r0 = (int64_t)blockIdx.x * RPB; r0 < n_rows; r0 += step) {
         const int64_t row = r0 + (threadIdx.x / G);
         const bool have = row < n_rows;
@@ -219,7 +226,7 @@ __global__ __launch_bounds__(STATS_WG, 4) void k_stats_rows(const uint8_t *__res
             x23 = src[1]; x45 = src[2];
         }
         int64_t p2 = 0, p4 = 0, n = 0;
-        const bool elig = have && stats_row_pos(nbytes, s, add, r23, r45, p2, p4, n);
+        const bool elig = have && row_pos<true, true>(nbytes, s, add, r23, r45, p2, p4, n);
         const bool is_long = elig && n > STATS_TILE;
         const bool live = elig && !is_long;
         const uint8_t *sq = d + (p2 - s), *qq = d + (p4 - s);
@@ -233,9 +240,8 @@ __global__ __launch_bounds__(STATS_WG, 4) void k_stats_rows(const uint8_t *__res
             if (live && o < n) { xs[k] = stats_ld(sq, o, n); xq[k] = stats_ld(qq, o, n); }
         }
 #pragma unroll
-        for (int k = 0; k < STATS_NS; k++) nl |= stats_has_nl(xs[k]) || stats_has_nl(xq[k]);
-        const bool any_nl = trim_first<G>(__ballot(nl), gshift) != G;
-        const bool count = live && !any_nl;
+        for (int k = 0; k < STATS_NS; k++) nl |= has_nl(xs[k]) || has_nl(xq[k]);
+        const bool count = live && !group_any<G>(nl, gshift);
         int sv = 0, gc = 0, nn = 0;
 #pragma unroll
         for (int k = 0; k < STATS_NS; k++) {
@@ -249,44 +255,18 @@ __global__ __launch_bounds__(STATS_WG, 4) void k_stats_rows(const uint8_t *__res
             }
         }
         // (uniform over the wave: a group without a row sums zeros)
-        sv = TrimGroup<G>::sum(sv); gc = TrimGroup<G>::sum(gc); nn = TrimGroup<G>::sum(nn);
+        sv = RowGroup<G>::sum(sv); gc = RowGroup<G>::sum(gc); nn = RowGroup<G>::sum(nn);
         if (gl == 0 && have && !is_long) {
             if (count) stats_read<uint32_t>(h, n, C, (uint32_t)sv, (uint32_t)gc, (uint32_t)nn, s_len, s_rq, s_gc);
             else h.v[1]++;
         }
-        // the long rows of the wave take their places on the list with one atomic
-        const unsigned long long lm = __ballot(is_long && gl == 0);
-        if (lm) {
-            unsigned long long at = 0;
-            if (lane == 0) at = atomicAdd(&blk->n_long, (unsigned long long)__popcll(lm));
-            at = (unsigned long long)__shfl((long long)at, 0);
-            if (is_long && gl == 0) long_list[at + __popcll(lm & ((1ull << lane) - 1ull))] = row;
-        }
-        if (++in_round == STATS_ROUND) {
-            in_round = 0;
-            __syncthreads();
-            stats_flush_tile(s_tile, 0, C, out);
-            stats_flush_hist(s_len, min(STATS_TILE, C) + 1, out + 8 + (int64_t)C * 101);
-            stats_flush_hist(s_rq, STATS_QBINS, out + 8 + (int64_t)C * 102 + 1);
-            stats_flush_hist(s_gc, STATS_GCBINS, out + 8 + (int64_t)C * 102 + 1 + STATS_QBINS);
-            __syncthreads();
-        }
+        const int64_t at = long_list_append(is_long && gl == 0, lane, &blk->n_long);
+        if (at >= 0) long_list[at] = row;
+        round.step(flush);
     }
     __syncthreads();
-    stats_flush_tile(s_tile, 0, C, out);
-    // (a row of this kernel has min(n, C) <= STATS_TILE; bins above C stay 0)
-    stats_flush_hist(s_len, min(STATS_TILE, C) + 1, out + 8 + (int64_t)C * 101);
-    stats_flush_hist(s_rq, STATS_QBINS, out + 8 + (int64_t)C * 102 + 1);
-    stats_flush_hist(s_gc, STATS_GCBINS, out + 8 + (int64_t)C * 102 + 1 + STATS_QBINS);
+    flush();
     stats_add_head(out, h);
-}
-
-// 64-bit sum over the wave
-__device__ __forceinline__ stats_u64 stats_wave_sum(stats_u64 x)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) x += (stats_u64)__shfl_xor((long long)x, o);
-    return x;
 }
 
 // the rows k_stats_rows left: a wave per row walks both lines once -- '\n' anywhere makes the row ineligible (struck off
@@ -294,9 +274,8 @@ __device__ __forceinline__ stats_u64 stats_wave_sum(stats_u64 x)
 __global__ __launch_bounds__(STATS_WG) void k_stats_long_check(const uint8_t *__restrict__ d, int64_t nbytes, int s, int64_t add,
                                                                const int64_t *__restrict__ table, int qbase, int C,
                                                                stats_u64 *__restrict__ out, int64_t *__restrict__ long_list,
-                                                               const TrimBlock *__restrict__ blk)
+                                                               const RowsBlock *__restrict__ blk)
 {
-    constexpr int WPB = STATS_WG / 64;
     const int64_t n_long = (int64_t)blk->n_long;
     if (n_long == 0) return;
     __shared__ uint32_t s_len[STATS_MAX_CYCLES + 1], s_rq[STATS_QBINS], s_gc[STATS_GCBINS];
@@ -308,55 +287,42 @@ __global__ __launch_bounds__(STATS_WG) void k_stats_long_check(const uint8_t *__
     StatsHead h;
 #pragma unroll
     for (int k = 0; k < 7; k++) h.v[k] = 0;
-    int64_t in_round = 0;
-    for (int64_t j0 = (int64_t)blockIdx.x * WPB; j0 < n_long; j0 += (int64_t)gridDim.x * WPB) {
-        const int64_t j = j0 + (threadIdx.x >> 6);
-        if (j < n_long) {                                   // (uniform over the wave)
-            const int64_t row = long_list[j];
-            const longlong2 *src = reinterpret_cast<const longlong2 *>(table + row * 6);
-            int64_t p2, p4, n;
-            const bool elig = stats_row_pos(nbytes, s, add, src[1], src[2], p2, p4, n);
-            const uint8_t *sq = d + (p2 - s), *qq = d + (p4 - s);
-            bool nl = false;
-            stats_u64 sv = 0, gc = 0, nn = 0;
-            if (elig) {
-                for (int64_t o = (int64_t)lane * 4; o < n; o += 256) {
-                    const uint32_t a = stats_ld(sq, o, n), b = stats_ld(qq, o, n);
-                    nl |= stats_has_nl(a) || stats_has_nl(b);
-                    const int cnt = (int)min(n - o, (int64_t)4);
-                    int v1 = 0, g1 = 0, n1 = 0;
+    auto flush = [&] { stats_flush_reads(s_len, C + 1, s_rq, s_gc, C, out); };
+    StatsRound round;
+    for (LongRows<STATS_WG, false> it(n_long, long_list, table); it.next(); round.step(flush)) {
+        if (!it.have) continue;                             // (uniform over the wave)
+        int64_t p2, p4, n;
+        const bool elig = row_pos<true, true>(nbytes, s, add, it.r23, it.r45, p2, p4, n);
+        const uint8_t *sq = d + (p2 - s), *qq = d + (p4 - s);
+        bool nl = false;
+        stats_u64 sv = 0, gc = 0, nn = 0;
+        if (elig) {
+            for (int64_t o = (int64_t)lane * 4; o < n; o += 256) {
+                const uint32_t a = stats_ld(sq, o, n), b = stats_ld(qq, o, n);
+                nl |= has_nl(a) || has_nl(b);
+                const int cnt = (int)min(n - o, (int64_t)4);
+                int v1 = 0, g1 = 0, n1 = 0;
 #pragma unroll
-                    for (int k = 0; k < 4; k++) {
-                        if (k < cnt) {
-                            const int cls = stats_cls((a >> (8 * k)) & 0xFFu);
-                            v1 += stats_qv((b >> (8 * k)) & 0xFFu, qbase);
-                            g1 += (cls == 1 || cls == 2) ? 1 : 0;
-                            n1 += cls == 4 ? 1 : 0;
-                        }
+                for (int k = 0; k < 4; k++) {
+                    if (k < cnt) {
+                        const int cls = stats_cls((a >> (8 * k)) & 0xFFu);
+                        v1 += stats_qv((b >> (8 * k)) & 0xFFu, qbase);
+                        g1 += (cls == 1 || cls == 2) ? 1 : 0;
+                        n1 += cls == 4 ? 1 : 0;
                     }
-                    sv += (stats_u64)v1; gc += (stats_u64)g1; nn += (stats_u64)n1;
                 }
-            }
-            const bool bad = !elig || __ballot(nl) != 0;
-            sv = stats_wave_sum(sv); gc = stats_wave_sum(gc); nn = stats_wave_sum(nn);
-            if (lane == 0) {
-                if (bad) { h.v[1]++; long_list[j] = -1; }
-                else stats_read<stats_u64>(h, n, C, sv, gc, nn, s_len, s_rq, s_gc);
+                sv += (stats_u64)v1; gc += (stats_u64)g1; nn += (stats_u64)n1;
             }
         }
-        if (++in_round == STATS_ROUND) {
-            in_round = 0;
-            __syncthreads();
-            stats_flush_hist(s_len, C + 1, out + 8 + (int64_t)C * 101);
-            stats_flush_hist(s_rq, STATS_QBINS, out + 8 + (int64_t)C * 102 + 1);
-            stats_flush_hist(s_gc, STATS_GCBINS, out + 8 + (int64_t)C * 102 + 1 + STATS_QBINS);
-            __syncthreads();
+        const bool bad = !elig || __ballot(nl) != 0;
+        sv = wave_sum_u64(sv); gc = wave_sum_u64(gc); nn = wave_sum_u64(nn);
+        if (lane == 0) {
+            if (bad) { h.v[1]++; long_list[it.j] = -1; }
+            else stats_read<stats_u64>(h, n, C, sv, gc, nn, s_len, s_rq, s_gc);
         }
     }
     __syncthreads();
-    stats_flush_hist(s_len, C + 1, out + 8 + (int64_t)C * 101);
-    stats_flush_hist(s_rq, STATS_QBINS, out + 8 + (int64_t)C * 102 + 1);
-    stats_flush_hist(s_gc, STATS_GCBINS, out + 8 + (int64_t)C * 102 + 1 + STATS_QBINS);
+    flush();
     stats_add_head(out, h);
 }
 
@@ -364,9 +330,8 @@ __global__ __launch_bounds__(STATS_WG) void k_stats_long_check(const uint8_t *__
 __global__ __launch_bounds__(STATS_WG) void k_stats_long_count(const uint8_t *__restrict__ d, int64_t nbytes, int s, int64_t add,
                                                                const int64_t *__restrict__ table, int qbase, int C,
                                                                stats_u64 *__restrict__ out, const int64_t *__restrict__ long_list,
-                                                               const TrimBlock *__restrict__ blk)
+                                                               const RowsBlock *__restrict__ blk)
 {
-    constexpr int WPB = STATS_WG / 64;
     const int64_t n_long = (int64_t)blk->n_long;
     if (n_long == 0) return;
     __shared__ uint32_t s_tile[STATS_TILE_WORDS];
@@ -375,39 +340,28 @@ __global__ __launch_bounds__(STATS_WG) void k_stats_long_count(const uint8_t *__
     const int lane = threadIdx.x & 63;
     const int64_t tile_lo = (int64_t)blockIdx.y * STATS_TILE;
     const int64_t tile_hi = min(tile_lo + STATS_TILE, (int64_t)C);
-    int64_t in_round = 0;
-    for (int64_t j0 = (int64_t)blockIdx.x * WPB; j0 < n_long; j0 += (int64_t)gridDim.x * WPB) {
-        const int64_t j = j0 + (threadIdx.x >> 6);
-        const int64_t row = j < n_long ? long_list[j] : -1;
-        if (row >= 0) {
-            const longlong2 *src = reinterpret_cast<const longlong2 *>(table + row * 6);
-            int64_t p2, p4, n;
-            if (stats_row_pos(nbytes, s, add, src[1], src[2], p2, p4, n)) {
-                const uint8_t *sq = d + (p2 - s), *qq = d + (p4 - s);
-                const int64_t hi = min(n, tile_hi);
-                // (STATS_TILE is below 256: one dword per lane covers the tile)
-                const int64_t o = tile_lo + (int64_t)lane * 4;
-                if (o < hi) {
-                    // bytes behind hi but inside the row may be loaded with the dword; they are not counted
-                    const uint32_t a = stats_ld(sq, o, n), b = stats_ld(qq, o, n);
-                    const int cnt = (int)min(hi - o, (int64_t)4);
-                    int sv = 0, gc = 0, nn = 0;
+    auto flush = [&] { stats_flush_tile(s_tile, tile_lo, C, out); };
+    StatsRound round;
+    for (LongRows<STATS_WG, false> it(n_long, long_list, table); it.next(); round.step(flush)) {
+        int64_t p2 = 0, p4 = 0, n = 0;
+        if (!it.have || !row_pos<true, true>(nbytes, s, add, it.r23, it.r45, p2, p4, n)) continue;
+        const uint8_t *sq = d + (p2 - s), *qq = d + (p4 - s);
+        const int64_t hi = min(n, tile_hi);
+        // (STATS_TILE is below 256: one dword per lane covers the tile)
+        const int64_t o = tile_lo + (int64_t)lane * 4;
+        if (o < hi) {
+            // bytes behind hi but inside the row may be loaded with the dword; they are not counted
+            const uint32_t a = stats_ld(sq, o, n), b = stats_ld(qq, o, n);
+            const int cnt = (int)min(hi - o, (int64_t)4);
+            int sv = 0, gc = 0, nn = 0;
 #pragma unroll
-                    for (int k = 0; k < 4; k++)
-                        // (o + k < hi <= min(C, tile_lo + STATS_TILE))
-                        if (k < cnt) stats_count((a >> (8 * k)) & 0xFFu, (b >> (8 * k)) & 0xFFu, lane * 4 + k, true, qbase, s_tile, sv, gc, nn);
-                }
-            }
-        }
-        if (++in_round == STATS_ROUND) {
-            in_round = 0;
-            __syncthreads();
-            stats_flush_tile(s_tile, tile_lo, C, out);
-            __syncthreads();
+            for (int k = 0; k < 4; k++)
+                // (o + k < hi <= min(C, tile_lo + STATS_TILE))
+                if (k < cnt) stats_count((a >> (8 * k)) & 0xFFu, (b >> (8 * k)) & 0xFFu, lane * 4 + k, true, qbase, s_tile, sv, gc, nn);
         }
     }
     __syncthreads();
-    stats_flush_tile(s_tile, tile_lo, C, out);
+    flush();
 }
 static_assert(STATS_TILE <= 256, "k_stats_long_count: a dword per lane covers a cycle tile");
 

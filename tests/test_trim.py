@@ -312,6 +312,129 @@ def test_length_and_alignment_sweep(gpu_ctx, regime):
             assert gstats == stats, (sentinel, add)
 
 
+def table_of_quals(quals):
+    """(bytes, rows) of four-line records with these quality values (arrays of Phred scores; the sequence is all 'A')"""
+    buf, rows = bytearray(b"#"), []
+    for q in quals:
+        n = len(q)
+        p0 = len(buf)
+        buf += b"@h\n"
+        p2 = len(buf)
+        buf += b"A" * n + b"\n+\n"
+        p4 = len(buf)
+        buf += (np.asarray(q, dtype=np.int64) + 33).astype(np.uint8).tobytes() + b"\n"
+        rows.append([p0, p0 + 2, p2, p2 + n, p4, p4 + n])
+    return bytes(buf), np.array(rows, dtype=np.int64).reshape(-1, 6)
+
+
+def check_device(ctx, buf, rows, cf=20, cb=20, combos=((0, 0, False),)):
+    """the device against the loop, every row and the stats, for (sentinel, add, in place) combinations"""
+    import torch
+    want, stats = loop_rows(buf, rows, cf, cb)
+    dbuf = torch.from_numpy(np.frombuffer(buf, dtype=np.uint8).copy()).cuda()
+    for sentinel, add, in_place in combos:
+        got, gstats = device_trim(ctx, dbuf, rows + sentinel + add, cf, cb, sentinel=bool(sentinel), add=add, in_place=in_place)
+        bad = np.nonzero((got != want + sentinel + add).any(axis=1))[0]
+        assert bad.size == 0, (sentinel, add, in_place, bad[:5], (got[bad[:5]] - sentinel - add).tolist(), want[bad[:5]].tolist())
+        assert gstats == stats, (sentinel, add, in_place)
+    return want, stats
+
+
+def long_table(trimmed):
+    """40 short reads and, at rows 13 and 31, one of 5000 and one of 70 000 quality bytes; trimmed: both ends of the long ones
+    are low for more than the 1024 bytes of a chunk of the long rows' kernel, else the long ones are high throughout"""
+    rng = np.random.default_rng(42)
+    short = [rng.integers(0, 41, int(rng.integers(0, 101))) for _ in range(40)]
+    longs = []
+    for n, k in ((5000, 1100), (70000, 3000)):
+        q = rng.integers(30, 41, n)
+        if trimmed:
+            q[:k] = rng.integers(0, 6, k)
+            q[n - k:] = rng.integers(0, 6, k)
+        longs.append(q)
+    return table_of_quals(short[:13] + [longs[0]] + short[13:30] + [longs[1]] + short[30:])
+
+
+def test_long_table_cuts_by_the_loop():
+    """what test_long_reads_among_short_ones rests on, by the loop alone"""
+    for trimmed in (True, False):
+        buf, rows = long_table(trimmed)
+        assert rows.shape[0] == 42 and [int(x) for x in (rows[:, 5] - rows[:, 4])[[13, 31]]] == [5000, 70000]
+        assert ((rows[:, 5] - rows[:, 4])[[12, 14, 30, 32]] <= 100).all()
+        want, stats = loop_rows(buf, rows, 20, 20)
+        for i in (13, 31):
+            front, back = want[i][4] - rows[i][4], rows[i][5] - want[i][5]
+            if trimmed:
+                assert front > 1024 and back > 1024 and want[i][5] > want[i][4]
+            else:
+                assert front == 0 and back == 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("trimmed", (True, False))
+def test_long_reads_among_short_ones(gpu_ctx, trimmed):
+    """one read of 5000 and one of 70 000 quality bytes in a wave of short ones: either end of them is cut beyond the first
+    chunk of the long rows' kernel; and the same reads with nothing to cut"""
+    buf, rows = long_table(trimmed)
+    want, stats = check_device(gpu_ctx, buf, rows, combos=((0, 0, False), (0, 0, True), (1, 7, False), (1, 7, True)))
+    for i in (13, 31):
+        front, back = want[i][4] - rows[i][4], rows[i][5] - want[i][5]
+        assert (front > 1024 and back > 1024) if trimmed else (front == 0 and back == 0)
+
+
+def idle_table(kind):
+    """runs of 64, 65 and 300 rows that are empty (or ineligible) between ordinary rows, and 64 at the end -> (bytes, rows, idle mask)"""
+    rng = np.random.default_rng(9)
+    buf, rows = table_of_quals([rng.integers(0, 41, int(rng.integers(0, 151))) for _ in range(50)])
+    p = int(rows[0][2])
+    idle = [0, 1, p, p, p + 2, p + 2] if kind == "empty" else [0, 1, p, p + 30, -1, -1]
+    table, mask, at = [], [], 0
+    for run in (64, 65, 300):
+        table += rows[at:at + 12].tolist() + [idle] * run
+        mask += [False] * 12 + [True] * run
+        at += 12
+    table += rows[at:].tolist() + [idle] * 64
+    mask += [False] * (50 - at) + [True] * 64
+    return buf, np.array(table, dtype=np.int64), np.array(mask)
+
+
+@pytest.mark.parametrize("kind", ("empty", "ineligible"))
+def test_idle_table_by_the_loop(kind):
+    buf, table, idle = idle_table(kind)
+    want, stats = loop_rows(buf, table, 20, 20)
+    assert idle.sum() == 64 + 65 + 300 + 64 and (want[idle] == table[idle]).all()
+    assert stats[2] == (0 if kind == "empty" else idle.sum()) and stats[0] > 5
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ("empty", "ineligible"))
+def test_runs_of_rows_with_nothing_to_do(gpu_ctx, kind):
+    """runs of 64, 65 and 300 consecutive rows that are empty (or ineligible) between ordinary rows, out of place and in place"""
+    buf, table, idle = idle_table(kind)
+    want, stats = check_device(gpu_ctx, buf, table, combos=((0, 0, False), (0, 0, True)))
+    assert stats[2] == (0 if kind == "empty" else 64 + 65 + 300 + 64) and stats[0] > 5
+    if kind == "ineligible":
+        got, gstats = device_trim(gpu_ctx, buf, table, 20, 20)
+        assert got[idle].tobytes() == table[idle].tobytes() and gstats[2] == idle.sum()
+
+
+def many_rows_table():
+    """140 000 rows of very short reads drawn from 3000 different ones"""
+    rng = np.random.default_rng(3)
+    pool = [rng.integers(0, 41, int(rng.integers(0, 13))) for _ in range(3000)]
+    return table_of_quals([pool[i] for i in rng.integers(0, len(pool), 140000)])
+
+
+@pytest.mark.gpu
+def test_more_rows_than_one_pass_of_the_grid(gpu_ctx):
+    """2048 workgroups of 32 rows: 65 536 rows a pass; 140 000 rows are a second and a third step, the last one with rows for
+    some of the workgroups only"""
+    buf, rows = many_rows_table()
+    assert rows.shape[0] > 2 * 2048 * 32 and len(buf) < 6 << 20
+    want, stats = check_device(gpu_ctx, buf, rows)
+    assert stats[0] > 10000 and stats[2] == 0
+
+
 def scan_on_device(ctx, data):
     import torch
     dbuf = torch.from_numpy(np.frombuffer(data, dtype=np.uint8).copy()).cuda()
