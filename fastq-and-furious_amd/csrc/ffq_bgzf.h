@@ -1,5 +1,5 @@
-// ffq_bgzf.h -- a byte RANGE of a BGZF file inflated on its own (host code of libffq_hip.so; included by ffq_hip.hip
-// behind ffq_stream.h, whose member parser and inflate pool it uses).
+// ffq_bgzf.h -- a byte RANGE of a BGZF file inflated on its own (host code of libffq_hip.so; the member parser and the
+// inflate pool are ffq_gzread.h's).
 //
 // A BGZF file (what bgzip writes; SAM specification section 4.1) is a series of gzip members of at most 64 KiB of data
 // each, every one saying in its header how long it is (BSIZE) and in its trailer what it inflates to (ISIZE): the
@@ -12,29 +12,18 @@
 // the uncompressed stream, as for the reference's loop over gzip.open(...) (/root/reference/src/fastqandfurious.py:241-279;
 // doc/user-guide.rst opens its files that way).
 #pragma once
+#include "ffq_gzread.h"
 
 namespace bgzf_range {
 
 constexpr int64_t WINDOW = 32 << 20;          // compressed bytes read at a time
 constexpr int CHAIN = 4;                      // headers that must line up behind a candidate member start
 
-static int64_t pread_full(int fd, uint8_t *dst, int64_t n, int64_t pos)
-{
-    int64_t got = 0;
-    while (got < n) {
-        const ssize_t r = pread(fd, dst + got, (size_t)(n - got), (off_t)(pos + got));
-        if (r < 0) { if (errno == EINTR) continue; return -1; }
-        if (r == 0) break;
-        got += r;
-    }
-    return got;
-}
-
 // the member at file offset p: its total length, or 0 (not a BGZF member / not all of its header there)
 static int64_t member_at(int fd, int64_t p, int64_t size)
 {
     uint8_t h[512];
-    const int64_t n = pread_full(fd, h, std::min<int64_t>((int64_t)sizeof h, size - p), p);
+    const int64_t n = ReadPool::read_full(fd, h, std::min<int64_t>((int64_t)sizeof h, size - p), p, true);
     if (n < 18) return 0;
     int xl = 0;
     const int64_t total = bgzf_member_len(h, n, &xl);
@@ -61,16 +50,12 @@ static int64_t first_member(int fd, int64_t from, int64_t size)
     // a member is at most 64 KiB long: one starts within that distance of any byte of the file
     const int64_t span = std::min<int64_t>(size - from, 65536 + 4);
     std::vector<uint8_t> w((size_t)span);
-    if (pread_full(fd, w.data(), span, from) != span) return -1;
+    if (ReadPool::read_full(fd, w.data(), span, from, true) != span) return -1;
     for (int64_t i = 0; i + 4 <= span; i++)
         if (w[(size_t)i] == 0x1f && w[(size_t)i + 1] == 0x8b && w[(size_t)i + 2] == 8 && w[(size_t)i + 3] == 4 && chain_ok(fd, from + i, size))
             return from + i;
     return size - from <= 65536 ? size : -1;          // (the tail of the last member: nothing starts here)
 }
-
-}  // namespace bgzf_range
-
-namespace bgzf_range {
 
 // the members of a range as they are met, and their inflation side by side
 struct Walk {
@@ -79,14 +64,11 @@ struct Walk {
     int64_t out = 0, members = 0;
     std::vector<GzJob> jobs;
     GzPool *pool = nullptr;
-    z_stream own;
+    z_stream own{};
     bool own_init = false;
     int nthreads;
 
-    Walk(uint8_t *dst, int64_t cap_, int threads) : h_dst(dst), cap(cap_), nthreads(threads > 0 ? std::min(threads, 256) : gz_threads_default())
-    {
-        memset(&own, 0, sizeof own);
-    }
+    Walk(uint8_t *dst, int64_t cap_, int threads) : h_dst(dst), cap(cap_), nthreads(threads > 0 ? std::min(threads, 256) : gz_threads_default()) {}
     ~Walk()
     {
         delete pool;
@@ -185,7 +167,7 @@ extern "C" int ffq_bgzf_range(int fd, int64_t c_lo, int64_t c_hi, uint8_t *h_dst
         // one window from member start p: its whole members, those that start in front of c_hi
         const int64_t n = std::min<int64_t>(WINDOW + 65536, size - p);
         try { win.resize((size_t)n + 16); } catch (const std::bad_alloc &) { rc = fail(FFQ_E_NOMEM, "out of host memory"); break; }
-        if (pread_full(fd, win.data(), n, p) != n) { rc = fail(FFQ_E_ARG, "ffq_bgzf_range: read failed at byte %lld: %s", (long long)p, strerror(errno)); break; }
+        if (ReadPool::read_full(fd, win.data(), n, p, true) != n) { rc = fail(FFQ_E_ARG, "ffq_bgzf_range: read failed at byte %lld: %s", (long long)p, strerror(errno)); break; }
         int64_t q = 0;
         while (p + q < c_hi && q < WINDOW && !rc) {
             int64_t total = 0;

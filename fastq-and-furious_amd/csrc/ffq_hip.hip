@@ -1990,15 +1990,28 @@ static int rows_end(ffq_ctx *c, int64_t stats[3])
     return FFQ_OK;
 }
 
+// parameters of a quality trim and of a statistics call, checked: for the table calls and for the stream's setters
+static int trim_arg(const char *who, int qual_base, int cutoff_front, int cutoff_back)
+{
+    if (cutoff_front < 0 || cutoff_front > 127 || cutoff_back < 0 || cutoff_back > 127) return fail(FFQ_E_ARG, "%s: cutoffs are 0..127", who);
+    if (qual_base < 0 || qual_base > 255) return fail(FFQ_E_ARG, "%s: qual_base is 0..255", who);
+    return FFQ_OK;
+}
+
+static int stats_arg(const char *who, int qual_base, int max_cycles)
+{
+    if (max_cycles < 1 || max_cycles > FFQ_STATS_MAX_CYCLES) return fail(FFQ_E_ARG, "%s: max_cycles is 1..%d", who, FFQ_STATS_MAX_CYCLES);
+    if (qual_base < 0 || qual_base > 255) return fail(FFQ_E_ARG, "%s: qual_base is 0..255", who);
+    return FFQ_OK;
+}
+
 extern "C" int ffq_table_trim_quality(ffq_ctx *c, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
                                       const int64_t *d_table, int64_t n_rows, int qual_base, int cutoff_front,
                                       int cutoff_back, int64_t *d_out, int64_t stats[3])
 {
     mark_other(c);
-    if (cutoff_front < 0 || cutoff_front > 127 || cutoff_back < 0 || cutoff_back > 127)
-        return fail(FFQ_E_ARG, "ffq_table_trim_quality: cutoffs are 0..127");
-    if (qual_base < 0 || qual_base > 255) return fail(FFQ_E_ARG, "ffq_table_trim_quality: qual_base is 0..255");
-    const int rc = rows_begin(c, "ffq_table_trim_quality", stats != nullptr, d_buf, n_bytes, d_table, n_rows, d_out);
+    int rc = trim_arg("ffq_table_trim_quality", qual_base, cutoff_front, cutoff_back);
+    if (!rc) rc = rows_begin(c, "ffq_table_trim_quality", stats != nullptr, d_buf, n_bytes, d_table, n_rows, d_out);
     if (rc) return rc;
     stats[0] = stats[1] = stats[2] = 0;
     if (n_rows == 0) return FFQ_OK;
@@ -2056,9 +2069,8 @@ extern "C" int ffq_table_stats(ffq_ctx *c, const uint8_t *d_buf, int64_t n_bytes
                                uint64_t *d_stats, int64_t head[FFQ_STATS_HEAD])
 {
     mark_other(c);
-    if (max_cycles < 1 || max_cycles > STATS_MAX_CYCLES) return fail(FFQ_E_ARG, "ffq_table_stats: max_cycles is 1..%d", STATS_MAX_CYCLES);
-    if (qual_base < 0 || qual_base > 255) return fail(FFQ_E_ARG, "ffq_table_stats: qual_base is 0..255");
-    const int rc = rows_begin(c, "ffq_table_stats", d_stats != nullptr, d_buf, n_bytes, d_table, n_rows, d_stats);
+    int rc = stats_arg("ffq_table_stats", qual_base, max_cycles);
+    if (!rc) rc = rows_begin(c, "ffq_table_stats", d_stats != nullptr, d_buf, n_bytes, d_table, n_rows, d_stats);
     if (rc) return rc;
     hipStream_t st = c->stream;
     stats_u64 *out = reinterpret_cast<stats_u64 *>(d_stats);
@@ -2286,6 +2298,7 @@ extern "C" int ffq_selftest(ffq_ctx *c)
     return FFQ_OK;
 }
 
+#include "ffq_gzread.h"
 #include "ffq_stream.h"
 #include "ffq_bgzf.h"
 #include "ffq_shard.h"

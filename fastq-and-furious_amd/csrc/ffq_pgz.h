@@ -4,7 +4,7 @@
 // (/root/reference/src/fastqandfurious.py:282-334; its benchmark input is a gzip FASTQ,
 // /root/reference/doc/performance.rst:21-22), and a plain `gzip` file is ONE deflate stream: zlib
 // inflates it at ~0.33 GB/s on one core, which is what the iterator over such a file was bound by
-// (BGZF members carry their own length and were already inflated side by side: ffq_stream.h).
+// (BGZF members carry their own length and were already inflated side by side: ffq_gzread.h).
 //
 // A deflate stream can be entered at any BLOCK boundary if one accepts not knowing the 32 KiB in
 // front of it: the compressed bytes of a batch are cut into chunks, chunk 0 starts where the last
@@ -21,7 +21,7 @@
 // zlib keeps the last word: the engine commits output batch by batch, and whatever it does not
 // understand -- a chunk-0 decode error, no progress, a block too long for its buffers, the end of the
 // file inside a block -- makes it give up AT THE LAST COMMITTED BLOCK BOUNDARY (bit position, window,
-// running CRC and length), from where the serial zlib inflate of ffq_stream.h goes on (inflatePrime +
+// running CRC and length), from where the serial zlib inflate of ffq_gzread.h goes on (inflatePrime +
 // inflateSetDictionary on a raw stream) and says what is wrong with the file in its own words.
 #pragma once
 #include <zlib.h>

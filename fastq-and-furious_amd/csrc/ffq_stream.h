@@ -24,29 +24,20 @@
 //   a descriptor        the feeder thread: pread in parallel slices (regular files), or read()
 //                       behind poll() (pipes: interruptible, and a chunk is handed over short when
 //                       nothing more has arrived for a while -- a short chunk is not the end)
-//   a gzip descriptor   the feeder thread inflates (zlib; concatenated members) straight into the
-//                       pinned slot: decompression is the feeder stage, no interpreter involved
+//   a gzip descriptor   the feeder thread inflates (GzReader, ffq_gzread.h; concatenated members) straight into
+//                       the pinned slot: decompression is the feeder stage, no interpreter involved
 //                       (reference: FORMAT_OPENERS / automagic_open, fastqandfurious.py:282-334)
 //   pushed chunks       no feeder thread: the host writes every chunk into the slot's pinned memory
 //                       itself (ffq_stream_push_buffer / ffq_stream_push) -- any Python file-like
 //                       object (BytesIO, bz2, lzma ...) read with readinto(), no bytes copy
 #pragma once
-#include <errno.h>
-#include <poll.h>
-#include <unistd.h>
-#include <zlib.h>
-#include <memory>
-#include <sys/stat.h>
+#include "ffq_gzread.h"
 
-#include "ffq_pgz.h"
-
-#include <atomic>
 #include <chrono>
 #include <condition_variable>
-#include <deque>
+#include <memory>
 #include <mutex>
 #include <thread>
-#include <vector>
 
 #ifndef FFQ_STREAM_SLOTS
 #define FFQ_STREAM_SLOTS 3
@@ -132,164 +123,14 @@ static hipError_t stream_copy_chunk(StreamBufs *b, StreamSlot &sl, int64_t got)
 }
 
 constexpr int SRC_FD = 0, SRC_GZIP = 1, SRC_PUSH = 2;
-constexpr int64_t GZ_IN = 4 << 20;      // compressed bytes held at a time
-
-// ---- BGZF members inflated side by side ------------------------------------------------------------
-// A gzip member says how long it is only if its writer put that into the header: bgzip does (the "BC"
-// extra field of the BGZF format, SAM specification section 4.1: BSIZE = length of the member - 1, at
-// most 64 KiB of data per member, the uncompressed length in the member's last four bytes).  Members of
-// such a file are found without inflating anything and inflated independently, each straight into its
-// place in the pinned chunk.  Anything else -- and any member that does not hold what its header and
-// trailer promise -- goes through the one-member-at-a-time inflate below, which has the last word.
-struct GzJob {
-    const uint8_t *src;     // raw deflate data of the member
-    uint32_t clen;
-    uint8_t *dst;
-    uint32_t isize, crc;    // from the member's trailer
-};
-
-struct GzPool {
-    std::vector<std::thread> th;
-    std::mutex m;
-    std::condition_variable cv_go, cv_done;
-    const GzJob *jobs = nullptr;
-    int njobs = 0, active = 0;
-    std::atomic<int> next{0}, failed{0};
-    uint64_t gen = 0;
-    bool quit = false;
-
-    static bool inflate_one(z_stream *z, const GzJob &j)
-    {
-        uint8_t none[8];
-        if (inflateReset(z) != Z_OK) return false;
-        z->next_in = const_cast<Bytef *>(j.src);
-        z->avail_in = j.clen;
-        z->next_out = j.isize ? j.dst : none;
-        z->avail_out = j.isize ? j.isize : (uInt)sizeof none;
-        const int r = inflate(z, Z_FINISH);
-        if (r != Z_STREAM_END || z->avail_in != 0 || z->total_out != j.isize) return false;
-        return (uint32_t)crc32(crc32(0L, Z_NULL, 0), j.dst, j.isize) == j.crc;
-    }
-    // The same member through this build's own decoder (ffq_pgz.h; about twice zlib's rate on FASTQ), into a scratch
-    // buffer of the thread (a match is copied a word at a time: the bytes behind a member's end belong to the next
-    // member, which another thread is writing); whatever it does not like is zlib's (inflate_one).
-    struct Scratch { pgz::Inflater<uint8_t> inf; std::vector<uint8_t> buf; };
-    static bool inflate_fast(const GzJob &j)
-    {
-        thread_local std::unique_ptr<Scratch> sc;
-        try {
-            if (!sc) sc.reset(new Scratch());
-            const int64_t cap = (int64_t)j.isize + pgz::OUT_SLACK + 8;
-            if ((int64_t)sc->buf.size() < cap) sc->buf.resize((size_t)cap);
-        } catch (const std::bad_alloc &) { return false; }
-        pgz::Inflater<uint8_t> &f = sc->inf;
-        f.win_valid = 0;
-        f.limit_bit = INT64_MAX;
-        f.set_out(sc->buf.data(), 0, (int64_t)j.isize + pgz::OUT_SLACK + 8);
-        f.start(j.src, j.clen, 0);
-        if (f.run() != pgz::R_FINAL || f.b_out != (int64_t)j.isize || ((f.b_bit + 7) >> 3) != (int64_t)j.clen) return false;
-        if ((uint32_t)crc32(crc32(0L, Z_NULL, 0), sc->buf.data(), j.isize) != j.crc) return false;
-        memcpy(j.dst, sc->buf.data(), j.isize);
-        return true;
-    }
-    void work(z_stream *z)
-    {
-        for (;;) {
-            const int j = next.fetch_add(1);
-            if (j >= njobs) break;
-            if (!inflate_fast(jobs[j]) && !inflate_one(z, jobs[j])) failed.store(1);
-        }
-    }
-    void worker()
-    {
-        z_stream z;
-        memset(&z, 0, sizeof z);
-        const bool ok = inflateInit2(&z, -15) == Z_OK;      // raw deflate: header and trailer are read by the parser
-        uint64_t seen = 0;
-        for (;;) {
-            {
-                std::unique_lock<std::mutex> lk(m);
-                cv_go.wait(lk, [&] { return quit || gen != seen; });
-                if (quit) break;
-                seen = gen;
-            }
-            if (ok) work(&z);
-            std::lock_guard<std::mutex> lk(m);
-            if (--active == 0) cv_done.notify_one();
-        }
-        if (ok) (void)inflateEnd(&z);
-    }
-    bool start(int nthreads)
-    {
-        try {
-            for (int i = 0; i < nthreads; i++) th.emplace_back(&GzPool::worker, this);
-        } catch (...) {}
-        return !th.empty();
-    }
-    // all jobs, by the pool's threads and the caller's (own: the caller's raw-deflate state); false: a member
-    // did not inflate to what its trailer says
-    bool run(const GzJob *js, int n, z_stream *own)
-    {
-        {
-            std::lock_guard<std::mutex> lk(m);
-            jobs = js; njobs = n; next.store(0); failed.store(0);
-            active = (int)th.size();
-            gen++;
-        }
-        cv_go.notify_all();
-        work(own);
-        std::unique_lock<std::mutex> lk(m);
-        cv_done.wait(lk, [&] { return active == 0; });
-        return failed.load() == 0;
-    }
-    ~GzPool()
-    {
-        { std::lock_guard<std::mutex> lk(m); quit = true; }
-        cv_go.notify_all();
-        for (auto &t : th) t.join();
-    }
-};
-
-// threads that inflate (FFQ_GZ_THREADS; default: this process's share of the host's cores -- cores / LOCAL_WORLD_SIZE
-// when a launcher runs one rank per GPU --, at most 32): 1 = no pool
-static int gz_threads_default()
-{
-    const char *e = getenv("FFQ_GZ_THREADS");
-    if (e && atoi(e) > 0) return std::min(atoi(e), 256);
-    unsigned hw = std::max<unsigned>(std::thread::hardware_concurrency(), 1u);
-    const char *lw = getenv("LOCAL_WORLD_SIZE");
-    if (lw && atoi(lw) > 1) hw = std::max<unsigned>(hw / (unsigned)atoi(lw), 1u);
-    return (int)std::min<unsigned>(hw, 32u);
-}
 
 struct ffq_stream {
     ffq_ctx *c = nullptr;
     StreamBufs *b = nullptr;
-    int fd = -1;
-    int src = SRC_FD;
+    int fd = -1, src = SRC_FD;
     bool seekable = false;
-    // ---- gzip source (feeder thread only) ----
-    z_stream zs;
-    bool z_init = false, z_member = false, z_in_eof = false;
-    uint8_t *zin = nullptr;
-    int64_t zin_len = 0, zin_pos = 0, z_filepos = 0;
-    std::string z_msg;
-    int gz_threads = 1;                 // > 1: BGZF members are inflated side by side
-    bool bgzf_ok = true;                // cleared when a member did not hold what it promised: one at a time from there
-    GzPool *gz_pool = nullptr;
-    z_stream zraw;                      // the reader thread's own raw-deflate state (it takes jobs too)
-    bool zraw_init = false;
-    std::vector<GzJob> gz_jobs;
-    int64_t bgzf_members = 0;           // members inflated by the pool (statistics)
-    // one member inflated by several threads (ffq_pgz.h: a regular file that is not BGZF), and zlib going on from
-    // the block boundary the engine gave up at
-    pgz::Engine *pgz = nullptr;
-    bool pgz_ok = true, pgz_active = false;
-    int pgz_small = 0;
-    int64_t pgz_member_off = 0, gz_file_size = -1;
-    bool z_raw = false;                 // zs is a raw deflate stream: the member's trailer is checked here
-    uint32_t z_crc = 0;
-    uint64_t z_isize = 0;
+    std::unique_ptr<GzReader> gz;       // SRC_GZIP: the inflating source (feeder thread only)
+    Interrupt irq = {nullptr, nullptr}; // what the feeder's blocking reads ask: stream_asked
     int64_t handed_pos = 0;             // position of the source behind the last chunk handed out
     uint32_t flags = 0;                 // FFQ_F_DECODE_QUAL: qualities decoded per fill
     int qual_add = -33;
@@ -311,299 +152,37 @@ struct ffq_stream {
     int64_t globaloffset = -1;          // readfastq_iter :242
     int64_t last_nq = 0;
     int last_path = -1;                 // ffq_scan_result.path of the last fill's scan
-    // push-down: rows by sequence length, one component of the kept rows (ffq_stream_set_filter)
-    bool filter_on = false;
-    int64_t f_min = 0, f_max = 0;
-    int f_col = 0, f_add = 0;
-    int64_t last_scanned = 0, last_kept = 0, last_col_bytes = 0;
-    // quality trimming of every fill's table, in front of the filter (ffq_stream_set_trim)
-    bool trim_on = false;
-    int t_base = 33, t_front = 0, t_back = 0;
-    int64_t last_trim[3] = {0, 0, 0};
-    // 3' adapter trimming of every fill's table, behind the quality trim and in front of the filter (ffq_stream_set_adapter)
-    bool adapter_on = false;
-    uint8_t ad_bytes[64] = {0};
-    int ad_len = 0, ad_err = 0, ad_overlap = 0;
-    int64_t last_adapter[3] = {0, 0, 0};
     // statistics of every fill's table, summed over the fills on the device (ffq_stream_set_stats): the IN block, the OUT block
-    int stats_which = 0, st_base = 33, st_cycles = 0;
-    DevBuf<uint64_t> stats_d;
+    struct { int which = 0, base = 33, cycles = 0; DevBuf<uint64_t> d; } stats;
+    // quality trimming of every fill's table, in front of the filter (ffq_stream_set_trim)
+    struct { bool on = false; int base = 33, front = 0, back = 0; int64_t last[3] = {0, 0, 0}; } trim;
+    // 3' adapter trimming of every fill's table, behind the quality trim and in front of the filter (ffq_stream_set_adapter)
+    struct { bool on = false; uint8_t bytes[64] = {0}; int len = 0, err = 0, overlap = 0; int64_t last[3] = {0, 0, 0}; } adapter;
+    // push-down: rows by sequence length, one component of the kept rows (ffq_stream_set_filter)
+    struct { bool on = false; int64_t min = 0, max = 0; int col = 0, add = 0; int64_t scanned = 0, col_bytes = 0; } filter;
     // FASTQ text of every fill's table, behind the trim and the filter (ffq_stream_set_render)
-    bool render_on = false;
-    int64_t last_render[3] = {0, 0, 0};
+    struct { bool on = false; int64_t last[3] = {0, 0, 0}; } render;
     // FFQ_STREAM_PROF=1: where the time of a stream goes (printed when it closes)
     bool prof = false;
     double t_read = 0, t_slot = 0, t_feed = 0, t_scan = 0, t_rows = 0, t_copy = 0;
 };
+
+// has the caller asked the feeder to stop -- or_park: or to park (stream_grow_room)?
+static bool stream_asked(void *owner, bool or_park)
+{
+    ffq_stream *s = static_cast<ffq_stream *>(owner);
+    std::lock_guard<std::mutex> lk(s->m);
+    return s->stop || (or_park && s->pause_req);
+}
 
 static inline double stream_now()
 {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-// One chunk from a descriptor that cannot seek (a pipe, a socket): read() behind poll(), so that a
-// request to stop or to park (stream_grow_room) is seen within 50 ms even when the writer keeps the
-// pipe open and idle.  Returns the bytes read; *eof: read() returned 0.  A chunk is handed over SHORT
-// (not eof) when something was read and then nothing arrived for 50 ms, or a pause was asked for:
-// records reach the caller as they come in.  -2: asked to stop / park before anything was read.
-// -1: error (errno).
-static int64_t stream_fd_read(ffq_stream *s, uint8_t *dst, int64_t n, bool *eof)
-{
-    int64_t got = 0;
-    *eof = false;
-    while (got < n) {
-        bool stop, pause;
-        { std::lock_guard<std::mutex> lk(s->m); stop = s->stop; pause = s->pause_req; }
-        if (stop || pause) return got > 0 ? got : -2;
-        struct pollfd pf = {s->fd, POLLIN, 0};
-        const int pr = poll(&pf, 1, 50);
-        if (pr < 0) { if (errno == EINTR) continue; return -1; }
-        if (pr == 0) { if (got > 0) return got; continue; }
-        const ssize_t r = read(s->fd, dst + got, (size_t)(n - got));
-        if (r < 0) { if (errno == EINTR || errno == EAGAIN) continue; return -1; }
-        if (r == 0) { *eof = true; break; }
-        got += r;
-    }
-    return got;
-}
-
-// One chunk of the DECOMPRESSED stream of a gzip file (RFC 1952; members may be concatenated, as
-// bgzip and `cat a.gz b.gz` produce them; zero padding behind the last member is ignored).  Fills
-// dst completely unless the stream ends (*eof).  -1: error, s->z_msg says what.
-// More compressed bytes behind what is left in zin (moved to the front).  1: something was added, 0: nothing
-// (end of the file, or zin is full), -1: error (z_msg), -2: asked to stop / park with nothing read.
-static int gz_more_input(ffq_stream *s)
-{
-    const int64_t rem = s->zin_len - s->zin_pos;
-    if (s->z_in_eof || rem >= GZ_IN) return 0;
-    if (rem > 0 && s->zin_pos > 0) memmove(s->zin, s->zin + s->zin_pos, (size_t)rem);
-    s->zin_pos = 0; s->zin_len = rem;
-    int64_t r;
-    bool in_eof = false;
-    if (s->seekable) { r = ReadPool::read_full(s->fd, s->zin + rem, GZ_IN - rem, s->z_filepos, true); in_eof = r >= 0 && r < GZ_IN - rem; }
-    else {
-        // a pipe: behind poll(), like the uncompressed case (a stop request is seen within 50 ms)
-        r = stream_fd_read(s, s->zin + rem, GZ_IN - rem, &in_eof);
-        if (r == -2) return -2;
-    }
-    if (r < 0) { s->z_msg = std::string("read failed: ") + strerror(errno); return -1; }
-    s->z_filepos += r;
-    s->zin_len += r;
-    if (in_eof) s->z_in_eof = true;
-    return r > 0 ? 1 : 0;
-}
-
-// Length of the BGZF member at p; 0: not one; -1: its header is not all there yet.  A BGZF member: gzip magic,
-// deflate, FLG = FEXTRA alone, a "BC" subfield of two bytes.  *xlen: length of the extra field.
-static int64_t bgzf_member_len(const uint8_t *p, int64_t avail, int *xlen)
-{
-    if (avail >= 4 && !(p[0] == 0x1f && p[1] == 0x8b && p[2] == 8 && p[3] == 4)) return 0;
-    if (avail < 12) return -1;
-    const int xl = p[10] | (p[11] << 8);
-    if (avail < 12 + xl) return -1;
-    for (int q = 0; q + 4 <= xl;) {
-        const uint8_t *f = p + 12 + q;
-        const int sl = f[2] | (f[3] << 8);
-        if (f[0] == 'B' && f[1] == 'C' && sl == 2 && q + 6 <= xl) {
-            const int64_t total = (int64_t)(f[4] | (f[5] << 8)) + 1;
-            *xlen = xl;
-            return total >= xl + 20 ? total : 0;
-        }
-        q += 4 + sl;
-    }
-    return 0;
-}
-
-// At a member boundary: as many whole BGZF members as zin holds and dst has room for, inflated side by side.
-// Returns the bytes written (zin_pos is behind those members then), 0 if there is nothing to do here (not
-// BGZF, a member that is not all there at the end of the file, no room for even one: the serial inflate
-// takes it from the same place), -1 / -2 as gz_more_input.
-static int64_t gz_bgzf_batch(ffq_stream *s, uint8_t *dst, int64_t room)
-{
-    int xl = 0;
-    for (;;) {        // the first member whole in zin
-        const int64_t avail = s->zin_len - s->zin_pos;
-        const int64_t total = bgzf_member_len(s->zin + s->zin_pos, avail, &xl);
-        if (total == 0) return 0;
-        if (total > 0 && total <= avail) break;
-        const int r = gz_more_input(s);
-        if (r <= 0) return r;
-    }
-    std::vector<GzJob> &jobs = s->gz_jobs;
-    jobs.clear();
-    int64_t p = s->zin_pos, out = 0;
-    while (p < s->zin_len) {
-        const int64_t total = bgzf_member_len(s->zin + p, s->zin_len - p, &xl);
-        if (total <= 0 || total > s->zin_len - p) break;
-        const uint8_t *e = s->zin + p + total;
-        const uint32_t crc = (uint32_t)e[-8] | ((uint32_t)e[-7] << 8) | ((uint32_t)e[-6] << 16) | ((uint32_t)e[-5] << 24);
-        const uint32_t isz = (uint32_t)e[-4] | ((uint32_t)e[-3] << 8) | ((uint32_t)e[-2] << 16) | ((uint32_t)e[-1] << 24);
-        if ((int64_t)isz > room - out) break;
-        jobs.push_back(GzJob{s->zin + p + 12 + xl, (uint32_t)(total - xl - 20), dst + out, isz, crc});
-        out += isz;
-        p += total;
-    }
-    if (jobs.size() < 2) return 0;            // (one member: the serial inflate is as good)
-    if (!s->gz_pool) {
-        s->gz_pool = new (std::nothrow) GzPool();
-        if (!s->gz_pool || !s->gz_pool->start(s->gz_threads - 1)) { delete s->gz_pool; s->gz_pool = nullptr; s->bgzf_ok = false; return 0; }
-    }
-    if (!s->zraw_init) {
-        memset(&s->zraw, 0, sizeof s->zraw);
-        if (inflateInit2(&s->zraw, -15) != Z_OK) { s->bgzf_ok = false; return 0; }
-        s->zraw_init = true;
-    }
-    if (!s->gz_pool->run(jobs.data(), (int)jobs.size(), &s->zraw)) { s->bgzf_ok = false; return 0; }
-    s->bgzf_members += (int64_t)jobs.size();
-    s->zin_pos = p;
-    return out;
-}
-
-// The compressed input goes on at file offset `off` (what zin held is dropped).
-static void gz_reposition(ffq_stream *s, int64_t off)
-{
-    s->z_filepos = off;
-    s->zin_len = s->zin_pos = 0;
-    s->z_in_eof = s->gz_file_size >= 0 && off >= s->gz_file_size;
-}
-
-// At a member boundary of a regular file: the member is handed to the several-thread engine if enough of the file
-// lies behind it to be worth a batch (FFQ_PGZ_MIN compressed bytes, default 4 MiB).  false: zlib takes the member.
-static bool gz_pgz_begin(ffq_stream *s)
-{
-    if (s->gz_file_size < 0) {
-        struct stat st;
-        if (fstat(s->fd, &st) != 0 || !S_ISREG(st.st_mode)) { s->pgz_ok = false; return false; }
-        s->gz_file_size = (int64_t)st.st_size;
-    }
-    int xl = 0;
-    if (bgzf_member_len(s->zin + s->zin_pos, s->zin_len - s->zin_pos, &xl) != 0) return false;      // (a BGZF member: 64 KiB at most)
-    const int64_t member_off = s->z_filepos - (s->zin_len - s->zin_pos);
-    if (s->gz_file_size - member_off < pgz::env_i64("FFQ_PGZ_MIN", 4 << 20)) return false;
-    if (!s->pgz) {
-        s->pgz = new (std::nothrow) pgz::Engine();
-        if (!s->pgz || !s->pgz->init(s->fd, s->gz_threads, s->gz_file_size)) { delete s->pgz; s->pgz = nullptr; s->pgz_ok = false; return false; }
-    }
-    if (!s->pgz->begin(member_off)) return false;
-    s->pgz_member_off = member_off;
-    s->pgz_active = true;
-    return true;
-}
-
-// The engine gave up at a block boundary: zlib goes on from that bit with the window the engine holds, as a raw
-// deflate stream; the CRC-32 and the length run on here and are compared with the trailer (gz_raw_trailer).
-static bool gz_handoff(ffq_stream *s)
-{
-    pgz::Engine &e = *s->pgz;
-    if (inflateReset2(&s->zs, -15) != Z_OK) { s->z_msg = "inflateReset failed"; return false; }
-    if (e.win_valid > 0 && inflateSetDictionary(&s->zs, e.window + pgz::WSIZE - e.win_valid, (uInt)e.win_valid) != Z_OK) {
-        s->z_msg = "inflateSetDictionary failed";
-        return false;
-    }
-    int64_t byte = e.pos_bit >> 3;
-    const int r = (int)(e.pos_bit & 7);
-    if (r) {
-        uint8_t b = 0;
-        if (e.pread_full(&b, 1, byte) != 1) { s->z_msg = "compressed file ended before the end-of-stream marker was reached"; return false; }
-        if (inflatePrime(&s->zs, 8 - r, b >> r) != Z_OK) { s->z_msg = "inflatePrime failed"; return false; }
-        byte++;
-    }
-    gz_reposition(s, byte);
-    s->z_raw = true; s->z_crc = e.crc; s->z_isize = e.isize;
-    s->z_member = true;
-    return true;
-}
-
-static bool gz_raw_trailer(ffq_stream *s)
-{
-    while (s->zin_len - s->zin_pos < 8) {
-        if (s->z_in_eof) { s->z_msg = "compressed file ended before the end-of-stream marker was reached"; return false; }
-        if (gz_more_input(s) < 0) return false;
-    }
-    const uint8_t *t = s->zin + s->zin_pos;
-    const uint32_t fcrc = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
-    const uint32_t flen = (uint32_t)t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) | ((uint32_t)t[7] << 24);
-    s->zin_pos += 8;
-    s->z_raw = false;
-    if (fcrc != s->z_crc) { s->z_msg = "incorrect data check"; return false; }
-    if (flen != (uint32_t)s->z_isize) { s->z_msg = "incorrect length check"; return false; }
-    return true;
-}
-
-static int64_t stream_gz_read(ffq_stream *s, uint8_t *dst, int64_t n, bool *eof)
-{
-    int64_t got = 0;
-    *eof = false;
-    while (got < n) {
-        { std::lock_guard<std::mutex> lk(s->m); if (s->stop) break; }
-        if (s->pgz_active) {
-            got += s->pgz->read(dst + got, n - got);
-            if (s->pgz->pending()) continue;                           // (the chunk is full)
-            if (s->pgz->failed) { s->z_msg = s->pgz->msg; return -1; }
-            if (s->pgz->member_done) {
-                s->pgz_active = false;
-                if (s->pgz->end_off - s->pgz_member_off < (2 << 20) && ++s->pgz_small >= 4) s->pgz_ok = false;   // (a file of small members)
-                gz_reposition(s, s->pgz->end_off);
-            } else if (s->pgz->gave_up) {
-                s->pgz_active = false;
-                if (!gz_handoff(s)) return -1;
-            }
-            continue;
-        }
-        if (s->zin_pos == s->zin_len && !s->z_in_eof) {
-            const int r = gz_more_input(s);
-            if (r == -2) break;                                  // asked to stop / park with nothing read
-            if (r < 0) return -1;
-        }
-        if (!s->z_member) {
-            // between members: zero padding, then the next member or the end of the file
-            while (s->zin_pos < s->zin_len && s->zin[s->zin_pos] == 0) s->zin_pos++;
-            if (s->zin_pos == s->zin_len) {
-                if (s->z_in_eof) { *eof = true; break; }
-                continue;
-            }
-            if (s->gz_threads > 1 && s->bgzf_ok) {
-                const int64_t r = gz_bgzf_batch(s, dst + got, n - got);
-                if (r == -2) break;
-                if (r < 0) return -1;
-                if (r > 0) { got += r; continue; }
-            }
-            if (s->gz_threads > 1 && s->seekable && s->pgz_ok && gz_pgz_begin(s)) continue;
-            if (inflateReset2(&s->zs, 15 + 16) != Z_OK) { s->z_msg = "inflateReset failed"; return -1; }
-            s->z_member = true;
-        } else if (s->zin_pos == s->zin_len && s->z_in_eof) {
-            s->z_msg = "compressed file ended before the end-of-stream marker was reached";
-            return -1;
-        }
-        s->zs.next_in = s->zin + s->zin_pos;
-        s->zs.avail_in = (uInt)(s->zin_len - s->zin_pos);
-        s->zs.next_out = dst + got;
-        s->zs.avail_out = (uInt)std::min<int64_t>(n - got, 1 << 30);
-        const uInt out0 = s->zs.avail_out;
-        const int zr = inflate(&s->zs, Z_NO_FLUSH);
-        s->zin_pos = s->zin_len - (int64_t)s->zs.avail_in;
-        if (s->z_raw) {
-            const int64_t made = (int64_t)(out0 - s->zs.avail_out);
-            s->z_crc = (uint32_t)crc32(s->z_crc, dst + got, (uInt)made);
-            s->z_isize += (uint64_t)made;
-        }
-        got += (int64_t)(out0 - s->zs.avail_out);
-        if (zr == Z_STREAM_END) {
-            if (s->z_raw && !gz_raw_trailer(s)) return -1;
-            s->z_member = false;
-        }
-        else if (zr != Z_OK && zr != Z_BUF_ERROR) {
-            s->z_msg = s->zs.msg ? s->zs.msg : (zr == Z_DATA_ERROR ? "not a gzip file / corrupt data" : "inflate failed");
-            return -1;
-        }
-    }
-    if (got == n && !*eof && s->zin_pos == s->zin_len && s->z_in_eof && !s->z_member) *eof = true;   // ended exactly at the chunk's end
-    return got;
-}
-
-// The feeder: queues the slices of chunk e as soon as slot e % STREAM_SLOTS is free (up to two
-// chunks being read at a time), and completes chunks in order: once the last slice of chunk p is
-// in, its H2D copy goes onto the copy stream and the caller may take it.
+// The feeder: queues the slices of chunk e as soon as slot e % STREAM_SLOTS is free (up to two chunks being read at a
+// time), and completes chunks in order: once the last slice of chunk p is in, its H2D copy goes onto the copy stream and
+// the caller may take it.
 static void stream_feeder(ffq_stream *s)
 {
     (void)hipSetDevice(s->c->device);
@@ -650,9 +229,9 @@ static void stream_feeder(ffq_stream *s)
         int64_t got;
         bool src_eof = false;
         if (s->seekable && s->src == SRC_FD) { b->pool->wait(&sl.cr); got = sl.cr.total(); src_eof = got < b->fbufsize; }
-        else if (s->src == SRC_GZIP) { got = stream_gz_read(s, sl.buf.h + b->room, b->fbufsize, &src_eof); e = p + 1; }
+        else if (s->src == SRC_GZIP) { got = s->gz->read(sl.buf.h + b->room, b->fbufsize, &src_eof); e = p + 1; }
         else {
-            got = stream_fd_read(s, sl.buf.h + b->room, b->fbufsize, &src_eof);
+            got = stream_fd_read(s->fd, &s->irq, sl.buf.h + b->room, b->fbufsize, &src_eof);
             if (got == -2) { p--; continue; }      // stop / pause asked for with nothing read yet: back to the parking loop
             e = p + 1;
         }
@@ -661,7 +240,7 @@ static void stream_feeder(ffq_stream *s)
         std::string msg;
         if (got < 0) {
             rc = FFQ_E_ARG;
-            msg = s->src == SRC_GZIP ? std::string("ffq_stream: gzip: ") + s->z_msg : std::string("ffq_stream: read failed: ") + strerror(errno);
+            msg = s->src == SRC_GZIP ? std::string("ffq_stream: gzip: ") + s->gz->msg() : std::string("ffq_stream: read failed: ") + strerror(errno);
         } else {
             sl.got = got;
             sl.eof = src_eof;
@@ -674,8 +253,7 @@ static void stream_feeder(ffq_stream *s)
             std::lock_guard<std::mutex> lk(s->m);
             if (rc) { s->feeder_rc = rc; s->feeder_msg = msg; s->feeder_done = true; }
             else {
-                s->file_pos = s->src != SRC_GZIP ? s->file_pos + got :
-                              s->pgz_active ? (s->pgz->pos_bit >> 3) : s->z_filepos - (s->zin_len - s->zin_pos);      // (inside a member the engine inflates: the block boundary it has committed)
+                s->file_pos = s->src == SRC_GZIP ? s->gz->file_pos() : s->file_pos + got;
                 sl.end_pos = s->file_pos;
                 s->produced = p + 1;
                 if (sl.eof) s->feeder_done = true;
@@ -703,11 +281,6 @@ static void stream_free(ffq_stream *s)
                         "for the reader, %.3f ms carry + scan (of which %.3f ms waiting for the chunk's copy), %.3f ms rows back\n",
                 (long long)(s->cur + 1), s->t_read * 1e3, s->t_slot * 1e3, s->t_feed * 1e3, s->t_scan * 1e3, s->t_copy * 1e3,
                 s->t_rows * 1e3);
-    if (s->z_init) (void)inflateEnd(&s->zs);
-    delete s->gz_pool;
-    delete s->pgz;
-    if (s->zraw_init) (void)inflateEnd(&s->zraw);
-    free(s->zin);
     if (s->b) {
         for (auto &st : s->b->cs) if (st) (void)hipStreamSynchronize(st);
         if (s->c->stream) (void)hipStreamSynchronize(s->c->stream);
@@ -745,38 +318,46 @@ static int stream_alloc_sel(ffq_stream *s, int64_t rows, int64_t bytes)
     StreamBufs *b = s->b;
     int rc = stream_grow(b->sel, rows * 6, "ffq_stream: no memory for %lld selected rows", rows);
     if (!rc) rc = stream_grow(b->idx, rows, "ffq_stream: no memory for %lld selected rows", rows);
-    if (!rc && s->f_col) rc = stream_grow(b->coff, rows + 1, "ffq_stream: no memory for %lld column offsets", rows);
-    if (!rc && s->f_col) rc = stream_grow(b->col, bytes, "ffq_stream: no memory for %lld column bytes", bytes);
+    if (!rc && s->filter.col) rc = stream_grow(b->coff, rows + 1, "ffq_stream: no memory for %lld column offsets", rows);
+    if (!rc && s->filter.col) rc = stream_grow(b->col, bytes, "ffq_stream: no memory for %lld column bytes", bytes);
     return rc;
 }
 
-// device / pinned buffer for the rendered text of a fill
-static int stream_alloc_render(ffq_stream *s, int64_t bytes)
-{
-    StreamBufs *b = s->b;
-    if (bytes <= b->ren.d.cap) return FFQ_OK;
-    NearGpu near(s->c);
-    return stream_grow(b->ren, bytes, "ffq_stream: no memory for %lld rendered bytes", bytes);
-}
+// One fill: chunk k in its slot behind the carry, slot bytes [start, start + len), and the ONE view of it that the scan and
+// every table pass are given: from the 16-byte aligned address below the fill's first byte (mis bytes below it); a row
+// (a stream offset) minus `add` is a coordinate of that view.
+struct Fill {
+    StreamSlot *sl;
+    int64_t start, len, mis;
+    bool eof;                    // the source ends behind this fill
+    const uint8_t *d_buf;        // sl->buf.d + start - mis
+    int64_t n, add;              // len + mis; the view's first byte as a stream offset
+};
+
+// the table the chain is at: the scan's rows at first, the kept rows behind the select
+struct Table { const int64_t *d_rows; int64_t n; };
 
 // The rows the fill hands out (trimmed and filtered, if the stream does that) as FASTQ text, on the device, and its copy
 // back enqueued.  BOUND: the rows of a fill are records of the fill that do not overlap, and a scanned record never
 // renders longer than it was -- "@header\n", "sequence\n" and "quality\n" are copied, the '+' line becomes the bare "+\n"
 // (it had at least that), a trim only takes bytes away -- except a record whose quality ends with the buffer, without a newline, which gains one
 // byte: a fill of `len` bytes renders to at most len + 1.
-static int stream_render(ffq_stream *s, const uint8_t *d_buf, int64_t len, int64_t add, const int64_t *d_rows, int64_t n)
+static int stream_render(ffq_stream *s, const Fill &f, const Table &t)
 {
     StreamBufs *b = s->b;
-    s->last_render[0] = s->last_render[1] = s->last_render[2] = 0;
-    if (n <= 0) return FFQ_OK;
-    int rc = stream_alloc_render(s, len + 64);
-    if (rc) return rc;
-    rc = ffq_table_render_fastq(s->c, d_buf, len, 0, add, d_rows, n, b->ren.d, len + 1, nullptr, s->last_render);
+    int64_t *last = s->render.last;
+    last[0] = last[1] = last[2] = 0;
+    if (t.n <= 0) return FFQ_OK;
+    int rc = FFQ_OK;
+    if (f.n + 64 > b->ren.d.cap) {
+        NearGpu near(s->c);
+        rc = stream_grow(b->ren, f.n + 64, "ffq_stream: no memory for %lld rendered bytes", f.n + 64);
+    }
+    if (!rc) rc = ffq_table_render_fastq(s->c, f.d_buf, f.n, 0, f.add, t.d_rows, t.n, b->ren.d, f.n + 1, nullptr, last);
     if (rc == FFQ_E_TABLE_FULL)
-        return fail(FFQ_E_INTERNAL, "ffq_stream: a fill of %lld bytes rendered to %lld", (long long)len, (long long)s->last_render[0]);
+        return fail(FFQ_E_INTERNAL, "ffq_stream: a fill of %lld bytes rendered to %lld", (long long)f.n, (long long)last[0]);
     if (rc) return rc;
-    if (s->last_render[0] > 0)
-        HIPCHK(hipMemcpyAsync(b->ren.h, b->ren.d, (size_t)s->last_render[0], hipMemcpyDeviceToHost, s->c->stream));
+    if (last[0] > 0) HIPCHK(hipMemcpyAsync(b->ren.h, b->ren.d, (size_t)last[0], hipMemcpyDeviceToHost, s->c->stream));
     return FFQ_OK;
 }
 
@@ -837,7 +418,7 @@ static int stream_open_impl(ffq_ctx *c, int src, int fd, int64_t fbufsize, uint3
     HIPCHK(hipSetDevice(c->device));
     ffq_stream *s = new (std::nothrow) ffq_stream();
     if (!s) return fail(FFQ_E_NOMEM, "out of host memory");
-    s->c = c; s->fd = fd; s->src = src;
+    s->c = c; s->fd = fd; s->src = src; s->irq = Interrupt{stream_asked, s};
     // (FFQ_F_SINGLE_PASS: the fill's qualities come SEGMENTED -- ffq_stream_quals -- from the pass that builds the index)
     s->flags = flags & (FFQ_F_DECODE_QUAL | ((flags & FFQ_F_DECODE_QUAL) ? FFQ_F_SINGLE_PASS : 0u)); s->qual_add = qual_add;
     s->prof = getenv("FFQ_STREAM_PROF") != nullptr;
@@ -851,15 +432,8 @@ static int stream_open_impl(ffq_ctx *c, int src, int fd, int64_t fbufsize, uint3
         s->handed_pos = s->file_pos;
     }
     if (src == SRC_GZIP) {
-        memset(&s->zs, 0, sizeof s->zs);
-        s->zin = static_cast<uint8_t *>(malloc((size_t)GZ_IN + 16));      // (+16: the decoders read whole words)
-        if (!s->zin || inflateInit2(&s->zs, 15 + 16) != Z_OK) {      // 16: gzip wrapper (header, CRC-32, length)
-            free(s->zin); delete s;
-            return fail(FFQ_E_NOMEM, "ffq_stream_open: zlib could not be initialised");
-        }
-        s->z_init = true;
-        s->z_filepos = s->file_pos;
-        s->gz_threads = gz_threads_default();
+        s->gz.reset(new (std::nothrow) GzReader(fd, s->file_pos, s->seekable, 0, &s->irq));
+        if (!s->gz || !s->gz->ok()) { delete s; return fail(FFQ_E_NOMEM, "ffq_stream_open: zlib could not be initialised"); }
     }
     StreamBufs *b = static_cast<StreamBufs *>(c->stream_cache);
     c->stream_cache = nullptr;
@@ -879,10 +453,8 @@ static int stream_open_impl(ffq_ctx *c, int src, int fd, int64_t fbufsize, uint3
         if (!rc) rc = streambufs_alloc_slots(c, b, 1 << 20);
     }
     if (!rc && !(b->pool = ctx_pool(c))) rc = fail(FFQ_E_NOMEM, "out of host memory");
-    {
-        const char *e1 = getenv("FFQ_STREAM_ONE_COPY_STREAM");                 // (measurements: 0 / 1 whatever the stream does)
-        b->one_copy_stream = e1 ? atoi(e1) != 0 : (flags & FFQ_F_DECODE_QUAL) != 0;
-    }
+    const char *e1 = getenv("FFQ_STREAM_ONE_COPY_STREAM");                 // (measurements: 0 / 1 whatever the stream does)
+    b->one_copy_stream = e1 ? atoi(e1) != 0 : (flags & FFQ_F_DECODE_QUAL) != 0;
     s->b = b;
     if (!rc) rc = stream_alloc_tab(s, fbufsize / 64 + 1024);
     if (rc) { stream_free(s); return rc; }
@@ -913,36 +485,20 @@ extern "C" int ffq_stream_open_gzip(ffq_ctx *c, int fd, int64_t fbufsize, uint32
 extern "C" int64_t ffq_gunzip_fd(int fd, uint8_t *h_dst, int64_t cap, int64_t chunk, int threads, int64_t *n_parallel_members)
 {
     if (fd < 0 || (!h_dst && cap > 0) || cap < 0 || chunk <= 0) return fail(FFQ_E_ARG, "ffq_gunzip_fd: bad argument");
-    ffq_stream *s = new (std::nothrow) ffq_stream();
-    if (!s) return fail(FFQ_E_NOMEM, "out of host memory");
-    s->fd = fd; s->src = SRC_GZIP;
     const off_t at = lseek(fd, 0, SEEK_CUR);
-    s->seekable = at != (off_t)-1;
-    s->z_filepos = s->seekable ? (int64_t)at : 0;
-    memset(&s->zs, 0, sizeof s->zs);
-    s->zin = static_cast<uint8_t *>(malloc((size_t)GZ_IN + 16));      // (+16: the decoders read whole words)
+    GzReader gz(fd, at != (off_t)-1 ? (int64_t)at : 0, at != (off_t)-1, threads, nullptr);
+    if (!gz.ok()) return fail(FFQ_E_NOMEM, "ffq_gunzip_fd: zlib could not be initialised");
     int64_t rc = FFQ_OK, got = 0;
-    if (!s->zin || inflateInit2(&s->zs, 15 + 16) != Z_OK) rc = fail(FFQ_E_NOMEM, "ffq_gunzip_fd: zlib could not be initialised");
-    else {
-        s->z_init = true;
-        s->gz_threads = threads > 0 ? std::min(threads, 256) : gz_threads_default();
-        bool eof = false;
-        uint8_t one[1];
-        while (!eof) {
-            const bool full = got == cap;
-            const int64_t r = stream_gz_read(s, full ? one : h_dst + got, full ? 1 : std::min(chunk, cap - got), &eof);
-            if (r < 0) { rc = fail(FFQ_E_ARG, "ffq_gunzip_fd: gzip: %s", s->z_msg.c_str()); break; }
-            if (full && r > 0) { rc = fail(FFQ_E_TABLE_FULL, "ffq_gunzip_fd: the file inflates to more than %lld bytes", (long long)cap); break; }
-            got += full ? 0 : r;
-        }
+    bool eof = false;
+    uint8_t one[1];
+    while (!eof) {
+        const bool full = got == cap;
+        const int64_t r = gz.read(full ? one : h_dst + got, full ? 1 : std::min(chunk, cap - got), &eof);
+        if (r < 0) { rc = fail(FFQ_E_ARG, "ffq_gunzip_fd: gzip: %s", gz.msg()); break; }
+        if (full && r > 0) { rc = fail(FFQ_E_TABLE_FULL, "ffq_gunzip_fd: the file inflates to more than %lld bytes", (long long)cap); break; }
+        got += full ? 0 : r;
     }
-    if (n_parallel_members) *n_parallel_members = s->bgzf_members;
-    if (s->z_init) (void)inflateEnd(&s->zs);
-    delete s->gz_pool;
-    delete s->pgz;
-    if (s->zraw_init) (void)inflateEnd(&s->zraw);
-    free(s->zin);
-    delete s;
+    if (n_parallel_members) *n_parallel_members = gz.parallel_members();
     return rc ? rc : got;
 }
 
@@ -1012,6 +568,21 @@ extern "C" int ffq_stream_quals(ffq_stream *s, const int8_t **h_qual, const int6
     return FFQ_OK;
 }
 
+// What the setters below share: a stage that cannot serve a stream that decodes says why (`decode_why`, behind the text
+// all three begin with), and every stage but the filter is set before the first fill.
+static const char *const DECODE_GATHERS = "; a filtered stream gathers the kept records' (column = FFQ_COL_QUALITY, value_add)";
+static const char *const DECODE_UNTRIMMED = " beside the scan, untrimmed; a filtered stream gathers the trimmed ones "
+                                            "(ffq_stream_set_filter: column = FFQ_COL_QUALITY, value_add)";
+static const char *const DECODE_TEXT = "; FASTQ text holds them as they are";
+
+static int stream_settable(ffq_stream *s, const char *who, const char *decode_why, bool fresh)
+{
+    if (decode_why && (s->flags & FFQ_F_DECODE_QUAL))
+        return fail(FFQ_E_ARG, "%s: the stream decodes every record's qualities (FFQ_F_DECODE_QUAL)%s", who, decode_why);
+    if (fresh && s->cur >= 0) return fail(FFQ_E_ARG, "%s: the stream has handed out a fill already", who);
+    return FFQ_OK;
+}
+
 // Push-down into the stream (the reference's user guide, doc/user-guide.rst:153-180: an entryfunc that looks at the read's
 // length and builds one component of the entries it keeps): from the next fill on, ffq_stream_next hands back only the rows
 // with min_seq_len <= pos3 - pos2 <= max_seq_len, in order, and -- column != 0 -- that component of every kept row as a
@@ -1020,11 +591,11 @@ extern "C" int ffq_stream_set_filter(ffq_stream *s, int64_t min_seq_len, int64_t
 {
     if (!s) return fail(FFQ_E_ARG, "ffq_stream_set_filter: NULL stream");
     if (column < 0 || column > 3) return fail(FFQ_E_ARG, "ffq_stream_set_filter: column is FFQ_COL_NONE / _HEADER / _SEQUENCE / _QUALITY");
-    if (s->flags & FFQ_F_DECODE_QUAL) return fail(FFQ_E_ARG, "ffq_stream_set_filter: the stream decodes every record's qualities (FFQ_F_DECODE_QUAL); "
-                                                              "a filtered stream gathers the kept records' (column = FFQ_COL_QUALITY, value_add)");
-    if (s->render_on && column) return fail(FFQ_E_ARG, "ffq_stream_set_filter: a stream that renders FASTQ (ffq_stream_set_render) gathers no column");
-    s->filter_on = true;
-    s->f_min = min_seq_len; s->f_max = max_seq_len; s->f_col = column; s->f_add = value_add;
+    const int rc = stream_settable(s, "ffq_stream_set_filter", DECODE_GATHERS, false);
+    if (rc) return rc;
+    if (s->render.on && column) return fail(FFQ_E_ARG, "ffq_stream_set_filter: a stream that renders FASTQ (ffq_stream_set_render) gathers no column");
+    s->filter.on = true;
+    s->filter.min = min_seq_len; s->filter.max = max_seq_len; s->filter.col = column; s->filter.add = value_add;
     return FFQ_OK;
 }
 
@@ -1034,15 +605,11 @@ extern "C" int ffq_stream_set_filter(ffq_stream *s, int64_t min_seq_len, int64_t
 extern "C" int ffq_stream_set_trim(ffq_stream *s, int qual_base, int cutoff_front, int cutoff_back)
 {
     if (!s) return fail(FFQ_E_ARG, "ffq_stream_set_trim: NULL stream");
-    if (cutoff_front < 0 || cutoff_front > 127 || cutoff_back < 0 || cutoff_back > 127)
-        return fail(FFQ_E_ARG, "ffq_stream_set_trim: cutoffs are 0..127");
-    if (qual_base < 0 || qual_base > 255) return fail(FFQ_E_ARG, "ffq_stream_set_trim: qual_base is 0..255");
-    if (s->flags & FFQ_F_DECODE_QUAL) return fail(FFQ_E_ARG, "ffq_stream_set_trim: the stream decodes every record's qualities (FFQ_F_DECODE_QUAL) "
-                                                              "beside the scan, untrimmed; a filtered stream gathers the trimmed ones "
-                                                              "(ffq_stream_set_filter: column = FFQ_COL_QUALITY, value_add)");
-    if (s->cur >= 0) return fail(FFQ_E_ARG, "ffq_stream_set_trim: the stream has handed out a fill already");
-    s->trim_on = true;
-    s->t_base = qual_base; s->t_front = cutoff_front; s->t_back = cutoff_back;
+    int rc = trim_arg("ffq_stream_set_trim", qual_base, cutoff_front, cutoff_back);
+    if (!rc) rc = stream_settable(s, "ffq_stream_set_trim", DECODE_UNTRIMMED, true);
+    if (rc) return rc;
+    s->trim.on = true;
+    s->trim.base = qual_base; s->trim.front = cutoff_front; s->trim.back = cutoff_back;
     return FFQ_OK;
 }
 
@@ -1050,8 +617,8 @@ extern "C" int ffq_stream_set_trim(ffq_stream *s, int qual_base, int cutoff_fron
 extern "C" int ffq_stream_trimmed(ffq_stream *s, int64_t stats[3])
 {
     if (!s || !stats) return fail(FFQ_E_ARG, "ffq_stream_trimmed: NULL argument");
-    if (!s->trim_on) return fail(FFQ_E_ARG, "ffq_stream_trimmed: the stream does not trim (ffq_stream_set_trim)");
-    for (int i = 0; i < 3; i++) stats[i] = s->last_trim[i];
+    if (!s->trim.on) return fail(FFQ_E_ARG, "ffq_stream_trimmed: the stream does not trim (ffq_stream_set_trim)");
+    for (int i = 0; i < 3; i++) stats[i] = s->trim.last[i];
     return FFQ_OK;
 }
 
@@ -1062,14 +629,11 @@ extern "C" int ffq_stream_set_adapter(ffq_stream *s, const uint8_t *adapter, int
 {
     if (!s) return fail(FFQ_E_ARG, "ffq_stream_set_adapter: NULL stream");
     int rc = adapter_arg("ffq_stream_set_adapter", adapter, adapter_len, err_permille, min_overlap, nullptr);
+    if (!rc) rc = stream_settable(s, "ffq_stream_set_adapter", DECODE_UNTRIMMED, true);
     if (rc) return rc;
-    if (s->flags & FFQ_F_DECODE_QUAL) return fail(FFQ_E_ARG, "ffq_stream_set_adapter: the stream decodes every record's qualities (FFQ_F_DECODE_QUAL) "
-                                                              "beside the scan, untrimmed; a filtered stream gathers the trimmed ones "
-                                                              "(ffq_stream_set_filter: column = FFQ_COL_QUALITY, value_add)");
-    if (s->cur >= 0) return fail(FFQ_E_ARG, "ffq_stream_set_adapter: the stream has handed out a fill already");
-    s->adapter_on = true;
-    memcpy(s->ad_bytes, adapter, (size_t)adapter_len);
-    s->ad_len = adapter_len; s->ad_err = err_permille; s->ad_overlap = min_overlap;
+    s->adapter.on = true;
+    memcpy(s->adapter.bytes, adapter, (size_t)adapter_len);
+    s->adapter.len = adapter_len; s->adapter.err = err_permille; s->adapter.overlap = min_overlap;
     return FFQ_OK;
 }
 
@@ -1077,8 +641,8 @@ extern "C" int ffq_stream_set_adapter(ffq_stream *s, const uint8_t *adapter, int
 extern "C" int ffq_stream_adapter_trimmed(ffq_stream *s, int64_t stats[3])
 {
     if (!s || !stats) return fail(FFQ_E_ARG, "ffq_stream_adapter_trimmed: NULL argument");
-    if (!s->adapter_on) return fail(FFQ_E_ARG, "ffq_stream_adapter_trimmed: the stream trims no adapter (ffq_stream_set_adapter)");
-    for (int i = 0; i < 3; i++) stats[i] = s->last_adapter[i];
+    if (!s->adapter.on) return fail(FFQ_E_ARG, "ffq_stream_adapter_trimmed: the stream trims no adapter (ffq_stream_set_adapter)");
+    for (int i = 0; i < 3; i++) stats[i] = s->adapter.last[i];
     return FFQ_OK;
 }
 
@@ -1089,36 +653,36 @@ extern "C" int ffq_stream_set_stats(ffq_stream *s, int which, int qual_base, int
 {
     if (!s) return fail(FFQ_E_ARG, "ffq_stream_set_stats: NULL stream");
     if (which < 1 || which > (FFQ_STATS_IN | FFQ_STATS_OUT)) return fail(FFQ_E_ARG, "ffq_stream_set_stats: which is FFQ_STATS_IN, FFQ_STATS_OUT or both");
-    if (max_cycles < 1 || max_cycles > FFQ_STATS_MAX_CYCLES) return fail(FFQ_E_ARG, "ffq_stream_set_stats: max_cycles is 1..%d", FFQ_STATS_MAX_CYCLES);
-    if (qual_base < 0 || qual_base > 255) return fail(FFQ_E_ARG, "ffq_stream_set_stats: qual_base is 0..255");
-    if (s->cur >= 0) return fail(FFQ_E_ARG, "ffq_stream_set_stats: the stream has handed out a fill already");
+    int rc = stats_arg("ffq_stream_set_stats", qual_base, max_cycles);
+    if (!rc) rc = stream_settable(s, "ffq_stream_set_stats", nullptr, true);
+    if (rc) return rc;
     ffq_ctx *c = s->c;
     HIPCHK(hipSetDevice(c->device));
     // (an even number of words per block: the OUT block is 16-byte aligned as well)
     const int64_t words = (FFQ_STATS_WORDS(max_cycles) + 1) & ~(int64_t)1;
-    if (s->stats_d.cap < 2 * words) {
+    if (s->stats.d.cap < 2 * words) {
         HIPCHK(hipStreamSynchronize(c->stream));
-        int rc = stream_grow(s->stats_d, 2 * words, "ffq_stream: no memory for %lld words of statistics", 2 * words);
+        rc = stream_grow(s->stats.d, 2 * words, "ffq_stream: no memory for %lld words of statistics", 2 * words);
         if (rc) return rc;
     }
-    HIPCHK(hipMemsetAsync(s->stats_d.p, 0, (size_t)(2 * words) * 8, c->stream));
-    s->stats_which = which; s->st_base = qual_base; s->st_cycles = max_cycles;
+    HIPCHK(hipMemsetAsync(s->stats.d.p, 0, (size_t)(2 * words) * 8, c->stream));
+    s->stats.which = which; s->stats.base = qual_base; s->stats.cycles = max_cycles;
     return FFQ_OK;
 }
 
 static uint64_t *stream_stats_block(ffq_stream *s, int which)
 {
-    const int64_t words = (FFQ_STATS_WORDS(s->st_cycles) + 1) & ~(int64_t)1;
-    return s->stats_d.p + (which == FFQ_STATS_OUT ? words : 0);
+    const int64_t words = (FFQ_STATS_WORDS(s->stats.cycles) + 1) & ~(int64_t)1;
+    return s->stats.d.p + (which == FFQ_STATS_OUT ? words : 0);
 }
 
 // the running totals of one of the blocks, over every fill handed out so far; one host wait
 extern "C" int ffq_stream_stats(ffq_stream *s, int which, uint64_t *h_out, int64_t cap_words)
 {
     if (!s || !h_out) return fail(FFQ_E_ARG, "ffq_stream_stats: NULL argument");
-    if ((which != FFQ_STATS_IN && which != FFQ_STATS_OUT) || !(s->stats_which & which))
+    if ((which != FFQ_STATS_IN && which != FFQ_STATS_OUT) || !(s->stats.which & which))
         return fail(FFQ_E_ARG, "ffq_stream_stats: the stream does not count that (ffq_stream_set_stats)");
-    const int64_t words = FFQ_STATS_WORDS(s->st_cycles);
+    const int64_t words = FFQ_STATS_WORDS(s->stats.cycles);
     if (cap_words < words) return fail(FFQ_E_ARG, "ffq_stream_stats: the totals have %lld words, the output holds %lld", (long long)words,
                                        (long long)cap_words);
     ffq_ctx *c = s->c;
@@ -1134,12 +698,13 @@ extern "C" int ffq_stream_stats(ffq_stream *s, int which, uint64_t *h_out, int64
 extern "C" int ffq_stream_set_render(ffq_stream *s)
 {
     if (!s) return fail(FFQ_E_ARG, "ffq_stream_set_render: NULL stream");
-    if (s->flags & FFQ_F_DECODE_QUAL) return fail(FFQ_E_ARG, "ffq_stream_set_render: the stream decodes every record's qualities (FFQ_F_DECODE_QUAL); "
-                                                              "FASTQ text holds them as they are");
-    if (s->filter_on && s->f_col) return fail(FFQ_E_ARG, "ffq_stream_set_render: the stream's filter gathers a column (ffq_stream_set_filter: "
-                                                          "column != FFQ_COL_NONE); a stream that renders FASTQ gathers none");
-    if (s->cur >= 0) return fail(FFQ_E_ARG, "ffq_stream_set_render: the stream has handed out a fill already");
-    s->render_on = true;
+    int rc = stream_settable(s, "ffq_stream_set_render", DECODE_TEXT, false);
+    if (rc) return rc;
+    if (s->filter.on && s->filter.col) return fail(FFQ_E_ARG, "ffq_stream_set_render: the stream's filter gathers a column (ffq_stream_set_filter: "
+                                                               "column != FFQ_COL_NONE); a stream that renders FASTQ gathers none");
+    rc = stream_settable(s, "ffq_stream_set_render", nullptr, true);
+    if (rc) return rc;
+    s->render.on = true;
     return FFQ_OK;
 }
 
@@ -1148,9 +713,9 @@ extern "C" int ffq_stream_set_render(ffq_stream *s)
 extern "C" int ffq_stream_rendered(ffq_stream *s, const uint8_t **h_fastq, int64_t *n_fastq_bytes, int64_t stats[3])
 {
     if (!s || !h_fastq || !n_fastq_bytes) return fail(FFQ_E_ARG, "ffq_stream_rendered: NULL argument");
-    if (!s->render_on) return fail(FFQ_E_ARG, "ffq_stream_rendered: the stream does not render (ffq_stream_set_render)");
-    *h_fastq = s->b->ren.h; *n_fastq_bytes = s->last_render[0];
-    if (stats) for (int i = 0; i < 3; i++) stats[i] = s->last_render[i];
+    if (!s->render.on) return fail(FFQ_E_ARG, "ffq_stream_rendered: the stream does not render (ffq_stream_set_render)");
+    *h_fastq = s->b->ren.h; *n_fastq_bytes = s->render.last[0];
+    if (stats) for (int i = 0; i < 3; i++) stats[i] = s->render.last[i];
     return FFQ_OK;
 }
 
@@ -1161,11 +726,129 @@ extern "C" int ffq_stream_selected(ffq_stream *s, const int64_t **h_index, int64
                                    const int64_t **h_coloff, int64_t *n_col_bytes)
 {
     if (!s || !h_index || !n_scanned) return fail(FFQ_E_ARG, "ffq_stream_selected: NULL argument");
-    if (!s->filter_on) return fail(FFQ_E_ARG, "ffq_stream_selected: the stream has no filter (ffq_stream_set_filter)");
-    *h_index = s->b->idx.h; *n_scanned = s->last_scanned;
-    if (h_col) *h_col = s->f_col ? s->b->col.h : nullptr;
-    if (h_coloff) *h_coloff = s->f_col ? s->b->coff.h : nullptr;
-    if (n_col_bytes) *n_col_bytes = s->last_col_bytes;
+    if (!s->filter.on) return fail(FFQ_E_ARG, "ffq_stream_selected: the stream has no filter (ffq_stream_set_filter)");
+    *h_index = s->b->idx.h; *n_scanned = s->filter.scanned;
+    if (h_col) *h_col = s->filter.col ? s->b->col.h : nullptr;
+    if (h_coloff) *h_coloff = s->filter.col ? s->b->coff.h : nullptr;
+    if (n_col_bytes) *n_col_bytes = s->filter.col_bytes;
+    return FFQ_OK;
+}
+
+// ---- chunk k: wait for the feeder -------------------------------------------------------
+static int stream_wait_chunk(ffq_stream *s, int64_t k)
+{
+    std::unique_lock<std::mutex> lk(s->m);
+    s->cv.wait(lk, [&] { return s->produced > k || s->feeder_done; });
+    if (s->produced > k) return FFQ_OK;
+    if (s->feeder_rc) return fail(s->feeder_rc, "%s", s->feeder_msg.c_str());
+    if (s->src == SRC_PUSH) { s->failed = false; return fail(FFQ_E_ARG, "ffq_stream_next: no chunk has been pushed"); }
+    return fail(FFQ_E_INTERNAL, "ffq_stream: the reader stopped early");
+}
+
+// ---- take chunk k: buf = buf[offset:] + chunk (:277); the first fill: b'\n' + chunk (:245) -----------------
+// The carry goes in front of the chunk (the slots grow if it needs more room); the scan stream gets its copy and the two waits.
+static int stream_take(ffq_stream *s, int64_t k, Fill *f)
+{
+    ffq_ctx *c = s->c;
+    StreamBufs *b = s->b;
+    const int64_t carry = k == 0 ? 1 : s->fill_len - s->carry_from;
+    if (carry > b->room) {
+        int rc = stream_grow_room(s, carry);
+        if (rc) return rc;
+    }
+    StreamSlot &sl = b->slot[k % STREAM_SLOTS];
+    const int64_t room = b->room;
+    if (k == 0) sl.buf.h[room - 1] = (uint8_t)'\n';
+    else {
+        const StreamSlot &pv = b->slot[s->cur % STREAM_SLOTS];
+        memcpy(sl.buf.h + room - carry, pv.buf.h + s->fill_start + s->carry_from, (size_t)carry);
+        // the previous fill's slot goes back to the feeder (the caller's pointers into it expired with this call)
+        { std::lock_guard<std::mutex> lk(s->m); s->released = k; }
+        s->cv.notify_all();
+    }
+    const int64_t start = room - carry, len = carry + sl.got, mis = start & 15;
+    *f = Fill{&sl, start, len, mis, sl.eof, sl.buf.d + start - mis, len + mis, s->globaloffset - mis};
+    mark_other(c);          // (a copy and two event waits go onto the scan stream in front of the scan)
+    HIPCHK(hipMemcpyAsync(sl.buf.d + start, sl.buf.h + start, (size_t)carry, hipMemcpyHostToDevice, c->stream));
+    if (s->prof) {          // (profiling only: the wait for the chunk's copy on its own)
+        const double t = stream_now();
+        HIPCHK(hipEventSynchronize(sl.copied[0]));
+        HIPCHK(hipEventSynchronize(sl.copied[1]));
+        s->t_copy += stream_now() - t;
+    }
+    HIPCHK(hipStreamWaitEvent(c->stream, sl.copied[0], 0));
+    HIPCHK(hipStreamWaitEvent(c->stream, sl.copied[1], 0));
+    return FFQ_OK;
+}
+
+// ---- scan: from the aligned address below the fill, searching from the fill's first byte ----
+static int stream_scan(ffq_stream *s, const Fill &f, ffq_scan_result *res)
+{
+    StreamBufs *b = s->b;
+    const bool decode = (s->flags & FFQ_F_DECODE_QUAL) != 0;
+    if (decode) {
+        // qualities are at most half of the bytes; the segmented layout of the single pass owns FFQ_SEG_STRIDE bytes per tile
+        int64_t need = f.len / 2 + 64;
+        if (s->flags & FFQ_F_SINGLE_PASS) need = std::max<int64_t>(need, ((f.n + 16383) >> 14) * (int64_t)FFQ_SEG_STRIDE);
+        int rc = stream_grow(b->qual, need, "ffq_stream: no memory for %lld decoded bytes", need);
+        if (rc) return rc;
+    }
+    memset(res, 0, sizeof *res);
+    for (int attempt = 0;; attempt++) {
+        int rc = ffq_scan_device(s->c, f.d_buf, f.n, 0, f.mis, f.eof ? 1 : 0, f.add, s->flags, s->qual_add, b->tab.d, stream_tab_rows(b),
+                                 decode ? b->qual.d.p : nullptr, decode ? b->qual.d.cap : 0, decode ? b->qoff.d : nullptr, res);
+        if (rc != FFQ_E_TABLE_FULL || attempt == 1) return rc;
+        rc = stream_alloc_tab(s, res->n_records + 1024);
+        if (rc) return rc;
+    }
+}
+
+// ---- the table chain of a fill: every stage the stream has switched on, over the fill's view, on the table the chain is
+// at.  With a filter the select REPLACES that table by the kept rows (on the DEVICE, before anything is copied back: a
+// dropped record costs the host nothing, doc/user-guide.rst:153-180); what follows is written once, for either table.
+// This is the one place that states the order of a fill's work on the scan stream, in every configuration:
+//     carry H2D, wait copied[0], wait copied[1], scan, [stats IN], [trim], [adapter], [select],
+//     [stats OUT], [render + text D2H], rows D2H, [idx D2H], [gather, col D2H, coff D2H],
+//     [qual D2H, qoff D2H], synchronise
+// No rows are copied back from an empty table; a fill without records allocates and launches nothing of the push-down,
+// but statistics OUT and the render are still called (n = 0).  *n_out: the rows handed out.
+static int stream_chain(ffq_stream *s, const Fill &f, const ffq_scan_result &res, int64_t *n_out)
+{
+    ffq_ctx *c = s->c;
+    StreamBufs *b = s->b;
+    Table t = {b->tab.d, res.n_records};
+    s->filter.scanned = res.n_records; s->filter.col_bytes = 0;
+    int rc = FFQ_OK;
+    if (s->stats.which & FFQ_STATS_IN)
+        rc = ffq_table_stats(c, f.d_buf, f.n, 0, f.add, t.d_rows, t.n, s->stats.base, s->stats.cycles, 1, stream_stats_block(s, FFQ_STATS_IN), nullptr);
+    if (!rc && s->trim.on)
+        rc = ffq_table_trim_quality(c, f.d_buf, f.n, 0, f.add, t.d_rows, t.n, s->trim.base, s->trim.front, s->trim.back, b->tab.d, s->trim.last);
+    if (!rc && s->adapter.on)       // (as the quality trim left them)
+        rc = ffq_table_trim_adapter(c, f.d_buf, f.n, 0, f.add, t.d_rows, t.n, s->adapter.bytes, s->adapter.len, s->adapter.err,
+                                    s->adapter.overlap, b->tab.d, s->adapter.last);
+    if (!rc && s->filter.on) {
+        if (res.n_records > 0) rc = stream_alloc_sel(s, res.n_records, f.len + 64);
+        t = Table{b->sel, 0};
+        if (!rc && res.n_records > 0) rc = table_select(c, b->tab.d, res.n_records, s->filter.min, s->filter.max, b->sel, b->idx.d, &t.n);
+    }
+    if (!rc && (s->stats.which & FFQ_STATS_OUT))
+        rc = ffq_table_stats(c, f.d_buf, f.n, 0, f.add, t.d_rows, t.n, s->stats.base, s->stats.cycles, 1, stream_stats_block(s, FFQ_STATS_OUT), nullptr);
+    if (!rc && s->render.on) rc = stream_render(s, f, t);
+    if (rc) return rc;
+    if (t.n > 0) HIPCHK(hipMemcpyAsync(b->tab.h, t.d_rows, (size_t)t.n * 48, hipMemcpyDeviceToHost, c->stream));
+    if (s->filter.on && t.n > 0) HIPCHK(hipMemcpyAsync(b->idx.h, b->idx.d, (size_t)t.n * 8, hipMemcpyDeviceToHost, c->stream));
+    if (s->filter.on && s->filter.col && res.n_records > 0) {
+        static const int COLS[4][3] = {{0, 0, 0}, {0, 1, 1}, {2, 0, 3}, {4, 0, 5}};       // header: buf[pos0 + 1 : pos1] (:161-171)
+        const int *col = COLS[s->filter.col];
+        int64_t nb = 0;
+        rc = ffq_table_gather_column(c, f.d_buf, f.n, 0, f.add, t.d_rows, t.n, col[0], col[1], col[2], s->filter.add, b->col.d, b->col.d.cap,
+                                     b->coff.d, &nb);
+        if (rc) return rc;
+        s->filter.col_bytes = nb;
+        if (nb > 0) HIPCHK(hipMemcpyAsync(b->col.h, b->col.d, (size_t)nb, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(b->coff.h, b->coff.d, (size_t)(t.n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    *n_out = t.n;
     return FFQ_OK;
 }
 
@@ -1186,147 +869,22 @@ extern "C" int ffq_stream_next(ffq_stream *s, const int64_t **h_rows, int64_t *n
     if (s->done) return FFQ_OK;
     s->failed = true;                    // until this call gets through: an error leaves no half-advanced state behind
 
-    // ---- chunk k: wait for the feeder -------------------------------------------------------
     const int64_t k = s->cur + 1;
-    const double tp0 = s->prof ? stream_now() : 0;
-    {
-        std::unique_lock<std::mutex> lk(s->m);
-        s->cv.wait(lk, [&] { return s->produced > k || s->feeder_done; });
-        if (s->produced <= k) {
-            if (s->feeder_rc) return fail(s->feeder_rc, "%s", s->feeder_msg.c_str());
-            if (s->src == SRC_PUSH) { s->failed = false; return fail(FFQ_E_ARG, "ffq_stream_next: no chunk has been pushed"); }
-            return fail(FFQ_E_INTERNAL, "ffq_stream: the reader stopped early");
-        }
-    }
-    const double tp1 = s->prof ? stream_now() : 0;
-    // ---- buf = buf[offset:] + chunk (:277); the first fill: b'\n' + chunk (:245) -----------------
-    int64_t carry;
-    if (k == 0) carry = 1;
-    else {
-        carry = s->fill_len - s->carry_from;
-        if (carry > b->room) {
-            int rc = stream_grow_room(s, carry);
-            if (rc) return rc;
-        }
-    }
-    StreamSlot &sl = b->slot[k % STREAM_SLOTS];
-    const int64_t room = b->room;
-    if (k == 0) sl.buf.h[room - 1] = (uint8_t)'\n';
-    else {
-        const StreamSlot &pv = b->slot[s->cur % STREAM_SLOTS];
-        memcpy(sl.buf.h + room - carry, pv.buf.h + s->fill_start + s->carry_from, (size_t)carry);
-        // the previous fill's slot goes back to the feeder (the caller's pointers into it expired
-        // with this call)
-        { std::lock_guard<std::mutex> lk(s->m); s->released = k; }
-        s->cv.notify_all();
-    }
-    const int64_t start = room - carry, len = carry + sl.got;
-    const bool fill_eof = sl.eof;
-    mark_other(c);          // (a copy and two event waits go onto the scan stream in front of the scan)
-    HIPCHK(hipMemcpyAsync(sl.buf.d + start, sl.buf.h + start, (size_t)carry, hipMemcpyHostToDevice, c->stream));
-    if (s->prof) {          // (profiling only: the wait for the chunk's copy on its own)
-        const double t = stream_now();
-        HIPCHK(hipEventSynchronize(sl.copied[0]));
-        HIPCHK(hipEventSynchronize(sl.copied[1]));
-        s->t_copy += stream_now() - t;
-    }
-    HIPCHK(hipStreamWaitEvent(c->stream, sl.copied[0], 0));
-    HIPCHK(hipStreamWaitEvent(c->stream, sl.copied[1], 0));
-
-    // ---- scan: from the aligned address below the fill, searching from the fill's first byte ----
-    const int64_t mis = start & 15;
-    const bool decode = (s->flags & FFQ_F_DECODE_QUAL) != 0;
-    if (decode) {
-        // qualities are at most half of the bytes; the segmented layout of the single pass owns FFQ_SEG_STRIDE bytes per tile
-        int64_t need = len / 2 + 64;
-        if (s->flags & FFQ_F_SINGLE_PASS) need = std::max<int64_t>(need, ((len + mis + 16383) >> 14) * (int64_t)FFQ_SEG_STRIDE);
-        int rc2 = stream_grow(b->qual, need, "ffq_stream: no memory for %lld decoded bytes", need);
-        if (rc2) return rc2;
-    }
+    Fill f;
     ffq_scan_result res;
-    memset(&res, 0, sizeof res);
-    int rc = FFQ_OK;
-    for (int attempt = 0; attempt < 2; attempt++) {
-        rc = ffq_scan_device(c, sl.buf.d + start - mis, len + mis, 0, mis, fill_eof ? 1 : 0, s->globaloffset - mis, s->flags,
-                             s->qual_add, b->tab.d, stream_tab_rows(b), decode ? b->qual.d.p : nullptr, decode ? b->qual.d.cap : 0,
-                             decode ? b->qoff.d : nullptr, &res);
-        if (rc != FFQ_E_TABLE_FULL) break;
-        int rc2 = stream_alloc_tab(s, res.n_records + 1024);
-        if (rc2) return rc2;
-    }
-    if (rc != FFQ_OK) return rc;
+    int64_t n_out = 0;
+    const double tp0 = s->prof ? stream_now() : 0;
+    int rc = stream_wait_chunk(s, k);
+    const double tp1 = s->prof ? stream_now() : 0;
+    if (!rc) rc = stream_take(s, k, &f);
+    if (!rc) rc = stream_scan(s, f, &res);
     const double tp2 = s->prof ? stream_now() : 0;
-    int64_t n_out = res.n_records;
-    s->last_scanned = res.n_records; s->last_kept = res.n_records; s->last_col_bytes = 0;
-    if (s->stats_which & FFQ_STATS_IN) {
-        // ---- the rows as scanned, counted into the stream's block (enqueued only) ----
-        int rc2 = ffq_table_stats(c, sl.buf.d + start - mis, len + mis, 0, s->globaloffset - mis, b->tab.d, res.n_records, s->st_base,
-                                  s->st_cycles, 1, stream_stats_block(s, FFQ_STATS_IN), nullptr);
-        if (rc2) return rc2;
-    }
-    if (s->trim_on) {
-        // ---- the fill's rows are trimmed where they lie, over the buffer and the `add` the scan was given ----
-        int rc2 = ffq_table_trim_quality(c, sl.buf.d + start - mis, len + mis, 0, s->globaloffset - mis, b->tab.d, res.n_records,
-                                         s->t_base, s->t_front, s->t_back, b->tab.d, s->last_trim);
-        if (rc2) return rc2;
-    }
-    if (s->adapter_on) {
-        // ---- ... and cut at the 3' adapter, as the quality trim left them ----
-        int rc2 = ffq_table_trim_adapter(c, sl.buf.d + start - mis, len + mis, 0, s->globaloffset - mis, b->tab.d, res.n_records,
-                                         s->ad_bytes, s->ad_len, s->ad_err, s->ad_overlap, b->tab.d, s->last_adapter);
-        if (rc2) return rc2;
-    }
-    if (s->filter_on) {
-        // ---- push-down: the fill's table is filtered (and one component of the kept rows gathered) on the DEVICE, before
-        // anything is copied back: a dropped record costs the host nothing (doc/user-guide.rst:153-180) -----------------
-        n_out = 0;
-        if (res.n_records > 0) {
-            int rc2 = stream_alloc_sel(s, res.n_records, len + 64);
-            if (rc2) return rc2;
-            rc2 = table_select(c, b->tab.d, res.n_records, s->f_min, s->f_max, b->sel, b->idx.d, &n_out);
-            if (rc2) return rc2;
-        }
-        s->last_kept = n_out;
-        if (s->stats_which & FFQ_STATS_OUT) {
-            int rc2 = ffq_table_stats(c, sl.buf.d + start - mis, len + mis, 0, s->globaloffset - mis, b->sel, n_out, s->st_base,
-                                      s->st_cycles, 1, stream_stats_block(s, FFQ_STATS_OUT), nullptr);
-            if (rc2) return rc2;
-        }
-        if (s->render_on) {
-            int rc2 = stream_render(s, sl.buf.d + start - mis, len + mis, s->globaloffset - mis, b->sel, n_out);
-            if (rc2) return rc2;
-        }
-        if (n_out > 0) {
-            HIPCHK(hipMemcpyAsync(b->tab.h, b->sel, (size_t)n_out * 48, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipMemcpyAsync(b->idx.h, b->idx.d, (size_t)n_out * 8, hipMemcpyDeviceToHost, c->stream));
-        }
-        if (s->f_col && res.n_records > 0) {
-            static const int COLS[4][3] = {{0, 0, 0}, {0, 1, 1}, {2, 0, 3}, {4, 0, 5}};       // header: buf[pos0 + 1 : pos1] (:161-171)
-            int64_t nb = 0;
-            // rows are stream offsets: buffer coordinate = row - add, with add = globaloffset - mis as the scan was given
-            int rc2 = ffq_table_gather_column(c, sl.buf.d + start - mis, len + mis, 0, s->globaloffset - mis, b->sel, n_out, COLS[s->f_col][0],
-                                              COLS[s->f_col][1], COLS[s->f_col][2], s->f_add, b->col.d, b->col.d.cap, b->coff.d, &nb);
-            if (rc2) return rc2;
-            s->last_col_bytes = nb;
-            if (nb > 0) HIPCHK(hipMemcpyAsync(b->col.h, b->col.d, (size_t)nb, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipMemcpyAsync(b->coff.h, b->coff.d, (size_t)(n_out + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-        }
-    } else {
-        if (s->stats_which & FFQ_STATS_OUT) {
-            int rc2 = ffq_table_stats(c, sl.buf.d + start - mis, len + mis, 0, s->globaloffset - mis, b->tab.d, res.n_records, s->st_base,
-                                      s->st_cycles, 1, stream_stats_block(s, FFQ_STATS_OUT), nullptr);
-            if (rc2) return rc2;
-        }
-        if (s->render_on) {
-            int rc2 = stream_render(s, sl.buf.d + start - mis, len + mis, s->globaloffset - mis, b->tab.d, res.n_records);
-            if (rc2) return rc2;
-        }
-        if (res.n_records > 0)
-            HIPCHK(hipMemcpyAsync(b->tab.h, b->tab.d, (size_t)res.n_records * 48, hipMemcpyDeviceToHost, c->stream));
-    }
-    s->last_nq = 0;
+    if (!rc) rc = stream_chain(s, f, res, &n_out);
+    if (rc) return rc;
+    // ---- the decoded qualities' copies, the one wait of the fill, and what the caller is told ----
     s->last_path = res.path;
-    if (decode) {
+    s->last_nq = 0;
+    if (s->flags & FFQ_F_DECODE_QUAL) {
         s->last_nq = res.n_qual_bytes;
         if (res.n_qual_bytes > 0)
             HIPCHK(hipMemcpyAsync(b->qual.h, b->qual.d, (size_t)res.n_qual_bytes, hipMemcpyDeviceToHost, c->stream));
@@ -1336,16 +894,16 @@ extern "C" int ffq_stream_next(ffq_stream *s, const int64_t **h_rows, int64_t *n
     if (s->prof) { const double t = stream_now(); s->t_feed += tp1 - tp0; s->t_scan += tp2 - tp1; s->t_rows += t - tp2; }
 
     s->cur = k;
-    s->handed_pos = sl.end_pos;
-    s->fill_start = start; s->fill_len = len;
+    s->handed_pos = f.sl->end_pos;
+    s->fill_start = f.start; s->fill_len = f.len;
     *h_rows = b->tab.h;
     *n_rows = n_out;
-    if (h_bytes) *h_bytes = sl.buf.h + start;
-    if (n_bytes) *n_bytes = len;
+    if (h_bytes) *h_bytes = f.sl->buf.h + f.start;
+    if (n_bytes) *n_bytes = f.len;
     // byte i of this fill is stream offset globaloffset + i (the sentinel of the first fill is -1)
     if (bytes_offset) *bytes_offset = s->globaloffset;
     *end_state = res.end_state;
-    const int64_t ds = res.end_offset - mis;             // the iterator's `offset` at exit, fill-relative
+    const int64_t ds = res.end_offset - f.mis;             // the iterator's `offset` at exit, fill-relative
     s->failed = false;
     if (res.end_state != FFQ_END_REFILL) {
         if (res.end_state != FFQ_END_OK && err_offset) *err_offset = s->globaloffset + ds;

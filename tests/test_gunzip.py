@@ -1,4 +1,4 @@
-"""The gzip reader of the stream front end (csrc/ffq_stream.h), on the host alone (ffq_gunzip_fd).
+"""The gzip reader of the stream front end (csrc/ffq_gzread.h), on the host alone (ffq_gunzip_fd).
 
 What the reference hands readfastq_iter for a compressed file is `gzip.open(...)`
 (/root/reference/src/fastqandfurious.py:282-334): Python's gzip module is the statement of what the

@@ -1,6 +1,6 @@
-"""The stream front end's per-fill chain -- scan, ffq_table_trim_quality in place, table_select, ffq_table_render_fastq or
-ffq_table_gather_column, the copies back, carry and refill (ffq_stream_next, csrc/ffq_stream.h) -- on reads as files hold
-them: short and long ones, wrapped records between single-line ones, empty headers, '+' lines that repeat the header,
+"""The stream front end's per-fill chain -- scan, ffq_table_trim_quality and ffq_table_trim_adapter in place, table_select,
+ffq_table_render_fastq or ffq_table_gather_column, the copies back, carry and refill (ffq_stream_next: stream_take,
+stream_scan, stream_chain in csrc/ffq_stream.h) -- on reads as files hold them: short and long ones, some with the 3' adapter, wrapped records between single-line ones, empty headers, '+' lines that repeat the header,
 quality lines that begin with '@' and '+', a bad tile, reads above the kernels' short / long split and a record longer
 than the buffer.
 
@@ -9,11 +9,12 @@ and the fill boundaries itself, so every fill is compared with the same slice of
 
     rows    the oracle's C-variant scan of the whole corpus (stream byte i is file byte i, the sentinel is -1)
     trim    test_trim.loop_rows over those rows
+    adapter test_adapter.loop_rows over what that left (cutadapt's order)
     filter  a numpy comparison of pos3 - pos2 of the trimmed rows
     text    test_render.loop_render of the kept rows
     column  test_gather.loop_gather of the kept rows
 
--- never the package's own trim, select, gather or render code.  Every comparison is exact.  The corpora come from the
+-- never the package's own trim, adapter, select, gather or render code.  Every comparison is exact.  The corpora come from the
 seeded generator below; no corpus holds a read of length 0 (the device scanners do not read one back:
 test_empty_reads_are_read_back_by_the_python_scanner_only), and rendered text is rescanned on the device only where the
 filter has min_len >= 1.
@@ -26,6 +27,7 @@ import os
 import numpy as np
 import pytest
 
+from test_adapter import AD, loop_rows as adapter_loop_rows
 from test_gather import loop_gather
 from test_render import loop_render
 from test_trim import expected_items, loop_rows
@@ -38,6 +40,7 @@ COUNTS = {"mixed": 12000, "long": 3000, "small": 500}
 SEEDS = {"mixed": 20241, "long": 20242, "small": 20243}
 TILE_AT = {"mixed": 5000, "long": 1500}             # first record of the bad tile
 TILE = 1100                                         # ... and its records: more than the 1024 of the gather's window walk
+ADAPTER_SHARE = 0.3                                 # of the reads: the 3' adapter (test_adapter.AD) from a random base on
 LONG_LENGTHS = (4095, 4096, 4097, 9000, 70000)      # either side of TRIM_LONG / RENDER_LONG; longer than every fbufsize below
 _ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
 _NOISE = np.frombuffer(b"@+#5?I", dtype=np.uint8)
@@ -67,6 +70,7 @@ def _wrap(b, w):
 
 def make_corpus(kind):
     rng = np.random.default_rng(SEEDS[kind])
+    arng = np.random.default_rng(SEEDS[kind] + 100)     # (the adapters' own generator: `rng` draws what it drew without them)
     tile = range(TILE_AT[kind], TILE_AT[kind] + TILE) if kind in TILE_AT else range(0)
     parts = []
     for i in range(COUNTS[kind]):
@@ -78,6 +82,10 @@ def make_corpus(kind):
         head = b"" if rng.random() < 0.03 else b"r%d:%d/%d" % (i, int(rng.integers(0, 10 ** int(rng.integers(1, 9)))), i % 2 + 1)
         plus = b"+" + head if rng.random() < 0.2 else b"+"
         seq = _ACGT[rng.integers(0, 4, n)].tobytes()
+        if arng.random() < ADAPTER_SHARE:
+            # a short insert: the adapter and what the sequencer read behind it, cut off by the read's end
+            p = int(arng.integers(0, n))
+            seq = (seq[:p] + AD + _ACGT[arng.integers(0, 4, n)].tobytes())[:n]
         qual = _quality(rng, n, 3 if i in tile else int(rng.choice(5, p=(0.35, 0.25, 0.15, 0.1, 0.15))))
         if wrapped:
             w = int(rng.integers(7, 91))
@@ -103,7 +111,7 @@ class Expect:
         self.rows, self.end, _status, self.end_offset = oracle.scan(data)
         self.rows.setflags(write=False)
         self.n = self.rows.shape[0]
-        self._trim = {}
+        self._trim, self._adapter = {}, {}
 
     def trimmed(self, trim):
         """(trimmed rows, cum int64[n + 1][3]): cum[b] - cum[a] = loop_rows' [changed, removed, skipped] over rows a..b-1
@@ -120,9 +128,22 @@ class Expect:
             self._trim[trim] = (t, cum)
         return self._trim[trim]
 
-    def kept(self, trim, lo=None, hi=None):
-        """(trimmed rows, cum, mask of the rows with lo <= pos3 - pos2 <= hi)"""
+    def adapted(self, trim):
+        """(the trimmed rows cut at the adapter, cum of test_adapter.loop_rows' counters), as trimmed()"""
+        if trim not in self._adapter:
+            out = [adapter_loop_rows(self.data, r[None, :]) for r in self.trimmed(trim)[0]]
+            t = np.concatenate([r for r, _s in out]) if out else np.zeros((0, 6), dtype=np.int64)
+            cum = np.zeros((self.n + 1, 3), dtype=np.int64)
+            np.cumsum(np.array([s for _r, s in out], dtype=np.int64).reshape(-1, 3), axis=0, out=cum[1:])
+            t.setflags(write=False)
+            self._adapter[trim] = (t, cum)
+        return self._adapter[trim]
+
+    def kept(self, trim, lo=None, hi=None, adapter=False):
+        """(trimmed rows -- cut at the adapter too, if `adapter` --, cum of the TRIM, mask of the rows with lo <= pos3 - pos2 <= hi)"""
         t, cum = self.trimmed(trim)
+        if adapter:
+            t = self.adapted(trim)[0]
         lens = t[:, 3] - t[:, 2]
         keep = np.ones(self.n, dtype=bool)
         if lo is not None:
@@ -195,6 +216,14 @@ def test_corpus_conditions(pkg, oracle, kind):
     assert (t[~wrapped][:, 3] == t[~wrapped][:, 2]).sum() > 0, "no read is trimmed away"
     assert 0 < changed < exp.n - skipped, "every eligible read is trimmed, or none"
     assert (t[wrapped] == exp.rows[wrapped]).all()
+    # the adapter behind that trim: found in a share of the eligible reads, neither none nor all; the filter still drops some
+    ta, acum = exp.adapted((20, 20))
+    a_changed, a_removed, a_skipped = acum[exp.n].tolist()
+    assert a_skipped == skipped and (ta[wrapped] == exp.rows[wrapped]).all()
+    assert exp.n // 10 <= a_changed <= exp.n // 2 and a_removed > a_changed, (a_changed, a_removed)
+    assert a_changed == ((ta[:, 3] != t[:, 3]).sum()) and (ta[:, :3] == t[:, :3]).all()
+    keep_a = exp.kept((20, 20), 30, None, adapter=True)[2]
+    assert 0 < keep_a.sum() < keep.sum()
     lens = exp.rows[:, 5] - exp.rows[:, 4]
     if kind in TILE_AT:
         assert longest_run_of_empty(t) >= TILE > 1024
@@ -274,6 +303,11 @@ CONFIGS = {
     "trim20-20_all_quality-33": dict(trim=(20, 20), flt=(None, None), column="quality", value_add=-33),
 }
 SOURCES = ("file", "gz", "push")
+# every editing pass switched on, down either way behind them: the table as edited, and the kept rows of the select
+ADAPTER_CONFIGS = {
+    "trim20-20_adapter_render": dict(trim=(20, 20), adapter=True, render=True),
+    "trim20-20_adapter_min30_quality-33": dict(trim=(20, 20), adapter=True, flt=(30, None), column="quality", value_add=-33),
+}
 
 
 @pytest.fixture(scope="module")
@@ -313,16 +347,19 @@ def run_stream(st, cfg, exp, tag):
     totals.  Returns what was seen: fills, end state, err_offset, the text, the longest run of rows of length 0 handed to
     the render / gather within one fill."""
     trim, flt, column, render = cfg.get("trim"), cfg.get("flt"), cfg.get("column"), cfg.get("render", False)
-    value_add = cfg.get("value_add", 0)
+    value_add, adapter = cfg.get("value_add", 0), cfg.get("adapter", False)
     if trim is not None:
         st.set_trim(trim[1], trim[0])
+    if adapter:
+        st.set_adapter(AD)
     if flt is not None:
         st.set_filter(flt[0], flt[1], column, value_add)
     if render:
         st.set_render()
-    t, cum, keep_all = exp.kept(trim, *(flt or (None, None)))
+    t, cum, keep_all = exp.kept(trim, *(flt or (None, None)), adapter=adapter)
+    acum = exp.adapted(trim)[1] if adapter else None
     base = fills = run = 0
-    sums = {"trim": np.zeros(3, dtype=np.int64), "render": np.zeros(3, dtype=np.int64)}
+    sums = {k: np.zeros(3, dtype=np.int64) for k in ("trim", "adapter", "render")}
     parts, end, err = [], None, None
     for rows, _fill, _off, end, err in st:
         where = (tag, "fill", fills, "records from", base)
@@ -352,6 +389,10 @@ def run_stream(st, cfg, exp, tag):
             got = st.trimmed()
             assert list(got) == (cum[hi] - cum[lo]).tolist(), (where, got)
             sums["trim"] += got
+        if adapter:
+            got = st.adapter_trimmed()
+            assert list(got) == (acum[hi] - acum[lo]).tolist(), (where, got)
+            sums["adapter"] += got
         if render:
             text, stats = st.rendered()
             wtext, _woff, wstats = loop_render(exp.data, want)
@@ -367,6 +408,8 @@ def run_stream(st, cfg, exp, tag):
     assert base == exp.n, (tag, base, exp.n)
     if trim is not None:
         assert sums["trim"].tolist() == cum[exp.n].tolist(), tag
+    if adapter:
+        assert sums["adapter"].tolist() == acum[exp.n].tolist(), tag
     text = b"".join(parts)
     if render:
         wtext, _woff, wstats = loop_render(exp.data, t[keep_all])
@@ -408,6 +451,24 @@ def test_stream_fill_by_fill(gpu_ctx, oracle, files, kind, source, config):
             table, res = gpu_ctx.scan_host(seen["text"])
             assert res.end_state == END_OK and table.shape == want_rows.shape and (table == want_rows).all(), tag
             assert entries_of(seen["text"], table) == entries_of(exp.data, t[keep]), tag
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("config", list(ADAPTER_CONFIGS))
+@pytest.mark.parametrize("source", ("file", "push"))
+@pytest.mark.parametrize("kind,sizes", (("small", (700, 3000)), ("mixed", (1 << 16,))))
+def test_stream_fill_by_fill_with_adapter(gpu_ctx, oracle, files, kind, sizes, source, config):
+    """the same comparison with the adapter cut behind the quality trim: without a filter (the edited table is counted,
+    rendered and copied back) and with one (the kept rows are); at 700 bytes nearly every fill carries and many hold no
+    record or one"""
+    from fastqandfurious_amd import hip
+    cfg, exp = ADAPTER_CONFIGS[config], expect(oracle, kind)
+    path, gz = files[kind]
+    for fbufsize in sizes:
+        tag = (kind, source, fbufsize, config)
+        with opened(hip, gpu_ctx, source, fbufsize, path, gz, exp.data) as st:
+            seen = run_stream(st, cfg, exp, tag)
+        assert seen["fills"] >= -(-len(exp.data) // fbufsize), tag
 
 
 @pytest.mark.gpu

@@ -4,8 +4,8 @@ inflate and in-process shard world do).
 
 A -fsanitize=thread (then: address,undefined) build of libffq_hip.so (hipcc instruments the HOST code; no device is touched by what runs here) +
 tests/tsan_host_threads.cpp + the oracle (the scan of the shard mode), all in one TSan runtime:
-  * ffq_gunzip_fd = the stream front end's gzip reader: BGZF members side by side (GzPool), ONE plain member by several
-    threads (csrc/ffq_pgz.h: chunks entered at block headers, hand-overs at odd bits, stitch, CRC pieces combined),
+  * ffq_gunzip_fd = the stream front end's gzip reader (csrc/ffq_gzread.h: GzReader): BGZF members side by side (GzPool), ONE
+    plain member by several threads (csrc/ffq_pgz.h: chunks entered at block headers, hand-overs at odd bits, stitch, CRC pieces combined),
     concatenated members, zlib taking over, corrupt and cut files;
   * the helper threads of a context (csrc/ffq_pool.h): slices of consecutive chunks through one queue;
   * ffq_shard_host_step with k ranks as threads over ffq_shard_world's breakable barrier (csrc/ffq_shard_proto.h): the
