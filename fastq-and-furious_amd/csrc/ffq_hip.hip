@@ -12,6 +12,7 @@
 #include "ffq_trim.h"
 #include "ffq_adapter.h"
 #include "ffq_stats.h"
+#include "ffq_filter.h"
 #include "ffq_render.h"
 #include "ffq_pool.h"
 #include "ffq_mem.h"
@@ -195,6 +196,9 @@ struct ffq_ctx {
     PinBuf<RowsBlock> h_rows;
     DevBuf<int64_t> rows_list;          //   rows left to the wave-per-row launch
     PinBuf<uint64_t> h_stats;           // ffq_table_stats: the head words handed back
+    DevBuf<FilterBlock> d_filter;       // ffq_table_select_reads: the call's counters and their pinned mirror
+    PinBuf<FilterBlock> h_filter;
+    DevBuf<uint8_t> filter_verdict;     //   a verdict byte per row
     DevBuf<RenderBlock> d_render;       // ffq_table_render_fastq: the call's counters and their pinned mirror
     PinBuf<RenderBlock> h_render;
     DevBuf<int64_t> render_list;        //   (row, place in the output) of the rows left to the wave-per-row launch
@@ -286,6 +290,8 @@ static int ctx_create_impl(int device, ffq_ctx *share, ffq_ctx **out)
     if (e == hipSuccess) e = c->d_rows.grow(1);
     if (e == hipSuccess) e = c->h_rows.grow(1);
     if (e == hipSuccess) e = c->h_stats.grow(STATS_HEAD);
+    if (e == hipSuccess) e = c->d_filter.grow(1);
+    if (e == hipSuccess) e = c->h_filter.grow(1);
     if (e == hipSuccess) e = c->d_render.grow(1);
     if (e == hipSuccess) e = c->h_render.grow(1);
     if (e == hipSuccess) e = c->fa_hdr.grow(1);
@@ -2094,6 +2100,85 @@ extern "C" int ffq_table_stats(ffq_ctx *c, const uint8_t *d_buf, int64_t n_bytes
         HIPCHK(hipStreamSynchronize(st));
         for (int i = 0; i < STATS_HEAD; i++) head[i] = (int64_t)c->h_stats[i];
     }
+    return FFQ_OK;
+}
+
+// ---- rows kept or dropped for what is in the read (csrc/ffq_filter.h) ---------------------------
+static_assert(FILTER_COUNTS == FFQ_FILTER_COUNTS, "include/ffq.h");
+static const uint32_t g_ee_micro[STATS_QBINS] = {FFQ_EE_MICRO_VALUES};
+extern "C" const uint32_t *ffq_ee_micro_table(void) { return g_ee_micro; }
+
+// content rules checked (NULL: every rule off); *on: one of rules 2 to 6 is switched on; R: as the kernels take them
+static int content_arg(const char *who, const ffq_content_rules *r, bool *on, FilterRules *R)
+{
+    *on = false;
+    if (!r) return FFQ_OK;
+    if (r->qual_base < 0 || r->qual_base > 255) return fail(FFQ_E_ARG, "%s: qual_base is 0..255", who);
+    if (r->max_n < -1) return fail(FFQ_E_ARG, "%s: max_n is -1 (off) or a count", who);
+    if (r->min_mean_qual < 0 || r->min_mean_qual > 95) return fail(FFQ_E_ARG, "%s: min_mean_qual is 0 (off) or 1..95", who);
+    if (r->qualified_qual < 0 || r->qualified_qual > 95) return fail(FFQ_E_ARG, "%s: qualified_qual is 0..95", who);
+    if (r->max_unqualified_pct < -1 || r->max_unqualified_pct > 100) return fail(FFQ_E_ARG, "%s: max_unqualified_pct is -1 (off) or 0..100", who);
+    if (r->min_complexity_pct < 0 || r->min_complexity_pct > 100) return fail(FFQ_E_ARG, "%s: min_complexity_pct is 0 (off) or 1..100", who);
+    if (r->max_ee_micro < -1) return fail(FFQ_E_ARG, "%s: max_ee_micro is -1 (off) or a number of millionths", who);
+    *on = r->max_n >= 0 || r->min_mean_qual > 0 || r->max_unqualified_pct >= 0 || r->max_ee_micro >= 0 || r->min_complexity_pct > 0;
+    if (R) *R = FilterRules{r->qual_base, r->max_n, r->min_mean_qual, r->qualified_qual, r->max_unqualified_pct, r->min_complexity_pct,
+                            (long long)r->max_ee_micro};
+    return FFQ_OK;
+}
+
+constexpr int FILTER_GRID_SHORT = 2048, FILTER_GRID_LONG = 1024;
+
+extern "C" int ffq_table_select_reads(ffq_ctx *c, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
+                                      const int64_t *d_table, int64_t n_rows, int64_t min_len, int64_t max_len,
+                                      const ffq_content_rules *rules, int64_t *d_out, int64_t *d_idx, int64_t *n_out,
+                                      int64_t counts[FFQ_FILTER_COUNTS])
+{
+    static const char *const who = "ffq_table_select_reads";
+    mark_other(c);
+    bool on = false;
+    FilterRules R = {};
+    int rc = content_arg(who, rules, &on, &R);
+    if (rc) return rc;
+    if (!c || !n_out || !counts || n_rows < 0 || n_bytes < 0 || (n_rows > 0 && (!d_table || !d_out)))
+        return fail(FFQ_E_ARG, "%s: bad argument", who);
+    if (c->pend.active) return fail(FFQ_E_ARG, "%s: a scan is pending on this context", who);
+    for (int i = 0; i < FFQ_FILTER_COUNTS; i++) counts[i] = 0;
+    if (!on) {
+        // no content rule: the length filter as it is -- nothing reads the buffer, nothing new is launched
+        rc = table_select(c, d_table, n_rows, min_len, max_len, d_out, d_idx, n_out);
+        if (!rc) { counts[0] = *n_out; counts[1] = n_rows - *n_out; }
+        return rc;
+    }
+    if (n_bytes > 0 && !d_buf) return fail(FFQ_E_ARG, "%s: no buffer to judge the rows by", who);
+    if (d_table == d_out && n_rows > 0) return fail(FFQ_E_ARG, "%s: d_out must not be d_table", who);
+    if (((reinterpret_cast<uintptr_t>(d_table) | reinterpret_cast<uintptr_t>(d_out)) & 15) != 0)
+        return fail(FFQ_E_ARG, "%s: tables must be 16-byte aligned", who);
+    HIPCHK(hipSetDevice(c->device));
+    *n_out = 0;
+    if (n_rows == 0) return FFQ_OK;
+    const int64_t nblk = (n_rows + 255) / 256;
+    // (everything is grown before anything is enqueued: growing waits for the stream)
+    rc = grow_dev(c, c->rows_list, n_rows);
+    if (!rc) rc = grow_dev(c, c->filter_verdict, n_rows);
+    if (!rc) rc = grow_dev(c, c->sel_cnt, nblk);
+    if (!rc) rc = grow_dev(c, c->sel_base, nblk);
+    if (rc) return rc;
+    hipStream_t st = c->stream;
+    const int s = sentinel ? 1 : 0;
+    HIPCHK(hipMemsetAsync(c->d_filter, 0, sizeof(FilterBlock), st));
+    hipLaunchKernelGGL(k_filter_rows, dim3(rows_grid(n_rows, FILTER_WG / FILTER_G, FILTER_GRID_SHORT)), dim3(FILTER_WG), 0, st, d_buf,
+                       n_bytes, s, add, d_table, n_rows, min_len, max_len, R, c->filter_verdict.p, c->rows_list.p, c->d_filter.p);
+    hipLaunchKernelGGL(k_filter_long, dim3(rows_grid(n_rows, FILTER_WG / 64, FILTER_GRID_LONG)), dim3(FILTER_WG), 0, st, d_buf,
+                       n_bytes, s, add, d_table, R, c->filter_verdict.p, (const int64_t *)c->rows_list, c->d_filter.p);
+    hipLaunchKernelGGL(k_filter_count, dim3((unsigned)nblk), dim3(256), 0, st, (const uint8_t *)c->filter_verdict, n_rows, c->sel_cnt.p);
+    if ((rc = launch_scan_u32(c, st, (const unsigned int *)c->sel_cnt, nblk, c->sel_base, (long long *)c->d_word.p))) return rc;
+    hipLaunchKernelGGL(k_filter_scatter, dim3((unsigned)nblk), dim3(256), 0, st, d_table, (const uint8_t *)c->filter_verdict, n_rows,
+                       (const long long *)c->sel_base, d_out, d_idx);
+    HIPCHK(hipMemcpyAsync(c->h_filter, c->d_filter, sizeof(FilterBlock), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    for (int i = 0; i < FFQ_FILTER_COUNTS; i++) counts[i] = (int64_t)c->h_filter->cnt[i];
+    *n_out = counts[0];
     return FFQ_OK;
 }
 

@@ -1,5 +1,5 @@
 // ffq_rows.h -- the row frame of the passes over a device offset table: quality trim (ffq_trim.h), adapter trim
-// (ffq_adapter.h), statistics (ffq_stats.h), render (ffq_render.h).
+// (ffq_adapter.h), statistics (ffq_stats.h), content filter (ffq_filter.h), render (ffq_render.h).
 //
 // What the passes share:
 //   the shape    workgroups stride over the table, a GROUP of ROWS_G = 8 lanes owns a row (WG / 8 rows per workgroup and step),
@@ -11,7 +11,7 @@
 // Every loop over rows is uniform over the wave: every group of a wave takes a step as long as one of them has a row, `have`
 // says whether this one does, and a group without a row -- or with a row that has nothing to do -- steps along.  What is done
 // with a row may therefore use ballots, DPP moves and barriers; it must not leave a step for some lanes only.
-// The strided walk of the three short-row kernels (k_trim_rows, k_adapter_rows, k_stats_rows) is NOT here: it stays written
+// The strided walk of the four short-row kernels (k_trim_rows, k_adapter_rows, k_stats_rows, k_filter_rows) is NOT here: it stays written
 // out in each of them.  Behind a shared function or iterator the compiler waited for the next row's prefetch before it asked for
 // the current row's bytes, or spilled.
 #pragma once

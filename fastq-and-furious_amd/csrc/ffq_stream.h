@@ -160,6 +160,8 @@ struct ffq_stream {
     struct { bool on = false; uint8_t bytes[64] = {0}; int len = 0, err = 0, overlap = 0; int64_t last[3] = {0, 0, 0}; } adapter;
     // push-down: rows by sequence length, one component of the kept rows (ffq_stream_set_filter)
     struct { bool on = false; int64_t min = 0, max = 0; int col = 0, add = 0; int64_t scanned = 0, col_bytes = 0; } filter;
+    // content rules of the filter (ffq_stream_set_content) and the eight counts of the last fill's select (with or without them)
+    struct { bool on = false; ffq_content_rules rules = {}; int64_t last[FFQ_FILTER_COUNTS] = {0, 0, 0, 0, 0, 0, 0, 0}; } content;
     // FASTQ text of every fill's table, behind the trim and the filter (ffq_stream_set_render)
     struct { bool on = false; int64_t last[3] = {0, 0, 0}; } render;
     // FFQ_STREAM_PROF=1: where the time of a stream goes (printed when it closes)
@@ -599,6 +601,35 @@ extern "C" int ffq_stream_set_filter(ffq_stream *s, int64_t min_seq_len, int64_t
     return FFQ_OK;
 }
 
+// Content rules in the stream: the select of every fill judges the rows by ffq_table_select_reads -- as the trims left them,
+// which is cutadapt's order -- instead of by their length alone.  Before the first fill.  A stream without a filter gets one
+// with unbounded length and no column; ffq_stream_set_filter, before or behind this call, sets the bounds and the column
+// and leaves the rules alone, as this call leaves those.
+extern "C" int ffq_stream_set_content(ffq_stream *s, const ffq_content_rules *rules)
+{
+    if (!s || !rules) return fail(FFQ_E_ARG, "ffq_stream_set_content: NULL argument");
+    bool on = false;
+    int rc = content_arg("ffq_stream_set_content", rules, &on, nullptr);
+    if (!rc) rc = stream_settable(s, "ffq_stream_set_content", DECODE_GATHERS, true);
+    if (rc) return rc;
+    if (!s->filter.on) {
+        s->filter.on = true;
+        s->filter.min = -((int64_t)1 << 62); s->filter.max = (int64_t)1 << 62; s->filter.col = 0; s->filter.add = 0;
+    }
+    s->content.on = true;
+    s->content.rules = *rules;
+    return FFQ_OK;
+}
+
+// the eight counts (FFQ_FILTER_COUNTS) of the select of the fill ffq_stream_next has just returned
+extern "C" int ffq_stream_filter_counts(ffq_stream *s, int64_t counts[FFQ_FILTER_COUNTS])
+{
+    if (!s || !counts) return fail(FFQ_E_ARG, "ffq_stream_filter_counts: NULL argument");
+    if (!s->filter.on) return fail(FFQ_E_ARG, "ffq_stream_filter_counts: the stream has no filter (ffq_stream_set_filter, ffq_stream_set_content)");
+    for (int i = 0; i < FFQ_FILTER_COUNTS; i++) counts[i] = s->content.last[i];
+    return FFQ_OK;
+}
+
 // Quality trimming in the stream: from the next fill on, every fill's table is trimmed in place on the device
 // (ffq_table_trim_quality) right behind the scan -- in front of the filter, the column gather and the rows' copy back, so
 // that all of them see the trimmed rows.  Refill and carry go by the scan's end offset, not by the table.
@@ -807,7 +838,8 @@ static int stream_scan(ffq_stream *s, const Fill &f, ffq_scan_result *res)
 // at.  With a filter the select REPLACES that table by the kept rows (on the DEVICE, before anything is copied back: a
 // dropped record costs the host nothing, doc/user-guide.rst:153-180); what follows is written once, for either table.
 // This is the one place that states the order of a fill's work on the scan stream, in every configuration:
-//     carry H2D, wait copied[0], wait copied[1], scan, [stats IN], [trim], [adapter], [select],
+//     carry H2D, wait copied[0], wait copied[1], scan, [stats IN], [trim], [adapter], [select: by length, or -- content rules --
+//     by length and content (ffq_table_select_reads), on the rows as the trims left them],
 //     [stats OUT], [render + text D2H], rows D2H, [idx D2H], [gather, col D2H, coff D2H],
 //     [qual D2H, qoff D2H], synchronise
 // No rows are copied back from an empty table; a fill without records allocates and launches nothing of the push-down,
@@ -829,7 +861,16 @@ static int stream_chain(ffq_stream *s, const Fill &f, const ffq_scan_result &res
     if (!rc && s->filter.on) {
         if (res.n_records > 0) rc = stream_alloc_sel(s, res.n_records, f.len + 64);
         t = Table{b->sel, 0};
-        if (!rc && res.n_records > 0) rc = table_select(c, b->tab.d, res.n_records, s->filter.min, s->filter.max, b->sel, b->idx.d, &t.n);
+        for (int i = 0; i < FFQ_FILTER_COUNTS; i++) s->content.last[i] = 0;
+        if (!rc && res.n_records > 0) {
+            if (s->content.on)
+                rc = ffq_table_select_reads(c, f.d_buf, f.n, 0, f.add, b->tab.d, res.n_records, s->filter.min, s->filter.max,
+                                            &s->content.rules, b->sel, b->idx.d, &t.n, s->content.last);
+            else {
+                rc = table_select(c, b->tab.d, res.n_records, s->filter.min, s->filter.max, b->sel, b->idx.d, &t.n);
+                s->content.last[0] = t.n; s->content.last[1] = res.n_records - t.n;
+            }
+        }
     }
     if (!rc && (s->stats.which & FFQ_STATS_OUT))
         rc = ffq_table_stats(c, f.d_buf, f.n, 0, f.add, t.d_rows, t.n, s->stats.base, s->stats.cycles, 1, stream_stats_block(s, FFQ_STATS_OUT), nullptr);

@@ -611,7 +611,8 @@ def readfastq_iter(fh: typing.BinaryIO, fbufsize: int,
         # the native stream front end: a real file, a gzip file, or anything with readinto() / read();
         # with entryfunc_phred the qualities of every fill are decoded on the device
         st = open_stream(fh, fbufsize, entryfunc is entryfunc_phred) if entryfunc is entryfunc_phred else open_stream(fh, fbufsize)
-        if st is not None and (_pushes_down(entryfunc) or _pushes_down_trim(entryfunc) or _pushes_down_adapter(entryfunc)):
+        if st is not None and (_pushes_down(entryfunc) or _pushes_down_trim(entryfunc) or _pushes_down_adapter(entryfunc)
+                               or _pushes_down_content(entryfunc)):
             # push-down: the filter runs on the device, on every fill's table, before anything is copied back -- behind the
             # quality and adapter trimming of the rows, if that is what the entryfunc does
             try:
@@ -622,6 +623,8 @@ def readfastq_iter(fh: typing.BinaryIO, fbufsize: int,
                         q = entryfunc.quality
                         st.set_trim(q.cutoff_back, q.cutoff_front, q.qual_base)
                     st.set_adapter(entryfunc.adapter, entryfunc.err_permille, entryfunc.min_overlap)
+                if isinstance(entryfunc, entryfunc_contentfilter):
+                    st.set_content(entryfunc.rules)
                 st.set_filter(entryfunc.min_len, entryfunc.max_len, None if entryfunc.column == "entry" else entryfunc.column)
             except BaseException:
                 st.close()                 # (the native stream, its pinned buffers and its feeder thread; a gzip stream's hook)
@@ -803,14 +806,135 @@ class FastqStats:
     q30_rate = property(lambda self: self._rate(30), doc="... with quality >= 30")
 
 
+# FFQ_EE_MICRO of include/ffq.h: floor(1e6 * 10 ** (-v / 10) + 0.5) for v = 0..95, the expected errors of a base of quality
+# v in millionths -- the literals the library holds (ffq_ee_micro_table)
+EE_MICRO = (1000000, 794328, 630957, 501187, 398107, 316228, 251189, 199526, 158489, 125893,
+            100000, 79433, 63096, 50119, 39811, 31623, 25119, 19953, 15849, 12589,
+            10000, 7943, 6310, 5012, 3981, 3162, 2512, 1995, 1585, 1259,
+            1000, 794, 631, 501, 398, 316, 251, 200, 158, 126,
+            100, 79, 63, 50, 40, 32, 25, 20, 16, 13,
+            10, 8, 6, 5, 4, 3, 3, 2, 2, 1, 1, 1, 1, 1) + (0,) * 32
+_EE_MICRO_NP = np.array(EE_MICRO, dtype=np.int64)
+
+
+class ContentRules:
+    """What a read is dropped for besides its length -- cutadapt's --max-n and --max-ee, fastp's -n, -e, -q / -u and -y -- as
+    ffq_table_select_reads takes it (include/ffq.h states the rule; this class is its host statement).  With v[i] =
+    clamp(quality[i] - qual_base, 0, 95), a read of n bases is dropped by the FIRST of these that fails:
+
+        2 "n"                max_n: more than max_n bases are 'N' or 'n'
+        3 "mean_quality"     min_mean_quality (1..95): sum(v) < min_mean_quality * n
+        4 "unqualified"      max_unqualified_percent (0..100): 100 * #{v[i] < qualified_quality} > max_unqualified_percent * n
+        5 "expected_errors"  max_expected_errors (a float, kept as millionths: max_ee_micro = int(round(x * 1e6))):
+                             sum(EE_MICRO[v[i]]) > max_ee_micro
+        6 "complexity"       min_complexity (1..100): n >= 2 and 100 * #{i < n - 1: seq[i] != seq[i + 1]} < min_complexity * (n - 1)
+
+    (rule 1, "length", is the length filter's and is not this class's).  None switches a rule off.  A read of length 0
+    passes all of them.  Integers throughout."""
+
+    REASONS = ("length", "n", "mean_quality", "unqualified", "expected_errors", "complexity")
+
+    def __init__(self, max_n=None, min_mean_quality=None, qualified_quality=15, max_unqualified_percent=None,
+                 max_expected_errors=None, min_complexity=None, qual_base=33):
+        def ranged(name, x, lo, hi, off):
+            if x is None:
+                return off
+            x = int(x)
+            if not lo <= x <= hi:
+                raise ValueError("%s is %d..%d (None: off)" % (name, lo, hi))
+            return x
+        self.max_n = ranged("max_n", max_n, 0, (1 << 31) - 1, -1)
+        self.min_mean_qual = ranged("min_mean_quality", min_mean_quality, 1, 95, 0)
+        self.qualified_qual = ranged("qualified_quality", 15 if qualified_quality is None else qualified_quality, 0, 95, 15)
+        self.max_unqualified_pct = ranged("max_unqualified_percent", max_unqualified_percent, 0, 100, -1)
+        self.min_complexity_pct = ranged("min_complexity", min_complexity, 1, 100, 0)
+        self.qual_base = ranged("qual_base", 33 if qual_base is None else qual_base, 0, 255, 33)
+        if max_expected_errors is None:
+            self.max_ee_micro = -1
+        else:
+            x = float(max_expected_errors)
+            if not 0 <= x <= 9.0e12:              # (also refuses NaN)
+                raise ValueError("max_expected_errors is a number of errors >= 0 (None: off)")
+            self.max_ee_micro = int(round(x * 1e6))
+        self._v = bytes(min(max(b - self.qual_base, 0), 95) for b in range(256))
+
+    @property
+    def active(self):
+        """Is one of the rules switched on?"""
+        return (self.max_n >= 0 or self.min_mean_qual > 0 or self.max_unqualified_pct >= 0 or self.max_ee_micro >= 0
+                or self.min_complexity_pct > 0)
+
+    def verdict(self, sequence, quality):
+        """0 if the rules keep the read, else the number (2..6, REASONS[number - 1]) of the first rule that drops it.
+        `sequence` and `quality` are bytes of one length."""
+        n = len(sequence)
+        if len(quality) != n:
+            raise ValueError("sequence and quality differ in length")
+        if n == 0:
+            return 0
+        if self.max_n >= 0 and sequence.count(b"N") + sequence.count(b"n") > self.max_n:
+            return 2
+        v = np.frombuffer(bytes(quality).translate(self._v), dtype=np.uint8)
+        if self.min_mean_qual > 0 and int(v.sum(dtype=np.int64)) < self.min_mean_qual * n:
+            return 3
+        if self.max_unqualified_pct >= 0 and 100 * int(np.count_nonzero(v < self.qualified_qual)) > self.max_unqualified_pct * n:
+            return 4
+        if self.max_ee_micro >= 0 and int(_EE_MICRO_NP[v].sum()) > self.max_ee_micro:
+            return 5
+        if self.min_complexity_pct > 0 and n >= 2:
+            s = np.frombuffer(sequence, dtype=np.uint8)
+            if 100 * int(np.count_nonzero(s[1:] != s[:-1])) < self.min_complexity_pct * (n - 1):
+                return 6
+        return 0
+
+    def verdict_pos(self, buf, pos):
+        """(verdict, judged) of one row of positions into `buf`: a row the rules do not apply to (stats_eligible: a wrapped
+        record, positions outside the buffer, lines of two lengths) is kept and not judged."""
+        if not stats_eligible(buf, pos):
+            return 0, False
+        return self.verdict(buf[pos[2]:pos[3]], buf[pos[4]:pos[5]]), True
+
+
+class entryfunc_contentfilter(entryfunc_lengthfilter):
+    """entryfunc_lengthfilter that also drops a record for what is in it: `rules` is a ContentRules, applied to a record
+    whose length min_len / max_len keep (rows the rules do not apply to -- wrapped records -- go by their length alone).
+    The item is None for a dropped record and the `column` of a kept one; yield_dropped=False leaves the Nones out.
+
+    readfastq_iter recognises the unchanged class when the scanner is the GPU one and judges every fill's rows on the
+    device (ffq_stream_set_content + ffq_stream_set_filter); a subclass with a __call__ of its own is called per record.
+    Same items, same order, with any scanner."""
+
+    def __init__(self, rules, min_len=None, max_len=None, column="sequence", yield_dropped=True):
+        if not isinstance(rules, ContentRules):
+            raise TypeError("rules must be a ContentRules")
+        super().__init__(None, min_len, max_len, column, yield_dropped)
+        self.rules = rules
+
+    def __call__(self, buf, pos, globaloffset=None):
+        if not self.keeps(pos[3] - pos[2]) or self.rules.verdict_pos(buf, pos)[0]:
+            return None
+        return entryfunc_lengthfilter.__call__(self, buf, pos, globaloffset)
+
+
+def _pushes_down_content(entryfunc):
+    """... and its own content filter, unchanged, with rules of the unchanged class."""
+    if not isinstance(entryfunc, entryfunc_contentfilter):
+        return False
+    t, r = type(entryfunc), type(entryfunc.rules)
+    return ((t is entryfunc_contentfilter or (t.__call__ is entryfunc_contentfilter.__call__ and
+                                              getattr(t, "keeps", None) is entryfunc_lengthfilter.keeps))
+            and (r is ContentRules or (r.verdict is ContentRules.verdict and r.verdict_pos is ContentRules.verdict_pos)))
+
+
 class FilterReport:
     """What filter_fastq(report=...) fills: the statistics of the reads as they came in (`before`) and as they were written
-    (`after`: behind the trims and the length filter)."""
+    (`after`: behind the trims and the filters), and `dropped`: how many records each reason (ContentRules.REASONS) dropped."""
 
     def __init__(self, max_cycles=512):
         self.max_cycles = int(max_cycles)
         self.before = FastqStats(self.max_cycles)
         self.after = FastqStats(self.max_cycles)
+        self.dropped = dict.fromkeys(ContentRules.REASONS, 0)
 
 
 def fastq_stats(fh: typing.BinaryIO, fbufsize: int = 1 << 24, qual_base: int = 33, max_cycles: int = 512,
@@ -848,7 +972,7 @@ FilterResult = namedtuple('FilterResult', 'records_in records_out bases_removed 
 
 def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1 << 24, quality_cutoff=None,
                  qual_base: int = 33, min_len=None, max_len=None, entrypos: typing.Optional[typing.Callable] = None,
-                 adapter=None, err_permille: int = 100, min_overlap: int = 3, report=None) -> FilterResult:
+                 adapter=None, err_permille: int = 100, min_overlap: int = 3, report=None, content=None) -> FilterResult:
     """Trim, filter and WRITE a FASTQ stream: the file `cutadapt -q 20 -m 30` leaves behind, which is what the tables of
     positions of the reference's user guide are kept for in the end ("to avoid saving a FASTQ file after each filtering or
     read-trimming step", doc/user-guide.rst:196-204).  Every record of `fh` is quality-trimmed (quality_cutoff: an int --
@@ -876,8 +1000,17 @@ def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1
 
     report: a FilterReport; its `before` is filled with the statistics of the records as read (qual_base as given here),
     its `after` with those of the records as written -- counted on the device beside the rest (ffq_stream_set_stats, no
-    host wait per fill) and read once at the end, or record by record with another scanner.  None: nothing is counted."""
+    host wait per fill) and read once at the end, or record by record with another scanner.  None: nothing is counted.
+    Its `dropped` says how many records each reason dropped ("length" and the content rules'), with or without `content`.
+
+    content: a ContentRules; a record that its trimmed length keeps is dropped by the first of its rules that fails (`cutadapt
+    --max-n --max-ee`, `fastp -n -e -q -u -y`): judged on the device with the GPU scanner (ffq_stream_set_content), by
+    ContentRules.verdict_pos with any other.  Rows the rules do not apply to (wrapped records) go by their length alone."""
+    if content is not None and not isinstance(content, ContentRules):
+        raise TypeError("content must be a ContentRules")
+    dropped = dict.fromkeys(ContentRules.REASONS, 0)
     if report is not None:
+        report.dropped = dropped
         report.before = FastqStats(report.max_cycles, qual_base)
         report.after = FastqStats(report.max_cycles, qual_base)
     trim = None
@@ -901,6 +1034,8 @@ def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1
                 st.set_trim(trim.cutoff_back, trim.cutoff_front, trim.qual_base)
             if cutter is not None:
                 st.set_adapter(cutter.adapter, cutter.err_permille, cutter.min_overlap)
+            if content is not None:
+                st.set_content(content)
             if lo is not None or hi is not None:
                 st.set_filter(lo, hi)
             st.set_render()
@@ -911,6 +1046,9 @@ def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1
                 if nb:
                     fh_out.write(memoryview(text))
                 n_in += st.selected()[1] if st.filtered else rows.shape[0]
+                if st.filtered:
+                    for reason, k in zip(ContentRules.REASONS, st.filter_counts()[1:7]):
+                        dropped[reason] += k
                 n_out += rendered
                 n_bytes += nb
                 if trim is not None:
@@ -937,7 +1075,13 @@ def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1
         cut = length - (pos[3] - pos[2])
         length -= cut
         if (lo is not None and length < lo) or (hi is not None and length > hi):
+            dropped["length"] += 1
             return cut, None
+        if content is not None:
+            v = content.verdict_pos(buf, pos)[0]
+            if v:
+                dropped[ContentRules.REASONS[v - 1]] += 1
+                return cut, None
         if report is not None:
             report.after.add_pos(buf, pos)
         return cut, b"".join((b"@", buf[(pos[0] + 1):pos[1]], b"\n", buf[pos[2]:pos[3]], b"\n+\n", buf[pos[4]:pos[5]], b"\n"))

@@ -98,7 +98,26 @@ SYMBOLS = (
     "ffq_table_render_fastq", "ffq_stream_set_render", "ffq_stream_rendered",
     "ffq_table_trim_adapter", "ffq_stream_set_adapter", "ffq_stream_adapter_trimmed",
     "ffq_table_stats", "ffq_stream_set_stats", "ffq_stream_stats",
+    "ffq_table_select_reads", "ffq_ee_micro_table", "ffq_stream_set_content", "ffq_stream_filter_counts",
 )
+
+
+FILTER_COUNTS = 8            # FFQ_FILTER_COUNTS: rows kept, dropped by rule 1..6, not judged by content
+
+
+class ContentRulesStruct(ctypes.Structure):
+    """struct ffq_content_rules (include/ffq.h)."""
+    _fields_ = [("qual_base", ctypes.c_int32), ("max_n", ctypes.c_int32), ("min_mean_qual", ctypes.c_int32),
+                ("qualified_qual", ctypes.c_int32), ("max_unqualified_pct", ctypes.c_int32),
+                ("min_complexity_pct", ctypes.c_int32), ("max_ee_micro", ctypes.c_int64)]
+
+
+def content_rules_struct(rules):
+    """What the library takes for `rules`: None, a ContentRulesStruct, or anything with its seven fields as attributes
+    (fastqandfurious.ContentRules)."""
+    if rules is None or isinstance(rules, ContentRulesStruct):
+        return rules
+    return ContentRulesStruct(*(int(getattr(rules, name)) for name, _ in ContentRulesStruct._fields_))
 
 
 class ScanResult(ctypes.Structure):
@@ -331,6 +350,11 @@ def lib():
         L.ffq_table_trim_quality.argtypes = [vp, vp, i64, i32, i64, vp, i64, i32, i32, i32, vp, P(i64)]
         L.ffq_table_trim_adapter.argtypes = [vp, vp, i64, i32, i64, vp, i64, ctypes.c_char_p, i32, i32, i32, vp, P(i64)]
         L.ffq_table_stats.argtypes = [vp, vp, i64, i32, i64, vp, i64, i32, i32, i32, vp, P(i64)]
+        L.ffq_table_select_reads.argtypes = [vp, vp, i64, i32, i64, vp, i64, i64, i64, P(ContentRulesStruct), vp, vp, P(i64), P(i64)]
+        L.ffq_ee_micro_table.argtypes = []
+        L.ffq_ee_micro_table.restype = P(u32)
+        L.ffq_stream_set_content.argtypes = [vp, P(ContentRulesStruct)]
+        L.ffq_stream_filter_counts.argtypes = [vp, P(i64)]
         L.ffq_table_render_fastq.argtypes = [vp, vp, i64, i32, i64, vp, i64, vp, i64, vp, P(i64)]
         L.ffq_table_gather_column.argtypes = [vp, vp, i64, i32, i64, vp, i64, i32, i32, i32, i32, vp, i64, vp, P(i64)]
         L.ffq_stream_open.argtypes = [vp, i32, i64, P(vp)]
@@ -650,6 +674,24 @@ class Context:
         check(lib().ffq_table_select_seqlen_idx(self.handle, ctypes.c_void_p(d_table), int(n_rows), int(min_len), int(max_len),
                                                 ctypes.c_void_p(d_out), ctypes.c_void_p(d_idx), ctypes.byref(k)))
         return k.value
+
+    def table_select_reads(self, d_buf, n_bytes, d_table, n_rows, d_out, rules=None, min_len=None, max_len=None, d_idx=None,
+                           sentinel=True, add=None):
+        """Rows of a device table kept by their length and by what is in the read (ffq_table_select_reads; include/ffq.h
+        states the rule), in order, into d_out, with d_idx[i] = the ordinal of kept row i (None: not wanted).  rules: a
+        fastqandfurious.ContentRules, a ContentRulesStruct, or None (the length alone: d_buf may then be 0).  Raw device
+        pointers; d_buf / n_bytes / sentinel / add as for table_gather_column.  Returns (rows kept, the eight counts: kept,
+        dropped by rule 1..6, not judged by content)."""
+        add = _add(add, sentinel)
+        lo, hi = length_bounds(min_len, max_len)
+        r = content_rules_struct(rules)
+        k = ctypes.c_int64(0)
+        counts = (ctypes.c_int64 * FILTER_COUNTS)()
+        check(lib().ffq_table_select_reads(self.handle, ctypes.c_void_p(d_buf) if d_buf else None, int(n_bytes), int(bool(sentinel)),
+                                           int(add), ctypes.c_void_p(d_table), int(n_rows), lo, hi,
+                                           None if r is None else ctypes.byref(r), ctypes.c_void_p(d_out),
+                                           ctypes.c_void_p(d_idx) if d_idx else None, ctypes.byref(k), counts))
+        return k.value, [int(x) for x in counts]
 
     COLUMNS = {"header": (0, 1, 1), "sequence": (2, 0, 3), "quality": (4, 0, 5)}
 
@@ -985,6 +1027,21 @@ class _Stream:
         lo, hi = length_bounds(min_seq_len, max_seq_len)
         check(lib().ffq_stream_set_filter(self._h, lo, hi, self.COLUMNS[column], int(value_add)))
         self.filtered = True
+
+    def set_content(self, rules):
+        """Content rules in the stream (ffq_stream_set_content; before the first fill): every fill's rows are judged on the
+        device by ffq_table_select_reads, as the trims left them; a stream without a filter gets one with open bounds and no
+        column (set_filter may come before or after and keeps the rules).  rules: as for Context.table_select_reads."""
+        r = content_rules_struct(rules)
+        check(lib().ffq_stream_set_content(self._h, None if r is None else ctypes.byref(r)))
+        self.filtered = True
+
+    def filter_counts(self):
+        """The eight counts (rows kept, dropped by rule 1..6, not judged by content) of the fill the iteration has just
+        yielded; any filtered stream."""
+        counts = (ctypes.c_int64 * FILTER_COUNTS)()
+        check(lib().ffq_stream_filter_counts(self._h, counts))
+        return [int(x) for x in counts]
 
     def set_trim(self, cutoff_back, cutoff_front=0, qual_base=33):
         """Quality trimming in the stream (ffq_stream_set_trim; before the first fill): every fill's rows are trimmed on

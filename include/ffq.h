@@ -371,6 +371,59 @@ int ffq_table_stats(ffq_ctx *ctx, const uint8_t *d_buf, int64_t n_bytes, int sen
                     const int64_t *d_table, int64_t n_rows, int qual_base, int max_cycles,
                     int accumulate, uint64_t *d_stats, int64_t head[FFQ_STATS_HEAD]);
 
+/* Rows kept or dropped for what is IN the read: cutadapt's --max-n and --max-ee, fastp's -n, -e, -q / -u and -y, evaluated
+ * on the table with the length filter in front of them.  The content rules: */
+typedef struct ffq_content_rules {
+    int32_t qual_base;            /* 0..255 */
+    int32_t max_n;                /* -1: off */
+    int32_t min_mean_qual;        /* 0: off; 1..95 */
+    int32_t qualified_qual;       /* 0..95: a base with v < this is "unqualified" */
+    int32_t max_unqualified_pct;  /* -1: off; 0..100 */
+    int32_t min_complexity_pct;   /* 0: off; 1..100 */
+    int64_t max_ee_micro;         /* -1: off; expected errors in millionths */
+} ffq_content_rules;
+/* For one row, seq = buf[pos2:pos3], q = buf[pos4:pos5], n = len(seq), v[i] = clamp(q[i] - qual_base, 0, 95) -- the v of
+ * ffq_table_stats.  The quantities a row is judged by:
+ *     nN = number of i with seq[i] equal to 'N' or 'n'
+ *     sv = sum of v[i]
+ *     u  = number of i with v[i] < qualified_qual
+ *     ee = sum of FFQ_EE_MICRO[v[i]]
+ *     d  = number of i < n - 1 with seq[i] != seq[i + 1]
+ * FFQ_EE_MICRO[v] = floor(1e6 * 10^(-v/10) + 0.5), 96 constants written into the source as literals (no entry lies closer
+ * than 0.001 to a rounding boundary): ffq_ee_micro_table() returns them.
+ * A row gets a VERDICT: the first rule that fails, in this order, or 0 for kept.
+ *     1 length           pos3 - pos2 < min_len or > max_len: the test of ffq_table_select_seqlen, on any row, eligible or
+ *                        not.  A row that fails it has none of its bytes read.
+ *     2 N                max_n >= 0 and nN > max_n
+ *     3 mean quality     min_mean_qual > 0 and sv < min_mean_qual * n
+ *     4 unqualified      max_unqualified_pct >= 0 and 100 * u > max_unqualified_pct * n
+ *     5 expected errors  max_ee_micro >= 0 and ee > max_ee_micro
+ *     6 complexity       min_complexity_pct > 0 and n >= 2 and 100 * d < min_complexity_pct * (n - 1)
+ * Rules 2 to 6 apply only to rows that are ELIGIBLE exactly as for ffq_table_stats (positions inside the buffer and in
+ * order, the two lines of one length, no line with bytes in it beginning at the sentinel's coordinate 0, no "\n" in the
+ * sequence or the quality).  Every other row -- wrapped records, FASTA rows (-1), rows that point outside the buffer -- is
+ * judged by its length alone and counted as "not judged".  A row of length 0 is eligible and passes rules 2 to 6.
+ * Everything is integer arithmetic; sv, ee and the products are carried in 64 bits wherever a row can be long.  No byte
+ * outside [d_buf, d_buf + n_bytes) is read.  Rows are independent: any order, repeated, overlapping, written by hand.
+ *
+ * ffq_table_select_reads writes the kept rows (verdict 0), in order, to d_out (n_rows rows of room; not d_table; both
+ * tables 16-byte aligned) and d_idx[i] = the ordinal in d_table of kept row i (NULL: none); *n_out = rows kept.  counts:
+ *     [0] rows kept; [1]..[6] rows dropped by rule 1..6; [0..6] sum to n_rows and *n_out == counts[0];
+ *     [7] rows not judged by content although a content rule is on; they are also counted in [0] or [1].  As a row dropped
+ *         by its length has no byte read, such a row counts in [7] only if its POSITIONS already make it ineligible (a
+ *         wrapped record that is too short or too long counts in [1] alone).
+ * d_buf / n_bytes / sentinel / add: as for ffq_table_gather_column.  rules == NULL, or rules with every content rule off:
+ * the call is ffq_table_select_seqlen_idx -- the same launches, rows and d_idx, no kernel reads the buffer and d_buf may be
+ * NULL; only counts[0] and [1] are non-zero.  n_rows == 0 is valid.  One host wait.  FFQ_E_ARG: a field outside its range, a
+ * scan pending on the context, d_buf NULL with n_bytes > 0 while a content rule is on.  Not done: paired-end files, the
+ * fraction form of --max-n.                                                                                            */
+#define FFQ_FILTER_COUNTS 8
+int ffq_table_select_reads(ffq_ctx *ctx, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
+                           const int64_t *d_table, int64_t n_rows, int64_t min_len, int64_t max_len,
+                           const ffq_content_rules *rules, int64_t *d_out, int64_t *d_idx, int64_t *n_out,
+                           int64_t counts[FFQ_FILTER_COUNTS]);
+const uint32_t *ffq_ee_micro_table(void);
+
 /* FASTQ text from (buffer, table): what a pipeline that excluded reads by deleting rows and trimmed them by editing rows
  * ("to avoid saving a FASTQ file after each filtering or read-trimming step", doc/user-guide.rst:196-204) saves at its
  * end.  Row p renders as
@@ -486,6 +539,15 @@ int  ffq_stream_trimmed(ffq_stream *s, int64_t stats[3]);
  * ffq_stream_next has just returned.                                                                                  */
 int  ffq_stream_set_adapter(ffq_stream *s, const uint8_t *adapter, int adapter_len, int err_permille, int min_overlap);
 int  ffq_stream_adapter_trimmed(ffq_stream *s, int64_t stats[3]);
+/* Content rules in the stream (the rules of ffq_stream_set_trim: before the first ffq_stream_next, not with
+ * FFQ_F_DECODE_QUAL): the select of every fill judges the rows by ffq_table_select_reads -- as the trims left them, which
+ * is cutadapt's order -- and everything behind it (statistics OUT, the render, the column gather, ffq_stream_selected) sees
+ * the kept rows.  A stream without a filter gets one with unbounded length and no column; ffq_stream_set_filter and this
+ * call may come in either order, each keeps what the other one set.  `rules` is copied.  ffq_stream_filter_counts: the
+ * eight counts of the fill ffq_stream_next has just returned, on any filtered stream (without content rules only [0] and
+ * [1] are non-zero).                                                                                                  */
+int  ffq_stream_set_content(ffq_stream *s, const ffq_content_rules *rules);
+int  ffq_stream_filter_counts(ffq_stream *s, int64_t counts[FFQ_FILTER_COUNTS]);
 /* Statistics in the stream (any kind of stream, also with FFQ_F_DECODE_QUAL, a filter, a gathered column and a render;
  * before the first ffq_stream_next): every fill's table is counted on the device (ffq_table_stats) into a block the stream
  * owns, summed over all fills.  FFQ_STATS_IN: the rows as scanned, before any trim; FFQ_STATS_OUT: the rows as handed out,
