@@ -13,6 +13,7 @@
 #include "ffq_adapter.h"
 #include "ffq_stats.h"
 #include "ffq_filter.h"
+#include "ffq_pair.h"
 #include "ffq_render.h"
 #include "ffq_pool.h"
 #include "ffq_mem.h"
@@ -199,6 +200,11 @@ struct ffq_ctx {
     DevBuf<FilterBlock> d_filter;       // ffq_table_select_reads: the call's counters and their pinned mirror
     PinBuf<FilterBlock> h_filter;
     DevBuf<uint8_t> filter_verdict;     //   a verdict byte per row
+    DevBuf<uint8_t> filter_verdict2;    //   ... and per row of the second mate (ffq_table_select_pairs; h_filter holds two blocks)
+    DevBuf<PairBlock> d_pair;           // ffq_table_select_pairs: the call's pair counts and their pinned mirror
+    PinBuf<PairBlock> h_pair;
+    DevBuf<PairNamesBlock> d_names;     // ffq_table_pair_names: the call's counters and their pinned mirror
+    PinBuf<PairNamesBlock> h_names;
     DevBuf<RenderBlock> d_render;       // ffq_table_render_fastq: the call's counters and their pinned mirror
     PinBuf<RenderBlock> h_render;
     DevBuf<int64_t> render_list;        //   (row, place in the output) of the rows left to the wave-per-row launch
@@ -291,7 +297,11 @@ static int ctx_create_impl(int device, ffq_ctx *share, ffq_ctx **out)
     if (e == hipSuccess) e = c->h_rows.grow(1);
     if (e == hipSuccess) e = c->h_stats.grow(STATS_HEAD);
     if (e == hipSuccess) e = c->d_filter.grow(1);
-    if (e == hipSuccess) e = c->h_filter.grow(1);
+    if (e == hipSuccess) e = c->h_filter.grow(2);
+    if (e == hipSuccess) e = c->d_pair.grow(1);
+    if (e == hipSuccess) e = c->h_pair.grow(1);
+    if (e == hipSuccess) e = c->d_names.grow(1);
+    if (e == hipSuccess) e = c->h_names.grow(1);
     if (e == hipSuccess) e = c->d_render.grow(1);
     if (e == hipSuccess) e = c->h_render.grow(1);
     if (e == hipSuccess) e = c->fa_hdr.grow(1);
@@ -2179,6 +2189,116 @@ extern "C" int ffq_table_select_reads(ffq_ctx *c, const uint8_t *d_buf, int64_t 
     HIPCHK(hipStreamSynchronize(st));
     for (int i = 0; i < FFQ_FILTER_COUNTS; i++) counts[i] = (int64_t)c->h_filter->cnt[i];
     *n_out = counts[0];
+    return FFQ_OK;
+}
+
+// ---- two tables whose rows are mates (csrc/ffq_pair.h) ------------------------------------------
+static_assert(PAIR_ANY == FFQ_PAIR_ANY && PAIR_BOTH == FFQ_PAIR_BOTH && PAIR_FIRST == FFQ_PAIR_FIRST, "include/ffq.h");
+
+constexpr int PAIR_GRID_COUNT = 1024;
+
+static bool view_ok(const ffq_table_view *m, int64_t n_rows)
+{
+    return m && m->n_bytes >= 0 && (n_rows == 0 || m->d_table) && (reinterpret_cast<uintptr_t>(m->d_table) & 15) == 0;
+}
+
+extern "C" int ffq_table_select_pairs(ffq_ctx *c, const ffq_table_view *m1, const ffq_table_view *m2, int64_t n_pairs,
+                                      const int64_t len_bounds[4], const ffq_content_rules *rules1, const ffq_content_rules *rules2,
+                                      int pair_filter, int64_t *d_out1, int64_t *d_out2, int64_t *d_idx, int64_t *n_out,
+                                      int64_t hist1[FFQ_FILTER_COUNTS], int64_t hist2[FFQ_FILTER_COUNTS], int64_t pairs[5])
+{
+    static const char *const who = "ffq_table_select_pairs";
+    mark_other(c);
+    bool on[2] = {false, false};
+    FilterRules R[2] = {};
+    int rc = content_arg(who, rules1, &on[0], &R[0]);
+    if (!rc) rc = content_arg(who, rules2, &on[1], &R[1]);
+    if (rc) return rc;
+    if (pair_filter != FFQ_PAIR_ANY && pair_filter != FFQ_PAIR_BOTH && pair_filter != FFQ_PAIR_FIRST)
+        return fail(FFQ_E_ARG, "%s: pair_filter is FFQ_PAIR_ANY, FFQ_PAIR_BOTH or FFQ_PAIR_FIRST", who);
+    if (!c || !len_bounds || !n_out || !hist1 || !hist2 || !pairs || n_pairs < 0 || !view_ok(m1, n_pairs) || !view_ok(m2, n_pairs) ||
+        (n_pairs > 0 && (!d_out1 || !d_out2)))
+        return fail(FFQ_E_ARG, "%s: bad argument", who);
+    if (((reinterpret_cast<uintptr_t>(d_out1) | reinterpret_cast<uintptr_t>(d_out2)) & 15) != 0)
+        return fail(FFQ_E_ARG, "%s: tables must be 16-byte aligned", who);
+    if (c->pend.active) return fail(FFQ_E_ARG, "%s: a scan is pending on this context", who);
+    const ffq_table_view *m[2] = {m1, m2};
+    int64_t *hist[2] = {hist1, hist2};
+    const int n_judged = pair_filter == FFQ_PAIR_FIRST ? 1 : 2;
+    for (int k = 0; k < n_judged; k++)
+        if (on[k] && m[k]->n_bytes > 0 && !m[k]->d_buf) return fail(FFQ_E_ARG, "%s: no buffer to judge the rows of mate %d by", who, k + 1);
+    if (n_pairs > 0 && (d_out1 == m1->d_table || d_out2 == m2->d_table || d_out1 == d_out2 || d_out1 == m2->d_table || d_out2 == m1->d_table))
+        return fail(FFQ_E_ARG, "%s: d_out1 and d_out2 must not be one of the tables, or each other", who);
+    for (int i = 0; i < FFQ_FILTER_COUNTS; i++) hist1[i] = hist2[i] = 0;
+    for (int i = 0; i < PAIR_COUNTS; i++) pairs[i] = 0;
+    HIPCHK(hipSetDevice(c->device));
+    *n_out = 0;
+    if (n_pairs == 0) return FFQ_OK;
+    const int64_t nblk = (n_pairs + 255) / 256;
+    // (everything is grown before anything is enqueued: growing waits for the stream)
+    rc = grow_dev(c, c->rows_list, n_pairs);
+    if (!rc) rc = grow_dev(c, c->filter_verdict, n_pairs);
+    if (!rc && n_judged == 2) rc = grow_dev(c, c->filter_verdict2, n_pairs);
+    if (!rc) rc = grow_dev(c, c->sel_cnt, nblk);
+    if (!rc) rc = grow_dev(c, c->sel_base, nblk);
+    if (rc) return rc;
+    hipStream_t st = c->stream;
+    uint8_t *verdict[2] = {c->filter_verdict.p, n_judged == 2 ? c->filter_verdict2.p : nullptr};
+    // the judging, once per mate: the list of long rows and the counters are the call's, cleared in front of each mate
+    for (int k = 0; k < n_judged; k++) {
+        const ffq_table_view *v = m[k];
+        const int s = v->sentinel ? 1 : 0;
+        const int64_t lo = len_bounds[2 * k], hi = len_bounds[2 * k + 1];
+        HIPCHK(hipMemsetAsync(c->d_filter, 0, sizeof(FilterBlock), st));
+        if (on[k]) {
+            hipLaunchKernelGGL(k_filter_rows, dim3(rows_grid(n_pairs, FILTER_WG / FILTER_G, FILTER_GRID_SHORT)), dim3(FILTER_WG), 0, st,
+                               v->d_buf, v->n_bytes, s, v->add, v->d_table, n_pairs, lo, hi, R[k], verdict[k], c->rows_list.p, c->d_filter.p);
+            hipLaunchKernelGGL(k_filter_long, dim3(rows_grid(n_pairs, FILTER_WG / 64, FILTER_GRID_LONG)), dim3(FILTER_WG), 0, st,
+                               v->d_buf, v->n_bytes, s, v->add, v->d_table, R[k], verdict[k], (const int64_t *)c->rows_list, c->d_filter.p);
+        } else {
+            hipLaunchKernelGGL(k_pair_len, dim3(rows_grid(n_pairs, 256, FILTER_GRID_SHORT)), dim3(256), 0, st, v->d_table, n_pairs, lo, hi,
+                               verdict[k], c->d_filter.p);
+        }
+        HIPCHK(hipMemcpyAsync(c->h_filter.p + k, c->d_filter, sizeof(FilterBlock), hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipMemsetAsync(c->d_pair, 0, sizeof(PairBlock), st));
+    hipLaunchKernelGGL(k_pair_count, dim3((unsigned)std::min<int64_t>(nblk, PAIR_GRID_COUNT)), dim3(256), 0, st, (const uint8_t *)verdict[0],
+                       (const uint8_t *)verdict[1], n_pairs, nblk, pair_filter, c->sel_cnt.p, c->d_pair.p);
+    if ((rc = launch_scan_u32(c, st, (const unsigned int *)c->sel_cnt, nblk, c->sel_base, (long long *)c->d_word.p))) return rc;
+    hipLaunchKernelGGL(k_pair_scatter, dim3((unsigned)nblk), dim3(256), 0, st, m1->d_table, m2->d_table, (const uint8_t *)verdict[0],
+                       (const uint8_t *)verdict[1], n_pairs, pair_filter, (const long long *)c->sel_base, d_out1, d_out2, d_idx);
+    HIPCHK(hipMemcpyAsync(c->h_pair, c->d_pair, sizeof(PairBlock), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    for (int k = 0; k < n_judged; k++)
+        for (int i = 0; i < FFQ_FILTER_COUNTS; i++) hist[k][i] = (int64_t)c->h_filter.p[k].cnt[i];
+    for (int i = 0; i < PAIR_COUNTS; i++) pairs[i] = (int64_t)c->h_pair->cnt[i];
+    *n_out = pairs[0];
+    return FFQ_OK;
+}
+
+extern "C" int ffq_table_pair_names(ffq_ctx *c, const ffq_table_view *m1, const ffq_table_view *m2, int64_t n_pairs, int64_t out[4])
+{
+    static const char *const who = "ffq_table_pair_names";
+    mark_other(c);
+    if (!c || !out || n_pairs < 0 || !view_ok(m1, n_pairs) || !view_ok(m2, n_pairs)) return fail(FFQ_E_ARG, "%s: bad argument", who);
+    if ((m1->n_bytes > 0 && !m1->d_buf) || (m2->n_bytes > 0 && !m2->d_buf)) return fail(FFQ_E_ARG, "%s: no buffer to read the headers from", who);
+    if (c->pend.active) return fail(FFQ_E_ARG, "%s: a scan is pending on this context", who);
+    HIPCHK(hipSetDevice(c->device));
+    out[0] = out[1] = out[2] = 0; out[3] = -1;
+    if (n_pairs == 0) return FFQ_OK;
+    hipStream_t st = c->stream;
+    *c->h_names.p = PairNamesBlock{0, 0, 0, (unsigned long long)n_pairs};
+    HIPCHK(hipMemcpyAsync(c->d_names, c->h_names, sizeof(PairNamesBlock), hipMemcpyHostToDevice, st));
+    const PairSide A = {m1->d_buf, m1->n_bytes, m1->sentinel ? 1 : 0, m1->add, m1->d_table};
+    const PairSide B = {m2->d_buf, m2->n_bytes, m2->sentinel ? 1 : 0, m2->add, m2->d_table};
+    hipLaunchKernelGGL(k_pair_names, dim3(rows_grid(n_pairs, PAIR_NAMES_WG / ROWS_G, EDIT_GRID_SHORT)), dim3(PAIR_NAMES_WG), 0, st, A, B,
+                       n_pairs, c->d_names.p);
+    HIPCHK(hipMemcpyAsync(c->h_names, c->d_names, sizeof(PairNamesBlock), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    out[0] = (int64_t)c->h_names->equal; out[1] = (int64_t)c->h_names->different; out[2] = (int64_t)c->h_names->not_compared;
+    out[3] = c->h_names->different ? (int64_t)c->h_names->first : -1;
     return FFQ_OK;
 }
 

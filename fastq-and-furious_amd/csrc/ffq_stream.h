@@ -32,6 +32,7 @@
 //                       object (BytesIO, bz2, lzma ...) read with readinto(), no bytes copy
 #pragma once
 #include "ffq_gzread.h"
+#include "ffq_pairwalk.h"
 
 #include <chrono>
 #include <condition_variable>
@@ -149,6 +150,7 @@ struct ffq_stream {
     int64_t fill_start = 0, fill_len = 0;   // that fill is slot.h[fill_start, fill_start + fill_len)
     int64_t carry_from = 0;             // fill-relative offset the next fill starts with (buf[offset:], :277)
     bool done = false, failed = false;
+    bool paired = false;                // a pair walks this stream (ffq_pair_open): ffq_stream_next is refused
     int64_t globaloffset = -1;          // readfastq_iter :242
     int64_t last_nq = 0;
     int last_path = -1;                 // ffq_scan_result.path of the last fill's scan
@@ -893,11 +895,45 @@ static int stream_chain(ffq_stream *s, const Fill &f, const ffq_scan_result &res
     return FFQ_OK;
 }
 
+// ---- the two pieces of a fill that ffq_stream_next and the pair walk (ffq_pair_next) share ---------------------------------
+// advance: the stream's next chunk waited for, taken behind the carry and scanned -- the fill and the scan's result
+static int stream_advance(ffq_stream *s, Fill *f, ffq_scan_result *res)
+{
+    const int64_t k = s->cur + 1;
+    const double tp0 = s->prof ? stream_now() : 0;
+    int rc = stream_wait_chunk(s, k);
+    const double tp1 = s->prof ? stream_now() : 0;
+    if (!rc) rc = stream_take(s, k, f);
+    if (!rc) rc = stream_scan(s, *f, res);
+    if (s->prof) { s->t_feed += tp1 - tp0; s->t_scan += stream_now() - tp1; }
+    return rc;
+}
+
+// finish: the fill is handed out -- the stream remembers it, ends (*err_offset: the byte an error state names, else -1) or
+// sets up the refill: buf = buf[offset:] + next chunk (:277), globaloffset += offset (:275)
+static void stream_finish(ffq_stream *s, const Fill &f, const ffq_scan_result &res, int64_t *err_offset)
+{
+    s->cur += 1;
+    s->handed_pos = f.sl->end_pos;
+    s->fill_start = f.start; s->fill_len = f.len;
+    const int64_t ds = res.end_offset - f.mis;             // the iterator's `offset` at exit, fill-relative
+    *err_offset = -1;
+    if (res.end_state != FFQ_END_REFILL) {
+        if (res.end_state != FFQ_END_OK) *err_offset = s->globaloffset + ds;
+        s->done = true;
+        stream_stop_feeder(s);
+        return;
+    }
+    s->carry_from = ds;
+    s->globaloffset += ds;
+}
+
 extern "C" int ffq_stream_next(ffq_stream *s, const int64_t **h_rows, int64_t *n_rows, int *end_state,
                                int64_t *err_offset, const uint8_t **h_bytes, int64_t *n_bytes,
                                int64_t *bytes_offset)
 {
     if (!s || !h_rows || !n_rows || !end_state) return fail(FFQ_E_ARG, "ffq_stream_next: NULL argument");
+    if (s->paired) return fail(FFQ_E_ARG, "ffq_stream_next: the stream belongs to a pair (ffq_pair_open): ffq_pair_next walks it");
     ffq_ctx *c = s->c;
     StreamBufs *b = s->b;
     HIPCHK(hipSetDevice(c->device));
@@ -910,15 +946,10 @@ extern "C" int ffq_stream_next(ffq_stream *s, const int64_t **h_rows, int64_t *n
     if (s->done) return FFQ_OK;
     s->failed = true;                    // until this call gets through: an error leaves no half-advanced state behind
 
-    const int64_t k = s->cur + 1;
     Fill f;
     ffq_scan_result res;
     int64_t n_out = 0;
-    const double tp0 = s->prof ? stream_now() : 0;
-    int rc = stream_wait_chunk(s, k);
-    const double tp1 = s->prof ? stream_now() : 0;
-    if (!rc) rc = stream_take(s, k, &f);
-    if (!rc) rc = stream_scan(s, f, &res);
+    int rc = stream_advance(s, &f, &res);
     const double tp2 = s->prof ? stream_now() : 0;
     if (!rc) rc = stream_chain(s, f, res, &n_out);
     if (rc) return rc;
@@ -932,11 +963,8 @@ extern "C" int ffq_stream_next(ffq_stream *s, const int64_t **h_rows, int64_t *n
         HIPCHK(hipMemcpyAsync(b->qoff.h, b->qoff.d, (size_t)(res.n_records + 1) * 8, hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(hipStreamSynchronize(c->stream));
-    if (s->prof) { const double t = stream_now(); s->t_feed += tp1 - tp0; s->t_scan += tp2 - tp1; s->t_rows += t - tp2; }
+    if (s->prof) s->t_rows += stream_now() - tp2;
 
-    s->cur = k;
-    s->handed_pos = f.sl->end_pos;
-    s->fill_start = f.start; s->fill_len = f.len;
     *h_rows = b->tab.h;
     *n_rows = n_out;
     if (h_bytes) *h_bytes = f.sl->buf.h + f.start;
@@ -944,16 +972,228 @@ extern "C" int ffq_stream_next(ffq_stream *s, const int64_t **h_rows, int64_t *n
     // byte i of this fill is stream offset globaloffset + i (the sentinel of the first fill is -1)
     if (bytes_offset) *bytes_offset = s->globaloffset;
     *end_state = res.end_state;
-    const int64_t ds = res.end_offset - f.mis;             // the iterator's `offset` at exit, fill-relative
+    int64_t err = -1;
+    stream_finish(s, f, res, &err);
+    if (err_offset) *err_offset = err;
     s->failed = false;
-    if (res.end_state != FFQ_END_REFILL) {
-        if (res.end_state != FFQ_END_OK && err_offset) *err_offset = s->globaloffset + ds;
-        s->done = true;
-        stream_stop_feeder(s);
-        return FFQ_OK;
+    return FFQ_OK;
+}
+
+// ---- two streams whose records are mates: ffq_pair (include/ffq.h; the bookkeeping is csrc/ffq_pairwalk.h) ------------------
+static_assert(WALK_END_OK == FFQ_END_OK && WALK_END_REFILL == FFQ_END_REFILL && WALK_END_ERR_PAIR_COUNT == FFQ_END_ERR_PAIR_COUNT &&
+              WALK_END_ERR_PAIR_NAMES == FFQ_END_ERR_PAIR_NAMES, "include/ffq.h");
+
+struct PairMate {
+    ffq_stream *s = nullptr;
+    Fill f = {};                 // the fill its window lies in
+    bool have = false;
+    int64_t bytes_offset = 0;    // byte i of that fill is stream offset bytes_offset + i
+};
+
+struct ffq_pair {
+    ffq_ctx *c = nullptr;
+    PairMate m[2];
+    PairWalk w;
+    int mode = FFQ_PAIR_ANY;
+    bool check_names = true, failed = false;
+    Mirror<int64_t> idx;         // the ordinals, among the round's pairs, of the kept ones
+    int64_t last_pairs[5] = {0, 0, 0, 0, 0};
+    int64_t last_out = 0;
+};
+
+extern "C" int ffq_pair_open(ffq_stream *mate1, ffq_stream *mate2, int pair_filter, int check_names, ffq_pair **out)
+{
+    if (!mate1 || !mate2 || !out || mate1 == mate2) return fail(FFQ_E_ARG, "ffq_pair_open: two streams and a place for the pair");
+    *out = nullptr;
+    if (pair_filter != FFQ_PAIR_ANY && pair_filter != FFQ_PAIR_BOTH && pair_filter != FFQ_PAIR_FIRST)
+        return fail(FFQ_E_ARG, "ffq_pair_open: pair_filter is FFQ_PAIR_ANY, FFQ_PAIR_BOTH or FFQ_PAIR_FIRST");
+    if (mate1->c != mate2->c) return fail(FFQ_E_ARG, "ffq_pair_open: the two streams are on different contexts");
+    ffq_stream *st[2] = {mate1, mate2};
+    for (int k = 0; k < 2; k++) {
+        ffq_stream *s = st[k];
+        if (s->paired) return fail(FFQ_E_ARG, "ffq_pair_open: mate %d belongs to a pair already", k + 1);
+        if (s->cur >= 0 || s->done || s->failed) return fail(FFQ_E_ARG, "ffq_pair_open: mate %d is not a fresh stream", k + 1);
+        if (s->flags & FFQ_F_DECODE_QUAL) return fail(FFQ_E_ARG, "ffq_pair_open: mate %d decodes every record's qualities (FFQ_F_DECODE_QUAL)", k + 1);
+        if (s->filter.on && s->filter.col) return fail(FFQ_E_ARG, "ffq_pair_open: mate %d's filter gathers a column", k + 1);
     }
-    // refill at the next call: buf = buf[offset:] + next chunk (:277), globaloffset += offset (:275)
-    s->carry_from = ds;
-    s->globaloffset += ds;
+    ffq_pair *p = new (std::nothrow) ffq_pair();
+    if (!p) return fail(FFQ_E_NOMEM, "out of host memory");
+    p->c = mate1->c; p->mode = pair_filter; p->check_names = check_names != 0;
+    for (int k = 0; k < 2; k++) { p->m[k].s = st[k]; st[k]->paired = true; }
+    *out = p;
+    return FFQ_OK;
+}
+
+extern "C" void ffq_pair_close(ffq_pair *p)
+{
+    if (!p) return;
+    if (p->c && p->c->stream) (void)hipStreamSynchronize(p->c->stream);      // (the index buffer goes away)
+    delete p;
+}
+
+extern "C" int ffq_pair_wants(ffq_pair *p) { return p && !p->failed ? walk_wants(p->w) : 0; }
+
+// what the per-stream accessors report for a round: zero until the round's chain says otherwise
+static void pair_clear_last(ffq_stream *s)
+{
+    for (int i = 0; i < 3; i++) s->trim.last[i] = s->adapter.last[i] = s->render.last[i] = 0;
+    for (int i = 0; i < FFQ_FILTER_COUNTS; i++) s->content.last[i] = 0;
+    s->filter.scanned = 0; s->filter.col_bytes = 0;
+}
+
+// The table chain of a round over the slices [lo, lo + m) of both mates' fills.  The order of a round's work on the scan
+// stream: [names check], then per stage both mates: [stats IN], [trim], [adapter], the pair select into each stream's own
+// `sel`, [stats OUT], [render + text D2H], rows D2H, and the ordinals D2H.  *differ: the names check found a different pair
+// (its ordinal in the round), nothing else was done.
+static int pair_chain(ffq_pair *p, int64_t m, int64_t *n_out, int64_t *differ)
+{
+    ffq_ctx *c = p->c;
+    ffq_table_view v[2];
+    for (int k = 0; k < 2; k++) {
+        const PairMate &pm = p->m[k];
+        v[k] = ffq_table_view{pm.f.d_buf, pm.f.n, 0, pm.f.add, pm.s->b->tab.d.p + 6 * p->w.m[k].lo};
+    }
+    *n_out = 0; *differ = -1;
+    int rc = FFQ_OK;
+    if (p->check_names) {
+        int64_t names[4];
+        rc = ffq_table_pair_names(c, &v[0], &v[1], m, names);
+        if (rc) return rc;
+        if (names[1] > 0) { *differ = names[3]; return FFQ_OK; }
+    }
+    int64_t bounds[4];
+    const ffq_content_rules *rules[2];
+    for (int k = 0; k < 2 && !rc; k++) {
+        ffq_stream *s = p->m[k].s;
+        const Fill &f = p->m[k].f;
+        int64_t *rows = const_cast<int64_t *>(v[k].d_table);
+        if (s->stats.which & FFQ_STATS_IN)
+            rc = ffq_table_stats(c, f.d_buf, f.n, 0, f.add, rows, m, s->stats.base, s->stats.cycles, 1, stream_stats_block(s, FFQ_STATS_IN), nullptr);
+        if (!rc && s->trim.on)
+            rc = ffq_table_trim_quality(c, f.d_buf, f.n, 0, f.add, rows, m, s->trim.base, s->trim.front, s->trim.back, rows, s->trim.last);
+        if (!rc && s->adapter.on)
+            rc = ffq_table_trim_adapter(c, f.d_buf, f.n, 0, f.add, rows, m, s->adapter.bytes, s->adapter.len, s->adapter.err, s->adapter.overlap,
+                                        rows, s->adapter.last);
+        if (!rc) rc = stream_alloc_sel(s, m, 0);
+        // a stream without a filter counts as unbounded and ruleless
+        bounds[2 * k] = s->filter.on ? s->filter.min : -((int64_t)1 << 62);
+        bounds[2 * k + 1] = s->filter.on ? s->filter.max : (int64_t)1 << 62;
+        rules[k] = s->content.on ? &s->content.rules : nullptr;
+        s->filter.scanned = m;
+    }
+    if (!rc && p->idx.d.cap < m) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        rc = stream_grow(p->idx, m, "ffq_pair: no memory for %lld selected pairs", m);
+    }
+    int64_t kept = 0;
+    if (!rc) rc = ffq_table_select_pairs(c, &v[0], &v[1], m, bounds, rules[0], rules[1], p->mode, p->m[0].s->b->sel, p->m[1].s->b->sel,
+                                         p->idx.d, &kept, p->m[0].s->content.last, p->m[1].s->content.last, p->last_pairs);
+    for (int k = 0; k < 2 && !rc; k++) {
+        ffq_stream *s = p->m[k].s;
+        StreamBufs *b = s->b;
+        const Fill &f = p->m[k].f;
+        const Table t = {b->sel, kept};
+        if (s->stats.which & FFQ_STATS_OUT)
+            rc = ffq_table_stats(c, f.d_buf, f.n, 0, f.add, t.d_rows, t.n, s->stats.base, s->stats.cycles, 1, stream_stats_block(s, FFQ_STATS_OUT), nullptr);
+        if (!rc && s->render.on) rc = stream_render(s, f, t);
+        if (!rc && kept > 0) HIPCHK(hipMemcpyAsync(b->tab.h, t.d_rows, (size_t)kept * 48, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (rc) return rc;
+    if (kept > 0) HIPCHK(hipMemcpyAsync(p->idx.h, p->idx.d, (size_t)kept * 8, hipMemcpyDeviceToHost, c->stream));
+    *n_out = kept;
+    return FFQ_OK;
+}
+
+extern "C" int ffq_pair_next(ffq_pair *p, int64_t *n_pairs_in, int64_t *n_pairs_out, int *end_state, int *err_mate, int64_t *err_offset)
+{
+    if (!p || !n_pairs_in || !n_pairs_out || !end_state) return fail(FFQ_E_ARG, "ffq_pair_next: NULL argument");
+    ffq_ctx *c = p->c;
+    HIPCHK(hipSetDevice(c->device));
+    *n_pairs_in = *n_pairs_out = 0; *end_state = FFQ_END_OK;
+    if (err_mate) *err_mate = 0;
+    if (err_offset) *err_offset = -1;
+    if (p->failed) return fail(FFQ_E_ARG, "ffq_pair_next: the pair has failed");
+    for (int i = 0; i < 5; i++) p->last_pairs[i] = 0;
+    p->last_out = 0;
+    for (int k = 0; k < 2; k++) pair_clear_last(p->m[k].s);
+    if (p->w.done) return FFQ_OK;
+    p->failed = true;                    // until this call gets through
+    for (int k = 0; k < 2; k++) p->m[k].s->failed = true;
+
+    // every mate whose window is empty takes its stream's next fill: the stream's own wait, take and scan -- the slot of the
+    // fill it had is released by that take, not before
+    walk_begin(p->w);
+    const int wants = walk_wants(p->w);
+    for (int k = 0; k < 2; k++) {
+        if (!(wants & (1 << k))) continue;
+        PairMate &pm = p->m[k];
+        ffq_scan_result res;
+        int rc = stream_advance(pm.s, &pm.f, &res);
+        if (rc) return rc;
+        pm.have = true;
+        pm.bytes_offset = pm.s->globaloffset;
+        pm.s->last_path = res.path;
+        int64_t err = -1;
+        stream_finish(pm.s, pm.f, res, &err);
+        walk_filled(p->w, k, res.n_records, res.end_state, err);
+    }
+    const int64_t m = walk_take(p->w);
+    if (!walk_check(p->w, m)) return fail(FFQ_E_INTERNAL, "ffq_pair_next: a round without pairs and without a new fill");
+    int64_t n_out = 0, differ = -1;
+    if (m > 0) {
+        const int rc = pair_chain(p, m, &n_out, &differ);
+        if (rc) return rc;
+    }
+    WalkRound r;
+    if (differ >= 0) {
+        // the round hands out nothing: what its stages reported so far is taken back
+        // ... and the two records that are not mates go back, one row each, for the caller's message
+        for (int k = 0; k < 2; k++) {
+            ffq_stream *s = p->m[k].s;
+            pair_clear_last(s);
+            HIPCHK(hipMemcpyAsync(s->b->tab.h, s->b->tab.d.p + 6 * (p->w.m[k].lo + differ), 48, hipMemcpyDeviceToHost, c->stream));
+        }
+        r = walk_names_differ(p->w, differ);
+    } else {
+        r = walk_moved(p->w, m);
+        if (r.end_state == FFQ_END_ERR_PAIR_COUNT) {
+            // pos0 of the longer mate's first unpaired record
+            const PairMate &pm = p->m[r.err_mate - 1];
+            HIPCHK(hipMemcpyAsync(c->h_word, pm.s->b->tab.d.p + 6 * r.err_row, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+            r.err_offset = c->h_word[0];
+        }
+        *n_pairs_in = m;
+        *n_pairs_out = n_out;
+        p->last_out = n_out;
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *end_state = r.end_state;
+    if (err_mate) *err_mate = r.err_mate;
+    if (err_offset) *err_offset = r.err_offset;
+    if (p->w.done)
+        for (int k = 0; k < 2; k++) { p->m[k].s->done = true; stream_stop_feeder(p->m[k].s); }
+    p->failed = false;
+    for (int k = 0; k < 2; k++) p->m[k].s->failed = false;
+    return FFQ_OK;
+}
+
+// a mate's share of the round ffq_pair_next has just returned: the kept rows, and the fill they point into
+extern "C" int ffq_pair_rows(ffq_pair *p, int mate, const int64_t **h_rows, const uint8_t **h_bytes, int64_t *n_bytes, int64_t *bytes_offset)
+{
+    if (!p || (mate != 1 && mate != 2) || !h_rows) return fail(FFQ_E_ARG, "ffq_pair_rows: a pair, mate 1 or 2, and a place for the rows");
+    const PairMate &pm = p->m[mate - 1];
+    *h_rows = pm.s->b->tab.h;
+    if (h_bytes) *h_bytes = pm.have ? pm.f.sl->buf.h + pm.f.start : nullptr;
+    if (n_bytes) *n_bytes = pm.have ? pm.f.len : 0;
+    if (bytes_offset) *bytes_offset = pm.bytes_offset;
+    return FFQ_OK;
+}
+
+extern "C" int ffq_pair_selected(ffq_pair *p, const int64_t **h_index, int64_t pairs[5])
+{
+    if (!p || !h_index) return fail(FFQ_E_ARG, "ffq_pair_selected: NULL argument");
+    *h_index = p->idx.h;
+    if (pairs) for (int i = 0; i < 5; i++) pairs[i] = p->last_pairs[i];
     return FFQ_OK;
 }

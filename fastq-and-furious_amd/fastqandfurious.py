@@ -362,7 +362,8 @@ class entryfunc_adaptertrim:
     Called per record (any scanner) it works on a copy of `pos`.  readfastq_iter RECOGNISES the unmodified class when the
     scanner is the GPU one: the stream front end trims every fill's table on the device (ffq_stream_set_trim,
     ffq_stream_set_adapter), filters it and gathers the one component of the kept rows.  Same items, same order, one per
-    record.  Not done: 5' and anchored adapters, indels, several adapters, paired-end files, readfastq_iter_range."""
+    record.  Paired-end files: filter_fastq_paired (an adapter per mate).  Not done: 5' and anchored adapters, indels, several
+    adapters, overlap-based adapter detection between mates, readfastq_iter_range."""
 
     yield_dropped = True
 
@@ -1094,6 +1095,244 @@ def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1
             n_out += 1
             n_bytes += len(text)
     return FilterResult(n_in, n_out, removed, n_bytes)
+
+
+def pair_id(header):
+    """What two mates of a pair have in common in their headers (include/ffq.h states the rule at ffq_table_pair_names; this
+    is its host statement): `header` -- bytes, as entryfunc cuts them -- up to, not including, its first space (0x20) or tab
+    (0x09), all of it if there is none; and if that has at least two bytes and ends in b"/1" or b"/2", without those two.
+    This package's own rule, not cutadapt's (which also drops a bare trailing 1, 2 or 3)."""
+    h = bytes(header)
+    for i, b in enumerate(h):
+        if b == 0x20 or b == 0x09:
+            h = h[:i]
+            break
+    if len(h) >= 2 and h[-2:] in (b"/1", b"/2"):
+        h = h[:-2]
+    return h
+
+
+PairedFilterResult = namedtuple('PairedFilterResult', 'pairs_in pairs_out bases_removed bytes_out1 bytes_out2 dropped')
+
+_PAIR_FILTERS = ("any", "both", "first")
+
+
+def _pair_dropped(pair_filter, v1, v2):
+    if pair_filter == "any":
+        return bool(v1 or v2)
+    if pair_filter == "both":
+        return bool(v1 and v2)
+    return bool(v1)
+
+
+def _raise_for_pair_end(end_state, err_mate, err_offset, names=None):
+    """The ValueError of a paired run: a mate's own malformed input, files of two lengths, records that are not mates."""
+    if end_state == _hip.END_ERR_PAIR_COUNT:
+        raise ValueError("mate %d: the file holds more records than mate %d's: its first unpaired record is at byte %d"
+                         % (err_mate, 3 - err_mate, err_offset))
+    if end_state == _hip.END_ERR_PAIR_NAMES:
+        id1, id2 = names if names is not None else (b"?", b"?")
+        raise ValueError("pair %d: the two records are not mates: %r and %r" % (err_offset, id1, id2))
+    try:
+        _raise_for_end(end_state, err_offset)
+    except ValueError as e:
+        raise ValueError("mate %d: %s" % (err_mate, e)) from None
+
+
+def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typing.BinaryIO, fh_out2: typing.BinaryIO,
+                        fbufsize: int = 1 << 24, quality_cutoff=None, qual_base: int = 33, min_len=None, max_len=None,
+                        adapter=None, adapter2=None, err_permille: int = 100, min_overlap: int = 3, content=None,
+                        pair_filter: str = "any", check_names: bool = True, report=None, report2=None,
+                        entrypos: typing.Optional[typing.Callable] = None) -> PairedFilterResult:
+    """filter_fastq for paired-end files: the i-th records of `fh1` and `fh2` are mates, and a pair is written or dropped
+    TOGETHER, so that `fh_out1` and `fh_out2` stay record for record in step (`cutadapt -q 20 -a ... -A ... -m 30:20
+    --pair-filter=any -o out1 -p out2 in1 in2`).  Every record is trimmed as filter_fastq trims it -- quality_cutoff for both
+    mates, `adapter` for mate 1 and `adapter2` for mate 2 (None: that mate is not adapter-trimmed) -- and judged on its own
+    by its trimmed length (min_len / max_len: an int for both mates or a (mate 1, mate 2) pair) and by `content` (a
+    ContentRules, both mates).  With v1 / v2 the two verdicts, the pair is dropped if
+
+        pair_filter "any"    v1 or v2 fails (cutadapt's default)
+        pair_filter "both"   both fail
+        pair_filter "first"  v1 fails; mate 2 is not judged at all
+
+    check_names: the two records must be mates by their names, pair_id(header 1) == pair_id(header 2).
+
+    Returns PairedFilterResult(pairs_in, pairs_out, bases_removed -- both mates, every record --, bytes_out1, bytes_out2,
+    dropped = {"mate1_only", "mate2_only", "both"}: the dropped pairs by which mate failed; with "first": all in
+    "mate1_only").  report / report2: FilterReports per mate -- `before` every record of that file, `after` its records as
+    written, `dropped` that mate's records by the reason they failed for, judged alone, whatever became of the pair (with
+    "first", report2.dropped stays zero).
+
+    entrypos None (the GPU scanner): two streams walked in lockstep on the device (hip.PairStream; include/ffq.h, ffq_pair),
+    one write per mate and round.  Any other scanner: two readfastq_iter loops zipped record by record, from the same host
+    functions as filter_fastq's.  Both routes write the same bytes and raise ValueError for
+
+        a malformed mate         "mate 2: Incomplete entry at byte ..." (what readfastq_iter raises, with the mate in front)
+        files of two lengths     naming the mate whose file holds more records
+        records that are no mates    naming the pair's ordinal and the two ids
+
+    each behind the pairs already written (the GPU route writes whole rounds: a round with a name error writes nothing).
+    Not done: interleaved input or output, overlap-based adapter detection, merging of overlapping mates."""
+    if content is not None and not isinstance(content, ContentRules):
+        raise TypeError("content must be a ContentRules")
+    if pair_filter not in _PAIR_FILTERS:
+        raise ValueError('pair_filter is "any", "both" or "first"')
+
+    def per_mate(x):
+        a, b = tuple(x) if isinstance(x, (tuple, list)) else (x, x)
+        return (None if a is None else int(a), None if b is None else int(b))
+    los, his = per_mate(min_len), per_mate(max_len)
+    reports = (report, report2)
+    hists = (dict.fromkeys(ContentRules.REASONS, 0), dict.fromkeys(ContentRules.REASONS, 0))
+    for rep, hist in zip(reports, hists):
+        if rep is not None:
+            rep.dropped = hist
+            rep.before = FastqStats(rep.max_cycles, qual_base)
+            rep.after = FastqStats(rep.max_cycles, qual_base)
+    trim = None
+    if quality_cutoff is not None:
+        front, back = (0, quality_cutoff) if isinstance(quality_cutoff, (int, np.integer)) else quality_cutoff
+        trim = entryfunc_qualitytrim(back, front, qual_base)            # (checks the ranges)
+    cutters = tuple(None if a is None else entryfunc_adaptertrim(a, err_permille, min_overlap, quality_cutoff, qual_base)
+                    for a in (adapter, adapter2))
+    dropped = {"mate1_only": 0, "mate2_only": 0, "both": 0}
+    judged = (True, pair_filter != "first")
+    if entrypos is None:
+        from . import _fastqandfurious as _C
+        entrypos = _C.entrypos
+    pairs_in = pairs_out = removed = 0
+    n_bytes = [0, 0]
+    outs = (fh_out1, fh_out2)
+    open_stream = getattr(entrypos, 'open_stream', None)
+    sts = []
+    if open_stream is not None:
+        for fh in (fh1, fh2):
+            st = open_stream(fh, fbufsize)
+            if st is None:
+                break
+            sts.append(st)
+        if len(sts) != 2:
+            for st in sts:
+                st.close()
+            sts = []
+    if sts:
+        ps = None
+        try:
+            for k, st in enumerate(sts):
+                if trim is not None:
+                    st.set_trim(trim.cutoff_back, trim.cutoff_front, trim.qual_base)
+                if cutters[k] is not None:
+                    st.set_adapter(cutters[k].adapter, cutters[k].err_permille, cutters[k].min_overlap)
+                if content is not None:
+                    st.set_content(content)
+                if los[k] is not None or his[k] is not None:
+                    st.set_filter(los[k], his[k])
+                st.set_render()
+                if reports[k] is not None:
+                    st.set_stats(_hip.STATS_IN | _hip.STATS_OUT, qual_base, reports[k].max_cycles)
+            ps = _hip.PairStream(sts[0], sts[1], pair_filter, check_names)
+            for n_in, n_out, end_state, err_mate, err_offset in ps:
+                pairs_in += n_in
+                pairs_out += n_out
+                for k, st in enumerate(sts):
+                    text, (nb, _rendered, _skipped) = st.rendered()
+                    if nb:
+                        outs[k].write(memoryview(text))
+                    n_bytes[k] += nb
+                    if st.filtered and judged[k]:
+                        for reason, c in zip(ContentRules.REASONS, st.filter_counts()[1:7]):
+                            hists[k][reason] += c
+                    if trim is not None:
+                        removed += st.trimmed()[1]
+                    if cutters[k] is not None:
+                        removed += st.adapter_trimmed()[1]
+                pc = ps.selected()[1]
+                if pair_filter != "both":            # (under "both" a pair with one failed mate is kept)
+                    dropped["mate1_only"] += pc[2]
+                    dropped["mate2_only"] += pc[3]
+                dropped["both"] += pc[4]
+                if end_state != _END_OK and end_state != _END_REFILL:
+                    names = None
+                    if end_state == _hip.END_ERR_PAIR_NAMES:
+                        names = tuple(pair_id(h) for h in ps.mismatch())
+                    _raise_for_pair_end(end_state, err_mate, err_offset, names)
+            for k, st in enumerate(sts):
+                if reports[k] is not None:
+                    reports[k].before = FastqStats.from_words(st.stats(_hip.STATS_IN), reports[k].max_cycles, qual_base)
+                    reports[k].after = FastqStats.from_words(st.stats(_hip.STATS_OUT), reports[k].max_cycles, qual_base)
+        finally:
+            if ps is not None:
+                ps.close()
+            for st in sts:
+                st.close()
+        return PairedFilterResult(pairs_in, pairs_out, removed, n_bytes[0], n_bytes[1], dropped)
+
+    def recorder(k):
+        cutter, lo, hi, rep = cutters[k], los[k], his[k], reports[k]
+
+        def record(buf, pos, globaloffset=None):
+            length = pos[3] - pos[2]
+            at = pos[0] + (globaloffset or 0)
+            name = pair_id(buf[(pos[0] + 1):pos[1]]) if check_names else None
+            if rep is not None:
+                rep.before.add_pos(buf, pos)
+            if cutter is not None:
+                pos = cutter.trimmed_pos(buf, pos)          # (the quality rule first, if there is one)
+            elif trim is not None:
+                pos = trim.trimmed_pos(buf, pos)
+            pos = tuple(pos[i] for i in range(6))
+            cut = length - (pos[3] - pos[2])
+            length -= cut
+            v = 0
+            if judged[k]:
+                if (lo is not None and length < lo) or (hi is not None and length > hi):
+                    v = 1
+                elif content is not None:
+                    v = content.verdict_pos(buf, pos)[0]
+            return at, name, cut, v, buf, pos
+        return record
+
+    its = [iter(readfastq_iter(fh, fbufsize, recorder(k), entrypos)) for k, fh in enumerate((fh1, fh2))]
+
+    def step(it):
+        """(record, None), (None, None) at the end, (None, error)"""
+        try:
+            return next(it), None
+        except StopIteration:
+            return None, None
+        except ValueError as e:
+            return None, e
+
+    while True:
+        (r1, e1), (r2, e2) = step(its[0]), step(its[1])
+        for k, e in ((1, e1), (2, e2)):
+            if e is not None:
+                raise ValueError("mate %d: %s" % (k, e)) from None
+        if r1 is None and r2 is None:
+            break
+        if r1 is None or r2 is None:
+            longer = 1 if r2 is None else 2
+            _raise_for_pair_end(_hip.END_ERR_PAIR_COUNT, longer, (r1 if r2 is None else r2)[0])
+        if check_names and r1[1] != r2[1]:
+            _raise_for_pair_end(_hip.END_ERR_PAIR_NAMES, 0, pairs_in, (r1[1], r2[1]))
+        pairs_in += 1
+        v1, v2 = r1[3], r2[3]
+        for k, (r, v) in enumerate(((r1, v1), (r2, v2))):
+            removed += r[2]
+            if v:
+                hists[k][ContentRules.REASONS[v - 1]] += 1
+        if _pair_dropped(pair_filter, v1, v2):
+            dropped["both" if (v1 and v2) else "mate1_only" if v1 else "mate2_only"] += 1
+            continue
+        pairs_out += 1
+        for k, r in enumerate((r1, r2)):
+            buf, pos = r[4], r[5]
+            if reports[k] is not None:
+                reports[k].after.add_pos(buf, pos)
+            text = b"".join((b"@", buf[(pos[0] + 1):pos[1]], b"\n", buf[pos[2]:pos[3]], b"\n+\n", buf[pos[4]:pos[5]], b"\n"))
+            outs[k].write(text)
+            n_bytes[k] += len(text)
+    return PairedFilterResult(pairs_in, pairs_out, removed, n_bytes[0], n_bytes[1], dropped)
 
 
 class RangeEntries:

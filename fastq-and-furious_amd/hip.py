@@ -26,6 +26,7 @@ COMPLETE = 6
 MISSING_QUALHEADER_END = 7
 
 END_OK, END_REFILL, END_ERR_FINAL_QUAL, END_ERR_INCOMPLETE, END_ERR_INVALID = range(5)
+END_ERR_PAIR_COUNT, END_ERR_PAIR_NAMES = 5, 6      # a pair of streams only (PairStream)
 _END_ERRORS = {END_ERR_FINAL_QUAL: 'Incomplete final quality string at byte',
                END_ERR_INCOMPLETE: 'Incomplete entry at byte %i',
                END_ERR_INVALID: 'Entry is invalid at byte %i'}
@@ -99,6 +100,8 @@ SYMBOLS = (
     "ffq_table_trim_adapter", "ffq_stream_set_adapter", "ffq_stream_adapter_trimmed",
     "ffq_table_stats", "ffq_stream_set_stats", "ffq_stream_stats",
     "ffq_table_select_reads", "ffq_ee_micro_table", "ffq_stream_set_content", "ffq_stream_filter_counts",
+    "ffq_table_select_pairs", "ffq_table_pair_names",
+    "ffq_pair_open", "ffq_pair_wants", "ffq_pair_next", "ffq_pair_rows", "ffq_pair_selected", "ffq_pair_close",
 )
 
 
@@ -118,6 +121,30 @@ def content_rules_struct(rules):
     if rules is None or isinstance(rules, ContentRulesStruct):
         return rules
     return ContentRulesStruct(*(int(getattr(rules, name)) for name, _ in ContentRulesStruct._fields_))
+
+
+PAIR_FILTERS = {"any": 0, "both": 1, "first": 2}       # FFQ_PAIR_ANY / _BOTH / _FIRST
+PAIR_COUNTS = 5              # pairs kept, dropped, only mate 1 failed, only mate 2 failed, both failed
+
+
+class TableView(ctypes.Structure):
+    """struct ffq_table_view (include/ffq.h): a mate's buffer and table as the pair passes take them."""
+    _fields_ = [("d_buf", ctypes.c_void_p), ("n_bytes", ctypes.c_int64), ("sentinel", ctypes.c_int32), ("add", ctypes.c_int64),
+                ("d_table", ctypes.c_void_p)]
+
+
+def table_view(d_buf, n_bytes, d_table, sentinel=True, add=None):
+    """A TableView of raw device pointers; d_buf / n_bytes / sentinel / add as for Context.table_gather_column."""
+    return TableView(int(d_buf) if d_buf else None, int(n_bytes), int(bool(sentinel)), int(_add(add, sentinel)),
+                     int(d_table) if d_table else None)
+
+
+def _pair_filter(mode):
+    if mode in PAIR_FILTERS:
+        return PAIR_FILTERS[mode]
+    if isinstance(mode, int):
+        return mode                                     # (the library checks the number)
+    raise ValueError('pair_filter is "any", "both" or "first"')
 
 
 class ScanResult(ctypes.Structure):
@@ -353,6 +380,16 @@ def lib():
         L.ffq_table_select_reads.argtypes = [vp, vp, i64, i32, i64, vp, i64, i64, i64, P(ContentRulesStruct), vp, vp, P(i64), P(i64)]
         L.ffq_ee_micro_table.argtypes = []
         L.ffq_ee_micro_table.restype = P(u32)
+        L.ffq_table_select_pairs.argtypes = [vp, P(TableView), P(TableView), i64, P(i64), P(ContentRulesStruct), P(ContentRulesStruct),
+                                             i32, vp, vp, vp, P(i64), P(i64), P(i64), P(i64)]
+        L.ffq_table_pair_names.argtypes = [vp, P(TableView), P(TableView), i64, P(i64)]
+        L.ffq_pair_open.argtypes = [vp, vp, i32, i32, P(vp)]
+        L.ffq_pair_wants.argtypes = [vp]
+        L.ffq_pair_next.argtypes = [vp, P(i64), P(i64), P(i32), P(i32), P(i64)]
+        L.ffq_pair_rows.argtypes = [vp, i32, P(vp), P(vp), P(i64), P(i64)]
+        L.ffq_pair_selected.argtypes = [vp, P(vp), P(i64)]
+        L.ffq_pair_close.argtypes = [vp]
+        L.ffq_pair_close.restype = None
         L.ffq_stream_set_content.argtypes = [vp, P(ContentRulesStruct)]
         L.ffq_stream_filter_counts.argtypes = [vp, P(i64)]
         L.ffq_table_render_fastq.argtypes = [vp, vp, i64, i32, i64, vp, i64, vp, i64, vp, P(i64)]
@@ -692,6 +729,35 @@ class Context:
                                            None if r is None else ctypes.byref(r), ctypes.c_void_p(d_out),
                                            ctypes.c_void_p(d_idx) if d_idx else None, ctypes.byref(k), counts))
         return k.value, [int(x) for x in counts]
+
+    def table_select_pairs(self, mate1, mate2, n_pairs, d_out1, d_out2, rules1=None, rules2=None, min_len=None, max_len=None,
+                           pair_filter="any", d_idx=None):
+        """Pairs of rows of two device tables kept or dropped together (ffq_table_select_pairs; include/ffq.h states the
+        rule).  mate1 / mate2: TableViews (table_view()); rules1 / rules2 as `rules` of table_select_reads; min_len / max_len:
+        an int (or None) for both mates or a (mate 1, mate 2) pair; pair_filter: "any", "both" or "first".  Kept pairs go to
+        d_out1 / d_out2, their ordinals to d_idx (None: not wanted).  Returns (pairs kept, hist1, hist2, pairs): the eight
+        counts of either mate judged alone, and [kept, dropped, only mate 1 failed, only mate 2 failed, both failed]."""
+        def per_mate(x):
+            return tuple(x) if isinstance(x, (tuple, list)) else (x, x)
+        (lo1, lo2), (hi1, hi2) = per_mate(min_len), per_mate(max_len)
+        bounds = (ctypes.c_int64 * 4)(*(length_bounds(lo1, hi1) + length_bounds(lo2, hi2)))
+        r1, r2 = content_rules_struct(rules1), content_rules_struct(rules2)
+        k = ctypes.c_int64(0)
+        h1, h2 = (ctypes.c_int64 * FILTER_COUNTS)(), (ctypes.c_int64 * FILTER_COUNTS)()
+        pairs = (ctypes.c_int64 * PAIR_COUNTS)()
+        check(lib().ffq_table_select_pairs(self.handle, ctypes.byref(mate1), ctypes.byref(mate2), int(n_pairs), bounds,
+                                           None if r1 is None else ctypes.byref(r1), None if r2 is None else ctypes.byref(r2),
+                                           _pair_filter(pair_filter), ctypes.c_void_p(d_out1), ctypes.c_void_p(d_out2),
+                                           ctypes.c_void_p(d_idx) if d_idx else None, ctypes.byref(k), h1, h2, pairs))
+        return k.value, [int(x) for x in h1], [int(x) for x in h2], [int(x) for x in pairs]
+
+    def table_pair_names(self, mate1, mate2, n_pairs):
+        """Are rows i of the two tables mates by their names (ffq_table_pair_names; include/ffq.h states the rule,
+        fastqandfurious.pair_id is its host statement)?  Returns (equal, different, not compared, ordinal of the first
+        different pair or -1)."""
+        out = (ctypes.c_int64 * 4)()
+        check(lib().ffq_table_pair_names(self.handle, ctypes.byref(mate1), ctypes.byref(mate2), int(n_pairs), out))
+        return tuple(int(x) for x in out)
 
     COLUMNS = {"header": (0, 1, 1), "sequence": (2, 0, 3), "quality": (4, 0, 5)}
 
@@ -1225,6 +1291,91 @@ class PushStream(_Stream):
             if t[3] != END_REFILL:
                 return
             self._pump()
+
+
+class PairStream:
+    """Two streams whose i-th records are mates, walked in lockstep (ffq_pair; include/ffq.h): mate1 / mate2 are fresh
+    FileStreams or PushStreams of one context, configured beforehand (set_trim, set_adapter, set_filter without a column,
+    set_content, set_stats, set_render).  Iterating yields (n_in, n_out, end_state, err_mate, err_offset) per ROUND; after
+    each step the streams' own accessors (rendered(), trimmed(), adapter_trimmed(), filter_counts(), stats()) report that
+    mate's share of the round.  PushStream mates are pumped here whenever the walk takes a new chunk of theirs.  The
+    iteration ends behind the first end_state that is not END_REFILL (END_OK, a mate's END_ERR_*, END_ERR_PAIR_COUNT,
+    END_ERR_PAIR_NAMES).  close() does not close the two streams."""
+
+    def __init__(self, mate1, mate2, pair_filter="any", check_names=True):
+        self._h = ctypes.c_void_p()
+        self.mates = (mate1, mate2)
+        self._ctx = mate1._ctx
+        self.rounds = 0
+        self._last_out = 0
+        check(lib().ffq_pair_open(mate1._h, mate2._h, _pair_filter(pair_filter), 1 if check_names else 0, ctypes.byref(self._h)))
+
+    def _next(self):
+        wants = lib().ffq_pair_wants(self._h)
+        for k, st in enumerate(self.mates):
+            if wants & (1 << k) and isinstance(st, PushStream):
+                st._pump()
+        n_in, n_out, err = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        end, mate = ctypes.c_int32(), ctypes.c_int32()
+        check(lib().ffq_pair_next(self._h, ctypes.byref(n_in), ctypes.byref(n_out), ctypes.byref(end), ctypes.byref(mate), ctypes.byref(err)))
+        self.rounds += 1
+        self._last_out = n_out.value
+        for st in self.mates:
+            st._last_rows = n_out.value
+        return n_in.value, n_out.value, end.value, mate.value, err.value
+
+    def __iter__(self):
+        while True:
+            t = self._next()
+            yield t
+            if t[2] != END_REFILL:
+                return
+
+    def rows(self, mate):
+        """(rows int64[n_out][6], fill uint8[], fill_offset) of mate 1 or 2 for the round just yielded: the kept rows and
+        the fill they point into (fill[i] = stream byte fill_offset + i).  Views, valid until the next step."""
+        rp, fp = ctypes.c_void_p(), ctypes.c_void_p()
+        nb, off = ctypes.c_int64(), ctypes.c_int64()
+        check(lib().ffq_pair_rows(self._h, int(mate), ctypes.byref(rp), ctypes.byref(fp), ctypes.byref(nb), ctypes.byref(off)))
+        n = self._last_out
+        rows = (np.ctypeslib.as_array((ctypes.c_int64 * (n * 6)).from_address(rp.value)).reshape(-1, 6)
+                if n else np.zeros((0, 6), dtype=np.int64))
+        fill = (np.ctypeslib.as_array((ctypes.c_uint8 * nb.value).from_address(fp.value))
+                if nb.value and fp.value else np.zeros(0, dtype=np.uint8))
+        return rows, fill, off.value
+
+    def mismatch(self):
+        """Behind END_ERR_PAIR_NAMES: the two headers (bytes, as entryfunc cuts them) of the pair that is not one."""
+        out = []
+        for mate in (1, 2):
+            rp, fp = ctypes.c_void_p(), ctypes.c_void_p()
+            nb, off = ctypes.c_int64(), ctypes.c_int64()
+            check(lib().ffq_pair_rows(self._h, mate, ctypes.byref(rp), ctypes.byref(fp), ctypes.byref(nb), ctypes.byref(off)))
+            row = (ctypes.c_int64 * 6).from_address(rp.value)
+            fill = (ctypes.c_uint8 * nb.value).from_address(fp.value)
+            out.append(bytes(fill[row[0] + 1 - off.value:row[1] - off.value]))
+        return tuple(out)
+
+    def selected(self):
+        """(index int64[n_out], pairs) of the round just yielded: index[k] = the ordinal, among the round's n_in pairs, of
+        kept pair k; pairs = [kept, dropped, only mate 1 failed, only mate 2 failed, both failed]."""
+        ip = ctypes.c_void_p()
+        pairs = (ctypes.c_int64 * PAIR_COUNTS)()
+        check(lib().ffq_pair_selected(self._h, ctypes.byref(ip), pairs))
+        n = self._last_out
+        idx = np.ctypeslib.as_array((ctypes.c_int64 * n).from_address(ip.value)) if n else np.zeros(0, dtype=np.int64)
+        return idx, [int(x) for x in pairs]
+
+    def close(self):
+        if self._h:
+            lib().ffq_pair_close(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 _default_ctx = {}

@@ -52,6 +52,9 @@ extern "C" {
 #define FFQ_END_ERR_INCOMPLETE  3   /* 'Incomplete entry at byte %i' (:269)            */
 #define FFQ_END_ERR_INVALID     4   /* 'Entry is invalid at byte %i' (:272; at eof the
                                        reference loops forever, we report this instead) */
+/* ... and of a pair of streams (ffq_pair_next) */
+#define FFQ_END_ERR_PAIR_COUNT  5   /* one file of a pair holds more records than the other */
+#define FFQ_END_ERR_PAIR_NAMES  6   /* the i-th records of the two files are not mates      */
 
 /* return codes */
 #define FFQ_OK               0
@@ -335,7 +338,7 @@ int ffq_table_trim_quality(ffq_ctx *ctx, const uint8_t *d_buf, int64_t n_bytes, 
  * MAY be d_table.  Both tables 16-byte aligned.  stats = {rows changed, bases removed, rows skipped}.  FFQ_E_ARG:
  * adapter_len outside 1..64, min_overlap outside 1..adapter_len, err_permille outside 0..1000, a scan pending on the
  * context.  One host wait.  Run it behind ffq_table_trim_quality (cutadapt's order: -q first).  Not done: 5' and anchored
- * adapters, indels, several adapters per call, paired-end files.                                                       */
+ * adapters, indels, several adapters per call, overlap-based adapter detection between the mates of a pair.            */
 int ffq_table_trim_adapter(ffq_ctx *ctx, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
                            const int64_t *d_table, int64_t n_rows, const uint8_t *adapter, int adapter_len,
                            int err_permille, int min_overlap, int64_t *d_out, int64_t stats[3]);
@@ -415,14 +418,58 @@ typedef struct ffq_content_rules {
  * d_buf / n_bytes / sentinel / add: as for ffq_table_gather_column.  rules == NULL, or rules with every content rule off:
  * the call is ffq_table_select_seqlen_idx -- the same launches, rows and d_idx, no kernel reads the buffer and d_buf may be
  * NULL; only counts[0] and [1] are non-zero.  n_rows == 0 is valid.  One host wait.  FFQ_E_ARG: a field outside its range, a
- * scan pending on the context, d_buf NULL with n_bytes > 0 while a content rule is on.  Not done: paired-end files, the
- * fraction form of --max-n.                                                                                            */
+ * scan pending on the context, d_buf NULL with n_bytes > 0 while a content rule is on.  Paired-end files:
+ * ffq_table_select_pairs below.  Not done: the fraction form of --max-n.                                               */
 #define FFQ_FILTER_COUNTS 8
 int ffq_table_select_reads(ffq_ctx *ctx, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
                            const int64_t *d_table, int64_t n_rows, int64_t min_len, int64_t max_len,
                            const ffq_content_rules *rules, int64_t *d_out, int64_t *d_idx, int64_t *n_out,
                            int64_t counts[FFQ_FILTER_COUNTS]);
 const uint32_t *ffq_ee_micro_table(void);
+
+/* ---- paired-end files: two tables whose i-th rows are mates (R1.fq / R2.fq) ------------------------------------------
+ * A mate's buffer and table, as every table pass takes them (d_buf / n_bytes / sentinel / add: as for
+ * ffq_table_gather_column; d_table 16-byte aligned).                                                                  */
+typedef struct ffq_table_view { const uint8_t *d_buf; int64_t n_bytes; int32_t sentinel; int64_t add; const int64_t *d_table; } ffq_table_view;
+#define FFQ_PAIR_ANY   0   /* drop the pair if either mate fails (cutadapt --pair-filter=any, its default) */
+#define FFQ_PAIR_BOTH  1   /* drop it only if both fail                                                  */
+#define FFQ_PAIR_FIRST 2   /* mate 1 alone decides; mate 2 is not judged and none of its bytes is read   */
+/* ffq_table_select_pairs: a pair is kept or dropped together.  Row i of m1 and row i of m2 are mates.  Each mate gets the
+ * VERDICT v1 / v2 that ffq_table_select_reads would give it on its own -- the same rules in the same order, the same
+ * eligibility, "a row dropped by its length has none of its bytes read" -- with its own length bounds (len_bounds = min1,
+ * max1, min2, max2: cutadapt -m 30:20) and its own rules.  rules == NULL or every content rule off: that mate is judged by
+ * its length alone, no kernel reads its buffer and its d_buf may be NULL.  The pair is DROPPED if
+ *     FFQ_PAIR_ANY    v1 != 0 || v2 != 0
+ *     FFQ_PAIR_BOTH   v1 != 0 && v2 != 0
+ *     FFQ_PAIR_FIRST  v1 != 0                   (mate 2 is not judged at all)
+ * Kept pairs go to d_out1 and d_out2 (n_pairs rows of room each; neither may be one of the tables; 16-byte aligned), in
+ * order; d_idx[k] = the ordinal of kept pair k (NULL: none); *n_out = pairs kept.
+ * hist1 / hist2: the eight counts of ffq_table_select_reads for that mate's rows judged alone, whatever became of the
+ * pair ([0] rows with verdict 0, [1..6] by rule, [7] not judged by content).  FFQ_PAIR_FIRST: hist2 is all zero.
+ * pairs = {kept, dropped, only mate 1 failed, only mate 2 failed, both failed}; [0] + [1] = n_pairs.  FFQ_PAIR_FIRST:
+ * [2] = number of pairs with v1 != 0, [3] = [4] = 0.
+ * n_pairs == 0 is valid.  One host wait.  FFQ_E_ARG: a pair_filter that is none of the three, a field of either rules out
+ * of range, a scan pending on the context, d_buf NULL with n_bytes > 0 for a judged mate whose content rules are on.
+ * Not done: interleaved input or output, overlap-based adapter detection, merging of overlapping mates.               */
+int ffq_table_select_pairs(ffq_ctx *ctx, const ffq_table_view *m1, const ffq_table_view *m2, int64_t n_pairs,
+                           const int64_t len_bounds[4] /* min1, max1, min2, max2 */,
+                           const ffq_content_rules *rules1, const ffq_content_rules *rules2, int pair_filter,
+                           int64_t *d_out1, int64_t *d_out2, int64_t *d_idx, int64_t *n_out,
+                           int64_t hist1[FFQ_FILTER_COUNTS], int64_t hist2[FFQ_FILTER_COUNTS], int64_t pairs[5]);
+/* ffq_table_pair_names: are these two files really mates?  For one row, h = buf[pos0 + 1 : pos1], the header as entryfunc
+ * cuts it.  id(h) = h up to, not including, its first byte that is 0x20 (space) or 0x09 (tab); all of h if there is none.
+ * If that id has at least two bytes and ends in "/1" or "/2", those two bytes go as well (an id that is exactly "/1"
+ * becomes empty).  A pair is EQUAL if the two ids have the same length and the same bytes.  A pair is COMPARED if, for both
+ * mates, pos0 - add >= 0, pos0 + 1 <= pos1 and the slice lies inside the buffer (it may end at its end; with sentinel,
+ * coordinate 0 is the virtual "\n": never read) -- the render pass's condition on its header slice.  Every other pair (FASTA
+ * rows, rows written by hand that point outside) counts as NOT COMPARED.  No byte outside either buffer is read.
+ * out = {equal, different, not compared, ordinal of the first different pair or -1}.  n_pairs == 0 is valid.  One host
+ * wait.  FFQ_E_ARG: a scan pending on the context, d_buf NULL with n_bytes > 0.
+ * This is this library's own rule, not cutadapt's: cutadapt strips "/1" and "/2" as well as a trailing "1", "2" or "3"
+ * of either id before it compares, and so accepts ids that differ in that last digit alone; here only the two-byte forms
+ * go, and everything else has to match byte for byte.                                                                 */
+int ffq_table_pair_names(ffq_ctx *ctx, const ffq_table_view *m1, const ffq_table_view *m2, int64_t n_pairs,
+                         int64_t out[4] /* equal, different, not compared, ordinal of the first different pair or -1 */);
 
 /* FASTQ text from (buffer, table): what a pipeline that excluded reads by deleting rows and trimmed them by editing rows
  * ("to avoid saving a FASTQ file after each filtering or read-trimming step", doc/user-guide.rst:196-204) saves at its
@@ -624,6 +671,47 @@ int  ffq_bgzf_range(int fd, int64_t c_lo, int64_t c_hi, uint8_t *h_dst, int64_t 
 int  ffq_stream_open_push(ffq_ctx *ctx, int64_t fbufsize, uint32_t flags, int qual_add, ffq_stream **out);
 int  ffq_stream_push_buffer(ffq_stream *s, uint8_t **dst, int64_t *cap);
 int  ffq_stream_push(ffq_stream *s, int64_t n, int eof);
+
+/* ---- paired-end files: two streams whose i-th records are mates (R1.fq.gz / R2.fq.gz) ---------------------------------
+ * ffq_pair walks two ffq_streams in lockstep so that mates are trimmed, judged and kept or dropped TOGETHER and the two
+ * outputs stay record for record in step.  Both streams are configured beforehand with the setters above -- set_trim,
+ * set_adapter (its own adapter per mate: cutadapt -a / -A), set_filter without a column, set_content, set_stats,
+ * set_render --; they must be fresh (no fill handed out), on the same context and opened without FFQ_F_DECODE_QUAL.  A
+ * stream without a filter counts as unbounded and ruleless; both without one: every pair is kept.  After ffq_pair_open,
+ * ffq_stream_next on either stream is FFQ_E_ARG: the pair walks them.
+ *
+ * The fills of two streams never hold the same number of records.  Each mate keeps its current fill and a window of its
+ * rows that are not yet paired.  A ROUND (ffq_pair_next) first advances every mate whose window is empty and whose stream
+ * has not ended -- the stream's own wait, take and scan, with carry and refill exactly as ffq_stream_next does them --,
+ * takes m = min(rows left in 1, rows left in 2) and runs ONE table chain over those m rows of both fills: the names check
+ * (ffq_table_pair_names, check_names != 0), statistics IN, quality trim, adapter trim, ffq_table_select_pairs under
+ * pair_filter, statistics OUT, render, copies back; then both windows move by m.  A mate's fill stays resident until its
+ * window is empty, so no row is processed or counted twice.  *n_pairs_in = m, *n_pairs_out = pairs kept; m may be 0 (a
+ * fill without a complete record; the round that finds the end).  After each round the per-stream accessors report that
+ * mate's share of it: ffq_stream_rendered, _trimmed, _adapter_trimmed, _stats and _filter_counts (that mate's hist of
+ * ffq_table_select_pairs).  ffq_pair_rows: the kept rows of a mate (n_pairs_out of them) and the fill they point into;
+ * ffq_pair_selected: h_index[k] = the ordinal, among the round's m pairs, of kept pair k, and the five pair counts.
+ * Pinned memory, valid until the next ffq_pair_next.
+ * ffq_pair_wants: bit 0 / bit 1 set: that mate takes a new chunk at the next ffq_pair_next -- a push stream must have one
+ * pushed first.
+ * *end_state: FFQ_END_REFILL while more follows; FFQ_END_OK with the round after which both mates are ended and empty; a
+ * mate's own FFQ_END_ERR_* in the round in which that mate's rows run out (*err_mate = 1 or 2, *err_offset the stream's:
+ * where ffq_stream_next reports it; mate 1 before mate 2);
+ *     FFQ_END_ERR_PAIR_COUNT  one mate is ended and empty while the other still holds a record: *err_mate is the longer
+ *                             one, *err_offset pos0 of its first unpaired record;
+ *     FFQ_END_ERR_PAIR_NAMES  the names check found a different pair: *err_offset is the global ordinal of that pair; the
+ *                             round hands out nothing, earlier rounds stand (h_rows of ffq_pair_rows then holds ONE row, that
+ *                             mate's record of the different pair, for the caller's message).
+ * After any state but FFQ_END_REFILL the pair is done.  ffq_pair_close does not close the two streams.
+ * Not done: interleaved input or output, overlap-based adapter detection, merging of overlapping mates, paired
+ * readfastq_iter_range.                                                                                               */
+typedef struct ffq_pair ffq_pair;
+int  ffq_pair_open(ffq_stream *mate1, ffq_stream *mate2, int pair_filter, int check_names, ffq_pair **out);
+int  ffq_pair_wants(ffq_pair *p);
+int  ffq_pair_next(ffq_pair *p, int64_t *n_pairs_in, int64_t *n_pairs_out, int *end_state, int *err_mate, int64_t *err_offset);
+int  ffq_pair_rows(ffq_pair *p, int mate, const int64_t **h_rows, const uint8_t **h_bytes, int64_t *n_bytes, int64_t *bytes_offset);
+int  ffq_pair_selected(ffq_pair *p, const int64_t **h_index, int64_t pairs[5]);
+void ffq_pair_close(ffq_pair *p);
 
 /* Bytes [pos, pos + n_bytes) of the file behind fd into device memory (read(), fastqandfurious.py:30-36, for a range
  * that stays resident): pread in slices by the context's helper threads into pinned slots, each slot over the link in
