@@ -14,6 +14,7 @@
 #include "ffq_stats.h"
 #include "ffq_filter.h"
 #include "ffq_pair.h"
+#include "ffq_overlap.h"
 #include "ffq_render.h"
 #include "ffq_pool.h"
 #include "ffq_mem.h"
@@ -205,6 +206,8 @@ struct ffq_ctx {
     PinBuf<PairBlock> h_pair;
     DevBuf<PairNamesBlock> d_names;     // ffq_table_pair_names: the call's counters and their pinned mirror
     PinBuf<PairNamesBlock> h_names;
+    DevBuf<OverlapBlock> d_overlap;     // ffq_table_pair_overlap: the call's counts and their pinned mirror
+    PinBuf<OverlapBlock> h_overlap;
     DevBuf<RenderBlock> d_render;       // ffq_table_render_fastq: the call's counters and their pinned mirror
     PinBuf<RenderBlock> h_render;
     DevBuf<int64_t> render_list;        //   (row, place in the output) of the rows left to the wave-per-row launch
@@ -302,6 +305,8 @@ static int ctx_create_impl(int device, ffq_ctx *share, ffq_ctx **out)
     if (e == hipSuccess) e = c->h_pair.grow(1);
     if (e == hipSuccess) e = c->d_names.grow(1);
     if (e == hipSuccess) e = c->h_names.grow(1);
+    if (e == hipSuccess) e = c->d_overlap.grow(1);
+    if (e == hipSuccess) e = c->h_overlap.grow(1);
     if (e == hipSuccess) e = c->d_render.grow(1);
     if (e == hipSuccess) e = c->h_render.grow(1);
     if (e == hipSuccess) e = c->fa_hdr.grow(1);
@@ -2299,6 +2304,58 @@ extern "C" int ffq_table_pair_names(ffq_ctx *c, const ffq_table_view *m1, const 
     HIPCHK(hipStreamSynchronize(st));
     out[0] = (int64_t)c->h_names->equal; out[1] = (int64_t)c->h_names->different; out[2] = (int64_t)c->h_names->not_compared;
     out[3] = c->h_names->different ? (int64_t)c->h_names->first : -1;
+    return FFQ_OK;
+}
+
+// ---- the overlap of the mates of a pair (csrc/ffq_overlap.h) -------------------------------------
+static_assert(OVL_MAX_LEN == FFQ_OVERLAP_MAX_LEN && OVERLAP_HIST == FFQ_OVERLAP_HIST_WORDS && OVERLAP_COUNTS == FFQ_OVERLAP_COUNTS,
+              "include/ffq.h");
+
+// the rules of an overlap call, checked: for the table call and for ffq_pair_set_overlap
+static int overlap_arg(const char *who, const ffq_overlap_rules *r)
+{
+    if (!r) return fail(FFQ_E_ARG, "%s: no rules", who);
+    if (r->min_overlap < 1 || r->min_overlap > FFQ_OVERLAP_MAX_LEN) return fail(FFQ_E_ARG, "%s: min_overlap is 1..%d", who, FFQ_OVERLAP_MAX_LEN);
+    if (r->max_diff < 0 || r->max_diff > FFQ_OVERLAP_MAX_LEN) return fail(FFQ_E_ARG, "%s: max_diff is 0..%d", who, FFQ_OVERLAP_MAX_LEN);
+    if (r->diff_permille < 0 || r->diff_permille > 1000) return fail(FFQ_E_ARG, "%s: diff_permille is 0..1000", who);
+    if (r->trim != 0 && r->trim != 1) return fail(FFQ_E_ARG, "%s: trim is 0 or 1", who);
+    return FFQ_OK;
+}
+
+extern "C" int ffq_table_pair_overlap(ffq_ctx *c, const ffq_table_view *m1, const ffq_table_view *m2, int64_t n_pairs,
+                                      const ffq_overlap_rules *rules, int64_t *d_out1, int64_t *d_out2, int32_t *d_insert,
+                                      uint64_t *d_hist, int accumulate, int64_t counts[FFQ_OVERLAP_COUNTS])
+{
+    static const char *const who = "ffq_table_pair_overlap";
+    mark_other(c);
+    int rc = overlap_arg(who, rules);
+    if (rc) return rc;
+    if (!c || !counts || n_pairs < 0 || !view_ok(m1, n_pairs) || !view_ok(m2, n_pairs) || (n_pairs > 0 && (!d_out1 || !d_out2)))
+        return fail(FFQ_E_ARG, "%s: bad argument", who);
+    if (((reinterpret_cast<uintptr_t>(d_out1) | reinterpret_cast<uintptr_t>(d_out2)) & 15) != 0)
+        return fail(FFQ_E_ARG, "%s: tables must be 16-byte aligned", who);
+    if ((reinterpret_cast<uintptr_t>(d_hist) & 7) != 0 || (reinterpret_cast<uintptr_t>(d_insert) & 3) != 0)
+        return fail(FFQ_E_ARG, "%s: d_hist must be 8-byte aligned, d_insert 4-byte aligned", who);
+    if ((m1->n_bytes > 0 && !m1->d_buf) || (m2->n_bytes > 0 && !m2->d_buf)) return fail(FFQ_E_ARG, "%s: no buffer to read the sequences from", who);
+    if (c->pend.active) return fail(FFQ_E_ARG, "%s: a scan is pending on this context", who);
+    HIPCHK(hipSetDevice(c->device));
+    for (int i = 0; i < OVERLAP_COUNTS; i++) counts[i] = 0;
+    hipStream_t st = c->stream;
+    if (d_hist && !accumulate) HIPCHK(hipMemsetAsync(d_hist, 0, (size_t)OVERLAP_HIST * 8, st));
+    if (n_pairs == 0) {
+        HIPCHK(hipStreamSynchronize(st));
+        return FFQ_OK;
+    }
+    HIPCHK(hipMemsetAsync(c->d_overlap, 0, sizeof(OverlapBlock), st));
+    const PairSide A = {m1->d_buf, m1->n_bytes, m1->sentinel ? 1 : 0, m1->add, m1->d_table};
+    const PairSide B = {m2->d_buf, m2->n_bytes, m2->sentinel ? 1 : 0, m2->add, m2->d_table};
+    const OverlapRules R = {rules->min_overlap, rules->max_diff, rules->diff_permille, rules->trim};
+    hipLaunchKernelGGL(k_pair_overlap, dim3(rows_grid(n_pairs, OVERLAP_WG / ROWS_G, EDIT_GRID_SHORT)), dim3(OVERLAP_WG), 0, st, A, B, n_pairs,
+                       R, d_out1, d_out2, d_insert, reinterpret_cast<unsigned long long *>(d_hist), c->d_overlap.p);
+    HIPCHK(hipMemcpyAsync(c->h_overlap, c->d_overlap, sizeof(OverlapBlock), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    for (int i = 0; i < OVERLAP_COUNTS; i++) counts[i] = (int64_t)c->h_overlap->cnt[i];
     return FFQ_OK;
 }
 

@@ -999,6 +999,10 @@ struct ffq_pair {
     Mirror<int64_t> idx;         // the ordinals, among the round's pairs, of the kept ones
     int64_t last_pairs[5] = {0, 0, 0, 0, 0};
     int64_t last_out = 0;
+    bool started = false;        // ffq_pair_next has been called: the setters are refused
+    // the mates' overlap analysed, and cut by, in every round (ffq_pair_set_overlap): the insert sizes summed over the rounds
+    // on the device, the six counts of the last round
+    struct { bool on = false; ffq_overlap_rules rules = {}; DevBuf<uint64_t> hist; int64_t last[FFQ_OVERLAP_COUNTS] = {0, 0, 0, 0, 0, 0}; } overlap;
 };
 
 extern "C" int ffq_pair_open(ffq_stream *mate1, ffq_stream *mate2, int pair_filter, int check_names, ffq_pair **out)
@@ -1031,6 +1035,43 @@ extern "C" void ffq_pair_close(ffq_pair *p)
     delete p;
 }
 
+extern "C" int ffq_pair_set_overlap(ffq_pair *p, const ffq_overlap_rules *rules)
+{
+    if (!p) return fail(FFQ_E_ARG, "ffq_pair_set_overlap: NULL pair");
+    if (p->started) return fail(FFQ_E_ARG, "ffq_pair_set_overlap: the walk has begun (call it before the first ffq_pair_next)");
+    if (!rules) { p->overlap.on = false; return FFQ_OK; }
+    int rc = overlap_arg("ffq_pair_set_overlap", rules);
+    if (rc) return rc;
+    ffq_ctx *c = p->c;
+    HIPCHK(hipSetDevice(c->device));
+    if (p->overlap.hist.cap < FFQ_OVERLAP_HIST_WORDS) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        rc = stream_grow(p->overlap.hist, (int64_t)FFQ_OVERLAP_HIST_WORDS, "ffq_pair: no memory for %lld words of insert sizes",
+                         (int64_t)FFQ_OVERLAP_HIST_WORDS);
+        if (rc) return rc;
+    }
+    HIPCHK(hipMemsetAsync(p->overlap.hist.p, 0, (size_t)FFQ_OVERLAP_HIST_WORDS * 8, c->stream));
+    p->overlap.rules = *rules;
+    p->overlap.on = true;
+    return FFQ_OK;
+}
+
+// the last round's six counts, and the insert sizes of every round so far; one host wait
+extern "C" int ffq_pair_overlap(ffq_pair *p, int64_t counts[FFQ_OVERLAP_COUNTS], uint64_t *h_hist, int64_t cap_words)
+{
+    if (!p || !counts) return fail(FFQ_E_ARG, "ffq_pair_overlap: NULL argument");
+    if (!p->overlap.on) return fail(FFQ_E_ARG, "ffq_pair_overlap: the pair does not analyse overlaps (ffq_pair_set_overlap)");
+    for (int i = 0; i < FFQ_OVERLAP_COUNTS; i++) counts[i] = p->overlap.last[i];
+    if (!h_hist) return FFQ_OK;
+    if (cap_words < FFQ_OVERLAP_HIST_WORDS)
+        return fail(FFQ_E_ARG, "ffq_pair_overlap: the insert sizes have %d words, the output holds %lld", FFQ_OVERLAP_HIST_WORDS, (long long)cap_words);
+    ffq_ctx *c = p->c;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(h_hist, p->overlap.hist.p, (size_t)FFQ_OVERLAP_HIST_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return FFQ_OK;
+}
+
 extern "C" int ffq_pair_wants(ffq_pair *p) { return p && !p->failed ? walk_wants(p->w) : 0; }
 
 // what the per-stream accessors report for a round: zero until the round's chain says otherwise
@@ -1042,8 +1083,8 @@ static void pair_clear_last(ffq_stream *s)
 }
 
 // The table chain of a round over the slices [lo, lo + m) of both mates' fills.  The order of a round's work on the scan
-// stream: [names check], then per stage both mates: [stats IN], [trim], [adapter], the pair select into each stream's own
-// `sel`, [stats OUT], [render + text D2H], rows D2H, and the ordinals D2H.  *differ: the names check found a different pair
+// stream: [names check], then per stage both mates: [stats IN], [trim], [adapter], [the mates' overlap, editing both slices in
+// place], the pair select into each stream's own `sel`, [stats OUT], [render + text D2H], rows D2H, and the ordinals D2H.  *differ: the names check found a different pair
 // (its ordinal in the round), nothing else was done.
 static int pair_chain(ffq_pair *p, int64_t m, int64_t *n_out, int64_t *differ)
 {
@@ -1085,6 +1126,9 @@ static int pair_chain(ffq_pair *p, int64_t m, int64_t *n_out, int64_t *differ)
         HIPCHK(hipStreamSynchronize(c->stream));
         rc = stream_grow(p->idx, m, "ffq_pair: no memory for %lld selected pairs", m);
     }
+    if (!rc && p->overlap.on)
+        rc = ffq_table_pair_overlap(c, &v[0], &v[1], m, &p->overlap.rules, const_cast<int64_t *>(v[0].d_table), const_cast<int64_t *>(v[1].d_table),
+                                    nullptr, p->overlap.hist.p, 1, p->overlap.last);
     int64_t kept = 0;
     if (!rc) rc = ffq_table_select_pairs(c, &v[0], &v[1], m, bounds, rules[0], rules[1], p->mode, p->m[0].s->b->sel, p->m[1].s->b->sel,
                                          p->idx.d, &kept, p->m[0].s->content.last, p->m[1].s->content.last, p->last_pairs);
@@ -1114,7 +1158,9 @@ extern "C" int ffq_pair_next(ffq_pair *p, int64_t *n_pairs_in, int64_t *n_pairs_
     if (err_offset) *err_offset = -1;
     if (p->failed) return fail(FFQ_E_ARG, "ffq_pair_next: the pair has failed");
     for (int i = 0; i < 5; i++) p->last_pairs[i] = 0;
+    for (int i = 0; i < FFQ_OVERLAP_COUNTS; i++) p->overlap.last[i] = 0;
     p->last_out = 0;
+    p->started = true;
     for (int k = 0; k < 2; k++) pair_clear_last(p->m[k].s);
     if (p->w.done) return FFQ_OK;
     p->failed = true;                    // until this call gets through

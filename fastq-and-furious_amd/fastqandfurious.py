@@ -362,8 +362,8 @@ class entryfunc_adaptertrim:
     Called per record (any scanner) it works on a copy of `pos`.  readfastq_iter RECOGNISES the unmodified class when the
     scanner is the GPU one: the stream front end trims every fill's table on the device (ffq_stream_set_trim,
     ffq_stream_set_adapter), filters it and gathers the one component of the kept rows.  Same items, same order, one per
-    record.  Paired-end files: filter_fastq_paired (an adapter per mate).  Not done: 5' and anchored adapters, indels, several
-    adapters, overlap-based adapter detection between mates, readfastq_iter_range."""
+    record.  Paired-end files: filter_fastq_paired (an adapter per mate, or none named: its `overlap`).  Not done: 5' and
+    anchored adapters, indels, several adapters, readfastq_iter_range."""
 
     yield_dropped = True
 
@@ -1112,6 +1112,72 @@ def pair_id(header):
     return h
 
 
+class OverlapRules:
+    """When the two mates of a pair count as overlapping (include/ffq.h, ffq_table_pair_overlap; fastp's defaults): at least
+    min_overlap positions, of which at most max_diff, and at most diff_permille thousandths (integer division), differ."""
+
+    MAX_LEN = _hip.OVERLAP_MAX_LEN
+
+    def __init__(self, min_overlap=30, max_diff=5, diff_permille=200):
+        if not 1 <= int(min_overlap) <= self.MAX_LEN:
+            raise ValueError("min_overlap is 1..%d" % self.MAX_LEN)
+        if not 0 <= int(max_diff) <= self.MAX_LEN:
+            raise ValueError("max_diff is 0..%d" % self.MAX_LEN)
+        if not 0 <= int(diff_permille) <= 1000:
+            raise ValueError("diff_permille is 0..1000")
+        self.min_overlap, self.max_diff, self.diff_permille = int(min_overlap), int(max_diff), int(diff_permille)
+
+
+_BASE_CLASS = np.full(256, 4, dtype=np.int8)
+for _i, _pair in enumerate((b"Aa", b"Cc", b"Gg", b"Tt")):
+    _BASE_CLASS[list(_pair)] = _i
+
+
+def pair_overlap(seq1, seq2, rules):
+    """The insert size of a pair from the overlap of its mates, or None if they do not overlap (include/ffq.h states the rule
+    at ffq_table_pair_overlap; this is its host statement).  seq1 / seq2: bytes of the two sequence lines; rules: an
+    OverlapRules.  With a = seq1 and rb = the reverse complement of seq2, the candidates o = 0, 1, ..., len(a) - min_overlap,
+    then -1, -2, ..., -(len(rb) - min_overlap) place rb[0] at a[o]; the FIRST whose overlapping positions differ in at most
+    min(max_diff, overlap * diff_permille // 1000) places gives insert = len(seq2) + o.  Bases match whatever their case;
+    any other byte (N) matches nothing, not even itself.  insert < len(seq2) (o < 0) means the fragment is shorter than
+    the reads: seq1[insert:] and seq2[insert:] are adapter."""
+    n1, n2, mo = len(seq1), len(seq2), rules.min_overlap
+    if n1 < mo or n2 < mo:
+        return None
+    a = _BASE_CLASS[np.frombuffer(seq1, dtype=np.uint8)]
+    b = _BASE_CLASS[np.frombuffer(seq2, dtype=np.uint8)][::-1]
+    rb = np.where(b < 4, 3 - b, 5)                    # (5: equal to no class of a, 4 included)
+    for o in list(range(0, n1 - mo + 1)) + list(range(-1, -(n2 - mo) - 1, -1)):
+        lo, hi = max(0, o), min(n1, n2 + o)
+        mm = int(np.count_nonzero(a[lo:hi] != rb[lo - o:hi - o]))
+        if mm <= min(rules.max_diff, (hi - lo) * rules.diff_permille // 1000):
+            return n2 + o
+    return None
+
+
+def overlap_analysable(buf1, pos1, buf2, pos2):
+    """Does the device analyse this pair (ffq_table_pair_overlap's eligibility)?  Both rows as adapter_trimmable asks, and
+    neither mate above OverlapRules.MAX_LEN bases."""
+    return (adapter_trimmable(buf1, pos1) and adapter_trimmable(buf2, pos2) and pos1[3] - pos1[2] <= OverlapRules.MAX_LEN
+            and pos2[3] - pos2[2] <= OverlapRules.MAX_LEN)
+
+
+class OverlapReport:
+    """What filter_fastq_paired(overlap_report=...) fills: pairs_analysed, pairs_overlapped (an insert size was found),
+    pairs_trimmed (at least one mate was cut), bases_removed = [from mate 1, from mate 2], insert_hist[i] = pairs with
+    insert size i (uint64[hip.OVERLAP_HIST_WORDS]); insert_peak: the most frequent insert size (the smallest of several),
+    None if no pair overlapped."""
+
+    def __init__(self):
+        self.pairs_analysed = self.pairs_overlapped = self.pairs_trimmed = 0
+        self.bases_removed = [0, 0]
+        self.insert_hist = np.zeros(_hip.OVERLAP_HIST_WORDS, dtype=np.uint64)
+
+    @property
+    def insert_peak(self):
+        return int(np.argmax(self.insert_hist)) if self.insert_hist.any() else None
+
+
 PairedFilterResult = namedtuple('PairedFilterResult', 'pairs_in pairs_out bases_removed bytes_out1 bytes_out2 dropped')
 
 _PAIR_FILTERS = ("any", "both", "first")
@@ -1143,7 +1209,8 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
                         fbufsize: int = 1 << 24, quality_cutoff=None, qual_base: int = 33, min_len=None, max_len=None,
                         adapter=None, adapter2=None, err_permille: int = 100, min_overlap: int = 3, content=None,
                         pair_filter: str = "any", check_names: bool = True, report=None, report2=None,
-                        entrypos: typing.Optional[typing.Callable] = None) -> PairedFilterResult:
+                        entrypos: typing.Optional[typing.Callable] = None, overlap=None,
+                        overlap_report=None) -> PairedFilterResult:
     """filter_fastq for paired-end files: the i-th records of `fh1` and `fh2` are mates, and a pair is written or dropped
     TOGETHER, so that `fh_out1` and `fh_out2` stay record for record in step (`cutadapt -q 20 -a ... -A ... -m 30:20
     --pair-filter=any -o out1 -p out2 in1 in2`).  Every record is trimmed as filter_fastq trims it -- quality_cutoff for both
@@ -1172,11 +1239,26 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
         records that are no mates    naming the pair's ordinal and the two ids
 
     each behind the pairs already written (the GPU route writes whole rounds: a round with a name error writes nothing).
-    Not done: interleaved input or output, overlap-based adapter detection, merging of overlapping mates."""
+
+    overlap: an OverlapRules; behind the per-mate trims and in front of the filters, the overlap of the two mates is looked
+    for (pair_overlap) and, where the fragment is shorter than the reads, both mates are cut to it -- adapters go without
+    being named (what fastp does to pairs by default).  The order is quality, adapter, overlap, filter; bases_removed then
+    includes what the overlap cut.  Pairs the rule does not apply to (overlap_analysable: wrapped records, mates above 512
+    bases) are left as they are.  overlap_report: an OverlapReport, filled on either route with the same numbers (its
+    insert_peak: the library's insert size).  None: nothing of this is done.
+    Not done: interleaved input or output, merging of overlapping mates, base correction inside the overlap."""
     if content is not None and not isinstance(content, ContentRules):
         raise TypeError("content must be a ContentRules")
     if pair_filter not in _PAIR_FILTERS:
         raise ValueError('pair_filter is "any", "both" or "first"')
+    if overlap is not None and not isinstance(overlap, OverlapRules):
+        raise TypeError("overlap must be an OverlapRules")
+    if overlap_report is not None and overlap is None:
+        raise ValueError("overlap_report needs overlap")
+    orep = OverlapReport() if overlap is not None else None
+    if overlap_report is not None:
+        overlap_report.__dict__.update(orep.__dict__)
+        orep = overlap_report
 
     def per_mate(x):
         a, b = tuple(x) if isinstance(x, (tuple, list)) else (x, x)
@@ -1231,9 +1313,19 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
                 if reports[k] is not None:
                     st.set_stats(_hip.STATS_IN | _hip.STATS_OUT, qual_base, reports[k].max_cycles)
             ps = _hip.PairStream(sts[0], sts[1], pair_filter, check_names)
+            if overlap is not None:
+                ps.set_overlap(overlap)
             for n_in, n_out, end_state, err_mate, err_offset in ps:
                 pairs_in += n_in
                 pairs_out += n_out
+                if overlap is not None:
+                    oc = ps.overlap(hist=False)[0]
+                    orep.pairs_analysed += oc[0]
+                    orep.pairs_overlapped += oc[1]
+                    orep.pairs_trimmed += oc[2]
+                    orep.bases_removed[0] += oc[3]
+                    orep.bases_removed[1] += oc[4]
+                    removed += oc[3] + oc[4]
                 for k, st in enumerate(sts):
                     text, (nb, _rendered, _skipped) = st.rendered()
                     if nb:
@@ -1260,6 +1352,8 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
                 if reports[k] is not None:
                     reports[k].before = FastqStats.from_words(st.stats(_hip.STATS_IN), reports[k].max_cycles, qual_base)
                     reports[k].after = FastqStats.from_words(st.stats(_hip.STATS_OUT), reports[k].max_cycles, qual_base)
+            if overlap is not None:
+                orep.insert_hist = ps.overlap()[1]
         finally:
             if ps is not None:
                 ps.close()
@@ -1268,7 +1362,7 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
         return PairedFilterResult(pairs_in, pairs_out, removed, n_bytes[0], n_bytes[1], dropped)
 
     def recorder(k):
-        cutter, lo, hi, rep = cutters[k], los[k], his[k], reports[k]
+        cutter, rep = cutters[k], reports[k]
 
         def record(buf, pos, globaloffset=None):
             length = pos[3] - pos[2]
@@ -1282,15 +1376,41 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
                 pos = trim.trimmed_pos(buf, pos)
             pos = tuple(pos[i] for i in range(6))
             cut = length - (pos[3] - pos[2])
-            length -= cut
-            v = 0
-            if judged[k]:
-                if (lo is not None and length < lo) or (hi is not None and length > hi):
-                    v = 1
-                elif content is not None:
-                    v = content.verdict_pos(buf, pos)[0]
-            return at, name, cut, v, buf, pos
+            return at, name, cut, buf, pos
         return record
+
+    def verdict(k, buf, pos):
+        """a mate judged alone, as the trims (and the overlap) left it"""
+        length = pos[3] - pos[2]
+        if judged[k]:
+            if (los[k] is not None and length < los[k]) or (his[k] is not None and length > his[k]):
+                return 1
+            if content is not None:
+                return content.verdict_pos(buf, pos)[0]
+        return 0
+
+    def overlap_cut(r1, r2):
+        """the two records with the overlap's cut applied, and the report filled"""
+        (buf1, pos1), (buf2, pos2) = r1[3:], r2[3:]
+        if not overlap_analysable(buf1, pos1, buf2, pos2):
+            return r1, r2
+        orep.pairs_analysed += 1
+        n1, n2 = pos1[3] - pos1[2], pos2[3] - pos2[2]
+        insert = pair_overlap(buf1[pos1[2]:pos1[3]], buf2[pos2[2]:pos2[3]], overlap)
+        if insert is None:
+            return r1, r2
+        orep.pairs_overlapped += 1
+        orep.insert_hist[insert] += 1
+        if insert >= n2:                                # (o >= 0: the fragment is not shorter than mate 2)
+            return r1, r2
+        out = []
+        for k, (r, n) in enumerate(((r1, n1), (r2, n2))):
+            c = min(n, insert)
+            pos = r[4]
+            orep.bases_removed[k] += n - c
+            out.append(r[:2] + (r[2] + n - c, r[3], (pos[0], pos[1], pos[2], pos[2] + c, pos[4], pos[4] + c)))
+        orep.pairs_trimmed += 1
+        return tuple(out)
 
     its = [iter(readfastq_iter(fh, fbufsize, recorder(k), entrypos)) for k, fh in enumerate((fh1, fh2))]
 
@@ -1316,7 +1436,9 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
         if check_names and r1[1] != r2[1]:
             _raise_for_pair_end(_hip.END_ERR_PAIR_NAMES, 0, pairs_in, (r1[1], r2[1]))
         pairs_in += 1
-        v1, v2 = r1[3], r2[3]
+        if overlap is not None:
+            r1, r2 = overlap_cut(r1, r2)
+        v1, v2 = verdict(0, r1[3], r1[4]), verdict(1, r2[3], r2[4])
         for k, (r, v) in enumerate(((r1, v1), (r2, v2))):
             removed += r[2]
             if v:
@@ -1326,7 +1448,7 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
             continue
         pairs_out += 1
         for k, r in enumerate((r1, r2)):
-            buf, pos = r[4], r[5]
+            buf, pos = r[3], r[4]
             if reports[k] is not None:
                 reports[k].after.add_pos(buf, pos)
             text = b"".join((b"@", buf[(pos[0] + 1):pos[1]], b"\n", buf[pos[2]:pos[3]], b"\n+\n", buf[pos[4]:pos[5]], b"\n"))

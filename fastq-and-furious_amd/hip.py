@@ -102,6 +102,7 @@ SYMBOLS = (
     "ffq_table_select_reads", "ffq_ee_micro_table", "ffq_stream_set_content", "ffq_stream_filter_counts",
     "ffq_table_select_pairs", "ffq_table_pair_names",
     "ffq_pair_open", "ffq_pair_wants", "ffq_pair_next", "ffq_pair_rows", "ffq_pair_selected", "ffq_pair_close",
+    "ffq_table_pair_overlap", "ffq_pair_set_overlap", "ffq_pair_overlap",
 )
 
 
@@ -137,6 +138,24 @@ def table_view(d_buf, n_bytes, d_table, sentinel=True, add=None):
     """A TableView of raw device pointers; d_buf / n_bytes / sentinel / add as for Context.table_gather_column."""
     return TableView(int(d_buf) if d_buf else None, int(n_bytes), int(bool(sentinel)), int(_add(add, sentinel)),
                      int(d_table) if d_table else None)
+
+
+OVERLAP_MAX_LEN = 512                            # FFQ_OVERLAP_MAX_LEN: mates above it are not analysed
+OVERLAP_HIST_WORDS = 2 * OVERLAP_MAX_LEN + 1     # insert sizes 0..1024
+OVERLAP_COUNTS = 6           # pairs analysed, with an overlap, changed, bases removed from mate 1, from mate 2, pairs not analysed
+
+
+class OverlapRulesStruct(ctypes.Structure):
+    """struct ffq_overlap_rules (include/ffq.h)."""
+    _fields_ = [("min_overlap", ctypes.c_int32), ("max_diff", ctypes.c_int32), ("diff_permille", ctypes.c_int32), ("trim", ctypes.c_int32)]
+
+
+def overlap_rules_struct(rules, trim=True):
+    """What the library takes for `rules`: an OverlapRulesStruct as it is, or anything with min_overlap, max_diff and
+    diff_permille as attributes (fastqandfurious.OverlapRules) and `trim` beside it."""
+    if rules is None or isinstance(rules, OverlapRulesStruct):
+        return rules
+    return OverlapRulesStruct(int(rules.min_overlap), int(rules.max_diff), int(rules.diff_permille), 1 if trim else 0)
 
 
 def _pair_filter(mode):
@@ -389,6 +408,9 @@ def lib():
         L.ffq_pair_rows.argtypes = [vp, i32, P(vp), P(vp), P(i64), P(i64)]
         L.ffq_pair_selected.argtypes = [vp, P(vp), P(i64)]
         L.ffq_pair_close.argtypes = [vp]
+        L.ffq_table_pair_overlap.argtypes = [vp, P(TableView), P(TableView), i64, P(OverlapRulesStruct), vp, vp, vp, vp, i32, P(i64)]
+        L.ffq_pair_set_overlap.argtypes = [vp, P(OverlapRulesStruct)]
+        L.ffq_pair_overlap.argtypes = [vp, P(i64), vp, i64]
         L.ffq_pair_close.restype = None
         L.ffq_stream_set_content.argtypes = [vp, P(ContentRulesStruct)]
         L.ffq_stream_filter_counts.argtypes = [vp, P(i64)]
@@ -758,6 +780,23 @@ class Context:
         out = (ctypes.c_int64 * 4)()
         check(lib().ffq_table_pair_names(self.handle, ctypes.byref(mate1), ctypes.byref(mate2), int(n_pairs), out))
         return tuple(int(x) for x in out)
+
+    def table_pair_overlap(self, mate1, mate2, n_pairs, rules, d_out1, d_out2, d_insert=None, d_hist=None, accumulate=False,
+                           trim=True):
+        """The overlap of the mates of every pair of two device tables (ffq_table_pair_overlap; include/ffq.h states the rule,
+        fastqandfurious.pair_overlap is its host statement): insert sizes, and with `trim` both rows cut to the fragment
+        where it is shorter than the reads.  mate1 / mate2: TableViews; rules: an OverlapRulesStruct, or anything with
+        min_overlap, max_diff and diff_permille (then `trim` says whether rows are cut).  d_out1 / d_out2 may be the tables
+        themselves.  d_insert: int32 per pair (None: not wanted); d_hist: OVERLAP_HIST_WORDS uint64, overwritten or -- accumulate
+        -- added to (None: not wanted).  Returns the six counts: [pairs analysed, with an overlap, changed, bases removed from
+        mate 1, from mate 2, pairs not analysed]."""
+        r = overlap_rules_struct(rules, trim)
+        counts = (ctypes.c_int64 * OVERLAP_COUNTS)()
+        check(lib().ffq_table_pair_overlap(self.handle, ctypes.byref(mate1), ctypes.byref(mate2), int(n_pairs),
+                                           None if r is None else ctypes.byref(r), ctypes.c_void_p(d_out1), ctypes.c_void_p(d_out2),
+                                           ctypes.c_void_p(d_insert) if d_insert else None, ctypes.c_void_p(d_hist) if d_hist else None,
+                                           1 if accumulate else 0, counts))
+        return [int(x) for x in counts]
 
     COLUMNS = {"header": (0, 1, 1), "sequence": (2, 0, 3), "quality": (4, 0, 5)}
 
@@ -1296,8 +1335,8 @@ class PushStream(_Stream):
 class PairStream:
     """Two streams whose i-th records are mates, walked in lockstep (ffq_pair; include/ffq.h): mate1 / mate2 are fresh
     FileStreams or PushStreams of one context, configured beforehand (set_trim, set_adapter, set_filter without a column,
-    set_content, set_stats, set_render).  Iterating yields (n_in, n_out, end_state, err_mate, err_offset) per ROUND; after
-    each step the streams' own accessors (rendered(), trimmed(), adapter_trimmed(), filter_counts(), stats()) report that
+    set_content, set_stats, set_render); set_overlap() here, before the first step.  Iterating yields (n_in, n_out,
+    end_state, err_mate, err_offset) per ROUND; after each step the streams' own accessors (rendered(), trimmed(), adapter_trimmed(), filter_counts(), stats()) report that
     mate's share of the round.  PushStream mates are pumped here whenever the walk takes a new chunk of theirs.  The
     iteration ends behind the first end_state that is not END_REFILL (END_OK, a mate's END_ERR_*, END_ERR_PAIR_COUNT,
     END_ERR_PAIR_NAMES).  close() does not close the two streams."""
@@ -1365,6 +1404,21 @@ class PairStream:
         n = self._last_out
         idx = np.ctypeslib.as_array((ctypes.c_int64 * n).from_address(ip.value)) if n else np.zeros(0, dtype=np.int64)
         return idx, [int(x) for x in pairs]
+
+    def set_overlap(self, rules, trim=True):
+        """Every round analyses the overlap of the mates behind the per-mate trims and in front of the filter, and with
+        `trim` cuts both mates by it (ffq_pair_set_overlap; rules as Context.table_pair_overlap takes them, None: off).
+        Before the first step only."""
+        r = overlap_rules_struct(rules, trim)
+        check(lib().ffq_pair_set_overlap(self._h, None if r is None else ctypes.byref(r)))
+
+    def overlap(self, hist=True):
+        """(counts, insert_hist): the six counts of the round just yielded (Context.table_pair_overlap's), and the insert sizes
+        of every round so far as uint64[OVERLAP_HIST_WORDS] (None without `hist`: no host wait)."""
+        counts = (ctypes.c_int64 * OVERLAP_COUNTS)()
+        h = np.zeros(OVERLAP_HIST_WORDS, dtype=np.uint64) if hist else None
+        check(lib().ffq_pair_overlap(self._h, counts, ctypes.c_void_p(h.ctypes.data) if hist else None, OVERLAP_HIST_WORDS))
+        return [int(x) for x in counts], h
 
     def close(self):
         if self._h:

@@ -338,7 +338,7 @@ int ffq_table_trim_quality(ffq_ctx *ctx, const uint8_t *d_buf, int64_t n_bytes, 
  * MAY be d_table.  Both tables 16-byte aligned.  stats = {rows changed, bases removed, rows skipped}.  FFQ_E_ARG:
  * adapter_len outside 1..64, min_overlap outside 1..adapter_len, err_permille outside 0..1000, a scan pending on the
  * context.  One host wait.  Run it behind ffq_table_trim_quality (cutadapt's order: -q first).  Not done: 5' and anchored
- * adapters, indels, several adapters per call, overlap-based adapter detection between the mates of a pair.            */
+ * adapters, indels, several adapters per call.  (Adapters found by the overlap of a pair's mates: ffq_table_pair_overlap.) */
 int ffq_table_trim_adapter(ffq_ctx *ctx, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
                            const int64_t *d_table, int64_t n_rows, const uint8_t *adapter, int adapter_len,
                            int err_permille, int min_overlap, int64_t *d_out, int64_t stats[3]);
@@ -450,7 +450,7 @@ typedef struct ffq_table_view { const uint8_t *d_buf; int64_t n_bytes; int32_t s
  * [2] = number of pairs with v1 != 0, [3] = [4] = 0.
  * n_pairs == 0 is valid.  One host wait.  FFQ_E_ARG: a pair_filter that is none of the three, a field of either rules out
  * of range, a scan pending on the context, d_buf NULL with n_bytes > 0 for a judged mate whose content rules are on.
- * Not done: interleaved input or output, overlap-based adapter detection, merging of overlapping mates.               */
+ * Not done: interleaved input or output, merging of overlapping mates.                                                 */
 int ffq_table_select_pairs(ffq_ctx *ctx, const ffq_table_view *m1, const ffq_table_view *m2, int64_t n_pairs,
                            const int64_t len_bounds[4] /* min1, max1, min2, max2 */,
                            const ffq_content_rules *rules1, const ffq_content_rules *rules2, int pair_filter,
@@ -470,6 +470,58 @@ int ffq_table_select_pairs(ffq_ctx *ctx, const ffq_table_view *m1, const ffq_tab
  * go, and everything else has to match byte for byte.                                                                 */
 int ffq_table_pair_names(ffq_ctx *ctx, const ffq_table_view *m1, const ffq_table_view *m2, int64_t n_pairs,
                          int64_t out[4] /* equal, different, not compared, ordinal of the first different pair or -1 */);
+
+/* ffq_table_pair_overlap: the overlap of the two mates of a pair -- the insert size of every pair, and adapters cut without
+ * naming them: what fastp does to paired-end reads by default.  The two mates read the same fragment from both ends; when
+ * the fragment is shorter than a read, mate 1 and the reverse complement of mate 2 overlap, and what sticks out beyond the
+ * overlap is adapter, whatever its sequence.  Row i of m1 and row i of m2 are mates.  For one pair:
+ *     a[0..n1)  = buf1[pos2:pos3] of mate 1, b[0..n2) = buf2[pos2:pos3] of mate 2
+ *     cls(x)    = the class of ffq_table_stats: 0 / 1 / 2 / 3 for A a / C c / G g / T t, 4 for every other byte
+ *     rb[j]     = 3 - cls(b[n2-1-j]) if that class is < 4, else 4: the reverse complement of mate 2
+ *     position i of a and j of rb MATCH if cls(a[i]) < 4 and cls(a[i]) == rb[j]; an N matches nothing, not even an N
+ *
+ *     if n1 < min_overlap or n2 < min_overlap: no candidate
+ *     candidates o, IN THIS ORDER: 0, 1, ..., n1 - min_overlap, then -1, -2, ..., -(n2 - min_overlap)
+ *         lo = max(0, o); hi = min(n1, n2 + o); ov = hi - lo              (>= min_overlap by construction)
+ *         mm = #{ i in [lo, hi) : a[i] and rb[i - o] do not match }
+ *         if mm <= min(max_diff, (ov * diff_permille) / 1000):            (integer division)
+ *             found: o* = o; stop
+ *     insert = n2 + o*          (the length of the fragment: from a's first base to rb's last)
+ *     if trim and o* < 0:       c1 = min(n1, insert), c2 = min(n2, insert)   (c2 == insert always)
+ *         row 1 becomes pos0, pos1, pos2, pos2 + c1, pos4, pos4 + c1; row 2 likewise with c2
+ * Only o* < 0 cuts -- fastp's choice: for o* >= 0, insert < n1 can only happen when mate 2 was shortened beforehand, and
+ * then a[insert:] is not known to be adapter.  THREE DIFFERENCES from fastp: the whole overlap is counted (fastp accepts a
+ * candidate on its first 50 positions); N never matches; both mates are cut to min(len, insert), not to fastp's
+ * overlap_len.  A consequence: bases that a 5' quality trim took off mate 2 make `insert` smaller by as many; mate 1 is then
+ * cut that much short of the adapter, never beyond it.  Mismatches only, no insertions or deletions.
+ * A pair is ANALYSED if both rows are eligible exactly as for ffq_table_trim_adapter (positions >= 0 and in order inside
+ * the buffer, pos3 - pos2 == pos5 - pos4, the sentinel's coordinate never read, no "\n" in the whole sequence) and both
+ * lengths are <= FFQ_OVERLAP_MAX_LEN.  Every other pair -- wrapped records, FASTA rows, rows written by hand that point
+ * outside, long reads -- has both rows copied unchanged and counts as not analysed.  No byte outside either [d_buf, d_buf +
+ * n_bytes) is read and none outside the rows' own checked sequence ranges; the quality line is never read.
+ * d_out1 / d_out2: n_pairs rows each, 16-byte aligned; they MAY be the input tables (pairs are independent).  d_insert
+ * (NULL: none): DEVICE memory, per pair `insert`, -1 for analysed without an overlap, -2 for not analysed.  d_hist (NULL:
+ * none): DEVICE memory, 8-byte aligned, FFQ_OVERLAP_HIST_WORDS uint64: hist[insert] += 1 per pair with an overlap;
+ * overwritten (accumulate == 0) or added to (accumulate != 0), as ffq_table_stats does; integer atomics only: the result
+ * does not depend on the order of anything.  counts: [0] pairs analysed, [1] pairs with an overlap, [2] pairs with at least
+ * one row changed, [3] bases removed from mate 1, [4] from mate 2, [5] pairs not analysed; [0] + [5] == n_pairs.
+ * n_pairs == 0 is valid.  One host wait.  FFQ_E_ARG: a field out of range, rules NULL, a scan pending on the context, a
+ * misaligned table, d_insert or d_hist, d_buf NULL with n_bytes > 0.  Run it behind the per-mate trims and in front of
+ * ffq_table_select_pairs.  Not done: merging of overlapping mates, base correction inside the overlap, indels, reads above
+ * FFQ_OVERLAP_MAX_LEN bases.                                                                                          */
+typedef struct ffq_overlap_rules {
+    int32_t min_overlap;     /* 1..FFQ_OVERLAP_MAX_LEN; fastp's default 30 */
+    int32_t max_diff;        /* 0..FFQ_OVERLAP_MAX_LEN; fastp's default 5  */
+    int32_t diff_permille;   /* 0..1000;                fastp's default 200 */
+    int32_t trim;            /* 0: analyse only, rows copied unchanged; 1: cut */
+} ffq_overlap_rules;
+#define FFQ_OVERLAP_MAX_LEN    512
+#define FFQ_OVERLAP_HIST_WORDS (2 * FFQ_OVERLAP_MAX_LEN + 1)   /* insert sizes 0..1024 */
+#define FFQ_OVERLAP_COUNTS     6
+int ffq_table_pair_overlap(ffq_ctx *ctx, const ffq_table_view *m1, const ffq_table_view *m2, int64_t n_pairs,
+                           const ffq_overlap_rules *rules, int64_t *d_out1, int64_t *d_out2,
+                           int32_t *d_insert, uint64_t *d_hist, int accumulate,
+                           int64_t counts[FFQ_OVERLAP_COUNTS]);
 
 /* FASTQ text from (buffer, table): what a pipeline that excluded reads by deleting rows and trimmed them by editing rows
  * ("to avoid saving a FASTQ file after each filtering or read-trimming step", doc/user-guide.rst:196-204) saves at its
@@ -684,7 +736,8 @@ int  ffq_stream_push(ffq_stream *s, int64_t n, int eof);
  * rows that are not yet paired.  A ROUND (ffq_pair_next) first advances every mate whose window is empty and whose stream
  * has not ended -- the stream's own wait, take and scan, with carry and refill exactly as ffq_stream_next does them --,
  * takes m = min(rows left in 1, rows left in 2) and runs ONE table chain over those m rows of both fills: the names check
- * (ffq_table_pair_names, check_names != 0), statistics IN, quality trim, adapter trim, ffq_table_select_pairs under
+ * (ffq_table_pair_names, check_names != 0), statistics IN, quality trim, adapter trim, the mates' overlap
+ * (ffq_table_pair_overlap, if ffq_pair_set_overlap asked for it: both slices edited in place), ffq_table_select_pairs under
  * pair_filter, statistics OUT, render, copies back; then both windows move by m.  A mate's fill stays resident until its
  * window is empty, so no row is processed or counted twice.  *n_pairs_in = m, *n_pairs_out = pairs kept; m may be 0 (a
  * fill without a complete record; the round that finds the end).  After each round the per-stream accessors report that
@@ -703,14 +756,20 @@ int  ffq_stream_push(ffq_stream *s, int64_t n, int eof);
  *                             round hands out nothing, earlier rounds stand (h_rows of ffq_pair_rows then holds ONE row, that
  *                             mate's record of the different pair, for the caller's message).
  * After any state but FFQ_END_REFILL the pair is done.  ffq_pair_close does not close the two streams.
- * Not done: interleaved input or output, overlap-based adapter detection, merging of overlapping mates, paired
- * readfastq_iter_range.                                                                                               */
+ * ffq_pair_set_overlap: every round analyses, and with rules->trim cuts by, the overlap of the mates behind the per-mate
+ * trims and in front of the filter; before the first ffq_pair_next only (FFQ_E_ARG afterwards, and for a field out of
+ * range); NULL switches it off.  ffq_pair_overlap: counts = the six counts of the last round; h_hist (HOST memory, NULL: not
+ * wanted; cap_words >= FFQ_OVERLAP_HIST_WORDS): the insert sizes of every round so far, as ffq_stream_stats reports its
+ * totals; one host wait.  FFQ_E_ARG without ffq_pair_set_overlap.
+ * Not done: interleaved input or output, merging of overlapping mates, paired readfastq_iter_range.                   */
 typedef struct ffq_pair ffq_pair;
 int  ffq_pair_open(ffq_stream *mate1, ffq_stream *mate2, int pair_filter, int check_names, ffq_pair **out);
 int  ffq_pair_wants(ffq_pair *p);
 int  ffq_pair_next(ffq_pair *p, int64_t *n_pairs_in, int64_t *n_pairs_out, int *end_state, int *err_mate, int64_t *err_offset);
 int  ffq_pair_rows(ffq_pair *p, int mate, const int64_t **h_rows, const uint8_t **h_bytes, int64_t *n_bytes, int64_t *bytes_offset);
 int  ffq_pair_selected(ffq_pair *p, const int64_t **h_index, int64_t pairs[5]);
+int  ffq_pair_set_overlap(ffq_pair *p, const ffq_overlap_rules *rules);
+int  ffq_pair_overlap(ffq_pair *p, int64_t counts[FFQ_OVERLAP_COUNTS], uint64_t *h_hist, int64_t cap_words);
 void ffq_pair_close(ffq_pair *p);
 
 /* Bytes [pos, pos + n_bytes) of the file behind fd into device memory (read(), fastqandfurious.py:30-36, for a range
