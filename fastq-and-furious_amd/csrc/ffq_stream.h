@@ -836,14 +836,41 @@ static int stream_scan(ffq_stream *s, const Fill &f, ffq_scan_result *res)
     }
 }
 
+// ---- the two ends of a mate's chain (a fill of a single stream, either mate of a round of a pair).  front: [stats IN], [trim],
+// [adapter] on the `n` scanned rows at `rows`, which the trims edit in place
+static int chain_front(ffq_stream *s, const Fill &f, int64_t *rows, int64_t n)
+{
+    int rc = FFQ_OK;
+    if (s->stats.which & FFQ_STATS_IN)
+        rc = ffq_table_stats(s->c, f.d_buf, f.n, 0, f.add, rows, n, s->stats.base, s->stats.cycles, 1, stream_stats_block(s, FFQ_STATS_IN), nullptr);
+    if (!rc && s->trim.on)
+        rc = ffq_table_trim_quality(s->c, f.d_buf, f.n, 0, f.add, rows, n, s->trim.base, s->trim.front, s->trim.back, rows, s->trim.last);
+    if (!rc && s->adapter.on)       // (as the quality trim left them)
+        rc = ffq_table_trim_adapter(s->c, f.d_buf, f.n, 0, f.add, rows, n, s->adapter.bytes, s->adapter.len, s->adapter.err, s->adapter.overlap, rows, s->adapter.last);
+    return rc;
+}
+
+// back: [stats OUT], [render + text D2H], rows D2H into the stream's tab.h, of the table that is handed out
+static int chain_back(ffq_stream *s, const Fill &f, const Table &t)
+{
+    int rc = FFQ_OK;
+    if (s->stats.which & FFQ_STATS_OUT)
+        rc = ffq_table_stats(s->c, f.d_buf, f.n, 0, f.add, t.d_rows, t.n, s->stats.base, s->stats.cycles, 1, stream_stats_block(s, FFQ_STATS_OUT), nullptr);
+    if (!rc && s->render.on) rc = stream_render(s, f, t);
+    if (rc) return rc;
+    if (t.n > 0) HIPCHK(hipMemcpyAsync(s->b->tab.h, t.d_rows, (size_t)t.n * 48, hipMemcpyDeviceToHost, s->c->stream));
+    return FFQ_OK;
+}
+
 // ---- the table chain of a fill: every stage the stream has switched on, over the fill's view, on the table the chain is
 // at.  With a filter the select REPLACES that table by the kept rows (on the DEVICE, before anything is copied back: a
 // dropped record costs the host nothing, doc/user-guide.rst:153-180); what follows is written once, for either table.
 // This is the one place that states the order of a fill's work on the scan stream, in every configuration:
-//     carry H2D, wait copied[0], wait copied[1], scan, [stats IN], [trim], [adapter], [select: by length, or -- content rules --
-//     by length and content (ffq_table_select_reads), on the rows as the trims left them],
-//     [stats OUT], [render + text D2H], rows D2H, [idx D2H], [gather, col D2H, coff D2H],
+//     carry H2D, wait copied[0], wait copied[1], scan, front, [select: by length, or -- content rules -- by length and
+//     content (ffq_table_select_reads), on the rows as the trims left them], back, [idx D2H], [gather, col D2H, coff D2H],
 //     [qual D2H, qoff D2H], synchronise
+// and of a round of a pair (pair_chain): [names check], mate 1: front, room for its kept rows (stream_alloc_sel), mate 2: the
+// same, room for the ordinals, [the mates' overlap], the pair select, mate 1: back, mate 2: back, ordinals D2H, synchronise
 // No rows are copied back from an empty table; a fill without records allocates and launches nothing of the push-down,
 // but statistics OUT and the render are still called (n = 0).  *n_out: the rows handed out.
 static int stream_chain(ffq_stream *s, const Fill &f, const ffq_scan_result &res, int64_t *n_out)
@@ -852,14 +879,7 @@ static int stream_chain(ffq_stream *s, const Fill &f, const ffq_scan_result &res
     StreamBufs *b = s->b;
     Table t = {b->tab.d, res.n_records};
     s->filter.scanned = res.n_records; s->filter.col_bytes = 0;
-    int rc = FFQ_OK;
-    if (s->stats.which & FFQ_STATS_IN)
-        rc = ffq_table_stats(c, f.d_buf, f.n, 0, f.add, t.d_rows, t.n, s->stats.base, s->stats.cycles, 1, stream_stats_block(s, FFQ_STATS_IN), nullptr);
-    if (!rc && s->trim.on)
-        rc = ffq_table_trim_quality(c, f.d_buf, f.n, 0, f.add, t.d_rows, t.n, s->trim.base, s->trim.front, s->trim.back, b->tab.d, s->trim.last);
-    if (!rc && s->adapter.on)       // (as the quality trim left them)
-        rc = ffq_table_trim_adapter(c, f.d_buf, f.n, 0, f.add, t.d_rows, t.n, s->adapter.bytes, s->adapter.len, s->adapter.err,
-                                    s->adapter.overlap, b->tab.d, s->adapter.last);
+    int rc = chain_front(s, f, b->tab.d, res.n_records);
     if (!rc && s->filter.on) {
         if (res.n_records > 0) rc = stream_alloc_sel(s, res.n_records, f.len + 64);
         t = Table{b->sel, 0};
@@ -874,11 +894,8 @@ static int stream_chain(ffq_stream *s, const Fill &f, const ffq_scan_result &res
             }
         }
     }
-    if (!rc && (s->stats.which & FFQ_STATS_OUT))
-        rc = ffq_table_stats(c, f.d_buf, f.n, 0, f.add, t.d_rows, t.n, s->stats.base, s->stats.cycles, 1, stream_stats_block(s, FFQ_STATS_OUT), nullptr);
-    if (!rc && s->render.on) rc = stream_render(s, f, t);
+    if (!rc) rc = chain_back(s, f, t);
     if (rc) return rc;
-    if (t.n > 0) HIPCHK(hipMemcpyAsync(b->tab.h, t.d_rows, (size_t)t.n * 48, hipMemcpyDeviceToHost, c->stream));
     if (s->filter.on && t.n > 0) HIPCHK(hipMemcpyAsync(b->idx.h, b->idx.d, (size_t)t.n * 8, hipMemcpyDeviceToHost, c->stream));
     if (s->filter.on && s->filter.col && res.n_records > 0) {
         static const int COLS[4][3] = {{0, 0, 0}, {0, 1, 1}, {2, 0, 3}, {4, 0, 5}};       // header: buf[pos0 + 1 : pos1] (:161-171)
@@ -1082,9 +1099,8 @@ static void pair_clear_last(ffq_stream *s)
     s->filter.scanned = 0; s->filter.col_bytes = 0;
 }
 
-// The table chain of a round over the slices [lo, lo + m) of both mates' fills.  The order of a round's work on the scan
-// stream: [names check], then per stage both mates: [stats IN], [trim], [adapter], [the mates' overlap, editing both slices in
-// place], the pair select into each stream's own `sel`, [stats OUT], [render + text D2H], rows D2H, and the ordinals D2H.  *differ: the names check found a different pair
+// The table chain of a round over the slices [lo, lo + m) of both mates' fills, in the order stated above stream_chain (the overlap
+// edits both slices in place, the pair select writes each stream's own `sel`).  *differ: the names check found a different pair
 // (its ordinal in the round), nothing else was done.
 static int pair_chain(ffq_pair *p, int64_t m, int64_t *n_out, int64_t *differ)
 {
@@ -1102,21 +1118,12 @@ static int pair_chain(ffq_pair *p, int64_t m, int64_t *n_out, int64_t *differ)
         if (rc) return rc;
         if (names[1] > 0) { *differ = names[3]; return FFQ_OK; }
     }
-    int64_t bounds[4];
+    int64_t bounds[4];              // (a stream without a filter counts as unbounded and ruleless)
     const ffq_content_rules *rules[2];
     for (int k = 0; k < 2 && !rc; k++) {
         ffq_stream *s = p->m[k].s;
-        const Fill &f = p->m[k].f;
-        int64_t *rows = const_cast<int64_t *>(v[k].d_table);
-        if (s->stats.which & FFQ_STATS_IN)
-            rc = ffq_table_stats(c, f.d_buf, f.n, 0, f.add, rows, m, s->stats.base, s->stats.cycles, 1, stream_stats_block(s, FFQ_STATS_IN), nullptr);
-        if (!rc && s->trim.on)
-            rc = ffq_table_trim_quality(c, f.d_buf, f.n, 0, f.add, rows, m, s->trim.base, s->trim.front, s->trim.back, rows, s->trim.last);
-        if (!rc && s->adapter.on)
-            rc = ffq_table_trim_adapter(c, f.d_buf, f.n, 0, f.add, rows, m, s->adapter.bytes, s->adapter.len, s->adapter.err, s->adapter.overlap,
-                                        rows, s->adapter.last);
+        rc = chain_front(s, p->m[k].f, const_cast<int64_t *>(v[k].d_table), m);
         if (!rc) rc = stream_alloc_sel(s, m, 0);
-        // a stream without a filter counts as unbounded and ruleless
         bounds[2 * k] = s->filter.on ? s->filter.min : -((int64_t)1 << 62);
         bounds[2 * k + 1] = s->filter.on ? s->filter.max : (int64_t)1 << 62;
         rules[k] = s->content.on ? &s->content.rules : nullptr;
@@ -1132,16 +1139,7 @@ static int pair_chain(ffq_pair *p, int64_t m, int64_t *n_out, int64_t *differ)
     int64_t kept = 0;
     if (!rc) rc = ffq_table_select_pairs(c, &v[0], &v[1], m, bounds, rules[0], rules[1], p->mode, p->m[0].s->b->sel, p->m[1].s->b->sel,
                                          p->idx.d, &kept, p->m[0].s->content.last, p->m[1].s->content.last, p->last_pairs);
-    for (int k = 0; k < 2 && !rc; k++) {
-        ffq_stream *s = p->m[k].s;
-        StreamBufs *b = s->b;
-        const Fill &f = p->m[k].f;
-        const Table t = {b->sel, kept};
-        if (s->stats.which & FFQ_STATS_OUT)
-            rc = ffq_table_stats(c, f.d_buf, f.n, 0, f.add, t.d_rows, t.n, s->stats.base, s->stats.cycles, 1, stream_stats_block(s, FFQ_STATS_OUT), nullptr);
-        if (!rc && s->render.on) rc = stream_render(s, f, t);
-        if (!rc && kept > 0) HIPCHK(hipMemcpyAsync(b->tab.h, t.d_rows, (size_t)kept * 48, hipMemcpyDeviceToHost, c->stream));
-    }
+    for (int k = 0; k < 2 && !rc; k++) rc = chain_back(p->m[k].s, p->m[k].f, Table{p->m[k].s->b->sel, kept});
     if (rc) return rc;
     if (kept > 0) HIPCHK(hipMemcpyAsync(p->idx.h, p->idx.d, (size_t)kept * 8, hipMemcpyDeviceToHost, c->stream));
     *n_out = kept;

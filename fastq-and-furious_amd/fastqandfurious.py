@@ -617,16 +617,11 @@ def readfastq_iter(fh: typing.BinaryIO, fbufsize: int,
             # push-down: the filter runs on the device, on every fill's table, before anything is copied back -- behind the
             # quality and adapter trimming of the rows, if that is what the entryfunc does
             try:
-                if isinstance(entryfunc, entryfunc_qualitytrim):
-                    st.set_trim(entryfunc.cutoff_back, entryfunc.cutoff_front, entryfunc.qual_base)
-                if isinstance(entryfunc, entryfunc_adaptertrim):
-                    if entryfunc.quality is not None:
-                        q = entryfunc.quality
-                        st.set_trim(q.cutoff_back, q.cutoff_front, q.qual_base)
-                    st.set_adapter(entryfunc.adapter, entryfunc.err_permille, entryfunc.min_overlap)
-                if isinstance(entryfunc, entryfunc_contentfilter):
-                    st.set_content(entryfunc.rules)
-                st.set_filter(entryfunc.min_len, entryfunc.max_len, None if entryfunc.column == "entry" else entryfunc.column)
+                cutter = entryfunc if isinstance(entryfunc, entryfunc_adaptertrim) else None
+                trim = cutter.quality if cutter is not None else entryfunc if isinstance(entryfunc, entryfunc_qualitytrim) else None
+                content = entryfunc.rules if isinstance(entryfunc, entryfunc_contentfilter) else None
+                _configure_stream(st, trim, cutter, content, (entryfunc.min_len, entryfunc.max_len),
+                                  None if entryfunc.column == "entry" else entryfunc.column)
             except BaseException:
                 st.close()                 # (the native stream, its pinned buffers and its feeder thread; a gzip stream's hook)
                 raise
@@ -938,6 +933,120 @@ class FilterReport:
         self.dropped = dict.fromkeys(ContentRules.REASONS, 0)
 
 
+def _scanner(entrypos):
+    """(the scanner, its open_stream or None): entrypos None is the GPU scanner, which has a native stream front end."""
+    if entrypos is None:
+        from . import _fastqandfurious as _C
+        entrypos = _C.entrypos
+    return entrypos, getattr(entrypos, 'open_stream', None)
+
+
+def _configure_stream(st, trim, cutter, content, bounds, column=None, render=False, stats=None):
+    """What a native stream is asked for, in the order its chain works (csrc/ffq_stream.h states it above stream_chain): the
+    quality trim (an entryfunc_qualitytrim), the adapter trim (an entryfunc_adaptertrim), the content rules, the length
+    filter (bounds: (min_len, max_len)) with the gathered column, the render, the statistics (stats: (qual_base,
+    max_cycles)).  None / False: that setter is not called.  A stage that is added to the chain is added HERE."""
+    if trim is not None:
+        st.set_trim(trim.cutoff_back, trim.cutoff_front, trim.qual_base)
+    if cutter is not None:
+        st.set_adapter(cutter.adapter, cutter.err_permille, cutter.min_overlap)
+    if content is not None:
+        st.set_content(content)
+    if bounds is not None:
+        st.set_filter(bounds[0], bounds[1], column)
+    if render:
+        st.set_render()
+    if stats is not None:
+        st.set_stats(_hip.STATS_IN | _hip.STATS_OUT, stats[0], stats[1])
+
+
+class _MatePlan:
+    """What the records of ONE input file go through in filter_fastq (one plan) and filter_fastq_paired (one per mate), said
+    once for both routes: quality trim, adapter trim, the verdict by length and then by content, the counts, the text.  On the
+    device route the plan configures the file's stream and drains every fill (or round) of it; on the host route it is
+    called record by record.  judged=False: the mate is trimmed, counted and written but never dropped (pair_filter "first").
+    `dropped`: this file's records by the reason (ContentRules.REASONS) they failed for; `report` (a FilterReport or None) is
+    reset and bound to it."""
+
+    def __init__(self, quality_cutoff, qual_base, adapter, err_permille, min_overlap, min_len, max_len, content, report, judged=True):
+        self.qual_base, self.content, self.report, self.judged = qual_base, content, report, judged
+        self.dropped = dict.fromkeys(ContentRules.REASONS, 0)
+        if report is not None:
+            report.dropped = self.dropped
+            report.before = FastqStats(report.max_cycles, qual_base)
+            report.after = FastqStats(report.max_cycles, qual_base)
+        self.trim = self.cutter = None
+        if quality_cutoff is not None:
+            front, back = (0, quality_cutoff) if isinstance(quality_cutoff, (int, np.integer)) else quality_cutoff
+            self.trim = entryfunc_qualitytrim(back, front, qual_base)            # (checks the ranges)
+        if adapter is not None:
+            self.cutter = entryfunc_adaptertrim(adapter, err_permille, min_overlap, quality_cutoff, qual_base)
+        self.lo = None if min_len is None else int(min_len)
+        self.hi = None if max_len is None else int(max_len)
+
+    # ---- the device route
+    def configure(self, st):
+        """the file's stream: what is switched on, the render, and the statistics if there is a report"""
+        rep = self.report
+        _configure_stream(st, self.trim, self.cutter, self.content, None if self.lo is None and self.hi is None else (self.lo, self.hi),
+                          render=True, stats=None if rep is None else (self.qual_base, rep.max_cycles))
+
+    def drain(self, st, fh_out):
+        """One fill (or round) of the stream: its text written with one write, its drops counted; (bytes written, rows
+        rendered, bases the two trims removed)."""
+        text, (nb, rendered, _skipped) = st.rendered()
+        if nb:
+            fh_out.write(memoryview(text))
+        if st.filtered and self.judged:
+            for reason, k in zip(ContentRules.REASONS, st.filter_counts()[1:7]):
+                self.dropped[reason] += k
+        removed = 0
+        if self.trim is not None:
+            removed += st.trimmed()[1]
+        if self.cutter is not None:
+            removed += st.adapter_trimmed()[1]
+        return nb, rendered, removed
+
+    def finish(self, st):
+        """the statistics the stream counted, read back once"""
+        rep = self.report
+        if rep is not None:
+            rep.before = FastqStats.from_words(st.stats(_hip.STATS_IN), rep.max_cycles, self.qual_base)
+            rep.after = FastqStats.from_words(st.stats(_hip.STATS_OUT), rep.max_cycles, self.qual_base)
+
+    # ---- the host route
+    def trimmed_pos(self, buf, pos):
+        """(the positions as the trims leave them, bases cut) of a record as read, which is counted into `before`."""
+        length = pos[3] - pos[2]
+        if self.report is not None:
+            self.report.before.add_pos(buf, pos)
+        if self.cutter is not None:
+            pos = self.cutter.trimmed_pos(buf, pos)          # (the quality rule first, if there is one)
+        elif self.trim is not None:
+            pos = self.trim.trimmed_pos(buf, pos)
+        return pos, length - (pos[3] - pos[2])
+
+    def verdict(self, buf, pos):
+        """0, or the 1-based reason (counted into `dropped`) the record fails for, as the trims (and the overlap) left it:
+        its length first, then the content rules."""
+        v = 0
+        if self.judged:
+            length = pos[3] - pos[2]
+            if (self.lo is not None and length < self.lo) or (self.hi is not None and length > self.hi):
+                v = 1
+            elif self.content is not None:
+                v = self.content.verdict_pos(buf, pos)[0]
+        if v:
+            self.dropped[ContentRules.REASONS[v - 1]] += 1
+        return v
+
+    def text(self, buf, pos):
+        """a kept record as it is written, which is counted into `after`"""
+        if self.report is not None:
+            self.report.after.add_pos(buf, pos)
+        return b"".join((b"@", buf[(pos[0] + 1):pos[1]], b"\n", buf[pos[2]:pos[3]], b"\n+\n", buf[pos[4]:pos[5]], b"\n"))
+
+
 def fastq_stats(fh: typing.BinaryIO, fbufsize: int = 1 << 24, qual_base: int = 33, max_cycles: int = 512,
                 entrypos: typing.Optional[typing.Callable] = None) -> FastqStats:
     """The statistics of every record of a FASTQ stream.  entrypos None (the GPU scanner): the stream front end scans
@@ -945,10 +1054,7 @@ def fastq_stats(fh: typing.BinaryIO, fbufsize: int = 1 << 24, qual_base: int = 3
     are read once at the end.  Any other scanner: a loop over readfastq_iter with FastqStats.add_pos.  Malformed input
     raises what readfastq_iter raises."""
     out = FastqStats(max_cycles, qual_base)
-    if entrypos is None:
-        from . import _fastqandfurious as _C
-        entrypos = _C.entrypos
-    open_stream = getattr(entrypos, 'open_stream', None)
+    entrypos, open_stream = _scanner(entrypos)
     st = open_stream(fh, fbufsize) if open_stream is not None else None
     if st is not None:
         try:
@@ -1009,83 +1115,29 @@ def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1
     ContentRules.verdict_pos with any other.  Rows the rules do not apply to (wrapped records) go by their length alone."""
     if content is not None and not isinstance(content, ContentRules):
         raise TypeError("content must be a ContentRules")
-    dropped = dict.fromkeys(ContentRules.REASONS, 0)
-    if report is not None:
-        report.dropped = dropped
-        report.before = FastqStats(report.max_cycles, qual_base)
-        report.after = FastqStats(report.max_cycles, qual_base)
-    trim = None
-    if quality_cutoff is not None:
-        front, back = (0, quality_cutoff) if isinstance(quality_cutoff, (int, np.integer)) else quality_cutoff
-        trim = entryfunc_qualitytrim(back, front, qual_base)            # (checks the ranges)
-    cutter = None
-    if adapter is not None:
-        cutter = entryfunc_adaptertrim(adapter, err_permille, min_overlap, quality_cutoff, qual_base)
-    lo = None if min_len is None else int(min_len)
-    hi = None if max_len is None else int(max_len)
-    if entrypos is None:
-        from . import _fastqandfurious as _C
-        entrypos = _C.entrypos
+    plan = _MatePlan(quality_cutoff, qual_base, adapter, err_permille, min_overlap, min_len, max_len, content, report)
+    entrypos, open_stream = _scanner(entrypos)
     n_in = n_out = removed = n_bytes = 0
-    open_stream = getattr(entrypos, 'open_stream', None)
     st = open_stream(fh, fbufsize) if open_stream is not None else None
     if st is not None:
         try:
-            if trim is not None:
-                st.set_trim(trim.cutoff_back, trim.cutoff_front, trim.qual_base)
-            if cutter is not None:
-                st.set_adapter(cutter.adapter, cutter.err_permille, cutter.min_overlap)
-            if content is not None:
-                st.set_content(content)
-            if lo is not None or hi is not None:
-                st.set_filter(lo, hi)
-            st.set_render()
-            if report is not None:
-                st.set_stats(_hip.STATS_IN | _hip.STATS_OUT, qual_base, report.max_cycles)
+            plan.configure(st)
             for rows, _fill, _fill_offset, end_state, err_offset in st:
-                text, (nb, rendered, _skipped) = st.rendered()
-                if nb:
-                    fh_out.write(memoryview(text))
+                nb, rendered, cut = plan.drain(st, fh_out)
                 n_in += st.selected()[1] if st.filtered else rows.shape[0]
-                if st.filtered:
-                    for reason, k in zip(ContentRules.REASONS, st.filter_counts()[1:7]):
-                        dropped[reason] += k
                 n_out += rendered
                 n_bytes += nb
-                if trim is not None:
-                    removed += st.trimmed()[1]
-                if cutter is not None:
-                    removed += st.adapter_trimmed()[1]
+                removed += cut
                 if end_state != _END_OK and end_state != _END_REFILL:
                     _raise_for_end(end_state, err_offset)
-            if report is not None:
-                report.before = FastqStats.from_words(st.stats(_hip.STATS_IN), report.max_cycles, qual_base)
-                report.after = FastqStats.from_words(st.stats(_hip.STATS_OUT), report.max_cycles, qual_base)
+            plan.finish(st)
         finally:
             st.close()
         return FilterResult(n_in, n_out, removed, n_bytes)
 
     def record(buf, pos, globaloffset=None):
-        length = pos[3] - pos[2]
-        if report is not None:
-            report.before.add_pos(buf, pos)
-        if cutter is not None:
-            pos = cutter.trimmed_pos(buf, pos)          # (the quality rule first, if there is one)
-        elif trim is not None:
-            pos = trim.trimmed_pos(buf, pos)
-        cut = length - (pos[3] - pos[2])
-        length -= cut
-        if (lo is not None and length < lo) or (hi is not None and length > hi):
-            dropped["length"] += 1
-            return cut, None
-        if content is not None:
-            v = content.verdict_pos(buf, pos)[0]
-            if v:
-                dropped[ContentRules.REASONS[v - 1]] += 1
-                return cut, None
-        if report is not None:
-            report.after.add_pos(buf, pos)
-        return cut, b"".join((b"@", buf[(pos[0] + 1):pos[1]], b"\n", buf[pos[2]:pos[3]], b"\n+\n", buf[pos[4]:pos[5]], b"\n"))
+        pos, cut = plan.trimmed_pos(buf, pos)
+        return cut, None if plan.verdict(buf, pos) else plan.text(buf, pos)
 
     for cut, text in readfastq_iter(fh, fbufsize, record, entrypos):
         n_in += 1
@@ -1264,28 +1316,13 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
         a, b = tuple(x) if isinstance(x, (tuple, list)) else (x, x)
         return (None if a is None else int(a), None if b is None else int(b))
     los, his = per_mate(min_len), per_mate(max_len)
-    reports = (report, report2)
-    hists = (dict.fromkeys(ContentRules.REASONS, 0), dict.fromkeys(ContentRules.REASONS, 0))
-    for rep, hist in zip(reports, hists):
-        if rep is not None:
-            rep.dropped = hist
-            rep.before = FastqStats(rep.max_cycles, qual_base)
-            rep.after = FastqStats(rep.max_cycles, qual_base)
-    trim = None
-    if quality_cutoff is not None:
-        front, back = (0, quality_cutoff) if isinstance(quality_cutoff, (int, np.integer)) else quality_cutoff
-        trim = entryfunc_qualitytrim(back, front, qual_base)            # (checks the ranges)
-    cutters = tuple(None if a is None else entryfunc_adaptertrim(a, err_permille, min_overlap, quality_cutoff, qual_base)
-                    for a in (adapter, adapter2))
+    plans = tuple(_MatePlan(quality_cutoff, qual_base, a, err_permille, min_overlap, lo, hi, content, rep, judged)
+                  for a, lo, hi, rep, judged in zip((adapter, adapter2), los, his, (report, report2), (True, pair_filter != "first")))
     dropped = {"mate1_only": 0, "mate2_only": 0, "both": 0}
-    judged = (True, pair_filter != "first")
-    if entrypos is None:
-        from . import _fastqandfurious as _C
-        entrypos = _C.entrypos
+    entrypos, open_stream = _scanner(entrypos)
     pairs_in = pairs_out = removed = 0
     n_bytes = [0, 0]
     outs = (fh_out1, fh_out2)
-    open_stream = getattr(entrypos, 'open_stream', None)
     sts = []
     if open_stream is not None:
         for fh in (fh1, fh2):
@@ -1300,18 +1337,8 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
     if sts:
         ps = None
         try:
-            for k, st in enumerate(sts):
-                if trim is not None:
-                    st.set_trim(trim.cutoff_back, trim.cutoff_front, trim.qual_base)
-                if cutters[k] is not None:
-                    st.set_adapter(cutters[k].adapter, cutters[k].err_permille, cutters[k].min_overlap)
-                if content is not None:
-                    st.set_content(content)
-                if los[k] is not None or his[k] is not None:
-                    st.set_filter(los[k], his[k])
-                st.set_render()
-                if reports[k] is not None:
-                    st.set_stats(_hip.STATS_IN | _hip.STATS_OUT, qual_base, reports[k].max_cycles)
+            for plan, st in zip(plans, sts):
+                plan.configure(st)
             ps = _hip.PairStream(sts[0], sts[1], pair_filter, check_names)
             if overlap is not None:
                 ps.set_overlap(overlap)
@@ -1326,18 +1353,10 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
                     orep.bases_removed[0] += oc[3]
                     orep.bases_removed[1] += oc[4]
                     removed += oc[3] + oc[4]
-                for k, st in enumerate(sts):
-                    text, (nb, _rendered, _skipped) = st.rendered()
-                    if nb:
-                        outs[k].write(memoryview(text))
+                for k, (plan, st) in enumerate(zip(plans, sts)):
+                    nb, _rendered, cut = plan.drain(st, outs[k])
                     n_bytes[k] += nb
-                    if st.filtered and judged[k]:
-                        for reason, c in zip(ContentRules.REASONS, st.filter_counts()[1:7]):
-                            hists[k][reason] += c
-                    if trim is not None:
-                        removed += st.trimmed()[1]
-                    if cutters[k] is not None:
-                        removed += st.adapter_trimmed()[1]
+                    removed += cut
                 pc = ps.selected()[1]
                 if pair_filter != "both":            # (under "both" a pair with one failed mate is kept)
                     dropped["mate1_only"] += pc[2]
@@ -1348,10 +1367,8 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
                     if end_state == _hip.END_ERR_PAIR_NAMES:
                         names = tuple(pair_id(h) for h in ps.mismatch())
                     _raise_for_pair_end(end_state, err_mate, err_offset, names)
-            for k, st in enumerate(sts):
-                if reports[k] is not None:
-                    reports[k].before = FastqStats.from_words(st.stats(_hip.STATS_IN), reports[k].max_cycles, qual_base)
-                    reports[k].after = FastqStats.from_words(st.stats(_hip.STATS_OUT), reports[k].max_cycles, qual_base)
+            for plan, st in zip(plans, sts):
+                plan.finish(st)
             if overlap is not None:
                 orep.insert_hist = ps.overlap()[1]
         finally:
@@ -1361,33 +1378,14 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
                 st.close()
         return PairedFilterResult(pairs_in, pairs_out, removed, n_bytes[0], n_bytes[1], dropped)
 
-    def recorder(k):
-        cutter, rep = cutters[k], reports[k]
-
+    def recorder(plan):
         def record(buf, pos, globaloffset=None):
-            length = pos[3] - pos[2]
+            """(where it is, its id, bases cut, its buffer, its positions as the trims left them): kept until its mate is there"""
             at = pos[0] + (globaloffset or 0)
             name = pair_id(buf[(pos[0] + 1):pos[1]]) if check_names else None
-            if rep is not None:
-                rep.before.add_pos(buf, pos)
-            if cutter is not None:
-                pos = cutter.trimmed_pos(buf, pos)          # (the quality rule first, if there is one)
-            elif trim is not None:
-                pos = trim.trimmed_pos(buf, pos)
-            pos = tuple(pos[i] for i in range(6))
-            cut = length - (pos[3] - pos[2])
-            return at, name, cut, buf, pos
+            pos, cut = plan.trimmed_pos(buf, pos)
+            return at, name, cut, buf, tuple(pos[i] for i in range(6))
         return record
-
-    def verdict(k, buf, pos):
-        """a mate judged alone, as the trims (and the overlap) left it"""
-        length = pos[3] - pos[2]
-        if judged[k]:
-            if (los[k] is not None and length < los[k]) or (his[k] is not None and length > his[k]):
-                return 1
-            if content is not None:
-                return content.verdict_pos(buf, pos)[0]
-        return 0
 
     def overlap_cut(r1, r2):
         """the two records with the overlap's cut applied, and the report filled"""
@@ -1412,7 +1410,7 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
         orep.pairs_trimmed += 1
         return tuple(out)
 
-    its = [iter(readfastq_iter(fh, fbufsize, recorder(k), entrypos)) for k, fh in enumerate((fh1, fh2))]
+    its = [iter(readfastq_iter(fh, fbufsize, recorder(plan), entrypos)) for plan, fh in zip(plans, (fh1, fh2))]
 
     def step(it):
         """(record, None), (None, None) at the end, (None, error)"""
@@ -1438,20 +1436,14 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
         pairs_in += 1
         if overlap is not None:
             r1, r2 = overlap_cut(r1, r2)
-        v1, v2 = verdict(0, r1[3], r1[4]), verdict(1, r2[3], r2[4])
-        for k, (r, v) in enumerate(((r1, v1), (r2, v2))):
-            removed += r[2]
-            if v:
-                hists[k][ContentRules.REASONS[v - 1]] += 1
+        v1, v2 = plans[0].verdict(r1[3], r1[4]), plans[1].verdict(r2[3], r2[4])
+        removed += r1[2] + r2[2]
         if _pair_dropped(pair_filter, v1, v2):
             dropped["both" if (v1 and v2) else "mate1_only" if v1 else "mate2_only"] += 1
             continue
         pairs_out += 1
         for k, r in enumerate((r1, r2)):
-            buf, pos = r[3], r[4]
-            if reports[k] is not None:
-                reports[k].after.add_pos(buf, pos)
-            text = b"".join((b"@", buf[(pos[0] + 1):pos[1]], b"\n", buf[pos[2]:pos[3]], b"\n+\n", buf[pos[4]:pos[5]], b"\n"))
+            text = plans[k].text(r[3], r[4])
             outs[k].write(text)
             n_bytes[k] += len(text)
     return PairedFilterResult(pairs_in, pairs_out, removed, n_bytes[0], n_bytes[1], dropped)
