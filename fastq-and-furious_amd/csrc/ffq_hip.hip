@@ -16,6 +16,7 @@
 #include "ffq_pair.h"
 #include "ffq_overlap.h"
 #include "ffq_render.h"
+#include "ffq_merge.h"
 #include "ffq_pool.h"
 #include "ffq_mem.h"
 
@@ -233,6 +234,8 @@ struct ffq_ctx {
     cpu_set_t near_cpus;           // the CPUs next to the GPU (ctx_near), near_ok: known
     int near_ok = -1;
     void *stream_cache = nullptr;  // buffers of the last closed ffq_stream (ffq_stream.h), reused by the next one
+    DevBuf<MergeBlock> d_merge;    // ffq_table_pair_merge: the call's counts and their pinned mirror
+    PinBuf<MergeBlock> h_merge;
 };
 
 extern "C" int ffq_abi_version(void) { return FFQ_ABI_VERSION; }
@@ -309,6 +312,8 @@ static int ctx_create_impl(int device, ffq_ctx *share, ffq_ctx **out)
     if (e == hipSuccess) e = c->h_overlap.grow(1);
     if (e == hipSuccess) e = c->d_render.grow(1);
     if (e == hipSuccess) e = c->h_render.grow(1);
+    if (e == hipSuccess) e = c->d_merge.grow(1);
+    if (e == hipSuccess) e = c->h_merge.grow(1);
     if (e == hipSuccess) e = c->fa_hdr.grow(1);
     if (e == hipSuccess) e = c->h_cut.grow(6);
     if (e == hipSuccess) e = c->h_L.grow(1);
@@ -2409,6 +2414,71 @@ extern "C" int ffq_table_render_fastq(ffq_ctx *c, const uint8_t *d_buf, int64_t 
     if (stats[0] > out_cap)
         return fail(FFQ_E_TABLE_FULL, "output holds %lld bytes, the rendered rows have %lld", (long long)out_cap,
                     (long long)stats[0]);
+    return FFQ_OK;
+}
+
+// ---- the mates of a pair merged into one read (csrc/ffq_merge.h) ------------------------------
+static_assert(MRG_MAX_LEN == FFQ_OVERLAP_MAX_LEN && MERGE_COUNTS == FFQ_MERGE_COUNTS, "include/ffq.h");
+
+extern "C" int ffq_table_pair_merge(ffq_ctx *c, const ffq_table_view *m1, const ffq_table_view *m2, int64_t n_pairs,
+                                    const int32_t *d_insert, const int64_t *d_ord, uint8_t *d_text, int64_t text_cap, int64_t *d_off,
+                                    int64_t *d_rest1, int64_t *d_rest2, int64_t *d_rest_ord, int64_t *n_rest,
+                                    int64_t counts[FFQ_MERGE_COUNTS])
+{
+    static const char *const who = "ffq_table_pair_merge";
+    mark_other(c);
+    if (!c || !counts || !n_rest || n_pairs < 0 || text_cap < 0 || (text_cap > 0 && !d_text) || !view_ok(m1, n_pairs) || !view_ok(m2, n_pairs) ||
+        (n_pairs > 0 && (!d_rest1 || !d_rest2)))
+        return fail(FFQ_E_ARG, "%s: bad argument", who);
+    if (n_pairs > 0 && !d_insert) return fail(FFQ_E_ARG, "%s: no insert sizes (d_insert)", who);
+    if (((reinterpret_cast<uintptr_t>(d_rest1) | reinterpret_cast<uintptr_t>(d_rest2)) & 15) != 0)
+        return fail(FFQ_E_ARG, "%s: tables must be 16-byte aligned", who);
+    if (((reinterpret_cast<uintptr_t>(d_off) | reinterpret_cast<uintptr_t>(d_ord) | reinterpret_cast<uintptr_t>(d_rest_ord)) & 7) != 0 ||
+        (reinterpret_cast<uintptr_t>(d_insert) & 3) != 0)
+        return fail(FFQ_E_ARG, "%s: d_off, d_ord and d_rest_ord must be 8-byte aligned, d_insert 4-byte aligned", who);
+    if ((m1->n_bytes > 0 && !m1->d_buf) || (m2->n_bytes > 0 && !m2->d_buf)) return fail(FFQ_E_ARG, "%s: no buffer to read the mates from", who);
+    if (n_pairs > 0 && (d_rest1 == m1->d_table || d_rest1 == m2->d_table || d_rest2 == m1->d_table || d_rest2 == m2->d_table || d_rest1 == d_rest2))
+        return fail(FFQ_E_ARG, "%s: d_rest1 and d_rest2 must not be one of the tables, or each other", who);
+    if (c->pend.active) return fail(FFQ_E_ARG, "%s: a scan is pending on this context", who);
+    HIPCHK(hipSetDevice(c->device));
+    for (int i = 0; i < MERGE_COUNTS; i++) counts[i] = 0;
+    *n_rest = 0;
+    hipStream_t st = c->stream;
+    if (n_pairs == 0) {
+        if (d_off) {
+            HIPCHK(hipMemsetAsync(d_off, 0, sizeof(int64_t), st));
+            HIPCHK(hipStreamSynchronize(st));
+        }
+        return FFQ_OK;
+    }
+    const int64_t nblk = (n_pairs + MERGE_WG - 1) / MERGE_WG;
+    // (everything is grown before anything is enqueued: growing waits for the stream)
+    int rc = grow_dev(c, c->col_sum, nblk);
+    if (!rc) rc = grow_dev(c, c->sel_cnt, nblk);
+    if (!rc) rc = grow_dev(c, c->sel_base, nblk);
+    if (!rc) {
+        const hipError_t e = c->col_res.grow(1);
+        if (e != hipSuccess) rc = fail(FFQ_E_NOMEM, "hipMalloc failed: %s", hipGetErrorString(e));
+    }
+    if (rc) return rc;
+    const PairSide A = {m1->d_buf, m1->n_bytes, m1->sentinel ? 1 : 0, m1->add, m1->d_table};
+    const PairSide B = {m2->d_buf, m2->n_bytes, m2->sentinel ? 1 : 0, m2->add, m2->d_table};
+    HIPCHK(hipMemsetAsync(c->d_merge, 0, sizeof(MergeBlock), st));
+    hipLaunchKernelGGL(k_merge_sum, dim3((unsigned)std::min<int64_t>(nblk, 2048)), dim3(MERGE_WG), 0, st, A, B, n_pairs, nblk, d_insert, d_ord,
+                       c->col_sum.p, c->sel_cnt.p, c->d_merge.p);
+    if ((rc = launch_scan_i64v(c, st, c->col_sum, nblk, n_pairs, c->col_res))) return rc;
+    if ((rc = launch_scan_u32(c, st, (const unsigned int *)c->sel_cnt, nblk, c->sel_base, (long long *)c->d_word.p))) return rc;
+    hipLaunchKernelGGL(k_merge_rows, dim3((unsigned)nblk), dim3(MERGE_WG), 0, st, A, B, n_pairs, d_insert, d_ord, (const long long *)c->col_sum,
+                       (const DevRes *)c->col_res, (const long long *)c->sel_base, d_text, text_cap, d_off, d_rest1, d_rest2, d_rest_ord,
+                       c->d_merge.p);
+    HIPCHK(hipMemcpyAsync(c->h_merge, c->d_merge, sizeof(MergeBlock), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    for (int i = 0; i < MERGE_COUNTS; i++) counts[i] = (int64_t)c->h_merge->cnt[i];
+    counts[1] = n_pairs - counts[0];
+    *n_rest = counts[1];
+    if (counts[2] > text_cap)
+        return fail(FFQ_E_TABLE_FULL, "text holds %lld bytes, the merged reads have %lld", (long long)text_cap, (long long)counts[2]);
     return FFQ_OK;
 }
 

@@ -870,7 +870,9 @@ static int chain_back(ffq_stream *s, const Fill &f, const Table &t)
 //     content (ffq_table_select_reads), on the rows as the trims left them], back, [idx D2H], [gather, col D2H, coff D2H],
 //     [qual D2H, qoff D2H], synchronise
 // and of a round of a pair (pair_chain): [names check], mate 1: front, room for its kept rows (stream_alloc_sel), mate 2: the
-// same, room for the ordinals, [the mates' overlap], the pair select, mate 1: back, mate 2: back, ordinals D2H, synchronise
+// same, room for the ordinals, [room for the merge], [the mates' overlap], the pair select, [the merge of the kept pairs: then
+// what follows is on the rest tables and the rest ordinals], mate 1: back, mate 2: back, ordinals D2H, [merged text D2H],
+// synchronise
 // No rows are copied back from an empty table; a fill without records allocates and launches nothing of the push-down,
 // but statistics OUT and the render are still called (n = 0).  *n_out: the rows handed out.
 static int stream_chain(ffq_stream *s, const Fill &f, const ffq_scan_result &res, int64_t *n_out)
@@ -1020,6 +1022,16 @@ struct ffq_pair {
     // the mates' overlap analysed, and cut by, in every round (ffq_pair_set_overlap): the insert sizes summed over the rounds
     // on the device, the six counts of the last round
     struct { bool on = false; ffq_overlap_rules rules = {}; DevBuf<uint64_t> hist; int64_t last[FFQ_OVERLAP_COUNTS] = {0, 0, 0, 0, 0, 0}; } overlap;
+    // the kept pairs merged where the rule allows it (ffq_pair_set_merge): the round's insert sizes, the rows and ordinals of the
+    // kept pairs that are not merged (what the round hands out then), the merged text and the six counts of the last round
+    struct {
+        bool on = false;
+        DevBuf<int32_t> insert;
+        DevBuf<int64_t> rest[2];
+        Mirror<int64_t> ord;
+        Mirror<uint8_t> text;
+        int64_t last[FFQ_MERGE_COUNTS] = {0, 0, 0, 0, 0, 0};
+    } merge;
 };
 
 extern "C" int ffq_pair_open(ffq_stream *mate1, ffq_stream *mate2, int pair_filter, int check_names, ffq_pair **out)
@@ -1056,7 +1068,7 @@ extern "C" int ffq_pair_set_overlap(ffq_pair *p, const ffq_overlap_rules *rules)
 {
     if (!p) return fail(FFQ_E_ARG, "ffq_pair_set_overlap: NULL pair");
     if (p->started) return fail(FFQ_E_ARG, "ffq_pair_set_overlap: the walk has begun (call it before the first ffq_pair_next)");
-    if (!rules) { p->overlap.on = false; return FFQ_OK; }
+    if (!rules) { p->overlap.on = p->merge.on = false; return FFQ_OK; }       // (no insert sizes: nothing to merge by)
     int rc = overlap_arg("ffq_pair_set_overlap", rules);
     if (rc) return rc;
     ffq_ctx *c = p->c;
@@ -1089,6 +1101,25 @@ extern "C" int ffq_pair_overlap(ffq_pair *p, int64_t counts[FFQ_OVERLAP_COUNTS],
     return FFQ_OK;
 }
 
+extern "C" int ffq_pair_set_merge(ffq_pair *p, int on)
+{
+    if (!p) return fail(FFQ_E_ARG, "ffq_pair_set_merge: NULL pair");
+    if (p->started) return fail(FFQ_E_ARG, "ffq_pair_set_merge: the walk has begun (call it before the first ffq_pair_next)");
+    if (on && !p->overlap.on) return fail(FFQ_E_ARG, "ffq_pair_set_merge: the pair does not analyse overlaps (ffq_pair_set_overlap first)");
+    p->merge.on = on != 0;
+    return FFQ_OK;
+}
+
+// the last round's merged text and its six counts
+extern "C" int ffq_pair_merged(ffq_pair *p, const uint8_t **h_text, int64_t *n_bytes, int64_t counts[FFQ_MERGE_COUNTS])
+{
+    if (!p || !h_text || !n_bytes) return fail(FFQ_E_ARG, "ffq_pair_merged: NULL argument");
+    if (!p->merge.on) return fail(FFQ_E_ARG, "ffq_pair_merged: the pair does not merge (ffq_pair_set_merge)");
+    *h_text = p->merge.text.h; *n_bytes = p->merge.last[2];
+    if (counts) for (int i = 0; i < FFQ_MERGE_COUNTS; i++) counts[i] = p->merge.last[i];
+    return FFQ_OK;
+}
+
 extern "C" int ffq_pair_wants(ffq_pair *p) { return p && !p->failed ? walk_wants(p->w) : 0; }
 
 // what the per-stream accessors report for a round: zero until the round's chain says otherwise
@@ -1097,6 +1128,28 @@ static void pair_clear_last(ffq_stream *s)
     for (int i = 0; i < 3; i++) s->trim.last[i] = s->adapter.last[i] = s->render.last[i] = 0;
     for (int i = 0; i < FFQ_FILTER_COUNTS; i++) s->content.last[i] = 0;
     s->filter.scanned = 0; s->filter.col_bytes = 0;
+}
+
+// The end of a merging round's chain, behind the pair select: the `kept` pairs of both `sel` tables merged by the insert sizes
+// of their ordinals, the two ends of the mates' chains on the rest tables, the rest ordinals and the merged text copied back.
+static int pair_chain_merge(ffq_pair *p, int64_t kept, int64_t *n_out)
+{
+    ffq_ctx *c = p->c;
+    ffq_table_view v[2];
+    for (int k = 0; k < 2; k++) v[k] = ffq_table_view{p->m[k].f.d_buf, p->m[k].f.n, 0, p->m[k].f.add, p->m[k].s->b->sel.p};
+    int64_t n_rest = 0;
+    int rc = ffq_table_pair_merge(c, &v[0], &v[1], kept, p->merge.insert.p, p->idx.d, p->merge.text.d, p->merge.text.d.cap, nullptr,
+                                  p->merge.rest[0].p, p->merge.rest[1].p, p->merge.ord.d, &n_rest, p->merge.last);
+    if (rc == FFQ_E_TABLE_FULL)
+        return fail(FFQ_E_INTERNAL, "ffq_pair: fills of %lld and %lld bytes merged to %lld", (long long)v[0].n_bytes, (long long)v[1].n_bytes,
+                    (long long)p->merge.last[2]);
+    for (int k = 0; k < 2 && !rc; k++) rc = chain_back(p->m[k].s, p->m[k].f, Table{p->merge.rest[k].p, n_rest});
+    if (rc) return rc;
+    if (n_rest > 0) HIPCHK(hipMemcpyAsync(p->merge.ord.h, p->merge.ord.d, (size_t)n_rest * 8, hipMemcpyDeviceToHost, c->stream));
+    if (p->merge.last[2] > 0)
+        HIPCHK(hipMemcpyAsync(p->merge.text.h, p->merge.text.d, (size_t)p->merge.last[2], hipMemcpyDeviceToHost, c->stream));
+    *n_out = n_rest;
+    return FFQ_OK;
 }
 
 // The table chain of a round over the slices [lo, lo + m) of both mates' fills, in the order stated above stream_chain (the overlap
@@ -1133,12 +1186,27 @@ static int pair_chain(ffq_pair *p, int64_t m, int64_t *n_out, int64_t *differ)
         HIPCHK(hipStreamSynchronize(c->stream));
         rc = stream_grow(p->idx, m, "ffq_pair: no memory for %lld selected pairs", m);
     }
+    int32_t *d_insert = nullptr;
+    if (!rc && p->merge.on) {
+        // (the merged text of a pair is shorter than its two records together: header + 2 (n1 + n2 - 1) + 6 bytes)
+        const int64_t text_cap = p->m[0].f.n + p->m[1].f.n + 64;
+        if (p->merge.insert.cap < m || p->merge.rest[0].cap < 6 * m || p->merge.rest[1].cap < 6 * m || p->merge.ord.d.cap < m ||
+            p->merge.text.d.cap < text_cap) {
+            HIPCHK(hipStreamSynchronize(c->stream));
+            rc = stream_grow(p->merge.insert, m, "ffq_pair: no memory for %lld insert sizes", m);
+            for (int k = 0; k < 2 && !rc; k++) rc = stream_grow(p->merge.rest[k], 6 * m, "ffq_pair: no memory for %lld unmerged rows", m);
+            if (!rc) rc = stream_grow(p->merge.ord, m, "ffq_pair: no memory for %lld unmerged pairs", m);
+            if (!rc) rc = stream_grow(p->merge.text, text_cap, "ffq_pair: no memory for %lld merged bytes", text_cap);
+        }
+        d_insert = p->merge.insert.p;
+    }
     if (!rc && p->overlap.on)
         rc = ffq_table_pair_overlap(c, &v[0], &v[1], m, &p->overlap.rules, const_cast<int64_t *>(v[0].d_table), const_cast<int64_t *>(v[1].d_table),
-                                    nullptr, p->overlap.hist.p, 1, p->overlap.last);
+                                    d_insert, p->overlap.hist.p, 1, p->overlap.last);
     int64_t kept = 0;
     if (!rc) rc = ffq_table_select_pairs(c, &v[0], &v[1], m, bounds, rules[0], rules[1], p->mode, p->m[0].s->b->sel, p->m[1].s->b->sel,
                                          p->idx.d, &kept, p->m[0].s->content.last, p->m[1].s->content.last, p->last_pairs);
+    if (!rc && p->merge.on) return pair_chain_merge(p, kept, n_out);
     for (int k = 0; k < 2 && !rc; k++) rc = chain_back(p->m[k].s, p->m[k].f, Table{p->m[k].s->b->sel, kept});
     if (rc) return rc;
     if (kept > 0) HIPCHK(hipMemcpyAsync(p->idx.h, p->idx.d, (size_t)kept * 8, hipMemcpyDeviceToHost, c->stream));
@@ -1157,6 +1225,7 @@ extern "C" int ffq_pair_next(ffq_pair *p, int64_t *n_pairs_in, int64_t *n_pairs_
     if (p->failed) return fail(FFQ_E_ARG, "ffq_pair_next: the pair has failed");
     for (int i = 0; i < 5; i++) p->last_pairs[i] = 0;
     for (int i = 0; i < FFQ_OVERLAP_COUNTS; i++) p->overlap.last[i] = 0;
+    for (int i = 0; i < FFQ_MERGE_COUNTS; i++) p->merge.last[i] = 0;
     p->last_out = 0;
     p->started = true;
     for (int k = 0; k < 2; k++) pair_clear_last(p->m[k].s);
@@ -1237,7 +1306,7 @@ extern "C" int ffq_pair_rows(ffq_pair *p, int mate, const int64_t **h_rows, cons
 extern "C" int ffq_pair_selected(ffq_pair *p, const int64_t **h_index, int64_t pairs[5])
 {
     if (!p || !h_index) return fail(FFQ_E_ARG, "ffq_pair_selected: NULL argument");
-    *h_index = p->idx.h;
+    *h_index = p->merge.on ? p->merge.ord.h : p->idx.h;
     if (pairs) for (int i = 0; i < 5; i++) pairs[i] = p->last_pairs[i];
     return FFQ_OK;
 }

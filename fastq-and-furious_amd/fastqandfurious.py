@@ -1230,6 +1230,63 @@ class OverlapReport:
         return int(np.argmax(self.insert_hist)) if self.insert_hist.any() else None
 
 
+_COMPLEMENT = np.arange(256, dtype=np.uint8)
+for _x, _y in (b"AT", b"CG", b"at", b"cg"):
+    _COMPLEMENT[_x], _COMPLEMENT[_y] = _y, _x
+
+
+def merge_mates(seq1, qual1, seq2, qual2, insert):
+    """The two mates of a pair merged into one read, or None if `insert` does not allow it (include/ffq.h states the rule at
+    ffq_table_pair_merge; this is its host statement).  seq / qual: bytes of the four lines as they stand, behind any trim;
+    insert: pair_overlap's.  With o = insert - len(seq2), position p of the merged read faces a[p] (p < n1) and byte
+    bi = n2 - 1 - (p - o) of mate 2 (0 <= p - o < n2), read backwards and complemented; where both are there, mate 2's base and
+    quality are taken if its quality byte is the higher one (unsigned; a tie goes to mate 1).  L = n2 + o for o < 0 (what lies
+    beyond is adapter), else max(n1, n2 + o).  Returns (bases, quals), bytes of length L.  None: insert None or negative, a
+    line pair of two lengths, a mate above OverlapRules.MAX_LEN, or not -n2 < o < n1."""
+    n1, n2 = len(seq1), len(seq2)
+    if insert is None or insert < 0 or len(qual1) != n1 or len(qual2) != n2 or n1 > OverlapRules.MAX_LEN or n2 > OverlapRules.MAX_LEN:
+        return None
+    o = int(insert) - n2
+    if not -n2 < o < n1:
+        return None
+    L = n2 + o if o < 0 else max(n1, n2 + o)
+    p = np.arange(L)
+    in_a, in_b = p < n1, (p >= o) & (p < o + n2)
+    a, qa, b, qb = (np.zeros(L, dtype=np.uint8) for _ in range(4))
+    k = min(n1, L)
+    a[:k] = np.frombuffer(seq1, dtype=np.uint8)[:k]
+    qa[:k] = np.frombuffer(qual1, dtype=np.uint8)[:k]
+    lo, hi = max(0, o), min(L, o + n2)
+    b[lo:hi] = _COMPLEMENT[np.frombuffer(seq2, dtype=np.uint8)][::-1][lo - o:hi - o]
+    qb[lo:hi] = np.frombuffer(qual2, dtype=np.uint8)[::-1][lo - o:hi - o]
+    take_b = np.where(in_a & in_b, qb > qa, ~in_a)
+    return np.where(take_b, b, a).tobytes(), np.where(take_b, qb, qa).tobytes()
+
+
+def merge_mergeable(buf1, pos1, buf2, pos2, insert):
+    """Does the device merge this pair (ffq_table_pair_merge's eligibility)?  Both rows' pos2..pos5 inside their buffers and in
+    order with sequence and quality of one length, mate 1's header slice buf1[pos0 + 1:pos1] inside its buffer, neither mate
+    above OverlapRules.MAX_LEN bases, insert >= 0 and -n2 < insert - n2 < n1.  Newlines are not looked for."""
+    for buf, pos in ((buf1, pos1), (buf2, pos2)):
+        p2, p3, p4, p5 = pos[2], pos[3], pos[4], pos[5]
+        if not (p2 >= 0 and p4 >= 0 and p2 <= p3 <= len(buf) and p4 <= p5 <= len(buf) and p3 - p2 == p5 - p4
+                and p3 - p2 <= OverlapRules.MAX_LEN):
+            return False
+    if not (pos1[0] >= 0 and pos1[0] + 1 <= pos1[1] <= len(buf1)):
+        return False
+    n1, n2 = pos1[3] - pos1[2], pos2[3] - pos2[2]
+    return insert is not None and insert >= 0 and -n2 < insert - n2 < n1
+
+
+class MergeReport:
+    """What filter_fastq_paired(merge_report=...) fills: pairs_merged, bases_merged (bases of the merged reads), bytes_merged
+    (bytes written to merged_out), overlap_positions (positions at which both mates had a base) and taken_from_mate2 (of
+    those, positions whose base and quality came from mate 2)."""
+
+    def __init__(self):
+        self.pairs_merged = self.bases_merged = self.bytes_merged = self.overlap_positions = self.taken_from_mate2 = 0
+
+
 PairedFilterResult = namedtuple('PairedFilterResult', 'pairs_in pairs_out bases_removed bytes_out1 bytes_out2 dropped')
 
 _PAIR_FILTERS = ("any", "both", "first")
@@ -1262,7 +1319,8 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
                         adapter=None, adapter2=None, err_permille: int = 100, min_overlap: int = 3, content=None,
                         pair_filter: str = "any", check_names: bool = True, report=None, report2=None,
                         entrypos: typing.Optional[typing.Callable] = None, overlap=None,
-                        overlap_report=None) -> PairedFilterResult:
+                        overlap_report=None, merged_out: typing.Optional[typing.BinaryIO] = None,
+                        merge_report=None) -> PairedFilterResult:
     """filter_fastq for paired-end files: the i-th records of `fh1` and `fh2` are mates, and a pair is written or dropped
     TOGETHER, so that `fh_out1` and `fh_out2` stay record for record in step (`cutadapt -q 20 -a ... -A ... -m 30:20
     --pair-filter=any -o out1 -p out2 in1 in2`).  Every record is trimmed as filter_fastq trims it -- quality_cutoff for both
@@ -1298,7 +1356,13 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
     includes what the overlap cut.  Pairs the rule does not apply to (overlap_analysable: wrapped records, mates above 512
     bases) are left as they are.  overlap_report: an OverlapReport, filled on either route with the same numbers (its
     insert_peak: the library's insert size).  None: nothing of this is done.
-    Not done: interleaved input or output, merging of overlapping mates, base correction inside the overlap."""
+
+    merged_out: a writable binary file (needs `overlap`); the order is then quality, adapter, overlap, filter, merge: a pair
+    the filter keeps and whose insert size lets the mates be merged (merge_mergeable, merge_mates: `fastp --merge`) is written
+    ONCE, to merged_out, as one read under mate 1's header, and to neither fh_out1 nor fh_out2.  pairs_out still counts every
+    pair the filter kept; bytes_out1 / bytes_out2 and report.after / report2.after count what went to those two files.
+    merge_report: a MergeReport (needs merged_out), filled on either route with the same numbers.
+    Not done: interleaved input or output, base correction inside the overlap of mates that are not merged."""
     if content is not None and not isinstance(content, ContentRules):
         raise TypeError("content must be a ContentRules")
     if pair_filter not in _PAIR_FILTERS:
@@ -1307,6 +1371,14 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
         raise TypeError("overlap must be an OverlapRules")
     if overlap_report is not None and overlap is None:
         raise ValueError("overlap_report needs overlap")
+    if merged_out is not None and overlap is None:
+        raise ValueError("merged_out needs overlap")
+    if merge_report is not None and merged_out is None:
+        raise ValueError("merge_report needs merged_out")
+    mrep = MergeReport()
+    if merge_report is not None:
+        merge_report.__dict__.update(mrep.__dict__)
+        mrep = merge_report
     orep = OverlapReport() if overlap is not None else None
     if overlap_report is not None:
         overlap_report.__dict__.update(orep.__dict__)
@@ -1342,9 +1414,22 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
             ps = _hip.PairStream(sts[0], sts[1], pair_filter, check_names)
             if overlap is not None:
                 ps.set_overlap(overlap)
+            if merged_out is not None:
+                ps.set_merge()
             for n_in, n_out, end_state, err_mate, err_offset in ps:
                 pairs_in += n_in
-                pairs_out += n_out
+                if merged_out is not None:           # (n_out: the kept pairs that were not merged)
+                    text, mc = ps.merged()
+                    if mc[2]:
+                        merged_out.write(memoryview(text))
+                    pairs_out += n_out + mc[0]
+                    mrep.pairs_merged += mc[0]
+                    mrep.bytes_merged += mc[2]
+                    mrep.bases_merged += mc[3]
+                    mrep.overlap_positions += mc[4]
+                    mrep.taken_from_mate2 += mc[5]
+                else:
+                    pairs_out += n_out
                 if overlap is not None:
                     oc = ps.overlap(hist=False)[0]
                     orep.pairs_analysed += oc[0]
@@ -1388,19 +1473,19 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
         return record
 
     def overlap_cut(r1, r2):
-        """the two records with the overlap's cut applied, and the report filled"""
+        """the two records with the overlap's cut applied and the pair's insert size (None: none), and the report filled"""
         (buf1, pos1), (buf2, pos2) = r1[3:], r2[3:]
         if not overlap_analysable(buf1, pos1, buf2, pos2):
-            return r1, r2
+            return r1, r2, None
         orep.pairs_analysed += 1
         n1, n2 = pos1[3] - pos1[2], pos2[3] - pos2[2]
         insert = pair_overlap(buf1[pos1[2]:pos1[3]], buf2[pos2[2]:pos2[3]], overlap)
         if insert is None:
-            return r1, r2
+            return r1, r2, None
         orep.pairs_overlapped += 1
         orep.insert_hist[insert] += 1
         if insert >= n2:                                # (o >= 0: the fragment is not shorter than mate 2)
-            return r1, r2
+            return r1, r2, insert
         out = []
         for k, (r, n) in enumerate(((r1, n1), (r2, n2))):
             c = min(n, insert)
@@ -1408,7 +1493,27 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
             orep.bases_removed[k] += n - c
             out.append(r[:2] + (r[2] + n - c, r[3], (pos[0], pos[1], pos[2], pos[2] + c, pos[4], pos[4] + c)))
         orep.pairs_trimmed += 1
-        return tuple(out)
+        return out[0], out[1], insert
+
+    def merged_text(r1, r2, insert):
+        """the pair as one record (None: it is not merged), and the report filled; behind the cut, with the insert size found
+        in front of it: the rule takes o against the current length of mate 2, the text is the same either way"""
+        (buf1, pos1), (buf2, pos2) = r1[3:], r2[3:]
+        if not merge_mergeable(buf1, pos1, buf2, pos2, insert):
+            return None
+        bases, quals = merge_mates(buf1[pos1[2]:pos1[3]], buf1[pos1[4]:pos1[5]], buf2[pos2[2]:pos2[3]], buf2[pos2[4]:pos2[5]], insert)
+        n1, n2 = pos1[3] - pos1[2], pos2[3] - pos2[2]
+        o = insert - n2
+        lo, hi = max(0, o), min(n1, n2 + o)
+        text = b"".join((b"@", buf1[(pos1[0] + 1):pos1[1]], b"\n", bases, b"\n+\n", quals, b"\n"))
+        mrep.pairs_merged += 1
+        mrep.bases_merged += len(bases)
+        mrep.bytes_merged += len(text)
+        mrep.overlap_positions += hi - lo
+        qa = np.frombuffer(buf1[pos1[4]:pos1[5]], dtype=np.uint8)[lo:hi]
+        qb = np.frombuffer(buf2[pos2[4]:pos2[5]], dtype=np.uint8)[::-1][lo - o:hi - o]
+        mrep.taken_from_mate2 += int(np.count_nonzero(qb > qa))
+        return text
 
     its = [iter(readfastq_iter(fh, fbufsize, recorder(plan), entrypos)) for plan, fh in zip(plans, (fh1, fh2))]
 
@@ -1434,14 +1539,20 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
         if check_names and r1[1] != r2[1]:
             _raise_for_pair_end(_hip.END_ERR_PAIR_NAMES, 0, pairs_in, (r1[1], r2[1]))
         pairs_in += 1
+        insert = None
         if overlap is not None:
-            r1, r2 = overlap_cut(r1, r2)
+            r1, r2, insert = overlap_cut(r1, r2)
         v1, v2 = plans[0].verdict(r1[3], r1[4]), plans[1].verdict(r2[3], r2[4])
         removed += r1[2] + r2[2]
         if _pair_dropped(pair_filter, v1, v2):
             dropped["both" if (v1 and v2) else "mate1_only" if v1 else "mate2_only"] += 1
             continue
         pairs_out += 1
+        if merged_out is not None:
+            text = merged_text(r1, r2, insert)
+            if text is not None:
+                merged_out.write(text)
+                continue
         for k, r in enumerate((r1, r2)):
             text = plans[k].text(r[3], r[4])
             outs[k].write(text)

@@ -103,6 +103,7 @@ SYMBOLS = (
     "ffq_table_select_pairs", "ffq_table_pair_names",
     "ffq_pair_open", "ffq_pair_wants", "ffq_pair_next", "ffq_pair_rows", "ffq_pair_selected", "ffq_pair_close",
     "ffq_table_pair_overlap", "ffq_pair_set_overlap", "ffq_pair_overlap",
+    "ffq_table_pair_merge", "ffq_pair_set_merge", "ffq_pair_merged",
 )
 
 
@@ -143,6 +144,7 @@ def table_view(d_buf, n_bytes, d_table, sentinel=True, add=None):
 OVERLAP_MAX_LEN = 512                            # FFQ_OVERLAP_MAX_LEN: mates above it are not analysed
 OVERLAP_HIST_WORDS = 2 * OVERLAP_MAX_LEN + 1     # insert sizes 0..1024
 OVERLAP_COUNTS = 6           # pairs analysed, with an overlap, changed, bases removed from mate 1, from mate 2, pairs not analysed
+MERGE_COUNTS = 6             # FFQ_MERGE_COUNTS: pairs merged, not merged, bytes of text, bases of the merged reads, positions inside overlaps, of those taken from mate 2
 
 
 class OverlapRulesStruct(ctypes.Structure):
@@ -411,6 +413,9 @@ def lib():
         L.ffq_table_pair_overlap.argtypes = [vp, P(TableView), P(TableView), i64, P(OverlapRulesStruct), vp, vp, vp, vp, i32, P(i64)]
         L.ffq_pair_set_overlap.argtypes = [vp, P(OverlapRulesStruct)]
         L.ffq_pair_overlap.argtypes = [vp, P(i64), vp, i64]
+        L.ffq_table_pair_merge.argtypes = [vp, P(TableView), P(TableView), i64, vp, vp, vp, i64, vp, vp, vp, vp, P(i64), P(i64)]
+        L.ffq_pair_set_merge.argtypes = [vp, i32]
+        L.ffq_pair_merged.argtypes = [vp, P(vp), P(i64), P(i64)]
         L.ffq_pair_close.restype = None
         L.ffq_stream_set_content.argtypes = [vp, P(ContentRulesStruct)]
         L.ffq_stream_filter_counts.argtypes = [vp, P(i64)]
@@ -797,6 +802,27 @@ class Context:
                                            ctypes.c_void_p(d_insert) if d_insert else None, ctypes.c_void_p(d_hist) if d_hist else None,
                                            1 if accumulate else 0, counts))
         return [int(x) for x in counts]
+
+    def table_pair_merge(self, mate1, mate2, n_pairs, d_insert, d_text, text_cap, d_rest1, d_rest2, d_ord=None, d_off=None,
+                         d_rest_ord=None):
+        """The mates of every pair of two device tables merged into one read where their insert size allows it, rendered as
+        FASTQ text (ffq_table_pair_merge; include/ffq.h states the rule, fastqandfurious.merge_mates is its host statement).
+        mate1 / mate2: TableViews; d_insert: int32 insert sizes (table_pair_overlap's), pair k's at d_insert[d_ord[k]] (d_ord
+        None: at d_insert[k]); d_text: text_cap bytes; d_off: n_pairs + 1 offsets or None; d_rest1 / d_rest2: n_pairs rows of
+        room each for the pairs that are not merged, not the input tables; d_rest_ord: their ordinals or None.  Raw device
+        pointers.  Returns (rc, pairs not merged, counts): rc is OK or E_TABLE_FULL (text_cap too small: counts[2] is the need,
+        d_text is not touched); counts = [pairs merged, not merged, bytes of text, bases of the merged reads, positions inside
+        overlaps, of those taken from mate 2]."""
+        n_rest = ctypes.c_int64(0)
+        counts = (ctypes.c_int64 * MERGE_COUNTS)()
+        rc = lib().ffq_table_pair_merge(self.handle, ctypes.byref(mate1), ctypes.byref(mate2), int(n_pairs),
+                                        ctypes.c_void_p(d_insert) if d_insert else None, ctypes.c_void_p(d_ord) if d_ord else None,
+                                        ctypes.c_void_p(d_text) if d_text else None, int(text_cap),
+                                        ctypes.c_void_p(d_off) if d_off else None, ctypes.c_void_p(d_rest1) if d_rest1 else None,
+                                        ctypes.c_void_p(d_rest2) if d_rest2 else None,
+                                        ctypes.c_void_p(d_rest_ord) if d_rest_ord else None, ctypes.byref(n_rest), counts)
+        check(rc, allow=(E_TABLE_FULL,))
+        return rc, n_rest.value, [int(x) for x in counts]
 
     COLUMNS = {"header": (0, 1, 1), "sequence": (2, 0, 3), "quality": (4, 0, 5)}
 
@@ -1335,7 +1361,7 @@ class PushStream(_Stream):
 class PairStream:
     """Two streams whose i-th records are mates, walked in lockstep (ffq_pair; include/ffq.h): mate1 / mate2 are fresh
     FileStreams or PushStreams of one context, configured beforehand (set_trim, set_adapter, set_filter without a column,
-    set_content, set_stats, set_render); set_overlap() here, before the first step.  Iterating yields (n_in, n_out,
+    set_content, set_stats, set_render); set_overlap() and set_merge() here, before the first step.  Iterating yields (n_in, n_out,
     end_state, err_mate, err_offset) per ROUND; after each step the streams' own accessors (rendered(), trimmed(), adapter_trimmed(), filter_counts(), stats()) report that
     mate's share of the round.  PushStream mates are pumped here whenever the walk takes a new chunk of theirs.  The
     iteration ends behind the first end_state that is not END_REFILL (END_OK, a mate's END_ERR_*, END_ERR_PAIR_COUNT,
@@ -1419,6 +1445,23 @@ class PairStream:
         h = np.zeros(OVERLAP_HIST_WORDS, dtype=np.uint64) if hist else None
         check(lib().ffq_pair_overlap(self._h, counts, ctypes.c_void_p(h.ctypes.data) if hist else None, OVERLAP_HIST_WORDS))
         return [int(x) for x in counts], h
+
+    def set_merge(self, on=True):
+        """Behind the filter every round merges the kept pairs whose insert size allows it (ffq_pair_set_merge; needs
+        set_overlap).  Those pairs leave the two ordinary outputs: rows(), selected()'s index and the mates' rendered() are
+        then the kept pairs that were not merged, n_out their number; merged() has the others.  Before the first step only."""
+        check(lib().ffq_pair_set_merge(self._h, 1 if on else 0))
+
+    def merged(self):
+        """(text uint8[], counts) of the round just yielded: the FASTQ text of the merged pairs (a view, valid until the next
+        step) and the six counts of Context.table_pair_merge."""
+        tp = ctypes.c_void_p()
+        nb = ctypes.c_int64()
+        counts = (ctypes.c_int64 * MERGE_COUNTS)()
+        check(lib().ffq_pair_merged(self._h, ctypes.byref(tp), ctypes.byref(nb), counts))
+        text = (np.ctypeslib.as_array((ctypes.c_uint8 * nb.value).from_address(tp.value))
+                if nb.value and tp.value else np.zeros(0, dtype=np.uint8))
+        return text, [int(x) for x in counts]
 
     def close(self):
         if self._h:

@@ -450,7 +450,7 @@ typedef struct ffq_table_view { const uint8_t *d_buf; int64_t n_bytes; int32_t s
  * [2] = number of pairs with v1 != 0, [3] = [4] = 0.
  * n_pairs == 0 is valid.  One host wait.  FFQ_E_ARG: a pair_filter that is none of the three, a field of either rules out
  * of range, a scan pending on the context, d_buf NULL with n_bytes > 0 for a judged mate whose content rules are on.
- * Not done: interleaved input or output, merging of overlapping mates.                                                 */
+ * Merging the kept pairs' mates: ffq_table_pair_merge.  Not done: interleaved input or output.                         */
 int ffq_table_select_pairs(ffq_ctx *ctx, const ffq_table_view *m1, const ffq_table_view *m2, int64_t n_pairs,
                            const int64_t len_bounds[4] /* min1, max1, min2, max2 */,
                            const ffq_content_rules *rules1, const ffq_content_rules *rules2, int pair_filter,
@@ -507,8 +507,8 @@ int ffq_table_pair_names(ffq_ctx *ctx, const ffq_table_view *m1, const ffq_table
  * one row changed, [3] bases removed from mate 1, [4] from mate 2, [5] pairs not analysed; [0] + [5] == n_pairs.
  * n_pairs == 0 is valid.  One host wait.  FFQ_E_ARG: a field out of range, rules NULL, a scan pending on the context, a
  * misaligned table, d_insert or d_hist, d_buf NULL with n_bytes > 0.  Run it behind the per-mate trims and in front of
- * ffq_table_select_pairs.  Not done: merging of overlapping mates, base correction inside the overlap, indels, reads above
- * FFQ_OVERLAP_MAX_LEN bases.                                                                                          */
+ * ffq_table_select_pairs.  Merging the mates by `insert`: ffq_table_pair_merge below.  Not done: base correction inside the
+ * overlap of mates that are not merged, indels, reads above FFQ_OVERLAP_MAX_LEN bases.                                */
 typedef struct ffq_overlap_rules {
     int32_t min_overlap;     /* 1..FFQ_OVERLAP_MAX_LEN; fastp's default 30 */
     int32_t max_diff;        /* 0..FFQ_OVERLAP_MAX_LEN; fastp's default 5  */
@@ -546,6 +546,44 @@ int ffq_table_pair_overlap(ffq_ctx *ctx, const ffq_table_view *m1, const ffq_tab
 int ffq_table_render_fastq(ffq_ctx *ctx, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
                            const int64_t *d_table, int64_t n_rows, uint8_t *d_out, int64_t out_cap, int64_t *d_off,
                            int64_t stats[3]);
+
+/* The two mates of a pair merged into ONE read and rendered as FASTQ text (`fastp --merge`, PEAR, FLASH, NGmerge): mate 2
+ * is read backwards and complemented, and inside the overlap the base and the quality come from whichever mate is surer.
+ * For input pair k, with j = d_ord ? d_ord[k] : k, ins = d_insert[j], a / qa = mate 1's sequence and quality (n1 bytes),
+ * b / qb = mate 2's (n2 bytes) -- all four as the rows stand NOW, behind any trim -- and o = ins - n2, the pair is MERGEABLE
+ * if both rows are eligible as ffq_table_stats asks (pos2..pos5 - add inside the buffer and in order, the two lines of one
+ * length, no line with bytes in it at the sentinel's coordinate 0), mate 1's header slice is renderable as
+ * ffq_table_render_fastq asks (p0 >= 0, p0 + 1 <= p1, inside the buffer), n1 and n2 <= FFQ_OVERLAP_MAX_LEN, ins >= 0 and
+ * -n2 < o < n1 (the overlap min(n1, n2 + o) - max(0, o) has at least one position).  Then
+ *     L = o < 0 ? n2 + o : max(n1, n2 + o)
+ *     for p in [0, L):
+ *         inA = p < n1;  j2 = p - o;  inB = 0 <= j2 < n2;  bi = n2 - 1 - j2        (at least one of inA, inB holds)
+ *         takeB = inA && inB ? qb[bi] > qa[p] : !inA        (bytes compared unsigned; on a tie mate 1 wins)
+ *         base[p] = takeB ? comp(b[bi]) : a[p];   qual[p] = takeB ? qb[bi] : qa[p]
+ *     comp: A<->T, C<->G, a<->t, c<->g; every other byte unchanged
+ *     text = "@" + buf1[p0 + 1 : p1] + "\n" + base + "\n+\n" + qual + "\n"
+ * For o < 0, a[L:] and the first -o bases of the reverse complement are adapter and are left out.  o is taken against the
+ * CURRENT n2, so the text is the same whether ffq_table_pair_overlap ran with trim 1 or 0: behind the cut n2' = ins,
+ * o' = 0, and bi names the same byte.  Every other pair -- ins of -1 or -2, an ins that does not fit these rows, FASTA rows,
+ * rows written by hand, long reads, wrapped records whose lengths differ -- is not merged: both its rows go to the rest
+ * tables unchanged, in order.  Positions and ranges are checked again here: no byte outside either buffer is read whatever
+ * d_insert holds.  "\n" is not looked for inside the lines: bytes are taken as they are, as the render does.
+ * THREE DIFFERENCES from fastp: the higher quality always wins and keeps its quality (fastp keeps mate 1's base unless its
+ * correction rule fires); the header is mate 1's, verbatim (no merged_x_y comment); no insertions or deletions.
+ * d_insert: DEVICE memory, int32 (ffq_table_pair_overlap's); d_ord (NULL: the identity): DEVICE memory, where pair k's
+ * insert size is (ffq_table_select_pairs' d_idx); d_text: text_cap bytes, no alignment asked; d_off (NULL: none):
+ * n_pairs + 1 offsets, a pair that is not merged has zero bytes; d_rest1 / d_rest2: room for n_pairs rows each, 16-byte
+ * aligned, NOT the input tables; d_rest_ord (NULL: none): j of every pair that is not merged; *n_rest: their number.
+ * counts: [0] pairs merged, [1] pairs not merged, [2] bytes of text, [3] bases of the merged reads, [4] positions inside
+ * overlaps, [5] of those, positions taken from mate 2; [0] + [1] == n_pairs.  FFQ_E_TABLE_FULL: text_cap is smaller than
+ * the total -- counts[2] holds the need, d_off and the rest tables are written, d_text is not touched.  FFQ_E_ARG: d_insert
+ * NULL, a misaligned table or array, a scan pending on the context, d_buf NULL with n_bytes > 0.  n_pairs == 0 is valid.
+ * One host wait.  Not done: base correction of mates that are not merged.                                              */
+#define FFQ_MERGE_COUNTS 6
+int ffq_table_pair_merge(ffq_ctx *ctx, const ffq_table_view *m1, const ffq_table_view *m2, int64_t n_pairs,
+                         const int32_t *d_insert, const int64_t *d_ord, uint8_t *d_text, int64_t text_cap, int64_t *d_off,
+                         int64_t *d_rest1, int64_t *d_rest2, int64_t *d_rest_ord, int64_t *n_rest,
+                         int64_t counts[FFQ_MERGE_COUNTS]);
 
 /* ---- FASTA (reference: the plug-in scanner entrypos_fasta, fastqandfurious.py:103-143) -------
  * Every COMPLETE entry of a buffer, i.e. the repeated scanner call with offset := pos[3]:
@@ -758,10 +796,17 @@ int  ffq_stream_push(ffq_stream *s, int64_t n, int eof);
  * After any state but FFQ_END_REFILL the pair is done.  ffq_pair_close does not close the two streams.
  * ffq_pair_set_overlap: every round analyses, and with rules->trim cuts by, the overlap of the mates behind the per-mate
  * trims and in front of the filter; before the first ffq_pair_next only (FFQ_E_ARG afterwards, and for a field out of
- * range); NULL switches it off.  ffq_pair_overlap: counts = the six counts of the last round; h_hist (HOST memory, NULL: not
+ * range); NULL switches it off, and ffq_pair_set_merge's merging with it.  ffq_pair_overlap: counts = the six counts of the last round; h_hist (HOST memory, NULL: not
  * wanted; cap_words >= FFQ_OVERLAP_HIST_WORDS): the insert sizes of every round so far, as ffq_stream_stats reports its
  * totals; one host wait.  FFQ_E_ARG without ffq_pair_set_overlap.
- * Not done: interleaved input or output, merging of overlapping mates, paired readfastq_iter_range.                   */
+ * ffq_pair_set_merge (on != 0; before the first ffq_pair_next only; FFQ_E_ARG without ffq_pair_set_overlap): behind
+ * ffq_table_select_pairs every round merges the kept pairs the rule of ffq_table_pair_merge can merge, with the insert sizes
+ * the round's overlap pass found.  Those pairs leave the two ordinary outputs: what ffq_pair_rows, ffq_pair_selected's
+ * h_index, the per-mate renders and statistics OUT hand out are then the kept pairs that were NOT merged, *n_pairs_out their
+ * number; pairs[0] of ffq_pair_selected still counts every pair the filter kept.  ffq_pair_merged: the round's merged text
+ * (pinned memory, valid until the next ffq_pair_next; *n_bytes == counts[2]) and the six counts of ffq_table_pair_merge;
+ * counts may be NULL.  FFQ_E_ARG without ffq_pair_set_merge.
+ * Not done: interleaved input or output, base correction of mates that are not merged, paired readfastq_iter_range.   */
 typedef struct ffq_pair ffq_pair;
 int  ffq_pair_open(ffq_stream *mate1, ffq_stream *mate2, int pair_filter, int check_names, ffq_pair **out);
 int  ffq_pair_wants(ffq_pair *p);
@@ -770,6 +815,8 @@ int  ffq_pair_rows(ffq_pair *p, int mate, const int64_t **h_rows, const uint8_t 
 int  ffq_pair_selected(ffq_pair *p, const int64_t **h_index, int64_t pairs[5]);
 int  ffq_pair_set_overlap(ffq_pair *p, const ffq_overlap_rules *rules);
 int  ffq_pair_overlap(ffq_pair *p, int64_t counts[FFQ_OVERLAP_COUNTS], uint64_t *h_hist, int64_t cap_words);
+int  ffq_pair_set_merge(ffq_pair *p, int on);
+int  ffq_pair_merged(ffq_pair *p, const uint8_t **h_text, int64_t *n_bytes, int64_t counts[FFQ_MERGE_COUNTS]);
 void ffq_pair_close(ffq_pair *p);
 
 /* Bytes [pos, pos + n_bytes) of the file behind fd into device memory (read(), fastqandfurious.py:30-36, for a range
