@@ -17,6 +17,7 @@
 #include "ffq_overlap.h"
 #include "ffq_render.h"
 #include "ffq_merge.h"
+#include "ffq_dedup.h"
 #include "ffq_pool.h"
 #include "ffq_mem.h"
 
@@ -2479,6 +2480,179 @@ extern "C" int ffq_table_pair_merge(ffq_ctx *c, const ffq_table_view *m1, const 
     *n_rest = counts[1];
     if (counts[2] > text_cap)
         return fail(FFQ_E_TABLE_FULL, "text holds %lld bytes, the merged reads have %lld", (long long)text_cap, (long long)counts[2]);
+    return FFQ_OK;
+}
+
+// ---- duplicate reads and pairs (csrc/ffq_dedup.h) -----------------------------------------------
+static_assert(DEDUP_KEY_NONE == FFQ_KEY_NONE && DEDUP_COUNTS == FFQ_DEDUP_COUNTS, "include/ffq.h");
+
+constexpr int SEQKEY_GRID_SHORT = 2048, SEQKEY_GRID_LONG = 1024, DEDUP_GRID_TABLE = 4096, DEDUP_GRID_ROWS = 2048;
+
+extern "C" uint64_t ffq_seq_key_host(const uint8_t *seq, int64_t n) { return (seq || n <= 0) ? dedup_seq_key(seq, n < 0 ? 0 : n) : FFQ_KEY_NONE; }
+extern "C" uint64_t ffq_pair_key_host(uint64_t k1, uint64_t k2) { return dedup_pair_key(k1, k2); }
+
+extern "C" int ffq_table_seq_keys(ffq_ctx *c, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
+                                  const int64_t *d_table, int64_t n_rows, uint64_t *d_keys, int64_t counts[2])
+{
+    static const char *const who = "ffq_table_seq_keys";
+    mark_other(c);
+    if (!c || !counts || n_rows < 0 || n_bytes < 0 || (n_bytes > 0 && !d_buf) || (n_rows > 0 && (!d_table || !d_keys)))
+        return fail(FFQ_E_ARG, "%s: bad argument", who);
+    if ((reinterpret_cast<uintptr_t>(d_table) & 15) != 0 || (reinterpret_cast<uintptr_t>(d_keys) & 7) != 0)
+        return fail(FFQ_E_ARG, "%s: the table must be 16-byte aligned, the keys 8-byte aligned", who);
+    if (c->pend.active) return fail(FFQ_E_ARG, "%s: a scan is pending on this context", who);
+    HIPCHK(hipSetDevice(c->device));
+    counts[0] = counts[1] = 0;
+    if (n_rows == 0) return FFQ_OK;
+    const int rc = grow_dev(c, c->rows_list, n_rows);      // (before anything is enqueued: growing waits for the stream)
+    if (rc) return rc;
+    hipStream_t st = c->stream;
+    const int s = sentinel ? 1 : 0;
+    unsigned long long *keys = reinterpret_cast<unsigned long long *>(d_keys);
+    HIPCHK(hipMemsetAsync(c->d_rows, 0, sizeof(RowsBlock), st));
+    hipLaunchKernelGGL(k_seqkey_rows, dim3(rows_grid(n_rows, SEQKEY_WG / SEQKEY_G, SEQKEY_GRID_SHORT)), dim3(SEQKEY_WG), 0, st, d_buf,
+                       n_bytes, s, add, d_table, n_rows, keys, c->rows_list.p, c->d_rows.p);
+    hipLaunchKernelGGL(k_seqkey_long, dim3(rows_grid(n_rows, SEQKEY_WG / 64, SEQKEY_GRID_LONG)), dim3(SEQKEY_WG), 0, st, d_buf,
+                       n_bytes, s, add, d_table, keys, (const int64_t *)c->rows_list, c->d_rows.p);
+    int64_t stats[3];
+    const int rc2 = rows_end(c, stats);
+    if (rc2) return rc2;
+    counts[0] = stats[0]; counts[1] = stats[2];
+    return FFQ_OK;
+}
+
+// The set: the table in use (tab[cur]) and the one it grew out of, which the next growth reuses -- the old and the new table
+// are alive together while one is rehashed into the other.  The host knows, without asking the device, how many keys the
+// table holds (`distinct`, from the last call's one wait) and how many rows were ever submitted (the next global ordinal).
+struct ffq_dedup {
+    ffq_ctx *c = nullptr;
+    DevBuf<DedupSlot> tab[2];
+    int cur = 0;
+    int64_t slots = 0, distinct = 0, submitted = 0, rehashes = 0, max_bytes = 0;
+    DevBuf<DedupBlock> d_blk;
+    PinBuf<DedupBlock> h_blk;
+};
+
+static unsigned dedup_table_grid(int64_t slots) { return (unsigned)std::min<int64_t>((slots + 255) / 256, DEDUP_GRID_TABLE); }
+
+extern "C" void ffq_dedup_destroy(ffq_dedup *d)
+{
+    if (!d) return;
+    if (d->c && d->c->stream && hipSetDevice(d->c->device) == hipSuccess) (void)hipStreamSynchronize(d->c->stream);
+    delete d;                    // (the buffers free themselves)
+}
+
+extern "C" int ffq_dedup_create(ffq_ctx *c, int64_t expected_keys, int64_t max_bytes, ffq_dedup **out)
+{
+    static const char *const who = "ffq_dedup_create";
+    mark_other(c);
+    if (!c || !out || expected_keys < 0 || max_bytes < 0 || expected_keys > ((int64_t)1 << 56))
+        return fail(FFQ_E_ARG, "%s: bad argument", who);
+    *out = nullptr;
+    HIPCHK(hipSetDevice(c->device));
+    const int64_t slots = dedup_slots_for(0, expected_keys, 0);
+    if (max_bytes > 0 && slots * (int64_t)sizeof(DedupSlot) > max_bytes)
+        return fail(FFQ_E_NOMEM, "%s: a set for %lld keys needs %lld bytes (%lld slots), max_bytes is %lld", who, (long long)expected_keys,
+                    (long long)(slots * (int64_t)sizeof(DedupSlot)), (long long)slots, (long long)max_bytes);
+    ffq_dedup *d = new (std::nothrow) ffq_dedup();
+    if (!d) return fail(FFQ_E_NOMEM, "out of host memory");
+    d->c = c; d->max_bytes = max_bytes;
+    hipError_t e = d->tab[0].grow(slots);
+    if (e == hipSuccess) e = d->d_blk.grow(1);
+    if (e == hipSuccess) e = d->h_blk.grow(1);
+    if (e != hipSuccess) {
+        delete d;
+        return fail(FFQ_E_NOMEM, "%s: no memory for %lld slots: %s", who, (long long)slots, hipGetErrorString(e));
+    }
+    d->slots = slots;
+    hipLaunchKernelGGL(k_dedup_clear, dim3(dedup_table_grid(slots)), dim3(256), 0, c->stream, d->tab[0].p, slots);
+    const hipError_t e2 = hipGetLastError();
+    if (e2 != hipSuccess) {
+        ffq_dedup_destroy(d);
+        return fail(FFQ_E_HIP, "%s: %s", who, hipGetErrorString(e2));
+    }
+    *out = d;
+    return FFQ_OK;
+}
+
+extern "C" int ffq_dedup_select(ffq_dedup *d, const uint64_t *d_keys1, const uint64_t *d_keys2, const int64_t *d_ord, int64_t n,
+                                const int64_t *d_table1, const int64_t *d_table2, int64_t *d_out1, int64_t *d_out2, int64_t *d_idx,
+                                int64_t *n_out, int drop, int64_t counts[FFQ_DEDUP_COUNTS])
+{
+    static const char *const who = "ffq_dedup_select";
+    if (!d) return fail(FFQ_E_ARG, "%s: NULL set", who);
+    ffq_ctx *c = d->c;
+    mark_other(c);
+    if (!n_out || !counts || n < 0 || (n > 0 && !d_keys1)) return fail(FFQ_E_ARG, "%s: bad argument", who);
+    if (d_table2 && !d_keys2) return fail(FFQ_E_ARG, "%s: a second table without a second mate's keys", who);
+    if ((d_table1 && !d_out1) || (d_table2 && !d_out2)) return fail(FFQ_E_ARG, "%s: a table without a place for its kept rows", who);
+    if (((reinterpret_cast<uintptr_t>(d_table1) | reinterpret_cast<uintptr_t>(d_table2) | reinterpret_cast<uintptr_t>(d_out1) |
+          reinterpret_cast<uintptr_t>(d_out2)) & 15) != 0)
+        return fail(FFQ_E_ARG, "%s: tables must be 16-byte aligned", who);
+    if (((reinterpret_cast<uintptr_t>(d_keys1) | reinterpret_cast<uintptr_t>(d_keys2) | reinterpret_cast<uintptr_t>(d_ord) |
+          reinterpret_cast<uintptr_t>(d_idx)) & 7) != 0)
+        return fail(FFQ_E_ARG, "%s: keys and ordinals must be 8-byte aligned", who);
+    if (n > 0 && ((d_table1 && (d_out1 == d_table1 || d_out1 == d_table2)) || (d_table2 && (d_out2 == d_table2 || d_out2 == d_table1)) ||
+                  (d_out1 && d_out1 == d_out2)))
+        return fail(FFQ_E_ARG, "%s: d_out1 and d_out2 must not be one of the tables, or each other", who);
+    if (c->pend.active) return fail(FFQ_E_ARG, "%s: a scan is pending on this context", who);
+    HIPCHK(hipSetDevice(c->device));
+    *n_out = 0;
+    counts[0] = counts[1] = counts[2] = 0;
+    counts[3] = d->distinct; counts[4] = d->slots; counts[5] = d->rehashes;
+    if (n == 0) return FFQ_OK;
+    // growth, decided here: a call of n rows adds at most n keys
+    const int64_t want = dedup_slots_for(d->slots, d->distinct, n);
+    if (want != d->slots && d->max_bytes > 0 && want * (int64_t)sizeof(DedupSlot) > d->max_bytes)
+        return fail(FFQ_E_NOMEM, "%s: %lld keys and %lld more rows need %lld bytes (%lld slots), max_bytes is %lld", who,
+                    (long long)d->distinct, (long long)n, (long long)(want * (int64_t)sizeof(DedupSlot)), (long long)want,
+                    (long long)d->max_bytes);
+    const int64_t nblk = (n + 255) / 256;
+    // (everything is grown before anything is enqueued: growing waits for the stream)
+    int rc = grow_dev(c, c->filter_verdict, n);
+    if (!rc) rc = grow_dev(c, c->sel_cnt, nblk);
+    if (!rc) rc = grow_dev(c, c->sel_base, nblk);
+    if (rc) return rc;
+    hipStream_t st = c->stream;
+    HIPCHK(hipMemsetAsync(d->d_blk, 0, sizeof(DedupBlock), st));
+    if (want != d->slots) {
+        DevBuf<DedupSlot> &nu = d->tab[d->cur ^ 1];
+        CTX_SYNC(c);                                        // (the table before last goes away)
+        const hipError_t e = nu.grow(want);
+        if (e != hipSuccess)
+            return fail(FFQ_E_NOMEM, "%s: no memory for %lld slots: %s", who, (long long)want, hipGetErrorString(e));
+        hipLaunchKernelGGL(k_dedup_clear, dim3(dedup_table_grid(want)), dim3(256), 0, st, nu.p, want);
+        hipLaunchKernelGGL(k_dedup_rehash, dim3(dedup_table_grid(d->slots)), dim3(256), 0, st, (const DedupSlot *)d->tab[d->cur].p, d->slots,
+                           nu.p, want, d->d_blk.p);
+        d->cur ^= 1; d->slots = want; d->rehashes++;
+    }
+    DedupSlot *tab = d->tab[d->cur].p;
+    const unsigned long long *k1 = reinterpret_cast<const unsigned long long *>(d_keys1);
+    const unsigned long long *k2 = reinterpret_cast<const unsigned long long *>(d_keys2);
+    const unsigned long long g0 = (unsigned long long)d->submitted;
+    uint8_t *verdict = c->filter_verdict.p;
+    const unsigned rows_wgs = (unsigned)std::min<int64_t>(nblk, DEDUP_GRID_ROWS);
+    hipLaunchKernelGGL(k_dedup_insert, dim3(rows_wgs), dim3(DEDUP_WG), 0, st, tab, d->slots, k1, k2, d_ord, n, g0, d->d_blk.p);
+    hipLaunchKernelGGL(k_dedup_resolve, dim3(rows_wgs), dim3(DEDUP_WG), 0, st, tab, d->slots, k1, k2, d_ord, n, g0, drop ? 1 : 0, verdict,
+                       d->d_blk.p);
+    if (d_table1 || d_table2 || d_idx) {
+        hipLaunchKernelGGL(k_filter_count, dim3((unsigned)nblk), dim3(256), 0, st, (const uint8_t *)verdict, n, c->sel_cnt.p);
+        if ((rc = launch_scan_u32(c, st, (const unsigned int *)c->sel_cnt, nblk, c->sel_base, (long long *)c->d_word.p))) return rc;
+        hipLaunchKernelGGL(k_dedup_scatter, dim3((unsigned)nblk), dim3(256), 0, st, d_table1, d_table2, (const uint8_t *)verdict, d_ord, n,
+                           (const long long *)c->sel_base, d_out1, d_out2, d_idx);
+    }
+    HIPCHK(hipMemcpyAsync(d->h_blk, d->d_blk, sizeof(DedupBlock), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    const DedupBlock &b = *d->h_blk.p;
+    d->submitted += n;
+    d->distinct += (int64_t)b.added;
+    if (b.err)
+        return fail(FFQ_E_INTERNAL, "%s: a probe visited all %lld slots (stage mask %llu): the table is damaged", who, (long long)d->slots,
+                    b.err);
+    counts[0] = (int64_t)b.kept; counts[1] = (int64_t)b.dups; counts[2] = (int64_t)b.nokey;
+    counts[3] = d->distinct; counts[4] = d->slots; counts[5] = d->rehashes;
+    *n_out = drop ? counts[0] : n;
     return FFQ_OK;
 }
 

@@ -166,6 +166,17 @@ struct ffq_stream {
     struct { bool on = false; ffq_content_rules rules = {}; int64_t last[FFQ_FILTER_COUNTS] = {0, 0, 0, 0, 0, 0, 0, 0}; } content;
     // FASTQ text of every fill's table, behind the trim and the filter (ffq_stream_set_render)
     struct { bool on = false; int64_t last[3] = {0, 0, 0}; } render;
+    // duplicate removal (ffq_stream_set_dedup): the stream's own set, the keys of the fill's rows as scanned, the rows and
+    // ordinals that remain behind it, and the counts summed over the fills.  keys_on alone: a pair takes the keys (ffq_pair_set_dedup)
+    struct {
+        bool on = false, keys_on = false;
+        int drop = 1;
+        ffq_dedup *set = nullptr;
+        DevBuf<uint64_t> keys;
+        DevBuf<int64_t> rows, idx;
+        int64_t keyed[2] = {0, 0};
+        int64_t total[FFQ_DEDUP_COUNTS] = {0, 0, 0, 0, 0, 0};
+    } dedup;
     // FFQ_STREAM_PROF=1: where the time of a stream goes (printed when it closes)
     bool prof = false;
     double t_read = 0, t_slot = 0, t_feed = 0, t_scan = 0, t_rows = 0, t_copy = 0;
@@ -285,6 +296,7 @@ static void stream_free(ffq_stream *s)
                         "for the reader, %.3f ms carry + scan (of which %.3f ms waiting for the chunk's copy), %.3f ms rows back\n",
                 (long long)(s->cur + 1), s->t_read * 1e3, s->t_slot * 1e3, s->t_feed * 1e3, s->t_scan * 1e3, s->t_copy * 1e3,
                 s->t_rows * 1e3);
+    ffq_dedup_destroy(s->dedup.set);         // (waits for the scan stream)
     if (s->b) {
         for (auto &st : s->b->cs) if (st) (void)hipStreamSynchronize(st);
         if (s->c->stream) (void)hipStreamSynchronize(s->c->stream);
@@ -632,6 +644,57 @@ extern "C" int ffq_stream_filter_counts(ffq_stream *s, int64_t counts[FFQ_FILTER
     return FFQ_OK;
 }
 
+// Duplicate removal in the stream (include/ffq.h states the rule): the stream owns one set for its whole life.  Every fill's
+// rows get their keys in FRONT of the trims, as scanned (ffq_table_seq_keys), and the rows the select kept are entered into
+// the set right BEHIND it (ffq_dedup_select with the select's ordinals): a read never loses to a copy the filters dropped.
+// drop == 0: counted only, every row stays.  A stream without a filter gets one with unbounded length and no column, as
+// ffq_stream_set_content arranges it.  Before the first fill; not with FFQ_F_DECODE_QUAL.
+extern "C" int ffq_stream_set_dedup(ffq_stream *s, int drop, int64_t expected_keys, int64_t max_bytes)
+{
+    if (!s) return fail(FFQ_E_ARG, "ffq_stream_set_dedup: NULL stream");
+    int rc = stream_settable(s, "ffq_stream_set_dedup", DECODE_GATHERS, true);
+    if (rc) return rc;
+    if (s->paired) return fail(FFQ_E_ARG, "ffq_stream_set_dedup: the stream belongs to a pair (ffq_pair_set_dedup)");
+    ffq_dedup *set = nullptr;
+    rc = ffq_dedup_create(s->c, expected_keys, max_bytes, &set);
+    if (rc) return rc;
+    ffq_dedup_destroy(s->dedup.set);
+    s->dedup.set = set;
+    if (!s->filter.on) {
+        s->filter.on = true;
+        s->filter.min = -((int64_t)1 << 62); s->filter.max = (int64_t)1 << 62; s->filter.col = 0; s->filter.add = 0;
+    }
+    s->dedup.on = s->dedup.keys_on = true;
+    s->dedup.drop = drop ? 1 : 0;
+    return FFQ_OK;
+}
+
+// The six counts (FFQ_DEDUP_COUNTS) over EVERY fill up to the one ffq_stream_next has just returned: [0] to [2] summed,
+// [3] to [5] the set as it stands.
+extern "C" int ffq_stream_dedup_counts(ffq_stream *s, int64_t counts[FFQ_DEDUP_COUNTS])
+{
+    if (!s || !counts) return fail(FFQ_E_ARG, "ffq_stream_dedup_counts: NULL argument");
+    if (!s->dedup.on) return fail(FFQ_E_ARG, "ffq_stream_dedup_counts: the stream does not look for duplicates (ffq_stream_set_dedup)");
+    for (int i = 0; i < FFQ_DEDUP_COUNTS; i++) counts[i] = s->dedup.total[i];
+    return FFQ_OK;
+}
+
+// what a round or a fill adds to the running counts
+static void dedup_tally(int64_t total[FFQ_DEDUP_COUNTS], const int64_t c[FFQ_DEDUP_COUNTS])
+{
+    for (int i = 0; i < 3; i++) total[i] += c[i];
+    for (int i = 3; i < FFQ_DEDUP_COUNTS; i++) total[i] = c[i];
+}
+
+// a device buffer of the dedup stage grown to n elements: the stream is waited for first (the old block goes away)
+template <class B>
+static int dedup_room(ffq_ctx *c, B &buf, int64_t n, const char *what)
+{
+    if (buf.cap >= n) return FFQ_OK;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return stream_grow(buf, std::max<int64_t>(n, 1 << 12), what, n);
+}
+
 // Quality trimming in the stream: from the next fill on, every fill's table is trimmed in place on the device
 // (ffq_table_trim_quality) right behind the scan -- in front of the filter, the column gather and the rows' copy back, so
 // that all of them see the trimmed rows.  Refill and carry go by the scan's end offset, not by the table.
@@ -836,12 +899,16 @@ static int stream_scan(ffq_stream *s, const Fill &f, ffq_scan_result *res)
     }
 }
 
-// ---- the two ends of a mate's chain (a fill of a single stream, either mate of a round of a pair).  front: [stats IN], [trim],
-// [adapter] on the `n` scanned rows at `rows`, which the trims edit in place
+// ---- the two ends of a mate's chain (a fill of a single stream, either mate of a round of a pair).  front: [keys], [stats IN],
+// [trim], [adapter] on the `n` scanned rows at `rows`, which the trims edit in place
 static int chain_front(ffq_stream *s, const Fill &f, int64_t *rows, int64_t n)
 {
     int rc = FFQ_OK;
-    if (s->stats.which & FFQ_STATS_IN)
+    if (s->dedup.keys_on && n > 0) {   // (the keys of the rows as scanned: a trim moves a row's end and the table forgets the old one)
+        rc = dedup_room(s->c, s->dedup.keys, n, "ffq_stream: no memory for %lld keys");
+        if (!rc) rc = ffq_table_seq_keys(s->c, f.d_buf, f.n, 0, f.add, rows, n, s->dedup.keys.p, s->dedup.keyed);
+    }
+    if (!rc && (s->stats.which & FFQ_STATS_IN))
         rc = ffq_table_stats(s->c, f.d_buf, f.n, 0, f.add, rows, n, s->stats.base, s->stats.cycles, 1, stream_stats_block(s, FFQ_STATS_IN), nullptr);
     if (!rc && s->trim.on)
         rc = ffq_table_trim_quality(s->c, f.d_buf, f.n, 0, f.add, rows, n, s->trim.base, s->trim.front, s->trim.back, rows, s->trim.last);
@@ -866,13 +933,15 @@ static int chain_back(ffq_stream *s, const Fill &f, const Table &t)
 // at.  With a filter the select REPLACES that table by the kept rows (on the DEVICE, before anything is copied back: a
 // dropped record costs the host nothing, doc/user-guide.rst:153-180); what follows is written once, for either table.
 // This is the one place that states the order of a fill's work on the scan stream, in every configuration:
-//     carry H2D, wait copied[0], wait copied[1], scan, front, [select: by length, or -- content rules -- by length and
-//     content (ffq_table_select_reads), on the rows as the trims left them], back, [idx D2H], [gather, col D2H, coff D2H],
+//     carry H2D, wait copied[0], wait copied[1], scan, front (the keys of the dedup first, on the rows as scanned), [select:
+//     by length, or -- content rules -- by length and content (ffq_table_select_reads), on the rows as the trims left them],
+//     [dedup: the kept rows entered into the stream's set by their keys and the select's ordinals, the first copies kept
+//     (ffq_dedup_select) -- what follows is on the rows that remain], back, [idx D2H], [gather, col D2H, coff D2H],
 //     [qual D2H, qoff D2H], synchronise
 // and of a round of a pair (pair_chain): [names check], mate 1: front, room for its kept rows (stream_alloc_sel), mate 2: the
-// same, room for the ordinals, [room for the merge], [the mates' overlap], the pair select, [the merge of the kept pairs: then
-// what follows is on the rest tables and the rest ordinals], mate 1: back, mate 2: back, ordinals D2H, [merged text D2H],
-// synchronise
+// same, room for the ordinals, [room for the merge], [the mates' overlap], the pair select, [the pair dedup: both tables
+// compacted in step by the pairs' keys], [the merge of the kept pairs: then what follows is on the rest tables and the rest
+// ordinals], mate 1: back, mate 2: back, ordinals D2H, [merged text D2H], synchronise
 // No rows are copied back from an empty table; a fill without records allocates and launches nothing of the push-down,
 // but statistics OUT and the render are still called (n = 0).  *n_out: the rows handed out.
 static int stream_chain(ffq_stream *s, const Fill &f, const ffq_scan_result &res, int64_t *n_out)
@@ -896,9 +965,23 @@ static int stream_chain(ffq_stream *s, const Fill &f, const ffq_scan_result &res
             }
         }
     }
+    const int64_t *d_idx = b->idx.d;
+    if (!rc && s->dedup.on && t.n > 0) {
+        // (count only: nothing is copied, the chain goes on with the select's rows)
+        const bool drop = s->dedup.drop != 0;
+        int64_t cnt[FFQ_DEDUP_COUNTS], kept = 0;
+        if (drop) rc = dedup_room(c, s->dedup.rows, 6 * t.n, "ffq_stream: no memory for %lld rows behind the dedup");
+        if (!rc && drop) rc = dedup_room(c, s->dedup.idx, t.n, "ffq_stream: no memory for %lld ordinals behind the dedup");
+        if (!rc) rc = ffq_dedup_select(s->dedup.set, s->dedup.keys.p, nullptr, b->idx.d, t.n, drop ? t.d_rows : nullptr, nullptr,
+                                       drop ? s->dedup.rows.p : nullptr, nullptr, drop ? s->dedup.idx.p : nullptr, &kept, drop ? 1 : 0, cnt);
+        if (!rc) {
+            dedup_tally(s->dedup.total, cnt);
+            if (drop) { t = Table{s->dedup.rows.p, kept}; d_idx = s->dedup.idx.p; }
+        }
+    }
     if (!rc) rc = chain_back(s, f, t);
     if (rc) return rc;
-    if (s->filter.on && t.n > 0) HIPCHK(hipMemcpyAsync(b->idx.h, b->idx.d, (size_t)t.n * 8, hipMemcpyDeviceToHost, c->stream));
+    if (s->filter.on && t.n > 0) HIPCHK(hipMemcpyAsync(b->idx.h, d_idx, (size_t)t.n * 8, hipMemcpyDeviceToHost, c->stream));
     if (s->filter.on && s->filter.col && res.n_records > 0) {
         static const int COLS[4][3] = {{0, 0, 0}, {0, 1, 1}, {2, 0, 3}, {4, 0, 5}};       // header: buf[pos0 + 1 : pos1] (:161-171)
         const int *col = COLS[s->filter.col];
@@ -1032,6 +1115,15 @@ struct ffq_pair {
         Mirror<uint8_t> text;
         int64_t last[FFQ_MERGE_COUNTS] = {0, 0, 0, 0, 0, 0};
     } merge;
+    // duplicate pairs dropped behind the pair select (ffq_pair_set_dedup): the pair's own set, the rows of both mates and the
+    // ordinals that remain, the counts summed over the rounds
+    struct {
+        bool on = false;
+        int drop = 1;
+        ffq_dedup *set = nullptr;
+        DevBuf<int64_t> rows[2], idx;
+        int64_t total[FFQ_DEDUP_COUNTS] = {0, 0, 0, 0, 0, 0};
+    } dedup;
 };
 
 extern "C" int ffq_pair_open(ffq_stream *mate1, ffq_stream *mate2, int pair_filter, int check_names, ffq_pair **out)
@@ -1048,6 +1140,7 @@ extern "C" int ffq_pair_open(ffq_stream *mate1, ffq_stream *mate2, int pair_filt
         if (s->cur >= 0 || s->done || s->failed) return fail(FFQ_E_ARG, "ffq_pair_open: mate %d is not a fresh stream", k + 1);
         if (s->flags & FFQ_F_DECODE_QUAL) return fail(FFQ_E_ARG, "ffq_pair_open: mate %d decodes every record's qualities (FFQ_F_DECODE_QUAL)", k + 1);
         if (s->filter.on && s->filter.col) return fail(FFQ_E_ARG, "ffq_pair_open: mate %d's filter gathers a column", k + 1);
+        if (s->dedup.on) return fail(FFQ_E_ARG, "ffq_pair_open: mate %d has a dedup of its own (ffq_stream_set_dedup); a pair's is ffq_pair_set_dedup", k + 1);
     }
     ffq_pair *p = new (std::nothrow) ffq_pair();
     if (!p) return fail(FFQ_E_NOMEM, "out of host memory");
@@ -1061,6 +1154,7 @@ extern "C" void ffq_pair_close(ffq_pair *p)
 {
     if (!p) return;
     if (p->c && p->c->stream) (void)hipStreamSynchronize(p->c->stream);      // (the index buffer goes away)
+    ffq_dedup_destroy(p->dedup.set);
     delete p;
 }
 
@@ -1120,6 +1214,34 @@ extern "C" int ffq_pair_merged(ffq_pair *p, const uint8_t **h_text, int64_t *n_b
     return FFQ_OK;
 }
 
+// Duplicate PAIRS dropped (include/ffq.h: the pair key): the pair owns the set; both mates' fronts compute their keys over the
+// round's window, and the kept pairs of the pair select are entered by their pair keys, in front of the merge.
+extern "C" int ffq_pair_set_dedup(ffq_pair *p, int drop, int64_t expected_keys, int64_t max_bytes)
+{
+    if (!p) return fail(FFQ_E_ARG, "ffq_pair_set_dedup: NULL pair");
+    if (p->started) return fail(FFQ_E_ARG, "ffq_pair_set_dedup: the walk has begun (call it before the first ffq_pair_next)");
+    for (int k = 0; k < 2; k++)
+        if (p->m[k].s->dedup.on) return fail(FFQ_E_ARG, "ffq_pair_set_dedup: mate %d has a dedup of its own (ffq_stream_set_dedup)", k + 1);
+    ffq_dedup *set = nullptr;
+    const int rc = ffq_dedup_create(p->c, expected_keys, max_bytes, &set);
+    if (rc) return rc;
+    ffq_dedup_destroy(p->dedup.set);
+    p->dedup.set = set;
+    p->dedup.on = true;
+    p->dedup.drop = drop ? 1 : 0;
+    for (int k = 0; k < 2; k++) p->m[k].s->dedup.keys_on = true;
+    return FFQ_OK;
+}
+
+// the six counts over every round so far (ffq_stream_dedup_counts' way), in pairs
+extern "C" int ffq_pair_dedup_counts(ffq_pair *p, int64_t counts[FFQ_DEDUP_COUNTS])
+{
+    if (!p || !counts) return fail(FFQ_E_ARG, "ffq_pair_dedup_counts: NULL argument");
+    if (!p->dedup.on) return fail(FFQ_E_ARG, "ffq_pair_dedup_counts: the pair does not look for duplicates (ffq_pair_set_dedup)");
+    for (int i = 0; i < FFQ_DEDUP_COUNTS; i++) counts[i] = p->dedup.total[i];
+    return FFQ_OK;
+}
+
 extern "C" int ffq_pair_wants(ffq_pair *p) { return p && !p->failed ? walk_wants(p->w) : 0; }
 
 // what the per-stream accessors report for a round: zero until the round's chain says otherwise
@@ -1130,15 +1252,15 @@ static void pair_clear_last(ffq_stream *s)
     s->filter.scanned = 0; s->filter.col_bytes = 0;
 }
 
-// The end of a merging round's chain, behind the pair select: the `kept` pairs of both `sel` tables merged by the insert sizes
-// of their ordinals, the two ends of the mates' chains on the rest tables, the rest ordinals and the merged text copied back.
-static int pair_chain_merge(ffq_pair *p, int64_t kept, int64_t *n_out)
+// The end of a merging round's chain, behind the pair select (and the pair dedup): the `kept` pairs of both tables `rows` merged
+// by the insert sizes of their ordinals `d_ord`, the two ends of the mates' chains on the rest tables, the rest ordinals and the merged text copied back.
+static int pair_chain_merge(ffq_pair *p, const int64_t *const rows[2], const int64_t *d_ord, int64_t kept, int64_t *n_out)
 {
     ffq_ctx *c = p->c;
     ffq_table_view v[2];
-    for (int k = 0; k < 2; k++) v[k] = ffq_table_view{p->m[k].f.d_buf, p->m[k].f.n, 0, p->m[k].f.add, p->m[k].s->b->sel.p};
+    for (int k = 0; k < 2; k++) v[k] = ffq_table_view{p->m[k].f.d_buf, p->m[k].f.n, 0, p->m[k].f.add, rows[k]};
     int64_t n_rest = 0;
-    int rc = ffq_table_pair_merge(c, &v[0], &v[1], kept, p->merge.insert.p, p->idx.d, p->merge.text.d, p->merge.text.d.cap, nullptr,
+    int rc = ffq_table_pair_merge(c, &v[0], &v[1], kept, p->merge.insert.p, d_ord, p->merge.text.d, p->merge.text.d.cap, nullptr,
                                   p->merge.rest[0].p, p->merge.rest[1].p, p->merge.ord.d, &n_rest, p->merge.last);
     if (rc == FFQ_E_TABLE_FULL)
         return fail(FFQ_E_INTERNAL, "ffq_pair: fills of %lld and %lld bytes merged to %lld", (long long)v[0].n_bytes, (long long)v[1].n_bytes,
@@ -1206,10 +1328,25 @@ static int pair_chain(ffq_pair *p, int64_t m, int64_t *n_out, int64_t *differ)
     int64_t kept = 0;
     if (!rc) rc = ffq_table_select_pairs(c, &v[0], &v[1], m, bounds, rules[0], rules[1], p->mode, p->m[0].s->b->sel, p->m[1].s->b->sel,
                                          p->idx.d, &kept, p->m[0].s->content.last, p->m[1].s->content.last, p->last_pairs);
-    if (!rc && p->merge.on) return pair_chain_merge(p, kept, n_out);
-    for (int k = 0; k < 2 && !rc; k++) rc = chain_back(p->m[k].s, p->m[k].f, Table{p->m[k].s->b->sel, kept});
+    const int64_t *rows[2] = {p->m[0].s->b->sel.p, p->m[1].s->b->sel.p}, *d_ord = p->idx.d;
+    if (!rc && p->dedup.on && kept > 0) {
+        // (count only: nothing is copied, the chain goes on with the select's rows)
+        const bool drop = p->dedup.drop != 0;
+        int64_t cnt[FFQ_DEDUP_COUNTS], left = 0;
+        for (int k = 0; k < 2 && !rc && drop; k++) rc = dedup_room(c, p->dedup.rows[k], 6 * kept, "ffq_pair: no memory for %lld rows behind the dedup");
+        if (!rc && drop) rc = dedup_room(c, p->dedup.idx, kept, "ffq_pair: no memory for %lld ordinals behind the dedup");
+        if (!rc) rc = ffq_dedup_select(p->dedup.set, p->m[0].s->dedup.keys.p, p->m[1].s->dedup.keys.p, p->idx.d, kept, drop ? rows[0] : nullptr,
+                                       drop ? rows[1] : nullptr, drop ? p->dedup.rows[0].p : nullptr, drop ? p->dedup.rows[1].p : nullptr,
+                                       drop ? p->dedup.idx.p : nullptr, &left, drop ? 1 : 0, cnt);
+        if (!rc) {
+            dedup_tally(p->dedup.total, cnt);
+            if (drop) { rows[0] = p->dedup.rows[0].p; rows[1] = p->dedup.rows[1].p; d_ord = p->dedup.idx.p; kept = left; }
+        }
+    }
+    if (!rc && p->merge.on) return pair_chain_merge(p, rows, d_ord, kept, n_out);
+    for (int k = 0; k < 2 && !rc; k++) rc = chain_back(p->m[k].s, p->m[k].f, Table{rows[k], kept});
     if (rc) return rc;
-    if (kept > 0) HIPCHK(hipMemcpyAsync(p->idx.h, p->idx.d, (size_t)kept * 8, hipMemcpyDeviceToHost, c->stream));
+    if (kept > 0) HIPCHK(hipMemcpyAsync(p->idx.h, d_ord, (size_t)kept * 8, hipMemcpyDeviceToHost, c->stream));
     *n_out = kept;
     return FFQ_OK;
 }

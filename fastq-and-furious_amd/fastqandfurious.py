@@ -694,7 +694,9 @@ class FastqStats:
     len_hist (C + 1, the last bin "C or longer"), readq_hist (96, by a read's mean quality), gc_hist (101, by its GC per
     cent) -- with C = max_cycles.  This class is the host statement of the rule: add_record for one eligible record,
     add_rows for a table (rows the rule does not apply to count in head[1] only); from_words wraps what the device counted;
-    += merges two of one shape (the ranks of a sharded read summing theirs)."""
+    += merges two of one shape (the ranks of a sharded read summing theirs).
+    keyed, distinct, duplicates, duplication_rate: set by fastq_stats(duplication=True) only (DedupReport's fields)."""
+    keyed = distinct = duplicates = duplication_rate = None
 
     def __init__(self, max_cycles=512, qual_base=33):
         max_cycles, qual_base = int(max_cycles), int(qual_base)
@@ -922,6 +924,102 @@ def _pushes_down_content(entryfunc):
             and (r is ContentRules or (r.verdict is ContentRules.verdict and r.verdict_pos is ContentRules.verdict_pos)))
 
 
+_M64 = (1 << 64) - 1
+
+
+def _sm64(z):
+    """the splitmix64 finaliser"""
+    z ^= z >> 30
+    z = (z * 0xbf58476d1ce4e5b9) & _M64
+    z ^= z >> 27
+    z = (z * 0x94d049bb133111eb) & _M64
+    return z ^ (z >> 31)
+
+
+def seq_key(sequence):
+    """The 64-bit key duplicate removal knows a read by (include/ffq.h states the rule at ffq_table_seq_keys; this is its host
+    statement, in plain integers): a sum of one mixed term per four bytes of `sequence` -- little-endian, zero behind the
+    end, the word's ordinal in the upper half --, mixed once more with the length; never 0.  Bytes are taken as they are."""
+    s = bytes(sequence)
+    n = len(s)
+    total = 0
+    for k in range((n + 3) // 4):
+        total += _sm64(((k + 1) << 32) | int.from_bytes(s[4 * k:4 * k + 4], "little"))
+    return _sm64((total + n * 0x9e3779b97f4a7c15) & _M64) or 1
+
+
+def pair_key(k1, k2):
+    """The key of a pair from its mates' keys, ordered; 0 (no key) if either mate has none."""
+    if not k1 or not k2:
+        return 0
+    return _sm64((_sm64(k1) + k2) & _M64) or 1
+
+
+class DedupRules:
+    """Duplicate removal for filter_fastq / filter_fastq_paired (`fastp --dedup`; include/ffq.h states the rule): of the reads
+    (pairs) the filters keep, those whose sequence -- as scanned, in front of any trim -- was seen before are dropped; the first
+    copy in file order stays.  expected_reads: sizes the device set so that it need not grow (0: it grows as the file goes);
+    max_bytes: cap of the device set (0: none); count_only: duplicates are counted (DedupReport), nothing is dropped."""
+
+    def __init__(self, expected_reads=0, max_bytes=0, count_only=False):
+        self.expected_reads, self.max_bytes, self.count_only = int(expected_reads), int(max_bytes), bool(count_only)
+        if self.expected_reads < 0 or self.max_bytes < 0:
+            raise ValueError("expected_reads and max_bytes are >= 0")
+
+
+class DedupReport:
+    """What filter_fastq(dedup_report=...) fills, of the reads (pairs) the filters kept: `keyed` had a key, `unkeyed` had none
+    (wrapped records: always written), `distinct` different keys, `duplicates` = keyed - distinct."""
+
+    def __init__(self):
+        self.keyed = self.unkeyed = self.distinct = self.duplicates = 0
+
+    @property
+    def duplication_rate(self):
+        return self.duplicates / self.keyed if self.keyed else 0.0
+
+    def _from_counts(self, counts):
+        """the six counts of a stream or a pair (hip: dedup_counts)"""
+        self.keyed, self.unkeyed = counts[0] + counts[1] - counts[2], counts[2]
+        self.duplicates, self.distinct = counts[1], counts[3]
+
+
+class _HostDedup:
+    """The set on the host route: a dict of keys.  key(): of a record as scanned; keep(): is the record (of that key) written?"""
+
+    def __init__(self, rules, report):
+        self.drop = not rules.count_only
+        self.report = report if report is not None else DedupReport()
+        self.report.__init__()
+        self.seen = set()
+
+    @staticmethod
+    def key(buf, pos):
+        return seq_key(buf[pos[2]:pos[3]]) if adapter_trimmable(buf, pos) else 0
+
+    def keep(self, key):
+        rep = self.report
+        if not key:
+            rep.unkeyed += 1
+            return True
+        rep.keyed += 1
+        if key in self.seen:
+            rep.duplicates += 1
+            return not self.drop
+        self.seen.add(key)
+        rep.distinct += 1
+        return True
+
+
+def _check_dedup(dedup, dedup_report):
+    if dedup is not None and not isinstance(dedup, DedupRules):
+        raise TypeError("dedup must be a DedupRules")
+    if dedup_report is not None and dedup is None:
+        raise ValueError("dedup_report needs dedup")
+    if dedup_report is not None and not isinstance(dedup_report, DedupReport):
+        raise TypeError("dedup_report must be a DedupReport")
+
+
 class FilterReport:
     """What filter_fastq(report=...) fills: the statistics of the reads as they came in (`before`) and as they were written
     (`after`: behind the trims and the filters), and `dropped`: how many records each reason (ContentRules.REASONS) dropped."""
@@ -941,11 +1039,14 @@ def _scanner(entrypos):
     return entrypos, getattr(entrypos, 'open_stream', None)
 
 
-def _configure_stream(st, trim, cutter, content, bounds, column=None, render=False, stats=None):
+def _configure_stream(st, trim, cutter, content, bounds, column=None, render=False, stats=None, dedup=None):
     """What a native stream is asked for, in the order its chain works (csrc/ffq_stream.h states it above stream_chain): the
     quality trim (an entryfunc_qualitytrim), the adapter trim (an entryfunc_adaptertrim), the content rules, the length
     filter (bounds: (min_len, max_len)) with the gathered column, the render, the statistics (stats: (qual_base,
-    max_cycles)).  None / False: that setter is not called.  A stage that is added to the chain is added HERE."""
+    max_cycles)), the duplicate removal (dedup: a DedupRules; the stream takes the keys in front of the trims and asks its set
+    behind the filter).  None / False: that setter is not called.  A stage that is added to the chain is added HERE."""
+    if dedup is not None:
+        st.set_dedup(not dedup.count_only, dedup.expected_reads, dedup.max_bytes)
     if trim is not None:
         st.set_trim(trim.cutoff_back, trim.cutoff_front, trim.qual_base)
     if cutter is not None:
@@ -968,8 +1069,10 @@ class _MatePlan:
     `dropped`: this file's records by the reason (ContentRules.REASONS) they failed for; `report` (a FilterReport or None) is
     reset and bound to it."""
 
-    def __init__(self, quality_cutoff, qual_base, adapter, err_permille, min_overlap, min_len, max_len, content, report, judged=True):
+    def __init__(self, quality_cutoff, qual_base, adapter, err_permille, min_overlap, min_len, max_len, content, report, judged=True,
+                 dedup=None):
         self.qual_base, self.content, self.report, self.judged = qual_base, content, report, judged
+        self.dedup = dedup           # (a single file's DedupRules; a pair's duplicates are the PairStream's, not a mate's)
         self.dropped = dict.fromkeys(ContentRules.REASONS, 0)
         if report is not None:
             report.dropped = self.dropped
@@ -989,7 +1092,7 @@ class _MatePlan:
         """the file's stream: what is switched on, the render, and the statistics if there is a report"""
         rep = self.report
         _configure_stream(st, self.trim, self.cutter, self.content, None if self.lo is None and self.hi is None else (self.lo, self.hi),
-                          render=True, stats=None if rep is None else (self.qual_base, rep.max_cycles))
+                          render=True, stats=None if rep is None else (self.qual_base, rep.max_cycles), dedup=self.dedup)
 
     def drain(self, st, fh_out):
         """One fill (or round) of the stream: its text written with one write, its drops counted; (bytes written, rows
@@ -1048,30 +1151,45 @@ class _MatePlan:
 
 
 def fastq_stats(fh: typing.BinaryIO, fbufsize: int = 1 << 24, qual_base: int = 33, max_cycles: int = 512,
-                entrypos: typing.Optional[typing.Callable] = None) -> FastqStats:
+                entrypos: typing.Optional[typing.Callable] = None, duplication: bool = False) -> FastqStats:
     """The statistics of every record of a FASTQ stream.  entrypos None (the GPU scanner): the stream front end scans
     every buffer fill and counts its table on the device (ffq_stream_set_stats); no row is looked at here and the totals
     are read once at the end.  Any other scanner: a loop over readfastq_iter with FastqStats.add_pos.  Malformed input
-    raises what readfastq_iter raises."""
+    raises what readfastq_iter raises.
+    duplication: the reads are also looked up in a set of sequence keys (DedupRules(count_only=True): the stream's dedup on the
+    device, a set of seq_key on the host) and the result's keyed, distinct, duplicates and duplication_rate are set."""
     out = FastqStats(max_cycles, qual_base)
+    hd = _HostDedup(DedupRules(count_only=True), None) if duplication else None
+
+    def with_duplication(res, rep):
+        res.keyed, res.distinct, res.duplicates, res.duplication_rate = rep.keyed, rep.distinct, rep.duplicates, rep.duplication_rate
+        return res
     entrypos, open_stream = _scanner(entrypos)
     st = open_stream(fh, fbufsize) if open_stream is not None else None
     if st is not None:
         try:
             st.set_stats(_hip.STATS_IN, qual_base, max_cycles)
+            if duplication:
+                st.set_dedup(False)
             for _rows, _fill, _fill_offset, end_state, err_offset in st:
                 if end_state != _END_OK and end_state != _END_REFILL:
                     _raise_for_end(end_state, err_offset)
-            return FastqStats.from_words(st.stats(_hip.STATS_IN), max_cycles, qual_base)
+            res = FastqStats.from_words(st.stats(_hip.STATS_IN), max_cycles, qual_base)
+            if duplication:
+                hd.report._from_counts(st.dedup_counts())
+                with_duplication(res, hd.report)
+            return res
         finally:
             st.close()
 
     def count(buf, pos, globaloffset=None):
         out.add_pos(buf, pos)
+        if hd is not None:
+            hd.keep(hd.key(buf, pos))
 
     for _ in readfastq_iter(fh, fbufsize, count, entrypos):
         pass
-    return out
+    return with_duplication(out, hd.report) if duplication else out
 
 
 FilterResult = namedtuple('FilterResult', 'records_in records_out bases_removed bytes_out')
@@ -1079,7 +1197,8 @@ FilterResult = namedtuple('FilterResult', 'records_in records_out bases_removed 
 
 def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1 << 24, quality_cutoff=None,
                  qual_base: int = 33, min_len=None, max_len=None, entrypos: typing.Optional[typing.Callable] = None,
-                 adapter=None, err_permille: int = 100, min_overlap: int = 3, report=None, content=None) -> FilterResult:
+                 adapter=None, err_permille: int = 100, min_overlap: int = 3, report=None, content=None, dedup=None,
+                 dedup_report=None) -> FilterResult:
     """Trim, filter and WRITE a FASTQ stream: the file `cutadapt -q 20 -m 30` leaves behind, which is what the tables of
     positions of the reference's user guide are kept for in the end ("to avoid saving a FASTQ file after each filtering or
     read-trimming step", doc/user-guide.rst:196-204).  Every record of `fh` is quality-trimmed (quality_cutoff: an int --
@@ -1112,10 +1231,18 @@ def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1
 
     content: a ContentRules; a record that its trimmed length keeps is dropped by the first of its rules that fails (`cutadapt
     --max-n --max-ee`, `fastp -n -e -q -u -y`): judged on the device with the GPU scanner (ffq_stream_set_content), by
-    ContentRules.verdict_pos with any other.  Rows the rules do not apply to (wrapped records) go by their length alone."""
+    ContentRules.verdict_pos with any other.  Rows the rules do not apply to (wrapped records) go by their length alone.
+
+    dedup: a DedupRules; of the records the filters keep, one whose sequence AS READ (in front of the trims: two copies that a
+    quality trim cut differently are still one read) was met before in the file is not written -- on the device with the GPU
+    scanner (ffq_stream_set_dedup: a set of 64-bit keys that lives there across the fills), with a set of seq_key on the host.
+    records_out does not count the duplicates; report.dropped does not either: dedup_report (a DedupReport) has the numbers.
+    A wrapped record has no key and is always written."""
     if content is not None and not isinstance(content, ContentRules):
         raise TypeError("content must be a ContentRules")
-    plan = _MatePlan(quality_cutoff, qual_base, adapter, err_permille, min_overlap, min_len, max_len, content, report)
+    _check_dedup(dedup, dedup_report)
+    plan = _MatePlan(quality_cutoff, qual_base, adapter, err_permille, min_overlap, min_len, max_len, content, report, dedup=dedup)
+    hd = _HostDedup(dedup, dedup_report) if dedup is not None else None
     entrypos, open_stream = _scanner(entrypos)
     n_in = n_out = removed = n_bytes = 0
     st = open_stream(fh, fbufsize) if open_stream is not None else None
@@ -1131,13 +1258,18 @@ def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1
                 if end_state != _END_OK and end_state != _END_REFILL:
                     _raise_for_end(end_state, err_offset)
             plan.finish(st)
+            if hd is not None:
+                hd.report._from_counts(st.dedup_counts())
         finally:
             st.close()
         return FilterResult(n_in, n_out, removed, n_bytes)
 
     def record(buf, pos, globaloffset=None):
+        key = hd.key(buf, pos) if hd is not None else 0
         pos, cut = plan.trimmed_pos(buf, pos)
-        return cut, None if plan.verdict(buf, pos) else plan.text(buf, pos)
+        if plan.verdict(buf, pos) or (hd is not None and not hd.keep(key)):
+            return cut, None
+        return cut, plan.text(buf, pos)
 
     for cut, text in readfastq_iter(fh, fbufsize, record, entrypos):
         n_in += 1
@@ -1320,7 +1452,7 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
                         pair_filter: str = "any", check_names: bool = True, report=None, report2=None,
                         entrypos: typing.Optional[typing.Callable] = None, overlap=None,
                         overlap_report=None, merged_out: typing.Optional[typing.BinaryIO] = None,
-                        merge_report=None) -> PairedFilterResult:
+                        merge_report=None, dedup=None, dedup_report=None) -> PairedFilterResult:
     """filter_fastq for paired-end files: the i-th records of `fh1` and `fh2` are mates, and a pair is written or dropped
     TOGETHER, so that `fh_out1` and `fh_out2` stay record for record in step (`cutadapt -q 20 -a ... -A ... -m 30:20
     --pair-filter=any -o out1 -p out2 in1 in2`).  Every record is trimmed as filter_fastq trims it -- quality_cutoff for both
@@ -1362,6 +1494,10 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
     ONCE, to merged_out, as one read under mate 1's header, and to neither fh_out1 nor fh_out2.  pairs_out still counts every
     pair the filter kept; bytes_out1 / bytes_out2 and report.after / report2.after count what went to those two files.
     merge_report: a MergeReport (needs merged_out), filled on either route with the same numbers.
+
+    dedup: a DedupRules; behind the filter and in front of the merge, a pair whose two sequences AS READ were met before as a
+    pair (pair_key of the mates' seq_key: ordered) is dropped; the first copy stays.  pairs_out does not count the duplicates,
+    `dropped` and the FilterReports do not know them: dedup_report (a DedupReport, in pairs) has the numbers.
     Not done: interleaved input or output, base correction inside the overlap of mates that are not merged."""
     if content is not None and not isinstance(content, ContentRules):
         raise TypeError("content must be a ContentRules")
@@ -1375,6 +1511,8 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
         raise ValueError("merged_out needs overlap")
     if merge_report is not None and merged_out is None:
         raise ValueError("merge_report needs merged_out")
+    _check_dedup(dedup, dedup_report)
+    hd = _HostDedup(dedup, dedup_report) if dedup is not None else None
     mrep = MergeReport()
     if merge_report is not None:
         merge_report.__dict__.update(mrep.__dict__)
@@ -1416,6 +1554,8 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
                 ps.set_overlap(overlap)
             if merged_out is not None:
                 ps.set_merge()
+            if dedup is not None:
+                ps.set_dedup(not dedup.count_only, dedup.expected_reads, dedup.max_bytes)
             for n_in, n_out, end_state, err_mate, err_offset in ps:
                 pairs_in += n_in
                 if merged_out is not None:           # (n_out: the kept pairs that were not merged)
@@ -1456,6 +1596,8 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
                 plan.finish(st)
             if overlap is not None:
                 orep.insert_hist = ps.overlap()[1]
+            if hd is not None:
+                hd.report._from_counts(ps.dedup_counts())
         finally:
             if ps is not None:
                 ps.close()
@@ -1465,16 +1607,18 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
 
     def recorder(plan):
         def record(buf, pos, globaloffset=None):
-            """(where it is, its id, bases cut, its buffer, its positions as the trims left them): kept until its mate is there"""
+            """(where it is, its id, bases cut, its buffer, its positions as the trims left them, its key as scanned): kept until its
+            mate is there"""
             at = pos[0] + (globaloffset or 0)
             name = pair_id(buf[(pos[0] + 1):pos[1]]) if check_names else None
+            key = hd.key(buf, pos) if hd is not None else 0
             pos, cut = plan.trimmed_pos(buf, pos)
-            return at, name, cut, buf, tuple(pos[i] for i in range(6))
+            return at, name, cut, buf, tuple(pos[i] for i in range(6)), key
         return record
 
     def overlap_cut(r1, r2):
         """the two records with the overlap's cut applied and the pair's insert size (None: none), and the report filled"""
-        (buf1, pos1), (buf2, pos2) = r1[3:], r2[3:]
+        (buf1, pos1), (buf2, pos2) = r1[3:5], r2[3:5]
         if not overlap_analysable(buf1, pos1, buf2, pos2):
             return r1, r2, None
         orep.pairs_analysed += 1
@@ -1491,14 +1635,14 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
             c = min(n, insert)
             pos = r[4]
             orep.bases_removed[k] += n - c
-            out.append(r[:2] + (r[2] + n - c, r[3], (pos[0], pos[1], pos[2], pos[2] + c, pos[4], pos[4] + c)))
+            out.append(r[:2] + (r[2] + n - c, r[3], (pos[0], pos[1], pos[2], pos[2] + c, pos[4], pos[4] + c)) + r[5:])
         orep.pairs_trimmed += 1
         return out[0], out[1], insert
 
     def merged_text(r1, r2, insert):
         """the pair as one record (None: it is not merged), and the report filled; behind the cut, with the insert size found
         in front of it: the rule takes o against the current length of mate 2, the text is the same either way"""
-        (buf1, pos1), (buf2, pos2) = r1[3:], r2[3:]
+        (buf1, pos1), (buf2, pos2) = r1[3:5], r2[3:5]
         if not merge_mergeable(buf1, pos1, buf2, pos2, insert):
             return None
         bases, quals = merge_mates(buf1[pos1[2]:pos1[3]], buf1[pos1[4]:pos1[5]], buf2[pos2[2]:pos2[3]], buf2[pos2[4]:pos2[5]], insert)
@@ -1546,6 +1690,8 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
         removed += r1[2] + r2[2]
         if _pair_dropped(pair_filter, v1, v2):
             dropped["both" if (v1 and v2) else "mate1_only" if v1 else "mate2_only"] += 1
+            continue
+        if hd is not None and not hd.keep(pair_key(r1[5], r2[5])):
             continue
         pairs_out += 1
         if merged_out is not None:

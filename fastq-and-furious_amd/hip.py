@@ -50,7 +50,7 @@ def _add(add, sentinel):
     return (-1 if sentinel else 0) if add is None else add
 
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 OK = 0
 E_NODEVICE, E_HIP, E_ARG, E_NOMEM, E_TABLE_FULL, E_INTERNAL, E_TIMEOUT = -1, -2, -3, -4, -5, -6, -7
 STAGE_NONE, STAGE_HANDOFF, STAGE_SCAN, STAGE_GATHER = 0, 1, 2, 3      # FFQ_SHARD_STAGE_*
@@ -104,10 +104,14 @@ SYMBOLS = (
     "ffq_pair_open", "ffq_pair_wants", "ffq_pair_next", "ffq_pair_rows", "ffq_pair_selected", "ffq_pair_close",
     "ffq_table_pair_overlap", "ffq_pair_set_overlap", "ffq_pair_overlap",
     "ffq_table_pair_merge", "ffq_pair_set_merge", "ffq_pair_merged",
+    "ffq_table_seq_keys", "ffq_seq_key_host", "ffq_pair_key_host", "ffq_dedup_create", "ffq_dedup_destroy", "ffq_dedup_select",
+    "ffq_stream_set_dedup", "ffq_stream_dedup_counts", "ffq_pair_set_dedup", "ffq_pair_dedup_counts",
 )
 
 
 FILTER_COUNTS = 8            # FFQ_FILTER_COUNTS: rows kept, dropped by rule 1..6, not judged by content
+KEY_NONE = 0                 # FFQ_KEY_NONE: a row without a key (ffq_table_seq_keys)
+DEDUP_COUNTS = 6             # FFQ_DEDUP_COUNTS: rows kept, duplicates, rows without a key, distinct keys, slots, rehashes
 
 
 class ContentRulesStruct(ctypes.Structure):
@@ -417,6 +421,19 @@ def lib():
         L.ffq_pair_set_merge.argtypes = [vp, i32]
         L.ffq_pair_merged.argtypes = [vp, P(vp), P(i64), P(i64)]
         L.ffq_pair_close.restype = None
+        L.ffq_table_seq_keys.argtypes = [vp, vp, i64, i32, i64, vp, i64, vp, P(i64)]
+        L.ffq_seq_key_host.argtypes = [ctypes.c_char_p, i64]
+        L.ffq_seq_key_host.restype = u64
+        L.ffq_pair_key_host.argtypes = [u64, u64]
+        L.ffq_pair_key_host.restype = u64
+        L.ffq_dedup_create.argtypes = [vp, i64, i64, P(vp)]
+        L.ffq_dedup_destroy.argtypes = [vp]
+        L.ffq_dedup_destroy.restype = None
+        L.ffq_dedup_select.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, P(i64), i32, P(i64)]
+        L.ffq_stream_set_dedup.argtypes = [vp, i32, i64, i64]
+        L.ffq_stream_dedup_counts.argtypes = [vp, P(i64)]
+        L.ffq_pair_set_dedup.argtypes = [vp, i32, i64, i64]
+        L.ffq_pair_dedup_counts.argtypes = [vp, P(i64)]
         L.ffq_stream_set_content.argtypes = [vp, P(ContentRulesStruct)]
         L.ffq_stream_filter_counts.argtypes = [vp, P(i64)]
         L.ffq_table_render_fastq.argtypes = [vp, vp, i64, i32, i64, vp, i64, vp, i64, vp, P(i64)]
@@ -824,6 +841,18 @@ class Context:
         check(rc, allow=(E_TABLE_FULL,))
         return rc, n_rest.value, [int(x) for x in counts]
 
+    def table_seq_keys(self, d_buf, n_bytes, d_table, n_rows, d_keys, sentinel=True, add=None):
+        """The 64-bit sequence key of every row of a device table (ffq_table_seq_keys; include/ffq.h states the rule,
+        fastqandfurious.seq_key is its host statement) into d_keys (uint64 per row; KEY_NONE for a row the rule does not
+        apply to).  Raw device pointers; d_buf / n_bytes / sentinel / add as for table_gather_column.  Returns (rows keyed,
+        rows not keyed)."""
+        add = _add(add, sentinel)
+        counts = (ctypes.c_int64 * 2)()
+        check(lib().ffq_table_seq_keys(self.handle, ctypes.c_void_p(d_buf) if d_buf else None, int(n_bytes), int(bool(sentinel)),
+                                       int(add), ctypes.c_void_p(d_table) if d_table else None, int(n_rows),
+                                       ctypes.c_void_p(d_keys) if d_keys else None, counts))
+        return int(counts[0]), int(counts[1])
+
     COLUMNS = {"header": (0, 1, 1), "sequence": (2, 0, 3), "quality": (4, 0, 5)}
 
     def table_gather_column(self, d_buf, n_bytes, d_table, n_rows, which, d_out, out_cap, d_off, sentinel=True,
@@ -904,6 +933,55 @@ class Context:
     def synth_wrapped(self, dptr, d_start, first, count, seed=43):
         check(lib().ffq_synth_wrapped(self.handle, ctypes.c_void_p(dptr), ctypes.c_void_p(d_start),
                                       int(first), int(count), int(seed)))
+
+
+def seq_key_host(sequence):
+    """ffq_seq_key_host: the key rule by the library's own host code (fastqandfurious.seq_key is the same in Python)."""
+    b = bytes(sequence)
+    return int(lib().ffq_seq_key_host(b, len(b)))
+
+
+def pair_key_host(k1, k2):
+    """ffq_pair_key_host"""
+    return int(lib().ffq_pair_key_host(int(k1), int(k2)))
+
+
+class Dedup:
+    """A device-resident set of sequence keys that outlives the calls on it (ffq_dedup; include/ffq.h states the rule): the
+    first copy of a key, in the order rows are submitted, is kept.  expected_keys: keys the table takes without growing (0:
+    the minimum); max_bytes: cap of the table (0: none; a call that would grow beyond it raises FFQError E_NOMEM and leaves
+    the set usable)."""
+
+    def __init__(self, ctx, expected_keys=0, max_bytes=0):
+        self._h = ctypes.c_void_p()
+        self._ctx = ctx
+        check(lib().ffq_dedup_create(ctx.handle, int(expected_keys), int(max_bytes), ctypes.byref(self._h)))
+
+    def select(self, d_keys1, n, d_keys2=None, d_ord=None, d_table1=None, d_table2=None, d_out1=None, d_out2=None, d_idx=None,
+               drop=True):
+        """Rows 0..n of a call entered and judged (ffq_dedup_select): row i has the key d_keys1[j] -- with d_keys2 the pair key
+        of d_keys1[j], d_keys2[j] --, j = d_ord[i] (None: i); the kept rows of d_table1 / d_table2 (None: nothing is copied)
+        go to d_out1 / d_out2, their j to d_idx (None: not wanted).  drop False: count only, every row is kept.  Raw device
+        pointers.  Returns (rows kept, counts): [kept, duplicates, rows without a key, distinct keys in the set, slots,
+        rehashes so far]."""
+        def ptr(x):
+            return ctypes.c_void_p(x) if x else None
+        k = ctypes.c_int64(0)
+        counts = (ctypes.c_int64 * DEDUP_COUNTS)()
+        check(lib().ffq_dedup_select(self._h, ptr(d_keys1), ptr(d_keys2), ptr(d_ord), int(n), ptr(d_table1), ptr(d_table2),
+                                     ptr(d_out1), ptr(d_out2), ptr(d_idx), ctypes.byref(k), 1 if drop else 0, counts))
+        return k.value, [int(x) for x in counts]
+
+    def close(self):
+        if self._h:
+            lib().ffq_dedup_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def shard_unique_id():
@@ -1172,6 +1250,20 @@ class _Stream:
         yielded; any filtered stream."""
         counts = (ctypes.c_int64 * FILTER_COUNTS)()
         check(lib().ffq_stream_filter_counts(self._h, counts))
+        return [int(x) for x in counts]
+
+    def set_dedup(self, drop=True, expected_keys=0, max_bytes=0):
+        """Duplicate removal in the stream (ffq_stream_set_dedup; before the first fill): the stream owns a set of sequence
+        keys; every fill's rows are keyed as scanned, in front of the trims, and the rows the filter kept are entered right
+        behind it -- the first copy in file order stays, what follows sees the rows that remain.  drop False: counted only."""
+        check(lib().ffq_stream_set_dedup(self._h, 1 if drop else 0, int(expected_keys), int(max_bytes)))
+        self.filtered = True
+
+    def dedup_counts(self):
+        """[rows kept, duplicates, rows without a key] summed over every fill so far, [distinct keys, slots, rehashes] of the
+        set as it stands (ffq_stream_dedup_counts)."""
+        counts = (ctypes.c_int64 * DEDUP_COUNTS)()
+        check(lib().ffq_stream_dedup_counts(self._h, counts))
         return [int(x) for x in counts]
 
     def set_trim(self, cutoff_back, cutoff_front=0, qual_base=33):
@@ -1451,6 +1543,17 @@ class PairStream:
         set_overlap).  Those pairs leave the two ordinary outputs: rows(), selected()'s index and the mates' rendered() are
         then the kept pairs that were not merged, n_out their number; merged() has the others.  Before the first step only."""
         check(lib().ffq_pair_set_merge(self._h, 1 if on else 0))
+
+    def set_dedup(self, drop=True, expected_keys=0, max_bytes=0):
+        """Duplicate PAIRS dropped behind the filter and in front of the merge (ffq_pair_set_dedup; before the first step;
+        neither stream may have a dedup of its own): a pair's key is made of both mates' sequence keys, as scanned."""
+        check(lib().ffq_pair_set_dedup(self._h, 1 if drop else 0, int(expected_keys), int(max_bytes)))
+
+    def dedup_counts(self):
+        """_Stream.dedup_counts, in pairs, over every round so far (ffq_pair_dedup_counts)."""
+        counts = (ctypes.c_int64 * DEDUP_COUNTS)()
+        check(lib().ffq_pair_dedup_counts(self._h, counts))
+        return [int(x) for x in counts]
 
     def merged(self):
         """(text uint8[], counts) of the round just yielded: the FASTQ text of the merged pairs (a view, valid until the next

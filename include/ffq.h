@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FFQ_ABI_VERSION 6
+#define FFQ_ABI_VERSION 7
 
 /* scanner status codes -- identical to the reference's module constants
  * (_fastqandfurious.c:7-15,254-262; fastqandfurious.py:19-27)             */
@@ -585,6 +585,71 @@ int ffq_table_pair_merge(ffq_ctx *ctx, const ffq_table_view *m1, const ffq_table
                          int64_t *d_rest1, int64_t *d_rest2, int64_t *d_rest_ord, int64_t *n_rest,
                          int64_t counts[FFQ_MERGE_COUNTS]);
 
+/* ---- duplicate reads and pairs: sequence keys, the first copy wins (`fastp --dedup`, clumpify, czid-dedup) ---------------
+ * There is no reference implementation of this: THE RULE STATED HERE IS THE SPECIFICATION.  fastqandfurious.seq_key and
+ * pair_key are its host statement in Python, ffq_seq_key_host / ffq_pair_key_host the same in C.
+ *
+ * KEY OF A ROW.  seq = buf[pos2 : pos3] as the row stands when the pass runs, n = len(seq).  With sm the splitmix64 finaliser
+ *     sm(z): z ^= z >> 30; z *= 0xbf58476d1ce4e5b9; z ^= z >> 27; z *= 0x94d049bb133111eb; z ^= z >> 31
+ *     w_k  = the 4 bytes seq[4k .. 4k + 4) as a little-endian uint32, bytes behind the end taken as 0, k = 0 .. ceil(n / 4) - 1
+ *     S    = sum over k of sm( ((k + 1) << 32) | w_k )          (mod 2^64)
+ *     key  = sm( S + n * 0x9e3779b97f4a7c15 );   a key of 0 becomes 1
+ * Words are counted from the sequence's first byte, wherever that lies in memory.  The sum is commutative on purpose: the
+ * lanes and steps of a kernel add their terms in any order and the result is bit-identical.  Bytes are taken verbatim: case
+ * is not folded, 'N' is a byte like any other.  A row is KEYED if it is eligible as ffq_table_trim_adapter asks: positions
+ * - add >= 0 and in order inside the buffer, pos3 - pos2 == pos5 - pos4, the sentinel's coordinate 0 never read, no "\n"
+ * in the sequence.  Every other row -- wrapped records, FASTA rows (-1), rows written by hand that point outside -- gets
+ * FFQ_KEY_NONE.  A read of length 0 is keyed; all empty reads share one key.  No byte outside [d_buf, d_buf + n_bytes) and
+ * none outside the row's checked sequence range is read; the quality line is never read.
+ * ffq_table_seq_keys: d_keys[i] = the key of row i (DEVICE memory, n_rows words, 8-byte aligned; d_table 16-byte aligned;
+ * d_buf / n_bytes / sentinel / add as for ffq_table_gather_column); counts = {rows keyed, rows not keyed}.  n_rows == 0 is
+ * valid.  FFQ_E_ARG: a misaligned table, a scan pending on the context.  One host wait.
+ * PAIR KEY.  pk = sm( sm(k1) + k2 ), 0 becomes 1; FFQ_KEY_NONE if either mate's key is FFQ_KEY_NONE.  Ordered: (k1, k2),
+ * (k2, k1) and (k1, k1) are three pairs.
+ *
+ * THE SET.  ffq_dedup is a device-resident set of {key, first} entries that lives across calls and grows with the file.  Every
+ * row submitted gets a global ordinal g = rows submitted to this set before this call + i.  A keyed row is KEPT if and only
+ * if no row with the same key and a smaller g was ever submitted, in this call or an earlier one: the first copy in file
+ * order wins, whatever the scheduling.  A row with FFQ_KEY_NONE is always kept and never entered.
+ * Two DIFFERENT sequences with equal 64-bit keys count as duplicates: among n reads the chance of one such false pair is
+ * about n^2 / 2^65 (the birthday bound: 3e-3 for a billion reads).
+ * DIFFERENCES from fastp --dedup: the set is exact on the key, not a fixed-size filter with an accuracy level; the key covers
+ * the whole read as scanned, not a prefix; only reads that survive the filters compete (the stream's order, below).
+ * ffq_dedup_create: expected_keys (0: the minimum table of 1024 slots) sizes the table so that this many keys enter without
+ * growth; max_bytes (0: no cap) caps the table's bytes -- a table that would have to grow beyond it makes the call return
+ * FFQ_E_NOMEM, with the need in ffq_last_error, BEFORE anything is launched, and the set stays as it was and usable.  The table
+ * is open addressing over 16-byte slots, grown by the host to the next power of two with slots >= 2 (keys + rows of the
+ * call) before a call that could fill it beyond 1/2; the old and the new table are alive together while one is rehashed
+ * into the other.
+ * ffq_dedup_select: row i of the call uses d_keys*[j], j = d_ord ? d_ord[i] : i, and d_idx[k] = j of kept row k: behind a
+ * select whose d_idx is handed in as d_ord, what comes out still names ordinals among the scanned rows.  d_keys2 (NULL:
+ * single reads): the second mates' keys -- the rows then go by their pair keys.  d_table1 / d_table2 (NULL: no rows are
+ * copied; d_table2 needs d_keys2): n rows each whose kept ones go to d_out1 / d_out2, in order -- room for n rows, 16-byte
+ * aligned, NOT the input tables; d_idx may be NULL; *n_out = rows kept.  drop == 0: count only -- every row is kept and
+ * copied, *n_out = n, the set and the counts advance exactly as with drop != 0, so counts[1] is what would have been dropped.
+ * counts: [0] rows kept, [1] duplicates, [2] rows without a key (also in [0]), [3] distinct keys in the set after the call,
+ * [4] slots, [5] rehashes so far; [0] + [1] == n.  n == 0 is valid.  One host wait.  FFQ_E_ARG: misalignment, a NULL set, a
+ * scan pending on the context, d_table2 without d_keys2.  FFQ_E_INTERNAL: a probe visited every slot -- no kernel of the set
+ * loops without a bound.  All DEVICE memory; calls on a set follow one another (its context's stream).
+ * Not done: a histogram of duplication levels, keys for wrapped records, reverse-complement-aware keys, a set larger than
+ * device memory.                                                                                                        */
+#define FFQ_KEY_NONE 0
+int ffq_table_seq_keys(ffq_ctx *ctx, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
+                       const int64_t *d_table, int64_t n_rows, uint64_t *d_keys,
+                       int64_t counts[2] /* keyed, not keyed */);
+uint64_t ffq_seq_key_host(const uint8_t *seq, int64_t n);          /* the rule on the host, for bindings and tests */
+uint64_t ffq_pair_key_host(uint64_t k1, uint64_t k2);
+
+typedef struct ffq_dedup ffq_dedup;
+int  ffq_dedup_create(ffq_ctx *ctx, int64_t expected_keys /* 0: the minimum */, int64_t max_bytes /* 0: no cap */, ffq_dedup **out);
+void ffq_dedup_destroy(ffq_dedup *d);
+#define FFQ_DEDUP_COUNTS 6
+int  ffq_dedup_select(ffq_dedup *d, const uint64_t *d_keys1, const uint64_t *d_keys2 /* NULL: single reads */,
+                      const int64_t *d_ord /* NULL: identity */, int64_t n,
+                      const int64_t *d_table1, const int64_t *d_table2,
+                      int64_t *d_out1, int64_t *d_out2, int64_t *d_idx, int64_t *n_out,
+                      int drop /* 0: count only, every row is kept and copied */, int64_t counts[FFQ_DEDUP_COUNTS]);
+
 /* ---- FASTA (reference: the plug-in scanner entrypos_fasta, fastqandfurious.py:103-143) -------
  * Every COMPLETE entry of a buffer, i.e. the repeated scanner call with offset := pos[3]:
  * rows = pos0 ('>'), pos1 (header end), pos2, pos3 (the "\n" of the next "\n>") + add, -1, -1.
@@ -706,6 +771,18 @@ int  ffq_stream_stats(ffq_stream *s, int which /* exactly one */, uint64_t *h_ou
  * that ends with the quality's last byte is FFQ_END_ERR_FINAL_QUAL) renders with one.                               */
 int  ffq_stream_set_render(ffq_stream *s);
 int  ffq_stream_rendered(ffq_stream *s, const uint8_t **h_fastq, int64_t *n_fastq_bytes, int64_t stats[3]);
+/* Duplicate removal in the stream (the rules of ffq_stream_set_trim: before the first ffq_stream_next, FFQ_E_ARG with
+ * FFQ_F_DECODE_QUAL).  The stream owns one ffq_dedup (expected_keys, max_bytes: ffq_dedup_create's) for its whole life.  The
+ * keys of every fill's rows are taken in FRONT of the trims, on the rows as scanned (ffq_table_seq_keys) -- two PCR copies
+ * whose quality trims ended at different bases are still one read, and a table does not remember a row's end once a trim
+ * has moved it --, and the set is asked right BEHIND the select (ffq_dedup_select with the select's ordinals), so that a
+ * read never loses to a copy the filters dropped.  Everything behind sees the rows that remain: statistics OUT, render,
+ * column gather, rows back, ffq_stream_selected (whose ordinals still name the scanned records).  drop == 0: counted only,
+ * every row stays.  A stream with dedup counts as filtered (unbounded, ruleless), as ffq_stream_set_content arranges it.  A
+ * fill without records launches nothing.  ffq_stream_dedup_counts: the six counts over EVERY fill up to the one
+ * ffq_stream_next has just returned -- [0] to [2] summed over the fills, [3] to [5] the set as it stands.              */
+int  ffq_stream_set_dedup(ffq_stream *s, int drop, int64_t expected_keys, int64_t max_bytes);
+int  ffq_stream_dedup_counts(ffq_stream *s, int64_t counts[FFQ_DEDUP_COUNTS]);
 /* The same over a gzip-compressed file (what FORMAT_OPENERS['gz'] / automagic_open hand to
  * readfastq_iter, fastqandfurious.py:282-334): the stream's reader thread inflates (zlib; concatenated
  * members, zero padding behind the last one) straight into the pinned chunk buffers -- decompression
@@ -806,6 +883,12 @@ int  ffq_stream_push(ffq_stream *s, int64_t n, int eof);
  * number; pairs[0] of ffq_pair_selected still counts every pair the filter kept.  ffq_pair_merged: the round's merged text
  * (pinned memory, valid until the next ffq_pair_next; *n_bytes == counts[2]) and the six counts of ffq_table_pair_merge;
  * counts may be NULL.  FFQ_E_ARG without ffq_pair_set_merge.
+ * ffq_pair_set_dedup (before the first ffq_pair_next only; FFQ_E_ARG if either stream has a dedup of its own -- ffq_pair_open
+ * refuses such a stream, too): the pair owns one ffq_dedup; both mates' fronts take their keys over the round's window, on
+ * the rows as scanned, and behind ffq_table_select_pairs, in front of the merge, the kept pairs are entered by their PAIR
+ * keys with both tables compacted in step.  *n_pairs_out, ffq_pair_rows and h_index follow it; pairs[0] of
+ * ffq_pair_selected keeps meaning "pairs the filter kept".  ffq_pair_dedup_counts: as ffq_stream_dedup_counts, in pairs,
+ * over every round so far.
  * Not done: interleaved input or output, base correction of mates that are not merged, paired readfastq_iter_range.   */
 typedef struct ffq_pair ffq_pair;
 int  ffq_pair_open(ffq_stream *mate1, ffq_stream *mate2, int pair_filter, int check_names, ffq_pair **out);
@@ -817,6 +900,8 @@ int  ffq_pair_set_overlap(ffq_pair *p, const ffq_overlap_rules *rules);
 int  ffq_pair_overlap(ffq_pair *p, int64_t counts[FFQ_OVERLAP_COUNTS], uint64_t *h_hist, int64_t cap_words);
 int  ffq_pair_set_merge(ffq_pair *p, int on);
 int  ffq_pair_merged(ffq_pair *p, const uint8_t **h_text, int64_t *n_bytes, int64_t counts[FFQ_MERGE_COUNTS]);
+int  ffq_pair_set_dedup(ffq_pair *p, int drop, int64_t expected_keys, int64_t max_bytes);
+int  ffq_pair_dedup_counts(ffq_pair *p, int64_t counts[FFQ_DEDUP_COUNTS]);
 void ffq_pair_close(ffq_pair *p);
 
 /* Bytes [pos, pos + n_bytes) of the file behind fd into device memory (read(), fastqandfurious.py:30-36, for a range
