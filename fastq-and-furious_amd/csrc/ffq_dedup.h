@@ -20,7 +20,8 @@
 //   k_dedup_resolve   a SEPARATE launch -- the kernel boundary is what orders it behind every insert: the slot is found again,
 //                     the row is kept iff first == g; one verdict byte per row (0 kept, 1 duplicate: the length filter's
 //                     count and scan take it from there), the call's counts
-//   k_dedup_scatter   behind the scan: rows of one or two tables and the ordinals, to their places
+//   (the compaction of ffq_compact.h follows on that byte: the rows of one or two tables, or of none, and the ordinals
+//                     through d_ord go to their places)
 //   k_dedup_rehash    every occupied slot of the old table entered, with its `first`, into the new one
 // NO LOOP ON THE DEVICE IS UNBOUNDED: a probe that has visited `slots` slots gives up and sets the block's error word, which
 // the host turns into FFQ_E_INTERNAL -- a table corrupted by a bug must not make a kernel spin.
@@ -263,30 +264,6 @@ __global__ __launch_bounds__(DEDUP_WG) void k_dedup_resolve(DedupSlot *__restric
         verdict[i] = (uint8_t)(dup && drop ? 1 : 0);
     }
     dedup_flush(n_kept, n_dup, n_nokey, 0, lost, 2ull, blk);
-}
-
-// k_filter_scatter for one or two tables (t1 / t2 may be NULL: no rows are copied) and the ordinals through `ord`
-__global__ __launch_bounds__(256) void k_dedup_scatter(const int64_t *__restrict__ t1, const int64_t *__restrict__ t2,
-                                                       const uint8_t *__restrict__ verdict, const int64_t *__restrict__ ord, int64_t n,
-                                                       const long long *__restrict__ bbase, int64_t *__restrict__ out1,
-                                                       int64_t *__restrict__ out2, int64_t *__restrict__ idx_out)
-{
-    __shared__ uint32_t s_w[4];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int64_t i = (int64_t)blockIdx.x * 256 + tid;
-    const bool keep = filter_keep(verdict, i, n);
-    const unsigned long long m = __ballot(keep);
-    if (lane == 0) s_w[wid] = (uint32_t)__popcll(m);
-    __syncthreads();
-    uint32_t wpre = 0;
-#pragma unroll
-    for (int q = 0; q < 4; q++)
-        if (q < wid) wpre += s_w[q];
-    if (!keep) return;
-    const int64_t r = bbase[blockIdx.x] + wpre + __popcll(m & ((1ull << lane) - 1ull));
-    if (t1) pair_row_copy(t1, i, out1, r);
-    if (t2) pair_row_copy(t2, i, out2, r);
-    if (idx_out) idx_out[r] = ord ? ord[i] : i;
 }
 
 // every key of the old table is in it once: the claim always meets an empty slot of the larger table, or the probe gives up

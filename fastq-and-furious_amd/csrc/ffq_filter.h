@@ -2,7 +2,7 @@
 // quality, share of unqualified bases, expected errors, complexity.  The rule, the order of its tests and what the eight
 // counts mean are stated in include/ffq.h.  Everything is an integer; rows are independent.
 //
-// Shape: the two launches of ffq_rows.h that judge, and the compaction of the length filter (ffq_kernels.h) behind them.
+// Shape: the two launches of ffq_rows.h that judge, and the compaction (ffq_compact.h) behind them.
 //   k_filter_rows     the short rows' shape, 32 rows per workgroup and step.  The length test comes first and needs the row's
 //                     positions only: a row that fails it has none of its bytes loaded.  A row of up to FILTER_TILE bases is
 //                     held in registers the way k_stats_rows holds it (lane gl: dwords gl, gl + 8, ... of either line, every
@@ -10,8 +10,7 @@
 //                     before anything counts --, the five quantities are per-lane partial sums added over the group with DPP
 //                     moves.  Longer rows go onto the list.
 //   k_filter_long     a wave per listed row, 256 bytes of either line per step, 64-bit sums.
-//   k_filter_count, k_filter_scatter    k_sel_count and k_sel_scatter with "kept" read from the verdict bytes; the scan
-//                     between them is the length filter's own (launch_scan_u32).
+//   The compaction behind them is ffq_compact.h's, with "kept" read from the verdict bytes (KeepVerdict).
 // Both judging kernels write ONE BYTE per row, the verdict: bits 0..2 the rule that dropped the row (0: kept), bit 7 "not
 // judged by content".  The counts are summed in registers, over the wave, over the workgroup's waves through LDS, and go out
 // with one set of atomics per workgroup.
@@ -247,43 +246,6 @@ __global__ __launch_bounds__(FILTER_WG) void k_filter_long(const uint8_t *__rest
         }
     }
     cnt.add_to<FILTER_WG>(blk);
-}
-
-// ---- compaction: k_sel_count / k_sel_scatter (ffq_kernels.h) with "kept" read from the verdict bytes ----------------------------
-__device__ __forceinline__ bool filter_keep(const uint8_t *__restrict__ verdict, int64_t i, int64_t n)
-{
-    return i < n && (verdict[i] & FILTER_REASON) == 0;
-}
-
-__global__ __launch_bounds__(256) void k_filter_count(const uint8_t *__restrict__ verdict, int64_t n, unsigned int *__restrict__ bcnt)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int c = __syncthreads_count(filter_keep(verdict, i, n) ? 1 : 0);
-    if (threadIdx.x == 0) bcnt[blockIdx.x] = (unsigned int)c;
-}
-
-__global__ __launch_bounds__(256) void k_filter_scatter(const int64_t *__restrict__ table, const uint8_t *__restrict__ verdict, int64_t n,
-                                                        const long long *__restrict__ bbase, int64_t *__restrict__ out,
-                                                        int64_t *__restrict__ idx_out)
-{
-    __shared__ uint32_t s_w[4];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int64_t i = (int64_t)blockIdx.x * 256 + tid;
-    const bool keep = filter_keep(verdict, i, n);
-    const unsigned long long m = __ballot(keep);
-    if (lane == 0) s_w[wid] = (uint32_t)__popcll(m);
-    __syncthreads();
-    uint32_t wpre = 0;
-#pragma unroll
-    for (int q = 0; q < 4; q++)
-        if (q < wid) wpre += s_w[q];
-    if (!keep) return;
-    const int64_t r = bbase[blockIdx.x] + wpre + __popcll(m & ((1ull << lane) - 1ull));
-    const longlong2 *src = reinterpret_cast<const longlong2 *>(table + i * 6);
-    longlong2 *dst = reinterpret_cast<longlong2 *>(out + r * 6);
-    const longlong2 a = src[0], b = src[1], c = src[2];
-    dst[0] = a; dst[1] = b; dst[2] = c;
-    if (idx_out) idx_out[r] = i;
 }
 
 }  // namespace ffq

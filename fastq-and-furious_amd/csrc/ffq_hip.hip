@@ -13,6 +13,7 @@
 #include "ffq_adapter.h"
 #include "ffq_stats.h"
 #include "ffq_filter.h"
+#include "ffq_compact.h"
 #include "ffq_pair.h"
 #include "ffq_overlap.h"
 #include "ffq_render.h"
@@ -141,6 +142,9 @@ struct RankMem {
     DevBuf<uint32_t> succ, S[2], C[2], D, root;
 };
 
+// words of a context's counter block: what the largest table call needs (ffq_tables.h asserts it per block type)
+constexpr int CALL_BLK_WORDS = 32;
+
 struct ffq_ctx {
     ScanState pend;                      // the scan enqueued by ffq_scan_submit, if any
     ffq_ctx *owner = nullptr;            // the context whose stream this one uses (itself unless created shared)
@@ -196,23 +200,13 @@ struct ffq_ctx {
     PinBuf<int64_t> h_word;             //   and their pinned mirror
     DevBuf<int64_t> d_cut;              // ffq_table_cut: 6 words
     PinBuf<int64_t> h_cut;
-    DevBuf<RowsBlock> d_rows;           // the table passes of ffq_rows.h: a call's counters and their pinned mirror
-    PinBuf<RowsBlock> h_rows;
-    DevBuf<int64_t> rows_list;          //   rows left to the wave-per-row launch
+    Mirror<uint64_t> blk;               // the table calls: a call's counters and their pinned mirror, CALL_BLK_WORDS words
+                                        //   (ffq_tables.h: call_blk_begin / call_blk_end)
+    DevBuf<int64_t> rows_list;          // the table passes of ffq_rows.h: rows left to the wave-per-row launch
     PinBuf<uint64_t> h_stats;           // ffq_table_stats: the head words handed back
-    DevBuf<FilterBlock> d_filter;       // ffq_table_select_reads: the call's counters and their pinned mirror
-    PinBuf<FilterBlock> h_filter;
-    DevBuf<uint8_t> filter_verdict;     //   a verdict byte per row
-    DevBuf<uint8_t> filter_verdict2;    //   ... and per row of the second mate (ffq_table_select_pairs; h_filter holds two blocks)
-    DevBuf<PairBlock> d_pair;           // ffq_table_select_pairs: the call's pair counts and their pinned mirror
-    PinBuf<PairBlock> h_pair;
-    DevBuf<PairNamesBlock> d_names;     // ffq_table_pair_names: the call's counters and their pinned mirror
-    PinBuf<PairNamesBlock> h_names;
-    DevBuf<OverlapBlock> d_overlap;     // ffq_table_pair_overlap: the call's counts and their pinned mirror
-    PinBuf<OverlapBlock> h_overlap;
-    DevBuf<RenderBlock> d_render;       // ffq_table_render_fastq: the call's counters and their pinned mirror
-    PinBuf<RenderBlock> h_render;
-    DevBuf<int64_t> render_list;        //   (row, place in the output) of the rows left to the wave-per-row launch
+    DevBuf<uint8_t> filter_verdict;     // ffq_table_select_reads: a verdict byte per row
+    DevBuf<uint8_t> filter_verdict2;    //   ... and per row of the second mate (ffq_table_select_pairs)
+    DevBuf<int64_t> render_list;        // ffq_table_render_fastq: (row, place in the output) of the rows left to the wave-per-row launch
     DevBuf<FaHdr> fa_hdr;               // FASTA scan: starts, the last start
     // staging for the host-buffer entry points
     DevBuf<uint8_t> stage_d;
@@ -235,8 +229,6 @@ struct ffq_ctx {
     cpu_set_t near_cpus;           // the CPUs next to the GPU (ctx_near), near_ok: known
     int near_ok = -1;
     void *stream_cache = nullptr;  // buffers of the last closed ffq_stream (ffq_stream.h), reused by the next one
-    DevBuf<MergeBlock> d_merge;    // ffq_table_pair_merge: the call's counts and their pinned mirror
-    PinBuf<MergeBlock> h_merge;
 };
 
 extern "C" int ffq_abi_version(void) { return FFQ_ABI_VERSION; }
@@ -296,25 +288,13 @@ static int ctx_create_impl(int device, ffq_ctx *share, ffq_ctx **out)
                                : hipEventCreateWithFlags(&c->ev[i], hipEventDisableSystemFence);
     if (e == hipSuccess) e = c->ctl.grow(1);
     if (e == hipSuccess) e = c->dres.grow(1);
+    if (e == hipSuccess) e = c->col_res.grow(1);
     if (e == hipSuccess) e = c->d_L.grow(1);
     if (e == hipSuccess) e = c->d_word.grow(2);
     if (e == hipSuccess) e = c->h_word.grow(2);
     if (e == hipSuccess) e = c->d_cut.grow(6);
-    if (e == hipSuccess) e = c->d_rows.grow(1);
-    if (e == hipSuccess) e = c->h_rows.grow(1);
+    if (e == hipSuccess) e = c->blk.grow(CALL_BLK_WORDS);
     if (e == hipSuccess) e = c->h_stats.grow(STATS_HEAD);
-    if (e == hipSuccess) e = c->d_filter.grow(1);
-    if (e == hipSuccess) e = c->h_filter.grow(2);
-    if (e == hipSuccess) e = c->d_pair.grow(1);
-    if (e == hipSuccess) e = c->h_pair.grow(1);
-    if (e == hipSuccess) e = c->d_names.grow(1);
-    if (e == hipSuccess) e = c->h_names.grow(1);
-    if (e == hipSuccess) e = c->d_overlap.grow(1);
-    if (e == hipSuccess) e = c->h_overlap.grow(1);
-    if (e == hipSuccess) e = c->d_render.grow(1);
-    if (e == hipSuccess) e = c->h_render.grow(1);
-    if (e == hipSuccess) e = c->d_merge.grow(1);
-    if (e == hipSuccess) e = c->h_merge.grow(1);
     if (e == hipSuccess) e = c->fa_hdr.grow(1);
     if (e == hipSuccess) e = c->h_cut.grow(6);
     if (e == hipSuccess) e = c->h_L.grow(1);
@@ -1740,42 +1720,6 @@ extern "C" int ffq_scan_host(ffq_ctx *c, const uint8_t *h_buf, int64_t n_bytes, 
     return rc2 ? rc2 : rc;
 }
 
-extern "C" int ffq_entrypos(ffq_ctx *c, const uint8_t *h_buf, int64_t len, int64_t offset, int64_t *pos,
-                            int *status)
-{
-    mark_other(c);
-    if (!c || !pos || !status) return fail(FFQ_E_ARG, "ffq_entrypos: NULL argument");
-    int64_t row[6];
-    ffq_scan_result r;
-    int rc = ffq_scan_host(c, h_buf, len, 0, offset, 0, 0, 0, 0, row, 1, nullptr, 0, nullptr, &r);
-    if (rc != FFQ_OK && rc != FFQ_E_TABLE_FULL) return rc;
-    if (r.n_records >= 1) {
-        for (int i = 0; i < 6; i++) pos[i] = row[i];
-        *status = FFQ_COMPLETE;
-    } else {
-        for (int i = 0; i < 6; i++) pos[i] = r.last_pos[i];
-        *status = r.last_status;
-    }
-    g_err.clear();
-    return FFQ_OK;
-}
-
-extern "C" int ffq_table_lower_bound(ffq_ctx *c, const int64_t *d_table, int64_t n_rows, int col,
-                                     int64_t value, int64_t *idx)
-{
-    mark_other(c);
-    if (!c || !idx || n_rows < 0 || col < 0 || col > 5 || (n_rows > 0 && !d_table))
-        return fail(FFQ_E_ARG, "ffq_table_lower_bound: bad argument");
-    HIPCHK(hipSetDevice(c->device));
-    int64_t *slot = c->h_word, *dslot = c->d_word;
-    hipLaunchKernelGGL(k_table_lower_bound, dim3(1), dim3(64), 0, c->stream, d_table, n_rows, col, value, dslot);
-    HIPCHK(hipMemcpyAsync(slot, dslot, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));
-    *idx = *slot;
-    return FFQ_OK;
-}
-
 // ---- FASTA (ffq_fasta.h) --------------------------------------------------------------------
 extern "C" int ffq_scan_fasta_device(ffq_ctx *c, const uint8_t *d_buf, int64_t n_bytes, int sentinel,
                                      int64_t offset, int64_t add, int64_t *d_table, int64_t table_cap,
@@ -1865,795 +1809,6 @@ extern "C" int ffq_scan_fasta_host(ffq_ctx *c, const uint8_t *h_buf, int64_t n_b
     const int64_t rows = std::min<int64_t>(res->n_records, table_cap);
     if (rows > 0) HIPCHK(hipMemcpy(h_table, c->tab_d, (size_t)rows * 48, hipMemcpyDeviceToHost));
     return rc;
-}
-
-extern "C" int ffq_table_cut(ffq_ctx *c, const int64_t *d_table, int64_t n_rows, int64_t lo, int64_t hi,
-                             int64_t out[6])
-{
-    mark_other(c);
-    if (!c || !out || n_rows < 0 || (n_rows > 0 && !d_table)) return fail(FFQ_E_ARG, "ffq_table_cut: bad argument");
-    HIPCHK(hipSetDevice(c->device));
-    hipLaunchKernelGGL(k_table_cut, dim3(1), dim3(64), 0, c->stream, d_table, n_rows, lo, hi, c->d_cut);
-    HIPCHK(hipMemcpyAsync(c->h_cut, c->d_cut, 6 * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));
-    for (int i = 0; i < 6; i++) out[i] = c->h_cut[i];
-    return FFQ_OK;
-}
-
-static int table_select(ffq_ctx *c, const int64_t *d_table, int64_t n_rows, int64_t min_len, int64_t max_len, int64_t *d_out,
-                        int64_t *d_idx, int64_t *n_out);
-
-extern "C" int ffq_table_select_seqlen(ffq_ctx *c, const int64_t *d_table, int64_t n_rows, int64_t min_len,
-                                       int64_t max_len, int64_t *d_out, int64_t *n_out)
-{
-    return table_select(c, d_table, n_rows, min_len, max_len, d_out, nullptr, n_out);
-}
-
-extern "C" int ffq_table_select_seqlen_idx(ffq_ctx *c, const int64_t *d_table, int64_t n_rows, int64_t min_len,
-                                           int64_t max_len, int64_t *d_out, int64_t *d_idx, int64_t *n_out)
-{
-    return table_select(c, d_table, n_rows, min_len, max_len, d_out, d_idx, n_out);
-}
-
-// (d_idx, optional: the ordinal of every kept row -- the stream front end's push-down, ffq_stream_set_filter)
-static int table_select(ffq_ctx *c, const int64_t *d_table, int64_t n_rows, int64_t min_len, int64_t max_len, int64_t *d_out,
-                        int64_t *d_idx, int64_t *n_out)
-{
-    mark_other(c);
-    if (!c || !n_out || n_rows < 0 || (n_rows > 0 && (!d_table || !d_out)))
-        return fail(FFQ_E_ARG, "ffq_table_select_seqlen: bad argument");
-    if (d_table == d_out && n_rows > 0) return fail(FFQ_E_ARG, "ffq_table_select_seqlen: d_out must not be d_table");
-    if (((reinterpret_cast<uintptr_t>(d_table) | reinterpret_cast<uintptr_t>(d_out)) & 15) != 0)
-        return fail(FFQ_E_ARG, "ffq_table_select_seqlen: tables must be 16-byte aligned");
-    HIPCHK(hipSetDevice(c->device));
-    *n_out = 0;
-    if (n_rows == 0) return FFQ_OK;
-    const int64_t nblk = (n_rows + 255) / 256;
-    int rc = grow_dev(c, c->sel_cnt, nblk);
-    if (!rc) rc = grow_dev(c, c->sel_base, nblk);
-    if (rc) return rc;
-    hipStream_t st = c->stream;
-    hipLaunchKernelGGL(k_sel_count, dim3((unsigned)nblk), dim3(256), 0, st, d_table, n_rows, min_len, max_len,
-                       c->sel_cnt);
-    if ((rc = launch_scan_u32(c, st, (const unsigned int *)c->sel_cnt, nblk, c->sel_base, (long long *)c->d_word.p))) return rc;
-    hipLaunchKernelGGL(k_sel_scatter, dim3((unsigned)nblk), dim3(256), 0, st, d_table, n_rows, min_len, max_len,
-                       (const long long *)c->sel_base, d_out, d_idx);
-    HIPCHK(hipMemcpyAsync(c->h_word, c->d_word, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-    *n_out = c->h_word[0];
-    return FFQ_OK;
-}
-
-// ---- column selection ----------------------------------------------------------------------
-extern "C" int ffq_table_gather_column(ffq_ctx *c, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
-                                       const int64_t *d_table, int64_t n_rows, int col_begin, int begin_shift,
-                                       int col_end, int value_add, int8_t *d_out, int64_t out_cap, int64_t *d_off,
-                                       int64_t *n_out_bytes)
-{
-    mark_other(c);
-    if (!c || !n_out_bytes || n_rows < 0 || n_bytes < 0 || out_cap < 0 || !d_off || (n_rows > 0 && !d_table))
-        return fail(FFQ_E_ARG, "ffq_table_gather_column: bad argument");
-    if (out_cap > 0 && (!d_out || (n_bytes > 0 && !d_buf)))
-        return fail(FFQ_E_ARG, "ffq_table_gather_column: no output, or no buffer, to copy %lld bytes", (long long)out_cap);
-    if (col_begin < 0 || col_begin > 5 || col_end < 0 || col_end > 5)
-        return fail(FFQ_E_ARG, "ffq_table_gather_column: columns are 0..5");
-    if (c->pend.active) return fail(FFQ_E_ARG, "ffq_table_gather_column: a scan is pending on this context");
-    HIPCHK(hipSetDevice(c->device));
-    *n_out_bytes = 0;
-    hipStream_t st = c->stream;
-    if (n_rows == 0) {
-        HIPCHK(hipMemsetAsync(d_off, 0, sizeof(int64_t), st));
-        HIPCHK(hipStreamSynchronize(st));
-        return FFQ_OK;
-    }
-    const int64_t nblk = (n_rows + 255) / 256;
-    int rc = grow_dev(c, c->col_sum, nblk);
-    if (!rc) {
-        const hipError_t e = c->col_res.grow(1);
-        if (e != hipSuccess) rc = fail(FFQ_E_NOMEM, "hipMalloc failed: %s", hipGetErrorString(e));
-    }
-    // the copy kernel's scratch: a start per row, the directory of the output stream
-    const int64_t nqb = (out_cap + DQ_BLK - 1) / DQ_BLK + 1;
-    if (!rc) rc = reserve_qdir(c, nqb);
-    if (!rc) rc = reserve_p4s(c, n_rows);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_col_sum, dim3((unsigned)nblk), dim3(256), 0, st, d_table, n_rows, col_begin, begin_shift, col_end,
-                       n_bytes, sentinel ? 1 : 0, add, c->col_sum);
-    if ((rc = launch_scan_i64v(c, st, c->col_sum, nblk, n_rows, c->col_res))) return rc;
-    hipLaunchKernelGGL(k_col_offsets, dim3((unsigned)nblk), dim3(256), 0, st, d_table, n_rows, col_begin, begin_shift,
-                       col_end, n_bytes, sentinel ? 1 : 0, add, (const long long *)c->col_sum, (const DevRes *)c->col_res, d_off,
-                       c->p4s, c->qdir, c->qdir.cap);
-    if (out_cap > 0)
-        hipLaunchKernelGGL(k_decode_stream, dim3((unsigned)nqb), dim3(256), 0, st, d_buf, n_bytes, sentinel ? 1 : 0,
-                           (const int64_t *)c->p4s, (const int64_t *)d_off, (const int64_t *)c->qdir,
-                           (const DevRes *)c->col_res, n_rows, add, value_add, d_out, out_cap);
-    HIPCHK(hipMemcpyAsync(c->h_word, &c->col_res->n_qual_bytes, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-    *n_out_bytes = c->h_word[0];
-    if (*n_out_bytes > out_cap)
-        return fail(FFQ_E_TABLE_FULL, "output holds %lld bytes, the column has %lld", (long long)out_cap,
-                    (long long)*n_out_bytes);
-    return FFQ_OK;
-}
-
-// ---- the table passes on csrc/ffq_rows.h: quality trim, adapter trim, statistics (ffq_trim.h, ffq_adapter.h, ffq_stats.h) ----
-// Workgroups of a pass's launches, each capped: they stride over what there is.  The short rows' launch has WG / ROWS_G rows
-// per workgroup and step; the long rows' launches have a wave per row, and as the list's length is known on the device only,
-// they are sized by the table.
-constexpr int EDIT_GRID_SHORT = 2048, EDIT_GRID_LONG = 1024;                       // the two trims
-constexpr int STATS_GRID_SHORT = 512, STATS_GRID_CHECK = 512, STATS_GRID_COUNT = 128;   // (two workgroups per CU: their LDS); x tiles
-
-static unsigned rows_grid(int64_t n_rows, int per_wg, int cap) { return (unsigned)std::min<int64_t>((n_rows + per_wg - 1) / per_wg, cap); }
-
-// What the passes check and set up alike.  args_ok: the caller's own pointers; d_dst: what the pass writes on the device.  With
-// rows, the long list is grown (before anything is enqueued: growing waits for the stream) and the call's counters are cleared.
-// The list and the counters are the context's, not a pass's: calls on a context follow one another.
-static int rows_begin(ffq_ctx *c, const char *who, bool args_ok, const uint8_t *d_buf, int64_t n_bytes, const int64_t *d_table,
-                      int64_t n_rows, const void *d_dst)
-{
-    if (!c || !args_ok || n_rows < 0 || n_bytes < 0 || (n_bytes > 0 && !d_buf) || (n_rows > 0 && (!d_table || !d_dst)))
-        return fail(FFQ_E_ARG, "%s: bad argument", who);
-    if (((reinterpret_cast<uintptr_t>(d_table) | reinterpret_cast<uintptr_t>(d_dst)) & 15) != 0)
-        return fail(FFQ_E_ARG, "%s: the table and what is written must be 16-byte aligned", who);
-    if (c->pend.active) return fail(FFQ_E_ARG, "%s: a scan is pending on this context", who);
-    HIPCHK(hipSetDevice(c->device));
-    if (n_rows == 0) return FFQ_OK;
-    const int rc = grow_dev(c, c->rows_list, n_rows);
-    if (rc) return rc;
-    HIPCHK(hipMemsetAsync(c->d_rows, 0, sizeof(RowsBlock), c->stream));
-    return FFQ_OK;
-}
-
-// the counters of an editing pass back: the call's one host wait
-static int rows_end(ffq_ctx *c, int64_t stats[3])
-{
-    HIPCHK(hipMemcpyAsync(c->h_rows, c->d_rows, sizeof(RowsBlock), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));
-    stats[0] = (int64_t)c->h_rows->changed; stats[1] = (int64_t)c->h_rows->removed; stats[2] = (int64_t)c->h_rows->skipped;
-    return FFQ_OK;
-}
-
-// parameters of a quality trim and of a statistics call, checked: for the table calls and for the stream's setters
-static int trim_arg(const char *who, int qual_base, int cutoff_front, int cutoff_back)
-{
-    if (cutoff_front < 0 || cutoff_front > 127 || cutoff_back < 0 || cutoff_back > 127) return fail(FFQ_E_ARG, "%s: cutoffs are 0..127", who);
-    if (qual_base < 0 || qual_base > 255) return fail(FFQ_E_ARG, "%s: qual_base is 0..255", who);
-    return FFQ_OK;
-}
-
-static int stats_arg(const char *who, int qual_base, int max_cycles)
-{
-    if (max_cycles < 1 || max_cycles > FFQ_STATS_MAX_CYCLES) return fail(FFQ_E_ARG, "%s: max_cycles is 1..%d", who, FFQ_STATS_MAX_CYCLES);
-    if (qual_base < 0 || qual_base > 255) return fail(FFQ_E_ARG, "%s: qual_base is 0..255", who);
-    return FFQ_OK;
-}
-
-extern "C" int ffq_table_trim_quality(ffq_ctx *c, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
-                                      const int64_t *d_table, int64_t n_rows, int qual_base, int cutoff_front,
-                                      int cutoff_back, int64_t *d_out, int64_t stats[3])
-{
-    mark_other(c);
-    int rc = trim_arg("ffq_table_trim_quality", qual_base, cutoff_front, cutoff_back);
-    if (!rc) rc = rows_begin(c, "ffq_table_trim_quality", stats != nullptr, d_buf, n_bytes, d_table, n_rows, d_out);
-    if (rc) return rc;
-    stats[0] = stats[1] = stats[2] = 0;
-    if (n_rows == 0) return FFQ_OK;
-    hipStream_t st = c->stream;
-    hipLaunchKernelGGL(k_trim_rows, dim3(rows_grid(n_rows, TRIM_WG / ROWS_G, EDIT_GRID_SHORT)), dim3(TRIM_WG), 0, st, d_buf, n_bytes,
-                       sentinel ? 1 : 0, add, d_table, n_rows, qual_base, cutoff_front, cutoff_back, d_out, c->rows_list, c->d_rows);
-    hipLaunchKernelGGL(k_trim_long, dim3(rows_grid(n_rows, TRIM_WG / 64, EDIT_GRID_LONG)), dim3(TRIM_WG), 0, st, d_buf, n_bytes,
-                       sentinel ? 1 : 0, add, d_table, qual_base, cutoff_front, cutoff_back, d_out, (const int64_t *)c->rows_list,
-                       c->d_rows);
-    return rows_end(c, stats);
-}
-
-// parameters of an adapter call, checked; the adapter's bytes and its wildcard mask as the kernels take them
-static int adapter_arg(const char *who, const uint8_t *adapter, int adapter_len, int err_permille, int min_overlap, AdapterArg *ad)
-{
-    if (!adapter || adapter_len < 1 || adapter_len > ADAPTER_MAX) return fail(FFQ_E_ARG, "%s: the adapter has 1..%d bytes", who, ADAPTER_MAX);
-    if (min_overlap < 1 || min_overlap > adapter_len) return fail(FFQ_E_ARG, "%s: min_overlap is 1..adapter_len", who);
-    if (err_permille < 0 || err_permille > 1000) return fail(FFQ_E_ARG, "%s: err_permille is 0..1000", who);
-    if (ad) {
-        memset(ad, 0, sizeof *ad);
-        for (int j = 0; j < adapter_len; j++) {
-            ad->a[j >> 2] |= (uint32_t)adapter[j] << (8 * (j & 3));
-            if (adapter[j] != (uint8_t)'N') ad->k[j >> 2] |= 0xFFu << (8 * (j & 3));
-        }
-    }
-    return FFQ_OK;
-}
-
-extern "C" int ffq_table_trim_adapter(ffq_ctx *c, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
-                                      const int64_t *d_table, int64_t n_rows, const uint8_t *adapter, int adapter_len,
-                                      int err_permille, int min_overlap, int64_t *d_out, int64_t stats[3])
-{
-    mark_other(c);
-    AdapterArg ad;
-    int rc = adapter_arg("ffq_table_trim_adapter", adapter, adapter_len, err_permille, min_overlap, &ad);
-    if (!rc) rc = rows_begin(c, "ffq_table_trim_adapter", stats != nullptr, d_buf, n_bytes, d_table, n_rows, d_out);
-    if (rc) return rc;
-    stats[0] = stats[1] = stats[2] = 0;
-    if (n_rows == 0) return FFQ_OK;
-    hipStream_t st = c->stream;
-    hipLaunchKernelGGL(k_adapter_rows, dim3(rows_grid(n_rows, ADAPTER_WG / ROWS_G, EDIT_GRID_SHORT)), dim3(ADAPTER_WG), 0, st, d_buf,
-                       n_bytes, sentinel ? 1 : 0, add, d_table, n_rows, ad, adapter_len, err_permille, min_overlap, d_out,
-                       c->rows_list, c->d_rows);
-    hipLaunchKernelGGL(k_adapter_long, dim3(rows_grid(n_rows, ADAPTER_WG / 64, EDIT_GRID_LONG)), dim3(ADAPTER_WG), 0, st, d_buf,
-                       n_bytes, sentinel ? 1 : 0, add, d_table, ad, adapter_len, err_permille, min_overlap, d_out,
-                       (const int64_t *)c->rows_list, c->d_rows);
-    return rows_end(c, stats);
-}
-
-static_assert(STATS_QBINS == FFQ_STATS_QBINS && STATS_GCBINS == FFQ_STATS_GCBINS && STATS_HEAD == FFQ_STATS_HEAD &&
-              STATS_MAX_CYCLES == FFQ_STATS_MAX_CYCLES && stats_words(150) == FFQ_STATS_WORDS(150), "include/ffq.h");
-
-extern "C" int ffq_table_stats(ffq_ctx *c, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
-                               const int64_t *d_table, int64_t n_rows, int qual_base, int max_cycles, int accumulate,
-                               uint64_t *d_stats, int64_t head[FFQ_STATS_HEAD])
-{
-    mark_other(c);
-    int rc = stats_arg("ffq_table_stats", qual_base, max_cycles);
-    if (!rc) rc = rows_begin(c, "ffq_table_stats", d_stats != nullptr, d_buf, n_bytes, d_table, n_rows, d_stats);
-    if (rc) return rc;
-    hipStream_t st = c->stream;
-    stats_u64 *out = reinterpret_cast<stats_u64 *>(d_stats);
-    if (!accumulate) HIPCHK(hipMemsetAsync(d_stats, 0, (size_t)stats_words(max_cycles) * 8, st));
-    if (n_rows > 0) {
-        // every workgroup of the short rows' launch flushes a whole tile at its end; the rows it left are checked and counted
-        // per read first, then per cycle tile
-        hipLaunchKernelGGL(k_stats_rows, dim3(rows_grid(n_rows, STATS_WG / STATS_G, STATS_GRID_SHORT)), dim3(STATS_WG), 0, st, d_buf,
-                           n_bytes, sentinel ? 1 : 0, add, d_table, n_rows, qual_base, max_cycles, out, c->rows_list, c->d_rows);
-        hipLaunchKernelGGL(k_stats_long_check, dim3(rows_grid(n_rows, STATS_WG / 64, STATS_GRID_CHECK)), dim3(STATS_WG), 0, st, d_buf,
-                           n_bytes, sentinel ? 1 : 0, add, d_table, qual_base, max_cycles, out, c->rows_list,
-                           (const RowsBlock *)c->d_rows);
-        const int n_tiles = (max_cycles + STATS_TILE - 1) / STATS_TILE;
-        hipLaunchKernelGGL(k_stats_long_count, dim3(rows_grid(n_rows, STATS_WG / 64, STATS_GRID_COUNT), (unsigned)n_tiles),
-                           dim3(STATS_WG), 0, st, d_buf, n_bytes, sentinel ? 1 : 0, add, d_table, qual_base, max_cycles, out,
-                           (const int64_t *)c->rows_list, (const RowsBlock *)c->d_rows);
-    }
-    HIPCHK(hipGetLastError());
-    if (head) {
-        HIPCHK(hipMemcpyAsync(c->h_stats, d_stats, STATS_HEAD * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (int i = 0; i < STATS_HEAD; i++) head[i] = (int64_t)c->h_stats[i];
-    }
-    return FFQ_OK;
-}
-
-// ---- rows kept or dropped for what is in the read (csrc/ffq_filter.h) ---------------------------
-static_assert(FILTER_COUNTS == FFQ_FILTER_COUNTS, "include/ffq.h");
-static const uint32_t g_ee_micro[STATS_QBINS] = {FFQ_EE_MICRO_VALUES};
-extern "C" const uint32_t *ffq_ee_micro_table(void) { return g_ee_micro; }
-
-// content rules checked (NULL: every rule off); *on: one of rules 2 to 6 is switched on; R: as the kernels take them
-static int content_arg(const char *who, const ffq_content_rules *r, bool *on, FilterRules *R)
-{
-    *on = false;
-    if (!r) return FFQ_OK;
-    if (r->qual_base < 0 || r->qual_base > 255) return fail(FFQ_E_ARG, "%s: qual_base is 0..255", who);
-    if (r->max_n < -1) return fail(FFQ_E_ARG, "%s: max_n is -1 (off) or a count", who);
-    if (r->min_mean_qual < 0 || r->min_mean_qual > 95) return fail(FFQ_E_ARG, "%s: min_mean_qual is 0 (off) or 1..95", who);
-    if (r->qualified_qual < 0 || r->qualified_qual > 95) return fail(FFQ_E_ARG, "%s: qualified_qual is 0..95", who);
-    if (r->max_unqualified_pct < -1 || r->max_unqualified_pct > 100) return fail(FFQ_E_ARG, "%s: max_unqualified_pct is -1 (off) or 0..100", who);
-    if (r->min_complexity_pct < 0 || r->min_complexity_pct > 100) return fail(FFQ_E_ARG, "%s: min_complexity_pct is 0 (off) or 1..100", who);
-    if (r->max_ee_micro < -1) return fail(FFQ_E_ARG, "%s: max_ee_micro is -1 (off) or a number of millionths", who);
-    *on = r->max_n >= 0 || r->min_mean_qual > 0 || r->max_unqualified_pct >= 0 || r->max_ee_micro >= 0 || r->min_complexity_pct > 0;
-    if (R) *R = FilterRules{r->qual_base, r->max_n, r->min_mean_qual, r->qualified_qual, r->max_unqualified_pct, r->min_complexity_pct,
-                            (long long)r->max_ee_micro};
-    return FFQ_OK;
-}
-
-constexpr int FILTER_GRID_SHORT = 2048, FILTER_GRID_LONG = 1024;
-
-extern "C" int ffq_table_select_reads(ffq_ctx *c, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
-                                      const int64_t *d_table, int64_t n_rows, int64_t min_len, int64_t max_len,
-                                      const ffq_content_rules *rules, int64_t *d_out, int64_t *d_idx, int64_t *n_out,
-                                      int64_t counts[FFQ_FILTER_COUNTS])
-{
-    static const char *const who = "ffq_table_select_reads";
-    mark_other(c);
-    bool on = false;
-    FilterRules R = {};
-    int rc = content_arg(who, rules, &on, &R);
-    if (rc) return rc;
-    if (!c || !n_out || !counts || n_rows < 0 || n_bytes < 0 || (n_rows > 0 && (!d_table || !d_out)))
-        return fail(FFQ_E_ARG, "%s: bad argument", who);
-    if (c->pend.active) return fail(FFQ_E_ARG, "%s: a scan is pending on this context", who);
-    for (int i = 0; i < FFQ_FILTER_COUNTS; i++) counts[i] = 0;
-    if (!on) {
-        // no content rule: the length filter as it is -- nothing reads the buffer, nothing new is launched
-        rc = table_select(c, d_table, n_rows, min_len, max_len, d_out, d_idx, n_out);
-        if (!rc) { counts[0] = *n_out; counts[1] = n_rows - *n_out; }
-        return rc;
-    }
-    if (n_bytes > 0 && !d_buf) return fail(FFQ_E_ARG, "%s: no buffer to judge the rows by", who);
-    if (d_table == d_out && n_rows > 0) return fail(FFQ_E_ARG, "%s: d_out must not be d_table", who);
-    if (((reinterpret_cast<uintptr_t>(d_table) | reinterpret_cast<uintptr_t>(d_out)) & 15) != 0)
-        return fail(FFQ_E_ARG, "%s: tables must be 16-byte aligned", who);
-    HIPCHK(hipSetDevice(c->device));
-    *n_out = 0;
-    if (n_rows == 0) return FFQ_OK;
-    const int64_t nblk = (n_rows + 255) / 256;
-    // (everything is grown before anything is enqueued: growing waits for the stream)
-    rc = grow_dev(c, c->rows_list, n_rows);
-    if (!rc) rc = grow_dev(c, c->filter_verdict, n_rows);
-    if (!rc) rc = grow_dev(c, c->sel_cnt, nblk);
-    if (!rc) rc = grow_dev(c, c->sel_base, nblk);
-    if (rc) return rc;
-    hipStream_t st = c->stream;
-    const int s = sentinel ? 1 : 0;
-    HIPCHK(hipMemsetAsync(c->d_filter, 0, sizeof(FilterBlock), st));
-    hipLaunchKernelGGL(k_filter_rows, dim3(rows_grid(n_rows, FILTER_WG / FILTER_G, FILTER_GRID_SHORT)), dim3(FILTER_WG), 0, st, d_buf,
-                       n_bytes, s, add, d_table, n_rows, min_len, max_len, R, c->filter_verdict.p, c->rows_list.p, c->d_filter.p);
-    hipLaunchKernelGGL(k_filter_long, dim3(rows_grid(n_rows, FILTER_WG / 64, FILTER_GRID_LONG)), dim3(FILTER_WG), 0, st, d_buf,
-                       n_bytes, s, add, d_table, R, c->filter_verdict.p, (const int64_t *)c->rows_list, c->d_filter.p);
-    hipLaunchKernelGGL(k_filter_count, dim3((unsigned)nblk), dim3(256), 0, st, (const uint8_t *)c->filter_verdict, n_rows, c->sel_cnt.p);
-    if ((rc = launch_scan_u32(c, st, (const unsigned int *)c->sel_cnt, nblk, c->sel_base, (long long *)c->d_word.p))) return rc;
-    hipLaunchKernelGGL(k_filter_scatter, dim3((unsigned)nblk), dim3(256), 0, st, d_table, (const uint8_t *)c->filter_verdict, n_rows,
-                       (const long long *)c->sel_base, d_out, d_idx);
-    HIPCHK(hipMemcpyAsync(c->h_filter, c->d_filter, sizeof(FilterBlock), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-    for (int i = 0; i < FFQ_FILTER_COUNTS; i++) counts[i] = (int64_t)c->h_filter->cnt[i];
-    *n_out = counts[0];
-    return FFQ_OK;
-}
-
-// ---- two tables whose rows are mates (csrc/ffq_pair.h) ------------------------------------------
-static_assert(PAIR_ANY == FFQ_PAIR_ANY && PAIR_BOTH == FFQ_PAIR_BOTH && PAIR_FIRST == FFQ_PAIR_FIRST, "include/ffq.h");
-
-constexpr int PAIR_GRID_COUNT = 1024;
-
-static bool view_ok(const ffq_table_view *m, int64_t n_rows)
-{
-    return m && m->n_bytes >= 0 && (n_rows == 0 || m->d_table) && (reinterpret_cast<uintptr_t>(m->d_table) & 15) == 0;
-}
-
-extern "C" int ffq_table_select_pairs(ffq_ctx *c, const ffq_table_view *m1, const ffq_table_view *m2, int64_t n_pairs,
-                                      const int64_t len_bounds[4], const ffq_content_rules *rules1, const ffq_content_rules *rules2,
-                                      int pair_filter, int64_t *d_out1, int64_t *d_out2, int64_t *d_idx, int64_t *n_out,
-                                      int64_t hist1[FFQ_FILTER_COUNTS], int64_t hist2[FFQ_FILTER_COUNTS], int64_t pairs[5])
-{
-    static const char *const who = "ffq_table_select_pairs";
-    mark_other(c);
-    bool on[2] = {false, false};
-    FilterRules R[2] = {};
-    int rc = content_arg(who, rules1, &on[0], &R[0]);
-    if (!rc) rc = content_arg(who, rules2, &on[1], &R[1]);
-    if (rc) return rc;
-    if (pair_filter != FFQ_PAIR_ANY && pair_filter != FFQ_PAIR_BOTH && pair_filter != FFQ_PAIR_FIRST)
-        return fail(FFQ_E_ARG, "%s: pair_filter is FFQ_PAIR_ANY, FFQ_PAIR_BOTH or FFQ_PAIR_FIRST", who);
-    if (!c || !len_bounds || !n_out || !hist1 || !hist2 || !pairs || n_pairs < 0 || !view_ok(m1, n_pairs) || !view_ok(m2, n_pairs) ||
-        (n_pairs > 0 && (!d_out1 || !d_out2)))
-        return fail(FFQ_E_ARG, "%s: bad argument", who);
-    if (((reinterpret_cast<uintptr_t>(d_out1) | reinterpret_cast<uintptr_t>(d_out2)) & 15) != 0)
-        return fail(FFQ_E_ARG, "%s: tables must be 16-byte aligned", who);
-    if (c->pend.active) return fail(FFQ_E_ARG, "%s: a scan is pending on this context", who);
-    const ffq_table_view *m[2] = {m1, m2};
-    int64_t *hist[2] = {hist1, hist2};
-    const int n_judged = pair_filter == FFQ_PAIR_FIRST ? 1 : 2;
-    for (int k = 0; k < n_judged; k++)
-        if (on[k] && m[k]->n_bytes > 0 && !m[k]->d_buf) return fail(FFQ_E_ARG, "%s: no buffer to judge the rows of mate %d by", who, k + 1);
-    if (n_pairs > 0 && (d_out1 == m1->d_table || d_out2 == m2->d_table || d_out1 == d_out2 || d_out1 == m2->d_table || d_out2 == m1->d_table))
-        return fail(FFQ_E_ARG, "%s: d_out1 and d_out2 must not be one of the tables, or each other", who);
-    for (int i = 0; i < FFQ_FILTER_COUNTS; i++) hist1[i] = hist2[i] = 0;
-    for (int i = 0; i < PAIR_COUNTS; i++) pairs[i] = 0;
-    HIPCHK(hipSetDevice(c->device));
-    *n_out = 0;
-    if (n_pairs == 0) return FFQ_OK;
-    const int64_t nblk = (n_pairs + 255) / 256;
-    // (everything is grown before anything is enqueued: growing waits for the stream)
-    rc = grow_dev(c, c->rows_list, n_pairs);
-    if (!rc) rc = grow_dev(c, c->filter_verdict, n_pairs);
-    if (!rc && n_judged == 2) rc = grow_dev(c, c->filter_verdict2, n_pairs);
-    if (!rc) rc = grow_dev(c, c->sel_cnt, nblk);
-    if (!rc) rc = grow_dev(c, c->sel_base, nblk);
-    if (rc) return rc;
-    hipStream_t st = c->stream;
-    uint8_t *verdict[2] = {c->filter_verdict.p, n_judged == 2 ? c->filter_verdict2.p : nullptr};
-    // the judging, once per mate: the list of long rows and the counters are the call's, cleared in front of each mate
-    for (int k = 0; k < n_judged; k++) {
-        const ffq_table_view *v = m[k];
-        const int s = v->sentinel ? 1 : 0;
-        const int64_t lo = len_bounds[2 * k], hi = len_bounds[2 * k + 1];
-        HIPCHK(hipMemsetAsync(c->d_filter, 0, sizeof(FilterBlock), st));
-        if (on[k]) {
-            hipLaunchKernelGGL(k_filter_rows, dim3(rows_grid(n_pairs, FILTER_WG / FILTER_G, FILTER_GRID_SHORT)), dim3(FILTER_WG), 0, st,
-                               v->d_buf, v->n_bytes, s, v->add, v->d_table, n_pairs, lo, hi, R[k], verdict[k], c->rows_list.p, c->d_filter.p);
-            hipLaunchKernelGGL(k_filter_long, dim3(rows_grid(n_pairs, FILTER_WG / 64, FILTER_GRID_LONG)), dim3(FILTER_WG), 0, st,
-                               v->d_buf, v->n_bytes, s, v->add, v->d_table, R[k], verdict[k], (const int64_t *)c->rows_list, c->d_filter.p);
-        } else {
-            hipLaunchKernelGGL(k_pair_len, dim3(rows_grid(n_pairs, 256, FILTER_GRID_SHORT)), dim3(256), 0, st, v->d_table, n_pairs, lo, hi,
-                               verdict[k], c->d_filter.p);
-        }
-        HIPCHK(hipMemcpyAsync(c->h_filter.p + k, c->d_filter, sizeof(FilterBlock), hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(hipMemsetAsync(c->d_pair, 0, sizeof(PairBlock), st));
-    hipLaunchKernelGGL(k_pair_count, dim3((unsigned)std::min<int64_t>(nblk, PAIR_GRID_COUNT)), dim3(256), 0, st, (const uint8_t *)verdict[0],
-                       (const uint8_t *)verdict[1], n_pairs, nblk, pair_filter, c->sel_cnt.p, c->d_pair.p);
-    if ((rc = launch_scan_u32(c, st, (const unsigned int *)c->sel_cnt, nblk, c->sel_base, (long long *)c->d_word.p))) return rc;
-    hipLaunchKernelGGL(k_pair_scatter, dim3((unsigned)nblk), dim3(256), 0, st, m1->d_table, m2->d_table, (const uint8_t *)verdict[0],
-                       (const uint8_t *)verdict[1], n_pairs, pair_filter, (const long long *)c->sel_base, d_out1, d_out2, d_idx);
-    HIPCHK(hipMemcpyAsync(c->h_pair, c->d_pair, sizeof(PairBlock), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-    for (int k = 0; k < n_judged; k++)
-        for (int i = 0; i < FFQ_FILTER_COUNTS; i++) hist[k][i] = (int64_t)c->h_filter.p[k].cnt[i];
-    for (int i = 0; i < PAIR_COUNTS; i++) pairs[i] = (int64_t)c->h_pair->cnt[i];
-    *n_out = pairs[0];
-    return FFQ_OK;
-}
-
-extern "C" int ffq_table_pair_names(ffq_ctx *c, const ffq_table_view *m1, const ffq_table_view *m2, int64_t n_pairs, int64_t out[4])
-{
-    static const char *const who = "ffq_table_pair_names";
-    mark_other(c);
-    if (!c || !out || n_pairs < 0 || !view_ok(m1, n_pairs) || !view_ok(m2, n_pairs)) return fail(FFQ_E_ARG, "%s: bad argument", who);
-    if ((m1->n_bytes > 0 && !m1->d_buf) || (m2->n_bytes > 0 && !m2->d_buf)) return fail(FFQ_E_ARG, "%s: no buffer to read the headers from", who);
-    if (c->pend.active) return fail(FFQ_E_ARG, "%s: a scan is pending on this context", who);
-    HIPCHK(hipSetDevice(c->device));
-    out[0] = out[1] = out[2] = 0; out[3] = -1;
-    if (n_pairs == 0) return FFQ_OK;
-    hipStream_t st = c->stream;
-    *c->h_names.p = PairNamesBlock{0, 0, 0, (unsigned long long)n_pairs};
-    HIPCHK(hipMemcpyAsync(c->d_names, c->h_names, sizeof(PairNamesBlock), hipMemcpyHostToDevice, st));
-    const PairSide A = {m1->d_buf, m1->n_bytes, m1->sentinel ? 1 : 0, m1->add, m1->d_table};
-    const PairSide B = {m2->d_buf, m2->n_bytes, m2->sentinel ? 1 : 0, m2->add, m2->d_table};
-    hipLaunchKernelGGL(k_pair_names, dim3(rows_grid(n_pairs, PAIR_NAMES_WG / ROWS_G, EDIT_GRID_SHORT)), dim3(PAIR_NAMES_WG), 0, st, A, B,
-                       n_pairs, c->d_names.p);
-    HIPCHK(hipMemcpyAsync(c->h_names, c->d_names, sizeof(PairNamesBlock), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-    out[0] = (int64_t)c->h_names->equal; out[1] = (int64_t)c->h_names->different; out[2] = (int64_t)c->h_names->not_compared;
-    out[3] = c->h_names->different ? (int64_t)c->h_names->first : -1;
-    return FFQ_OK;
-}
-
-// ---- the overlap of the mates of a pair (csrc/ffq_overlap.h) -------------------------------------
-static_assert(OVL_MAX_LEN == FFQ_OVERLAP_MAX_LEN && OVERLAP_HIST == FFQ_OVERLAP_HIST_WORDS && OVERLAP_COUNTS == FFQ_OVERLAP_COUNTS,
-              "include/ffq.h");
-
-// the rules of an overlap call, checked: for the table call and for ffq_pair_set_overlap
-static int overlap_arg(const char *who, const ffq_overlap_rules *r)
-{
-    if (!r) return fail(FFQ_E_ARG, "%s: no rules", who);
-    if (r->min_overlap < 1 || r->min_overlap > FFQ_OVERLAP_MAX_LEN) return fail(FFQ_E_ARG, "%s: min_overlap is 1..%d", who, FFQ_OVERLAP_MAX_LEN);
-    if (r->max_diff < 0 || r->max_diff > FFQ_OVERLAP_MAX_LEN) return fail(FFQ_E_ARG, "%s: max_diff is 0..%d", who, FFQ_OVERLAP_MAX_LEN);
-    if (r->diff_permille < 0 || r->diff_permille > 1000) return fail(FFQ_E_ARG, "%s: diff_permille is 0..1000", who);
-    if (r->trim != 0 && r->trim != 1) return fail(FFQ_E_ARG, "%s: trim is 0 or 1", who);
-    return FFQ_OK;
-}
-
-extern "C" int ffq_table_pair_overlap(ffq_ctx *c, const ffq_table_view *m1, const ffq_table_view *m2, int64_t n_pairs,
-                                      const ffq_overlap_rules *rules, int64_t *d_out1, int64_t *d_out2, int32_t *d_insert,
-                                      uint64_t *d_hist, int accumulate, int64_t counts[FFQ_OVERLAP_COUNTS])
-{
-    static const char *const who = "ffq_table_pair_overlap";
-    mark_other(c);
-    int rc = overlap_arg(who, rules);
-    if (rc) return rc;
-    if (!c || !counts || n_pairs < 0 || !view_ok(m1, n_pairs) || !view_ok(m2, n_pairs) || (n_pairs > 0 && (!d_out1 || !d_out2)))
-        return fail(FFQ_E_ARG, "%s: bad argument", who);
-    if (((reinterpret_cast<uintptr_t>(d_out1) | reinterpret_cast<uintptr_t>(d_out2)) & 15) != 0)
-        return fail(FFQ_E_ARG, "%s: tables must be 16-byte aligned", who);
-    if ((reinterpret_cast<uintptr_t>(d_hist) & 7) != 0 || (reinterpret_cast<uintptr_t>(d_insert) & 3) != 0)
-        return fail(FFQ_E_ARG, "%s: d_hist must be 8-byte aligned, d_insert 4-byte aligned", who);
-    if ((m1->n_bytes > 0 && !m1->d_buf) || (m2->n_bytes > 0 && !m2->d_buf)) return fail(FFQ_E_ARG, "%s: no buffer to read the sequences from", who);
-    if (c->pend.active) return fail(FFQ_E_ARG, "%s: a scan is pending on this context", who);
-    HIPCHK(hipSetDevice(c->device));
-    for (int i = 0; i < OVERLAP_COUNTS; i++) counts[i] = 0;
-    hipStream_t st = c->stream;
-    if (d_hist && !accumulate) HIPCHK(hipMemsetAsync(d_hist, 0, (size_t)OVERLAP_HIST * 8, st));
-    if (n_pairs == 0) {
-        HIPCHK(hipStreamSynchronize(st));
-        return FFQ_OK;
-    }
-    HIPCHK(hipMemsetAsync(c->d_overlap, 0, sizeof(OverlapBlock), st));
-    const PairSide A = {m1->d_buf, m1->n_bytes, m1->sentinel ? 1 : 0, m1->add, m1->d_table};
-    const PairSide B = {m2->d_buf, m2->n_bytes, m2->sentinel ? 1 : 0, m2->add, m2->d_table};
-    const OverlapRules R = {rules->min_overlap, rules->max_diff, rules->diff_permille, rules->trim};
-    hipLaunchKernelGGL(k_pair_overlap, dim3(rows_grid(n_pairs, OVERLAP_WG / ROWS_G, EDIT_GRID_SHORT)), dim3(OVERLAP_WG), 0, st, A, B, n_pairs,
-                       R, d_out1, d_out2, d_insert, reinterpret_cast<unsigned long long *>(d_hist), c->d_overlap.p);
-    HIPCHK(hipMemcpyAsync(c->h_overlap, c->d_overlap, sizeof(OverlapBlock), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-    for (int i = 0; i < OVERLAP_COUNTS; i++) counts[i] = (int64_t)c->h_overlap->cnt[i];
-    return FFQ_OK;
-}
-
-// ---- FASTQ text from (buffer, table) (csrc/ffq_render.h) ---------------------------------------
-extern "C" int ffq_table_render_fastq(ffq_ctx *c, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
-                                      const int64_t *d_table, int64_t n_rows, uint8_t *d_out, int64_t out_cap,
-                                      int64_t *d_off, int64_t stats[3])
-{
-    mark_other(c);
-    if (!c || !stats || n_rows < 0 || n_bytes < 0 || out_cap < 0 || (n_bytes > 0 && !d_buf) || (n_rows > 0 && !d_table) ||
-        (out_cap > 0 && !d_out))
-        return fail(FFQ_E_ARG, "ffq_table_render_fastq: bad argument");
-    if ((reinterpret_cast<uintptr_t>(d_table) & 15) != 0 || (reinterpret_cast<uintptr_t>(d_off) & 7) != 0)
-        return fail(FFQ_E_ARG, "ffq_table_render_fastq: the table must be 16-byte aligned, the offsets 8-byte");
-    if (c->pend.active) return fail(FFQ_E_ARG, "ffq_table_render_fastq: a scan is pending on this context");
-    HIPCHK(hipSetDevice(c->device));
-    stats[0] = stats[1] = stats[2] = 0;
-    hipStream_t st = c->stream;
-    if (n_rows == 0) {
-        if (d_off) {
-            HIPCHK(hipMemsetAsync(d_off, 0, sizeof(int64_t), st));
-            HIPCHK(hipStreamSynchronize(st));
-        }
-        return FFQ_OK;
-    }
-    const int64_t nblk = (n_rows + RENDER_WG - 1) / RENDER_WG;
-    int rc = grow_dev(c, c->col_sum, nblk);
-    if (!rc) rc = grow_dev(c, c->render_list, 2 * n_rows);
-    if (!rc) {
-        const hipError_t e = c->col_res.grow(1);
-        if (e != hipSuccess) rc = fail(FFQ_E_NOMEM, "hipMalloc failed: %s", hipGetErrorString(e));
-    }
-    if (rc) return rc;
-    const int s = sentinel ? 1 : 0;
-    HIPCHK(hipMemsetAsync(c->d_render, 0, sizeof(RenderBlock), st));
-    hipLaunchKernelGGL(k_render_sum, dim3((unsigned)std::min<int64_t>(nblk, 2048)), dim3(RENDER_WG), 0, st, n_bytes, s, add,
-                       d_table, n_rows, nblk, c->col_sum, c->d_render);
-    if ((rc = launch_scan_i64v(c, st, c->col_sum, nblk, n_rows, c->col_res))) return rc;
-    hipLaunchKernelGGL(k_render_rows, dim3((unsigned)nblk), dim3(RENDER_WG), 0, st, d_buf, n_bytes, s, add, d_table, n_rows,
-                       (const long long *)c->col_sum, (const DevRes *)c->col_res, d_out, out_cap, d_off, c->render_list,
-                       c->d_render);
-    // the rows it left (above RENDER_LONG output bytes; their number is known on the device only): a wave each
-    const int64_t nblk_long = std::min<int64_t>((n_rows + 3) / 4, 1024);
-    hipLaunchKernelGGL(k_render_long, dim3((unsigned)nblk_long), dim3(RENDER_WG), 0, st, d_buf, n_bytes, s, add, d_table, n_rows,
-                       d_out, (const int64_t *)c->render_list, (const RenderBlock *)c->d_render);
-    HIPCHK(hipMemcpyAsync(c->h_render, c->d_render, sizeof(RenderBlock), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-    stats[0] = (int64_t)c->h_render->total; stats[1] = (int64_t)c->h_render->rendered;
-    stats[2] = n_rows - stats[1];
-    if (stats[0] > out_cap)
-        return fail(FFQ_E_TABLE_FULL, "output holds %lld bytes, the rendered rows have %lld", (long long)out_cap,
-                    (long long)stats[0]);
-    return FFQ_OK;
-}
-
-// ---- the mates of a pair merged into one read (csrc/ffq_merge.h) ------------------------------
-static_assert(MRG_MAX_LEN == FFQ_OVERLAP_MAX_LEN && MERGE_COUNTS == FFQ_MERGE_COUNTS, "include/ffq.h");
-
-extern "C" int ffq_table_pair_merge(ffq_ctx *c, const ffq_table_view *m1, const ffq_table_view *m2, int64_t n_pairs,
-                                    const int32_t *d_insert, const int64_t *d_ord, uint8_t *d_text, int64_t text_cap, int64_t *d_off,
-                                    int64_t *d_rest1, int64_t *d_rest2, int64_t *d_rest_ord, int64_t *n_rest,
-                                    int64_t counts[FFQ_MERGE_COUNTS])
-{
-    static const char *const who = "ffq_table_pair_merge";
-    mark_other(c);
-    if (!c || !counts || !n_rest || n_pairs < 0 || text_cap < 0 || (text_cap > 0 && !d_text) || !view_ok(m1, n_pairs) || !view_ok(m2, n_pairs) ||
-        (n_pairs > 0 && (!d_rest1 || !d_rest2)))
-        return fail(FFQ_E_ARG, "%s: bad argument", who);
-    if (n_pairs > 0 && !d_insert) return fail(FFQ_E_ARG, "%s: no insert sizes (d_insert)", who);
-    if (((reinterpret_cast<uintptr_t>(d_rest1) | reinterpret_cast<uintptr_t>(d_rest2)) & 15) != 0)
-        return fail(FFQ_E_ARG, "%s: tables must be 16-byte aligned", who);
-    if (((reinterpret_cast<uintptr_t>(d_off) | reinterpret_cast<uintptr_t>(d_ord) | reinterpret_cast<uintptr_t>(d_rest_ord)) & 7) != 0 ||
-        (reinterpret_cast<uintptr_t>(d_insert) & 3) != 0)
-        return fail(FFQ_E_ARG, "%s: d_off, d_ord and d_rest_ord must be 8-byte aligned, d_insert 4-byte aligned", who);
-    if ((m1->n_bytes > 0 && !m1->d_buf) || (m2->n_bytes > 0 && !m2->d_buf)) return fail(FFQ_E_ARG, "%s: no buffer to read the mates from", who);
-    if (n_pairs > 0 && (d_rest1 == m1->d_table || d_rest1 == m2->d_table || d_rest2 == m1->d_table || d_rest2 == m2->d_table || d_rest1 == d_rest2))
-        return fail(FFQ_E_ARG, "%s: d_rest1 and d_rest2 must not be one of the tables, or each other", who);
-    if (c->pend.active) return fail(FFQ_E_ARG, "%s: a scan is pending on this context", who);
-    HIPCHK(hipSetDevice(c->device));
-    for (int i = 0; i < MERGE_COUNTS; i++) counts[i] = 0;
-    *n_rest = 0;
-    hipStream_t st = c->stream;
-    if (n_pairs == 0) {
-        if (d_off) {
-            HIPCHK(hipMemsetAsync(d_off, 0, sizeof(int64_t), st));
-            HIPCHK(hipStreamSynchronize(st));
-        }
-        return FFQ_OK;
-    }
-    const int64_t nblk = (n_pairs + MERGE_WG - 1) / MERGE_WG;
-    // (everything is grown before anything is enqueued: growing waits for the stream)
-    int rc = grow_dev(c, c->col_sum, nblk);
-    if (!rc) rc = grow_dev(c, c->sel_cnt, nblk);
-    if (!rc) rc = grow_dev(c, c->sel_base, nblk);
-    if (!rc) {
-        const hipError_t e = c->col_res.grow(1);
-        if (e != hipSuccess) rc = fail(FFQ_E_NOMEM, "hipMalloc failed: %s", hipGetErrorString(e));
-    }
-    if (rc) return rc;
-    const PairSide A = {m1->d_buf, m1->n_bytes, m1->sentinel ? 1 : 0, m1->add, m1->d_table};
-    const PairSide B = {m2->d_buf, m2->n_bytes, m2->sentinel ? 1 : 0, m2->add, m2->d_table};
-    HIPCHK(hipMemsetAsync(c->d_merge, 0, sizeof(MergeBlock), st));
-    hipLaunchKernelGGL(k_merge_sum, dim3((unsigned)std::min<int64_t>(nblk, 2048)), dim3(MERGE_WG), 0, st, A, B, n_pairs, nblk, d_insert, d_ord,
-                       c->col_sum.p, c->sel_cnt.p, c->d_merge.p);
-    if ((rc = launch_scan_i64v(c, st, c->col_sum, nblk, n_pairs, c->col_res))) return rc;
-    if ((rc = launch_scan_u32(c, st, (const unsigned int *)c->sel_cnt, nblk, c->sel_base, (long long *)c->d_word.p))) return rc;
-    hipLaunchKernelGGL(k_merge_rows, dim3((unsigned)nblk), dim3(MERGE_WG), 0, st, A, B, n_pairs, d_insert, d_ord, (const long long *)c->col_sum,
-                       (const DevRes *)c->col_res, (const long long *)c->sel_base, d_text, text_cap, d_off, d_rest1, d_rest2, d_rest_ord,
-                       c->d_merge.p);
-    HIPCHK(hipMemcpyAsync(c->h_merge, c->d_merge, sizeof(MergeBlock), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-    for (int i = 0; i < MERGE_COUNTS; i++) counts[i] = (int64_t)c->h_merge->cnt[i];
-    counts[1] = n_pairs - counts[0];
-    *n_rest = counts[1];
-    if (counts[2] > text_cap)
-        return fail(FFQ_E_TABLE_FULL, "text holds %lld bytes, the merged reads have %lld", (long long)text_cap, (long long)counts[2]);
-    return FFQ_OK;
-}
-
-// ---- duplicate reads and pairs (csrc/ffq_dedup.h) -----------------------------------------------
-static_assert(DEDUP_KEY_NONE == FFQ_KEY_NONE && DEDUP_COUNTS == FFQ_DEDUP_COUNTS, "include/ffq.h");
-
-constexpr int SEQKEY_GRID_SHORT = 2048, SEQKEY_GRID_LONG = 1024, DEDUP_GRID_TABLE = 4096, DEDUP_GRID_ROWS = 2048;
-
-extern "C" uint64_t ffq_seq_key_host(const uint8_t *seq, int64_t n) { return (seq || n <= 0) ? dedup_seq_key(seq, n < 0 ? 0 : n) : FFQ_KEY_NONE; }
-extern "C" uint64_t ffq_pair_key_host(uint64_t k1, uint64_t k2) { return dedup_pair_key(k1, k2); }
-
-extern "C" int ffq_table_seq_keys(ffq_ctx *c, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
-                                  const int64_t *d_table, int64_t n_rows, uint64_t *d_keys, int64_t counts[2])
-{
-    static const char *const who = "ffq_table_seq_keys";
-    mark_other(c);
-    if (!c || !counts || n_rows < 0 || n_bytes < 0 || (n_bytes > 0 && !d_buf) || (n_rows > 0 && (!d_table || !d_keys)))
-        return fail(FFQ_E_ARG, "%s: bad argument", who);
-    if ((reinterpret_cast<uintptr_t>(d_table) & 15) != 0 || (reinterpret_cast<uintptr_t>(d_keys) & 7) != 0)
-        return fail(FFQ_E_ARG, "%s: the table must be 16-byte aligned, the keys 8-byte aligned", who);
-    if (c->pend.active) return fail(FFQ_E_ARG, "%s: a scan is pending on this context", who);
-    HIPCHK(hipSetDevice(c->device));
-    counts[0] = counts[1] = 0;
-    if (n_rows == 0) return FFQ_OK;
-    const int rc = grow_dev(c, c->rows_list, n_rows);      // (before anything is enqueued: growing waits for the stream)
-    if (rc) return rc;
-    hipStream_t st = c->stream;
-    const int s = sentinel ? 1 : 0;
-    unsigned long long *keys = reinterpret_cast<unsigned long long *>(d_keys);
-    HIPCHK(hipMemsetAsync(c->d_rows, 0, sizeof(RowsBlock), st));
-    hipLaunchKernelGGL(k_seqkey_rows, dim3(rows_grid(n_rows, SEQKEY_WG / SEQKEY_G, SEQKEY_GRID_SHORT)), dim3(SEQKEY_WG), 0, st, d_buf,
-                       n_bytes, s, add, d_table, n_rows, keys, c->rows_list.p, c->d_rows.p);
-    hipLaunchKernelGGL(k_seqkey_long, dim3(rows_grid(n_rows, SEQKEY_WG / 64, SEQKEY_GRID_LONG)), dim3(SEQKEY_WG), 0, st, d_buf,
-                       n_bytes, s, add, d_table, keys, (const int64_t *)c->rows_list, c->d_rows.p);
-    int64_t stats[3];
-    const int rc2 = rows_end(c, stats);
-    if (rc2) return rc2;
-    counts[0] = stats[0]; counts[1] = stats[2];
-    return FFQ_OK;
-}
-
-// The set: the table in use (tab[cur]) and the one it grew out of, which the next growth reuses -- the old and the new table
-// are alive together while one is rehashed into the other.  The host knows, without asking the device, how many keys the
-// table holds (`distinct`, from the last call's one wait) and how many rows were ever submitted (the next global ordinal).
-struct ffq_dedup {
-    ffq_ctx *c = nullptr;
-    DevBuf<DedupSlot> tab[2];
-    int cur = 0;
-    int64_t slots = 0, distinct = 0, submitted = 0, rehashes = 0, max_bytes = 0;
-    DevBuf<DedupBlock> d_blk;
-    PinBuf<DedupBlock> h_blk;
-};
-
-static unsigned dedup_table_grid(int64_t slots) { return (unsigned)std::min<int64_t>((slots + 255) / 256, DEDUP_GRID_TABLE); }
-
-extern "C" void ffq_dedup_destroy(ffq_dedup *d)
-{
-    if (!d) return;
-    if (d->c && d->c->stream && hipSetDevice(d->c->device) == hipSuccess) (void)hipStreamSynchronize(d->c->stream);
-    delete d;                    // (the buffers free themselves)
-}
-
-extern "C" int ffq_dedup_create(ffq_ctx *c, int64_t expected_keys, int64_t max_bytes, ffq_dedup **out)
-{
-    static const char *const who = "ffq_dedup_create";
-    mark_other(c);
-    if (!c || !out || expected_keys < 0 || max_bytes < 0 || expected_keys > ((int64_t)1 << 56))
-        return fail(FFQ_E_ARG, "%s: bad argument", who);
-    *out = nullptr;
-    HIPCHK(hipSetDevice(c->device));
-    const int64_t slots = dedup_slots_for(0, expected_keys, 0);
-    if (max_bytes > 0 && slots * (int64_t)sizeof(DedupSlot) > max_bytes)
-        return fail(FFQ_E_NOMEM, "%s: a set for %lld keys needs %lld bytes (%lld slots), max_bytes is %lld", who, (long long)expected_keys,
-                    (long long)(slots * (int64_t)sizeof(DedupSlot)), (long long)slots, (long long)max_bytes);
-    ffq_dedup *d = new (std::nothrow) ffq_dedup();
-    if (!d) return fail(FFQ_E_NOMEM, "out of host memory");
-    d->c = c; d->max_bytes = max_bytes;
-    hipError_t e = d->tab[0].grow(slots);
-    if (e == hipSuccess) e = d->d_blk.grow(1);
-    if (e == hipSuccess) e = d->h_blk.grow(1);
-    if (e != hipSuccess) {
-        delete d;
-        return fail(FFQ_E_NOMEM, "%s: no memory for %lld slots: %s", who, (long long)slots, hipGetErrorString(e));
-    }
-    d->slots = slots;
-    hipLaunchKernelGGL(k_dedup_clear, dim3(dedup_table_grid(slots)), dim3(256), 0, c->stream, d->tab[0].p, slots);
-    const hipError_t e2 = hipGetLastError();
-    if (e2 != hipSuccess) {
-        ffq_dedup_destroy(d);
-        return fail(FFQ_E_HIP, "%s: %s", who, hipGetErrorString(e2));
-    }
-    *out = d;
-    return FFQ_OK;
-}
-
-extern "C" int ffq_dedup_select(ffq_dedup *d, const uint64_t *d_keys1, const uint64_t *d_keys2, const int64_t *d_ord, int64_t n,
-                                const int64_t *d_table1, const int64_t *d_table2, int64_t *d_out1, int64_t *d_out2, int64_t *d_idx,
-                                int64_t *n_out, int drop, int64_t counts[FFQ_DEDUP_COUNTS])
-{
-    static const char *const who = "ffq_dedup_select";
-    if (!d) return fail(FFQ_E_ARG, "%s: NULL set", who);
-    ffq_ctx *c = d->c;
-    mark_other(c);
-    if (!n_out || !counts || n < 0 || (n > 0 && !d_keys1)) return fail(FFQ_E_ARG, "%s: bad argument", who);
-    if (d_table2 && !d_keys2) return fail(FFQ_E_ARG, "%s: a second table without a second mate's keys", who);
-    if ((d_table1 && !d_out1) || (d_table2 && !d_out2)) return fail(FFQ_E_ARG, "%s: a table without a place for its kept rows", who);
-    if (((reinterpret_cast<uintptr_t>(d_table1) | reinterpret_cast<uintptr_t>(d_table2) | reinterpret_cast<uintptr_t>(d_out1) |
-          reinterpret_cast<uintptr_t>(d_out2)) & 15) != 0)
-        return fail(FFQ_E_ARG, "%s: tables must be 16-byte aligned", who);
-    if (((reinterpret_cast<uintptr_t>(d_keys1) | reinterpret_cast<uintptr_t>(d_keys2) | reinterpret_cast<uintptr_t>(d_ord) |
-          reinterpret_cast<uintptr_t>(d_idx)) & 7) != 0)
-        return fail(FFQ_E_ARG, "%s: keys and ordinals must be 8-byte aligned", who);
-    if (n > 0 && ((d_table1 && (d_out1 == d_table1 || d_out1 == d_table2)) || (d_table2 && (d_out2 == d_table2 || d_out2 == d_table1)) ||
-                  (d_out1 && d_out1 == d_out2)))
-        return fail(FFQ_E_ARG, "%s: d_out1 and d_out2 must not be one of the tables, or each other", who);
-    if (c->pend.active) return fail(FFQ_E_ARG, "%s: a scan is pending on this context", who);
-    HIPCHK(hipSetDevice(c->device));
-    *n_out = 0;
-    counts[0] = counts[1] = counts[2] = 0;
-    counts[3] = d->distinct; counts[4] = d->slots; counts[5] = d->rehashes;
-    if (n == 0) return FFQ_OK;
-    // growth, decided here: a call of n rows adds at most n keys
-    const int64_t want = dedup_slots_for(d->slots, d->distinct, n);
-    if (want != d->slots && d->max_bytes > 0 && want * (int64_t)sizeof(DedupSlot) > d->max_bytes)
-        return fail(FFQ_E_NOMEM, "%s: %lld keys and %lld more rows need %lld bytes (%lld slots), max_bytes is %lld", who,
-                    (long long)d->distinct, (long long)n, (long long)(want * (int64_t)sizeof(DedupSlot)), (long long)want,
-                    (long long)d->max_bytes);
-    const int64_t nblk = (n + 255) / 256;
-    // (everything is grown before anything is enqueued: growing waits for the stream)
-    int rc = grow_dev(c, c->filter_verdict, n);
-    if (!rc) rc = grow_dev(c, c->sel_cnt, nblk);
-    if (!rc) rc = grow_dev(c, c->sel_base, nblk);
-    if (rc) return rc;
-    hipStream_t st = c->stream;
-    HIPCHK(hipMemsetAsync(d->d_blk, 0, sizeof(DedupBlock), st));
-    if (want != d->slots) {
-        DevBuf<DedupSlot> &nu = d->tab[d->cur ^ 1];
-        CTX_SYNC(c);                                        // (the table before last goes away)
-        const hipError_t e = nu.grow(want);
-        if (e != hipSuccess)
-            return fail(FFQ_E_NOMEM, "%s: no memory for %lld slots: %s", who, (long long)want, hipGetErrorString(e));
-        hipLaunchKernelGGL(k_dedup_clear, dim3(dedup_table_grid(want)), dim3(256), 0, st, nu.p, want);
-        hipLaunchKernelGGL(k_dedup_rehash, dim3(dedup_table_grid(d->slots)), dim3(256), 0, st, (const DedupSlot *)d->tab[d->cur].p, d->slots,
-                           nu.p, want, d->d_blk.p);
-        d->cur ^= 1; d->slots = want; d->rehashes++;
-    }
-    DedupSlot *tab = d->tab[d->cur].p;
-    const unsigned long long *k1 = reinterpret_cast<const unsigned long long *>(d_keys1);
-    const unsigned long long *k2 = reinterpret_cast<const unsigned long long *>(d_keys2);
-    const unsigned long long g0 = (unsigned long long)d->submitted;
-    uint8_t *verdict = c->filter_verdict.p;
-    const unsigned rows_wgs = (unsigned)std::min<int64_t>(nblk, DEDUP_GRID_ROWS);
-    hipLaunchKernelGGL(k_dedup_insert, dim3(rows_wgs), dim3(DEDUP_WG), 0, st, tab, d->slots, k1, k2, d_ord, n, g0, d->d_blk.p);
-    hipLaunchKernelGGL(k_dedup_resolve, dim3(rows_wgs), dim3(DEDUP_WG), 0, st, tab, d->slots, k1, k2, d_ord, n, g0, drop ? 1 : 0, verdict,
-                       d->d_blk.p);
-    if (d_table1 || d_table2 || d_idx) {
-        hipLaunchKernelGGL(k_filter_count, dim3((unsigned)nblk), dim3(256), 0, st, (const uint8_t *)verdict, n, c->sel_cnt.p);
-        if ((rc = launch_scan_u32(c, st, (const unsigned int *)c->sel_cnt, nblk, c->sel_base, (long long *)c->d_word.p))) return rc;
-        hipLaunchKernelGGL(k_dedup_scatter, dim3((unsigned)nblk), dim3(256), 0, st, d_table1, d_table2, (const uint8_t *)verdict, d_ord, n,
-                           (const long long *)c->sel_base, d_out1, d_out2, d_idx);
-    }
-    HIPCHK(hipMemcpyAsync(d->h_blk, d->d_blk, sizeof(DedupBlock), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-    const DedupBlock &b = *d->h_blk.p;
-    d->submitted += n;
-    d->distinct += (int64_t)b.added;
-    if (b.err)
-        return fail(FFQ_E_INTERNAL, "%s: a probe visited all %lld slots (stage mask %llu): the table is damaged", who, (long long)d->slots,
-                    b.err);
-    counts[0] = (int64_t)b.kept; counts[1] = (int64_t)b.dups; counts[2] = (int64_t)b.nokey;
-    counts[3] = d->distinct; counts[4] = d->slots; counts[5] = d->rehashes;
-    *n_out = drop ? counts[0] : n;
-    return FFQ_OK;
 }
 
 // ---- arrayadd ----------------------------------------------------------------
@@ -2804,6 +1959,7 @@ extern "C" int ffq_selftest(ffq_ctx *c)
     return FFQ_OK;
 }
 
+#include "ffq_tables.h"
 #include "ffq_gzread.h"
 #include "ffq_stream.h"
 #include "ffq_bgzf.h"

@@ -4,7 +4,7 @@
 //   k_chain_serial    single-lane walker: exact on any input, the last tier
 //   k_finalize*       end offset / result block, published to host-mapped memory
 //   k_decode_stream   Phred decode of every record's quality span (output-aligned stream)
-//   k_sel_*, k_scan_i64, k_table_cut, k_table_lower_bound   table utilities
+//   k_scan_i64, k_table_cut, k_table_lower_bound            table utilities (the compaction: ffq_compact.h)
 //   k_arrayadd_b/q    the reference's array utilities
 //   k_synth_*, k_read_probe, k_selftest                     generators, diagnostics
 // The record chain itself: ffq_rows4.h (four-line fast path), ffq_chain.h (general path),
@@ -622,30 +622,9 @@ __global__ __launch_bounds__(256) void k_decode_stream(const uint8_t *__restrict
 }
 
 // =========================================================================
-// Row selection by sequence length (push-down of the length filter of
-// /root/reference/doc/user-guide.rst:153-180, evaluated on the offset table):
-// stable compaction of the rows with min_len <= pos3 - pos2 <= max_len.
-//   k_sel_count    one row per thread: kept rows per workgroup
-//   k_scan_i64     exclusive scan of those counts (one workgroup)
-//   k_sel_scatter  rank inside the workgroup by ballots, 48-byte row copy
+// k_scan_i64: exclusive scan of the kept-row counts of a compaction (ffq_compact.h) and of the FASTA scan's
+// entries per tile, one workgroup (launch_scan_u32 picks it for short arrays).
 // =========================================================================
-__device__ __forceinline__ bool sel_keep(const int64_t *__restrict__ table, int64_t i, int64_t n, int64_t lo,
-                                         int64_t hi)
-{
-    if (i >= n) return false;
-    const longlong2 p = *reinterpret_cast<const longlong2 *>(table + i * 6 + 2);      // pos2, pos3
-    const int64_t ln = p.y - p.x;
-    return ln >= lo && ln <= hi;
-}
-
-__global__ __launch_bounds__(256) void k_sel_count(const int64_t *__restrict__ table, int64_t n, int64_t lo,
-                                                   int64_t hi, unsigned int *__restrict__ bcnt)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int c = __syncthreads_count(sel_keep(table, i, n, lo, hi) ? 1 : 0);
-    if (threadIdx.x == 0) bcnt[blockIdx.x] = (unsigned int)c;
-}
-
 __global__ __launch_bounds__(1024) void k_scan_i64(const unsigned int *__restrict__ v, int64_t nv,
                                                    long long *__restrict__ base, long long *__restrict__ total)
 {
@@ -707,32 +686,6 @@ __global__ __launch_bounds__(1024) void k_scan_i64(const unsigned int *__restric
         carry += tot;
     }
     if (tid == 0) *total = carry;
-}
-
-__global__ __launch_bounds__(256) void k_sel_scatter(const int64_t *__restrict__ table, int64_t n, int64_t lo,
-                                                     int64_t hi, const long long *__restrict__ bbase,
-                                                     int64_t *__restrict__ out, int64_t *__restrict__ idx_out)
-{
-    // idx_out (optional): the ordinal in `table` of every kept row -- what a host that must hand back one item per
-    // ORIGINAL row (None for a dropped one, /root/reference/doc/user-guide.rst:166-170) puts the kept ones back by
-    __shared__ uint32_t s_w[4];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int64_t i = (int64_t)blockIdx.x * 256 + tid;
-    const bool keep = sel_keep(table, i, n, lo, hi);
-    const unsigned long long m = __ballot(keep);
-    if (lane == 0) s_w[wid] = (uint32_t)__popcll(m);
-    __syncthreads();
-    uint32_t wpre = 0;
-#pragma unroll
-    for (int q = 0; q < 4; q++)
-        if (q < wid) wpre += s_w[q];
-    if (!keep) return;
-    const int64_t r = bbase[blockIdx.x] + wpre + __popcll(m & ((1ull << lane) - 1ull));
-    const longlong2 *src = reinterpret_cast<const longlong2 *>(table + i * 6);
-    longlong2 *dst = reinterpret_cast<longlong2 *>(out + r * 6);
-    const longlong2 a = src[0], b = src[1], c = src[2];
-    dst[0] = a; dst[1] = b; dst[2] = c;
-    if (idx_out) idx_out[r] = i;
 }
 
 // =========================================================================

@@ -6,14 +6,14 @@
 // its own verdict bytes; a mate without content rules gets them from k_pair_len, which looks at the row's positions only.  Then
 //   k_pair_count     blocks of 256 pairs: the two verdict bytes combined under the mode, the kept pairs per block for the scan,
 //                    and the call's five pair counts -- summed over everything a workgroup strides over, one set of atomics each
-//   k_pair_scatter   behind the length filter's own scan (launch_scan_u32): rank inside the workgroup by ballots, the 48-byte
-//                    rows of BOTH tables and the ordinal copied to the pair's place
+//   and the compaction of ffq_compact.h behind its scan: the 48-byte rows of BOTH tables and the ordinal copied to the pair's
+//   place, "kept" said by KeepPair -- the predicate k_pair_count takes apart for its counts
 // ffq_table_pair_names:
 //   k_pair_names     in the row frame of ffq_rows.h, a group of 8 lanes per pair: 32 bytes of either header per round as
 //                    unaligned dwords, the delimiter found with a byte-mask test, the first differing byte with an xor; the
 //                    round loop is uniform over the wave (every group steps as long as one group of the wave has bytes left)
 #pragma once
-#include "ffq_filter.h"
+#include "ffq_compact.h"
 
 namespace ffq {
 
@@ -31,11 +31,12 @@ struct PairNamesBlock { unsigned long long equal, different, not_compared, first
 __global__ __launch_bounds__(256) void k_pair_len(const int64_t *__restrict__ table, int64_t n, int64_t lo, int64_t hi,
                                                   uint8_t *__restrict__ verdict, FilterBlock *__restrict__ blk)
 {
+    const KeepLen keep = {table, lo, hi};
     FilterCounts cnt;
     for (int64_t i0 = (int64_t)blockIdx.x * 256; i0 < n; i0 += (int64_t)gridDim.x * 256) {
         const int64_t i = i0 + threadIdx.x;
         if (i < n) {
-            const uint32_t v = sel_keep(table, i, n, lo, hi) ? 0u : 1u;
+            const uint32_t v = keep(i, n) ? 0u : 1u;
             verdict[i] = (uint8_t)v;
             cnt.add(v);
         }
@@ -43,31 +44,39 @@ __global__ __launch_bounds__(256) void k_pair_len(const int64_t *__restrict__ ta
     cnt.add_to<256>(blk);
 }
 
-// is pair i dropped?  f1, f2: the mates failed (v2 == nullptr: mate 2 is not judged)
-__device__ __forceinline__ void pair_verdicts(const uint8_t *__restrict__ v1, const uint8_t *__restrict__ v2, int64_t i, int64_t n,
-                                              bool &f1, bool &f2)
-{
-    f1 = i < n && (v1[i] & FILTER_REASON) != 0;
-    f2 = i < n && v2 != nullptr && (v2[i] & FILTER_REASON) != 0;
-}
-
-__device__ __forceinline__ bool pair_dropped(int mode, bool f1, bool f2)
-{
-    return mode == PAIR_ANY ? (f1 || f2) : mode == PAIR_BOTH ? (f1 && f2) : f1;
-}
+// Is pair i kept?  failed(): the mates' verdicts name a reason (v2 == nullptr: mate 2 is not judged); dropped(): what the mode
+// makes of the two.
+struct KeepPair {
+    const uint8_t *v1, *v2; int mode;
+    __device__ __forceinline__ void failed(int64_t i, int64_t n, bool &f1, bool &f2) const
+    {
+        f1 = i < n && (v1[i] & FILTER_REASON) != 0;
+        f2 = i < n && v2 != nullptr && (v2[i] & FILTER_REASON) != 0;
+    }
+    __device__ __forceinline__ bool dropped(bool f1, bool f2) const
+    {
+        return mode == PAIR_ANY ? (f1 || f2) : mode == PAIR_BOTH ? (f1 && f2) : f1;
+    }
+    __device__ __forceinline__ bool operator()(int64_t i, int64_t n) const
+    {
+        bool f1, f2;
+        failed(i, n, f1, f2);
+        return i < n && !dropped(f1, f2);
+    }
+};
 
 // (a workgroup strides over the blocks of 256 pairs: the kept pairs of every block go to the scan, the five counts are summed
 // in registers and leave with one set of atomics per WORKGROUP -- with a set per block of 256, 13 000 of them for the 3.3 M
 // pairs of a GiB, the call took 1.40 ms where it takes 1.08: DESIGN.md 4h)
-__global__ __launch_bounds__(256) void k_pair_count(const uint8_t *__restrict__ v1, const uint8_t *__restrict__ v2, int64_t n, int64_t nblk,
-                                                    int mode, unsigned int *__restrict__ bcnt, PairBlock *__restrict__ blk)
+__global__ __launch_bounds__(256) void k_pair_count(KeepPair keep, int64_t n, int64_t nblk, unsigned int *__restrict__ bcnt,
+                                                    PairBlock *__restrict__ blk)
 {
     unsigned int c[PAIR_COUNTS] = {0, 0, 0, 0, 0};
     for (int64_t b = blockIdx.x; b < nblk; b += gridDim.x) {         // (uniform over the workgroup: a barrier inside)
         const int64_t i = b * 256 + threadIdx.x;
         bool f1, f2;
-        pair_verdicts(v1, v2, i, n, f1, f2);
-        const bool have = i < n, drop = pair_dropped(mode, f1, f2);
+        keep.failed(i, n, f1, f2);
+        const bool have = i < n, drop = keep.dropped(f1, f2);
         const int kept = __syncthreads_count(have && !drop ? 1 : 0);
         if (threadIdx.x == 0) bcnt[b] = (unsigned int)kept;
         c[0] += have && !drop ? 1u : 0u;
@@ -87,39 +96,6 @@ __global__ __launch_bounds__(256) void k_pair_count(const uint8_t *__restrict__ 
         const unsigned long long t = s_cnt[0][threadIdx.x] + s_cnt[1][threadIdx.x] + s_cnt[2][threadIdx.x] + s_cnt[3][threadIdx.x];
         if (t) atomicAdd(&blk->cnt[threadIdx.x], t);
     }
-}
-
-__device__ __forceinline__ void pair_row_copy(const int64_t *__restrict__ table, int64_t i, int64_t *__restrict__ out, int64_t r)
-{
-    const longlong2 *src = reinterpret_cast<const longlong2 *>(table + i * 6);
-    longlong2 *dst = reinterpret_cast<longlong2 *>(out + r * 6);
-    const longlong2 a = src[0], b = src[1], c = src[2];
-    dst[0] = a; dst[1] = b; dst[2] = c;
-}
-
-__global__ __launch_bounds__(256) void k_pair_scatter(const int64_t *__restrict__ t1, const int64_t *__restrict__ t2,
-                                                      const uint8_t *__restrict__ v1, const uint8_t *__restrict__ v2, int64_t n, int mode,
-                                                      const long long *__restrict__ bbase, int64_t *__restrict__ out1,
-                                                      int64_t *__restrict__ out2, int64_t *__restrict__ idx_out)
-{
-    __shared__ uint32_t s_w[4];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int64_t i = (int64_t)blockIdx.x * 256 + tid;
-    bool f1, f2;
-    pair_verdicts(v1, v2, i, n, f1, f2);
-    const bool keep = i < n && !pair_dropped(mode, f1, f2);
-    const unsigned long long m = __ballot(keep);
-    if (lane == 0) s_w[wid] = (uint32_t)__popcll(m);
-    __syncthreads();
-    uint32_t wpre = 0;
-#pragma unroll
-    for (int q = 0; q < 4; q++)
-        if (q < wid) wpre += s_w[q];
-    if (!keep) return;
-    const int64_t r = bbase[blockIdx.x] + wpre + __popcll(m & ((1ull << lane) - 1ull));
-    pair_row_copy(t1, i, out1, r);
-    pair_row_copy(t2, i, out2, r);
-    if (idx_out) idx_out[r] = i;
 }
 
 // ---- names -------------------------------------------------------------------------------------------------------------------

@@ -125,6 +125,19 @@ static hipError_t stream_copy_chunk(StreamBufs *b, StreamSlot &sl, int64_t got)
 
 constexpr int SRC_FD = 0, SRC_GZIP = 1, SRC_PUSH = 2;
 
+// a length bound that bounds nothing: what a stream without a length filter is selected by
+constexpr int64_t LEN_UNBOUNDED = (int64_t)1 << 62;
+
+// What the dedup stage of a chain owns, in a stream (one table) and in a pair (two): the set, the rows and the ordinals that
+// remain behind it, the counts summed over the fills or rounds.
+struct DedupStage {
+    bool on = false;
+    int drop = 1;
+    ffq_dedup *set = nullptr;
+    DevBuf<int64_t> rows[2], idx;
+    int64_t total[FFQ_DEDUP_COUNTS] = {0, 0, 0, 0, 0, 0};
+};
+
 struct ffq_stream {
     ffq_ctx *c = nullptr;
     StreamBufs *b = nullptr;
@@ -168,14 +181,10 @@ struct ffq_stream {
     struct { bool on = false; int64_t last[3] = {0, 0, 0}; } render;
     // duplicate removal (ffq_stream_set_dedup): the stream's own set, the keys of the fill's rows as scanned, the rows and
     // ordinals that remain behind it, and the counts summed over the fills.  keys_on alone: a pair takes the keys (ffq_pair_set_dedup)
-    struct {
-        bool on = false, keys_on = false;
-        int drop = 1;
-        ffq_dedup *set = nullptr;
+    struct : DedupStage {
+        bool keys_on = false;
         DevBuf<uint64_t> keys;
-        DevBuf<int64_t> rows, idx;
         int64_t keyed[2] = {0, 0};
-        int64_t total[FFQ_DEDUP_COUNTS] = {0, 0, 0, 0, 0, 0};
     } dedup;
     // FFQ_STREAM_PROF=1: where the time of a stream goes (printed when it closes)
     bool prof = false;
@@ -615,6 +624,15 @@ extern "C" int ffq_stream_set_filter(ffq_stream *s, int64_t min_seq_len, int64_t
     return FFQ_OK;
 }
 
+// a stream without a filter gets one with unbounded length and no column: every stage behind the select finds its rows and
+// ordinals where a filter leaves them
+static void stream_filter_default(ffq_stream *s)
+{
+    if (s->filter.on) return;
+    s->filter.on = true;
+    s->filter.min = -LEN_UNBOUNDED; s->filter.max = LEN_UNBOUNDED; s->filter.col = 0; s->filter.add = 0;
+}
+
 // Content rules in the stream: the select of every fill judges the rows by ffq_table_select_reads -- as the trims left them,
 // which is cutadapt's order -- instead of by their length alone.  Before the first fill.  A stream without a filter gets one
 // with unbounded length and no column; ffq_stream_set_filter, before or behind this call, sets the bounds and the column
@@ -626,10 +644,7 @@ extern "C" int ffq_stream_set_content(ffq_stream *s, const ffq_content_rules *ru
     int rc = content_arg("ffq_stream_set_content", rules, &on, nullptr);
     if (!rc) rc = stream_settable(s, "ffq_stream_set_content", DECODE_GATHERS, true);
     if (rc) return rc;
-    if (!s->filter.on) {
-        s->filter.on = true;
-        s->filter.min = -((int64_t)1 << 62); s->filter.max = (int64_t)1 << 62; s->filter.col = 0; s->filter.add = 0;
-    }
+    stream_filter_default(s);
     s->content.on = true;
     s->content.rules = *rules;
     return FFQ_OK;
@@ -660,10 +675,7 @@ extern "C" int ffq_stream_set_dedup(ffq_stream *s, int drop, int64_t expected_ke
     if (rc) return rc;
     ffq_dedup_destroy(s->dedup.set);
     s->dedup.set = set;
-    if (!s->filter.on) {
-        s->filter.on = true;
-        s->filter.min = -((int64_t)1 << 62); s->filter.max = (int64_t)1 << 62; s->filter.col = 0; s->filter.add = 0;
-    }
+    stream_filter_default(s);
     s->dedup.on = s->dedup.keys_on = true;
     s->dedup.drop = drop ? 1 : 0;
     return FFQ_OK;
@@ -688,11 +700,37 @@ static void dedup_tally(int64_t total[FFQ_DEDUP_COUNTS], const int64_t c[FFQ_DED
 
 // a device buffer of the dedup stage grown to n elements: the stream is waited for first (the old block goes away)
 template <class B>
-static int dedup_room(ffq_ctx *c, B &buf, int64_t n, const char *what)
+static int dedup_room(ffq_ctx *c, B &buf, int64_t n, const char *who, const char *what)
 {
     if (buf.cap >= n) return FFQ_OK;
     HIPCHK(hipStreamSynchronize(c->stream));
-    return stream_grow(buf, std::max<int64_t>(n, 1 << 12), what, n);
+    if (buf.grow(std::max<int64_t>(n, 1 << 12)) == hipSuccess) return FFQ_OK;
+    return fail(FFQ_E_NOMEM, "%s: no memory for %lld %s", who, (long long)n, what);
+}
+
+// The dedup stage of a chain, over the one table of a stream's fill or the two of a round of a pair (rows[1] and keys[1] NULL
+// for one): the *n rows the select kept entered into the stage's set by their keys and the select's ordinals *d_ord, the
+// counts tallied.  Dropping, there is room for the rows and ordinals that remain, and rows[], *d_ord and *n are switched to
+// them; counting only, nothing is copied and the chain goes on with the select's rows.  who: "ffq_stream" or "ffq_pair".
+static int chain_dedup(ffq_ctx *c, const char *who, DedupStage &d, const uint64_t *const keys[2], const int64_t *rows[2], const int64_t **d_ord,
+                       int64_t *n)
+{
+    const bool drop = d.drop != 0;
+    int64_t cnt[FFQ_DEDUP_COUNTS], left = 0;
+    int rc = FFQ_OK;
+    for (int k = 0; k < 2 && !rc && drop; k++)
+        if (rows[k]) rc = dedup_room(c, d.rows[k], 6 * *n, who, "rows behind the dedup");
+    if (!rc && drop) rc = dedup_room(c, d.idx, *n, who, "ordinals behind the dedup");
+    if (!rc) rc = ffq_dedup_select(d.set, keys[0], keys[1], *d_ord, *n, drop ? rows[0] : nullptr, drop ? rows[1] : nullptr,
+                                   drop ? d.rows[0].p : nullptr, drop ? d.rows[1].p : nullptr, drop ? d.idx.p : nullptr, &left, drop ? 1 : 0, cnt);
+    if (rc) return rc;
+    dedup_tally(d.total, cnt);
+    if (drop) {
+        for (int k = 0; k < 2; k++)
+            if (rows[k]) rows[k] = d.rows[k].p;
+        *d_ord = d.idx.p; *n = left;
+    }
+    return FFQ_OK;
 }
 
 // Quality trimming in the stream: from the next fill on, every fill's table is trimmed in place on the device
@@ -905,7 +943,7 @@ static int chain_front(ffq_stream *s, const Fill &f, int64_t *rows, int64_t n)
 {
     int rc = FFQ_OK;
     if (s->dedup.keys_on && n > 0) {   // (the keys of the rows as scanned: a trim moves a row's end and the table forgets the old one)
-        rc = dedup_room(s->c, s->dedup.keys, n, "ffq_stream: no memory for %lld keys");
+        rc = dedup_room(s->c, s->dedup.keys, n, "ffq_stream", "keys");
         if (!rc) rc = ffq_table_seq_keys(s->c, f.d_buf, f.n, 0, f.add, rows, n, s->dedup.keys.p, s->dedup.keyed);
     }
     if (!rc && (s->stats.which & FFQ_STATS_IN))
@@ -967,17 +1005,10 @@ static int stream_chain(ffq_stream *s, const Fill &f, const ffq_scan_result &res
     }
     const int64_t *d_idx = b->idx.d;
     if (!rc && s->dedup.on && t.n > 0) {
-        // (count only: nothing is copied, the chain goes on with the select's rows)
-        const bool drop = s->dedup.drop != 0;
-        int64_t cnt[FFQ_DEDUP_COUNTS], kept = 0;
-        if (drop) rc = dedup_room(c, s->dedup.rows, 6 * t.n, "ffq_stream: no memory for %lld rows behind the dedup");
-        if (!rc && drop) rc = dedup_room(c, s->dedup.idx, t.n, "ffq_stream: no memory for %lld ordinals behind the dedup");
-        if (!rc) rc = ffq_dedup_select(s->dedup.set, s->dedup.keys.p, nullptr, b->idx.d, t.n, drop ? t.d_rows : nullptr, nullptr,
-                                       drop ? s->dedup.rows.p : nullptr, nullptr, drop ? s->dedup.idx.p : nullptr, &kept, drop ? 1 : 0, cnt);
-        if (!rc) {
-            dedup_tally(s->dedup.total, cnt);
-            if (drop) { t = Table{s->dedup.rows.p, kept}; d_idx = s->dedup.idx.p; }
-        }
+        const uint64_t *const keys[2] = {s->dedup.keys.p, nullptr};
+        const int64_t *rows[2] = {t.d_rows, nullptr};
+        rc = chain_dedup(c, "ffq_stream", s->dedup, keys, rows, &d_idx, &t.n);
+        t.d_rows = rows[0];
     }
     if (!rc) rc = chain_back(s, f, t);
     if (rc) return rc;
@@ -1117,13 +1148,7 @@ struct ffq_pair {
     } merge;
     // duplicate pairs dropped behind the pair select (ffq_pair_set_dedup): the pair's own set, the rows of both mates and the
     // ordinals that remain, the counts summed over the rounds
-    struct {
-        bool on = false;
-        int drop = 1;
-        ffq_dedup *set = nullptr;
-        DevBuf<int64_t> rows[2], idx;
-        int64_t total[FFQ_DEDUP_COUNTS] = {0, 0, 0, 0, 0, 0};
-    } dedup;
+    DedupStage dedup;
 };
 
 extern "C" int ffq_pair_open(ffq_stream *mate1, ffq_stream *mate2, int pair_filter, int check_names, ffq_pair **out)
@@ -1299,8 +1324,8 @@ static int pair_chain(ffq_pair *p, int64_t m, int64_t *n_out, int64_t *differ)
         ffq_stream *s = p->m[k].s;
         rc = chain_front(s, p->m[k].f, const_cast<int64_t *>(v[k].d_table), m);
         if (!rc) rc = stream_alloc_sel(s, m, 0);
-        bounds[2 * k] = s->filter.on ? s->filter.min : -((int64_t)1 << 62);
-        bounds[2 * k + 1] = s->filter.on ? s->filter.max : (int64_t)1 << 62;
+        bounds[2 * k] = s->filter.on ? s->filter.min : -LEN_UNBOUNDED;
+        bounds[2 * k + 1] = s->filter.on ? s->filter.max : LEN_UNBOUNDED;
         rules[k] = s->content.on ? &s->content.rules : nullptr;
         s->filter.scanned = m;
     }
@@ -1330,18 +1355,8 @@ static int pair_chain(ffq_pair *p, int64_t m, int64_t *n_out, int64_t *differ)
                                          p->idx.d, &kept, p->m[0].s->content.last, p->m[1].s->content.last, p->last_pairs);
     const int64_t *rows[2] = {p->m[0].s->b->sel.p, p->m[1].s->b->sel.p}, *d_ord = p->idx.d;
     if (!rc && p->dedup.on && kept > 0) {
-        // (count only: nothing is copied, the chain goes on with the select's rows)
-        const bool drop = p->dedup.drop != 0;
-        int64_t cnt[FFQ_DEDUP_COUNTS], left = 0;
-        for (int k = 0; k < 2 && !rc && drop; k++) rc = dedup_room(c, p->dedup.rows[k], 6 * kept, "ffq_pair: no memory for %lld rows behind the dedup");
-        if (!rc && drop) rc = dedup_room(c, p->dedup.idx, kept, "ffq_pair: no memory for %lld ordinals behind the dedup");
-        if (!rc) rc = ffq_dedup_select(p->dedup.set, p->m[0].s->dedup.keys.p, p->m[1].s->dedup.keys.p, p->idx.d, kept, drop ? rows[0] : nullptr,
-                                       drop ? rows[1] : nullptr, drop ? p->dedup.rows[0].p : nullptr, drop ? p->dedup.rows[1].p : nullptr,
-                                       drop ? p->dedup.idx.p : nullptr, &left, drop ? 1 : 0, cnt);
-        if (!rc) {
-            dedup_tally(p->dedup.total, cnt);
-            if (drop) { rows[0] = p->dedup.rows[0].p; rows[1] = p->dedup.rows[1].p; d_ord = p->dedup.idx.p; kept = left; }
-        }
+        const uint64_t *const keys[2] = {p->m[0].s->dedup.keys.p, p->m[1].s->dedup.keys.p};
+        rc = chain_dedup(c, "ffq_pair", p->dedup, keys, rows, &d_ord, &kept);
     }
     if (!rc && p->merge.on) return pair_chain_merge(p, rows, d_ord, kept, n_out);
     for (int k = 0; k < 2 && !rc; k++) rc = chain_back(p->m[k].s, p->m[k].f, Table{rows[k], kept});

@@ -8,7 +8,7 @@ several thresholds; plus the same filter building the header / quality / whole e
 
 CPU: the object called per record by this package's iterator with the pure-Python scanner.
 GPU: the same call with the GPU scanner -- the stream front end filters every fill's table ON THE DEVICE
-(ffq_stream_set_filter: k_sel_count / k_scan / k_sel_scatter, then the column kernels over the kept rows) before
+(ffq_stream_set_filter: the compaction of csrc/ffq_compact.h -- count, scan, scatter --, then the column kernels over the kept rows) before
 anything is copied back -- through every kind of source (descriptor, gzip, BGZF, pushed chunks) and buffer size;
 and the C ABI itself (ffq_stream_selected: kept rows, their ordinals, the gathered column) against the oracle."""
 import hashlib
