@@ -1,5 +1,5 @@
 // ffq_bgzf.h -- a byte RANGE of a BGZF file inflated on its own (host code of libffq_hip.so; the member parser and the
-// inflate pool are ffq_gzread.h's).
+// batch of members inflated side by side, BgzfBatch, are ffq_gzread.h's).
 //
 // A BGZF file (what bgzip writes; SAM specification section 4.1) is a series of gzip members of at most 64 KiB of data
 // each, every one saying in its header how long it is (BSIZE) and in its trailer what it inflates to (ISIZE): the
@@ -7,7 +7,7 @@
 // rank r takes the members whose FIRST byte lies in its share [c_lo, c_hi) of the compressed file -- the first one is
 // found by its signature and proven by the chain of headers behind it, nothing is inflated to find it --, learns from
 // the trailers how many bytes they hold, the ranks add those up (one exchange of a number per rank) and have the cut
-// points of the UNCOMPRESSED stream; then every rank inflates its members side by side (GzPool) and the ordinary
+// points of the UNCOMPRESSED stream; then every rank inflates its members side by side (BgzfBatch) and the ordinary
 // sharded step runs over the inflated ranges, halos handed over between the ranks.  Offsets in every row are offsets of
 // the uncompressed stream, as for the reference's loop over gzip.open(...) (/root/reference/src/fastqandfurious.py:241-279;
 // doc/user-guide.rst opens its files that way).
@@ -62,18 +62,9 @@ struct Walk {
     uint8_t *h_dst;
     int64_t cap;
     int64_t out = 0, members = 0;
-    std::vector<GzJob> jobs;
-    GzPool *pool = nullptr;
-    z_stream own{};
-    bool own_init = false;
-    int nthreads;
+    BgzfBatch batch;
 
-    Walk(uint8_t *dst, int64_t cap_, int threads) : h_dst(dst), cap(cap_), nthreads(threads > 0 ? std::min(threads, 256) : gz_threads_default()) {}
-    ~Walk()
-    {
-        delete pool;
-        if (own_init) (void)inflateEnd(&own);
-    }
+    Walk(uint8_t *dst, int64_t cap_, int threads) : h_dst(dst), cap(cap_), batch(threads > 0 ? std::min(threads, 256) : gz_threads_default()) {}
     // the member of `avail` readable bytes at mem = byte `at` of the file (size bytes long): its length through *total, or an error
     int take(const uint8_t *mem, int64_t avail, int64_t at, int64_t size, int64_t *total_out)
     {
@@ -86,39 +77,23 @@ struct Walk {
                 return fail(FFQ_E_ARG, "ffq_bgzf_range: gzip: compressed file ended before the end-of-stream marker was reached (the BGZF member at byte %lld is cut short)", (long long)at);
             return 1;                       // (all there in the file, not in what the caller holds of it)
         }
-        const uint8_t *e = mem + total;
-        const uint32_t crc = (uint32_t)e[-8] | ((uint32_t)e[-7] << 8) | ((uint32_t)e[-6] << 16) | ((uint32_t)e[-5] << 24);
-        const uint32_t isz = (uint32_t)e[-4] | ((uint32_t)e[-3] << 8) | ((uint32_t)e[-2] << 16) | ((uint32_t)e[-1] << 24);
-        if (isz > 65536) return fail(FFQ_E_ARG, "ffq_bgzf_range: gzip: the member at byte %lld says it holds %u bytes (a BGZF member holds at most 65536)", (long long)at, isz);
+        const GzJob j = BgzfBatch::job(mem, total, xl, h_dst ? h_dst + out : nullptr);
+        if (j.isize > 65536) return fail(FFQ_E_ARG, "ffq_bgzf_range: gzip: the member at byte %lld says it holds %u bytes (a BGZF member holds at most 65536)", (long long)at, j.isize);
         if (h_dst) {
-            if (out + (int64_t)isz > cap) return fail(FFQ_E_TABLE_FULL, "ffq_bgzf_range: the range inflates to more than %lld bytes", (long long)cap);
-            try { jobs.push_back(GzJob{mem + 12 + xl, (uint32_t)(total - xl - 20), h_dst + out, isz, crc}); }
+            if (out + (int64_t)j.isize > cap) return fail(FFQ_E_TABLE_FULL, "ffq_bgzf_range: the range inflates to more than %lld bytes", (long long)cap);
+            try { batch.add(j); }
             catch (const std::bad_alloc &) { return fail(FFQ_E_NOMEM, "out of host memory"); }
         }
-        out += isz;
+        out += j.isize;
         members++;
         return FFQ_OK;
     }
     // the jobs gathered so far (their compressed bytes still where take() saw them), by the pool's threads and this one
     int inflate(int64_t from, int64_t to)
     {
-        if (!h_dst || jobs.empty()) { jobs.clear(); return FFQ_OK; }
-        if (!own_init) {
-            if (inflateInit2(&own, -15) != Z_OK) return fail(FFQ_E_NOMEM, "ffq_bgzf_range: zlib could not be initialised");
-            own_init = true;
-        }
-        if (!pool && nthreads > 1 && jobs.size() > 1) {
-            pool = new (std::nothrow) GzPool();
-            if (pool && !pool->start(nthreads - 1)) { delete pool; pool = nullptr; }
-        }
-        bool ok = true;
-        for (size_t j0 = 0; j0 < jobs.size() && ok; j0 += (size_t)1 << 20) {              // (in batches the pool's counter can hold)
-            const int nj = (int)std::min<size_t>((size_t)1 << 20, jobs.size() - j0);
-            if (pool) ok = pool->run(jobs.data() + j0, nj, &own);
-            else for (int j = 0; j < nj && ok; j++) ok = GzPool::inflate_fast(jobs[j0 + (size_t)j]) || GzPool::inflate_one(&own, jobs[j0 + (size_t)j]);
-        }
-        jobs.clear();
-        if (!ok) return fail(FFQ_E_ARG, "ffq_bgzf_range: gzip: a member between bytes %lld and %lld does not inflate to what its trailer says (length or CRC-32)", (long long)from, (long long)to);
+        if (batch.jobs.empty()) return FFQ_OK;
+        if (!batch.zstate(0)) return fail(FFQ_E_NOMEM, "ffq_bgzf_range: zlib could not be initialised");
+        if (!batch.run()) return fail(FFQ_E_ARG, "ffq_bgzf_range: gzip: a member between bytes %lld and %lld does not inflate to what its trailer says (length or CRC-32)", (long long)from, (long long)to);
         return FFQ_OK;
     }
 };

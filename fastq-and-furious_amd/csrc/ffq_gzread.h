@@ -1,8 +1,9 @@
 // ffq_gzread.h -- a gzip file behind a descriptor as a source of DECOMPRESSED bytes (host code of libffq_hip.so, no HIP
 // in it; included by ffq_hip.hip, whose `fail` words the errors of ffq_bgzf.h behind it).  GzReader owns everything the
-// inflate needs -- the compressed window, the zlib states, the pool of BGZF threads, the several-thread engine of
-// ffq_pgz.h -- and frees it in its destructor.  It is the feeder stage of a gzip stream (ffq_stream.h) and all of
-// ffq_gunzip_fd; the pool and the member parser serve the BGZF range walker (ffq_bgzf.h) as well.
+// inflate needs -- the compressed window, the zlib states, ONE BatchPool (ffq_pool.h) that the batch of BGZF members and
+// the several-thread engine of ffq_pgz.h both run on -- and frees it in its destructor.  It is the feeder stage of a
+// gzip stream (ffq_stream.h) and all of ffq_gunzip_fd; the batch (BgzfBatch) and the member parser serve the BGZF range
+// walker (ffq_bgzf.h) as well.
 #pragma once
 #include <poll.h>
 #include <sys/stat.h>
@@ -27,105 +28,91 @@ struct GzJob {
     uint32_t isize, crc;    // from the member's trailer
 };
 
-struct GzPool {
-    std::vector<std::thread> th;
-    std::mutex m;
-    std::condition_variable cv_go, cv_done;
-    const GzJob *jobs = nullptr;
-    int njobs = 0, active = 0;
-    std::atomic<int> next{0}, failed{0};
-    uint64_t gen = 0;
-    bool quit = false;
+static bool inflate_one(z_stream *z, const GzJob &j)
+{
+    uint8_t none[8];
+    if (inflateReset(z) != Z_OK) return false;
+    z->next_in = const_cast<Bytef *>(j.src);
+    z->avail_in = j.clen;
+    z->next_out = j.isize ? j.dst : none;
+    z->avail_out = j.isize ? j.isize : (uInt)sizeof none;
+    const int r = inflate(z, Z_FINISH);
+    if (r != Z_STREAM_END || z->avail_in != 0 || z->total_out != j.isize) return false;
+    return (uint32_t)crc32(crc32(0L, Z_NULL, 0), j.dst, j.isize) == j.crc;
+}
+// The same member through this build's own decoder (ffq_pgz.h; about twice zlib's rate on FASTQ), into a scratch
+// buffer of the thread (a match is copied a word at a time: the bytes behind a member's end belong to the next
+// member, which another thread is writing); whatever it does not like is zlib's (inflate_one).
+struct GzScratch { pgz::Inflater<uint8_t> inf; std::vector<uint8_t> buf; };
+static bool inflate_fast(const GzJob &j)
+{
+    thread_local std::unique_ptr<GzScratch> sc;
+    try {
+        if (!sc) sc.reset(new GzScratch());
+        const int64_t cap = (int64_t)j.isize + pgz::OUT_SLACK + 8;
+        if ((int64_t)sc->buf.size() < cap) sc->buf.resize((size_t)cap);
+    } catch (const std::bad_alloc &) { return false; }
+    pgz::Inflater<uint8_t> &f = sc->inf;
+    f.win_valid = 0;
+    f.limit_bit = INT64_MAX;
+    f.set_out(sc->buf.data(), 0, (int64_t)j.isize + pgz::OUT_SLACK + 8);
+    f.start(j.src, j.clen, 0);
+    if (f.run() != pgz::R_FINAL || f.b_out != (int64_t)j.isize || ((f.b_bit + 7) >> 3) != (int64_t)j.clen) return false;
+    if ((uint32_t)crc32(crc32(0L, Z_NULL, 0), sc->buf.data(), j.isize) != j.crc) return false;
+    memcpy(j.dst, sc->buf.data(), j.isize);
+    return true;
+}
 
-    static bool inflate_one(z_stream *z, const GzJob &j)
+// The members gathered for one side-by-side inflate, and what inflating them takes: a BatchPool (the owner's, or one of
+// its own; started when a batch first has two jobs for it) and one raw-deflate zlib state per worker (header and trailer
+// are read by the parser), made when that worker first needs zlib.
+struct BgzfBatch {
+    struct ZState { z_stream z; bool init; };
+    std::vector<GzJob> jobs;
+    const int threads;                  // the caller's included
+    BatchPool own, *const pool;
+    std::unique_ptr<ZState[]> zs;       // [threads], by worker
+
+    explicit BgzfBatch(int threads_, BatchPool *shared = nullptr) : threads(threads_), pool(shared ? shared : &own) {}
+    BgzfBatch(const BgzfBatch &) = delete;
+    ~BgzfBatch()
     {
-        uint8_t none[8];
-        if (inflateReset(z) != Z_OK) return false;
-        z->next_in = const_cast<Bytef *>(j.src);
-        z->avail_in = j.clen;
-        z->next_out = j.isize ? j.dst : none;
-        z->avail_out = j.isize ? j.isize : (uInt)sizeof none;
-        const int r = inflate(z, Z_FINISH);
-        if (r != Z_STREAM_END || z->avail_in != 0 || z->total_out != j.isize) return false;
-        return (uint32_t)crc32(crc32(0L, Z_NULL, 0), j.dst, j.isize) == j.crc;
+        for (int w = 0; zs && w < threads; w++)
+            if (zs[w].init) (void)inflateEnd(&zs[w].z);
     }
-    // The same member through this build's own decoder (ffq_pgz.h; about twice zlib's rate on FASTQ), into a scratch
-    // buffer of the thread (a match is copied a word at a time: the bytes behind a member's end belong to the next
-    // member, which another thread is writing); whatever it does not like is zlib's (inflate_one).
-    struct Scratch { pgz::Inflater<uint8_t> inf; std::vector<uint8_t> buf; };
-    static bool inflate_fast(const GzJob &j)
+    // The member of `total` bytes at `member` (extra field of xlen bytes) as a job that inflates to dst: the ONE place a
+    // trailer (CRC-32, ISIZE) is read.  The caller looks at what it promises, then adds it.
+    static GzJob job(const uint8_t *member, int64_t total, int xlen, uint8_t *dst)
     {
-        thread_local std::unique_ptr<Scratch> sc;
-        try {
-            if (!sc) sc.reset(new Scratch());
-            const int64_t cap = (int64_t)j.isize + pgz::OUT_SLACK + 8;
-            if ((int64_t)sc->buf.size() < cap) sc->buf.resize((size_t)cap);
-        } catch (const std::bad_alloc &) { return false; }
-        pgz::Inflater<uint8_t> &f = sc->inf;
-        f.win_valid = 0;
-        f.limit_bit = INT64_MAX;
-        f.set_out(sc->buf.data(), 0, (int64_t)j.isize + pgz::OUT_SLACK + 8);
-        f.start(j.src, j.clen, 0);
-        if (f.run() != pgz::R_FINAL || f.b_out != (int64_t)j.isize || ((f.b_bit + 7) >> 3) != (int64_t)j.clen) return false;
-        if ((uint32_t)crc32(crc32(0L, Z_NULL, 0), sc->buf.data(), j.isize) != j.crc) return false;
-        memcpy(j.dst, sc->buf.data(), j.isize);
-        return true;
+        const uint8_t *e = member + total;
+        return GzJob{member + 12 + xlen, (uint32_t)(total - xlen - 20), dst, pgz::le32(e - 4), pgz::le32(e - 8)};
     }
-    void work(z_stream *z)
+    void add(const GzJob &j) { jobs.push_back(j); }
+    // zlib's state of a worker (0: the caller; the array itself is made by the caller: run() asks for it first); NULL: zlib could not be initialised
+    z_stream *zstate(int worker)
     {
-        for (;;) {
-            const int j = next.fetch_add(1);
-            if (j >= njobs) break;
-            if (!inflate_fast(jobs[j]) && !inflate_one(z, jobs[j])) failed.store(1);
+        if (!zs) zs.reset(new (std::nothrow) ZState[(size_t)threads]());
+        if (!zs || worker >= threads) return nullptr;
+        ZState &s = zs[worker];
+        if (!s.init) s.init = inflateInit2(&s.z, -15) == Z_OK;
+        return s.init ? &s.z : nullptr;
+    }
+    // Every job inflated (and forgotten), by the pool's threads and the caller; false: a member did not inflate to what
+    // its trailer says.
+    bool run()
+    {
+        std::atomic<int> failed{zstate(0) ? 0 : 1};
+        if (threads > 1 && jobs.size() > 1) (void)pool->start(threads - 1);      // (fewer threads than asked for: the rest do it)
+        for (size_t j0 = 0; j0 < jobs.size() && !failed.load(); j0 += (size_t)1 << 20) {       // (in batches the pool's counter can hold)
+            const GzJob *js = jobs.data() + j0;
+            pool->run((int)std::min<size_t>((size_t)1 << 20, jobs.size() - j0), [&](int j, int w) {
+                if (inflate_fast(js[j])) return;
+                z_stream *z = zstate(w);
+                if (!z || !inflate_one(z, js[j])) failed.store(1);
+            });
         }
-    }
-    void worker()
-    {
-        z_stream z;
-        memset(&z, 0, sizeof z);
-        const bool ok = inflateInit2(&z, -15) == Z_OK;      // raw deflate: header and trailer are read by the parser
-        uint64_t seen = 0;
-        for (;;) {
-            {
-                std::unique_lock<std::mutex> lk(m);
-                cv_go.wait(lk, [&] { return quit || gen != seen; });
-                if (quit) break;
-                seen = gen;
-            }
-            if (ok) work(&z);
-            std::lock_guard<std::mutex> lk(m);
-            if (--active == 0) cv_done.notify_one();
-        }
-        if (ok) (void)inflateEnd(&z);
-    }
-    bool start(int nthreads)
-    {
-        try {
-            for (int i = 0; i < nthreads; i++) th.emplace_back(&GzPool::worker, this);
-        } catch (...) {}
-        return !th.empty();
-    }
-    // all jobs, by the pool's threads and the caller's (own: the caller's raw-deflate state); false: a member
-    // did not inflate to what its trailer says
-    bool run(const GzJob *js, int n, z_stream *own)
-    {
-        {
-            std::lock_guard<std::mutex> lk(m);
-            jobs = js; njobs = n; next.store(0); failed.store(0);
-            active = (int)th.size();
-            gen++;
-        }
-        cv_go.notify_all();
-        work(own);
-        std::unique_lock<std::mutex> lk(m);
-        cv_done.wait(lk, [&] { return active == 0; });
+        jobs.clear();
         return failed.load() == 0;
-    }
-    ~GzPool()
-    {
-        { std::lock_guard<std::mutex> lk(m); quit = true; }
-        cv_go.notify_all();
-        for (auto &t : th) t.join();
     }
 };
 
@@ -203,14 +190,14 @@ struct GzReader {
     const bool seekable;
     const Interrupt *const irq;         // (not owned; may be NULL)
     const int threads;                  // > 1: BGZF members are inflated side by side
-    z_stream zs{}, zraw{};               // the members one at a time; this thread's own raw-deflate state (it takes jobs too)
-    bool z_init = false, zraw_init = false, z_member = false, z_in_eof = false;
+    z_stream zs{};                      // the members one at a time
+    bool z_init = false, z_member = false, z_in_eof = false;
     uint8_t *zin = nullptr;
     int64_t zin_len = 0, zin_pos = 0, z_filepos;
     std::string z_msg;
     bool bgzf_ok = true;                // cleared when a member did not hold what it promised: one at a time from there
-    GzPool *pool = nullptr;
-    std::vector<GzJob> jobs;
+    BatchPool pool;                     // threads - 1 threads, started on first use: the batch's and the engine's
+    BgzfBatch batch;
     int64_t bgzf_members = 0;           // members inflated by the pool (statistics)
     // one member inflated by several threads (ffq_pgz.h: a regular file that is not BGZF), and zlib going on from
     // the block boundary the engine gave up at
@@ -224,7 +211,8 @@ struct GzReader {
 
     // the compressed bytes are read from `pos` on (a descriptor that seeks: pread), by nthreads threads (<= 0: the default)
     GzReader(int fd_, int64_t pos, bool seekable_, int nthreads, const Interrupt *irq_)
-        : fd(fd_), seekable(seekable_), irq(irq_), threads(nthreads > 0 ? std::min(nthreads, 256) : gz_threads_default()), z_filepos(pos)
+        : fd(fd_), seekable(seekable_), irq(irq_), threads(nthreads > 0 ? std::min(nthreads, 256) : gz_threads_default()), z_filepos(pos),
+          batch(threads, &pool)
     {
         zin = static_cast<uint8_t *>(malloc((size_t)GZ_IN + 16));      // (+16: the decoders read whole words)
         z_init = zin && inflateInit2(&zs, 15 + 16) == Z_OK;            // 16: gzip wrapper (header, CRC-32, length)
@@ -233,9 +221,7 @@ struct GzReader {
     ~GzReader()
     {
         if (z_init) (void)inflateEnd(&zs);
-        delete pool;
         delete engine;
-        if (zraw_init) (void)inflateEnd(&zraw);
         free(zin);
     }
     bool ok() const { return z_init; }                       // false: "zlib could not be initialised"
@@ -282,30 +268,21 @@ struct GzReader {
             const int r = more_input();
             if (r <= 0) return r;
         }
-        jobs.clear();
+        batch.jobs.clear();
         int64_t p = zin_pos, out = 0;
         while (p < zin_len) {
             const int64_t total = bgzf_member_len(zin + p, zin_len - p, &xl);
             if (total <= 0 || total > zin_len - p) break;
-            const uint8_t *e = zin + p + total;
-            const uint32_t crc = (uint32_t)e[-8] | ((uint32_t)e[-7] << 8) | ((uint32_t)e[-6] << 16) | ((uint32_t)e[-5] << 24);
-            const uint32_t isz = (uint32_t)e[-4] | ((uint32_t)e[-3] << 8) | ((uint32_t)e[-2] << 16) | ((uint32_t)e[-1] << 24);
-            if ((int64_t)isz > room - out) break;
-            jobs.push_back(GzJob{zin + p + 12 + xl, (uint32_t)(total - xl - 20), dst + out, isz, crc});
-            out += isz;
+            const GzJob j = BgzfBatch::job(zin + p, total, xl, dst + out);
+            if ((int64_t)j.isize > room - out) break;
+            batch.add(j);
+            out += j.isize;
             p += total;
         }
-        if (jobs.size() < 2) return 0;            // (one member: the serial inflate is as good)
-        if (!pool) {
-            pool = new (std::nothrow) GzPool();
-            if (!pool || !pool->start(threads - 1)) { delete pool; pool = nullptr; bgzf_ok = false; return 0; }
-        }
-        if (!zraw_init) {
-            if (inflateInit2(&zraw, -15) != Z_OK) { bgzf_ok = false; return 0; }
-            zraw_init = true;
-        }
-        if (!pool->run(jobs.data(), (int)jobs.size(), &zraw)) { bgzf_ok = false; return 0; }
-        bgzf_members += (int64_t)jobs.size();
+        const int64_t n = (int64_t)batch.jobs.size();
+        if (n < 2) return 0;                      // (one member: the serial inflate is as good)
+        if (!batch.run()) { bgzf_ok = false; return 0; }
+        bgzf_members += n;
         zin_pos = p;
         return out;
     }
@@ -333,7 +310,7 @@ struct GzReader {
         if (file_size - member_off < pgz::env_i64("FFQ_PGZ_MIN", 4 << 20)) return false;
         if (!engine) {
             engine = new (std::nothrow) pgz::Engine();
-            if (!engine || !engine->init(fd, threads, file_size)) { delete engine; engine = nullptr; pgz_ok = false; return false; }
+            if (!engine || !engine->init(fd, threads, file_size, &pool)) { delete engine; engine = nullptr; pgz_ok = false; return false; }
         }
         if (!engine->begin(member_off)) return false;
         pgz_member_off = member_off;
@@ -372,8 +349,7 @@ struct GzReader {
             if (more_input() < 0) return false;
         }
         const uint8_t *t = zin + zin_pos;
-        const uint32_t fcrc = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
-        const uint32_t flen = (uint32_t)t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) | ((uint32_t)t[7] << 24);
+        const uint32_t fcrc = pgz::le32(t), flen = pgz::le32(t + 4);
         zin_pos += 8;
         z_raw = false;
         if (fcrc != z_crc) { z_msg = "incorrect data check"; return false; }

@@ -30,19 +30,18 @@
 #include <atomic>
 #include <cerrno>
 #include <chrono>
-#include <condition_variable>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <functional>
-#include <mutex>
 #include <new>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include <emmintrin.h>
 #include <unistd.h>
+
+#include "ffq_pool.h"
 
 namespace ffq {
 namespace pgz {
@@ -61,6 +60,8 @@ static const uint8_t DIST_EXTRA[30] = {0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5,
 static const uint8_t CL_ORDER[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
 
 static inline uint64_t ld64(const uint8_t *p) { uint64_t v; memcpy(&v, p, 8); return v; }     // (x86-64: little endian)
+// a 32-bit field of a gzip trailer (RFC 1952: least significant byte first)
+static inline uint32_t le32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
 
 static inline uint32_t bitrev(uint32_t c, int len)
 {
@@ -443,57 +444,6 @@ struct Inflater {
     }
 };
 
-// ---- a few threads that run the chunks of a batch ---------------------------------------------------------------------
-struct Pool {
-    std::vector<std::thread> th;
-    std::mutex m;
-    std::condition_variable cv_go, cv_done;
-    const std::function<void(int)> *fn = nullptr;
-    int njobs = 0, active = 0;
-    std::atomic<int> next{0};
-    uint64_t gen = 0;
-    bool quit = false;
-
-    void work() { for (;;) { const int j = next.fetch_add(1); if (j >= njobs) break; (*fn)(j); } }
-    void worker()
-    {
-        uint64_t seen = 0;
-        for (;;) {
-            {
-                std::unique_lock<std::mutex> lk(m);
-                cv_go.wait(lk, [&] { return quit || gen != seen; });
-                if (quit) break;
-                seen = gen;
-            }
-            work();
-            std::lock_guard<std::mutex> lk(m);
-            if (--active == 0) cv_done.notify_one();
-        }
-    }
-    bool start(int n)
-    {
-        try { for (int i = 0; i < n; i++) th.emplace_back(&Pool::worker, this); } catch (...) {}
-        return (int)th.size() == n;
-    }
-    void run(int n, const std::function<void(int)> &f)
-    {
-        {
-            std::lock_guard<std::mutex> lk(m);
-            fn = &f; njobs = n; next.store(0); active = (int)th.size(); gen++;
-        }
-        cv_go.notify_all();
-        work();
-        std::unique_lock<std::mutex> lk(m);
-        cv_done.wait(lk, [&] { return active == 0; });
-    }
-    ~Pool()
-    {
-        { std::lock_guard<std::mutex> lk(m); quit = true; }
-        cv_go.notify_all();
-        for (auto &t : th) t.join();
-    }
-};
-
 struct Stats { std::atomic<int64_t> batches{0}, chunks{0}, rejected{0}, giveups{0}, members{0}, ns_find{0}, ns_exact{0}, ns_markers{0}, ns_stage1{0}, ns_stitch{0}, ns_stage2{0}, ns_read{0}; };
 static inline int64_t now_ns() { return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 static Stats &stats() { static Stats s; return s; }
@@ -534,7 +484,7 @@ struct Engine {
     std::atomic<int64_t> mem16{0};
     int64_t nbatches = 0;
     int64_t file_size = 0;
-    Pool *pool = nullptr;
+    BatchPool *pool = nullptr;          // the owner's (ffq_pool.h; not owned): the reads, stage 1 and stage 2 of a batch run on it
     std::vector<Chunk *> ck;
     std::vector<uint8_t> in;
     // ---- the commit point ----
@@ -551,16 +501,15 @@ struct Engine {
     int64_t end_off = 0;                // file offset behind the member's trailer
     std::string msg;
 
-    ~Engine() { for (Chunk *c : ck) delete c; delete pool; }
+    ~Engine() { for (Chunk *c : ck) delete c; }
 
-    bool init(int fd_, int threads_, int64_t file_size_)
+    bool init(int fd_, int threads_, int64_t file_size_, BatchPool *pool_)
     {
-        fd = fd_; threads = threads_; file_size = file_size_;
+        fd = fd_; threads = threads_; file_size = file_size_; pool = pool_;
         chunk_bytes = env_i64("FFQ_PGZ_CHUNK", chunk_bytes);
         max_out = env_i64("FFQ_PGZ_MAX_OUT", max_out);
         giveup_after = env_i64("FFQ_PGZ_GIVEUP_AFTER", 0);
-        pool = new (std::nothrow) Pool();
-        if (!pool || !pool->start(threads - 1)) return false;
+        if (!pool->start(threads - 1)) return false;
         nslots = threads * (int)std::min<int64_t>(env_i64("FFQ_PGZ_CPT", threads > 1 ? 2 : 1), 8);
         mem_budget = env_i64("FFQ_PGZ_MEM", mem_budget);
         const int64_t per_chunk = (int64_t)(WSIZE + cap0()) * (int64_t)sizeof(uint16_t);
@@ -747,9 +696,9 @@ struct Engine {
         const int64_t rp = 4 << 20;
         const int nrp = (int)((want + rp - 1) / rp);
         std::vector<int64_t> rgot((size_t)nrp, 0);
-        const std::function<void(int)> rd = [&](int q) { rgot[(size_t)q] = pread_full(in.data() + q * rp, std::min(rp, want - q * rp), byte0 + q * rp); };
+        const std::function<void(int, int)> rd = [&](int q, int) { rgot[(size_t)q] = pread_full(in.data() + q * rp, std::min(rp, want - q * rp), byte0 + q * rp); };
         if (nrp > 1) pool->run(nrp, rd);
-        else rd(0);
+        else rd(0, 0);
         int64_t in_len = 0;
         for (int q = 0; q < nrp; q++) {
             if (rgot[(size_t)q] < 0) return -1;
@@ -766,7 +715,7 @@ struct Engine {
         }
         const int64_t rel0 = pos_bit - byte0 * 8;
         std::atomic<int> oom{0};
-        const std::function<void(int)> stage1 = [&](int k) {
+        const std::function<void(int, int)> stage1 = [&](int k, int) {
             try {
                 const int64_t t = now_ns();
                 if (k == 0) run_exact(ck[0], in_len, rel0);
@@ -828,7 +777,7 @@ struct Engine {
         const int64_t m = std::min(n, b_total - emit_pos);
         const int P = (int)std::min<int64_t>(threads, std::max<int64_t>(1, m >> 18));
         std::vector<uint32_t> sums((size_t)P);
-        const std::function<void(int)> fn = [&](int p) {
+        const std::function<void(int, int)> fn = [&](int p, int) {
             const int64_t a = emit_pos + m * p / P, b = emit_pos + m * (p + 1) / P;
             uint32_t c32 = (uint32_t)crc32(0L, Z_NULL, 0);
             int k = 0;
@@ -848,7 +797,7 @@ struct Engine {
             }
             sums[(size_t)p] = c32;
         };
-        if (P == 1) fn(0);
+        if (P == 1) fn(0, 0);
         else pool->run(P, fn);
         for (int p = 0; p < P; p++) {
             const int64_t len = (emit_pos + m * (p + 1) / P) - (emit_pos + m * p / P);
@@ -870,8 +819,7 @@ struct Engine {
         const int64_t t = (pos_bit + 7) >> 3;
         uint8_t tr[8];
         if (pread_full(tr, 8, t) != 8) { failed = true; msg = "compressed file ended before the end-of-stream marker was reached"; return; }
-        const uint32_t fcrc = (uint32_t)tr[0] | ((uint32_t)tr[1] << 8) | ((uint32_t)tr[2] << 16) | ((uint32_t)tr[3] << 24);
-        const uint32_t flen = (uint32_t)tr[4] | ((uint32_t)tr[5] << 8) | ((uint32_t)tr[6] << 16) | ((uint32_t)tr[7] << 24);
+        const uint32_t fcrc = le32(tr), flen = le32(tr + 4);
         if (fcrc != crc) { failed = true; msg = "incorrect data check"; }
         else if (flen != (uint32_t)isize) { failed = true; msg = "incorrect length check"; }
         member_done = true;

@@ -1,16 +1,24 @@
-// ffq_pool.h -- helper threads of a context (host code of libffq_hip.so): slices of file reads
-// (the stream front end, ffq_stream.h) and of host-to-host copies (the staging of the host-buffer
-// entry points, ffq_scan_host) run on them in parallel.
+// ffq_pool.h -- the host threads of libffq_hip.so (host code, no HIP in it), two pools:
+//   ReadPool    helper threads of a context behind ONE queue: slices of file reads (the stream front end,
+//               ffq_stream.h) and of host-to-host copies (the staging of the host-buffer entry points,
+//               ffq_scan_host) run on them in parallel, the caller goes on and waits per chunk;
+//   BatchPool   fork-join: the caller and the pool's threads run the jobs of one batch and meet behind it
+//               (BGZF members side by side, ffq_gzread.h / ffq_bgzf.h; the stages of the several-thread
+//               inflate, ffq_pgz.h).
 #pragma once
 #include <errno.h>
 #include <sched.h>
+#include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include <unistd.h>
 
 #include <algorithm>
+#include <atomic>
 #include <condition_variable>
 #include <deque>
+#include <functional>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -123,11 +131,10 @@ struct ReadPool {
         cv_job.notify_all();
         for (auto &t : th) t.join();
     }
-    // queue the slices of one chunk of a seekable descriptor (returns at once)
-    void enqueue(int fd, uint8_t *dst, int64_t n, int64_t pos, ChunkRead *cr)
+    // n bytes in at most min(threads, n / slice, 64) page-rounded slices, one job each (src: copies, else preads of fd at pos)
+    void enqueue_slices(int fd, const uint8_t *src, uint8_t *dst, int64_t n, int64_t pos, int64_t slice, ChunkRead *cr)
     {
-        const int64_t SL = 1 << 20;
-        const int nsl = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)th.size(), n / SL, (int64_t)64}));
+        const int nsl = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)th.size(), n / slice, (int64_t)64}));
         const int64_t per = ((n + nsl - 1) / nsl + 4095) & ~(int64_t)4095;
         {
             std::lock_guard<std::mutex> lk(m);
@@ -137,13 +144,15 @@ struct ReadPool {
                 if (a >= n) break;
                 cr->want[t] = std::min(per, n - a);
                 cr->got[t] = 0;
-                q.push_back(Job{fd, nullptr, dst + a, cr->want[t], pos + a, cr, t});
+                q.push_back(Job{fd, src ? src + a : nullptr, dst + a, cr->want[t], pos + a, cr, t});
                 cr->nsl = t + 1;
             }
             cr->left = cr->nsl;
         }
         cv_job.notify_all();
     }
+    // queue the slices of one chunk of a seekable descriptor (returns at once)
+    void enqueue(int fd, uint8_t *dst, int64_t n, int64_t pos, ChunkRead *cr) { enqueue_slices(fd, nullptr, dst, n, pos, 1 << 20, cr); }
     // queue a host-to-host copy in slices (pageable <-> pinned staging of the host-buffer entry points)
     void enqueue_copy(uint8_t *dst, const uint8_t *src, int64_t n, ChunkRead *cr)
     {
@@ -154,22 +163,7 @@ struct ReadPool {
             cr->nsl = 0; cr->left = 0;
             return;
         }
-        const int nsl = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)th.size(), n / SL, (int64_t)64}));
-        const int64_t per = ((n + nsl - 1) / nsl + 4095) & ~(int64_t)4095;
-        {
-            std::lock_guard<std::mutex> lk(m);
-            cr->nsl = 0;
-            for (int t = 0; t < nsl; t++) {
-                const int64_t a = (int64_t)t * per;
-                if (a >= n) break;
-                cr->want[t] = std::min(per, n - a);
-                cr->got[t] = 0;
-                q.push_back(Job{-1, src + a, dst + a, cr->want[t], 0, cr, t});
-                cr->nsl = t + 1;
-            }
-            cr->left = cr->nsl;
-        }
-        cv_job.notify_all();
+        enqueue_slices(-1, src, dst, n, 0, SL, cr);
     }
     void wait(ChunkRead *cr)
     {
@@ -178,3 +172,59 @@ struct ReadPool {
     }
 };
 
+// ---- fork-join: the jobs of one batch on the pool's threads and the caller's -------------------------------------------
+// run(njobs, fn): fn(job, worker) once for every job in [0, njobs), worker = 0 on the calling thread and 1..n on the pool's
+// n; returns when all are through.  One caller at a time.  The threads sleep on a generation counter between batches
+// (nobody spins); a pool that was never started runs everything on the caller.
+struct BatchPool {
+    std::vector<std::thread> th;
+    std::mutex m;
+    std::condition_variable cv_go, cv_done;
+    const std::function<void(int, int)> *fn = nullptr;
+    int njobs = 0, active = 0;
+    std::atomic<int> next{0};
+    uint64_t gen = 0;
+    bool quit = false;
+
+    void work(int w) { for (;;) { const int j = next.fetch_add(1); if (j >= njobs) break; (*fn)(j, w); } }
+    void worker(int w)
+    {
+        uint64_t seen = 0;
+        for (;;) {
+            {
+                std::unique_lock<std::mutex> lk(m);
+                cv_go.wait(lk, [&] { return quit || gen != seen; });
+                if (quit) break;
+                seen = gen;
+            }
+            work(w);
+            std::lock_guard<std::mutex> lk(m);
+            if (--active == 0) cv_done.notify_one();
+        }
+    }
+    // n threads, once: a pool that has threads keeps them (its users share it and all ask).  false: not all of them started
+    bool start(int n)
+    {
+        if (th.empty())
+            try { for (int i = 0; i < n; i++) th.emplace_back(&BatchPool::worker, this, i + 1); } catch (...) {}
+        return (int)th.size() >= n;
+    }
+    int size() const { return (int)th.size(); }
+    void run(int n, const std::function<void(int, int)> &f)
+    {
+        {
+            std::lock_guard<std::mutex> lk(m);
+            fn = &f; njobs = n; next.store(0); active = (int)th.size(); gen++;
+        }
+        cv_go.notify_all();
+        work(0);
+        std::unique_lock<std::mutex> lk(m);
+        cv_done.wait(lk, [&] { return active == 0; });
+    }
+    ~BatchPool()
+    {
+        { std::lock_guard<std::mutex> lk(m); quit = true; }
+        cv_go.notify_all();
+        for (auto &t : th) t.join();
+    }
+};

@@ -143,6 +143,7 @@ struct ffq_stream {
     StreamBufs *b = nullptr;
     int fd = -1, src = SRC_FD;
     bool seekable = false;
+    bool sliced = false;                // the source is read in slices queued ahead: a plain descriptor that can seek
     std::unique_ptr<GzReader> gz;       // SRC_GZIP: the inflating source (feeder thread only)
     Interrupt irq = {nullptr, nullptr}; // what the feeder's blocking reads ask: stream_asked
     int64_t handed_pos = 0;             // position of the source behind the last chunk handed out
@@ -204,87 +205,122 @@ static inline double stream_now()
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-// The feeder: queues the slices of chunk e as soon as slot e % STREAM_SLOTS is free (up to two chunks being read at a
-// time), and completes chunks in order: once the last slice of chunk p is in, its H2D copy goes onto the copy stream and
-// the caller may take it.
+// ---- the feeder thread ------------------------------------------------------------------------------------------------
+// It completes chunks in order: once chunk p is in its slot, its H2D copy goes onto the copy stream and the caller may take
+// it.  Of a sliced source it queues the slices of chunk e as soon as slot e % STREAM_SLOTS is free, up to FFQ_STREAM_AHEAD
+// chunks in front of p; any other source is read when its chunk's turn comes (e == p between chunks).  Each turn of its
+// loop is three steps: feeder_wait, feeder_queue (as often as feeder_wait says), feeder_complete.
+struct Feeder {
+    ffq_stream *s;
+    StreamBufs *b;
+    int64_t pos0;                // the file offset of chunk 0
+    int64_t p = 0, e = 0;        // chunk to complete next; chunks [0, e) have their slices queued
+};
+
+enum FeedNext { FEED_STOP, FEED_QUEUE, FEED_READ };
+
+// Step 1: wait for a free slot, a park request or a stop (under s->m); what to do next.
+static FeedNext feeder_wait(Feeder &f)
+{
+    ffq_stream *s = f.s;
+    std::unique_lock<std::mutex> lk(s->m);
+    for (;;) {
+        if (s->stop) return FEED_STOP;
+        if (s->pause_req && f.e == f.p) {          // the caller reallocates the slots: park here (nothing in flight)
+            s->paused = true;
+            s->cv.notify_all();
+            s->cv.wait(lk);
+            continue;
+        }
+        s->paused = false;
+        if (f.e > f.p || (s->sliced ? f.e : f.p) - s->released < STREAM_SLOTS) break;   // a read to wait for, or a free slot
+        s->cv.wait(lk);
+    }
+    const bool ahead = s->sliced && !s->pause_req && f.e - s->released < STREAM_SLOTS && f.e - f.p < FFQ_STREAM_AHEAD;
+    return ahead ? FEED_QUEUE : FEED_READ;
+}
+
+// Step 2 (a sliced source): queue the slices of chunk e.
+static void feeder_queue(Feeder &f)
+{
+    StreamSlot &sq = f.b->slot[f.e % STREAM_SLOTS];
+    f.b->pool->enqueue(f.s->fd, sq.buf.h + f.b->room, f.b->fbufsize, f.pos0 + f.e * f.b->fbufsize, &sq.cr);
+    f.e++;
+}
+
+// the slices of chunks [from, e) are in flight: nothing may be freed or reallocated under them
+static void feeder_drain(Feeder &f, int64_t from)
+{
+    for (int64_t k = from; k < f.e; k++) f.b->pool->wait(&f.b->slot[k % STREAM_SLOTS].cr);
+}
+
+// Chunk p of each kind of source into its slot.  Returns the bytes; -1: error; -2 (a pipe): asked to stop / park with
+// nothing read.  *eof: the source ends behind them.
+static int64_t feed_slices(Feeder &f, StreamSlot &sl, bool *eof)
+{
+    f.b->pool->wait(&sl.cr);
+    const int64_t got = sl.cr.total();
+    *eof = got < f.b->fbufsize;
+    return got;
+}
+static int64_t feed_gzip(Feeder &f, StreamSlot &sl, bool *eof) { return f.s->gz->read(sl.buf.h + f.b->room, f.b->fbufsize, eof); }
+static int64_t feed_pipe(Feeder &f, StreamSlot &sl, bool *eof) { return stream_fd_read(f.s->fd, &f.s->irq, sl.buf.h + f.b->room, f.b->fbufsize, eof); }
+
+// Step 3: read chunk p from its source, enqueue its copy, publish it.  false: the feeder is through (the end, or an error).
+static bool feeder_complete(Feeder &f, double tw0)
+{
+    ffq_stream *s = f.s;
+    StreamBufs *b = f.b;
+    StreamSlot &sl = b->slot[f.p % STREAM_SLOTS];
+    const double tr0 = s->prof ? stream_now() : 0;
+    bool src_eof = false;
+    const int64_t got = (s->sliced ? feed_slices : s->src == SRC_GZIP ? feed_gzip : feed_pipe)(f, sl, &src_eof);
+    if (got == -2) return true;                    // back to feeder_wait, for the same chunk
+    if (!s->sliced) f.e = f.p + 1;
+    if (s->prof) { const double t = stream_now(); s->t_slot += tr0 - tw0; s->t_read += t - tr0; }
+    int rc = FFQ_OK;
+    std::string msg;
+    if (got < 0) {
+        rc = FFQ_E_ARG;
+        msg = s->src == SRC_GZIP ? std::string("ffq_stream: gzip: ") + s->gz->msg() : std::string("ffq_stream: read failed: ") + strerror(errno);
+    } else {
+        sl.got = got;
+        sl.eof = src_eof;
+        const hipError_t er = stream_copy_chunk(b, sl, got);
+        if (er != hipSuccess) { rc = FFQ_E_HIP; msg = std::string("ffq_stream: chunk copy failed: ") + hipGetErrorString(er); }
+    }
+    if (rc || sl.eof) feeder_drain(f, f.p + 1);    // reads past the end
+    {
+        std::lock_guard<std::mutex> lk(s->m);
+        if (rc) { s->feeder_rc = rc; s->feeder_msg = msg; s->feeder_done = true; }
+        else {
+            s->file_pos = s->src == SRC_GZIP ? s->gz->file_pos() : s->file_pos + got;
+            sl.end_pos = s->file_pos;
+            s->produced = f.p + 1;
+            if (sl.eof) s->feeder_done = true;
+        }
+    }
+    s->cv.notify_all();
+    f.p++;
+    return !(rc || sl.eof);
+}
+
 static void stream_feeder(ffq_stream *s)
 {
     (void)hipSetDevice(s->c->device);
-    StreamBufs *b = s->b;
-    const int64_t pos0 = s->file_pos;
-    int64_t e = 0;                        // chunks [0, e) have their slices queued (seekable descriptors)
-    for (int64_t p = 0;; p++) {           // chunk to complete next
+    Feeder f{s, s->b, s->file_pos};
+    for (;;) {
         const double tw0 = s->prof ? stream_now() : 0;
-        for (;;) {
-            {
-                std::unique_lock<std::mutex> lk(s->m);
-                for (;;) {
-                    if (s->stop) break;
-                    if (s->pause_req && e == p) {          // the caller reallocates the slots: park here (nothing in flight)
-                        s->paused = true;
-                        s->cv.notify_all();
-                        s->cv.wait(lk);
-                        continue;
-                    }
-                    s->paused = false;
-                    if (e > p || ((s->seekable && s->src == SRC_FD) ? e : p) - s->released < STREAM_SLOTS) break;   // a read to wait for, or a free slot
-                    s->cv.wait(lk);
-                }
-                if (s->stop) {
-                    lk.unlock();
-                    for (int64_t k = p; k < e; k++) b->pool->wait(&b->slot[k % STREAM_SLOTS].cr);   // reads in flight
-                    lk.lock();
-                    s->feeder_done = true;
-                    s->cv.notify_all();
-                    return;
-                }
-                if (s->seekable && s->src == SRC_FD && !s->pause_req && e - s->released < STREAM_SLOTS && e - p < FFQ_STREAM_AHEAD) {
-                    StreamSlot &sq = b->slot[e % STREAM_SLOTS];
-                    lk.unlock();
-                    b->pool->enqueue(s->fd, sq.buf.h + b->room, b->fbufsize, pos0 + e * b->fbufsize, &sq.cr);
-                    e++;
-                    continue;
-                }
-            }
-            break;
-        }
-        StreamSlot &sl = b->slot[p % STREAM_SLOTS];
-        const double tr0 = s->prof ? stream_now() : 0;
-        int64_t got;
-        bool src_eof = false;
-        if (s->seekable && s->src == SRC_FD) { b->pool->wait(&sl.cr); got = sl.cr.total(); src_eof = got < b->fbufsize; }
-        else if (s->src == SRC_GZIP) { got = s->gz->read(sl.buf.h + b->room, b->fbufsize, &src_eof); e = p + 1; }
-        else {
-            got = stream_fd_read(s->fd, &s->irq, sl.buf.h + b->room, b->fbufsize, &src_eof);
-            if (got == -2) { p--; continue; }      // stop / pause asked for with nothing read yet: back to the parking loop
-            e = p + 1;
-        }
-        if (s->prof) { const double t = stream_now(); s->t_slot += tr0 - tw0; s->t_read += t - tr0; }
-        int rc = FFQ_OK;
-        std::string msg;
-        if (got < 0) {
-            rc = FFQ_E_ARG;
-            msg = s->src == SRC_GZIP ? std::string("ffq_stream: gzip: ") + s->gz->msg() : std::string("ffq_stream: read failed: ") + strerror(errno);
-        } else {
-            sl.got = got;
-            sl.eof = src_eof;
-            const hipError_t er = stream_copy_chunk(b, sl, got);
-            if (er != hipSuccess) { rc = FFQ_E_HIP; msg = std::string("ffq_stream: chunk copy failed: ") + hipGetErrorString(er); }
-        }
-        if (rc || sl.eof)
-            for (int64_t k = p + 1; k < e; k++) b->pool->wait(&b->slot[k % STREAM_SLOTS].cr);    // reads past the end
-        {
+        FeedNext next;
+        while ((next = feeder_wait(f)) == FEED_QUEUE) feeder_queue(f);
+        if (next == FEED_STOP) {
+            feeder_drain(f, f.p);                  // reads in flight
             std::lock_guard<std::mutex> lk(s->m);
-            if (rc) { s->feeder_rc = rc; s->feeder_msg = msg; s->feeder_done = true; }
-            else {
-                s->file_pos = s->src == SRC_GZIP ? s->gz->file_pos() : s->file_pos + got;
-                sl.end_pos = s->file_pos;
-                s->produced = p + 1;
-                if (sl.eof) s->feeder_done = true;
-            }
+            s->feeder_done = true;
+            s->cv.notify_all();
+            return;
         }
-        s->cv.notify_all();
-        if (rc || sl.eof) return;
+        if (!feeder_complete(f, tw0)) return;
     }
 }
 
@@ -453,6 +489,7 @@ static int stream_open_impl(ffq_ctx *c, int src, int fd, int64_t fbufsize, uint3
         // descriptor's current position if start < 0; a descriptor that cannot seek is read in order
         const off_t at = lseek(fd, 0, SEEK_CUR);
         s->seekable = at != (off_t)-1;
+        s->sliced = s->seekable && src == SRC_FD;
         s->file_pos = s->seekable ? (start >= 0 ? start : (int64_t)at) : 0;
         s->handed_pos = s->file_pos;
     }

@@ -116,6 +116,63 @@ def test_stream_long_record_grows_the_carry(mods, gpu_ctx, oracle, tmp_path):
     assert err is None and np.array_equal(np.array(rows, dtype=np.int64), want)
 
 
+@pytest.fixture(scope="module")
+def long_middle(oracle):
+    """50 short records, one whose sequence and quality are 1.2 MiB each (longer than the initial 1 MiB carry space), 50
+    more short ones: ~2.5 MB, and the oracle's rows of the whole"""
+    rng = np.random.default_rng(5)
+    L = 1258291                                                 # 1.2 MiB
+    seq = rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), size=L).tobytes()
+    qual = rng.choice(np.frombuffer(bytes(range(35, 74)), dtype=np.uint8), size=L).tobytes()
+    short = lambda lo: b"".join(b"@r%d\nACGTACGTAC\n+\nIIIIIHHHGG\n" % i for i in range(lo, lo + 50))
+    data = short(0) + b"@long\n" + seq + b"\n+\n" + qual + b"\n" + short(50)
+    want, end, *_ = oracle.scan(data)
+    assert len(want) == 101
+    return data, want
+
+
+def _rows_and_end(mods, gpu_ctx, fd, bufsize, **kw):
+    _, hip, _ = mods
+    rows, end = [], None
+    st = hip.FileStream(gpu_ctx, fd, bufsize, **kw)
+    try:
+        for t, fill, off, end_state, err_off in st:
+            rows.extend(t.tolist())
+            end = end_state
+    finally:
+        st.close()
+    return np.array(rows, dtype=np.int64).reshape(-1, 6), end
+
+
+def test_gzip_stream_long_record_parks_the_feeder(mods, gpu_ctx, long_middle, tmp_path):
+    """the carry outgrows its room while the feeder INFLATES: it parks between chunks, the slots are reallocated"""
+    import gzip
+    _, hip, _ = mods
+    data, want = long_middle
+    rows, end = with_file(tmp_path, gzip.compress(data, 1), lambda fd: _rows_and_end(mods, gpu_ctx, fd, 1 << 18, gzip=True))
+    assert np.array_equal(rows, want) and end == hip.END_OK
+
+
+def test_pipe_stream_long_record_parks_the_feeder(mods, gpu_ctx, long_middle):
+    """the same with the feeder behind poll() on a pipe that a writer fills in 64 KiB pieces"""
+    _, hip, _ = mods
+    data, want = long_middle
+    r, w = os.pipe()
+
+    def feed():
+        with os.fdopen(w, "wb") as fh:
+            for i in range(0, len(data), 65536):
+                fh.write(data[i:i + 65536])
+    t = threading.Thread(target=feed)
+    t.start()
+    try:
+        rows, end = _rows_and_end(mods, gpu_ctx, r, 1 << 18)
+    finally:
+        os.close(r)
+        t.join()
+    assert np.array_equal(rows, want) and end == hip.END_OK
+
+
 def test_stream_pipe_and_empty(mods, gpu_ctx, golden, tmp_path):
     """a descriptor that cannot seek (read() instead of pread()); an empty file"""
     data = golden_file("test.fq") * 50

@@ -4,10 +4,11 @@ inflate and in-process shard world do).
 
 A -fsanitize=thread (then: address,undefined) build of libffq_hip.so (hipcc instruments the HOST code; no device is touched by what runs here) +
 tests/tsan_host_threads.cpp + the oracle (the scan of the shard mode), all in one TSan runtime:
-  * ffq_gunzip_fd = the stream front end's gzip reader (csrc/ffq_gzread.h: GzReader): BGZF members side by side (GzPool), ONE
+  * ffq_gunzip_fd = the stream front end's gzip reader (csrc/ffq_gzread.h: GzReader): BGZF members side by side (BgzfBatch), ONE
     plain member by several threads (csrc/ffq_pgz.h: chunks entered at block headers, hand-overs at odd bits, stitch, CRC pieces combined),
-    concatenated members, zlib taking over, corrupt and cut files;
-  * the helper threads of a context (csrc/ffq_pool.h): slices of consecutive chunks through one queue;
+    both on the reader's one BatchPool, concatenated members, zlib taking over, corrupt and cut files;
+  * the two pools of csrc/ffq_pool.h: the fork-join BatchPool on its own, and the helper threads of a context (ReadPool):
+    slices of consecutive chunks through one queue;
   * ffq_shard_host_step with k ranks as threads over ffq_shard_world's breakable barrier (csrc/ffq_shard_proto.h): the
     settle rounds of the shard protocol, and a rank that fails while the others wait.
 0 reports is the bar; the detector is shown to be awake by a deliberate race.  What stays outside: the feeder thread of
@@ -123,6 +124,26 @@ def test_gunzip_threads_under_tsan(tsan, tmp_path):
             b[at:at + 2000] = bytes(random.randrange(256) for _ in range(2000))
         bad.write_bytes(bytes(b))
         tsan("gunzip", bad, 4, 1 << 20, env={"FFQ_PGZ_MIN": "1", "FFQ_PGZ_CHUNK": "65536"}, ok=(0, 1))
+
+
+def test_gunzip_mixed_members_share_one_pool_under_tsan(tsan, tmp_path):
+    """BGZF members, then one plain member, then BGZF members again: ONE reader inflates members side by side and runs the
+    several-thread engine, both on its one BatchPool."""
+    from fastqandfurious_amd import bgzf
+    data = _fastq(8000, 21)                                     # 3 MB
+    a, b = 500_000, 2_500_000
+    f = tmp_path / "mixed.gz"
+    f.write_bytes(bgzf.compress(data[:a], level=1, eof_marker=False) + gzip.compress(data[a:b], 6) + bgzf.compress(data[b:], level=1))
+    out = tsan("gunzip", f, 5, 1 << 20, env={"FFQ_PGZ_MIN": "1", "FFQ_PGZ_CHUNK": "65536"}).stdout.split()
+    assert " ".join(out[:2]) == "%d %08x" % (len(data), zlib.crc32(data))
+    assert int(out[2]) > 0, "no BGZF members were inflated side by side"
+    assert int(out[3]) > 4, "the several-thread engine did not run"
+
+
+def test_batch_pool_under_tsan(tsan):
+    """BatchPool (csrc/ffq_pool.h) on its own: every job exactly once, on the caller (worker 0) or a pool thread (1..n),
+    200 runs back to back on one pool, a pool destroyed without a run."""
+    assert tsan("batch", "-").stdout.startswith("equal")
 
 
 def test_reader_pool_under_tsan(tsan, tmp_path):

@@ -2,11 +2,15 @@
 // device is touched).  Linked against a -fsanitize=thread build of libffq_hip.so (hipcc instruments the host code, the
 // device code is left alone) and of the test oracle (oracle/ffq_oracle.c: the scan of the shard mode).
 //
-//   gunzip FILE THREADS CHUNK      ffq_gunzip_fd: the stream front end's gzip reader -- BGZF members side by side (GzPool),
+//   gunzip FILE THREADS CHUNK      ffq_gunzip_fd: the stream front end's gzip reader -- BGZF members side by side (BgzfBatch),
 //                                  ONE plain member by several threads (ffq_pgz.h: chunk hand-overs, stitch, CRC pieces),
-//                                  zlib taking over; prints "bytes crc32" (the test compares with Python's gzip)
-//   pool FILE                      the context's helper threads (ffq_pool.h): slices of preads and of host copies of
-//                                  consecutive chunks through ONE queue; compared with a plain read
+//                                  both on the reader's one BatchPool, zlib taking over; prints "bytes crc32" (the test
+//                                  compares with Python's gzip)
+//   pool FILE                      the context's helper threads (ffq_pool.h: ReadPool): slices of preads and of host copies
+//                                  of consecutive chunks through ONE queue; copies either side of the inline threshold,
+//                                  reads across and behind the end of the file; compared with a plain read
+//   batch -                        the fork-join pool (ffq_pool.h: BatchPool) with 0, 1, 3 and 8 threads: 200 runs back to
+//                                  back, every job exactly once, its worker in [0, threads]; a pool that never ran
 //   shards FILE WORLD TAIL HEAD    WORLD threads, each a rank of ffq_shard_host_step over its byte range of FILE: exchange and
 //                                  gather through ffq_shard_world's breakable barrier (csrc/ffq_shard_proto.h), the settle
 //                                  rounds of the protocol; prints the rows' checksum
@@ -89,10 +93,79 @@ static int mode_pool(const char *path)
         got += m;
     }
     for (int i = 0; i < 3; i++) if (used[i]) pool.wait(&cc[i]);
+    bool ok = got == n && memcmp(b.data(), want.data(), (size_t)n) == 0;
+    // copies either side of the inline threshold (two 512 KiB slices), two in flight: each against one memcpy
+    const int64_t MB = 1 << 20, csz[6] = {0, 1, MB - 1, MB, MB + 1, 5 * MB + 3};
+    if (n < 6 * MB) { printf("file too small\n"); return 2; }
+    std::vector<uint8_t> cdst[2];
+    ChunkRead c2[2];
+    for (int i = 0; i <= 6 && ok; i++) {
+        if (i < 6) {
+            cdst[i % 2].assign((size_t)csz[i] + 64, 0xEE);
+            pool.enqueue_copy(cdst[i % 2].data(), want.data() + 77 * i, csz[i], &c2[i % 2]);
+        }
+        if (i > 0) {
+            const int j = i - 1;
+            pool.wait(&c2[j % 2]);
+            std::vector<uint8_t> ref((size_t)csz[j] + 64, 0xEE);
+            memcpy(ref.data(), want.data() + 77 * j, (size_t)csz[j]);
+            if (ref != cdst[j % 2]) { printf("copy of %lld bytes differs\n", (long long)csz[j]); ok = false; }
+        }
+    }
+    // reads inside the file, across its end (short: total() below what was asked) and wholly behind it (0 bytes), two
+    // chunks in flight: each against one pread
+    const int64_t rsz[4] = {1, MB - 1, MB, 3 * MB + 5};
+    struct Rd { int64_t n, pos; };
+    std::vector<Rd> rds;
+    for (const int64_t sz : rsz) {
+        rds.push_back({sz, 4099});
+        rds.push_back({sz, n - sz / 2});
+        rds.push_back({sz, n + 4096});
+    }
+    std::vector<uint8_t> rdst[2];
+    for (size_t i = 0; i <= rds.size() && ok; i++) {
+        if (i < rds.size()) {
+            rdst[i % 2].assign((size_t)rds[i].n + 64, 0xEE);
+            pool.enqueue(fd, rdst[i % 2].data(), rds[i].n, rds[i].pos, &c2[i % 2]);
+        }
+        if (i > 0) {
+            const Rd &r = rds[i - 1];
+            pool.wait(&c2[(i - 1) % 2]);
+            std::vector<uint8_t> ref((size_t)r.n + 64, 0xEE);
+            const int64_t m = ReadPool::read_full(fd, ref.data(), r.n, r.pos, true);
+            const int64_t expect = std::max<int64_t>(0, std::min(r.n, n - r.pos));
+            if (m != expect || c2[(i - 1) % 2].total() != m || memcmp(ref.data(), rdst[(i - 1) % 2].data(), (size_t)m) != 0) {
+                printf("read of %lld bytes at %lld: %lld, one pread %lld\n", (long long)r.n, (long long)r.pos, (long long)c2[(i - 1) % 2].total(), (long long)m);
+                ok = false;
+            }
+        }
+    }
     close(fd);
-    const bool ok = got == n && memcmp(b.data(), want.data(), (size_t)n) == 0;
     printf("%s %lld\n", ok ? "equal" : "DIFFERENT", (long long)n);
     return ok ? 0 : 1;
+}
+
+// BatchPool on its own: every job of a run exactly once, by the caller (worker 0) or a pool thread (1..n)
+static int mode_batch()
+{
+    for (const int nth : {0, 1, 3, 8}) {
+        { BatchPool idle; if (!idle.start(nth)) { printf("no threads\n"); return 2; } }      // started, never run
+        BatchPool pool;
+        if (!pool.start(nth)) { printf("no threads\n"); return 2; }
+        const int sizes[5] = {0, 1, 2, nth + 1, 1000};
+        for (int rep = 0; rep < 200; rep++) {
+            const int nj = sizes[rep % 5];
+            std::vector<int> count((size_t)nj, 0), who((size_t)nj, -1);
+            pool.run(nj, [&](int j, int w) { count[(size_t)j]++; who[(size_t)j] = w; });
+            for (int j = 0; j < nj; j++)
+                if (count[(size_t)j] != 1 || who[(size_t)j] < 0 || who[(size_t)j] > nth) {
+                    printf("DIFFERENT: %d threads, run %d of %d jobs: job %d ran %d times, on worker %d\n", nth, rep, nj, j, count[(size_t)j], who[(size_t)j]);
+                    return 1;
+                }
+        }
+    }
+    printf("equal\n");
+    return 0;
 }
 
 // ---- k ranks as threads over the breakable barrier ------------------------------------------------------------------------
@@ -236,6 +309,7 @@ int main(int argc, char **argv)
     const std::string mode = argv[1];
     if (mode == "gunzip") return mode_gunzip(argv[2], argc > 3 ? atoi(argv[3]) : 4, argc > 4 ? atoll(argv[4]) : (4 << 20));
     if (mode == "pool") return mode_pool(argv[2]);
+    if (mode == "batch") return mode_batch();
     if (mode == "shards") return mode_shards(argv[2], argc > 3 ? atoi(argv[3]) : 3, argc > 4 ? atoll(argv[4]) : (1 << 20), argc > 5 ? atoll(argv[5]) : (1 << 20), false);
     if (mode == "race") {           // (is the detector awake?  two threads, one plain int)
         int x = 0;

@@ -10,7 +10,7 @@ over the 1 GiB file; every process takes the best of its runs, the driver prints
 import json, os, statistics, subprocess, sys, time
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, R)
-REPS = 4
+REPS = int(os.environ.get("AB_STREAM_REPS", "4"))          # processes a side
 N_PLAIN, N_GZ = 1 << 30, 256 << 20
 
 

@@ -19,8 +19,9 @@ int main(int argc, char **argv)
     if (fd < 0) { perror("open"); return 2; }
     struct stat st;
     fstat(fd, &st);
+    BatchPool pool;
     ffq::pgz::Engine e;
-    if (!e.init(fd, threads, st.st_size)) { fprintf(stderr, "init failed\n"); return 2; }
+    if (!e.init(fd, threads, st.st_size, &pool)) { fprintf(stderr, "init failed\n"); return 2; }
     std::vector<uint8_t> out;
     const int64_t piece = 64 << 20;
     std::vector<uint8_t> buf((size_t)piece);
