@@ -11,6 +11,7 @@
 #include "ffq_rows.h"
 #include "ffq_trim.h"
 #include "ffq_adapter.h"
+#include "ffq_poly.h"
 #include "ffq_stats.h"
 #include "ffq_filter.h"
 #include "ffq_compact.h"

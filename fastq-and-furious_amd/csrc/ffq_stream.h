@@ -174,6 +174,8 @@ struct ffq_stream {
     struct { bool on = false; int base = 33, front = 0, back = 0; int64_t last[3] = {0, 0, 0}; } trim;
     // 3' adapter trimming of every fill's table, behind the quality trim and in front of the filter (ffq_stream_set_adapter)
     struct { bool on = false; uint8_t bytes[64] = {0}; int len = 0, err = 0, overlap = 0; int64_t last[3] = {0, 0, 0}; } adapter;
+    // poly-tail trimming of every fill's table: poly-G in front of the adapter trim, poly-X behind it (ffq_stream_set_poly; 0: off)
+    struct { int g = 0, x = 0; int64_t last_g[3] = {0, 0, 0}, last_x[3] = {0, 0, 0}; } poly;
     // push-down: rows by sequence length, one component of the kept rows (ffq_stream_set_filter)
     struct { bool on = false; int64_t min = 0, max = 0; int col = 0, add = 0; int64_t scanned = 0, col_bytes = 0; } filter;
     // content rules of the filter (ffq_stream_set_content) and the eight counts of the last fill's select (with or without them)
@@ -817,6 +819,31 @@ extern "C" int ffq_stream_adapter_trimmed(ffq_stream *s, int64_t stats[3])
     return FFQ_OK;
 }
 
+// Poly-tail trimming in the stream: every fill's table goes through ffq_table_trim_poly in place on the device -- poly-G behind
+// the quality trim and in front of the adapter trim (the G tail behind an adapter spoils the adapter match), poly-X behind the
+// adapter trim.  Per mate, in front of a pair's overlap (fastp runs poly-X behind its overlap trim: a departure).  The other
+// rules are ffq_stream_set_trim's.
+extern "C" int ffq_stream_set_poly(ffq_stream *s, int poly_g_min_len, int poly_x_min_len)
+{
+    if (!s) return fail(FFQ_E_ARG, "ffq_stream_set_poly: NULL stream");
+    if (!poly_g_min_len && !poly_x_min_len) return fail(FFQ_E_ARG, "ffq_stream_set_poly: both steps are off");
+    int rc = poly_g_min_len ? poly_arg("ffq_stream_set_poly", 2, poly_g_min_len) : FFQ_OK;
+    if (!rc && poly_x_min_len) rc = poly_arg("ffq_stream_set_poly", FFQ_POLY_ANY, poly_x_min_len);
+    if (!rc) rc = stream_settable(s, "ffq_stream_set_poly", DECODE_UNTRIMMED, true);
+    if (rc) return rc;
+    s->poly.g = poly_g_min_len; s->poly.x = poly_x_min_len;
+    return FFQ_OK;
+}
+
+// {rows changed, bases removed, rows skipped} by either poly step of the fill ffq_stream_next has just returned
+extern "C" int ffq_stream_poly_trimmed(ffq_stream *s, int64_t stats_g[3], int64_t stats_x[3])
+{
+    if (!s || !stats_g || !stats_x) return fail(FFQ_E_ARG, "ffq_stream_poly_trimmed: NULL argument");
+    if (!s->poly.g && !s->poly.x) return fail(FFQ_E_ARG, "ffq_stream_poly_trimmed: the stream trims no poly tails (ffq_stream_set_poly)");
+    for (int i = 0; i < 3; i++) { stats_g[i] = s->poly.last_g[i]; stats_x[i] = s->poly.last_x[i]; }
+    return FFQ_OK;
+}
+
 // Statistics in the stream: every fill's table is counted on the device (ffq_table_stats, accumulating, no host wait) --
 // FFQ_STATS_IN right behind the scan, FFQ_STATS_OUT on the table that is rendered and copied back -- into two blocks of
 // FFQ_STATS_WORDS(max_cycles) words the stream owns.
@@ -975,7 +1002,7 @@ static int stream_scan(ffq_stream *s, const Fill &f, ffq_scan_result *res)
 }
 
 // ---- the two ends of a mate's chain (a fill of a single stream, either mate of a round of a pair).  front: [keys], [stats IN],
-// [trim], [adapter] on the `n` scanned rows at `rows`, which the trims edit in place
+// [quality trim], [poly-G], [adapter], [poly-X] on the `n` scanned rows at `rows`, which the trims edit in place
 static int chain_front(ffq_stream *s, const Fill &f, int64_t *rows, int64_t n)
 {
     int rc = FFQ_OK;
@@ -987,8 +1014,12 @@ static int chain_front(ffq_stream *s, const Fill &f, int64_t *rows, int64_t n)
         rc = ffq_table_stats(s->c, f.d_buf, f.n, 0, f.add, rows, n, s->stats.base, s->stats.cycles, 1, stream_stats_block(s, FFQ_STATS_IN), nullptr);
     if (!rc && s->trim.on)
         rc = ffq_table_trim_quality(s->c, f.d_buf, f.n, 0, f.add, rows, n, s->trim.base, s->trim.front, s->trim.back, rows, s->trim.last);
-    if (!rc && s->adapter.on)       // (as the quality trim left them)
+    if (!rc && s->poly.g)           // (in front of the adapter: the G tail behind an adapter spoils its match)
+        rc = ffq_table_trim_poly(s->c, f.d_buf, f.n, 0, f.add, rows, n, 2, s->poly.g, rows, s->poly.last_g);
+    if (!rc && s->adapter.on)       // (as the trims in front left them)
         rc = ffq_table_trim_adapter(s->c, f.d_buf, f.n, 0, f.add, rows, n, s->adapter.bytes, s->adapter.len, s->adapter.err, s->adapter.overlap, rows, s->adapter.last);
+    if (!rc && s->poly.x)
+        rc = ffq_table_trim_poly(s->c, f.d_buf, f.n, 0, f.add, rows, n, FFQ_POLY_ANY, s->poly.x, rows, s->poly.last_x);
     return rc;
 }
 
@@ -1008,7 +1039,8 @@ static int chain_back(ffq_stream *s, const Fill &f, const Table &t)
 // at.  With a filter the select REPLACES that table by the kept rows (on the DEVICE, before anything is copied back: a
 // dropped record costs the host nothing, doc/user-guide.rst:153-180); what follows is written once, for either table.
 // This is the one place that states the order of a fill's work on the scan stream, in every configuration:
-//     carry H2D, wait copied[0], wait copied[1], scan, front (the keys of the dedup first, on the rows as scanned), [select:
+//     carry H2D, wait copied[0], wait copied[1], scan, front (the keys of the dedup first, on the rows as scanned; then
+//     [stats IN], [quality trim], [poly-G], [adapter], [poly-X]), [select:
 //     by length, or -- content rules -- by length and content (ffq_table_select_reads), on the rows as the trims left them],
 //     [dedup: the kept rows entered into the stream's set by their keys and the select's ordinals, the first copies kept
 //     (ffq_dedup_select) -- what follows is on the rows that remain], back, [idx D2H], [gather, col D2H, coff D2H],
@@ -1309,7 +1341,7 @@ extern "C" int ffq_pair_wants(ffq_pair *p) { return p && !p->failed ? walk_wants
 // what the per-stream accessors report for a round: zero until the round's chain says otherwise
 static void pair_clear_last(ffq_stream *s)
 {
-    for (int i = 0; i < 3; i++) s->trim.last[i] = s->adapter.last[i] = s->render.last[i] = 0;
+    for (int i = 0; i < 3; i++) s->trim.last[i] = s->adapter.last[i] = s->poly.last_g[i] = s->poly.last_x[i] = s->render.last[i] = 0;
     for (int i = 0; i < FFQ_FILTER_COUNTS; i++) s->content.last[i] = 0;
     s->filter.scanned = 0; s->filter.col_bytes = 0;
 }

@@ -252,11 +252,11 @@ extern "C" int ffq_table_gather_column(ffq_ctx *c, const uint8_t *d_buf, int64_t
     return FFQ_OK;
 }
 
-// ---- the table passes on csrc/ffq_rows.h: quality trim, adapter trim, statistics (ffq_trim.h, ffq_adapter.h, ffq_stats.h) ----
+// ---- the table passes on csrc/ffq_rows.h: quality trim, adapter trim, poly tails, statistics (ffq_trim.h, ffq_adapter.h, ffq_poly.h, ffq_stats.h) ----
 // Workgroups of a pass's launches, each capped: they stride over what there is.  The short rows' launch has WG / ROWS_G rows
 // per workgroup and step; the long rows' launches have a wave per row, and as the list's length is known on the device only,
 // they are sized by the table.
-constexpr int EDIT_GRID_SHORT = 2048, EDIT_GRID_LONG = 1024;                       // the two trims
+constexpr int EDIT_GRID_SHORT = 2048, EDIT_GRID_LONG = 1024;                       // the three trims
 constexpr int STATS_GRID_SHORT = 512, STATS_GRID_CHECK = 512, STATS_GRID_COUNT = 128;   // (two workgroups per CU: their LDS); x tiles
 
 // What the passes check and set up alike.  args_ok: the caller's own pointers; d_dst: what the pass writes on the device.  With
@@ -356,6 +356,33 @@ extern "C" int ffq_table_trim_adapter(ffq_ctx *c, const uint8_t *d_buf, int64_t 
     hipLaunchKernelGGL(k_adapter_long, dim3(rows_grid(n_rows, ADAPTER_WG / 64, EDIT_GRID_LONG)), dim3(ADAPTER_WG), 0, st, d_buf,
                        n_bytes, sentinel ? 1 : 0, add, d_table, ad, adapter_len, err_permille, min_overlap, d_out,
                        (const int64_t *)c->rows_list, blk);
+    return rows_end(c, stats);
+}
+
+// parameters of a poly-tail call, checked: for the table call and for ffq_stream_set_poly
+static_assert(POLY_ANY == FFQ_POLY_ANY, "include/ffq.h");
+static int poly_arg(const char *who, int base, int min_len)
+{
+    if (base != FFQ_POLY_ANY && (base < 0 || base > 3)) return fail(FFQ_E_ARG, "%s: base is 0..3 (A, C, G, T) or FFQ_POLY_ANY", who);
+    if (min_len < POLY_MIN_LEN_LO || min_len > POLY_MIN_LEN_HI) return fail(FFQ_E_ARG, "%s: min_len is %d..%d", who, POLY_MIN_LEN_LO, POLY_MIN_LEN_HI);
+    return FFQ_OK;
+}
+
+extern "C" int ffq_table_trim_poly(ffq_ctx *c, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
+                                   const int64_t *d_table, int64_t n_rows, int base, int min_len, int64_t *d_out, int64_t stats[3])
+{
+    mark_other(c);
+    int rc = poly_arg("ffq_table_trim_poly", base, min_len);
+    RowsBlock *blk = nullptr;
+    if (!rc) rc = rows_begin(c, "ffq_table_trim_poly", stats != nullptr, d_buf, n_bytes, d_table, n_rows, d_out, &blk);
+    if (rc) return rc;
+    stats[0] = stats[1] = stats[2] = 0;
+    if (n_rows == 0) return FFQ_OK;
+    hipStream_t st = c->stream;
+    hipLaunchKernelGGL(k_poly_rows, dim3(rows_grid(n_rows, POLY_WG / ROWS_G, EDIT_GRID_SHORT)), dim3(POLY_WG), 0, st, d_buf, n_bytes,
+                       sentinel ? 1 : 0, add, d_table, n_rows, base, min_len, d_out, c->rows_list, blk);
+    hipLaunchKernelGGL(k_poly_long, dim3(rows_grid(n_rows, POLY_WG / 64, EDIT_GRID_LONG)), dim3(POLY_WG), 0, st, d_buf, n_bytes,
+                       sentinel ? 1 : 0, add, d_table, base, min_len, d_out, (const int64_t *)c->rows_list, blk);
     return rows_end(c, stats);
 }
 

@@ -351,6 +351,75 @@ def adapter_trimmable(buf, pos):
             and b'\n' not in buf[p2:p3])
 
 
+_POLY_BASES = _hip.POLY_BASES
+
+
+def _poly_min_len(name, min_len):
+    """min_len of a poly pass as an int (None: the pass is off) or ValueError naming the setting: the range ffq_table_trim_poly takes."""
+    if min_len is None:
+        return None
+    lo, hi = _hip.POLY_MIN_LEN
+    if isinstance(min_len, bool) or not isinstance(min_len, (int, np.integer)) or not lo <= int(min_len) <= hi:
+        raise ValueError("%s is None or %d..%d" % (name, lo, hi))
+    return int(min_len)
+
+
+def poly_tail_cut(sequence, base=None, min_len=10):
+    """Length that is left of `sequence` (bytes of one record's sequence line) when its poly tail is cut off: the host
+    statement of ffq_table_trim_poly's rule (include/ffq.h states it as a loop).  base: b"A", b"C", b"G" or b"T" -- poly-G is
+    b"G" --, or None for any of the four (poly-X).  The read is walked from its 3' end; per base of the set, the positions that
+    are not that base (either case; N and every other byte match nothing) are counted, and the walk stops at the first position
+    i >= min_len - 1 at which every base of the set has more than min(5, (i + 1) // 8) of them.  A walk that got to min_len
+    positions cuts the read behind the deepest exact copy of the base with the most hits; len(sequence) otherwise."""
+    if base not in _POLY_BASES:
+        raise ValueError('base is b"A", b"C", b"G", b"T" or None')
+    min_len = _poly_min_len("min_len", min_len)
+    if min_len is None:
+        raise ValueError("min_len is 2..65535")
+    n = len(sequence)
+    if n < min_len:
+        return n
+    k = _BASE_CLASS[np.frombuffer(sequence, dtype=np.uint8)[::-1]]           # classes in walk order
+    bases = range(4) if base is None else (_POLY_BASES[base],)
+    i = np.arange(n)
+    allowed = np.minimum(5, (i + 1) // 8)
+    failing = i >= min_len - 1
+    for b in bases:
+        failing &= np.cumsum(k != b) > allowed
+    at = np.flatnonzero(failing)
+    stop = int(at[0]) if at.size else n
+    if stop < min_len:
+        return n
+    hits = [int(np.count_nonzero(k[:stop] == b)) for b in bases]
+    best = bases[hits.index(max(hits))]                                      # (ties: the lowest class)
+    where = np.flatnonzero(k[:stop] == best)
+    return n - 1 - (int(where[-1]) if where.size else -1)
+
+
+def poly_trimmable(buf, pos):
+    """Does the device cut a poly tail off this row (ffq_table_trim_poly's eligibility)?  adapter_trimmable's rule."""
+    return adapter_trimmable(buf, pos)
+
+
+def _poly_pos(buf, pos, base, min_len):
+    """(the six positions -- a list, edited in place -- with the rule applied, bases cut)"""
+    if not poly_trimmable(buf, pos):
+        return pos, 0
+    n = pos[3] - pos[2]
+    cut = poly_tail_cut(buf[pos[2]:pos[3]], base, min_len)
+    pos[3], pos[5] = pos[2] + cut, pos[4] + cut
+    return pos, n - cut
+
+
+class PolyReport:
+    """What filter_fastq / filter_fastq_paired (poly_report=...) fill: poly_g_reads and poly_g_bases, the reads the poly-G step
+    changed and the bases it removed; poly_x_reads and poly_x_bases, the same for poly-X.  Both mates of a pair are added
+    together; every record counts, the dropped ones included.  The same numbers on either route."""
+
+    def __init__(self):
+        self.poly_g_reads = self.poly_g_bases = self.poly_x_reads = self.poly_x_bases = 0
+
+
 class entryfunc_adaptertrim:
     """3' adapter trimming as an entryfunc OBJECT, beside entryfunc_qualitytrim: what `cutadapt [-q CUTOFF] -a ADAPTER
     --no-indels -e E -O O` does to a record.  The quality rule first if quality_cutoff is given (an int -- the 3' end -- or a
@@ -1039,9 +1108,11 @@ def _scanner(entrypos):
     return entrypos, getattr(entrypos, 'open_stream', None)
 
 
-def _configure_stream(st, trim, cutter, content, bounds, column=None, render=False, stats=None, dedup=None):
+def _configure_stream(st, trim, cutter, content, bounds, column=None, render=False, stats=None, dedup=None, poly_g=None, poly_x=None):
     """What a native stream is asked for, in the order its chain works (csrc/ffq_stream.h states it above stream_chain): the
-    quality trim (an entryfunc_qualitytrim), the adapter trim (an entryfunc_adaptertrim), the content rules, the length
+    quality trim (an entryfunc_qualitytrim), the poly tails (poly_g / poly_x: a min_len each; one call for both steps, where
+    the first of them works: poly-G runs in front of the adapter trim, poly-X behind it), the adapter trim (an
+    entryfunc_adaptertrim), the content rules, the length
     filter (bounds: (min_len, max_len)) with the gathered column, the render, the statistics (stats: (qual_base,
     max_cycles)), the duplicate removal (dedup: a DedupRules; the stream takes the keys in front of the trims and asks its set
     behind the filter).  None / False: that setter is not called.  A stage that is added to the chain is added HERE."""
@@ -1049,6 +1120,8 @@ def _configure_stream(st, trim, cutter, content, bounds, column=None, render=Fal
         st.set_dedup(not dedup.count_only, dedup.expected_reads, dedup.max_bytes)
     if trim is not None:
         st.set_trim(trim.cutoff_back, trim.cutoff_front, trim.qual_base)
+    if poly_g is not None or poly_x is not None:
+        st.set_poly(poly_g, poly_x)
     if cutter is not None:
         st.set_adapter(cutter.adapter, cutter.err_permille, cutter.min_overlap)
     if content is not None:
@@ -1063,15 +1136,18 @@ def _configure_stream(st, trim, cutter, content, bounds, column=None, render=Fal
 
 class _MatePlan:
     """What the records of ONE input file go through in filter_fastq (one plan) and filter_fastq_paired (one per mate), said
-    once for both routes: quality trim, adapter trim, the verdict by length and then by content, the counts, the text.  On the
+    once for both routes: quality trim, poly-G, adapter trim, poly-X, the verdict by length and then by content, the counts, the
+    text.  poly_report: a PolyReport the plan ADDS to (a pair's two plans share one; the caller resets it).  On the
     device route the plan configures the file's stream and drains every fill (or round) of it; on the host route it is
     called record by record.  judged=False: the mate is trimmed, counted and written but never dropped (pair_filter "first").
     `dropped`: this file's records by the reason (ContentRules.REASONS) they failed for; `report` (a FilterReport or None) is
     reset and bound to it."""
 
     def __init__(self, quality_cutoff, qual_base, adapter, err_permille, min_overlap, min_len, max_len, content, report, judged=True,
-                 dedup=None):
+                 dedup=None, poly_g=None, poly_x=None, poly_report=None):
         self.qual_base, self.content, self.report, self.judged = qual_base, content, report, judged
+        self.poly_g, self.poly_x = _poly_min_len("poly_g", poly_g), _poly_min_len("poly_x", poly_x)
+        self.poly_report = poly_report
         self.dedup = dedup           # (a single file's DedupRules; a pair's duplicates are the PairStream's, not a mate's)
         self.dropped = dict.fromkeys(ContentRules.REASONS, 0)
         if report is not None:
@@ -1083,7 +1159,7 @@ class _MatePlan:
             front, back = (0, quality_cutoff) if isinstance(quality_cutoff, (int, np.integer)) else quality_cutoff
             self.trim = entryfunc_qualitytrim(back, front, qual_base)            # (checks the ranges)
         if adapter is not None:
-            self.cutter = entryfunc_adaptertrim(adapter, err_permille, min_overlap, quality_cutoff, qual_base)
+            self.cutter = entryfunc_adaptertrim(adapter, err_permille, min_overlap)      # (the adapter alone: the plan orders the trims)
         self.lo = None if min_len is None else int(min_len)
         self.hi = None if max_len is None else int(max_len)
 
@@ -1092,11 +1168,12 @@ class _MatePlan:
         """the file's stream: what is switched on, the render, and the statistics if there is a report"""
         rep = self.report
         _configure_stream(st, self.trim, self.cutter, self.content, None if self.lo is None and self.hi is None else (self.lo, self.hi),
-                          render=True, stats=None if rep is None else (self.qual_base, rep.max_cycles), dedup=self.dedup)
+                          render=True, stats=None if rep is None else (self.qual_base, rep.max_cycles), dedup=self.dedup,
+                          poly_g=self.poly_g, poly_x=self.poly_x)
 
     def drain(self, st, fh_out):
         """One fill (or round) of the stream: its text written with one write, its drops counted; (bytes written, rows
-        rendered, bases the two trims removed)."""
+        rendered, bases the trims removed)."""
         text, (nb, rendered, _skipped) = st.rendered()
         if nb:
             fh_out.write(memoryview(text))
@@ -1108,7 +1185,19 @@ class _MatePlan:
             removed += st.trimmed()[1]
         if self.cutter is not None:
             removed += st.adapter_trimmed()[1]
+        if self.poly_g is not None or self.poly_x is not None:
+            g, x = st.poly_trimmed()
+            removed += g[1] + x[1]
+            self._poly_count(g[0], g[1], x[0], x[1])
         return nb, rendered, removed
+
+    def _poly_count(self, g_reads, g_bases, x_reads, x_bases):
+        rep = self.poly_report
+        if rep is not None:
+            rep.poly_g_reads += g_reads
+            rep.poly_g_bases += g_bases
+            rep.poly_x_reads += x_reads
+            rep.poly_x_bases += x_bases
 
     def finish(self, st):
         """the statistics the stream counted, read back once"""
@@ -1123,10 +1212,17 @@ class _MatePlan:
         length = pos[3] - pos[2]
         if self.report is not None:
             self.report.before.add_pos(buf, pos)
-        if self.cutter is not None:
-            pos = self.cutter.trimmed_pos(buf, pos)          # (the quality rule first, if there is one)
-        elif self.trim is not None:
+        g = x = 0
+        if self.trim is not None:                            # (the chain's order: quality, poly-G, adapter, poly-X)
             pos = self.trim.trimmed_pos(buf, pos)
+        if self.poly_g is not None:
+            pos, g = _poly_pos(buf, list(pos), b"G", self.poly_g)
+        if self.cutter is not None:
+            pos = self.cutter.trimmed_pos(buf, pos)
+        if self.poly_x is not None:
+            pos, x = _poly_pos(buf, list(pos), None, self.poly_x)
+        if g or x:
+            self._poly_count(int(g > 0), g, int(x > 0), x)
         return pos, length - (pos[3] - pos[2])
 
     def verdict(self, buf, pos):
@@ -1195,10 +1291,18 @@ def fastq_stats(fh: typing.BinaryIO, fbufsize: int = 1 << 24, qual_base: int = 3
 FilterResult = namedtuple('FilterResult', 'records_in records_out bases_removed bytes_out')
 
 
+def _check_poly_report(poly_report):
+    """a PolyReport (reset: the plans add to it) or None"""
+    if poly_report is not None:
+        if not isinstance(poly_report, PolyReport):
+            raise TypeError("poly_report must be a PolyReport")
+        poly_report.__init__()
+
+
 def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1 << 24, quality_cutoff=None,
                  qual_base: int = 33, min_len=None, max_len=None, entrypos: typing.Optional[typing.Callable] = None,
                  adapter=None, err_permille: int = 100, min_overlap: int = 3, report=None, content=None, dedup=None,
-                 dedup_report=None) -> FilterResult:
+                 dedup_report=None, poly_g=None, poly_x=None, poly_report=None) -> FilterResult:
     """Trim, filter and WRITE a FASTQ stream: the file `cutadapt -q 20 -m 30` leaves behind, which is what the tables of
     positions of the reference's user guide are kept for in the end ("to avoid saving a FASTQ file after each filtering or
     read-trimming step", doc/user-guide.rst:196-204).  Every record of `fh` is quality-trimmed (quality_cutoff: an int --
@@ -1237,11 +1341,20 @@ def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1
     quality trim cut differently are still one read) was met before in the file is not written -- on the device with the GPU
     scanner (ffq_stream_set_dedup: a set of 64-bit keys that lives there across the fills), with a set of seq_key on the host.
     records_out does not count the duplicates; report.dropped does not either: dedup_report (a DedupReport) has the numbers.
-    A wrapped record has no key and is always written."""
+    A wrapped record has no key and is always written.
+
+    poly_g / poly_x: None, or the min_len (2..65535; fastp's default is 10) of a homopolymer tail trim (poly_tail_cut): poly_g
+    cuts a G tail -- what a two-colour instrument reads where the fragment has ended -- behind the quality trim and IN FRONT
+    of the adapter trim, so that the adapter is still found with its G tail gone (`fastp --trim_poly_g`); poly_x cuts a tail
+    of any one base behind the adapter trim (`--trim_poly_x`).  On the device with the GPU scanner (ffq_stream_set_poly).
+    bases_removed includes what they cut; poly_report (a PolyReport) has the numbers, the same on either route.  Not done:
+    wrapped records, 5' tails, per-base poly-X counts."""
     if content is not None and not isinstance(content, ContentRules):
         raise TypeError("content must be a ContentRules")
     _check_dedup(dedup, dedup_report)
-    plan = _MatePlan(quality_cutoff, qual_base, adapter, err_permille, min_overlap, min_len, max_len, content, report, dedup=dedup)
+    _check_poly_report(poly_report)
+    plan = _MatePlan(quality_cutoff, qual_base, adapter, err_permille, min_overlap, min_len, max_len, content, report, dedup=dedup,
+                     poly_g=poly_g, poly_x=poly_x, poly_report=poly_report)
     hd = _HostDedup(dedup, dedup_report) if dedup is not None else None
     entrypos, open_stream = _scanner(entrypos)
     n_in = n_out = removed = n_bytes = 0
@@ -1452,7 +1565,8 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
                         pair_filter: str = "any", check_names: bool = True, report=None, report2=None,
                         entrypos: typing.Optional[typing.Callable] = None, overlap=None,
                         overlap_report=None, merged_out: typing.Optional[typing.BinaryIO] = None,
-                        merge_report=None, dedup=None, dedup_report=None) -> PairedFilterResult:
+                        merge_report=None, dedup=None, dedup_report=None, poly_g=None, poly_x=None,
+                        poly_report=None) -> PairedFilterResult:
     """filter_fastq for paired-end files: the i-th records of `fh1` and `fh2` are mates, and a pair is written or dropped
     TOGETHER, so that `fh_out1` and `fh_out2` stay record for record in step (`cutadapt -q 20 -a ... -A ... -m 30:20
     --pair-filter=any -o out1 -p out2 in1 in2`).  Every record is trimmed as filter_fastq trims it -- quality_cutoff for both
@@ -1498,6 +1612,11 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
     dedup: a DedupRules; behind the filter and in front of the merge, a pair whose two sequences AS READ were met before as a
     pair (pair_key of the mates' seq_key: ordered) is dropped; the first copy stays.  pairs_out does not count the duplicates,
     `dropped` and the FilterReports do not know them: dedup_report (a DedupReport, in pairs) has the numbers.
+
+    poly_g / poly_x: filter_fastq's, a min_len that applies to both mates; either step works per mate, in front of the overlap:
+    the order is quality, poly-G, adapter, poly-X, overlap, filter, so the overlap and the merge see the rows as the per-mate
+    trims left them (fastp runs its poly-X behind its overlap trim: a departure).  poly_report: a PolyReport, both mates added
+    together.
     Not done: interleaved input or output, base correction inside the overlap of mates that are not merged."""
     if content is not None and not isinstance(content, ContentRules):
         raise TypeError("content must be a ContentRules")
@@ -1526,7 +1645,9 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
         a, b = tuple(x) if isinstance(x, (tuple, list)) else (x, x)
         return (None if a is None else int(a), None if b is None else int(b))
     los, his = per_mate(min_len), per_mate(max_len)
-    plans = tuple(_MatePlan(quality_cutoff, qual_base, a, err_permille, min_overlap, lo, hi, content, rep, judged)
+    _check_poly_report(poly_report)
+    plans = tuple(_MatePlan(quality_cutoff, qual_base, a, err_permille, min_overlap, lo, hi, content, rep, judged, poly_g=poly_g,
+                            poly_x=poly_x, poly_report=poly_report)
                   for a, lo, hi, rep, judged in zip((adapter, adapter2), los, his, (report, report2), (True, pair_filter != "first")))
     dropped = {"mate1_only": 0, "mate2_only": 0, "both": 0}
     entrypos, open_stream = _scanner(entrypos)

@@ -50,7 +50,7 @@ def _add(add, sentinel):
     return (-1 if sentinel else 0) if add is None else add
 
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 OK = 0
 E_NODEVICE, E_HIP, E_ARG, E_NOMEM, E_TABLE_FULL, E_INTERNAL, E_TIMEOUT = -1, -2, -3, -4, -5, -6, -7
 STAGE_NONE, STAGE_HANDOFF, STAGE_SCAN, STAGE_GATHER = 0, 1, 2, 3      # FFQ_SHARD_STAGE_*
@@ -106,10 +106,14 @@ SYMBOLS = (
     "ffq_table_pair_merge", "ffq_pair_set_merge", "ffq_pair_merged",
     "ffq_table_seq_keys", "ffq_seq_key_host", "ffq_pair_key_host", "ffq_dedup_create", "ffq_dedup_destroy", "ffq_dedup_select",
     "ffq_stream_set_dedup", "ffq_stream_dedup_counts", "ffq_pair_set_dedup", "ffq_pair_dedup_counts",
+    "ffq_table_trim_poly", "ffq_stream_set_poly", "ffq_stream_poly_trimmed",
 )
 
 
 FILTER_COUNTS = 8            # FFQ_FILTER_COUNTS: rows kept, dropped by rule 1..6, not judged by content
+POLY_ANY = -1                # FFQ_POLY_ANY: ffq_table_trim_poly's `base` for poly-X (any of the four bases)
+POLY_BASES = {b"A": 0, b"C": 1, b"G": 2, b"T": 3, None: POLY_ANY}
+POLY_MIN_LEN = (2, 65535)    # the range of a poly pass's min_len
 KEY_NONE = 0                 # FFQ_KEY_NONE: a row without a key (ffq_table_seq_keys)
 DEDUP_COUNTS = 6             # FFQ_DEDUP_COUNTS: rows kept, duplicates, rows without a key, distinct keys, slots, rehashes
 
@@ -401,6 +405,7 @@ def lib():
         L.ffq_table_cut.argtypes = [vp, vp, i64, i64, i64, P(i64)]
         L.ffq_table_trim_quality.argtypes = [vp, vp, i64, i32, i64, vp, i64, i32, i32, i32, vp, P(i64)]
         L.ffq_table_trim_adapter.argtypes = [vp, vp, i64, i32, i64, vp, i64, ctypes.c_char_p, i32, i32, i32, vp, P(i64)]
+        L.ffq_table_trim_poly.argtypes = [vp, vp, i64, i32, i64, vp, i64, i32, i32, vp, P(i64)]
         L.ffq_table_stats.argtypes = [vp, vp, i64, i32, i64, vp, i64, i32, i32, i32, vp, P(i64)]
         L.ffq_table_select_reads.argtypes = [vp, vp, i64, i32, i64, vp, i64, i64, i64, P(ContentRulesStruct), vp, vp, P(i64), P(i64)]
         L.ffq_ee_micro_table.argtypes = []
@@ -493,6 +498,8 @@ def lib():
         L.ffq_stream_trimmed.argtypes = [vp, P(i64)]
         L.ffq_stream_set_adapter.argtypes = [vp, ctypes.c_char_p, i32, i32, i32]
         L.ffq_stream_adapter_trimmed.argtypes = [vp, P(i64)]
+        L.ffq_stream_set_poly.argtypes = [vp, i32, i32]
+        L.ffq_stream_poly_trimmed.argtypes = [vp, P(i64), P(i64)]
         L.ffq_stream_set_stats.argtypes = [vp, i32, i32, i32]
         L.ffq_stream_stats.argtypes = [vp, i32, vp, i64]
         L.ffq_stream_set_render.argtypes = [vp]
@@ -899,6 +906,20 @@ class Context:
                                            int(min_overlap), ctypes.c_void_p(d_table if d_out is None else d_out), stats))
         return int(stats[0]), int(stats[1]), int(stats[2])
 
+    def table_trim_poly(self, d_buf, n_bytes, d_table, n_rows, base=b"G", min_len=10, d_out=None, sentinel=True, add=None):
+        """Cut poly tails off the rows of a device table (ffq_table_trim_poly: the walk from the 3' end that include/ffq.h
+        states; base: b"A", b"C", b"G" or b"T" -- poly-G is b"G" --, None for any of the four (poly-X), or the C ABI's own 0..3
+        / POLY_ANY): pos3 and pos5 of every eligible row move inwards, every other row is copied unchanged.  d_out: n_rows rows
+        of room (None: in place); raw device pointers; d_buf / n_bytes / sentinel / add as for table_gather_column.  Returns
+        (rows changed, bases removed, rows skipped)."""
+        add = _add(add, sentinel)
+        base = POLY_BASES.get(base, base)
+        stats = (ctypes.c_int64 * 3)()
+        check(lib().ffq_table_trim_poly(self.handle, ctypes.c_void_p(d_buf), int(n_bytes), int(bool(sentinel)), int(add),
+                                        ctypes.c_void_p(d_table), int(n_rows), int(base), int(min_len),
+                                        ctypes.c_void_p(d_table if d_out is None else d_out), stats))
+        return int(stats[0]), int(stats[1]), int(stats[2])
+
     def table_stats(self, d_buf, n_bytes, d_table, n_rows, d_stats, qual_base=33, max_cycles=512, accumulate=False, sentinel=True,
                     add=None, wait=True):
         """Per-cycle base and quality statistics of the rows of a device table (ffq_table_stats), counted into the
@@ -1289,6 +1310,19 @@ class _Stream:
         stats = (ctypes.c_int64 * 3)()
         check(lib().ffq_stream_adapter_trimmed(self._h, stats))
         return int(stats[0]), int(stats[1]), int(stats[2])
+
+    def set_poly(self, poly_g=None, poly_x=None):
+        """Poly-tail trimming in the stream (ffq_stream_set_poly; before the first fill): poly_g / poly_x are the min_len of
+        that step, None: off (one of them is on).  Poly-G runs behind the quality trim and in front of the adapter trim,
+        poly-X behind the adapter trim."""
+        check(lib().ffq_stream_set_poly(self._h, int(poly_g or 0), int(poly_x or 0)))
+
+    def poly_trimmed(self):
+        """((rows changed, bases removed, rows skipped) by poly-G, the same by poly-X) of the fill the iteration has just
+        yielded; zeros for a step that is off."""
+        g, x = (ctypes.c_int64 * 3)(), (ctypes.c_int64 * 3)()
+        check(lib().ffq_stream_poly_trimmed(self._h, g, x))
+        return (int(g[0]), int(g[1]), int(g[2])), (int(x[0]), int(x[1]), int(x[2]))
 
     def set_stats(self, which, qual_base=33, max_cycles=512):
         """Statistics in the stream (ffq_stream_set_stats; before the first fill): which = STATS_IN (the rows as scanned),

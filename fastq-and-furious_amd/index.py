@@ -213,6 +213,22 @@ def trim_adapter_rows_device(ctx, buf, table, adapter, err_permille=100, min_ove
     return out, stats
 
 
+def poly_rows(buf, table, base=None, min_len=10, shift=0):
+    """Copy of a table with the poly tails cut off, on the host: pos3 and pos5 of every row the rule applies to
+    (_F.poly_trimmable: positions minus `shift` index `buf`) moved to where _F.poly_tail_cut says (base: b"A", b"C", b"G",
+    b"T", or None for any of the four); the same rows, none dropped.  Poly-G runs behind trim_rows and in front of
+    trim_adapter_rows, poly-X behind that.  On the GPU: hip.Context.table_trim_poly."""
+    t = np.array(table, dtype=np.int64).reshape(-1, 6)
+    buf = bytes(buf) if not isinstance(buf, bytes) else buf
+    _F.poly_tail_cut(b"", base, min_len)                # (checks the arguments)
+    for row in t:
+        rel = (row - shift).tolist()
+        if _F.poly_trimmable(buf, rel):
+            cut = _F.poly_tail_cut(buf[rel[2]:rel[3]], base, min_len)
+            row[3], row[5] = row[2] + cut, row[4] + cut
+    return t
+
+
 def stats_rows(buf, table, qual_base=33, max_cycles=512, shift=0):
     """Per-cycle base and quality statistics of the rows of a table, on the host (_F.FastqStats.add_rows: positions minus
     `shift` index `buf`; a row the rule does not apply to counts as skipped)."""

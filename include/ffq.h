@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FFQ_ABI_VERSION 7
+#define FFQ_ABI_VERSION 8
 
 /* scanner status codes -- identical to the reference's module constants
  * (_fastqandfurious.c:7-15,254-262; fastqandfurious.py:19-27)             */
@@ -342,6 +342,39 @@ int ffq_table_trim_quality(ffq_ctx *ctx, const uint8_t *d_buf, int64_t n_bytes, 
 int ffq_table_trim_adapter(ffq_ctx *ctx, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
                            const int64_t *d_table, int64_t n_rows, const uint8_t *adapter, int adapter_len,
                            int err_permille, int min_overlap, int64_t *d_out, int64_t stats[3]);
+
+/* Poly-G / poly-X tail trimming by MODIFYING rows: what `fastp --trim_poly_g` / `--trim_poly_x` are for.  A two-colour
+ * instrument reads "no signal" as G, so a fragment shorter than the read ends in a run of high-quality G that the quality trim
+ * cannot see.  For one row, seq[0..n) = buf[pos2:pos3]; cls(byte) = 0 / 1 / 2 / 3 for A a / C c / G g / T t and 4 for anything
+ * else (the classes of ffq_table_stats; a byte that is no base -- N -- matches nothing); the walk position i = 0, 1, ... is
+ * byte seq[n-1-i]; allowed(i) = min(5, (i + 1) / 8), integer division; the set of bases is S = {base} for base 0..3 (poly-G:
+ * base 2) and S = {0, 1, 2, 3} for FFQ_POLY_ANY (poly-X); min_len in 2..65535:
+ *     mm[b] = 0, hit[b] = 0, last[b] = -1   for b in S;   stop = n
+ *     for i = 0 .. n-1:
+ *         k = cls(seq[n-1-i])
+ *         t[b] = mm[b] + (k != b)                          for b in S
+ *         if i >= min_len - 1 and t[b] > allowed(i) for EVERY b in S:  stop = i; break
+ *         mm = t;  if k in S: hit[k] += 1, last[k] = i
+ *     if stop < min_len: the row is unchanged
+ *     else: b* = the b in S with the most hits (ties: the lowest class); new length len' = n - 1 - last[b*]
+ * and the row becomes pos0, pos1, pos2, pos2 + len', pos4, pos4 + len'.  Inside the first min_len - 1 positions nothing stops
+ * the walk.  A row that is trimmed had exactly one base still passing at stop - 1 -- two bases mismatch each other at every
+ * position, so they cannot both be within `allowed` -- and the tie rule never decides a trimmed row.  The tail is cut back to
+ * its deepest exact b*: mismatching bytes at the inner edge of the tail stay on the read.  A read that is all tail goes to
+ * length 0.  This is fastp's rule in spirit -- one mismatch allowed per eight positions, at most five; min_len is its
+ * poly_g_min_len / poly_x_min_len (default 10) -- but it has NOT been checked against fastp's source, which was not at hand.
+ * One known departure: N never matches, whereas fastp's poly-X counts N for every base.  Eligibility is
+ * ffq_table_trim_adapter's: pos2..pos5 - add all >= 0, in order, inside the buffer (with sentinel, coordinate 0 is the
+ * virtual "\n": never read), pos3 - pos2 == pos5 - pos4 and no byte of the whole sequence is "\n" (a wrapped record is left
+ * alone even when its last line is all G); every other row is copied unchanged and counted as skipped; a row of length 0 is
+ * eligible and unchanged.  No byte outside the row's own checked sequence range is read; the quality line is never read.
+ * d_buf / n_bytes / sentinel / add: as for ffq_table_gather_column.  d_out: n_rows rows; it MAY be d_table.  Both tables
+ * 16-byte aligned.  stats = {rows changed, bases removed, rows skipped}.  FFQ_E_ARG: base outside 0..3 and not FFQ_POLY_ANY,
+ * min_len outside 2..65535, misaligned tables, a scan pending on the context.  One host wait.  Not done: wrapped records, 5'
+ * tails, cutadapt's --nextseq-trim quality weighting.                                                                  */
+#define FFQ_POLY_ANY (-1)
+int ffq_table_trim_poly(ffq_ctx *ctx, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
+                        const int64_t *d_table, int64_t n_rows, int base, int min_len, int64_t *d_out, int64_t stats[3]);
 
 /* Per-cycle base and quality statistics of a table, counted on the device: what the QC report of fastp / FastQC is made
  * of.  d_stats: DEVICE memory, 16-byte aligned, FFQ_STATS_WORDS(C) uint64 words with C = max_cycles; overwritten
@@ -741,6 +774,15 @@ int  ffq_stream_trimmed(ffq_stream *s, int64_t stats[3]);
  * ffq_stream_next has just returned.                                                                                  */
 int  ffq_stream_set_adapter(ffq_stream *s, const uint8_t *adapter, int adapter_len, int err_permille, int min_overlap);
 int  ffq_stream_adapter_trimmed(ffq_stream *s, int64_t stats[3]);
+/* Poly-tail trimming in the stream (the rules of ffq_stream_set_trim: before the first ffq_stream_next, not with
+ * FFQ_F_DECODE_QUAL): every fill's table goes through ffq_table_trim_poly in place on the device -- poly-G (base 2,
+ * poly_g_min_len; 0: off) BEHIND the quality trim and IN FRONT of the adapter trim, so that the adapter match is not spoiled
+ * by the G tail behind the adapter; poly-X (FFQ_POLY_ANY, poly_x_min_len; 0: off) BEHIND the adapter trim.  Both are per
+ * mate and in front of a pair's overlap analysis; fastp runs its poly-X behind its overlap trim: a departure.  At least one
+ * of the two is on; a min_len that is on is 2..65535.  ffq_stream_poly_trimmed: {rows changed, bases removed, rows skipped}
+ * of either step for the fill ffq_stream_next has just returned (zeros for a step that is off).                        */
+int  ffq_stream_set_poly(ffq_stream *s, int poly_g_min_len, int poly_x_min_len);
+int  ffq_stream_poly_trimmed(ffq_stream *s, int64_t stats_g[3], int64_t stats_x[3]);
 /* Content rules in the stream (the rules of ffq_stream_set_trim: before the first ffq_stream_next, not with
  * FFQ_F_DECODE_QUAL): the select of every fill judges the rows by ffq_table_select_reads -- as the trims left them, which
  * is cutadapt's order -- and everything behind it (statistics OUT, the render, the column gather, ffq_stream_selected) sees
