@@ -1,4 +1,5 @@
-"""A BGZF writer (what bgzip produces; SAM specification section 4.1) in a few lines of zlib: for tests, the bench
+"""A BGZF writer (what bgzip produces; SAM specification section 4.1) in a few lines of zlib: for tests, the bench, and the
+host route of filter_fastq(compress="bgzf") -- the GPU route deflates on the device (hip.Context.deflate_bgzf)
 
 A BGZF file is a series of gzip members of at most 64 KiB of data each, every one with a "BC" extra
 subfield that holds the member's total length - 1, and an empty member as the end-of-file marker.

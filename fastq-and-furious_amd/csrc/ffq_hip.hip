@@ -20,6 +20,7 @@
 #include "ffq_render.h"
 #include "ffq_merge.h"
 #include "ffq_dedup.h"
+#include "ffq_deflate.h"
 #include "ffq_pool.h"
 #include "ffq_mem.h"
 
@@ -208,6 +209,8 @@ struct ffq_ctx {
     DevBuf<uint8_t> filter_verdict;     // ffq_table_select_reads: a verdict byte per row
     DevBuf<uint8_t> filter_verdict2;    //   ... and per row of the second mate (ffq_table_select_pairs)
     DevBuf<int64_t> render_list;        // ffq_table_render_fastq: (row, place in the output) of the rows left to the wave-per-row launch
+    DevBuf<uint32_t> deflate_slots;     // ffq_deflate_bgzf: candidates, then tokens, DFL_BLOCK words per workgroup of its capped grid
+    DevBuf<uint8_t> deflate_members;    //   ... and a DFL_SLOT bytes slot per block, where its member is built
     DevBuf<FaHdr> fa_hdr;               // FASTA scan: starts, the last start
     // staging for the host-buffer entry points
     DevBuf<uint8_t> stage_d;

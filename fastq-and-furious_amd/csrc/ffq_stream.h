@@ -76,6 +76,8 @@ struct StreamBufs {
     Mirror<int64_t> coff;
     // rendering (ffq_stream_set_render): the fill's FASTQ text
     Mirror<uint8_t> ren;
+    // ... and, compressed (ffq_stream_set_compress), its BGZF members: what is copied back in the text's place
+    Mirror<uint8_t> bgz;
     ReadPool *pool = nullptr;    // the context's helper threads (not owned)
 };
 
@@ -182,6 +184,8 @@ struct ffq_stream {
     struct { bool on = false; ffq_content_rules rules = {}; int64_t last[FFQ_FILTER_COUNTS] = {0, 0, 0, 0, 0, 0, 0, 0}; } content;
     // FASTQ text of every fill's table, behind the trim and the filter (ffq_stream_set_render)
     struct { bool on = false; int64_t last[3] = {0, 0, 0}; } render;
+    // ... written as BGZF members on the device, which go back in its place (ffq_stream_set_compress)
+    struct { bool on = false; int64_t last[FFQ_DEFLATE_COUNTS] = {0, 0, 0, 0}; } compress;
     // duplicate removal (ffq_stream_set_dedup): the stream's own set, the keys of the fill's rows as scanned, the rows and
     // ordinals that remain behind it, and the counts summed over the fills.  keys_on alone: a pair takes the keys (ffq_pair_set_dedup)
     struct : DedupStage {
@@ -404,22 +408,38 @@ struct Table { const int64_t *d_rows; int64_t n; };
 // back enqueued.  BOUND: the rows of a fill are records of the fill that do not overlap, and a scanned record never
 // renders longer than it was -- "@header\n", "sequence\n" and "quality\n" are copied, the '+' line becomes the bare "+\n"
 // (it had at least that), a trim only takes bytes away -- except a record whose quality ends with the buffer, without a newline, which gains one
-// byte: a fill of `len` bytes renders to at most len + 1.
+// byte: a fill of `len` bytes renders to at most len + 1.  A stream that compresses (ffq_stream_set_compress) deflates the
+// text where it lies, behind the render, and only the members go back.
 static int stream_render(ffq_stream *s, const Fill &f, const Table &t)
 {
     StreamBufs *b = s->b;
     int64_t *last = s->render.last;
     last[0] = last[1] = last[2] = 0;
+    for (int64_t &x : s->compress.last) x = 0;
     if (t.n <= 0) return FFQ_OK;
     int rc = FFQ_OK;
     if (f.n + 64 > b->ren.d.cap) {
         NearGpu near(s->c);
         rc = stream_grow(b->ren, f.n + 64, "ffq_stream: no memory for %lld rendered bytes", f.n + 64);
     }
+    const int64_t bgz_cap = ffq_deflate_bgzf_bound(f.n + 1);
+    if (!rc && s->compress.on && bgz_cap > b->bgz.d.cap) {
+        NearGpu near(s->c);
+        rc = stream_grow(b->bgz, bgz_cap, "ffq_stream: no memory for %lld compressed bytes", bgz_cap);
+    }
     if (!rc) rc = ffq_table_render_fastq(s->c, f.d_buf, f.n, 0, f.add, t.d_rows, t.n, b->ren.d, f.n + 1, nullptr, last);
     if (rc == FFQ_E_TABLE_FULL)
         return fail(FFQ_E_INTERNAL, "ffq_stream: a fill of %lld bytes rendered to %lld", (long long)f.n, (long long)last[0]);
     if (rc) return rc;
+    if (s->compress.on) {
+        int64_t *z = s->compress.last;
+        rc = ffq_deflate_bgzf(s->c, b->ren.d, last[0], b->bgz.d, b->bgz.d.cap, nullptr, z);
+        if (rc == FFQ_E_TABLE_FULL)
+            return fail(FFQ_E_INTERNAL, "ffq_stream: %lld rendered bytes deflated to %lld", (long long)last[0], (long long)z[1]);
+        if (rc) return rc;
+        if (z[1] > 0) HIPCHK(hipMemcpyAsync(b->bgz.h, b->bgz.d, (size_t)z[1], hipMemcpyDeviceToHost, s->c->stream));
+        return FFQ_OK;
+    }
     if (last[0] > 0) HIPCHK(hipMemcpyAsync(b->ren.h, b->ren.d, (size_t)last[0], hipMemcpyDeviceToHost, s->c->stream));
     return FFQ_OK;
 }
@@ -912,8 +932,33 @@ extern "C" int ffq_stream_rendered(ffq_stream *s, const uint8_t **h_fastq, int64
 {
     if (!s || !h_fastq || !n_fastq_bytes) return fail(FFQ_E_ARG, "ffq_stream_rendered: NULL argument");
     if (!s->render.on) return fail(FFQ_E_ARG, "ffq_stream_rendered: the stream does not render (ffq_stream_set_render)");
-    *h_fastq = s->b->ren.h; *n_fastq_bytes = s->render.last[0];
+    *h_fastq = s->compress.on ? nullptr : s->b->ren.h.p;      // (compressed: the text never leaves the device)
+    *n_fastq_bytes = s->render.last[0];
     if (stats) for (int i = 0; i < 3; i++) stats[i] = s->render.last[i];
+    return FFQ_OK;
+}
+
+// Compression in a stream that renders (before the first ffq_stream_next): every fill's text is written as BGZF members on
+// the device (ffq_deflate_bgzf) behind the render, and the members are copied back instead of the text.
+extern "C" int ffq_stream_set_compress(ffq_stream *s, int mode)
+{
+    if (!s) return fail(FFQ_E_ARG, "ffq_stream_set_compress: NULL stream");
+    if (mode != FFQ_COMPRESS_NONE && mode != FFQ_COMPRESS_BGZF) return fail(FFQ_E_ARG, "ffq_stream_set_compress: mode is FFQ_COMPRESS_NONE or FFQ_COMPRESS_BGZF");
+    if (!s->render.on) return fail(FFQ_E_ARG, "ffq_stream_set_compress: the stream does not render (ffq_stream_set_render first)");
+    const int rc = stream_settable(s, "ffq_stream_set_compress", nullptr, true);
+    if (rc) return rc;
+    s->compress.on = mode == FFQ_COMPRESS_BGZF;
+    return FFQ_OK;
+}
+
+// the BGZF members of the fill ffq_stream_next has just returned and {bytes in, bytes out, members, members stored}; pinned
+// memory, valid until the next call
+extern "C" int ffq_stream_compressed(ffq_stream *s, const uint8_t **h_bgzf, int64_t *n_bytes, int64_t stats[FFQ_DEFLATE_COUNTS])
+{
+    if (!s || !h_bgzf || !n_bytes) return fail(FFQ_E_ARG, "ffq_stream_compressed: NULL argument");
+    if (!s->compress.on) return fail(FFQ_E_ARG, "ffq_stream_compressed: the stream does not compress (ffq_stream_set_compress)");
+    *h_bgzf = s->b->bgz.h; *n_bytes = s->compress.last[1];
+    if (stats) for (int i = 0; i < FFQ_DEFLATE_COUNTS; i++) stats[i] = s->compress.last[i];
     return FFQ_OK;
 }
 
@@ -1214,6 +1259,10 @@ struct ffq_pair {
         Mirror<int64_t> ord;
         Mirror<uint8_t> text;
         int64_t last[FFQ_MERGE_COUNTS] = {0, 0, 0, 0, 0, 0};
+        // the merged text as BGZF members (ffq_pair_set_compress), which go back in its place
+        bool compress = false;
+        Mirror<uint8_t> bgz;
+        int64_t zlast[FFQ_DEFLATE_COUNTS] = {0, 0, 0, 0};
     } merge;
     // duplicate pairs dropped behind the pair select (ffq_pair_set_dedup): the pair's own set, the rows of both mates and the
     // ordinals that remain, the counts summed over the rounds
@@ -1303,8 +1352,30 @@ extern "C" int ffq_pair_merged(ffq_pair *p, const uint8_t **h_text, int64_t *n_b
 {
     if (!p || !h_text || !n_bytes) return fail(FFQ_E_ARG, "ffq_pair_merged: NULL argument");
     if (!p->merge.on) return fail(FFQ_E_ARG, "ffq_pair_merged: the pair does not merge (ffq_pair_set_merge)");
-    *h_text = p->merge.text.h; *n_bytes = p->merge.last[2];
+    *h_text = p->merge.compress ? nullptr : p->merge.text.h.p;      // (compressed: the text never leaves the device)
+    *n_bytes = p->merge.last[2];
     if (counts) for (int i = 0; i < FFQ_MERGE_COUNTS; i++) counts[i] = p->merge.last[i];
+    return FFQ_OK;
+}
+
+// the merged text of every round as BGZF members (ffq_stream_set_compress's way; the mates' own text is their streams' business)
+extern "C" int ffq_pair_set_compress(ffq_pair *p, int mode)
+{
+    if (!p) return fail(FFQ_E_ARG, "ffq_pair_set_compress: NULL pair");
+    if (mode != FFQ_COMPRESS_NONE && mode != FFQ_COMPRESS_BGZF) return fail(FFQ_E_ARG, "ffq_pair_set_compress: mode is FFQ_COMPRESS_NONE or FFQ_COMPRESS_BGZF");
+    if (p->started) return fail(FFQ_E_ARG, "ffq_pair_set_compress: the walk has begun (call it before the first ffq_pair_next)");
+    if (!p->merge.on) return fail(FFQ_E_ARG, "ffq_pair_set_compress: the pair does not merge (ffq_pair_set_merge first)");
+    p->merge.compress = mode == FFQ_COMPRESS_BGZF;
+    return FFQ_OK;
+}
+
+// the last round's merged text as BGZF members and {bytes in, bytes out, members, members stored}
+extern "C" int ffq_pair_merged_bgzf(ffq_pair *p, const uint8_t **h_bgzf, int64_t *n_bytes, int64_t stats[FFQ_DEFLATE_COUNTS])
+{
+    if (!p || !h_bgzf || !n_bytes) return fail(FFQ_E_ARG, "ffq_pair_merged_bgzf: NULL argument");
+    if (!p->merge.compress) return fail(FFQ_E_ARG, "ffq_pair_merged_bgzf: the pair does not compress its merged reads (ffq_pair_set_compress)");
+    *h_bgzf = p->merge.bgz.h; *n_bytes = p->merge.zlast[1];
+    if (stats) for (int i = 0; i < FFQ_DEFLATE_COUNTS; i++) stats[i] = p->merge.zlast[i];
     return FFQ_OK;
 }
 
@@ -1342,6 +1413,7 @@ extern "C" int ffq_pair_wants(ffq_pair *p) { return p && !p->failed ? walk_wants
 static void pair_clear_last(ffq_stream *s)
 {
     for (int i = 0; i < 3; i++) s->trim.last[i] = s->adapter.last[i] = s->poly.last_g[i] = s->poly.last_x[i] = s->render.last[i] = 0;
+    for (int64_t &x : s->compress.last) x = 0;
     for (int i = 0; i < FFQ_FILTER_COUNTS; i++) s->content.last[i] = 0;
     s->filter.scanned = 0; s->filter.col_bytes = 0;
 }
@@ -1362,8 +1434,16 @@ static int pair_chain_merge(ffq_pair *p, const int64_t *const rows[2], const int
     for (int k = 0; k < 2 && !rc; k++) rc = chain_back(p->m[k].s, p->m[k].f, Table{p->merge.rest[k].p, n_rest});
     if (rc) return rc;
     if (n_rest > 0) HIPCHK(hipMemcpyAsync(p->merge.ord.h, p->merge.ord.d, (size_t)n_rest * 8, hipMemcpyDeviceToHost, c->stream));
-    if (p->merge.last[2] > 0)
+    if (p->merge.compress) {
+        int64_t *z = p->merge.zlast;
+        rc = ffq_deflate_bgzf(c, p->merge.text.d, p->merge.last[2], p->merge.bgz.d, p->merge.bgz.d.cap, nullptr, z);
+        if (rc == FFQ_E_TABLE_FULL)
+            return fail(FFQ_E_INTERNAL, "ffq_pair: %lld merged bytes deflated to %lld", (long long)p->merge.last[2], (long long)z[1]);
+        if (rc) return rc;
+        if (z[1] > 0) HIPCHK(hipMemcpyAsync(p->merge.bgz.h, p->merge.bgz.d, (size_t)z[1], hipMemcpyDeviceToHost, c->stream));
+    } else if (p->merge.last[2] > 0) {
         HIPCHK(hipMemcpyAsync(p->merge.text.h, p->merge.text.d, (size_t)p->merge.last[2], hipMemcpyDeviceToHost, c->stream));
+    }
     *n_out = n_rest;
     return FFQ_OK;
 }
@@ -1407,12 +1487,14 @@ static int pair_chain(ffq_pair *p, int64_t m, int64_t *n_out, int64_t *differ)
         // (the merged text of a pair is shorter than its two records together: header + 2 (n1 + n2 - 1) + 6 bytes)
         const int64_t text_cap = p->m[0].f.n + p->m[1].f.n + 64;
         if (p->merge.insert.cap < m || p->merge.rest[0].cap < 6 * m || p->merge.rest[1].cap < 6 * m || p->merge.ord.d.cap < m ||
-            p->merge.text.d.cap < text_cap) {
+            p->merge.text.d.cap < text_cap || (p->merge.compress && p->merge.bgz.d.cap < ffq_deflate_bgzf_bound(text_cap))) {
             HIPCHK(hipStreamSynchronize(c->stream));
             rc = stream_grow(p->merge.insert, m, "ffq_pair: no memory for %lld insert sizes", m);
             for (int k = 0; k < 2 && !rc; k++) rc = stream_grow(p->merge.rest[k], 6 * m, "ffq_pair: no memory for %lld unmerged rows", m);
             if (!rc) rc = stream_grow(p->merge.ord, m, "ffq_pair: no memory for %lld unmerged pairs", m);
             if (!rc) rc = stream_grow(p->merge.text, text_cap, "ffq_pair: no memory for %lld merged bytes", text_cap);
+            if (!rc && p->merge.compress)
+                rc = stream_grow(p->merge.bgz, ffq_deflate_bgzf_bound(text_cap), "ffq_pair: no memory for %lld compressed bytes", ffq_deflate_bgzf_bound(text_cap));
         }
         d_insert = p->merge.insert.p;
     }
@@ -1447,6 +1529,7 @@ extern "C" int ffq_pair_next(ffq_pair *p, int64_t *n_pairs_in, int64_t *n_pairs_
     for (int i = 0; i < 5; i++) p->last_pairs[i] = 0;
     for (int i = 0; i < FFQ_OVERLAP_COUNTS; i++) p->overlap.last[i] = 0;
     for (int i = 0; i < FFQ_MERGE_COUNTS; i++) p->merge.last[i] = 0;
+    for (int64_t &x : p->merge.zlast) x = 0;
     p->last_out = 0;
     p->started = true;
     for (int k = 0; k < 2; k++) pair_clear_last(p->m[k].s);

@@ -688,6 +688,65 @@ extern "C" int ffq_table_render_fastq(ffq_ctx *c, const uint8_t *d_buf, int64_t 
     return FFQ_OK;
 }
 
+// ---- BGZF members from device bytes (csrc/ffq_deflate.h) --------------------------------------
+static_assert(DFL_BLOCK == FFQ_BGZF_BLOCK_BYTES && DFL_SEG == FFQ_DEFLATE_SEG_BYTES && DFL_ROUND == FFQ_DEFLATE_ROUND_POSITIONS &&
+              DEFLATE_COUNTS == FFQ_DEFLATE_COUNTS, "include/ffq.h");
+
+static int64_t deflate_blocks(int64_t n_bytes) { return (n_bytes + DFL_BLOCK - 1) / DFL_BLOCK; }
+
+extern "C" int64_t ffq_deflate_bgzf_bound(int64_t n_bytes) { return n_bytes <= 0 ? 0 : n_bytes + DFL_OVERHEAD * deflate_blocks(n_bytes); }
+
+extern "C" void ffq_bgzf_eof_block(uint8_t out[28]) { if (out) dfl_eof_member(out); }
+
+// everything a deflate of n_bytes needs, grown (before anything is enqueued: growing waits for the stream)
+static int deflate_reserve(ffq_ctx *c, int64_t n_bytes)
+{
+    const int64_t n_blocks = deflate_blocks(n_bytes);
+    int rc = grow_dev(c, c->deflate_slots, std::min<int64_t>(n_blocks, DEFLATE_GRID) * DFL_BLOCK);
+    if (!rc) rc = grow_dev(c, c->deflate_members, n_blocks * DFL_SLOT);
+    if (!rc) rc = grow_dev(c, c->col_sum, n_blocks);
+    return rc;
+}
+
+// the three launches, behind whatever the stream holds; the counters in *blk (cleared by the caller), the total there too
+static int deflate_enqueue(ffq_ctx *c, hipStream_t st, const uint8_t *d_src, int64_t n_bytes, uint8_t *d_out, int64_t out_cap,
+                           int64_t *d_member_off, DeflateBlock *blk)
+{
+    const int64_t n_blocks = deflate_blocks(n_bytes);
+    hipLaunchKernelGGL(k_deflate_members, dim3((unsigned)std::min<int64_t>(n_blocks, DEFLATE_GRID)), dim3(DFL_LANES), 0, st, d_src, n_bytes,
+                       n_blocks, c->deflate_slots.p, c->deflate_members.p, c->col_sum.p, blk);
+    if (int rc = launch_scan_i64v(c, st, c->col_sum, n_blocks, n_blocks, c->col_res)) return rc;
+    hipLaunchKernelGGL(k_deflate_pack, dim3((unsigned)std::min<int64_t>(n_blocks, 4096)), dim3(256), 0, st, (const uint8_t *)c->deflate_members.p,
+                       (const long long *)c->col_sum.p, n_blocks, (const DevRes *)c->col_res.p, d_out, out_cap, d_member_off, blk);
+    return FFQ_OK;
+}
+
+extern "C" int ffq_deflate_bgzf(ffq_ctx *c, const uint8_t *d_src, int64_t n_bytes, uint8_t *d_out, int64_t out_cap, int64_t *d_member_off,
+                                int64_t stats[FFQ_DEFLATE_COUNTS])
+{
+    static const char *const who = "ffq_deflate_bgzf";
+    mark_other(c);
+    if (!c || !stats || n_bytes < 0 || out_cap < 0 || (n_bytes > 0 && !d_src) || (out_cap > 0 && !d_out))
+        return fail(FFQ_E_ARG, "%s: bad argument", who);
+    if (!aligned({d_member_off}, 8)) return fail(FFQ_E_ARG, "%s: d_member_off must be 8-byte aligned", who);
+    int rc = no_pending(c, who);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    for (int i = 0; i < FFQ_DEFLATE_COUNTS; i++) stats[i] = 0;
+    if (n_bytes == 0) return no_rows_offsets(c, d_member_off);
+    if ((rc = deflate_reserve(c, n_bytes))) return rc;
+    hipStream_t st = c->stream;
+    DeflateBlock *blk = nullptr;
+    if ((rc = call_blk_begin(c, &blk))) return rc;
+    if ((rc = deflate_enqueue(c, st, d_src, n_bytes, d_out, out_cap, d_member_off, blk))) return rc;
+    const DeflateBlock *h = nullptr;
+    if ((rc = call_blk_end(c, &h))) return rc;
+    stats[0] = n_bytes; stats[1] = (int64_t)h->total; stats[2] = deflate_blocks(n_bytes); stats[3] = (int64_t)h->stored;
+    if (stats[1] > out_cap)
+        return fail(FFQ_E_TABLE_FULL, "output holds %lld bytes, the members have %lld", (long long)out_cap, (long long)stats[1]);
+    return FFQ_OK;
+}
+
 // ---- the mates of a pair merged into one read (csrc/ffq_merge.h) ------------------------------
 static_assert(MRG_MAX_LEN == FFQ_OVERLAP_MAX_LEN && MERGE_COUNTS == FFQ_MERGE_COUNTS, "include/ffq.h");
 

@@ -1134,6 +1134,71 @@ def _configure_stream(st, trim, cutter, content, bounds, column=None, render=Fal
         st.set_stats(_hip.STATS_IN | _hip.STATS_OUT, stats[0], stats[1])
 
 
+class CompressReport:
+    """What filter_fastq(compress="bgzf", compress_report=...) fills, summed over every output it compresses: the bytes of
+    text that went in, the bytes of the BGZF members that came out (the EOF markers not counted), the members, and those
+    of them that are stored blocks (text that does not compress); `ratio` = bytes_in / bytes_out."""
+
+    def __init__(self):
+        self.bytes_in = self.bytes_out = self.members = self.members_stored = 0
+
+    @property
+    def ratio(self):
+        return self.bytes_in / self.bytes_out if self.bytes_out else 0.0
+
+    def _add(self, stats):
+        self.bytes_in += stats[0]
+        self.bytes_out += stats[1]
+        self.members += stats[2]
+        self.members_stored += stats[3]
+
+
+def _check_compress(compress, compress_report):
+    if compress not in _hip.COMPRESS_MODES:
+        raise ValueError("compress: %r is not one of %s" % (compress, sorted(_hip.COMPRESS_MODES, key=str)))
+    if compress_report is not None and compress is None:
+        raise ValueError("compress_report needs compress")
+    if compress_report is not None and not isinstance(compress_report, CompressReport):
+        raise TypeError("compress_report must be a CompressReport")
+    if compress_report is not None:
+        compress_report.__init__()
+
+
+class _BgzfSink:
+    """One output file written as BGZF.  The device route hands it whole members, a fill's or a round's at a time
+    (members()); the host route hands it text (write()), which it cuts into bgzf.block members of BGZF_BLOCK_BYTES -- other
+    bytes than the device's, the same text.  finish() writes what is left and, once, the EOF marker."""
+
+    def __init__(self, fh, report):
+        self.fh, self.report, self.buf = fh, report, bytearray()
+
+    def members(self, members, stats):
+        if stats[1]:
+            self.fh.write(memoryview(members))
+        if self.report is not None:
+            self.report._add(stats)
+
+    def _block(self, chunk):
+        from . import bgzf
+        m = bgzf.block(chunk, 1)
+        self.fh.write(m)
+        if self.report is not None:
+            self.report._add((len(chunk), len(m), 1, int((m[18] & 6) == 0)))
+
+    def write(self, text):
+        self.buf += text
+        size = _hip.BGZF_BLOCK_BYTES
+        while len(self.buf) >= size:
+            self._block(bytes(self.buf[:size]))
+            del self.buf[:size]
+
+    def finish(self):
+        if self.buf:
+            self._block(bytes(self.buf))
+            self.buf = bytearray()
+        self.fh.write(_hip.BGZF_EOF)
+
+
 class _MatePlan:
     """What the records of ONE input file go through in filter_fastq (one plan) and filter_fastq_paired (one per mate), said
     once for both routes: quality trim, poly-G, adapter trim, poly-X, the verdict by length and then by content, the counts, the
@@ -1141,11 +1206,13 @@ class _MatePlan:
     device route the plan configures the file's stream and drains every fill (or round) of it; on the host route it is
     called record by record.  judged=False: the mate is trimmed, counted and written but never dropped (pair_filter "first").
     `dropped`: this file's records by the reason (ContentRules.REASONS) they failed for; `report` (a FilterReport or None) is
-    reset and bound to it."""
+    reset and bound to it.  compress ("bgzf" or None): the text is written as BGZF -- sink() wraps an output file for it,
+    and everything that is written goes through what sink() returned; compress_report: a CompressReport the plan's sinks ADD to."""
 
     def __init__(self, quality_cutoff, qual_base, adapter, err_permille, min_overlap, min_len, max_len, content, report, judged=True,
-                 dedup=None, poly_g=None, poly_x=None, poly_report=None):
+                 dedup=None, poly_g=None, poly_x=None, poly_report=None, compress=None, compress_report=None):
         self.qual_base, self.content, self.report, self.judged = qual_base, content, report, judged
+        self.compress, self.compress_report = compress, compress_report
         self.poly_g, self.poly_x = _poly_min_len("poly_g", poly_g), _poly_min_len("poly_x", poly_x)
         self.poly_report = poly_report
         self.dedup = dedup           # (a single file's DedupRules; a pair's duplicates are the PairStream's, not a mate's)
@@ -1170,12 +1237,25 @@ class _MatePlan:
         _configure_stream(st, self.trim, self.cutter, self.content, None if self.lo is None and self.hi is None else (self.lo, self.hi),
                           render=True, stats=None if rep is None else (self.qual_base, rep.max_cycles), dedup=self.dedup,
                           poly_g=self.poly_g, poly_x=self.poly_x)
+        if self.compress is not None:
+            st.set_compress(self.compress)
+
+    def sink(self, fh_out):
+        """what an output file is written through: itself, or with compress its BGZF writer"""
+        return fh_out if self.compress is None or fh_out is None else _BgzfSink(fh_out, self.compress_report)
+
+    def end(self, out):
+        """behind the last write to what sink() returned: a compressed file gets its last member and the EOF marker"""
+        if isinstance(out, _BgzfSink):
+            out.finish()
 
     def drain(self, st, fh_out):
-        """One fill (or round) of the stream: its text written with one write, its drops counted; (bytes written, rows
-        rendered, bases the trims removed)."""
+        """One fill (or round) of the stream: its text -- or, compressed, its members -- written with one write, its drops
+        counted; (bytes of TEXT written, rows rendered, bases the trims removed)."""
         text, (nb, rendered, _skipped) = st.rendered()
-        if nb:
+        if self.compress is not None:
+            fh_out.members(*st.compressed())
+        elif nb:
             fh_out.write(memoryview(text))
         if st.filtered and self.judged:
             for reason, k in zip(ContentRules.REASONS, st.filter_counts()[1:7]):
@@ -1302,7 +1382,8 @@ def _check_poly_report(poly_report):
 def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1 << 24, quality_cutoff=None,
                  qual_base: int = 33, min_len=None, max_len=None, entrypos: typing.Optional[typing.Callable] = None,
                  adapter=None, err_permille: int = 100, min_overlap: int = 3, report=None, content=None, dedup=None,
-                 dedup_report=None, poly_g=None, poly_x=None, poly_report=None) -> FilterResult:
+                 dedup_report=None, poly_g=None, poly_x=None, poly_report=None, compress=None,
+                 compress_report=None) -> FilterResult:
     """Trim, filter and WRITE a FASTQ stream: the file `cutadapt -q 20 -m 30` leaves behind, which is what the tables of
     positions of the reference's user guide are kept for in the end ("to avoid saving a FASTQ file after each filtering or
     read-trimming step", doc/user-guide.rst:196-204).  Every record of `fh` is quality-trimmed (quality_cutoff: an int --
@@ -1348,13 +1429,23 @@ def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1
     of the adapter trim, so that the adapter is still found with its G tail gone (`fastp --trim_poly_g`); poly_x cuts a tail
     of any one base behind the adapter trim (`--trim_poly_x`).  On the device with the GPU scanner (ffq_stream_set_poly).
     bases_removed includes what they cut; poly_report (a PolyReport) has the numbers, the same on either route.  Not done:
-    wrapped records, 5' tails, per-base poly-X counts."""
+    wrapped records, 5' tails, per-base poly-X counts.
+
+    compress: None, or "bgzf": `fh_out` (a binary file object, NOT a gzip.open one) is written as BGZF, what bgzip writes --
+    gzip members of at most BGZF_BLOCK_BYTES of text each, which `zcat`, gzip.open and this package's own readers
+    (automagic_open, hip.gunzip_fd, hip.bgzf_range, readfastq_iter_range) read, the last three member-parallel.  With the
+    GPU scanner every fill's text is deflated on the device behind the render (ffq_stream_set_compress) and only the members
+    come back, one fh_out.write per fill; with any other scanner the text is buffered and written as zlib level 1 members:
+    other bytes, the same text.  The EOF marker is written once at the end.  bytes_out stays the bytes of TEXT; compress_report
+    (a CompressReport) has the compressed size.  Not done: members aligned to records, a .gzi index, plain gzip."""
     if content is not None and not isinstance(content, ContentRules):
         raise TypeError("content must be a ContentRules")
     _check_dedup(dedup, dedup_report)
     _check_poly_report(poly_report)
+    _check_compress(compress, compress_report)
     plan = _MatePlan(quality_cutoff, qual_base, adapter, err_permille, min_overlap, min_len, max_len, content, report, dedup=dedup,
-                     poly_g=poly_g, poly_x=poly_x, poly_report=poly_report)
+                     poly_g=poly_g, poly_x=poly_x, poly_report=poly_report, compress=compress, compress_report=compress_report)
+    fh_out = plan.sink(fh_out)
     hd = _HostDedup(dedup, dedup_report) if dedup is not None else None
     entrypos, open_stream = _scanner(entrypos)
     n_in = n_out = removed = n_bytes = 0
@@ -1371,6 +1462,7 @@ def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1
                 if end_state != _END_OK and end_state != _END_REFILL:
                     _raise_for_end(end_state, err_offset)
             plan.finish(st)
+            plan.end(fh_out)
             if hd is not None:
                 hd.report._from_counts(st.dedup_counts())
         finally:
@@ -1391,6 +1483,7 @@ def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1
             fh_out.write(text)
             n_out += 1
             n_bytes += len(text)
+    plan.end(fh_out)
     return FilterResult(n_in, n_out, removed, n_bytes)
 
 
@@ -1566,7 +1659,7 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
                         entrypos: typing.Optional[typing.Callable] = None, overlap=None,
                         overlap_report=None, merged_out: typing.Optional[typing.BinaryIO] = None,
                         merge_report=None, dedup=None, dedup_report=None, poly_g=None, poly_x=None,
-                        poly_report=None) -> PairedFilterResult:
+                        poly_report=None, compress=None, compress_report=None) -> PairedFilterResult:
     """filter_fastq for paired-end files: the i-th records of `fh1` and `fh2` are mates, and a pair is written or dropped
     TOGETHER, so that `fh_out1` and `fh_out2` stay record for record in step (`cutadapt -q 20 -a ... -A ... -m 30:20
     --pair-filter=any -o out1 -p out2 in1 in2`).  Every record is trimmed as filter_fastq trims it -- quality_cutoff for both
@@ -1617,7 +1710,10 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
     the order is quality, poly-G, adapter, poly-X, overlap, filter, so the overlap and the merge see the rows as the per-mate
     trims left them (fastp runs its poly-X behind its overlap trim: a departure).  poly_report: a PolyReport, both mates added
     together.
-    Not done: interleaved input or output, base correction inside the overlap of mates that are not merged."""
+    Not done: interleaved input or output, base correction inside the overlap of mates that are not merged.
+    compress / compress_report: filter_fastq's, over `fh_out1`, `fh_out2` and `merged_out`: each is written as a BGZF file of
+    its own, each mate's text deflated by its stream and the merged text by the pair (ffq_pair_set_compress); the report sums
+    over the three."""
     if content is not None and not isinstance(content, ContentRules):
         raise TypeError("content must be a ContentRules")
     if pair_filter not in _PAIR_FILTERS:
@@ -1646,14 +1742,21 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
         return (None if a is None else int(a), None if b is None else int(b))
     los, his = per_mate(min_len), per_mate(max_len)
     _check_poly_report(poly_report)
+    _check_compress(compress, compress_report)
     plans = tuple(_MatePlan(quality_cutoff, qual_base, a, err_permille, min_overlap, lo, hi, content, rep, judged, poly_g=poly_g,
-                            poly_x=poly_x, poly_report=poly_report)
+                            poly_x=poly_x, poly_report=poly_report, compress=compress, compress_report=compress_report)
                   for a, lo, hi, rep, judged in zip((adapter, adapter2), los, his, (report, report2), (True, pair_filter != "first")))
     dropped = {"mate1_only": 0, "mate2_only": 0, "both": 0}
     entrypos, open_stream = _scanner(entrypos)
     pairs_in = pairs_out = removed = 0
     n_bytes = [0, 0]
-    outs = (fh_out1, fh_out2)
+    # (compress: all three outputs are BGZF, filter_fastq's way, and compress_report sums over them)
+    outs = (plans[0].sink(fh_out1), plans[1].sink(fh_out2))
+    merged_out = plans[0].sink(merged_out)
+
+    def end_outputs():
+        for out in outs + (merged_out,):
+            plans[0].end(out)
     sts = []
     if open_stream is not None:
         for fh in (fh1, fh2):
@@ -1675,13 +1778,17 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
                 ps.set_overlap(overlap)
             if merged_out is not None:
                 ps.set_merge()
+                if compress is not None:
+                    ps.set_compress(compress)
             if dedup is not None:
                 ps.set_dedup(not dedup.count_only, dedup.expected_reads, dedup.max_bytes)
             for n_in, n_out, end_state, err_mate, err_offset in ps:
                 pairs_in += n_in
                 if merged_out is not None:           # (n_out: the kept pairs that were not merged)
                     text, mc = ps.merged()
-                    if mc[2]:
+                    if compress is not None:
+                        merged_out.members(*ps.merged_bgzf())
+                    elif mc[2]:
                         merged_out.write(memoryview(text))
                     pairs_out += n_out + mc[0]
                     mrep.pairs_merged += mc[0]
@@ -1715,6 +1822,7 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
                     _raise_for_pair_end(end_state, err_mate, err_offset, names)
             for plan, st in zip(plans, sts):
                 plan.finish(st)
+            end_outputs()
             if overlap is not None:
                 orep.insert_hist = ps.overlap()[1]
             if hd is not None:
@@ -1824,6 +1932,7 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
             text = plans[k].text(r[3], r[4])
             outs[k].write(text)
             n_bytes[k] += len(text)
+    end_outputs()
     return PairedFilterResult(pairs_in, pairs_out, removed, n_bytes[0], n_bytes[1], dropped)
 
 

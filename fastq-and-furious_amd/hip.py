@@ -50,7 +50,7 @@ def _add(add, sentinel):
     return (-1 if sentinel else 0) if add is None else add
 
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 OK = 0
 E_NODEVICE, E_HIP, E_ARG, E_NOMEM, E_TABLE_FULL, E_INTERNAL, E_TIMEOUT = -1, -2, -3, -4, -5, -6, -7
 STAGE_NONE, STAGE_HANDOFF, STAGE_SCAN, STAGE_GATHER = 0, 1, 2, 3      # FFQ_SHARD_STAGE_*
@@ -107,6 +107,8 @@ SYMBOLS = (
     "ffq_table_seq_keys", "ffq_seq_key_host", "ffq_pair_key_host", "ffq_dedup_create", "ffq_dedup_destroy", "ffq_dedup_select",
     "ffq_stream_set_dedup", "ffq_stream_dedup_counts", "ffq_pair_set_dedup", "ffq_pair_dedup_counts",
     "ffq_table_trim_poly", "ffq_stream_set_poly", "ffq_stream_poly_trimmed",
+    "ffq_deflate_bgzf_bound", "ffq_deflate_bgzf", "ffq_bgzf_eof_block",
+    "ffq_stream_set_compress", "ffq_stream_compressed", "ffq_pair_set_compress", "ffq_pair_merged_bgzf",
 )
 
 
@@ -115,6 +117,13 @@ POLY_ANY = -1                # FFQ_POLY_ANY: ffq_table_trim_poly's `base` for po
 POLY_BASES = {b"A": 0, b"C": 1, b"G": 2, b"T": 3, None: POLY_ANY}
 POLY_MIN_LEN = (2, 65535)    # the range of a poly pass's min_len
 KEY_NONE = 0                 # FFQ_KEY_NONE: a row without a key (ffq_table_seq_keys)
+BGZF_BLOCK_BYTES = 65280     # FFQ_BGZF_BLOCK_BYTES: the bytes ffq_deflate_bgzf puts into a member (what bgzip does)
+DEFLATE_SEG_BYTES = 256      # FFQ_DEFLATE_SEG_BYTES: a match does not cross a multiple of this inside its block
+DEFLATE_ROUND_POSITIONS = 1024   # FFQ_DEFLATE_ROUND_POSITIONS: a position finds candidates of earlier rounds only
+COMPRESS_NONE, COMPRESS_BGZF = 0, 1      # FFQ_COMPRESS_*: ffq_stream_set_compress, ffq_pair_set_compress
+COMPRESS_MODES = {None: COMPRESS_NONE, "bgzf": COMPRESS_BGZF}
+BGZF_EOF = bytes([0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0])    # ffq_bgzf_eof_block
+DEFLATE_COUNTS = 4           # FFQ_DEFLATE_COUNTS: bytes in, bytes out, members, members stored
 DEDUP_COUNTS = 6             # FFQ_DEDUP_COUNTS: rows kept, duplicates, rows without a key, distinct keys, slots, rehashes
 
 
@@ -442,6 +451,11 @@ def lib():
         L.ffq_stream_set_content.argtypes = [vp, P(ContentRulesStruct)]
         L.ffq_stream_filter_counts.argtypes = [vp, P(i64)]
         L.ffq_table_render_fastq.argtypes = [vp, vp, i64, i32, i64, vp, i64, vp, i64, vp, P(i64)]
+        L.ffq_deflate_bgzf_bound.argtypes = [i64]
+        L.ffq_deflate_bgzf_bound.restype = i64
+        L.ffq_deflate_bgzf.argtypes = [vp, vp, i64, vp, i64, vp, P(i64)]
+        L.ffq_bgzf_eof_block.argtypes = [vp]
+        L.ffq_bgzf_eof_block.restype = None
         L.ffq_table_gather_column.argtypes = [vp, vp, i64, i32, i64, vp, i64, i32, i32, i32, i32, vp, i64, vp, P(i64)]
         L.ffq_stream_open.argtypes = [vp, i32, i64, P(vp)]
         L.ffq_stream_next.argtypes = [vp, P(vp), P(i64), P(i32), P(i64), P(vp), P(i64), P(i64)]
@@ -504,6 +518,10 @@ def lib():
         L.ffq_stream_stats.argtypes = [vp, i32, vp, i64]
         L.ffq_stream_set_render.argtypes = [vp]
         L.ffq_stream_rendered.argtypes = [vp, P(vp), P(i64), P(i64)]
+        L.ffq_stream_set_compress.argtypes = [vp, i32]
+        L.ffq_stream_compressed.argtypes = [vp, P(vp), P(i64), P(i64)]
+        L.ffq_pair_set_compress.argtypes = [vp, i32]
+        L.ffq_pair_merged_bgzf.argtypes = [vp, P(vp), P(i64), P(i64)]
         L.ffq_stream_selected.argtypes = [vp, P(vp), P(i64), P(vp), P(vp), P(i64)]
         L.ffq_stream_quals.argtypes = [vp, P(vp), P(vp), P(i64)]
         L.ffq_stream_close.restype = None
@@ -948,12 +966,38 @@ class Context:
         check(rc, allow=(E_TABLE_FULL,))
         return rc, (int(stats[0]), int(stats[1]), int(stats[2]))
 
+    def deflate_bgzf(self, d_src, n_bytes, d_out, out_cap, d_member_off=None):
+        """n_bytes of device memory written as BGZF members, deflated on the device (ffq_deflate_bgzf; include/ffq.h has the
+        container, the bound and the match rule): a member per BGZF_BLOCK_BYTES, back to back in d_out, the same bytes for
+        the same input on every call.  d_out: out_cap bytes -- deflate_bgzf_bound(n_bytes) always suffices --, any alignment;
+        d_member_off: members + 1 offsets or None; raw device pointers.  The empty member that ends a BGZF file is not
+        written (bgzf_eof_block()).  Returns (rc, (bytes in, bytes out, members, members stored)); rc is OK or E_TABLE_FULL
+        (out_cap too small: stats[1] is the need, d_out is not touched)."""
+        stats = (ctypes.c_int64 * DEFLATE_COUNTS)()
+        rc = lib().ffq_deflate_bgzf(self.handle, ctypes.c_void_p(d_src) if d_src else None, int(n_bytes),
+                                    ctypes.c_void_p(d_out) if d_out else None, int(out_cap),
+                                    ctypes.c_void_p(d_member_off) if d_member_off else None, stats)
+        check(rc, allow=(E_TABLE_FULL,))
+        return rc, tuple(int(x) for x in stats)
+
     def synth_single(self, dptr, first, count, seed=42):
         check(lib().ffq_synth_single(self.handle, ctypes.c_void_p(dptr), int(first), int(count), int(seed)))
 
     def synth_wrapped(self, dptr, d_start, first, count, seed=43):
         check(lib().ffq_synth_wrapped(self.handle, ctypes.c_void_p(dptr), ctypes.c_void_p(d_start),
                                       int(first), int(count), int(seed)))
+
+
+def deflate_bgzf_bound(n_bytes):
+    """ffq_deflate_bgzf_bound: bytes that hold the BGZF members of n_bytes whatever they are, n + 31 per block."""
+    return int(lib().ffq_deflate_bgzf_bound(int(n_bytes)))
+
+
+def bgzf_eof_block():
+    """ffq_bgzf_eof_block: the 28 bytes of the empty member that ends a BGZF file."""
+    out = (ctypes.c_uint8 * 28)()
+    lib().ffq_bgzf_eof_block(out)
+    return bytes(out)
 
 
 def seq_key_host(sequence):
@@ -1214,6 +1258,21 @@ class Shard:
             pass
 
 
+def _compress_mode(mode):
+    if mode not in COMPRESS_MODES:
+        raise ValueError("compress: %r is not one of %s" % (mode, sorted(COMPRESS_MODES, key=str)))
+    return COMPRESS_MODES[mode]
+
+
+def _members_of(call, handle):
+    bp, nb = ctypes.c_void_p(), ctypes.c_int64()
+    stats = (ctypes.c_int64 * DEFLATE_COUNTS)()
+    check(call(handle, ctypes.byref(bp), ctypes.byref(nb), stats))
+    members = (np.ctypeslib.as_array((ctypes.c_uint8 * nb.value).from_address(bp.value)) if nb.value
+               else np.zeros(0, dtype=np.uint8))
+    return members, tuple(int(x) for x in stats)
+
+
 class _Stream:
     """What the native stream front ends (ffq_stream_*) have in common.  Iterating yields
     (rows, fill, fill_offset, end_state, err_offset): `rows` int64[n][6] absolute offsets and
@@ -1350,9 +1409,24 @@ class _Stream:
         tp, nb = ctypes.c_void_p(), ctypes.c_int64()
         stats = (ctypes.c_int64 * 3)()
         check(lib().ffq_stream_rendered(self._h, ctypes.byref(tp), ctypes.byref(nb), stats))
-        text = (np.ctypeslib.as_array((ctypes.c_uint8 * nb.value).from_address(tp.value)) if nb.value
-                else np.zeros(0, dtype=np.uint8))
+        if nb.value and not tp.value:
+            text = None                          # (set_compress: the text never leaves the device; compressed() has the members)
+        else:
+            text = (np.ctypeslib.as_array((ctypes.c_uint8 * nb.value).from_address(tp.value)) if nb.value
+                    else np.zeros(0, dtype=np.uint8))
         return text, (int(stats[0]), int(stats[1]), int(stats[2]))
+
+    def set_compress(self, mode="bgzf"):
+        """The text compressed in the stream (ffq_stream_set_compress; behind set_render, before the first fill): every fill's
+        text is written as BGZF members on the device and only those are copied back (compressed()); rendered() then has
+        None for the text and its three counts as before.  mode: "bgzf" or None."""
+        check(lib().ffq_stream_set_compress(self._h, _compress_mode(mode)))
+
+    def compressed(self):
+        """(members, (bytes in, bytes out, members, members stored)) of the fill the iteration has just yielded
+        (set_compress): `members` is a uint8 view of the stream's pinned memory, whole BGZF members, valid until the next
+        iteration step.  The fills' members one behind another and bgzf_eof_block() at the end are a BGZF file."""
+        return _members_of(lib().ffq_stream_compressed, self._h)
 
     def selected(self):
         """(index int64[kept], n_scanned, col int8[] or None, coloff int64[kept + 1] or None) of the fill the iteration has
@@ -1599,6 +1673,15 @@ class PairStream:
         text = (np.ctypeslib.as_array((ctypes.c_uint8 * nb.value).from_address(tp.value))
                 if nb.value and tp.value else np.zeros(0, dtype=np.uint8))
         return text, [int(x) for x in counts]
+
+    def set_compress(self, mode="bgzf"):
+        """The round's merged text as BGZF members (ffq_pair_set_compress; behind set_merge, before the first step):
+        merged_bgzf() has them, merged() then has an empty text and its counts.  The mates' own text is their streams'."""
+        check(lib().ffq_pair_set_compress(self._h, _compress_mode(mode)))
+
+    def merged_bgzf(self):
+        """_Stream.compressed() for the merged reads of the round just yielded (ffq_pair_merged_bgzf)."""
+        return _members_of(lib().ffq_pair_merged_bgzf, self._h)
 
     def close(self):
         if self._h:

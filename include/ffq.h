@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FFQ_ABI_VERSION 8
+#define FFQ_ABI_VERSION 9
 
 /* scanner status codes -- identical to the reference's module constants
  * (_fastqandfurious.c:7-15,254-262; fastqandfurious.py:19-27)             */
@@ -580,6 +580,38 @@ int ffq_table_render_fastq(ffq_ctx *ctx, const uint8_t *d_buf, int64_t n_bytes, 
                            const int64_t *d_table, int64_t n_rows, uint8_t *d_out, int64_t out_cap, int64_t *d_off,
                            int64_t stats[3]);
 
+/* Device bytes written as BGZF (SAM specification 4.1: what bgzip writes, gzip members that say how long they are), deflated
+ * on the device: what a pipeline that ends in .fq.gz does with the text ffq_table_render_fastq leaves there.
+ * CONTAINER.  d_src[0, n_bytes) is cut into blocks of FFQ_BGZF_BLOCK_BYTES = 65280 bytes, the last one shorter.  Block k
+ * becomes one gzip member: 18 bytes of header (1f 8b 08 04, no time, XFL 0, OS ff, XLEN 6, the subfield "BC" with BSIZE =
+ * the member's bytes - 1), ONE raw deflate stream of one block with BFINAL set, CRC-32 and ISIZE.  The members stand back to
+ * back in d_out; d_member_off (NULL, or members + 1 words): where each begins, and the total.  The empty member that ends a
+ * BGZF FILE is not written: that is the file writer's business (ffq_bgzf_eof_block gives its 28 bytes).
+ * BOUND.  The deflate block is BTYPE=2 -- literals and (length, distance) pairs under two Huffman codes built from the
+ * block's own counts, at most 15 bits, the code lengths themselves under a third of at most 7 bits, without run-length
+ * symbols -- unless that stream would be longer than a stored block: then the member is one stored block (BTYPE=0), data +
+ * 31 bytes.  So no member exceeds 65536 bytes, and ffq_deflate_bgzf_bound(n) = n + 31 * ceil(n / 65280) holds any result.
+ * MATCH RULE.  Positions are taken in rounds of FFQ_DEFLATE_ROUND_POSITIONS.  Every position of a round with four bytes
+ * behind it first looks up, under a hash of those four bytes, the most recent position of an EARLIER round with that hash;
+ * then the round's positions are entered.  The second candidate of a position is distance 1 (runs).  The block is cut into
+ * segments of FFQ_DEFLATE_SEG_BYTES and each is parsed greedily on its own: at a position the longer candidate is taken if
+ * it agrees in 4 bytes or more (a tie: distance 1), at most 258 and never across the end of the segment; else the byte is a
+ * literal.  A candidate farther back than 32768 is refused.  No lazy matching.  The output is DETERMINISTIC: the same
+ * bytes give the same members on every call and every device.
+ * stats = {bytes in, bytes out, members, members stored}.  n_bytes == 0 is valid and writes nothing (d_member_off: one
+ * zero).  FFQ_E_TABLE_FULL: out_cap is smaller than the total -- stats[1] holds the need, d_member_off is written, d_out
+ * is not touched.  FFQ_E_ARG: a scan pending on the context.  Scratch is the context's and grows with n_bytes (a 64 KiB
+ * slot per block, in which the member is built before its place is known).  One host wait.  d_src and d_out: no alignment
+ * asked, and they must not overlap.                                                                                     */
+#define FFQ_BGZF_BLOCK_BYTES 65280
+#define FFQ_DEFLATE_SEG_BYTES 256
+#define FFQ_DEFLATE_ROUND_POSITIONS 1024
+#define FFQ_DEFLATE_COUNTS 4
+int64_t ffq_deflate_bgzf_bound(int64_t n_bytes);
+int ffq_deflate_bgzf(ffq_ctx *ctx, const uint8_t *d_src, int64_t n_bytes, uint8_t *d_out, int64_t out_cap,
+                     int64_t *d_member_off /* NULL or members + 1 */, int64_t stats[FFQ_DEFLATE_COUNTS]);
+void ffq_bgzf_eof_block(uint8_t out[28]);
+
 /* The two mates of a pair merged into ONE read and rendered as FASTQ text (`fastp --merge`, PEAR, FLASH, NGmerge): mate 2
  * is read backwards and complemented, and inside the overlap the base and the quality come from whichever mate is surer.
  * For input pair k, with j = d_ord ? d_ord[k] : k, ins = d_insert[j], a / qa = mate 1's sequence and quality (n1 bytes),
@@ -813,6 +845,17 @@ int  ffq_stream_stats(ffq_stream *s, int which /* exactly one */, uint64_t *h_ou
  * that ends with the quality's last byte is FFQ_END_ERR_FINAL_QUAL) renders with one.                               */
 int  ffq_stream_set_render(ffq_stream *s);
 int  ffq_stream_rendered(ffq_stream *s, const uint8_t **h_fastq, int64_t *n_fastq_bytes, int64_t stats[3]);
+/* The text compressed in the stream (before the first ffq_stream_next; FFQ_E_ARG unless the stream renders): with
+ * FFQ_COMPRESS_BGZF every fill's text is written as BGZF members on the device, behind the render (ffq_deflate_bgzf over at
+ * most fill + 1 bytes), and ONLY THE MEMBERS are copied back.  ffq_stream_compressed: the members of the fill
+ * ffq_stream_next has just returned -- whole members, so the fills' members written one behind another, and
+ * ffq_bgzf_eof_block once at the end, are a BGZF file -- and {bytes in, bytes out, members, members stored}; pinned memory,
+ * valid until the next call.  ffq_stream_rendered then keeps its three counts and returns *h_fastq = NULL: the text never
+ * leaves the device.  A stream without this setter does exactly what it did.                                          */
+#define FFQ_COMPRESS_NONE 0
+#define FFQ_COMPRESS_BGZF 1
+int  ffq_stream_set_compress(ffq_stream *s, int mode);
+int  ffq_stream_compressed(ffq_stream *s, const uint8_t **h_bgzf, int64_t *n_bytes, int64_t stats[FFQ_DEFLATE_COUNTS]);
 /* Duplicate removal in the stream (the rules of ffq_stream_set_trim: before the first ffq_stream_next, FFQ_E_ARG with
  * FFQ_F_DECODE_QUAL).  The stream owns one ffq_dedup (expected_keys, max_bytes: ffq_dedup_create's) for its whole life.  The
  * keys of every fill's rows are taken in FRONT of the trims, on the rows as scanned (ffq_table_seq_keys) -- two PCR copies
@@ -925,6 +968,10 @@ int  ffq_stream_push(ffq_stream *s, int64_t n, int eof);
  * number; pairs[0] of ffq_pair_selected still counts every pair the filter kept.  ffq_pair_merged: the round's merged text
  * (pinned memory, valid until the next ffq_pair_next; *n_bytes == counts[2]) and the six counts of ffq_table_pair_merge;
  * counts may be NULL.  FFQ_E_ARG without ffq_pair_set_merge.
+ * ffq_pair_set_compress (FFQ_COMPRESS_BGZF; before the first ffq_pair_next only; FFQ_E_ARG without ffq_pair_set_merge): the
+ * round's merged text is written as BGZF members on the device (ffq_stream_set_compress's way; each mate's own text is its
+ * stream's business) and ffq_pair_merged_bgzf hands out the members and {bytes in, bytes out, members, members stored};
+ * ffq_pair_merged then returns *h_text = NULL and keeps its counts.
  * ffq_pair_set_dedup (before the first ffq_pair_next only; FFQ_E_ARG if either stream has a dedup of its own -- ffq_pair_open
  * refuses such a stream, too): the pair owns one ffq_dedup; both mates' fronts take their keys over the round's window, on
  * the rows as scanned, and behind ffq_table_select_pairs, in front of the merge, the kept pairs are entered by their PAIR
@@ -942,6 +989,8 @@ int  ffq_pair_set_overlap(ffq_pair *p, const ffq_overlap_rules *rules);
 int  ffq_pair_overlap(ffq_pair *p, int64_t counts[FFQ_OVERLAP_COUNTS], uint64_t *h_hist, int64_t cap_words);
 int  ffq_pair_set_merge(ffq_pair *p, int on);
 int  ffq_pair_merged(ffq_pair *p, const uint8_t **h_text, int64_t *n_bytes, int64_t counts[FFQ_MERGE_COUNTS]);
+int  ffq_pair_set_compress(ffq_pair *p, int mode);
+int  ffq_pair_merged_bgzf(ffq_pair *p, const uint8_t **h_bgzf, int64_t *n_bytes, int64_t stats[FFQ_DEFLATE_COUNTS]);
 int  ffq_pair_set_dedup(ffq_pair *p, int drop, int64_t expected_keys, int64_t max_bytes);
 int  ffq_pair_dedup_counts(ffq_pair *p, int64_t counts[FFQ_DEDUP_COUNTS]);
 void ffq_pair_close(ffq_pair *p);
