@@ -23,6 +23,7 @@
 #include "ffq_deflate.h"
 #include "ffq_pool.h"
 #include "ffq_mem.h"
+#include "ffq_scanwalk.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -68,33 +69,19 @@ struct ScanArgs {
     int qual_add; int64_t *d_table; int64_t table_cap; int8_t *d_qual; int64_t qual_cap; int64_t *d_qoff;
 };
 
-struct ScanState {
+// A scan between ffq_scan_submit and ffq_scan_wait: what the ladder decides on (ScanWalk, ffq_scanwalk.h) and what the
+// launches need beside it.
+struct ScanState : ScanWalk {
     bool active = false;
     ScanArgs a{};
-    // the caller's FFQ_F_* flags, read once at submit
-    bool serial = false, decode = false, single_pass = false, force_ranked = false, force_general = false;
-    bool poll_result = false, no_timing = false;
-    int retries = 0;
-    int repairs = 0;          // repair passes of the general kernels (reported with retries)
-    bool dense_cfg = false, fast4_failed = false;
-    bool probe4 = false;      // the front carries the fast path's kernels as a probe (see InputMemory::fast4_skip)
-    bool untimed = false;     // FFQ_F_NO_TIMING: no marks around the index kernel, which may start beside the previous front's last kernel
-
-    bool dense4 = false;      // the fast path's row kernel is the DENSE instantiation (it met a dense tile on this buffer, or the context remembers one)
-    bool fused = false;       // the front is the single-pass index + decode kernel (ffq_fused.h)
-    bool no_fused = false;    // ... which did not stand on this buffer: the two-pass kernels take it
-    bool in_place = false;    // the single pass of this front writes in place (k_scan_ident) rather than segments (k_scan_seg)
-    bool seg_refused = false; // the segmented single pass met a shape it cannot take (a long line): the in-place one is next
     unsigned long long poll_seq = 0;   // FFQ_F_POLL_RESULT: the front ends in a publisher that writes this number; no end event
-    bool wide = false;        // the index kernel of this scan also wrote EVERY byte decoded in place (k_scan_lines<.., WIDE>): the general
-                              //   path's decode in one pass -- no tier of this scan runs a decode kernel, qoff[i] = pos4's offset in the buffer
-    bool go_ranked = false;   // the front is the index kernel only: the list-ranking tier follows at the wait
-    bool index_done = false;  // the line index of this buffer is built (a later tier re-uses it)
-    bool lite_ran = false;    // the general front of this scan used the lean kernel
-    int stage = 0;            // what the pending front consisted of: 1 fast four-line path, 2 general path
-    int64_t ntiles = 0;
-    int ngroups = 0;
 };
+
+static_assert(WALK_ERR_POOL == ERR_POOL && WALK_ERR_INTERNAL == ERR_INTERNAL && WALK_ERR_DSTAGE == ERR_DSTAGE &&
+              WALK_FZ_BAD_SHAPE == (int32_t)FZ_BAD_SHAPE && WALK_FZ_BAD_INDEX == (int32_t)FZ_BAD_INDEX && WALK_TILE == TILE &&
+              WALK_SEG_STRIDE == SG_STRIDE && WALK_POOL_MIN == (unsigned long long)POOL_NB * TILE &&
+              WALK_PATH_IN_PLACE == FFQ_PATH_IN_PLACE && WALK_E_INTERNAL == FFQ_E_INTERNAL,
+              "ffq_scanwalk.h disagrees with ffq_dev.h, ffq_fused.h or include/ffq.h");
 
 // What the library knows about the tail of a scan stream (kept in the context that owns the stream; contexts that share it
 // point there).  FFQ_F_NO_TIMING lets a front start its index kernel without a barrier in front -- beside the previous scan's
@@ -107,25 +94,6 @@ struct StreamTail {
     bool exposed = false;                // ffq_ctx_stream() handed the stream out: others may enqueue on it unseen
     const void *out_p[3] = {nullptr, nullptr, nullptr};      // that scan's outputs (table, qualities, quality offsets)
     size_t out_n[3] = {0, 0, 0};
-};
-
-// How long a verdict about a context's input holds: the scans that follow take the tier it chose without asking again.
-constexpr int HOLD_OFF = 15;
-
-// What a context remembers about its recent input: which tier its next scans start with.  ffq_ctx_forget resets all of it.
-struct InputMemory {
-    bool fast4_remember = false;         // the recent input was not plain four-line: scans start with the general kernels
-    int fast4_skip = 0;                  //   ... and this many of them do so without asking again; the one after is a PROBE
-                                         //   scan: general kernels as before, the fast path's kernels in front of them just
-                                         //   to see whether they would have stood (DevRes::fast4_hint) -- no host round trip,
-                                         //   no second front, whichever way it comes out
-    int ranked_skip = 0;                 // scans left that go straight to the list-ranking tier (long records)
-    int dense_skip = 0;                  // scans left that start with the dense configuration of the group kernels
-    int lite_skip = 0;                   // scans left whose general path runs k_chain_wave over all groups (the lean kernel declined too many)
-    bool dense4_remember = false;        // four-line input with dense tiles (reads of a dozen bases): the fast path starts with k_rows4<., true>
-    int fused_skip = 0;                  // scans left that do not try the single pass (it failed: odd records) ...
-    int fused_backoff = HOLD_OFF;        //   ... and the count after its next failure (grows 4 b + 3, up to 1023)
-    bool fz_in_place = false;            // the last single pass that stood wrote in place (long lines): start with that one
 };
 
 // The memory behind the kernel argument structs ChainBufs (ffq_chain.h) and RankBufs (ffq_ranked.h).  Those are plain
@@ -561,7 +529,7 @@ static int reserve_pool(ffq_ctx *c, unsigned long long entries)
 
 extern "C" void ffq_ctx_forget(ffq_ctx *c)
 {
-    if (c) c->mem = InputMemory{};
+    if (c) forget(c->mem);
 }
 
 extern "C" int ffq_ctx_reserve(ffq_ctx *c, int64_t max_bytes)
@@ -803,6 +771,15 @@ static ChainBufs chain_bufs(ffq_ctx *c, int ngroups, int nmax)
     return cb;
 }
 
+// FFQ_NO_FAST4 is read at every call (tests flip it while a process runs), the other three once
+static Switches scan_switches()
+{
+    static const Switches once{false, getenv("FFQ_NO_WIDE") != nullptr, getenv("FFQ_NO_LITE") != nullptr, getenv("FFQ_NO_RANKED") != nullptr};
+    Switches sw = once;
+    sw.no_fast4 = getenv("FFQ_NO_FAST4") != nullptr;
+    return sw;
+}
+
 // repair pass: the groups whose entry guess the verification rejected are re-run from their
 // predecessor's exit (k_repair_mark), then everything is verified again
 static int enqueue_repair(ffq_ctx *c, const ScanState &st, const LineIndex &L)
@@ -840,12 +817,7 @@ static int enqueue_general(ffq_ctx *c, ScanState &st, const LineIndex &L, bool t
     ChainBufs cb = chain_bufs(c, ngroups, nmax);
     hipStream_t sA = c->stream;
     HIPCHK(hipMemsetAsync(cb.flags, 0, (2 * (size_t)ngroups + 3) * 4, sA));      // flags, and: no group has a chunk of the walked groups' stage yet
-    static const bool no_lite = getenv("FFQ_NO_LITE") != nullptr;
-    bool lite = !dense_cfg && !no_lite;
-    // (a context whose recent input the lean kernel mostly declined -- tiles of more than LT_E lines that still fit the usual
-    // window: lines of 43-48 bytes -- runs k_chain_wave directly for a while: the list kernel is the slower way to run many groups)
-    if (lite && c->mem.lite_skip > 0) { c->mem.lite_skip--; lite = false; }
-    st.lite_ran = lite;
+    const bool lite = plan_lite(st, c->mem, scan_switches());
     if (lite) {
         // ordinary groups by the lean kernel; what it declines (flag bit 3) goes to k_chain_wave right behind.  The groups it
         // cannot take by their place -- the first one (sentinel, search offset), the last ones (the buffer's end) -- are
@@ -906,79 +878,70 @@ static int end_front(ffq_ctx *c, const ScanState &st)
     return FFQ_OK;
 }
 
+// The four-line rows of a front: k_sbscan -> k_rows4<...> -> k_finalize4.  `o` is what the row kernel writes for the decode
+// beside the table (all null: the rows only) and the single pass's verdict word for k_finalize4.
+struct Rows4Out {
+    bool zero_tileq; uint32_t *qrel; int64_t *p4s; int64_t p4_cap;       // the fast path's own decode
+    int64_t fz_stride; const uint8_t *fz_phase; int64_t *fz_qoff;       // the single pass: its layout, per-tile phases, offsets
+    const uint32_t *fz_bad;
+};
+static int enqueue_rows4(ffq_ctx *c, const ScanState &st, const LineIndex &L, decltype(&k_rows4<0, false>) rows4, const Rows4Out &o,
+                         const Pub &pub)
+{
+    const ScanArgs &a = st.a;
+    hipStream_t sA = c->stream;
+    enqueue_sbscan(c, L, st.ntiles, (int)((st.ntiles + SB_TILES - 1) / SB_TILES), a.offset);
+    if (o.zero_tileq) HIPCHK(hipMemsetAsync(c->tileq, 0, (size_t)st.ntiles * sizeof(TileQ), sA));
+    hipLaunchKernelGGL(rows4, dim3((unsigned)((st.ntiles + 3) / 4)), dim3(256), 0, sA, L, (const long long *)c->sbbase, a.eof, a.add,
+                       c->hdr4, c->tinfo4, a.d_table, a.table_cap, o.qrel, c->tileq, o.p4s, o.p4_cap, o.fz_stride, o.fz_phase, o.fz_qoff);
+    hipLaunchKernelGGL(k_finalize4, dim3(1), dim3(64), 0, sA, L, c->hdr4, (const TermInfo4 *)c->tinfo4, a.eof, a.offset, a.add,
+                       (const int64_t *)a.d_table, a.table_cap, c->dres, pub, o.fz_bad);
+    return FFQ_OK;
+}
+
 // front of a scan: everything on ONE in-order stream (the context's), no host synchronisation
 // and no copy or fill between the kernels:
 //     k_scan_lines -> (k_sbscan -> k_rows4 -> k_finalize4)  or  (general kernels) [-> decode]
 // The ragged last tile of the buffer rides along in the index kernel's launch (workgroup 0's
 // second tile).  The last result-writing kernel publishes the result block into host-mapped
 // memory and zeroes the control block for the next scan; ev[3] follows the last kernel.  A
-// second context on the same stream queues its front right behind: the GPU never idles.
+// second context on the same stream queues its front right behind: the GPU never idles.  Which front: plan_front
+// (ffq_scanwalk.h); this function launches what the plan says.
 static int enqueue_front(ffq_ctx *c, ScanState &st)
 {
     const ScanArgs &a = st.a;
-    const bool serial = st.serial, decode = st.decode;
+    const bool decode = st.decode;
     hipStream_t sA = c->stream;
     const int64_t ntiles = st.ntiles;
     const int nsb = (int)((ntiles + SB_TILES - 1) / SB_TILES);
-    // the four-line fast path (ffq_rows4.h) is tried first unless it already failed on this buffer
-    // (nor while the context remembers that its recent input was not four-line)
-    if (c->mem.ranked_skip > 0 && !serial && !st.index_done) { c->mem.ranked_skip--; st.go_ranked = true; }
-    if (st.force_ranked && !serial) st.go_ranked = true;
-    st.probe4 = false;
-    if (c->mem.fast4_remember && !st.fast4_failed) {
-        st.fast4_failed = true;
-        if (c->mem.fast4_skip > 0) c->mem.fast4_skip--;
-        else st.probe4 = !serial && !st.go_ranked && !st.index_done;
-    }
-    if (c->mem.dense_skip > 0 && !st.dense_cfg && !st.index_done) { c->mem.dense_skip--; st.dense_cfg = true; }
-    const bool try_fast4 = !serial && !st.go_ranked && !st.dense_cfg && !st.fast4_failed && !st.force_general &&
-                           getenv("FFQ_NO_FAST4") == nullptr;
+    const FrontPlan p = plan_front(st, c->mem, CallFacts{a.offset, a.qual_cap, a.n_bytes, (reinterpret_cast<uintptr_t>(a.d_qual) & 15) == 0},
+                                   scan_switches());
     const LineIndex L = make_index(c, a, ntiles);
     c->decode_timed = false;
-    // without the decode every front ends in a publisher: it can say "done" itself
-    st.poll_seq = (st.poll_result && !decode) ? ++c->seq : 0;
+    st.poll_seq = p.polled ? ++c->seq : 0;
     c->pub_seq = st.poll_seq;
     c->ctl_was_clean = c->ctl_clean;
     if (!c->ctl_clean) HIPCHK(hipMemsetAsync(c->ctl, 0, sizeof(Ctl), sA));    // first scan, or an abandoned front
     c->ctl_clean = false;
+    const Rows4Out rows_only{false, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr};
 
-    // ---- four-line input with the decode: index AND decoded stream in one pass over the bytes ---------
-    st.fused = false;
-    // (two layouts, both "record i at d_qual + d_qoff[i]", include/ffq.h: SEGMENTED -- SG_STRIDE bytes of the caller's buffer
-    // per tile, lines up to SG_EXT bytes behind a tile's end -- and IN PLACE -- TILE bytes per tile, lines of any length, a
-    // few per cent slower on short reads (more bytes written); both write whole 16-byte pieces: an unaligned d_qual gets the
-    // packed stream.  The segmented one first; once it has refused a buffer for its shape the in-place one, which the
-    // context then remembers.)
-    st.in_place = (c->mem.fz_in_place || st.seg_refused) && a.qual_cap >= ntiles * (int64_t)TILE;
-    if (decode && st.single_pass && try_fast4 && !st.index_done && !st.no_fused && a.offset < 16 &&
-        (st.in_place || (!st.seg_refused && a.qual_cap >= ntiles * (int64_t)SG_STRIDE)) && (reinterpret_cast<uintptr_t>(a.d_qual) & 15) == 0) {
-        if (c->mem.fused_skip > 0) c->mem.fused_skip--;
-        else st.fused = true;
-    }
-    if (st.fused) {
-        int rc = enqueue_fused_index(c, a, ntiles, st.in_place);
+    if (p.front == FRONT_FUSED) {
+        // ---- four-line input with the decode: index AND decoded stream in one pass over the bytes ---------
+        int rc = enqueue_fused_index(c, a, ntiles, p.in_place);
         if (rc) return rc;
-        enqueue_sbscan(c, L, ntiles, nsb, a.offset);
-        auto rows4 = st.in_place ? k_rows4<2, false> : k_rows4<1, false>;
-        hipLaunchKernelGGL(rows4, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, sA, L,
-                           (const long long *)c->sbbase, a.eof, a.add, c->hdr4, c->tinfo4, a.d_table, a.table_cap,
-                           (uint32_t *)nullptr, c->tileq, (int64_t *)nullptr, a.table_cap,
-                           (int64_t)(st.in_place ? TILE : SG_STRIDE), (const uint8_t *)c->fz_qphase, a.d_qoff);
-        hipLaunchKernelGGL(k_finalize4, dim3(1), dim3(64), 0, sA, L, c->hdr4, (const TermInfo4 *)c->tinfo4, a.eof,
-                           a.offset, a.add, (const int64_t *)a.d_table, a.table_cap, c->dres, no_pub(c), (const uint32_t *)c->fz_bad);
+        rc = enqueue_rows4(c, st, L, p.in_place ? k_rows4<2, false> : k_rows4<1, false>,
+                           Rows4Out{false, nullptr, nullptr, a.table_cap, (int64_t)(p.in_place ? TILE : SG_STRIDE), c->fz_qphase, a.d_qoff, c->fz_bad},
+                           no_pub(c));
+        if (rc) return rc;
         hipLaunchKernelGGL(k_qtotal4, dim3(1), dim3(1), 0, sA, c->dres, (const int64_t *)a.d_table, a.table_cap,
                            a.d_qoff, make_pub(c));
         c->ctl_clean = true;
-        st.stage = 1;
         return end_front(c, st);
     }
 
     // ---- line index --------------------------------------------------------------------
-    // (FFQ_F_NO_TIMING with the polled completion: no stream marker anywhere in the front -- each is a barrier
-    // packet with a few microseconds of idle GPU around it)
-    st.untimed = st.no_timing && st.poll_seq && !st.index_done;
-    // ... and the index kernel without a barrier in front of it only where the library itself can vouch for it (StreamTail)
-    bool any_order = st.untimed && c->ctl_was_clean;
+    // the index kernel without a barrier in front of it only where the library itself can vouch for it (StreamTail)
+    bool any_order = p.untimed && c->ctl_was_clean;
     {
         const StreamTail &tl = c->owner->tail;
         if (!tl.is_scan || tl.exposed) any_order = false;
@@ -988,36 +951,18 @@ static int enqueue_front(ffq_ctx *c, ScanState &st)
             if (tl.out_p[i] && o0 < b1 && b0 < o1) any_order = false;
         }
     }
-    // The decode of records of ANY layout in one pass (round 6): a scan that starts on the general path (wrapped records:
-    // the context remembers them; FFQ_F_FORCE_GENERAL; the ranking / one-wave tiers) with FFQ_F_SINGLE_PASS and
-    // FFQ_INPLACE_STRIDE bytes of quality buffer per tile has its index kernel write EVERY byte decoded at the offset it has
-    // in the buffer (k_scan_lines<.., WIDE>): no tier of the scan then runs a decode kernel -- qoff[i] = pos4's offset --
-    // and the input is read once.  (The four-line fast path has its own single passes, above; a scan that comes here from a
-    // refused fast path already has its index and takes the packed decode, as before.)
-    static const bool no_wide = getenv("FFQ_NO_WIDE") != nullptr;
-    if (!st.index_done)
-        st.wide = decode && st.single_pass && !try_fast4 && !no_wide &&
-                  a.qual_cap >= ntiles * (int64_t)TILE && (reinterpret_cast<uintptr_t>(a.d_qual) & 15) == 0;
-    if (!st.untimed) HIPCHK(hipEventRecord(c->ev[0], sA));
-    if (!st.index_done)          // (a later tier of the same scan: the index is there already)
-        launch_scan_lines(c, sA, a.d_buf, a.n_bytes, ntiles, L, (uint32_t)'@', any_order && !st.wide,
-                          st.wide ? a.d_qual : (int8_t *)nullptr, a.qual_add);
-    if (!st.untimed) HIPCHK(hipEventRecord(c->ev[1], sA));
+    if (!p.untimed) HIPCHK(hipEventRecord(c->ev[0], sA));
+    if (p.run_index)             // (a later tier of the same scan: the index is there already)
+        launch_scan_lines(c, sA, a.d_buf, a.n_bytes, ntiles, L, (uint32_t)'@', any_order && !p.wide,
+                          p.wide ? a.d_qual : (int8_t *)nullptr, a.qual_add);
+    if (!p.untimed) HIPCHK(hipEventRecord(c->ev[1], sA));
 
-    if (try_fast4) {
+    if (p.front == FRONT_FAST4) {
         // ---- plain four-line records: rows straight from newline ordinals, then validated -----
-        enqueue_sbscan(c, L, ntiles, nsb, a.offset);
-        if (decode) HIPCHK(hipMemsetAsync(c->tileq, 0, (size_t)ntiles * sizeof(TileQ), sA));
-        if (c->mem.dense4_remember) st.dense4 = true;
-        auto rows4 = st.dense4 ? k_rows4<false, true> : k_rows4<false, false>;
-        hipLaunchKernelGGL(rows4, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, sA, L,
-                           (const long long *)c->sbbase, a.eof, a.add, c->hdr4, c->tinfo4, a.d_table, a.table_cap,
-                           decode ? c->qrel : (uint32_t *)nullptr, c->tileq, decode ? c->p4s : (int64_t *)nullptr,
-                           decode ? std::min<int64_t>(a.table_cap, c->p4s.cap) : (int64_t)0,
-                           (int64_t)0, (const uint8_t *)nullptr, (int64_t *)nullptr);
-        hipLaunchKernelGGL(k_finalize4, dim3(1), dim3(64), 0, sA, L, c->hdr4, (const TermInfo4 *)c->tinfo4, a.eof,
-                           a.offset, a.add, (const int64_t *)a.d_table, a.table_cap, c->dres,
-                           decode ? no_pub(c) : make_pub(c));
+        const Rows4Out with_decode{true, c->qrel, c->p4s, std::min<int64_t>(a.table_cap, c->p4s.cap), 0, nullptr, nullptr, nullptr};
+        int rc = enqueue_rows4(c, st, L, p.dense4 ? k_rows4<false, true> : k_rows4<false, false>, decode ? with_decode : rows_only,
+                               decode ? no_pub(c) : make_pub(c));
+        if (rc) return rc;
         if (decode) {
             // quality offsets: superblock sums + scan, per-tile fix-up (+ stream directory), total
             // (publishes); then the decode itself.  All of it is skipped on the device if the
@@ -1034,29 +979,21 @@ static int enqueue_front(ffq_ctx *c, ScanState &st)
             enqueue_decode(c, a, sA, true);
         }
         c->ctl_clean = true;
-        st.stage = 1;
+        return end_front(c, st);
+    }
+    if (p.probe4) {
+        // has the input turned plain four-line again?  The fast path's kernels (rows into the caller's
+        // table, which the general kernels then write again; no decode tail), their verdict left in
+        // DevRes::fast4_hint for the publisher of the general path to carry out
+        int rc = enqueue_rows4(c, st, L, p.dense4 ? k_rows4<false, true> : k_rows4<false, false>, rows_only, no_pub(c));
+        if (rc) return rc;
+    }
+    if (p.front == FRONT_GENERAL) {
+        int rc = enqueue_general(c, st, L, true);
+        if (rc) return rc;
     } else {
-        if (st.probe4) {
-            // has the input turned plain four-line again?  The fast path's kernels (rows into the caller's
-            // table, which the general kernels then write again; no decode tail), their verdict left in
-            // DevRes::fast4_hint for the publisher of the general path to carry out
-            enqueue_sbscan(c, L, ntiles, nsb, a.offset);
-            auto rows4 = c->mem.dense4_remember ? k_rows4<false, true> : k_rows4<false, false>;
-            hipLaunchKernelGGL(rows4, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, sA, L,
-                               (const long long *)c->sbbase, a.eof, a.add, c->hdr4, c->tinfo4, a.d_table, a.table_cap,
-                               (uint32_t *)nullptr, c->tileq, (int64_t *)nullptr, (int64_t)0,
-                               (int64_t)0, (const uint8_t *)nullptr, (int64_t *)nullptr);
-            hipLaunchKernelGGL(k_finalize4, dim3(1), dim3(64), 0, sA, L, c->hdr4, (const TermInfo4 *)c->tinfo4, a.eof,
-                               a.offset, a.add, (const int64_t *)a.d_table, a.table_cap, c->dres, no_pub(c));
-        }
-        if (!serial && !st.go_ranked) {
-            int rc = enqueue_general(c, st, L, true);
-            if (rc) return rc;
-        } else {
-            hipLaunchKernelGGL(k_publish, dim3(1), dim3(1), 0, sA, c->dres, make_pub(c), 1);
-            c->ctl_clean = true;
-        }
-        st.stage = 2;
+        hipLaunchKernelGGL(k_publish, dim3(1), dim3(1), 0, sA, c->dres, make_pub(c), 1);
+        c->ctl_clean = true;
     }
     return end_front(c, st);
 }
@@ -1129,25 +1066,30 @@ static bool rank_reserve_cands(ffq_ctx *c, int64_t nc)
     return ok;
 }
 
-// Returns FFQ_OK with the result published, 1 if the tier cannot run here (too many candidates for
-// 32-bit ranks, no memory: the caller then takes the one-wave walker), 2 if only_if_sparse is set
-// and the buffer has more than one candidate per 512 bytes.
-static int run_ranked(ffq_ctx *c, const ScanArgs &a, const LineIndex &L, int64_t ntiles, bool only_if_sparse)
+// The tier in two halves around its host wait.  ranked_count: the candidates ("\n@" matches) per tile, their scan, the total
+// back on the host in *nc.  ranked_emit: the ranking over nc candidates and the rows, published.  Both return FFQ_OK, or
+// RK_CANNOT if the tier cannot run here (no memory: the caller then takes the one-wave walker); ranked_verdict
+// (ffq_scanwalk.h) judges nc between them.
+static int ranked_count(ffq_ctx *c, const LineIndex &L, int64_t ntiles, int64_t *nc)
 {
     hipStream_t sA = c->stream;
     RankBufs &R = c->rk;
-    if (!rank_reserve_tiles(c, ntiles)) return 1;
-    if (c->col_res.grow(1) != hipSuccess) return 1;
+    if (!rank_reserve_tiles(c, ntiles)) return RK_CANNOT;
+    if (c->col_res.grow(1) != hipSuccess) return RK_CANNOT;
     hipLaunchKernelGGL(k_rk_count, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, sA, L, R.tbase);
-    if (launch_scan_i64v(c, sA, R.tbase, ntiles, (int64_t)0, c->col_res)) return 1;
+    if (launch_scan_i64v(c, sA, R.tbase, ntiles, (int64_t)0, c->col_res)) return RK_CANNOT;
     HIPCHK(hipMemcpyAsync(c->h_word, &c->col_res->n_qual_bytes, sizeof(int64_t), hipMemcpyDeviceToHost, sA));
     HIPCHK(hipGetLastError());
     CTX_SYNC(c);
-    const int64_t nc = c->h_word[0];
-    if (nc >= 0x7FFFFFF0ll) return 1;
-    // a context that remembers long records meets short ones again: back to the group kernels
-    if (only_if_sparse && nc * 512 > a.n_bytes) return 2;
-    if (!rank_reserve_cands(c, nc)) { (void)hipGetLastError(); return 1; }
+    *nc = c->h_word[0];
+    return FFQ_OK;
+}
+
+static int ranked_emit(ffq_ctx *c, const ScanArgs &a, const LineIndex &L, int64_t ntiles, int64_t nc)
+{
+    hipStream_t sA = c->stream;
+    RankBufs &R = c->rk;
+    if (!rank_reserve_cands(c, nc)) { (void)hipGetLastError(); return RK_CANNOT; }
     R.nc = nc;
     const unsigned gthr = (unsigned)std::max<int64_t>((nc + 255) / 256, 1);
     if (nc > 0) {
@@ -1219,226 +1161,138 @@ static int run_tier(ffq_ctx *c, ffq_scan_result *res, Enqueue enqueue)
     return FFQ_OK;
 }
 
+// the list-ranking tier behind a front: *how = RK_* (ffq_scanwalk.h); where it ran, with the quality offsets and the decode
+// it does not do on the way, its time added like a tier's
+static int ranked_tier(ffq_ctx *c, const ScanState &st, const LineIndex &L, ffq_scan_result *res, bool only_if_sparse, int *how)
+{
+    const ScanArgs &a = st.a;
+    hipStream_t sA = c->stream;
+    HIPCHK(hipEventRecord(c->ev[4], sA));
+    int64_t nc = 0;
+    int rr = ranked_count(c, L, st.ntiles, &nc);
+    if (rr == FFQ_OK) rr = ranked_verdict(nc, a.n_bytes, only_if_sparse);
+    if (rr == RK_GO) rr = ranked_emit(c, a, L, st.ntiles, nc);
+    if (rr < 0) return rr;
+    *how = rr;
+    if (rr != RK_GO) return FFQ_OK;
+    HIPCHK(hipEventRecord(c->ev[2], sA));
+    CTX_WAIT_EVENT(c, c->ev[2]);
+    if (st.decode && !c->h_res->fallback) {
+        int rc = st.wide ? enqueue_offsets_in_place(c, a, c->h_res->n_records) : enqueue_offsets_and_decode(c, a, c->h_res->n_records);
+        if (rc) return rc;
+        HIPCHK(hipEventRecord(c->ev[2], sA));
+        HIPCHK(hipGetLastError());
+        CTX_WAIT_EVENT(c, c->ev[2]);
+    }
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev[4], c->ev[2]));
+    res->ms_chain += ms; res->ms_total += ms;
+    return FFQ_OK;
+}
+
+// the one-wave walk: exact on anything, one wave for the whole buffer
+static int enqueue_walk(ffq_ctx *c, const ScanState &st, const LineIndex &L)
+{
+    const ScanArgs &a = st.a;
+    hipStream_t sA = c->stream;
+    const bool decode = st.decode;
+    int64_t *const sq = (decode && !st.wide) ? a.d_qoff : (int64_t *)nullptr;       // (wide: the offsets from the finished table, below)
+    hipLaunchKernelGGL(k_chain_serial, dim3(1), dim3(64), 0, sA, L, a.offset, a.eof, a.add, a.d_table,
+                       a.table_cap, sq, c->qdir, c->qdir.cap, sq ? c->p4s : (int64_t *)nullptr,
+                       sq ? std::min<int64_t>(a.table_cap, c->p4s.cap) : (int64_t)0, c->dres);
+    hipLaunchKernelGGL(k_finalize_serial, dim3(1), dim3(64), 0, sA, c->dres, a.table_cap, sq, (decode && st.wide) ? no_pub(c) : make_pub(c));
+    c->ctl_clean = true;
+    if (decode && st.wide) hipLaunchKernelGGL(k_qoff_in_place, dim3(256), dim3(256), 0, sA, c->dres, (const int64_t *)a.d_table, a.table_cap, a.add, a.s, a.d_qoff, make_pub(c));
+    else if (decode) enqueue_decode(c, a, sA);
+    return FFQ_OK;
+}
+
+// wait for THIS scan's front only: the stream may already hold the next scan of a context that shares it
+static int wait_front(ffq_ctx *c, const ScanState &st)
+{
+    if (st.poll_seq) {
+        int rc = poll_seq(c, st.poll_seq);
+        if (rc) return rc;
+        // (the GPU is past this mark; the wait only lets the runtime note it before the mark is read)
+        if (!st.untimed) CTX_WAIT_EVENT(c, c->ev[1]);
+    } else CTX_WAIT_EVENT(c, c->ev[3]);
+    return FFQ_OK;
+}
+
+// the times of a front that stood, from its marks (`untimed`, `had_index`: as the front was enqueued)
+static int time_front(ffq_ctx *c, const ScanState &st, ffq_scan_result *res, bool untimed, bool had_index)
+{
+    float ms = 0;
+    if (!untimed) HIPCHK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    if (!had_index) res->ms_index = ms;
+    res->ms_decode = 0;
+    if (!st.poll_seq) {                // (a polled front has no end mark: its tail is not timed)
+        HIPCHK(hipEventElapsedTime(&ms, c->ev[1], c->ev[3])); res->ms_chain += ms;
+        if (c->decode_timed) {
+            // the decode kernel is the tail of the front: split it off the chain time
+            HIPCHK(hipEventElapsedTime(&ms, c->ev[6], c->ev[3]));
+            res->ms_decode = ms; res->ms_chain -= ms;
+        }
+        HIPCHK(hipEventElapsedTime(&ms, c->ev[0], c->ev[3])); res->ms_total += ms;
+    }
+    return FFQ_OK;
+}
+
+static Report read_report(const ffq_ctx *c, int ranked)
+{
+    const Ctl &k = *c->h_ctl;
+    const DevRes &d = *c->h_res;
+    Report r;
+    r.err = k.err; r.pool_head = k.pool_head;
+    r.fallback = d.fallback; r.fast4_hint = d.fast4_hint; r.fused_bad = d.fused_bad; r.fast4_dense = d.fast4_dense;
+    r.bad_group = d.bad_group; r.bad_irregular = d.bad_irregular; r.n_bad = d.n_bad; r.n_declined = d.n_declined;
+    r.approx_records = d.approx_records;
+    r.ranked = ranked;
+    return r;
+}
+
+// The scan from its first front (enqueued by the submit) to its result: wait, read the report, ask next_step
+// (ffq_scanwalk.h), run what it says.
 static int scan_finish(ffq_ctx *c, ScanState &st, ffq_scan_result *res)
 {
     const ScanArgs &a = st.a;
-    const bool serial = st.serial, decode = st.decode;
-    int64_t *qoff = decode ? a.d_qoff : nullptr;
-    hipStream_t sA = c->stream;
-    bool front_done = true;           // the first front was enqueued by the caller (submit)
-    for (;;) {
-        if (!front_done) {
-            int rc = enqueue_front(c, st);
-            if (rc) return rc;
-        }
-        front_done = false;
-        // wait for THIS scan's front only: the stream may already hold the next scan of a
-        // context that shares it
-        if (st.poll_seq) {
-            int rc = poll_seq(c, st.poll_seq);
-            if (rc) return rc;
-            // (the GPU is past this mark; the wait only lets the runtime note it before the mark is read)
-            if (!st.untimed) CTX_WAIT_EVENT(c, c->ev[1]);
-        } else CTX_WAIT_EVENT(c, c->ev[3]);
+    int ranked = RK_GO;
+    int rc = wait_front(c, st);
+    while (!rc) {
         const LineIndex L = make_index(c, a, st.ntiles);
-
-        if (c->h_ctl->err & ERR_POOL) {
-            // dense tiles did not fit the overflow pool: size it for what was asked and re-run
-            if (st.retries >= 2) return fail(FFQ_E_INTERNAL, "line-index pool overflow persists");
-            int rc = reserve_pool(c, std::max<unsigned long long>(c->h_ctl->pool_head + (c->h_ctl->pool_head >> 4), POOL_MIN));
-            if (rc) return rc;
-            st.retries++;
-            st.index_done = false;
-            continue;
-        }
-        if (c->h_ctl->err & ERR_INTERNAL) return fail(FFQ_E_INTERNAL, "chain kernel invariant failed");
-        // more groups were walked (dense regions, ffq_dense.h) than their stage has chunks for: size it for what was
-        // asked and run the chain kernels again, from the index that is there
-        auto dstage_short = [&]() -> int {
-            if (!(c->h_ctl->err & ERR_DSTAGE)) return 0;
-            if (st.retries >= 4) return fail(FFQ_E_INTERNAL, "the walked groups' stage stays too small");
+        const bool untimed = st.untimed, had_index = st.index_done;
+        const Step s = next_step(st, c->mem, read_report(c, ranked), scan_switches());
+        if (s.front_counts && (rc = time_front(c, st, res, untimed, had_index))) return rc;
+        bool front = false;
+        switch (s.kind) {
+        case STEP_DONE:
+            fill_result(res, *c->h_res, s.path, s.retries);
+            if (res->n_records > a.table_cap)
+                return fail(FFQ_E_TABLE_FULL, "table holds %lld rows, the buffer has %lld records", (long long)a.table_cap,
+                            (long long)res->n_records);
+            if (st.decode && res->n_qual_bytes > a.qual_cap)
+                return fail(FFQ_E_TABLE_FULL, "quality buffer holds %lld bytes, %lld needed", (long long)a.qual_cap,
+                            (long long)res->n_qual_bytes);
+            return FFQ_OK;
+        case STEP_FAIL: return fail(s.code, "%s", s.text);
+        case STEP_FRONT: front = true; break;
+        case STEP_GROW_POOL: rc = reserve_pool(c, s.n); front = true; break;
+        case STEP_GROW_STAGE: {
             uint32_t asked = 0;
             HIPCHK(hipMemcpy(&asked, c->cb.flags + 2 * (size_t)st.ngroups, sizeof asked, hipMemcpyDeviceToHost));
-            int rc = reserve_dstage(c, std::max<int64_t>((int64_t)asked + (asked >> 3) + 8, 2 * (int64_t)c->cb.dchunks));
-            if (rc) return rc;
-            st.retries++;
-            st.index_done = true;
-            return 1;
-        };
-        float ms = 0;
-        if (!st.untimed) HIPCHK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-        if (!st.index_done) res->ms_index = ms;
-        st.untimed = false;
-        st.index_done = true;
-        res->ms_decode = 0;
-        if (!st.poll_seq) {                // (a polled front has no end mark: its tail is not timed)
-            HIPCHK(hipEventElapsedTime(&ms, c->ev[1], c->ev[3])); res->ms_chain += ms;
-            if (c->decode_timed) {
-                // the decode kernel is the tail of the front: split it off the chain time
-                HIPCHK(hipEventElapsedTime(&ms, c->ev[6], c->ev[3]));
-                res->ms_decode = ms; res->ms_chain -= ms;
-            }
-            HIPCHK(hipEventElapsedTime(&ms, c->ev[0], c->ev[3])); res->ms_total += ms;
+            rc = reserve_dstage(c, stage_chunks(asked, c->cb.dchunks));
+            front = true;
+            break;
         }
-
-        const bool tiers = !serial && !st.go_ranked;       // the group kernels ran: their fallbacks apply
-        if (st.probe4) {
-            // the probe's verdict: the next scan starts with the fast path again, or HOLD_OFF more do not ask
-            st.probe4 = false;
-            if (c->h_res->fast4_hint == 1) { c->mem.fast4_remember = false; c->mem.fast4_skip = 0; }
-            else c->mem.fast4_skip = HOLD_OFF;
+        case STEP_GENERAL: rc = run_tier(c, res, [&] { return enqueue_general(c, st, L); }); break;
+        case STEP_REPAIR: rc = run_tier(c, res, [&] { return enqueue_repair(c, st, L); }); break;
+        case STEP_RANKED: rc = ranked_tier(c, st, L, res, s.only_if_sparse, &ranked); break;
+        case STEP_WALK: rc = run_tier(c, res, [&] { return enqueue_walk(c, st, L); }); break;
         }
-        if (st.stage == 1) {
-            if (!c->h_res->fallback) {
-                fill_result(res, *c->h_res, st.fused ? 6 : 3, st.retries);
-                if (st.fused) { c->mem.fused_backoff = HOLD_OFF; c->mem.fz_in_place = st.in_place; }
-                break;
-            }
-            if (st.fused) {
-                // the single pass did not stand (lines longer than a tile, a quality line that is not as
-                // long as its sequence line, text in front of the first record, not four-line input at
-                // all ...): the two-pass kernels, from the index it built if that is whole
-                if (!st.in_place && !st.seg_refused && (c->h_res->fused_bad & (int32_t)FZ_BAD_SHAPE) &&
-                    !(c->h_res->fused_bad & (int32_t)FZ_BAD_INDEX) && a.qual_cap >= st.ntiles * (int64_t)TILE) {
-                    // a shape the segments cannot take (a line longer than SG_EXT behind a tile, no S P pair in a tile
-                    // of a few long lines) and the caller's buffer has room for the in-place layout: that pass next
-                    st.seg_refused = true;
-                    st.fused = false;
-                    st.index_done = false;          // (that pass builds the index itself)
-                    st.retries++;
-                    continue;
-                }
-                c->mem.fz_in_place = false;
-                st.no_fused = true;
-                st.fused = false;
-                c->mem.fused_skip = c->mem.fused_backoff;
-                c->mem.fused_backoff = std::min(4 * c->mem.fused_backoff + 3, 1023);
-                st.index_done = !(c->h_res->fused_bad & (int32_t)FZ_BAD_INDEX);
-                st.retries++;
-                continue;
-            }
-            if (c->h_res->fast4_dense && !st.dense4 && !st.fused && !st.no_fused) {
-                // the row kernel met a DENSE tile (lines under 16 bytes on average: reads of a dozen bases): its DENSE
-                // instantiation takes those -- the same front again from the index that is there, and the context's next
-                // scans start with it
-                st.dense4 = true;
-                c->mem.dense4_remember = true;
-                st.retries++;
-                continue;
-            }
-            // not plain four-line input: the general kernels, from the same line index.  The next
-            // scans of this context skip the attempt (and the host round trip it costs here).
-            st.fast4_failed = true;
-            c->mem.fast4_remember = true;
-            c->mem.fast4_skip = HOLD_OFF;
-            int rc = run_tier(c, res, [&] { return enqueue_general(c, st, L); });
-            if (rc) return rc;
-            if (c->h_ctl->err & ERR_INTERNAL) return fail(FFQ_E_INTERNAL, "chain kernel invariant failed");
-        }
-        int path = 0;
-        // a guess the verification rejected is repaired, not escalated: the rejected groups are
-        // re-run from their predecessor's exit and everything is verified again.  Every round
-        // makes the first rejected group exact, so the first bad group moves forward; a round
-        // that does not move it (a group that does not fit the kernel at all) ends the repairs.
-        static const bool no_ranked = getenv("FFQ_NO_RANKED") != nullptr;
-        if (tiers) {
-            int prev_bad = -1;
-            const int first_bad = c->h_res->bad_group;
-            // (a group that does not FIT the kernel -- bad_irregular -- is walked by k_group_walk in
-            // the same passes; if that cannot take it either, the first bad group does not move)
-            // With list ranking behind them the repair passes only mend sporadic wrong guesses (two
-            // rounds); records that span whole groups correct one another a few groups per round,
-            // and list ranking is the tool for that.
-            // (groups that do not FIT -- dense tiles -- are walked one repair pass after their
-            // predecessor: those passes go on as before)
-            for (int round = 0; round < 16 && c->h_res->fallback && c->h_res->bad_group > prev_bad &&
-                                c->h_res->bad_group < st.ngroups && !(c->h_ctl->err & ERR_DSTAGE); round++) {
-                if (!no_ranked && round >= 2 && !c->h_res->bad_irregular) break;
-                // a guess in eight did not stand and the records are long (2.5 KB and more on average:
-                // wrapped reads from ~1.2 kb): repair passes would mend them a pass at a time; list ranking
-                // needs no guess and, at one wave per "\n@" match, costs less than two such passes there
-                // (tools/shape_sweep_wrapped.py: 1.5-3 kb reads 0.75-0.46 -> TB/s figures in DESIGN.md)
-                if (!no_ranked && !c->h_res->bad_irregular && (int64_t)c->h_res->n_bad * 8 > (int64_t)st.ngroups &&
-                    c->h_res->approx_records * 2560 < a.n_bytes) break;
-                if (round >= 4 && !c->h_res->bad_irregular &&
-                    c->h_res->bad_group - first_bad < round * std::max(st.ngroups / 64, 1)) break;
-                prev_bad = c->h_res->bad_group;
-                int rc = run_tier(c, res, [&] { return enqueue_repair(c, st, L); });
-                if (rc) return rc;
-                st.repairs++;
-                if (c->h_ctl->err & ERR_INTERNAL) return fail(FFQ_E_INTERNAL, "chain kernel invariant failed");
-            }
-        }
-        if (tiers) {
-            const int ds = dstage_short();
-            if (ds < 0) return ds;
-            if (ds > 0) { st.fast4_failed = true; continue; }
-        }
-        if (tiers && c->h_res->fallback && !st.dense_cfg && c->h_res->bad_irregular) {
-            // second tier: the same kernels with the LDS budget for short lines / short records
-            // (only a group that does not FIT is helped by it; a guess that stays wrong is not)
-            st.dense_cfg = true;
-            c->mem.dense_skip = HOLD_OFF;    // and the next scans of this context start there
-            continue;
-        }
-        if (st.dense_cfg) path = 2;
-        bool walk = serial || (tiers && c->h_res->fallback);
-        if (!serial && !no_ranked && (st.go_ranked || c->h_res->fallback)) {
-            // the group kernels could not prove a chain (records long against a group): list ranking
-            HIPCHK(hipEventRecord(c->ev[4], sA));
-            int rr = run_ranked(c, a, L, st.ntiles, st.go_ranked && !st.force_ranked);
-            if (rr < 0) return rr;
-            if (rr == 2) {
-                c->mem.ranked_skip = 0;
-                c->mem.fast4_skip = 0;           // (the input has changed character: what is remembered of it is void)
-                c->mem.fast4_remember = false;
-                st.go_ranked = false;
-                st.fast4_failed = false;
-                continue;                    // the usual tiers, from the line index that is there
-            }
-            walk = rr > 0;
-            if (rr == 0) {
-                HIPCHK(hipEventRecord(c->ev[2], sA));
-                CTX_WAIT_EVENT(c, c->ev[2]);
-                if (decode && !c->h_res->fallback) {
-                    int rc = st.wide ? enqueue_offsets_in_place(c, a, c->h_res->n_records) : enqueue_offsets_and_decode(c, a, c->h_res->n_records);
-                    if (rc) return rc;
-                    HIPCHK(hipEventRecord(c->ev[2], sA));
-                    HIPCHK(hipGetLastError());
-                    CTX_WAIT_EVENT(c, c->ev[2]);
-                }
-                HIPCHK(hipEventElapsedTime(&ms, c->ev[4], c->ev[2]));
-                res->ms_chain += ms; res->ms_total += ms;
-                path = 5;
-                if (!st.force_ranked) c->mem.ranked_skip = HOLD_OFF;     // and the next scans of this context start there
-            }
-        } else if (st.go_ranked) walk = true;
-        if (walk) {
-            path = 1;
-            int rc = run_tier(c, res, [&] {
-                int64_t *const sq = st.wide ? (int64_t *)nullptr : qoff;       // (wide: the offsets from the finished table, below)
-                hipLaunchKernelGGL(k_chain_serial, dim3(1), dim3(64), 0, sA, L, a.offset, a.eof, a.add, a.d_table,
-                                   a.table_cap, sq, c->qdir, c->qdir.cap, sq ? c->p4s : (int64_t *)nullptr,
-                                   sq ? std::min<int64_t>(a.table_cap, c->p4s.cap) : (int64_t)0, c->dres);
-                hipLaunchKernelGGL(k_finalize_serial, dim3(1), dim3(64), 0, sA, c->dres, a.table_cap, sq, (decode && st.wide) ? no_pub(c) : make_pub(c));
-                c->ctl_clean = true;
-                if (decode && st.wide) hipLaunchKernelGGL(k_qoff_in_place, dim3(256), dim3(256), 0, sA, c->dres, (const int64_t *)a.d_table, a.table_cap, a.add, a.s, a.d_qoff, make_pub(c));
-                else if (decode) enqueue_decode(c, a, sA);
-                return FFQ_OK;
-            });
-            if (rc) return rc;
-        }
-        if (tiers && st.lite_ran && (int64_t)c->h_res->n_declined * 4 > (int64_t)st.ngroups) c->mem.lite_skip = HOLD_OFF;
-        fill_result(res, *c->h_res, path | ((decode && st.wide) ? FFQ_PATH_IN_PLACE : 0), st.retries + st.repairs);
-        break;
+        if (front && !rc) rc = enqueue_front(c, st);
+        if (front && !rc) rc = wait_front(c, st);
     }
-    if (res->n_records > a.table_cap)
-        return fail(FFQ_E_TABLE_FULL, "table holds %lld rows, the buffer has %lld records", (long long)a.table_cap,
-                    (long long)res->n_records);
-    if (decode && res->n_qual_bytes > a.qual_cap)
-        return fail(FFQ_E_TABLE_FULL, "quality buffer holds %lld bytes, %lld needed", (long long)a.qual_cap,
-                    (long long)res->n_qual_bytes);
-    return FFQ_OK;
+    return rc;
 }
 
 // the scratch a scan of n_bytes needs (grow-only: a second call with the same sizes does nothing)

@@ -1,4 +1,4 @@
-"""Scans of a context that REMEMBERS another kind of input (InputMemory, csrc/ffq_hip.hip:102-115).
+"""Scans of a context that REMEMBERS another kind of input (InputMemory, csrc/ffq_scanwalk.h:59-72).
 
 Which tier a scan starts on is decided by what the context met before: the fast path is skipped while fast4_remember
 holds, a PROBE scan queues its row kernels in front of the general ones when fast4_skip has run out, ranked_skip /
@@ -23,7 +23,7 @@ from test_gpu_parity import _mess, random_records
 
 pytestmark = pytest.mark.gpu
 
-HOLD_OFF = 15                    # csrc/ffq_hip.hip:99 -- how many scans a verdict about the input holds
+HOLD_OFF = 15                    # csrc/ffq_scanwalk.h:56 -- how many scans a verdict about the input holds
 COUNTDOWN = HOLD_OFF + 3         # crosses every hold-off and includes the probe scan, however its off-by-one reads
 TILE = 16384
 
