@@ -20,9 +20,11 @@
 // from that neighbour's exit; each round settles the first unsettled rank.  Stream errors (the iterator's three
 // ValueErrors) are reported by every rank alike, once the failing rank's entry is proven.
 //
-// This is the C++ restatement of the protocol fastq-and-furious_amd/sharded.py runs over torch.distributed (kept there for
-// the CPU tests over gloo); the transports here are RCCL (librccl, resolved at run time: the library loads without it) and
-// an in-process one (k logical ranks as threads of one process on one GPU: tests, single-GPU dry runs).
+// The protocol -- the words, one look at them (sh_decide), the loop that looks until every edge is proven (sh_settle) -- is
+// stated once, in ffq_shard_proto.h, without a device: the device step and the slabs (here) and the host step
+// (ffq_shard_host.h, what the CPU tests drive) are three sets of hooks under that one loop.  The transports here are RCCL
+// (librccl, resolved at run time: the library loads without it), an in-process one (k logical ranks as threads of one
+// process on one GPU: tests, single-GPU dry runs) and the caller's own callbacks (hosted).
 #pragma once
 #include "ffq_shard_proto.h"
 #include <rccl/rccl.h>
@@ -35,7 +37,7 @@
 namespace ffq {
 
 // ---- step 3 on the device: rows of my range + the hand-off words ----------------------------------------------------
-// out[0..7] the words (ffq_shard_proto.h: sh_words_from), out[8] row_lo, out[9] row_hi, out[10] rows in the table
+// out: the rank's own block (ffq_shard_proto.h) -- the words (sh_words_from), SH_ROW_LO, SH_ROW_HI, SH_ROWS in the table
 __global__ __launch_bounds__(64) void k_shard_words(const DevRes *__restrict__ res, const int64_t *__restrict__ table,
                                                     int64_t table_cap, int64_t qual_cap, ShView v, int64_t offset, int64_t head_bytes,
                                                     int64_t *__restrict__ out, int64_t *__restrict__ host_out)
@@ -79,12 +81,12 @@ __global__ __launch_bounds__(64) void k_shard_words(const DevRes *__restrict__ r
     if (lane == 0) {
 #pragma unroll
         for (int i = 0; i < SH_WORDS; i++) out[i] = w[i];
-        out[8] = i0; out[9] = i1; out[10] = nrows;
+        out[SH_ROW_LO] = i0; out[SH_ROW_HI] = i1; out[SH_ROWS] = nrows;
         // (the same into host-mapped memory: this rank's own copy, no copy packet on the scan stream; visible to the host
         // once the gather behind this kernel is through)
 #pragma unroll
         for (int i = 0; i < SH_WORDS; i++) host_out[i] = w[i];
-        host_out[8] = i0; host_out[9] = i1; host_out[10] = nrows;
+        host_out[SH_ROW_LO] = i0; host_out[SH_ROW_HI] = i1; host_out[SH_ROWS] = nrows;
         __threadfence_system();
     }
 }
@@ -433,6 +435,69 @@ struct ShHosted : ShTransport {
     const char *name() const override { return "hosted"; }
 };
 
+// A failure of a rank's OWN step (a scan error, no memory) must not leave the peers waiting in the next collective for a
+// rank that has gone home: the code and the text are remembered, its words say "failed" and own no rows -- sh_decide makes
+// that INTERNAL on every rank --, and sh_settle returns the rank its own error once everybody has seen them.
+struct ShOwnFailure { int code = 0; std::string msg; };
+static void sh_fail_locally(ShOwnFailure &f, int rc, const ShView &v, int64_t *block)
+{
+    f.code = rc; f.msg = ffq_last_error();
+    sh_words_failed(v, block); sh_owns_no_rows(block);
+}
+
+// a verdict that is no result, worded (the ONE place these texts are written) -- and what the two "full" answers leave in
+// the caller's scan result
+static int shard_fail_verdict(const ShVerdict &v, const ShOwnFailure &mine, ffq_shard_result *out)
+{
+    switch (v.kind) {
+    case ShVerdict::TABLE_FULL:
+        out->scan.n_records = v.need;
+        return fail(FFQ_E_TABLE_FULL, "rank %d: offset table too small (%lld records in its view)", v.who, (long long)v.need);
+    case ShVerdict::QUAL_FULL:
+        out->scan.n_records = 0; out->scan.n_qual_bytes = v.need;
+        return fail(FFQ_E_TABLE_FULL, "rank %d: quality buffer too small (%lld decoded bytes in its view)", v.who, (long long)v.need);
+    case ShVerdict::INTERNAL: return fail(FFQ_E_INTERNAL, "sharded scan: rank %d %s", v.who, v.what);
+    case ShVerdict::MINE: return fail(v.code, "%s", mine.msg.c_str());            // (my own error, not "rank r failed")
+    case ShVerdict::NOT_READY: return fail(FFQ_E_INTERNAL, "sharded scan: a rank's result does not become ready");
+    case ShVerdict::UNSETTLED: return fail(FFQ_E_INTERNAL, "sharded scan does not settle (%d rounds)", v.rounds);
+    default: return v.code;              // HOOK: worded where it happened
+    }
+}
+
+// what every driver's result ends with: my rows and edges out of my own block, the ordinals out of everybody's counts
+static void shard_fill_result(ffq_shard_result *out, const int64_t *own, const int64_t *all, int W, int rank, const ShVerdict &v)
+{
+    out->n_rows = own[SH_ROWS]; out->row_lo = own[SH_ROW_LO]; out->row_hi = own[SH_ROW_HI];
+    out->exit_pos = own[0]; out->first_pos = own[1];
+    out->n_own_records = own[SH_ROW_HI] - own[SH_ROW_LO];
+    int64_t base = 0, tot = 0;
+    for (int r = 0; r < W; r++) {
+        const int64_t cnt = all[(size_t)r * SH_WORDS + 2];
+        if (r < rank) base += cnt;
+        tot += cnt;
+    }
+    out->record_base = base; out->total_records = tot;
+    out->err_state = v.err_state; out->err_byte = v.err_byte;
+    out->rounds = v.rounds; out->regathers = v.regathers;
+}
+
+static bool sh_debug() { static const bool on = getenv("FFQ_SHARD_DEBUG") != nullptr; return on; }
+
+// FFQ_SHARD_DEBUG=1: what a rank sees in every round (a run on several GPUs that nobody can attach to)
+static void sh_debug_round(const char *driver, int rank, int W, const ShRound &d, const int64_t *A, int rounds, int regathers, const ShView &v, const int64_t *own)
+{
+    std::string line;
+    char buf[256];
+    for (int r = 0; r < W; r++) {
+        const int64_t *w = A + (size_t)r * SH_WORDS;
+        snprintf(buf, sizeof buf, " [%d: exit %lld first %lld n %lld want %lld had %lld err %lld/%lld search %lld]", r, (long long)w[0], (long long)w[1],
+                 (long long)w[2], (long long)w[3], (long long)w[4], (long long)w[5], (long long)w[6], (long long)w[7]);
+        line += buf;
+    }
+    fprintf(stderr, "[ffq shard %d/%d%s] round %d regather %d kind %d view [%lld | %lld, %lld | %lld] rows %lld..%lld of %lld:%s\n", rank, W, driver, rounds, regathers, (int)d.kind,
+            (long long)v.tail, (long long)v.lo, (long long)v.hi, (long long)v.head, (long long)own[SH_ROW_LO], (long long)own[SH_ROW_HI], (long long)own[SH_ROWS], line.c_str());
+}
+
 }  // namespace ffq
 
 using namespace ffq;
@@ -448,7 +513,7 @@ struct ffq_shard {
     hipStream_t comm = nullptr;            // the hand-off stream
     hipStream_t gstream = nullptr;         // the gather stream
     hipEvent_t ev_x[2] = {nullptr, nullptr}, ev_g[2] = {nullptr, nullptr}, ev_w = nullptr;
-    int64_t *d_words = nullptr;            // [16]: the words, row_lo, row_hi, rows
+    int64_t *d_words = nullptr;            // [SH_BLOCK]: the rank's own block -- the words, row_lo, row_hi, rows
     int64_t *d_all = nullptr;              // [world * SH_WORDS]
     int64_t *h_all = nullptr, *h_own = nullptr;      // pinned
     int64_t *hm_own = nullptr;             // h_own as the device sees it (host-mapped)
@@ -458,7 +523,6 @@ struct ffq_shard {
     bool pending = false, handoff_timed = false;
     ShView v{};
     uint8_t *ext = nullptr;
-    int64_t start = -1;                    // stream offset the first search of the last local scan started at (-1: the view's start)
     uint32_t flags = 0;
     int qual_add = 0;
     int64_t *d_table = nullptr, table_cap = 0, *d_qoff = nullptr, qual_cap = 0;
@@ -481,16 +545,14 @@ struct ffq_shard {
     hipEvent_t diag_ev = nullptr;          //   allocated or freed while a kernel is stuck -- those calls wait for the device)
     int64_t *h_diag = nullptr;
     bool leaked = false;                   // an abort could not drain the streams: destroy frees nothing on the device
-    // a failure of THIS rank's own scan inside a step: the peers are told through the words before it is returned
-    int local_fail = 0;
-    std::string local_msg;
+    ShOwnFailure mine;                     // a failure of THIS rank's own scan inside a step (sh_fail_locally)
 };
+
+static void shard_fail_locally(ffq_shard *s, int rc) { sh_fail_locally(s->mine, rc, s->v, s->h_own); }
 
 // the streams of a step: the pipelined step's own three, or -- serial -- the scan stream for everything
 static hipStream_t sh_xs(const ffq_shard *s, bool overlap) { return (overlap && !s->tr->serial) ? s->comm : s->c->stream; }
 static hipStream_t sh_gs(const ffq_shard *s) { return s->tr->serial ? s->c->stream : s->gstream; }
-
-static bool sh_debug() { static const bool on = getenv("FFQ_SHARD_DEBUG") != nullptr; return on; }
 
 static ShView sh_view(const ffq_shard *s, int64_t tail, int64_t head) { return sh_make_view(s->lo, s->hi, s->total, s->origin, tail, head); }
 
@@ -507,10 +569,10 @@ static int shard_alloc(ffq_shard *s, ffq_shard *parent = nullptr)
     for (auto &e : s->ev_x) HIPCHK(hipEventCreate(&e));
     for (auto &e : s->ev_g) HIPCHK(hipEventCreate(&e));
     HIPCHK(hipEventCreateWithFlags(&s->ev_w, hipEventDisableTiming));
-    HIPCHK(hipMalloc((void **)&s->d_words, 16 * 8));
+    HIPCHK(hipMalloc((void **)&s->d_words, SH_BLOCK * 8));
     HIPCHK(hipMalloc((void **)&s->d_all, (size_t)s->world * SH_WORDS * 8));
     HIPCHK(hipHostMalloc((void **)&s->h_all, (size_t)s->world * SH_WORDS * 8, hipHostMallocDefault));
-    HIPCHK(hipHostMalloc((void **)&s->h_own, 16 * 8, hipHostMallocMapped));
+    HIPCHK(hipHostMalloc((void **)&s->h_own, SH_BLOCK * 8, hipHostMallocMapped));
     HIPCHK(hipHostGetDevicePointer((void **)&s->hm_own, s->h_own, 0));
     HIPCHK(hipStreamCreateWithFlags(&s->diag_st, hipStreamNonBlocking));
     HIPCHK(hipEventCreateWithFlags(&s->diag_ev, hipEventDisableTiming));
@@ -823,7 +885,7 @@ static int shard_gather_host_words(ffq_shard *s)
 {
     hipStream_t st = s->c->stream;
     mark_other(s->c);
-    HIPCHK(hipMemcpyAsync(s->d_words, s->h_own, 16 * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(s->d_words, s->h_own, SH_BLOCK * 8, hipMemcpyHostToDevice, st));
     return shard_gather(s);
 }
 
@@ -904,11 +966,11 @@ extern "C" int ffq_shard_step_submit(ffq_shard *s, uint8_t *d_ext, int overlap_h
     int64_t tail, head;
     sh_halo_sizes(s->B, s->rank, s->tail_bytes, s->head_bytes, &tail, &head);
     s->v = sh_view(s, tail, head);
-    s->ext = d_ext; s->start = -1;
+    s->ext = d_ext;
     s->flags = flags; s->qual_add = qual_add;        // (FFQ_F_NO_TIMING: no marks; the hand-off's wait in front of the scan rules the barrier-free dispatch out)
     s->d_table = d_table; s->table_cap = table_cap; s->d_qual = d_qual; s->qual_cap = qual_cap; s->d_qoff = d_qoff;
     s->handoff_bytes = 0; s->handoff_timed = false;
-    s->local_fail = 0; s->last_stage = FFQ_SHARD_STAGE_NONE;
+    s->mine.code = 0; s->last_stage = FFQ_SHARD_STAGE_NONE;
     s->from_file = s->fd >= 0 && d_ext == s->file_ext;
     // The scan's scratch FIRST: a scratch that has to grow waits for the scan stream (and hipFree for the device), and that
     // wait must not sit behind this step's hand-off -- a collective whose peer may never come.
@@ -927,9 +989,8 @@ extern "C" int ffq_shard_step_submit(ffq_shard *s, uint8_t *d_ext, int overlap_h
     if (s->v.n_bytes == 0) {
         // an empty view (nothing is enqueued for it, the device holds no result block of this scan): its words on the host --
         // no rows, the search "ended" at the view's start, more look-ahead wanted unless the view ends the stream
-        int64_t *h = s->h_own;
-        sh_words_empty(s->v, s->head_bytes, h);
-        h[8] = h[9] = h[10] = 0;
+        sh_words_empty(s->v, s->head_bytes, s->h_own);
+        sh_owns_no_rows(s->h_own);
         rc = shard_gather_host_words(s);
     } else rc = shard_words_and_gather(s, 0);
     if (rc) return rc;
@@ -941,7 +1002,6 @@ extern "C" int ffq_shard_step_submit(ffq_shard *s, uint8_t *d_ext, int overlap_h
 static int shard_local(ffq_shard *s, ffq_scan_result *res, int64_t start)
 {
     const int64_t offset = start < 0 ? 0 : std::max(start, s->v.start) - s->v.add;
-    s->start = start;
     s->c->watchdog_s = s->tr->timeout_s;
     int rc = ffq_scan_device(s->c, s->ext, s->v.n_bytes, s->v.sentinel, offset, s->v.eof, s->v.add, s->flags, s->qual_add,
                              s->d_table, s->table_cap, s->d_qual, s->qual_cap, s->d_qoff, res);
@@ -949,13 +1009,118 @@ static int shard_local(ffq_shard *s, ffq_scan_result *res, int64_t start)
     if (rc == FFQ_E_TIMEOUT) return shard_tripped(s, s->tr->timeout_s);
     if (rc && rc != FFQ_E_TABLE_FULL) {
         // (every rank gathers at the end of a repair round: mine says "failed", and the step ends with INTERNAL everywhere)
-        s->local_fail = rc; s->local_msg = ffq_last_error();
-        sh_words_failed(s->v, s->h_own);
-        s->h_own[8] = s->h_own[9] = s->h_own[10] = 0;
+        shard_fail_locally(s, rc);
         return shard_gather_host_words(s);
     }
     return shard_words_and_gather(s, offset);
 }
+
+// ---- growing a view ------------------------------------------------------------------------------------------------------
+// A view with `head` bytes of look-ahead (the caller's buffer has room for its own halo only): the block it goes into -- a
+// NEW one, or, reuse allowed, s->grown again when that has room and is not the view in use -- and the old view's bytes
+// copied across, queued on the scan stream.  Nothing of the shard changes before shard_adopt_view.
+struct ShLarger { ShView v; uint8_t *blk; int64_t cap; bool fresh; };
+
+static int shard_larger_view(ffq_shard *s, int64_t head, bool reuse, ShLarger *L)
+{
+    L->v = sh_view(s, s->v.tail, head);
+    L->fresh = !reuse || L->v.n_bytes + 64 > s->grown_cap || s->ext == s->grown;
+    L->blk = s->grown; L->cap = s->grown_cap;
+    if (L->fresh) {
+        L->blk = nullptr; L->cap = L->v.n_bytes + 64;
+        if (hipMalloc((void **)&L->blk, (size_t)L->cap) != hipSuccess) return fail(FFQ_E_NOMEM, "ffq_shard: no memory for a view of %lld bytes", (long long)L->cap);
+    }
+    mark_other(s->c);
+    const hipError_t e = hipMemcpyAsync(L->blk, s->ext, (size_t)s->v.n_bytes, hipMemcpyDeviceToDevice, s->c->stream);
+    if (e == hipSuccess) return FFQ_OK;
+    if (L->fresh) s->graveyard.push_back(L->blk);
+    return fail(FFQ_E_HIP, "ffq_shard: %s", hipGetErrorString(e));
+}
+
+// (views that are replaced go to the graveyard, not to hipFree: a free waits for the DEVICE -- for the other lane's hand-off,
+// for a collective whose peer may never come, for the exchange that still reads the old view)
+static void shard_adopt_view(ffq_shard *s, const ShLarger &L)
+{
+    if (L.fresh) {
+        if (s->grown) s->graveyard.push_back(s->grown);
+        s->grown = L.blk; s->grown_cap = L.cap;
+    }
+    s->ext = L.blk; s->v = L.v;
+}
+
+// every rank's bytes are the file's: a rank that needs more look-ahead reads it itself, nobody serves anybody.  Always a
+// new block, and the scan stream drained under the watchdog before the file's bytes go in behind the old view's.
+static int shard_grow_from_file(ffq_shard *s, int64_t head)
+{
+    ShLarger L;
+    int rc = shard_larger_view(s, head, false, &L);
+    if (rc) return rc;
+    rc = shard_sync_scan_stream(s);
+    int64_t got = 0;
+    const int64_t more = L.v.head - s->v.head;
+    if (!rc) rc = stage_fd2d(s->c, L.blk + s->v.n_bytes, s->fd, s->hi + s->v.head, more, &got);
+    if (!rc && got != more) rc = fail(FFQ_E_ARG, "ffq_shard: the file ends at byte %lld, its bounds say %lld", (long long)(s->hi + s->v.head + got), (long long)s->total);
+    if (rc) { s->graveyard.push_back(L.blk); return rc; }
+    shard_adopt_view(s, L);
+    return FFQ_OK;
+}
+
+// the look-ahead of every growing rank served by whoever owns the bytes: ONE exchange on the scan stream.  A rank that
+// grows receives into its larger view; what it PROVIDES in this round still comes out of the view in use -- which may be
+// the old grown block (a rank growing a second time that a neighbour's look-ahead reaches into): that block leaves for the
+// graveyard only behind the exchange that reads it.
+static int shard_grow_by_exchange(ffq_shard *s, const ShRound &d, const int64_t *A)
+{
+    std::vector<ShPiece> plan;
+    sh_grow_plan(A, s->B, d.grow, plan);
+    ShLarger L{s->v, s->ext, 0, false};
+    int rc = d.i_grow ? shard_larger_view(s, A[(size_t)s->rank * SH_WORDS + 3], true, &L) : FFQ_OK;
+    if (rc) return rc;
+    mark_other(s->c);
+    rc = shard_serve(s, plan, s->ext, s->v.tail, L.blk, L.v.start, s->c->stream);
+    if (rc) { if (L.fresh) s->graveyard.push_back(L.blk); return rc; }
+    if (d.i_grow) shard_adopt_view(s, L);
+    return FFQ_OK;
+}
+
+// ---- sh_settle's hooks over a shard (ffq_shard_proto.h) --------------------------------------------------------------------
+// what the device step and the slabs share: the gather in flight waited for under the watchdog, host-made words published
+struct ShDevRank {
+    ffq_shard *s;
+    ffq_shard_result *out;
+    int gather(const int64_t **A)
+    {
+        int rc = shard_wait_mark(s, s->ev_g[1]);
+        if (!rc) rc = s->tr->gather_finish(s->h_all, s->ev_g[1]);
+        if (rc) { if (rc == FFQ_E_TIMEOUT) { s->tr->poisoned = true; if (!s->last_stage) s->last_stage = FFQ_SHARD_STAGE_GATHER; } return rc; }
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, s->ev_g[0], s->ev_g[1]) == hipSuccess) out->allgather_ms += ms;
+        *A = s->h_all;
+        return FFQ_OK;
+    }
+    const ShView &view() const { return s->v; }
+    int local_failure() const { return s->mine.code; }
+    int publish(const int64_t *w)         // (NULL: my words stand, the others' rounds need them again)
+    {
+        if (w) { memcpy(s->h_own, w, SH_WORDS * 8); sh_owns_no_rows(s->h_own); }
+        return shard_gather_host_words(s);
+    }
+};
+
+struct ShStepRank : ShDevRank {
+    void look(const ShRound &d, const int64_t *A, int rounds, int regathers)
+    {
+        if (sh_debug()) sh_debug_round("", s->rank, s->world, d, A, rounds, regathers, s->v, s->h_own);
+    }
+    // (the scan that needed a later tier is through: k_shard_words over its result once more)
+    int not_ready(int64_t start) { return shard_words_and_gather(s, start < 0 ? 0 : std::max(start, s->v.start) - s->v.add); }
+    int grow(const ShRound &d, const int64_t *A)
+    {
+        if (!s->from_file) return shard_grow_by_exchange(s, d, A);
+        return d.i_grow ? shard_grow_from_file(s, A[(size_t)s->rank * SH_WORDS + 3]) : FFQ_OK;
+    }
+    int rescan(int64_t start) { return shard_local(s, &out->scan, start); }
+};
 
 extern "C" int ffq_shard_step_wait(ffq_shard *s, ffq_shard_result *out)
 {
@@ -964,8 +1129,6 @@ extern "C" int ffq_shard_step_wait(ffq_shard *s, ffq_shard_result *out)
     memset(out, 0, sizeof *out);
     ffq_ctx *c = s->c;
     HIPCHK(hipSetDevice(c->device));
-    const int W = s->world, rank = s->rank;
-    const std::vector<int64_t> &B = s->B;
     out->nranks = s->tr->nranks(s->tr->serial ? 0 : 1);
     out->serial = s->tr->serial ? 1 : 0;
     // The watchdog's first look: the mark behind the scan front.  Once it is through, the hand-off is (the scan waited
@@ -981,150 +1144,16 @@ extern "C" int ffq_shard_step_wait(ffq_shard *s, ffq_shard_result *out)
     if (rc == FFQ_E_TIMEOUT) return shard_tripped(s, s->tr->timeout_s);
     // A scan that failed HERE (not the stream's error: a kernel invariant, no memory for a later tier) must not leave the
     // peers waiting in the next collective: such a scan's words say "not ready" (its result block is marked), every rank
-    // gathers once more, and this rank's words then say "failed" -- INTERNAL on every rank.
-    int &local_fail = s->local_fail;
-    std::string &local_msg = s->local_msg;
-    local_fail = 0;
-    if (rc && rc != FFQ_E_TABLE_FULL) { local_fail = rc; local_msg = ffq_last_error(); }
-    int rounds = 0, regathers = 0;
-    float ms = 0;
-    for (;;) {
-        rc = shard_wait_mark(s, s->ev_g[1]);
-        if (!rc) rc = s->tr->gather_finish(s->h_all, s->ev_g[1]);
-        if (rc) { if (rc == FFQ_E_TIMEOUT) { s->tr->poisoned = true; if (!s->last_stage) s->last_stage = FFQ_SHARD_STAGE_GATHER; } return rc; }
-        if (hipEventElapsedTime(&ms, s->ev_g[0], s->ev_g[1]) == hipSuccess) out->allgather_ms += ms;
-        const int64_t *A = s->h_all;
-        auto word = [&](int r, int k) { return A[(size_t)r * SH_WORDS + k]; };
-        const ShRound d = sh_decide(A, W, rank, B, s->v);          // (ffq_shard_proto.h: the protocol's one statement)
-        if (sh_debug()) {
-            // FFQ_SHARD_DEBUG=1: what this rank sees in every round (a run on several GPUs that nobody can attach to)
-            std::string line;
-            char buf[256];
-            for (int r = 0; r < W; r++) {
-                snprintf(buf, sizeof buf, " [%d: exit %lld first %lld n %lld want %lld had %lld err %lld/%lld search %lld]", r, (long long)word(r, 0), (long long)word(r, 1),
-                         (long long)word(r, 2), (long long)word(r, 3), (long long)word(r, 4), (long long)word(r, 5), (long long)word(r, 6), (long long)word(r, 7));
-                line += buf;
-            }
-            fprintf(stderr, "[ffq shard %d/%d] round %d regather %d kind %d view [%lld | %lld, %lld | %lld] rows %lld..%lld of %lld:%s\n", rank, W, rounds, regathers, (int)d.kind,
-                    (long long)s->v.tail, (long long)s->v.lo, (long long)s->v.hi, (long long)s->v.head, (long long)s->h_own[8], (long long)s->h_own[9], (long long)s->h_own[10], line.c_str());
-        }
-        if (d.kind == ShRound::TABLE_FULL) {
-            out->scan.n_records = d.need;
-            return fail(FFQ_E_TABLE_FULL, "rank %d: offset table too small (%lld records in its view)", d.who, (long long)d.need);
-        }
-        if (d.kind == ShRound::QUAL_FULL) {
-            out->scan.n_records = 0; out->scan.n_qual_bytes = d.need;
-            return fail(FFQ_E_TABLE_FULL, "rank %d: quality buffer too small (%lld decoded bytes in its view)", d.who, (long long)d.need);
-        }
-        if (d.kind == ShRound::INTERNAL) {
-            if (local_fail) return fail(local_fail, "%s", local_msg.c_str());            // (mine: my own error, not "rank r failed")
-            return fail(FFQ_E_INTERNAL, "sharded scan: rank %d %s", d.who, d.what);
-        }
-        if (d.kind == ShRound::NOT_READY) {
-            // some rank's scan needed a later tier (a host round trip inside its ffq_scan_wait): every rank's scan is through
-            // by now -- the words once more
-            if (++regathers > 4) return fail(FFQ_E_INTERNAL, "sharded scan: a rank's result does not become ready");
-            if (local_fail) {
-                sh_words_failed(s->v, s->h_own);
-                s->h_own[8] = s->h_own[9] = s->h_own[10] = 0;
-                rc = shard_gather_host_words(s);
-            } else {
-                int64_t off = s->start < 0 ? 0 : std::max(s->start, s->v.start) - s->v.add;
-                rc = shard_words_and_gather(s, off);
-            }
-            if (rc) return rc;
-            continue;
-        }
-        if (local_fail) return fail(local_fail, "%s", local_msg.c_str());
-        if (d.kind == ShRound::STREAM_ERROR) { out->err_state = d.err_state; out->err_byte = d.err_byte; break; }
-        if (d.kind == ShRound::SETTLED) break;
-        const std::vector<int> &grow = d.grow;
-        if (++rounds > sh_max_rounds(W)) return fail(FFQ_E_INTERNAL, "sharded scan does not settle (%d rounds)", rounds);
-        const bool i_grow = d.i_grow, i_force = d.i_force;
-        int64_t start = s->start;
-        if (!grow.empty() && s->from_file) {
-            // every rank's bytes are the file's: a rank that needs more look-ahead reads it itself, nobody serves anybody
-            if (i_grow) {
-                ShView nv = sh_view(s, s->v.tail, word(rank, 3));
-                uint8_t *g = nullptr;
-                const int64_t cap = nv.n_bytes + 64;
-                if (hipMalloc((void **)&g, (size_t)cap) != hipSuccess) return fail(FFQ_E_NOMEM, "ffq_shard: no memory for a view of %lld bytes", (long long)cap);
-                mark_other(c);
-                hipError_t e = hipMemcpyAsync(g, s->ext, (size_t)s->v.n_bytes, hipMemcpyDeviceToDevice, c->stream);
-                // (waits with the watchdog's deadline; views that are replaced go to the graveyard, not to hipFree: a free waits
-                // for the DEVICE -- for the other lane's hand-off, for a collective whose peer may never come)
-                rc = e != hipSuccess ? fail(FFQ_E_HIP, "ffq_shard: %s", hipGetErrorString(e)) : shard_sync_scan_stream(s);
-                int64_t got = 0;
-                const int64_t more = nv.head - s->v.head;
-                if (!rc) rc = stage_fd2d(c, g + s->v.n_bytes, s->fd, s->hi + s->v.head, more, &got);
-                if (!rc && got != more) rc = fail(FFQ_E_ARG, "ffq_shard: the file ends at byte %lld, its bounds say %lld", (long long)(s->hi + s->v.head + got), (long long)s->total);
-                if (rc) { s->graveyard.push_back(g); return rc; }
-                if (s->grown) s->graveyard.push_back(s->grown);
-                s->grown = g; s->grown_cap = cap;
-                s->ext = g; s->v = nv;
-            }
-        } else if (!grow.empty()) {
-            std::vector<ShPiece> plan;
-            sh_grow_plan(A, B, grow, plan);
-            uint8_t *src_ext = s->ext;
-            uint8_t *dst_ext = s->ext;
-            int64_t dst_start = s->v.start;
-            ShView nv = s->v;
-            uint8_t *old_grown = nullptr;
-            if (i_grow) {
-                // a view with more look-ahead (the caller's buffer has room for its own halo only)
-                nv = sh_view(s, s->v.tail, word(rank, 3));
-                if (nv.n_bytes + 64 > s->grown_cap || s->ext == s->grown) {
-                    uint8_t *g = nullptr;
-                    const int64_t cap = nv.n_bytes + 64;
-                    if (hipMalloc((void **)&g, (size_t)cap) != hipSuccess) return fail(FFQ_E_NOMEM, "ffq_shard: no memory for a view of %lld bytes", (long long)cap);
-                    old_grown = s->grown;
-                    s->grown = g; s->grown_cap = cap;
-                }
-                mark_other(c);
-                HIPCHK(hipMemcpyAsync(s->grown, s->ext, (size_t)s->v.n_bytes, hipMemcpyDeviceToDevice, c->stream));
-                dst_ext = s->grown; dst_start = nv.start;
-            }
-            mark_other(c);
-            // (src_ext may BE the old grown view -- a rank growing a second time that a neighbour's look-ahead reaches into in
-            // the same round: it is freed only once the exchange that reads it is through)
-            rc = shard_serve(s, plan, src_ext, s->v.tail, dst_ext, dst_start, c->stream);
-            if (old_grown) s->graveyard.push_back(old_grown);      // (freed with the shard: the exchange that reads it may still be in flight)
-            if (rc) return rc;
-            if (i_grow) { s->ext = s->grown; s->v = nv; }
-        }
-        bool rescan = i_grow || i_force;
-        if (i_force) {
-            if (d.passed_over) {
-                // the chain passes over my whole range (or ends before it): I own nothing
-                int64_t *h = s->h_own;
-                sh_words_passed_over(s->v, d.prev_exit, d.prev_search, h);
-                h[8] = 0; h[9] = 0; h[10] = 0;
-                s->start = d.prev_search;
-                rc = shard_gather_host_words(s);
-                if (rc) return rc;
-                continue;
-            }
-            start = d.prev_search;
-        }
-        if (rescan) rc = shard_local(s, &out->scan, start);
-        else rc = shard_gather_host_words(s);      // (my words stand: the others' rounds need them again)
-        if (rc) return rc;
-    }
+    // gathers once more, and this rank's words then say "failed" -- INTERNAL on every rank (sh_settle's NOT_READY).
+    s->mine.code = 0;
+    if (rc && rc != FFQ_E_TABLE_FULL) { s->mine.code = rc; s->mine.msg = ffq_last_error(); }
+    ShStepRank R{{s, out}};
+    const ShVerdict v = sh_settle(R, s->world, s->rank, s->B);
+    if (!v.ok()) return shard_fail_verdict(v, s->mine, out);
     // the hand-off's own time (events on the stream it ran on)
+    float ms = 0;
     if (s->handoff_timed && hipEventElapsedTime(&ms, s->ev_x[0], s->ev_x[1]) == hipSuccess) out->handoff_ms = ms;
-    const int64_t *h = s->h_own;
-    out->n_rows = h[10]; out->row_lo = h[8]; out->row_hi = h[9];
-    out->exit_pos = h[0]; out->first_pos = h[1];
-    out->n_own_records = h[9] - h[8];
-    int64_t base = 0, tot = 0;
-    for (int r = 0; r < W; r++) {
-        const int64_t cnt = s->h_all[(size_t)r * SH_WORDS + 2];
-        if (r < rank) base += cnt;
-        tot += cnt;
-    }
-    out->record_base = base; out->total_records = tot;
-    out->rounds = rounds; out->regathers = regathers;
+    shard_fill_result(out, s->h_own, s->h_all, s->world, s->rank, v);
     out->halo_source = s->from_file ? 1 : 0;
     out->handoff_bytes = s->handoff_bytes;
     out->d_ext = s->ext; out->tail = s->v.tail; out->head = s->v.head;
@@ -1270,6 +1299,23 @@ static int slab_pass(ffq_shard *s, int fd, int64_t slab_bytes, uint32_t flags, i
     return FFQ_OK;
 }
 
+// sh_settle's hooks over the slabs: a rescan is a streaming pass of the whole range and its words, made on the host
+template <class Pass>
+struct ShSlabRank : ShDevRank {
+    Pass &pass;
+    const int64_t *n_slabs;
+    void look(const ShRound &d, const int64_t *A, int rounds, int regathers)
+    {
+        if (!sh_debug()) return;
+        char driver[48];
+        snprintf(driver, sizeof driver, " slabs %lld", (long long)*n_slabs);
+        sh_debug_round(driver, s->rank, s->world, d, A, rounds, regathers, s->v, s->h_own);
+    }
+    int not_ready(int64_t) { return SH_REFUSED; }              // (every slab's scan is through when its words are made)
+    int grow(const ShRound &, const int64_t *) { return FFQ_OK; }      // (nobody asks: a pass reads its own look-ahead on)
+    int rescan(int64_t start) { pass(start); return shard_gather_host_words(s); }
+};
+
 extern "C" int ffq_shard_scan_fd_slabs(ffq_shard *s, int fd, int64_t slab_bytes, uint32_t flags, int64_t *d_table, int64_t table_cap,
                                        ffq_shard_result *out)
 {
@@ -1289,37 +1335,32 @@ extern "C" int ffq_shard_scan_fd_slabs(ffq_shard *s, int fd, int64_t slab_bytes,
     }
     int rc = scan_reserve(c, s->slab_cap, flags, table_cap, 0);
     if (rc) return rc;
-    const int W = s->world, rank = s->rank;
-    const std::vector<int64_t> &B = s->B;
     int64_t tail, head;
-    sh_halo_sizes(B, rank, s->tail_bytes, s->head_bytes, &tail, &head);
+    sh_halo_sizes(s->B, s->rank, s->tail_bytes, s->head_bytes, &tail, &head);
     out->nranks = s->tr->nranks(s->tr->serial ? 0 : 1);
     out->serial = s->tr->serial ? 1 : 0;
-    s->handoff_bytes = 0; s->handoff_timed = false; s->local_fail = 0; s->last_stage = FFQ_SHARD_STAGE_NONE;
+    s->handoff_bytes = 0; s->handoff_timed = false; s->mine.code = 0; s->last_stage = FFQ_SHARD_STAGE_NONE;
     s->flags = flags; s->d_table = d_table; s->table_cap = table_cap; s->ext = nullptr; s->from_file = true;
-    int64_t n_slabs = 0, n_loaded = 0, nrows = 0, start = -1;
+    int64_t n_slabs = 0, n_loaded = 0;
     int64_t *h = s->h_own;
-    int64_t i0 = 0, i1 = 0;
-    // one streaming pass of my view from `start` (< 0: the view's beginning, a guess) and its eight words
-    auto pass = [&](int64_t st) -> int {
-        start = st;
-        i0 = i1 = 0; nrows = 0;
+    // one streaming pass of my view from `st` (< 0: the view's beginning, a guess) and its eight words
+    auto pass = [&](int64_t st) {
+        int64_t nrows = 0;
+        sh_owns_no_rows(h);
         s->v = sh_view(s, tail, head);
-        if (s->v.n_bytes == 0) { sh_words_empty(s->v, s->head_bytes, h); h[8] = h[9] = h[10] = 0; return FFQ_OK; }
+        if (s->v.n_bytes == 0) { sh_words_empty(s->v, s->head_bytes, h); return; }
         ffq_scan_result last;
         int r = slab_pass(s, fd, s->slab_cap, flags, d_table, table_cap, st, &head, &last, &nrows, &n_slabs, &n_loaded);
         out->scan = last;
         if (r == FFQ_E_TABLE_FULL) {
             const int64_t tf[SH_WORDS] = {SH_UNKNOWN, SH_UNKNOWN, 0, 0, head, SH_ERR_TABLE_FULL, nrows, 0};
-            memcpy(h, tf, sizeof tf); h[8] = h[9] = h[10] = 0;
-            return FFQ_OK;
+            memcpy(h, tf, sizeof tf);
+            return;
         }
-        if (r) { s->local_fail = r; s->local_msg = ffq_last_error(); sh_words_failed(s->v, h); h[8] = h[9] = h[10] = 0; return FFQ_OK; }
+        if (r) return shard_fail_locally(s, r);
         s->v = sh_view(s, tail, head);                                 // (the look-ahead the pass ended with)
         int64_t cut[6];
-        if ((r = ffq_table_cut(c, d_table, nrows, sh_lo_bound(s->v), sh_hi_bound(s->v), cut))) {     // (the peers hear of it in the gather)
-            s->local_fail = r; s->local_msg = ffq_last_error(); sh_words_failed(s->v, h); h[8] = h[9] = h[10] = 0; return FFQ_OK;
-        }
+        if ((r = ffq_table_cut(c, d_table, nrows, sh_lo_bound(s->v), sh_hi_bound(s->v), cut))) return shard_fail_locally(s, r);      // (the peers hear of it in the gather)
         ShScanFacts f;
         f.n = nrows; f.i0 = cut[0]; f.i1 = cut[1]; f.p_i0 = cut[2]; f.p_i1 = cut[3]; f.q1 = cut[5];
         f.end_state = last.end_state; f.last_status = last.last_status; f.last_pos0 = last.last_pos[0];
@@ -1329,65 +1370,13 @@ extern "C" int ffq_shard_scan_fd_slabs(ffq_shard *s, int fd, int64_t slab_bytes,
         const int64_t off0 = st < 0 ? 0 : std::max(st, s->v.start) - s->v.add;
         sh_words_from(s->v, f, off0, s->head_bytes, h);
         h[3] = 0;                                                      // (a look-ahead that had to grow was read on, above)
-        i0 = cut[0]; i1 = cut[1];
-        h[8] = i0; h[9] = i1; h[10] = nrows;
-        return FFQ_OK;
+        h[SH_ROW_LO] = cut[0]; h[SH_ROW_HI] = cut[1]; h[SH_ROWS] = nrows;
     };
-    if ((rc = pass(-1))) return rc;
-    if ((rc = shard_gather_host_words(s))) return rc;
-    int rounds = 0;
-    float ms = 0;
-    for (;;) {
-        rc = shard_wait_mark(s, s->ev_g[1]);
-        if (!rc) rc = s->tr->gather_finish(s->h_all, s->ev_g[1]);
-        if (rc) { if (rc == FFQ_E_TIMEOUT) { s->tr->poisoned = true; if (!s->last_stage) s->last_stage = FFQ_SHARD_STAGE_GATHER; } return rc; }
-        if (hipEventElapsedTime(&ms, s->ev_g[0], s->ev_g[1]) == hipSuccess) out->allgather_ms += ms;
-        const int64_t *A = s->h_all;
-        const ShRound d = sh_decide(A, W, rank, B, s->v);
-        if (sh_debug()) {
-            std::string line;
-            char buf[256];
-            for (int r = 0; r < W; r++) {
-                snprintf(buf, sizeof buf, " [%d: exit %lld first %lld n %lld err %lld/%lld search %lld]", r, (long long)A[r * SH_WORDS], (long long)A[r * SH_WORDS + 1],
-                         (long long)A[r * SH_WORDS + 2], (long long)A[r * SH_WORDS + 5], (long long)A[r * SH_WORDS + 6], (long long)A[r * SH_WORDS + 7]);
-                line += buf;
-            }
-            fprintf(stderr, "[ffq shard %d/%d slabs] round %d kind %d slabs %lld rows %lld..%lld of %lld:%s\n", rank, W, rounds, (int)d.kind, (long long)n_slabs,
-                    (long long)h[8], (long long)h[9], (long long)h[10], line.c_str());
-        }
-        if (d.kind == ShRound::TABLE_FULL) {
-            out->scan.n_records = d.need;
-            return fail(FFQ_E_TABLE_FULL, "rank %d: offset table too small (%lld records in its view)", d.who, (long long)d.need);
-        }
-        if (d.kind == ShRound::INTERNAL || d.kind == ShRound::QUAL_FULL || d.kind == ShRound::NOT_READY) {
-            if (s->local_fail) return fail(s->local_fail, "%s", s->local_msg.c_str());
-            return fail(FFQ_E_INTERNAL, "sharded scan: rank %d %s", d.who, d.what);
-        }
-        if (s->local_fail) return fail(s->local_fail, "%s", s->local_msg.c_str());
-        if (d.kind == ShRound::STREAM_ERROR) { out->err_state = d.err_state; out->err_byte = d.err_byte; break; }
-        if (d.kind == ShRound::SETTLED) break;
-        if (++rounds > sh_max_rounds(W)) return fail(FFQ_E_INTERNAL, "sharded scan does not settle (%d rounds)", rounds);
-        if (d.i_force) {
-            if (d.passed_over) {
-                sh_words_passed_over(s->v, d.prev_exit, d.prev_search, h);
-                h[8] = h[9] = h[10] = 0;
-                i0 = i1 = 0; nrows = 0;
-                start = d.prev_search;
-            } else if ((rc = pass(d.prev_search))) return rc;           // my range again, from the left neighbour's exit
-        }
-        if ((rc = shard_gather_host_words(s))) return rc;               // (mine stand, or are new: the others' rounds need them)
-    }
-    out->n_rows = h[10]; out->row_lo = h[8]; out->row_hi = h[9];
-    out->exit_pos = h[0]; out->first_pos = h[1];
-    out->n_own_records = h[9] - h[8];
-    int64_t base = 0, tot = 0;
-    for (int r = 0; r < W; r++) {
-        const int64_t cnt = s->h_all[(size_t)r * SH_WORDS + 2];
-        if (r < rank) base += cnt;
-        tot += cnt;
-    }
-    out->record_base = base; out->total_records = tot;
-    out->rounds = rounds;
+    ShSlabRank<decltype(pass)> R{{s, out}, pass, &n_slabs};
+    if ((rc = R.rescan(-1))) return rc;
+    const ShVerdict v = sh_settle(R, s->world, s->rank, s->B);
+    if (!v.ok()) return shard_fail_verdict(v, s->mine, out);
+    shard_fill_result(out, h, s->h_all, s->world, s->rank, v);
     out->halo_source = 1;
     out->handoff_bytes = 0;
     out->n_slabs = n_slabs; out->bytes_read = n_loaded;

@@ -1,10 +1,13 @@
 // ffq_shard_proto.h -- the PROTOCOL of the byte-range shards, and nothing of a device: what a rank's scan says about its
 // two edges (the eight words), what everybody's words mean for the next round (settled / an error of the stream / a
 // look-ahead to grow / an entry to re-enter from the left neighbour's exit), who hands which bytes to whom, the barrier of
-// the in-process world.  ONE statement of it: the device step (ffq_shard.h: HIP streams, RCCL) and the host step
-// (ffq_shard_host.h: caller-supplied scan / exchange / gather, what the CPU tests drive over gloo) both run on these
-// functions, so a change of the protocol lands once.  No HIP in here (tests/tsan_host_threads.cpp includes it for the
-// barrier it runs its ranks over); under hipcc sh_words_from is also device code (k_shard_words calls it).
+// the in-process world, and THE LOOP that looks at the words round after round until every rank's edge is proven
+// (sh_settle: the order a round's outcome is answered in, the two limits, the repair sequence).  ONE statement of it: the
+// device step and the slabs (ffq_shard.h: HIP streams, RCCL) and the host step (ffq_shard_host.h: caller-supplied scan /
+// exchange / gather, what the CPU tests drive over gloo) all run on these functions -- each is a set of hooks under
+// sh_settle --, so a change of the protocol lands once.  No HIP in here (tests/tsan_host_threads.cpp includes it for the
+// barrier it runs its ranks over, tests/shard_settle_host.cpp drives the loop with scripted words); under hipcc
+// sh_words_from is also device code (k_shard_words calls it).
 //
 // What is sharded is the record chain of readfastq_iter (/root/reference/src/fastqandfurious.py:251-279): rank r owns the
 // stream bytes [S_r, S_r+1) and every record whose '@' lies in them; what the reference does with a record that does not
@@ -37,6 +40,9 @@ constexpr int64_t SH_ERR_TABLE_FULL = 100; // (beside the FFQ_END_ERR_* codes) t
 constexpr int64_t SH_ERR_QUAL_FULL = 102;  // ... nor its quality buffer the view's decoded bytes
 constexpr int64_t SH_NOT_READY = 101;      // this rank's scan needs a later tier (host round trip): gather again when it is through
 constexpr int SH_WORDS = 8;                // exit, first, own count, look-ahead wanted, look-ahead had, error, error byte / rows needed, exit's search start
+// a rank's OWN BLOCK: the eight words it publishes and, behind them, what only the rank itself needs of its scan
+constexpr int SH_BLOCK = 16, SH_ROW_LO = 8, SH_ROW_HI = 9, SH_ROWS = 10;      // its first row, the row behind its last, rows in the table
+static inline void sh_owns_no_rows(int64_t *block) { block[SH_ROW_LO] = block[SH_ROW_HI] = block[SH_ROWS] = 0; }
 
 struct ShView {                            // a rank's [tail | own | head] buffer and its coordinates
     int64_t lo, hi, total, origin;         // my range, the stream's end, the offset of the stream's first byte
@@ -228,6 +234,82 @@ static inline int sh_max_rounds(int W) { return 2 * W + 48; }
 static inline void sh_words_failed(const ShView &v, int64_t w[SH_WORDS])
 {
     w[0] = SH_UNKNOWN; w[1] = SH_UNKNOWN; w[2] = 0; w[3] = 0; w[4] = v.head; w[5] = FFQ_E_INTERNAL; w[6] = 0; w[7] = 0;
+}
+
+// ---- the loop: one look after another until every rank's edge is proven ----------------------------------------------
+// What a step ends with.  No text in here: ffq_shard.h words it (shard_fail_verdict) and fills the result (shard_fill_result).
+struct ShVerdict {
+    enum Kind { SETTLED, STREAM_ERROR, TABLE_FULL, QUAL_FULL, INTERNAL, MINE, NOT_READY, UNSETTLED, HOOK } kind = SETTLED;
+    int who = -1;                        // TABLE_FULL / QUAL_FULL / INTERNAL: the rank
+    int64_t need = 0;                    // TABLE_FULL: rows its view holds; QUAL_FULL: decoded bytes
+    const char *what = "";               // INTERNAL: what that rank's words say
+    int code = 0;                        // MINE: my own step's failure; HOOK: what the hook returned (it has worded it)
+    int32_t err_state = 0;               // STREAM_ERROR (which is a RESULT, like SETTLED: every rank reports it alike)
+    int64_t err_byte = 0;
+    int rounds = 0, regathers = 0;       // repair rounds; gathers repeated because some rank's scan needed a later tier
+    bool ok() const { return kind == SETTLED || kind == STREAM_ERROR; }
+};
+
+constexpr int SH_MAX_REGATHERS = 4;
+constexpr int SH_REFUSED = 1;            // not_ready()'s answer of a rank whose scans are through when it publishes
+
+// The hooks of `Rank` -- what differs between the device step, the slabs and the host step.  Each returns FFQ_OK or an
+// error it has worded itself, which ends the loop at once (HOOK); the words of the first scan are published before the call.
+//   int gather(const int64_t **A)      finish the gather in flight; *A: everybody's words, valid until the next hook
+//   const ShView &view()               my current view
+//   int local_failure()                the code of a failure of my own step that the peers must hear of first, or 0
+//   void look(d, A, rounds, regathers) a round has been decided (FFQ_SHARD_DEBUG)
+//   int not_ready(start)               publish again what my scan from `start` says by now, or SH_REFUSED
+//   int grow(d, A)                     collective: the look-ahead of d.grow grows; if d.i_grow, my view is the larger one afterwards
+//   int rescan(start)                  scan my view from stream offset `start` (< 0: its beginning) and publish the words
+//   int publish(w)                     w: host-made words of a rank that owns no rows; NULL: my words as they stand
+template <class Rank>
+static inline ShVerdict sh_settle(Rank &R, int W, int rank, const std::vector<int64_t> &B)
+{
+    ShVerdict v;
+    int64_t start = -1;                  // where my last scan's first search started (what a rescan after growing starts at again)
+    int64_t w[SH_WORDS];
+    auto ends = [&v](ShVerdict::Kind k, int code = 0) { v.kind = k; v.code = code; return v; };
+    for (;;) {
+        const int64_t *A = nullptr;
+        int rc = R.gather(&A);
+        if (rc) return ends(ShVerdict::HOOK, rc);
+        const ShRound d = sh_decide(A, W, rank, B, R.view());
+        R.look(d, A, v.rounds, v.regathers);
+        v.who = d.who; v.need = d.need; v.what = d.what;
+        // the order of the answers: a table that is too small (every rank must hear the need), then failures -- mine as mine
+        if (d.kind == ShRound::TABLE_FULL) return ends(ShVerdict::TABLE_FULL);
+        if (d.kind == ShRound::QUAL_FULL) return ends(ShVerdict::QUAL_FULL);
+        const int mine = R.local_failure();
+        if (d.kind == ShRound::INTERNAL) return mine ? ends(ShVerdict::MINE, mine) : ends(ShVerdict::INTERNAL);
+        if (d.kind == ShRound::NOT_READY) {
+            // some rank's scan needed a later tier (a host round trip inside its wait): every rank's scan is through by
+            // now -- the words once more; a scan that FAILED there says so now, and the next look is INTERNAL everywhere
+            if (++v.regathers > SH_MAX_REGATHERS) return ends(ShVerdict::NOT_READY);
+            if (mine) { sh_words_failed(R.view(), w); rc = R.publish(w); }
+            else rc = R.not_ready(start);
+            if (rc == SH_REFUSED) return ends(ShVerdict::INTERNAL);
+            if (rc) return ends(ShVerdict::HOOK, rc);
+            continue;
+        }
+        if (mine) return ends(ShVerdict::MINE, mine);
+        if (d.kind == ShRound::STREAM_ERROR) { v.err_state = d.err_state; v.err_byte = d.err_byte; return ends(ShVerdict::STREAM_ERROR); }
+        if (d.kind == ShRound::SETTLED) return ends(ShVerdict::SETTLED);
+        // REPAIR: grow for everybody if anybody grows; then I am passed over / re-enter from the left neighbour's exit /
+        // scan again because my view grew / my words stand (the others' rounds need them again)
+        if (++v.rounds > sh_max_rounds(W)) return ends(ShVerdict::UNSETTLED);
+        if (!d.grow.empty() && (rc = R.grow(d, A))) return ends(ShVerdict::HOOK, rc);
+        if (d.i_force && d.passed_over) {
+            // the chain passes over my whole range (or ends before it): I own nothing
+            sh_words_passed_over(R.view(), d.prev_exit, d.prev_search, w);
+            start = d.prev_search;
+            rc = R.publish(w);
+        } else if (d.i_grow || d.i_force) {
+            if (d.i_force) start = d.prev_search;
+            rc = R.rescan(start);
+        } else rc = R.publish(nullptr);
+        if (rc) return ends(ShVerdict::HOOK, rc);
+    }
 }
 
 // the step watchdog's default: FFQ_SHARD_TIMEOUT_S seconds without progress at one stage of a step (0: wait for ever)
