@@ -690,7 +690,7 @@ extern "C" int ffq_table_render_fastq(ffq_ctx *c, const uint8_t *d_buf, int64_t 
 
 // ---- BGZF members from device bytes (csrc/ffq_deflate.h) --------------------------------------
 static_assert(DFL_BLOCK == FFQ_BGZF_BLOCK_BYTES && DFL_SEG == FFQ_DEFLATE_SEG_BYTES && DFL_ROUND == FFQ_DEFLATE_ROUND_POSITIONS &&
-              DEFLATE_COUNTS == FFQ_DEFLATE_COUNTS, "include/ffq.h");
+              DEFLATE_GRID == FFQ_DEFLATE_GRID_BLOCKS && DEFLATE_COUNTS == FFQ_DEFLATE_COUNTS, "include/ffq.h");
 
 static int64_t deflate_blocks(int64_t n_bytes) { return (n_bytes + DFL_BLOCK - 1) / DFL_BLOCK; }
 

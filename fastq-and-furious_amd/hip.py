@@ -120,6 +120,7 @@ KEY_NONE = 0                 # FFQ_KEY_NONE: a row without a key (ffq_table_seq_
 BGZF_BLOCK_BYTES = 65280     # FFQ_BGZF_BLOCK_BYTES: the bytes ffq_deflate_bgzf puts into a member (what bgzip does)
 DEFLATE_SEG_BYTES = 256      # FFQ_DEFLATE_SEG_BYTES: a match does not cross a multiple of this inside its block
 DEFLATE_ROUND_POSITIONS = 1024   # FFQ_DEFLATE_ROUND_POSITIONS: a position finds candidates of earlier rounds only
+DEFLATE_GRID_BLOCKS = 256    # FFQ_DEFLATE_GRID_BLOCKS: blocks deflated at a time; a workgroup takes every 256th block
 COMPRESS_NONE, COMPRESS_BGZF = 0, 1      # FFQ_COMPRESS_*: ffq_stream_set_compress, ffq_pair_set_compress
 COMPRESS_MODES = {None: COMPRESS_NONE, "bgzf": COMPRESS_BGZF}
 BGZF_EOF = bytes([0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0])    # ffq_bgzf_eof_block

@@ -606,6 +606,7 @@ int ffq_table_render_fastq(ffq_ctx *ctx, const uint8_t *d_buf, int64_t n_bytes, 
 #define FFQ_BGZF_BLOCK_BYTES 65280
 #define FFQ_DEFLATE_SEG_BYTES 256
 #define FFQ_DEFLATE_ROUND_POSITIONS 1024
+#define FFQ_DEFLATE_GRID_BLOCKS 256           /* blocks deflated at a time: an input of more takes the device several passes */
 #define FFQ_DEFLATE_COUNTS 4
 int64_t ffq_deflate_bgzf_bound(int64_t n_bytes);
 int ffq_deflate_bgzf(ffq_ctx *ctx, const uint8_t *d_src, int64_t n_bytes, uint8_t *d_out, int64_t out_cap,

@@ -65,6 +65,33 @@ def illumina_like(n_records, seed=7):
     return b"".join(out)
 
 
+GRID_KINDS = ("noise", "text", "byte")     # a stored member, a dynamic one, a tiny one
+GRID_LAST = 1000                           # bytes of grid_source's last block
+
+
+def grid_source(grid, block_bytes, seed=11):
+    """2 * grid + 3 blocks for a device that deflates `grid` blocks at a time, so that whoever took block k takes blocks
+    grid + k and 2 * grid + k behind it.  Blocks [0, grid) cycle through GRID_KINDS, seeded per block: no two are alike.
+    Block grid + k is a COPY of block (k + 1) % grid and block 2 * grid + k one of block (k + 2) % grid -- of the next kind
+    after the block in front of it in the same place of the grid, save where k + 1 or k + 2 wraps --, the last one cut to GRID_LAST bytes.
+    -> (bytes, kind of every block, twin: the block of [0, grid) every block holds the bytes of)"""
+    assert grid >= 3 and grid <= 256 and block_bytes > GRID_LAST
+    first = []
+    for k in range(grid):
+        kind = GRID_KINDS[k % 3]
+        if kind == "noise":
+            first.append(np.random.default_rng((seed, k)).integers(0, 256, block_bytes, dtype=np.uint8).tobytes())
+        elif kind == "text":
+            first.append(illumina_like(block_bytes // 300, seed=seed * 1000 + k)[:block_bytes])
+        else:
+            first.append(bytes([k]) * block_bytes)
+        assert len(first[-1]) == block_bytes
+    twin = list(range(grid)) + [(k + 1) % grid for k in range(grid)] + [(k + 2) % grid for k in range(3)]
+    blocks = [first[t] for t in twin]
+    blocks[-1] = blocks[-1][:GRID_LAST]
+    return b"".join(blocks), [GRID_KINDS[t % 3] for t in twin], twin
+
+
 def huffman_only_bytes(data, block_bytes):
     """What zlib's Z_HUFFMAN_ONLY makes of the same blocks as BGZF members: the raw streams plus 26 bytes each."""
     total = 0

@@ -216,6 +216,36 @@ def long_table(seed=3):
     return bytes(buf), tuple(tuple(r) for r in rows)
 
 
+@functools.lru_cache(maxsize=None)
+def grid_pool():
+    """(bytes, rows, idle, long): the pool of the tables above one pass of the grid (tests/grid_expect.py) -- every row of the
+    hand table, 260 of the seeded table's, empty and ineligible rows, the long table's long rows and two more just above LONG.
+    idle: the pool rows with nothing to do (empty or ineligible); long: those above LONG.  No sentinel, add 0."""
+    hbuf, hrows, names = hand_table()
+    assert names[-1] == "past the buffer"
+    buf, rows = bytearray(hbuf), [list(r) for r in hrows[:-1]]
+    idle = list(range(len(HAND), len(rows)))
+    sbuf, srows = seeded_table()
+    for i, r in enumerate(srows[:260]):
+        rows.append(record(buf, b"s%d" % i, sbuf[r[2]:r[3]]))
+    for i in range(8):
+        idle += [len(rows), len(rows) + 1]
+        rows.append(record(buf, b"e%d" % i, b""))
+        rows.append(record(buf, b"f%d" % i, b"ACGT" + b"G" * (12 + i))[:4] + [-1, -1])
+    lbuf, lrows = long_table()
+    rng = np.random.default_rng(19)
+    seqs = [lbuf[r[2]:r[3]] for r in lrows if r[3] - r[2] >= LONG]
+    seqs += [body_of(rng, 90) + b"G" * (LONG - 88), body_of(rng, LONG + 3)]
+    long = []
+    for i, s in enumerate(seqs):
+        if len(s) > LONG:
+            long.append(len(rows))
+        rows.append(record(buf, b"l%d" % i, s))
+    idle.append(len(rows))
+    rows.append([0, 1, len(buf) - 12, len(buf) + 1, 2, 15])        # past the buffer
+    return bytes(buf), tuple(tuple(r) for r in rows), tuple(idle), tuple(long)
+
+
 # ---- files: reads that end in adapter + G tail, bad ends, tails of other bases ---------------------------------------------------
 def one_read(rng, n, adapter):
     """(sequence, quality) of n bases; kinds: plain, a bad 3' end, the adapter at the end, the adapter followed by a G tail

@@ -6,10 +6,13 @@ package's own host implementation.  Bulk cases use a per-row numpy form of the s
 the plain loop on the hand vectors and on random reads.  Coordinates: a row minus `add` indexes the buffer the scanner saw;
 with a sentinel that buffer is b'\\n' + bytes.
 """
+import functools
 import io
 
 import numpy as np
 import pytest
+
+import grid_expect as GE
 
 from test_trim import loop_span, loop_rows as quality_loop_rows
 
@@ -480,6 +483,59 @@ def test_more_rows_than_one_pass_of_the_grid(gpu_ctx):
     assert rows.shape[0] > 2 * 2048 * 32 and len(buf) < 6 << 20
     want, stats = check_device(gpu_ctx, buf, rows)
     assert stats[0] > 10000 and stats[2] == 0
+
+
+# ---- more long rows than one pass of the long launch's grid (tests/grid_expect.py) ------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def long_list_table():
+    """(bytes, rows of the table, which of them are long, the long pool rows): 40 short reads, one of LONG bases and six above it
+    -- just above and up to 5000, the only hit in front of, across and far behind the threshold, or none --, drawn 9195 times
+    among as many short ones"""
+    rng = np.random.default_rng(46)
+    alpha = np.frombuffer(b"CGT", dtype=np.uint8)           # (no 'A': no place of such a read matches AGATCGGAAGAGC)
+    reads = random_reads(rng, 40, 100)
+    for n, p in ((LONG, LONG - 5), (LONG + 1, None), (LONG + 2, LONG - 3), (LONG + 3, 100), (3000, CHUNK_LONG * 5 - 5), (4000, None), (5000, 4995)):
+        s = alpha[rng.integers(0, 3, n)].copy()
+        if p is not None:
+            k = min(len(AD), n - p)
+            s[p:p + k] = np.frombuffer(AD, dtype=np.uint8)[:k]
+        reads.append(s.tobytes())
+    buf, rows = table_of(reads)
+    long = [i for i, s in enumerate(reads) if len(s) > LONG]
+    idx = GE.long_idx(long, [i for i in range(len(reads)) if i not in long], seed=47)
+    return buf, rows[idx], np.isin(idx, long), rows[long]
+
+
+def test_the_long_list_table_is_what_the_loop_says():
+    buf, table, is_long, long_rows = long_list_table()
+    n = long_rows[:, 3] - long_rows[:, 2]
+    assert len(n) == 6 and sorted(n)[:3] == [LONG + 1, LONG + 2, LONG + 3] and max(n) == 5000
+    assert int(is_long.sum()) == GE.N_LONG > 2 * 1024 * 4 and len(table) == 2 * GE.N_LONG >= 4096
+    want, stats = loop_rows(buf, table)
+    cut = (want[:, 3] - want[:, 2])[is_long]
+    full = (table[:, 3] - table[:, 2])[is_long]
+    assert (cut == full).sum() > 1000 and (cut < LONG).sum() > 1000 and ((cut > LONG) & (cut < full)).sum() > 1000
+    at = GE.sample_rows(len(table), GE.P_LONG)
+    assert len(at) >= 2000 and (loop_rows(buf, table[at], cut=loop_cut)[0] == want[at]).all()
+    order = np.flatnonzero(is_long)
+    assert len(GE.passes(len(order), GE.P_LONG)) == 3
+    for s in GE.passes(len(order), GE.P_LONG):
+        assert len({tuple(r) for r in table[order[s]].tolist()}) == 6
+
+
+@pytest.mark.gpu
+def test_more_long_rows_than_one_pass_of_the_grid(gpu_ctx):
+    """9195 rows above LONG among as many short ones: k_adapter_long's 1024 workgroups of four waves take three steps over the
+    list, the last for 1003 entries; out of place, in place, with a sentinel and add = 7"""
+    buf, table, is_long, _long_rows = long_list_table()
+    assert int(is_long.sum()) > 2 * 1024 * 4 and len(table) >= 4096
+    want, stats = loop_rows(buf, table)
+    for sentinel, add, in_place in ((0, 0, False), (0, 0, True), (1, 7, True)):
+        got, gstats = device_cut(gpu_ctx, buf, table + sentinel + add, sentinel=bool(sentinel), add=add, in_place=in_place)
+        what = "sentinel %d, add %d, in place %s" % (sentinel, add, in_place)
+        GE.same_rows(got[is_long], (want + sentinel + add)[is_long], GE.P_LONG, what + ": the long rows (list entries)")
+        GE.same_rows(got, want + sentinel + add, GE.P_SHORT, what)
+        assert gstats == stats, what
 
 
 @pytest.mark.gpu

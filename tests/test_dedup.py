@@ -4,13 +4,14 @@ a row minus `add` indexes the buffer the scanner saw; with a sentinel that buffe
 of a device allocation of whole pages and begins at a multiple of 16, so that a read past its end leaves the allocation and a
 sequence's address modulo 16 is what the table builder says it is."""
 import ctypes
+import functools
 
 import numpy as np
 import pytest
 
 import dedup_expect as X
+import grid_expect as GE
 
-pytestmark = pytest.mark.gpu
 
 GROUP_BYTES = 32        # bytes of a row that its 8 lanes take per round (csrc/ffq_dedup.h: SEQKEY_G * 4)
 TILE = 160              # bases above which a row goes onto the long list and gets a wave of its own (SEQKEY_TILE)
@@ -110,6 +111,7 @@ def lengths_table(gpu_ctx):
     dev.close()
 
 
+@pytest.mark.gpu
 def test_keys_at_every_length_and_alignment(lengths_table):
     dev, buf, rows = lengths_table
     want = check_keys(dev, buf, rows, ((0, 0), (1, 0), (0, 1000003), (1, -77)))
@@ -122,6 +124,7 @@ def test_keys_at_every_length_and_alignment(lengths_table):
     check_keys(dev, buf, rows[rng.integers(0, len(rows), 700)])
 
 
+@pytest.mark.gpu
 def test_keys_of_rows_the_rule_does_not_apply_to(gpu_ctx):
     rng = np.random.default_rng(23)
     buf, rows = bytearray(b"#"), []
@@ -166,6 +169,125 @@ def test_keys_of_rows_the_rule_does_not_apply_to(gpu_ctx):
         assert got == [X.KEY_NONE, X.loop_key(b""), X.loop_key(seen[1:5])] == [X.row_key(seen, r, True) for r in first]
         assert counts == (2, 1)
         assert dev.keys(np.zeros((0, 6), dtype=np.int64)) == ([], (0, 0))
+    finally:
+        dev.close()
+
+
+# ---- more rows than one pass of the grid (tests/grid_expect.py) -------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def keys_pool():
+    """(bytes, rows, idle, long, keys by the loop without and with a sentinel): a read of every length of LENGTHS at four
+    addresses modulo 16, reads just above TILE and of a few thousand bases, empty reads, and the rows without a key -- wrapped
+    (short and long), lines of two lengths, a FASTA row, rows that point outside"""
+    rng = np.random.default_rng(29)
+    buf, rows = bytearray(b"#"), []
+    for n in LENGTHS:
+        s = read_of(rng, n)
+        for a in (0, 5, 10, 15):
+            place(buf, rows, s, None, a)
+    for n in (TILE + 1, TILE + 2, TILE + 3, 1000, 3001, 5000):
+        place(buf, rows, read_of(rng, n), None, int(rng.integers(0, 16)))
+    idle = [i for i, r in enumerate(rows) if r[3] == r[2]]
+    good = [list(r) for r in rows]
+    for src in (good[4 * 30], good[-2]):                                       # a short row and a long one, wrapped
+        s = bytearray(buf[src[2]:src[3]])
+        s[len(s) // 2] = 10
+        idle.append(len(rows))
+        place(buf, rows, bytes(s), None, 7)
+    r = good[4 * 20]
+    n0 = len(rows)
+    rows.append(r[:5] + [r[5] - 1])
+    rows.append(r[:4] + [-1, -1])
+    rows.append([r[0], r[1], r[2], 1 << 40, r[4], r[4] + (1 << 40) - r[2]])
+    rows.append([r[0], r[1], r[3], r[2], r[4], r[4] + r[2] - r[3]])
+    rows.append([r[0], r[1], -5, -5 + r[3] - r[2], r[4], r[5]])
+    rows.append([-1] * 6)
+    idle += list(range(n0, len(rows)))
+    buf, rows = finish(buf, rows)
+    rows[n0 + 1, 4:] = -1                                                      # (finish moved them)
+    rows[n0 + 5] = -1
+    long = [i for i, r in enumerate(rows.tolist()) if i < n0 and r[3] - r[2] > TILE]
+    keys = []
+    for sentinel in (0, 1):
+        seen = (b"\n" if sentinel else b"") + buf
+        keys.append(np.array([X.row_key(seen, r, bool(sentinel)) for r in (rows + sentinel).tolist()], dtype=np.uint64))
+    return buf, rows, tuple(idle), tuple(long), keys
+
+
+def keys_table(arrangement, long_rows=False):
+    _buf, rows, idle, long, _keys = keys_pool()
+    if long_rows:
+        return GE.long_idx(long, [i for i in range(len(rows)) if i not in long], seed=47)
+    return GE.table_idx(arrangement, GE.n_above(GE.P_SHORT), GE.P_SHORT, len(rows), idle, seed=47)
+
+
+def check_keys_above(dev, idx, sentinel, add, P, what):
+    import torch
+    _buf, rows, _idle, _long, keys = keys_pool()
+    want = keys[sentinel][idx]
+    t = torch.from_numpy(rows[idx] + sentinel + add).cuda()
+    k = torch.full((len(idx) + 1,), -7, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    counts = dev.ctx.table_seq_keys(dev.ptr, dev.n, t.data_ptr(), len(idx), k.data_ptr(), sentinel=bool(sentinel), add=add)
+    got = k.cpu().numpy()
+    assert got[-1] == -7, "a key behind the last row was written"
+    GE.same_rows(got[:-1].view(np.uint64), want, P, what)
+    assert tuple(counts) == (int((want != X.KEY_NONE).sum()), int((want == X.KEY_NONE).sum())), what
+
+
+@pytest.mark.parametrize("long_rows", (False, True))
+def test_the_table_above_one_pass_is_what_the_loop_says(long_rows):
+    buf, rows, idle, long, keys = keys_pool()
+    lengths = rows[:, 3] - rows[:, 2]
+    assert len(rows) < 300 and len(buf) < 1 << 20 and len(long) >= 6 and sorted(lengths[list(long)])[:3] == [TILE + 1, TILE + 1, TILE + 1]
+    assert (keys[0][list(idle)] == X.KEY_NONE).sum() == 8 and (keys[1][list(idle)] == X.KEY_NONE).sum() == 7     # ([-1] * 6 + 1: an empty read)
+    P = GE.P_LONG if long_rows else GE.P_SHORT
+    for arrangement in ("random",) if long_rows else GE.ARRANGEMENTS:
+        idx = keys_table(arrangement, long_rows)
+        n = len(idx)
+        assert (n == 2 * GE.N_LONG and int(np.isin(idx, long).sum()) == GE.N_LONG > 2 * 1024 * 4 and n >= 4096) if long_rows else n > 2 * 2048 * 32
+        at = GE.sample_rows(n, P)
+        for sentinel in (0, 1):
+            seen = (b"\n" if sentinel else b"") + buf
+            want = [X.row_key(seen, r, bool(sentinel)) for r in (rows[idx[at]] + sentinel).tolist()]
+            assert len(at) >= 2000 and want == keys[sentinel][idx[at]].tolist()
+        order = np.flatnonzero(np.isin(idx, long)) if long_rows else np.arange(n)
+        for k, s in enumerate(GE.passes(len(order), P)):
+            part = idx[order[s]]
+            if (arrangement, k > 0) in (("late work", False), ("early work", True)):
+                assert set(part.tolist()) <= set(idle)
+            elif long_rows:
+                assert set(part.tolist()) == set(long)
+            else:
+                assert (keys[0][part] == X.KEY_NONE).any() and (lengths[part] == 0).any() and (lengths[part] > TILE).any() and \
+                    ((lengths[part] > 0) & (lengths[part] <= TILE)).any()
+
+
+@pytest.mark.gpu
+def test_more_rows_than_one_pass_of_the_grid(gpu_ctx):
+    """three steps of every workgroup of k_seqkey_rows, the last for 1001 of the 2048 with five rows for the last of those: every
+    key and both counts, in the three arrangements; "late work" with a sentinel and add = 1000003"""
+    buf = keys_pool()[0]
+    dev = Dev(gpu_ctx, buf)
+    try:
+        for arrangement in GE.ARRANGEMENTS:
+            sentinel, add = (1, 1000003) if arrangement == "late work" else (0, 0)
+            idx = keys_table(arrangement)
+            assert len(idx) > 2 * 2048 * 32
+            check_keys_above(dev, idx, sentinel, add, GE.P_SHORT, arrangement)
+    finally:
+        dev.close()
+
+
+@pytest.mark.gpu
+def test_more_long_rows_than_one_pass_of_the_grid(gpu_ctx):
+    """9195 rows above TILE among as many others: the long launch's 1024 workgroups take three steps over the list"""
+    buf, _rows, _idle, long, _keys = keys_pool()
+    dev = Dev(gpu_ctx, buf)
+    try:
+        idx = keys_table("random", long_rows=True)
+        assert int(np.isin(idx, long).sum()) > 2 * 1024 * 4 and len(idx) >= 4096
+        check_keys_above(dev, idx, 0, 0, GE.P_SHORT, "long rows among short ones")
     finally:
         dev.close()
 
@@ -240,6 +362,7 @@ def rand_keys(rng, n):
     return [int(x) | 1 for x in rng.integers(1, 1 << 63, n)]
 
 
+@pytest.mark.gpu
 @pytest.mark.parametrize("drop", (True, False))
 def test_first_copy_wins(fresh, drop):
     rng = np.random.default_rng(31)
@@ -261,6 +384,7 @@ def test_first_copy_wins(fresh, drop):
     assert check_call(dd, model, [], drop=drop)[:3] == [0, 0, 0]
 
 
+@pytest.mark.gpu
 @pytest.mark.parametrize("drop", (True, False))
 def test_contention_probing_and_wrap_around(fresh, drop):
     dd, model = fresh(70000)
@@ -279,6 +403,7 @@ def test_contention_probing_and_wrap_around(fresh, drop):
     assert check_call(dd, model, wrap[::-1] + chain[:50], drop=drop)[:2] == [50, 120]
 
 
+@pytest.mark.gpu
 @pytest.mark.parametrize("drop", (True, False))
 def test_growth_keeps_every_key_and_its_first_ordinal(fresh, drop):
     rng = np.random.default_rng(37)
@@ -299,6 +424,100 @@ def test_growth_keeps_every_key_and_its_first_ordinal(fresh, drop):
     assert gc[:4] == [0, len(everything), 0, 3 * 4096]
 
 
+# ---- more rows than one pass of the grid: the set ---------------------------------------------------------------------------------
+N_SET = GE.n_above(GE.P_WIDE)         # rows of either call: two steps of k_dedup_insert / k_dedup_resolve's 2048 workgroups of 256
+P_TABLE = 4096 * 256                  # slots k_dedup_clear / k_dedup_rehash take in one pass
+
+
+def np_pair_key(k1, k2):
+    """X.loop_pair_key over arrays (uint64 arithmetic wraps as the loop's masks do)"""
+    def sm(z):
+        z = z ^ (z >> np.uint64(30))
+        z = z * np.uint64(0xbf58476d1ce4e5b9)
+        z = z ^ (z >> np.uint64(27))
+        z = z * np.uint64(0x94d049bb133111eb)
+        return z ^ (z >> np.uint64(31))
+    with np.errstate(over="ignore"):
+        k = sm(sm(k1) + k2)
+    k[k == 0] = 1
+    k[(k1 == X.KEY_NONE) | (k2 == X.KEY_NONE)] = X.KEY_NONE
+    return k
+
+
+@functools.lru_cache(maxsize=None)
+def set_calls(pairs=False):
+    """[(keys 1, keys 2 or None)] of two calls of N_SET rows on a set made for no keys at all.  Call 1: 560 000 distinct keys,
+    copies of some of them, rows without a key -- the set grows from 1024 to 2^21 slots (k_dedup_clear strides).  Call 2: 200 000
+    new keys, 50 000 more that come twice in this call, copies of call 1's keys, rows without a key -- 2^21 to 2^22
+    (k_dedup_rehash strides over more than 2^20 slots).  Every call is shuffled, so every kind lies in every pass and a key's
+    second copy often belongs to a workgroup that runs before the one of its first."""
+    rng = np.random.default_rng(53)
+    n_none = 11095
+
+    def fresh_keys(m):
+        return rng.integers(1, 1 << 63, m, dtype=np.uint64) | np.uint64(1)
+    d1 = fresh_keys(560000)
+    call1 = np.concatenate([d1, d1[rng.integers(0, len(d1), N_SET - len(d1) - n_none)], np.zeros(n_none, dtype=np.uint64)])
+    new, twice = fresh_keys(200000), fresh_keys(50000)
+    call2 = np.concatenate([new, twice, twice, d1[rng.integers(0, len(d1), N_SET - 300000 - n_none)], np.zeros(n_none, dtype=np.uint64)])
+    out = []
+    for c in (call1, call2):
+        rng.shuffle(c)
+        assert len(c) == N_SET
+        # (pairs: mate 2's key is drawn from a few values, so that equal mate 1 keys make equal and unequal pairs)
+        out.append((c, (rng.integers(1, 4, N_SET).astype(np.uint64) * np.uint64(977)) if pairs else None))
+    return out
+
+
+def test_the_calls_above_one_pass_are_what_they_should_be():
+    assert N_SET == 601095 and N_SET > 2048 * 256 and (1 << 21) > P_TABLE
+    for pairs in (False, True):
+        model = X.LoopSet(0)
+        seen = set()
+        for c, (k1, k2) in enumerate(set_calls(pairs)):
+            eff = k1 if k2 is None else np_pair_key(k1, k2)
+            if k2 is not None:
+                at = GE.sample_rows(N_SET, GE.P_WIDE)
+                assert len(at) >= 2000 and [X.loop_pair_key(a, b) for a, b in zip(k1[at].tolist(), k2[at].tolist())] == eff[at].tolist()
+            kept, counts = model.select(eff.tolist(), True)
+            assert counts[4] == 1 << (21 + c) and counts[5] == c + 1 and counts[0] + counts[1] == N_SET
+            is_kept = np.zeros(N_SET, dtype=bool)
+            is_kept[kept] = True
+            for s in GE.passes(N_SET, GE.P_WIDE):                            # every kind in every pass
+                e = eff[s]
+                assert (e == X.KEY_NONE).sum() > 100 and (~is_kept[s]).sum() > 1000 and (is_kept[s] & (e != X.KEY_NONE)).sum() > 1000
+            if c == 1:
+                # a key of THIS call alone with two copies: the first in pass 1 and the second in pass 2 in an EARLIER workgroup's
+                # place; both in pass 2
+                fresh = ~np.isin(eff, np.fromiter(seen, dtype=np.uint64, count=len(seen))) & (eff != X.KEY_NONE)
+                order = np.argsort(eff[fresh], kind="stable")
+                pos, key = np.flatnonzero(fresh)[order], eff[fresh][order]
+                two = (key[:-1] == key[1:]) & np.concatenate([[True], key[1:-1] != key[:-2]])      # a key's first two copies
+                i, j = pos[:-1][two], pos[1:][two]
+                P = GE.P_WIDE
+                assert ((i < P) & (j >= P) & ((j - P) // 256 < i // 256)).sum() > 100 and ((i >= P) & (j > i)).sum() > 100
+                assert (~is_kept[j]).all() and is_kept[i].all()
+            seen.update(eff.tolist())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("drop,pairs", ((True, False), (False, False), (True, True)))
+def test_more_rows_than_one_pass_of_the_grid_in_the_set(fresh, drop, pairs):
+    """two calls of 601 095 rows on a set made for no keys: two steps of the insert and the resolve, the clear striding over
+    2^21 slots and the rehash over 2^21 old ones; kept rows, d_idx and all six counts against the dict"""
+    dd, model = fresh(0)
+    for c, (k1, k2) in enumerate(set_calls(pairs)):
+        eff = k1 if k2 is None else np_pair_key(k1, k2)
+        kept, counts = model.select(eff.tolist(), drop)
+        idx, got, gc, tabs, k = dev_select(dd, k1, k2, None, 2 if pairs else 1, drop)
+        assert gc == counts, (c, gc, counts)
+        assert gc[4] == 1 << (21 + c) and gc[5] == c + 1 and k == len(kept)
+        GE.same_kept(idx, kept, GE.P_WIDE, "call %d" % (c + 1))
+        for t, g in zip(tabs, got):
+            GE.same_rows(g, t[kept], GE.P_WIDE, "call %d: the kept rows (row: among the kept)" % (c + 1))
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("drop", (True, False))
 def test_rows_without_a_key_and_pair_keys(fresh, drop):
     rng = np.random.default_rng(41)
@@ -320,6 +539,7 @@ def test_rows_without_a_key_and_pair_keys(fresh, drop):
     assert gc[3] <= 3 + 144
 
 
+@pytest.mark.gpu
 def test_a_cap_that_is_too_small_and_bad_arguments(gpu_ctx, fresh):
     import torch
     from fastqandfurious_amd import hip

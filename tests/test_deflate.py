@@ -2,7 +2,8 @@
 
 The judge is zlib (tests/deflate_expect.py: no package code): gzip.decompress gives the input back, and every member is
 walked by its BSIZE -- header bytes, size, a raw deflate stream that ends where the member says, CRC-32, ISIZE.  S is the
-segment a match may not leave, R the positions of a round, B the bytes of a member: all three read from the binding.
+segment a match may not leave, R the positions of a round, B the bytes of a member, G the blocks deflated at a time: all
+read from the binding.
 """
 import gzip
 
@@ -11,7 +12,6 @@ import pytest
 
 import deflate_expect as E
 
-pytestmark = pytest.mark.gpu
 GUARD = 0xEE
 PHRASE = bytes(range(32, 132))               # 100 bytes no four of which come twice
 
@@ -71,7 +71,7 @@ def deflate(ctx, src, misalign_src=0, misalign_out=3, cap=None):
 
 
 def check_case(ctx, src, want_stored=None, from_isize=0, **kw):
-    """want_stored: what every member of from_isize bytes or more must be"""
+    """want_stored: what every member of from_isize bytes or more must be -- one answer for all, or one per member"""
     from fastqandfurious_amd import hip
     B = hip.BGZF_BLOCK_BYTES
     n = len(src)
@@ -86,7 +86,10 @@ def check_case(ctx, src, want_stored=None, from_isize=0, **kw):
     assert off == [m[0] for m in members] + [len(out)]
     assert all(m[1] <= m[2] + 31 for m in members) and len(out) <= hip.deflate_bgzf_bound(n)
     if want_stored is not None:
-        assert all(m[3] == want_stored for m in members if m[2] >= from_isize), [m[2:] for m in members]
+        want = list(want_stored) if isinstance(want_stored, (list, tuple)) else [want_stored] * len(members)
+        assert len(want) == len(members)
+        bad = [(i, m[2:]) for i, (m, w) in enumerate(zip(members, want)) if m[2] >= from_isize and m[3] != w]
+        assert not bad, bad[:8]
     # the same bytes on a second call
     rc2, stats2, out2, off2, _u = deflate(ctx, src, **kw)
     assert (rc2, stats2, off2) == (rc, stats, off) and out2 == out
@@ -98,6 +101,7 @@ def check_case(ctx, src, want_stored=None, from_isize=0, **kw):
     return out, members
 
 
+@pytest.mark.gpu
 @pytest.mark.parametrize("n", sizes())
 def test_one_byte_repeated(gpu_ctx, n):
     """a chain of matches of length 258 at distance 1: one distance symbol, a code of length 1"""
@@ -107,12 +111,14 @@ def test_one_byte_repeated(gpu_ctx, n):
         assert members[0][1] < 1000, members[0]        # 255 segments of (a literal, a 255-byte match)
 
 
+@pytest.mark.gpu
 @pytest.mark.parametrize("n", sizes())
 def test_two_bytes_alternating(gpu_ctx, n):
     # (from 256 bytes: all code lengths are 0, 1 or 2, so the header is under 75 bytes and the literals under 2 bits each)
     out, members = check_case(gpu_ctx, (b"AC" * (n // 2 + 1))[:n], want_stored=False, from_isize=256)
 
 
+@pytest.mark.gpu
 @pytest.mark.parametrize("n", sizes())
 def test_noise_is_stored(gpu_ctx, n):
     S, _R, B = consts()
@@ -123,11 +129,13 @@ def test_noise_is_stored(gpu_ctx, n):
     assert len(out) == n + 31 * len(members)
 
 
+@pytest.mark.gpu
 def test_fibonacci_counts(gpu_ctx):
     """counts whose Huffman code is deeper than deflate's 15 bits: the lengths are cut to the limit"""
     check_case(gpu_ctx, fibonacci_bytes(), want_stored=False)
 
 
+@pytest.mark.gpu
 def test_a_repeat_farther_than_a_distance_reaches(gpu_ctx):
     """65280 bytes offer candidates up to 65279 back; deflate's distances end at 32768"""
     _S, _R, B = consts()
@@ -141,6 +149,7 @@ def test_a_repeat_farther_than_a_distance_reaches(gpu_ctx):
     assert len(edge) + 40 < len(past) and len(edge) + 40 < len(far), (len(edge), len(past), len(far))
 
 
+@pytest.mark.gpu
 def test_repeats_across_a_round_and_a_segment(gpu_ctx):
     S, R, _B = consts()
     check_case(gpu_ctx, phrase_twice(8 * R, R - 50, 2 * R))
@@ -149,6 +158,7 @@ def test_repeats_across_a_round_and_a_segment(gpu_ctx):
     check_case(gpu_ctx, phrase_twice(8 * R, 3 * S - 50, 2 * R + 17, quiet=True), want_stored=False)
 
 
+@pytest.mark.gpu
 @pytest.mark.parametrize("kind", ("synth.single", "illumina-like"))
 def test_fastq_text(gpu_ctx, kind):
     """20000 records: no member stored, and the whole within 2 % of what zlib's Huffman-only coding gives for the same
@@ -165,6 +175,57 @@ def test_fastq_text(gpu_ctx, kind):
     assert len(out) <= 1.02 * huff, (len(out), huff)
 
 
+def grid_consts():
+    from fastqandfurious_amd import hip
+    return hip.DEFLATE_GRID_BLOCKS, hip.BGZF_BLOCK_BYTES
+
+
+def test_the_grid_source_is_what_it_says():
+    """zlib's own compression of every block alone stores the noise blocks and no others; copies are copies"""
+    import zlib
+    G, B = grid_consts()
+    src, kinds, twin = E.grid_source(G, B)
+    n = len(kinds)
+    assert n == len(twin) == 2 * G + 3 and n > 2 * G and len(src) == (n - 1) * B + E.GRID_LAST
+    blocks = [src[a:a + B] for a in range(0, len(src), B)]
+    assert len(set(blocks[:G])) == G                                       # no two alike
+    for k in range(G):
+        assert blocks[G + k] == blocks[(k + 1) % G] and twin[G + k] == (k + 1) % G
+    assert blocks[2 * G] == blocks[2] and blocks[2 * G + 1] == blocks[3] and blocks[2 * G + 2] == blocks[4][:E.GRID_LAST]
+    for p in range(0, n, G):                                               # every kind in every pass of the grid
+        assert set(kinds[p:p + G]) == set(E.GRID_KINDS)
+    assert kinds[-1] == "text"
+    for k in list(range(G)) + [n - 1]:
+        c = zlib.compressobj(1, zlib.DEFLATED, -15)
+        raw = c.compress(blocks[k]) + c.flush()
+        stored = (raw[0] & 6) == 0
+        assert stored == (kinds[k] == "noise"), (k, kinds[k], len(raw))
+        assert stored or len(raw) < len(blocks[k]) // 2, (k, kinds[k], len(raw))
+
+
+@pytest.mark.gpu
+def test_more_blocks_than_one_pass_of_the_grid(gpu_ctx):
+    """2 * G + 3 blocks under a grid of G workgroups: the workgroup of block k takes blocks G + k and 2 * G + k behind it,
+    on the LDS and the scratch it used before.  Members do not depend on one another and the call is deterministic, so the
+    member of a copied block IS the member of the block it copies, byte for byte -- which the round trip cannot see: stale
+    counts give a legal stream under another code."""
+    from fastqandfurious_amd import hip
+    G, B = grid_consts()
+    src, kinds, twin = E.grid_source(G, B)
+    n = len(kinds)
+    assert n == 2 * G + 3 and n > 2 * G and len(src) == (n - 1) * B + E.GRID_LAST
+    out, members = check_case(gpu_ctx, src, want_stored=[k == "noise" for k in kinds])
+    assert len(members) == n and sum(m[3] for m in members) == kinds.count("noise")      # (stats[3]: check_case)
+    blob = [out[m[0]:m[0] + m[1]] for m in members]
+    for i in range(G, n - 1):
+        assert blob[i] == blob[twin[i]], "block %d (pass %d of its workgroup, %s behind %s) is not the member of block %d" % (
+            i, i // G, kinds[i], kinds[i - G], twin[i])
+    rc, stats, alone, _off, untouched = deflate(gpu_ctx, src[(n - 1) * B:])
+    assert rc == hip.OK and untouched and stats[2] == 1
+    assert blob[n - 1] == alone, "the short last block (%s behind %s)" % (kinds[n - 1], kinds[n - 1 - G])
+
+
+@pytest.mark.gpu
 def test_arguments(gpu_ctx):
     import torch
     from fastqandfurious_amd import hip

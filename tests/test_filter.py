@@ -8,8 +8,12 @@ buffer the scanner saw; with a sentinel that buffer is b'\\n' + bytes.
 A miscounted quantity shows only where a verdict hangs on it, so the reads of the length and boundary tests are MADE to sit
 on a rule's edge: one variant that the rule just keeps and one that it just drops.
 """
+import functools
+
 import numpy as np
 import pytest
+
+import grid_expect as GE
 
 GROUP_BYTES = 32        # bytes of a row that its 8 lanes take per round (csrc/ffq_filter.h: FILTER_G * 4)
 TILE = 160              # bases above which a row gets a wave of its own (FILTER_TILE)
@@ -527,12 +531,13 @@ def test_compaction(gpu_ctx):
         dev.close()
 
 
-@pytest.mark.gpu
-def test_bulk(gpu_ctx):
-    """20 000 random rows, lengths 0..600, mixed eligibility, all six rules on: a long list of some thousands of rows"""
-    rng = np.random.default_rng(77)
+BULK_RULES = rules(max_n=30, min_mean_qual=17, qualified_qual=15, max_unqualified_pct=40, max_ee_micro=12 * 10 ** 6, min_complexity_pct=30)
+
+
+def bulk_pool(rng, n_reads=400):
+    """(bytes, rows): reads of 0..600 bases of four kinds at every alignment, the ineligible rows after every fortieth"""
     buf, rows = bytearray(b"#"), []
-    for k in range(400):
+    for k in range(n_reads):
         n = int(rng.integers(0, 601))
         kind = int(rng.integers(0, 4))
         s, qq = one_read(rng, n, alphabet=b"ACGTN" if kind == 0 else b"AAAAAAAC" if kind == 1 else b"ACGT",
@@ -540,9 +545,16 @@ def test_bulk(gpu_ctx):
         record(buf, rows, s, qq, k % 4, (k // 4) % 4)
         if k % 40 == 7:
             ineligible_rows(buf, rows)
-    buf, rows = bytes(buf), np.array(rows, dtype=np.int64)
+    return bytes(buf), np.array(rows, dtype=np.int64)
+
+
+@pytest.mark.gpu
+def test_bulk(gpu_ctx):
+    """20 000 random rows, lengths 0..600, mixed eligibility, all six rules on: a long list of some thousands of rows"""
+    rng = np.random.default_rng(77)
+    buf, rows = bulk_pool(rng)
     table = rows[rng.integers(0, len(rows), 20000)]
-    R = rules(max_n=30, min_mean_qual=17, qualified_qual=15, max_unqualified_pct=40, max_ee_micro=12 * 10 ** 6, min_complexity_pct=30)
+    R = BULK_RULES
     assert loop_select(buf, rows[::9], R, 20, 580, verdict=np_verdict) == loop_select(buf, rows[::9], R, 20, 580)
     memo = {}
 
@@ -557,6 +569,93 @@ def test_bulk(gpu_ctx):
     try:
         check(dev, buf, table, R, lo=20, hi=580, want=want)
         check(dev, buf, table[::-1], R, lo=20, hi=580, verdict=once)
+    finally:
+        dev.close()
+
+
+# ---- more rows than one pass of the grid (tests/grid_expect.py) -------------------------------------------------------------
+GRID_BOUNDS = (20, 580)
+
+
+@functools.lru_cache(maxsize=None)
+def grid_pool():
+    """the bulk pool's kind; empty reads and reads at and one above the long rows' threshold; the ineligible rows once more at
+    the very end, where "past the buffer" is past the buffer"""
+    rng = np.random.default_rng(78)
+    buf, rows = bulk_pool(rng, 300)
+    buf, rows = bytearray(buf), rows.tolist()
+    for n in (0, 0, 1, TILE, TILE, TILE + 1, TILE + 1):
+        record(buf, rows, *one_read(rng, n, alphabet=b"ACGT", qlo=50, qhi=75))
+    ineligible_rows(buf, rows)
+    return bytes(buf), np.array(rows, dtype=np.int64)
+
+
+@functools.lru_cache(maxsize=None)
+def grid_parts(sentinel):
+    """the loop's answer for every pool row ALONE: (verdict, 1 if a content rule is on and the row is not judged)"""
+    buf, rows = grid_pool()
+    seen = (b"\n" if sentinel else b"") + buf
+    per = [loop_select(seen, r + sentinel, BULK_RULES, *GRID_BOUNDS, 0, bool(sentinel)) for r in rows]
+    return np.array([v[0] for _k, _c, v in per]), np.array([c[NJ] for _k, c, _v in per])
+
+
+def grid_idle(sentinel=0):
+    """pool rows with nothing to do: not judged, or dropped by their length (no byte of them is read)"""
+    verdict, nj = grid_parts(sentinel)
+    return np.flatnonzero((verdict == 1) | (nj == 1))
+
+
+def grid_want(idx, sentinel):
+    """(kept ordinals, the eight counts) of a call over pool[idx]"""
+    verdict, nj = grid_parts(sentinel)
+    v = verdict[idx]
+    return np.flatnonzero(v == 0), np.bincount(v, minlength=7).tolist()[:7] + [int(nj[idx].sum())]
+
+
+@pytest.mark.parametrize("arrangement", GE.ARRANGEMENTS)
+def test_the_table_above_one_pass_is_what_the_loop_says(arrangement):
+    buf, rows = grid_pool()
+    n, P = GE.n_above(GE.P_SHORT), GE.P_SHORT
+    assert n > 2 * 2048 * 32 and len(rows) < 500 and len(buf) < 1 << 20
+    lengths = rows[:, 3] - rows[:, 2]
+    for sentinel in (0, 1):
+        idx = GE.table_idx(arrangement, n, P, len(rows), grid_idle(), seed=9)
+        kept, counts = grid_want(idx, sentinel)
+        at = GE.sample_rows(n, P)
+        seen = (b"\n" if sentinel else b"") + buf
+        assert len(at) >= 2000 and tuple(loop_select(seen, rows[idx[at]] + sentinel, BULK_RULES, *GRID_BOUNDS, 0, bool(sentinel))[:2]) == \
+            (grid_want(idx[at], sentinel)[0].tolist(), grid_want(idx[at], sentinel)[1])
+        assert sum(counts[:7]) == n and counts[0] == len(kept)
+        for k, s in enumerate(GE.passes(n, P)):
+            c = grid_want(idx[s], sentinel)[1]
+            if (arrangement, k > 0) in (("late work", False), ("early work", True)):
+                assert c[2:7] == [0] * 5 and c[1] > 0 and c[NJ] > 0, (k, c)
+            else:
+                # every verdict, rows that are not judged, empty reads, reads on both sides of the long rows' threshold
+                assert all(x > 0 for x in c), (k, c)
+                here = lengths[idx[s]]
+                assert (here == 0).any() and ((here > 0) & (here <= TILE)).any() and (here > TILE).any()
+
+
+@pytest.mark.gpu
+def test_more_rows_than_one_pass_of_the_grid(gpu_ctx):
+    """three steps of every workgroup of k_filter_rows, the last for 1001 of the 2048 with five rows for the last of those (and a
+    long list of some hundred thousand rows): the kept rows, d_idx and the eight counts, in the three arrangements; "late
+    work" with a sentinel and add = 500"""
+    buf, rows = grid_pool()
+    n, P = GE.n_above(GE.P_SHORT), GE.P_SHORT
+    assert n > 2 * 2048 * 32
+    dev = Dev(gpu_ctx, buf)
+    try:
+        for arrangement in GE.ARRANGEMENTS:
+            sentinel, add = (1, 500) if arrangement == "late work" else (0, 0)
+            idx = GE.table_idx(arrangement, n, P, len(rows), grid_idle(), seed=9)
+            kept, counts = grid_want(idx, sentinel)
+            moved = rows[idx] + sentinel + add
+            got, gi, gc = dev.select(moved, BULK_RULES, *GRID_BOUNDS, bool(sentinel), add)
+            GE.same_kept(gi, kept, P, arrangement)
+            assert gc == counts, (arrangement, gc, counts)
+            GE.same_rows(got, moved[kept], P, "%s: the kept rows (row: among the kept)" % arrangement)
     finally:
         dev.close()
 

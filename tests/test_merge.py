@@ -11,11 +11,11 @@ import functools
 import numpy as np
 import pytest
 
+import grid_expect as GE
 import merge_expect as M
 import overlap_expect as X
 from test_overlap import Dev
 
-pytestmark = pytest.mark.gpu
 
 ADD1, ADD2 = 1000, -5                 # mate 1: sentinel, add 1000; mate 2: no sentinel, add -5
 SIZES = (0, 1, 2, 31, 32, 33, 257)    # group and workgroup edges: 8 lanes per pair, 32 pairs per step, 256 per workgroup
@@ -147,24 +147,17 @@ def build(pairs):
     return bytes(b1), r1, bytes(b2), r2
 
 
-class Table:
-    """both mates on the device, the insert sizes, and the loop's verdict per pair (computed once)"""
+class HostTable:
+    """both mates' bytes and rows, the insert sizes, and the loop's verdict per pair (computed once)"""
 
-    def __init__(self, ctx, pairs):
-        import torch
-        from fastqandfurious_amd import hip
+    def __init__(self, pairs):
         self.pairs, self.n = pairs, len(pairs)
         b1, r1, b2, r2 = build(pairs)
+        self.bytes = (b1, b2)
         self.seen = (b"\n" + b1, b2)
         self.coord = (r1, r2)
         self.m = (np.array(r1, dtype=np.int64) + ADD1, np.array(r2, dtype=np.int64) + ADD2)
         self.ins = np.array([p["ins"] for p in pairs], dtype=np.int32)
-        self.d = (Dev(ctx, b1), Dev(ctx, b2))
-        self.t = tuple(torch.from_numpy(m.copy()).cuda() for m in self.m)
-        self.dins = torch.from_numpy(self.ins.copy()).cuda()
-        torch.cuda.synchronize()
-        self.v = (hip.table_view(self.d[0].ptr, self.d[0].n, self.t[0].data_ptr(), True, ADD1),
-                  hip.table_view(self.d[1].ptr, self.d[1].n, self.t[1].data_ptr(), False, ADD2))
 
     @functools.lru_cache(maxsize=None)
     def per_pair(self):
@@ -172,6 +165,21 @@ class Table:
 
     def expect(self, n, ords=None):
         return M.summarize(self.per_pair()[:n], self.m[0][:n], self.m[1][:n], np.arange(n) if ords is None else ords)
+
+
+class Table(HostTable):
+    """... and both mates on the device"""
+
+    def __init__(self, ctx, pairs):
+        import torch
+        from fastqandfurious_amd import hip
+        HostTable.__init__(self, pairs)
+        self.d = (Dev(ctx, self.bytes[0]), Dev(ctx, self.bytes[1]))
+        self.t = tuple(torch.from_numpy(m.copy()).cuda() for m in self.m)
+        self.dins = torch.from_numpy(self.ins.copy()).cuda()
+        torch.cuda.synchronize()
+        self.v = (hip.table_view(self.d[0].ptr, self.d[0].n, self.t[0].data_ptr(), True, ADD1),
+                  hip.table_view(self.d[1].ptr, self.d[1].n, self.t[1].data_ptr(), False, ADD2))
 
     def close(self):
         for d in self.d:
@@ -229,6 +237,7 @@ def hand(gpu_ctx):
     T.close()
 
 
+@pytest.mark.gpu
 def test_the_hand_table_holds_every_kind(hand):
     """what the tests below rely on, said by the loop itself"""
     per = hand.per_pair()
@@ -266,11 +275,13 @@ def test_the_hand_table_holds_every_kind(hand):
     assert {len(hand.pairs[k]["a"]) for k in merged} >= set(LENS) <= {len(hand.pairs[k]["b"]) for k in merged}
 
 
+@pytest.mark.gpu
 @pytest.mark.parametrize("n", SIZES)
 def test_pair_counts(gpu_ctx, hand, n):
     same(run(gpu_ctx, hand, n), hand.expect(n), n)
 
 
+@pytest.mark.gpu
 def test_whole_table(gpu_ctx, hand):
     want = hand.expect(hand.n)
     same(run(gpu_ctx, hand, hand.n), want, hand.n)
@@ -280,6 +291,7 @@ def test_whole_table(gpu_ctx, hand):
     same(run(gpu_ctx, hand, hand.n, cap=want[5][2], slack=0), want, hand.n)
 
 
+@pytest.mark.gpu
 def test_text_one_byte_short(gpu_ctx, hand):
     """FFQ_E_TABLE_FULL: counts[2] is the need, the offsets and the rest tables are written, the text is not touched"""
     from fastqandfurious_amd import hip
@@ -290,6 +302,134 @@ def test_text_one_byte_short(gpu_ctx, hand):
         same(got, want, n, written=False)
 
 
+# ---- more pairs than one pass of the grid (tests/grid_expect.py) -------------------------------------------------------------
+SHORT_LENS = (1, 2, 15, 16, 17, 31, 32, 33)
+
+
+@functools.lru_cache(maxsize=None)
+def grid_pairs():
+    """a pool of short pairs, so that 601 095 of them merge into less than 64 MiB: every length of SHORT_LENS with every other in
+    every alignment, a few pairs of 150 bases, pairs that must not merge of every flavour, empty pairs"""
+    rng = np.random.default_rng(29)
+    pairs = [pair(rng, 33, 33, -7)]
+    k = 0
+    for n1 in SHORT_LENS:
+        for n2 in SHORT_LENS:
+            for o in alignments(n1, n2):
+                qm = (("band", "band"), ("tie", "tie"), ("low", "high"), ("high", "low"), ("wide", "wide"), ("band", "wide"))[k % 6]
+                pairs.append(pair(rng, n1, n2, o, h=b"h" * (1 + k % 17), qm=qm, alphabet=(b"ACGT", b"ACGTacgt", b"ACGTN.", b"acgtn")[k % 4]))
+                k += 1
+    pairs += [pair(rng, 150, 150 - i, 3 * i - 20) for i in range(10)]
+    pairs += [pair(rng, 33, 33, ins=-1), pair(rng, 33, 33, ins=-2), pair(rng, 33, 33, ins=0), pair(rng, 33, 31, ins=64), pair(rng, 33, 31, ins=65),
+              pair(rng, 33, 33, ins=-(1 << 31)), pair(rng, 33, 33, ins=(1 << 31) - 1), pair(rng, 513, 33, -10, flavour="long")]
+    pairs += [pair(rng, 40, 40, -5, flavour=f) for f in ("fasta1", "fasta2", "outside1", "outside2", "negative1", "negative2", "unequal1",
+                                                          "unequal2", "coord0", "header_neg", "header_empty", "header_out")]
+    pairs += [dict(h=b"e", a=b"", qa=b"", b=b"", qb=b"", ins=-1, flavour="")] * 4
+    pairs.append(pair(rng, 33, 33, -7))
+    return pairs
+
+
+@functools.lru_cache(maxsize=None)
+def grid_host():
+    return HostTable(grid_pairs())
+
+
+def grid_idx(H, arrangement):
+    idle = [i for i, m in enumerate(H.per_pair()) if m is None]
+    return GE.table_idx(arrangement, GE.n_above(GE.P_WIDE), GE.P_WIDE, H.n, idle, seed=83)
+
+
+def grid_want(H, idx):
+    """M.summarize's answer for pool[idx] with the identity for d_ord"""
+    per = H.per_pair()
+    texts = [m[0] if m is not None else b"" for m in per]
+    nums = np.array([[1, 0, len(m[0]), m[1], m[2], m[3]] if m is not None else [0, 1, 0, 0, 0, 0] for m in per], dtype=np.int64)
+    off = np.concatenate([[0], np.cumsum(nums[idx, 2])])
+    keep = np.flatnonzero(nums[idx, 1] == 1)
+    return b"".join([texts[i] for i in idx.tolist()]), off, H.m[0][idx][keep], H.m[1][idx][keep], keep, nums[idx].sum(axis=0).tolist()
+
+
+class Expanded:
+    """pool[idx] as run() takes it: the pool's buffers on the device, tables and insert sizes of its own"""
+
+    def __init__(self, T, idx, want):
+        import torch
+        self.t = (torch.from_numpy(T.m[0][idx]).cuda(), torch.from_numpy(T.m[1][idx]).cuda())
+        self.dins = torch.from_numpy(T.ins[idx]).cuda()
+        torch.cuda.synchronize()
+        self.v = tuple(type(x)(x.d_buf, x.n_bytes, x.sentinel, x.add, t.data_ptr()) for x, t in zip(T.v, self.t))
+        self.want = want
+
+    def expect(self, n):
+        return self.want
+
+
+def same_above(got, want, n, P, what, written=True):
+    rc, text, doff, o1, o2, ro, n_rest, counts = got
+    wtext, woff, w1, w2, word, wcounts = want
+    GE.same_rows(doff[:n + 1], woff, P, what + ": offsets")
+    k = wcounts[1]
+    GE.same_kept(ro[:n_rest], word, P, what + ": the pairs that are not merged")
+    GE.same_rows(o1[:k], w1, P, what + ": mate 1's rest (row: among the rest)")
+    GE.same_rows(o2[:k], w2, P, what + ": mate 2's rest (row: among the rest)")
+    if written:
+        bad = np.flatnonzero(text[3:3 + len(wtext)] != np.frombuffer(wtext, dtype=np.uint8))
+        if bad.size:
+            r = int(np.searchsorted(woff, bad[0], side="right") - 1)
+            raise AssertionError("%s: first difference at text byte %d: pair %d, pass %d" % (what, bad[0], r, r // P))
+    same(got, want, n, written=written)
+
+
+@pytest.mark.parametrize("arrangement", GE.ARRANGEMENTS)
+def test_the_pairs_above_one_pass_are_what_the_loop_says(arrangement):
+    H = grid_host()
+    n, P = GE.n_above(GE.P_WIDE), GE.P_WIDE
+    assert n > 2048 * 256 and H.n < 400
+    idx = grid_idx(H, arrangement)
+    want = grid_want(H, idx)
+    assert len(want[0]) == want[5][2] < 64 << 20 and want[5][0] + want[5][1] == n
+    at = GE.sample_rows(n, P)
+    j = idx[at]
+    per = [M.merged_text(H.seen[0], H.coord[0][k], True, H.seen[1], H.coord[1][k], False, int(H.ins[k])) for k in j.tolist()]
+    loop, mine = M.summarize(per, H.m[0][j], H.m[1][j], np.arange(len(j))), grid_want(H, j)
+    assert len(at) >= 2000 and loop[0] == mine[0] and loop[5] == mine[5] and all((a == b).all() for a, b in zip(loop[1:5], mine[1:5]))
+    flavours = {p["flavour"] for p in H.pairs}
+    for k, s in enumerate(GE.passes(n, P)):
+        c = grid_want(H, idx[s])[5]
+        here = {H.pairs[i]["flavour"] for i in set(idx[s].tolist())}
+        if (arrangement, k > 0) in (("late work", False), ("early work", True)):
+            assert c[0] == 0 and c[2:] == [0] * 4 and c[1] == s.stop - s.start
+        else:
+            assert all(x > 0 for x in c) and here == flavours and len(flavours) == 14, (k, c)
+            lens = {(len(H.pairs[i]["a"]), len(H.pairs[i]["b"])) for i in set(idx[s].tolist())}
+            assert {(0, 0), (1, 1), (33, 1), (1, 33), (150, 150)} <= lens
+
+
+@pytest.mark.gpu
+def test_more_pairs_than_one_pass_of_the_grid(gpu_ctx):
+    """two steps of every workgroup of k_merge_sum and the kernels behind it, the second for 301 of the 2048 with seven pairs for
+    the last of those: every byte of the text, every offset, both rest tables, the rest ordinals and the six counts; and a text
+    one byte short: the need reported, nothing written, the offsets and the rest all the same"""
+    from fastqandfurious_amd import hip
+    H = grid_host()
+    T = Table(gpu_ctx, H.pairs)
+    try:
+        for arrangement in GE.ARRANGEMENTS:
+            idx = grid_idx(H, arrangement)
+            n = len(idx)
+            assert n > 2048 * 256
+            want = grid_want(H, idx)
+            E = Expanded(T, idx, want)
+            same_above(run(gpu_ctx, E, n), want, n, GE.P_WIDE, arrangement)
+            if arrangement == "random":
+                got = run(gpu_ctx, E, n, cap=want[5][2] - 1)
+                assert got[0] == hip.E_TABLE_FULL
+                same_above(got, want, n, GE.P_WIDE, arrangement + ", one byte short", written=False)
+    finally:
+        T.close()
+
+
+@pytest.mark.gpu
 def test_ordinals_into_a_larger_insert_array(gpu_ctx, hand):
     """d_ord: a non-monotone map; pair k's insert size is d_insert[d_ord[k]], and d_rest_ord holds d_ord[k]"""
     import torch
@@ -305,6 +445,7 @@ def test_ordinals_into_a_larger_insert_array(gpu_ctx, hand):
     same(run(gpu_ctx, hand, 33, dins=dins, dord=dord), hand.expect(33, ords[:33]), 33)
 
 
+@pytest.mark.gpu
 def test_trim_or_not_the_text_is_the_same(gpu_ctx):
     """ffq_table_pair_overlap with trim 1 and with trim 0, each followed by the merge with the insert sizes it wrote: o is
     taken against the current length of mate 2, so the cut changes nothing"""
@@ -348,6 +489,7 @@ def test_trim_or_not_the_text_is_the_same(gpu_ctx):
         T.close()
 
 
+@pytest.mark.gpu
 def test_argument_errors(gpu_ctx, hand):
     import ctypes
     import torch

@@ -10,9 +10,9 @@ import functools
 import numpy as np
 import pytest
 
+import grid_expect as GE
 import overlap_expect as X
 
-pytestmark = pytest.mark.gpu
 
 ADD1, ADD2 = 1000, -5                 # mate 1: sentinel, add 1000; mate 2: no sentinel, add -5
 SIZES = (0, 1, 2, 31, 32, 33, 257)    # group and workgroup edges for 8 lanes per pair, 32 pairs per workgroup
@@ -109,25 +109,19 @@ def build_mate(pairs, k, first, last):
     return bytes(buf), rows
 
 
-class Table:
-    """both mates on the device, and the loop's verdict per pair and rule set (computed when first asked for)"""
+class HostTable:
+    """both mates' bytes and rows, and the loop's verdict per pair and rule set (computed when first asked for)"""
 
-    def __init__(self, ctx, pairs, first, last):
-        import torch
-        from fastqandfurious_amd import hip
+    def __init__(self, pairs, first, last):
         self.pairs = pairs
         b1, r1 = build_mate(pairs, 0, first[0], last[0])
         b2, r2 = build_mate(pairs, 1, first[1], last[1])
+        self.bytes = (b1, b2)
         # coordinates of the buffer as the scanner saw it: mate 1 has its sentinel in front
         self.seen = (b"\n" + b1, b2)
         c1 = [[None if x is None else x + 1 for x in r] for r in r1]
         self.coord = ([[-1 - ADD1 if x is None else x for x in r] for r in c1], [[-100 - ADD2 if x is None else x for x in r] for r in r2])
         self.m = (np.array(self.coord[0], dtype=np.int64) + ADD1, np.array(self.coord[1], dtype=np.int64) + ADD2)
-        self.d = (Dev(ctx, b1), Dev(ctx, b2))
-        self.t = tuple(torch.from_numpy(m.copy()).cuda() for m in self.m)
-        torch.cuda.synchronize()
-        self.v = (hip.table_view(self.d[0].ptr, self.d[0].n, self.t[0].data_ptr(), True, ADD1),
-                  hip.table_view(self.d[1].ptr, self.d[1].n, self.t[1].data_ptr(), False, ADD2))
         self.n = len(pairs)
 
     @functools.lru_cache(maxsize=None)
@@ -136,6 +130,21 @@ class Table:
 
     def expect(self, n, rules, trim):
         return X.summarize(self.per_pair(rules, trim)[:n], self.m[0][:n], self.m[1][:n])
+
+
+class Table(HostTable):
+    """... and both mates on the device"""
+
+    def __init__(self, ctx, pairs, first, last):
+        import torch
+        from fastqandfurious_amd import hip
+        HostTable.__init__(self, pairs, first, last)
+        b1, b2 = self.bytes
+        self.d = (Dev(ctx, b1), Dev(ctx, b2))
+        self.t = tuple(torch.from_numpy(m.copy()).cuda() for m in self.m)
+        torch.cuda.synchronize()
+        self.v = (hip.table_view(self.d[0].ptr, self.d[0].n, self.t[0].data_ptr(), True, ADD1),
+                  hip.table_view(self.d[1].ptr, self.d[1].n, self.t[1].data_ptr(), False, ADD2))
 
     def close(self):
         for d in self.d:
@@ -199,21 +208,27 @@ def same(got, want, insert=True, hist=True):
         assert (gh == wh).all()
 
 
+def hand_layout(pairs):
+    """(first, last) of the hand table: a 150-base pair at the buffer's first byte of either mate, one at its last"""
+    plain = [i for i, p in enumerate(pairs) if p[2] == "" and len(p[0]) == len(p[1]) == 150]
+    return (plain[0], plain[1]), (plain[2], plain[3])
+
+
 @pytest.fixture(scope="module")
 def hand(gpu_ctx):
     pairs = hand_pairs()
     assert len(pairs) >= max(SIZES)
     by = {p[2] for p in pairs}
     assert {"", "long", "wrapped", "wrapped0", "fasta1", "fasta2", "outside1", "outside2", "negative1", "unequal1", "unequal2"} <= by
-    # a 150-base pair at the buffer's first byte of either mate, one at its last
     plain = [i for i, p in enumerate(pairs) if p[2] == "" and len(p[0]) == len(p[1]) == 150]
-    T = Table(gpu_ctx, pairs, (plain[0], plain[1]), (plain[2], plain[3]))
+    T = Table(gpu_ctx, pairs, *hand_layout(pairs))
     assert T.coord[0][plain[0]][2] == 1 and T.coord[1][plain[1]][2] == 0
     assert T.coord[0][plain[2]][3] == len(T.seen[0]) and T.coord[1][plain[3]][3] == len(T.seen[1])
     yield T
     T.close()
 
 
+@pytest.mark.gpu
 def test_the_hand_table_holds_every_kind(hand):
     """what the tests below rely on"""
     per = hand.per_pair(X.DEFAULT, True)
@@ -234,11 +249,13 @@ def test_the_hand_table_holds_every_kind(hand):
     assert per[i] == (60, None, None)
 
 
+@pytest.mark.gpu
 @pytest.mark.parametrize("n", SIZES)
 def test_pair_counts(gpu_ctx, hand, n):
     same(run(gpu_ctx, hand, n, X.DEFAULT, True), hand.expect(n, X.DEFAULT, True))
 
 
+@pytest.mark.gpu
 @pytest.mark.parametrize("name", sorted(RULESETS))
 def test_whole_table_under_every_rule_set(gpu_ctx, hand, name):
     rules = RULESETS[name]
@@ -250,6 +267,7 @@ def test_whole_table_under_every_rule_set(gpu_ctx, hand, name):
     same(run(gpu_ctx, hand, hand.n, rules, True, in_place=True), want)
 
 
+@pytest.mark.gpu
 def test_bounds_exactly_at_and_one_above(hand):
     """the loop itself says that the hand table's mismatch pairs sit on either side of both bounds"""
     base = [i for i, p in enumerate(hand.pairs) if p[2] == "" and len(p[0]) == len(p[1]) == 150]
@@ -262,6 +280,7 @@ def test_bounds_exactly_at_and_one_above(hand):
     assert sum(per_t[i][0] == 12 for i in base) == 2
 
 
+@pytest.mark.gpu
 def test_analyse_only_leaves_every_row(gpu_ctx, hand):
     """trim = 0: rows copied unchanged (out of place) or untouched (in place), d_insert and d_hist filled all the same"""
     want = hand.expect(hand.n, X.DEFAULT, False)
@@ -272,6 +291,7 @@ def test_analyse_only_leaves_every_row(gpu_ctx, hand):
     same(run(gpu_ctx, hand, hand.n, X.DEFAULT, False, in_place=True), want)
 
 
+@pytest.mark.gpu
 def test_optional_outputs_and_accumulate(gpu_ctx, hand):
     n = 200
     want = hand.expect(n, X.DEFAULT, True)
@@ -319,6 +339,7 @@ def mixed_pairs(n=513, seed=17):
     return pairs
 
 
+@pytest.mark.gpu
 def test_seeded_mixed_table(gpu_ctx):
     pairs = mixed_pairs()
     assert len(pairs) == 513
@@ -338,7 +359,122 @@ def test_seeded_mixed_table(gpu_ctx):
         T.close()
 
 
+# ---- more pairs than one pass of the grid (tests/grid_expect.py) -----------------------------------------------------------------
+# A group of eight lanes takes pair i, then pair i + P_GRID, in the same four LDS planes: only the planes' guard words are cleared,
+# once, so every pair behind a group's first finds its predecessor's words behind its own.  The pool is the hand table.
+P_GRID = GE.P_SHORT
+
+
+@functools.lru_cache(maxsize=None)
+def pool():
+    pairs = hand_pairs()
+    return HostTable(pairs, *hand_layout(pairs))
+
+
+def idle_pairs(H):
+    """pool pairs with nothing to do: not analysed, or without a base"""
+    return [i for i, p in enumerate(H.pairs) if p[2] != "" or not (p[0] or p[1])]
+
+
+@functools.lru_cache(maxsize=None)
+def pool_parts(H, rules, trim):
+    """the loop's answer for every pool pair ALONE: (rows of mate 1 out, of mate 2, insert, the six counts, kind)"""
+    per = H.per_pair(rules, trim)
+    o1, o2, ins, _hist, _counts = X.summarize(per, H.m[0], H.m[1])
+    counts = np.array([X.summarize(per[i:i + 1], H.m[0][i:i + 1], H.m[1][i:i + 1])[4] for i in range(H.n)], dtype=np.int64)
+    kinds = np.array(["not analysed" if i == -2 else "none" if i == -1 else "cut" if c1 is not None else "kept" for i, c1, _ in per])
+    return o1, o2, ins, counts, kinds
+
+
+def expand(parts, idx):
+    """what a call over pool[idx] gives, as X.summarize states it"""
+    o1, o2, ins, counts, _kinds = parts
+    gi = ins[idx]
+    hist = np.bincount(gi[gi >= 0], minlength=X.HIST_WORDS).astype(np.uint64)
+    return o1[idx], o2[idx], gi, hist, counts[idx].sum(axis=0).tolist()
+
+
+def used_plane_pairs(H, parts, idx):
+    """per pass behind the first: the pairs that are cut and shorter, in both mates, than the pair that had their group's planes
+    before them -- what is left in the planes reaches beyond their own words"""
+    n1, n2 = (np.array([len(p[k]) if p[2] == "" else 0 for p in H.pairs]) for k in (0, 1))
+    cut = parts[3][:, 2] > 0
+    i = np.arange(P_GRID, len(idx))
+    ok = cut[idx[i]] & (n1[idx[i]] < n1[idx[i - P_GRID]]) & (n2[idx[i]] < n2[idx[i - P_GRID]])
+    return [int(ok[i // P_GRID == k].sum()) for k in range(1, (len(idx) + P_GRID - 1) // P_GRID)]
+
+
+class Expanded:
+    """pool[idx] as run() takes it: the pool's buffers on the device, a table of its own"""
+
+    def __init__(self, T, idx):
+        import torch
+        self.m = (T.m[0][idx], T.m[1][idx])
+        self.t = tuple(torch.from_numpy(m.copy()).cuda() for m in self.m)
+        torch.cuda.synchronize()
+        self.v = tuple(type(x)(x.d_buf, x.n_bytes, x.sentinel, x.add, t.data_ptr()) for x, t in zip(T.v, self.t))
+        self.n = len(idx)
+
+
+def same_above(got, want):
+    for g, w, what in zip(got[:3], want[:3], ("mate 1's rows", "mate 2's rows", "insert sizes")):
+        GE.same_rows(g, w, P_GRID, what)
+    assert (got[3] == want[3]).all(), ("histogram", np.flatnonzero(got[3] != want[3])[:8])
+    assert got[4] == want[4]
+
+
+@pytest.mark.parametrize("arrangement", GE.ARRANGEMENTS)
+def test_the_table_above_one_pass_is_what_the_loop_says(arrangement):
+    """the expansion through idx against the plain loop on 2000 of the table's pairs; what every pass holds"""
+    H, rules = pool(), X.DEFAULT
+    n = GE.n_above(P_GRID)
+    assert n > 2 * 2048 * 32 and H.n <= 512
+    parts = pool_parts(H, rules, True)
+    idle = idle_pairs(H)
+    assert (parts[3][idle][:, 1:5] == 0).all() and {"cut", "kept", "none"} <= set(parts[4][[i for i in range(H.n) if i not in idle]])
+    idx = GE.table_idx(arrangement, n, P_GRID, H.n, idle, seed=23)
+    rows = GE.sample_rows(n, P_GRID)
+    assert len(rows) >= 2000 and {0, P_GRID - 1, P_GRID, 2 * P_GRID - 1, 2 * P_GRID, n - 1} <= set(rows.tolist())
+    j = idx[rows]
+    per = X.expect_table(H.seen[0], [H.coord[0][k] for k in j], True, H.seen[1], [H.coord[1][k] for k in j], False, rules, True)
+    same_above(X.summarize(per, H.m[0][j], H.m[1][j]), expand(parts, j))
+    for k, s in enumerate(GE.passes(n, P_GRID)):
+        counts, kinds = parts[3][idx[s]].sum(axis=0), set(parts[4][idx[s]])
+        if (arrangement, k > 0) in (("late work", False), ("early work", True)):
+            assert not counts[1:5].any() and kinds <= {"not analysed", "none"} and counts[0] > 0 and counts[5] > 0
+        else:
+            assert (counts > 0).all() and kinds == {"not analysed", "none", "cut", "kept"}, (k, counts)
+            # mates of very different lengths, and overlaps that end at the last base of mate 1
+            here = sorted(set(idx[s].tolist()))
+            assert {(512, 30), (30, 512)} <= {(len(H.pairs[i][0]), len(H.pairs[i][1])) for i in here}
+            assert any(parts[4][i] == "kept" and parts[2][i] >= len(H.pairs[i][0]) > 0 for i in here)
+    if arrangement == "random":
+        assert all(c > 100 for c in used_plane_pairs(H, parts, idx)), used_plane_pairs(H, parts, idx)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(RULESETS))
+def test_more_pairs_than_one_pass_of_the_grid(gpu_ctx, hand, name):
+    """three steps of every workgroup, the last for 1001 of the 2048 and five pairs for the last of those: every pair's rows and
+    insert size, the histogram and the six counts, out of place and in place, in the three arrangements"""
+    rules = RULESETS[name]
+    n = GE.n_above(P_GRID)
+    assert n > 2 * 2048 * 32
+    parts = pool_parts(hand, rules, True)
+    for arrangement in GE.ARRANGEMENTS:
+        idx = GE.table_idx(arrangement, n, P_GRID, hand.n, idle_pairs(hand), seed=23)
+        if arrangement == "random":
+            # passes 2 and 3 each hold pairs that are cut on planes a longer pair has used
+            used = used_plane_pairs(hand, parts, idx)
+            assert len(used) == 2 and all(c > 0 for c in used), used
+        want = expand(parts, idx)
+        T = Expanded(hand, idx)
+        same_above(run(gpu_ctx, T, n, rules, True), want)
+        same_above(run(gpu_ctx, T, n, rules, True, in_place=True), want)
+
+
 # ---- arguments -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
 def test_argument_errors(gpu_ctx, hand):
     import torch
     from fastqandfurious_amd import hip

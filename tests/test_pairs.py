@@ -6,11 +6,13 @@ histograms, the five pair counts; the four numbers of the names check.  The two 
 different `add`, mate 1 with a sentinel and mate 2 without.
 """
 import ctypes
+import functools
 
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
+import grid_expect as GE
+
 
 EE = [int(np.floor(1e6 * 10.0 ** (-v / 10.0) + 0.5)) for v in range(96)]
 RULES = dict(qual_base=33, max_n=1, min_mean_qual=20, qualified_qual=15, max_unqualified_pct=30, min_complexity_pct=30,
@@ -237,14 +239,12 @@ def build_mate(plan_kinds, junk):
 BOUNDS = ((1, 0), (200, 170))         # (min of mate 1, of mate 2), (max of mate 1, of mate 2)
 
 
-@pytest.fixture(scope="module")
-def hand(gpu_ctx):
-    """both mates' files on the device once, and every row's verdict by the loop once"""
-    from fastqandfurious_amd import hip
+@functools.lru_cache(maxsize=None)
+def hand_host():
+    """both mates' files, their rows as the tables hold them, and every row's verdict by the loop, once"""
     plan = pair_plan()
     b1, r1 = build_mate([p[0] for p in plan], b"")
     b2, r2 = build_mate([p[1] for p in plan], b"##junk##\n")
-    d1, d2 = Dev(gpu_ctx, b1), Dev(gpu_ctx, b2)
     # mate 1 has a sentinel: coordinate = position + 1; FASTA rows keep their -1
     c1 = np.where(r1 < 0, r1, r1 + 1)
     m1 = np.where(r1 < 0, r1, c1 + ADD1)
@@ -252,19 +252,31 @@ def hand(gpu_ctx):
     # (a -1 minus add is not a coordinate of the buffer either way: ADD1 > 0 keeps it negative, ADD2 < 0 makes it 4 -- so the
     # FASTA rows of mate 2 are given positions that stay outside)
     m2 = np.where(r2 < 0, -100, m2)
-    t1, t2 = dev_rows(m1), dev_rows(m2)
-    v1 = hip.table_view(d1.ptr, d1.n, t1.data_ptr(), True, ADD1)
-    v2 = hip.table_view(d2.ptr, d2.n, t2.data_ptr(), False, ADD2)
+    c2 = np.where(r2 < 0, -100 - ADD2, r2)
     seen1 = b"\n" + b1
     ver = {}
     for name, R in (("rules", RULES), ("off", None)):
         ver[name] = (mate_verdicts(seen1, c1.tolist(), R, BOUNDS[0][0], BOUNDS[1][0], True),
-                     mate_verdicts(b2, np.where(r2 < 0, -100 - ADD2, r2).tolist(), R, BOUNDS[0][1], BOUNDS[1][1], False))
-    yield dict(v1=v1, v2=v2, t1=t1, t2=t2, m1=m1, m2=m2, ver=ver, d1=d1, d2=d2, plan=plan)
+                     mate_verdicts(b2, c2.tolist(), R, BOUNDS[0][1], BOUNDS[1][1], False))
+    return dict(b1=b1, b2=b2, c1=c1, c2=c2, m1=m1, m2=m2, ver=ver, plan=plan)
+
+
+@pytest.fixture(scope="module")
+def hand(gpu_ctx):
+    """... and both files on the device"""
+    from fastqandfurious_amd import hip
+    H = dict(hand_host())
+    d1, d2 = Dev(gpu_ctx, H["b1"]), Dev(gpu_ctx, H["b2"])
+    t1, t2 = dev_rows(H["m1"]), dev_rows(H["m2"])
+    v1 = hip.table_view(d1.ptr, d1.n, t1.data_ptr(), True, ADD1)
+    v2 = hip.table_view(d2.ptr, d2.n, t2.data_ptr(), False, ADD2)
+    H.update(v1=v1, v2=v2, t1=t1, t2=t2, d1=d1, d2=d2)
+    yield H
     d1.close()
     d2.close()
 
 
+@pytest.mark.gpu
 def test_the_hand_table_holds_every_class(hand):
     """what the tests below rely on: every rule fires on either side, on both sides of the block edge, and not judged rows exist"""
     ver1, ver2 = hand["ver"]["rules"]
@@ -278,6 +290,7 @@ def test_the_hand_table_holds_every_class(hand):
     assert {(bool(a[0]), bool(b[0])) for a, b in zip(ver1[256:272], ver2[256:272])} >= {(True, False), (False, True), (True, True), (False, False)}
 
 
+@pytest.mark.gpu
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("n", SIZES)
 def test_select_pairs_with_every_rule(gpu_ctx, hand, n, mode):
@@ -290,6 +303,7 @@ def test_select_pairs_with_every_rule(gpu_ctx, hand, n, mode):
     assert sum(g1[:7]) == n and (mode == "first" or sum(g2[:7]) == n)
 
 
+@pytest.mark.gpu
 @pytest.mark.parametrize("mode", MODES)
 def test_one_mate_with_rules_the_other_by_length(gpu_ctx, hand, mode):
     """rules on mate 2 only (the positions-only kernel judges mate 1), and the other way round; no d_idx"""
@@ -303,6 +317,7 @@ def test_one_mate_with_rules_the_other_by_length(gpu_ctx, hand, mode):
         assert (o1 == hand["m1"][kept]).all() and (o2 == hand["m2"][kept]).all()
 
 
+@pytest.mark.gpu
 @pytest.mark.parametrize("mode", MODES)
 def test_length_only_reads_no_buffer(gpu_ctx, hand, mode):
     """no content rule on either side: both d_buf NULL"""
@@ -318,12 +333,15 @@ def test_length_only_reads_no_buffer(gpu_ctx, hand, mode):
     assert g1[2:] == [0] * 6 and g2[2:] == [0] * 6
 
 
+@pytest.mark.gpu
 def test_more_blocks_than_the_count_kernel_has_workgroups(gpu_ctx):
-    """k_pair_count strides over the blocks of 256 pairs with at most 1024 workgroups: 1024 * 256 + 300 pairs, judged by their
-    length alone (positions made up, no buffer), so that a workgroup takes a second block and the last block is a part of one"""
+    """k_pair_len strides over the pairs with at most 2048 workgroups of 256, k_pair_count over the blocks of 256 pairs with at
+    most 1024: 2048 * 256 + 300 pairs, judged by their length alone (positions made up, no buffer), so that a workgroup of
+    either takes a second block and the last block is a part of one"""
     import torch
     from fastqandfurious_amd import hip
-    n = 1024 * 256 + 300
+    n = 2048 * 256 + 300
+    assert n > GE.P_WIDE
     rng = np.random.default_rng(7)
     len1, len2 = rng.integers(0, 100, n), rng.integers(0, 100, n)
     rows1, rows2 = np.zeros((n, 6), dtype=np.int64), np.zeros((n, 6), dtype=np.int64)
@@ -334,20 +352,81 @@ def test_more_blocks_than_the_count_kernel_has_workgroups(gpu_ctx):
     t1, t2 = dev_rows(rows1), dev_rows(rows2)
     v1, v2 = hip.table_view(0, 1 << 20, t1.data_ptr(), True, 0), hip.table_view(0, 1 << 20, t2.data_ptr(), False, 0)
     for mode in MODES:
-        kept, pairs = [], [0] * 5
-        for i, (a, b) in enumerate(zip(len1.tolist(), len2.tolist())):
-            f1, f2 = not 20 <= a <= 90, mode != "first" and not 10 <= b <= 80
-            drop = (f1 or f2) if mode == "any" else (f1 and f2) if mode == "both" else f1
-            pairs[1 if drop else 0] += 1
-            pairs[4 if f1 and f2 else 2 if f1 else 3 if f2 else 0] += 1 if (f1 or f2) else 0
-            if not drop:
-                kept.append(i)
+        f1 = ~((len1 >= 20) & (len1 <= 90))
+        f2 = ~((len2 >= 10) & (len2 <= 80)) if mode != "first" else np.zeros(n, dtype=bool)
+        drop = (f1 | f2) if mode == "any" else (f1 & f2) if mode == "both" else f1
+        kept = np.flatnonzero(~drop)
+        pairs = [int((~drop).sum()), int(drop.sum()), int((f1 & ~f2).sum()), int((f2 & ~f1).sum()), int((f1 & f2).sum())]
         o1, o2, idx, g1, g2, gp = select_pairs(gpu_ctx, v1, v2, t1, t2, n, None, None, (20, 10), (90, 80), mode)
         assert gp == pairs
         assert g1[:2] == [int(((len1 >= 20) & (len1 <= 90)).sum()), int(((len1 < 20) | (len1 > 90)).sum())]
+        GE.same_kept(idx, kept, GE.P_WIDE, mode)
         assert (idx == np.array(kept)).all() and (o1 == rows1[kept]).all() and (o2 == rows2[kept]).all()
 
 
+# ---- more pairs than one pass of the grid (tests/grid_expect.py): the pool is the hand table, either mate with an idx of its own
+def grid_pairs(H, arrangement):
+    """(idx of mate 1, idx of mate 2): both mates idle in the same part of the table"""
+    n, P = GE.n_above(GE.P_SHORT), GE.P_SHORT
+    out = []
+    for k, ver in enumerate(H["ver"]["rules"]):
+        idle = [i for i, (v, judged) in enumerate(ver) if v == 1 or not judged]
+        out.append(GE.table_idx(arrangement, n, P, len(ver), idle, seed=50 + k))
+    return out
+
+
+def grid_pairs_want(H, idx1, idx2, mode):
+    ver1, ver2 = H["ver"]["rules"]
+    return loop_pairs([ver1[i] for i in idx1.tolist()], [ver2[i] for i in idx2.tolist()], mode, True, True)
+
+
+@pytest.mark.parametrize("arrangement", GE.ARRANGEMENTS)
+def test_the_pairs_above_one_pass_are_what_the_loop_says(arrangement):
+    H = hand_host()
+    n, P = GE.n_above(GE.P_SHORT), GE.P_SHORT
+    assert n > 2 * 2048 * 32
+    idx1, idx2 = grid_pairs(H, arrangement)
+    assert len(idx1) == len(idx2) == n and (idx1 != idx2).sum() > n // 2
+    at = GE.sample_rows(n, P)
+    assert len(at) >= 2000
+    # the verdicts of the table's own rows by the loop, against the pool's through idx
+    ver1, ver2 = H["ver"]["rules"]
+    assert mate_verdicts(b"\n" + H["b1"], H["c1"][idx1[at]].tolist(), RULES, BOUNDS[0][0], BOUNDS[1][0], True) == [ver1[i] for i in idx1[at]]
+    assert mate_verdicts(H["b2"], H["c2"][idx2[at]].tolist(), RULES, BOUNDS[0][1], BOUNDS[1][1], False) == [ver2[i] for i in idx2[at]]
+    for k, s in enumerate(GE.passes(n, P)):
+        kept, h1, h2, pairs = grid_pairs_want(H, idx1[s], idx2[s], "any")
+        if (arrangement, k > 0) in (("late work", False), ("early work", True)):
+            assert h1[2:7] == [0] * 5 and h2[2:7] == [0] * 5 and h1[7] > 0 and h2[7] > 0 and h1[1] > 0 and h2[1] > 0
+        else:
+            assert all(x > 0 for x in h1 + h2 + pairs), (k, h1, h2, pairs)
+            names = {H["plan"][i][0] for i in idx1[s]} | {H["plan"][i][1] for i in idx2[s]}
+            assert names == set(kinds())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", MODES)
+def test_more_pairs_than_one_pass_of_the_grid(gpu_ctx, hand, mode):
+    """content rules on both mates: k_filter_rows takes three steps over either table, the last for 1001 of its 2048 workgroups
+    with five rows for the last of those; the kept rows of both, d_idx, both histograms, the five pair counts"""
+    from fastqandfurious_amd import hip
+    P = GE.P_SHORT
+    for arrangement in GE.ARRANGEMENTS:
+        idx1, idx2 = grid_pairs(hand, arrangement)
+        n = len(idx1)
+        assert n > 2 * 2048 * 32
+        kept, h1, h2, pairs = grid_pairs_want(hand, idx1, idx2, mode)
+        m1, m2 = hand["m1"][idx1], hand["m2"][idx2]
+        t1, t2 = dev_rows(m1), dev_rows(m2)
+        v1 = hip.table_view(hand["d1"].ptr, hand["d1"].n, t1.data_ptr(), True, ADD1)
+        v2 = hip.table_view(hand["d2"].ptr, hand["d2"].n, t2.data_ptr(), False, ADD2)
+        o1, o2, idx, g1, g2, gp = select_pairs(gpu_ctx, v1, v2, t1, t2, n, RULES, RULES, BOUNDS[0], BOUNDS[1], mode)
+        GE.same_kept(idx, kept, P, arrangement)
+        assert gp == pairs and g1 == h1 and g2 == h2, (arrangement, gp, pairs, g1, h1, g2, h2)
+        GE.same_rows(o1, m1[kept], P, "%s: mate 1's kept rows (row: among the kept)" % arrangement)
+        GE.same_rows(o2, m2[kept], P, "%s: mate 2's kept rows (row: among the kept)" % arrangement)
+
+
+@pytest.mark.gpu
 def test_first_reads_nothing_of_mate_2(gpu_ctx, hand):
     """FFQ_PAIR_FIRST with rules on both sides, mate 2's d_buf NULL and a poisoned hist2: it comes back all zero"""
     import torch
@@ -373,6 +452,7 @@ def test_first_reads_nothing_of_mate_2(gpu_ctx, hand):
     assert (out1.cpu().numpy()[:k.value] == hand["m1"][kept]).all() and (out2.cpu().numpy()[:k.value] == hand["m2"][kept]).all()
 
 
+@pytest.mark.gpu
 def test_a_table_paired_with_itself_is_select_reads(gpu_ctx, hand):
     """select_pairs(T, T, ANY) gives the rows and counts ffq_table_select_reads(T) gives"""
     import torch
@@ -390,6 +470,7 @@ def test_a_table_paired_with_itself_is_select_reads(gpu_ctx, hand):
     assert (o1 == out.cpu().numpy()[:k]).all() and (o2 == o1).all()
 
 
+@pytest.mark.gpu
 def test_select_pairs_argument_errors(gpu_ctx, hand):
     import torch
     from fastqandfurious_amd import hip
@@ -460,11 +541,13 @@ def names_on_device(ctx, b1, rows1, b2, rows2):
     return got, loop_names(b"\n" + bytes(b1), c1, bytes(b2), rows2)
 
 
+@pytest.mark.gpu
 def test_the_id_loop_gives_the_hand_values():
     assert loop_id(b"r1/1 comment") == b"r1" and loop_id(b"r1\t/2") == b"r1" and loop_id(b"/1") == b"" and loop_id(b"/") == b"/"
     assert loop_id(b"a/3") == b"a/3" and loop_id(b"") == b"" and loop_id(b" x") == b"" and loop_id(b"a/1/2") == b"a/1"
 
 
+@pytest.mark.gpu
 def test_pair_names_on_every_case(gpu_ctx):
     cases = name_cases()
     b1, rows1 = build_headers([c[0] for c in cases], b"")
@@ -489,6 +572,7 @@ def test_pair_names_on_every_case(gpu_ctx):
     assert all(g == w for g, w in got_each), [i for i, (g, w) in enumerate(got_each) if g != w]
 
 
+@pytest.mark.gpu
 def test_pair_names_one_long_id_in_a_wave_of_short_ones(gpu_ctx):
     """a wave of eight groups: one with a 300-byte id, four with 1-byte ids, three without a row -- the shape a round loop that
     is not uniform over the wave hangs on; and the same with the long id last, and differing in its last byte"""
@@ -502,6 +586,7 @@ def test_pair_names_one_long_id_in_a_wave_of_short_ones(gpu_ctx):
         assert got == want
 
 
+@pytest.mark.gpu
 def test_pair_names_rows_that_are_not_compared_and_the_first_different(gpu_ctx):
     """600 pairs (19 workgroups of 32): different pairs at 77, 300 and 599, and rows that point outside in between"""
     heads = [b"r%d" % i for i in range(600)]
@@ -521,3 +606,103 @@ def test_pair_names_rows_that_are_not_compared_and_the_first_different(gpu_ctx):
     assert want == (600 - 2 - 6, 2, 6, 77)
     from fastqandfurious_amd import hip
     assert gpu_ctx.table_pair_names(hip.table_view(0, 0, 0), hip.table_view(0, 0, 0), 0) == (0, 0, 0, -1)
+
+
+# ---- more pairs than one pass of the grid: the names --------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def names_pool():
+    """(bytes 1, rows 1, bytes 2, rows 2, class of every pool pair by the loop: 0 equal, 1 different, 2 not compared): the cases
+    of name_cases(), a header that ends with the buffer on either side, and rows that point outside"""
+    cases = name_cases()
+    b1, rows1 = build_headers([c[0] for c in cases], b"")
+    b2, rows2 = build_headers([c[1] for c in cases], b"#\n")
+    n1, n2 = len(b1), len(b2)
+    for k in range(6):
+        rows1.append(list(rows1[3 * k]))
+        rows2.append(list(rows2[3 * k]))
+    rows1[-6][1] = n1 + 400                         # ends behind the buffer
+    rows2[-5][0] = -1 - ADD2 - 7                    # begins in front of it
+    rows1[-4][1] = rows1[-4][0]                     # pos0 + 1 > pos1
+    rows2[-3] = [-100, -100, 0, 0, 0, 0]
+    rows1[-2] = [n1 + 1000, n1 + 1020, 0, 0, 0, 0]
+    rows2[-1][1] = n2 + 400
+    tail = make_id(33, 5)
+    for buf, rows in ((b1, rows1), (b2, rows2)):
+        p0 = len(buf)
+        buf += b"@" + tail
+        rows.append([p0, len(buf), 0, 0, 0, 0])
+    c1 = [[r[0] + 1, r[1] + 1] + r[2:] for r in rows1]
+    cls = []
+    for a, b in zip(c1, rows2):
+        eq, df, nc, _first = loop_names(b"\n" + bytes(b1), [a], bytes(b2), [b])
+        cls.append(0 if eq else 1 if df else 2)
+    return bytes(b1), np.array(c1, dtype=np.int64), bytes(b2), np.array(rows2, dtype=np.int64), np.array(cls)
+
+
+def names_want(cls, idx):
+    """(equal, different, not compared, first different or -1) of pool[idx]"""
+    c = cls[idx]
+    df = np.flatnonzero(c == 1)
+    return int((c == 0).sum()), int(df.size), int((c == 2).sum()), int(df[0]) if df.size else -1
+
+
+NAMES_PLACES = ("none", "inside pass 1", "first of pass 2", "last row")
+
+
+def names_tables():
+    """[(what, idx)]: the three arrangements, and tables whose ONLY different pair stands at one of three places, or nowhere"""
+    cls = names_pool()[4]
+    n, P = GE.n_above(GE.P_SHORT), GE.P_SHORT
+    out = [(a, GE.table_idx(a, n, P, len(cls), np.flatnonzero(cls == 2), seed=61)) for a in GE.ARRANGEMENTS]
+    same = np.flatnonzero(cls != 1)
+    base = same[np.random.default_rng(62).integers(0, len(same), n)]
+    for what, at in zip(NAMES_PLACES, (None, 40001, P, n - 1)):
+        idx = base.copy()
+        if at is not None:
+            idx[at] = int(np.flatnonzero(cls == 1)[at % int((cls == 1).sum())])
+        out.append((what, idx))
+    return out
+
+
+def test_the_names_above_one_pass_are_what_the_loop_says():
+    b1, c1, b2, r2, cls = names_pool()
+    n, P = GE.n_above(GE.P_SHORT), GE.P_SHORT
+    assert n > 2 * 2048 * 32 and len(cls) < 200 and set(cls.tolist()) == {0, 1, 2} and int((cls == 2).sum()) == 6
+    tables = names_tables()
+    at = GE.sample_rows(n, P)
+    for what, idx in tables:
+        assert len(idx) == n
+        if what in ("random", "last row"):
+            j = idx[at]
+            eq, df, nc, first = loop_names(b"\n" + b1, c1[j].tolist(), b2, r2[j].tolist())
+            assert len(at) >= 2000 and (eq, df, nc, first) == names_want(cls, j)
+        want = names_want(cls, idx)
+        if what in NAMES_PLACES:
+            assert want[1] == (what != "none") and want[3] == {"none": -1, "inside pass 1": 40001, "first of pass 2": P, "last row": n - 1}[what]
+            assert 0 < 40001 < P and want[2] > 0
+        for k, s in enumerate(GE.passes(n, P)):
+            w = names_want(cls, idx[s])
+            if (what, k > 0) in (("late work", False), ("early work", True)):
+                assert w[:2] == (0, 0) and w[2] == s.stop - s.start
+            elif what in GE.ARRANGEMENTS:
+                assert min(w[:3]) > 0
+
+
+@pytest.mark.gpu
+def test_pair_names_more_pairs_than_one_pass_of_the_grid(gpu_ctx):
+    """three steps of every workgroup of k_pair_names; the four numbers in the three arrangements, and `first` with the only
+    different pair inside pass 1, as the first pair of pass 2, as the table's last row, and nowhere (-1)"""
+    from fastqandfurious_amd import hip
+    b1, c1, b2, r2, cls = names_pool()
+    d1, d2 = Dev(gpu_ctx, b1), Dev(gpu_ctx, b2)
+    try:
+        for what, idx in names_tables():
+            t1 = dev_rows(c1[idx] + np.array([ADD1, ADD1, 0, 0, 0, 0]))
+            t2 = dev_rows(r2[idx] + np.array([ADD2, ADD2, 0, 0, 0, 0]))
+            got = gpu_ctx.table_pair_names(hip.table_view(d1.ptr, d1.n, t1.data_ptr(), True, ADD1),
+                                           hip.table_view(d2.ptr, d2.n, t2.data_ptr(), False, ADD2), len(idx))
+            want = names_want(cls, idx)
+            assert tuple(got) == want, "%s: got %s, expected %s (first different: pass %s)" % (what, tuple(got), want, want[3] // GE.P_SHORT)
+    finally:
+        d1.close()
+        d2.close()

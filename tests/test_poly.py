@@ -5,9 +5,12 @@ The expectation of every test is the loop of tests/poly_expect.py -- the rule as
 never the package's own host implementation.  Coordinates: a row minus `add` indexes the buffer the scanner saw; with a
 sentinel that buffer is b'\\n' + bytes.
 """
+import functools
+
 import numpy as np
 import pytest
 
+import grid_expect as GE
 import poly_expect as E
 
 
@@ -185,6 +188,92 @@ def test_long_rows_device(gpu_ctx):
             bad = np.flatnonzero((got != want).any(axis=1))
             assert bad.size == 0, (base, bad.tolist(), got[bad].tolist(), want[bad].tolist())
             assert gstats == stats
+
+
+# ---- more rows than one pass of the grid (tests/grid_expect.py) -------------------------------------------------------------
+GRID_BASES = (b"G", b"T", None)
+
+
+@functools.lru_cache(maxsize=None)
+def grid_parts(base, sentinel=False, add=0):
+    """the loop's answer for every pool row ALONE: (rows in, rows out, [changed, bases removed, skipped] each)"""
+    buf, rows, _idle, _long = E.grid_pool()
+    seen, shift = (b"\n" if sentinel else b"") + buf, add + (1 if sentinel else 0)
+    rows = np.array(rows, dtype=np.int64) + shift
+    per = [E.loop_rows(seen, [r], base, add=add) for r in rows]
+    return rows, np.array([w[0] for w, _s, _l in per], dtype=np.int64), np.array([s for _w, s, _l in per], dtype=np.int64)
+
+
+def grid_table(arrangement, base, sentinel=False, add=0, long_rows=False):
+    """(rows in, rows out, stats, idx) of pool[idx]"""
+    _buf, rows, idle, long = E.grid_pool()
+    if long_rows:
+        idx = GE.long_idx(long, [i for i in range(len(rows)) if i not in long], seed=41)
+    else:
+        idx = GE.table_idx(arrangement, GE.n_above(GE.P_SHORT), GE.P_SHORT, len(rows), idle, seed=41)
+    rin, rout, stats = grid_parts(base, sentinel, add)
+    return rin[idx], rout[idx], stats[idx].sum(axis=0).tolist(), idx
+
+
+@pytest.mark.parametrize("long_rows", (False, True))
+def test_the_table_above_one_pass_is_what_the_loop_says(long_rows):
+    buf, rows, idle, long = E.grid_pool()
+    lengths = np.array([r[3] - r[2] for r in rows])
+    assert len(rows) < 400 and len(buf) < 1 << 20 and {E.LONG, E.LONG + 1} <= set(lengths.tolist()) and len(long) >= 6
+    assert (lengths[list(long)] > E.LONG).all() and sorted(lengths[list(long)])[1] < E.LONG + 8 and max(lengths) <= 6000
+    P = GE.P_LONG if long_rows else GE.P_SHORT
+    for arrangement in ("random",) if long_rows else GE.ARRANGEMENTS:
+        for base, sentinel, add in ((b"G", False, 0), (None, True, 500)):
+            rin, rout, stats, idx = grid_table(arrangement, base, sentinel, add, long_rows)
+            n = len(idx)
+            assert (n == 2 * GE.N_LONG and int(np.isin(idx, long).sum()) == GE.N_LONG > 2 * 1024 * 4 and n >= 4096) if long_rows else n > 2 * 2048 * 32
+            _r, rout1, stats1 = grid_parts(base, sentinel, add)
+            # the expansion against the loop over the table's own rows
+            at = GE.sample_rows(n, P) if arrangement == "random" and base == b"G" else GE.sample_rows(n, P, 50)
+            want, wstats, _l = E.loop_rows((b"\n" if sentinel else b"") + buf, rin[at], base, add=add)
+            GE.same_rows(rout[at], want, P, "rows")
+            assert stats1[idx[at]].sum(axis=0).tolist() == wstats
+            # what every pass holds: changed rows, skipped rows, rows left as they are, empty rows
+            order = np.flatnonzero(np.isin(idx, long)) if long_rows else np.arange(n)        # (the list's entries, in row order)
+            for k, s in enumerate(GE.passes(len(order), P)):
+                part = idx[order[s]]
+                c = stats1[part].sum(axis=0)
+                if (arrangement, k > 0) in (("late work", False), ("early work", True)):
+                    assert c[0] == c[1] == 0 and c[2] > 0 and set(part.tolist()) <= set(idle)
+                else:
+                    assert (c[:2] > 0).all() and (c[2] > 0 or long_rows) and (stats1[part][:, 0] == 0).any(), (arrangement, k, c)
+                    assert long_rows or ((lengths[part] == 0).any() and (lengths[part] > E.LONG).any())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("base", GRID_BASES)
+def test_more_rows_than_one_pass_of_the_grid(gpu_ctx, base):
+    """three steps of every workgroup, the last for 1001 of the 2048 with five rows for the last of those; every row and the
+    three counts, out of place and in place; "late work" with a sentinel and add = 500"""
+    buf = E.grid_pool()[0]
+    for arrangement in GE.ARRANGEMENTS:
+        sentinel, add = (True, 500) if arrangement == "late work" else (False, 0)
+        rin, want, stats, idx = grid_table(arrangement, base, sentinel, add)
+        assert len(idx) > 2 * 2048 * 32
+        for in_place in (False, True):
+            got, gstats = device_poly(gpu_ctx, buf, rin, base, sentinel=sentinel, add=add, in_place=in_place)
+            GE.same_rows(got, want, GE.P_SHORT, "%s, in place %s" % (arrangement, in_place))
+            assert gstats == stats, (arrangement, in_place)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("base", GRID_BASES)
+def test_more_long_rows_than_one_pass_of_the_grid(gpu_ctx, base):
+    """9195 rows above LONG among as many short ones: the long launch's 1024 workgroups take three steps over the list"""
+    buf, _rows, _idle, long = E.grid_pool()
+    rin, want, stats, idx = grid_table("random", base, long_rows=True)
+    is_long = np.isin(idx, long)
+    assert int(is_long.sum()) > 2 * 1024 * 4 and len(idx) >= 4096
+    for in_place in (False, True):
+        got, gstats = device_poly(gpu_ctx, buf, rin, base, in_place=in_place)
+        GE.same_rows(got[is_long], want[is_long], GE.P_LONG, "long rows (list entries), in place %s" % in_place)
+        GE.same_rows(got, want, GE.P_SHORT, "all rows, in place %s" % in_place)
+        assert gstats == stats
 
 
 @pytest.mark.gpu

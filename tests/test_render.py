@@ -5,10 +5,13 @@ reference's entryfunc -- never the package's own host implementation and never t
 a row minus `add` indexes the buffer the scanner saw; with a sentinel that buffer is b'\\n' + bytes, and its byte 0 is
 never read.
 """
+import functools
 import io
 
 import numpy as np
 import pytest
+
+import grid_expect as GE
 
 from conftest import golden_file
 from test_trim import loop_rows as loop_trim, scan_on_device
@@ -267,6 +270,131 @@ def test_exact_capacity(gpu_ctx):
     # sizing call: no output at all
     rc, st = gpu_ctx.table_render_fastq(0, 0, 0, 0, None, 0, None)
     assert rc == 0 and st == (0, 0, 0)
+
+
+# ---- more rows than one pass of the grid (tests/grid_expect.py) -------------------------------------------------------------
+RENDER_LONG = 4096                    # output bytes above which the library gives a row a wave of its own (csrc/ffq_render.h)
+
+
+@functools.lru_cache(maxsize=None)
+def grid_pool():
+    """(bytes, rows, idle, long, text of every pool row by the loop): the first 300 records of the sweep -- lengths 0..40, rows that
+    render as nothing --, rows that point outside, records of RENDER_LONG - 1, RENDER_LONG output bytes and six above it"""
+    sbuf, srows = sweep()[:2]
+    parts, rows, at = [sbuf], srows[:300].tolist(), len(sbuf)
+    r = rows[0]
+    rows += [[r[0], r[1], r[2], r[3], len(sbuf) + (1 << 30), len(sbuf) + (1 << 30) + 4], [-5, r[1], r[2], r[3], r[4], r[5]],
+             [r[0], r[0], r[2], r[3], r[4], r[5]]]
+    rng = np.random.default_rng(71)
+    for h, s, q in ((2, 2043, 2044), (2, 2044, 2044), (2, 2044, 2045), (2, 2045, 2045), (30, 2100, 2100), (2, 2500, 2500), (2, 1, 6000),
+                    (3000, 600, 600)):
+        hb, sb, qb = (rng.integers(65, 91, k, dtype=np.uint8).tobytes() for k in (h, s, q))
+        rec = b"@" + hb + b"\n" + sb + b"\n+\n" + qb + b"\n"
+        p0, p2 = at, at + h + 2
+        p4 = p2 + s + 3
+        rows.append([p0, p0 + 1 + h, p2, p2 + s, p4, p4 + q])
+        parts.append(rec)
+        at += len(rec)
+    buf, rows = b"".join(parts), np.array(rows, dtype=np.int64)
+    texts = [loop_render(buf, [r])[0] for r in rows]
+    idle = [i for i, t in enumerate(texts) if not t]
+    long = [i for i, t in enumerate(texts) if len(t) > RENDER_LONG]
+    return buf, rows, tuple(idle), tuple(long), texts
+
+
+def grid_want(idx):
+    """(text, offsets, [bytes, rows rendered, rows skipped]) of pool[idx]"""
+    texts = grid_pool()[4]
+    lens = np.array([len(t) for t in texts], dtype=np.int64)
+    off = np.concatenate([[0], np.cumsum(lens[idx])])
+    return b"".join([texts[i] for i in idx.tolist()]), off, [int(off[-1]), int((lens[idx] > 0).sum()), int((lens[idx] == 0).sum())]
+
+
+def grid_table(arrangement, long_rows=False):
+    _buf, rows, idle, long, _texts = grid_pool()
+    if long_rows:
+        return GE.long_idx(long, [i for i in range(len(rows)) if i not in long], seed=73)
+    # (of the rows around RENDER_LONG, the one at it and the one a byte above it: the text stays below 64 MiB)
+    texts = grid_pool()[4]
+    short = np.array([i for i in range(len(rows)) if i not in long[1:] and len(texts[i]) != RENDER_LONG - 1])
+    idx = GE.table_idx(arrangement, GE.n_above(GE.P_WIDE), GE.P_WIDE, len(short), np.flatnonzero(np.isin(short, idle)), seed=73)
+    return short[idx]
+
+
+def check_above(ctx, dbuf, idx, P, what, sentinel=False, add=0, short_by_one=False):
+    from fastqandfurious_amd import hip
+    rows = grid_pool()[1]
+    want, off, stats = grid_want(idx)
+    moved = rows[idx] + int(sentinel) + add
+    moved[rows[idx] < 0] = -1                     # (a negative entry is not a position: it does not move)
+    rc, text, goff, gstats = device_render(ctx, dbuf, moved, sentinel=sentinel, add=add, misalign=3, cap=len(want) - int(short_by_one))
+    GE.same_rows(goff, off, P, what + ": offsets")
+    assert gstats == stats, (what, gstats, stats)
+    got = np.frombuffer(text, dtype=np.uint8)
+    if short_by_one:                                            # the need reported, nothing written, the offsets all the same
+        assert rc == hip.E_TABLE_FULL and (got == GUARD).all(), what
+        return
+    assert rc == 0
+    bad = np.flatnonzero(got != np.frombuffer(want, dtype=np.uint8))
+    if bad.size:
+        r = int(np.searchsorted(off, bad[0], side="right") - 1)
+        raise AssertionError("%s: first difference at output byte %d: row %d, pass %d: %r != %r"
+                             % (what, bad[0], r, r // P, text[bad[0] - 8:bad[0] + 24], want[bad[0] - 8:bad[0] + 24]))
+
+
+@pytest.mark.parametrize("long_rows", (False, True))
+def test_the_table_above_one_pass_is_what_the_loop_says(long_rows):
+    buf, rows, idle, long, texts = grid_pool()
+    lens = np.array([len(t) for t in texts])
+    assert len(rows) < 400 and len(buf) < 1 << 20 and len(idle) >= 6 and len(long) == 6
+    assert {RENDER_LONG - 1, RENDER_LONG, RENDER_LONG + 1, RENDER_LONG + 2} <= set(lens.tolist()) and max(lens) < 8000
+    P = GE.P_LONG if long_rows else GE.P_WIDE
+    for arrangement in ("random",) if long_rows else GE.ARRANGEMENTS:
+        idx = grid_table(arrangement, long_rows)
+        n = len(idx)
+        assert (n == 2 * GE.N_LONG and int(np.isin(idx, long).sum()) == GE.N_LONG > 2 * 1024 * 4 and n >= 4096) if long_rows else n > 2048 * 256
+        want, off, stats = grid_want(idx)
+        assert len(want) == stats[0] < 64 << 20 and stats[1] + stats[2] == n
+        at = GE.sample_rows(n, P)
+        text, loff, lstats = loop_render(buf, rows[idx[at]])
+        assert len(at) >= 2000 and (text, loff, lstats) == (grid_want(idx[at])[0], grid_want(idx[at])[1].tolist(), grid_want(idx[at])[2])
+        assert all(want[off[i]:off[i + 1]] == texts[idx[i]] for i in at.tolist())
+        order = np.flatnonzero(np.isin(idx, long)) if long_rows else np.arange(n)
+        for k, s in enumerate(GE.passes(len(order), P)):
+            part = idx[order[s]]
+            if (arrangement, k > 0) in (("late work", False), ("early work", True)):
+                assert set(part.tolist()) <= set(idle)
+            elif long_rows:
+                assert set(part.tolist()) == set(long)
+            else:
+                assert (lens[part] == 0).any() and (lens[part] == RENDER_LONG).any() and (lens[part] > RENDER_LONG).any() and \
+                    (lens[part] == 6).any()
+
+
+@pytest.mark.gpu
+def test_more_rows_than_one_pass_of_the_grid(gpu_ctx):
+    """two steps of every workgroup of k_render_sum and the copy behind it, the second for 301 of the 2048 with seven rows for the
+    last of those: every byte, every offset, the three counts; "late work" with a sentinel and add; a capacity one byte short"""
+    import torch
+    dbuf = torch.from_numpy(np.frombuffer(grid_pool()[0], dtype=np.uint8).copy()).cuda()
+    for arrangement in GE.ARRANGEMENTS:
+        idx = grid_table(arrangement)
+        assert len(idx) > 2048 * 256
+        sentinel, add = (True, (1 << 32) + 5) if arrangement == "late work" else (False, 0)
+        check_above(gpu_ctx, dbuf, idx, GE.P_WIDE, arrangement, sentinel, add)
+        if arrangement == "random":
+            check_above(gpu_ctx, dbuf, idx, GE.P_WIDE, arrangement + ", one byte short", short_by_one=True)
+
+
+@pytest.mark.gpu
+def test_more_long_rows_than_one_pass_of_the_grid(gpu_ctx):
+    """9195 rows above RENDER_LONG output bytes among as many others: k_render_long's 1024 workgroups take three steps over the list"""
+    import torch
+    dbuf = torch.from_numpy(np.frombuffer(grid_pool()[0], dtype=np.uint8).copy()).cuda()
+    idx = grid_table("random", long_rows=True)
+    assert int(np.isin(idx, grid_pool()[3]).sum()) > 2 * 1024 * 4 and len(idx) >= 4096
+    check_above(gpu_ctx, dbuf, idx, GE.P_WIDE, "long rows among short ones")
+    check_above(gpu_ctx, dbuf, idx, GE.P_WIDE, "long rows, one byte short", short_by_one=True)
 
 
 def _trim_filter_loop(data, rows, cf, cb, min_len):

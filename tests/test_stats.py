@@ -5,10 +5,13 @@ FastqStats itself.  Bulk cases use a numpy form of that loop (np_words), which i
 hand vectors.  Every comparison is exact equality over every word.  Coordinates: a row minus `add` indexes the buffer the
 scanner saw; with a sentinel that buffer is b'\\n' + bytes.
 """
+import functools
 import io
 
 import numpy as np
 import pytest
+
+import grid_expect as GE
 
 TILE = 152              # cycles per LDS tile, and the bases above which a row gets a wave of its own (csrc/ffq_stats.h: STATS_TILE)
 GROUP_BYTES = 32        # bytes of a row that its 8 lanes take per step (STATS_G * 4)
@@ -502,6 +505,60 @@ def test_contention(gpu_ctx):
     want = check_device(gpu_ctx, buf, table, 150)
     check_device(gpu_ctx, buf, table[::-1], 150, want=want)
     assert want[0] == 70000 and want[2] == 350000
+
+
+# ---- more long rows than one pass of the long launches' grids (tests/grid_expect.py) ----------------------------------------------
+LONG_LIST_CYCLES = (512, 200)         # four cycle tiles, the last one of 56 cycles; two, the last one of 48
+
+
+@functools.lru_cache(maxsize=None)
+def long_list_table():
+    """(bytes, rows of the table, which of them go onto the long list, the long pool rows): short reads up to TILE bases and the
+    rows the rule does not apply to; eight rows above TILE -- one, two and eight bases above it, 700, 1500 and 2500 bases, and
+    two with a newline in a line, which the check strikes off the list -- drawn 9195 times among as many of the others"""
+    rng = np.random.default_rng(48)
+    buf, rows = bytearray(b"#"), []
+    for n in [0, 1, 5, TILE - 1, TILE, TILE] + [int(x) for x in rng.integers(0, TILE + 1, 30)]:
+        record(buf, rows, *one_read(rng, n))
+    ineligible_rows(buf, rows)
+    for n in (TILE + 1, TILE + 2, TILE + 8, 700, 1500, 2500):
+        record(buf, rows, *one_read(rng, n))
+    rows = np.array(rows, dtype=np.int64)
+    n = rows[:, 3] - rows[:, 2]
+    ok = (rows[:, 2:] >= 0).all(axis=1) & (rows[:, 3] <= len(buf)) & (rows[:, 5] <= len(buf)) & (n == rows[:, 5] - rows[:, 4])
+    long = np.flatnonzero(ok & (n > TILE))
+    idx = GE.long_idx(long, [i for i in range(len(rows)) if i not in long], seed=49)
+    return bytes(buf), rows[idx], np.isin(idx, long), rows[long]
+
+
+def test_the_long_list_table_is_what_the_loop_says():
+    buf, table, is_long, long_rows = long_list_table()
+    n = long_rows[:, 3] - long_rows[:, 2]
+    recs = records_of(buf, long_rows)
+    assert len(n) == 8 and sorted(n)[:2] == [TILE + 1, TILE + 2] and max(n) == 2500 and sum(r is None for r in recs) == 2
+    assert int(is_long.sum()) == GE.N_LONG > 2 * 512 * 8 and len(table) == 2 * GE.N_LONG >= 4096
+    order = np.flatnonzero(is_long)
+    assert len(GE.passes(len(order), GE.P_LONG)) == 3
+    for s in GE.passes(len(order), GE.P_LONG):                 # every long pool row, the two struck off among them, in every pass
+        assert len({tuple(r) for r in table[order[s]].tolist()}) == 8
+    at = GE.sample_rows(len(table), GE.P_LONG)
+    recs = records_of(buf, table[at])
+    for C in LONG_LIST_CYCLES:
+        assert -(-C // TILE) >= 2 and C % TILE != 0
+        want = np_words(recs, C)
+        assert len(at) >= 2000 and (want == loop_words(recs, C)).all()
+        check_invariants(want, C)
+        assert want[1] > 100 and want[3] > 0 and want[8 + 101 * C + C] > 100
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("C", LONG_LIST_CYCLES)
+def test_more_long_rows_than_one_pass_of_the_grid(gpu_ctx, C):
+    """9195 rows above TILE among as many others: k_stats_long_check's 512 workgroups of eight waves take three steps over the
+    list and strike entries off it in each, k_stats_long_count's 128 take nine per cycle tile; every word of the block"""
+    buf, table, is_long, _long_rows = long_list_table()
+    assert int(is_long.sum()) > 2 * 512 * 8 and int(is_long.sum()) > 8 * 128 * 8 and len(table) >= 4096
+    check_device(gpu_ctx, buf, table, C, combos=((0, 0), (1, (1 << 33) + 5)))
 
 
 @pytest.mark.gpu

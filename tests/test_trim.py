@@ -5,11 +5,14 @@ The expectation of every test is the loop below -- the rule as include/ffq.h sta
 package's own host implementation.  Coordinates: a row minus `add` indexes the buffer the scanner saw; with a sentinel
 that buffer is b'\\n' + bytes.
 """
+import functools
 import io
 import os
 
 import numpy as np
 import pytest
+
+import grid_expect as GE
 
 from conftest import GOLDEN_DIR, golden_file
 
@@ -433,6 +436,65 @@ def test_more_rows_than_one_pass_of_the_grid(gpu_ctx):
     assert rows.shape[0] > 2 * 2048 * 32 and len(buf) < 6 << 20
     want, stats = check_device(gpu_ctx, buf, rows)
     assert stats[0] > 10000 and stats[2] == 0
+
+
+# ---- more long rows than one pass of the long launch's grid (tests/grid_expect.py) ------------------------------------------------
+TRIM_LONG = 4096                      # quality bytes above which the library gives a row a wave of its own (csrc/ffq_trim.h)
+
+
+@functools.lru_cache(maxsize=None)
+def long_list_pool():
+    """(bytes, rows, long, rows out and [changed, removed, skipped] of every pool row ALONE, by the loop): 40 short reads, one of
+    TRIM_LONG quality bytes, and six above it -- just above and up to 6000, low ends of several lengths, none, all low"""
+    rng = np.random.default_rng(44)
+    quals = [rng.integers(0, 41, int(rng.integers(0, 101))) for _ in range(40)] + [rng.integers(25, 41, TRIM_LONG)]
+    for n, k in ((TRIM_LONG + 1, 0), (TRIM_LONG + 2, 7), (TRIM_LONG + 4, 1100), (4500, 300), (5200, 2000), (6000, 6000)):
+        q = rng.integers(30, 41, n)
+        q[:k] = rng.integers(0, 6, k)
+        q[n - k:] = rng.integers(0, 6, k)
+        quals.append(q)
+    buf, rows = table_of_quals(quals)
+    long = [i for i, q in enumerate(quals) if len(q) > TRIM_LONG]
+    per = [loop_rows(buf, [r], 20, 20) for r in rows]
+    return buf, rows, tuple(long), np.array([w[0] for w, _s in per], dtype=np.int64), np.array([st for _w, st in per], dtype=np.int64)
+
+
+def long_list_table():
+    """(rows in, rows out, stats, which rows are long) of pool[idx]"""
+    _buf, rows, long, out, stats = long_list_pool()
+    idx = GE.long_idx(long, [i for i in range(len(rows)) if i not in long], seed=45)
+    return rows[idx], out[idx], stats[idx].sum(axis=0).tolist(), np.isin(idx, long)
+
+
+def test_the_long_list_table_is_what_the_loop_says():
+    buf, rows, long, out, stats = long_list_pool()
+    n = rows[:, 5] - rows[:, 4]
+    assert len(long) == 6 and sorted(n[list(long)])[:2] == [TRIM_LONG + 1, TRIM_LONG + 2] and max(n) == 6000 and (n == TRIM_LONG).any()
+    assert (stats[list(long), 0] > 0).sum() == 5 and (stats[list(long), 0] == 0).sum() == 1
+    rin, want, wstats, is_long = long_list_table()
+    assert int(is_long.sum()) == GE.N_LONG > 2 * 1024 * 4 and len(rin) == 2 * GE.N_LONG >= 4096
+    at = GE.sample_rows(len(rin), GE.P_LONG)
+    loop, lstats = loop_rows(buf, rin[at], 20, 20)
+    assert len(at) >= 2000 and (loop == want[at]).all()
+    order = np.flatnonzero(is_long)
+    for s in GE.passes(len(order), GE.P_LONG):                         # every long pool row in every pass over the list
+        assert len({tuple(r) for r in rin[order[s]].tolist()}) == 6
+    assert len(GE.passes(len(order), GE.P_LONG)) == 3
+
+
+@pytest.mark.gpu
+def test_more_long_rows_than_one_pass_of_the_grid(gpu_ctx):
+    """9195 rows above TRIM_LONG among as many short ones: k_trim_long's 1024 workgroups of four waves take three steps over the
+    list, the last for 1003 entries; out of place and in place, and with a sentinel and add = 7"""
+    buf = long_list_pool()[0]
+    rin, want, stats, is_long = long_list_table()
+    assert int(is_long.sum()) > 2 * 1024 * 4 and len(rin) >= 4096
+    for sentinel, add, in_place in ((0, 0, False), (0, 0, True), (1, 7, False)):
+        got, gstats = device_trim(gpu_ctx, buf, rin + sentinel + add, 20, 20, sentinel=bool(sentinel), add=add, in_place=in_place)
+        what = "sentinel %d, add %d, in place %s" % (sentinel, add, in_place)
+        GE.same_rows(got[is_long], (want + sentinel + add)[is_long], GE.P_LONG, what + ": the long rows (list entries)")
+        GE.same_rows(got, want + sentinel + add, GE.P_SHORT, what)
+        assert gstats == stats, what
 
 
 def scan_on_device(ctx, data):
