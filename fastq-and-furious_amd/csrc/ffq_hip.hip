@@ -19,6 +19,7 @@
 #include "ffq_overlap.h"
 #include "ffq_render.h"
 #include "ffq_merge.h"
+#include "ffq_correct.h"
 #include "ffq_dedup.h"
 #include "ffq_deflate.h"
 #include "ffq_pool.h"

@@ -1091,7 +1091,7 @@ static int chain_back(ffq_stream *s, const Fill &f, const Table &t)
 //     (ffq_dedup_select) -- what follows is on the rows that remain], back, [idx D2H], [gather, col D2H, coff D2H],
 //     [qual D2H, qoff D2H], synchronise
 // and of a round of a pair (pair_chain): [names check], mate 1: front, room for its kept rows (stream_alloc_sel), mate 2: the
-// same, room for the ordinals, [room for the merge], [the mates' overlap], the pair select, [the pair dedup: both tables
+// same, room for the ordinals, [room for the merge], [the mates' overlap], [bases corrected inside it], the pair select, [the pair dedup: both tables
 // compacted in step by the pairs' keys], [the merge of the kept pairs: then what follows is on the rest tables and the rest
 // ordinals], mate 1: back, mate 2: back, ordinals D2H, [merged text D2H], synchronise
 // No rows are copied back from an empty table; a fill without records allocates and launches nothing of the push-down,
@@ -1267,6 +1267,15 @@ struct ffq_pair {
     // duplicate pairs dropped behind the pair select (ffq_pair_set_dedup): the pair's own set, the rows of both mates and the
     // ordinals that remain, the counts summed over the rounds
     DedupStage dedup;
+    // bases corrected inside the overlap, in both fills' device bytes (ffq_pair_set_correct): between the overlap and the pair
+    // select, by the round's insert sizes (merge.insert, which is then allocated without merging too); the six counts of the last
+    // round, the matrix summed over the rounds
+    struct {
+        bool on = false;
+        ffq_correct_rules rules = {};
+        int64_t last[FFQ_CORRECT_COUNTS] = {0, 0, 0, 0, 0, 0};
+        int64_t matrix[FFQ_CORRECT_MATRIX_WORDS] = {0};
+    } correct;
 };
 
 extern "C" int ffq_pair_open(ffq_stream *mate1, ffq_stream *mate2, int pair_filter, int check_names, ffq_pair **out)
@@ -1305,7 +1314,7 @@ extern "C" int ffq_pair_set_overlap(ffq_pair *p, const ffq_overlap_rules *rules)
 {
     if (!p) return fail(FFQ_E_ARG, "ffq_pair_set_overlap: NULL pair");
     if (p->started) return fail(FFQ_E_ARG, "ffq_pair_set_overlap: the walk has begun (call it before the first ffq_pair_next)");
-    if (!rules) { p->overlap.on = p->merge.on = false; return FFQ_OK; }       // (no insert sizes: nothing to merge by)
+    if (!rules) { p->overlap.on = p->merge.on = p->correct.on = false; return FFQ_OK; }       // (no insert sizes: nothing to merge or correct by)
     int rc = overlap_arg("ffq_pair_set_overlap", rules);
     if (rc) return rc;
     ffq_ctx *c = p->c;
@@ -1376,6 +1385,31 @@ extern "C" int ffq_pair_merged_bgzf(ffq_pair *p, const uint8_t **h_bgzf, int64_t
     if (!p->merge.compress) return fail(FFQ_E_ARG, "ffq_pair_merged_bgzf: the pair does not compress its merged reads (ffq_pair_set_compress)");
     *h_bgzf = p->merge.bgz.h; *n_bytes = p->merge.zlast[1];
     if (stats) for (int i = 0; i < FFQ_DEFLATE_COUNTS; i++) stats[i] = p->merge.zlast[i];
+    return FFQ_OK;
+}
+
+// Bases corrected inside the mates' overlap in every round (include/ffq.h, ffq_table_pair_correct), by the round's insert sizes.
+extern "C" int ffq_pair_set_correct(ffq_pair *p, const ffq_correct_rules *rules)
+{
+    if (!p) return fail(FFQ_E_ARG, "ffq_pair_set_correct: NULL pair");
+    if (p->started) return fail(FFQ_E_ARG, "ffq_pair_set_correct: the walk has begun (call it before the first ffq_pair_next)");
+    if (!rules) { p->correct.on = false; return FFQ_OK; }
+    if (!p->overlap.on) return fail(FFQ_E_ARG, "ffq_pair_set_correct: the pair does not analyse overlaps (ffq_pair_set_overlap first)");
+    const int rc = correct_arg("ffq_pair_set_correct", rules);
+    if (rc) return rc;
+    p->correct.rules = *rules;
+    p->correct.on = true;
+    for (int64_t &x : p->correct.matrix) x = 0;
+    return FFQ_OK;
+}
+
+// the last round's six counts, and the corrections of every round so far by kind
+extern "C" int ffq_pair_corrected(ffq_pair *p, int64_t counts[FFQ_CORRECT_COUNTS], int64_t matrix[FFQ_CORRECT_MATRIX_WORDS])
+{
+    if (!p) return fail(FFQ_E_ARG, "ffq_pair_corrected: NULL pair");
+    if (!p->correct.on) return fail(FFQ_E_ARG, "ffq_pair_corrected: the pair does not correct (ffq_pair_set_correct)");
+    if (counts) for (int i = 0; i < FFQ_CORRECT_COUNTS; i++) counts[i] = p->correct.last[i];
+    if (matrix) for (int i = 0; i < FFQ_CORRECT_MATRIX_WORDS; i++) matrix[i] = p->correct.matrix[i];
     return FFQ_OK;
 }
 
@@ -1483,6 +1517,14 @@ static int pair_chain(ffq_pair *p, int64_t m, int64_t *n_out, int64_t *differ)
         rc = stream_grow(p->idx, m, "ffq_pair: no memory for %lld selected pairs", m);
     }
     int32_t *d_insert = nullptr;
+    if (!rc && p->correct.on) {
+        // (the correction needs the insert sizes even where nothing is merged)
+        if (p->merge.insert.cap < m) {
+            HIPCHK(hipStreamSynchronize(c->stream));
+            rc = stream_grow(p->merge.insert, m, "ffq_pair: no memory for %lld insert sizes", m);
+        }
+        d_insert = p->merge.insert.p;
+    }
     if (!rc && p->merge.on) {
         // (the merged text of a pair is shorter than its two records together: header + 2 (n1 + n2 - 1) + 6 bytes)
         const int64_t text_cap = p->m[0].f.n + p->m[1].f.n + 64;
@@ -1501,6 +1543,13 @@ static int pair_chain(ffq_pair *p, int64_t m, int64_t *n_out, int64_t *differ)
     if (!rc && p->overlap.on)
         rc = ffq_table_pair_overlap(c, &v[0], &v[1], m, &p->overlap.rules, const_cast<int64_t *>(v[0].d_table), const_cast<int64_t *>(v[1].d_table),
                                     d_insert, p->overlap.hist.p, 1, p->overlap.last);
+    if (!rc && p->correct.on) {
+        // (both fills' device bytes are edited: the filter, statistics OUT, the render and the merge behind this see the corrected
+        // bytes; statistics IN and the dedup keys were taken by chain_front, and the pinned host copy stays as read)
+        int64_t mat[FFQ_CORRECT_MATRIX_WORDS];
+        rc = ffq_table_pair_correct(c, &v[0], &v[1], m, d_insert, &p->correct.rules, p->correct.last, mat);
+        for (int i = 0; i < FFQ_CORRECT_MATRIX_WORDS && !rc; i++) p->correct.matrix[i] += mat[i];
+    }
     int64_t kept = 0;
     if (!rc) rc = ffq_table_select_pairs(c, &v[0], &v[1], m, bounds, rules[0], rules[1], p->mode, p->m[0].s->b->sel, p->m[1].s->b->sel,
                                          p->idx.d, &kept, p->m[0].s->content.last, p->m[1].s->content.last, p->last_pairs);
@@ -1530,6 +1579,7 @@ extern "C" int ffq_pair_next(ffq_pair *p, int64_t *n_pairs_in, int64_t *n_pairs_
     for (int i = 0; i < FFQ_OVERLAP_COUNTS; i++) p->overlap.last[i] = 0;
     for (int i = 0; i < FFQ_MERGE_COUNTS; i++) p->merge.last[i] = 0;
     for (int64_t &x : p->merge.zlast) x = 0;
+    for (int64_t &x : p->correct.last) x = 0;
     p->last_out = 0;
     p->started = true;
     for (int k = 0; k < 2; k++) pair_clear_last(p->m[k].s);

@@ -799,6 +799,54 @@ extern "C" int ffq_table_pair_merge(ffq_ctx *c, const ffq_table_view *m1, const 
     return FFQ_OK;
 }
 
+// ---- bases corrected inside the mates' overlap (csrc/ffq_correct.h) ---------------------------
+static_assert(CORRECT_COUNTS == FFQ_CORRECT_COUNTS && CORRECT_MATRIX == FFQ_CORRECT_MATRIX_WORDS, "include/ffq.h");
+
+// the rules of a correction call, checked: for the table call and for ffq_pair_set_correct
+static int correct_arg(const char *who, const ffq_correct_rules *r)
+{
+    if (!r) return fail(FFQ_E_ARG, "%s: no rules", who);
+    if (r->bad_quality < 0 || r->bad_quality >= r->good_quality) return fail(FFQ_E_ARG, "%s: 0 <= bad_quality < good_quality", who);
+    if (r->qual_base < 0 || r->qual_base > 255 || r->good_quality > 255 - r->qual_base)
+        return fail(FFQ_E_ARG, "%s: qual_base is 0..255 and qual_base + good_quality at most 255", who);
+    return FFQ_OK;
+}
+
+// THE ONE PLACE where a view's bytes become writable.  A ffq_table_view says `const uint8_t *d_buf` because every other table
+// pass only reads the bytes and edits rows; the correction is the one pass that edits the bytes themselves, and its caller
+// hands it device memory of its own (the stream: its fill's slot) knowing that.
+static uint8_t *correct_writable(const ffq_table_view *m) { return const_cast<uint8_t *>(m->d_buf); }
+
+extern "C" int ffq_table_pair_correct(ffq_ctx *c, const ffq_table_view *m1, const ffq_table_view *m2, int64_t n_pairs,
+                                      const int32_t *d_insert, const ffq_correct_rules *rules, int64_t counts[FFQ_CORRECT_COUNTS],
+                                      int64_t matrix[FFQ_CORRECT_MATRIX_WORDS])
+{
+    static const char *const who = "ffq_table_pair_correct";
+    mark_other(c);
+    int rc = correct_arg(who, rules);
+    if (rc) return rc;
+    if (!c || !counts || n_pairs < 0 || !view_ok(m1, n_pairs) || !view_ok(m2, n_pairs)) return fail(FFQ_E_ARG, "%s: bad argument", who);
+    if (n_pairs > 0 && !d_insert) return fail(FFQ_E_ARG, "%s: no insert sizes (d_insert)", who);
+    if (!aligned({d_insert}, 4)) return fail(FFQ_E_ARG, "%s: d_insert must be 4-byte aligned", who);
+    if ((m1->n_bytes > 0 && !m1->d_buf) || (m2->n_bytes > 0 && !m2->d_buf)) return fail(FFQ_E_ARG, "%s: no buffer to correct the mates in", who);
+    if ((rc = no_pending(c, who))) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    for (int i = 0; i < CORRECT_COUNTS; i++) counts[i] = 0;
+    if (matrix) for (int i = 0; i < CORRECT_MATRIX; i++) matrix[i] = 0;
+    if (n_pairs == 0) return FFQ_OK;
+    hipStream_t st = c->stream;
+    CorrectBlock *blk = nullptr;
+    if ((rc = call_blk_begin(c, &blk))) return rc;
+    const CorrectRules R = {(uint32_t)(rules->qual_base + rules->good_quality), (uint32_t)(rules->qual_base + rules->bad_quality)};
+    hipLaunchKernelGGL(k_pair_correct, dim3(rows_grid(n_pairs, CORRECT_WG / ROWS_G, EDIT_GRID_SHORT)), dim3(CORRECT_WG), 0, st, pair_side(m1),
+                       pair_side(m2), correct_writable(m1), correct_writable(m2), n_pairs, d_insert, R, matrix ? 1 : 0, blk);
+    const CorrectBlock *h = nullptr;
+    if ((rc = call_blk_end(c, &h))) return rc;
+    for (int i = 0; i < CORRECT_COUNTS; i++) counts[i] = (int64_t)h->cnt[i];
+    if (matrix) for (int i = 0; i < CORRECT_MATRIX; i++) matrix[i] = (int64_t)h->matrix[i];
+    return FFQ_OK;
+}
+
 // ---- duplicate reads and pairs (csrc/ffq_dedup.h) -----------------------------------------------
 static_assert(DEDUP_KEY_NONE == FFQ_KEY_NONE && DEDUP_COUNTS == FFQ_DEDUP_COUNTS, "include/ffq.h");
 

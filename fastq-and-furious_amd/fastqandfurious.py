@@ -1625,6 +1625,100 @@ class MergeReport:
         self.pairs_merged = self.bases_merged = self.bytes_merged = self.overlap_positions = self.taken_from_mate2 = 0
 
 
+class CorrectionRules:
+    """When a mismatched base inside the mates' overlap is corrected (include/ffq.h, ffq_table_pair_correct; fastp's values): the
+    other mate's call has a quality of good_quality or more and this one's of bad_quality or less."""
+
+    def __init__(self, good_quality=30, bad_quality=14):
+        if not 0 <= int(bad_quality) < int(good_quality):
+            raise ValueError("0 <= bad_quality < good_quality")
+        if int(good_quality) > 255:
+            raise ValueError("good_quality is at most 255 - qual_base")
+        self.good_quality, self.bad_quality = int(good_quality), int(bad_quality)
+
+
+class CorrectionReport:
+    """What filter_fastq_paired(correction_report=...) fills: pairs_checked (pairs the rule looked at), pairs_corrected (at
+    least one base was), bases_corrected = [in mate 1, in mate 2], mismatches (positions of the overlaps at which the mates
+    disagree, corrected or not) and matrix[class before][class after] (int64[5][4]; classes A C G T, 4 = any other byte), both
+    mates together."""
+
+    def __init__(self):
+        self.pairs_checked = self.pairs_corrected = self.mismatches = 0
+        self.bases_corrected = [0, 0]
+        self.matrix = np.zeros((5, 4), dtype=np.int64)
+
+    def _add_counts(self, counts):
+        self.pairs_checked += counts[0]
+        self.pairs_corrected += counts[1]
+        self.bases_corrected[0] += counts[2]
+        self.bases_corrected[1] += counts[3]
+        self.mismatches += counts[4]
+
+
+def _check_correction(rules, qual_base):
+    if not isinstance(rules, CorrectionRules):
+        raise TypeError("correction must be a CorrectionRules")
+    if not (0 <= int(qual_base) and int(qual_base) + rules.good_quality <= 255):
+        raise ValueError("qual_base + good_quality is at most 255")
+
+
+def _correct_lines(seq1, qual1, seq2, qual2, insert, rules, qual_base):
+    """correct_mates' work: None if the lines and `insert` do not let the pair be looked at, else (seq1, qual1, seq2, qual2,
+    corrected in mate 1, in mate 2, mismatch positions, matrix int64[5][4])."""
+    _check_correction(rules, qual_base)
+    n1, n2 = len(seq1), len(seq2)
+    if insert is None or insert < 0 or len(qual1) != n1 or len(qual2) != n2 or n1 > OverlapRules.MAX_LEN or n2 > OverlapRules.MAX_LEN:
+        return None
+    o = int(insert) - n2
+    if not -n2 < o < n1:
+        return None
+    good, bad = qual_base + rules.good_quality, qual_base + rules.bad_quality
+    a, qa, b, qb = (np.frombuffer(bytes(x), dtype=np.uint8).copy() for x in (seq1, qual1, seq2, qual2))
+    p = np.arange(max(0, o), min(n1, n2 + o))
+    bi = n2 - 1 - (p - o)
+    ca, cb = _BASE_CLASS[a[p]], _BASE_CLASS[b[bi]]
+    mismatch = ~((ca < 4) & (cb < 4) & (ca == 3 - cb))
+    fix2 = mismatch & (qa[p] >= good) & (qb[bi] <= bad) & (ca < 4)
+    fix1 = mismatch & ~fix2 & (qb[bi] >= good) & (qa[p] <= bad) & (cb < 4)
+    matrix = np.zeros((5, 4), dtype=np.int64)
+    np.add.at(matrix, (cb[fix2], 3 - ca[fix2]), 1)
+    np.add.at(matrix, (ca[fix1], 3 - cb[fix1]), 1)
+    # (positions are independent: every right-hand side is of the lines as they came)
+    new_b, new_qb, new_a, new_qa = _COMPLEMENT[a[p[fix2]]], qa[p[fix2]], _COMPLEMENT[b[bi[fix1]]], qb[bi[fix1]]
+    b[bi[fix2]], qb[bi[fix2]], a[p[fix1]], qa[p[fix1]] = new_b, new_qb, new_a, new_qa
+    return (a.tobytes(), qa.tobytes(), b.tobytes(), qb.tobytes(), int(np.count_nonzero(fix1)), int(np.count_nonzero(fix2)),
+            int(np.count_nonzero(mismatch)), matrix)
+
+
+def correct_mates(seq1, qual1, seq2, qual2, insert, rules, qual_base=33):
+    """Mismatched bases inside the overlap of a pair's mates corrected by the surer mate (include/ffq.h states the rule at
+    ffq_table_pair_correct; this is its host statement).  seq / qual: bytes of the four lines as they stand, behind any trim;
+    insert: pair_overlap's; rules: a CorrectionRules.  With o = insert - len(seq2), position p of mate 1 faces byte
+    bi = n2 - 1 - (p - o) of mate 2; where the two do not match (by class, as pair_overlap matches: an N matches nothing) and
+    one quality byte is >= qual_base + good_quality while the other is <= qual_base + bad_quality, the poor mate's base becomes
+    the complement of the sure one -- if that is a base -- and its quality the sure one's.  Returns (seq1, qual1, seq2, qual2,
+    bases corrected in mate 1, in mate 2); the lines unchanged and 0, 0 where the pair is not looked at (insert None or
+    negative, a line pair of two lengths, a mate above OverlapRules.MAX_LEN, or not -n2 < o < n1)."""
+    r = _correct_lines(seq1, qual1, seq2, qual2, insert, rules, qual_base)
+    if r is None:
+        return bytes(seq1), bytes(qual1), bytes(seq2), bytes(qual2), 0, 0
+    return r[:6]
+
+
+def correct_correctable(buf1, pos1, buf2, pos2, insert):
+    """Does the device look at this pair (ffq_table_pair_correct's eligibility)?  merge_mergeable without its question about
+    mate 1's header: both rows' pos2..pos5 inside their buffers and in order with sequence and quality of one length, neither
+    mate above OverlapRules.MAX_LEN bases, insert >= 0 and -n2 < insert - n2 < n1.  Newlines are not looked for."""
+    for buf, pos in ((buf1, pos1), (buf2, pos2)):
+        p2, p3, p4, p5 = pos[2], pos[3], pos[4], pos[5]
+        if not (p2 >= 0 and p4 >= 0 and p2 <= p3 <= len(buf) and p4 <= p5 <= len(buf) and p3 - p2 == p5 - p4
+                and p3 - p2 <= OverlapRules.MAX_LEN):
+            return False
+    n1, n2 = pos1[3] - pos1[2], pos2[3] - pos2[2]
+    return insert is not None and insert >= 0 and -n2 < insert - n2 < n1
+
+
 PairedFilterResult = namedtuple('PairedFilterResult', 'pairs_in pairs_out bases_removed bytes_out1 bytes_out2 dropped')
 
 _PAIR_FILTERS = ("any", "both", "first")
@@ -1659,7 +1753,8 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
                         entrypos: typing.Optional[typing.Callable] = None, overlap=None,
                         overlap_report=None, merged_out: typing.Optional[typing.BinaryIO] = None,
                         merge_report=None, dedup=None, dedup_report=None, poly_g=None, poly_x=None,
-                        poly_report=None, compress=None, compress_report=None) -> PairedFilterResult:
+                        poly_report=None, compress=None, compress_report=None, correction=None,
+                        correction_report=None) -> PairedFilterResult:
     """filter_fastq for paired-end files: the i-th records of `fh1` and `fh2` are mates, and a pair is written or dropped
     TOGETHER, so that `fh_out1` and `fh_out2` stay record for record in step (`cutadapt -q 20 -a ... -A ... -m 30:20
     --pair-filter=any -o out1 -p out2 in1 in2`).  Every record is trimmed as filter_fastq trims it -- quality_cutoff for both
@@ -1710,7 +1805,13 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
     the order is quality, poly-G, adapter, poly-X, overlap, filter, so the overlap and the merge see the rows as the per-mate
     trims left them (fastp runs its poly-X behind its overlap trim: a departure).  poly_report: a PolyReport, both mates added
     together.
-    Not done: interleaved input or output, base correction inside the overlap of mates that are not merged.
+    correction: a CorrectionRules (needs `overlap`; `fastp --correction`); behind the overlap and in front of the filters, every
+    position of a pair's overlap at which the mates disagree, one call sure and the other poor, has the poor base and quality
+    replaced (correct_correctable, correct_mates).  The order is quality, poly-G, adapter, poly-X, overlap, correct, filter,
+    dedup, merge: `before` and the dedup keys are of the records as read; the filters, `after`, the merge and everything
+    written see the corrected bytes.  correction_report: a CorrectionReport (needs `correction`), filled on either route with
+    the same numbers.
+    Not done: interleaved input or output.
     compress / compress_report: filter_fastq's, over `fh_out1`, `fh_out2` and `merged_out`: each is written as a BGZF file of
     its own, each mate's text deflated by its stream and the merged text by the pair (ffq_pair_set_compress); the report sums
     over the three."""
@@ -1726,6 +1827,16 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
         raise ValueError("merged_out needs overlap")
     if merge_report is not None and merged_out is None:
         raise ValueError("merge_report needs merged_out")
+    if correction is not None and overlap is None:
+        raise ValueError("correction needs overlap")
+    if correction_report is not None and correction is None:
+        raise ValueError("correction_report needs correction")
+    if correction is not None:
+        _check_correction(correction, qual_base)
+    crep = CorrectionReport()
+    if correction_report is not None:
+        correction_report.__dict__.update(crep.__dict__)
+        crep = correction_report
     _check_dedup(dedup, dedup_report)
     hd = _HostDedup(dedup, dedup_report) if dedup is not None else None
     mrep = MergeReport()
@@ -1776,6 +1887,8 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
             ps = _hip.PairStream(sts[0], sts[1], pair_filter, check_names)
             if overlap is not None:
                 ps.set_overlap(overlap)
+            if correction is not None:
+                ps.set_correct(correction, qual_base)
             if merged_out is not None:
                 ps.set_merge()
                 if compress is not None:
@@ -1806,6 +1919,8 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
                     orep.bases_removed[0] += oc[3]
                     orep.bases_removed[1] += oc[4]
                     removed += oc[3] + oc[4]
+                if correction is not None:
+                    crep._add_counts(ps.corrected()[0])
                 for k, (plan, st) in enumerate(zip(plans, sts)):
                     nb, _rendered, cut = plan.drain(st, outs[k])
                     n_bytes[k] += nb
@@ -1825,6 +1940,8 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
             end_outputs()
             if overlap is not None:
                 orep.insert_hist = ps.overlap()[1]
+            if correction is not None:
+                crep.matrix = ps.corrected()[1]
             if hd is not None:
                 hd.report._from_counts(ps.dedup_counts())
         finally:
@@ -1867,6 +1984,30 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
             out.append(r[:2] + (r[2] + n - c, r[3], (pos[0], pos[1], pos[2], pos[2] + c, pos[4], pos[4] + c)) + r[5:])
         orep.pairs_trimmed += 1
         return out[0], out[1], insert
+
+    def corrected(r1, r2, insert):
+        """the two records with the correction applied, and the report filled: a mate with a corrected base continues as a
+        private buffer -- its record cut out and patched -- with its positions shifted; everything behind (verdict, text,
+        merged_text) takes buffer and positions from the record and sees the corrected bytes"""
+        (buf1, pos1), (buf2, pos2) = r1[3:5], r2[3:5]
+        if not correct_correctable(buf1, pos1, buf2, pos2, insert):
+            return r1, r2
+        lines = _correct_lines(buf1[pos1[2]:pos1[3]], buf1[pos1[4]:pos1[5]], buf2[pos2[2]:pos2[3]], buf2[pos2[4]:pos2[5]], insert,
+                               correction, qual_base)
+        c1, c2, mismatches, matrix = lines[4:]
+        crep._add_counts((1, int(c1 + c2 > 0), c1, c2, mismatches))
+        crep.matrix += matrix
+        out = []
+        for r, n_fixed, seq, qual in ((r1, c1, lines[0], lines[1]), (r2, c2, lines[2], lines[3])):
+            if n_fixed:
+                buf, pos = r[3], r[4]
+                lo, hi = pos[0], max(pos[1], pos[3], pos[5])
+                own = bytearray(buf[lo:hi])
+                own[pos[2] - lo:pos[3] - lo] = seq
+                own[pos[4] - lo:pos[5] - lo] = qual
+                r = r[:3] + (bytes(own), tuple(x - lo for x in pos)) + r[5:]
+            out.append(r)
+        return out[0], out[1]
 
     def merged_text(r1, r2, insert):
         """the pair as one record (None: it is not merged), and the report filled; behind the cut, with the insert size found
@@ -1915,6 +2056,8 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
         insert = None
         if overlap is not None:
             r1, r2, insert = overlap_cut(r1, r2)
+            if correction is not None:
+                r1, r2 = corrected(r1, r2, insert)
         v1, v2 = plans[0].verdict(r1[3], r1[4]), plans[1].verdict(r2[3], r2[4])
         removed += r1[2] + r2[2]
         if _pair_dropped(pair_filter, v1, v2):

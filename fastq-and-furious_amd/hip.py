@@ -50,7 +50,7 @@ def _add(add, sentinel):
     return (-1 if sentinel else 0) if add is None else add
 
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 OK = 0
 E_NODEVICE, E_HIP, E_ARG, E_NOMEM, E_TABLE_FULL, E_INTERNAL, E_TIMEOUT = -1, -2, -3, -4, -5, -6, -7
 STAGE_NONE, STAGE_HANDOFF, STAGE_SCAN, STAGE_GATHER = 0, 1, 2, 3      # FFQ_SHARD_STAGE_*
@@ -104,6 +104,7 @@ SYMBOLS = (
     "ffq_pair_open", "ffq_pair_wants", "ffq_pair_next", "ffq_pair_rows", "ffq_pair_selected", "ffq_pair_close",
     "ffq_table_pair_overlap", "ffq_pair_set_overlap", "ffq_pair_overlap",
     "ffq_table_pair_merge", "ffq_pair_set_merge", "ffq_pair_merged",
+    "ffq_table_pair_correct", "ffq_pair_set_correct", "ffq_pair_corrected",
     "ffq_table_seq_keys", "ffq_seq_key_host", "ffq_pair_key_host", "ffq_dedup_create", "ffq_dedup_destroy", "ffq_dedup_select",
     "ffq_stream_set_dedup", "ffq_stream_dedup_counts", "ffq_pair_set_dedup", "ffq_pair_dedup_counts",
     "ffq_table_trim_poly", "ffq_stream_set_poly", "ffq_stream_poly_trimmed",
@@ -163,6 +164,23 @@ OVERLAP_MAX_LEN = 512                            # FFQ_OVERLAP_MAX_LEN: mates ab
 OVERLAP_HIST_WORDS = 2 * OVERLAP_MAX_LEN + 1     # insert sizes 0..1024
 OVERLAP_COUNTS = 6           # pairs analysed, with an overlap, changed, bases removed from mate 1, from mate 2, pairs not analysed
 MERGE_COUNTS = 6             # FFQ_MERGE_COUNTS: pairs merged, not merged, bytes of text, bases of the merged reads, positions inside overlaps, of those taken from mate 2
+
+
+CORRECT_COUNTS = 6           # FFQ_CORRECT_COUNTS: pairs looked at, with a correction, bases corrected in mate 1, in mate 2, mismatch positions, pairs not looked at
+CORRECT_MATRIX_WORDS = 20    # FFQ_CORRECT_MATRIX_WORDS: corrections by (class before 0..4, class after 0..3)
+
+
+class CorrectRulesStruct(ctypes.Structure):
+    """struct ffq_correct_rules (include/ffq.h)."""
+    _fields_ = [("good_quality", ctypes.c_int32), ("bad_quality", ctypes.c_int32), ("qual_base", ctypes.c_int32)]
+
+
+def correct_rules_struct(rules, qual_base=33):
+    """What the library takes for `rules`: None or a CorrectRulesStruct as it is, or anything with good_quality and bad_quality as
+    attributes (fastqandfurious.CorrectionRules) and `qual_base` beside it."""
+    if rules is None or isinstance(rules, CorrectRulesStruct):
+        return rules
+    return CorrectRulesStruct(int(rules.good_quality), int(rules.bad_quality), int(qual_base))
 
 
 class OverlapRulesStruct(ctypes.Structure):
@@ -434,6 +452,9 @@ def lib():
         L.ffq_pair_overlap.argtypes = [vp, P(i64), vp, i64]
         L.ffq_table_pair_merge.argtypes = [vp, P(TableView), P(TableView), i64, vp, vp, vp, i64, vp, vp, vp, vp, P(i64), P(i64)]
         L.ffq_pair_set_merge.argtypes = [vp, i32]
+        L.ffq_table_pair_correct.argtypes = [vp, P(TableView), P(TableView), i64, vp, P(CorrectRulesStruct), P(i64), P(i64)]
+        L.ffq_pair_set_correct.argtypes = [vp, P(CorrectRulesStruct)]
+        L.ffq_pair_corrected.argtypes = [vp, P(i64), P(i64)]
         L.ffq_pair_merged.argtypes = [vp, P(vp), P(i64), P(i64)]
         L.ffq_pair_close.restype = None
         L.ffq_table_seq_keys.argtypes = [vp, vp, i64, i32, i64, vp, i64, vp, P(i64)]
@@ -866,6 +887,22 @@ class Context:
                                         ctypes.c_void_p(d_rest_ord) if d_rest_ord else None, ctypes.byref(n_rest), counts)
         check(rc, allow=(E_TABLE_FULL,))
         return rc, n_rest.value, [int(x) for x in counts]
+
+    def table_pair_correct(self, mate1, mate2, n_pairs, d_insert, rules, qual_base=33, matrix=True):
+        """Mismatched bases inside the overlap of the mates of every pair of two device tables corrected IN THE BUFFERS
+        (ffq_table_pair_correct; include/ffq.h states the rule, fastqandfurious.correct_mates is its host statement).  mate1 /
+        mate2: TableViews whose d_buf is written through; the rows of different pairs must not share bytes.  d_insert: int32
+        insert sizes (table_pair_overlap's), a raw device pointer; rules: a CorrectRulesStruct, or anything with good_quality
+        and bad_quality (then `qual_base` beside it).  Returns (counts, matrix): counts = [pairs looked at, with a correction,
+        bases corrected in mate 1, in mate 2, mismatch positions, pairs not looked at]; matrix int64[5][4] by (class before,
+        class after), None without `matrix`."""
+        r = correct_rules_struct(rules, qual_base)
+        counts = (ctypes.c_int64 * CORRECT_COUNTS)()
+        mat = (ctypes.c_int64 * CORRECT_MATRIX_WORDS)() if matrix else None
+        check(lib().ffq_table_pair_correct(self.handle, ctypes.byref(mate1), ctypes.byref(mate2), int(n_pairs),
+                                           ctypes.c_void_p(d_insert) if d_insert else None, None if r is None else ctypes.byref(r),
+                                           counts, mat))
+        return [int(x) for x in counts], (np.array(mat, dtype=np.int64).reshape(5, 4) if matrix else None)
 
     def table_seq_keys(self, d_buf, n_bytes, d_table, n_rows, d_keys, sentinel=True, add=None):
         """The 64-bit sequence key of every row of a device table (ffq_table_seq_keys; include/ffq.h states the rule,
@@ -1562,7 +1599,7 @@ class PushStream(_Stream):
 class PairStream:
     """Two streams whose i-th records are mates, walked in lockstep (ffq_pair; include/ffq.h): mate1 / mate2 are fresh
     FileStreams or PushStreams of one context, configured beforehand (set_trim, set_adapter, set_filter without a column,
-    set_content, set_stats, set_render); set_overlap() and set_merge() here, before the first step.  Iterating yields (n_in, n_out,
+    set_content, set_stats, set_render); set_overlap(), set_correct() and set_merge() here, before the first step.  Iterating yields (n_in, n_out,
     end_state, err_mate, err_offset) per ROUND; after each step the streams' own accessors (rendered(), trimmed(), adapter_trimmed(), filter_counts(), stats()) report that
     mate's share of the round.  PushStream mates are pumped here whenever the walk takes a new chunk of theirs.  The
     iteration ends behind the first end_state that is not END_REFILL (END_OK, a mate's END_ERR_*, END_ERR_PAIR_COUNT,
@@ -1652,6 +1689,22 @@ class PairStream:
         set_overlap).  Those pairs leave the two ordinary outputs: rows(), selected()'s index and the mates' rendered() are
         then the kept pairs that were not merged, n_out their number; merged() has the others.  Before the first step only."""
         check(lib().ffq_pair_set_merge(self._h, 1 if on else 0))
+
+    def set_correct(self, rules, qual_base=33):
+        """Every round corrects mismatched bases inside the mates' overlap in both fills' device bytes, between the overlap and
+        the filter (ffq_pair_set_correct; needs set_overlap; rules as Context.table_pair_correct takes them, None: off).  The
+        filter, statistics OUT, rendered() and merged() see the corrected bytes; rows()' fill stays as read.  Before the first
+        step only."""
+        r = correct_rules_struct(rules, qual_base)
+        check(lib().ffq_pair_set_correct(self._h, None if r is None else ctypes.byref(r)))
+
+    def corrected(self):
+        """(counts, matrix): the six counts of the round just yielded (Context.table_pair_correct's) and the corrections of
+        every round so far as int64[5][4] by (class before, class after) (ffq_pair_corrected)."""
+        counts = (ctypes.c_int64 * CORRECT_COUNTS)()
+        mat = (ctypes.c_int64 * CORRECT_MATRIX_WORDS)()
+        check(lib().ffq_pair_corrected(self._h, counts, mat))
+        return [int(x) for x in counts], np.array(mat, dtype=np.int64).reshape(5, 4)
 
     def set_dedup(self, drop=True, expected_keys=0, max_bytes=0):
         """Duplicate PAIRS dropped behind the filter and in front of the merge (ffq_pair_set_dedup; before the first step;

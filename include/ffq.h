@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FFQ_ABI_VERSION 9
+#define FFQ_ABI_VERSION 10
 
 /* scanner status codes -- identical to the reference's module constants
  * (_fastqandfurious.c:7-15,254-262; fastqandfurious.py:19-27)             */
@@ -540,8 +540,8 @@ int ffq_table_pair_names(ffq_ctx *ctx, const ffq_table_view *m1, const ffq_table
  * one row changed, [3] bases removed from mate 1, [4] from mate 2, [5] pairs not analysed; [0] + [5] == n_pairs.
  * n_pairs == 0 is valid.  One host wait.  FFQ_E_ARG: a field out of range, rules NULL, a scan pending on the context, a
  * misaligned table, d_insert or d_hist, d_buf NULL with n_bytes > 0.  Run it behind the per-mate trims and in front of
- * ffq_table_select_pairs.  Merging the mates by `insert`: ffq_table_pair_merge below.  Not done: base correction inside the
- * overlap of mates that are not merged, indels, reads above FFQ_OVERLAP_MAX_LEN bases.                                */
+ * ffq_table_select_pairs.  Merging the mates by `insert`: ffq_table_pair_merge below; correcting bases inside the overlap:
+ * ffq_table_pair_correct.  Not done: indels, reads above FFQ_OVERLAP_MAX_LEN bases.                                    */
 typedef struct ffq_overlap_rules {
     int32_t min_overlap;     /* 1..FFQ_OVERLAP_MAX_LEN; fastp's default 30 */
     int32_t max_diff;        /* 0..FFQ_OVERLAP_MAX_LEN; fastp's default 5  */
@@ -644,12 +644,58 @@ void ffq_bgzf_eof_block(uint8_t out[28]);
  * overlaps, [5] of those, positions taken from mate 2; [0] + [1] == n_pairs.  FFQ_E_TABLE_FULL: text_cap is smaller than
  * the total -- counts[2] holds the need, d_off and the rest tables are written, d_text is not touched.  FFQ_E_ARG: d_insert
  * NULL, a misaligned table or array, a scan pending on the context, d_buf NULL with n_bytes > 0.  n_pairs == 0 is valid.
- * One host wait.  Not done: base correction of mates that are not merged.                                              */
+ * One host wait.  Correcting the mates' bases in place, for pairs that are not merged too: ffq_table_pair_correct.      */
 #define FFQ_MERGE_COUNTS 6
 int ffq_table_pair_merge(ffq_ctx *ctx, const ffq_table_view *m1, const ffq_table_view *m2, int64_t n_pairs,
                          const int32_t *d_insert, const int64_t *d_ord, uint8_t *d_text, int64_t text_cap, int64_t *d_off,
                          int64_t *d_rest1, int64_t *d_rest2, int64_t *d_rest_ord, int64_t *n_rest,
                          int64_t counts[FFQ_MERGE_COUNTS]);
+
+/* Mismatched bases inside the overlap of a pair's mates corrected IN THE BUFFERS (`fastp --correction`): where both mates read
+ * the same position and disagree, and one call is sure while the other is poor, the poor base and its quality are replaced by
+ * the sure ones.  THE RULE STATED HERE IS THE SPECIFICATION; fastqandfurious.correct_mates is its host statement.  Run it behind
+ * ffq_table_pair_overlap and in front of ffq_table_select_pairs.  For pair k, with ins = d_insert[k], a / qa = mate 1's
+ * sequence and quality (n1 bytes), b / qb = mate 2's (n2 bytes) -- all four as the rows stand NOW -- and o = ins - n2, the pair
+ * is LOOKED AT if both rows are eligible as ffq_table_pair_merge asks of pos2..pos5 (inside the buffer and in order, the two
+ * lines of one length, no line with bytes in it at the sentinel's coordinate 0; the header is not asked about), n1 and
+ * n2 <= FFQ_OVERLAP_MAX_LEN, ins >= 0 and -n2 < o < n1.  Every other pair is left untouched and counted as not looked at.  Then
+ *     G = qual_base + good_quality;  B = qual_base + bad_quality            (bytes; qualities are compared unsigned)
+ *     for p in [max(0, o), min(n1, n2 + o)):
+ *         bi = n2 - 1 - (p - o);  ca = cls(a[p]);  cb = cls(b[bi])          (cls: the classes of ffq_table_stats)
+ *         if ca < 4 and cb < 4 and ca == 3 - cb: nothing                    (ffq_table_pair_overlap's MATCH)
+ *         else, a MISMATCH POSITION:
+ *             if   qa[p]  >= G and qb[bi] <= B and ca < 4:  b[bi] = comp(a[p]);  qb[bi] = qa[p]      (mate 2 corrected)
+ *             elif qb[bi] >= G and qa[p]  <= B and cb < 4:  a[p]  = comp(b[bi]); qa[p]  = qb[bi]     (mate 1 corrected)
+ *     comp: ffq_table_pair_merge's (A<->T, C<->G, the case kept)
+ * An N is never written over a base; an N with a poor quality IS replaced by a sure base.  o is taken against the CURRENT n2, so
+ * the result is the same whether ffq_table_pair_overlap ran with trim 1 or 0 (behind the cut n2' = ins, o' = 0, and bi names the
+ * same byte: ffq_table_pair_merge's argument).  fastp's gate "more than 5 differences: skip the pair" needs no word here: a
+ * pair has an insert size only if its mismatches are <= max_diff.  "\n" is not looked for: bytes are taken as they are, as in
+ * the merge.  The pass is IDEMPOTENT (a corrected position matches: a second run changes nothing and corrects 0), and the
+ * positions of a pair are independent of each other.  TWO DIFFERENCES from fastp: matching is by class, so N never matches
+ * (fastp compares bytes); fastp's per-read "corrected" flags are not kept.
+ * CONTRACT.  Only the bytes named above are written -- one byte at a time, never a block around them.  No byte outside either
+ * [d_buf, d_buf + n_bytes), and none outside the two rows' checked sequence and quality ranges, is read or written, whatever
+ * d_insert holds.  UNLIKE EVERY OTHER TABLE CALL, THE ROWS OF DIFFERENT PAIRS MUST NOT SHARE BYTES: pairs are corrected
+ * concurrently, and a byte two rows name would be read by one pair while the other rewrites it.  (The rows of a scanned fill
+ * never do.)  m1->d_buf / m2->d_buf are WRITTEN through, although the view declares them const: they must be device memory the
+ * caller may modify.
+ * counts: [0] pairs looked at, [1] pairs with at least one correction, [2] bases corrected in mate 1, [3] in mate 2, [4]
+ * mismatch positions met, [5] pairs not looked at; [0] + [5] == n_pairs.  matrix (NULL: not wanted):
+ * matrix[4 * (class before, 0..4) + (class after, 0..3)] = corrections of that kind, both mates together.  n_pairs == 0 is
+ * valid.  One host wait.  FFQ_E_ARG: rules NULL or out of range (0 <= bad_quality < good_quality, qual_base 0..255,
+ * qual_base + good_quality <= 255), d_insert NULL or misaligned, a misaligned table, a scan pending on the context, d_buf NULL
+ * with n_bytes > 0.  Not done: indels, reads above FFQ_OVERLAP_MAX_LEN bases.                                            */
+typedef struct ffq_correct_rules {
+    int32_t good_quality;    /* a call at or above it is sure; fastp's 30 */
+    int32_t bad_quality;     /* a call at or below it is poor; fastp's 14 */
+    int32_t qual_base;       /* 33 or 64 */
+} ffq_correct_rules;
+#define FFQ_CORRECT_COUNTS 6
+#define FFQ_CORRECT_MATRIX_WORDS 20
+int ffq_table_pair_correct(ffq_ctx *ctx, const ffq_table_view *m1, const ffq_table_view *m2, int64_t n_pairs,
+                           const int32_t *d_insert, const ffq_correct_rules *rules, int64_t counts[FFQ_CORRECT_COUNTS],
+                           int64_t matrix[FFQ_CORRECT_MATRIX_WORDS]);
 
 /* ---- duplicate reads and pairs: sequence keys, the first copy wins (`fastp --dedup`, clumpify, czid-dedup) ---------------
  * There is no reference implementation of this: THE RULE STATED HERE IS THE SPECIFICATION.  fastqandfurious.seq_key and
@@ -979,7 +1025,16 @@ int  ffq_stream_push(ffq_stream *s, int64_t n, int eof);
  * keys with both tables compacted in step.  *n_pairs_out, ffq_pair_rows and h_index follow it; pairs[0] of
  * ffq_pair_selected keeps meaning "pairs the filter kept".  ffq_pair_dedup_counts: as ffq_stream_dedup_counts, in pairs,
  * over every round so far.
- * Not done: interleaved input or output, base correction of mates that are not merged, paired readfastq_iter_range.   */
+ * ffq_pair_set_correct (before the first ffq_pair_next only; FFQ_E_ARG afterwards, for rules out of range and without
+ * ffq_pair_set_overlap; NULL switches it off, as does ffq_pair_set_overlap(NULL)): every round runs ffq_table_pair_correct on
+ * both fills' device bytes, between the overlap and ffq_table_select_pairs, with the insert sizes the round's overlap pass
+ * found.  The order of a round is then quality, poly-G, adapter, poly-X, overlap, CORRECT, filter, dedup, merge.  Statistics IN
+ * and the dedup keys are taken in front of the correction, on the bytes as read; the content filter, statistics OUT, the
+ * render, the merge and the deflate see the corrected bytes.  ffq_pair_rows' h_bytes remain the bytes AS READ (the pinned
+ * host copy is not corrected): a caller that cuts records from them itself does not see the corrections -- the rendered text
+ * does.  ffq_pair_corrected: counts (NULL: not wanted) = the six counts of the last round, matrix (NULL: not wanted) = the
+ * corrections of every round so far by kind, as ffq_table_pair_correct lays them out.  FFQ_E_ARG without ffq_pair_set_correct.
+ * Not done: interleaved input or output, paired readfastq_iter_range.                                                  */
 typedef struct ffq_pair ffq_pair;
 int  ffq_pair_open(ffq_stream *mate1, ffq_stream *mate2, int pair_filter, int check_names, ffq_pair **out);
 int  ffq_pair_wants(ffq_pair *p);
@@ -994,6 +1049,8 @@ int  ffq_pair_set_compress(ffq_pair *p, int mode);
 int  ffq_pair_merged_bgzf(ffq_pair *p, const uint8_t **h_bgzf, int64_t *n_bytes, int64_t stats[FFQ_DEFLATE_COUNTS]);
 int  ffq_pair_set_dedup(ffq_pair *p, int drop, int64_t expected_keys, int64_t max_bytes);
 int  ffq_pair_dedup_counts(ffq_pair *p, int64_t counts[FFQ_DEDUP_COUNTS]);
+int  ffq_pair_set_correct(ffq_pair *p, const ffq_correct_rules *rules);
+int  ffq_pair_corrected(ffq_pair *p, int64_t counts[FFQ_CORRECT_COUNTS], int64_t matrix[FFQ_CORRECT_MATRIX_WORDS]);
 void ffq_pair_close(ffq_pair *p);
 
 /* Bytes [pos, pos + n_bytes) of the file behind fd into device memory (read(), fastqandfurious.py:30-36, for a range
