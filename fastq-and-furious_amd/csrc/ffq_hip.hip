@@ -12,6 +12,7 @@
 #include "ffq_trim.h"
 #include "ffq_adapter.h"
 #include "ffq_poly.h"
+#include "ffq_ends.h"
 #include "ffq_stats.h"
 #include "ffq_filter.h"
 #include "ffq_compact.h"

@@ -172,6 +172,8 @@ struct ffq_stream {
     int last_path = -1;                 // ffq_scan_result.path of the last fill's scan
     // statistics of every fill's table, summed over the fills on the device (ffq_stream_set_stats): the IN block, the OUT block
     struct { int which = 0, base = 33, cycles = 0; DevBuf<uint64_t> d; } stats;
+    // fixed trims and sliding-window cutting of every fill's table, in front of every other trim (ffq_stream_set_ends)
+    struct { bool on = false; ffq_ends_rules rules = {}; int64_t last[3] = {0, 0, 0}; } ends;
     // quality trimming of every fill's table, in front of the filter (ffq_stream_set_trim)
     struct { bool on = false; int base = 33, front = 0, back = 0; int64_t last[3] = {0, 0, 0}; } trim;
     // 3' adapter trimming of every fill's table, behind the quality trim and in front of the filter (ffq_stream_set_adapter)
@@ -839,6 +841,29 @@ extern "C" int ffq_stream_adapter_trimmed(ffq_stream *s, int64_t stats[3])
     return FFQ_OK;
 }
 
+// Fixed trims and sliding-window cutting in the stream: every fill's table goes through ffq_table_trim_ends in place on the
+// device, behind the statistics IN and in front of the quality trim and every trim behind that (fastp's order).  Per mate, in
+// front of a pair's overlap.  The other rules are ffq_stream_set_trim's.
+extern "C" int ffq_stream_set_ends(ffq_stream *s, const ffq_ends_rules *rules)
+{
+    if (!s) return fail(FFQ_E_ARG, "ffq_stream_set_ends: NULL stream");
+    int rc = ends_arg("ffq_stream_set_ends", rules, nullptr);
+    if (!rc) rc = stream_settable(s, "ffq_stream_set_ends", DECODE_UNTRIMMED, true);
+    if (rc) return rc;
+    s->ends.on = true;
+    s->ends.rules = *rules;
+    return FFQ_OK;
+}
+
+// {rows changed, bases removed, rows skipped} by the ends step of the fill ffq_stream_next has just returned
+extern "C" int ffq_stream_ends_trimmed(ffq_stream *s, int64_t stats[3])
+{
+    if (!s || !stats) return fail(FFQ_E_ARG, "ffq_stream_ends_trimmed: NULL argument");
+    if (!s->ends.on) return fail(FFQ_E_ARG, "ffq_stream_ends_trimmed: the stream trims no ends (ffq_stream_set_ends)");
+    for (int i = 0; i < 3; i++) stats[i] = s->ends.last[i];
+    return FFQ_OK;
+}
+
 // Poly-tail trimming in the stream: every fill's table goes through ffq_table_trim_poly in place on the device -- poly-G behind
 // the quality trim and in front of the adapter trim (the G tail behind an adapter spoils the adapter match), poly-X behind the
 // adapter trim.  Per mate, in front of a pair's overlap (fastp runs poly-X behind its overlap trim: a departure).  The other
@@ -1047,7 +1072,7 @@ static int stream_scan(ffq_stream *s, const Fill &f, ffq_scan_result *res)
 }
 
 // ---- the two ends of a mate's chain (a fill of a single stream, either mate of a round of a pair).  front: [keys], [stats IN],
-// [quality trim], [poly-G], [adapter], [poly-X] on the `n` scanned rows at `rows`, which the trims edit in place
+// [ends], [quality trim], [poly-G], [adapter], [poly-X] on the `n` scanned rows at `rows`, which the trims edit in place
 static int chain_front(ffq_stream *s, const Fill &f, int64_t *rows, int64_t n)
 {
     int rc = FFQ_OK;
@@ -1057,6 +1082,8 @@ static int chain_front(ffq_stream *s, const Fill &f, int64_t *rows, int64_t n)
     }
     if (!rc && (s->stats.which & FFQ_STATS_IN))
         rc = ffq_table_stats(s->c, f.d_buf, f.n, 0, f.add, rows, n, s->stats.base, s->stats.cycles, 1, stream_stats_block(s, FFQ_STATS_IN), nullptr);
+    if (!rc && s->ends.on)          // (in front of every other trim: fastp's order)
+        rc = ffq_table_trim_ends(s->c, f.d_buf, f.n, 0, f.add, rows, n, &s->ends.rules, rows, s->ends.last);
     if (!rc && s->trim.on)
         rc = ffq_table_trim_quality(s->c, f.d_buf, f.n, 0, f.add, rows, n, s->trim.base, s->trim.front, s->trim.back, rows, s->trim.last);
     if (!rc && s->poly.g)           // (in front of the adapter: the G tail behind an adapter spoils its match)
@@ -1085,7 +1112,7 @@ static int chain_back(ffq_stream *s, const Fill &f, const Table &t)
 // dropped record costs the host nothing, doc/user-guide.rst:153-180); what follows is written once, for either table.
 // This is the one place that states the order of a fill's work on the scan stream, in every configuration:
 //     carry H2D, wait copied[0], wait copied[1], scan, front (the keys of the dedup first, on the rows as scanned; then
-//     [stats IN], [quality trim], [poly-G], [adapter], [poly-X]), [select:
+//     [stats IN], [ends], [quality trim], [poly-G], [adapter], [poly-X]), [select:
 //     by length, or -- content rules -- by length and content (ffq_table_select_reads), on the rows as the trims left them],
 //     [dedup: the kept rows entered into the stream's set by their keys and the select's ordinals, the first copies kept
 //     (ffq_dedup_select) -- what follows is on the rows that remain], back, [idx D2H], [gather, col D2H, coff D2H],
@@ -1446,7 +1473,7 @@ extern "C" int ffq_pair_wants(ffq_pair *p) { return p && !p->failed ? walk_wants
 // what the per-stream accessors report for a round: zero until the round's chain says otherwise
 static void pair_clear_last(ffq_stream *s)
 {
-    for (int i = 0; i < 3; i++) s->trim.last[i] = s->adapter.last[i] = s->poly.last_g[i] = s->poly.last_x[i] = s->render.last[i] = 0;
+    for (int i = 0; i < 3; i++) s->ends.last[i] = s->trim.last[i] = s->adapter.last[i] = s->poly.last_g[i] = s->poly.last_x[i] = s->render.last[i] = 0;
     for (int64_t &x : s->compress.last) x = 0;
     for (int i = 0; i < FFQ_FILTER_COUNTS; i++) s->content.last[i] = 0;
     s->filter.scanned = 0; s->filter.col_bytes = 0;

@@ -252,7 +252,7 @@ extern "C" int ffq_table_gather_column(ffq_ctx *c, const uint8_t *d_buf, int64_t
     return FFQ_OK;
 }
 
-// ---- the table passes on csrc/ffq_rows.h: quality trim, adapter trim, poly tails, statistics (ffq_trim.h, ffq_adapter.h, ffq_poly.h, ffq_stats.h) ----
+// ---- the table passes on csrc/ffq_rows.h: quality trim, adapter trim, poly tails, ends, statistics (ffq_trim.h, ffq_adapter.h, ffq_poly.h, ffq_ends.h, ffq_stats.h) ----
 // Workgroups of a pass's launches, each capped: they stride over what there is.  The short rows' launch has WG / ROWS_G rows
 // per workgroup and step; the long rows' launches have a wave per row, and as the list's length is known on the device only,
 // they are sized by the table.
@@ -383,6 +383,44 @@ extern "C" int ffq_table_trim_poly(ffq_ctx *c, const uint8_t *d_buf, int64_t n_b
                        sentinel ? 1 : 0, add, d_table, n_rows, base, min_len, d_out, c->rows_list, blk);
     hipLaunchKernelGGL(k_poly_long, dim3(rows_grid(n_rows, POLY_WG / 64, EDIT_GRID_LONG)), dim3(POLY_WG), 0, st, d_buf, n_bytes,
                        sentinel ? 1 : 0, add, d_table, base, min_len, d_out, (const int64_t *)c->rows_list, blk);
+    return rows_end(c, stats);
+}
+
+// the rules of an ends call, checked, as the kernels take them: for the table call and for ffq_stream_set_ends
+static_assert(ENDS_WINDOW_MAX == 64 && ENDS_QUALITY_LO == 1 && ENDS_QUALITY_HI == 93, "include/ffq.h");
+static int ends_arg(const char *who, const ffq_ends_rules *r, EndsRules *R)
+{
+    if (!r) return fail(FFQ_E_ARG, "%s: NULL rules", who);
+    if (r->trim_front < 0 || r->trim_tail < 0 || r->keep_len < 0) return fail(FFQ_E_ARG, "%s: trim_front, trim_tail and keep_len are >= 0", who);
+    if (r->qual_base < 0 || r->qual_base > 255) return fail(FFQ_E_ARG, "%s: qual_base is 0..255", who);
+    const EndsStage st[3] = {{r->front_window, r->front_quality}, {r->right_window, r->right_quality}, {r->tail_window, r->tail_quality}};
+    for (const EndsStage &e : st) {
+        if (e.window < 0 || e.window > ENDS_WINDOW_MAX) return fail(FFQ_E_ARG, "%s: a window is 0..%d", who, ENDS_WINDOW_MAX);
+        if (e.window > 0 && (e.quality < ENDS_QUALITY_LO || e.quality > ENDS_QUALITY_HI))
+            return fail(FFQ_E_ARG, "%s: the quality of a window is %d..%d", who, ENDS_QUALITY_LO, ENDS_QUALITY_HI);
+    }
+    if (!r->trim_front && !r->trim_tail && !r->keep_len && !st[0].window && !st[1].window && !st[2].window)
+        return fail(FFQ_E_ARG, "%s: every rule is off", who);
+    if (R) *R = EndsRules{r->trim_front, r->trim_tail, r->keep_len, r->qual_base, st[0], st[1], st[2]};
+    return FFQ_OK;
+}
+
+extern "C" int ffq_table_trim_ends(ffq_ctx *c, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
+                                   const int64_t *d_table, int64_t n_rows, const ffq_ends_rules *rules, int64_t *d_out, int64_t stats[3])
+{
+    mark_other(c);
+    EndsRules R;
+    int rc = ends_arg("ffq_table_trim_ends", rules, &R);
+    RowsBlock *blk = nullptr;
+    if (!rc) rc = rows_begin(c, "ffq_table_trim_ends", stats != nullptr, d_buf, n_bytes, d_table, n_rows, d_out, &blk);
+    if (rc) return rc;
+    stats[0] = stats[1] = stats[2] = 0;
+    if (n_rows == 0) return FFQ_OK;
+    hipStream_t st = c->stream;
+    hipLaunchKernelGGL(k_ends_rows, dim3(rows_grid(n_rows, ENDS_WG / ROWS_G, EDIT_GRID_SHORT)), dim3(ENDS_WG), 0, st, d_buf, n_bytes,
+                       sentinel ? 1 : 0, add, d_table, n_rows, R, d_out, c->rows_list, blk);
+    hipLaunchKernelGGL(k_ends_long, dim3(rows_grid(n_rows, ENDS_WG / 64, EDIT_GRID_LONG)), dim3(ENDS_WG), 0, st, d_buf, n_bytes,
+                       sentinel ? 1 : 0, add, d_table, R, d_out, (const int64_t *)c->rows_list, blk);
     return rows_end(c, stats);
 }
 

@@ -411,6 +411,126 @@ def _poly_pos(buf, pos, base, min_len):
     return pos, n - cut
 
 
+class EndRules:
+    """What ffq_table_trim_ends does to both ends of a read, in front of every other trim (include/ffq.h states the rule):
+    trim_front / trim_tail bases go from the 5' / 3' end whatever they are (`fastp -f / -t`, `cutadapt -u`), keep_len (None: no
+    limit) is the most that is then left, the 3' end giving way (`fastp -b`, `cutadapt -l`); front, right and tail are each None
+    or (window, quality), window 1..64 and quality 1..93: the sliding windows of `fastp --cut_front / --cut_right / --cut_tail`
+    (-5 / -r / -3) and of Trimmomatic's SLIDINGWINDOW (`right`), which cut where the mean quality of `window` bases drops
+    below `quality`.  At least one of the six is on."""
+
+    WINDOW_MAX = _hip.ENDS_WINDOW_MAX
+    QUALITY = _hip.ENDS_QUALITY
+
+    def __init__(self, trim_front=0, trim_tail=0, keep_len=None, front=None, right=None, tail=None):
+        def count(name, x, none_ok=False):
+            if x is None and none_ok:
+                return None
+            if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not 0 <= int(x) < 1 << 31:
+                raise ValueError("ends: %s is %san int >= 0" % (name, "None or " if none_ok else ""))
+            return int(x)
+
+        def window(name, st):
+            if st is None:
+                return None
+            try:
+                w, q = st
+            except (TypeError, ValueError):
+                raise ValueError("ends: %s is None or (window, quality)" % name) from None
+            for x in (w, q):
+                if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
+                    raise ValueError("ends: %s is None or (window, quality), two ints" % name)
+            if not 1 <= int(w) <= self.WINDOW_MAX:
+                raise ValueError("ends: the window of %s is 1..%d" % (name, self.WINDOW_MAX))
+            if not self.QUALITY[0] <= int(q) <= self.QUALITY[1]:
+                raise ValueError("ends: the quality of %s is %d..%d" % ((name,) + self.QUALITY))
+            return int(w), int(q)
+        self.trim_front, self.trim_tail = count("trim_front", trim_front), count("trim_tail", trim_tail)
+        self.keep_len = count("keep_len", keep_len, True) or None
+        self.front, self.right, self.tail = window("front", front), window("right", right), window("tail", tail)
+        if not (self.trim_front or self.trim_tail or self.keep_len or self.front or self.right or self.tail):
+            raise ValueError("ends: every rule is off")
+
+
+def _check_ends(ends):
+    """an EndRules or None; ValueError naming `ends` for anything else"""
+    if ends is not None and not isinstance(ends, EndRules):
+        raise ValueError("ends must be an EndRules or None, not %r" % (ends,))
+    return ends
+
+
+def _ends_qual_base(qual_base):
+    if not 0 <= int(qual_base) <= 255:
+        raise ValueError("qual_base is 0..255")
+    return int(qual_base)
+
+
+def ends_cut(quality, rules, qual_base=33):
+    """(a, b): what is left of a read whose quality line is `quality` (bytes) when `rules` (an EndRules) are applied -- the host
+    statement of ffq_table_trim_ends's rule (include/ffq.h states it as a loop), here with prefix sums over the whole line.
+    (0, 0) for a read that goes away."""
+    if not isinstance(rules, EndRules):
+        raise ValueError("rules must be an EndRules")
+    qual_base = _ends_qual_base(qual_base)
+    n = len(quality)
+    a = min(rules.trim_front, n)
+    b = n - min(rules.trim_tail, n - a)
+    if rules.keep_len and b - a > rules.keep_len:
+        b = a + rules.keep_len
+    v = np.frombuffer(bytes(quality), dtype=np.uint8).astype(np.int64) - qual_base
+    csum = np.concatenate((np.zeros(1, dtype=np.int64), np.cumsum(v)))
+
+    def sums(w):                                          # S(i, w) for i = a .. b - w
+        return csum[a + w:b + 1] - csum[a:b - w + 1]
+    if rules.front is not None and b > a:
+        w, q = min(rules.front[0], b - a), rules.front[1]
+        at = np.flatnonzero(sums(w) >= q * w)
+        if not at.size:
+            return 0, 0
+        a += int(at[0])
+        a += int(np.flatnonzero(v[a:a + w] >= q)[0])
+    if rules.right is not None and b > a:
+        w, q = min(rules.right[0], b - a), rules.right[1]
+        at = np.flatnonzero(sums(w) < q * w)
+        if at.size:
+            s = a + int(at[0])
+            bad = np.flatnonzero(v[s:s + w] < q)
+            b = s + (int(bad[0]) if bad.size else w)
+    if rules.tail is not None and b > a:
+        w, q = min(rules.tail[0], b - a), rules.tail[1]
+        at = np.flatnonzero(sums(w) >= q * w)
+        if not at.size:
+            return 0, 0
+        e = a + int(at[-1]) + w
+        b = e - w + int(np.flatnonzero(v[e - w:e] >= q)[-1]) + 1
+    return (a, b) if a < b else (0, 0)
+
+
+def ends_trimmable(buf, pos):
+    """Does the device apply an EndRules to this row (ffq_table_trim_ends's eligibility)?  trimmable()'s rule: the newline is
+    looked for in the whole quality line."""
+    return trimmable(buf, pos)
+
+
+def _ends_pos(buf, pos, rules, qual_base):
+    """(the six positions -- a list, edited in place -- with the rule applied, bases cut)"""
+    if not ends_trimmable(buf, pos):
+        return pos, 0
+    n = pos[5] - pos[4]
+    a, b = ends_cut(buf[pos[4]:pos[5]], rules, qual_base)
+    pos[2], pos[3], pos[4], pos[5] = pos[2] + a, pos[2] + b, pos[4] + a, pos[4] + b
+    return pos, n - (b - a)
+
+
+class EndsReport:
+    """What filter_fastq / filter_fastq_paired (ends_report=...) fill: reads_cut, the reads the ends step (EndRules) changed,
+    and bases_cut, the bases it removed.  Both mates of a pair are added together; every record counts, the dropped ones
+    included.  The same numbers on either route."""
+
+    def __init__(self):
+        self.reads_cut = self.bases_cut = 0
+
+
 class PolyReport:
     """What filter_fastq / filter_fastq_paired (poly_report=...) fill: poly_g_reads and poly_g_bases, the reads the poly-G step
     changed and the bases it removed; poly_x_reads and poly_x_bases, the same for poly-X.  Both mates of a pair are added
@@ -1108,8 +1228,10 @@ def _scanner(entrypos):
     return entrypos, getattr(entrypos, 'open_stream', None)
 
 
-def _configure_stream(st, trim, cutter, content, bounds, column=None, render=False, stats=None, dedup=None, poly_g=None, poly_x=None):
+def _configure_stream(st, trim, cutter, content, bounds, column=None, render=False, stats=None, dedup=None, poly_g=None, poly_x=None,
+                      ends=None):
     """What a native stream is asked for, in the order its chain works (csrc/ffq_stream.h states it above stream_chain): the
+    ends (ends: (an EndRules, qual_base); fixed trims and sliding windows, in front of every other trim), the
     quality trim (an entryfunc_qualitytrim), the poly tails (poly_g / poly_x: a min_len each; one call for both steps, where
     the first of them works: poly-G runs in front of the adapter trim, poly-X behind it), the adapter trim (an
     entryfunc_adaptertrim), the content rules, the length
@@ -1118,6 +1240,8 @@ def _configure_stream(st, trim, cutter, content, bounds, column=None, render=Fal
     behind the filter).  None / False: that setter is not called.  A stage that is added to the chain is added HERE."""
     if dedup is not None:
         st.set_dedup(not dedup.count_only, dedup.expected_reads, dedup.max_bytes)
+    if ends is not None:
+        st.set_ends(ends[0], ends[1])
     if trim is not None:
         st.set_trim(trim.cutoff_back, trim.cutoff_front, trim.qual_base)
     if poly_g is not None or poly_x is not None:
@@ -1201,8 +1325,9 @@ class _BgzfSink:
 
 class _MatePlan:
     """What the records of ONE input file go through in filter_fastq (one plan) and filter_fastq_paired (one per mate), said
-    once for both routes: quality trim, poly-G, adapter trim, poly-X, the verdict by length and then by content, the counts, the
-    text.  poly_report: a PolyReport the plan ADDS to (a pair's two plans share one; the caller resets it).  On the
+    once for both routes: the ends (an EndRules), quality trim, poly-G, adapter trim, poly-X, the verdict by length and then by
+    content, the counts, the text.  poly_report / ends_report: a PolyReport / an EndsReport the plan ADDS to (a pair's two plans
+    share one; the caller resets it).  On the
     device route the plan configures the file's stream and drains every fill (or round) of it; on the host route it is
     called record by record.  judged=False: the mate is trimmed, counted and written but never dropped (pair_filter "first").
     `dropped`: this file's records by the reason (ContentRules.REASONS) they failed for; `report` (a FilterReport or None) is
@@ -1210,8 +1335,12 @@ class _MatePlan:
     and everything that is written goes through what sink() returned; compress_report: a CompressReport the plan's sinks ADD to."""
 
     def __init__(self, quality_cutoff, qual_base, adapter, err_permille, min_overlap, min_len, max_len, content, report, judged=True,
-                 dedup=None, poly_g=None, poly_x=None, poly_report=None, compress=None, compress_report=None):
+                 dedup=None, poly_g=None, poly_x=None, poly_report=None, compress=None, compress_report=None, ends=None,
+                 ends_report=None):
         self.qual_base, self.content, self.report, self.judged = qual_base, content, report, judged
+        self.ends, self.ends_report = _check_ends(ends), ends_report
+        if ends is not None:
+            _ends_qual_base(qual_base)
         self.compress, self.compress_report = compress, compress_report
         self.poly_g, self.poly_x = _poly_min_len("poly_g", poly_g), _poly_min_len("poly_x", poly_x)
         self.poly_report = poly_report
@@ -1236,7 +1365,7 @@ class _MatePlan:
         rep = self.report
         _configure_stream(st, self.trim, self.cutter, self.content, None if self.lo is None and self.hi is None else (self.lo, self.hi),
                           render=True, stats=None if rep is None else (self.qual_base, rep.max_cycles), dedup=self.dedup,
-                          poly_g=self.poly_g, poly_x=self.poly_x)
+                          poly_g=self.poly_g, poly_x=self.poly_x, ends=None if self.ends is None else (self.ends, self.qual_base))
         if self.compress is not None:
             st.set_compress(self.compress)
 
@@ -1261,6 +1390,10 @@ class _MatePlan:
             for reason, k in zip(ContentRules.REASONS, st.filter_counts()[1:7]):
                 self.dropped[reason] += k
         removed = 0
+        if self.ends is not None:
+            e = st.ends_trimmed()
+            removed += e[1]
+            self._ends_count(e[0], e[1])
         if self.trim is not None:
             removed += st.trimmed()[1]
         if self.cutter is not None:
@@ -1270,6 +1403,12 @@ class _MatePlan:
             removed += g[1] + x[1]
             self._poly_count(g[0], g[1], x[0], x[1])
         return nb, rendered, removed
+
+    def _ends_count(self, reads, bases):
+        rep = self.ends_report
+        if rep is not None:
+            rep.reads_cut += reads
+            rep.bases_cut += bases
 
     def _poly_count(self, g_reads, g_bases, x_reads, x_bases):
         rep = self.poly_report
@@ -1293,7 +1432,11 @@ class _MatePlan:
         if self.report is not None:
             self.report.before.add_pos(buf, pos)
         g = x = 0
-        if self.trim is not None:                            # (the chain's order: quality, poly-G, adapter, poly-X)
+        if self.ends is not None:                            # (the chain's order: ends, quality, poly-G, adapter, poly-X)
+            pos, e = _ends_pos(buf, list(pos), self.ends, self.qual_base)
+            if e:
+                self._ends_count(1, e)
+        if self.trim is not None:
             pos = self.trim.trimmed_pos(buf, pos)
         if self.poly_g is not None:
             pos, g = _poly_pos(buf, list(pos), b"G", self.poly_g)
@@ -1371,6 +1514,16 @@ def fastq_stats(fh: typing.BinaryIO, fbufsize: int = 1 << 24, qual_base: int = 3
 FilterResult = namedtuple('FilterResult', 'records_in records_out bases_removed bytes_out')
 
 
+def _check_ends_report(ends, ends_report):
+    """an EndsReport (reset: the plans add to it) or None"""
+    if ends_report is not None:
+        if ends is None:
+            raise ValueError("ends_report needs ends")
+        if not isinstance(ends_report, EndsReport):
+            raise TypeError("ends_report must be an EndsReport")
+        ends_report.__init__()
+
+
 def _check_poly_report(poly_report):
     """a PolyReport (reset: the plans add to it) or None"""
     if poly_report is not None:
@@ -1383,7 +1536,7 @@ def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1
                  qual_base: int = 33, min_len=None, max_len=None, entrypos: typing.Optional[typing.Callable] = None,
                  adapter=None, err_permille: int = 100, min_overlap: int = 3, report=None, content=None, dedup=None,
                  dedup_report=None, poly_g=None, poly_x=None, poly_report=None, compress=None,
-                 compress_report=None) -> FilterResult:
+                 compress_report=None, ends=None, ends_report=None) -> FilterResult:
     """Trim, filter and WRITE a FASTQ stream: the file `cutadapt -q 20 -m 30` leaves behind, which is what the tables of
     positions of the reference's user guide are kept for in the end ("to avoid saving a FASTQ file after each filtering or
     read-trimming step", doc/user-guide.rst:196-204).  Every record of `fh` is quality-trimmed (quality_cutoff: an int --
@@ -1431,6 +1584,13 @@ def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1
     bases_removed includes what they cut; poly_report (a PolyReport) has the numbers, the same on either route.  Not done:
     wrapped records, 5' tails, per-base poly-X counts.
 
+    ends: None, or an EndRules: fixed trims (`fastp -f / -t / -b`, `cutadapt -u / -l`) and sliding-window quality cutting of
+    both ends (`fastp -5 / -r / -3`, Trimmomatic's SLIDINGWINDOW), IN FRONT of the quality trim and every other step -- fastp's
+    order; ends_cut is the rule.  On the device with the GPU scanner (ffq_stream_set_ends).  bases_removed includes what it
+    cut; ends_report (an EndsReport) has the numbers, the same on either route.  The rule has not been checked against
+    fastp's or Trimmomatic's sources.  Not done: windows above 64, wrapped records, push-down through readfastq_iter,
+    per-stage counts.
+
     compress: None, or "bgzf": `fh_out` (a binary file object, NOT a gzip.open one) is written as BGZF, what bgzip writes --
     gzip members of at most BGZF_BLOCK_BYTES of text each, which `zcat`, gzip.open and this package's own readers
     (automagic_open, hip.gunzip_fd, hip.bgzf_range, readfastq_iter_range) read, the last three member-parallel.  With the
@@ -1442,9 +1602,11 @@ def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1
         raise TypeError("content must be a ContentRules")
     _check_dedup(dedup, dedup_report)
     _check_poly_report(poly_report)
+    _check_ends_report(_check_ends(ends), ends_report)
     _check_compress(compress, compress_report)
     plan = _MatePlan(quality_cutoff, qual_base, adapter, err_permille, min_overlap, min_len, max_len, content, report, dedup=dedup,
-                     poly_g=poly_g, poly_x=poly_x, poly_report=poly_report, compress=compress, compress_report=compress_report)
+                     poly_g=poly_g, poly_x=poly_x, poly_report=poly_report, compress=compress, compress_report=compress_report,
+                     ends=ends, ends_report=ends_report)
     fh_out = plan.sink(fh_out)
     hd = _HostDedup(dedup, dedup_report) if dedup is not None else None
     entrypos, open_stream = _scanner(entrypos)
@@ -1754,7 +1916,7 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
                         overlap_report=None, merged_out: typing.Optional[typing.BinaryIO] = None,
                         merge_report=None, dedup=None, dedup_report=None, poly_g=None, poly_x=None,
                         poly_report=None, compress=None, compress_report=None, correction=None,
-                        correction_report=None) -> PairedFilterResult:
+                        correction_report=None, ends=None, ends_report=None) -> PairedFilterResult:
     """filter_fastq for paired-end files: the i-th records of `fh1` and `fh2` are mates, and a pair is written or dropped
     TOGETHER, so that `fh_out1` and `fh_out2` stay record for record in step (`cutadapt -q 20 -a ... -A ... -m 30:20
     --pair-filter=any -o out1 -p out2 in1 in2`).  Every record is trimmed as filter_fastq trims it -- quality_cutoff for both
@@ -1805,6 +1967,9 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
     the order is quality, poly-G, adapter, poly-X, overlap, filter, so the overlap and the merge see the rows as the per-mate
     trims left them (fastp runs its poly-X behind its overlap trim: a departure).  poly_report: a PolyReport, both mates added
     together.
+    ends: filter_fastq's, one EndRules for both mates or a (mate 1, mate 2) pair of them (either may be None), as min_len is;
+    the step works per mate in front of every other one: the order is ends, quality, poly-G, adapter, poly-X, overlap, filter,
+    so the overlap and the merge see the reads as it left them.  ends_report: an EndsReport, both mates added together.
     correction: a CorrectionRules (needs `overlap`; `fastp --correction`); behind the overlap and in front of the filters, every
     position of a pair's overlap at which the mates disagree, one call sure and the other poor, has the poor base and quality
     replaced (correct_correctable, correct_mates).  The order is quality, poly-G, adapter, poly-X, overlap, correct, filter,
@@ -1852,11 +2017,20 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
         a, b = tuple(x) if isinstance(x, (tuple, list)) else (x, x)
         return (None if a is None else int(a), None if b is None else int(b))
     los, his = per_mate(min_len), per_mate(max_len)
+    if isinstance(ends, (tuple, list)):
+        if len(ends) != 2:
+            raise ValueError("ends is an EndRules for both mates or a pair of them")
+        ends_pair = (_check_ends(ends[0]), _check_ends(ends[1]))
+    else:
+        ends_pair = (_check_ends(ends),) * 2
     _check_poly_report(poly_report)
+    _check_ends_report(ends_pair[0] or ends_pair[1], ends_report)
     _check_compress(compress, compress_report)
     plans = tuple(_MatePlan(quality_cutoff, qual_base, a, err_permille, min_overlap, lo, hi, content, rep, judged, poly_g=poly_g,
-                            poly_x=poly_x, poly_report=poly_report, compress=compress, compress_report=compress_report)
-                  for a, lo, hi, rep, judged in zip((adapter, adapter2), los, his, (report, report2), (True, pair_filter != "first")))
+                            poly_x=poly_x, poly_report=poly_report, compress=compress, compress_report=compress_report,
+                            ends=e, ends_report=ends_report)
+                  for a, lo, hi, rep, judged, e in zip((adapter, adapter2), los, his, (report, report2), (True, pair_filter != "first"),
+                                                       ends_pair))
     dropped = {"mate1_only": 0, "mate2_only": 0, "both": 0}
     entrypos, open_stream = _scanner(entrypos)
     pairs_in = pairs_out = removed = 0

@@ -50,7 +50,7 @@ def _add(add, sentinel):
     return (-1 if sentinel else 0) if add is None else add
 
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 OK = 0
 E_NODEVICE, E_HIP, E_ARG, E_NOMEM, E_TABLE_FULL, E_INTERNAL, E_TIMEOUT = -1, -2, -3, -4, -5, -6, -7
 STAGE_NONE, STAGE_HANDOFF, STAGE_SCAN, STAGE_GATHER = 0, 1, 2, 3      # FFQ_SHARD_STAGE_*
@@ -108,6 +108,7 @@ SYMBOLS = (
     "ffq_table_seq_keys", "ffq_seq_key_host", "ffq_pair_key_host", "ffq_dedup_create", "ffq_dedup_destroy", "ffq_dedup_select",
     "ffq_stream_set_dedup", "ffq_stream_dedup_counts", "ffq_pair_set_dedup", "ffq_pair_dedup_counts",
     "ffq_table_trim_poly", "ffq_stream_set_poly", "ffq_stream_poly_trimmed",
+    "ffq_table_trim_ends", "ffq_stream_set_ends", "ffq_stream_ends_trimmed",
     "ffq_deflate_bgzf_bound", "ffq_deflate_bgzf", "ffq_bgzf_eof_block",
     "ffq_stream_set_compress", "ffq_stream_compressed", "ffq_pair_set_compress", "ffq_pair_merged_bgzf",
 )
@@ -142,6 +143,27 @@ def content_rules_struct(rules):
     if rules is None or isinstance(rules, ContentRulesStruct):
         return rules
     return ContentRulesStruct(*(int(getattr(rules, name)) for name, _ in ContentRulesStruct._fields_))
+
+
+ENDS_WINDOW_MAX = 64         # the widest window of ffq_table_trim_ends
+ENDS_QUALITY = (1, 93)       # the range of a window's quality
+
+
+class EndsRulesStruct(ctypes.Structure):
+    """struct ffq_ends_rules (include/ffq.h)."""
+    _fields_ = [(name, ctypes.c_int32) for name in ("trim_front", "trim_tail", "keep_len", "qual_base", "front_window", "front_quality",
+                                                    "right_window", "right_quality", "tail_window", "tail_quality")]
+
+
+def ends_rules_struct(rules, qual_base=33):
+    """What the library takes for `rules`: None or an EndsRulesStruct as it is, or anything with trim_front, trim_tail, keep_len
+    (None: no limit) and front, right, tail -- each (window, quality) or None -- as attributes (fastqandfurious.EndRules) and
+    `qual_base` beside it."""
+    if rules is None or isinstance(rules, EndsRulesStruct):
+        return rules
+    w = [tuple(int(x) for x in st) if st is not None else (0, 0) for st in (rules.front, rules.right, rules.tail)]
+    return EndsRulesStruct(int(rules.trim_front), int(rules.trim_tail), int(rules.keep_len or 0), int(qual_base),
+                           w[0][0], w[0][1], w[1][0], w[1][1], w[2][0], w[2][1])
 
 
 PAIR_FILTERS = {"any": 0, "both": 1, "first": 2}       # FFQ_PAIR_ANY / _BOTH / _FIRST
@@ -434,6 +456,7 @@ def lib():
         L.ffq_table_trim_quality.argtypes = [vp, vp, i64, i32, i64, vp, i64, i32, i32, i32, vp, P(i64)]
         L.ffq_table_trim_adapter.argtypes = [vp, vp, i64, i32, i64, vp, i64, ctypes.c_char_p, i32, i32, i32, vp, P(i64)]
         L.ffq_table_trim_poly.argtypes = [vp, vp, i64, i32, i64, vp, i64, i32, i32, vp, P(i64)]
+        L.ffq_table_trim_ends.argtypes = [vp, vp, i64, i32, i64, vp, i64, P(EndsRulesStruct), vp, P(i64)]
         L.ffq_table_stats.argtypes = [vp, vp, i64, i32, i64, vp, i64, i32, i32, i32, vp, P(i64)]
         L.ffq_table_select_reads.argtypes = [vp, vp, i64, i32, i64, vp, i64, i64, i64, P(ContentRulesStruct), vp, vp, P(i64), P(i64)]
         L.ffq_ee_micro_table.argtypes = []
@@ -535,6 +558,8 @@ def lib():
         L.ffq_stream_set_adapter.argtypes = [vp, ctypes.c_char_p, i32, i32, i32]
         L.ffq_stream_adapter_trimmed.argtypes = [vp, P(i64)]
         L.ffq_stream_set_poly.argtypes = [vp, i32, i32]
+        L.ffq_stream_set_ends.argtypes = [vp, P(EndsRulesStruct)]
+        L.ffq_stream_ends_trimmed.argtypes = [vp, P(i64)]
         L.ffq_stream_poly_trimmed.argtypes = [vp, P(i64), P(i64)]
         L.ffq_stream_set_stats.argtypes = [vp, i32, i32, i32]
         L.ffq_stream_stats.argtypes = [vp, i32, vp, i64]
@@ -976,6 +1001,20 @@ class Context:
                                         ctypes.c_void_p(d_table if d_out is None else d_out), stats))
         return int(stats[0]), int(stats[1]), int(stats[2])
 
+    def table_trim_ends(self, d_buf, n_bytes, d_table, n_rows, rules, qual_base=33, d_out=None, sentinel=True, add=None):
+        """Fixed trims and sliding-window quality cutting of the rows of a device table (ffq_table_trim_ends: the rule that
+        include/ffq.h states; rules: a fastqandfurious.EndRules with `qual_base` beside it, or an EndsRulesStruct): pos2..pos5
+        of every eligible row move inwards, every other row is copied unchanged.  Run it in front of the other trims.  d_out:
+        n_rows rows of room (None: in place); raw device pointers; d_buf / n_bytes / sentinel / add as for
+        table_gather_column.  Returns (rows changed, bases removed, rows skipped)."""
+        add = _add(add, sentinel)
+        r = ends_rules_struct(rules, qual_base)
+        stats = (ctypes.c_int64 * 3)()
+        check(lib().ffq_table_trim_ends(self.handle, ctypes.c_void_p(d_buf), int(n_bytes), int(bool(sentinel)), int(add),
+                                        ctypes.c_void_p(d_table), int(n_rows), ctypes.byref(r) if r is not None else None,
+                                        ctypes.c_void_p(d_table if d_out is None else d_out), stats))
+        return int(stats[0]), int(stats[1]), int(stats[2])
+
     def table_stats(self, d_buf, n_bytes, d_table, n_rows, d_stats, qual_base=33, max_cycles=512, accumulate=False, sentinel=True,
                     add=None, wait=True):
         """Per-cycle base and quality statistics of the rows of a device table (ffq_table_stats), counted into the
@@ -1406,6 +1445,19 @@ class _Stream:
         """(rows changed, bases removed, rows skipped) by the adapter step of the fill the iteration has just yielded."""
         stats = (ctypes.c_int64 * 3)()
         check(lib().ffq_stream_adapter_trimmed(self._h, stats))
+        return int(stats[0]), int(stats[1]), int(stats[2])
+
+    def set_ends(self, rules, qual_base=33):
+        """Fixed trims and sliding-window cutting in the stream (ffq_stream_set_ends; before the first fill): every fill's rows
+        go through ffq_table_trim_ends on the device in front of the quality trim and every other trim.  rules: as for
+        Context.table_trim_ends."""
+        r = ends_rules_struct(rules, qual_base)
+        check(lib().ffq_stream_set_ends(self._h, ctypes.byref(r) if r is not None else None))
+
+    def ends_trimmed(self):
+        """(rows changed, bases removed, rows skipped) by the ends step of the fill the iteration has just yielded."""
+        stats = (ctypes.c_int64 * 3)()
+        check(lib().ffq_stream_ends_trimmed(self._h, stats))
         return int(stats[0]), int(stats[1]), int(stats[2])
 
     def set_poly(self, poly_g=None, poly_x=None):

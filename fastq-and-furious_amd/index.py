@@ -229,6 +229,22 @@ def poly_rows(buf, table, base=None, min_len=10, shift=0):
     return t
 
 
+def ends_rows(buf, table, rules, qual_base=33, shift=0):
+    """Copy of a table with the fixed trims and sliding windows of `rules` (an _F.EndRules) applied, on the host: pos2..pos5 of
+    every row the rule applies to (_F.ends_trimmable: positions minus `shift` index `buf`) moved to where _F.ends_cut says;
+    the same rows, none dropped.  It runs in front of trim_rows and every other trim.  On the GPU:
+    hip.Context.table_trim_ends."""
+    t = np.array(table, dtype=np.int64).reshape(-1, 6)
+    buf = bytes(buf) if not isinstance(buf, bytes) else buf
+    _F.ends_cut(b"", rules, qual_base)                  # (checks the arguments)
+    for row in t:
+        rel = (row - shift).tolist()
+        if _F.ends_trimmable(buf, rel):
+            a, b = _F.ends_cut(buf[rel[4]:rel[5]], rules, qual_base)
+            row[2:6] = (row[2] + a, row[2] + b, row[4] + a, row[4] + b)
+    return t
+
+
 def stats_rows(buf, table, qual_base=33, max_cycles=512, shift=0):
     """Per-cycle base and quality statistics of the rows of a table, on the host (_F.FastqStats.add_rows: positions minus
     `shift` index `buf`; a row the rule does not apply to counts as skipped)."""

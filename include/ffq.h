@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FFQ_ABI_VERSION 10
+#define FFQ_ABI_VERSION 11
 
 /* scanner status codes -- identical to the reference's module constants
  * (_fastqandfurious.c:7-15,254-262; fastqandfurious.py:19-27)             */
@@ -375,6 +375,44 @@ int ffq_table_trim_adapter(ffq_ctx *ctx, const uint8_t *d_buf, int64_t n_bytes, 
 #define FFQ_POLY_ANY (-1)
 int ffq_table_trim_poly(ffq_ctx *ctx, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
                         const int64_t *d_table, int64_t n_rows, int base, int min_len, int64_t *d_out, int64_t stats[3]);
+
+/* Fixed trims and sliding-window quality cutting of both read ends by MODIFYING rows: what fastp's -f / -t / -b and its
+ * --cut_front / --cut_right / --cut_tail (-5 / -r / -3), Trimmomatic's SLIDINGWINDOW and cutadapt's -u / -l are for.  Run it
+ * in FRONT of every other trim (fastp's order).  For one row, q[0..n) = buf[pos4:pos5] as unsigned bytes; v[i] = (int)q[i] -
+ * qual_base, which may be negative; S(i, W) = v[i] + ... + v[i+W-1].  Sums are 32 bits inside a window, positions 64 bits.
+ * trim_front, trim_tail, keep_len: each >= 0.  Three windows, FRONT, RIGHT and TAIL: each with `window` in 0..64 (0: off) and
+ * `quality` in 1..93:
+ *     a = min(trim_front, n);  b = n - min(trim_tail, n - a)             (fixed trims)
+ *     if keep_len > 0 and b - a > keep_len:  b = a + keep_len            (the 3' end gives way)
+ *     front (if on and b > a):   W = min(window, b - a);  T = quality * W
+ *         s = the smallest i in a .. b-W with S(i, W) >= T;   none: the read goes to length 0, done
+ *         a = s;  while v[a] < quality: a += 1              (a window that passes holds such a base: this ends inside it)
+ *     right (if on and b > a):   W = min(window, b - a);  T = quality * W
+ *         s = the smallest i in a .. b-W with S(i, W) < T;    none: nothing happens
+ *         b' = s;  while b' < s + W and v[b'] >= quality: b' += 1;   b = b'  (the good bases at the head of the bad window stay)
+ *     tail (if on and b > a):    W = min(window, b - a);  T = quality * W
+ *         e = the largest j in a+W .. b with S(j-W, W) >= T;   none: length 0, done
+ *         b = e;  while v[b-1] < quality: b -= 1
+ *     if a >= b: a = b = 0
+ * and the row becomes pos0, pos1, pos2 + a, pos2 + b, pos4 + a, pos4 + b.  A range shorter than the window is judged as one
+ * window of its own length (W = min(...)); a stage that meets an empty range does nothing.  "Mean >= quality" is compared as
+ * sum >= quality * W, with no division.  Positions behind the last full window of `right` are never judged: that is what
+ * `tail` is for.  This is fastp's -5 / -r / -3 and Trimmomatic's SLIDINGWINDOW in spirit, but it has NOT been checked
+ * against either source, which was not at hand.  Eligibility is ffq_table_trim_quality's: pos2..pos5 - add all >= 0, in
+ * order, inside the buffer (with sentinel, coordinate 0 is the virtual "\n": never read), pos3 - pos2 == pos5 - pos4 and no
+ * byte of the WHOLE quality line is "\n" -- the bytes the fixed trims take off included; every other row is copied unchanged
+ * and counted as skipped; a row of length 0 is eligible and unchanged.  No byte outside the row's own checked quality range
+ * is read; the sequence line is never read.  d_buf / n_bytes / sentinel / add: as for ffq_table_gather_column.  d_out:
+ * n_rows rows; it MAY be d_table.  Both tables 16-byte aligned.  stats = {rows changed, bases removed, rows skipped}.
+ * FFQ_E_ARG: a window above 64, a quality outside 1..93 on a window that is on, negative counts, qual_base outside 0..255,
+ * all of it off, misaligned tables, a scan pending on the context.  One host wait.  Not done: windows above 64, wrapped
+ * records, push-down through readfastq_iter, per-stage counts.                                                          */
+typedef struct ffq_ends_rules {
+    int32_t trim_front, trim_tail, keep_len, qual_base, front_window, front_quality, right_window, right_quality, tail_window,
+        tail_quality;
+} ffq_ends_rules;
+int ffq_table_trim_ends(ffq_ctx *ctx, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
+                        const int64_t *d_table, int64_t n_rows, const ffq_ends_rules *rules, int64_t *d_out, int64_t stats[3]);
 
 /* Per-cycle base and quality statistics of a table, counted on the device: what the QC report of fastp / FastQC is made
  * of.  d_stats: DEVICE memory, 16-byte aligned, FFQ_STATS_WORDS(C) uint64 words with C = max_cycles; overwritten
@@ -862,6 +900,13 @@ int  ffq_stream_adapter_trimmed(ffq_stream *s, int64_t stats[3]);
  * of either step for the fill ffq_stream_next has just returned (zeros for a step that is off).                        */
 int  ffq_stream_set_poly(ffq_stream *s, int poly_g_min_len, int poly_x_min_len);
 int  ffq_stream_poly_trimmed(ffq_stream *s, int64_t stats_g[3], int64_t stats_x[3]);
+/* Fixed trims and sliding-window cutting in the stream (the rules of ffq_stream_set_trim: before the first
+ * ffq_stream_next, not with FFQ_F_DECODE_QUAL): every fill's table goes through ffq_table_trim_ends in place on the device
+ * BEHIND the statistics IN and IN FRONT of the quality trim and every other trim -- fastp's order --, per mate and in front
+ * of a pair's overlap analysis.  `rules` is copied.  ffq_stream_ends_trimmed: {rows changed, bases removed, rows skipped} of
+ * the fill ffq_stream_next has just returned.                                                                          */
+int  ffq_stream_set_ends(ffq_stream *s, const ffq_ends_rules *rules);
+int  ffq_stream_ends_trimmed(ffq_stream *s, int64_t stats[3]);
 /* Content rules in the stream (the rules of ffq_stream_set_trim: before the first ffq_stream_next, not with
  * FFQ_F_DECODE_QUAL): the select of every fill judges the rows by ffq_table_select_reads -- as the trims left them, which
  * is cutadapt's order -- and everything behind it (statistics OUT, the render, the column gather, ffq_stream_selected) sees
@@ -1028,7 +1073,7 @@ int  ffq_stream_push(ffq_stream *s, int64_t n, int eof);
  * ffq_pair_set_correct (before the first ffq_pair_next only; FFQ_E_ARG afterwards, for rules out of range and without
  * ffq_pair_set_overlap; NULL switches it off, as does ffq_pair_set_overlap(NULL)): every round runs ffq_table_pair_correct on
  * both fills' device bytes, between the overlap and ffq_table_select_pairs, with the insert sizes the round's overlap pass
- * found.  The order of a round is then quality, poly-G, adapter, poly-X, overlap, CORRECT, filter, dedup, merge.  Statistics IN
+ * found.  The order of a round is then ends, quality, poly-G, adapter, poly-X, overlap, CORRECT, filter, dedup, merge.  Statistics IN
  * and the dedup keys are taken in front of the correction, on the bytes as read; the content filter, statistics OUT, the
  * render, the merge and the deflate see the corrected bytes.  ffq_pair_rows' h_bytes remain the bytes AS READ (the pinned
  * host copy is not corrected): a caller that cuts records from them itself does not see the corrections -- the rendered text
