@@ -15,8 +15,8 @@
 //     of DIFFERENT pairs must not share bytes -- the call's contract, unlike every other table pass.
 // The loop over a lane's chunks holds no ballot, DPP move or barrier: its trip count differs from lane to lane.  Behind it the
 // group sums its corrections with DPP moves (uniform again).  No pair above 512 bases is touched: there is no long rows' launch.
-// The matrix goes to counters in LDS (32 bit, one set per workgroup) and leaves with one set of 64-bit atomics per workgroup;
-// the six counts leave as RowCounts::add_to's do.
+// The matrix goes to counters in LDS (32 bit, one set per workgroup) and leaves with one set of 64-bit atomics per workgroup
+// (lds_hist_flush); the six counts leave by wg_counts_flush (ffq_rows.h).
 #pragma once
 #include "ffq_pair.h"
 #include "ffq_correctwalk.h"
@@ -33,21 +33,11 @@ struct CorrectBlock { unsigned long long cnt[CORRECT_COUNTS]; unsigned long long
 
 struct CorrectRules { uint32_t G, B; };           // the threshold BYTES: qual_base + good_quality, qual_base + bad_quality
 
-// Is pair (rows a.., b.., insert size ins) looked at?  Positions and ranges only.
+// Is pair (rows a.., b.., insert size ins) looked at?  The pair's geometry (ffq_pair.h) and nothing else.
 __device__ __forceinline__ bool correct_parse(const PairSide &A, const PairSide &B, longlong2 a23, longlong2 a45, longlong2 b23, longlong2 b45,
                                               int32_t ins, CorPair &P)
 {
-    int64_t pa2 = 0, pa4 = 0, na = 0, pb2 = 0, pb4 = 0, nb = 0;
-    bool ok = row_pos<true, true>(A.nbytes, A.s, A.add, a23, a45, pa2, pa4, na);
-    ok = ok && row_pos<true, true>(B.nbytes, B.s, B.add, b23, b45, pb2, pb4, nb);
-    ok = ok && na <= MRG_MAX_LEN && nb <= MRG_MAX_LEN && ins >= 0;
-    const int64_t o = (int64_t)ins - nb;
-    ok = ok && -nb < o && o < na;
-    P.asrc = P.qasrc = P.bsrc = P.qbsrc = 0; P.n1 = P.n2 = P.o = 0;
-    if (!ok) return false;
-    P.asrc = pa2 - A.s; P.qasrc = pa4 - A.s; P.bsrc = pb2 - B.s; P.qbsrc = pb4 - B.s;
-    P.n1 = (int32_t)na; P.n2 = (int32_t)nb; P.o = (int32_t)o;
-    return true;
+    return pair_geometry(A, B, a23, a45, b23, b45, ins, MRG_MAX_LEN, P);
 }
 
 // w1 / w2: the two buffers again (A.d, B.d), writable
@@ -57,7 +47,6 @@ __global__ __launch_bounds__(CORRECT_WG) void k_pair_correct(PairSide A, PairSid
 {
     constexpr int G = ROWS_G, RPB = CORRECT_WG / G, U = CORRECT_U;
     __shared__ uint32_t s_mat[CORRECT_MATRIX];
-    __shared__ unsigned long long s_cnt[CORRECT_WG / 64][CORRECT_COUNTS];
     const int lane = threadIdx.x & 63, gl = lane & (G - 1);
     if (threadIdx.x < CORRECT_MATRIX) s_mat[threadIdx.x] = 0;
     __syncthreads();
@@ -134,25 +123,11 @@ __global__ __launch_bounds__(CORRECT_WG) void k_pair_correct(PairSide A, PairSid
         }
     }
 
-    // the matrix, and the counts: wave, workgroup, one set of atomics
+    // the matrix (lds_hist_flush), and the counts (wg_counts_flush)
     __syncthreads();
-    if (want_matrix && threadIdx.x < CORRECT_MATRIX) {
-        const uint32_t x = s_mat[threadIdx.x];
-        if (x) atomicAdd(&blk->matrix[threadIdx.x], (unsigned long long)x);
-    }
-    const unsigned long long t_lk = wave_sum_u64(c_look), t_pr = wave_sum_u64(c_pairs), t_f1 = wave_sum_u64(c_f1), t_f2 = wave_sum_u64(c_f2),
-                             t_mm = wave_sum_u64(c_mm), t_nt = wave_sum_u64(c_not);
-    if (lane == 0) {
-        unsigned long long *w = s_cnt[threadIdx.x >> 6];
-        w[0] = t_lk; w[1] = t_pr; w[2] = t_f1; w[3] = t_f2; w[4] = t_mm; w[5] = t_nt;
-    }
-    __syncthreads();
-    if (threadIdx.x < CORRECT_COUNTS) {
-        unsigned long long s = 0;
-#pragma unroll
-        for (int w = 0; w < CORRECT_WG / 64; w++) s += s_cnt[w][threadIdx.x];
-        if (s) atomicAdd(&blk->cnt[threadIdx.x], s);
-    }
+    if (want_matrix) lds_hist_flush<CORRECT_WG>(s_mat, CORRECT_MATRIX, blk->matrix);
+    const unsigned long long c[CORRECT_COUNTS] = {c_look, c_pairs, c_f1, c_f2, c_mm, c_not};
+    wg_counts_flush<CORRECT_WG>(c, blk->cnt);
 }
 
 }  // namespace ffq

@@ -163,32 +163,26 @@ struct DedupBlock { unsigned long long kept, dups, nokey, added, err; };
 constexpr int DEDUP_WG = 256;
 
 // A workgroup's share of the counters, and whether one of its probes gave up (`bit` of the error word).  Every thread of the
-// workgroup is here: sums over the wave, over the workgroup's waves through LDS, one set of atomics per WORKGROUP (RowCounts::add_to's
-// way).  The launches stride over the rows for this: with an atomic per wave on the same three addresses -- 52 000 waves for the
-// 3.3 M rows of a GiB -- k_dedup_resolve took 0.64 - 1.24 ms, the counters served one at a time.
+// workgroup is here: the four counts leave by wg_counts_flush, one set of atomics per WORKGROUP.  The launches stride over the
+// rows for this: with an atomic per wave on the same three addresses -- 52 000 waves for the 3.3 M rows of a GiB --
+// k_dedup_resolve took 0.64 - 1.24 ms, the counters served one at a time.  `lost` is an OR, not a sum: a flag
+// per wave, read behind the flush's barrier, and one atomic per workgroup that lost a probe.
 __device__ __forceinline__ void dedup_flush(unsigned int kept, unsigned int dups, unsigned int nokey, unsigned int added, bool lost,
                                             unsigned long long bit, DedupBlock *__restrict__ blk)
 {
-    __shared__ unsigned long long s_cnt[DEDUP_WG / 64][5];
-    const unsigned int c[4] = {kept, dups, nokey, added};
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const unsigned long long t = wave_sum_u64(c[k]);
-        if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6][k] = t;
-    }
+    __shared__ bool s_lost[DEDUP_WG / 64];
     const unsigned long long ml = __ballot(lost);
-    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6][4] = ml ? 1 : 0;
-    __syncthreads();
-    if (threadIdx.x < 5) {
-        unsigned long long t = 0;
+    if ((threadIdx.x & 63) == 0) s_lost[threadIdx.x >> 6] = ml != 0;
+    const unsigned int c[4] = {kept, dups, nokey, added};
+    wg_counts_flush<DEDUP_WG>(c, &blk->kept);
+    if (threadIdx.x == 0) {
+        bool any = false;
 #pragma unroll
-        for (int w = 0; w < DEDUP_WG / 64; w++) t += s_cnt[w][threadIdx.x];
-        unsigned long long *dst = threadIdx.x == 0 ? &blk->kept : threadIdx.x == 1 ? &blk->dups : threadIdx.x == 2 ? &blk->nokey
-                                  : threadIdx.x == 3 ? &blk->added : &blk->err;
-        if (t && threadIdx.x < 4) atomicAdd(dst, t);
-        if (t && threadIdx.x == 4) atomicOr(dst, bit);
+        for (int w = 0; w < DEDUP_WG / 64; w++) any |= s_lost[w];
+        if (any) atomicOr(&blk->err, bit);
     }
 }
+static_assert(offsetof(DedupBlock, dups) == 8 && offsetof(DedupBlock, nokey) == 16 && offsetof(DedupBlock, added) == 24, "dedup_flush: the four counts in a row");
 
 __global__ __launch_bounds__(256) void k_dedup_clear(DedupSlot *__restrict__ tab, int64_t slots)
 {

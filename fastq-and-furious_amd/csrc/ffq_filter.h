@@ -79,23 +79,15 @@ struct FilterCounts {
         c[7] += (verdict & FILTER_NOT_JUDGED) ? 1u : 0u;
     }
 
-    // every thread of the workgroup is here (RowCounts::add_to's way: wave, workgroup, one set of atomics)
+    // every thread of the workgroup is here (wg_counts_flush; widened for it: handed in as 32-bit counts, k_filter_rows took
+    // 97 VGPRs where it takes 96 -- four waves a SIMD where there are five)
     template <int WG>
     __device__ __forceinline__ void add_to(FilterBlock *__restrict__ blk) const
     {
-        __shared__ unsigned long long s_cnt[WG / 64][FILTER_COUNTS];
+        unsigned long long w[FILTER_COUNTS];
 #pragma unroll
-        for (int k = 0; k < FILTER_COUNTS; k++) {
-            const unsigned long long t = wave_sum_u64(c[k]);
-            if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6][k] = t;
-        }
-        __syncthreads();
-        if (threadIdx.x < FILTER_COUNTS) {
-            unsigned long long t = 0;
-#pragma unroll
-            for (int w = 0; w < WG / 64; w++) t += s_cnt[w][threadIdx.x];
-            if (t) atomicAdd(&blk->cnt[threadIdx.x], t);
-        }
+        for (int k = 0; k < FILTER_COUNTS; k++) w[k] = c[k];
+        wg_counts_flush<WG>(w, blk->cnt);
     }
 };
 

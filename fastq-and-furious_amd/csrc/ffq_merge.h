@@ -38,19 +38,16 @@ struct MergeBlock { unsigned long long cnt[MERGE_COUNTS]; };
 __device__ __forceinline__ int64_t merge_parse(const PairSide &A, const PairSide &B, longlong2 a01, longlong2 a23, longlong2 a45,
                                                longlong2 b23, longlong2 b45, int32_t ins, MrgPair &P)
 {
-    int64_t pa2 = 0, pa4 = 0, na = 0, pb2 = 0, pb4 = 0, nb = 0;
-    bool ok = row_pos<true, true>(A.nbytes, A.s, A.add, a23, a45, pa2, pa4, na);
-    ok = ok && row_pos<true, true>(B.nbytes, B.s, B.add, b23, b45, pb2, pb4, nb);
+    // the pair's geometry (ffq_pair.h), and mate 1's header
+    const bool geo = pair_geometry(A, B, a23, a45, b23, b45, ins, MRG_MAX_LEN, P);
     const int64_t p0 = row_coord(a01.x, A.add), p1 = row_coord(a01.y, A.add);
-    ok = ok && p0 >= 0 && p0 < p1 && p1 <= A.nbytes + A.s;
-    ok = ok && na <= MRG_MAX_LEN && nb <= MRG_MAX_LEN && ins >= 0;
-    const int64_t o = (int64_t)ins - nb;
-    ok = ok && -nb < o && o < na;
-    P.hsrc = P.asrc = P.qasrc = P.bsrc = P.qbsrc = 0; P.h = 0; P.n1 = P.n2 = P.o = P.L = 0;
-    if (!ok) return 0;
+    P.hsrc = 0; P.h = 0; P.L = 0;
+    if (!geo || !(p0 >= 0 && p0 < p1 && p1 <= A.nbytes + A.s)) {
+        P.asrc = P.qasrc = P.bsrc = P.qbsrc = 0; P.n1 = P.n2 = P.o = 0;
+        return 0;
+    }
     P.hsrc = p0 + 1 - A.s; P.h = p1 - p0 - 1;
-    P.asrc = pa2 - A.s; P.qasrc = pa4 - A.s; P.bsrc = pb2 - B.s; P.qbsrc = pb4 - B.s;
-    P.n1 = (int32_t)na; P.n2 = (int32_t)nb; P.o = (int32_t)o; P.L = mrg_L(P.n1, P.n2, P.o);
+    P.L = mrg_L(P.n1, P.n2, P.o);
     return mrg_len(P);
 }
 
@@ -67,13 +64,13 @@ __device__ __forceinline__ void merge_fetch(const PairSide &A, const PairSide &B
     I.ins = d_insert[I.j];
 }
 
-// Workgroups stride over the blocks of 256 pairs; the counts leave with one set of atomics per workgroup of the launch.
+// Workgroups stride over the blocks of 256 pairs; the three sums leave with one set of atomics per workgroup of the launch
+// (wg_counts_flush, to the call's counts [0], [3], [4]).
 __global__ __launch_bounds__(MERGE_WG) void k_merge_sum(PairSide A, PairSide B, int64_t n_pairs, int64_t nblk,
                                                         const int32_t *__restrict__ d_insert, const int64_t *__restrict__ d_ord,
                                                         long long *__restrict__ bsum, unsigned int *__restrict__ brest,
                                                         MergeBlock *__restrict__ blk)
 {
-    __shared__ unsigned long long s_cnt[MERGE_WG / 64][3];
     unsigned long long c_m = 0, c_b = 0, c_o = 0;
     for (int64_t b = blockIdx.x; b < nblk; b += gridDim.x) {             // (uniform over the workgroup: barriers inside)
         const int64_t k = b * MERGE_WG + threadIdx.x;
@@ -91,16 +88,8 @@ __global__ __launch_bounds__(MERGE_WG) void k_merge_sum(PairSide A, PairSide B, 
         const int rest = __syncthreads_count(have && len == 0 ? 1 : 0);  // (and the scan's LDS may be written again)
         if (threadIdx.x == 0) { bsum[b] = tot; brest[b] = (unsigned int)rest; }
     }
-    const unsigned long long t_m = wave_sum_u64(c_m), t_b = wave_sum_u64(c_b), t_o = wave_sum_u64(c_o);
-    if ((threadIdx.x & 63) == 0) { s_cnt[threadIdx.x >> 6][0] = t_m; s_cnt[threadIdx.x >> 6][1] = t_b; s_cnt[threadIdx.x >> 6][2] = t_o; }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        unsigned long long s = 0;
-#pragma unroll
-        for (int w = 0; w < MERGE_WG / 64; w++) s += s_cnt[w][threadIdx.x];
-        const int at = threadIdx.x == 0 ? 0 : threadIdx.x == 1 ? 3 : 4;
-        if (s) atomicAdd(&blk->cnt[at], s);
-    }
+    const unsigned long long c[3] = {c_m, c_b, c_o};
+    wg_counts_flush<MERGE_WG, 0, 3, 4>(c, blk->cnt);
 }
 
 // One merged pair by a group of G lanes (gl: this lane's place in it): `o` = where its first byte goes, len > 0 its length.

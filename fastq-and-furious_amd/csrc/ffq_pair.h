@@ -85,17 +85,7 @@ __global__ __launch_bounds__(256) void k_pair_count(KeepPair keep, int64_t n, in
         c[3] += f2 && !f1 ? 1u : 0u;
         c[4] += f1 && f2 ? 1u : 0u;
     }
-    __shared__ unsigned long long s_cnt[4][PAIR_COUNTS];
-#pragma unroll
-    for (int k = 0; k < PAIR_COUNTS; k++) {
-        const unsigned long long t = wave_sum_u64(c[k]);
-        if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6][k] = t;
-    }
-    __syncthreads();
-    if (threadIdx.x < PAIR_COUNTS) {
-        const unsigned long long t = s_cnt[0][threadIdx.x] + s_cnt[1][threadIdx.x] + s_cnt[2][threadIdx.x] + s_cnt[3][threadIdx.x];
-        if (t) atomicAdd(&blk->cnt[threadIdx.x], t);
-    }
+    wg_counts_flush<256>(c, blk->cnt);
 }
 
 // ---- names -------------------------------------------------------------------------------------------------------------------
@@ -112,6 +102,27 @@ __device__ __forceinline__ bool pair_header(const PairSide &S, longlong2 r01, co
     h = S.d + (ok ? p0 + 1 - S.s : 0);
     n = ok ? p1 - p0 - 1 : 0;
     return ok;
+}
+
+// The geometry of a pair that has an insert size, for the passes that walk the mates' overlap (ffq_correct.h, ffq_merge.h).
+// True: both rows are eligible with both of their lines read (row_pos), neither has more than max_len bases, ins >= 0 and
+// mate 2 lies at o = ins - n2 with -n2 < o < n1.  P (CorPair, MrgPair) gets where the four lines begin in memory, n1, n2 and o
+// -- zeros if the pair fails.  Positions and ranges only: no byte of the reads is looked at.
+template <class Pair>
+__device__ __forceinline__ bool pair_geometry(const PairSide &A, const PairSide &B, longlong2 a23, longlong2 a45, longlong2 b23, longlong2 b45,
+                                              int32_t ins, int max_len, Pair &P)
+{
+    int64_t pa2 = 0, pa4 = 0, na = 0, pb2 = 0, pb4 = 0, nb = 0;
+    bool ok = row_pos<true, true>(A.nbytes, A.s, A.add, a23, a45, pa2, pa4, na);
+    ok = ok && row_pos<true, true>(B.nbytes, B.s, B.add, b23, b45, pb2, pb4, nb);
+    ok = ok && na <= max_len && nb <= max_len && ins >= 0;
+    const int64_t o = (int64_t)ins - nb;
+    ok = ok && -nb < o && o < na;
+    P.asrc = P.qasrc = P.bsrc = P.qbsrc = 0; P.n1 = P.n2 = P.o = 0;
+    if (!ok) return false;
+    P.asrc = pa2 - A.s; P.qasrc = pa4 - A.s; P.bsrc = pb2 - B.s; P.qbsrc = pb4 - B.s;
+    P.n1 = (int32_t)na; P.n2 = (int32_t)nb; P.o = (int32_t)o;
+    return true;
 }
 
 // place (0..3) of the first byte of x that is 0x20 or 0x09; 4: none.  (The zero-byte test may flag a byte ABOVE a true hit,
@@ -180,24 +191,21 @@ __global__ __launch_bounds__(PAIR_NAMES_WG) void k_pair_names(PairSide A, PairSi
             }
         }
     }
-    // wave, workgroup, one set of atomics (RowCounts::add_to's way)
-    __shared__ unsigned long long s_cnt[PAIR_NAMES_WG / 64][4];
+    // the three counts leave by wg_counts_flush; `first` is a MINIMUM: over the wave here, over the waves behind the flush's
+    // barrier, and one atomic per workgroup that has a different pair
+    __shared__ unsigned long long s_first[PAIR_NAMES_WG / 64];
 #pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        c_eq += __shfl_xor(c_eq, o); c_df += __shfl_xor(c_df, o); c_nc += __shfl_xor(c_nc, o);
-        first = min(first, (unsigned long long)__shfl_xor((long long)first, o));
-    }
-    if (lane == 0) { s_cnt[threadIdx.x >> 6][0] = c_eq; s_cnt[threadIdx.x >> 6][1] = c_df; s_cnt[threadIdx.x >> 6][2] = c_nc; s_cnt[threadIdx.x >> 6][3] = first; }
-    __syncthreads();
+    for (int o = 32; o >= 1; o >>= 1) first = min(first, (unsigned long long)__shfl_xor((long long)first, o));
+    if (lane == 0) s_first[threadIdx.x >> 6] = first;
+    const unsigned int c[3] = {c_eq, c_df, c_nc};
+    wg_counts_flush<PAIR_NAMES_WG>(c, &blk->equal);
     if (threadIdx.x == 0) {
-        unsigned long long t[3] = {0, 0, 0}, f = (unsigned long long)n_pairs;
+        unsigned long long f = s_first[0];
 #pragma unroll
-        for (int w = 0; w < PAIR_NAMES_WG / 64; w++) { t[0] += s_cnt[w][0]; t[1] += s_cnt[w][1]; t[2] += s_cnt[w][2]; f = min(f, s_cnt[w][3]); }
-        if (t[0]) atomicAdd(&blk->equal, t[0]);
-        if (t[1]) atomicAdd(&blk->different, t[1]);
-        if (t[2]) atomicAdd(&blk->not_compared, t[2]);
+        for (int w = 1; w < PAIR_NAMES_WG / 64; w++) f = min(f, s_first[w]);
         if (f < (unsigned long long)n_pairs) atomicMin(&blk->first, f);
     }
 }
+static_assert(offsetof(PairNamesBlock, different) == 8 && offsetof(PairNamesBlock, not_compared) == 16, "k_pair_names: the three counts in a row");
 
 }  // namespace ffq

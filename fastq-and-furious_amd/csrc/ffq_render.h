@@ -97,7 +97,6 @@ __global__ __launch_bounds__(RENDER_WG) void k_render_sum(int64_t nbytes, int s,
                                                           int64_t n_rows, int64_t nblk, long long *__restrict__ bsum,
                                                           RenderBlock *__restrict__ blk)
 {
-    __shared__ unsigned int s_cnt[RENDER_WG / 64];
     unsigned int cnt = 0;
     for (int64_t b = blockIdx.x; b < nblk; b += gridDim.x) {
         const int64_t row = b * RENDER_WG + threadIdx.x;
@@ -109,14 +108,9 @@ __global__ __launch_bounds__(RENDER_WG) void k_render_sum(int64_t nbytes, int s,
         cnt += (unsigned int)__popcll(__ballot(len > 0));
         __syncthreads();                                    // (the scan's LDS is written again by the next block of rows)
     }
-    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long c = 0;
-#pragma unroll
-        for (int w = 0; w < RENDER_WG / 64; w++) c += s_cnt[w];
-        if (c) atomicAdd(&blk->rendered, c);
-    }
+    // (cnt is the WAVE's count, the same in all of its lanes: one lane hands it in)
+    const unsigned int c[1] = {(threadIdx.x & 63) == 0 ? cnt : 0u};
+    wg_counts_flush<RENDER_WG>(c, &blk->rendered);
 }
 
 // bytes [a, b) of x into y

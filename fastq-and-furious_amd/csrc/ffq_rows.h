@@ -7,6 +7,7 @@
 //                list (long_list_append), and a second launch gives every listed row a whole wave (LongRows)
 //   row_pos      a row's buffer coordinates and whether its positions make it eligible
 //   row_edit_finish, RowCounts   what the two row-editing passes do with a row once they know its cut
+//   wg_counts_flush, lds_hist_flush   how a pass's counts and LDS histograms leave: one set of atomics per workgroup
 //   the small pieces: the unaligned dword, has_nl, wave_sum_u64, sums and maxima over a group, the newline looks
 // Every loop over rows is uniform over the wave: every group of a wave takes a step as long as one of them has a row, `have`
 // says whether this one does, and a group without a row -- or with a row that has nothing to do -- steps along.  What is done
@@ -35,6 +36,53 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long x)
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) x += (unsigned long long)__shfl_xor((long long)x, o);
     return x;
+}
+
+// ---- how a pass's counts leave ---------------------------------------------------------------------------------------------
+// A lane's N counts c[] summed over the wave, over the workgroup's waves through LDS, and added to dst[] with one atomic per
+// non-zero sum and WORKGROUP (device-wide atomics on a few addresses are served one at a time: DESIGN.md 4a, 4l).  Sum k goes
+// to dst[k], or -- with an index list AT..., one entry per count -- to dst[AT[k]].
+//   who calls it    every thread of the workgroup, once, at a point that is uniform over the workgroup: in front of it a
+//                   kernel may return only with all of its threads (k_seqkey_long's `n_long == 0`)
+//   what it costs   one barrier, and at most N atomics per workgroup; none for a sum of zero
+// A lane's counters stay as narrow as they are in its loop, and T is their type (unsigned, 32 or 64 bits): a WAVE's sum crosses
+// LDS as a T -- the lanes of a capped grid that count in 32 bits have waves that count far fewer than 2^32 --, the workgroup's
+// sum has 64 bits.  Counters of both widths are widened in the array built for the call.  c[k] is a LANE's share: a value the
+// whole wave already holds (a ballot's popcount) is handed in by one lane and as 0 by the others.  Hand in the counts there
+// are and no zeros to fill gaps between destinations: a padded array costs a register and LDS.
+template <int WG, int... AT, class T, int N>
+__device__ __forceinline__ void wg_counts_flush(const T (&c)[N], unsigned long long *__restrict__ dst)
+{
+    static_assert(sizeof...(AT) == 0 || sizeof...(AT) == N, "one destination per count");
+    __shared__ T s_cnt[WG / 64][N];
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+        const unsigned long long t = wave_sum_u64(c[k]);
+        if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6][k] = (T)t;
+    }
+    __syncthreads();
+    if (threadIdx.x < N) {
+        unsigned long long t = 0;
+#pragma unroll
+        for (int w = 0; w < WG / 64; w++) t += s_cnt[w][threadIdx.x];
+        [[maybe_unused]] int k = 0;
+        int at = threadIdx.x;
+        ((at = (int)threadIdx.x == k++ ? AT : at), ...);
+        if (t) atomicAdd(&dst[at], t);
+    }
+}
+
+// n 32-bit counters in LDS added to dst[0 .. n) with one 64-bit atomic per non-zero counter, and cleared if `clear`.  Every
+// thread of the workgroup calls it; the barriers -- in front of it, and behind it before the counters are counted in again --
+// are the caller's.
+template <int WG>
+__device__ __forceinline__ void lds_hist_flush(uint32_t *__restrict__ s, int n, unsigned long long *__restrict__ dst, bool clear = false)
+{
+    for (int i = threadIdx.x; i < n; i += WG) {
+        const uint32_t x = s[i];
+        if (clear) s[i] = 0;
+        if (x) atomicAdd(&dst[i], (unsigned long long)x);
+    }
 }
 
 // first lane of this lane's group whose bit is set in a wave ballot; G if none (gshift: the wave's lane of the group's first)
@@ -203,28 +251,15 @@ struct RowCounts {
     unsigned int changed = 0, skipped = 0;
     unsigned long long removed = 0;
 
-    // every thread of the workgroup is here: sums over the wave, over the workgroup's waves through LDS, and one set of
-    // atomics per workgroup (device-wide atomics on three addresses are served one at a time)
+    // every thread of the workgroup is here (wg_counts_flush)
     template <int WG>
     __device__ __forceinline__ void add_to(RowsBlock *__restrict__ blk) const
     {
-        __shared__ unsigned long long s_cnt[WG / 64][3];
-        unsigned int c = changed, k = skipped;
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) { c += __shfl_xor(c, o); k += __shfl_xor(k, o); }
-        const unsigned long long r = wave_sum_u64(removed);
-        if ((threadIdx.x & 63) == 0) { s_cnt[threadIdx.x >> 6][0] = c; s_cnt[threadIdx.x >> 6][1] = r; s_cnt[threadIdx.x >> 6][2] = k; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            unsigned long long t[3] = {0, 0, 0};
-#pragma unroll
-            for (int w = 0; w < WG / 64; w++) { t[0] += s_cnt[w][0]; t[1] += s_cnt[w][1]; t[2] += s_cnt[w][2]; }
-            if (t[0]) atomicAdd(&blk->changed, t[0]);
-            if (t[1]) atomicAdd(&blk->removed, t[1]);
-            if (t[2]) atomicAdd(&blk->skipped, t[2]);
-        }
+        const unsigned long long c[3] = {changed, removed, skipped};
+        wg_counts_flush<WG>(c, &blk->changed);
     }
 };
+static_assert(offsetof(RowsBlock, removed) == 8 && offsetof(RowsBlock, skipped) == 16, "RowCounts::add_to: changed, removed, skipped in a row");
 
 // the 48 bytes of a row by the first three lanes of its group
 __device__ __forceinline__ void row_store(int64_t *__restrict__ out, int64_t row, int gl, longlong2 a, longlong2 b, longlong2 c)

@@ -112,23 +112,13 @@ __device__ __forceinline__ void stats_flush_tile(uint32_t *__restrict__ s_tile, 
     }
 }
 
-// n_bins counters added to out[0 .. n_bins) and cleared
-__device__ __forceinline__ void stats_flush_hist(uint32_t *__restrict__ s_h, int n_bins, stats_u64 *__restrict__ out)
-{
-    for (int i = threadIdx.x; i < n_bins; i += STATS_WG) {
-        const uint32_t x = s_h[i];
-        s_h[i] = 0;
-        if (x) atomicAdd(&out[i], (stats_u64)x);
-    }
-}
-
-// the three per-read histograms (n_len bins of the first)
+// the three per-read histograms (n_len bins of the first) added to the block and cleared
 __device__ __forceinline__ void stats_flush_reads(uint32_t *__restrict__ s_len, int n_len, uint32_t *__restrict__ s_rq,
                                                   uint32_t *__restrict__ s_gc, int C, stats_u64 *__restrict__ out)
 {
-    stats_flush_hist(s_len, n_len, out + 8 + (int64_t)C * 101);
-    stats_flush_hist(s_rq, STATS_QBINS, out + 8 + (int64_t)C * 102 + 1);
-    stats_flush_hist(s_gc, STATS_GCBINS, out + 8 + (int64_t)C * 102 + 1 + STATS_QBINS);
+    lds_hist_flush<STATS_WG>(s_len, n_len, out + 8 + (int64_t)C * 101, true);
+    lds_hist_flush<STATS_WG>(s_rq, STATS_QBINS, out + 8 + (int64_t)C * 102 + 1, true);
+    lds_hist_flush<STATS_WG>(s_gc, STATS_GCBINS, out + 8 + (int64_t)C * 102 + 1 + STATS_QBINS, true);
 }
 
 // once per step of the three kernels, by every thread of the workgroup: every STATS_ROUND steps the workgroup flushes its counters (Wrap, above)
@@ -146,23 +136,8 @@ struct StatsRound {
     }
 };
 
-// every thread of the workgroup is here: the head sums over the wave, over the waves through LDS, one set of atomics
-__device__ __forceinline__ void stats_add_head(stats_u64 *__restrict__ out, StatsHead h)
-{
-    __shared__ stats_u64 s_head[STATS_WG / 64][7];
-#pragma unroll
-    for (int k = 0; k < 7; k++) {
-        const stats_u64 t = wave_sum_u64(h.v[k]);
-        if ((threadIdx.x & 63) == 0) s_head[threadIdx.x >> 6][k] = t;
-    }
-    __syncthreads();
-    if (threadIdx.x < 7) {
-        stats_u64 t = 0;
-#pragma unroll
-        for (int w = 0; w < STATS_WG / 64; w++) t += s_head[w][threadIdx.x];
-        if (t) atomicAdd(&out[threadIdx.x], t);
-    }
-}
+// every thread of the workgroup is here: the seven head sums to out[0 .. 7) (wg_counts_flush)
+__device__ __forceinline__ void stats_add_head(stats_u64 *__restrict__ out, const StatsHead &h) { wg_counts_flush<STATS_WG>(h.v, out); }
 
 // the per-read counts of one eligible row of n bases (one lane of its group or wave); T: wide enough for 100 * n
 template <class T>

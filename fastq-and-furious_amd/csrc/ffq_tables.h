@@ -48,6 +48,30 @@ static int no_rows_offsets(ffq_ctx *c, int64_t *d_off)
 // a mate's buffer and table as the pair kernels take them
 static PairSide pair_side(const ffq_table_view *m) { return PairSide{m->d_buf, m->n_bytes, m->sentinel ? 1 : 0, m->add, m->d_table}; }
 
+// a buffer behind either view that has bytes; to_what: the call's words for what it reads them for
+static int pair_bufs(const char *who, const ffq_table_view *m1, const ffq_table_view *m2, const char *to_what)
+{
+    if ((m1->n_bytes > 0 && !m1->d_buf) || (m2->n_bytes > 0 && !m2->d_buf)) return fail(FFQ_E_ARG, "%s: no buffer to %s", who, to_what);
+    return FFQ_OK;
+}
+
+// What the calls on two tables of mates check and set up alike, in the order a call with two bad arguments is answered in:
+// the context, args_ok (the caller's own pointers) and the two views; own() -- the checks that are the call's alone --; a buffer
+// behind the views (to_what NULL: the call does not read the mates' bytes, or looks for the buffers itself, in own() or later);
+// no scan pending; the device.
+template <class Own>
+static int pairs_begin(ffq_ctx *c, const char *who, bool args_ok, const ffq_table_view *m1, const ffq_table_view *m2, int64_t n_pairs,
+                       const char *to_what, Own own)
+{
+    if (!c || !args_ok || n_pairs < 0 || !view_ok(m1, n_pairs) || !view_ok(m2, n_pairs)) return fail(FFQ_E_ARG, "%s: bad argument", who);
+    int rc = own();
+    if (!rc && to_what) rc = pair_bufs(who, m1, m2, to_what);
+    if (!rc) rc = no_pending(c, who);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    return FFQ_OK;
+}
+
 // The counters of a call, one block per context: calls on a context follow one another, so one block serves all of them.  B is
 // the call's block type, at the head of the context's words.  begin: cleared on the stream, the device's copy handed back;
 // end: copied to the pinned half and waited for -- the call's one host wait -- and that half handed back.
@@ -286,6 +310,23 @@ static int rows_end(ffq_ctx *c, int64_t stats[3])
     return FFQ_OK;
 }
 
+// A row-editing pass from its call to its counters: the frame of the four trims.  arg_rc: what the pass's own check of its
+// parameters said; launch(st, s, blk): its two launches, the short rows' and the long rows', on the context's stream.
+template <class Launch>
+static int rows_edit(ffq_ctx *c, const char *who, int arg_rc, const uint8_t *d_buf, int64_t n_bytes, int sentinel, const int64_t *d_table,
+                     int64_t n_rows, int64_t *d_out, int64_t stats[3], Launch launch)
+{
+    mark_other(c);
+    RowsBlock *blk = nullptr;
+    int rc = arg_rc;
+    if (!rc) rc = rows_begin(c, who, stats != nullptr, d_buf, n_bytes, d_table, n_rows, d_out, &blk);
+    if (rc) return rc;
+    stats[0] = stats[1] = stats[2] = 0;
+    if (n_rows == 0) return FFQ_OK;
+    launch(c->stream, sentinel ? 1 : 0, blk);
+    return rows_end(c, stats);
+}
+
 // parameters of a quality trim and of a statistics call, checked: for the table calls and for the stream's setters
 static int trim_arg(const char *who, int qual_base, int cutoff_front, int cutoff_back)
 {
@@ -305,20 +346,14 @@ extern "C" int ffq_table_trim_quality(ffq_ctx *c, const uint8_t *d_buf, int64_t 
                                       const int64_t *d_table, int64_t n_rows, int qual_base, int cutoff_front,
                                       int cutoff_back, int64_t *d_out, int64_t stats[3])
 {
-    mark_other(c);
-    int rc = trim_arg("ffq_table_trim_quality", qual_base, cutoff_front, cutoff_back);
-    RowsBlock *blk = nullptr;
-    if (!rc) rc = rows_begin(c, "ffq_table_trim_quality", stats != nullptr, d_buf, n_bytes, d_table, n_rows, d_out, &blk);
-    if (rc) return rc;
-    stats[0] = stats[1] = stats[2] = 0;
-    if (n_rows == 0) return FFQ_OK;
-    hipStream_t st = c->stream;
-    hipLaunchKernelGGL(k_trim_rows, dim3(rows_grid(n_rows, TRIM_WG / ROWS_G, EDIT_GRID_SHORT)), dim3(TRIM_WG), 0, st, d_buf, n_bytes,
-                       sentinel ? 1 : 0, add, d_table, n_rows, qual_base, cutoff_front, cutoff_back, d_out, c->rows_list, blk);
-    hipLaunchKernelGGL(k_trim_long, dim3(rows_grid(n_rows, TRIM_WG / 64, EDIT_GRID_LONG)), dim3(TRIM_WG), 0, st, d_buf, n_bytes,
-                       sentinel ? 1 : 0, add, d_table, qual_base, cutoff_front, cutoff_back, d_out, (const int64_t *)c->rows_list,
-                       blk);
-    return rows_end(c, stats);
+    static const char *const who = "ffq_table_trim_quality";
+    return rows_edit(c, who, trim_arg(who, qual_base, cutoff_front, cutoff_back), d_buf, n_bytes, sentinel, d_table, n_rows, d_out, stats,
+                     [&](hipStream_t st, int s, RowsBlock *blk) {
+        hipLaunchKernelGGL(k_trim_rows, dim3(rows_grid(n_rows, TRIM_WG / ROWS_G, EDIT_GRID_SHORT)), dim3(TRIM_WG), 0, st, d_buf, n_bytes, s,
+                           add, d_table, n_rows, qual_base, cutoff_front, cutoff_back, d_out, c->rows_list, blk);
+        hipLaunchKernelGGL(k_trim_long, dim3(rows_grid(n_rows, TRIM_WG / 64, EDIT_GRID_LONG)), dim3(TRIM_WG), 0, st, d_buf, n_bytes, s,
+                           add, d_table, qual_base, cutoff_front, cutoff_back, d_out, (const int64_t *)c->rows_list, blk);
+    });
 }
 
 // parameters of an adapter call, checked; the adapter's bytes and its wildcard mask as the kernels take them
@@ -341,22 +376,15 @@ extern "C" int ffq_table_trim_adapter(ffq_ctx *c, const uint8_t *d_buf, int64_t 
                                       const int64_t *d_table, int64_t n_rows, const uint8_t *adapter, int adapter_len,
                                       int err_permille, int min_overlap, int64_t *d_out, int64_t stats[3])
 {
-    mark_other(c);
+    static const char *const who = "ffq_table_trim_adapter";
     AdapterArg ad;
-    int rc = adapter_arg("ffq_table_trim_adapter", adapter, adapter_len, err_permille, min_overlap, &ad);
-    RowsBlock *blk = nullptr;
-    if (!rc) rc = rows_begin(c, "ffq_table_trim_adapter", stats != nullptr, d_buf, n_bytes, d_table, n_rows, d_out, &blk);
-    if (rc) return rc;
-    stats[0] = stats[1] = stats[2] = 0;
-    if (n_rows == 0) return FFQ_OK;
-    hipStream_t st = c->stream;
-    hipLaunchKernelGGL(k_adapter_rows, dim3(rows_grid(n_rows, ADAPTER_WG / ROWS_G, EDIT_GRID_SHORT)), dim3(ADAPTER_WG), 0, st, d_buf,
-                       n_bytes, sentinel ? 1 : 0, add, d_table, n_rows, ad, adapter_len, err_permille, min_overlap, d_out,
-                       c->rows_list, blk);
-    hipLaunchKernelGGL(k_adapter_long, dim3(rows_grid(n_rows, ADAPTER_WG / 64, EDIT_GRID_LONG)), dim3(ADAPTER_WG), 0, st, d_buf,
-                       n_bytes, sentinel ? 1 : 0, add, d_table, ad, adapter_len, err_permille, min_overlap, d_out,
-                       (const int64_t *)c->rows_list, blk);
-    return rows_end(c, stats);
+    return rows_edit(c, who, adapter_arg(who, adapter, adapter_len, err_permille, min_overlap, &ad), d_buf, n_bytes, sentinel, d_table, n_rows,
+                     d_out, stats, [&](hipStream_t st, int s, RowsBlock *blk) {
+        hipLaunchKernelGGL(k_adapter_rows, dim3(rows_grid(n_rows, ADAPTER_WG / ROWS_G, EDIT_GRID_SHORT)), dim3(ADAPTER_WG), 0, st, d_buf,
+                           n_bytes, s, add, d_table, n_rows, ad, adapter_len, err_permille, min_overlap, d_out, c->rows_list, blk);
+        hipLaunchKernelGGL(k_adapter_long, dim3(rows_grid(n_rows, ADAPTER_WG / 64, EDIT_GRID_LONG)), dim3(ADAPTER_WG), 0, st, d_buf,
+                           n_bytes, s, add, d_table, ad, adapter_len, err_permille, min_overlap, d_out, (const int64_t *)c->rows_list, blk);
+    });
 }
 
 // parameters of a poly-tail call, checked: for the table call and for ffq_stream_set_poly
@@ -371,19 +399,14 @@ static int poly_arg(const char *who, int base, int min_len)
 extern "C" int ffq_table_trim_poly(ffq_ctx *c, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
                                    const int64_t *d_table, int64_t n_rows, int base, int min_len, int64_t *d_out, int64_t stats[3])
 {
-    mark_other(c);
-    int rc = poly_arg("ffq_table_trim_poly", base, min_len);
-    RowsBlock *blk = nullptr;
-    if (!rc) rc = rows_begin(c, "ffq_table_trim_poly", stats != nullptr, d_buf, n_bytes, d_table, n_rows, d_out, &blk);
-    if (rc) return rc;
-    stats[0] = stats[1] = stats[2] = 0;
-    if (n_rows == 0) return FFQ_OK;
-    hipStream_t st = c->stream;
-    hipLaunchKernelGGL(k_poly_rows, dim3(rows_grid(n_rows, POLY_WG / ROWS_G, EDIT_GRID_SHORT)), dim3(POLY_WG), 0, st, d_buf, n_bytes,
-                       sentinel ? 1 : 0, add, d_table, n_rows, base, min_len, d_out, c->rows_list, blk);
-    hipLaunchKernelGGL(k_poly_long, dim3(rows_grid(n_rows, POLY_WG / 64, EDIT_GRID_LONG)), dim3(POLY_WG), 0, st, d_buf, n_bytes,
-                       sentinel ? 1 : 0, add, d_table, base, min_len, d_out, (const int64_t *)c->rows_list, blk);
-    return rows_end(c, stats);
+    static const char *const who = "ffq_table_trim_poly";
+    return rows_edit(c, who, poly_arg(who, base, min_len), d_buf, n_bytes, sentinel, d_table, n_rows, d_out, stats,
+                     [&](hipStream_t st, int s, RowsBlock *blk) {
+        hipLaunchKernelGGL(k_poly_rows, dim3(rows_grid(n_rows, POLY_WG / ROWS_G, EDIT_GRID_SHORT)), dim3(POLY_WG), 0, st, d_buf, n_bytes, s,
+                           add, d_table, n_rows, base, min_len, d_out, c->rows_list, blk);
+        hipLaunchKernelGGL(k_poly_long, dim3(rows_grid(n_rows, POLY_WG / 64, EDIT_GRID_LONG)), dim3(POLY_WG), 0, st, d_buf, n_bytes, s,
+                           add, d_table, base, min_len, d_out, (const int64_t *)c->rows_list, blk);
+    });
 }
 
 // the rules of an ends call, checked, as the kernels take them: for the table call and for ffq_stream_set_ends
@@ -408,20 +431,15 @@ static int ends_arg(const char *who, const ffq_ends_rules *r, EndsRules *R)
 extern "C" int ffq_table_trim_ends(ffq_ctx *c, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
                                    const int64_t *d_table, int64_t n_rows, const ffq_ends_rules *rules, int64_t *d_out, int64_t stats[3])
 {
-    mark_other(c);
+    static const char *const who = "ffq_table_trim_ends";
     EndsRules R;
-    int rc = ends_arg("ffq_table_trim_ends", rules, &R);
-    RowsBlock *blk = nullptr;
-    if (!rc) rc = rows_begin(c, "ffq_table_trim_ends", stats != nullptr, d_buf, n_bytes, d_table, n_rows, d_out, &blk);
-    if (rc) return rc;
-    stats[0] = stats[1] = stats[2] = 0;
-    if (n_rows == 0) return FFQ_OK;
-    hipStream_t st = c->stream;
-    hipLaunchKernelGGL(k_ends_rows, dim3(rows_grid(n_rows, ENDS_WG / ROWS_G, EDIT_GRID_SHORT)), dim3(ENDS_WG), 0, st, d_buf, n_bytes,
-                       sentinel ? 1 : 0, add, d_table, n_rows, R, d_out, c->rows_list, blk);
-    hipLaunchKernelGGL(k_ends_long, dim3(rows_grid(n_rows, ENDS_WG / 64, EDIT_GRID_LONG)), dim3(ENDS_WG), 0, st, d_buf, n_bytes,
-                       sentinel ? 1 : 0, add, d_table, R, d_out, (const int64_t *)c->rows_list, blk);
-    return rows_end(c, stats);
+    return rows_edit(c, who, ends_arg(who, rules, &R), d_buf, n_bytes, sentinel, d_table, n_rows, d_out, stats,
+                     [&](hipStream_t st, int s, RowsBlock *blk) {
+        hipLaunchKernelGGL(k_ends_rows, dim3(rows_grid(n_rows, ENDS_WG / ROWS_G, EDIT_GRID_SHORT)), dim3(ENDS_WG), 0, st, d_buf, n_bytes, s,
+                           add, d_table, n_rows, R, d_out, c->rows_list, blk);
+        hipLaunchKernelGGL(k_ends_long, dim3(rows_grid(n_rows, ENDS_WG / 64, EDIT_GRID_LONG)), dim3(ENDS_WG), 0, st, d_buf, n_bytes, s,
+                           add, d_table, R, d_out, (const int64_t *)c->rows_list, blk);
+    });
 }
 
 static_assert(STATS_QBINS == FFQ_STATS_QBINS && STATS_GCBINS == FFQ_STATS_GCBINS && STATS_HEAD == FFQ_STATS_HEAD &&
@@ -556,11 +574,11 @@ extern "C" int ffq_table_select_pairs(ffq_ctx *c, const ffq_table_view *m1, cons
     if (rc) return rc;
     if (pair_filter != FFQ_PAIR_ANY && pair_filter != FFQ_PAIR_BOTH && pair_filter != FFQ_PAIR_FIRST)
         return fail(FFQ_E_ARG, "%s: pair_filter is FFQ_PAIR_ANY, FFQ_PAIR_BOTH or FFQ_PAIR_FIRST", who);
-    if (!c || !len_bounds || !n_out || !hist1 || !hist2 || !pairs || n_pairs < 0 || !view_ok(m1, n_pairs) || !view_ok(m2, n_pairs) ||
-        (n_pairs > 0 && (!d_out1 || !d_out2)))
-        return fail(FFQ_E_ARG, "%s: bad argument", who);
-    if (!aligned({d_out1, d_out2}, 16)) return fail(FFQ_E_ARG, "%s: tables must be 16-byte aligned", who);
-    if ((rc = no_pending(c, who))) return rc;
+    // (which mates' buffers are read depends on the rules: looked for below)
+    rc = pairs_begin(c, who, len_bounds && n_out && hist1 && hist2 && pairs && (n_pairs <= 0 || (d_out1 && d_out2)), m1, m2, n_pairs, nullptr, [&] {
+        return aligned({d_out1, d_out2}, 16) ? FFQ_OK : fail(FFQ_E_ARG, "%s: tables must be 16-byte aligned", who);
+    });
+    if (rc) return rc;
     const ffq_table_view *m[2] = {m1, m2};
     int64_t *hist[2] = {hist1, hist2};
     const int n_judged = pair_filter == FFQ_PAIR_FIRST ? 1 : 2;
@@ -570,7 +588,6 @@ extern "C" int ffq_table_select_pairs(ffq_ctx *c, const ffq_table_view *m1, cons
         return fail(FFQ_E_ARG, "%s: d_out1 and d_out2 must not be one of the tables, or each other", who);
     for (int i = 0; i < FFQ_FILTER_COUNTS; i++) hist1[i] = hist2[i] = 0;
     for (int i = 0; i < PAIR_COUNTS; i++) pairs[i] = 0;
-    HIPCHK(hipSetDevice(c->device));
     *n_out = 0;
     if (n_pairs == 0) return FFQ_OK;
     const int64_t nblk = (n_pairs + 255) / 256;
@@ -616,10 +633,7 @@ extern "C" int ffq_table_pair_names(ffq_ctx *c, const ffq_table_view *m1, const 
 {
     static const char *const who = "ffq_table_pair_names";
     mark_other(c);
-    if (!c || !out || n_pairs < 0 || !view_ok(m1, n_pairs) || !view_ok(m2, n_pairs)) return fail(FFQ_E_ARG, "%s: bad argument", who);
-    if ((m1->n_bytes > 0 && !m1->d_buf) || (m2->n_bytes > 0 && !m2->d_buf)) return fail(FFQ_E_ARG, "%s: no buffer to read the headers from", who);
-    if (int rc = no_pending(c, who)) return rc;
-    HIPCHK(hipSetDevice(c->device));
+    if (int rc = pairs_begin(c, who, out != nullptr, m1, m2, n_pairs, "read the headers from", [] { return FFQ_OK; })) return rc;
     out[0] = out[1] = out[2] = 0; out[3] = -1;
     if (n_pairs == 0) return FFQ_OK;
     hipStream_t st = c->stream;
@@ -658,13 +672,12 @@ extern "C" int ffq_table_pair_overlap(ffq_ctx *c, const ffq_table_view *m1, cons
     mark_other(c);
     int rc = overlap_arg(who, rules);
     if (rc) return rc;
-    if (!c || !counts || n_pairs < 0 || !view_ok(m1, n_pairs) || !view_ok(m2, n_pairs) || (n_pairs > 0 && (!d_out1 || !d_out2)))
-        return fail(FFQ_E_ARG, "%s: bad argument", who);
-    if (!aligned({d_out1, d_out2}, 16)) return fail(FFQ_E_ARG, "%s: tables must be 16-byte aligned", who);
-    if (!aligned({d_hist}, 8) || !aligned({d_insert}, 4)) return fail(FFQ_E_ARG, "%s: d_hist must be 8-byte aligned, d_insert 4-byte aligned", who);
-    if ((m1->n_bytes > 0 && !m1->d_buf) || (m2->n_bytes > 0 && !m2->d_buf)) return fail(FFQ_E_ARG, "%s: no buffer to read the sequences from", who);
-    if ((rc = no_pending(c, who))) return rc;
-    HIPCHK(hipSetDevice(c->device));
+    rc = pairs_begin(c, who, counts && (n_pairs <= 0 || (d_out1 && d_out2)), m1, m2, n_pairs, "read the sequences from", [&]() -> int {
+        if (!aligned({d_out1, d_out2}, 16)) return fail(FFQ_E_ARG, "%s: tables must be 16-byte aligned", who);
+        if (!aligned({d_hist}, 8) || !aligned({d_insert}, 4)) return fail(FFQ_E_ARG, "%s: d_hist must be 8-byte aligned, d_insert 4-byte aligned", who);
+        return FFQ_OK;
+    });
+    if (rc) return rc;
     for (int i = 0; i < OVERLAP_COUNTS; i++) counts[i] = 0;
     hipStream_t st = c->stream;
     if (d_hist && !accumulate) HIPCHK(hipMemsetAsync(d_hist, 0, (size_t)OVERLAP_HIST * 8, st));
@@ -795,25 +808,26 @@ extern "C" int ffq_table_pair_merge(ffq_ctx *c, const ffq_table_view *m1, const 
 {
     static const char *const who = "ffq_table_pair_merge";
     mark_other(c);
-    if (!c || !counts || !n_rest || n_pairs < 0 || text_cap < 0 || (text_cap > 0 && !d_text) || !view_ok(m1, n_pairs) || !view_ok(m2, n_pairs) ||
-        (n_pairs > 0 && (!d_rest1 || !d_rest2)))
-        return fail(FFQ_E_ARG, "%s: bad argument", who);
-    if (n_pairs > 0 && !d_insert) return fail(FFQ_E_ARG, "%s: no insert sizes (d_insert)", who);
-    if (!aligned({d_rest1, d_rest2}, 16)) return fail(FFQ_E_ARG, "%s: tables must be 16-byte aligned", who);
-    if (!aligned({d_off, d_ord, d_rest_ord}, 8) || !aligned({d_insert}, 4))
-        return fail(FFQ_E_ARG, "%s: d_off, d_ord and d_rest_ord must be 8-byte aligned, d_insert 4-byte aligned", who);
-    if ((m1->n_bytes > 0 && !m1->d_buf) || (m2->n_bytes > 0 && !m2->d_buf)) return fail(FFQ_E_ARG, "%s: no buffer to read the mates from", who);
-    if (n_pairs > 0 && (d_rest1 == m1->d_table || d_rest1 == m2->d_table || d_rest2 == m1->d_table || d_rest2 == m2->d_table || d_rest1 == d_rest2))
-        return fail(FFQ_E_ARG, "%s: d_rest1 and d_rest2 must not be one of the tables, or each other", who);
-    if (int rc = no_pending(c, who)) return rc;
-    HIPCHK(hipSetDevice(c->device));
+    // (the rest tables are told from the mates' behind the look for the buffers: that look is in own())
+    int rc = pairs_begin(c, who, counts && n_rest && text_cap >= 0 && (text_cap == 0 || d_text) && (n_pairs <= 0 || (d_rest1 && d_rest2)), m1, m2,
+                         n_pairs, nullptr, [&]() -> int {
+        if (n_pairs > 0 && !d_insert) return fail(FFQ_E_ARG, "%s: no insert sizes (d_insert)", who);
+        if (!aligned({d_rest1, d_rest2}, 16)) return fail(FFQ_E_ARG, "%s: tables must be 16-byte aligned", who);
+        if (!aligned({d_off, d_ord, d_rest_ord}, 8) || !aligned({d_insert}, 4))
+            return fail(FFQ_E_ARG, "%s: d_off, d_ord and d_rest_ord must be 8-byte aligned, d_insert 4-byte aligned", who);
+        if (int e = pair_bufs(who, m1, m2, "read the mates from")) return e;
+        if (n_pairs > 0 && (d_rest1 == m1->d_table || d_rest1 == m2->d_table || d_rest2 == m1->d_table || d_rest2 == m2->d_table || d_rest1 == d_rest2))
+            return fail(FFQ_E_ARG, "%s: d_rest1 and d_rest2 must not be one of the tables, or each other", who);
+        return FFQ_OK;
+    });
+    if (rc) return rc;
     for (int i = 0; i < MERGE_COUNTS; i++) counts[i] = 0;
     *n_rest = 0;
     hipStream_t st = c->stream;
     if (n_pairs == 0) return no_rows_offsets(c, d_off);
     const int64_t nblk = (n_pairs + MERGE_WG - 1) / MERGE_WG;
     // (everything is grown before anything is enqueued: growing waits for the stream)
-    int rc = grow_dev(c, c->col_sum, nblk);
+    rc = grow_dev(c, c->col_sum, nblk);
     if (!rc) rc = grow_dev(c, c->sel_cnt, nblk);
     if (!rc) rc = grow_dev(c, c->sel_base, nblk);
     if (rc) return rc;
@@ -863,12 +877,12 @@ extern "C" int ffq_table_pair_correct(ffq_ctx *c, const ffq_table_view *m1, cons
     mark_other(c);
     int rc = correct_arg(who, rules);
     if (rc) return rc;
-    if (!c || !counts || n_pairs < 0 || !view_ok(m1, n_pairs) || !view_ok(m2, n_pairs)) return fail(FFQ_E_ARG, "%s: bad argument", who);
-    if (n_pairs > 0 && !d_insert) return fail(FFQ_E_ARG, "%s: no insert sizes (d_insert)", who);
-    if (!aligned({d_insert}, 4)) return fail(FFQ_E_ARG, "%s: d_insert must be 4-byte aligned", who);
-    if ((m1->n_bytes > 0 && !m1->d_buf) || (m2->n_bytes > 0 && !m2->d_buf)) return fail(FFQ_E_ARG, "%s: no buffer to correct the mates in", who);
-    if ((rc = no_pending(c, who))) return rc;
-    HIPCHK(hipSetDevice(c->device));
+    rc = pairs_begin(c, who, counts != nullptr, m1, m2, n_pairs, "correct the mates in", [&]() -> int {
+        if (n_pairs > 0 && !d_insert) return fail(FFQ_E_ARG, "%s: no insert sizes (d_insert)", who);
+        if (!aligned({d_insert}, 4)) return fail(FFQ_E_ARG, "%s: d_insert must be 4-byte aligned", who);
+        return FFQ_OK;
+    });
+    if (rc) return rc;
     for (int i = 0; i < CORRECT_COUNTS; i++) counts[i] = 0;
     if (matrix) for (int i = 0; i < CORRECT_MATRIX; i++) matrix[i] = 0;
     if (n_pairs == 0) return FFQ_OK;
