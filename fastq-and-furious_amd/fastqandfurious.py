@@ -522,6 +522,18 @@ def _ends_pos(buf, pos, rules, qual_base):
     return pos, n - (b - a)
 
 
+def _report(given, cls):
+    """The report a plan fills, which it then always has: the caller's -- reset in place, not added to -- or, given None, a
+    private one of `cls`.  Every report fills from the count vectors hip returns, with one _add_counts (_from_counts: totals)."""
+    if given is None:
+        return cls()
+    if isinstance(given, cls):
+        given.__init__()                         # (a subclass resets what it added)
+    else:
+        given.__dict__.update(cls().__dict__)    # (overlap, merge, correction: any object will do, as it did)
+    return given
+
+
 class EndsReport:
     """What filter_fastq / filter_fastq_paired (ends_report=...) fill: reads_cut, the reads the ends step (EndRules) changed,
     and bases_cut, the bases it removed.  Both mates of a pair are added together; every record counts, the dropped ones
@@ -529,6 +541,11 @@ class EndsReport:
 
     def __init__(self):
         self.reads_cut = self.bases_cut = 0
+
+    def _add_counts(self, counts):
+        """(rows changed, bases removed, ...) of the ends step (hip: ends_trimmed)"""
+        self.reads_cut += counts[0]
+        self.bases_cut += counts[1]
 
 
 class PolyReport:
@@ -538,6 +555,14 @@ class PolyReport:
 
     def __init__(self):
         self.poly_g_reads = self.poly_g_bases = self.poly_x_reads = self.poly_x_bases = 0
+
+    def _add_counts(self, counts):
+        """((rows changed, bases removed, ...) by poly-G, the same by poly-X) (hip: poly_trimmed)"""
+        g, x = counts
+        self.poly_g_reads += g[0]
+        self.poly_g_bases += g[1]
+        self.poly_x_reads += x[0]
+        self.poly_x_bases += x[1]
 
 
 class entryfunc_adaptertrim:
@@ -1174,13 +1199,11 @@ class DedupReport:
 
 
 class _HostDedup:
-    """The set on the host route: a dict of keys.  key(): of a record as scanned; keep(): is the record (of that key) written?"""
+    """The set on the host route: a set of keys, and the DedupReport it counts into.  key(): of a record as scanned; keep(): is
+    the record (of that key) written?"""
 
     def __init__(self, rules, report):
-        self.drop = not rules.count_only
-        self.report = report if report is not None else DedupReport()
-        self.report.__init__()
-        self.seen = set()
+        self.drop, self.report, self.seen = not rules.count_only, report, set()
 
     @staticmethod
     def key(buf, pos):
@@ -1270,7 +1293,8 @@ class CompressReport:
     def ratio(self):
         return self.bytes_in / self.bytes_out if self.bytes_out else 0.0
 
-    def _add(self, stats):
+    def _add_counts(self, stats):
+        """(bytes in, bytes out, members, members stored) (hip: compressed, merged_bgzf)"""
         self.bytes_in += stats[0]
         self.bytes_out += stats[1]
         self.members += stats[2]
@@ -1284,8 +1308,7 @@ def _check_compress(compress, compress_report):
         raise ValueError("compress_report needs compress")
     if compress_report is not None and not isinstance(compress_report, CompressReport):
         raise TypeError("compress_report must be a CompressReport")
-    if compress_report is not None:
-        compress_report.__init__()
+    return _report(compress_report, CompressReport)         # (the one to fill)
 
 
 class _BgzfSink:
@@ -1299,15 +1322,13 @@ class _BgzfSink:
     def members(self, members, stats):
         if stats[1]:
             self.fh.write(memoryview(members))
-        if self.report is not None:
-            self.report._add(stats)
+        self.report._add_counts(stats)
 
     def _block(self, chunk):
         from . import bgzf
         m = bgzf.block(chunk, 1)
         self.fh.write(m)
-        if self.report is not None:
-            self.report._add((len(chunk), len(m), 1, int((m[18] & 6) == 0)))
+        self.report._add_counts((len(chunk), len(m), 1, int((m[18] & 6) == 0)))
 
     def write(self, text):
         self.buf += text
@@ -1323,27 +1344,46 @@ class _BgzfSink:
         self.fh.write(_hip.BGZF_EOF)
 
 
+class _MateSettings:
+    """What filter_fastq's one _MatePlan and filter_fastq_paired's two are built from beside each file's own arguments: the
+    settings the mates share, with the three reports the plans ADD to checked -- poly, ends, compress: in this order -- and made
+    (_report).  ends: the file's EndRules or, of a pair, one that is on for some mate; None: none is."""
+
+    def __init__(self, quality_cutoff, qual_base, err_permille, min_overlap, content, poly_g, poly_x, poly_report, compress,
+                 compress_report, ends, ends_report):
+        self.quality_cutoff, self.qual_base, self.err_permille, self.min_overlap = quality_cutoff, qual_base, err_permille, min_overlap
+        self.content, self.poly_g, self.poly_x, self.compress = content, poly_g, poly_x, compress
+        if poly_report is not None and not isinstance(poly_report, PolyReport):
+            raise TypeError("poly_report must be a PolyReport")
+        self.poly_report = _report(poly_report, PolyReport)
+        if _check_ends(ends) is None and ends_report is not None:
+            raise ValueError("ends_report needs ends")
+        if ends_report is not None and not isinstance(ends_report, EndsReport):
+            raise TypeError("ends_report must be an EndsReport")
+        self.ends_report = _report(ends_report, EndsReport)
+        self.compress_report = _check_compress(compress, compress_report)
+
+
 class _MatePlan:
     """What the records of ONE input file go through in filter_fastq (one plan) and filter_fastq_paired (one per mate), said
     once for both routes: the ends (an EndRules), quality trim, poly-G, adapter trim, poly-X, the verdict by length and then by
-    content, the counts, the text.  poly_report / ends_report: a PolyReport / an EndsReport the plan ADDS to (a pair's two plans
-    share one; the caller resets it).  On the
+    content, the counts, the text.  shared: the _MateSettings of the call -- a pair's two plans ADD to one PolyReport, one
+    EndsReport and one CompressReport; the rest is this file's own.  On the
     device route the plan configures the file's stream and drains every fill (or round) of it; on the host route it is
     called record by record.  judged=False: the mate is trimmed, counted and written but never dropped (pair_filter "first").
     `dropped`: this file's records by the reason (ContentRules.REASONS) they failed for; `report` (a FilterReport or None) is
     reset and bound to it.  compress ("bgzf" or None): the text is written as BGZF -- sink() wraps an output file for it,
-    and everything that is written goes through what sink() returned; compress_report: a CompressReport the plan's sinks ADD to."""
+    and everything that is written goes through what sink() returned."""
 
-    def __init__(self, quality_cutoff, qual_base, adapter, err_permille, min_overlap, min_len, max_len, content, report, judged=True,
-                 dedup=None, poly_g=None, poly_x=None, poly_report=None, compress=None, compress_report=None, ends=None,
-                 ends_report=None):
-        self.qual_base, self.content, self.report, self.judged = qual_base, content, report, judged
-        self.ends, self.ends_report = _check_ends(ends), ends_report
+    def __init__(self, shared, adapter, min_len, max_len, report, judged=True, dedup=None, ends=None):
+        quality_cutoff, qual_base = shared.quality_cutoff, shared.qual_base
+        self.qual_base, self.content, self.report, self.judged = qual_base, shared.content, report, judged
+        self.ends, self.ends_report = _check_ends(ends), shared.ends_report
         if ends is not None:
             _ends_qual_base(qual_base)
-        self.compress, self.compress_report = compress, compress_report
-        self.poly_g, self.poly_x = _poly_min_len("poly_g", poly_g), _poly_min_len("poly_x", poly_x)
-        self.poly_report = poly_report
+        self.compress, self.compress_report = shared.compress, shared.compress_report
+        self.poly_g, self.poly_x = _poly_min_len("poly_g", shared.poly_g), _poly_min_len("poly_x", shared.poly_x)
+        self.poly_report = shared.poly_report
         self.dedup = dedup           # (a single file's DedupRules; a pair's duplicates are the PairStream's, not a mate's)
         self.dropped = dict.fromkeys(ContentRules.REASONS, 0)
         if report is not None:
@@ -1355,7 +1395,7 @@ class _MatePlan:
             front, back = (0, quality_cutoff) if isinstance(quality_cutoff, (int, np.integer)) else quality_cutoff
             self.trim = entryfunc_qualitytrim(back, front, qual_base)            # (checks the ranges)
         if adapter is not None:
-            self.cutter = entryfunc_adaptertrim(adapter, err_permille, min_overlap)      # (the adapter alone: the plan orders the trims)
+            self.cutter = entryfunc_adaptertrim(adapter, shared.err_permille, shared.min_overlap)    # (the adapter alone: the plan orders the trims)
         self.lo = None if min_len is None else int(min_len)
         self.hi = None if max_len is None else int(max_len)
 
@@ -1393,7 +1433,7 @@ class _MatePlan:
         if self.ends is not None:
             e = st.ends_trimmed()
             removed += e[1]
-            self._ends_count(e[0], e[1])
+            self.ends_report._add_counts(e)
         if self.trim is not None:
             removed += st.trimmed()[1]
         if self.cutter is not None:
@@ -1401,22 +1441,8 @@ class _MatePlan:
         if self.poly_g is not None or self.poly_x is not None:
             g, x = st.poly_trimmed()
             removed += g[1] + x[1]
-            self._poly_count(g[0], g[1], x[0], x[1])
+            self.poly_report._add_counts((g, x))
         return nb, rendered, removed
-
-    def _ends_count(self, reads, bases):
-        rep = self.ends_report
-        if rep is not None:
-            rep.reads_cut += reads
-            rep.bases_cut += bases
-
-    def _poly_count(self, g_reads, g_bases, x_reads, x_bases):
-        rep = self.poly_report
-        if rep is not None:
-            rep.poly_g_reads += g_reads
-            rep.poly_g_bases += g_bases
-            rep.poly_x_reads += x_reads
-            rep.poly_x_bases += x_bases
 
     def finish(self, st):
         """the statistics the stream counted, read back once"""
@@ -1435,7 +1461,7 @@ class _MatePlan:
         if self.ends is not None:                            # (the chain's order: ends, quality, poly-G, adapter, poly-X)
             pos, e = _ends_pos(buf, list(pos), self.ends, self.qual_base)
             if e:
-                self._ends_count(1, e)
+                self.ends_report._add_counts((1, e))
         if self.trim is not None:
             pos = self.trim.trimmed_pos(buf, pos)
         if self.poly_g is not None:
@@ -1445,7 +1471,7 @@ class _MatePlan:
         if self.poly_x is not None:
             pos, x = _poly_pos(buf, list(pos), None, self.poly_x)
         if g or x:
-            self._poly_count(int(g > 0), g, int(x > 0), x)
+            self.poly_report._add_counts(((int(g > 0), g), (int(x > 0), x)))
         return pos, length - (pos[3] - pos[2])
 
     def verdict(self, buf, pos):
@@ -1478,7 +1504,7 @@ def fastq_stats(fh: typing.BinaryIO, fbufsize: int = 1 << 24, qual_base: int = 3
     duplication: the reads are also looked up in a set of sequence keys (DedupRules(count_only=True): the stream's dedup on the
     device, a set of seq_key on the host) and the result's keyed, distinct, duplicates and duplication_rate are set."""
     out = FastqStats(max_cycles, qual_base)
-    hd = _HostDedup(DedupRules(count_only=True), None) if duplication else None
+    hd = _HostDedup(DedupRules(count_only=True), DedupReport()) if duplication else None
 
     def with_duplication(res, rep):
         res.keyed, res.distinct, res.duplicates, res.duplication_rate = rep.keyed, rep.distinct, rep.duplicates, rep.duplication_rate
@@ -1512,24 +1538,6 @@ def fastq_stats(fh: typing.BinaryIO, fbufsize: int = 1 << 24, qual_base: int = 3
 
 
 FilterResult = namedtuple('FilterResult', 'records_in records_out bases_removed bytes_out')
-
-
-def _check_ends_report(ends, ends_report):
-    """an EndsReport (reset: the plans add to it) or None"""
-    if ends_report is not None:
-        if ends is None:
-            raise ValueError("ends_report needs ends")
-        if not isinstance(ends_report, EndsReport):
-            raise TypeError("ends_report must be an EndsReport")
-        ends_report.__init__()
-
-
-def _check_poly_report(poly_report):
-    """a PolyReport (reset: the plans add to it) or None"""
-    if poly_report is not None:
-        if not isinstance(poly_report, PolyReport):
-            raise TypeError("poly_report must be a PolyReport")
-        poly_report.__init__()
 
 
 def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1 << 24, quality_cutoff=None,
@@ -1601,14 +1609,11 @@ def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1
     if content is not None and not isinstance(content, ContentRules):
         raise TypeError("content must be a ContentRules")
     _check_dedup(dedup, dedup_report)
-    _check_poly_report(poly_report)
-    _check_ends_report(_check_ends(ends), ends_report)
-    _check_compress(compress, compress_report)
-    plan = _MatePlan(quality_cutoff, qual_base, adapter, err_permille, min_overlap, min_len, max_len, content, report, dedup=dedup,
-                     poly_g=poly_g, poly_x=poly_x, poly_report=poly_report, compress=compress, compress_report=compress_report,
-                     ends=ends, ends_report=ends_report)
+    shared = _MateSettings(quality_cutoff, qual_base, err_permille, min_overlap, content, poly_g, poly_x, poly_report, compress,
+                           compress_report, ends, ends_report)
+    plan = _MatePlan(shared, adapter, min_len, max_len, report, dedup=dedup, ends=ends)
     fh_out = plan.sink(fh_out)
-    hd = _HostDedup(dedup, dedup_report) if dedup is not None else None
+    hd = _HostDedup(dedup, _report(dedup_report, DedupReport)) if dedup is not None else None
     entrypos, open_stream = _scanner(entrypos)
     n_in = n_out = removed = n_bytes = 0
     st = open_stream(fh, fbufsize) if open_stream is not None else None
@@ -1725,6 +1730,14 @@ class OverlapReport:
         self.bases_removed = [0, 0]
         self.insert_hist = np.zeros(_hip.OVERLAP_HIST_WORDS, dtype=np.uint64)
 
+    def _add_counts(self, counts):
+        """(pairs analysed, with an overlap, changed, bases removed from mate 1, from mate 2, ...) (hip: overlap)"""
+        self.pairs_analysed += counts[0]
+        self.pairs_overlapped += counts[1]
+        self.pairs_trimmed += counts[2]
+        self.bases_removed[0] += counts[3]
+        self.bases_removed[1] += counts[4]
+
     @property
     def insert_peak(self):
         return int(np.argmax(self.insert_hist)) if self.insert_hist.any() else None
@@ -1767,15 +1780,8 @@ def merge_mergeable(buf1, pos1, buf2, pos2, insert):
     """Does the device merge this pair (ffq_table_pair_merge's eligibility)?  Both rows' pos2..pos5 inside their buffers and in
     order with sequence and quality of one length, mate 1's header slice buf1[pos0 + 1:pos1] inside its buffer, neither mate
     above OverlapRules.MAX_LEN bases, insert >= 0 and -n2 < insert - n2 < n1.  Newlines are not looked for."""
-    for buf, pos in ((buf1, pos1), (buf2, pos2)):
-        p2, p3, p4, p5 = pos[2], pos[3], pos[4], pos[5]
-        if not (p2 >= 0 and p4 >= 0 and p2 <= p3 <= len(buf) and p4 <= p5 <= len(buf) and p3 - p2 == p5 - p4
-                and p3 - p2 <= OverlapRules.MAX_LEN):
-            return False
-    if not (pos1[0] >= 0 and pos1[0] + 1 <= pos1[1] <= len(buf1)):
-        return False
-    n1, n2 = pos1[3] - pos1[2], pos2[3] - pos2[2]
-    return insert is not None and insert >= 0 and -n2 < insert - n2 < n1
+    # (correct_correctable asks the rest: the correction does not look at the header)
+    return bool(pos1[0] >= 0 and pos1[0] + 1 <= pos1[1] <= len(buf1)) and correct_correctable(buf1, pos1, buf2, pos2, insert)
 
 
 class MergeReport:
@@ -1785,6 +1791,14 @@ class MergeReport:
 
     def __init__(self):
         self.pairs_merged = self.bases_merged = self.bytes_merged = self.overlap_positions = self.taken_from_mate2 = 0
+
+    def _add_counts(self, counts):
+        """(pairs merged, not merged, bytes of text, bases, positions inside overlaps, of those taken from mate 2) (hip: merged)"""
+        self.pairs_merged += counts[0]
+        self.bytes_merged += counts[2]
+        self.bases_merged += counts[3]
+        self.overlap_positions += counts[4]
+        self.taken_from_mate2 += counts[5]
 
 
 class CorrectionRules:
@@ -1811,6 +1825,7 @@ class CorrectionReport:
         self.matrix = np.zeros((5, 4), dtype=np.int64)
 
     def _add_counts(self, counts):
+        """(pairs looked at, with a correction, bases corrected in mate 1, in mate 2, mismatch positions, ...) (hip: corrected)"""
         self.pairs_checked += counts[0]
         self.pairs_corrected += counts[1]
         self.bases_corrected[0] += counts[2]
@@ -1886,14 +1901,6 @@ PairedFilterResult = namedtuple('PairedFilterResult', 'pairs_in pairs_out bases_
 _PAIR_FILTERS = ("any", "both", "first")
 
 
-def _pair_dropped(pair_filter, v1, v2):
-    if pair_filter == "any":
-        return bool(v1 or v2)
-    if pair_filter == "both":
-        return bool(v1 and v2)
-    return bool(v1)
-
-
 def _raise_for_pair_end(end_state, err_mate, err_offset, names=None):
     """The ValueError of a paired run: a mate's own malformed input, files of two lengths, records that are not mates."""
     if end_state == _hip.END_ERR_PAIR_COUNT:
@@ -1906,6 +1913,194 @@ def _raise_for_pair_end(end_state, err_mate, err_offset, names=None):
         _raise_for_end(end_state, err_offset)
     except ValueError as e:
         raise ValueError("mate %d: %s" % (err_mate, e)) from None
+
+
+class _HostRecord:
+    """A record of the paired host route, kept until its mate is there: `at` (where it is in its file), `name` (its pair_id, or
+    None), `cut` (bases the trims removed so far), `buf` and `pos` (its buffer and its six positions as the trims left them),
+    `key` (its seq_key as scanned, 0: none)."""
+    __slots__ = ("at", "name", "cut", "buf", "pos", "key")
+
+    def __init__(self, at, name, cut, buf, pos, key):
+        self.at, self.name, self.cut, self.buf, self.pos, self.key = at, name, cut, buf, pos, key
+
+    def cut_to(self, c):
+        """the record with sequence and quality cut to their first `c` bytes"""
+        p = self.pos
+        return _HostRecord(self.at, self.name, self.cut + p[3] - p[2] - c, self.buf, (p[0], p[1], p[2], p[2] + c, p[4], p[4] + c), self.key)
+
+    def patched(self, seq, qual):
+        """the record in a buffer of its own -- itself cut out, with `seq` and `qual` in place of its two lines -- and its
+        positions shifted to it"""
+        p = self.pos
+        lo, hi = p[0], max(p[1], p[3], p[5])
+        own = bytearray(self.buf[lo:hi])
+        own[p[2] - lo:p[3] - lo] = seq
+        own[p[4] - lo:p[5] - lo] = qual
+        return _HostRecord(self.at, self.name, self.cut, bytes(own), tuple(x - lo for x in p), self.key)
+
+
+def _per_mate(x):
+    """a bound for both mates or a (mate 1, mate 2) pair of them -> the pair"""
+    a, b = tuple(x) if isinstance(x, (tuple, list)) else (x, x)
+    return (None if a is None else int(a), None if b is None else int(b))
+
+
+def _ends_per_mate(ends):
+    """one EndRules (or None) for both mates or a (mate 1, mate 2) pair of them -> the pair, checked"""
+    if not isinstance(ends, (tuple, list)):
+        return (_check_ends(ends),) * 2
+    if len(ends) != 2:
+        raise ValueError("ends is an EndRules for both mates or a pair of them")
+    return (_check_ends(ends[0]), _check_ends(ends[1]))
+
+
+def _step(it):
+    """(record, None), (None, None) at the end, (None, error)"""
+    try:
+        return next(it), None
+    except StopIteration:
+        return None, None
+    except ValueError as e:
+        return None, e
+
+
+def _check_pair_end(ps, end_state, err_mate, err_offset):
+    """behind a round's drains: the ValueError of a round of `ps` that did not end well"""
+    if end_state != _END_OK and end_state != _END_REFILL:
+        names = tuple(pair_id(h) for h in ps.mismatch()) if end_state == _hip.END_ERR_PAIR_NAMES else None
+        _raise_for_pair_end(end_state, err_mate, err_offset, names)
+
+
+class _PairPlan:
+    """What belongs to the PAIR in filter_fastq_paired, beside the two mates' _MatePlans and said once for both routes: the
+    verdict of the pair (pair_filter) and its names (check_names), the overlap (an OverlapRules or None), the correction (a
+    CorrectionRules or None, with qual_base), the duplicate pairs (a DedupRules or None), the merge (merging: is there a
+    merged_out) and, merging, how the merged text is compressed.  The four reports are the caller's or private ones (_report):
+    the plan always fills them.  `dropped`: the dropped pairs by the mate that failed.  On the device route the plan configures
+    the hip.PairStream and drains every round of it; on the host route it is called pair by pair, with _HostRecords."""
+
+    def __init__(self, pair_filter, check_names, overlap, overlap_report, correction, qual_base, correction_report, dedup, dedup_report,
+                 merging, merge_report, compress):
+        self.pair_filter, self.check_names, self.overlap, self.correction, self.qual_base = pair_filter, check_names, overlap, correction, qual_base
+        self.dedup, self.merging, self.compress = dedup, merging, compress
+        self.overlap_report, self.correction_report, self.merge_report = overlap_report, correction_report, merge_report
+        self.hd = _HostDedup(dedup, dedup_report) if dedup is not None else None
+        self.dropped = {"mate1_only": 0, "mate2_only": 0, "both": 0}
+
+    # ---- the device route
+    def configure(self, ps):
+        """What the pair is asked for, in the order its round works: the overlap behind the mates' trims, the correction, the
+        merge (with the compression of its text) and, between the filter and the merge, the duplicates.  None / False: that
+        setter is not called.  A stage of the PAIR that is added is added HERE."""
+        if self.overlap is not None:
+            ps.set_overlap(self.overlap)
+        if self.correction is not None:
+            ps.set_correct(self.correction, self.qual_base)
+        if self.merging:
+            ps.set_merge()
+            if self.compress is not None:
+                ps.set_compress(self.compress)
+        if self.dedup is not None:
+            ps.set_dedup(not self.dedup.count_only, self.dedup.expected_reads, self.dedup.max_bytes)
+
+    def drain(self, ps, merged_out):
+        """One round of the pair: its merged text -- or, compressed, its members -- written with one write, the reports and
+        `dropped` counted; (pairs merged: kept, and not among the round's n_out; bases the overlap removed).
+        No host wait: the insert sizes and the matrix are read in finish()."""
+        merged = removed = 0
+        if self.merging:
+            text, counts = ps.merged()
+            if self.compress is not None:
+                merged_out.members(*ps.merged_bgzf())
+            elif counts[2]:
+                merged_out.write(memoryview(text))
+            self.merge_report._add_counts(counts)
+            merged = counts[0]
+        if self.overlap is not None:
+            counts = ps.overlap(hist=False)[0]
+            self.overlap_report._add_counts(counts)
+            removed = counts[3] + counts[4]
+        if self.correction is not None:
+            self.correction_report._add_counts(ps.corrected()[0])
+        _kept, _dropped, only1, only2, both = ps.selected()[1]
+        if self.pair_filter != "both":            # (under "both" a pair with one failed mate is kept)
+            self.dropped["mate1_only"] += only1
+            self.dropped["mate2_only"] += only2
+        self.dropped["both"] += both
+        return merged, removed
+
+    def finish(self, ps):
+        """what the pair counted over all rounds, read back once"""
+        if self.overlap is not None:
+            self.overlap_report.insert_hist = ps.overlap()[1]
+        if self.correction is not None:
+            self.correction_report.matrix = ps.corrected()[1]
+        if self.hd is not None:
+            self.hd.report._from_counts(ps.dedup_counts())
+
+    # ---- the host route
+    def recorder(self, plan):
+        """the entryfunc of one mate's readfastq_iter: the record as a _HostRecord, trimmed by the mate's plan"""
+        def record(buf, pos, globaloffset=None):
+            at = pos[0] + (globaloffset or 0)
+            name = pair_id(buf[(pos[0] + 1):pos[1]]) if self.check_names else None
+            key = self.hd.key(buf, pos) if self.hd is not None else 0
+            pos, cut = plan.trimmed_pos(buf, pos)
+            return _HostRecord(at, name, cut, buf, tuple(pos[i] for i in range(6)), key)
+        return record
+
+    def overlap_cut(self, r1, r2):
+        """the two records with the overlap's cut applied and the pair's insert size (None: none), and the report filled"""
+        (buf1, pos1), (buf2, pos2) = (r1.buf, r1.pos), (r2.buf, r2.pos)
+        if self.overlap is None or not overlap_analysable(buf1, pos1, buf2, pos2):
+            return r1, r2, None
+        n1, n2 = pos1[3] - pos1[2], pos2[3] - pos2[2]
+        insert = pair_overlap(buf1[pos1[2]:pos1[3]], buf2[pos2[2]:pos2[3]], self.overlap)
+        if insert is not None:
+            self.overlap_report.insert_hist[insert] += 1
+        if insert is None or insert >= n2:              # (o >= 0: the fragment is not shorter than mate 2)
+            self.overlap_report._add_counts((1, int(insert is not None), 0, 0, 0))
+            return r1, r2, insert
+        c1, c2 = min(n1, insert), min(n2, insert)
+        self.overlap_report._add_counts((1, 1, 1, n1 - c1, n2 - c2))
+        return r1.cut_to(c1), r2.cut_to(c2), insert
+
+    def corrected(self, r1, r2, insert):
+        """the two records with the correction applied, and the report filled: a mate with a corrected base continues as a
+        private buffer (_HostRecord.patched); everything behind (verdict, text, merged_text) takes buffer and positions from the
+        record and sees the corrected bytes"""
+        (buf1, pos1), (buf2, pos2) = (r1.buf, r1.pos), (r2.buf, r2.pos)
+        if self.correction is None or not correct_correctable(buf1, pos1, buf2, pos2, insert):
+            return r1, r2
+        seq1, qual1, seq2, qual2, c1, c2, mismatches, matrix = _correct_lines(
+            buf1[pos1[2]:pos1[3]], buf1[pos1[4]:pos1[5]], buf2[pos2[2]:pos2[3]], buf2[pos2[4]:pos2[5]], insert, self.correction, self.qual_base)
+        self.correction_report._add_counts((1, int(c1 + c2 > 0), c1, c2, mismatches))
+        self.correction_report.matrix += matrix
+        return r1.patched(seq1, qual1) if c1 else r1, r2.patched(seq2, qual2) if c2 else r2
+
+    def drops(self, v1, v2):
+        """is the pair dropped by its mates' verdicts?  Counted into `dropped`."""
+        by = (v1 or v2) if self.pair_filter == "any" else (v1 and v2) if self.pair_filter == "both" else v1
+        if by:
+            self.dropped["both" if (v1 and v2) else "mate1_only" if v1 else "mate2_only"] += 1
+        return bool(by)
+
+    def merged_text(self, r1, r2, insert):
+        """the pair as one record (None: it is not merged), and the report filled; behind the cut, with the insert size found
+        in front of it: the rule takes o against the current length of mate 2, the text is the same either way"""
+        (buf1, pos1), (buf2, pos2) = (r1.buf, r1.pos), (r2.buf, r2.pos)
+        if not self.merging or not merge_mergeable(buf1, pos1, buf2, pos2, insert):
+            return None
+        bases, quals = merge_mates(buf1[pos1[2]:pos1[3]], buf1[pos1[4]:pos1[5]], buf2[pos2[2]:pos2[3]], buf2[pos2[4]:pos2[5]], insert)
+        n1, n2 = pos1[3] - pos1[2], pos2[3] - pos2[2]
+        o = insert - n2
+        lo, hi = max(0, o), min(n1, n2 + o)
+        text = b"".join((b"@", buf1[(pos1[0] + 1):pos1[1]], b"\n", bases, b"\n+\n", quals, b"\n"))
+        qa = np.frombuffer(buf1[pos1[4]:pos1[5]], dtype=np.uint8)[lo:hi]
+        qb = np.frombuffer(buf2[pos2[4]:pos2[5]], dtype=np.uint8)[::-1][lo - o:hi - o]
+        self.merge_report._add_counts((1, 0, len(text), len(bases), hi - lo, int(np.count_nonzero(qb > qa))))
+        return text
 
 
 def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typing.BinaryIO, fh_out2: typing.BinaryIO,
@@ -1998,50 +2193,21 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
         raise ValueError("correction_report needs correction")
     if correction is not None:
         _check_correction(correction, qual_base)
-    crep = CorrectionReport()
-    if correction_report is not None:
-        correction_report.__dict__.update(crep.__dict__)
-        crep = correction_report
+    crep = _report(correction_report, CorrectionReport)
     _check_dedup(dedup, dedup_report)
-    hd = _HostDedup(dedup, dedup_report) if dedup is not None else None
-    mrep = MergeReport()
-    if merge_report is not None:
-        merge_report.__dict__.update(mrep.__dict__)
-        mrep = merge_report
-    orep = OverlapReport() if overlap is not None else None
-    if overlap_report is not None:
-        overlap_report.__dict__.update(orep.__dict__)
-        orep = overlap_report
-
-    def per_mate(x):
-        a, b = tuple(x) if isinstance(x, (tuple, list)) else (x, x)
-        return (None if a is None else int(a), None if b is None else int(b))
-    los, his = per_mate(min_len), per_mate(max_len)
-    if isinstance(ends, (tuple, list)):
-        if len(ends) != 2:
-            raise ValueError("ends is an EndRules for both mates or a pair of them")
-        ends_pair = (_check_ends(ends[0]), _check_ends(ends[1]))
-    else:
-        ends_pair = (_check_ends(ends),) * 2
-    _check_poly_report(poly_report)
-    _check_ends_report(ends_pair[0] or ends_pair[1], ends_report)
-    _check_compress(compress, compress_report)
-    plans = tuple(_MatePlan(quality_cutoff, qual_base, a, err_permille, min_overlap, lo, hi, content, rep, judged, poly_g=poly_g,
-                            poly_x=poly_x, poly_report=poly_report, compress=compress, compress_report=compress_report,
-                            ends=e, ends_report=ends_report)
-                  for a, lo, hi, rep, judged, e in zip((adapter, adapter2), los, his, (report, report2), (True, pair_filter != "first"),
-                                                       ends_pair))
-    dropped = {"mate1_only": 0, "mate2_only": 0, "both": 0}
+    drep, mrep, orep = _report(dedup_report, DedupReport), _report(merge_report, MergeReport), _report(overlap_report, OverlapReport)
+    los, his, ends_pair = _per_mate(min_len), _per_mate(max_len), _ends_per_mate(ends)
+    shared = _MateSettings(quality_cutoff, qual_base, err_permille, min_overlap, content, poly_g, poly_x, poly_report, compress,
+                           compress_report, ends_pair[0] or ends_pair[1], ends_report)
+    plans = tuple(_MatePlan(shared, a, lo, hi, rep, judged, ends=e) for a, lo, hi, rep, judged, e
+                  in zip((adapter, adapter2), los, his, (report, report2), (True, pair_filter != "first"), ends_pair))
+    pair = _PairPlan(pair_filter, check_names, overlap, orep, correction, qual_base, crep, dedup, drep, merged_out is not None, mrep,
+                     compress)
     entrypos, open_stream = _scanner(entrypos)
     pairs_in = pairs_out = removed = 0
     n_bytes = [0, 0]
     # (compress: all three outputs are BGZF, filter_fastq's way, and compress_report sums over them)
-    outs = (plans[0].sink(fh_out1), plans[1].sink(fh_out2))
-    merged_out = plans[0].sink(merged_out)
-
-    def end_outputs():
-        for out in outs + (merged_out,):
-            plans[0].end(out)
+    outs = (plans[0].sink(fh_out1), plans[1].sink(fh_out2), plans[0].sink(merged_out))
     sts = []
     if open_stream is not None:
         for fh in (fh1, fh2):
@@ -2059,198 +2225,58 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
             for plan, st in zip(plans, sts):
                 plan.configure(st)
             ps = _hip.PairStream(sts[0], sts[1], pair_filter, check_names)
-            if overlap is not None:
-                ps.set_overlap(overlap)
-            if correction is not None:
-                ps.set_correct(correction, qual_base)
-            if merged_out is not None:
-                ps.set_merge()
-                if compress is not None:
-                    ps.set_compress(compress)
-            if dedup is not None:
-                ps.set_dedup(not dedup.count_only, dedup.expected_reads, dedup.max_bytes)
+            pair.configure(ps)
             for n_in, n_out, end_state, err_mate, err_offset in ps:
-                pairs_in += n_in
-                if merged_out is not None:           # (n_out: the kept pairs that were not merged)
-                    text, mc = ps.merged()
-                    if compress is not None:
-                        merged_out.members(*ps.merged_bgzf())
-                    elif mc[2]:
-                        merged_out.write(memoryview(text))
-                    pairs_out += n_out + mc[0]
-                    mrep.pairs_merged += mc[0]
-                    mrep.bytes_merged += mc[2]
-                    mrep.bases_merged += mc[3]
-                    mrep.overlap_positions += mc[4]
-                    mrep.taken_from_mate2 += mc[5]
-                else:
-                    pairs_out += n_out
-                if overlap is not None:
-                    oc = ps.overlap(hist=False)[0]
-                    orep.pairs_analysed += oc[0]
-                    orep.pairs_overlapped += oc[1]
-                    orep.pairs_trimmed += oc[2]
-                    orep.bases_removed[0] += oc[3]
-                    orep.bases_removed[1] += oc[4]
-                    removed += oc[3] + oc[4]
-                if correction is not None:
-                    crep._add_counts(ps.corrected()[0])
+                merged, cut = pair.drain(ps, outs[2])
+                pairs_in, pairs_out, removed = pairs_in + n_in, pairs_out + n_out + merged, removed + cut
                 for k, (plan, st) in enumerate(zip(plans, sts)):
                     nb, _rendered, cut = plan.drain(st, outs[k])
                     n_bytes[k] += nb
                     removed += cut
-                pc = ps.selected()[1]
-                if pair_filter != "both":            # (under "both" a pair with one failed mate is kept)
-                    dropped["mate1_only"] += pc[2]
-                    dropped["mate2_only"] += pc[3]
-                dropped["both"] += pc[4]
-                if end_state != _END_OK and end_state != _END_REFILL:
-                    names = None
-                    if end_state == _hip.END_ERR_PAIR_NAMES:
-                        names = tuple(pair_id(h) for h in ps.mismatch())
-                    _raise_for_pair_end(end_state, err_mate, err_offset, names)
+                _check_pair_end(ps, end_state, err_mate, err_offset)
             for plan, st in zip(plans, sts):
                 plan.finish(st)
-            end_outputs()
-            if overlap is not None:
-                orep.insert_hist = ps.overlap()[1]
-            if correction is not None:
-                crep.matrix = ps.corrected()[1]
-            if hd is not None:
-                hd.report._from_counts(ps.dedup_counts())
+            for out in outs:
+                plans[0].end(out)
+            pair.finish(ps)
         finally:
             if ps is not None:
                 ps.close()
             for st in sts:
                 st.close()
-        return PairedFilterResult(pairs_in, pairs_out, removed, n_bytes[0], n_bytes[1], dropped)
+        return PairedFilterResult(pairs_in, pairs_out, removed, n_bytes[0], n_bytes[1], pair.dropped)
 
-    def recorder(plan):
-        def record(buf, pos, globaloffset=None):
-            """(where it is, its id, bases cut, its buffer, its positions as the trims left them, its key as scanned): kept until its
-            mate is there"""
-            at = pos[0] + (globaloffset or 0)
-            name = pair_id(buf[(pos[0] + 1):pos[1]]) if check_names else None
-            key = hd.key(buf, pos) if hd is not None else 0
-            pos, cut = plan.trimmed_pos(buf, pos)
-            return at, name, cut, buf, tuple(pos[i] for i in range(6)), key
-        return record
-
-    def overlap_cut(r1, r2):
-        """the two records with the overlap's cut applied and the pair's insert size (None: none), and the report filled"""
-        (buf1, pos1), (buf2, pos2) = r1[3:5], r2[3:5]
-        if not overlap_analysable(buf1, pos1, buf2, pos2):
-            return r1, r2, None
-        orep.pairs_analysed += 1
-        n1, n2 = pos1[3] - pos1[2], pos2[3] - pos2[2]
-        insert = pair_overlap(buf1[pos1[2]:pos1[3]], buf2[pos2[2]:pos2[3]], overlap)
-        if insert is None:
-            return r1, r2, None
-        orep.pairs_overlapped += 1
-        orep.insert_hist[insert] += 1
-        if insert >= n2:                                # (o >= 0: the fragment is not shorter than mate 2)
-            return r1, r2, insert
-        out = []
-        for k, (r, n) in enumerate(((r1, n1), (r2, n2))):
-            c = min(n, insert)
-            pos = r[4]
-            orep.bases_removed[k] += n - c
-            out.append(r[:2] + (r[2] + n - c, r[3], (pos[0], pos[1], pos[2], pos[2] + c, pos[4], pos[4] + c)) + r[5:])
-        orep.pairs_trimmed += 1
-        return out[0], out[1], insert
-
-    def corrected(r1, r2, insert):
-        """the two records with the correction applied, and the report filled: a mate with a corrected base continues as a
-        private buffer -- its record cut out and patched -- with its positions shifted; everything behind (verdict, text,
-        merged_text) takes buffer and positions from the record and sees the corrected bytes"""
-        (buf1, pos1), (buf2, pos2) = r1[3:5], r2[3:5]
-        if not correct_correctable(buf1, pos1, buf2, pos2, insert):
-            return r1, r2
-        lines = _correct_lines(buf1[pos1[2]:pos1[3]], buf1[pos1[4]:pos1[5]], buf2[pos2[2]:pos2[3]], buf2[pos2[4]:pos2[5]], insert,
-                               correction, qual_base)
-        c1, c2, mismatches, matrix = lines[4:]
-        crep._add_counts((1, int(c1 + c2 > 0), c1, c2, mismatches))
-        crep.matrix += matrix
-        out = []
-        for r, n_fixed, seq, qual in ((r1, c1, lines[0], lines[1]), (r2, c2, lines[2], lines[3])):
-            if n_fixed:
-                buf, pos = r[3], r[4]
-                lo, hi = pos[0], max(pos[1], pos[3], pos[5])
-                own = bytearray(buf[lo:hi])
-                own[pos[2] - lo:pos[3] - lo] = seq
-                own[pos[4] - lo:pos[5] - lo] = qual
-                r = r[:3] + (bytes(own), tuple(x - lo for x in pos)) + r[5:]
-            out.append(r)
-        return out[0], out[1]
-
-    def merged_text(r1, r2, insert):
-        """the pair as one record (None: it is not merged), and the report filled; behind the cut, with the insert size found
-        in front of it: the rule takes o against the current length of mate 2, the text is the same either way"""
-        (buf1, pos1), (buf2, pos2) = r1[3:5], r2[3:5]
-        if not merge_mergeable(buf1, pos1, buf2, pos2, insert):
-            return None
-        bases, quals = merge_mates(buf1[pos1[2]:pos1[3]], buf1[pos1[4]:pos1[5]], buf2[pos2[2]:pos2[3]], buf2[pos2[4]:pos2[5]], insert)
-        n1, n2 = pos1[3] - pos1[2], pos2[3] - pos2[2]
-        o = insert - n2
-        lo, hi = max(0, o), min(n1, n2 + o)
-        text = b"".join((b"@", buf1[(pos1[0] + 1):pos1[1]], b"\n", bases, b"\n+\n", quals, b"\n"))
-        mrep.pairs_merged += 1
-        mrep.bases_merged += len(bases)
-        mrep.bytes_merged += len(text)
-        mrep.overlap_positions += hi - lo
-        qa = np.frombuffer(buf1[pos1[4]:pos1[5]], dtype=np.uint8)[lo:hi]
-        qb = np.frombuffer(buf2[pos2[4]:pos2[5]], dtype=np.uint8)[::-1][lo - o:hi - o]
-        mrep.taken_from_mate2 += int(np.count_nonzero(qb > qa))
-        return text
-
-    its = [iter(readfastq_iter(fh, fbufsize, recorder(plan), entrypos)) for plan, fh in zip(plans, (fh1, fh2))]
-
-    def step(it):
-        """(record, None), (None, None) at the end, (None, error)"""
-        try:
-            return next(it), None
-        except StopIteration:
-            return None, None
-        except ValueError as e:
-            return None, e
-
+    its = [iter(readfastq_iter(fh, fbufsize, pair.recorder(plan), entrypos)) for plan, fh in zip(plans, (fh1, fh2))]
     while True:
-        (r1, e1), (r2, e2) = step(its[0]), step(its[1])
+        (r1, e1), (r2, e2) = _step(its[0]), _step(its[1])
         for k, e in ((1, e1), (2, e2)):
             if e is not None:
                 raise ValueError("mate %d: %s" % (k, e)) from None
         if r1 is None and r2 is None:
             break
         if r1 is None or r2 is None:
-            longer = 1 if r2 is None else 2
-            _raise_for_pair_end(_hip.END_ERR_PAIR_COUNT, longer, (r1 if r2 is None else r2)[0])
-        if check_names and r1[1] != r2[1]:
-            _raise_for_pair_end(_hip.END_ERR_PAIR_NAMES, 0, pairs_in, (r1[1], r2[1]))
+            _raise_for_pair_end(_hip.END_ERR_PAIR_COUNT, 1 if r2 is None else 2, (r1 if r2 is None else r2).at)
+        if check_names and r1.name != r2.name:
+            _raise_for_pair_end(_hip.END_ERR_PAIR_NAMES, 0, pairs_in, (r1.name, r2.name))
         pairs_in += 1
-        insert = None
-        if overlap is not None:
-            r1, r2, insert = overlap_cut(r1, r2)
-            if correction is not None:
-                r1, r2 = corrected(r1, r2, insert)
-        v1, v2 = plans[0].verdict(r1[3], r1[4]), plans[1].verdict(r2[3], r2[4])
-        removed += r1[2] + r2[2]
-        if _pair_dropped(pair_filter, v1, v2):
-            dropped["both" if (v1 and v2) else "mate1_only" if v1 else "mate2_only"] += 1
-            continue
-        if hd is not None and not hd.keep(pair_key(r1[5], r2[5])):
+        r1, r2, insert = pair.overlap_cut(r1, r2)
+        r1, r2 = pair.corrected(r1, r2, insert)
+        v1, v2 = plans[0].verdict(r1.buf, r1.pos), plans[1].verdict(r2.buf, r2.pos)
+        removed += r1.cut + r2.cut
+        if pair.drops(v1, v2) or (pair.hd is not None and not pair.hd.keep(pair_key(r1.key, r2.key))):
             continue
         pairs_out += 1
-        if merged_out is not None:
-            text = merged_text(r1, r2, insert)
-            if text is not None:
-                merged_out.write(text)
-                continue
+        text = pair.merged_text(r1, r2, insert)
+        if text is not None:
+            outs[2].write(text)
+            continue
         for k, r in enumerate((r1, r2)):
-            text = plans[k].text(r[3], r[4])
+            text = plans[k].text(r.buf, r.pos)
             outs[k].write(text)
             n_bytes[k] += len(text)
-    end_outputs()
-    return PairedFilterResult(pairs_in, pairs_out, removed, n_bytes[0], n_bytes[1], dropped)
+    for out in outs:
+        plans[0].end(out)
+    return PairedFilterResult(pairs_in, pairs_out, removed, n_bytes[0], n_bytes[1], pair.dropped)
 
 
 class RangeEntries:

@@ -1341,13 +1341,27 @@ def _compress_mode(mode):
     return COMPRESS_MODES[mode]
 
 
+def _counts(call, handle, n, *more):
+    """What a getter of the library counts: call(handle, n int64 it fills, *more), checked, as a list of ints."""
+    counts = (ctypes.c_int64 * n)()
+    check(call(handle, counts, *more))
+    return [int(x) for x in counts]
+
+
+def _pinned_view(ptr, n, ctype, shape=None):
+    """numpy view of the n `ctype` elements at address `ptr` -- memory the library owns: valid as long as that says --, as
+    `shape` if given; n 0: an empty array of the same type.  Elements without an address are the library's error."""
+    if n and not ptr:
+        raise FFQError(E_INTERNAL, "the library handed out %d elements and no address" % n)
+    a = np.ctypeslib.as_array((ctype * n).from_address(ptr)) if n else np.zeros(0, dtype=ctype)
+    return a if shape is None else a.reshape(shape)
+
+
 def _members_of(call, handle):
     bp, nb = ctypes.c_void_p(), ctypes.c_int64()
     stats = (ctypes.c_int64 * DEFLATE_COUNTS)()
     check(call(handle, ctypes.byref(bp), ctypes.byref(nb), stats))
-    members = (np.ctypeslib.as_array((ctypes.c_uint8 * nb.value).from_address(bp.value)) if nb.value
-               else np.zeros(0, dtype=np.uint8))
-    return members, tuple(int(x) for x in stats)
+    return _pinned_view(bp.value, nb.value, ctypes.c_uint8), tuple(int(x) for x in stats)
 
 
 class _Stream:
@@ -1378,11 +1392,7 @@ class _Stream:
         (include/ffq.h, FFQ_F_SINGLE_PASS); qoff[n] is where the last record's bytes end."""
         qp, op, nq = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()
         check(lib().ffq_stream_quals(self._h, ctypes.byref(qp), ctypes.byref(op), ctypes.byref(nq)))
-        n = self._last_rows
-        qual = (np.ctypeslib.as_array((ctypes.c_int8 * nq.value).from_address(qp.value)) if nq.value
-                else np.zeros(0, dtype=np.int8))
-        qoff = np.ctypeslib.as_array((ctypes.c_int64 * (n + 1)).from_address(op.value))
-        return qual, qoff
+        return _pinned_view(qp.value, nq.value, ctypes.c_int8), _pinned_view(op.value, self._last_rows + 1, ctypes.c_int64)
 
     COLUMNS = {None: 0, "entry": 0, "header": 1, "sequence": 2, "quality": 3}
 
@@ -1405,9 +1415,7 @@ class _Stream:
     def filter_counts(self):
         """The eight counts (rows kept, dropped by rule 1..6, not judged by content) of the fill the iteration has just
         yielded; any filtered stream."""
-        counts = (ctypes.c_int64 * FILTER_COUNTS)()
-        check(lib().ffq_stream_filter_counts(self._h, counts))
-        return [int(x) for x in counts]
+        return _counts(lib().ffq_stream_filter_counts, self._h, FILTER_COUNTS)
 
     def set_dedup(self, drop=True, expected_keys=0, max_bytes=0):
         """Duplicate removal in the stream (ffq_stream_set_dedup; before the first fill): the stream owns a set of sequence
@@ -1419,9 +1427,7 @@ class _Stream:
     def dedup_counts(self):
         """[rows kept, duplicates, rows without a key] summed over every fill so far, [distinct keys, slots, rehashes] of the
         set as it stands (ffq_stream_dedup_counts)."""
-        counts = (ctypes.c_int64 * DEDUP_COUNTS)()
-        check(lib().ffq_stream_dedup_counts(self._h, counts))
-        return [int(x) for x in counts]
+        return _counts(lib().ffq_stream_dedup_counts, self._h, DEDUP_COUNTS)
 
     def set_trim(self, cutoff_back, cutoff_front=0, qual_base=33):
         """Quality trimming in the stream (ffq_stream_set_trim; before the first fill): every fill's rows are trimmed on
@@ -1430,9 +1436,7 @@ class _Stream:
 
     def trimmed(self):
         """(rows changed, bases removed, rows skipped) of the fill the iteration has just yielded (set_trim)."""
-        stats = (ctypes.c_int64 * 3)()
-        check(lib().ffq_stream_trimmed(self._h, stats))
-        return int(stats[0]), int(stats[1]), int(stats[2])
+        return tuple(_counts(lib().ffq_stream_trimmed, self._h, 3))
 
     def set_adapter(self, adapter, err_permille=100, min_overlap=3):
         """3' adapter trimming in the stream (ffq_stream_set_adapter; before the first fill): every fill's rows are cut at
@@ -1443,9 +1447,7 @@ class _Stream:
 
     def adapter_trimmed(self):
         """(rows changed, bases removed, rows skipped) by the adapter step of the fill the iteration has just yielded."""
-        stats = (ctypes.c_int64 * 3)()
-        check(lib().ffq_stream_adapter_trimmed(self._h, stats))
-        return int(stats[0]), int(stats[1]), int(stats[2])
+        return tuple(_counts(lib().ffq_stream_adapter_trimmed, self._h, 3))
 
     def set_ends(self, rules, qual_base=33):
         """Fixed trims and sliding-window cutting in the stream (ffq_stream_set_ends; before the first fill): every fill's rows
@@ -1456,9 +1458,7 @@ class _Stream:
 
     def ends_trimmed(self):
         """(rows changed, bases removed, rows skipped) by the ends step of the fill the iteration has just yielded."""
-        stats = (ctypes.c_int64 * 3)()
-        check(lib().ffq_stream_ends_trimmed(self._h, stats))
-        return int(stats[0]), int(stats[1]), int(stats[2])
+        return tuple(_counts(lib().ffq_stream_ends_trimmed, self._h, 3))
 
     def set_poly(self, poly_g=None, poly_x=None):
         """Poly-tail trimming in the stream (ffq_stream_set_poly; before the first fill): poly_g / poly_x are the min_len of
@@ -1469,9 +1469,8 @@ class _Stream:
     def poly_trimmed(self):
         """((rows changed, bases removed, rows skipped) by poly-G, the same by poly-X) of the fill the iteration has just
         yielded; zeros for a step that is off."""
-        g, x = (ctypes.c_int64 * 3)(), (ctypes.c_int64 * 3)()
-        check(lib().ffq_stream_poly_trimmed(self._h, g, x))
-        return (int(g[0]), int(g[1]), int(g[2])), (int(x[0]), int(x[1]), int(x[2]))
+        x = (ctypes.c_int64 * 3)()
+        return tuple(_counts(lib().ffq_stream_poly_trimmed, self._h, 3, x)), tuple(int(v) for v in x)
 
     def set_stats(self, which, qual_base=33, max_cycles=512):
         """Statistics in the stream (ffq_stream_set_stats; before the first fill): which = STATS_IN (the rows as scanned),
@@ -1483,7 +1482,6 @@ class _Stream:
     def stats(self, which):
         """The running totals (numpy uint64[stats_words(max_cycles)]) of STATS_IN or STATS_OUT over every fill up to and
         including the one the iteration has just yielded (ffq_stream_stats; one host wait)."""
-        import numpy as np
         out = np.zeros(stats_words(getattr(self, "_stats_cycles", 1)), dtype=np.uint64)
         check(lib().ffq_stream_stats(self._h, int(which), ctypes.c_void_p(out.ctypes.data), int(out.size)))
         return out
@@ -1496,14 +1494,10 @@ class _Stream:
     def rendered(self):
         """(text, (bytes rendered, rows rendered, rows skipped)) of the fill the iteration has just yielded (set_render):
         `text` is a uint8 view of the stream's pinned memory, valid until the next iteration step."""
-        tp, nb = ctypes.c_void_p(), ctypes.c_int64()
-        stats = (ctypes.c_int64 * 3)()
+        tp, nb, stats = ctypes.c_void_p(), ctypes.c_int64(), (ctypes.c_int64 * 3)()
         check(lib().ffq_stream_rendered(self._h, ctypes.byref(tp), ctypes.byref(nb), stats))
-        if nb.value and not tp.value:
-            text = None                          # (set_compress: the text never leaves the device; compressed() has the members)
-        else:
-            text = (np.ctypeslib.as_array((ctypes.c_uint8 * nb.value).from_address(tp.value)) if nb.value
-                    else np.zeros(0, dtype=np.uint8))
+        # (set_compress: the text never leaves the device -- None; compressed() has the members)
+        text = None if nb.value and not tp.value else _pinned_view(tp.value, nb.value, ctypes.c_uint8)
         return text, (int(stats[0]), int(stats[1]), int(stats[2]))
 
     def set_compress(self, mode="bgzf"):
@@ -1526,12 +1520,10 @@ class _Stream:
         ns, nb = ctypes.c_int64(), ctypes.c_int64()
         check(lib().ffq_stream_selected(self._h, ctypes.byref(ip), ctypes.byref(ns), ctypes.byref(cp), ctypes.byref(op), ctypes.byref(nb)))
         k = self._last_rows
-        idx = np.ctypeslib.as_array((ctypes.c_int64 * k).from_address(ip.value)) if k else np.zeros(0, dtype=np.int64)
         col = off = None
         if op.value:
-            off = np.ctypeslib.as_array((ctypes.c_int64 * (k + 1)).from_address(op.value))
-            col = np.ctypeslib.as_array((ctypes.c_int8 * nb.value).from_address(cp.value)) if nb.value else np.zeros(0, dtype=np.int8)
-        return idx, int(ns.value), col, off
+            off, col = _pinned_view(op.value, k + 1, ctypes.c_int64), _pinned_view(cp.value, nb.value, ctypes.c_int8)
+        return _pinned_view(ip.value, k, ctypes.c_int64), int(ns.value), col, off
 
     def close(self):
         if self._h:
@@ -1557,11 +1549,8 @@ class _Stream:
         self._last_rows = n.value
         self.consumed = off.value + nb.value     # stream bytes handed out so far (byte i of the fill is stream offset off + i)
         self.at_end = end.value != END_REFILL    # the stream is through (cleanly or with its error): nothing follows
-        rows = (np.ctypeslib.as_array((ctypes.c_int64 * (n.value * 6)).from_address(rows_p.value)).reshape(-1, 6)
-                if n.value else np.zeros((0, 6), dtype=np.int64))
-        fill = (np.ctypeslib.as_array((ctypes.c_uint8 * nb.value).from_address(fill_p.value))
-                if nb.value else np.zeros(0, dtype=np.uint8))
-        return rows, fill, off.value, end.value, err.value
+        rows = _pinned_view(rows_p.value, n.value * 6, ctypes.c_int64, (-1, 6))
+        return rows, _pinned_view(fill_p.value, nb.value, ctypes.c_uint8), off.value, end.value, err.value
 
 
 def _decode_flags(decode, single_pass):
@@ -1686,29 +1675,25 @@ class PairStream:
             if t[2] != END_REFILL:
                 return
 
-    def rows(self, mate):
-        """(rows int64[n_out][6], fill uint8[], fill_offset) of mate 1 or 2 for the round just yielded: the kept rows and
-        the fill they point into (fill[i] = stream byte fill_offset + i).  Views, valid until the next step."""
+    def _rows(self, mate, n_rows):
+        """ffq_pair_rows of one mate: (its first n_rows rows, the fill, the fill's offset)"""
         rp, fp = ctypes.c_void_p(), ctypes.c_void_p()
         nb, off = ctypes.c_int64(), ctypes.c_int64()
         check(lib().ffq_pair_rows(self._h, int(mate), ctypes.byref(rp), ctypes.byref(fp), ctypes.byref(nb), ctypes.byref(off)))
-        n = self._last_out
-        rows = (np.ctypeslib.as_array((ctypes.c_int64 * (n * 6)).from_address(rp.value)).reshape(-1, 6)
-                if n else np.zeros((0, 6), dtype=np.int64))
-        fill = (np.ctypeslib.as_array((ctypes.c_uint8 * nb.value).from_address(fp.value))
-                if nb.value and fp.value else np.zeros(0, dtype=np.uint8))
-        return rows, fill, off.value
+        fill = _pinned_view(fp.value, nb.value if fp.value else 0, ctypes.c_uint8)
+        return _pinned_view(rp.value, n_rows * 6, ctypes.c_int64, (-1, 6)), fill, off.value
+
+    def rows(self, mate):
+        """(rows int64[n_out][6], fill uint8[], fill_offset) of mate 1 or 2 for the round just yielded: the kept rows and
+        the fill they point into (fill[i] = stream byte fill_offset + i).  Views, valid until the next step."""
+        return self._rows(mate, self._last_out)
 
     def mismatch(self):
         """Behind END_ERR_PAIR_NAMES: the two headers (bytes, as entryfunc cuts them) of the pair that is not one."""
         out = []
         for mate in (1, 2):
-            rp, fp = ctypes.c_void_p(), ctypes.c_void_p()
-            nb, off = ctypes.c_int64(), ctypes.c_int64()
-            check(lib().ffq_pair_rows(self._h, mate, ctypes.byref(rp), ctypes.byref(fp), ctypes.byref(nb), ctypes.byref(off)))
-            row = (ctypes.c_int64 * 6).from_address(rp.value)
-            fill = (ctypes.c_uint8 * nb.value).from_address(fp.value)
-            out.append(bytes(fill[row[0] + 1 - off.value:row[1] - off.value]))
+            (row,), fill, off = self._rows(mate, 1)
+            out.append(bytes(fill[row[0] + 1 - off:row[1] - off]))
         return tuple(out)
 
     def selected(self):
@@ -1717,9 +1702,7 @@ class PairStream:
         ip = ctypes.c_void_p()
         pairs = (ctypes.c_int64 * PAIR_COUNTS)()
         check(lib().ffq_pair_selected(self._h, ctypes.byref(ip), pairs))
-        n = self._last_out
-        idx = np.ctypeslib.as_array((ctypes.c_int64 * n).from_address(ip.value)) if n else np.zeros(0, dtype=np.int64)
-        return idx, [int(x) for x in pairs]
+        return _pinned_view(ip.value, self._last_out, ctypes.c_int64), [int(x) for x in pairs]
 
     def set_overlap(self, rules, trim=True):
         """Every round analyses the overlap of the mates behind the per-mate trims and in front of the filter, and with
@@ -1731,10 +1714,8 @@ class PairStream:
     def overlap(self, hist=True):
         """(counts, insert_hist): the six counts of the round just yielded (Context.table_pair_overlap's), and the insert sizes
         of every round so far as uint64[OVERLAP_HIST_WORDS] (None without `hist`: no host wait)."""
-        counts = (ctypes.c_int64 * OVERLAP_COUNTS)()
         h = np.zeros(OVERLAP_HIST_WORDS, dtype=np.uint64) if hist else None
-        check(lib().ffq_pair_overlap(self._h, counts, ctypes.c_void_p(h.ctypes.data) if hist else None, OVERLAP_HIST_WORDS))
-        return [int(x) for x in counts], h
+        return _counts(lib().ffq_pair_overlap, self._h, OVERLAP_COUNTS, ctypes.c_void_p(h.ctypes.data) if hist else None, OVERLAP_HIST_WORDS), h
 
     def set_merge(self, on=True):
         """Behind the filter every round merges the kept pairs whose insert size allows it (ffq_pair_set_merge; needs
@@ -1753,10 +1734,8 @@ class PairStream:
     def corrected(self):
         """(counts, matrix): the six counts of the round just yielded (Context.table_pair_correct's) and the corrections of
         every round so far as int64[5][4] by (class before, class after) (ffq_pair_corrected)."""
-        counts = (ctypes.c_int64 * CORRECT_COUNTS)()
         mat = (ctypes.c_int64 * CORRECT_MATRIX_WORDS)()
-        check(lib().ffq_pair_corrected(self._h, counts, mat))
-        return [int(x) for x in counts], np.array(mat, dtype=np.int64).reshape(5, 4)
+        return _counts(lib().ffq_pair_corrected, self._h, CORRECT_COUNTS, mat), np.array(mat, dtype=np.int64).reshape(5, 4)
 
     def set_dedup(self, drop=True, expected_keys=0, max_bytes=0):
         """Duplicate PAIRS dropped behind the filter and in front of the merge (ffq_pair_set_dedup; before the first step;
@@ -1765,20 +1744,14 @@ class PairStream:
 
     def dedup_counts(self):
         """_Stream.dedup_counts, in pairs, over every round so far (ffq_pair_dedup_counts)."""
-        counts = (ctypes.c_int64 * DEDUP_COUNTS)()
-        check(lib().ffq_pair_dedup_counts(self._h, counts))
-        return [int(x) for x in counts]
+        return _counts(lib().ffq_pair_dedup_counts, self._h, DEDUP_COUNTS)
 
     def merged(self):
         """(text uint8[], counts) of the round just yielded: the FASTQ text of the merged pairs (a view, valid until the next
         step) and the six counts of Context.table_pair_merge."""
-        tp = ctypes.c_void_p()
-        nb = ctypes.c_int64()
-        counts = (ctypes.c_int64 * MERGE_COUNTS)()
+        tp, nb, counts = ctypes.c_void_p(), ctypes.c_int64(), (ctypes.c_int64 * MERGE_COUNTS)()
         check(lib().ffq_pair_merged(self._h, ctypes.byref(tp), ctypes.byref(nb), counts))
-        text = (np.ctypeslib.as_array((ctypes.c_uint8 * nb.value).from_address(tp.value))
-                if nb.value and tp.value else np.zeros(0, dtype=np.uint8))
-        return text, [int(x) for x in counts]
+        return _pinned_view(tp.value, nb.value if tp.value else 0, ctypes.c_uint8), [int(x) for x in counts]
 
     def set_compress(self, mode="bgzf"):
         """The round's merged text as BGZF members (ffq_pair_set_compress; behind set_merge, before the first step):

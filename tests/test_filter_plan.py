@@ -1,11 +1,12 @@
 """How filter_fastq, filter_fastq_paired and readfastq_iter CONFIGURE a native stream, without a GPU: a scanner whose
-open_stream hands out recording fakes (the setters and getters of hip._Stream, no fill).  What the three callers ask of
+open_stream hands out recording fakes (tests/plan_fakes.py: the setters and getters of hip._Stream, no fill).  What the three callers ask of
 a stream for one parameter set is compared with literals written here: the same setters, in the same order, with the same
 arguments; an argument that is switched off calls nothing; a setter that raises leaves no stream open."""
 import io
 
-import numpy as np
 import pytest
+
+from plan_fakes import FakeScanner, no_rounds, paired, single  # noqa: F401
 
 ADAPTER = b"AGATCGGAAGAGC"
 
@@ -20,120 +21,6 @@ def F(pkg):
 def hip(pkg):
     from fastqandfurious_amd import hip
     return hip
-
-
-class FakeStream:
-    """hip._Stream's surface: every setter call is logged with its arguments as the real signature binds them."""
-    decode = False
-
-    def __init__(self, fail=None):
-        self.log, self.fail, self.filtered, self.closed, self.cycles = [], fail, False, 0, 1
-
-    def _call(self, name, *args):
-        if name == self.fail:
-            raise RuntimeError("%s refused" % name)
-        self.log.append((name,) + args)
-
-    def set_filter(self, min_seq_len=None, max_seq_len=None, column=None, value_add=0):
-        self._call("set_filter", min_seq_len, max_seq_len, column, value_add)
-        self.filtered = True
-
-    def set_content(self, rules):
-        self._call("set_content", rules)
-        self.filtered = True
-
-    def set_trim(self, cutoff_back, cutoff_front=0, qual_base=33):
-        self._call("set_trim", cutoff_back, cutoff_front, qual_base)
-
-    def set_adapter(self, adapter, err_permille=100, min_overlap=3):
-        self._call("set_adapter", adapter, err_permille, min_overlap)
-
-    def set_stats(self, which, qual_base=33, max_cycles=512):
-        self._call("set_stats", which, qual_base, max_cycles)
-        self.cycles = max_cycles
-
-    def set_render(self):
-        self._call("set_render")
-
-    # what a fill would be asked for; the fake yields none, so only stats() is ever reached
-    def rendered(self):
-        return np.zeros(0, dtype=np.uint8), (0, 0, 0)
-
-    def filter_counts(self):
-        return [0] * 8
-
-    def trimmed(self):
-        return 0, 0, 0
-
-    adapter_trimmed = trimmed
-
-    def selected(self):
-        return np.zeros(0, dtype=np.int64), 0, None, None
-
-    def stats(self, which):
-        from fastqandfurious_amd import hip
-        return np.zeros(hip.stats_words(self.cycles), dtype=np.uint64)
-
-    def __iter__(self):
-        return iter(())
-
-    def close(self):
-        self.closed += 1
-
-
-class FakeScanner:
-    """An `entrypos` with an open_stream attribute; fail: (ordinal of the stream, setter that raises); none_at: the ordinal
-    at which open_stream declines (returns None, as the real one does for a source it cannot stream)."""
-
-    def __init__(self, fail=None, none_at=None):
-        self.streams, self.fail, self.none_at = [], fail, none_at
-
-    def open_stream(self, fh, fbufsize, decode=False):
-        k = len(self.streams)
-        if k == self.none_at:
-            return None
-        self.streams.append(FakeStream(self.fail[1] if self.fail is not None and self.fail[0] == k else None))
-        return self.streams[-1]
-
-    def __call__(self, buf, offset, posbuffer):
-        raise AssertionError("the host route was taken")
-
-
-class NoRounds:
-    """hip.PairStream's surface, yielding no round."""
-    made = []
-
-    def __init__(self, mate1, mate2, pair_filter="any", check_names=True):
-        self.mates, self.closed = (mate1, mate2), 0
-        NoRounds.made.append(self)
-
-    def set_overlap(self, rules, trim=True):
-        pass
-
-    def overlap(self, hist=True):
-        from fastqandfurious_amd import hip
-        return [0] * 6, np.zeros(hip.OVERLAP_HIST_WORDS, dtype=np.uint64)
-
-    def __iter__(self):
-        return iter(())
-
-    def close(self):
-        self.closed += 1
-
-
-@pytest.fixture
-def no_rounds(hip, monkeypatch):
-    NoRounds.made = []
-    monkeypatch.setattr(hip, "PairStream", NoRounds)
-    return NoRounds
-
-
-def single(F, scanner, **kw):
-    return F.filter_fastq(io.BytesIO(b""), io.BytesIO(), 4096, entrypos=scanner, **kw)
-
-
-def paired(F, scanner, **kw):
-    return F.filter_fastq_paired(io.BytesIO(b""), io.BytesIO(b""), io.BytesIO(), io.BytesIO(), 4096, entrypos=scanner, **kw)
 
 
 def iterated(F, scanner, entryfunc):
@@ -254,3 +141,59 @@ def test_two_streams_or_none(F, no_rounds):
     with pytest.raises(AssertionError, match="the host route was taken"):
         paired(F, sc)
     assert [s.closed for s in sc.streams] == [1] and sc.streams[0].log == [] and no_rounds.made == []
+
+
+# ---- the pair's own ladder (hip.PairStream's setters)
+def pair_features(F):
+    """every feature of the pair -> (its arguments, the setter calls they alone cause)"""
+    overlap, correction = F.OverlapRules(20, 3, 100), F.CorrectionRules(31, 13)
+    dedup = F.DedupRules(expected_reads=1000, max_bytes=1 << 20, count_only=True)
+    return {
+        "overlap": (dict(overlap=overlap), [("set_overlap", overlap, True)]),
+        "correction": (dict(overlap=overlap, correction=correction, qual_base=64),
+                       [("set_overlap", overlap, True), ("set_correct", correction, 64)]),
+        "merge": (dict(overlap=overlap, merged_out=io.BytesIO()), [("set_overlap", overlap, True), ("set_merge", True)]),
+        "compress": (dict(compress="bgzf"), []),
+        "dedup": (dict(dedup=dedup), [("set_dedup", False, 1000, 1 << 20)]),
+    }
+
+
+def test_the_pairs_ladder_with_everything_on(F, no_rounds):
+    overlap, correction, dedup = F.OverlapRules(), F.CorrectionRules(), F.DedupRules()
+    sc = FakeScanner()
+    paired(F, sc, overlap=overlap, correction=correction, merged_out=io.BytesIO(), compress="bgzf", dedup=dedup)
+    assert len(no_rounds.made) == 1
+    ps = no_rounds.made[0]
+    assert ps.log == [("set_overlap", overlap, True), ("set_correct", correction, 33), ("set_merge", True),
+                      ("set_compress", "bgzf"), ("set_dedup", True, 0, 0)]
+    assert ps.mates == tuple(sc.streams) and ps.opened == ("any", True) and ps.closed == 1
+    # (the mates compress their own text; a pair's duplicates are the pair's, not a mate's)
+    assert [s.log for s in sc.streams] == [[("set_render",), ("set_compress", "bgzf")]] * 2
+    assert [s.closed for s in sc.streams] == [1, 1]
+
+
+@pytest.mark.parametrize("feature", ("overlap", "correction", "merge", "compress", "dedup"))
+def test_a_pair_feature_alone_calls_its_own_setter(F, no_rounds, feature):
+    kw, want = pair_features(F)[feature]
+    sc = FakeScanner()
+    paired(F, sc, pair_filter="first", check_names=False, **kw)
+    ps = no_rounds.made[0]
+    assert ps.log == want and ps.opened == ("first", False) and ps.closed == 1
+    assert [s.closed for s in sc.streams] == [1, 1]
+
+
+@pytest.mark.parametrize("setter", ("set_overlap", "set_correct", "set_merge", "set_compress", "set_dedup"))
+def test_a_pair_setter_that_raises_closes_everything(F, no_rounds, monkeypatch, setter):
+    class Out:
+        writes = 0
+
+        def write(self, data):
+            Out.writes += 1
+    monkeypatch.setattr(no_rounds, "fail", setter)
+    sc = FakeScanner()
+    with pytest.raises(RuntimeError, match=setter + " refused"):
+        F.filter_fastq_paired(io.BytesIO(b""), io.BytesIO(b""), Out(), Out(), 4096, entrypos=sc, overlap=F.OverlapRules(),
+                              correction=F.CorrectionRules(), merged_out=Out(), compress="bgzf", dedup=F.DedupRules())
+    assert [s.closed for s in sc.streams] == [1, 1]
+    assert len(no_rounds.made) == 1 and no_rounds.made[0].closed == 1
+    assert Out.writes == 0
