@@ -1,8 +1,8 @@
 // ffq_compact.h -- stable compaction of table rows, once: every table call that keeps some rows and drops the rest
 // (ffq_table_select_seqlen[_idx], ffq_table_select_reads, ffq_table_select_pairs, ffq_dedup_select) does the same three steps
 //   k_compact_count<Keep>     one row per thread: kept rows per block of 256 into bcnt
-//   launch_scan_u32           exclusive scan of those counts, their total (ffq_hip.hip)
-//   k_compact_scatter<Keep, NT, ORD>   rank inside the workgroup by ballots; the 48-byte rows of NT tables (0, 1 or 2) and the
+//   launch_scan               exclusive scan of those counts, their total (ffq_scan.h, ffq_hip.hip)
+//   k_compact_scatter<Keep, NT, ORD>   rank inside the workgroup by ballots (wg_rank); the 48-byte rows of NT tables (0, 1 or 2) and the
 //                             row's ordinal (ORD: through `ord`) copied to the rank.  The host picks the instantiation by
 //                             the pointers it was given: a kernel that tested them itself was 1 % slower than the
 //                             one-table kernel it replaced
@@ -13,6 +13,7 @@
 // with the table calls (ffq_tables.h).
 #pragma once
 #include "ffq_filter.h"
+#include "ffq_scan.h"
 
 namespace ffq {
 
@@ -23,22 +24,6 @@ __device__ __forceinline__ void row_copy48(const int64_t *__restrict__ table, in
     longlong2 *dst = reinterpret_cast<longlong2 *>(out + r * 6);
     const longlong2 a = src[0], b = src[1], c = src[2];
     dst[0] = a; dst[1] = b; dst[2] = c;
-}
-
-// How many threads with a lower number in the workgroup of 256 keep theirs.  Every thread calls it (a barrier inside); the
-// value means something to the keeping ones only.
-__device__ __forceinline__ uint32_t block_rank256(bool keep)
-{
-    __shared__ uint32_t s_w[4];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const unsigned long long m = __ballot(keep);
-    if (lane == 0) s_w[wid] = (uint32_t)__popcll(m);
-    __syncthreads();
-    uint32_t wpre = 0;
-#pragma unroll
-    for (int q = 0; q < 4; q++)
-        if (q < wid) wpre += s_w[q];
-    return wpre + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
 }
 
 // min_len <= pos3 - pos2 <= max_len, read from the table (push-down of the length filter of
@@ -79,7 +64,7 @@ __global__ __launch_bounds__(256) void k_compact_scatter(Keep keep, int64_t n, c
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const bool kept = keep(i, n);
-    const uint32_t rank = block_rank256(kept);
+    const uint32_t rank = wg_rank<256>(kept);
     if (!kept) return;
     const int64_t r = bbase[blockIdx.x] + rank;
     if (NT >= 1) row_copy48(t1, i, out1, r);

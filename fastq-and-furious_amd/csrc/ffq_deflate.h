@@ -6,7 +6,7 @@
 // would be longer.  Members do not depend on one another, so a WORKGROUP TAKES A BLOCK, under a capped persistent grid.
 //   k_deflate_members  a workgroup of 256 lanes per block: everything ffq_deflatewalk.h lists, in one kernel, the member
 //                      built in LDS and copied into the block's own 64 KiB slot of the scratch; its size
-//   k_scan_i64v        exclusive scan of the sizes (launch_scan_i64v)
+//   launch_scan        exclusive scan of the sizes (ffq_scan.h)
 //   k_deflate_pack     a workgroup per member: slot -> d_out, destination-aligned words; nothing if the total exceeds out_cap
 // The pack costs the compressed bytes once more, and spares the blocks any knowledge of one another.
 //
@@ -55,29 +55,6 @@ struct DeflateWords {
     __device__ __forceinline__ void plain(uint32_t i, uint32_t v) { w[i] = v; }
     __device__ __forceinline__ void shared(uint32_t i, uint32_t v) { atomicOr(&w[i], v); }
 };
-
-// exclusive prefix of x over the workgroup's lanes, and the sum (between two barriers of the caller's: wsum is reused)
-__device__ __forceinline__ uint32_t deflate_scan(uint32_t x, uint32_t *wsum, uint32_t &total)
-{
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    uint32_t incl = x;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(incl, d);
-        if (lane >= d) incl += y;
-    }
-    if (lane == 63) wsum[wid] = incl;
-    __syncthreads();
-    uint32_t pre = 0;
-    total = 0;
-#pragma unroll
-    for (int q = 0; q < DFL_LANES / 64; q++) {
-        const uint32_t t = wsum[q];
-        if (q < wid) pre += t;
-        total += t;
-    }
-    return pre + incl - x;
-}
 
 // slots: DFL_BLOCK words per workgroup; members: DFL_SLOT bytes per block; sizes: a word per block
 __global__ __launch_bounds__(DFL_LANES) void k_deflate_members(const uint8_t *__restrict__ src, int64_t n_bytes, int64_t n_blocks,
@@ -182,7 +159,8 @@ __global__ __launch_bounds__(DFL_LANES) void k_deflate_members(const uint8_t *__
             if (tid == nseg - 1) bits += s.llen[DFL_EOB];
         }
         uint32_t body_bits;
-        const uint32_t at = deflate_scan(bits, s.wsum, body_bits);
+        // (the words are handed in: the kernel has no LDS to spare; the barriers around this step are its own)
+        const uint32_t at = wg_excl_scan<DFL_LANES, SCAN_ANY>(bits, body_bits, s.wsum);
         const int head_bits = s.pl.head_bits;
         const int64_t stream_bits = (int64_t)head_bits + body_bits;
         const bool stored = dfl_stored(stream_bits, n);

@@ -10,7 +10,7 @@
 // or after `offset` (its parity comes from a wave-wide look at the entries in front, 64 per step).
 // No speculation, no chain walk:
 //   k_fa_count   one wave per tile: record starts per tile
-//   k_scan_i64   exclusive scan of those counts (ffq_kernels.h)
+//   launch_scan  exclusive scan of those counts (ffq_scan.h)
 //   k_fa_rows    one wave per tile: pos0, pos1, pos2 of every start at its rank, and pos3 (= pos0 of the
 //                next start, minus one) of every start but the tile's last
 //   k_fa_fix     pos3 of each tile's last start, from the row behind it (one thread per tile); status and

@@ -191,8 +191,7 @@ struct ffq_ctx {
     DevBuf<unsigned int> sel_cnt;       // row selection: kept rows per workgroup, their scan
     DevBuf<long long> sel_base;
     DevBuf<long long> col_sum;          // column selection: bytes per block of rows, their scan
-    DevBuf<long long> scan_bs;          // block sums of the two-level scan (launch_scan_i64v)
-    DevBuf<DevRes> scan_res;            // (the middle level's result block: nobody reads it)
+    DevBuf<long long> scan_bs;          // block sums of the two-level scan (launch_scan)
     DevBuf<DevRes> col_res;             //   its result block (row count, total bytes)
     // ffq_scan_host: pageable memory goes through three pinned staging slots, copied in by the
     // helper threads and out over two copy streams (and back the same way)
@@ -1003,37 +1002,22 @@ static int enqueue_front(ffq_ctx *c, ScanState &st)
 template <class T>
 static int grow_dev(ffq_ctx *c, DevBuf<T> &b, int64_t need);
 
-// in-place exclusive scan of nv int64 values on stream st, total into res (k_scan_i64v's contract): one workgroup for short
-// arrays, two levels for long ones
-static int launch_scan_i64v(ffq_ctx *c, hipStream_t st, long long *v, int64_t nv, int64_t n_rows, DevRes *res)
+// Exclusive scan of the nv values v[] (u32 counts or int64; hipMalloc'ed) into out[] on stream st -- out may be v -- and the
+// total where `total` puts it (ScanToWord, ScanToRes: ffq_scan.h).  One workgroup for short arrays, two levels for long ones;
+// the middle level scans the blocks' sums in place and its total is the array's.
+template <class T, class Total>
+static int launch_scan(ffq_ctx *c, hipStream_t st, const T *v, int64_t nv, long long *out, Total total)
 {
-    if (nv <= 2 * 32768) {
-        hipLaunchKernelGGL(k_scan_i64v, dim3(1), dim3(1024), 0, st, v, nv, n_rows, res);
+    if (nv <= scan_one_max<T>()) {
+        hipLaunchKernelGGL((k_scan_one<T, Total>), dim3(1), dim3(SCAN_ONE_WG), 0, st, v, nv, out, total);
         return FFQ_OK;
     }
     const int64_t nb = (nv + SCAN_BLK - 1) / SCAN_BLK;
     int rc = grow_dev(c, c->scan_bs, nb);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_scan_blksum, dim3((unsigned)nb), dim3(256), 0, st, (const long long *)v, nv, c->scan_bs);
-    hipLaunchKernelGGL(k_scan_i64v, dim3(1), dim3(1024), 0, st, c->scan_bs, nb, n_rows, res);
-    hipLaunchKernelGGL(k_scan_blkapply, dim3((unsigned)nb), dim3(256), 0, st, v, nv, (const long long *)c->scan_bs);
-    return FFQ_OK;
-}
-
-// the same for u32 counts -> int64 offsets + their total (k_scan_i64's contract)
-static int launch_scan_u32(ffq_ctx *c, hipStream_t st, const unsigned int *v, int64_t nv, long long *base, long long *total)
-{
-    if (nv <= 32768) {
-        hipLaunchKernelGGL(k_scan_i64, dim3(1), dim3(1024), 0, st, v, nv, base, total);
-        return FFQ_OK;
-    }
-    const int64_t nb = (nv + SCAN_BLK - 1) / SCAN_BLK;
-    int rc = grow_dev(c, c->scan_bs, nb);
-    if (rc) return rc;
-    if (c->scan_res.grow(1) != hipSuccess) return fail(FFQ_E_NOMEM, "hipMalloc failed");
-    hipLaunchKernelGGL(k_scan_blksum_u32, dim3((unsigned)nb), dim3(256), 0, st, v, nv, c->scan_bs);
-    hipLaunchKernelGGL(k_scan_i64v, dim3(1), dim3(1024), 0, st, c->scan_bs, nb, (int64_t)0, c->scan_res);
-    hipLaunchKernelGGL(k_scan_blkapply_u32, dim3((unsigned)nb), dim3(256), 0, st, v, nv, (const long long *)c->scan_bs, base, total);
+    hipLaunchKernelGGL(k_scan_blksum<T>, dim3((unsigned)nb), dim3(SCAN_BLK_WG), 0, st, v, nv, c->scan_bs);
+    hipLaunchKernelGGL((k_scan_one<long long, Total>), dim3(1), dim3(SCAN_ONE_WG), 0, st, (const long long *)c->scan_bs, nb, c->scan_bs, total);
+    hipLaunchKernelGGL(k_scan_blkapply<T>, dim3((unsigned)nb), dim3(SCAN_BLK_WG), 0, st, v, nv, (const long long *)c->scan_bs, out);
     return FFQ_OK;
 }
 
@@ -1079,7 +1063,7 @@ static int ranked_count(ffq_ctx *c, const LineIndex &L, int64_t ntiles, int64_t 
     if (!rank_reserve_tiles(c, ntiles)) return RK_CANNOT;
     if (c->col_res.grow(1) != hipSuccess) return RK_CANNOT;
     hipLaunchKernelGGL(k_rk_count, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, sA, L, R.tbase);
-    if (launch_scan_i64v(c, sA, R.tbase, ntiles, (int64_t)0, c->col_res)) return RK_CANNOT;
+    if (launch_scan(c, sA, (const long long *)R.tbase, ntiles, R.tbase, ScanToRes{c->col_res, 0})) return RK_CANNOT;
     HIPCHK(hipMemcpyAsync(c->h_word, &c->col_res->n_qual_bytes, sizeof(int64_t), hipMemcpyDeviceToHost, sA));
     HIPCHK(hipGetLastError());
     CTX_SYNC(c);
@@ -1128,7 +1112,7 @@ static int enqueue_offsets_and_decode(ffq_ctx *c, const ScanArgs &a, int64_t n_r
     hipLaunchKernelGGL(k_col_sum, dim3((unsigned)nblk), dim3(256), 0, sA, (const int64_t *)a.d_table, n_rows, 4, 0, 5,
                        a.n_bytes, a.s, a.add, c->col_sum);
     // (the scan's totals go into the scan's own result block: the decode kernel and the host read them there)
-    if ((rc = launch_scan_i64v(c, sA, c->col_sum, nblk, n_rows, c->dres))) return rc;
+    if ((rc = launch_scan(c, sA, (const long long *)c->col_sum, nblk, c->col_sum, ScanToRes{c->dres, n_rows}))) return rc;
     hipLaunchKernelGGL(k_col_offsets, dim3((unsigned)nblk), dim3(256), 0, sA, (const int64_t *)a.d_table, n_rows, 4, 0, 5,
                        a.n_bytes, a.s, a.add, (const long long *)c->col_sum, (const DevRes *)c->dres, a.d_qoff, c->p4s, c->qdir,
                        c->qdir.cap);
@@ -1623,7 +1607,7 @@ extern "C" int ffq_scan_fasta_device(ffq_ctx *c, const uint8_t *d_buf, int64_t n
         HIPCHK(hipEventRecord(c->ev[1], sA));
         const unsigned tb = (unsigned)((ntiles + 3) / 4);
         hipLaunchKernelGGL(k_fa_count, dim3(tb), dim3(256), 0, sA, L, offset, c->sel_cnt);
-        { const int rs = launch_scan_u32(c, sA, (const unsigned int *)c->sel_cnt, ntiles, c->sel_base, (long long *)c->d_word.p); if (rs) return rs; }
+        { const int rs = launch_scan(c, sA, (const unsigned int *)c->sel_cnt, ntiles, c->sel_base, ScanToWord{(long long *)c->d_word.p}); if (rs) return rs; }
         hipLaunchKernelGGL(k_fa_rows, dim3(tb), dim3(256), 0, sA, L, offset, add, (const long long *)c->sel_base,
                            (const long long *)c->d_word.p, d_table, table_cap, c->fa_hdr, (const unsigned int *)c->sel_cnt);
         hipLaunchKernelGGL(k_fa_fix, dim3((unsigned)((ntiles + 255) / 256)), dim3(256), 0, sA, L, offset, add,

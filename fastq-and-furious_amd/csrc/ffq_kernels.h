@@ -4,7 +4,8 @@
 //   k_chain_serial    single-lane walker: exact on any input, the last tier
 //   k_finalize*       end offset / result block, published to host-mapped memory
 //   k_decode_stream   Phred decode of every record's quality span (output-aligned stream)
-//   k_scan_i64, k_table_cut, k_table_lower_bound            table utilities (the compaction: ffq_compact.h)
+//   k_table_cut, k_table_lower_bound                        table utilities (the compaction: ffq_compact.h; the workgroup
+//                                                           prefix sum and the scan of an array: ffq_scan.h)
 //   k_arrayadd_b/q    the reference's array utilities
 //   k_synth_*, k_read_probe, k_selftest                     generators, diagnostics
 // The record chain itself: ffq_rows4.h (four-line fast path), ffq_chain.h (general path),
@@ -278,6 +279,7 @@ __global__ __launch_bounds__(256, MINW) void k_scan_lines(const uint8_t *__restr
 #include "ffq_rows4.h"
 #include "ffq_dense.h"
 #include "ffq_lite.h"
+#include "ffq_scan.h"
 
 namespace ffq {
 
@@ -622,79 +624,12 @@ __global__ __launch_bounds__(256) void k_decode_stream(const uint8_t *__restrict
 }
 
 // =========================================================================
-// k_scan_i64: exclusive scan of the kept-row counts of a compaction (ffq_compact.h) and of the FASTA scan's
-// entries per tile, one workgroup (launch_scan_u32 picks it for short arrays).
-// =========================================================================
-__global__ __launch_bounds__(1024) void k_scan_i64(const unsigned int *__restrict__ v, int64_t nv,
-                                                   long long *__restrict__ base, long long *__restrict__ total)
-{
-    // Exclusive scan of u32 counts into i64, one workgroup.  A thread owns 32 CONSECUTIVE values (eight 16-byte
-    // loads in flight, a sum in registers), the 1024 thread sums are scanned once per 32768 values, and the thread
-    // writes its 32 results -- one barrier round per 32768 values (a round per 1024 values took 65 us for the
-    // 65536 tiles of a GiB, 1 us each).
-    __shared__ long long s_w[16];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    long long carry = 0;
-    const bool vec = (reinterpret_cast<uintptr_t>(v) & 15) == 0 && (reinterpret_cast<uintptr_t>(base) & 15) == 0;
-    for (int64_t c0 = 0; c0 < nv; c0 += 32768) {
-        const int64_t b0 = c0 + (int64_t)tid * 32;
-        uint32_t x[32];
-        if (vec && b0 + 32 <= nv) {
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                const uint4 t = *reinterpret_cast<const uint4 *>(v + b0 + 4 * k);
-                x[4 * k] = t.x; x[4 * k + 1] = t.y; x[4 * k + 2] = t.z; x[4 * k + 3] = t.w;
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < 32; k++) x[k] = (b0 + k < nv) ? v[b0 + k] : 0u;
-        }
-        // (values are counts per tile / block: 32 of them and a wave's 64 sums fit 32 bits ... the running total
-        // of a thread is kept in 64 bits all the same)
-        unsigned long long mine = 0;
-#pragma unroll
-        for (int k = 0; k < 32; k++) mine += x[k];
-        // scan of the thread sums: within the wave in two 32-bit halves, the 16 wave totals through LDS
-        const uint32_t lo = wave_incl_scan((uint32_t)(mine & 0xFFFFFFu)), hi = wave_incl_scan((uint32_t)(mine >> 24));
-        const unsigned long long incl = ((unsigned long long)hi << 24) + lo;
-        if (lane == 63) s_w[wid] = (long long)incl;
-        __syncthreads();
-        long long wpre = 0, tot = 0;
-#pragma unroll
-        for (int q = 0; q < 16; q++) {
-            const long long t = s_w[q];
-            if (q < wid) wpre += t;
-            tot += t;
-        }
-        long long run = carry + wpre + (long long)(incl - mine);
-        if (vec && b0 + 32 <= nv) {
-#pragma unroll
-            for (int k = 0; k < 16; k++) {
-                longlong2 o;
-                o.x = run; run += x[2 * k];
-                o.y = run; run += x[2 * k + 1];
-                *reinterpret_cast<longlong2 *>(base + b0 + 2 * k) = o;
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < 32; k++) {
-                if (b0 + k < nv) base[b0 + k] = run;
-                run += x[k];
-            }
-        }
-        __syncthreads();
-        carry += tot;
-    }
-    if (tid == 0) *total = carry;
-}
-
-// =========================================================================
 // Column selection (push-down of an entryfunc that builds only ONE component of an entry,
 // /root/reference/doc/user-guide.rst:153-180: `buf[posarray[2]:posarray[3]]`; the header as
 // entryfunc cuts it, /root/reference/src/fastqandfurious.py:161-171: `buf[pos[0] + 1:pos[1]]`):
 // the packed stream buf[pos[ca] + shift : pos[cb]] (+ value) of every row and its CSR offsets.
 //   k_col_sum      bytes of the component per block of 256 rows
-//   k_scan_i64v    exclusive scan of those (one workgroup); total -> a result block
+//   launch_scan    exclusive scan of those (ffq_scan.h); total -> a result block
 //   k_col_offsets  offsets[i], start[i], directory of the output stream (qdir_mark)
 //   k_decode_stream (above) then copies: it is the Phred decode with another pair of columns
 // =========================================================================
@@ -712,223 +647,16 @@ __device__ __forceinline__ int64_t col_len(const int64_t *__restrict__ table, in
     return min(len, (int64_t)0x7FFFFFF0);
 }
 
-// exclusive prefix of `len` inside a 256-thread workgroup (lengths below 2^31) and the block's sum
-__device__ __forceinline__ int64_t block_excl_scan_len(int64_t len, int64_t &block_sum)
-{
-    __shared__ long long s_w[4];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const uint32_t lo = wave_incl_scan((uint32_t)len & 0xFFFFu), hi = wave_incl_scan((uint32_t)(len >> 16));
-    const long long incl = ((long long)hi << 16) + (long long)lo;
-    if (lane == 63) s_w[wid] = incl;
-    __syncthreads();
-    long long wpre = 0, tot = 0;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const long long t = s_w[q];
-        if (q < wid) wpre += t;
-        tot += t;
-    }
-    block_sum = tot;
-    return wpre + incl - len;
-}
+// (col_len's clamp keeps a length below 2^31: the wave scan of the two kernels below goes in two halves of 16 bits)
+constexpr int COL_LEN_BITS = 32;
 
 __global__ __launch_bounds__(256) void k_col_sum(const int64_t *__restrict__ table, int64_t n, int ca, int shift, int cb,
                                                  int64_t nbytes, int s, int64_t add, long long *__restrict__ bsum)
 {
     int64_t start, tot;
     const int64_t len = col_len(table, (int64_t)blockIdx.x * 256 + threadIdx.x, n, ca, shift, cb, nbytes, s, add, start);
-    (void)block_excl_scan_len(len, tot);
+    (void)wg_excl_scan<256, COL_LEN_BITS>(len, tot);
     if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-
-// in-place exclusive scan of int64 values by one workgroup; the total goes to res (n_records = n,
-// n_qual_bytes = total: what k_decode_stream reads)
-__global__ __launch_bounds__(1024) void k_scan_i64v(long long *__restrict__ v, int64_t nv, int64_t n_rows, DevRes *res)
-{
-    // A thread owns 32 CONSECUTIVE values (a sum in registers), the 1024 thread sums are scanned once per 32768 values (six
-    // shuffles inside the wave, the sixteen wave totals through LDS): one barrier round per 32768 values.  (The
-    // Hillis-Steele version this replaces took twenty barriers per 1024 values: 483 us for the 262144 tiles of 4 GiB --
-    // a fifth of the list-ranking tier's time --, 200 us for the row blocks of a 10 GiB table.)
-    __shared__ long long s_w[16];
-    constexpr int PER = 32;
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    long long carry = 0;
-    for (int64_t c0 = 0; c0 < nv; c0 += 1024 * PER) {
-        const int64_t b0 = c0 + (int64_t)tid * PER;
-        long long x[PER];
-        if (b0 + PER <= nv) {
-#pragma unroll
-            for (int k = 0; k < PER / 2; k++) {
-                const longlong2 t = *reinterpret_cast<const longlong2 *>(v + b0 + 2 * k);      // (v: hipMalloc'ed, b0 a multiple of 32)
-                x[2 * k] = t.x; x[2 * k + 1] = t.y;
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < PER; k++) x[k] = (b0 + k < nv) ? v[b0 + k] : 0;
-        }
-        long long mine = 0;
-#pragma unroll
-        for (int k = 0; k < PER; k++) mine += x[k];
-        long long incl = mine;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const long long y = __shfl_up(incl, d);
-            if (lane >= d) incl += y;
-        }
-        if (lane == 63) s_w[wid] = incl;
-        __syncthreads();
-        long long wpre = 0, tot = 0;
-#pragma unroll
-        for (int q = 0; q < 16; q++) {
-            const long long t = s_w[q];
-            if (q < wid) wpre += t;
-            tot += t;
-        }
-        long long run = carry + wpre + incl - mine;
-        if (b0 + PER <= nv) {
-#pragma unroll
-            for (int k = 0; k < PER / 2; k++) {
-                longlong2 o;
-                o.x = run; run += x[2 * k];
-                o.y = run; run += x[2 * k + 1];
-                *reinterpret_cast<longlong2 *>(v + b0 + 2 * k) = o;
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < PER; k++) { if (b0 + k < nv) v[b0 + k] = run; run += x[k]; }
-        }
-        __syncthreads();
-        carry += tot;
-    }
-    if (tid == 0) { res->n_records = n_rows; res->n_qual_bytes = carry; res->fallback = 0; }
-}
-
-// The same scan in two levels for long arrays (the per-tile counts of a 4 GiB buffer: 262 144 values took the one
-// workgroup above 132 us -- eight rounds, every lane reading its own 256 bytes): k_scan_blksum, one workgroup per 2048
-// values, their sums; k_scan_i64v over the sums (it also writes the total); k_scan_blkapply, the scan inside each block
-// on top of its base.  Three launches of a few microseconds.
-constexpr int SCAN_BLK = 2048;
-
-__device__ __forceinline__ long long scan_blk_load8(const long long *__restrict__ v, int64_t nv, int64_t b0, long long (&x)[8])
-{
-    if (b0 + 8 <= nv) {
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const longlong2 t = *reinterpret_cast<const longlong2 *>(v + b0 + 2 * k);      // (v: hipMalloc'ed, b0 a multiple of 8)
-            x[2 * k] = t.x; x[2 * k + 1] = t.y;
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < 8; k++) x[k] = (b0 + k < nv) ? v[b0 + k] : 0;
-    }
-    long long s = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) s += x[k];
-    return s;
-}
-
-__global__ __launch_bounds__(256) void k_scan_blksum(const long long *__restrict__ v, int64_t nv, long long *__restrict__ bs)
-{
-    __shared__ long long s_w[4];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    long long x[8];
-    long long s = scan_blk_load8(v, nv, (int64_t)blockIdx.x * SCAN_BLK + (int64_t)tid * 8, x);
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
-    if (lane == 0) s_w[wid] = s;
-    __syncthreads();
-    if (tid == 0) bs[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-}
-
-// ... and of u32 counts into i64 offsets (k_scan_i64's contract: base[i] = values in front of i, *total = all of them)
-__device__ __forceinline__ long long scan_blk_load8u(const unsigned int *__restrict__ v, int64_t nv, int64_t b0, uint32_t (&x)[8])
-{
-    if (b0 + 8 <= nv) {
-        const uint4 a = *reinterpret_cast<const uint4 *>(v + b0), b = *reinterpret_cast<const uint4 *>(v + b0 + 4);   // (hipMalloc'ed, b0 a multiple of 8)
-        x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 8; k++) x[k] = (b0 + k < nv) ? v[b0 + k] : 0u;
-    }
-    long long s = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) s += (long long)x[k];
-    return s;
-}
-
-__global__ __launch_bounds__(256) void k_scan_blksum_u32(const unsigned int *__restrict__ v, int64_t nv, long long *__restrict__ bs)
-{
-    __shared__ long long s_w[4];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    uint32_t x[8];
-    long long s = scan_blk_load8u(v, nv, (int64_t)blockIdx.x * SCAN_BLK + (int64_t)tid * 8, x);
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
-    if (lane == 0) s_w[wid] = s;
-    __syncthreads();
-    if (tid == 0) bs[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-}
-
-__global__ __launch_bounds__(256) void k_scan_blkapply_u32(const unsigned int *__restrict__ v, int64_t nv, const long long *__restrict__ bs,
-                                                           long long *__restrict__ base, long long *__restrict__ total)
-{
-    __shared__ long long s_w[4];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int64_t b0 = (int64_t)blockIdx.x * SCAN_BLK + (int64_t)tid * 8;
-    const long long bb = bs[blockIdx.x];
-    uint32_t x[8];
-    const long long mine = scan_blk_load8u(v, nv, b0, x);
-    long long incl = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const long long y = __shfl_up(incl, d);
-        if (lane >= d) incl += y;
-    }
-    if (lane == 63) s_w[wid] = incl;
-    __syncthreads();
-    long long wpre = 0;
-#pragma unroll
-    for (int q = 0; q < 4; q++)
-        if (q < wid) wpre += s_w[q];
-    long long run = bb + wpre + incl - mine;
-#pragma unroll
-    for (int k = 0; k < 8; k++) { if (b0 + k < nv) base[b0 + k] = run; run += (long long)x[k]; }
-    if (blockIdx.x == gridDim.x - 1 && tid == 255) *total = run;        // (values past nv count as zero)
-}
-
-__global__ __launch_bounds__(256) void k_scan_blkapply(long long *__restrict__ v, int64_t nv, const long long *__restrict__ bs)
-{
-    __shared__ long long s_w[4];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int64_t b0 = (int64_t)blockIdx.x * SCAN_BLK + (int64_t)tid * 8;
-    const long long base = bs[blockIdx.x];
-    long long x[8];
-    const long long mine = scan_blk_load8(v, nv, b0, x);
-    long long incl = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const long long y = __shfl_up(incl, d);
-        if (lane >= d) incl += y;
-    }
-    if (lane == 63) s_w[wid] = incl;
-    __syncthreads();
-    long long wpre = 0;
-#pragma unroll
-    for (int q = 0; q < 4; q++)
-        if (q < wid) wpre += s_w[q];
-    long long run = base + wpre + incl - mine;
-    if (b0 + 8 <= nv) {
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            longlong2 o;
-            o.x = run; run += x[2 * k];
-            o.y = run; run += x[2 * k + 1];
-            *reinterpret_cast<longlong2 *>(v + b0 + 2 * k) = o;
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < 8; k++) { if (b0 + k < nv) v[b0 + k] = run; run += x[k]; }
-    }
 }
 
 __global__ __launch_bounds__(256) void k_col_offsets(const int64_t *__restrict__ table, int64_t n, int ca, int shift, int cb,
@@ -939,7 +667,7 @@ __global__ __launch_bounds__(256) void k_col_offsets(const int64_t *__restrict__
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     int64_t start, tot;
     const int64_t len = col_len(table, i, n, ca, shift, cb, nbytes, s, add, start);
-    const int64_t off = bbase[blockIdx.x] + block_excl_scan_len(len, tot);
+    const int64_t off = bbase[blockIdx.x] + wg_excl_scan<256, COL_LEN_BITS>(len, tot);
     if (i < n) {
         coff[i] = off;
         starts[i] = start;

@@ -4,7 +4,7 @@
 // Shape: the render pass's three steps (ffq_render.h).
 //   k_merge_sum     per block of 256 pairs, from the rows' positions and the pair's insert size alone: the bytes of merged
 //                   text and the number of pairs that are NOT merged; the call's counts [0], [3], [4] on the way
-//   the two scans   launch_scan_i64v over the bytes, launch_scan_u32 over the unmerged pairs
+//   the two scans   launch_scan (ffq_scan.h) over the bytes and over the unmerged pairs
 //   k_merge_rows    a workgroup per block of 256 pairs.  A thread per pair first: the pair is parsed again, the prefix inside
 //                   the block gives a merged pair its place in the text (d_off) and an unmerged pair its place in the rest
 //                   tables, where the thread copies both rows (96 bytes) and the ordinal.  Then a GROUP of eight lanes per
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(MERGE_WG) void k_merge_sum(PairSide A, PairSide B, 
             if (len > 0) { c_m++; c_b += (unsigned long long)P.L; c_o += (unsigned long long)mrg_overlap(P.n1, P.n2, P.o); }
         }
         int64_t tot;
-        (void)render_block_scan(len, tot);
+        (void)wg_excl_scan<MERGE_WG, SCAN_ANY>(len, tot);
         const int rest = __syncthreads_count(have && len == 0 ? 1 : 0);  // (and the scan's LDS may be written again)
         if (threadIdx.x == 0) { bsum[b] = tot; brest[b] = (unsigned int)rest; }
     }
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(MERGE_WG) void k_merge_rows(PairSide A, PairSide B,
     __shared__ MrgPair s_pair[MERGE_WG];
     __shared__ int64_t s_off[MERGE_WG], s_len[MERGE_WG];
     __shared__ uint32_t s_w[MERGE_WG / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
     const int64_t r0 = (int64_t)blockIdx.x * MERGE_WG, k = r0 + tid;
     const int64_t total = res->n_qual_bytes;
     {
@@ -155,10 +155,9 @@ __global__ __launch_bounds__(MERGE_WG) void k_merge_rows(PairSide A, PairSide B,
             len = merge_parse(A, B, I.a01, I.a23, I.a45, I.b23, I.b45, I.ins, P);
         }
         const bool unm = have && len == 0;
-        const unsigned long long m = __ballot(unm);
-        if (lane == 0) s_w[wid] = (uint32_t)__popcll(m);
+        const unsigned long long m = wg_rank_put<MERGE_WG>(unm, s_w);
         int64_t tot;
-        const int64_t at = tbase[blockIdx.x] + render_block_scan(len, tot);       // (a barrier inside: s_w is there behind it)
+        const int64_t at = tbase[blockIdx.x] + wg_excl_scan<MERGE_WG, SCAN_ANY>(len, tot);    // (a barrier inside: s_w is there behind it)
         s_pair[tid] = P; s_off[tid] = at; s_len[tid] = len;
         if (off && have) off[k] = at;
         if (blockIdx.x == 0 && tid == 0) {
@@ -166,11 +165,7 @@ __global__ __launch_bounds__(MERGE_WG) void k_merge_rows(PairSide A, PairSide B,
             blk->cnt[2] = (unsigned long long)total;
         }
         if (unm) {
-            uint32_t wpre = 0;
-#pragma unroll
-            for (int q = 0; q < MERGE_WG / 64; q++)
-                if (q < wid) wpre += s_w[q];
-            const int64_t r = rbase[blockIdx.x] + wpre + __popcll(m & ((1ull << lane) - 1ull));
+            const int64_t r = rbase[blockIdx.x] + wg_rank_get<MERGE_WG>(m, s_w);
             longlong2 *da = reinterpret_cast<longlong2 *>(rest1 + r * 6), *db = reinterpret_cast<longlong2 *>(rest2 + r * 6);
             da[0] = I.a01; da[1] = I.a23; da[2] = I.a45;
             db[0] = I.b01; db[1] = I.b23; db[2] = I.b45;

@@ -10,7 +10,7 @@
 // first candidate at >= offset.  No speculation at all:
 //
 //   k_rk_count   candidates per tile                          (one wave per tile)
-//   k_scan_i64v  exclusive scan -> candidate ordinals
+//   launch_scan  exclusive scan -> candidate ordinals (ffq_scan.h)
 //   k_rk_list    candidate c -> its line-index entry
 //   k_rk_succ    ONE WAVE PER CANDIDATE: the scanner call and the successor search, with the wave-wide
 //                searches of the serial walker (a few memory round trips whatever the record's

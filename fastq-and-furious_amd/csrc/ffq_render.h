@@ -11,7 +11,7 @@
 //
 // Shape.  Three launches behind one another:
 //   k_render_sum    rendered bytes per block of 256 rows (and the number of renderable rows)
-//   k_scan_i64v     exclusive scan of those (launch_scan_i64v: the machinery of the column gather)
+//   launch_scan     exclusive scan of those (ffq_scan.h: the machinery of the column gather)
 //   k_render_rows   a workgroup per block of 256 rows: the prefix inside the block gives every row its place in the
 //                   output (d_off), then a GROUP of eight lanes copies a row -- thirty-two rows at a time, neighbours in
 //                   the output, so that a wave's stores fall into one run of lines
@@ -33,6 +33,8 @@ constexpr int RENDER_WG = 256;
 constexpr int RENDER_G = 8;           // lanes per row of the short rows' kernel
 constexpr int RENDER_U = 4;           // chunks per lane in flight
 constexpr int RENDER_LONG = 4096;     // output bytes above which a row gets a wave of its own
+// (the prefix of the rows' lengths inside a block is wg_excl_scan<RENDER_WG, SCAN_ANY>, 64-bit throughout: a row that repeats
+// most of a large buffer three times over is longer than 2^31)
 
 // counters of a call: output bytes, rows rendered, rows on the long list
 struct RenderBlock { unsigned long long total, rendered, n_long; };
@@ -58,31 +60,6 @@ __device__ __forceinline__ int64_t render_parse(longlong2 r01, longlong2 r23, lo
     return R.h + R.s + R.q + 6;
 }
 
-// exclusive prefix of `len` inside a 256-thread workgroup and the block's sum (64-bit throughout: a row that repeats
-// most of a large buffer three times over is longer than 2^31)
-__device__ __forceinline__ int64_t render_block_scan(int64_t len, int64_t &block_sum)
-{
-    __shared__ long long s_w[RENDER_WG / 64];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    long long incl = len;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const long long y = __shfl_up(incl, d);
-        if (lane >= d) incl += y;
-    }
-    if (lane == 63) s_w[wid] = incl;
-    __syncthreads();
-    long long wpre = 0, tot = 0;
-#pragma unroll
-    for (int q = 0; q < RENDER_WG / 64; q++) {
-        const long long t = s_w[q];
-        if (q < wid) wpre += t;
-        tot += t;
-    }
-    block_sum = tot;
-    return wpre + incl - len;
-}
-
 __device__ __forceinline__ int64_t render_row_len(const int64_t *__restrict__ table, int64_t row, int64_t n_rows,
                                                   int64_t nbytes, int s, int64_t add, RenderRow &R)
 {
@@ -103,7 +80,7 @@ __global__ __launch_bounds__(RENDER_WG) void k_render_sum(int64_t nbytes, int s,
         RenderRow R;
         const int64_t len = render_row_len(table, row, n_rows, nbytes, s, add, R);
         int64_t tot;
-        (void)render_block_scan(len, tot);
+        (void)wg_excl_scan<RENDER_WG, SCAN_ANY>(len, tot);
         if (threadIdx.x == 0) bsum[b] = tot;
         cnt += (unsigned int)__popcll(__ballot(len > 0));
         __syncthreads();                                    // (the scan's LDS is written again by the next block of rows)
@@ -227,7 +204,7 @@ __global__ __launch_bounds__(RENDER_WG) void k_render_rows(const uint8_t *__rest
         RenderRow R;
         const int64_t len = render_row_len(table, r0 + tid, n_rows, nbytes, s, add, R);
         int64_t tot;
-        const int64_t at = bbase[blockIdx.x] + render_block_scan(len, tot);
+        const int64_t at = bbase[blockIdx.x] + wg_excl_scan<RENDER_WG, SCAN_ANY>(len, tot);
         s_row[tid] = R; s_off[tid] = at; s_len[tid] = len;
         if (off && r0 + tid < n_rows) off[r0 + tid] = at;
         if (blockIdx.x == 0 && tid == 0) {

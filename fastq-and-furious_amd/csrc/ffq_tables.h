@@ -125,7 +125,7 @@ static int compact_scatter(ffq_ctx *c, hipStream_t st, Keep keep, int64_t n, con
                            int64_t *out1, int64_t *out2, int64_t *idx)
 {
     const int64_t nblk = (n + 255) / 256;
-    const int rc = launch_scan_u32(c, st, (const unsigned int *)c->sel_cnt, nblk, c->sel_base, (long long *)c->d_word.p);
+    const int rc = launch_scan(c, st, (const unsigned int *)c->sel_cnt, nblk, c->sel_base, ScanToWord{(long long *)c->d_word.p});
     if (rc) return rc;
     if (!t1) { t1 = t2; out1 = out2; t2 = nullptr; }       // (one table: it is the first)
     auto *launch = !t1 ? (ord ? compact_launch<Keep, 0, true> : compact_launch<Keep, 0, false>)
@@ -258,7 +258,7 @@ extern "C" int ffq_table_gather_column(ffq_ctx *c, const uint8_t *d_buf, int64_t
     if (rc) return rc;
     hipLaunchKernelGGL(k_col_sum, dim3((unsigned)nblk), dim3(256), 0, st, d_table, n_rows, col_begin, begin_shift, col_end,
                        n_bytes, sentinel ? 1 : 0, add, c->col_sum);
-    if ((rc = launch_scan_i64v(c, st, c->col_sum, nblk, n_rows, c->col_res))) return rc;
+    if ((rc = launch_scan(c, st, (const long long *)c->col_sum, nblk, c->col_sum, ScanToRes{c->col_res, n_rows}))) return rc;
     hipLaunchKernelGGL(k_col_offsets, dim3((unsigned)nblk), dim3(256), 0, st, d_table, n_rows, col_begin, begin_shift,
                        col_end, n_bytes, sentinel ? 1 : 0, add, (const long long *)c->col_sum, (const DevRes *)c->col_res, d_off,
                        c->p4s, c->qdir, c->qdir.cap);
@@ -721,7 +721,7 @@ extern "C" int ffq_table_render_fastq(ffq_ctx *c, const uint8_t *d_buf, int64_t 
     if ((rc = call_blk_begin(c, &blk))) return rc;
     hipLaunchKernelGGL(k_render_sum, dim3((unsigned)std::min<int64_t>(nblk, 2048)), dim3(RENDER_WG), 0, st, n_bytes, s, add,
                        d_table, n_rows, nblk, c->col_sum, blk);
-    if ((rc = launch_scan_i64v(c, st, c->col_sum, nblk, n_rows, c->col_res))) return rc;
+    if ((rc = launch_scan(c, st, (const long long *)c->col_sum, nblk, c->col_sum, ScanToRes{c->col_res, n_rows}))) return rc;
     hipLaunchKernelGGL(k_render_rows, dim3((unsigned)nblk), dim3(RENDER_WG), 0, st, d_buf, n_bytes, s, add, d_table, n_rows,
                        (const long long *)c->col_sum, (const DevRes *)c->col_res, d_out, out_cap, d_off, c->render_list,
                        blk);
@@ -766,7 +766,7 @@ static int deflate_enqueue(ffq_ctx *c, hipStream_t st, const uint8_t *d_src, int
     const int64_t n_blocks = deflate_blocks(n_bytes);
     hipLaunchKernelGGL(k_deflate_members, dim3((unsigned)std::min<int64_t>(n_blocks, DEFLATE_GRID)), dim3(DFL_LANES), 0, st, d_src, n_bytes,
                        n_blocks, c->deflate_slots.p, c->deflate_members.p, c->col_sum.p, blk);
-    if (int rc = launch_scan_i64v(c, st, c->col_sum, n_blocks, n_blocks, c->col_res)) return rc;
+    if (int rc = launch_scan(c, st, (const long long *)c->col_sum, n_blocks, c->col_sum, ScanToRes{c->col_res, n_blocks})) return rc;
     hipLaunchKernelGGL(k_deflate_pack, dim3((unsigned)std::min<int64_t>(n_blocks, 4096)), dim3(256), 0, st, (const uint8_t *)c->deflate_members.p,
                        (const long long *)c->col_sum.p, n_blocks, (const DevRes *)c->col_res.p, d_out, out_cap, d_member_off, blk);
     return FFQ_OK;
@@ -836,8 +836,8 @@ extern "C" int ffq_table_pair_merge(ffq_ctx *c, const ffq_table_view *m1, const 
     if ((rc = call_blk_begin(c, &blk))) return rc;
     hipLaunchKernelGGL(k_merge_sum, dim3((unsigned)std::min<int64_t>(nblk, 2048)), dim3(MERGE_WG), 0, st, A, B, n_pairs, nblk, d_insert, d_ord,
                        c->col_sum.p, c->sel_cnt.p, blk);
-    if ((rc = launch_scan_i64v(c, st, c->col_sum, nblk, n_pairs, c->col_res))) return rc;
-    if ((rc = launch_scan_u32(c, st, (const unsigned int *)c->sel_cnt, nblk, c->sel_base, (long long *)c->d_word.p))) return rc;
+    if ((rc = launch_scan(c, st, (const long long *)c->col_sum, nblk, c->col_sum, ScanToRes{c->col_res, n_pairs}))) return rc;
+    if ((rc = launch_scan(c, st, (const unsigned int *)c->sel_cnt, nblk, c->sel_base, ScanToWord{(long long *)c->d_word.p}))) return rc;
     hipLaunchKernelGGL(k_merge_rows, dim3((unsigned)nblk), dim3(MERGE_WG), 0, st, A, B, n_pairs, d_insert, d_ord, (const long long *)c->col_sum,
                        (const DevRes *)c->col_res, (const long long *)c->sel_base, d_text, text_cap, d_off, d_rest1, d_rest2, d_rest_ord,
                        blk);

@@ -263,7 +263,7 @@ def test_fasta_long_header_runs(gpu_ctx, oracle, pkg):
 
 @pytest.mark.gpu
 def test_fasta_and_select_at_size(gpu_ctx, oracle, pkg):
-    """Past 32 768 tiles / row blocks the offsets come from the two-level scan (launch_scan_u32): 640 MiB of FASTA (an
+    """Past 32 768 tiles / row blocks the offsets come from the two-level scan (launch_scan): 640 MiB of FASTA (an
     8 MiB block of distinct entries repeated on the device) -- EVERY row against the oracle's rows of the block + the
     repeat's offset --, then the length filter over that table (9 M rows would do; here what the scan gave) against torch."""
     import numpy as np
