@@ -28,7 +28,7 @@ CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(CSRC, "libffq_hip.so")
 PROBE_LIB = os.path.join(CSRC, "libffq_probe.so")
-SOURCES = ["ffq_hip.hip"]
+SOURCES = ["ffq_hip.hip", "ffq_umi.hip"]      # (ffq_umi.hip: the UMI kernels, a translation unit of their own -- csrc/ffq_umi.h says why)
 
 
 def _hipcc():

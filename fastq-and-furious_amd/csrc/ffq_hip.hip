@@ -19,6 +19,8 @@
 #include "ffq_pair.h"
 #include "ffq_overlap.h"
 #include "ffq_render.h"
+#include "ffq_umiwalk.h"
+#include "ffq_umi_launch.h"
 #include "ffq_merge.h"
 #include "ffq_correct.h"
 #include "ffq_dedup.h"

@@ -180,6 +180,9 @@ struct ffq_stream {
     struct { bool on = false; uint8_t bytes[64] = {0}; int len = 0, err = 0, overlap = 0; int64_t last[3] = {0, 0, 0}; } adapter;
     // poly-tail trimming of every fill's table: poly-G in front of the adapter trim, poly-X behind it (ffq_stream_set_poly; 0: off)
     struct { int g = 0, x = 0; int64_t last_g[3] = {0, 0, 0}, last_x[3] = {0, 0, 0}; } poly;
+    // UMIs (ffq_stream_set_umi, ffq_pair_set_umi): on: the render puts the tag into the names; take: this stream's reads begin with
+    // one, which every fill's table loses in front of the trims; the take's counts and the tagged rows of the last fill or round
+    struct { bool on = false, take = false; ffq_umi_rules rules = {}; int64_t last[3] = {0, 0, 0}, tagged = 0; } umi;
     // push-down: rows by sequence length, one component of the kept rows (ffq_stream_set_filter)
     struct { bool on = false; int64_t min = 0, max = 0; int col = 0, add = 0; int64_t scanned = 0, col_bytes = 0; } filter;
     // content rules of the filter (ffq_stream_set_content) and the eight counts of the last fill's select (with or without them)
@@ -412,24 +415,37 @@ struct Table { const int64_t *d_rows; int64_t n; };
 // (it had at least that), a trim only takes bytes away -- except a record whose quality ends with the buffer, without a newline, which gains one
 // byte: a fill of `len` bytes renders to at most len + 1.  A stream that compresses (ffq_stream_set_compress) deflates the
 // text where it lies, behind the render, and only the members go back.
-static int stream_render(ffq_stream *s, const Fill &f, const Table &t)
+// THE TAGGED ROUTE (s->umi.on) has another bound: a row gains its insert -- a mate that gives no bases still gains a tag, so "never
+// longer than it was" no longer holds --, at most 3 + prefix_len + 2 * len bytes (delim, prefix and '_', two tags and the '_'
+// between them): len + 1 + rows * that.  src: the views whose row i may carry the tag of read 1 / read 2, in step with t's rows;
+// NULL: the rendered table itself carries it (a single stream).
+static int stream_render(ffq_stream *s, const Fill &f, const Table &t, const ffq_table_view *src)
 {
     StreamBufs *b = s->b;
     int64_t *last = s->render.last;
     last[0] = last[1] = last[2] = 0;
+    s->umi.tagged = 0;
     for (int64_t &x : s->compress.last) x = 0;
     if (t.n <= 0) return FFQ_OK;
     int rc = FFQ_OK;
-    if (f.n + 64 > b->ren.d.cap) {
+    const int64_t cap = f.n + 1 + (s->umi.on ? t.n * (3 + s->umi.rules.prefix_len + 2 * (int64_t)s->umi.rules.len) : 0);
+    if (cap + 63 > b->ren.d.cap) {
         NearGpu near(s->c);
-        rc = stream_grow(b->ren, f.n + 64, "ffq_stream: no memory for %lld rendered bytes", f.n + 64);
+        rc = stream_grow(b->ren, cap + 63, "ffq_stream: no memory for %lld rendered bytes", cap + 63);
     }
-    const int64_t bgz_cap = ffq_deflate_bgzf_bound(f.n + 1);
+    const int64_t bgz_cap = ffq_deflate_bgzf_bound(cap);
     if (!rc && s->compress.on && bgz_cap > b->bgz.d.cap) {
         NearGpu near(s->c);
         rc = stream_grow(b->bgz, bgz_cap, "ffq_stream: no memory for %lld compressed bytes", bgz_cap);
     }
-    if (!rc) rc = ffq_table_render_fastq(s->c, f.d_buf, f.n, 0, f.add, t.d_rows, t.n, b->ren.d, f.n + 1, nullptr, last);
+    if (!rc && s->umi.on) {
+        const ffq_table_view own = {f.d_buf, f.n, 0, f.add, t.d_rows};
+        int64_t st[4] = {0, 0, 0, 0};
+        rc = ffq_table_render_fastq_umi(s->c, &own, t.n, src ? &src[0] : &own, src ? &src[1] : &own, &s->umi.rules, b->ren.d, cap, nullptr, st);
+        last[0] = st[0]; last[1] = st[1]; last[2] = st[2];
+        s->umi.tagged = st[3];
+    } else if (!rc)
+        rc = ffq_table_render_fastq(s->c, f.d_buf, f.n, 0, f.add, t.d_rows, t.n, b->ren.d, f.n + 1, nullptr, last);
     if (rc == FFQ_E_TABLE_FULL)
         return fail(FFQ_E_INTERNAL, "ffq_stream: a fill of %lld bytes rendered to %lld", (long long)f.n, (long long)last[0]);
     if (rc) return rc;
@@ -889,6 +905,32 @@ extern "C" int ffq_stream_poly_trimmed(ffq_stream *s, int64_t stats_g[3], int64_
     return FFQ_OK;
 }
 
+// UMIs in the stream: every fill's table goes through ffq_table_take_umi in place on the device, in front of every trim, and the
+// render puts the tag into the names (ffq_table_render_fastq_umi, the rendered rows their own source).  A single stream has
+// read 1 only.  The other rules are ffq_stream_set_trim's.
+extern "C" int ffq_stream_set_umi(ffq_stream *s, const ffq_umi_rules *rules)
+{
+    if (!s) return fail(FFQ_E_ARG, "ffq_stream_set_umi: NULL stream");
+    int rc = umi_arg("ffq_stream_set_umi", rules, nullptr);
+    if (!rc && rules->loc != FFQ_UMI_READ1) rc = fail(FFQ_E_ARG, "ffq_stream_set_umi: a single stream has read 1 only (loc is FFQ_UMI_READ1)");
+    if (!rc && s->paired) rc = fail(FFQ_E_ARG, "ffq_stream_set_umi: a pair walks this stream (ffq_pair_set_umi)");
+    if (!rc) rc = stream_settable(s, "ffq_stream_set_umi", DECODE_UNTRIMMED, true);
+    if (rc) return rc;
+    s->umi.on = s->umi.take = true;
+    s->umi.rules = *rules;
+    return FFQ_OK;
+}
+
+// {rows taken, bases removed, rows skipped, rows tagged in the output} of the fill ffq_stream_next has just returned
+extern "C" int ffq_stream_umi_counts(ffq_stream *s, int64_t counts[4])
+{
+    if (!s || !counts) return fail(FFQ_E_ARG, "ffq_stream_umi_counts: NULL argument");
+    if (!s->umi.on) return fail(FFQ_E_ARG, "ffq_stream_umi_counts: the stream takes no UMIs (ffq_stream_set_umi)");
+    for (int i = 0; i < 3; i++) counts[i] = s->umi.last[i];
+    counts[3] = s->umi.tagged;
+    return FFQ_OK;
+}
+
 // Statistics in the stream: every fill's table is counted on the device (ffq_table_stats, accumulating, no host wait) --
 // FFQ_STATS_IN right behind the scan, FFQ_STATS_OUT on the table that is rendered and copied back -- into two blocks of
 // FFQ_STATS_WORDS(max_cycles) words the stream owns.
@@ -1072,7 +1114,7 @@ static int stream_scan(ffq_stream *s, const Fill &f, ffq_scan_result *res)
 }
 
 // ---- the two ends of a mate's chain (a fill of a single stream, either mate of a round of a pair).  front: [keys], [stats IN],
-// [ends], [quality trim], [poly-G], [adapter], [poly-X] on the `n` scanned rows at `rows`, which the trims edit in place
+// [UMI take], [ends], [quality trim], [poly-G], [adapter], [poly-X] on the `n` scanned rows at `rows`, which the trims edit in place
 static int chain_front(ffq_stream *s, const Fill &f, int64_t *rows, int64_t n)
 {
     int rc = FFQ_OK;
@@ -1082,6 +1124,8 @@ static int chain_front(ffq_stream *s, const Fill &f, int64_t *rows, int64_t n)
     }
     if (!rc && (s->stats.which & FFQ_STATS_IN))
         rc = ffq_table_stats(s->c, f.d_buf, f.n, 0, f.add, rows, n, s->stats.base, s->stats.cycles, 1, stream_stats_block(s, FFQ_STATS_IN), nullptr);
+    if (!rc && s->umi.take)         // (behind the keys and the statistics IN, which see the read as read; every trim sees it without its UMI)
+        rc = ffq_table_take_umi(s->c, f.d_buf, f.n, 0, f.add, rows, n, s->umi.rules.len, s->umi.rules.skip, rows, s->umi.last);
     if (!rc && s->ends.on)          // (in front of every other trim: fastp's order)
         rc = ffq_table_trim_ends(s->c, f.d_buf, f.n, 0, f.add, rows, n, &s->ends.rules, rows, s->ends.last);
     if (!rc && s->trim.on)
@@ -1095,13 +1139,15 @@ static int chain_front(ffq_stream *s, const Fill &f, int64_t *rows, int64_t n)
     return rc;
 }
 
-// back: [stats OUT], [render + text D2H], rows D2H into the stream's tab.h, of the table that is handed out
-static int chain_back(ffq_stream *s, const Fill &f, const Table &t)
+// back: [stats OUT], [render + text D2H], rows D2H into the stream's tab.h, of the table that is handed out.  umi_src: of a pair
+// whose names get a UMI, both mates' views of their kept rows (stream_render's src): the tag may be the other mate's, which is
+// handed in here -- a mate's chain does not reach across
+static int chain_back(ffq_stream *s, const Fill &f, const Table &t, const ffq_table_view *umi_src = nullptr)
 {
     int rc = FFQ_OK;
     if (s->stats.which & FFQ_STATS_OUT)
         rc = ffq_table_stats(s->c, f.d_buf, f.n, 0, f.add, t.d_rows, t.n, s->stats.base, s->stats.cycles, 1, stream_stats_block(s, FFQ_STATS_OUT), nullptr);
-    if (!rc && s->render.on) rc = stream_render(s, f, t);
+    if (!rc && s->render.on) rc = stream_render(s, f, t, umi_src);
     if (rc) return rc;
     if (t.n > 0) HIPCHK(hipMemcpyAsync(s->b->tab.h, t.d_rows, (size_t)t.n * 48, hipMemcpyDeviceToHost, s->c->stream));
     return FFQ_OK;
@@ -1112,7 +1158,7 @@ static int chain_back(ffq_stream *s, const Fill &f, const Table &t)
 // dropped record costs the host nothing, doc/user-guide.rst:153-180); what follows is written once, for either table.
 // This is the one place that states the order of a fill's work on the scan stream, in every configuration:
 //     carry H2D, wait copied[0], wait copied[1], scan, front (the keys of the dedup first, on the rows as scanned; then
-//     [stats IN], [ends], [quality trim], [poly-G], [adapter], [poly-X]), [select:
+//     [stats IN], [UMI take], [ends], [quality trim], [poly-G], [adapter], [poly-X]), [select:
 //     by length, or -- content rules -- by length and content (ffq_table_select_reads), on the rows as the trims left them],
 //     [dedup: the kept rows entered into the stream's set by their keys and the select's ordinals, the first copies kept
 //     (ffq_dedup_select) -- what follows is on the rows that remain], back, [idx D2H], [gather, col D2H, coff D2H],
@@ -1123,6 +1169,10 @@ static int chain_back(ffq_stream *s, const Fill &f, const Table &t)
 // ordinals], mate 1: back, mate 2: back, ordinals D2H, [merged text D2H], synchronise
 // No rows are copied back from an empty table; a fill without records allocates and launches nothing of the push-down,
 // but statistics OUT and the render are still called (n = 0).  *n_out: the rows handed out.
+// The UMI take stands behind the keys and the statistics IN and in front of every trim: keys and "before" statistics see the read
+// as read -- two reads with the same sequence and different UMIs are no duplicates --, every trim, the overlap, the correction and
+// the "after" statistics see it without its UMI.  A pair's names check compares the headers as read; both mates' renders put the
+// same insert into their names.
 static int stream_chain(ffq_stream *s, const Fill &f, const ffq_scan_result &res, int64_t *n_out)
 {
     ffq_ctx *c = s->c;
@@ -1379,6 +1429,7 @@ extern "C" int ffq_pair_set_merge(ffq_pair *p, int on)
     if (!p) return fail(FFQ_E_ARG, "ffq_pair_set_merge: NULL pair");
     if (p->started) return fail(FFQ_E_ARG, "ffq_pair_set_merge: the walk has begun (call it before the first ffq_pair_next)");
     if (on && !p->overlap.on) return fail(FFQ_E_ARG, "ffq_pair_set_merge: the pair does not analyse overlaps (ffq_pair_set_overlap first)");
+    if (on && p->m[0].s->umi.on) return fail(FFQ_E_ARG, "ffq_pair_set_merge: the pair puts UMIs into the names (ffq_pair_set_umi); a merged read's header is not tagged");
     p->merge.on = on != 0;
     return FFQ_OK;
 }
@@ -1468,6 +1519,36 @@ extern "C" int ffq_pair_dedup_counts(ffq_pair *p, int64_t counts[FFQ_DEDUP_COUNT
     return FFQ_OK;
 }
 
+// UMIs of a pair (include/ffq.h): the take runs in the front of the mate or mates the location names, and BOTH mates' renders
+// put the same insert into their names, each from the kept rows of the mate that carries the tag.  Not with merging: the merged
+// read's header is written by ffq_merge.h.
+extern "C" int ffq_pair_set_umi(ffq_pair *p, const ffq_umi_rules *rules)
+{
+    if (!p) return fail(FFQ_E_ARG, "ffq_pair_set_umi: NULL pair");
+    if (p->started) return fail(FFQ_E_ARG, "ffq_pair_set_umi: the walk has begun (call it before the first ffq_pair_next)");
+    int rc = umi_arg("ffq_pair_set_umi", rules, nullptr);
+    if (!rc && p->merge.on) rc = fail(FFQ_E_ARG, "ffq_pair_set_umi: the pair merges (ffq_pair_set_merge); a merged read's header is not tagged");
+    for (int k = 0; k < 2 && !rc; k++) rc = stream_settable(p->m[k].s, "ffq_pair_set_umi", DECODE_UNTRIMMED, true);
+    if (rc) return rc;
+    for (int k = 0; k < 2; k++) {
+        ffq_stream *s = p->m[k].s;
+        s->umi.on = true;
+        s->umi.take = rules->loc == FFQ_UMI_PER_READ || rules->loc == (k == 0 ? FFQ_UMI_READ1 : FFQ_UMI_READ2);
+        s->umi.rules = *rules;
+    }
+    return FFQ_OK;
+}
+
+// ffq_stream_umi_counts of both mates for the round ffq_pair_next has just returned (a mate the location does not name takes nothing)
+extern "C" int ffq_pair_umi_counts(ffq_pair *p, int64_t counts1[4], int64_t counts2[4])
+{
+    if (!p || !counts1 || !counts2) return fail(FFQ_E_ARG, "ffq_pair_umi_counts: NULL argument");
+    if (!p->m[0].s->umi.on) return fail(FFQ_E_ARG, "ffq_pair_umi_counts: the pair takes no UMIs (ffq_pair_set_umi)");
+    int rc = ffq_stream_umi_counts(p->m[0].s, counts1);
+    if (!rc) rc = ffq_stream_umi_counts(p->m[1].s, counts2);
+    return rc;
+}
+
 extern "C" int ffq_pair_wants(ffq_pair *p) { return p && !p->failed ? walk_wants(p->w) : 0; }
 
 // what the per-stream accessors report for a round: zero until the round's chain says otherwise
@@ -1475,6 +1556,8 @@ static void pair_clear_last(ffq_stream *s)
 {
     for (int i = 0; i < 3; i++) s->ends.last[i] = s->trim.last[i] = s->adapter.last[i] = s->poly.last_g[i] = s->poly.last_x[i] = s->render.last[i] = 0;
     for (int64_t &x : s->compress.last) x = 0;
+    for (int i = 0; i < 3; i++) s->umi.last[i] = 0;
+    s->umi.tagged = 0;
     for (int i = 0; i < FFQ_FILTER_COUNTS; i++) s->content.last[i] = 0;
     s->filter.scanned = 0; s->filter.col_bytes = 0;
 }
@@ -1586,7 +1669,13 @@ static int pair_chain(ffq_pair *p, int64_t m, int64_t *n_out, int64_t *differ)
         rc = chain_dedup(c, "ffq_pair", p->dedup, keys, rows, &d_ord, &kept);
     }
     if (!rc && p->merge.on) return pair_chain_merge(p, rows, d_ord, kept, n_out);
-    for (int k = 0; k < 2 && !rc; k++) rc = chain_back(p->m[k].s, p->m[k].f, Table{rows[k], kept});
+    if (p->m[0].s->umi.on) {
+        // (a pair with UMIs: either mate's render is handed both mates' kept rows, which are in step)
+        ffq_table_view uv[2];
+        for (int k = 0; k < 2; k++) uv[k] = ffq_table_view{p->m[k].f.d_buf, p->m[k].f.n, 0, p->m[k].f.add, rows[k]};
+        for (int k = 0; k < 2 && !rc; k++) rc = chain_back(p->m[k].s, p->m[k].f, Table{rows[k], kept}, uv);
+    } else
+        for (int k = 0; k < 2 && !rc; k++) rc = chain_back(p->m[k].s, p->m[k].f, Table{rows[k], kept});
     if (rc) return rc;
     if (kept > 0) HIPCHK(hipMemcpyAsync(p->idx.h, d_ord, (size_t)kept * 8, hipMemcpyDeviceToHost, c->stream));
     *n_out = kept;

@@ -739,6 +739,101 @@ extern "C" int ffq_table_render_fastq(ffq_ctx *c, const uint8_t *d_buf, int64_t 
     return FFQ_OK;
 }
 
+// ---- UMIs: off the reads, into the names (csrc/ffq_umi.h, built as csrc/ffq_umi.hip and launched through ffq_umi_launch.h) ----
+typedef ffq_umi::Arg UmiArg;
+typedef ffq_umi::RenderCounts UmiRenderBlock;
+static_assert(ffq_umi::RENDER_WG == RENDER_WG, "ffq_umi_launch.h");
+static_assert(UMI_READ1 == FFQ_UMI_READ1 && UMI_READ2 == FFQ_UMI_READ2 && UMI_PER_READ == FFQ_UMI_PER_READ &&
+              UMI_PREFIX_MAX == sizeof(((ffq_umi_rules *)nullptr)->prefix), "include/ffq.h");
+
+static int umi_take_arg(const char *who, int len, int skip)
+{
+    if (len < 1 || len > UMI_LEN_MAX) return fail(FFQ_E_ARG, "%s: umi_len is 1..%d", who, UMI_LEN_MAX);
+    if (skip < 0 || skip > UMI_SKIP_MAX) return fail(FFQ_E_ARG, "%s: umi_skip is 0..%d", who, UMI_SKIP_MAX);
+    return FFQ_OK;
+}
+
+// the rules of a UMI call, checked, as the kernels take them (A may be NULL): for the table call and for the setters
+static int umi_arg(const char *who, const ffq_umi_rules *r, UmiArg *A)
+{
+    if (!r) return fail(FFQ_E_ARG, "%s: NULL rules", who);
+    if (r->loc != FFQ_UMI_READ1 && r->loc != FFQ_UMI_READ2 && r->loc != FFQ_UMI_PER_READ)
+        return fail(FFQ_E_ARG, "%s: loc is FFQ_UMI_READ1, FFQ_UMI_READ2 or FFQ_UMI_PER_READ", who);
+    if (int rc = umi_take_arg(who, r->len, r->skip)) return rc;
+    if (r->delim < 0x21 || r->delim > 0x7E) return fail(FFQ_E_ARG, "%s: delim is a printable byte, 0x21..0x7E", who);
+    if (r->prefix_len > UMI_PREFIX_MAX) return fail(FFQ_E_ARG, "%s: prefix_len is 0..%d", who, UMI_PREFIX_MAX);
+    for (int j = 0; j < r->prefix_len; j++)
+        if (const uint8_t b = r->prefix[j]; !((b >= '0' && b <= '9') || (b >= 'A' && b <= 'Z') || (b >= 'a' && b <= 'z'))) return fail(FFQ_E_ARG, "%s: the prefix is bytes of [A-Za-z0-9]", who);
+    if (A) {
+        memset(A, 0, sizeof *A);
+        A->loc = r->loc; A->len = r->len; A->prefix_len = r->prefix_len;
+        uint8_t lit[sizeof A->lit] = {0};
+        static_assert(sizeof lit >= UMI_LIT_MAX, "UmiArg::lit");
+        umi_literal(lit, r->delim, r->prefix, r->prefix_len);
+        for (size_t j = 0; j < sizeof lit; j++) A->lit[j >> 2] |= (uint32_t)lit[j] << (8 * (j & 3));
+    }
+    return FFQ_OK;
+}
+
+extern "C" int ffq_table_take_umi(ffq_ctx *c, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
+                                  const int64_t *d_table, int64_t n_rows, int umi_len, int umi_skip, int64_t *d_out, int64_t stats[3])
+{
+    static const char *const who = "ffq_table_take_umi";
+    return rows_edit(c, who, umi_take_arg(who, umi_len, umi_skip), d_buf, n_bytes, sentinel, d_table, n_rows, d_out, stats,
+                     [&](hipStream_t st, int s, RowsBlock *blk) {
+        ffq_umi::launch_take(st, rows_grid(n_rows, ffq_umi::TAKE_WG / ROWS_G, EDIT_GRID_SHORT), rows_grid(n_rows, ffq_umi::TAKE_WG / 64, EDIT_GRID_LONG),
+                             d_buf, n_bytes, s, add, d_table, n_rows, umi_len, umi_skip, d_out, c->rows_list, blk);
+    });
+}
+
+// Workgroups of the tagged render's capped launches (the rows' launch has a workgroup per block of 256 rows, uncapped)
+constexpr int UMI_GRID_SUM = 2048, UMI_GRID_LONG = 1024;
+
+extern "C" int ffq_table_render_fastq_umi(ffq_ctx *c, const ffq_table_view *rows, int64_t n_rows, const ffq_table_view *src1,
+                                          const ffq_table_view *src2, const ffq_umi_rules *rules, uint8_t *d_out, int64_t out_cap,
+                                          int64_t *d_off, int64_t stats[4])
+{
+    static const char *const who = "ffq_table_render_fastq_umi";
+    mark_other(c);
+    if (!c || !stats || n_rows < 0 || out_cap < 0 || !view_ok(rows, n_rows) || (out_cap > 0 && !d_out))
+        return fail(FFQ_E_ARG, "%s: bad argument", who);
+    UmiArg A;
+    if (int rc = umi_arg(who, rules, &A)) return rc;
+    const bool need1 = A.loc != UMI_READ2, need2 = A.loc != UMI_READ1;
+    if ((need1 && !view_ok(src1, n_rows)) || (need2 && !view_ok(src2, n_rows)))
+        return fail(FFQ_E_ARG, "%s: the location needs a source table that is not there", who);
+    if (!need1) src1 = rows;                                // (a side the location does not name is never looked at)
+    if (!need2) src2 = rows;
+    for (const ffq_table_view *m : {rows, src1, src2})
+        if (m->n_bytes > 0 && !m->d_buf) return fail(FFQ_E_ARG, "%s: no buffer to read the rows from", who);
+    if (!aligned({d_off}, 8)) return fail(FFQ_E_ARG, "%s: the tables must be 16-byte aligned, the offsets 8-byte", who);
+    if (int rc = no_pending(c, who)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    stats[0] = stats[1] = stats[2] = stats[3] = 0;
+    hipStream_t st = c->stream;
+    if (n_rows == 0) return no_rows_offsets(c, d_off);
+    const int64_t nblk = (n_rows + RENDER_WG - 1) / RENDER_WG;
+    int rc = grow_dev(c, c->col_sum, nblk);
+    if (!rc) rc = grow_dev(c, c->render_list, 2 * n_rows);
+    if (rc) return rc;
+    UmiRenderBlock *blk = nullptr;
+    if ((rc = call_blk_begin(c, &blk))) return rc;
+    const auto side = [](const ffq_table_view *m) { return ffq_umi::Side{m->d_buf, m->n_bytes, m->sentinel ? 1 : 0, m->add, m->d_table}; };
+    const ffq_umi::Side S0 = side(rows), S1 = side(src1), S2 = side(src2);
+    ffq_umi::launch_render_sum(st, (unsigned)std::min<int64_t>(nblk, UMI_GRID_SUM), S0, S1, S2, A, n_rows, nblk, c->col_sum, blk);
+    if ((rc = launch_scan(c, st, (const long long *)c->col_sum, nblk, c->col_sum, ScanToRes{c->col_res, n_rows}))) return rc;
+    ffq_umi::launch_render_rows(st, (unsigned)nblk, (unsigned)std::min<int64_t>((n_rows + 3) / 4, UMI_GRID_LONG), S0, S1, S2, A, n_rows,
+                                (const long long *)c->col_sum, (const DevRes *)c->col_res, d_out, out_cap, d_off, c->render_list, blk);
+    const UmiRenderBlock *h = nullptr;
+    if ((rc = call_blk_end(c, &h))) return rc;
+    stats[0] = (int64_t)h->total; stats[1] = (int64_t)h->rendered;
+    stats[2] = n_rows - stats[1];
+    stats[3] = (int64_t)h->tagged;
+    if (stats[0] > out_cap)
+        return fail(FFQ_E_TABLE_FULL, "output holds %lld bytes, the rendered rows have %lld", (long long)out_cap, (long long)stats[0]);
+    return FFQ_OK;
+}
+
 // ---- BGZF members from device bytes (csrc/ffq_deflate.h) --------------------------------------
 static_assert(DFL_BLOCK == FFQ_BGZF_BLOCK_BYTES && DFL_SEG == FFQ_DEFLATE_SEG_BYTES && DFL_ROUND == FFQ_DEFLATE_ROUND_POSITIONS &&
               DEFLATE_GRID == FFQ_DEFLATE_GRID_BLOCKS && DEFLATE_COUNTS == FFQ_DEFLATE_COUNTS, "include/ffq.h");

@@ -411,6 +411,116 @@ def _poly_pos(buf, pos, base, min_len):
     return pos, n - cut
 
 
+class UmiRules:
+    """Where a read's unique molecular identifier is and how it goes into the name (`fastp --umi --umi_loc --umi_len --umi_skip
+    --umi_prefix`; include/ffq.h states the rule, which follows fastp's documented behaviour and has not been checked against
+    its source).  loc: "read1", "read2" or "per_read" -- the mate whose first `length` (1..64) bases are the UMI, or both;
+    skip (0..64): bases dropped behind it; the name gets delim (one printable byte) + prefix + b"_" (prefix: 0..16 bytes of
+    [A-Za-z0-9], nothing of this if empty) + the UMI (per_read: both, with b"_" between) in front of its first blank.
+    ValueError names the setting that is out of range."""
+
+    def __init__(self, loc="read1", length=8, skip=0, prefix=b"", delim=b":"):
+        self.loc, self.length, self.skip, self.prefix, self.delim = loc, length, skip, prefix, delim
+        self._check()
+
+    def _check(self):
+        def whole(x, lo, hi):
+            return not isinstance(x, bool) and isinstance(x, (int, np.integer)) and lo <= int(x) <= hi
+        if self.loc not in _hip.UMI_LOCS:
+            raise ValueError('loc is "read1", "read2" or "per_read"')
+        if not whole(self.length, 1, _hip.UMI_LEN_MAX):
+            raise ValueError("length is 1..%d" % _hip.UMI_LEN_MAX)
+        if not whole(self.skip, 0, _hip.UMI_SKIP_MAX):
+            raise ValueError("skip is 0..%d" % _hip.UMI_SKIP_MAX)
+        if not isinstance(self.prefix, (bytes, bytearray)) or len(self.prefix) > _hip.UMI_PREFIX_MAX or \
+                not all(48 <= b <= 57 or 65 <= b <= 90 or 97 <= b <= 122 for b in self.prefix):
+            raise ValueError("prefix is 0..%d bytes of [A-Za-z0-9]" % _hip.UMI_PREFIX_MAX)
+        if not isinstance(self.delim, (bytes, bytearray)) or len(self.delim) != 1 or not 0x21 <= self.delim[0] <= 0x7E:
+            raise ValueError("delim is one printable byte (0x21..0x7E)")
+        self.length, self.skip, self.prefix, self.delim = int(self.length), int(self.skip), bytes(self.prefix), bytes(self.delim)
+
+    def takes(self, mate):
+        """does mate 1 or 2 lose bases?"""
+        return self.loc == "per_read" or self.loc == ("read1", "read2")[mate - 1]
+
+
+def umi_take(sequence, quality, rules):
+    """(the UMI or None, sequence, quality) of one ELIGIBLE read (umi_takable) with its UMI taken off: the host statement of
+    ffq_table_take_umi's rule.  A read shorter than rules.length keeps its bases and gives None; any other loses
+    min(length + skip, len) bases at its 5' end, and may go to length 0."""
+    n = len(sequence)
+    if n < rules.length:
+        return None, sequence, quality
+    cut = min(rules.length + rules.skip, n)
+    return bytes(sequence[:rules.length]), sequence[cut:], quality[cut:]
+
+
+def umi_name(header, tags, rules):
+    """`header` (bytes, as entryfunc cuts it) with the insert in front of its first b" " or b"\t", at its end if it has none:
+    the host statement of ffq_table_render_fastq_umi's rule.  tags: the UMI, or the two of "per_read" (mate 1's first)."""
+    k = len(header)
+    for blank in (b" ", b"\t"):
+        at = header.find(blank, 0, k)
+        if at >= 0:
+            k = at
+    return b"".join((header[:k], rules.delim, rules.prefix + b"_" if rules.prefix else b"", b"_".join(tags), header[k:]))
+
+
+def umi_takable(buf, pos):
+    """Does the device take a UMI off this row (ffq_table_take_umi's eligibility)?  adapter_trimmable's rule, no newline in
+    the quality either, and the sequence begins right behind the header's newline (a scanned, unwrapped record)."""
+    return adapter_trimmable(buf, pos) and b'\n' not in buf[pos[4]:pos[5]] and pos[2] == pos[1] + 1
+
+
+def _umi_pos(buf, pos, rules):
+    """(the six positions -- a list, edited in place -- with the UMI taken, the UMI or None, was the row skipped)"""
+    if not umi_takable(buf, pos):
+        return pos, None, True
+    n = pos[3] - pos[2]
+    if n < rules.length:
+        return pos, None, False
+    tag = bytes(buf[pos[2]:pos[2] + rules.length])
+    cut = min(rules.length + rules.skip, n)
+    pos[2] += cut
+    pos[4] += cut
+    return pos, tag, False
+
+
+class UmiReport:
+    """What filter_fastq(umi=..., umi_report=...) and filter_fastq_paired fill, the same on either route: reads_tagged (records
+    WRITTEN with a UMI in their name, both outputs of a pair counted), bases_removed (UMI and skipped bases, over every record
+    read), reads_skipped (records the take does not apply to: wrapped records)."""
+
+    def __init__(self):
+        self.reads_tagged = self.bases_removed = self.reads_skipped = 0
+
+    def _add_counts(self, counts):
+        """(rows taken, bases removed, rows skipped, rows tagged in the output) (hip: umi_counts)"""
+        self.bases_removed += counts[1]
+        self.reads_skipped += counts[2]
+        self.reads_tagged += counts[3]
+
+
+def _check_umi(umi, umi_report, single, merging=False):
+    """filter_fastq's / filter_fastq_paired's umi and umi_report, checked before anything is opened or read; the report to fill"""
+    if umi is not None:
+        if not isinstance(umi, UmiRules):
+            raise TypeError("umi must be a UmiRules")
+        try:
+            umi._check()
+        except ValueError as e:
+            raise ValueError("umi: %s" % e) from None
+        if single and umi.loc != "read1":
+            raise ValueError('umi: a single file has read 1 only (loc is "read1")')
+        if merging:
+            raise ValueError("umi does not go with merged_out: a merged read's name is not tagged")
+    if umi_report is not None and umi is None:
+        raise ValueError("umi_report needs umi")
+    if umi_report is not None and not isinstance(umi_report, UmiReport):
+        raise TypeError("umi_report must be a UmiReport")
+    return _report(umi_report, UmiReport)
+
+
 class EndRules:
     """What ffq_table_trim_ends does to both ends of a read, in front of every other trim (include/ffq.h states the rule):
     trim_front / trim_tail bases go from the 5' / 3' end whatever they are (`fastp -f / -t`, `cutadapt -u`), keep_len (None: no
@@ -1252,8 +1362,9 @@ def _scanner(entrypos):
 
 
 def _configure_stream(st, trim, cutter, content, bounds, column=None, render=False, stats=None, dedup=None, poly_g=None, poly_x=None,
-                      ends=None):
-    """What a native stream is asked for, in the order its chain works (csrc/ffq_stream.h states it above stream_chain): the
+                      ends=None, umi=None):
+    """What a native stream is asked for, in the order its chain works (csrc/ffq_stream.h states it above stream_chain): the UMI
+    (umi: a UmiRules of a single file; taken in front of every trim, put into the names by the render), the
     ends (ends: (an EndRules, qual_base); fixed trims and sliding windows, in front of every other trim), the
     quality trim (an entryfunc_qualitytrim), the poly tails (poly_g / poly_x: a min_len each; one call for both steps, where
     the first of them works: poly-G runs in front of the adapter trim, poly-X behind it), the adapter trim (an
@@ -1263,6 +1374,8 @@ def _configure_stream(st, trim, cutter, content, bounds, column=None, render=Fal
     behind the filter).  None / False: that setter is not called.  A stage that is added to the chain is added HERE."""
     if dedup is not None:
         st.set_dedup(not dedup.count_only, dedup.expected_reads, dedup.max_bytes)
+    if umi is not None:
+        st.set_umi(umi)
     if ends is not None:
         st.set_ends(ends[0], ends[1])
     if trim is not None:
@@ -1375,8 +1488,12 @@ class _MatePlan:
     reset and bound to it.  compress ("bgzf" or None): the text is written as BGZF -- sink() wraps an output file for it,
     and everything that is written goes through what sink() returned."""
 
-    def __init__(self, shared, adapter, min_len, max_len, report, judged=True, dedup=None, ends=None):
+    def __init__(self, shared, adapter, min_len, max_len, report, judged=True, dedup=None, ends=None, umi=None, umi_report=None, mate=0):
         quality_cutoff, qual_base = shared.quality_cutoff, shared.qual_base
+        # umi: the call's UmiRules (checked: _check_umi); mate 0: the one file of filter_fastq, 1 / 2: a pair's -- the PAIR sets the
+        # rule on the device then (_PairPlan.configure), and this mate loses bases only if the location names it
+        self.umi, self.umi_report, self.mate = umi, umi_report, mate
+        self.umi_takes = umi is not None and (mate == 0 or umi.takes(mate))
         self.qual_base, self.content, self.report, self.judged = qual_base, shared.content, report, judged
         self.ends, self.ends_report = _check_ends(ends), shared.ends_report
         if ends is not None:
@@ -1405,7 +1522,8 @@ class _MatePlan:
         rep = self.report
         _configure_stream(st, self.trim, self.cutter, self.content, None if self.lo is None and self.hi is None else (self.lo, self.hi),
                           render=True, stats=None if rep is None else (self.qual_base, rep.max_cycles), dedup=self.dedup,
-                          poly_g=self.poly_g, poly_x=self.poly_x, ends=None if self.ends is None else (self.ends, self.qual_base))
+                          poly_g=self.poly_g, poly_x=self.poly_x, ends=None if self.ends is None else (self.ends, self.qual_base),
+                          umi=self.umi if self.mate == 0 else None)
         if self.compress is not None:
             st.set_compress(self.compress)
 
@@ -1430,6 +1548,10 @@ class _MatePlan:
             for reason, k in zip(ContentRules.REASONS, st.filter_counts()[1:7]):
                 self.dropped[reason] += k
         removed = 0
+        if self.umi is not None:
+            u = st.umi_counts()
+            removed += u[1]
+            self.umi_report._add_counts(u)
         if self.ends is not None:
             e = st.ends_trimmed()
             removed += e[1]
@@ -1453,11 +1575,16 @@ class _MatePlan:
 
     # ---- the host route
     def trimmed_pos(self, buf, pos):
-        """(the positions as the trims leave them, bases cut) of a record as read, which is counted into `before`."""
+        """(the positions as the trims leave them, bases cut, the UMI taken off it or None) of a record as read, which is
+        counted into `before`.  The UMI goes on WITH the record: nothing behind this looks for it in the buffer again."""
         length = pos[3] - pos[2]
         if self.report is not None:
             self.report.before.add_pos(buf, pos)
         g = x = 0
+        tag = None
+        if self.umi_takes:                                   # (in front of every trim; `before` and the dedup key saw the read as read)
+            pos, tag, skipped = _umi_pos(buf, list(pos), self.umi)
+            self.umi_report._add_counts((int(tag is not None), length - (pos[3] - pos[2]), int(skipped), 0))
         if self.ends is not None:                            # (the chain's order: ends, quality, poly-G, adapter, poly-X)
             pos, e = _ends_pos(buf, list(pos), self.ends, self.qual_base)
             if e:
@@ -1472,7 +1599,7 @@ class _MatePlan:
             pos, x = _poly_pos(buf, list(pos), None, self.poly_x)
         if g or x:
             self.poly_report._add_counts(((int(g > 0), g), (int(x > 0), x)))
-        return pos, length - (pos[3] - pos[2])
+        return pos, length - (pos[3] - pos[2]), tag
 
     def verdict(self, buf, pos):
         """0, or the 1-based reason (counted into `dropped`) the record fails for, as the trims (and the overlap) left it:
@@ -1488,11 +1615,16 @@ class _MatePlan:
             self.dropped[ContentRules.REASONS[v - 1]] += 1
         return v
 
-    def text(self, buf, pos):
-        """a kept record as it is written, which is counted into `after`"""
+    def text(self, buf, pos, tags=None):
+        """a kept record as it is written, which is counted into `after`; tags: the UMI or UMIs that go into its name (None, or
+        one of them None: the name stays as it is)"""
         if self.report is not None:
             self.report.after.add_pos(buf, pos)
-        return b"".join((b"@", buf[(pos[0] + 1):pos[1]], b"\n", buf[pos[2]:pos[3]], b"\n+\n", buf[pos[4]:pos[5]], b"\n"))
+        header = buf[(pos[0] + 1):pos[1]]
+        if tags is not None and None not in tags:
+            header = umi_name(bytes(header), tags, self.umi)
+            self.umi_report.reads_tagged += 1
+        return b"".join((b"@", header, b"\n", buf[pos[2]:pos[3]], b"\n+\n", buf[pos[4]:pos[5]], b"\n"))
 
 
 def fastq_stats(fh: typing.BinaryIO, fbufsize: int = 1 << 24, qual_base: int = 33, max_cycles: int = 512,
@@ -1544,7 +1676,7 @@ def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1
                  qual_base: int = 33, min_len=None, max_len=None, entrypos: typing.Optional[typing.Callable] = None,
                  adapter=None, err_permille: int = 100, min_overlap: int = 3, report=None, content=None, dedup=None,
                  dedup_report=None, poly_g=None, poly_x=None, poly_report=None, compress=None,
-                 compress_report=None, ends=None, ends_report=None) -> FilterResult:
+                 compress_report=None, ends=None, ends_report=None, umi=None, umi_report=None) -> FilterResult:
     """Trim, filter and WRITE a FASTQ stream: the file `cutadapt -q 20 -m 30` leaves behind, which is what the tables of
     positions of the reference's user guide are kept for in the end ("to avoid saving a FASTQ file after each filtering or
     read-trimming step", doc/user-guide.rst:196-204).  Every record of `fh` is quality-trimmed (quality_cutoff: an int --
@@ -1605,13 +1737,24 @@ def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1
     GPU scanner every fill's text is deflated on the device behind the render (ffq_stream_set_compress) and only the members
     come back, one fh_out.write per fill; with any other scanner the text is buffered and written as zlib level 1 members:
     other bytes, the same text.  The EOF marker is written once at the end.  bytes_out stays the bytes of TEXT; compress_report
-    (a CompressReport) has the compressed size.  Not done: members aligned to records, a .gzi index, plain gzip."""
+    (a CompressReport) has the compressed size.  Not done: members aligned to records, a .gzi index, plain gzip.
+
+    umi: None, or a UmiRules with loc "read1" (`fastp --umi --umi_loc read1 --umi_len 8`): the first `length` bases of every
+    read are its unique molecular identifier; they (and `skip` bases behind them) are taken off the read IN FRONT of every
+    trim and put into the name of the record as it is written, in front of the name's first blank (umi_take, umi_name).
+    `before` and the dedup keys see the read as read -- two reads with the same sequence and different UMIs are no
+    duplicates --, every trim, the filters and `after` see it without its UMI.  A read shorter than the UMI keeps its bases and
+    its name; a wrapped record is left alone.  On the device with the GPU scanner (ffq_stream_set_umi).  bases_removed
+    includes the UMI and the skipped bases; umi_report (a UmiReport) has the numbers, the same on either route.  The rule
+    has not been checked against fastp's source.  Not done: UMIs in the index part of a header, push-down through
+    readfastq_iter / readfastq_iter_range."""
     if content is not None and not isinstance(content, ContentRules):
         raise TypeError("content must be a ContentRules")
     _check_dedup(dedup, dedup_report)
+    urep = _check_umi(umi, umi_report, single=True)
     shared = _MateSettings(quality_cutoff, qual_base, err_permille, min_overlap, content, poly_g, poly_x, poly_report, compress,
                            compress_report, ends, ends_report)
-    plan = _MatePlan(shared, adapter, min_len, max_len, report, dedup=dedup, ends=ends)
+    plan = _MatePlan(shared, adapter, min_len, max_len, report, dedup=dedup, ends=ends, umi=umi, umi_report=urep)
     fh_out = plan.sink(fh_out)
     hd = _HostDedup(dedup, _report(dedup_report, DedupReport)) if dedup is not None else None
     entrypos, open_stream = _scanner(entrypos)
@@ -1638,10 +1781,10 @@ def filter_fastq(fh: typing.BinaryIO, fh_out: typing.BinaryIO, fbufsize: int = 1
 
     def record(buf, pos, globaloffset=None):
         key = hd.key(buf, pos) if hd is not None else 0
-        pos, cut = plan.trimmed_pos(buf, pos)
+        pos, cut, tag = plan.trimmed_pos(buf, pos)
         if plan.verdict(buf, pos) or (hd is not None and not hd.keep(key)):
             return cut, None
-        return cut, plan.text(buf, pos)
+        return cut, plan.text(buf, pos, None if umi is None else (tag,))
 
     for cut, text in readfastq_iter(fh, fbufsize, record, entrypos):
         n_in += 1
@@ -1918,16 +2061,17 @@ def _raise_for_pair_end(end_state, err_mate, err_offset, names=None):
 class _HostRecord:
     """A record of the paired host route, kept until its mate is there: `at` (where it is in its file), `name` (its pair_id, or
     None), `cut` (bases the trims removed so far), `buf` and `pos` (its buffer and its six positions as the trims left them),
-    `key` (its seq_key as scanned, 0: none)."""
-    __slots__ = ("at", "name", "cut", "buf", "pos", "key")
+    `key` (its seq_key as scanned, 0: none), `tag` (the UMI taken off it, or None: it goes with the record, whatever becomes of
+    its buffer and positions)."""
+    __slots__ = ("at", "name", "cut", "buf", "pos", "key", "tag")
 
-    def __init__(self, at, name, cut, buf, pos, key):
-        self.at, self.name, self.cut, self.buf, self.pos, self.key = at, name, cut, buf, pos, key
+    def __init__(self, at, name, cut, buf, pos, key, tag=None):
+        self.at, self.name, self.cut, self.buf, self.pos, self.key, self.tag = at, name, cut, buf, pos, key, tag
 
     def cut_to(self, c):
         """the record with sequence and quality cut to their first `c` bytes"""
         p = self.pos
-        return _HostRecord(self.at, self.name, self.cut + p[3] - p[2] - c, self.buf, (p[0], p[1], p[2], p[2] + c, p[4], p[4] + c), self.key)
+        return _HostRecord(self.at, self.name, self.cut + p[3] - p[2] - c, self.buf, (p[0], p[1], p[2], p[2] + c, p[4], p[4] + c), self.key, self.tag)
 
     def patched(self, seq, qual):
         """the record in a buffer of its own -- itself cut out, with `seq` and `qual` in place of its two lines -- and its
@@ -1937,7 +2081,7 @@ class _HostRecord:
         own = bytearray(self.buf[lo:hi])
         own[p[2] - lo:p[3] - lo] = seq
         own[p[4] - lo:p[5] - lo] = qual
-        return _HostRecord(self.at, self.name, self.cut, bytes(own), tuple(x - lo for x in p), self.key)
+        return _HostRecord(self.at, self.name, self.cut, bytes(own), tuple(x - lo for x in p), self.key, self.tag)
 
 
 def _per_mate(x):
@@ -1981,7 +2125,8 @@ class _PairPlan:
     the hip.PairStream and drains every round of it; on the host route it is called pair by pair, with _HostRecords."""
 
     def __init__(self, pair_filter, check_names, overlap, overlap_report, correction, qual_base, correction_report, dedup, dedup_report,
-                 merging, merge_report, compress):
+                 merging, merge_report, compress, umi=None):
+        self.umi = umi               # (the pair's UmiRules: set on the device by the pair; tags() says what a pair's names get)
         self.pair_filter, self.check_names, self.overlap, self.correction, self.qual_base = pair_filter, check_names, overlap, correction, qual_base
         self.dedup, self.merging, self.compress = dedup, merging, compress
         self.overlap_report, self.correction_report, self.merge_report = overlap_report, correction_report, merge_report
@@ -1993,6 +2138,8 @@ class _PairPlan:
         """What the pair is asked for, in the order its round works: the overlap behind the mates' trims, the correction, the
         merge (with the compression of its text) and, between the filter and the merge, the duplicates.  None / False: that
         setter is not called.  A stage of the PAIR that is added is added HERE."""
+        if self.umi is not None:
+            ps.set_umi(self.umi)
         if self.overlap is not None:
             ps.set_overlap(self.overlap)
         if self.correction is not None:
@@ -2046,9 +2193,15 @@ class _PairPlan:
             at = pos[0] + (globaloffset or 0)
             name = pair_id(buf[(pos[0] + 1):pos[1]]) if self.check_names else None
             key = self.hd.key(buf, pos) if self.hd is not None else 0
-            pos, cut = plan.trimmed_pos(buf, pos)
-            return _HostRecord(at, name, cut, buf, tuple(pos[i] for i in range(6)), key)
+            pos, cut, tag = plan.trimmed_pos(buf, pos)
+            return _HostRecord(at, name, cut, buf, tuple(pos[i] for i in range(6)), key, tag)
         return record
+
+    def tags(self, r1, r2):
+        """what the names of BOTH mates of a pair get: the UMI the location names, both for "per_read" (None: no UMIs)"""
+        if self.umi is None:
+            return None
+        return (r1.tag, r2.tag) if self.umi.loc == "per_read" else (r1.tag,) if self.umi.loc == "read1" else (r2.tag,)
 
     def overlap_cut(self, r1, r2):
         """the two records with the overlap's cut applied and the pair's insert size (None: none), and the report filled"""
@@ -2111,7 +2264,7 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
                         overlap_report=None, merged_out: typing.Optional[typing.BinaryIO] = None,
                         merge_report=None, dedup=None, dedup_report=None, poly_g=None, poly_x=None,
                         poly_report=None, compress=None, compress_report=None, correction=None,
-                        correction_report=None, ends=None, ends_report=None) -> PairedFilterResult:
+                        correction_report=None, ends=None, ends_report=None, umi=None, umi_report=None) -> PairedFilterResult:
     """filter_fastq for paired-end files: the i-th records of `fh1` and `fh2` are mates, and a pair is written or dropped
     TOGETHER, so that `fh_out1` and `fh_out2` stay record for record in step (`cutadapt -q 20 -a ... -A ... -m 30:20
     --pair-filter=any -o out1 -p out2 in1 in2`).  Every record is trimmed as filter_fastq trims it -- quality_cutoff for both
@@ -2174,7 +2327,12 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
     Not done: interleaved input or output.
     compress / compress_report: filter_fastq's, over `fh_out1`, `fh_out2` and `merged_out`: each is written as a BGZF file of
     its own, each mate's text deflated by its stream and the merged text by the pair (ffq_pair_set_compress); the report sums
-    over the three."""
+    over the three.
+    umi / umi_report: filter_fastq's, with loc "read1", "read2" or "per_read": the mate or mates it names lose their UMI in
+    front of every other step -- the names check still compares the headers as read --, and BOTH mates' names get the same
+    insert (per_read: mate 1's UMI, b"_", mate 2's; a pair one of whose named mates is too short for a UMI gets none).  Not
+    with merged_out (ValueError): a merged read's name is not tagged.  umi_report: both mates added together."""
+    urep = _check_umi(umi, umi_report, single=False, merging=merged_out is not None)
     if content is not None and not isinstance(content, ContentRules):
         raise TypeError("content must be a ContentRules")
     if pair_filter not in _PAIR_FILTERS:
@@ -2199,10 +2357,10 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
     los, his, ends_pair = _per_mate(min_len), _per_mate(max_len), _ends_per_mate(ends)
     shared = _MateSettings(quality_cutoff, qual_base, err_permille, min_overlap, content, poly_g, poly_x, poly_report, compress,
                            compress_report, ends_pair[0] or ends_pair[1], ends_report)
-    plans = tuple(_MatePlan(shared, a, lo, hi, rep, judged, ends=e) for a, lo, hi, rep, judged, e
-                  in zip((adapter, adapter2), los, his, (report, report2), (True, pair_filter != "first"), ends_pair))
+    plans = tuple(_MatePlan(shared, a, lo, hi, rep, judged, ends=e, umi=umi, umi_report=urep, mate=k) for a, lo, hi, rep, judged, e, k
+                  in zip((adapter, adapter2), los, his, (report, report2), (True, pair_filter != "first"), ends_pair, (1, 2)))
     pair = _PairPlan(pair_filter, check_names, overlap, orep, correction, qual_base, crep, dedup, drep, merged_out is not None, mrep,
-                     compress)
+                     compress, umi)
     entrypos, open_stream = _scanner(entrypos)
     pairs_in = pairs_out = removed = 0
     n_bytes = [0, 0]
@@ -2270,8 +2428,9 @@ def filter_fastq_paired(fh1: typing.BinaryIO, fh2: typing.BinaryIO, fh_out1: typ
         if text is not None:
             outs[2].write(text)
             continue
+        tags = pair.tags(r1, r2)
         for k, r in enumerate((r1, r2)):
-            text = plans[k].text(r.buf, r.pos)
+            text = plans[k].text(r.buf, r.pos, tags)
             outs[k].write(text)
             n_bytes[k] += len(text)
     for out in outs:

@@ -50,7 +50,7 @@ def _add(add, sentinel):
     return (-1 if sentinel else 0) if add is None else add
 
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 OK = 0
 E_NODEVICE, E_HIP, E_ARG, E_NOMEM, E_TABLE_FULL, E_INTERNAL, E_TIMEOUT = -1, -2, -3, -4, -5, -6, -7
 STAGE_NONE, STAGE_HANDOFF, STAGE_SCAN, STAGE_GATHER = 0, 1, 2, 3      # FFQ_SHARD_STAGE_*
@@ -111,6 +111,8 @@ SYMBOLS = (
     "ffq_table_trim_ends", "ffq_stream_set_ends", "ffq_stream_ends_trimmed",
     "ffq_deflate_bgzf_bound", "ffq_deflate_bgzf", "ffq_bgzf_eof_block",
     "ffq_stream_set_compress", "ffq_stream_compressed", "ffq_pair_set_compress", "ffq_pair_merged_bgzf",
+    "ffq_table_take_umi", "ffq_table_render_fastq_umi", "ffq_stream_set_umi", "ffq_stream_umi_counts", "ffq_pair_set_umi",
+    "ffq_pair_umi_counts",
 )
 
 
@@ -168,6 +170,31 @@ def ends_rules_struct(rules, qual_base=33):
 
 PAIR_FILTERS = {"any": 0, "both": 1, "first": 2}       # FFQ_PAIR_ANY / _BOTH / _FIRST
 PAIR_COUNTS = 5              # pairs kept, dropped, only mate 1 failed, only mate 2 failed, both failed
+
+
+UMI_READ1, UMI_READ2, UMI_PER_READ = 1, 2, 3          # FFQ_UMI_*: where the UMI is
+UMI_LOCS = {"read1": UMI_READ1, "read2": UMI_READ2, "per_read": UMI_PER_READ}
+UMI_LEN_MAX, UMI_SKIP_MAX, UMI_PREFIX_MAX = 64, 64, 16
+
+
+class UmiRulesStruct(ctypes.Structure):
+    """struct ffq_umi_rules (include/ffq.h)."""
+    _fields_ = [("loc", ctypes.c_int32), ("len", ctypes.c_int32), ("skip", ctypes.c_int32), ("delim", ctypes.c_uint8),
+                ("prefix_len", ctypes.c_uint8), ("prefix", ctypes.c_uint8 * 16)]
+
+
+def umi_rules_struct(rules):
+    """A UmiRulesStruct of a fastqandfurious.UmiRules (anything with loc, length, skip, prefix and delim; loc a name of
+    UMI_LOCS or the C ABI's own number), or the struct itself.  Nothing is checked here: the library answers E_ARG."""
+    if rules is None or isinstance(rules, UmiRulesStruct):
+        return rules
+    prefix, delim = bytes(rules.prefix), bytes(rules.delim)
+    loc = UMI_LOCS.get(rules.loc, rules.loc if isinstance(rules.loc, int) else 0)
+    r = UmiRulesStruct(int(loc), int(rules.length), int(rules.skip), delim[0] if len(delim) == 1 else 0,
+                       min(len(prefix), 255))
+    for j, b in enumerate(prefix[:16]):
+        r.prefix[j] = b
+    return r
 
 
 class TableView(ctypes.Structure):
@@ -496,6 +523,8 @@ def lib():
         L.ffq_stream_set_content.argtypes = [vp, P(ContentRulesStruct)]
         L.ffq_stream_filter_counts.argtypes = [vp, P(i64)]
         L.ffq_table_render_fastq.argtypes = [vp, vp, i64, i32, i64, vp, i64, vp, i64, vp, P(i64)]
+        L.ffq_table_take_umi.argtypes = [vp, vp, i64, i32, i64, vp, i64, i32, i32, vp, P(i64)]
+        L.ffq_table_render_fastq_umi.argtypes = [vp, P(TableView), i64, P(TableView), P(TableView), P(UmiRulesStruct), vp, i64, vp, P(i64)]
         L.ffq_deflate_bgzf_bound.argtypes = [i64]
         L.ffq_deflate_bgzf_bound.restype = i64
         L.ffq_deflate_bgzf.argtypes = [vp, vp, i64, vp, i64, vp, P(i64)]
@@ -561,6 +590,10 @@ def lib():
         L.ffq_stream_set_ends.argtypes = [vp, P(EndsRulesStruct)]
         L.ffq_stream_ends_trimmed.argtypes = [vp, P(i64)]
         L.ffq_stream_poly_trimmed.argtypes = [vp, P(i64), P(i64)]
+        L.ffq_stream_set_umi.argtypes = [vp, P(UmiRulesStruct)]
+        L.ffq_stream_umi_counts.argtypes = [vp, P(i64)]
+        L.ffq_pair_set_umi.argtypes = [vp, P(UmiRulesStruct)]
+        L.ffq_pair_umi_counts.argtypes = [vp, P(i64), P(i64)]
         L.ffq_stream_set_stats.argtypes = [vp, i32, i32, i32]
         L.ffq_stream_stats.argtypes = [vp, i32, vp, i64]
         L.ffq_stream_set_render.argtypes = [vp]
@@ -1043,6 +1076,36 @@ class Context:
         check(rc, allow=(E_TABLE_FULL,))
         return rc, (int(stats[0]), int(stats[1]), int(stats[2]))
 
+    def table_take_umi(self, d_buf, n_bytes, d_table, n_rows, umi_len, umi_skip=0, d_out=None, sentinel=True, add=None):
+        """Take the UMI off the rows of a device table (ffq_table_take_umi; include/ffq.h states the rule): pos2 and pos4 of
+        every eligible row of at least umi_len bases move inwards by min(umi_len + umi_skip, length), every other row is copied
+        unchanged.  pos1 stays, so the tag is found again at buf[pos1 + 1:pos1 + 1 + umi_len] (table_render_fastq_umi).  d_out:
+        n_rows rows of room (None: in place); raw device pointers; d_buf / n_bytes / sentinel / add as for
+        table_gather_column.  Returns (rows changed, bases removed, rows skipped)."""
+        add = _add(add, sentinel)
+        stats = (ctypes.c_int64 * 3)()
+        check(lib().ffq_table_take_umi(self.handle, ctypes.c_void_p(d_buf), int(n_bytes), int(bool(sentinel)), int(add),
+                                       ctypes.c_void_p(d_table), int(n_rows), int(umi_len), int(umi_skip),
+                                       ctypes.c_void_p(d_table if d_out is None else d_out), stats))
+        return int(stats[0]), int(stats[1]), int(stats[2])
+
+    def table_render_fastq_umi(self, rows, n_rows, rules, d_out, out_cap, d_off=None, src1=None, src2=None):
+        """FASTQ text of the rows of a device table with the UMI in the names (ffq_table_render_fastq_umi; include/ffq.h
+        states the rule).  rows: a TableView (table_view()); src1 / src2: the TableViews whose row i may carry the tag of read 1
+        / read 2 -- `rows` itself, or a table over another buffer; rules: a fastqandfurious.UmiRules or a UmiRulesStruct.  A
+        row whose sources do not all carry a tag renders as table_render_fastq renders it.  Returns (rc, (bytes rendered, rows
+        rendered, rows skipped, rows tagged)); rc is OK or E_TABLE_FULL (out_cap too small: stats[0] is the need, d_out is
+        not touched)."""
+        r = umi_rules_struct(rules)
+        stats = (ctypes.c_int64 * 4)()
+        rc = lib().ffq_table_render_fastq_umi(self.handle, ctypes.byref(rows), int(n_rows),
+                                              ctypes.byref(src1) if src1 is not None else None,
+                                              ctypes.byref(src2) if src2 is not None else None,
+                                              ctypes.byref(r) if r is not None else None, ctypes.c_void_p(d_out) if d_out else None,
+                                              int(out_cap), ctypes.c_void_p(d_off) if d_off else None, stats)
+        check(rc, allow=(E_TABLE_FULL,))
+        return rc, tuple(int(x) for x in stats)
+
     def deflate_bgzf(self, d_src, n_bytes, d_out, out_cap, d_member_off=None):
         """n_bytes of device memory written as BGZF members, deflated on the device (ffq_deflate_bgzf; include/ffq.h has the
         container, the bound and the match rule): a member per BGZF_BLOCK_BYTES, back to back in d_out, the same bytes for
@@ -1472,6 +1535,17 @@ class _Stream:
         x = (ctypes.c_int64 * 3)()
         return tuple(_counts(lib().ffq_stream_poly_trimmed, self._h, 3, x)), tuple(int(v) for v in x)
 
+    def set_umi(self, rules):
+        """UMIs in the stream (ffq_stream_set_umi; before the first fill): every fill's rows lose their UMI on the device in
+        front of every trim, and a stream that renders puts it into the names.  rules: a fastqandfurious.UmiRules with loc
+        "read1", or a UmiRulesStruct."""
+        r = umi_rules_struct(rules)
+        check(lib().ffq_stream_set_umi(self._h, ctypes.byref(r) if r is not None else None))
+
+    def umi_counts(self):
+        """(rows taken, bases removed, rows skipped, rows tagged in the output) of the fill the iteration has just yielded."""
+        return tuple(_counts(lib().ffq_stream_umi_counts, self._h, 4))
+
     def set_stats(self, which, qual_base=33, max_cycles=512):
         """Statistics in the stream (ffq_stream_set_stats; before the first fill): which = STATS_IN (the rows as scanned),
         STATS_OUT (the rows as handed out, behind trim, adapter and filter) or both; counted on the device over all fills,
@@ -1716,6 +1790,19 @@ class PairStream:
         of every round so far as uint64[OVERLAP_HIST_WORDS] (None without `hist`: no host wait)."""
         h = np.zeros(OVERLAP_HIST_WORDS, dtype=np.uint64) if hist else None
         return _counts(lib().ffq_pair_overlap, self._h, OVERLAP_COUNTS, ctypes.c_void_p(h.ctypes.data) if hist else None, OVERLAP_HIST_WORDS), h
+
+    def set_umi(self, rules):
+        """UMIs of the pair (ffq_pair_set_umi; before the first step, not with set_merge): the mate or mates rules.loc names
+        lose their UMI in front of every trim, and both mates' rendered() names get the same insert.  rules: a
+        fastqandfurious.UmiRules or a UmiRulesStruct."""
+        r = umi_rules_struct(rules)
+        check(lib().ffq_pair_set_umi(self._h, ctypes.byref(r) if r is not None else None))
+
+    def umi_counts(self):
+        """((rows taken, bases removed, rows skipped, rows tagged in the output) of mate 1, the same of mate 2) for the round
+        just yielded."""
+        x = (ctypes.c_int64 * 4)()
+        return tuple(_counts(lib().ffq_pair_umi_counts, self._h, 4, x)), tuple(int(v) for v in x)
 
     def set_merge(self, on=True):
         """Behind the filter every round merges the kept pairs whose insert size allows it (ffq_pair_set_merge; needs

@@ -229,6 +229,24 @@ def poly_rows(buf, table, base=None, min_len=10, shift=0):
     return t
 
 
+def umi_rows(buf, table, rules, shift=0):
+    """Copy of a table with the UMIs taken off, on the host: pos2 and pos4 of every row the rule applies to (_F.umi_takable:
+    positions minus `shift` index `buf`) and that is at least rules.length long moved inwards by min(length + skip, the
+    read's length) (rules: an _F.UmiRules; its loc does not matter here); the same rows, none dropped.  pos1 stays: the UMI
+    is buf[pos1 + 1:pos1 + 1 + length].  It runs in front of ends_rows and every other trim.  On the GPU:
+    hip.Context.table_take_umi."""
+    t = np.array(table, dtype=np.int64).reshape(-1, 6)
+    buf = bytes(buf) if not isinstance(buf, bytes) else buf
+    rules._check()
+    for row in t:
+        rel = (row - shift).tolist()
+        if _F.umi_takable(buf, rel) and rel[3] - rel[2] >= rules.length:
+            cut = min(rules.length + rules.skip, rel[3] - rel[2])
+            row[2] += cut
+            row[4] += cut
+    return t
+
+
 def ends_rows(buf, table, rules, qual_base=33, shift=0):
     """Copy of a table with the fixed trims and sliding windows of `rules` (an _F.EndRules) applied, on the host: pos2..pos5 of
     every row the rule applies to (_F.ends_trimmable: positions minus `shift` index `buf`) moved to where _F.ends_cut says;

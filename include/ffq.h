@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FFQ_ABI_VERSION 11
+#define FFQ_ABI_VERSION 12
 
 /* scanner status codes -- identical to the reference's module constants
  * (_fastqandfurious.c:7-15,254-262; fastqandfurious.py:19-27)             */
@@ -618,6 +618,62 @@ int ffq_table_render_fastq(ffq_ctx *ctx, const uint8_t *d_buf, int64_t n_bytes, 
                            const int64_t *d_table, int64_t n_rows, uint8_t *d_out, int64_t out_cap, int64_t *d_off,
                            int64_t stats[3]);
 
+/* Unique molecular identifiers (UMIs): the first bases of a read that tag the molecule and are no part of the fragment.  They
+ * are taken off the read before anything else looks at it and kept in the read's NAME, where aligners and umi_tools-style
+ * deduplicators look for them: what `fastp --umi --umi_loc read1|read2|per_read --umi_len N [--umi_skip M] [--umi_prefix P]`
+ * is for.  The rule below follows fastp's DOCUMENTED behaviour from memory: fastp's source was not at hand, the rule has NOT
+ * been checked against it, and no parity is claimed.
+ *
+ * THE TAKE, ffq_table_take_umi, MODIFIES rows.  For one row, n = pos3 - pos2; len in 1..64, skip in 0..64:
+ *     eligible = pos2..pos5 - add all >= 0, in order, inside the buffer, pos3 - pos2 == pos5 - pos4 (with sentinel, coordinate
+ *                0 is the virtual "\n": a line with bytes in it may not begin there), no byte of the sequence and no byte of
+ *                the quality is "\n", and pos2 == pos1 + 1 (a scanned, unwrapped record: the sequence begins behind the
+ *                header's newline)
+ *     if not eligible:   the row is copied unchanged and counted as skipped
+ *     else if n < len:   the row is unchanged (and not skipped): a read shorter than its tag keeps its bases
+ *     else:              cut = min(len + skip, n);  the row becomes pos0, pos1, pos2 + cut, pos3, pos4 + cut, pos5
+ * A read may go to length 0.  pos0 and pos1 never move -- no pass moves them -- so the tag of a row the take changed still
+ * lies at buf[pos1 + 1 : pos1 + 1 + len] when the row is rendered, whatever selects, dedups and pair compactions it went
+ * through: the take needs no side table.  stats = {rows changed, bases removed, rows skipped}; d_out MAY be d_table; the other
+ * arguments, FFQ_E_ARG and the one host wait are ffq_table_trim_poly's.  No byte outside the row's two checked lines is read.
+ *
+ * A CARRIER.  A source row carries a tag under len if pos1 - add >= 0 and pos2 - add >= 0, pos1 + 1 + len <= pos2,
+ * [pos1 + 1, pos1 + 1 + len) lies inside its buffer (it begins behind coordinate 0) and none of those bytes is "\n"; the tag is
+ * those bytes.  Behind the take a scanned record carries a tag exactly if the take changed it (DESIGN.md 4w says why no later
+ * pass makes a carrier of a row the take left alone).
+ *
+ * THE INSERT, ffq_table_render_fastq_umi, renders `rows` as ffq_table_render_fastq does, with the tag in the name.  src1 is
+ * the table whose row i may carry the tag of read 1 (needed for FFQ_UMI_READ1 and _PER_READ), src2 the same for read 2 (_READ2
+ * and _PER_READ); either may be `rows` itself or a table over another buffer with another add and sentinel; the rows are in
+ * step.  For row i, with h = buf[pos0 + 1 : pos1] of `rows`:
+ *     k    = index of the first ' ' or '\t' in h, len(h) if there is none
+ *     tag  = tag1 | tag2 | tag1 + "_" + tag2                          (by loc)
+ *     ins  = delim + (prefix + "_" if prefix_len else "") + tag
+ *     if row i is renderable and every source row the location names is a carrier:
+ *         "@" + h[:k] + ins + h[k:] + "\n" + seq + "\n+\n" + qual + "\n"
+ *     else: exactly what ffq_table_render_fastq renders (nothing, for a row that is not renderable)
+ * stats = {bytes rendered, rows rendered, rows skipped, rows tagged}.  Renderability, d_off, FFQ_E_TABLE_FULL (stats[0] holds
+ * the need, d_off is written, d_out is not touched), "any order, repeated, overlapping" and "no byte outside the buffers is
+ * read" are ffq_table_render_fastq's.  FFQ_E_ARG: loc, len, skip, delim (0x21..0x7E), prefix_len (0..16) or a prefix byte
+ * (A-Z a-z 0-9) out of range, a source the location needs missing, misaligned tables, a scan pending.  One host wait.
+ * Not done: UMIs in the index part of a header (index1 / index2), UMI with merged pairs, separate lengths per mate.      */
+#define FFQ_UMI_READ1 1
+#define FFQ_UMI_READ2 2
+#define FFQ_UMI_PER_READ 3
+typedef struct ffq_umi_rules {
+    int32_t loc;            /* FFQ_UMI_READ1 | _READ2 | _PER_READ */
+    int32_t len;            /* 1..64: bases of the UMI */
+    int32_t skip;           /* 0..64: bases dropped behind it */
+    uint8_t delim;          /* 0x21..0x7E, default ':' */
+    uint8_t prefix_len;     /* 0..16 */
+    uint8_t prefix[16];     /* bytes of [A-Za-z0-9] */
+} ffq_umi_rules;
+int ffq_table_take_umi(ffq_ctx *ctx, const uint8_t *d_buf, int64_t n_bytes, int sentinel, int64_t add,
+                       const int64_t *d_table, int64_t n_rows, int umi_len, int umi_skip, int64_t *d_out, int64_t stats[3]);
+int ffq_table_render_fastq_umi(ffq_ctx *ctx, const ffq_table_view *rows, int64_t n_rows, const ffq_table_view *src1,
+                               const ffq_table_view *src2, const ffq_umi_rules *rules, uint8_t *d_out, int64_t out_cap,
+                               int64_t *d_off, int64_t stats[4]);
+
 /* Device bytes written as BGZF (SAM specification 4.1: what bgzip writes, gzip members that say how long they are), deflated
  * on the device: what a pipeline that ends in .fq.gz does with the text ffq_table_render_fastq leaves there.
  * CONTAINER.  d_src[0, n_bytes) is cut into blocks of FFQ_BGZF_BLOCK_BYTES = 65280 bytes, the last one shorter.  Block k
@@ -900,6 +956,16 @@ int  ffq_stream_adapter_trimmed(ffq_stream *s, int64_t stats[3]);
  * of either step for the fill ffq_stream_next has just returned (zeros for a step that is off).                        */
 int  ffq_stream_set_poly(ffq_stream *s, int poly_g_min_len, int poly_x_min_len);
 int  ffq_stream_poly_trimmed(ffq_stream *s, int64_t stats_g[3], int64_t stats_x[3]);
+/* UMIs in the stream (the rules of ffq_stream_set_trim: before the first ffq_stream_next, not with FFQ_F_DECODE_QUAL): every
+ * fill's table goes through ffq_table_take_umi in place on the device BEHIND the dedup keys and the statistics IN -- they see
+ * the read as read, so two reads with the same sequence and different UMIs are no duplicates -- and IN FRONT of the ends and
+ * every other trim, which see the read without its UMI, as the statistics OUT do; a stream that renders puts the tag into the
+ * names (ffq_table_render_fastq_umi, the rendered rows their own source), also behind ffq_stream_set_compress.  On a single
+ * stream only FFQ_UMI_READ1 is valid (FFQ_E_ARG); a pair: ffq_pair_set_umi.  ffq_stream_umi_counts: {rows taken, bases
+ * removed, rows skipped, rows tagged in the output} for the fill ffq_stream_next has just returned.  Not done: push-down
+ * through the iterators (the rows handed out have their UMI taken, the entries built from them do not name it).          */
+int  ffq_stream_set_umi(ffq_stream *s, const ffq_umi_rules *rules);
+int  ffq_stream_umi_counts(ffq_stream *s, int64_t counts[4]);
 /* Fixed trims and sliding-window cutting in the stream (the rules of ffq_stream_set_trim: before the first
  * ffq_stream_next, not with FFQ_F_DECODE_QUAL): every fill's table goes through ffq_table_trim_ends in place on the device
  * BEHIND the statistics IN and IN FRONT of the quality trim and every other trim -- fastp's order --, per mate and in front
@@ -1094,6 +1160,13 @@ int  ffq_pair_set_compress(ffq_pair *p, int mode);
 int  ffq_pair_merged_bgzf(ffq_pair *p, const uint8_t **h_bgzf, int64_t *n_bytes, int64_t stats[FFQ_DEFLATE_COUNTS]);
 int  ffq_pair_set_dedup(ffq_pair *p, int drop, int64_t expected_keys, int64_t max_bytes);
 int  ffq_pair_dedup_counts(ffq_pair *p, int64_t counts[FFQ_DEDUP_COUNTS]);
+/* UMIs of a pair (before the first ffq_pair_next): the names check still compares the headers as read; the take runs in the
+ * front of the mate or mates rules->loc names; BOTH mates' renders put the same insert into their names, each tag read from
+ * the kept rows of the mate that carries it (a pair whose named mate -- with _PER_READ: either of them -- is too short for
+ * a tag gets none).  FFQ_E_ARG with merging switched on, and ffq_pair_set_merge behind it: the merged read's header is not
+ * tagged.  ffq_pair_umi_counts: ffq_stream_umi_counts of either mate for the round ffq_pair_next has just returned.      */
+int  ffq_pair_set_umi(ffq_pair *p, const ffq_umi_rules *rules);
+int  ffq_pair_umi_counts(ffq_pair *p, int64_t counts1[4], int64_t counts2[4]);
 int  ffq_pair_set_correct(ffq_pair *p, const ffq_correct_rules *rules);
 int  ffq_pair_corrected(ffq_pair *p, int64_t counts[FFQ_CORRECT_COUNTS], int64_t matrix[FFQ_CORRECT_MATRIX_WORDS]);
 void ffq_pair_close(ffq_pair *p);
